@@ -8,7 +8,7 @@ lib/ohnsw.ml:877-897) over the batch, queries already resident in HBM; with N > 
 holds a replica of the index, searches its own 10,000-query shard and the per-shard results are
 all-gathered over RCCL (weak scaling: per-GPU work fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `value` is measured the way the reference's benchmark times knn_batch (benchmark/benchmark.ml:89-96) and SURVEY 8d
@@ -125,6 +125,25 @@ def search_nslot(ef, nch=2):
 
 LINE_LIMIT = 4096          # bytes of the ONE stdout line (round 5's 25 KB line fell off the driver's record)
 DETAIL_FILE = "bench_detail.json"
+DUMP_LIMIT = 64 << 20      # bytes of --dump-outputs files at most
+
+
+def dump_outputs(dir_, ids, dist):
+    """--dump-outputs: the result matrices of the last timed step as DIR/ids.npy (float64: every int32 id exactly) and
+    DIR/distances.npy (float32).  A result too large for DUMP_LIMIT is cut to a sample of query rows drawn with a fixed
+    seed; their indices go to DIR/query_rows.npy, so the same arguments always give the same files."""
+    ids = np.asarray(ids, dtype=np.float64)
+    dist = np.asarray(dist, dtype=np.float32)
+    os.makedirs(dir_, exist_ok=True)
+    out = {"ids": ids, "distances": dist}
+    row_bytes = ids[:1].nbytes + dist[:1].nbytes + 8
+    room = DUMP_LIMIT - 4096     # 4 KiB for the .npy headers
+    if ids.shape[0] * row_bytes > room:
+        rows = np.sort(np.random.default_rng(0).choice(ids.shape[0], room // row_bytes, replace=False))
+        out = {"ids": ids[rows], "distances": dist[rows], "query_rows": rows.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(dir_, name + ".npy"), a)
+    log("--dump-outputs: %s (%s)" % (dir_, ", ".join("%s %s" % (n_, "x".join(map(str, a.shape))) for n_, a in out.items())))
 
 
 def _finite(o):
@@ -342,7 +361,12 @@ def main():
                     help="optional real data instead of the synthetic C2 set: an ann-benchmarks .hdf5 file, or a "
                          "directory holding *base.fvecs and *query.fvecs (TEXMEX); n and d come from the file")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL; the measured path) or gloo (functional rehearsal of N > 1 on fewer GPUs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps of `value`, write what their last step returned (ids, distances; N > 1: the "
+                         "all-gathered table) as DIR/<name>.npy, for comparing two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -624,6 +648,13 @@ def main():
     # the K timed steps of `value`, with the library's kernel events in them (roofline.kernel_ms is measured over THIS region;
     # three event records per call cost 0.003-0.015 ms of a 0.44 ms step), and once more without, for the record
     wall, host_stats, host_lib = timed_host(ef, args.steps, args.warmup, instrument=True)
+    if args.dump_outputs and rank == 0:     # before the next pass overwrites the result matrices
+        if multi:
+            tab = all_res[(args.steps - 1) & 1].view(world, 2, nq, k).cpu()
+            dump_outputs(args.dump_outputs, tab[:, 0].reshape(world * nq, k).numpy(),
+                         tab[:, 1].reshape(world * nq, k).view(torch.float32).numpy())
+        else:
+            dump_outputs(args.dump_outputs, host_i, host_d)
     wall_hi = wall
     wall_plain, _, _ = timed_host(ef, args.steps, 1)
     qps = world * nq * args.steps / wall

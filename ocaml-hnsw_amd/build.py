@@ -59,7 +59,9 @@ def build(force=False, verbose=False, resource_log=None):
     units = [(s_, s_, []) for s_ in SOURCES]
     units += [("hnsw_search_variants_%d_%d_%d" % v, VARIANT_SOURCE,
                ["-DHNSW_V_METRIC=%d" % v[0], "-DHNSW_V_SEMF=%d" % v[1], "-DHNSW_V_FULL=%d" % v[2]]) for v in VARIANTS]
-    jobs = max(1, int(os.environ.get("HNSW_BUILD_JOBS", os.cpu_count() or 4)))
+    # the CPUs this process may use (a shared host's os.cpu_count() can be many times that), at most 16 compilers
+    usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)
+    jobs = max(1, int(os.environ.get("HNSW_BUILD_JOBS") or os.environ.get("MAX_JOBS") or min(16, usable)))
     pending = list(units)
     running, objs, logs = [], [], []
     n_compiled = [0]

@@ -135,6 +135,30 @@ def test_counter_means_keys_by_kernel_instance_and_launch_size():
     assert bench.search_kernel_name(128, 128, 0, 0, -1) == "hnsw_search_kernel<2,4,2,0,0,1,0>"
 
 
+def test_dump_outputs_writes_exact_float_arrays_and_samples_within_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    rng = np.random.default_rng(5)
+    ids = rng.integers(-1, 1 << 30, size=(300, 10)).astype(np.int32)
+    dist = rng.random((300, 10), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "all"), ids, dist)
+    got_i, got_d = np.load(tmp_path / "all" / "ids.npy"), np.load(tmp_path / "all" / "distances.npy")
+    assert got_i.dtype == np.float64 and np.array_equal(got_i, ids)
+    assert got_d.dtype == np.float32 and np.array_equal(got_d.view(np.uint32), dist.view(np.uint32))
+    assert sorted(os.listdir(tmp_path / "all")) == ["distances.npy", "ids.npy"]
+    # a result above the limit: a fixed sample of query rows, the same on every call, named in query_rows.npy
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096 + 100 * (80 + 40 + 8))
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), ids, dist)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["distances.npy", "ids.npy", "query_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= bench.DUMP_LIMIT
+    rows = np.load(tmp_path / "s1" / "query_rows.npy").astype(np.int64)
+    assert len(rows) == 100 and np.array_equal(np.load(tmp_path / "s1" / "ids.npy"), ids[rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "distances.npy"), dist[rows])
+    for f in files:
+        assert (tmp_path / "s1" / f).read_bytes() == (tmp_path / "s2" / f).read_bytes()
+
+
 @pytest.mark.timeout(300)
 def test_self_launch_starts_the_ranks_and_relays_rank_zeros_line(tmp_path):
     """`python3 bench.py --gpus 2` without a launcher: bench.self_launch starts the ranks through torch.distributed.run on

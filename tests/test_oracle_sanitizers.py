@@ -15,7 +15,9 @@ def test_oracle_tests_pass_under_asan_and_ubsan():
     asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
     if not asan or not os.path.exists(asan):
         pytest.skip("no libasan beside this gcc")
-    env = dict(os.environ, ORACLE_SANITIZE="1", LD_PRELOAD=asan,
+    # the ASan runtime must come first; libraries the environment already preloads stay behind it
+    preload = " ".join(p for p in (asan, os.environ.get("LD_PRELOAD")) if p)
+    env = dict(os.environ, ORACLE_SANITIZE="1", LD_PRELOAD=preload,
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
                         os.path.join(ROOT, "tests", "test_oracle_golden.py"), os.path.join(ROOT, "tests", "test_oracle_paths.py")],
