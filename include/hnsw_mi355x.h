@@ -28,6 +28,7 @@
  *   hnsw_select_neighbours_batch  Ohnsw.select_neighbours (lib/ohnsw.ml:647-663),
  *                            Hnsw_algo.SelectNeighbours.select_neighbours (lib/hnsw_algo.ml:572-609)
  *   hnsw_build               Ohnsw.build_batch_bigarray (lib/ohnsw.ml:840-857), batched on the device
+ *   hnsw_index_insert        Ohnsw.insert (lib/ohnsw.ml:766-837) of m vectors into an index the library holds
  *   hnsw_host_alloc / hnsw_host_register   (nothing in the reference) page-locked query / result matrices,
  *                            which the entry points above read and write from the device in place
  *
@@ -413,6 +414,33 @@ typedef struct hnsw_build_params {
 
 int32_t hnsw_build(const float *vectors, int64_t n, int32_t d, int64_t row_stride,
                    const hnsw_build_params *params, int32_t device, hnsw_index **out);
+
+/* Ohnsw.insert (lib/ohnsw.ml:766-837) for m vectors, on the device, into an index this library holds (made by
+ * hnsw_index_create, hnsw_build or hnsw_index_load); the fold of build_batch_bigarray (:840-857) continued.
+ *   - Ids: the new nodes get ids n_old .. n_old+m-1 (plus id_base), in row order.  m == 0 is a no-op (HNSW_OK).
+ *   - Each new node goes through hnsw_build's per-node steps (level draw, search_one descent, search_k with efConstruction,
+ *     select_neighbours with M / 2M on layer 0, symmetric links, shrink), batched exactly as hnsw_build batches (max_batch,
+ *     batch_div, a node that raises max_layer ends its batch), continuing from position n_old: the same code runs both.
+ *   - Levels: node i's level is the draw hnsw_build with the same seed gives node i (splitmix64 of the state
+ *     seed + i * 0x9E3779B97F4A7C15; node 0 draws nothing).  So build(X[:a]) then inserts of X[a:b], X[b:] with max_batch 1
+ *     equal hnsw_build(X) with max_batch 1 link for link, however the inserts are split; with default batching they do when a
+ *     is a batch boundary of hnsw_build(X)'s schedule.  Inserting into an empty index equals hnsw_build of the same vectors.
+ *   - params: metric and id_base must be the index's (HNSW_ERR_BAD_ARG); num_connections 2..32 and
+ *     num_nodes_search_construction 1..512 as for hnsw_build; the vectors have the index's d, row_stride >= d.
+ *   - Row widths: rows narrower than the insert needs (max_degree0 < 2M, max_degree < M: e.g. a graph flattened from OCaml,
+ *     whose widths are its longest lists) are widened to 2M / M first, order kept; wider rows (max_degree0 > 2M, or
+ *     max_degree > M with an upper layer) are refused (HNSW_ERR_BAD_ARG).
+ *   - expected_ef / expected_semantics: as for hnsw_build.  Shapes prepared before (hnsw_index_prepare) are prepared again.
+ *   - Refused (HNSW_ERR_BAD_ARG): a handle with submitted requests not yet waited for; a replica owned by an hnsw_multi (the
+ *     other replicas would not follow); a device fallback slab (option device_fallback_slab_bytes) that holds no query of the
+ *     grown index.  Work on caller streams (hnsw_search_batch_device) is waited for before any table is freed.
+ *   - What the handle derived from its graph follows it: byte rows (kept only if old and new vectors are all byte-valued),
+ *     split rows (rebuilt; not after option split_rows -1), locality codes (new node v gets code v), the options' effects.
+ *     The device fallback slab keeps its bytes and so holds fewer queries (bytes / (4 n)).
+ *   - All or nothing: on ANY error (including HNSW_ERR_OOM) the index is exactly as before.  The grown tables are built beside
+ *     the old ones and swapped in at the end, so at its peak the call holds two copies of the index on the device. */
+int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride,
+                          const hnsw_build_params *params);
 
 /* select_neighbours as a batched operator (Ohnsw.select_neighbours lib/ohnsw.ml:647-663;
  * keep_all_if_few = 1 adds the functor path's "#candidates <= M returns them all" shortcut,

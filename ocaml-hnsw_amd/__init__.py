@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "hnsw_abi_version", "hnsw_last_error", "hnsw_device_count", "hnsw_index_create",
     "hnsw_index_destroy", "hnsw_index_get_info", "hnsw_index_set_option", "hnsw_index_row_bytes", "hnsw_search_batch",
     "hnsw_search_batch_device", "hnsw_search_batch_h2d", "hnsw_knn", "hnsw_distance_batch", "hnsw_distance_batch_device",
-    "hnsw_build", "hnsw_select_neighbours_batch", "hnsw_index_export_layer0", "hnsw_index_export_upper_count", "hnsw_index_export_upper",
+    "hnsw_build", "hnsw_index_insert", "hnsw_select_neighbours_batch", "hnsw_index_export_layer0", "hnsw_index_export_upper_count", "hnsw_index_export_upper",
     "hnsw_index_layer_stats", "hnsw_index_layer_isolated", "hnsw_index_locality_codes", "hnsw_index_visited_blocks", "hnsw_index_prepare", "hnsw_index_save", "hnsw_index_load",
     "hnsw_search_layer_batch", "hnsw_search_one_batch",
     "hnsw_search_submit", "hnsw_search_wait", "hnsw_index_kernel_times",
@@ -118,6 +118,7 @@ def load():
     L.hnsw_distance_batch.argtypes = [vp, vp, i64, i64, vp, i32, vp]
     L.hnsw_distance_batch_device.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp]
     L.hnsw_build.argtypes = [vp, i64, i32, i64, vp, i32, vp]
+    L.hnsw_index_insert.argtypes = [vp, vp, i64, i64, vp]
     L.hnsw_select_neighbours_batch.argtypes = [vp, vp, i64, i64, vp, vp, i32, i32, i32, vp, vp, vp]
     L.hnsw_select_neighbours_batch.restype = i32
     L.hnsw_index_layer_stats.argtypes = [vp, i32, vp]
@@ -135,7 +136,7 @@ def load():
     L.hnsw_index_export_layer0.argtypes = [vp, vp, vp]
     L.hnsw_index_export_upper_count.argtypes = [vp, i32, vp]
     L.hnsw_index_export_upper.argtypes = [vp, i32, vp, vp, vp]
-    for f in ("hnsw_build", "hnsw_select_neighbours_batch", "hnsw_index_export_layer0", "hnsw_index_export_upper_count",
+    for f in ("hnsw_build", "hnsw_index_insert", "hnsw_select_neighbours_batch", "hnsw_index_export_layer0", "hnsw_index_export_upper_count",
               "hnsw_index_export_upper"):
         getattr(L, f).restype = i32
     for f in ("hnsw_device_count", "hnsw_index_create", "hnsw_index_destroy", "hnsw_index_get_info",
@@ -238,6 +239,30 @@ class Hgraph:
         self.expected_ef, self.expected_sem = int(expected_ef), int(expected_sem)
         self._index = None
         self._device = None
+
+    # The host copy of the vectors.  Ohnsw.insert_batch appends the new rows as parts of their own: one call costs its own
+    # rows, not a copy of all n; the parts are joined into one [n][d] array when the vectors are next read.
+    @property
+    def vectors(self):
+        parts = self.__dict__.get("_vparts")
+        if parts is None:
+            return None
+        if len(parts) > 1:
+            parts[:] = [_np.concatenate(parts)]
+        return parts[0]
+
+    @vectors.setter
+    def vectors(self, value):
+        self._vparts = None if value is None else [value]
+
+    def _append_vectors(self, rows):
+        parts = self.__dict__.get("_vparts")
+        if parts is None:
+            return
+        if len(parts) == 1:
+            parts[0] = _np.ascontiguousarray(parts[0], dtype=_np.float32)     # (no copy for a contiguous float32 array)
+        parts.append(_np.array(rows, dtype=_np.float32))
+        self.row_stride = self.d
 
     @classmethod
     def _from_handle(cls, handle, device, vectors, id_base, metric):
@@ -596,6 +621,33 @@ class Ohnsw:
         h = _C.c_void_p()
         _check(load().hnsw_build(_ptr(X), X.shape[0], X.shape[1], X.shape[1], _C.byref(p), device, _C.byref(h)))
         return Hgraph._from_handle(h, device, X, 0, metric)
+
+    @staticmethod
+    def insert_batch(hgraph, batch, num_connections, num_nodes_search_construction, seed=0, max_batch=0, batch_div=0,
+                     expected_ef=0, expected_sem=SEM_OHNSW):
+        """Ohnsw.insert (lib/ohnsw.ml:766-837) for every row of `batch`, in order, on the device (hnsw_index_insert): the
+        index grows in place.  -> the new ids (np.int64, n_old + id_base onwards).  Levels are the draws hnsw_build with
+        the same seed gives those positions.  Afterwards the Hgraph follows the device index: n, widths, max_layer and
+        entry_point are refreshed, the host vectors (if any) grow by the batch, and deg0 / nbr0 / upper are None until
+        export()."""
+        X, xs = _rows(batch)
+        if X.ndim != 2 or (X.shape[0] and X.shape[1] != hgraph.d):
+            raise InvalidArgument("batch must be [m][d] with the index's d = %d" % hgraph.d)
+        m = X.shape[0]
+        n_old = hgraph.n
+        p = _BuildParams(num_connections, num_nodes_search_construction, hgraph.metric, hgraph.id_base, seed, max_batch,
+                         batch_div, expected_ef, expected_sem)
+        _check(load().hnsw_index_insert(hgraph.handle, _ptr(X), m, max(xs, hgraph.d), _C.byref(p)))
+        if m == 0:
+            return _np.arange(0, dtype=_np.int64)
+        inf = IndexInfo()
+        _check(load().hnsw_index_get_info(hgraph.handle, _C.byref(inf)))
+        hgraph._append_vectors(X)
+        hgraph.n = int(inf.n)
+        hgraph.max_degree0, hgraph.max_degree, hgraph.max_layer = inf.max_degree0, inf.max_degree, inf.max_layer
+        hgraph.entry_point = int(inf.entry_point) if inf.entry_point >= hgraph.id_base else None
+        hgraph.deg0 = hgraph.nbr0 = hgraph.upper = None
+        return _np.arange(n_old + hgraph.id_base, n_old + m + hgraph.id_base, dtype=_np.int64)
 
     @staticmethod
     def select_neighbours(hgraph, targets, candidates, num_neighbours, keep_all_if_few=False, degrees=None):

@@ -102,51 +102,37 @@ hipError_t dispatch_link(int nch, const BuildView &bv, const hnsw_dev::LinkArgs 
 
 } // namespace
 
-// One attempt with a removal buffer of rem_scale * (2 * max_batch * 2M) entries; *rem_overflow tells the
-// caller that some step produced more removals than that (the graph is then discarded, never patched).
-static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t row_stride,
-                             const hnsw_build_params *p, int32_t device, hnsw_index **out,
-                             int64_t rem_scale, bool *rem_overflow) {
+// ---- levels (lib/ohnsw.ml:781): node i's draw is the i-th of one splitmix64 stream, i.e. the mix of the state
+// seed + i * 0x9E3779B97F4A7C15; the first node draws nothing (:774-778).  A function of (seed, i) alone, so an index grown
+// by hnsw_index_insert gets the levels hnsw_build of all its vectors would have given it, however the inserts were split.
+static uint8_t node_level(uint64_t seed, int64_t i, double level_mult) {
+    if (i == 0) return 0;
+    uint64_t s = seed + (uint64_t)(i - 1) * 0x9E3779B97F4A7C15ULL;    // splitmix64 advances the state before mixing
+    const double u = rng_unit(&s);
+    const int l = (int)std::floor(-std::log(u) * level_mult + 0.5);
+    return (uint8_t)std::min(l, 15);
+}
+
+// log2 entries of the construction search's visited cache for a graph of n nodes
+static int build_vt_bits(int efc, int64_t n) {
+    int b = efc <= 256 ? 11 : 12;
+    while (b < 16 && ((int64_t)0xFFFF << (b - 1)) < n) ++b;   // tags identify ids exactly, 0xFFFF = empty way
+    return b;
+}
+
+// The batch loop of the builder: inserts the nodes at positions [pos0, n) into the tables of bv (bv.iv.n == n; rows of the nodes
+// before pos0 hold their graph, compacted or with holes; rows of the others are empty), batch by batch in node order (fold_cols,
+// lib/ohnsw.ml:848), and compacts every row at the end.  lvl[j - pos0] is node j's level; *cur_max / *entry are the graph's
+// state before pos0 and after n.  One attempt with a removal buffer of rem_scale * (2 * max_batch * 2M) entries; *rem_overflow
+// tells the caller that some step produced more removals than that (the tables are then to be discarded, never patched).
+// hnsw_build runs it from pos0 = 1 on fresh tables, hnsw_index_insert from the old node count on grown copies.
+static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int64_t n, int lcap, const hnsw_build_params *p,
+                           int64_t rem_scale, bool *rem_overflow, int *cur_max_io, int *entry_io) {
     *rem_overflow = false;
-    if (!out || !p) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    *out = nullptr;
-    if (n < 1 || n > 0x7FFFFFF0LL) return fail(HNSW_ERR_BAD_ARG, "n=%lld out of range", (long long)n);
-    if (!vectors || d < 1 || row_stride < d) return fail(HNSW_ERR_BAD_ARG, "bad vectors/d/row_stride");
-    if (p->metric != HNSW_METRIC_L2 && p->metric != HNSW_METRIC_IP) return fail(HNSW_ERR_BAD_ARG, "bad metric");
     const int M = p->num_connections, efc = p->num_nodes_search_construction;
-    if (M < 2 || 2 * M > 64) return fail(HNSW_ERR_UNSUPPORTED, "num_connections=%d must be in 2..32", M);
-    if (efc < 1 || efc > 512) return fail(HNSW_ERR_UNSUPPORTED, "num_nodes_search_construction=%d must be in 1..512", efc);
-    const int nchunks = (d + 3) / 4;
-    const int nch = pick_nch(nchunks);
-    if (!nch) return fail(HNSW_ERR_UNSUPPORTED, "d=%d > 1024 not supported", d);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(HNSW_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)"); }
-    if (device < 0 || device >= ndev) return fail(HNSW_ERR_BAD_ARG, "device %d out of range", device);
-    HIP_TRY(hipSetDevice(device));
-
-    // ---- levels (lib/ohnsw.ml:781): the first node draws nothing (:774-778) ----
-    const double level_mult = 1.0 / std::log((double)M);                                  // :844
-    std::vector<uint8_t> lvl((size_t)n, 0);
-    {
-        uint64_t rng = p->seed;
-        for (int64_t i = 1; i < n; ++i) {
-            const double u = rng_unit(&rng);
-            int l = (int)std::floor(-std::log(u) * level_mult + 0.5);
-            lvl[(size_t)i] = (uint8_t)std::min(l, 15);
-        }
-    }
-    int lcap = 1;
-    for (int64_t i = 0; i < n; ++i) lcap = std::max(lcap, (int)lvl[(size_t)i] + 1);
-    std::vector<int32_t> off((size_t)n, -1);
-    int64_t rowsU = 0;
-    for (int64_t i = 0; i < n; ++i) if (lvl[(size_t)i]) { off[(size_t)i] = (int32_t)rowsU; rowsU += lvl[(size_t)i]; }
-
-    hnsw_index *idx = new hnsw_index();
-    idx->device = device;
+    const int nch = pick_nch(bv.iv.nchunks);
     int rc = HNSW_OK;
     const int S0 = 2 * M, SU = M;
-    const int64_t stride = padded_stride(d);
-    size_t xbytes = 0;
     const int bdiv = p->batch_div > 0 ? p->batch_div : 16;
     const int bmax = p->max_batch > 0 ? p->max_batch : 8192;
     const int cand_stride = (efc + 63) / 64 * 64;
@@ -154,41 +140,19 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
     const int64_t maxrec = (int64_t)bmax * lcap;
     const int64_t max_edges = (int64_t)bmax * S0;
     const int64_t rem_cap = max_edges * 2 * rem_scale;
+    const int64_t rowsU = bv.iv.rowsU;
     uint32_t rem_over = 0;
     hipStream_t st = nullptr;
     void *dNodes = nullptr, *dRecOf = nullptr, *dRecNode = nullptr, *dCandId = nullptr, *dCandKey = nullptr,
          *dCandCnt = nullptr, *dEdges = nullptr, *dEdgesSorted = nullptr, *dRem = nullptr, *dRemCnt = nullptr, *dTemp = nullptr;
     size_t temp_bytes = 0;
-    BuildView bv{};
     int32_t *hp_nodes[2] = {nullptr, nullptr}, *hp_rec_of[2] = {nullptr, nullptr}, *hp_rec_node[2] = {nullptr, nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr};
     int64_t batch_no = 0;
     std::vector<int32_t> rec_begin((size_t)lcap + 1, 0);
-    int cur_max = 0, entry = 0;
-
-    if ((rc = upload_vectors(vectors, n, d, row_stride, &idx->dX, &xbytes))) goto done;
-    HIP_TRY_B(hipMalloc(&idx->dNbr0, (size_t)n * S0 * 4));
-    HIP_TRY_B(hipMemset(idx->dNbr0, 0xFF, (size_t)n * S0 * 4));
-    HIP_TRY_B(hipMalloc(&idx->dNbrU, (size_t)std::max<int64_t>(rowsU, 1) * SU * 4));
-    HIP_TRY_B(hipMemset(idx->dNbrU, 0xFF, (size_t)std::max<int64_t>(rowsU, 1) * SU * 4));
-    HIP_TRY_B(hipMalloc(&idx->dOff, (size_t)n * 4));
-    HIP_TRY_B(hipMemcpy(idx->dOff, off.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY_B(hipMalloc(&idx->dLvl, (size_t)n));
-    HIP_TRY_B(hipMemcpy(idx->dLvl, lvl.data(), (size_t)n, hipMemcpyHostToDevice));
-    if ((rc = upload_upper_ref(off.data(), lvl.data(), n, &idx->dRef))) goto done;
-    idx->rowsU = rowsU; idx->iv.rowsU = rowsU;
-    {
-        IndexView &iv = idx->iv;
-        iv.X = (const float *)idx->dX; iv.stride = stride; iv.n = n; iv.d = d; iv.nchunks = nchunks;
-        iv.nbr0 = (const int32_t *)idx->dNbr0; iv.S0 = S0; iv.SU = SU;
-        iv.nbrU = (const int32_t *)idx->dNbrU; iv.upper_off = (const int32_t *)idx->dOff;
-        iv.upper_lvl = (const uint8_t *)idx->dLvl; iv.upper_ref = (const int2 *)idx->dRef;
-        iv.max_layer = 0; iv.entry_point = 0; iv.id_base = p->id_base;
-    }
-    bv.iv = idx->iv; bv.nbr0_w = (int32_t *)idx->dNbr0; bv.nbrU_w = (int32_t *)idx->dNbrU;
+    int cur_max = *cur_max_io, entry = *entry_io;
     bv.efc = efc; bv.cand_stride = cand_stride;
-    bv.vt_bits = efc <= 256 ? 11 : 12;
-    while (bv.vt_bits < 16 && ((int64_t)0xFFFF << (bv.vt_bits - 1)) < n) ++bv.vt_bits;   // tags identify ids exactly, 0xFFFF = empty way
+    bv.vt_bits = build_vt_bits(efc, n);
 
     HIP_TRY_B(hipStreamCreate(&st));
     HIP_TRY_B(hipMalloc(&dNodes, (size_t)bmax * 4));
@@ -212,12 +176,12 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
         HIP_TRY_B(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
     }
 
-    // ---- batches, in node order (fold_cols, lib/ohnsw.ml:848); node 0 is the first entry point ----
-    for (int64_t pos = 1; pos < n;) {
+    // ---- batches, in node order (fold_cols, lib/ohnsw.ml:848) ----
+    for (int64_t pos = pos0; pos < n;) {
         int64_t bsz = std::max<int64_t>(1, std::min<int64_t>(bmax, pos / bdiv));
         int64_t end = std::min(n, pos + bsz);
         for (int64_t j = pos; j < end; ++j)
-            if ((int)lvl[(size_t)j] > cur_max) { end = j + 1; break; }       // :832-836
+            if ((int)lvl[(size_t)(j - pos0)] > cur_max) { end = j + 1; break; }       // :832-836
         const int B = (int)(end - pos);
         const int kb = (int)(batch_no & 1);
         if (batch_no >= 2) HIP_TRY_B(hipEventSynchronize(ev[kb]));
@@ -229,7 +193,7 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
             rec_begin[(size_t)l] = nrec;
             for (int i = 0; i < B; ++i) {
                 h_nodes[i] = (int32_t)(pos + i);
-                if ((int)lvl[(size_t)(pos + i)] >= l) { h_rec_of[(size_t)i * lcap + l] = nrec; h_rec_node[nrec] = (int32_t)(pos + i); nrec++; }
+                if ((int)lvl[(size_t)(pos + i - pos0)] >= l) { h_rec_of[(size_t)i * lcap + l] = nrec; h_rec_node[nrec] = (int32_t)(pos + i); nrec++; }
             }
         }
         rec_begin[(size_t)cur_max + 1] = nrec;
@@ -274,17 +238,97 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
                                (const uint64_t *)dRem, (const uint32_t *)dRemCnt, (uint32_t)rem_cap, l);
             HIP_TRY_B(hipGetLastError());
         }
-        if ((int)lvl[(size_t)(end - 1)] > cur_max) { cur_max = lvl[(size_t)(end - 1)]; entry = (int)(end - 1); } // :832-836
+        if ((int)lvl[(size_t)(end - 1 - pos0)] > cur_max) { cur_max = lvl[(size_t)(end - 1 - pos0)]; entry = (int)(end - 1); } // :832-836
         pos = end;
         batch_no++;
     }
-    hipLaunchKernelGGL(hnsw_dev::build_compact_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (int32_t *)idx->dNbr0, n, S0);
+    hipLaunchKernelGGL(hnsw_dev::build_compact_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, bv.nbr0_w, n, S0);
     if (rowsU > 0)
-        hipLaunchKernelGGL(hnsw_dev::build_compact_kernel, dim3((unsigned)((rowsU + 3) / 4)), dim3(256), 0, st, (int32_t *)idx->dNbrU, rowsU, SU);
+        hipLaunchKernelGGL(hnsw_dev::build_compact_kernel, dim3((unsigned)((rowsU + 3) / 4)), dim3(256), 0, st, bv.nbrU_w, rowsU, SU);
     HIP_TRY_B(hipGetLastError());
     HIP_TRY_B(hipStreamSynchronize(st));
     HIP_TRY_B(hipMemcpy(&rem_over, (const uint32_t *)dRemCnt + 1, 4, hipMemcpyDeviceToHost));
     if (rem_over) { *rem_overflow = true; rc = fail(HNSW_ERR_DEGREE_OVERFLOW, "a build step produced %u symmetric removals, more than the %lld the buffer holds", rem_over, (long long)rem_cap); goto done; }
+    *cur_max_io = cur_max; *entry_io = entry;
+done:
+    for (void *q : {dNodes, dRecOf, dRecNode, dCandId, dCandKey, dCandCnt, dEdges, dEdgesSorted, dRem, dRemCnt, dTemp}) if (q) (void)hipFree(q);
+    for (int k = 0; k < 2; ++k) {
+        if (hp_nodes[k]) (void)hipHostFree(hp_nodes[k]);
+        if (hp_rec_of[k]) (void)hipHostFree(hp_rec_of[k]);
+        if (hp_rec_node[k]) (void)hipHostFree(hp_rec_node[k]);
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    }
+    if (st) (void)hipStreamDestroy(st);
+    return rc;
+}
+
+// the builder's parameter checks, shared by hnsw_build and hnsw_index_insert
+static int32_t check_build_params(const hnsw_build_params *p) {
+    if (p->metric != HNSW_METRIC_L2 && p->metric != HNSW_METRIC_IP) return fail(HNSW_ERR_BAD_ARG, "bad metric");
+    const int M = p->num_connections, efc = p->num_nodes_search_construction;
+    if (M < 2 || 2 * M > 64) return fail(HNSW_ERR_UNSUPPORTED, "num_connections=%d must be in 2..32", M);
+    if (efc < 1 || efc > 512) return fail(HNSW_ERR_UNSUPPORTED, "num_nodes_search_construction=%d must be in 1..512", efc);
+    return HNSW_OK;
+}
+
+// One attempt of hnsw_build (see run_batches for rem_scale / rem_overflow).
+static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t row_stride,
+                             const hnsw_build_params *p, int32_t device, hnsw_index **out,
+                             int64_t rem_scale, bool *rem_overflow) {
+    *rem_overflow = false;
+    if (!out || !p) return fail(HNSW_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (n < 1 || n > 0x7FFFFFF0LL) return fail(HNSW_ERR_BAD_ARG, "n=%lld out of range", (long long)n);
+    if (!vectors || d < 1 || row_stride < d) return fail(HNSW_ERR_BAD_ARG, "bad vectors/d/row_stride");
+    { const int32_t rcp = check_build_params(p); if (rcp) return rcp; }
+    const int M = p->num_connections;
+    const int nchunks = (d + 3) / 4;
+    const int nch = pick_nch(nchunks);
+    if (!nch) return fail(HNSW_ERR_UNSUPPORTED, "d=%d > 1024 not supported", d);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(HNSW_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)"); }
+    if (device < 0 || device >= ndev) return fail(HNSW_ERR_BAD_ARG, "device %d out of range", device);
+    HIP_TRY(hipSetDevice(device));
+
+    const double level_mult = 1.0 / std::log((double)M);                                  // :844
+    std::vector<uint8_t> lvl((size_t)n, 0);
+    for (int64_t i = 0; i < n; ++i) lvl[(size_t)i] = node_level(p->seed, i, level_mult);
+    int lcap = 1;
+    for (int64_t i = 0; i < n; ++i) lcap = std::max(lcap, (int)lvl[(size_t)i] + 1);
+    std::vector<int32_t> off((size_t)n, -1);
+    int64_t rowsU = 0;
+    for (int64_t i = 0; i < n; ++i) if (lvl[(size_t)i]) { off[(size_t)i] = (int32_t)rowsU; rowsU += lvl[(size_t)i]; }
+
+    hnsw_index *idx = new hnsw_index();
+    idx->device = device;
+    int rc = HNSW_OK;
+    const int S0 = 2 * M, SU = M;
+    const int64_t stride = padded_stride(d);
+    size_t xbytes = 0;
+    BuildView bv{};
+    int cur_max = 0, entry = 0;                 // node 0 is the first entry point
+
+    if ((rc = upload_vectors(vectors, n, d, row_stride, &idx->dX, &xbytes))) goto done;
+    HIP_TRY_B(hipMalloc(&idx->dNbr0, (size_t)n * S0 * 4));
+    HIP_TRY_B(hipMemset(idx->dNbr0, 0xFF, (size_t)n * S0 * 4));
+    HIP_TRY_B(hipMalloc(&idx->dNbrU, (size_t)std::max<int64_t>(rowsU, 1) * SU * 4));
+    HIP_TRY_B(hipMemset(idx->dNbrU, 0xFF, (size_t)std::max<int64_t>(rowsU, 1) * SU * 4));
+    HIP_TRY_B(hipMalloc(&idx->dOff, (size_t)n * 4));
+    HIP_TRY_B(hipMemcpy(idx->dOff, off.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY_B(hipMalloc(&idx->dLvl, (size_t)n));
+    HIP_TRY_B(hipMemcpy(idx->dLvl, lvl.data(), (size_t)n, hipMemcpyHostToDevice));
+    if ((rc = upload_upper_ref(off.data(), lvl.data(), n, &idx->dRef))) goto done;
+    idx->rowsU = rowsU; idx->iv.rowsU = rowsU;
+    {
+        IndexView &iv = idx->iv;
+        iv.X = (const float *)idx->dX; iv.stride = stride; iv.n = n; iv.d = d; iv.nchunks = nchunks;
+        iv.nbr0 = (const int32_t *)idx->dNbr0; iv.S0 = S0; iv.SU = SU;
+        iv.nbrU = (const int32_t *)idx->dNbrU; iv.upper_off = (const int32_t *)idx->dOff;
+        iv.upper_lvl = (const uint8_t *)idx->dLvl; iv.upper_ref = (const int2 *)idx->dRef;
+        iv.max_layer = 0; iv.entry_point = 0; iv.id_base = p->id_base;
+    }
+    bv.iv = idx->iv; bv.nbr0_w = (int32_t *)idx->dNbr0; bv.nbrU_w = (int32_t *)idx->dNbrU;
+    if ((rc = run_batches(bv, lvl.data() + 1, 1, n, lcap, p, rem_scale, rem_overflow, &cur_max, &entry))) goto done;
 
     idx->iv.max_layer = cur_max; idx->iv.entry_point = entry;
     {
@@ -295,20 +339,131 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
         inf.row_stride_bytes = stride * 4; inf.device = device;
     }
 done:
-    for (void *q : {dNodes, dRecOf, dRecNode, dCandId, dCandKey, dCandCnt, dEdges, dEdgesSorted, dRem, dRemCnt, dTemp}) if (q) (void)hipFree(q);
-    for (int k = 0; k < 2; ++k) {
-        if (hp_nodes[k]) (void)hipHostFree(hp_nodes[k]);
-        if (hp_rec_of[k]) (void)hipHostFree(hp_rec_of[k]);
-        if (hp_rec_node[k]) (void)hipHostFree(hp_rec_node[k]);
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
-    }
-    if (st) (void)hipStreamDestroy(st);
     if (!rc) rc = make_byte_rows(idx);      // the finished index serves searches from the byte copy where the data allows
     if (!rc) rc = make_split_rows(idx);     // ... or from split rows where a row ends just past a 128-byte line
     if (rc) { hnsw_index_destroy(idx); return rc; }
     (void)warm_up(idx);                     // ... and its first search call does not pay for the process's code loading (an optimisation:
     prepare_quietly(idx, p->expected_ef, p->expected_semantics);      //  failures are left to the first search) nor for its shape's one-time decisions
     *out = idx;
+    return HNSW_OK;
+}
+
+namespace {
+// one thread per slot of the wider table: row r of `src` (width ws, compacted) becomes row r of `dst` (width wd >= ws) in the
+// same order, the new slots empty
+__global__ void __launch_bounds__(256)
+widen_rows_kernel(const int32_t *src, int64_t rows, int32_t ws, int32_t *dst, int32_t wd) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= rows * wd) return;
+    const int64_t r = e / wd;
+    const int j = (int)(e - r * wd);
+    dst[e] = j < ws ? src[r * ws + j] : -1;
+}
+
+// flag[0] = 1 if an upper-layer row lists a node that is not on that layer, or the entry point is not on the top layer.  The
+// builder WRITES into the rows of the nodes it finds on a layer, so a graph handed to hnsw_index_create that breaks this would
+// send it outside the tables; hnsw_index_insert refuses such a graph instead.
+__global__ void __launch_bounds__(256)
+upper_rows_check_kernel(const int2 *upper_ref, const int32_t *nbrU, int32_t SU, int64_t n, int32_t entry, int32_t max_layer, int32_t *flag) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    const int2 ref = upper_ref[v];
+    if (v == entry && ref.y < max_layer) flag[0] = 1;
+    for (int l = 1; l <= ref.y; ++l) {
+        const int32_t *row = nbrU + ((int64_t)ref.x + (l - 1)) * SU;
+        for (int j = 0; j < SU; ++j) {
+            const int32_t u = row[j];
+            if (u >= 0 && (u >= n || upper_ref[u].y < l)) flag[0] = 1;
+        }
+    }
+}
+
+hipError_t widen_rows(const void *src, int64_t rows, int ws, void *dst, int wd) {
+    if (rows <= 0) return hipSuccess;
+    if (ws == wd) return hipMemcpy(dst, src, (size_t)rows * ws * 4, hipMemcpyDeviceToDevice);
+    const int64_t total = rows * wd;
+    hipLaunchKernelGGL(widen_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr,
+                       (const int32_t *)src, rows, ws, (int32_t *)dst, wd);
+    return hipGetLastError();
+}
+} // namespace
+
+// One attempt of hnsw_index_insert: a new handle `*out` with the graph of idx grown by the m vectors -- idx's tables copied
+// (rows widened to 2M / M) into tables sized for n_old + m nodes, then run_batches from position n_old.  idx is only read.
+// The derived tables (byte / split rows, locality codes) are the caller's.
+static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p,
+                              int64_t rem_scale, bool *rem_overflow, hnsw_index **out) {
+    *rem_overflow = false;
+    *out = nullptr;
+    const IndexView &ov = idx->iv;
+    const int64_t n_old = ov.n, n = n_old + m;
+    const int M = p->num_connections, S0 = 2 * M, SU = M;
+    const int S0o = ov.S0, SUo = ov.SU;
+    const int64_t stride = ov.stride, rowsU_old = n_old > 0 ? idx->rowsU : 0;
+    const double level_mult = 1.0 / std::log((double)M);
+    std::vector<uint8_t> lvl((size_t)m);
+    for (int64_t j = 0; j < m; ++j) lvl[(size_t)j] = node_level(p->seed, n_old + j, level_mult);
+    int cur_max = n_old > 0 ? ov.max_layer : 0, entry = n_old > 0 ? ov.entry_point : 0;
+    int lcap = cur_max + 1;
+    for (uint8_t l : lvl) lcap = std::max(lcap, (int)l + 1);
+    std::vector<int32_t> off((size_t)m, -1);
+    std::vector<int2> ref((size_t)m);
+    int64_t rowsU = rowsU_old;
+    for (int64_t j = 0; j < m; ++j) {
+        if (lvl[(size_t)j]) { off[(size_t)j] = (int32_t)rowsU; rowsU += lvl[(size_t)j]; }
+        ref[(size_t)j] = make_int2(off[(size_t)j], (int)lvl[(size_t)j]);
+    }
+    if (rowsU > 0x7FFFFFF0LL) return fail(HNSW_ERR_UNSUPPORTED, "too many upper rows");
+
+    hnsw_index *nx = new hnsw_index();
+    nx->device = idx->device;
+    int rc = HNSW_OK;
+    const size_t xbytes = (size_t)n * stride * 4;
+    BuildView bv{};
+    HIP_TRY_B(hipMalloc(&nx->dX, xbytes));
+    if (n_old > 0) HIP_TRY_B(hipMemcpy(nx->dX, idx->dX, (size_t)n_old * stride * 4, hipMemcpyDeviceToDevice));
+    if ((rc = upload_rows(vectors, m, ov.d, row_stride, (float *)nx->dX + n_old * stride))) goto done;
+    HIP_TRY_B(hipMalloc(&nx->dNbr0, (size_t)n * S0 * 4));
+    HIP_TRY_B(widen_rows(idx->dNbr0, n_old, S0o, nx->dNbr0, S0));
+    HIP_TRY_B(hipMemset((int32_t *)nx->dNbr0 + n_old * S0, 0xFF, (size_t)m * S0 * 4));
+    HIP_TRY_B(hipMalloc(&nx->dNbrU, (size_t)std::max<int64_t>(rowsU, 1) * SU * 4));
+    HIP_TRY_B(widen_rows(idx->dNbrU, rowsU_old, SUo, nx->dNbrU, SU));
+    HIP_TRY_B(hipMemset((int32_t *)nx->dNbrU + rowsU_old * SU, 0xFF, (size_t)(std::max<int64_t>(rowsU, 1) - rowsU_old) * SU * 4));
+    HIP_TRY_B(hipMalloc(&nx->dOff, (size_t)n * 4));
+    HIP_TRY_B(hipMalloc(&nx->dLvl, (size_t)n));
+    HIP_TRY_B(hipMalloc(&nx->dRef, (size_t)n * sizeof(int2)));
+    if (n_old > 0) {
+        HIP_TRY_B(hipMemcpy(nx->dOff, idx->dOff, (size_t)n_old * 4, hipMemcpyDeviceToDevice));
+        HIP_TRY_B(hipMemcpy(nx->dLvl, idx->dLvl, (size_t)n_old, hipMemcpyDeviceToDevice));
+        HIP_TRY_B(hipMemcpy(nx->dRef, idx->dRef, (size_t)n_old * sizeof(int2), hipMemcpyDeviceToDevice));
+    }
+    HIP_TRY_B(hipMemcpy((int32_t *)nx->dOff + n_old, off.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+    HIP_TRY_B(hipMemcpy((uint8_t *)nx->dLvl + n_old, lvl.data(), (size_t)m, hipMemcpyHostToDevice));
+    HIP_TRY_B(hipMemcpy((int2 *)nx->dRef + n_old, ref.data(), (size_t)m * sizeof(int2), hipMemcpyHostToDevice));
+    nx->rowsU = rowsU;
+    {
+        IndexView &iv = nx->iv;
+        iv = ov;                                                        // d, stride, nchunks, id_base
+        iv.X = (const float *)nx->dX; iv.n = n;
+        iv.nbr0 = (const int32_t *)nx->dNbr0; iv.S0 = S0; iv.SU = SU;
+        iv.nbrU = (const int32_t *)nx->dNbrU; iv.rowsU = rowsU; iv.upper_off = (const int32_t *)nx->dOff;
+        iv.upper_lvl = (const uint8_t *)nx->dLvl; iv.upper_ref = (const int2 *)nx->dRef;
+        iv.X8 = nullptr; iv.Xm = nullptr; iv.tail0 = nullptr; iv.lcode = nullptr; iv.lcode0 = nullptr;   // the caller's
+        iv.max_layer = cur_max; iv.entry_point = entry;
+    }
+    bv.iv = nx->iv; bv.nbr0_w = (int32_t *)nx->dNbr0; bv.nbrU_w = (int32_t *)nx->dNbrU;
+    if (n > 1 && (rc = run_batches(bv, lvl.data() + (n_old > 0 ? 0 : 1), std::max<int64_t>(n_old, 1), n, lcap, p, rem_scale,
+                                   rem_overflow, &cur_max, &entry))) goto done;
+    nx->iv.max_layer = cur_max; nx->iv.entry_point = entry;
+    {
+        hnsw_index_info &inf = nx->info;
+        inf = idx->info;                                                // d, metric, id_base, row_stride_bytes, device
+        inf.n = n; inf.max_degree0 = S0; inf.max_degree = SU; inf.max_layer = cur_max; inf.entry_point = (int64_t)entry + ov.id_base;
+        inf.device_bytes = (int64_t)(xbytes + (size_t)n * S0 * 4 + (size_t)std::max<int64_t>(rowsU, 1) * SU * 4 + (size_t)n * 13);
+    }
+done:
+    if (rc) { hnsw_index_destroy(nx); return rc; }
+    *out = nx;
     return HNSW_OK;
 }
 
@@ -327,6 +482,94 @@ int32_t hnsw_build(const float *vectors, int64_t n, int32_t d, int64_t row_strid
         if (!overflow) return rc;
     }
     return rc;   // HNSW_ERR_DEGREE_OVERFLOW with the message of the last attempt
+}
+
+int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p) {
+    if (!idx || !p) return fail(HNSW_ERR_BAD_ARG, "null argument");
+    if (m < 0) return fail(HNSW_ERR_BAD_ARG, "m=%lld < 0", (long long)m);
+    if (m == 0) return HNSW_OK;
+    const int64_t n_old = idx->iv.n, n = n_old + m;
+    if (!vectors) return fail(HNSW_ERR_BAD_ARG, "null vectors");
+    if (n > 0x7FFFFFF0LL) return fail(HNSW_ERR_BAD_ARG, "n=%lld out of range", (long long)n);
+    if (row_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "row_stride=%lld < d=%d", (long long)row_stride, idx->iv.d);
+    if (p->metric != idx->info.metric) return fail(HNSW_ERR_BAD_ARG, "metric %d differs from the index's %d", p->metric, idx->info.metric);
+    if (p->id_base != idx->iv.id_base) return fail(HNSW_ERR_BAD_ARG, "id_base %d differs from the index's %d", p->id_base, idx->iv.id_base);
+    { const int32_t rcp = check_build_params(p); if (rcp) return rcp; }
+    const int M = p->num_connections;
+    if (n_old > 0 && idx->iv.S0 > 2 * M)
+        return fail(HNSW_ERR_BAD_ARG, "max_degree0=%d of the index is wider than 2 * num_connections=%d", idx->iv.S0, 2 * M);
+    if (n_old > 0 && idx->iv.max_layer > 0 && idx->iv.SU > M)
+        return fail(HNSW_ERR_BAD_ARG, "max_degree=%d of the index is wider than num_connections=%d", idx->iv.SU, M);
+    if (n_old > 0 && idx->iv.entry_point < 0) return fail(HNSW_ERR_BAD_ARG, "the index has nodes but no entry point");
+    if (idx->live_requests > 0) return fail(HNSW_ERR_BAD_ARG, "%d submitted requests not waited for (hnsw_search_wait first)", idx->live_requests);
+    if (idx->multi_replica) return fail(HNSW_ERR_BAD_ARG, "the index is a replica of an hnsw_multi: inserting into one replica would desynchronise the others");
+    if (idx->fb_queries > 0 && (int64_t)idx->dFbSlab.cap / (n * 4) < 1)
+        return fail(HNSW_ERR_BAD_ARG, "device_fallback_slab_bytes=%lld holds no query of the grown index: one needs 4 n = %lld bytes",
+                    (long long)idx->dFbSlab.cap, (long long)(n * 4));
+    HIP_TRY(hipSetDevice(idx->device));
+    if (n_old > 0) {
+        int32_t *dflag = nullptr, bad = 0;
+        HIP_TRY(hipMalloc((void **)&dflag, 4));
+        hipError_t e = hipMemset(dflag, 0, 4);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(upper_rows_check_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, nullptr, idx->iv.upper_ref,
+                               idx->iv.nbrU, idx->iv.SU, n_old, idx->iv.entry_point, idx->iv.max_layer, dflag);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(&bad, dflag, 4, hipMemcpyDeviceToHost);
+        (void)hipFree(dflag);
+        if (e != hipSuccess) return fail(HNSW_ERR_HIP, "upper-row check failed: %s", hipGetErrorString(e));
+        if (bad) return fail(HNSW_ERR_BAD_ARG, "the graph lists a node on a layer it is not on (or its entry point is not on the top layer): not grown");
+    }
+
+    // the grown graph, in tables of its own: on any error idx is as it was (overflow: again from idx's tables, 4x the room)
+    hnsw_index *nx = nullptr;
+    int32_t rc = HNSW_OK;
+    for (int64_t scale = 1; scale <= 64; scale *= 4) {
+        bool overflow = false;
+        rc = insert_attempt(idx, vectors, m, row_stride, p, scale, &overflow, &nx);
+        if (!overflow) break;
+    }
+    // ... and what the handle derives from the graph, made again for it: the byte rows if ALL vectors are byte-valued, the split
+    // rows (per-slot tails follow the changed adjacency) unless option split_rows -1 freed them for good, the locality codes
+    if (!rc) rc = make_byte_rows(nx);
+    if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx);
+    if (!rc) rc = extend_locality_codes(idx, nx);
+    if (rc) {
+        if (nx) hnsw_index_destroy(nx);
+        (void)hipGetLastError();                    // (a failed allocation must not surface in the next call on this handle)
+        return rc;
+    }
+    // swap: work still in flight on caller streams (hnsw_search_batch_device) reads the old tables
+    {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) { hnsw_index_destroy(nx); return fail(HNSW_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); }
+    }
+    const bool bytes_before = idx->iv.X8 != nullptr, split_before = idx->iv.Xm != nullptr;
+    void **mine[] = {&idx->dX, &idx->dX8, &idx->dXm, &idx->dTail0, &idx->dLcode, &idx->dLcode0, &idx->dNbr0, &idx->dNbrU, &idx->dOff, &idx->dLvl, &idx->dRef};
+    void **theirs[] = {&nx->dX, &nx->dX8, &nx->dXm, &nx->dTail0, &nx->dLcode, &nx->dLcode0, &nx->dNbr0, &nx->dNbrU, &nx->dOff, &nx->dLvl, &nx->dRef};
+    for (size_t i = 0; i < sizeof mine / sizeof mine[0]; ++i) {
+        if (*mine[i]) (void)hipFree(*mine[i]);
+        *mine[i] = *theirs[i]; *theirs[i] = nullptr;
+    }
+    idx->iv = nx->iv;
+    if (idx->byte_rows_off) idx->iv.X8 = nullptr;          // the options keep their effect
+    if (idx->split_rows_off) idx->iv.Xm = nullptr;
+    idx->info = nx->info;
+    idx->rowsU = nx->rowsU;
+    idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
+    hnsw_index_destroy(nx);
+    // the per-shape choices that follow n or the row format
+    idx->resident_queries = 0; idx->vt_grow_key = -1;
+    if (bytes_before != (idx->iv.X8 != nullptr) || split_before != (idx->iv.Xm != nullptr))
+        for (auto &c : idx->blk_choice) c[0] = c[1] = -1;
+    if (idx->fb_queries > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.cap / (n * 4), 65536);
+    // the grown index is searched at the steady-state rate from its first call, as a loaded one
+    (void)warm_up(idx);
+    const std::vector<std::pair<int, int>> shapes = idx->prepared;
+    for (const auto &pr : shapes) prepare_quietly(idx, pr.first, pr.second);
+    prepare_quietly(idx, p->expected_ef, p->expected_semantics);
+    return HNSW_OK;
 }
 
 // ---- select_neighbours operator ----------------------------------------------------------------------

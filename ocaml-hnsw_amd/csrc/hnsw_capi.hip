@@ -74,19 +74,24 @@ int upload_vectors(const float *vectors, int64_t n, int d, int64_t row_stride, v
     const size_t xbytes = (size_t)std::max<int64_t>(n, 1) * stride * sizeof(float);
     *bytes = xbytes;
     if (hipMalloc(dX, xbytes) != hipSuccess) { (void)hipGetLastError(); return fail(HNSW_ERR_OOM, "hipMalloc(%zu) for vectors failed", xbytes); }
+    return upload_rows(vectors, n, d, row_stride, (float *)*dX);
+}
+
+int upload_rows(const float *vectors, int64_t n, int d, int64_t row_stride, float *dst) {
+    const int64_t stride = padded_stride(d);
     if (n == 0) return HNSW_OK;
     if (stride == row_stride) {
-        if (hipMemcpy(*dX, vectors, xbytes, hipMemcpyHostToDevice) != hipSuccess) return fail(HNSW_ERR_HIP, "vector upload failed");
+        if (hipMemcpy(dst, vectors, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(HNSW_ERR_HIP, "vector upload failed");
         return HNSW_OK;
     }
     const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (stride * 4));
-    std::vector<float> stage((size_t)chunk_rows * stride);
+    std::vector<float> stage((size_t)std::min(chunk_rows, n) * stride);
     for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
         const int64_t nr = std::min(chunk_rows, n - r0);
         std::fill(stage.begin(), stage.begin() + (size_t)nr * stride, 0.0f);
         for (int64_t i = 0; i < nr; ++i)
             memcpy(&stage[(size_t)i * stride], vectors + (r0 + i) * row_stride, sizeof(float) * (size_t)d);
-        if (hipMemcpy((float *)*dX + r0 * stride, stage.data(), (size_t)nr * stride * 4, hipMemcpyHostToDevice) != hipSuccess)
+        if (hipMemcpy(dst + r0 * stride, stage.data(), (size_t)nr * stride * 4, hipMemcpyHostToDevice) != hipSuccess)
             return fail(HNSW_ERR_HIP, "vector upload failed");
     }
     return HNSW_OK;
@@ -699,6 +704,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     if (!strcmp(name, "lds_pad")) { idx->lds_pad = value < 0 ? -1 : (int)std::min<int64_t>(value, 32768); return HNSW_OK; }
     if (!strcmp(name, "byte_rows")) {     // 0: search the fp32 rows even where a byte copy exists; otherwise: use it where it exists
         idx->iv.X8 = value != 0 ? (const uint8_t *)idx->dX8 : nullptr;
+        idx->byte_rows_off = value == 0;
         forget_shape_choices();
         return HNSW_OK;
     }
@@ -711,6 +717,8 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
             idx->dXm = nullptr; idx->dTail0 = nullptr; idx->iv.tail0 = nullptr;
         }
         idx->iv.Xm = value > 0 ? (const float *)idx->dXm : nullptr;
+        idx->split_rows_off = value <= 0;
+        idx->split_rows_freed = idx->split_rows_freed || value < 0;
         forget_shape_choices();
         return HNSW_OK;
     }

@@ -74,6 +74,8 @@ int upload_upper_ref(const int32_t *off, const uint8_t *lvl, int64_t n, void **d
 
 // copies [n][row_stride] host rows into a fresh zero-padded device table
 int upload_vectors(const float *vectors, int64_t n, int d, int64_t row_stride, void **dX, size_t *bytes);
+// ... into n zero-padded rows of an existing device table (rows of padded_stride(d) floats)
+int upload_rows(const float *vectors, int64_t n, int d, int64_t row_stride, float *dst);
 
 } // namespace hnsw_host
 
@@ -130,6 +132,10 @@ struct hnsw_index {
     int vt_grow_key = -1, vt_grow_bits = 0;   // knn_vt_bits' cached choice for (kernel variant, base size)
     int lds_pad = -1;                    // option "lds_pad": extra LDS bytes per search wave (-1 = balanced_lds_pad's choice)
     std::vector<std::pair<int, int>> prepared;   // (ef, accept rule) of every hnsw_index_prepare: what hnsw_index_save writes down
+    // what the options "byte_rows" / "split_rows" asked for, so that hnsw_index_insert, which makes the row copies again, keeps
+    // their effect: byte_rows 0, split_rows 0 (off), split_rows -1 (off and freed for good)
+    bool byte_rows_off = false, split_rows_off = false, split_rows_freed = false;
+    bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
 };
 
 namespace hnsw_host {
@@ -164,6 +170,10 @@ int build_locality_codes(::hnsw_index *idx);
 int materialise_lcode0(::hnsw_index *idx);
 void drop_lcode0(::hnsw_index *idx);
 int adopt_locality_codes(::hnsw_index *idx, const int32_t *codes);
+// hnsw_index_insert: the codes of `from` (n_old nodes) carried over to the grown `to`, whose new nodes v get code v (still a
+// permutation); the per-slot table is made again over to's rows if `from` had one.  Not enough memory is an error here
+// (HNSW_ERR_OOM): a handle whose kernel shapes run the bitmap blocks cannot go on without them.
+int extend_locality_codes(const ::hnsw_index *from, ::hnsw_index *to);
 
 // Longest-first ordering of a large batch (hnsw_order.hip): runs the descent kernel and a radix sort
 // on `st`; on success *block points to the handle's scratch for that stream (nothing to release)

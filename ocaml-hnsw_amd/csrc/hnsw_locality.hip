@@ -28,6 +28,13 @@ lcode0_fill_kernel(const int32_t *nbr0, const int32_t *lcode, int64_t total, int
     const int32_t v = nbr0[i];
     out[i] = v >= 0 ? lcode[v] : 0;
 }
+// codes of the nodes an insert appended: node v gets code v (the old codes are a permutation of [0, n_old), so the whole table
+// stays a permutation of [0, n))
+__global__ void __launch_bounds__(256)
+lcode_append_kernel(int32_t *lcode, int64_t n_old, int64_t n) {
+    const int64_t v = n_old + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n) lcode[v] = (int32_t)v;
+}
 } // namespace
 
 namespace hnsw_host {
@@ -181,6 +188,31 @@ int adopt_locality_codes(::hnsw_index *idx, const int32_t *codes) {
     idx->info.device_bytes += n * 4;
     idx->lcode_state = 1;
     return HNSW_OK;
+}
+
+// hnsw_index_insert: the old codes (a device copy), the appended nodes numbered after them; the per-slot table again if `from`
+// had one (the adjacency of old nodes changed, so from's table is stale)
+int extend_locality_codes(const ::hnsw_index *from, ::hnsw_index *to) {
+    if (from->lcode_state != 1 || !from->dLcode) return HNSW_OK;
+    HIP_TRY(hipSetDevice(to->device));
+    const int64_t n_old = from->iv.n, n = to->iv.n;
+    void *dL = nullptr;
+    HIP_TRY(hipMalloc(&dL, (size_t)std::max<int64_t>(n, 1) * 4));
+    hipError_t e = hipMemcpy(dL, from->dLcode, (size_t)n_old * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && n > n_old) {
+        hipLaunchKernelGGL(lcode_append_kernel, dim3((unsigned)((n - n_old + 255) / 256)), dim3(256), 0, nullptr, (int32_t *)dL, n_old, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { (void)hipFree(dL); return fail(HNSW_ERR_HIP, "extending the locality codes failed: %s", hipGetErrorString(e)); }
+    to->dLcode = dL;
+    to->iv.lcode = (const int32_t *)dL;
+    to->info.device_bytes += n * 4;
+    to->lcode_state = 1;
+    if (!from->dLcode0) return HNSW_OK;
+    int rc = materialise_lcode0(to);
+    if (rc == HNSW_OK && !to->dLcode0) rc = fail(HNSW_ERR_OOM, "no room for the per-slot locality codes of the grown index (%lld bytes)", (long long)n * to->iv.S0 * 4);
+    return rc;
 }
 
 } // namespace hnsw_host

@@ -285,6 +285,7 @@ int32_t hnsw_multi_create(const hnsw_index_desc *desc, const int32_t *devices, i
         hnsw_index *idx = nullptr;
         const int rc = hnsw_index_create(desc, devices[g], &idx);
         if (rc) { hnsw_multi_destroy(m); return rc; }   // the message of the failing create stays
+        idx->multi_replica = true;       // grown only together with the other replicas (hnsw_index_insert refuses it)
         m->replicas.push_back(idx);
         m->devices.push_back(devices[g]);
         for (int h = 0; h < g; ++h) if (devices[h] == devices[g]) m->distinct = false;

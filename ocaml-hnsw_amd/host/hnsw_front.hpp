@@ -1,7 +1,7 @@
 // hnsw_front.hpp -- C++ host-side mirror of the reference's module interface for the search path,
 // over the C ABI of include/hnsw_mi355x.h (header only; link with libhnsw_mi355x.so).
 //
-//   Hnsw::Ohnsw::knn / knn_batch_bigarray / build_batch_bigarray / distance_l2   lib/ohnsw.ml:840-899
+//   Hnsw::Ohnsw::knn / knn_batch_bigarray / build_batch_bigarray / insert / distance_l2   lib/ohnsw.ml:766-899
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
 //   Hnsw::MultiHgraph (one process, several GPUs)                                SURVEY 8e
@@ -127,6 +127,18 @@ inline Hgraph build_batch_bigarray(const Mat &batch, int num_connections, int nu
     hnsw_index *h = nullptr;
     check(hnsw_build(batch.data, batch.dim2, batch.dim1, batch.dim1, &p, device, &h));
     return Hgraph::adopt(h, 0, batch.dim1);
+}
+
+// Ohnsw.insert (lib/ohnsw.ml:766-837) for every vector of `batch`, in order, into g on the device (hnsw_index_insert): the
+// graph grows in place, the new ids follow the old ones.  Returns the first new id.  Levels are the draws
+// build_batch_bigarray with the same seed gives those positions.
+inline int64_t insert(Hgraph &g, const Mat &batch, int num_connections, int num_nodes_search_construction,
+                      uint64_t seed = 0, int max_batch = 0, int expected_ef = 0) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    hnsw_build_params p{num_connections, num_nodes_search_construction, inf.metric, inf.id_base, seed, max_batch, 0, expected_ef, HNSW_SEM_OHNSW};
+    check(hnsw_index_insert(g.handle(), batch.data, batch.dim2, batch.dim1, &p));
+    return inf.n + inf.id_base;
 }
 
 // Ohnsw.knn hgraph visited ~k target (lib/ohnsw.ml:859-875): the MinQueue popped ascending.

@@ -140,6 +140,9 @@ let () = seal build_params
 let hnsw_build =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_build"
     (ptr float @-> int64_t @-> int32_t @-> int64_t @-> ptr build_params @-> int32_t @-> ptr index @-> returning int32_t)
+let hnsw_index_insert =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_insert"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> ptr build_params @-> returning int32_t)
 let hnsw_index_save = foreign ~from:lib ~release_runtime_lock:true "hnsw_index_save" (index @-> string @-> returning int32_t)
 let hnsw_index_load =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_load" (string @-> int32_t @-> ptr index @-> returning int32_t)
@@ -748,6 +751,25 @@ let build ?(device = 0) ?(metric = 0) ?(seed = 0) ?(max_batch = 0) ?(batch_div =
   let t = { handle = !@out; k_base = id_base; dim; scratch = Hashtbl.create 4 } in
   Gc.finalise (fun t -> ignore (hnsw_index_destroy t.handle)) t;
   t
+
+(* Ohnsw.insert (lib/ohnsw.ml:766-837) for every column of [batch], in order, on the device (hnsw_index_insert), into an
+   index the device owns (from [build] or [load]); returns the first new id (the others follow).  Levels are the device RNG's
+   draws for those positions (the ones [build] with the same seed gives them), not OCaml's Random: an OCaml hgraph and a device
+   index grown by inserts are two graphs, not one mirrored.  An index made from an OCaml hgraph ([of_ohnsw] / [of_ba]) is not
+   grown here: the handle cache makes it again when the OCaml side inserts. *)
+let insert_batch t (batch : Lacaml.S.mat) ~num_connections ~num_nodes_search_construction ?(seed = 0) ?(max_batch = 0)
+    ?(batch_div = 0) ?(expected_ef = 0) ?(expected_semantics = 0) () : int =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  if A2.dim1 batch <> t.dim then invalid_arg "insert_batch: vectors of another dimension";
+  let b = make build_params in
+  setf b b_num_connections (Int32.of_int num_connections); setf b b_efc (Int32.of_int num_nodes_search_construction);
+  setf b b_metric (getf inf ii_metric); setf b b_id_base (getf inf ii_id_base);
+  setf b b_seed (Unsigned.UInt64.of_int seed); setf b b_max_batch (Int32.of_int max_batch);
+  setf b b_batch_div (Int32.of_int batch_div);
+  setf b b_expected_ef (Int32.of_int expected_ef); setf b b_expected_semantics (Int32.of_int expected_semantics);
+  check (hnsw_index_insert t.handle (bigarray_start array2 batch) (Int64.of_int (A2.dim2 batch)) (Int64.of_int t.dim) (addr b));
+  Int64.to_int (getf inf ii_n) + Int32.to_int (getf inf ii_id_base)
 
 (* flattened-index file (the reference has no persistence: lib/hnsw.ml:348, lib/ohnsw.ml:312 derive sexp with opaque values) *)
 let save (t : t) (path : string) = check (hnsw_index_save t.handle path)
