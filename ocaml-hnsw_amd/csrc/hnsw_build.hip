@@ -295,57 +295,33 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
     for (int64_t i = 0; i < n; ++i) lvl[(size_t)i] = node_level(p->seed, i, level_mult);
     int lcap = 1;
     for (int64_t i = 0; i < n; ++i) lcap = std::max(lcap, (int)lvl[(size_t)i] + 1);
-    std::vector<int32_t> off((size_t)n, -1);
-    int64_t rowsU = 0;
-    for (int64_t i = 0; i < n; ++i) if (lvl[(size_t)i]) { off[(size_t)i] = (int32_t)rowsU; rowsU += lvl[(size_t)i]; }
+    std::vector<int2> ref;
+    const int64_t rowsU = upper_layout(lvl.data(), n, 0, ref);
 
     hnsw_index *idx = new hnsw_index();
     idx->device = device;
     int rc = HNSW_OK;
     const int S0 = 2 * M, SU = M;
     const int64_t stride = padded_stride(d);
-    size_t xbytes = 0;
     BuildView bv{};
     int cur_max = 0, entry = 0;                 // node 0 is the first entry point
+    IndexView &iv = idx->iv;
 
-    if ((rc = upload_vectors(vectors, n, d, row_stride, &idx->dX, &xbytes))) goto done;
-    HIP_TRY_B(hipMalloc(&idx->dNbr0, (size_t)n * S0 * 4));
-    HIP_TRY_B(hipMemset(idx->dNbr0, 0xFF, (size_t)n * S0 * 4));
-    HIP_TRY_B(hipMalloc(&idx->dNbrU, (size_t)std::max<int64_t>(rowsU, 1) * SU * 4));
-    HIP_TRY_B(hipMemset(idx->dNbrU, 0xFF, (size_t)std::max<int64_t>(rowsU, 1) * SU * 4));
-    HIP_TRY_B(hipMalloc(&idx->dOff, (size_t)n * 4));
-    HIP_TRY_B(hipMemcpy(idx->dOff, off.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY_B(hipMalloc(&idx->dLvl, (size_t)n));
-    HIP_TRY_B(hipMemcpy(idx->dLvl, lvl.data(), (size_t)n, hipMemcpyHostToDevice));
-    if ((rc = upload_upper_ref(off.data(), lvl.data(), n, &idx->dRef))) goto done;
-    idx->rowsU = rowsU; idx->iv.rowsU = rowsU;
-    {
-        IndexView &iv = idx->iv;
-        iv.X = (const float *)idx->dX; iv.stride = stride; iv.n = n; iv.d = d; iv.nchunks = nchunks;
-        iv.nbr0 = (const int32_t *)idx->dNbr0; iv.S0 = S0; iv.SU = SU;
-        iv.nbrU = (const int32_t *)idx->dNbrU; iv.upper_off = (const int32_t *)idx->dOff;
-        iv.upper_lvl = (const uint8_t *)idx->dLvl; iv.upper_ref = (const int2 *)idx->dRef;
-        iv.max_layer = 0; iv.entry_point = 0; iv.id_base = p->id_base;
-    }
-    bv.iv = idx->iv; bv.nbr0_w = (int32_t *)idx->dNbr0; bv.nbrU_w = (int32_t *)idx->dNbrU;
+    if ((rc = alloc_graph_tables(idx->tables, n, stride, S0, SU, rowsU)) ||
+        (rc = upload_rows(vectors, n, d, row_stride, (float *)idx->tables.X.p)) || (rc = upload_upper_layout(idx->tables, 0, ref))) goto done;
+    iv.stride = stride; iv.n = n; iv.d = d; iv.nchunks = nchunks; iv.S0 = S0; iv.SU = SU; iv.rowsU = rowsU;
+    iv.max_layer = 0; iv.entry_point = 0; iv.id_base = p->id_base;
+    bind_view(idx);
+    bv.iv = iv; bv.nbr0_w = (int32_t *)idx->tables.nbr0.p; bv.nbrU_w = (int32_t *)idx->tables.nbrU.p;
     if ((rc = run_batches(bv, lvl.data() + 1, 1, n, lcap, p, rem_scale, rem_overflow, &cur_max, &entry))) goto done;
-
-    idx->iv.max_layer = cur_max; idx->iv.entry_point = entry;
+    iv.max_layer = cur_max; iv.entry_point = entry;
     {
         hnsw_index_info &inf = idx->info;
-        inf.n = n; inf.d = d; inf.metric = p->metric; inf.id_base = p->id_base; inf.max_degree0 = S0;
-        inf.max_degree = SU; inf.max_layer = cur_max; inf.entry_point = (int64_t)entry + p->id_base;
-        inf.device_bytes = (int64_t)(xbytes + (size_t)n * S0 * 4 + (size_t)std::max<int64_t>(rowsU, 1) * SU * 4 + (size_t)n * 13);
-        inf.row_stride_bytes = stride * 4; inf.device = device;
+        inf.d = d; inf.metric = p->metric; inf.id_base = p->id_base; inf.max_degree = SU; inf.device = device;
     }
 done:
-    if (!rc) rc = make_byte_rows(idx);      // the finished index serves searches from the byte copy where the data allows
-    if (!rc) rc = make_split_rows(idx);     // ... or from split rows where a row ends just past a 128-byte line
     if (rc) { hnsw_index_destroy(idx); return rc; }
-    (void)warm_up(idx);                     // ... and its first search call does not pay for the process's code loading (an optimisation:
-    prepare_quietly(idx, p->expected_ef, p->expected_semantics);      //  failures are left to the first search) nor for its shape's one-time decisions
-    *out = idx;
-    return HNSW_OK;
+    return finish_index(idx, p->expected_ef, p->expected_semantics, out);
 }
 
 namespace {
@@ -399,68 +375,45 @@ static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64
     const int64_t n_old = ov.n, n = n_old + m;
     const int M = p->num_connections, S0 = 2 * M, SU = M;
     const int S0o = ov.S0, SUo = ov.SU;
-    const int64_t stride = ov.stride, rowsU_old = n_old > 0 ? idx->rowsU : 0;
+    const int64_t stride = ov.stride, rowsU_old = n_old > 0 ? ov.rowsU : 0;
     const double level_mult = 1.0 / std::log((double)M);
     std::vector<uint8_t> lvl((size_t)m);
     for (int64_t j = 0; j < m; ++j) lvl[(size_t)j] = node_level(p->seed, n_old + j, level_mult);
     int cur_max = n_old > 0 ? ov.max_layer : 0, entry = n_old > 0 ? ov.entry_point : 0;
     int lcap = cur_max + 1;
     for (uint8_t l : lvl) lcap = std::max(lcap, (int)l + 1);
-    std::vector<int32_t> off((size_t)m, -1);
-    std::vector<int2> ref((size_t)m);
-    int64_t rowsU = rowsU_old;
-    for (int64_t j = 0; j < m; ++j) {
-        if (lvl[(size_t)j]) { off[(size_t)j] = (int32_t)rowsU; rowsU += lvl[(size_t)j]; }
-        ref[(size_t)j] = make_int2(off[(size_t)j], (int)lvl[(size_t)j]);
-    }
+    std::vector<int2> ref;
+    const int64_t rowsU = upper_layout(lvl.data(), m, rowsU_old, ref);
     if (rowsU > 0x7FFFFFF0LL) return fail(HNSW_ERR_UNSUPPORTED, "too many upper rows");
 
     hnsw_index *nx = new hnsw_index();
     nx->device = idx->device;
     int rc = HNSW_OK;
-    const size_t xbytes = (size_t)n * stride * 4;
+    const IndexTables &ot = idx->tables;
+    IndexTables &t = nx->tables;
+    IndexView &iv = nx->iv;
     BuildView bv{};
-    HIP_TRY_B(hipMalloc(&nx->dX, xbytes));
-    if (n_old > 0) HIP_TRY_B(hipMemcpy(nx->dX, idx->dX, (size_t)n_old * stride * 4, hipMemcpyDeviceToDevice));
-    if ((rc = upload_rows(vectors, m, ov.d, row_stride, (float *)nx->dX + n_old * stride))) goto done;
-    HIP_TRY_B(hipMalloc(&nx->dNbr0, (size_t)n * S0 * 4));
-    HIP_TRY_B(widen_rows(idx->dNbr0, n_old, S0o, nx->dNbr0, S0));
-    HIP_TRY_B(hipMemset((int32_t *)nx->dNbr0 + n_old * S0, 0xFF, (size_t)m * S0 * 4));
-    HIP_TRY_B(hipMalloc(&nx->dNbrU, (size_t)std::max<int64_t>(rowsU, 1) * SU * 4));
-    HIP_TRY_B(widen_rows(idx->dNbrU, rowsU_old, SUo, nx->dNbrU, SU));
-    HIP_TRY_B(hipMemset((int32_t *)nx->dNbrU + rowsU_old * SU, 0xFF, (size_t)(std::max<int64_t>(rowsU, 1) - rowsU_old) * SU * 4));
-    HIP_TRY_B(hipMalloc(&nx->dOff, (size_t)n * 4));
-    HIP_TRY_B(hipMalloc(&nx->dLvl, (size_t)n));
-    HIP_TRY_B(hipMalloc(&nx->dRef, (size_t)n * sizeof(int2)));
+    if ((rc = alloc_graph_tables(t, n, stride, S0, SU, rowsU))) goto done;
     if (n_old > 0) {
-        HIP_TRY_B(hipMemcpy(nx->dOff, idx->dOff, (size_t)n_old * 4, hipMemcpyDeviceToDevice));
-        HIP_TRY_B(hipMemcpy(nx->dLvl, idx->dLvl, (size_t)n_old, hipMemcpyDeviceToDevice));
-        HIP_TRY_B(hipMemcpy(nx->dRef, idx->dRef, (size_t)n_old * sizeof(int2), hipMemcpyDeviceToDevice));
+        HIP_TRY_B(hipMemcpy(t.X.p, ot.X.p, (size_t)n_old * stride * 4, hipMemcpyDeviceToDevice));
+        HIP_TRY_B(hipMemcpy(t.off.p, ot.off.p, (size_t)n_old * 4, hipMemcpyDeviceToDevice));
+        HIP_TRY_B(hipMemcpy(t.lvl.p, ot.lvl.p, (size_t)n_old, hipMemcpyDeviceToDevice));
+        HIP_TRY_B(hipMemcpy(t.ref.p, ot.ref.p, (size_t)n_old * sizeof(int2), hipMemcpyDeviceToDevice));
     }
-    HIP_TRY_B(hipMemcpy((int32_t *)nx->dOff + n_old, off.data(), (size_t)m * 4, hipMemcpyHostToDevice));
-    HIP_TRY_B(hipMemcpy((uint8_t *)nx->dLvl + n_old, lvl.data(), (size_t)m, hipMemcpyHostToDevice));
-    HIP_TRY_B(hipMemcpy((int2 *)nx->dRef + n_old, ref.data(), (size_t)m * sizeof(int2), hipMemcpyHostToDevice));
-    nx->rowsU = rowsU;
-    {
-        IndexView &iv = nx->iv;
-        iv = ov;                                                        // d, stride, nchunks, id_base
-        iv.X = (const float *)nx->dX; iv.n = n;
-        iv.nbr0 = (const int32_t *)nx->dNbr0; iv.S0 = S0; iv.SU = SU;
-        iv.nbrU = (const int32_t *)nx->dNbrU; iv.rowsU = rowsU; iv.upper_off = (const int32_t *)nx->dOff;
-        iv.upper_lvl = (const uint8_t *)nx->dLvl; iv.upper_ref = (const int2 *)nx->dRef;
-        iv.X8 = nullptr; iv.Xm = nullptr; iv.tail0 = nullptr; iv.lcode = nullptr; iv.lcode0 = nullptr;   // the caller's
-        iv.max_layer = cur_max; iv.entry_point = entry;
-    }
-    bv.iv = nx->iv; bv.nbr0_w = (int32_t *)nx->dNbr0; bv.nbrU_w = (int32_t *)nx->dNbrU;
+    if ((rc = upload_rows(vectors, m, ov.d, row_stride, (float *)t.X.p + n_old * stride))) goto done;
+    HIP_TRY_B(widen_rows(ot.nbr0.p, n_old, S0o, t.nbr0.p, S0));
+    HIP_TRY_B(widen_rows(ot.nbrU.p, rowsU_old, SUo, t.nbrU.p, SU));
+    if ((rc = upload_upper_layout(t, n_old, ref))) goto done;
+    iv = ov;                                                            // d, stride, nchunks, id_base
+    iv.n = n; iv.S0 = S0; iv.SU = SU; iv.rowsU = rowsU; iv.max_layer = cur_max; iv.entry_point = entry;
+    bind_view(nx);                                                      // (the derived tables are the caller's)
+    bv.iv = iv; bv.nbr0_w = (int32_t *)t.nbr0.p; bv.nbrU_w = (int32_t *)t.nbrU.p;
     if (n > 1 && (rc = run_batches(bv, lvl.data() + (n_old > 0 ? 0 : 1), std::max<int64_t>(n_old, 1), n, lcap, p, rem_scale,
                                    rem_overflow, &cur_max, &entry))) goto done;
-    nx->iv.max_layer = cur_max; nx->iv.entry_point = entry;
-    {
-        hnsw_index_info &inf = nx->info;
-        inf = idx->info;                                                // d, metric, id_base, row_stride_bytes, device
-        inf.n = n; inf.max_degree0 = S0; inf.max_degree = SU; inf.max_layer = cur_max; inf.entry_point = (int64_t)entry + ov.id_base;
-        inf.device_bytes = (int64_t)(xbytes + (size_t)n * S0 * 4 + (size_t)std::max<int64_t>(rowsU, 1) * SU * 4 + (size_t)n * 13);
-    }
+    iv.max_layer = cur_max; iv.entry_point = entry;
+    nx->info = idx->info;                                               // d, metric, id_base, device
+    nx->info.max_degree = SU;
+    bind_view(nx);
 done:
     if (rc) { hnsw_index_destroy(nx); return rc; }
     *out = nx;
@@ -546,17 +499,10 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
         if (e != hipSuccess) { hnsw_index_destroy(nx); return fail(HNSW_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); }
     }
     const bool bytes_before = idx->iv.X8 != nullptr, split_before = idx->iv.Xm != nullptr;
-    void **mine[] = {&idx->dX, &idx->dX8, &idx->dXm, &idx->dTail0, &idx->dLcode, &idx->dLcode0, &idx->dNbr0, &idx->dNbrU, &idx->dOff, &idx->dLvl, &idx->dRef};
-    void **theirs[] = {&nx->dX, &nx->dX8, &nx->dXm, &nx->dTail0, &nx->dLcode, &nx->dLcode0, &nx->dNbr0, &nx->dNbrU, &nx->dOff, &nx->dLvl, &nx->dRef};
-    for (size_t i = 0; i < sizeof mine / sizeof mine[0]; ++i) {
-        if (*mine[i]) (void)hipFree(*mine[i]);
-        *mine[i] = *theirs[i]; *theirs[i] = nullptr;
-    }
+    std::swap(idx->tables, nx->tables);                    // (nx takes the old tables with it)
     idx->iv = nx->iv;
-    if (idx->byte_rows_off) idx->iv.X8 = nullptr;          // the options keep their effect
-    if (idx->split_rows_off) idx->iv.Xm = nullptr;
     idx->info = nx->info;
-    idx->rowsU = nx->rowsU;
+    bind_view(idx);                                        // the options keep their effect
     idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
     hnsw_index_destroy(nx);
     // the per-shape choices that follow n or the row format
@@ -647,7 +593,7 @@ int32_t hnsw_index_export_layer0(const hnsw_index *idx, int32_t *deg0, int32_t *
     if (!idx || !deg0 || !nbr0) return fail(HNSW_ERR_BAD_ARG, "null argument");
     HIP_TRY(hipSetDevice(idx->device));
     const int64_t n = idx->iv.n; const int S0 = idx->iv.S0; const int base = idx->iv.id_base;
-    HIP_TRY(hipMemcpy(nbr0, idx->dNbr0, (size_t)n * S0 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nbr0, idx->tables.nbr0.p, (size_t)n * S0 * 4, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < n; ++i) {
         int w = 0;
         int32_t *row = nbr0 + i * S0;
@@ -663,7 +609,7 @@ int32_t hnsw_index_export_upper_count(const hnsw_index *idx, int32_t layer, int6
     if (layer < 1 || layer > idx->iv.max_layer) return fail(HNSW_ERR_BAD_ARG, "layer %d out of range", layer);
     HIP_TRY(hipSetDevice(idx->device));
     std::vector<uint8_t> lvl((size_t)idx->iv.n);
-    HIP_TRY(hipMemcpy(lvl.data(), idx->dLvl, (size_t)idx->iv.n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lvl.data(), idx->tables.lvl.p, (size_t)idx->iv.n, hipMemcpyDeviceToHost));
     int64_t c = 0;
     for (int64_t i = 0; i < idx->iv.n; ++i) c += lvl[(size_t)i] >= layer;
     *n_nodes = c;
@@ -676,10 +622,10 @@ int32_t hnsw_index_export_upper(const hnsw_index *idx, int32_t layer, int64_t *n
     HIP_TRY(hipSetDevice(idx->device));
     const int64_t n = idx->iv.n; const int SU = idx->iv.SU; const int base = idx->iv.id_base;
     std::vector<uint8_t> lvl((size_t)n);
-    std::vector<int32_t> off((size_t)n), rows((size_t)std::max<int64_t>(idx->rowsU, 1) * SU);
-    HIP_TRY(hipMemcpy(lvl.data(), idx->dLvl, (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(off.data(), idx->dOff, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rows.data(), idx->dNbrU, rows.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> off((size_t)n), rows((size_t)std::max<int64_t>(idx->iv.rowsU, 1) * SU);
+    HIP_TRY(hipMemcpy(lvl.data(), idx->tables.lvl.p, (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(off.data(), idx->tables.off.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rows.data(), idx->tables.nbrU.p, rows.size() * 4, hipMemcpyDeviceToHost));
     int64_t s = 0;
     for (int64_t i = 0; i < n; ++i) {
         if (lvl[(size_t)i] < layer) continue;
@@ -805,7 +751,7 @@ int32_t hnsw_index_save(const hnsw_index *idx, const char *path) {
         std::vector<float> stage((size_t)chunk * stride), packed((size_t)chunk * d);
         for (int64_t r0 = 0; ok && r0 < n; r0 += chunk) {
             const int64_t nr = std::min(chunk, n - r0);
-            if (hipMemcpy(stage.data(), (const float *)idx->dX + r0 * stride, (size_t)nr * stride * 4, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
+            if (hipMemcpy(stage.data(), (const float *)idx->tables.X.p + r0 * stride, (size_t)nr * stride * 4, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
             for (int64_t i = 0; i < nr; ++i) memcpy(&packed[(size_t)i * d], &stage[(size_t)i * stride], (size_t)d * 4);
             ok = wr(f, packed.data(), (size_t)nr * d * 4);
         }
@@ -829,11 +775,11 @@ int32_t hnsw_index_save(const hnsw_index *idx, const char *path) {
             for (size_t i = 0; i + 2 < dec.size(); i += 3) have = have || (dec[i] == pr.first && dec[i + 1] == (pr.second ? 1 : 0));
             if (!have) { dec.push_back(pr.first); dec.push_back(pr.second); dec.push_back(-1); }
         }
-        const uint32_t n_dec = (uint32_t)(dec.size() / 3), has_codes = idx->lcode_state == 1 && idx->dLcode ? 1u : 0u;
+        const uint32_t n_dec = (uint32_t)(dec.size() / 3), has_codes = idx->lcode_state == 1 && idx->tables.lcode.p ? 1u : 0u;
         ok = ok && wr(f, "PREP", 4) && wr(f, &n_dec, 4) && wr(f, dec.data(), dec.size() * 4) && wr(f, &has_codes, 4);
         if (ok && has_codes) {
             std::vector<int32_t> codes((size_t)n);
-            ok = hipMemcpy(codes.data(), idx->dLcode, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess && wr(f, codes.data(), (size_t)n * 4);
+            ok = hipMemcpy(codes.data(), idx->tables.lcode.p, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess && wr(f, codes.data(), (size_t)n * 4);
         }
     }
     ok = (fclose(f) == 0) && ok;

@@ -69,14 +69,6 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-int upload_vectors(const float *vectors, int64_t n, int d, int64_t row_stride, void **dX, size_t *bytes) {
-    const int64_t stride = padded_stride(d);
-    const size_t xbytes = (size_t)std::max<int64_t>(n, 1) * stride * sizeof(float);
-    *bytes = xbytes;
-    if (hipMalloc(dX, xbytes) != hipSuccess) { (void)hipGetLastError(); return fail(HNSW_ERR_OOM, "hipMalloc(%zu) for vectors failed", xbytes); }
-    return upload_rows(vectors, n, d, row_stride, (float *)*dX);
-}
-
 int upload_rows(const float *vectors, int64_t n, int d, int64_t row_stride, float *dst) {
     const int64_t stride = padded_stride(d);
     if (n == 0) return HNSW_OK;
@@ -97,11 +89,37 @@ int upload_rows(const float *vectors, int64_t n, int d, int64_t row_stride, floa
     return HNSW_OK;
 }
 
-int upload_upper_ref(const int32_t *off, const uint8_t *lvl, int64_t n, void **dRef) {
-    std::vector<int2> ref((size_t)std::max<int64_t>(n, 1));
-    for (int64_t i = 0; i < n; ++i) ref[(size_t)i] = make_int2(off[(size_t)i], (int)lvl[(size_t)i]);
-    if (hipMalloc(dRef, ref.size() * sizeof(int2)) != hipSuccess) { (void)hipGetLastError(); return fail(HNSW_ERR_OOM, "hipMalloc for the upper-row table failed"); }
-    if (hipMemcpy(*dRef, ref.data(), ref.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) return fail(HNSW_ERR_HIP, "upper-row table upload failed");
+int alloc_graph_tables(IndexTables &t, int64_t n, int64_t stride, int S0, int SU, int64_t rowsU) {
+    const size_t n1 = (size_t)std::max<int64_t>(n, 1), nbr0_bytes = (size_t)n * S0 * 4, nbrU_bytes = (size_t)std::max<int64_t>(rowsU, 1) * SU * 4;
+    HIP_TRY(t.X.alloc(n1 * stride * sizeof(float)));
+    HIP_TRY(t.nbr0.alloc(nbr0_bytes));
+    HIP_TRY(hipMemset(t.nbr0.p, 0xFF, nbr0_bytes));
+    HIP_TRY(t.nbrU.alloc(nbrU_bytes));
+    HIP_TRY(hipMemset(t.nbrU.p, 0xFF, nbrU_bytes));
+    HIP_TRY(t.off.alloc(n1 * 4));
+    HIP_TRY(t.lvl.alloc(n1));
+    HIP_TRY(t.ref.alloc(n1 * sizeof(int2)));
+    return HNSW_OK;
+}
+
+int64_t upper_layout(const uint8_t *lvl, int64_t m, int64_t row0, std::vector<int2> &ref) {
+    ref.resize((size_t)m);
+    int64_t rows = row0;
+    for (int64_t j = 0; j < m; ++j) {
+        ref[(size_t)j] = make_int2(lvl[j] ? (int32_t)rows : -1, (int)lvl[j]);
+        rows += lvl[j];
+    }
+    return rows;
+}
+
+int upload_upper_layout(IndexTables &t, int64_t n0, const std::vector<int2> &ref) {
+    const size_t m = ref.size();
+    std::vector<int32_t> off(m);
+    std::vector<uint8_t> lvl(m);
+    for (size_t j = 0; j < m; ++j) { off[j] = ref[j].x; lvl[j] = (uint8_t)ref[j].y; }
+    HIP_TRY(hipMemcpy((int32_t *)t.off.p + n0, off.data(), m * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((uint8_t *)t.lvl.p + n0, lvl.data(), m, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((int2 *)t.ref.p + n0, ref.data(), m * sizeof(int2), hipMemcpyHostToDevice));
     return HNSW_OK;
 }
 
@@ -210,7 +228,7 @@ int launch_search_args(hnsw_index *idx, SearchArgs &a, hipStream_t st);
 // re-makes the table with one fill kernel instead of the whole build.  Only called with the device idle (the measurement
 // synchronises; nothing in flight reads the table when no shape has chosen it).
 void release_unused_lcode0(hnsw_index *idx) {
-    if (!idx->dLcode0) return;
+    if (!idx->tables.lcode0.p) return;
     const int mode = idx->blk_mode >= 0 ? idx->blk_mode : env_int("HNSW_VISITED_BLOCKS", -1);
     if (mode == 1) return;                   // the caller asked for blocks wherever they can run: keep the table
     for (auto &c : idx->blk_choice) if (c[0] > 0 || c[1] > 0) return;
@@ -259,7 +277,7 @@ int knn_blk_bits(hnsw_index *idx, int ef, int semf) {
     if (choice >= 0) return choice;
     const int bits = blk_capacity_bits(idx, ef, semf), vt = knn_vt_bits(idx, ef, semf);
     if (bits == 0) return choice = 0;
-    if (build_locality_codes(idx) != HNSW_OK || idx->lcode_state != 1 || !idx->dLcode0) return choice = 0;
+    if (build_locality_codes(idx) != HNSW_OK || idx->lcode_state != 1 || !idx->tables.lcode0.p) return choice = 0;
     if (mode == 1) return choice = bits;
     // measure: 256 probe queries -- the midpoint between every (n / 256)-th vector of the index and its first layer-0 neighbour:
     // where queries of the data's own distribution fall, without being stored vectors themselves (a stored vector finds itself
@@ -439,7 +457,7 @@ static int warm_up_steps(hnsw_index *idx) {
     const int mode = idx->order_mode;
     for (int ordered = 0; ordered < 2 && !rc; ++ordered) {
         idx->order_mode = ordered;
-        rc = search_batch_device_flag(idx, (const float *)idx->dX, 1, idx->iv.stride, &p, (int32_t *)out.p, (float *)out.p + 1,
+        rc = search_batch_device_flag(idx, idx->iv.X, 1, idx->iv.stride, &p, (int32_t *)out.p, (float *)out.p + 1,
                                       nullptr, nullptr, (uint32_t *)out.p + 2, nullptr, idx->hs[0]);
     }
     idx->order_mode = mode;
@@ -447,6 +465,32 @@ static int warm_up_steps(hnsw_index *idx) {
     out.release();
     if (!rc && e != hipSuccess) rc = fail(HNSW_ERR_HIP, "warm-up search failed: %s", hipGetErrorString(e));
     return rc;
+}
+
+void bind_view(hnsw_index *idx) {
+    const IndexTables &t = idx->tables;
+    IndexView &iv = idx->iv;
+    iv.X = (const float *)t.X.p;
+    iv.X8 = idx->byte_rows_off ? nullptr : (const uint8_t *)t.X8.p;
+    iv.Xm = idx->split_rows_off ? nullptr : (const float *)t.Xm.p;
+    iv.tail0 = (const float *)t.tail0.p;
+    iv.nbr0 = (const int32_t *)t.nbr0.p; iv.nbrU = (const int32_t *)t.nbrU.p;
+    iv.upper_off = (const int32_t *)t.off.p; iv.upper_lvl = (const uint8_t *)t.lvl.p; iv.upper_ref = (const int2 *)t.ref.p;
+    iv.lcode = (const int32_t *)t.lcode.p; iv.lcode0 = (const int32_t *)t.lcode0.p;
+    hnsw_index_info &inf = idx->info;
+    inf.n = iv.n; inf.max_degree0 = iv.S0; inf.max_layer = iv.max_layer; inf.entry_point = (int64_t)iv.entry_point + iv.id_base;
+    inf.row_stride_bytes = iv.stride * 4;
+}
+
+int finish_index(hnsw_index *idx, int32_t expected_ef, int32_t expected_semantics, hnsw_index **out) {
+    bind_view(idx);
+    int rc = make_byte_rows(idx);           // the index serves searches from the byte copy where the data allows
+    if (!rc) rc = make_split_rows(idx);     // ... or from split rows where a row ends just past a 128-byte line
+    if (rc) { hnsw_index_destroy(idx); return rc; }
+    (void)warm_up(idx);                     // ... and its first search call does not pay for the process's code loading (an optimisation:
+    prepare_quietly(idx, expected_ef, expected_semantics);      //  failures are left to the first search) nor for its shape's one-time decisions
+    *out = idx;
+    return HNSW_OK;
 }
 } // namespace hnsw_host
 
@@ -514,9 +558,8 @@ int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index *
             lvl[(size_t)v] = (uint8_t)std::max<int>(lvl[(size_t)v], l);
         }
     }
-    std::vector<int32_t> off((size_t)std::max<int64_t>(n, 1), -1);
-    int64_t rowsU = 0;
-    for (int64_t i = 0; i < n; ++i) if (lvl[(size_t)i]) { off[(size_t)i] = (int32_t)rowsU; rowsU += lvl[(size_t)i]; }
+    std::vector<int2> ref;
+    const int64_t rowsU = upper_layout(lvl.data(), (int64_t)lvl.size(), 0, ref);
     if (rowsU > 0x7FFFFFF0LL) return fail(HNSW_ERR_UNSUPPORTED, "too many upper rows");
     std::vector<int32_t> nbrU((size_t)std::max<int64_t>(rowsU, 1) * SU, -1);
     for (int l = 1; l <= d->max_layer; ++l) {
@@ -526,7 +569,7 @@ int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index *
             const int dg = L.deg[s];
             if (dg < 0) return fail(HNSW_ERR_BAD_ARG, "layer %d: negative degree", l);
             if (dg > SU) return fail(HNSW_ERR_DEGREE_OVERFLOW, "node %lld has %d neighbours on layer %d > max_degree=%d", (long long)v + base, dg, l, SU);
-            int32_t *row = &nbrU[((size_t)off[(size_t)v] + (l - 1)) * SU];
+            int32_t *row = &nbrU[((size_t)ref[(size_t)v].x + (l - 1)) * SU];
             for (int j = 0; j < dg; ++j) {
                 const int64_t u = (int64_t)L.nbr[s * SU + j] - base;
                 if (u < 0 || u >= n) return fail(HNSW_ERR_BAD_ARG, "layer %d: neighbour id out of range", l);
@@ -538,54 +581,32 @@ int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index *
     HIP_TRY(hipSetDevice(device));
     hnsw_index *idx = new hnsw_index();
     idx->device = device;
-    auto bail = [&](int code) { hnsw_index_destroy(idx); return code; };
-
+    IndexTables &t = idx->tables;
     // ---- vectors: rows zero-padded to a multiple of 64 B so every float4 chunk is in bounds ----
     const int64_t stride = padded_stride(d->d);
-    size_t xbytes = 0;
-    { int rcv = upload_vectors(d->vectors, n, d->d, d->row_stride, &idx->dX, &xbytes); if (rcv) return bail(rcv); }
-    auto upload = [&](void **dst, const void *src, size_t bytes) -> bool {
-        if (hipMalloc(dst, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
-        return bytes == 0 || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!upload(&idx->dNbr0, nbr0.data(), nbr0.size() * 4) || !upload(&idx->dNbrU, nbrU.data(), nbrU.size() * 4) ||
-        !upload(&idx->dOff, off.data(), off.size() * 4) || !upload(&idx->dLvl, lvl.data(), lvl.size())) {
-        (void)hipGetLastError();
-        return bail(fail(HNSW_ERR_OOM, "graph upload failed"));
-    }
-
-    { int rcr = upload_upper_ref(off.data(), lvl.data(), n, &idx->dRef); if (rcr) return bail(rcr); }
+    int rc = alloc_graph_tables(t, n, stride, S0, SU, rowsU);
+    if (!rc) rc = upload_rows(d->vectors, n, d->d, d->row_stride, (float *)t.X.p);
+    if (!rc && hipMemcpy(t.nbr0.p, nbr0.data(), nbr0.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNSW_ERR_OOM, "graph upload failed");
+    if (!rc && hipMemcpy(t.nbrU.p, nbrU.data(), nbrU.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNSW_ERR_OOM, "graph upload failed");
+    if (!rc) rc = upload_upper_layout(t, 0, ref);
+    if (rc) { hnsw_index_destroy(idx); return rc; }
     IndexView &iv = idx->iv;
-    iv.upper_ref = (const int2 *)idx->dRef;
-    iv.X = (const float *)idx->dX; iv.stride = stride; iv.n = n; iv.d = d->d; iv.nchunks = nchunks;
-    iv.nbr0 = (const int32_t *)idx->dNbr0; iv.S0 = S0; iv.SU = SU;
-    iv.nbrU = (const int32_t *)idx->dNbrU; iv.upper_off = (const int32_t *)idx->dOff;
-    iv.upper_lvl = (const uint8_t *)idx->dLvl;
+    iv.stride = stride; iv.n = n; iv.d = d->d; iv.nchunks = nchunks; iv.S0 = S0; iv.SU = SU; iv.rowsU = rowsU;
     iv.max_layer = d->max_layer; iv.entry_point = (int32_t)ep; iv.id_base = base;
-    idx->rowsU = rowsU; iv.rowsU = rowsU;
-
     hnsw_index_info &inf = idx->info;
-    inf.n = n; inf.d = d->d; inf.metric = d->metric; inf.id_base = base; inf.max_degree0 = S0;
-    inf.max_degree = d->max_degree; inf.max_layer = d->max_layer; inf.entry_point = ep < 0 ? base - 1 : ep + base;
-    inf.device_bytes = (int64_t)(xbytes + nbr0.size() * 4 + nbrU.size() * 4 + off.size() * 12 + lvl.size());
-    inf.row_stride_bytes = stride * 4; inf.device = device;
-    { int rc8 = make_byte_rows(idx); if (rc8) return bail(rc8); }
-    { int rcs = make_split_rows(idx); if (rcs) return bail(rcs); }
-    (void)warm_up(idx);      // an optimisation: whatever fails in it is left to the first search call
-    prepare_quietly(idx, d->expected_ef, d->expected_semantics);
-    *out = idx;
-    return HNSW_OK;
+    inf.d = d->d; inf.metric = d->metric; inf.id_base = base; inf.max_degree = d->max_degree; inf.device = device;
+    return finish_index(idx, d->expected_ef, d->expected_semantics, out);
 }
 
 int32_t hnsw_index_destroy(hnsw_index *idx) {
     if (!idx) return HNSW_OK;
     if (idx->device >= 0) (void)hipSetDevice(idx->device);
-    for (void *p : {idx->dX, idx->dX8, idx->dXm, idx->dTail0, idx->dLcode, idx->dLcode0, idx->dNbr0, idx->dNbrU, idx->dOff, idx->dLvl, idx->dRef}) if (p) (void)hipFree(p);
+    idx->tables.release();
     idx->dFbSlab.release(); idx->dFbMap.release();
-    idx->sQ.release(); idx->sIds.release(); idx->sDist.release(); idx->sNd.release(); idx->sNh.release(); idx->sSt.release(); idx->sFlag.release();
+    idx->scratch.release();
     (void)hipDeviceSynchronize();                      // requests never waited for
     for (hnsw_request *r : idx->all_requests) {
-        r->q.release(); r->ids.release(); r->dist.release(); r->nd.release(); r->nh.release(); r->st.release(); r->flag.release();
+        r->buf.release();
         delete r;
     }
     for (hipStream_t st : idx->hs) if (st) (void)hipStreamDestroy(st);
@@ -600,6 +621,7 @@ int32_t hnsw_index_destroy(hnsw_index *idx) {
 int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info) {
     if (!idx || !info) return fail(HNSW_ERR_BAD_ARG, "null argument");
     *info = idx->info;
+    info->device_bytes = (int64_t)idx->tables.bytes();
     info->row_format = idx->iv.X8 ? HNSW_ROWS_BYTES : idx->iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
     return HNSW_OK;
 }
@@ -609,7 +631,7 @@ int32_t hnsw_index_locality_codes(hnsw_index *idx, int32_t *out) {
     int rc = build_locality_codes(idx);
     if (rc) return rc;
     if (idx->lcode_state != 1) return fail(HNSW_ERR_UNSUPPORTED, "no locality codes: the index has no upper layer (or no room for the tables)");
-    HIP_TRY(hipMemcpy(out, idx->dLcode, (size_t)idx->iv.n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, idx->tables.lcode.p, (size_t)idx->iv.n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipDeviceSynchronize());
     release_unused_lcode0(idx);              // introspection needs the per-node codes only
     return HNSW_OK;
@@ -640,7 +662,7 @@ int32_t hnsw_index_prepare(hnsw_index *idx, const hnsw_search_params *params) {
     const int mode = idx->order_mode;
     for (int ordered = 0; ordered < 2 && !rc; ++ordered) {
         idx->order_mode = ordered;
-        rc = search_batch_device_flag(idx, (const float *)idx->dX, 1, idx->iv.stride, &p, (int32_t *)out.p, (float *)out.p + 1,
+        rc = search_batch_device_flag(idx, idx->iv.X, 1, idx->iv.stride, &p, (int32_t *)out.p, (float *)out.p + 1,
                                       nullptr, nullptr, (uint32_t *)out.p + 2, nullptr, idx->hs[0]);
     }
     idx->order_mode = mode;
@@ -667,7 +689,7 @@ void adopt_blk_choice(hnsw_index *idx, int32_t ef, int32_t semantics, bool block
     const int semf = semantics ? 1 : 0, nslot = pick_nslot_knn(ef, pick_nch(idx->iv.nchunks));
     if (nslot < 3 || idx->blk_choice[slot_class(nslot)][semf] >= 0) return;
     int bits = 0;
-    if (blocks && idx->lcode_state == 1 && (bits = blk_capacity_bits(idx, ef, semf)) > 0 && materialise_lcode0(idx) == HNSW_OK && idx->dLcode0) {
+    if (blocks && idx->lcode_state == 1 && (bits = blk_capacity_bits(idx, ef, semf)) > 0 && materialise_lcode0(idx) == HNSW_OK && idx->tables.lcode0.p) {
         idx->blk_choice[slot_class(nslot)][semf] = bits;
         return;
     }
@@ -703,22 +725,20 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     if (!strcmp(name, "vt_bits")) { idx->vt_bits_override = (int)value; forget_shape_choices(); return HNSW_OK; }
     if (!strcmp(name, "lds_pad")) { idx->lds_pad = value < 0 ? -1 : (int)std::min<int64_t>(value, 32768); return HNSW_OK; }
     if (!strcmp(name, "byte_rows")) {     // 0: search the fp32 rows even where a byte copy exists; otherwise: use it where it exists
-        idx->iv.X8 = value != 0 ? (const uint8_t *)idx->dX8 : nullptr;
         idx->byte_rows_off = value == 0;
+        bind_view(idx);
         forget_shape_choices();
         return HNSW_OK;
     }
     if (!strcmp(name, "split_rows")) {    // 0: search the plain fp32 rows even where a split copy exists; -1: ... and free the copy; otherwise: use it where it exists
-        if (value < 0 && idx->dXm) {
+        if (value < 0 && idx->tables.Xm.p) {
             HIP_TRY(hipSetDevice(idx->device));
             HIP_TRY(hipDeviceSynchronize());             // launches that still read the copy
-            idx->info.device_bytes -= idx->iv.n * idx->iv.stride_m + idx->iv.n * idx->iv.S0 * 16 * idx->iv.tail_chunks;
-            (void)hipFree(idx->dXm); (void)hipFree(idx->dTail0);
-            idx->dXm = nullptr; idx->dTail0 = nullptr; idx->iv.tail0 = nullptr;
+            idx->tables.Xm.release(); idx->tables.tail0.release();
         }
-        idx->iv.Xm = value > 0 ? (const float *)idx->dXm : nullptr;
         idx->split_rows_off = value <= 0;
         idx->split_rows_freed = idx->split_rows_freed || value < 0;
+        bind_view(idx);
         forget_shape_choices();
         return HNSW_OK;
     }
@@ -887,10 +907,7 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
     HIP_TRY(hipSetDevice(idx->device));
     const int k = params->k;
     const size_t qbytes = ((size_t)(nq - 1) * q_stride + idx->iv.d) * sizeof(float);
-    if ((rc = idx->sQ.ensure(qbytes)) || (rc = idx->sIds.ensure((size_t)nq * k * 4)) ||
-        (rc = idx->sDist.ensure((size_t)nq * k * 4)) || (rc = idx->sNd.ensure((size_t)nq * 4)) ||
-        (rc = idx->sNh.ensure((size_t)nq * 4)) || (rc = idx->sSt.ensure((size_t)nq * 4)) || (rc = idx->sFlag.ensure(16)))
-        return rc;
+    if ((rc = idx->scratch.ensure(nq, qbytes, k))) return rc;
     // Upload, search (ordered longest walk first when the batch is larger than the chip holds) and download on one
     // of the handle's streams, ONE stream synchronisation at the end.
     //
@@ -939,22 +956,22 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
         if (out_ndist) memcpy(out_ndist, idx->hSmall + 3 * SMALL, (size_t)nq * 4);
         if (out_nhops) memcpy(out_nhops, idx->hSmall + 4 * SMALL, (size_t)nq * 4);
     };
-    const float *dQ = zq ? zq : (const float *)idx->sQ.p;            // where the queries can be read from the device
-    int32_t *dI = zi ? zi : (int32_t *)idx->sIds.p;
-    float *dD = zi ? zd : (float *)idx->sDist.p;
-    uint32_t *dNd = znd ? znd : (uint32_t *)idx->sNd.p, *dNh = znh ? znh : (uint32_t *)idx->sNh.p;
+    const float *dQ = zq ? zq : (const float *)idx->scratch.q.p;            // where the queries can be read from the device
+    int32_t *dI = zi ? zi : (int32_t *)idx->scratch.ids.p;
+    float *dD = zi ? zd : (float *)idx->scratch.dist.p;
+    uint32_t *dNd = znd ? znd : (uint32_t *)idx->scratch.nd.p, *dNh = znh ? znh : (uint32_t *)idx->scratch.nh.p;
     *(volatile uint32_t *)idx->hFlag = 0;
-    if (!zq) HIP_TRY(hipMemcpyAsync(idx->sQ.p, queries, qbytes, hipMemcpyHostToDevice, st));
-    rc = search_batch_device_flag(idx, dQ, nq, q_stride, params, dI, dD, dNd, dNh, (uint32_t *)idx->sSt.p, idx->hFlagDev, st,
-                                  zq ? (float *)idx->sQ.p : nullptr);
+    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
+    rc = search_batch_device_flag(idx, dQ, nq, q_stride, params, dI, dD, dNd, dNh, (uint32_t *)idx->scratch.st.p, idx->hFlagDev, st,
+                                  zq ? (float *)idx->scratch.q.p : nullptr);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     auto copy_out = [&](hipStream_t s_) -> int {
         if (!zi) {
-            HIP_TRY(hipMemcpyAsync(out_ids, idx->sIds.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s_));
-            HIP_TRY(hipMemcpyAsync(out_dist, idx->sDist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s_));
+            HIP_TRY(hipMemcpyAsync(out_ids, idx->scratch.ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s_));
+            HIP_TRY(hipMemcpyAsync(out_dist, idx->scratch.dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s_));
         }
-        if (out_ndist && !znd) HIP_TRY(hipMemcpyAsync(out_ndist, idx->sNd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s_));
-        if (out_nhops && !znh) HIP_TRY(hipMemcpyAsync(out_nhops, idx->sNh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s_));
+        if (out_ndist && !znd) HIP_TRY(hipMemcpyAsync(out_ndist, idx->scratch.nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s_));
+        if (out_nhops && !znh) HIP_TRY(hipMemcpyAsync(out_nhops, idx->scratch.nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s_));
         return HNSW_OK;
     };
     rc = copy_out(st);
@@ -967,9 +984,9 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
     // Exactness fallback for queries whose tie-overflow stack outgrew its LDS slots (rare: the rows
     // of the whole batch are then copied out again)
     int64_t n_rerun = 0;
-    rc = rerun_overflowed(idx, nq, (const uint32_t *)idx->sSt.p,
+    rc = rerun_overflowed(idx, nq, (const uint32_t *)idx->scratch.st.p,
                           [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
-                              return search_rerun_device(idx, dQ, nq, q_stride, params, dI, dD, dNd, dNh, (uint32_t *)idx->sSt.p,
+                              return search_rerun_device(idx, dQ, nq, q_stride, params, dI, dD, dNd, dNh, (uint32_t *)idx->scratch.st.p,
                                                          qmap, c, slab, cap, nullptr);
                           }, &n_rerun);
     if (rc) return rc;
@@ -993,13 +1010,13 @@ int32_t hnsw_search_batch_h2d(hnsw_index *idx, const float *queries, int64_t nq,
     if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
     HIP_TRY(hipSetDevice(idx->device));
     const size_t qbytes = ((size_t)(nq - 1) * q_stride + idx->iv.d) * sizeof(float);
-    if ((rc = idx->sQ.ensure(qbytes))) return rc;
+    if ((rc = idx->scratch.q.ensure(qbytes))) return rc;
     static const int zero_copy = env_int("HNSW_ZERO_COPY", 1);
     const float *zq = zero_copy ? (const float *)registered_device_address(queries, qbytes) : nullptr;
-    if (!zq) HIP_TRY(hipMemcpyAsync(idx->sQ.p, queries, qbytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, (hipStream_t)stream));
     // registered matrix: read by the device directly, the pre-pass (when there is one) leaves the device copy in sQ
-    rc = search_batch_device_flag(idx, zq ? zq : (const float *)idx->sQ.p, nq, q_stride, params, d_ids, d_dist, d_ndist, d_nhops, d_status,
-                                  nullptr, stream, zq ? (float *)idx->sQ.p : nullptr);
+    rc = search_batch_device_flag(idx, zq ? zq : (const float *)idx->scratch.q.p, nq, q_stride, params, d_ids, d_dist, d_ndist, d_nhops, d_status,
+                                  nullptr, stream, zq ? (float *)idx->scratch.q.p : nullptr);
     // the call returns while the device still reads the caller's matrix (in place, or as the source of the DMA above): the
     // range remembers it, so that hnsw_host_unregister / hnsw_host_free wait instead of pulling the pages from under a kernel
     range_reader_enqueued(queries, qbytes, (hipStream_t)stream);
@@ -1025,17 +1042,14 @@ int32_t hnsw_search_submit(hnsw_index *idx, const float *queries, int64_t nq, in
         return give_back(fail(HNSW_ERR_HIP, "hipStreamCreate failed"));
     const int k = params->k;
     const size_t qbytes = ((size_t)(nq - 1) * q_stride + idx->iv.d) * sizeof(float);
-    if ((rc = r->q.ensure(qbytes)) || (rc = r->ids.ensure((size_t)nq * k * 4)) || (rc = r->dist.ensure((size_t)nq * k * 4)) ||
-        (rc = r->nd.ensure((size_t)nq * 4)) || (rc = r->nh.ensure((size_t)nq * 4)) || (rc = r->st.ensure((size_t)nq * 4)) ||
-        (rc = r->flag.ensure(16)))
-        return give_back(rc);
+    if ((rc = r->buf.ensure(nq, qbytes, k))) return give_back(rc);
     hipStream_t st = idx->hs[r->stream];
-    if (hipMemcpyAsync(r->q.p, queries, qbytes, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemcpyAsync(r->buf.q.p, queries, qbytes, hipMemcpyHostToDevice, st) != hipSuccess)
         return give_back(fail(HNSW_ERR_HIP, "query upload failed"));
     range_reader_enqueued(queries, qbytes, st);    // page-locked source: the DMA above outlives this call (see hnsw_host_unregister)
-    if (hipMemsetAsync(r->flag.p, 0, 4, st) != hipSuccess) return give_back(fail(HNSW_ERR_HIP, "hipMemsetAsync failed"));
-    rc = search_batch_device_flag(idx, (const float *)r->q.p, nq, q_stride, params, (int32_t *)r->ids.p, (float *)r->dist.p,
-                                  (uint32_t *)r->nd.p, (uint32_t *)r->nh.p, (uint32_t *)r->st.p, (uint32_t *)r->flag.p, st);
+    if (hipMemsetAsync(r->buf.flag.p, 0, 4, st) != hipSuccess) return give_back(fail(HNSW_ERR_HIP, "hipMemsetAsync failed"));
+    rc = search_batch_device_flag(idx, (const float *)r->buf.q.p, nq, q_stride, params, (int32_t *)r->buf.ids.p, (float *)r->buf.dist.p,
+                                  (uint32_t *)r->buf.nd.p, (uint32_t *)r->buf.nh.p, (uint32_t *)r->buf.st.p, (uint32_t *)r->buf.flag.p, st);
     if (rc) return give_back(rc);
     // the results follow the search on the request's stream: hnsw_search_wait only has to wait for them
     r->host_flag = 0;
@@ -1056,11 +1070,11 @@ int32_t hnsw_search_wait(hnsw_request *r, int32_t *out_ids, float *out_dist, uin
     // results and the "any query flagged" word in one go; the exactness fallback (as in hnsw_search_batch) only if set
     uint32_t flag = 0;
     {
-        hipError_t e0 = hipMemcpyAsync(out_ids, r->ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
-        if (e0 == hipSuccess) e0 = hipMemcpyAsync(out_dist, r->dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
-        if (e0 == hipSuccess && out_ndist) e0 = hipMemcpyAsync(out_ndist, r->nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-        if (e0 == hipSuccess && out_nhops) e0 = hipMemcpyAsync(out_nhops, r->nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-        if (e0 == hipSuccess) e0 = hipMemcpyAsync(&flag, r->flag.p, 4, hipMemcpyDeviceToHost, st);
+        hipError_t e0 = hipMemcpyAsync(out_ids, r->buf.ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
+        if (e0 == hipSuccess) e0 = hipMemcpyAsync(out_dist, r->buf.dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
+        if (e0 == hipSuccess && out_ndist) e0 = hipMemcpyAsync(out_ndist, r->buf.nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+        if (e0 == hipSuccess && out_nhops) e0 = hipMemcpyAsync(out_nhops, r->buf.nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+        if (e0 == hipSuccess) e0 = hipMemcpyAsync(&flag, r->buf.flag.p, 4, hipMemcpyDeviceToHost, st);
         // synchronise whatever happened: copies already queued target the caller's arrays and `flag` (a stack word),
         // and the request goes back to the pool only once its stream is idle
         const hipError_t es = hipStreamSynchronize(st);
@@ -1068,17 +1082,17 @@ int32_t hnsw_search_wait(hnsw_request *r, int32_t *out_ids, float *out_dist, uin
         if (e0 != hipSuccess) return done(fail(HNSW_ERR_HIP, "search failed: %s", hipGetErrorString(e0)));
     }
     if (!(flag & 1u)) return done(HNSW_OK);
-    int rc = rerun_overflowed(idx, nq, (const uint32_t *)r->st.p,
+    int rc = rerun_overflowed(idx, nq, (const uint32_t *)r->buf.st.p,
                               [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
-                                  return search_rerun_device(idx, (const float *)r->q.p, nq, r->q_stride, &r->params, (int32_t *)r->ids.p,
-                                                             (float *)r->dist.p, (uint32_t *)r->nd.p, (uint32_t *)r->nh.p, (uint32_t *)r->st.p,
+                                  return search_rerun_device(idx, (const float *)r->buf.q.p, nq, r->q_stride, &r->params, (int32_t *)r->buf.ids.p,
+                                                             (float *)r->buf.dist.p, (uint32_t *)r->buf.nd.p, (uint32_t *)r->buf.nh.p, (uint32_t *)r->buf.st.p,
                                                              qmap, c, slab, cap, st);
                               });
     if (rc) return done(rc);
-    hipError_t e = hipMemcpyAsync(out_ids, r->ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_dist, r->dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out_ndist) e = hipMemcpyAsync(out_ndist, r->nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out_nhops) e = hipMemcpyAsync(out_nhops, r->nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(out_ids, r->buf.ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_dist, r->buf.dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && out_ndist) e = hipMemcpyAsync(out_ndist, r->buf.nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && out_nhops) e = hipMemcpyAsync(out_nhops, r->buf.nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
     { const hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess) e = es; }
     if (e != hipSuccess) return done(fail(HNSW_ERR_HIP, "result download failed: %s", hipGetErrorString(e)));
     return done(HNSW_OK);
@@ -1240,13 +1254,13 @@ int32_t hnsw_distance_batch(hnsw_index *idx, const float *queries, int64_t nq, i
     HIP_TRY(hipSetDevice(idx->device));
     int rc;
     const size_t qbytes = ((size_t)(nq - 1) * q_stride + idx->iv.d) * sizeof(float);
-    if ((rc = idx->sQ.ensure(qbytes)) || (rc = idx->sIds.ensure((size_t)nq * m * 4)) || (rc = idx->sDist.ensure((size_t)nq * m * 4))) return rc;
-    HIP_TRY(hipMemcpy(idx->sQ.p, queries, qbytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(idx->sIds.p, ids, (size_t)nq * m * 4, hipMemcpyHostToDevice));
-    rc = hnsw_distance_batch_device(idx, (const float *)idx->sQ.p, nq, q_stride, (const int32_t *)idx->sIds.p, m, (float *)idx->sDist.p, nullptr);
+    if ((rc = idx->scratch.q.ensure(qbytes)) || (rc = idx->scratch.ids.ensure((size_t)nq * m * 4)) || (rc = idx->scratch.dist.ensure((size_t)nq * m * 4))) return rc;
+    HIP_TRY(hipMemcpy(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(idx->scratch.ids.p, ids, (size_t)nq * m * 4, hipMemcpyHostToDevice));
+    rc = hnsw_distance_batch_device(idx, (const float *)idx->scratch.q.p, nq, q_stride, (const int32_t *)idx->scratch.ids.p, m, (float *)idx->scratch.dist.p, nullptr);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, idx->sDist.p, (size_t)nq * m * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, idx->scratch.dist.p, (size_t)nq * m * 4, hipMemcpyDeviceToHost));
     return HNSW_OK;
 }
 

@@ -41,6 +41,50 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// One device table of an index and the bytes hnsw_index_info.device_bytes counts for it.  An empty table still gets an
+// allocation (16 bytes at least: kernels may be handed its pointer), which is not counted.
+struct Table {
+    void *p = nullptr;
+    size_t bytes = 0;
+    hipError_t alloc(size_t b) {
+        release();
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(b, 16));
+        if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; return e; }
+        bytes = b;
+        return hipSuccess;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+
+// Every device table an index holds: the vectors and the graph, and the copies derived from them -- byte rows (X8, hnsw_rows8.hip),
+// split rows (Xm / tail0, hnsw_rows_split.hip), locality codes (lcode / lcode0, hnsw_locality.hip); a derived table that does not
+// exist has p == nullptr.  bind_view points the handle's IndexView at them.
+struct IndexTables {
+    Table X, X8, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
+    template <class Self, class F> static void each(Self &t, F f) {
+        static constexpr Table IndexTables::*all[] = {&IndexTables::X, &IndexTables::X8, &IndexTables::Xm, &IndexTables::tail0,
+                                                      &IndexTables::lcode, &IndexTables::lcode0, &IndexTables::nbr0, &IndexTables::nbrU,
+                                                      &IndexTables::off, &IndexTables::lvl, &IndexTables::ref};
+        for (Table IndexTables::*m : all) f(t.*m);
+    }
+    void release() { each(*this, [](Table &t) { t.release(); }); }
+    size_t bytes() const { size_t s = 0; each(*this, [&](const Table &t) { s += t.bytes; }); return s; }
+};
+
+// the device buffers of one batch of nq queries: the queries (qbytes), k ids and distances per query, the per-query counters
+// and status words, and the launch's "any query flagged" word
+struct BatchBufs {
+    DevBuf q, ids, dist, nd, nh, st, flag;
+    int ensure(int64_t nq, size_t qbytes, int k) {
+        int rc;
+        if ((rc = q.ensure(qbytes)) || (rc = ids.ensure((size_t)nq * k * 4)) || (rc = dist.ensure((size_t)nq * k * 4)) ||
+            (rc = nd.ensure((size_t)nq * 4)) || (rc = nh.ensure((size_t)nq * 4)) || (rc = st.ensure((size_t)nq * 4)) || (rc = flag.ensure(16)))
+            return rc;
+        return HNSW_OK;
+    }
+    void release() { for (DevBuf *b : {&q, &ids, &dist, &nd, &nh, &st, &flag}) b->release(); }
+};
+
 inline int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
     return (s && *s) ? atoi(s) : dflt;
@@ -69,12 +113,16 @@ inline int slot_class(int nslot) {
 constexpr int SLOT_CLASSES = 7;
 inline int64_t padded_stride(int d) { return ((int64_t)d + 15) / 16 * 16; } // floats: rows are multiples of 64 B
 
-// {upper_off, upper_lvl} of every node side by side (IndexView::upper_ref) from the two host tables
-int upload_upper_ref(const int32_t *off, const uint8_t *lvl, int64_t n, void **dRef);
+// The graph tables of an index of n nodes: X (max(n, 1) rows of `stride` floats), nbr0 ([n][S0]) and nbrU ([max(rowsU, 1)][SU])
+// with every slot empty (-1), off / lvl / ref (max(n, 1) entries each, written by upload_upper_layout)
+int alloc_graph_tables(IndexTables &t, int64_t n, int64_t stride, int S0, int SU, int64_t rowsU);
+// The upper-row layout of m nodes of levels lvl[0..m): a node's rows of layers 1..lvl lie side by side, the nodes' in order from
+// row `row0` on.  ref[j] = {first row or -1, level} (IndexView::upper_ref); returns the row count after them.
+int64_t upper_layout(const uint8_t *lvl, int64_t m, int64_t row0, std::vector<int2> &ref);
+// ... written into off / lvl / ref of the nodes [n0, n0 + ref.size())
+int upload_upper_layout(IndexTables &t, int64_t n0, const std::vector<int2> &ref);
 
-// copies [n][row_stride] host rows into a fresh zero-padded device table
-int upload_vectors(const float *vectors, int64_t n, int d, int64_t row_stride, void **dX, size_t *bytes);
-// ... into n zero-padded rows of an existing device table (rows of padded_stride(d) floats)
+// copies [n][row_stride] host rows into n zero-padded rows of a device table (rows of padded_stride(d) floats)
 int upload_rows(const float *vectors, int64_t n, int d, int64_t row_stride, float *dst);
 
 } // namespace hnsw_host
@@ -85,7 +133,7 @@ struct hnsw_request {
     hnsw_index *idx = nullptr;
     int64_t nq = 0, q_stride = 0;
     hnsw_search_params params{};
-    hnsw_host::DevBuf q, ids, dist, nd, nh, st, flag;
+    hnsw_host::BatchBufs buf;
     int stream = 0;
     uint32_t host_flag = 0;
 };
@@ -94,17 +142,13 @@ struct hnsw_index {
     int device = -1;
     hnsw_dev::IndexView iv{};
     hnsw_index_info info{};
-    void *dX8 = nullptr;                 // byte rows (hnsw_rows8.hip), nullptr when the data does not qualify
-    void *dXm = nullptr, *dTail0 = nullptr; // split rows (hnsw_rows_split.hip), nullptr when the row shape does not qualify
-    // locality codes (hnsw_locality.hip): per node and per layer-0 adjacency slot; built when the visited set first runs as
-    // bitmap blocks.  lcode_state: 0 not built yet, 1 built, -1 cannot be built (no upper layer to derive an order from)
-    void *dLcode = nullptr, *dLcode0 = nullptr;
+    hnsw_host::IndexTables tables;       // every device table: device_bytes is their sum (hnsw_index_get_info)
+    // locality codes (tables.lcode / lcode0): built when the visited set first runs as bitmap blocks.  lcode_state: 0 not built
+    // yet, 1 built, -1 cannot be built (no upper layer to derive an order from)
     int lcode_state = 0;
     int blk_mode = -1;                   // option "visited_blocks": -1 automatic (measured per kernel shape on the index's own vectors), 0 never, 1 always
     int blk_choice[7][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};   // [slot_class(NSLOT)][accept rule]: -1 undecided, 0 tag cache, else log2 of the block slots
-    void *dX = nullptr, *dNbr0 = nullptr, *dNbrU = nullptr, *dOff = nullptr, *dLvl = nullptr, *dRef = nullptr;
-    int64_t rowsU = 0;
-    hnsw_host::DevBuf sQ, sIds, sDist, sNd, sNh, sSt, sFlag; // scratch for the host-buffer entry points (sFlag: the launch's "any query flagged" word)
+    hnsw_host::BatchBufs scratch;                            // scratch for the host-buffer entry points
     uint32_t *hFlag = nullptr, *hFlagDev = nullptr;          // the same word in pinned host memory (zero-copy calls) and its device address
     char *hSmall = nullptr, *hSmallDev = nullptr;            // page-locked block for small host-buffer calls (hnsw_search_batch: queries, ids, distances, counters)
     // option "device_fallback_slab_bytes": a slab of the caller's chosen size for the exactness fallback of
@@ -132,18 +176,27 @@ struct hnsw_index {
     int vt_grow_key = -1, vt_grow_bits = 0;   // knn_vt_bits' cached choice for (kernel variant, base size)
     int lds_pad = -1;                    // option "lds_pad": extra LDS bytes per search wave (-1 = balanced_lds_pad's choice)
     std::vector<std::pair<int, int>> prepared;   // (ef, accept rule) of every hnsw_index_prepare: what hnsw_index_save writes down
-    // what the options "byte_rows" / "split_rows" asked for, so that hnsw_index_insert, which makes the row copies again, keeps
-    // their effect: byte_rows 0, split_rows 0 (off), split_rows -1 (off and freed for good)
+    // what the options "byte_rows" / "split_rows" asked for (bind_view leaves an unused copy out of the view), so that
+    // hnsw_index_insert, which makes the row copies again, keeps their effect: byte_rows 0, split_rows 0 (off), split_rows -1
+    // (off and freed for good)
     bool byte_rows_off = false, split_rows_off = false, split_rows_freed = false;
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
 };
 
 namespace hnsw_host {
 
-// hnsw_rows8.hip: if every value of idx->dX is an integer in 0..255, build the byte copy (idx->dX8, iv.X8, iv.stride8)
+// hnsw_capi.hip: IndexView's table pointers from idx->tables (X8 / Xm left out while option byte_rows / split_rows is 0), and the
+// hnsw_index_info fields that restate the view (n, max_degree0, max_layer, entry_point, row_stride_bytes).  Called by every
+// change of the tables or of those options.
+void bind_view(::hnsw_index *idx);
+// hnsw_capi.hip: the end of hnsw_index_create and hnsw_build, once the graph tables are complete: the view bound, the row copies
+// made, the first search's one-time costs paid.  *out = idx on success; on an error idx is destroyed.
+int finish_index(::hnsw_index *idx, int32_t expected_ef, int32_t expected_semantics, ::hnsw_index **out);
+
+// hnsw_rows8.hip: if every value of tables.X is an integer in 0..255, build the byte copy (tables.X8, iv.stride8)
 int make_byte_rows(::hnsw_index *idx);
 // hnsw_rows_split.hip: if a row ends 1..32 bytes past a 128-byte line (and there are no byte rows), build the split copy
-// (idx->dXm / dTail0, iv.Xm / tail0 / stride_m / main_chunks / tail_chunks); call after make_byte_rows, graph in place
+// (tables.Xm / tail0, iv.stride_m / main_chunks / tail_chunks); call after make_byte_rows, graph in place
 int make_split_rows(::hnsw_index *idx);
 
 // hnsw_order.hip: the descent alone for nq device-resident queries: d_entry[q] = the node the greedy descent reaches on layer
@@ -163,9 +216,9 @@ void list_blk_choices(const ::hnsw_index *idx, std::vector<int32_t> &out3);
 // nearest node found per target
 int layer_nearest_device(::hnsw_index *idx, int32_t layer, const float *d_targets, int64_t t_stride, int64_t nq, const int32_t *d_qmap,
                          int64_t n_launch, const int32_t *d_starts, int32_t ef, int32_t *d_out_ids, float *d_out_dist);
-// hnsw_locality.hip: builds idx->dLcode / dLcode0 (and iv.lcode / lcode0) once; lcode_state says how it went.  The per-slot
-// table dLcode0 (n * max_degree0 * 4 bytes) exists only while a kernel shape uses the bitmap blocks or is being measured:
-// drop_lcode0 frees it, materialise_lcode0 (also reached through build_locality_codes) makes it again from dLcode.
+// hnsw_locality.hip: builds tables.lcode / lcode0 once; lcode_state says how it went.  The per-slot table lcode0
+// (n * max_degree0 * 4 bytes) exists only while a kernel shape uses the bitmap blocks or is being measured: drop_lcode0 frees
+// it, materialise_lcode0 (also reached through build_locality_codes) makes it again from lcode.
 int build_locality_codes(::hnsw_index *idx);
 int materialise_lcode0(::hnsw_index *idx);
 void drop_lcode0(::hnsw_index *idx);

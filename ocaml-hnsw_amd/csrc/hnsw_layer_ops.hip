@@ -243,35 +243,32 @@ int32_t hnsw_search_layer_batch(hnsw_index *idx, int32_t layer, const float *tar
     const size_t qbytes = ((size_t)(nq - 1) * t_stride + idx->iv.d) * sizeof(float);
     DevBuf dStart, dCnt;
     struct Guard { DevBuf &a, &b; ~Guard() { a.release(); b.release(); } } guard{dStart, dCnt};
-    if ((rc = idx->sQ.ensure(qbytes)) || (rc = idx->sIds.ensure((size_t)nq * k * 4)) ||
-        (rc = idx->sDist.ensure((size_t)nq * k * 4)) || (rc = idx->sNd.ensure((size_t)nq * 4)) ||
-        (rc = idx->sNh.ensure((size_t)nq * 4)) || (rc = idx->sSt.ensure((size_t)nq * 4)) ||
-        (rc = dStart.ensure(st.size() * 4)) || (rc = dCnt.ensure((size_t)nq * 4)))
+    if ((rc = idx->scratch.ensure(nq, qbytes, k)) || (rc = dStart.ensure(st.size() * 4)) || (rc = dCnt.ensure((size_t)nq * 4)))
         return rc;
-    HIP_TRY(hipMemcpy(idx->sQ.p, targets, qbytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(idx->scratch.q.p, targets, qbytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dStart.p, st.data(), st.size() * 4, hipMemcpyHostToDevice));
 
     LayerSearchArgs a{};
-    a.Q = (const float *)idx->sQ.p; a.q_stride = t_stride; a.nq = nq;
+    a.Q = (const float *)idx->scratch.q.p; a.q_stride = t_stride; a.nq = nq;
     a.starts = (const int32_t *)dStart.p; a.n_start = n_start; a.layer = layer;
     a.ef = p->ef; a.k = k; a.fill = p->fill; a.sem = p->semantics;
     a.vt_bits = search_vt_bits(idx, p->ef);
-    a.out_ids = (int32_t *)idx->sIds.p; a.out_dist = (float *)idx->sDist.p; a.out_cnt = (int32_t *)dCnt.p;
-    a.out_ndist = (uint32_t *)idx->sNd.p; a.out_nhops = (uint32_t *)idx->sNh.p; a.out_status = (uint32_t *)idx->sSt.p;
+    a.out_ids = (int32_t *)idx->scratch.ids.p; a.out_dist = (float *)idx->scratch.dist.p; a.out_cnt = (int32_t *)dCnt.p;
+    a.out_ndist = (uint32_t *)idx->scratch.nd.p; a.out_nhops = (uint32_t *)idx->scratch.nh.p; a.out_status = (uint32_t *)idx->scratch.st.p;
     if ((rc = launch_layer_args(idx, a))) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    rc = rerun_overflowed(idx, nq, (const uint32_t *)idx->sSt.p,
+    rc = rerun_overflowed(idx, nq, (const uint32_t *)idx->scratch.st.p,
                           [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
                               LayerSearchArgs b = a;
                               b.nq = c; b.qmap = qmap; b.ovf_g = slab; b.ovf_gcap = cap;
                               return launch_layer_args(idx, b);
                           });
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_ids, idx->sIds.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_dist, idx->sDist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_ids, idx->scratch.ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_dist, idx->scratch.dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
     if (out_cnt) HIP_TRY(hipMemcpy(out_cnt, dCnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    if (out_ndist) HIP_TRY(hipMemcpy(out_ndist, idx->sNd.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    if (out_nhops) HIP_TRY(hipMemcpy(out_nhops, idx->sNh.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    if (out_ndist) HIP_TRY(hipMemcpy(out_ndist, idx->scratch.nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    if (out_nhops) HIP_TRY(hipMemcpy(out_nhops, idx->scratch.nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
     return HNSW_OK;
 }
 
@@ -288,21 +285,21 @@ int32_t hnsw_search_one_batch(hnsw_index *idx, int32_t layer, const float *targe
     if (rc) return rc;
     HIP_TRY(hipSetDevice(idx->device));
     const size_t qbytes = ((size_t)(nq - 1) * t_stride + idx->iv.d) * sizeof(float);
-    if ((rc = idx->sQ.ensure(qbytes)) || (rc = idx->sIds.ensure((size_t)nq * 4)) || (rc = idx->sDist.ensure((size_t)nq * 4)) ||
-        (rc = idx->sNd.ensure((size_t)nq * 4)))
+    if ((rc = idx->scratch.q.ensure(qbytes)) || (rc = idx->scratch.ids.ensure((size_t)nq * 4)) || (rc = idx->scratch.dist.ensure((size_t)nq * 4)) ||
+        (rc = idx->scratch.nd.ensure((size_t)nq * 4)))
         return rc;
-    HIP_TRY(hipMemcpy(idx->sQ.p, targets, qbytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(idx->sNd.p, st.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(idx->scratch.q.p, targets, qbytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(idx->scratch.nd.p, st.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
     const int nch = pick_nch(idx->iv.nchunks);
     hipError_t e = idx->info.metric == HNSW_METRIC_L2
-                       ? one_nch<0>(nch, idx->iv, (const float *)idx->sQ.p, t_stride, nq, layer, (const int32_t *)idx->sNd.p, (int32_t *)idx->sIds.p, (float *)idx->sDist.p)
-                       : one_nch<1>(nch, idx->iv, (const float *)idx->sQ.p, t_stride, nq, layer, (const int32_t *)idx->sNd.p, (int32_t *)idx->sIds.p, (float *)idx->sDist.p);
+                       ? one_nch<0>(nch, idx->iv, (const float *)idx->scratch.q.p, t_stride, nq, layer, (const int32_t *)idx->scratch.nd.p, (int32_t *)idx->scratch.ids.p, (float *)idx->scratch.dist.p)
+                       : one_nch<1>(nch, idx->iv, (const float *)idx->scratch.q.p, t_stride, nq, layer, (const int32_t *)idx->scratch.nd.p, (int32_t *)idx->scratch.ids.p, (float *)idx->scratch.dist.p);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "search_one kernel launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipDeviceSynchronize());
     std::vector<int32_t> nodes((size_t)nq);
-    HIP_TRY(hipMemcpy(nodes.data(), idx->sIds.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nodes.data(), idx->scratch.ids.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < nq; ++i) out_node[i] = nodes[(size_t)i];
-    if (out_dist) HIP_TRY(hipMemcpy(out_dist, idx->sDist.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    if (out_dist) HIP_TRY(hipMemcpy(out_dist, idx->scratch.dist.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
     return HNSW_OK;
 }
 

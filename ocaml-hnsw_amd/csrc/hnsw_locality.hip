@@ -65,7 +65,7 @@ static int build_codes(::hnsw_index *idx) {
         (rc = bdist.ensure((size_t)n * 4)) || (rc = qmap.ensure((size_t)n * 4)))
         return rc;
     std::vector<uint8_t> lvl_h((size_t)n);
-    HIP_TRY(hipMemcpy(lvl_h.data(), idx->dLvl, (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lvl_h.data(), idx->iv.upper_lvl, (size_t)n, hipMemcpyDeviceToHost));
     // ent[l - lo][v]: the nearest node of layer l to v that the index's own search finds: the greedy descent (Ohnsw.search_one,
     // lib/ohnsw.ml:865-867) down to layer l, then Ohnsw.search_k on layer l from there with W bounded by ef_b, its nearest result.
     // (The greedy descent alone is not enough: on clustered data it ends in the wrong cluster's node for half of the vectors, and
@@ -74,7 +74,7 @@ static int build_codes(::hnsw_index *idx) {
     std::vector<std::vector<int32_t>> ent((size_t)(T - lo + 1));
     std::vector<int32_t> list;
     for (int l = lo; l <= T; ++l) {
-        if ((rc = descent_entries(idx, (const float *)idx->dX, n, idx->iv.stride, l, (int32_t *)entry.p, (uint32_t *)scratch.p, nullptr))) return rc;
+        if ((rc = descent_entries(idx, idx->iv.X, n, idx->iv.stride, l, (int32_t *)entry.p, (uint32_t *)scratch.p, nullptr))) return rc;
         HIP_TRY(hipMemcpy(best.p, entry.p, (size_t)n * 4, hipMemcpyDeviceToDevice));     // (targets not searched below keep the descent's node)
         const int32_t *d_qmap = nullptr;
         int64_t n_launch = n;
@@ -85,7 +85,7 @@ static int build_codes(::hnsw_index *idx) {
             if (n_launch > 0) HIP_TRY(hipMemcpy(qmap.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
             d_qmap = (const int32_t *)qmap.p;
         }
-        if (ef_b > 1 && (rc = layer_nearest_device(idx, l, (const float *)idx->dX, idx->iv.stride, n, d_qmap, n_launch, (const int32_t *)entry.p, ef_b,
+        if (ef_b > 1 && (rc = layer_nearest_device(idx, l, idx->iv.X, idx->iv.stride, n, d_qmap, n_launch, (const int32_t *)entry.p, ef_b,
                                                    (int32_t *)best.p, (float *)bdist.p))) return rc;
         ent[(size_t)(l - lo)].resize((size_t)n);
         HIP_TRY(hipMemcpy(ent[(size_t)(l - lo)].data(), best.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -117,21 +117,18 @@ static int build_codes(::hnsw_index *idx) {
     number_layer(0, &ent[0]);                       // all nodes, by (number of their layer-`lo` node, id): the codes
     // the per-node table (n * 4 bytes) stays with the handle from here on; the per-slot table (n * max_degree0 * 4 bytes: the large
     // one) is made from it by materialise_lcode0 and can be dropped and made again in milliseconds (drop_lcode0)
-    void *dL = nullptr;
-    if (hipMalloc(&dL, (size_t)n * 4) != hipSuccess) {
-        (void)hipGetLastError();
+    Table &L = idx->tables.lcode;
+    if (L.alloc((size_t)n * 4) != hipSuccess) {
         idx->lcode_state = -1;                      // no room: the tag cache stays (not an error of the search)
         return HNSW_OK;
     }
-    if (hipMemcpy(dL, rank.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(L.p, rank.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(dL);
+        L.release();
         idx->lcode_state = -1;                      // a failed build is not retried by every later search
         return fail(HNSW_ERR_HIP, "upload of the locality codes failed");
     }
-    idx->dLcode = dL;
-    idx->iv.lcode = (const int32_t *)dL;
-    idx->info.device_bytes += (int64_t)n * 4;
+    bind_view(idx);
     idx->lcode_state = 1;
     return materialise_lcode0(idx);
 }
@@ -139,40 +136,35 @@ static int build_codes(::hnsw_index *idx) {
 // lcode0[c][j] = L[nbr0[c][j]], the table the block filter reads beside the adjacency row: n * max_degree0 * 4 bytes
 // (C5's shape: 2.56 GB), counted in hnsw_index_info.device_bytes while it exists
 int materialise_lcode0(::hnsw_index *idx) {
-    if (idx->lcode_state != 1 || idx->dLcode0) return HNSW_OK;
+    IndexTables &t = idx->tables;
+    if (idx->lcode_state != 1 || t.lcode0.p) return HNSW_OK;
     HIP_TRY(hipSetDevice(idx->device));
     const size_t total = (size_t)idx->iv.n * (size_t)idx->iv.S0;
-    void *dL0 = nullptr;
-    if (hipMalloc(&dL0, std::max<size_t>(total, 1) * 4) != hipSuccess) {
-        (void)hipGetLastError();
+    if (t.lcode0.alloc(total * 4) != hipSuccess) {
         idx->lcode_state = -1;                      // no room for the large table: the tag cache stays
-        (void)hipFree(idx->dLcode);
-        idx->info.device_bytes -= (int64_t)idx->iv.n * 4;
-        idx->dLcode = nullptr; idx->iv.lcode = nullptr;
+        t.lcode.release();
+        bind_view(idx);
         return HNSW_OK;
     }
     hipLaunchKernelGGL(lcode0_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr,
-                       (const int32_t *)idx->dNbr0, (const int32_t *)idx->dLcode, (int64_t)total, (int32_t *)dL0);
+                       (const int32_t *)t.nbr0.p, (const int32_t *)t.lcode.p, (int64_t)total, (int32_t *)t.lcode0.p);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        (void)hipFree(dL0);
+        t.lcode0.release();
         idx->lcode_state = -1;
         return fail(HNSW_ERR_HIP, "filling the per-slot locality codes failed: %s", hipGetErrorString(e));
     }
-    idx->dLcode0 = dL0;
-    idx->iv.lcode0 = (const int32_t *)dL0;
-    idx->info.device_bytes += (int64_t)total * 4;
+    bind_view(idx);
     return HNSW_OK;
 }
 
 // frees the per-slot table again (no launch that reads it may be in flight: the caller has synchronised); the per-node codes stay
 void drop_lcode0(::hnsw_index *idx) {
-    if (!idx->dLcode0) return;
+    if (!idx->tables.lcode0.p) return;
     (void)hipSetDevice(idx->device);
-    (void)hipFree(idx->dLcode0);
-    idx->dLcode0 = nullptr; idx->iv.lcode0 = nullptr;
-    idx->info.device_bytes -= (int64_t)idx->iv.n * (int64_t)idx->iv.S0 * 4;
+    idx->tables.lcode0.release();
+    bind_view(idx);
 }
 
 // the codes of a saved index (hnsw_index_load): adopted instead of built
@@ -180,12 +172,10 @@ int adopt_locality_codes(::hnsw_index *idx, const int32_t *codes) {
     if (idx->lcode_state != 0) return HNSW_OK;
     const int64_t n = idx->iv.n;
     HIP_TRY(hipSetDevice(idx->device));
-    void *dL = nullptr;
-    if (hipMalloc(&dL, (size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess) { (void)hipGetLastError(); return HNSW_OK; }   // built later, if ever
-    if (hipMemcpy(dL, codes, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(dL); return HNSW_OK; }
-    idx->dLcode = dL;
-    idx->iv.lcode = (const int32_t *)dL;
-    idx->info.device_bytes += n * 4;
+    Table &L = idx->tables.lcode;
+    if (L.alloc((size_t)n * 4) != hipSuccess) return HNSW_OK;    // built later, if ever
+    if (hipMemcpy(L.p, codes, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); L.release(); return HNSW_OK; }
+    bind_view(idx);
     idx->lcode_state = 1;
     return HNSW_OK;
 }
@@ -193,25 +183,23 @@ int adopt_locality_codes(::hnsw_index *idx, const int32_t *codes) {
 // hnsw_index_insert: the old codes (a device copy), the appended nodes numbered after them; the per-slot table again if `from`
 // had one (the adjacency of old nodes changed, so from's table is stale)
 int extend_locality_codes(const ::hnsw_index *from, ::hnsw_index *to) {
-    if (from->lcode_state != 1 || !from->dLcode) return HNSW_OK;
+    if (from->lcode_state != 1 || !from->tables.lcode.p) return HNSW_OK;
     HIP_TRY(hipSetDevice(to->device));
     const int64_t n_old = from->iv.n, n = to->iv.n;
-    void *dL = nullptr;
-    HIP_TRY(hipMalloc(&dL, (size_t)std::max<int64_t>(n, 1) * 4));
-    hipError_t e = hipMemcpy(dL, from->dLcode, (size_t)n_old * 4, hipMemcpyDeviceToDevice);
+    Table &L = to->tables.lcode;
+    HIP_TRY(L.alloc((size_t)n * 4));
+    hipError_t e = hipMemcpy(L.p, from->tables.lcode.p, (size_t)n_old * 4, hipMemcpyDeviceToDevice);
     if (e == hipSuccess && n > n_old) {
-        hipLaunchKernelGGL(lcode_append_kernel, dim3((unsigned)((n - n_old + 255) / 256)), dim3(256), 0, nullptr, (int32_t *)dL, n_old, n);
+        hipLaunchKernelGGL(lcode_append_kernel, dim3((unsigned)((n - n_old + 255) / 256)), dim3(256), 0, nullptr, (int32_t *)L.p, n_old, n);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(dL); return fail(HNSW_ERR_HIP, "extending the locality codes failed: %s", hipGetErrorString(e)); }
-    to->dLcode = dL;
-    to->iv.lcode = (const int32_t *)dL;
-    to->info.device_bytes += n * 4;
+    if (e != hipSuccess) { L.release(); return fail(HNSW_ERR_HIP, "extending the locality codes failed: %s", hipGetErrorString(e)); }
+    bind_view(to);
     to->lcode_state = 1;
-    if (!from->dLcode0) return HNSW_OK;
+    if (!from->tables.lcode0.p) return HNSW_OK;
     int rc = materialise_lcode0(to);
-    if (rc == HNSW_OK && !to->dLcode0) rc = fail(HNSW_ERR_OOM, "no room for the per-slot locality codes of the grown index (%lld bytes)", (long long)n * to->iv.S0 * 4);
+    if (rc == HNSW_OK && !to->tables.lcode0.p) rc = fail(HNSW_ERR_OOM, "no room for the per-slot locality codes of the grown index (%lld bytes)", (long long)n * to->iv.S0 * 4);
     return rc;
 }
 

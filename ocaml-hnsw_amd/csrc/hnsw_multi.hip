@@ -67,9 +67,10 @@ struct hnsw_multi {
     std::vector<ncclComm_t> comms;        // [G], created at the first device-resident search
     std::vector<hipStream_t> streams;     // [G]
     std::vector<hipEvent_t> done;         // [G] "this device's search is enqueued up to here" (the same-device copy arrangement)
-    std::vector<DevBuf> dQ, dIds, dDist, dNd, dNh, dSt;   // per device: its query shard; the FULL [nq][k] result; per-shard counters
+    // per device: its query shard; the FULL [nq][k] result; per-shard counters; the launch's "any query flagged" word (see
+    // hnsw_search_batch)
+    std::vector<BatchBufs> buf;
     int64_t last_nq = 0; int last_k = 0;
-    std::vector<DevBuf> dFlag;            // per device: the launch's "any query flagged" word (see hnsw_search_batch)
     uint32_t *hFlags = nullptr;           // [G] pinned host words the flags are copied into
     // what the exchanges of this handle were made of (hnsw_multi_debug_counters): calls issued, summed over the devices
     int64_t n_allgather = 0, n_broadcast = 0, n_peer_copies = 0, n_repaired_shards = 0;
@@ -87,7 +88,7 @@ int ensure_streams(hnsw_multi *m) {
     const size_t G = m->replicas.size();
     if (m->streams.size() == G) return HNSW_OK;
     m->streams.assign(G, nullptr);
-    m->dQ.resize(G); m->dIds.resize(G); m->dDist.resize(G); m->dNd.resize(G); m->dNh.resize(G); m->dSt.resize(G); m->dFlag.resize(G);
+    m->buf.resize(G);
     if (!m->hFlags) HIP_TRY(hipHostMalloc((void **)&m->hFlags, G * sizeof(uint32_t), hipHostMallocPortable));
     for (size_t g = 0; g < G; ++g) {
         HIP_TRY(hipSetDevice(m->devices[g]));
@@ -143,26 +144,23 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
     for (int g = 0; g < G; ++g) {
         const int64_t lo = shard_lo(nq, g, G), hi = shard_lo(nq, g + 1, G);
         hnsw_index *idx = m->replicas[(size_t)g];
+        BatchBufs &b = m->buf[(size_t)g];
         HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
-        if ((rc = m->dIds[(size_t)g].ensure(std::max<size_t>(full, 1) * 4)) || (rc = m->dDist[(size_t)g].ensure(std::max<size_t>(full, 1) * 4)) ||
-            (rc = m->dFlag[(size_t)g].ensure(16)))
+        if ((rc = b.ids.ensure(std::max<size_t>(full, 1) * 4)) || (rc = b.dist.ensure(std::max<size_t>(full, 1) * 4)) || (rc = b.flag.ensure(16)))
             return rc;
         m->hFlags[g] = 0;
         if (hi <= lo) continue;
         const int64_t ns = hi - lo;
         const size_t qbytes = ((size_t)(ns - 1) * q_stride + d) * sizeof(float);
-        if ((rc = m->dQ[(size_t)g].ensure(qbytes)) || (rc = m->dNd[(size_t)g].ensure((size_t)ns * 4)) ||
-            (rc = m->dNh[(size_t)g].ensure((size_t)ns * 4)) || (rc = m->dSt[(size_t)g].ensure((size_t)ns * 4)))
+        if ((rc = b.q.ensure(qbytes)) || (rc = b.nd.ensure((size_t)ns * 4)) || (rc = b.nh.ensure((size_t)ns * 4)) || (rc = b.st.ensure((size_t)ns * 4)))
             return rc;
         hipStream_t st = m->streams[(size_t)g];
-        HIP_TRY(hipMemsetAsync(m->dFlag[(size_t)g].p, 0, 4, st));
-        HIP_TRY(hipMemcpyAsync(m->dQ[(size_t)g].p, queries + lo * q_stride, qbytes, hipMemcpyHostToDevice, st));
-        rc = search_batch_device_flag(idx, (const float *)m->dQ[(size_t)g].p, ns, q_stride, params,
-                                      (int32_t *)m->dIds[(size_t)g].p + lo * k, (float *)m->dDist[(size_t)g].p + lo * k,
-                                      (uint32_t *)m->dNd[(size_t)g].p, (uint32_t *)m->dNh[(size_t)g].p, (uint32_t *)m->dSt[(size_t)g].p,
-                                      (uint32_t *)m->dFlag[(size_t)g].p, st);
+        HIP_TRY(hipMemsetAsync(b.flag.p, 0, 4, st));
+        HIP_TRY(hipMemcpyAsync(b.q.p, queries + lo * q_stride, qbytes, hipMemcpyHostToDevice, st));
+        rc = search_batch_device_flag(idx, (const float *)b.q.p, ns, q_stride, params, (int32_t *)b.ids.p + lo * k, (float *)b.dist.p + lo * k,
+                                      (uint32_t *)b.nd.p, (uint32_t *)b.nh.p, (uint32_t *)b.st.p, (uint32_t *)b.flag.p, st);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(&m->hFlags[g], m->dFlag[(size_t)g].p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&m->hFlags[g], b.flag.p, 4, hipMemcpyDeviceToHost, st));
     }
     // ---- the exchange: every device receives every shard (shards [r_lo, r_hi) only: the whole table, or, after the
     //      fallback, the repaired shards again) ----
@@ -177,8 +175,8 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
             for (int g = 0; g < G && !err; ++g) {
                 if (hipSetDevice(m->devices[(size_t)g]) != hipSuccess) { err = fail(HNSW_ERR_HIP, "hipSetDevice failed"); break; }
                 if (g == fail_at) { err = fail(HNSW_ERR_HIP, "RCCL exchange failed: enqueue on device %d refused (HNSW_MULTI_FAIL_ENQUEUE)", g); break; }
-                int32_t *ids = (int32_t *)m->dIds[(size_t)g].p;
-                float *dd = (float *)m->dDist[(size_t)g].p;
+                int32_t *ids = (int32_t *)m->buf[(size_t)g].ids.p;
+                float *dd = (float *)m->buf[(size_t)g].dist.p;
                 ncclResult_t r1 = ncclSuccess;
                 if (equal) {       // in place: the send buffer is this rank's slice of the receive buffer
                     const size_t cnt = (size_t)(nq / G) * k;
@@ -220,9 +218,9 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
                         hipEvent_t ev = m->done[(size_t)r];
                         HIP_TRY(hipStreamWaitEvent(m->streams[(size_t)g], ev, 0));
                     }
-                    HIP_TRY(hipMemcpyPeerAsync((int32_t *)m->dIds[(size_t)g].p + lo * k, m->devices[(size_t)g], (int32_t *)m->dIds[(size_t)r].p + lo * k,
+                    HIP_TRY(hipMemcpyPeerAsync((int32_t *)m->buf[(size_t)g].ids.p + lo * k, m->devices[(size_t)g], (int32_t *)m->buf[(size_t)r].ids.p + lo * k,
                                                m->devices[(size_t)r], (size_t)(hi - lo) * k * 4, m->streams[(size_t)g]));
-                    HIP_TRY(hipMemcpyPeerAsync((float *)m->dDist[(size_t)g].p + lo * k, m->devices[(size_t)g], (float *)m->dDist[(size_t)r].p + lo * k,
+                    HIP_TRY(hipMemcpyPeerAsync((float *)m->buf[(size_t)g].dist.p + lo * k, m->devices[(size_t)g], (float *)m->buf[(size_t)r].dist.p + lo * k,
                                                m->devices[(size_t)r], (size_t)(hi - lo) * k * 4, m->streams[(size_t)g]));
                     m->n_peer_copies += 2;
                 }
@@ -244,21 +242,21 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
         const int64_t lo = shard_lo(nq, g, G), hi = shard_lo(nq, g + 1, G);
         if (hi <= lo) continue;
         hnsw_index *idx = m->replicas[(size_t)g];
+        BatchBufs &b = m->buf[(size_t)g];
         HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
         if (m->hFlags[g] & 1u) {
-            rc = rerun_overflowed(idx, hi - lo, (const uint32_t *)m->dSt[(size_t)g].p,
+            rc = rerun_overflowed(idx, hi - lo, (const uint32_t *)b.st.p,
                                   [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
-                                      return search_rerun_device(idx, (const float *)m->dQ[(size_t)g].p, hi - lo, q_stride, params,
-                                                                 (int32_t *)m->dIds[(size_t)g].p + lo * k, (float *)m->dDist[(size_t)g].p + lo * k,
-                                                                 (uint32_t *)m->dNd[(size_t)g].p, (uint32_t *)m->dNh[(size_t)g].p,
-                                                                 (uint32_t *)m->dSt[(size_t)g].p, qmap, c, slab, cap, nullptr);
+                                      return search_rerun_device(idx, (const float *)b.q.p, hi - lo, q_stride, params, (int32_t *)b.ids.p + lo * k,
+                                                                 (float *)b.dist.p + lo * k, (uint32_t *)b.nd.p, (uint32_t *)b.nh.p,
+                                                                 (uint32_t *)b.st.p, qmap, c, slab, cap, nullptr);
                                   });
             if (rc) return rc;
             m->n_repaired_shards++;
             if ((rc = exchange(g))) return rc;
         }
-        if (out_ndist) HIP_TRY(hipMemcpyAsync(out_ndist + lo, m->dNd[(size_t)g].p, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, m->streams[(size_t)g]));
-        if (out_nhops) HIP_TRY(hipMemcpyAsync(out_nhops + lo, m->dNh[(size_t)g].p, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, m->streams[(size_t)g]));
+        if (out_ndist) HIP_TRY(hipMemcpyAsync(out_ndist + lo, b.nd.p, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, m->streams[(size_t)g]));
+        if (out_nhops) HIP_TRY(hipMemcpyAsync(out_nhops + lo, b.nh.p, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, m->streams[(size_t)g]));
     }
     m->last_nq = nq; m->last_k = k;
     return HNSW_OK;
@@ -303,7 +301,7 @@ int32_t hnsw_multi_destroy(hnsw_multi *m) {
     for (ncclComm_t c : m->comms) if (c) (void)m->rccl.CommDestroy(c);
     for (size_t g = 0; g < m->streams.size(); ++g) {
         (void)hipSetDevice(m->devices[g]);
-        m->dQ[g].release(); m->dIds[g].release(); m->dDist[g].release(); m->dNd[g].release(); m->dNh[g].release(); m->dSt[g].release(); m->dFlag[g].release();
+        m->buf[g].release();
         if (m->streams[g]) (void)hipStreamDestroy(m->streams[g]);
         if (g < m->done.size()) (void)hipEventDestroy(m->done[g]);
     }
@@ -340,8 +338,8 @@ int32_t hnsw_multi_search_batch_device(hnsw_multi *m, const float *queries, int6
     if (rc) { (void)sync_all(m); return rc; }
     if ((rc = sync_all(m))) return rc;
     for (size_t g = 0; g < m->replicas.size(); ++g) {
-        if (d_ids) d_ids[g] = (int32_t *)m->dIds[g].p;
-        if (d_dist) d_dist[g] = (float *)m->dDist[g].p;
+        if (d_ids) d_ids[g] = (int32_t *)m->buf[g].ids.p;
+        if (d_dist) d_dist[g] = (float *)m->buf[g].dist.p;
     }
     return HNSW_OK;
 }
@@ -358,8 +356,8 @@ int32_t hnsw_multi_copy_result(hnsw_multi *m, int32_t g, int32_t *out_ids, float
     if (m->last_nq < 1 || m->streams.empty()) return fail(HNSW_ERR_BAD_ARG, "no device-resident result yet");
     HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
     const size_t bytes = (size_t)m->last_nq * m->last_k * 4;
-    HIP_TRY(hipMemcpy(out_ids, m->dIds[(size_t)g].p, bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_dist, m->dDist[(size_t)g].p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_ids, m->buf[(size_t)g].ids.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_dist, m->buf[(size_t)g].dist.p, bytes, hipMemcpyDeviceToHost));
     return HNSW_OK;
 }
 
@@ -384,8 +382,8 @@ int32_t hnsw_multi_search_batch(hnsw_multi *m, const float *queries, int64_t nq,
     if (rc) { (void)sync_all(m); return rc; }
     // the host gets the table from ONE device (it is complete everywhere after the exchange)
     HIP_TRY(hipSetDevice(m->devices[0]));
-    HIP_TRY(hipMemcpyAsync(out_ids, m->dIds[0].p, full, hipMemcpyDeviceToHost, m->streams[0]));
-    HIP_TRY(hipMemcpyAsync(out_dist, m->dDist[0].p, full, hipMemcpyDeviceToHost, m->streams[0]));
+    HIP_TRY(hipMemcpyAsync(out_ids, m->buf[0].ids.p, full, hipMemcpyDeviceToHost, m->streams[0]));
+    HIP_TRY(hipMemcpyAsync(out_dist, m->buf[0].dist.p, full, hipMemcpyDeviceToHost, m->streams[0]));
     return sync_all(m);
 }
 

@@ -47,7 +47,7 @@ pack_byte_rows_kernel(const float *X, int64_t stride, int64_t n, int32_t d, uint
 namespace hnsw_host {
 
 int make_byte_rows(::hnsw_index *idx) {
-    if (!idx || !idx->dX || idx->iv.n <= 0) return HNSW_OK;
+    if (!idx || !idx->tables.X.p || idx->iv.n <= 0) return HNSW_OK;
     if (!env_int("HNSW_BYTE_ROWS", 1)) return HNSW_OK;
     HIP_TRY(hipSetDevice(idx->device));
     const int64_t n = idx->iv.n;
@@ -61,7 +61,7 @@ int make_byte_rows(::hnsw_index *idx) {
     if (e == hipSuccess) {
         const int blocks = (int)std::min<int64_t>(65536, (n * (int64_t)d + 255) / 256);
         hipLaunchKernelGGL(rows_are_bytes_kernel, dim3((unsigned)std::max(1, blocks)), dim3(256), 0, 0,
-                           (const float *)idx->dX, idx->iv.stride, n, d, dflag);
+                           (const float *)idx->tables.X.p, idx->iv.stride, n, d, dflag);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(&ok, dflag, 4, hipMemcpyDeviceToHost);
@@ -69,22 +69,17 @@ int make_byte_rows(::hnsw_index *idx) {
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "byte-row check failed: %s", hipGetErrorString(e));
     if (env_int("HNSW_DEBUG_ROWS", 0)) fprintf(stderr, "hnsw: byte-row check n=%lld d=%d stride=%lld -> %d\n", (long long)n, d, (long long)idx->iv.stride, ok);
     if (!ok) return HNSW_OK;
-    const size_t bytes = (size_t)n * (size_t)row_bytes;
-    if (hipMalloc(&idx->dX8, bytes) != hipSuccess) {       // no room for the copy: not an error, the fp32 rows serve
-        (void)hipGetLastError();
-        idx->dX8 = nullptr;
-        return HNSW_OK;
-    }
+    Table &X8 = idx->tables.X8;
+    if (X8.alloc((size_t)n * (size_t)row_bytes) != hipSuccess) return HNSW_OK;     // no room for the copy: not an error, the fp32 rows serve
     const int32_t words = row_bytes / 4;
     const int blocks = (int)std::min<int64_t>(65536, (n * (int64_t)words + 255) / 256);
     hipLaunchKernelGGL(pack_byte_rows_kernel, dim3((unsigned)std::max(1, blocks)), dim3(256), 0, 0,
-                       (const float *)idx->dX, idx->iv.stride, n, d, (uint32_t *)idx->dX8, words);
+                       (const float *)idx->tables.X.p, idx->iv.stride, n, d, (uint32_t *)X8.p, words);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(idx->dX8); idx->dX8 = nullptr; return fail(HNSW_ERR_HIP, "byte-row packing failed: %s", hipGetErrorString(e)); }
-    idx->iv.X8 = (const uint8_t *)idx->dX8;
+    if (e != hipSuccess) { X8.release(); return fail(HNSW_ERR_HIP, "byte-row packing failed: %s", hipGetErrorString(e)); }
     idx->iv.stride8 = row_bytes;
-    idx->info.device_bytes += (int64_t)bytes;
+    bind_view(idx);
     return HNSW_OK;
 }
 

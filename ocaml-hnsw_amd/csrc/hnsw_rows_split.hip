@@ -49,8 +49,9 @@ pack_tails_kernel(const float4 *X, int64_t stride4, const int32_t *nbr0, int64_t
 namespace hnsw_host {
 
 int make_split_rows(::hnsw_index *idx) {
-    if (!idx || !idx->dX || !idx->dNbr0 || idx->iv.n <= 0) return HNSW_OK;
-    if (idx->dX8) return HNSW_OK;                        // byte rows are a single line per vector already
+    if (!idx || !idx->tables.X.p || !idx->tables.nbr0.p || idx->iv.n <= 0) return HNSW_OK;
+    IndexTables &t = idx->tables;
+    if (t.X8.p) return HNSW_OK;                          // byte rows are a single line per vector already
     if (!env_int("HNSW_SPLIT_ROWS", 1)) return HNSW_OK;
     const int nchunks = idx->iv.nchunks;
     const int T = nchunks % 8;                           // float4 chunks past the last whole 128-byte line
@@ -58,30 +59,25 @@ int make_split_rows(::hnsw_index *idx) {
     HIP_TRY(hipSetDevice(idx->device));
     const int64_t n = idx->iv.n;
     const int main_chunks = nchunks - T, S0 = idx->iv.S0;
-    const size_t main_bytes = (size_t)n * main_chunks * 16, tail_bytes = (size_t)n * S0 * T * 16;
-    void *dXm = nullptr, *dTail = nullptr;
-    if (hipMalloc(&dXm, main_bytes) != hipSuccess || hipMalloc(&dTail, tail_bytes) != hipSuccess) {
-        (void)hipGetLastError();                         // no room for the copy: not an error, the plain rows serve
-        if (dXm) (void)hipFree(dXm);
+    if (t.Xm.alloc((size_t)n * main_chunks * 16) != hipSuccess || t.tail0.alloc((size_t)n * S0 * T * 16) != hipSuccess) {
+        t.Xm.release();                                  // no room for the copy: not an error, the plain rows serve
         return HNSW_OK;
     }
     const int64_t stride4 = idx->iv.stride / 4;
     int blocks = (int)std::min<int64_t>(65536, (n * (int64_t)main_chunks + 255) / 256);
     hipLaunchKernelGGL(pack_main_rows_kernel, dim3((unsigned)std::max(1, blocks)), dim3(256), 0, 0,
-                       (const float4 *)idx->dX, stride4, n, main_chunks, (float4 *)dXm);
+                       (const float4 *)t.X.p, stride4, n, main_chunks, (float4 *)t.Xm.p);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         blocks = (int)std::min<int64_t>(65536, (n * (int64_t)S0 * T + 255) / 256);
         hipLaunchKernelGGL(pack_tails_kernel, dim3((unsigned)std::max(1, blocks)), dim3(256), 0, 0,
-                           (const float4 *)idx->dX, stride4, (const int32_t *)idx->dNbr0, n * (int64_t)S0, main_chunks, T, (float4 *)dTail);
+                           (const float4 *)t.X.p, stride4, (const int32_t *)t.nbr0.p, n * (int64_t)S0, main_chunks, T, (float4 *)t.tail0.p);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(dXm); (void)hipFree(dTail); return fail(HNSW_ERR_HIP, "split-row packing failed: %s", hipGetErrorString(e)); }
-    idx->dXm = dXm; idx->dTail0 = dTail;
-    idx->iv.Xm = (const float *)dXm; idx->iv.tail0 = (const float *)dTail;
+    if (e != hipSuccess) { t.Xm.release(); t.tail0.release(); return fail(HNSW_ERR_HIP, "split-row packing failed: %s", hipGetErrorString(e)); }
     idx->iv.stride_m = main_chunks * 16; idx->iv.main_chunks = main_chunks; idx->iv.tail_chunks = T;
-    idx->info.device_bytes += (int64_t)(main_bytes + tail_bytes);
+    bind_view(idx);
     return HNSW_OK;
 }
 

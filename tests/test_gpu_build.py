@@ -343,3 +343,36 @@ def test_hub_with_more_than_64_new_links_in_one_batch_stays_symmetric(H, oracle)
     assert all(i in sets[j] for i in range(n) for j in sets[i])             # symmetric
     assert hg.deg0.max() <= 2 * M
     assert hg.deg0[0] == 2 * M                                              # the hub's row is full, and was re-selected many times
+
+
+def test_device_bytes_are_the_tables_sizes(H, oracle):
+    """hnsw_index_info.device_bytes, exactly: the graph tables of built and created indices, plus the byte rows or the split
+    rows each one gets (still counted while option byte_rows 0 leaves them unused; split_rows -1 frees and uncounts them)"""
+    from device_bytes import base_bytes, byte_row_bytes, expected, split_row_bytes
+    rng = np.random.default_rng(3)
+    sift = lambda n, d: rng.integers(0, 219, size=(n, d)).astype(np.float32)
+    for X, M, fmt in [(_uniform(3000, 32, 5), 8, 0), (sift(3000, 128), 16, 2), (_uniform(3000, 100, 6), 12, 3),
+                      (_uniform(1, 8, 7), 4, 0), (_uniform(2, 8, 7), 4, 0), (_uniform(50, 5, 8), 4, 0)]:
+        n, d = X.shape
+        hg = H.Ohnsw.build_batch_bigarray(X, M, 40, seed=1).export()
+        inf = hg.info()
+        assert inf.row_format == fmt, (n, d)
+        assert inf.device_bytes == expected(hg, d), (n, d)
+        if fmt == 2:
+            assert inf.device_bytes == base_bytes(hg) + byte_row_bytes(n, d)
+            hg.set_option("byte_rows", 0)
+            assert hg.info().row_format == 0 and hg.info().device_bytes == inf.device_bytes
+        if fmt == 3:
+            assert inf.device_bytes == base_bytes(hg) + split_row_bytes(n, d, 2 * M) > base_bytes(hg)
+            hg.set_option("split_rows", 0)
+            assert hg.info().row_format == 0 and hg.info().device_bytes == inf.device_bytes
+            hg.set_option("split_rows", -1)
+            assert hg.info().device_bytes == base_bytes(hg)
+        # the same graph handed to hnsw_index_create
+        cg = H.Hgraph(X, hg.deg0, hg.nbr0, hg.upper, entry_point=hg.entry_point, id_base=0, max_degree=M)
+        assert cg.info().row_format == fmt
+        assert cg.info().device_bytes == expected(cg.export(), d, created=True), (n, d)
+        cg.release()
+        hg.release()
+    empty = H.Hgraph(np.zeros((0, 16), np.float32), np.zeros(0, np.int32), np.zeros((0, 8), np.int32))
+    assert empty.info().device_bytes == expected(empty.export(), 16, created=True)

@@ -7,6 +7,7 @@ import tempfile
 
 import numpy as np
 import pytest
+from device_bytes import base_bytes, expected
 
 pytestmark = pytest.mark.gpu
 
@@ -241,8 +242,12 @@ def test_search_on_a_grown_index_matches_the_oracle(H, oracle, case):
         bytes0 = hg.info().device_bytes
         hg.set_option("split_rows", -1)
         assert hg.info().device_bytes < bytes0 and hg.info().row_format == ROWS_F32
+        assert hg.info().device_bytes == base_bytes(hg.export())
+    assert hg.info().device_bytes == expected(hg.export(), X.shape[1])
     H.Ohnsw.insert_batch(hg, X[3000:3400], M, 60, seed=1)
+    assert hg.info().device_bytes == expected(hg.export(), X.shape[1])          # the grown tables and row copies, exactly
     H.Ohnsw.insert_batch(hg, X[3400:], M, 60, seed=1)
+    assert hg.info().device_bytes == expected(hg.export(), X.shape[1])
     inf = hg.info()
     assert inf.n == 4000 and hg.n == 4000
     want_fmt = {"bytes": ROWS_BYTES, "bytes_then_float": ROWS_F32, "split": ROWS_SPLIT, "split_freed": ROWS_F32}.get(case, ROWS_F32)

@@ -11,6 +11,7 @@ third of the rows in round 4 -- plus the bound on the evaluations the device add
 """
 import numpy as np
 import pytest
+from device_bytes import base_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -247,6 +248,7 @@ def test_structureless_vectors_keep_the_tag_cache(H, oracle):
     # for the measurement: only the per-node codes (n x 4 bytes) stay, and hnsw_index_info.device_bytes says so
     n, S0 = 200_000, 64
     without_table = int(hg.info().device_bytes)
+    assert without_table == base_bytes(hg.export()) + n * 4                # the graph tables and the per-node codes
     hg.set_option("visited_blocks", 1)
     H.Ohnsw.knn_batch_bigarray(hg, 10, Q[:8], ef=512)
     assert int(hg.info().device_bytes) == without_table + n * S0 * 4          # an explicit 1 re-makes it (one fill kernel) ...
@@ -287,6 +289,8 @@ def test_prepared_shapes_are_saved_and_a_loaded_index_starts_at_full_speed(H, or
         bits = hg.visited_blocks(ef)
         assert bits > 0
         base = int(hg.info().device_bytes)
+        n0 = hg.info().n * hg.info().max_degree0
+        assert base == base_bytes(hg.export()) + n * 4 + n0 * 4           # + the codes and the per-slot table
         first = _timed(lambda: H.Ohnsw.knn_batch_bigarray(hg, k, Q, ef=ef), 1)[0]
         steady = sorted(_timed(lambda: H.Ohnsw.knn_batch_bigarray(hg, k, Q, ef=ef), 7))
         assert capfd.readouterr().err.count("visited set for") == 0        # ... and never again
