@@ -155,8 +155,10 @@ typedef struct hnsw_search_params {
 
 enum { HNSW_ROWS_F32 = 0,   /* the float32 rows as handed over                                              */
        HNSW_ROWS_BYTES = 2, /* lossless byte copy (every value an integer in 0..255)                         */
-       HNSW_ROWS_SPLIT = 3 };/* float32 rows whose last 16 / 32 bytes past a 128-byte line are stored beside the
+       HNSW_ROWS_SPLIT = 3, /* float32 rows whose last 16 / 32 bytes past a 128-byte line are stored beside the
                                neighbour in the layer-0 adjacency (option "split_rows")                      */
+       HNSW_ROWS_HALF = 4 };/* the values rounded to fp16 (option "half_rows"): NOT the search over the float32
+                               vectors but the exact search over X rounded to fp16                          */
 
 typedef struct hnsw_index_info {
     int64_t n;
@@ -165,7 +167,8 @@ typedef struct hnsw_index_info {
     int64_t device_bytes;      /* HBM held by the index                                       */
     int64_t row_stride_bytes;  /* padded vector row on the device                             */
     int32_t device;
-    int32_t row_format;        /* HNSW_ROWS_*: what the knn searches read right now (options "byte_rows", "split_rows") */
+    int32_t row_format;        /* HNSW_ROWS_*: what the knn searches read right now (options "byte_rows", "split_rows",
+                                  "half_rows") */
 } hnsw_index_info;
 
 int32_t hnsw_abi_version(void);
@@ -229,9 +232,25 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   bytes / (4 n) queries per call; those it could not take keep their flag.  Needs d_status.  The list and
  *                   the slab belong to the handle: with this option ONE hnsw_search_batch_device / hnsw_search_batch_h2d call
  *                   in flight per handle (calls on one stream are ordered and therefore fine; calls on different streams
- *                   must not overlap). */
+ *                   must not overlap).
+ * and one that CHANGES results (off by default):
+ *   "half_rows"     the knn searches read a copy of the vectors rounded to fp16 (round to nearest even; subnormals and
+ *                   -0 kept: numpy's astype(float16)), 8 bytes per 4 dimensions in rows of 128-byte lines -- half the
+ *                   bytes gathered per evaluation of float32 rows.  Each half is converted back to float exactly and the
+ *                   arithmetic is that of the float32 rows, so the results are BIT FOR BIT those of the same search over
+ *                   Xh = X.astype(float16).astype(float32): exact over Xh, approximate over X.  The query stays float32.
+ *                   1 = make the copy if it does not exist and read it (it takes the place of the split rows and of the
+ *                   float32 rows), 0 = read the float32 / split rows again (the copy is kept), -1 = ... and FREE the copy
+ *                   (after a device synchronisation).  The copy costs n * 128 * NCH bytes, NCH = ceil(d / 64) rounded up
+ *                   to 1, 2, 4, 8 or 16 (the kernel's lane grid, zero padded), counted in hnsw_index_info.device_bytes.  Refused, the index unchanged: HNSW_ERR_BAD_ARG while byte rows are in
+ *                   use (they are exact and half the size: set "byte_rows" 0 first; "byte_rows" 1 later puts them
+ *                   first again), HNSW_ERR_UNSUPPORTED when a value is NaN or rounds to an fp16 infinity (|x| >= 65520).
+ *                   The builder, hnsw_index_insert's searches, the layer operators and hnsw_distance_batch keep reading
+ *                   the float32 rows.  hnsw_index_insert makes the copy again for the grown index (new vectors out of
+ *                   range: the whole insert is refused).  Not saved: a loaded index starts without half rows.
+ *                   (Hand-scheduled loops exist for the other row formats only: half rows run the C++ hop loop.) */
 int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value);
-/* Bytes of one vector as the knn searches read it: d for byte rows, 4 * d for float32 rows. */
+/* Bytes of one vector as the knn searches read it: d for byte rows, 2 * d for half rows, 4 * d for float32 rows. */
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes);
 /* Mean durations (ms) over the device-entry calls recorded since the last call of this function
  * (option "time_kernels"): the search kernel itself, and the ordering pre-pass (descent kernel +
@@ -508,7 +527,7 @@ int32_t hnsw_index_layer_isolated(const hnsw_index *idx, int32_t layer, int64_t 
  * the locality codes, if built (n int32), and for every prepared / measured kernel shape whether it took the bitmap blocks --
  * hnsw_index_load adopts the codes (a permutation check: a corrupt table is dropped and rebuilt on demand) and the decisions
  * instead of building and measuring again, and prepares the saved shapes, so the first search after a load runs at the
- * steady-state rate. */
+ * steady-state rate.  Option "half_rows" is not saved (the format is unchanged): a loaded index starts without half rows. */
 int32_t hnsw_index_save(const hnsw_index *idx, const char *path);
 int32_t hnsw_index_load(const char *path, int32_t device, hnsw_index **out);
 

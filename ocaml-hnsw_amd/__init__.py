@@ -26,6 +26,8 @@ ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED = -4, -5, -6, -7
 METRIC_L2, METRIC_IP = 0, 1
 FILL_OHNSW, FILL_BA = 0, 1
 SEM_OHNSW, SEM_FUNCTOR, SEM_FUNCTOR_NEAREST_K = 0, 1, 2
+# IndexInfo.row_format: what the knn searches read (HNSW_ROWS_*); ROWS_HALF only after set_option("half_rows", 1)
+ROWS_F32, ROWS_BYTES, ROWS_SPLIT, ROWS_HALF = 0, 2, 3, 4
 
 # every symbol include/hnsw_mi355x.h declares (tests check the .so exports all of them)
 ABI_VERSION = 3          # HNSW_ABI_VERSION of include/hnsw_mi355x.h this mirror was written against
@@ -403,7 +405,7 @@ class Hgraph:
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
 
     def row_bytes(self):
-        """Bytes of one vector as the knn searches read it (d: byte rows, 4 d: float32 rows)."""
+        """Bytes of one vector as the knn searches read it (d: byte rows, 2 d: half rows, 4 d: float32 rows)."""
         v = _C.c_int64(0)
         _check(load().hnsw_index_row_bytes(self.handle, _C.byref(v)))
         return v.value

@@ -484,9 +484,12 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
         if (!overflow) break;
     }
     // ... and what the handle derives from the graph, made again for it: the byte rows if ALL vectors are byte-valued, the split
-    // rows (per-slot tails follow the changed adjacency) unless option split_rows -1 freed them for good, the locality codes
+    // rows (per-slot tails follow the changed adjacency) unless option split_rows -1 freed them for good, the half rows while
+    // option half_rows is 1 (new vectors that do not fit fp16 refuse the whole insert; at 0 the copy is not carried over), the
+    // locality codes
     if (!rc) rc = make_byte_rows(nx);
     if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx);
+    if (!rc && idx->half_rows_on) rc = make_half_rows(nx);
     if (!rc) rc = extend_locality_codes(idx, nx);
     if (rc) {
         if (nx) hnsw_index_destroy(nx);
@@ -498,7 +501,7 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
         const hipError_t e = hipDeviceSynchronize();
         if (e != hipSuccess) { hnsw_index_destroy(nx); return fail(HNSW_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); }
     }
-    const bool bytes_before = idx->iv.X8 != nullptr, split_before = idx->iv.Xm != nullptr;
+    const int rows_before = idx->info.row_format;
     std::swap(idx->tables, nx->tables);                    // (nx takes the old tables with it)
     idx->iv = nx->iv;
     idx->info = nx->info;
@@ -507,7 +510,7 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
     hnsw_index_destroy(nx);
     // the per-shape choices that follow n or the row format
     idx->resident_queries = 0; idx->vt_grow_key = -1;
-    if (bytes_before != (idx->iv.X8 != nullptr) || split_before != (idx->iv.Xm != nullptr))
+    if (rows_before != idx->info.row_format)
         for (auto &c : idx->blk_choice) c[0] = c[1] = -1;
     if (idx->fb_queries > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.cap / (n * 4), 65536);
     // the grown index is searched at the steady-state rate from its first call, as a loaded one

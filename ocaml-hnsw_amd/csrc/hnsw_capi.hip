@@ -132,10 +132,10 @@ int upload_upper_layout(IndexTables &t, int64_t n0, const std::vector<int2> &ref
     hipError_t search_launch_##m##_##s##_##f(int nch, int nslot, const IndexView &iv, const SearchArgs &a, hipStream_t st); \
     int search_occupancy_##m##_##s##_##f(int nch, int nslot, size_t lds, int blk);                                    \
     }
-HNSW_DECL_VARIANT(0, 0, 0) HNSW_DECL_VARIANT(0, 0, 1) HNSW_DECL_VARIANT(0, 0, 2) HNSW_DECL_VARIANT(0, 0, 3)
-HNSW_DECL_VARIANT(0, 1, 0) HNSW_DECL_VARIANT(0, 1, 1) HNSW_DECL_VARIANT(0, 1, 2) HNSW_DECL_VARIANT(0, 1, 3)
-HNSW_DECL_VARIANT(1, 0, 0) HNSW_DECL_VARIANT(1, 0, 1) HNSW_DECL_VARIANT(1, 0, 2) HNSW_DECL_VARIANT(1, 0, 3)
-HNSW_DECL_VARIANT(1, 1, 0) HNSW_DECL_VARIANT(1, 1, 1) HNSW_DECL_VARIANT(1, 1, 2) HNSW_DECL_VARIANT(1, 1, 3)
+HNSW_DECL_VARIANT(0, 0, 0) HNSW_DECL_VARIANT(0, 0, 1) HNSW_DECL_VARIANT(0, 0, 2) HNSW_DECL_VARIANT(0, 0, 3) HNSW_DECL_VARIANT(0, 0, 4)
+HNSW_DECL_VARIANT(0, 1, 0) HNSW_DECL_VARIANT(0, 1, 1) HNSW_DECL_VARIANT(0, 1, 2) HNSW_DECL_VARIANT(0, 1, 3) HNSW_DECL_VARIANT(0, 1, 4)
+HNSW_DECL_VARIANT(1, 0, 0) HNSW_DECL_VARIANT(1, 0, 1) HNSW_DECL_VARIANT(1, 0, 2) HNSW_DECL_VARIANT(1, 0, 3) HNSW_DECL_VARIANT(1, 0, 4)
+HNSW_DECL_VARIANT(1, 1, 0) HNSW_DECL_VARIANT(1, 1, 1) HNSW_DECL_VARIANT(1, 1, 2) HNSW_DECL_VARIANT(1, 1, 3) HNSW_DECL_VARIANT(1, 1, 4)
 #undef HNSW_DECL_VARIANT
 
 // probe queries of the visited-structure measurement (knn_blk_bits): query j = the midpoint between node j * step's vector and
@@ -153,19 +153,28 @@ namespace {
 
 typedef hipError_t (*search_launch_fn)(int, int, const IndexView &, const SearchArgs &, hipStream_t);
 typedef int (*search_occupancy_fn)(int, int, size_t, int);
-const search_launch_fn k_launch[2][2][4] = {
-    {{search_launch_0_0_0, search_launch_0_0_1, search_launch_0_0_2, search_launch_0_0_3}, {search_launch_0_1_0, search_launch_0_1_1, search_launch_0_1_2, search_launch_0_1_3}},
-    {{search_launch_1_0_0, search_launch_1_0_1, search_launch_1_0_2, search_launch_1_0_3}, {search_launch_1_1_0, search_launch_1_1_1, search_launch_1_1_2, search_launch_1_1_3}}};
-const search_occupancy_fn k_occupancy[2][2][4] = {
-    {{search_occupancy_0_0_0, search_occupancy_0_0_1, search_occupancy_0_0_2, search_occupancy_0_0_3}, {search_occupancy_0_1_0, search_occupancy_0_1_1, search_occupancy_0_1_2, search_occupancy_0_1_3}},
-    {{search_occupancy_1_0_0, search_occupancy_1_0_1, search_occupancy_1_0_2, search_occupancy_1_0_3}, {search_occupancy_1_1_0, search_occupancy_1_1_1, search_occupancy_1_1_2, search_occupancy_1_1_3}}};
+constexpr int ROW_VARIANTS = 5;          // HNSW_V_FULL 0..4, see variant_full
+const search_launch_fn k_launch[2][2][ROW_VARIANTS] = {
+    {{search_launch_0_0_0, search_launch_0_0_1, search_launch_0_0_2, search_launch_0_0_3, search_launch_0_0_4},
+     {search_launch_0_1_0, search_launch_0_1_1, search_launch_0_1_2, search_launch_0_1_3, search_launch_0_1_4}},
+    {{search_launch_1_0_0, search_launch_1_0_1, search_launch_1_0_2, search_launch_1_0_3, search_launch_1_0_4},
+     {search_launch_1_1_0, search_launch_1_1_1, search_launch_1_1_2, search_launch_1_1_3, search_launch_1_1_4}}};
+const search_occupancy_fn k_occupancy[2][2][ROW_VARIANTS] = {
+    {{search_occupancy_0_0_0, search_occupancy_0_0_1, search_occupancy_0_0_2, search_occupancy_0_0_3, search_occupancy_0_0_4},
+     {search_occupancy_0_1_0, search_occupancy_0_1_1, search_occupancy_0_1_2, search_occupancy_0_1_3, search_occupancy_0_1_4}},
+    {{search_occupancy_1_0_0, search_occupancy_1_0_1, search_occupancy_1_0_2, search_occupancy_1_0_3, search_occupancy_1_0_4},
+     {search_occupancy_1_1_0, search_occupancy_1_1_1, search_occupancy_1_1_2, search_occupancy_1_1_3, search_occupancy_1_1_4}}};
 
-// the knn kernel's row format: 2 = byte rows (hnsw_rows8.hip), 3 = split fp32 rows (hnsw_rows_split.hip), else plain fp32
-// rows, 1 = every chunk of the lane grid inside the row
+// the knn kernel's row format: 2 = byte rows (hnsw_rows8.hip), 3 = split fp32 rows (hnsw_rows_split.hip), 4 = half rows
+// (hnsw_rows16.hip), else plain fp32 rows, 1 = every chunk of the lane grid inside the row.  (From the record bind_view keeps:
+// byte and half rows share IndexView's pointer.)
 inline int variant_full(const hnsw_index *idx) {
-    if (idx->iv.X8) return 2;
-    if (idx->iv.Xm) return 3;
-    return idx->iv.nchunks == 16 * pick_nch(idx->iv.nchunks) ? 1 : 0;
+    switch (idx->info.row_format) {
+    case HNSW_ROWS_BYTES: return 2;
+    case HNSW_ROWS_SPLIT: return 3;
+    case HNSW_ROWS_HALF: return 4;
+    default: return idx->iv.nchunks == 16 * pick_nch(idx->iv.nchunks) ? 1 : 0;
+    }
 }
 
 template <int METRIC>
@@ -199,7 +208,7 @@ int knn_vt_bits(hnsw_index *idx, int ef, int semf) {
     const int base = search_vt_bits(idx, ef);
     if (idx->vt_bits_override || env_int("HNSW_VT_BITS", 0) > 0 || !env_int("HNSW_VT_GROW", 1)) return base;
     const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(ef, nch);
-    const int vkey = ((nslot * 2 + semf) * 4 + variant_full(idx)) * 32 + base;
+    const int vkey = ((nslot * 2 + semf) * ROW_VARIANTS + variant_full(idx)) * 32 + base;
     if (idx->vt_grow_key == vkey) return idx->vt_grow_bits;
     const search_occupancy_fn occ = k_occupancy[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][semf][variant_full(idx)];
     const int occ0 = occ(nch, nslot, hnsw_dev::wave_lds_words(base) * sizeof(uint32_t), 0);
@@ -317,7 +326,7 @@ int64_t resident_queries(hnsw_index *idx, int ef, int semf) {
     // cached in the handle; the answer depends on the kernel variant's registers and LDS
     const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(ef, nch);
     const size_t lds = knn_lds_bytes(idx, ef, semf);
-    const int vkey = (nslot * 2 + semf) * 4 + variant_full(idx);
+    const int vkey = (nslot * 2 + semf) * ROW_VARIANTS + variant_full(idx);
     if (idx->resident_queries && idx->resident_nslot == vkey && idx->resident_lds == lds) return idx->resident_queries;
     const int per_cu = k_occupancy[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][semf][variant_full(idx)](nch, nslot, lds, knn_blk_bits(idx, ef, semf) > 0);
     int cus = 0;
@@ -346,7 +355,7 @@ int balanced_lds_pad(hnsw_index *idx, int64_t nq, int ef, int semf) {
     if (nq <= resident || idx->resident_per_cu <= 0) return 0;
     // byte rows: a quarter of the bytes per evaluation, the launch is bound by the latency of a hop, not by the
     // memory system, and holds as many queries as the registers allow (C2: 0.60 ms per call at 8192 held, 0.65 at 5376)
-    if (idx->iv.X8) return 0;
+    if (variant_full(idx) == 2) return 0;
     constexpr int64_t GRANULE = 1280, GRANULES_PER_CU = 128;
     const int64_t base = (int64_t)knn_lds_bytes(idx, ef, semf);
     const int64_t passes = (nq + resident - 1) / resident;
@@ -470,9 +479,14 @@ static int warm_up_steps(hnsw_index *idx) {
 void bind_view(hnsw_index *idx) {
     const IndexTables &t = idx->tables;
     IndexView &iv = idx->iv;
+    // the knn searches read, in this order of precedence: byte rows (exact, the smallest), half rows (option half_rows 1),
+    // split rows, the plain float32 rows
+    const bool bytes = !idx->byte_rows_off && t.X8.p, half = !bytes && idx->half_rows_on && t.Xh.p;
     iv.X = (const float *)t.X.p;
-    iv.X8 = idx->byte_rows_off ? nullptr : (const uint8_t *)t.X8.p;
-    iv.Xm = idx->split_rows_off ? nullptr : (const float *)t.Xm.p;
+    iv.X8 = bytes ? (const uint8_t *)t.X8.p : nullptr;
+    if (half) iv.Xh = (const uint2 *)t.Xh.p;
+    iv.stride8 = (half ? 128 : 64) * pick_nch(iv.nchunks);
+    iv.Xm = idx->split_rows_off || half ? nullptr : (const float *)t.Xm.p;
     iv.tail0 = (const float *)t.tail0.p;
     iv.nbr0 = (const int32_t *)t.nbr0.p; iv.nbrU = (const int32_t *)t.nbrU.p;
     iv.upper_off = (const int32_t *)t.off.p; iv.upper_lvl = (const uint8_t *)t.lvl.p; iv.upper_ref = (const int2 *)t.ref.p;
@@ -480,6 +494,7 @@ void bind_view(hnsw_index *idx) {
     hnsw_index_info &inf = idx->info;
     inf.n = iv.n; inf.max_degree0 = iv.S0; inf.max_layer = iv.max_layer; inf.entry_point = (int64_t)iv.entry_point + iv.id_base;
     inf.row_stride_bytes = iv.stride * 4;
+    inf.row_format = bytes ? HNSW_ROWS_BYTES : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
 }
 
 int finish_index(hnsw_index *idx, int32_t expected_ef, int32_t expected_semantics, hnsw_index **out) {
@@ -622,7 +637,6 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info) {
     if (!idx || !info) return fail(HNSW_ERR_BAD_ARG, "null argument");
     *info = idx->info;
     info->device_bytes = (int64_t)idx->tables.bytes();
-    info->row_format = idx->iv.X8 ? HNSW_ROWS_BYTES : idx->iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
     return HNSW_OK;
 }
 
@@ -710,7 +724,8 @@ void list_blk_choices(const hnsw_index *idx, std::vector<int32_t> &out3) {
 
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes) {
     if (!idx || !row_bytes) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    *row_bytes = idx->iv.X8 ? (int64_t)idx->iv.d : (int64_t)idx->iv.d * 4;
+    const int f = idx->info.row_format;
+    *row_bytes = (int64_t)idx->iv.d * (f == HNSW_ROWS_BYTES ? 1 : f == HNSW_ROWS_HALF ? 2 : 4);
     return HNSW_OK;
 }
 
@@ -738,6 +753,28 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         }
         idx->split_rows_off = value <= 0;
         idx->split_rows_freed = idx->split_rows_freed || value < 0;
+        bind_view(idx);
+        forget_shape_choices();
+        return HNSW_OK;
+    }
+    if (!strcmp(name, "half_rows")) {     // 1: search the fp16 copy (made now if missing); 0: the fp32 / split rows again, the copy kept; -1: ... and freed
+        if (value > 0) {
+            if (idx->info.row_format == HNSW_ROWS_BYTES)
+                return fail(HNSW_ERR_BAD_ARG, "half_rows: the index searches its byte rows, which are exact and half the size of half rows "
+                                              "(set byte_rows 0 first)");
+            if (!idx->tables.Xh.p) {
+                const int rc = make_half_rows(idx);     // (a refusal -- NaN, fp16 overflow -- leaves the index as it was)
+                if (rc) return rc;
+            }
+            idx->half_rows_on = true;
+        } else {
+            if (value < 0 && idx->tables.Xh.p) {
+                HIP_TRY(hipSetDevice(idx->device));
+                HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy
+                idx->tables.Xh.release();
+            }
+            idx->half_rows_on = false;
+        }
         bind_view(idx);
         forget_shape_choices();
         return HNSW_OK;

@@ -56,10 +56,14 @@ struct IndexView {
     int32_t max_layer;
     int32_t entry_point;     // 0-based, -1 = empty
     int32_t id_base;
-    // optional lossless copy of X for data whose every value is an integer in 0..255 (SIFT descriptors): rows of
-    // 64*NCH bytes, zero padded; chunk c of a row (dims 4c..4c+3) is one dword.  nullptr = not available / switched off
-    const uint8_t *X8;
-    int32_t stride8;         // bytes per byte row
+    // optional compact copy of X that the knn kernel reads instead of it; at most one of the two is in the view, and the
+    // kernel's ROWS parameter says which (the host's record: hnsw_index_info.row_format).  nullptr = not available / switched off
+    //   X8 (ROWS 2): a lossless copy for data whose every value is an integer in 0..255 (SIFT descriptors): rows of 64*NCH
+    //       bytes, zero padded; chunk c of a row (dims 4c..4c+3) is one dword
+    //   Xh (ROWS 4, option "half_rows"): the values rounded to fp16: rows of 128*NCH bytes, zero padded; chunk c is 8 bytes
+    // (one member for both, so that the view's layout -- every kernel's arguments -- is what it was before half rows existed)
+    union { const uint8_t *X8; const uint2 *Xh; };
+    int32_t stride8;         // bytes per row of that copy
     // optional split copy of X for rows that end a little past a 128-byte line (4d mod 128 in 1..32, e.g. d = 100: 400 B =
     // three lines + 16 B; hnsw_rows_split.hip): the first main_chunks float4 chunks of every row in a table of 128-byte
     // multiples (a row costs exactly main_chunks / 8 lines), and the remaining tail_chunks chunks stored beside the
@@ -121,6 +125,10 @@ template <int METRIC> __device__ __forceinline__ float key_to_dist(uint32_t key)
     uint32_t b = (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key;
     return __uint_as_float(b);
 }
+
+// ---- half rows (ROWS 4): the low / high fp16 of a dword as float -- exact (v_cvt_f32_f16; the high half by SDWA) ------------
+__device__ __forceinline__ float half_lo(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(u & 0xFFFFu)); }
+__device__ __forceinline__ float half_hi(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(u >> 16)); }
 
 // ---- DPP helpers ---------------------------------------------------------------------------
 template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
@@ -712,13 +720,16 @@ __device__ __forceinline__ int adj_entry(const IndexView &iv, int layer, int c, 
 // chunk c of a row is still evaluated by lane c % 16 in its (c / 16)-th step -- but the lanes whose chunk lies in the
 // tail take it from the expanded node's tail row (`tail_row`, at the candidate's position in that node's adjacency row,
 // which the compaction left in cand_key[]) instead of from a fourth 128-byte line of the vector's own row.
+// 4 = half rows (IndexView::Xh, hnsw_rows16.hip): one uint2 per chunk -- a group's step is one whole 128-byte line --,
+// each half converted to float exactly, then the arithmetic of the fp32 row: the result is that of the fp32 row of
+// X rounded to fp16 bit for bit.  (The zero padding of a half row meets the zero padding of the query: it adds +0.)
 template <int NCH, int NB, int METRIC, int ROWS>
 __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv)[NCH], const WaveCtx &cx,
                                           int base, int cnt, uint32_t &out_key, uint32_t &out_id,
                                           const char *tail_row = nullptr) {
-    constexpr bool FULL = ROWS == 1 || ROWS == 2;
+    constexpr bool FULL = ROWS == 1 || ROWS == 2 || ROWS == 4;
     const int r = cx.r, l16 = cx.l16;
-    const uint32_t stride_b = ROWS == 2 ? (uint32_t)iv.stride8 : (uint32_t)iv.stride * 4u;
+    const uint32_t stride_b = (ROWS == 2 || ROWS == 4) ? (uint32_t)iv.stride8 : (uint32_t)iv.stride * 4u;
     const int mine = base + NB * r;
     uint32_t id[NB];
 #pragma unroll
@@ -726,9 +737,18 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
         const int ci = (mine + b < cnt) ? mine + b : base + b;   // base + b < cnt: a round of NB batches has > 4*(NB-1) candidates
         id[b] = (uint32_t)cx.cand_id[ci];
     }
-    float4 v[ROWS == 2 ? 1 : NB][ROWS == 2 ? 1 : NCH];
+    float4 v[ROWS == 2 || ROWS == 4 ? 1 : NB][ROWS == 2 || ROWS == 4 ? 1 : NCH];
     uint32_t v8[ROWS == 2 ? NB : 1][ROWS == 2 ? NCH : 1];
-    if constexpr (ROWS == 2) {
+    uint2 vh[ROWS == 4 ? NB : 1][ROWS == 4 ? NCH : 1];
+    if constexpr (ROWS == 4) {
+        const char *xlane = reinterpret_cast<const char *>(iv.Xh) + 8 * l16;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const uint2 *row = reinterpret_cast<const uint2 *>(xlane + (uint64_t)id[b] * stride_b);
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) vh[b][i] = row[i * 16];
+        }
+    } else if constexpr (ROWS == 2) {
         const char *xlane = reinterpret_cast<const char *>(iv.X8) + 4 * l16;
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
@@ -852,6 +872,8 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
             if constexpr (ROWS == 2) {
                 const uint32_t u = v8[b][i];
                 z = make_float4((float)(u & 0xFFu), (float)((u >> 8) & 0xFFu), (float)((u >> 16) & 0xFFu), (float)(u >> 24));
+            } else if constexpr (ROWS == 4) {
+                z = make_float4(half_lo(vh[b][i].x), half_hi(vh[b][i].x), half_lo(vh[b][i].y), half_hi(vh[b][i].y));
             } else {
                 z = v[b][i];
             }
@@ -935,6 +957,7 @@ __device__ __forceinline__ void greedy_descend(const IndexView &iv, const float4
             for (int base = 0; base < cnt;) {
                 uint32_t ckey, cid;
                 if (ROWS == 2) base += eval_round<NCH, RB, METRIC, 2>(iv, qv, cx, base, cnt, ckey, cid);
+                else if (ROWS == 4) base += eval_round<NCH, RB, METRIC, 4>(iv, qv, cx, base, cnt, ckey, cid);   // (half rows: every layer, as the oracle's space over Xh)
                 else if (ROWS == 1 || (ROWS < 0 && full_rows)) base += eval_round<NCH, RB, METRIC, 1>(iv, qv, cx, base, cnt, ckey, cid);
                 else base += eval_round<NCH, RB, METRIC, 0>(iv, qv, cx, base, cnt, ckey, cid);
                 const uint32_t mk = wave_min_u32(ckey);
@@ -1142,7 +1165,8 @@ namespace hnsw_dev {
 // in the oracle's TIES_HEAP mode) is fixed to (d, id) here: VisitMe pops the smallest id first, a
 // replacement evicts the largest id of the farthest class.
 // ROWS: 1 = every float4 chunk of the 16 x NCH lane grid lies inside a row (d in 64*NCH-3 .. 64*NCH: no
-// masking), 0 = ragged rows, 2 = byte rows (see hop_round), -1 = fp32 rows, shape decided at run time (the builder and
+// masking), 0 = ragged rows, 2 = byte rows, 3 = split rows, 4 = half rows (see hop_round; 4 never has a hand-scheduled
+// loop: HopLoop's primary template), -1 = fp32 rows, shape decided at run time (the builder and
 // the layer operators; the knn kernel is instantiated per case so that neither pays for the other's registers).
 // BLK 1 (the knn kernel's layer-0 search only): Visited is the bitmap-block cache over the neighbours' locality codes
 // (visited_blocks_mem_add) instead of the tag cache.
@@ -1304,6 +1328,7 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
                 hop_eval<NCH, RB, NSLOT, METRIC, SEM, 3>(iv, qv, w, cx, cnt, status, pc,
                                                          reinterpret_cast<const char *>(iv.tail0) + (uint64_t)(uint32_t)c * (uint32_t)(iv.S0 * 16 * iv.tail_chunks));
             else if (ROWS == 2) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 2>(iv, qv, w, cx, cnt, status, pc);                                  // :573-577
+            else if (ROWS == 4) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 4>(iv, qv, w, cx, cnt, status, pc);
             else if (ROWS == 1 || (ROWS < 0 && full_rows)) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 1>(iv, qv, w, cx, cnt, status, pc);
             else hop_eval<NCH, RB, NSLOT, METRIC, SEM, 0>(iv, qv, w, cx, cnt, status, pc);
         }
@@ -1395,7 +1420,7 @@ __device__ __forceinline__ void load_row(float4 (&qv)[NCH], const IndexView &iv,
     (((NCH) <= 2 && (NSLOT) <= 2 && (METRIC) == 0 && (ROWS) == 1) ? 7 : \
      (HNSW_ASM_LOOP && (NCH) == 2 && (NSLOT) <= 4 && (METRIC) == 0 && (ROWS) == 2 && ((SEMF) == 0 || HNSW_SEM1_8WAVES)) ? 8 : 1)
 #endif
-// SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3, see hop_round
+// SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3 | 4, see hop_round
 // BLK: 1 = Visited as bitmap blocks (a.blk_bits slots, iv.lcode / lcode0 present), see search_layer
 template <int NCH, int RB, int NSLOT, int METRIC, int SEMF, int ROWS, int BLK = 0>
 __global__ void __launch_bounds__(64, HNSW_SEARCH_MIN_WAVES(NCH, NSLOT, METRIC, ROWS, SEMF))
@@ -1514,9 +1539,9 @@ hnsw_descent_kernel(const IndexView iv, const float *Q, int64_t q_stride, int64_
     if (lane == 0) cx.cand_id[0] = cur;
     __syncthreads();
     uint32_t cur_key;
-    if (ROWS == 2) {
+    if (ROWS == 2 || ROWS == 4) {     // (the compact rows: their own evaluation, as in the search kernel)
         uint32_t ck, ci;
-        hop_round<NCH, 1, METRIC, ROWS == 2 ? 2 : 1>(iv, qv, cx, 0, 1, ck, ci);
+        hop_round<NCH, 1, METRIC, ROWS == 2 || ROWS == 4 ? ROWS : 1>(iv, qv, cx, 0, 1, ck, ci);
         cur_key = rdlane(ck, 0);
     } else {
         eval_candidates<NCH, RB, METRIC>(iv, qv, cx.cand_id, cx.cand_key, cx.trash, 1, cx.r, cx.l16);

@@ -57,12 +57,12 @@ struct Table {
 };
 
 // Every device table an index holds: the vectors and the graph, and the copies derived from them -- byte rows (X8, hnsw_rows8.hip),
-// split rows (Xm / tail0, hnsw_rows_split.hip), locality codes (lcode / lcode0, hnsw_locality.hip); a derived table that does not
-// exist has p == nullptr.  bind_view points the handle's IndexView at them.
+// half rows (Xh, hnsw_rows16.hip), split rows (Xm / tail0, hnsw_rows_split.hip), locality codes (lcode / lcode0, hnsw_locality.hip);
+// a derived table that does not exist has p == nullptr.  bind_view points the handle's IndexView at them.
 struct IndexTables {
-    Table X, X8, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
+    Table X, X8, Xh, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
     template <class Self, class F> static void each(Self &t, F f) {
-        static constexpr Table IndexTables::*all[] = {&IndexTables::X, &IndexTables::X8, &IndexTables::Xm, &IndexTables::tail0,
+        static constexpr Table IndexTables::*all[] = {&IndexTables::X, &IndexTables::X8, &IndexTables::Xh, &IndexTables::Xm, &IndexTables::tail0,
                                                       &IndexTables::lcode, &IndexTables::lcode0, &IndexTables::nbr0, &IndexTables::nbrU,
                                                       &IndexTables::off, &IndexTables::lvl, &IndexTables::ref};
         for (Table IndexTables::*m : all) f(t.*m);
@@ -180,14 +180,18 @@ struct hnsw_index {
     // hnsw_index_insert, which makes the row copies again, keeps their effect: byte_rows 0, split_rows 0 (off), split_rows -1
     // (off and freed for good)
     bool byte_rows_off = false, split_rows_off = false, split_rows_freed = false;
+    // option "half_rows": the knn searches read tables.Xh (1), or it is off (0, -1).  Not a default: half rows change results.
+    // hnsw_index_insert makes the copy again while it is on.
+    bool half_rows_on = false;
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
 };
 
 namespace hnsw_host {
 
-// hnsw_capi.hip: IndexView's table pointers from idx->tables (X8 / Xm left out while option byte_rows / split_rows is 0), and the
-// hnsw_index_info fields that restate the view (n, max_degree0, max_layer, entry_point, row_stride_bytes).  Called by every
-// change of the tables or of those options.
+// hnsw_capi.hip: IndexView's table pointers from idx->tables (X8 / Xm left out while option byte_rows / split_rows is 0; Xh in
+// the view while option half_rows is 1 and no byte rows are: it takes the place of Xm), and the hnsw_index_info fields that
+// restate the view (n, max_degree0, max_layer, entry_point, row_stride_bytes, row_format).  Called by every change of the tables
+// or of those options.
 void bind_view(::hnsw_index *idx);
 // hnsw_capi.hip: the end of hnsw_index_create and hnsw_build, once the graph tables are complete: the view bound, the row copies
 // made, the first search's one-time costs paid.  *out = idx on success; on an error idx is destroyed.
@@ -195,6 +199,9 @@ int finish_index(::hnsw_index *idx, int32_t expected_ef, int32_t expected_semant
 
 // hnsw_rows8.hip: if every value of tables.X is an integer in 0..255, build the byte copy (tables.X8, iv.stride8)
 int make_byte_rows(::hnsw_index *idx);
+// hnsw_rows16.hip: the half copy of tables.X (tables.Xh): HNSW_ERR_UNSUPPORTED, nothing allocated, when a value is NaN or
+// rounds to an fp16 infinity; HNSW_ERR_OOM when there is no room for it.  Leaves the view to the caller (bind_view).
+int make_half_rows(::hnsw_index *idx);
 // hnsw_rows_split.hip: if a row ends 1..32 bytes past a 128-byte line (and there are no byte rows), build the split copy
 // (tables.Xm / tail0, iv.stride_m / main_chunks / tail_chunks); call after make_byte_rows, graph in place
 int make_split_rows(::hnsw_index *idx);

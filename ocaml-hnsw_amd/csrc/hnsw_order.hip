@@ -86,7 +86,7 @@ hipError_t launch_descent_rows(int nch, const IndexView &iv, const float *Q, int
                                uint32_t *nd, uint32_t *sortkey, int32_t *index, float *stage, hipStream_t st) {
     const size_t lds = hnsw_dev::wave_lds_words(4) * sizeof(uint32_t);
     dim3 grid((unsigned)nq), block(64);
-    constexpr bool B = ROWS == 2;            // byte rows: a quarter of the registers per row in flight
+    constexpr bool B = ROWS == 2 || ROWS == 4;   // byte / half rows: a quarter / half of the registers per row in flight
     switch (nch) {
     case 1: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<1, 8, METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
     case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<2, (B ? 8 : HNSW_RB_NCH2), METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
@@ -96,11 +96,16 @@ hipError_t launch_descent_rows(int nch, const IndexView &iv, const float *Q, int
     }
     return hipGetLastError();
 }
+// the descent reads what the knn kernel reads on the upper layers (row_format: hnsw_index_info.row_format; split rows serve
+// layer 0 only)
 template <int METRIC>
-hipError_t launch_descent(int nch, const IndexView &iv, const float *Q, int64_t qs, int64_t nq, int32_t to_layer, int32_t *entry, uint32_t *key,
-                          uint32_t *nd, uint32_t *sortkey, int32_t *index, float *stage, hipStream_t st) {
-    return iv.X8 ? launch_descent_rows<METRIC, 2>(nch, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage, st)
-                 : launch_descent_rows<METRIC, -1>(nch, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage, st);
+hipError_t launch_descent(int row_format, int nch, const IndexView &iv, const float *Q, int64_t qs, int64_t nq, int32_t to_layer, int32_t *entry,
+                          uint32_t *key, uint32_t *nd, uint32_t *sortkey, int32_t *index, float *stage, hipStream_t st) {
+    switch (row_format) {
+    case HNSW_ROWS_BYTES: return launch_descent_rows<METRIC, 2>(nch, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage, st);
+    case HNSW_ROWS_HALF: return launch_descent_rows<METRIC, 4>(nch, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage, st);
+    default: return launch_descent_rows<METRIC, -1>(nch, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage, st);
+    }
 }
 } // namespace
 
@@ -112,9 +117,12 @@ int descent_entries(::hnsw_index *idx, const float *d_queries, int64_t nq, int64
     const int nch = pick_nch(idx->iv.nchunks);
     uint32_t *key = d_scratch, *nd = d_scratch + nq, *sortkey = d_scratch + 2 * nq;
     int32_t *index = (int32_t *)(d_scratch + 3 * nq);
+    // (the locality codes' descents: over X whatever option half_rows says -- byte rows are X itself -- so that the codes do not
+    // depend on it)
+    const int rows = idx->info.row_format == HNSW_ROWS_BYTES ? HNSW_ROWS_BYTES : HNSW_ROWS_F32;
     const hipError_t e = idx->info.metric == HNSW_METRIC_L2
-        ? launch_descent<0>(nch, idx->iv, d_queries, q_stride, nq, to_layer, d_entry, key, nd, sortkey, index, nullptr, st)
-        : launch_descent<1>(nch, idx->iv, d_queries, q_stride, nq, to_layer, d_entry, key, nd, sortkey, index, nullptr, st);
+        ? launch_descent<0>(rows, nch, idx->iv, d_queries, q_stride, nq, to_layer, d_entry, key, nd, sortkey, index, nullptr, st)
+        : launch_descent<1>(rows, nch, idx->iv, d_queries, q_stride, nq, to_layer, d_entry, key, nd, sortkey, index, nullptr, st);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "descent launch failed: %s", hipGetErrorString(e));
     return HNSW_OK;
 }
@@ -155,8 +163,8 @@ int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, i
     int32_t *index = (int32_t *)(base + 5 * slot), *order = (int32_t *)(base + 6 * slot);
     void *temp = base + 7 * slot;
     const int nch = pick_nch(idx->iv.nchunks);
-    e = idx->info.metric == HNSW_METRIC_L2 ? launch_descent<0>(nch, idx->iv, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st)
-                                           : launch_descent<1>(nch, idx->iv, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st);
+    e = idx->info.metric == HNSW_METRIC_L2 ? launch_descent<0>(idx->info.row_format, nch, idx->iv, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st)
+                                           : launch_descent<1>(idx->info.row_format, nch, idx->iv, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st);
     if (e == hipSuccess) {
         if (nq <= 16 * ORDER_THREADS && !env_int("HNSW_ORDER_FULL_SORT", 0)) {
             static_assert(ORDER_BUCKETS == 2 * ORDER_THREADS, "two counters per thread in the scan");

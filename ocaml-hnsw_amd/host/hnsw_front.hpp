@@ -35,6 +35,12 @@ inline void check(int rc) {
     throw std::runtime_error(msg);
 }
 
+// hnsw_index_info.row_format: what the knn searches read (HNSW_ROWS_*); HALF only after hnsw_index_set_option(h, "half_rows", 1),
+// which makes them search the vectors rounded to fp16
+namespace Rows {
+constexpr int F32 = HNSW_ROWS_F32, BYTES = HNSW_ROWS_BYTES, SPLIT = HNSW_ROWS_SPLIT, HALF = HNSW_ROWS_HALF;
+}
+
 // Flattened Ohnsw.Hgraph.t / Hnsw.Ba.Hgraph.t resident on the device.
 class Hgraph {
 public:

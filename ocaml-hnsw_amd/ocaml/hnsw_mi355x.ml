@@ -77,7 +77,8 @@ let hnsw_index_set_option =
 (* bytes of one vector as the knn searches read it: d when the library serves byte-valued data (SIFT: float32
    values that are all integers 0..255) from its lossless byte copy of the rows, 4 d otherwise.  Nothing to do on
    this side: the copy is built by hnsw_index_create itself and is invisible to knn_batch* (same results, bit for
-   bit); `hnsw_index_set_option idx "byte_rows" 0L` reads the float32 rows again. *)
+   bit); `hnsw_index_set_option idx "byte_rows" 0L` reads the float32 rows again.  2 d after
+   `hnsw_index_set_option idx "half_rows" 1L` (the vectors rounded to fp16: results change, see the C header). *)
 let hnsw_index_row_bytes =
   foreign ~from:lib "hnsw_index_row_bytes" (index @-> ptr int64_t @-> returning int32_t)
 let hnsw_index_kernel_times =
@@ -190,6 +191,12 @@ let ii_device_bytes = field index_info "device_bytes" int64_t
 let ii_row_stride_bytes = field index_info "row_stride_bytes" int64_t
 let ii_device = field index_info "device" int32_t
 let ii_row_format = field index_info "row_format" int32_t
+(* its values, HNSW_ROWS_*: float32 rows, byte rows, split rows, half rows (only after `hnsw_index_set_option idx
+   "half_rows" 1L`: the search over the vectors rounded to fp16) *)
+let rows_f32 = 0l
+let rows_bytes = 2l
+let rows_split = 3l
+let rows_half = 4l
 let () = seal index_info
 let hnsw_index_get_info = foreign ~from:lib "hnsw_index_get_info" (index @-> ptr index_info @-> returning int32_t)
 (* the flattened graph of a device index (built there by hnsw_build, or loaded from a file) back to the host *)
