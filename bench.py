@@ -8,8 +8,12 @@ lib/ohnsw.ml:877-897) over the batch, queries already resident in HBM; with N > 
 holds a replica of the index, searches its own 10,000-query shard and the per-shard results are
 all-gathered over RCCL (weak scaling: per-GPU work fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what `value` needs and nothing else: data, index, the first calls on it (`cold`), warm-up, the K timed
+steps, --dump-outputs, the line.  Every other leg named below, the checks, the roofline and the CPU baseline run with
+--full only (about three minutes more).
 
 `value` is measured the way the reference's benchmark times knn_batch (benchmark/benchmark.ml:89-96) and SURVEY 8d
 prescribes: host matrices in, host results out, one synchronous call per batch -- hnsw_search_batch, the body of
@@ -181,7 +185,7 @@ def driver_line(detail):
     c_["workload"] = str(c_.get("workload", ""))[:300]
     c_["rows"] = str(cfg.get("rows", ""))[:8].split(" ")[0]
     out["config"] = c_
-    r_ = _pick(roof, "bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "bytes_per_query", "row_bytes",
+    r_ = _pick(d_.get("roofline"), "bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "bytes_per_query", "row_bytes",
                "n_dist_per_query", "n_hops_per_query")
     if r_ is not None:
         r_["latency_floor"] = _pick(roof.get("latency_floor"), "longest_walk_hops", "lone_hop_us", "floor_ms", "kernel_over_floor",
@@ -331,6 +335,34 @@ def _restore_stdout(saved):
     os.close(saved)
 
 
+def finish(out, saved_stdout, dist=None):
+    """The end of every run.  Rank 0 (out = its result dictionary): everything measured to DETAIL_FILE beside this script
+    and to stderr, then the short driver line alone on stdout.  The other ranks pass None.  dist: leave the process group."""
+    if out is not None:
+        detail_txt = json.dumps(_finite(out), allow_nan=False)
+        path_ = os.path.join(ROOT, DETAIL_FILE)
+        try:
+            with open(path_, "w") as f_:
+                f_.write(detail_txt + "\n")
+        except OSError as e:
+            log("could not write %s: %r" % (path_, e))
+        print("[bench-detail] " + detail_txt, file=sys.stderr, flush=True)
+        line = driver_line(out)
+        r_, checks = out.get("roofline") or {}, out.get("checks") or {}
+        log("SUMMARY value %.0f q/s (%.4f ms/step, n_gpus %d); roofline frac %s (kernel %s ms, traffic %s B); cpu_baseline %s q/s; recall@10 %s; line %d bytes" %
+            (out["value"], out["ms_per_step"], out["n_gpus"], r_.get("frac"), r_.get("kernel_ms"), r_.get("traffic"),
+             (out.get("cpu_baseline") or {}).get("value"), checks.get("recall_at_10"), len(line)))
+        _restore_stdout(saved_stdout)
+        saved_stdout = None
+        print(line, flush=True)
+        os.dup2(2, 1)                      # whatever teardown prints does not follow the JSON line
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    if saved_stdout is not None:
+        os.close(saved_stdout)
+
+
 def main():
     saved_stdout = _stdout_to_stderr()
     ap = argparse.ArgumentParser()
@@ -355,7 +387,7 @@ def main():
     ap.add_argument("--no-others", action="store_true", help="skip the C3 / C5 configurations (object `others`; about 100 s)")
     ap.add_argument("--no-clustered", action="store_true", help="skip the clustered variant of C3 inside `others` (its dispatches carry C3's kernel name)")
     ap.add_argument("--pipelined", action="store_true",
-                    help="also time the same steps alternated over two HIP streams (extra object `pipelined`, never `value`); "
+                    help="with --full, also time the same steps alternated over two HIP streams (extra object `pipelined`, never `value`); "
                          "off by default so that the default run's kernel trace holds serialized launches only")
     ap.add_argument("--dataset", default=None,
                     help="optional real data instead of the synthetic C2 set: an ann-benchmarks .hdf5 file, or a "
@@ -364,6 +396,10 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps of `value`, write what their last step returned (ids, distances; N > 1: the "
                          "all-gathered table) as DIR/<name>.npy, for comparing two builds output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps of `value`, run every other leg too: device-resident and float32-row steps, the "
+                         "bandwidth point, checks and recall, roofline, CPU baseline, the other data sets and configurations, the "
+                         "live counter passes (the --no-* options leave single legs out)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -463,7 +499,7 @@ def main():
         hg = H.Ohnsw.build_batch_bigarray(X, args.M, args.efc, seed=1, device=gpu)
         build_s = time.time() - t0
         log("graph built on the GPU in %.1fs (max_layer %d)" % (build_s, hg.max_layer))
-        if multi or not args.no_cpu:
+        if multi or (args.full and not args.no_cpu):
             hg.export()
     if multi:
         deg0, nbr0, upper, entry = sharding.replicate_graph(dist, cdev, hg if rank == 0 else None, args.M)
@@ -616,7 +652,8 @@ def main():
     # ---- the very first call after the index upload (nothing of this index in any cache; its scratch buffers allocated in it --
     #      the kernels' code objects, the handle's stream and flag word are paid at index construction), then calls with the
     #      caches flushed in front (2 GiB written) on batches the device has never seen: what ONE call of the reference's benchmark
-    #      (benchmark/benchmark.ml:89-96) pays when it is not the twentieth of its kind ----
+    #      (benchmark/benchmark.ml:89-96) pays when it is not the twentieth of its kind.  A plain run makes these calls too
+    #      (a few ms): they leave the device as the warm-up finds it -- without them `value` at --warmup 0 or 1 is ~2.5 % lower ----
     cold = None
     if not args.dataset:
         sync()
@@ -646,7 +683,7 @@ def main():
                         "before and behind a 2 GiB write that empties L2 and the Infinity Cache"}
         log("first call after the index upload %.3f ms; calls on unseen batches behind a cache flush %.3f ms (median of 3)" % (first_ms, cts[1]))
     # the K timed steps of `value`, with the library's kernel events in them (roofline.kernel_ms is measured over THIS region;
-    # three event records per call cost 0.003-0.015 ms of a 0.44 ms step), and once more without, for the record
+    # three event records per call cost 0.003-0.015 ms of a 0.44 ms step), and with --full once more without, for the record
     wall, host_stats, host_lib = timed_host(ef, args.steps, args.warmup, instrument=True)
     if args.dump_outputs and rank == 0:     # before the next pass overwrites the result matrices
         if multi:
@@ -655,12 +692,45 @@ def main():
                          tab[:, 1].reshape(world * nq, k).view(torch.float32).numpy())
         else:
             dump_outputs(args.dump_outputs, host_i, host_d)
-    wall_hi = wall
-    wall_plain, _, _ = timed_host(ef, args.steps, 1)
     qps = world * nq * args.steps / wall
     search_ms, prepass_ms = host_lib["search_ms"], host_lib["prepass_ms"]
-    log("ef=%d, host matrices in and out: %.0f q/s, %.3f ms/step (median %.3f; %.3f without the kernel events); per step: ordering pre-pass %.3f ms + search kernel %.3f ms%s" %
-        (ef, qps, 1e3 * wall / args.steps, host_stats["median"], 1e3 * wall_plain / args.steps, prepass_ms, search_ms, " [byte rows]" if byte_rows else ""))
+    log("ef=%d, host matrices in and out: %.0f q/s, %.3f ms/step (median %.3f); per step: ordering pre-pass %.3f ms + search kernel %.3f ms%s" %
+        (ef, qps, 1e3 * wall / args.steps, host_stats["median"], prepass_ms, search_ms, " [byte rows]" if byte_rows else ""))
+    # what every run reports: the headline and its configuration (--full adds its legs to this further down)
+    out = {
+        "metric": "queries/sec at recall@10>=0.95, SIFT1M d=128 ef=128 k=10",
+        "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * wall / args.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        # the arithmetic of the timed kernel, not a precision claim: byte rows are gathered as uint8 and summed with
+        # v_dot4_u32_u8 (exact: every partial sum < 2^24, the float32 result bit for bit); float data computes in f32
+        "dtype": "u8" if byte_rows else "f32",
+        "dtype_note": "u8 rows, u32 dot products (exact) -> f32 distances" if byte_rows else "f32",
+        "data": ("file:" + os.path.basename(os.path.normpath(args.dataset))) if args.dataset else "synthetic",
+        "config": {"workload": "C2: %s (n=%d d=%d), M=%d efC=%d (built on the GPU), ef=%d k=%d, %d queries/GPU/step, replicated index%s"
+                               % ("vectors from " + args.dataset if args.dataset else "SIFT1M-shaped synthetic, clustered ints 0..218 as fp32",
+                                  n, d, args.M, args.efc, ef, k, nq, ", RCCL all-gather of results" if world > 1 else ""),
+                   "n": n, "d": d, "M": args.M, "ef_construction": args.efc, "ef": ef, "k": k,
+                   "queries_per_gpu": nq, "global_batch": world * nq, "parallelism": "replica x%d" % world,
+                   "batches_rotated": NB,
+                   "rows": "bytes (lossless copy of integer-valued float32 data)" if byte_rows else "float32"},
+        "cold_first_call_ms": None if not cold else cold["first_call_ms"],
+        "cold": cold,
+        "protocol": ("one synchronous call per %d-query batch with HOST matrices in and out, as benchmark/benchmark.ml:89-96 times knn_batch "
+                     "and SURVEY 8d prescribes; the warm-up and the timed steps rotate through %d distinct batches (seeds 2..%d): " % (nq, NB, 1 + NB)) +
+                    ("hnsw_search_batch (H2D of the queries, ordering pre-pass, search kernel, D2H of the results; the caller's matrices in "
+                     "page-locked memory: hnsw_host_alloc / hnsw_host_register)" if world == 1 else
+                     "per rank hnsw_search_batch_h2d (its registered query shard read by the device, ordering pre-pass, search kernel, results in "
+                     "HBM), RCCL all-gather of the per-shard results (the full table resident on every GPU), D2H of the rank's own shard, stream "
+                     "synchronisation") +
+                    "; the rate with the queries already resident in HBM and the results left there is `device_resident` (--full)",
+        "full": bool(args.full),
+    }
+    if not args.full:
+        finish(out if rank == 0 else None, saved_stdout, dist)
+        return
+    wall_plain, _, _ = timed_host(ef, args.steps, 1)
+    log("ef=%d, the same steps without the kernel events: %.3f ms/step" % (ef, 1e3 * wall_plain / args.steps))
     # ---- the same steps with the queries already resident in HBM and the results left there (hnsw_search_batch_device) ----
     wall_dev, _ = timed(ef, args.steps, args.warmup, instrument=False)
     wall_dev_i, kern_ms = timed(ef, args.steps, 1)
@@ -1717,40 +1787,15 @@ def main():
         # which synthetic set is the closer stand-in for SIFT1M (about 2.5-3 k evaluations per query at ef 128)
         nd_head = roofline["n_dist_per_query"] if roofline else None
         nd_hard = secondary["roofline"]["n_dist_per_query"] if secondary else None
-        out = {
-            "metric": "queries/sec at recall@10>=0.95, SIFT1M d=128 ef=128 k=10",
-            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * wall / args.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            # the arithmetic of the timed kernel, not a precision claim: byte rows are gathered as uint8 and summed with
-            # v_dot4_u32_u8 (exact: every partial sum < 2^24, the float32 result bit for bit); float data computes in f32
-            "dtype": "u8" if byte_rows else "f32",
-            "dtype_note": "u8 rows, u32 dot products (exact) -> f32 distances" if byte_rows else "f32",
-            "data": ("file:" + os.path.basename(os.path.normpath(args.dataset))) if args.dataset else "synthetic",
-            "config": {"workload": "C2: %s (n=%d d=%d), M=%d efC=%d (built on the GPU), ef=%d k=%d, %d queries/GPU/step, "
-                                   "replicated index%s; easier than SIFT1M (%s evals/query vs ~2.5-3k): see harder_set_at_recall_gate (%s)"
-                                   % ("vectors from " + args.dataset if args.dataset else "SIFT1M-shaped synthetic, clustered ints 0..218 as fp32",
-                                      n, d, args.M, args.efc, ef, k, nq,
-                                      ", RCCL all-gather of results" if world > 1 else "", nd_head, nd_hard),
-                       "n": n, "d": d, "M": args.M, "ef_construction": args.efc, "ef": ef, "k": k,
-                       "queries_per_gpu": nq, "global_batch": world * nq, "parallelism": "replica x%d" % world,
-                       "batches_rotated": NB,
-                       "rows": "bytes (lossless copy of integer-valued float32 data)" if byte_rows else "float32",
-                       "headline_set": {"n_dist_per_query": nd_head, "recall_at_10": checks.get("recall_at_10"), "ef": ef},
-                       "harder_set": (None if not secondary else
-                                      {"n_dist_per_query": nd_hard, "recall_at_10": secondary["checks"]["recall_at_10"], "ef": ef,
-                                       "ef_at_recall_gate": (harder_gate or {}).get("ef"),
-                                       "closer_to_SIFT1M": True})},
-            "cold_first_call_ms": None if not cold else cold["first_call_ms"],
-            "cold": cold,
-            "protocol": ("one synchronous call per %d-query batch with HOST matrices in and out, as benchmark/benchmark.ml:89-96 times knn_batch "
-                         "and SURVEY 8d prescribes; the warm-up and the timed steps rotate through %d distinct batches (seeds 2..%d): " % (nq, NB, 1 + NB)) +
-                        ("hnsw_search_batch (H2D of the queries, ordering pre-pass, search kernel, D2H of the results; the caller's matrices in "
-                         "page-locked memory: hnsw_host_alloc / hnsw_host_register)" if world == 1 else
-                         "per rank hnsw_search_batch_h2d (its registered query shard read by the device, ordering pre-pass, search kernel, results in "
-                         "HBM), RCCL all-gather of the per-shard results (the full table resident on every GPU), D2H of the rank's own shard, stream "
-                         "synchronisation") +
-                        "; the rate with the queries already resident in HBM and the results left there is `device_resident`",
+        out["config"]["workload"] += ("; easier than SIFT1M (%s evals/query vs ~2.5-3k): see harder_set_at_recall_gate (%s)"
+                                      % (nd_head, nd_hard))
+        out["config"].update({
+            "headline_set": {"n_dist_per_query": nd_head, "recall_at_10": checks.get("recall_at_10"), "ef": ef},
+            "harder_set": (None if not secondary else
+                           {"n_dist_per_query": nd_hard, "recall_at_10": secondary["checks"]["recall_at_10"], "ef": ef,
+                            "ef_at_recall_gate": (harder_gate or {}).get("ef"),
+                            "closer_to_SIFT1M": True})})
+        out.update({
             "device_resident": {"value": round(qps_dev, 1), "unit": "queries/s", "ms_per_step": round(1e3 * wall_dev / args.steps, 4),
                                 "ms_per_step_with_events": round(1e3 * wall_dev_i / args.steps, 4), "ms_per_step_stats_with_events": headline_steps,
                                 "kernel_ms": round(dev_lib["search_ms"], 4), "prepass_ms": round(dev_lib["prepass_ms"], 4),
@@ -1777,34 +1822,11 @@ def main():
                                              "value": round(qps, 1) if gate_ok else checks.get("qps_at_that_ef")},
                             "harder_set": _pick(harder_gate, "ef", "recall_at_10", "value")} if rank == 0 and world == 1 else None,
             "others": others, "bench_dist": bench_dist, "strong": strong, "one_process": one_process, "pipelined": pipelined, "checks": checks,
-        }
+        })
         if big and roofline:
             # the 100 k launch against the same line: whole-path bytes per query x its rate (no kernel-only duration is taken there)
             big["frac"] = round(roofline["step"]["bytes_per_query_whole_path"] * big["value"] / world / 1e9 / HBM_PEAK_GBS, 4)
-        # Everything measured goes to DETAIL_FILE beside this script (and to stderr); stdout carries the short driver line only
-        detail_txt = json.dumps(_finite(out), allow_nan=False)
-        for path_ in (os.path.join(ROOT, DETAIL_FILE), os.path.join(ROOT, "gpurun_out", DETAIL_FILE)):
-            try:
-                if os.path.isdir(os.path.dirname(path_)):
-                    with open(path_, "w") as f_:
-                        f_.write(detail_txt + "\n")
-            except OSError as e:
-                log("could not write %s: %r" % (path_, e))
-        print("[bench-detail] " + detail_txt, file=sys.stderr, flush=True)
-        line = driver_line(out)
-        r_ = roofline or {}
-        log("SUMMARY value %.0f q/s (%.4f ms/step, n_gpus %d); roofline frac %s (kernel %s ms, traffic %s B); cpu_baseline %s q/s; recall@10 %s; line %d bytes" %
-            (out["value"], out["ms_per_step"], world, r_.get("frac"), r_.get("kernel_ms"), r_.get("traffic"),
-             (cpu_baseline or {}).get("value"), checks.get("recall_at_10"), len(line)))
-        _restore_stdout(saved_stdout)
-        saved_stdout = None
-        print(line, flush=True)
-        os.dup2(2, 1)                      # whatever teardown prints does not follow the JSON line
-    if multi:
-        dist.barrier()
-        dist.destroy_process_group()
-    if saved_stdout is not None:
-        os.close(saved_stdout)
+    finish(out if rank == 0 else None, saved_stdout, dist)
 
 
 if __name__ == "__main__":

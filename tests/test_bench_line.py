@@ -101,6 +101,22 @@ def test_driver_line_of_a_minimal_multi_gpu_result():
     assert out["n_gpus"] == 8 and out["cpu_baseline"] is None and out["strong"]["equals_single_device"] is True
 
 
+def test_driver_line_of_a_plain_run():
+    """bench.py without --full: the headline, its configuration and its protocol, no other leg"""
+    d = canned()
+    plain = {k: d[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                               "vs_baseline", "dtype", "data", "config")}
+    plain["full"] = False
+    line = bench.driver_line(plain)
+    assert len(line) < bench.LINE_LIMIT and "truncated" not in line
+    out = strict(line)
+    for key in REQUIRED:
+        assert key in out, key
+    assert out["value"] == 21935123.1 and out["ms_per_step"] == d["ms_per_step"] and out["dtype"] == d["dtype"]
+    for key in ("roofline", "cpu_baseline", "checks", "recall_at_10", "float32_rows", "device_resident", "others", "cold", "strong"):
+        assert out[key] is None, key
+
+
 def _row(kernel, grid, counter, value):
     return {"Kernel_Name": kernel, "Grid_Size": str(grid), "Counter_Name": counter, "Counter_Value": str(value)}
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of whole-library variants on the C3 / C5 shapes (bench.py's `others` leg), alternating on one box:
 #   tools/ab_others.sh exp/a.so exp/b.so [rounds]      -> gpurun_out/ab_others.txt
-# Each run is one `bench.py --no-cpu --no-secondary --no-pmc --no-bench-dist`; the lines printed are kernel ms, q/s and the
+# Each run is one `bench.py --full --no-cpu --no-secondary --no-pmc --no-bench-dist`; the lines printed are kernel ms, q/s and the
 # roofline fraction per configuration, and whether the sample agreed with the oracle.
 R=$(cd "$(dirname "$0")/.." && pwd)
 A=$1; B=$2; ROUNDS=${3:-2}
@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/ab_others.txt; mkdir -p $R/gpurun_out; : > $OUT
 for r in $(seq $ROUNDS); do
   for lib in $A $B; do
     echo "== $lib (round $r)" >> $OUT
-    HNSW_LIB_PATH=$R/$lib BENCH_NO_TAGS_AB=1 timeout -k 10 500 python3 $R/bench.py --no-cpu --no-secondary --no-pmc --no-bench-dist --steps 10 \
+    HNSW_LIB_PATH=$R/$lib BENCH_NO_TAGS_AB=1 timeout -k 10 500 python3 $R/bench.py --full --no-cpu --no-secondary --no-pmc --no-bench-dist --steps 10 \
         > $R/gpurun_out/ab_others_line.json 2> $R/gpurun_out/ab_others_err.log || { echo "bench failed" >> $OUT; tail -5 $R/gpurun_out/ab_others_err.log >> $OUT; exit 1; }
     python3 - $R/bench_detail.json >> $OUT <<'PY'
 import json, sys

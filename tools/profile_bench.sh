@@ -11,7 +11,7 @@ export BENCH_NO_TAGS_AB=1     # no tag-cache comparison launches on the clustere
 # secondary data set), need the CPU oracle, or start rocprofv3 themselves: every hnsw_search_kernel dispatch below is the
 # headline workload (C2) -- the harder set at the ef of its recall gate has a profile of its own: tools/profile_gate.py under
 # tools/profile_cmd.sh --; BENCH_EXTRA=" " adds the C3 / C5 legs (`others`), whose kernels then show too, the clustered twins under their own names (<...,1>: Visited as bitmap blocks)
-BENCH="python3 $PWD/bench.py --steps 20 --warmup 3 --no-cpu --no-secondary --no-bench-dist --no-pmc ${BENCH_EXTRA:---no-others}"
+BENCH="python3 $PWD/bench.py --full --steps 20 --warmup 3 --no-cpu --no-secondary --no-bench-dist --no-pmc ${BENCH_EXTRA:---no-others}"
 cd /tmp
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.json 2> $OUT/trace.log || exit 1
