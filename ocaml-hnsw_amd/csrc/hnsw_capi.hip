@@ -12,6 +12,31 @@ using hnsw_dev::IndexView;
 using hnsw_dev::SearchArgs;
 using namespace hnsw_host;
 
+// probe queries of the visited-structure measurement (knn_blk_bits): query j = the midpoint between node j * step's vector and
+// its first layer-0 neighbour's (the node's own vector if it has none); rows of `stride` floats, padding zero as in the table
+__global__ void __launch_bounds__(64)
+probe_queries_kernel(const IndexView iv, int64_t step, float *out) {
+    const int64_t v = (int64_t)blockIdx.x * step;
+    const int32_t nb = iv.nbr0[v * iv.S0];
+    const int64_t u = nb >= 0 ? (int64_t)nb : v;
+    for (int64_t i = threadIdx.x; i < iv.stride; i += 64)
+        out[(int64_t)blockIdx.x * iv.stride + i] = 0.5f * (iv.X[v * iv.stride + i] + iv.X[u * iv.stride + i]);
+}
+
+// The flagged queries of a launch (status bit 0), listed on the device: map[0 .. cap) = their indices, -1 beyond the count
+// (the re-run kernel's blocks with a -1 entry leave at once); map[cap] = how many there were.  One workgroup.
+__global__ void __launch_bounds__(1024)
+flagged_list_kernel(const uint32_t *status, int64_t nq, int32_t *map, int32_t cap) {
+    __shared__ int32_t count;
+    if (threadIdx.x == 0) count = 0;
+    for (int i = threadIdx.x; i < cap; i += blockDim.x) map[i] = -1;
+    __syncthreads();
+    for (int64_t q = threadIdx.x; q < nq; q += blockDim.x)
+        if (status[q] & 1u) { const int at = atomicAdd(&count, 1); if (at < cap) map[at] = (int32_t)q; }
+    __syncthreads();
+    if (threadIdx.x == 0) map[cap] = count;
+}
+
 namespace hnsw_host {
 
 thread_local std::string g_last_error;
@@ -57,6 +82,30 @@ void range_reader_enqueued(const void *p, size_t bytes, hipStream_t st) {
         r.readers.push_back(f);
         return;
     }
+}
+
+void remember_range(const void *p, size_t bytes, void *dev, int kind) {
+    std::lock_guard<std::mutex> lk(g_ranges_mu);
+    g_ranges.push_back({(const char *)p, bytes, (char *)dev, kind, {}});
+}
+// takes the range that STARTS at p off the list (no launch can pick it for direct access any more) and waits for the
+// readers that earlier asynchronous calls left on it; false: no such range
+bool retire_range(const void *p, int *kind) {
+    std::vector<InFlight> readers;
+    {
+        std::lock_guard<std::mutex> lk(g_ranges_mu);
+        size_t i = 0;
+        while (i < g_ranges.size() && g_ranges[i].p != (const char *)p) ++i;
+        if (i == g_ranges.size()) return false;
+        *kind = g_ranges[i].kind;
+        readers.swap(g_ranges[i].readers);
+        g_ranges.erase(g_ranges.begin() + (long)i);
+    }
+    for (InFlight &f : readers) {
+        if (hipEventSynchronize(f.ev) != hipSuccess) (void)hipGetLastError();
+        (void)hipEventDestroy(f.ev);
+    }
+    return true;
 }
 
 int fail(int code, const char *fmt, ...) {
@@ -123,33 +172,17 @@ int upload_upper_layout(IndexTables &t, int64_t n0, const std::vector<int2> &ref
     return HNSW_OK;
 }
 
-} // namespace hnsw_host
 
 // ---- kernel dispatch ---------------------------------------------------------------------------
 // the knn kernel's variants live in hnsw_search_variants.hip, one object per (metric, accept rule, row shape)
-#define HNSW_DECL_VARIANT(m, s, f)                                                                          \
-    namespace hnsw_host {                                                                                    \
+#define HNSW_DECL_VARIANT(m, s, f)                                                                                   \
     hipError_t search_launch_##m##_##s##_##f(int nch, int nslot, const IndexView &iv, const SearchArgs &a, hipStream_t st); \
-    int search_occupancy_##m##_##s##_##f(int nch, int nslot, size_t lds, int blk);                                    \
-    }
+    int search_occupancy_##m##_##s##_##f(int nch, int nslot, size_t lds, int blk);
 HNSW_DECL_VARIANT(0, 0, 0) HNSW_DECL_VARIANT(0, 0, 1) HNSW_DECL_VARIANT(0, 0, 2) HNSW_DECL_VARIANT(0, 0, 3) HNSW_DECL_VARIANT(0, 0, 4)
 HNSW_DECL_VARIANT(0, 1, 0) HNSW_DECL_VARIANT(0, 1, 1) HNSW_DECL_VARIANT(0, 1, 2) HNSW_DECL_VARIANT(0, 1, 3) HNSW_DECL_VARIANT(0, 1, 4)
 HNSW_DECL_VARIANT(1, 0, 0) HNSW_DECL_VARIANT(1, 0, 1) HNSW_DECL_VARIANT(1, 0, 2) HNSW_DECL_VARIANT(1, 0, 3) HNSW_DECL_VARIANT(1, 0, 4)
 HNSW_DECL_VARIANT(1, 1, 0) HNSW_DECL_VARIANT(1, 1, 1) HNSW_DECL_VARIANT(1, 1, 2) HNSW_DECL_VARIANT(1, 1, 3) HNSW_DECL_VARIANT(1, 1, 4)
 #undef HNSW_DECL_VARIANT
-
-// probe queries of the visited-structure measurement (knn_blk_bits): query j = the midpoint between node j * step's vector and
-// its first layer-0 neighbour's (the node's own vector if it has none); rows of `stride` floats, padding zero as in the table
-__global__ void __launch_bounds__(64)
-probe_queries_kernel(const IndexView iv, int64_t step, float *out) {
-    const int64_t v = (int64_t)blockIdx.x * step;
-    const int32_t nb = iv.nbr0[v * iv.S0];
-    const int64_t u = nb >= 0 ? (int64_t)nb : v;
-    for (int64_t i = threadIdx.x; i < iv.stride; i += 64)
-        out[(int64_t)blockIdx.x * iv.stride + i] = 0.5f * (iv.X[v * iv.stride + i] + iv.X[u * iv.stride + i]);
-}
-
-namespace {
 
 typedef hipError_t (*search_launch_fn)(int, int, const IndexView &, const SearchArgs &, hipStream_t);
 typedef int (*search_occupancy_fn)(int, int, size_t, int);
@@ -218,7 +251,24 @@ int knn_vt_bits(hnsw_index *idx, int ef, int semf) {
     return b;
 }
 
-int launch_search_args(hnsw_index *idx, SearchArgs &a, hipStream_t st);
+int launch_search_args(hnsw_index *idx, SearchArgs &a, hipStream_t st) {
+    const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(a.ef, nch);
+    hipError_t e = k_launch[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][a.sem ? 1 : 0][variant_full(idx)](nch, nslot, idx->iv, a, st);
+    if (e != hipSuccess) return fail(HNSW_ERR_HIP, "search kernel launch failed: %s", hipGetErrorString(e));
+    return HNSW_OK;
+}
+
+// the SearchArgs of a plain launch over the batch: every query in its row, nothing ordered, no global slab.  The caller passes
+// the visited structure's sizes (knn_vt_bits, knn_blk_bits) because knn_blk_bits' own measurement launches through here.
+SearchArgs knn_args(const hnsw_search_params &p, const KnnBatch &b, int vt_bits, int blk_bits) {
+    SearchArgs a{};
+    a.Q = b.Q; a.q_stride = b.q_stride; a.nq = b.nq; a.ef = p.ef; a.k = p.k; a.fill = p.fill; a.sem = p.semantics;
+    a.vt_bits = vt_bits; a.blk_bits = blk_bits;
+    a.out_ids = b.ids; a.out_dist = b.dist; a.out_ndist = b.nd; a.out_nhops = b.nh; a.out_status = b.st;
+    a.any_flag = b.any_flag;
+    a.prio_tail = 0x7FFFFFFF;
+    return a;
+}
 
 // Visited as bitmap blocks over the locality codes (visited_blocks_mem_add; hnsw_locality.hip) for the kernels with W in four
 // or more registers (ef > 128: the walks that visit several times what the tag cache holds): log2 of the block slots, or 0 =
@@ -297,14 +347,15 @@ int knn_blk_bits(hnsw_index *idx, int ef, int semf) {
     hipLaunchKernelGGL(probe_queries_kernel, dim3((unsigned)nq), dim3(64), 0, nullptr, idx->iv, step, (float *)probes.p);
     uint64_t sum[2] = {0, 0};
     bool ok = hipGetLastError() == hipSuccess;
+    hnsw_search_params p{};
+    p.ef = ef; p.k = 1; p.fill = HNSW_FILL_OHNSW; p.semantics = semf;
+    const KnnBatch b{(const float *)probes.p, nq, idx->iv.stride, (int32_t *)out.p, (float *)out.p + nq, (uint32_t *)out.p + 2 * nq,
+                     (uint32_t *)out.p + 3 * nq, nullptr, nullptr};
     for (int pass = 0; pass < 2 && ok; ++pass) {
-        SearchArgs a{};
-        a.Q = (const float *)probes.p; a.q_stride = idx->iv.stride; a.nq = nq; a.ef = ef; a.k = 1; a.fill = HNSW_FILL_OHNSW; a.sem = semf;
-        a.vt_bits = vt; a.blk_bits = pass ? bits : 0; a.prio_tail = 0x7FFFFFFF;
-        a.out_ids = (int32_t *)out.p; a.out_dist = (float *)out.p + nq; a.out_ndist = (uint32_t *)out.p + 2 * nq; a.out_nhops = (uint32_t *)out.p + 3 * nq;
+        SearchArgs a = knn_args(p, b, vt, pass ? bits : 0);
         std::vector<uint32_t> nd((size_t)nq);
         ok = launch_search_args(idx, a, nullptr) == HNSW_OK && hipDeviceSynchronize() == hipSuccess &&
-             hipMemcpy(nd.data(), a.out_ndist, (size_t)nq * 4, hipMemcpyDeviceToHost) == hipSuccess;
+             hipMemcpy(nd.data(), b.nd, (size_t)nq * 4, hipMemcpyDeviceToHost) == hipSuccess;
         for (uint32_t v : nd) sum[pass] += v;
     }
     out.release(); probes.release();
@@ -415,23 +466,105 @@ int check_params(const hnsw_index *idx, const hnsw_search_params *p) {
     return HNSW_OK;
 }
 
-} // namespace
-
-// The flagged queries of a launch (status bit 0), listed on the device: map[0 .. cap) = their indices, -1 beyond the count
-// (the re-run kernel's blocks with a -1 entry leave at once); map[cap] = how many there were.  One workgroup.
-__global__ void __launch_bounds__(1024)
-flagged_list_kernel(const uint32_t *status, int64_t nq, int32_t *map, int32_t cap) {
-    __shared__ int32_t count;
-    if (threadIdx.x == 0) count = 0;
-    for (int i = threadIdx.x; i < cap; i += blockDim.x) map[i] = -1;
-    __syncthreads();
-    for (int64_t q = threadIdx.x; q < nq; q += blockDim.x)
-        if (status[q] & 1u) { const int at = atomicAdd(&count, 1); if (at < cap) map[at] = (int32_t)q; }
-    __syncthreads();
-    if (threadIdx.x == 0) map[cap] = count;
+// the checks of the batch entry points, in this order: the params and the handle, 0 <= nq <= INT32_MAX, then -- unless nq is
+// 0, which passes -- the buffers (`buffers`: none of the required ones is null) and q_stride >= d
+int check_batch(const hnsw_index *idx, const hnsw_search_params *p, int64_t nq, int64_t q_stride, bool buffers) {
+    int rc = check_params(idx, p);
+    if (rc) return rc;
+    if (nq < 0 || nq > 0x7FFFFFFFLL) return fail(HNSW_ERR_BAD_ARG, "nq=%lld out of range", (long long)nq);
+    if (nq == 0) return HNSW_OK;
+    if (!buffers) return fail(HNSW_ERR_BAD_ARG, "null buffer");
+    if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
+    return HNSW_OK;
 }
 
-namespace hnsw_host {
+// The exactness fallback's launch: the `c` flagged queries listed in qmap are searched again, each with `cap` slots of `slab`
+// for its tie list; their results, counters and status words overwrite their rows of the batch.  Its arguments are the plain
+// launch's and nothing of an ordered one: the pre-pass's entries and key, the LDS padding and the priorities describe the order
+// of all nq queries in the first launch, not of this list.
+int launch_rerun(hnsw_index *idx, const hnsw_search_params &p, const KnnBatch &b, const int32_t *qmap, int64_t c, uint32_t *slab,
+                 int32_t cap, hipStream_t st) {
+    const int semf = p.semantics ? 1 : 0;
+    const int vt = knn_vt_bits(idx, p.ef, semf), blk = knn_blk_bits(idx, p.ef, semf);
+    SearchArgs a = knn_args(p, b, vt, blk);
+    a.nq = c; a.qmap = qmap; a.q_limit = b.nq; a.ovf_g = slab; a.ovf_gcap = cap;
+    a.any_flag = nullptr;                   // (the host has read the word already; a re-run query cannot overflow)
+    return launch_search_args(idx, a, st);
+}
+
+int knn_search(hnsw_index *idx, const hnsw_search_params *params, const KnnBatch &b, hipStream_t st, float *d_stage) {
+    int rc = check_batch(idx, params, b.nq, b.q_stride, b.Q && b.ids && b.dist);
+    if (rc || b.nq == 0) return rc;
+    HIP_TRY(hipSetDevice(idx->device));
+    const int semf = params->semantics ? 1 : 0;
+    const int vt = knn_vt_bits(idx, params->ef, semf), blk = knn_blk_bits(idx, params->ef, semf);
+    SearchArgs a = knn_args(*params, b, vt, blk);
+    // A batch larger than the chip holds at once is searched longest walk first (hnsw_order.hip):
+    // per-query results are unchanged, the launch's drain phase is made of short walks.
+    void *block = nullptr;
+    hipEvent_t *ev = nullptr;
+    if (idx->time_kernels && idx->tev_used + 3 <= 3 * 4096) {
+        while (idx->tev.size() < idx->tev_used + 3) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            idx->tev.push_back(e);
+        }
+        ev = &idx->tev[idx->tev_used];      // claimed (tev_used advanced) only once all three are recorded
+        HIP_TRY(hipEventRecord(ev[0], st));
+    }
+    const int mode = idx->order_mode;
+    // Ordered when more than half of what the chip holds: a batch that fits is faster too with its long walks
+    // dispatched first and spread over the CUs (C2, 7168 queries: 0.59 -> 0.45 ms byte rows, 0.68 -> 0.65 ms fp32);
+    // below that the pre-pass costs more than it returns.
+    if (mode != 0 && (mode == 1 || 2 * b.nq > resident_queries(idx, params->ef, semf))) {
+        rc = order_longest_first(idx, b.Q, b.nq, b.q_stride, d_stage, st, &block, &a.qmap, &a.pre_entry, &a.pre_key, &a.pre_nd, &a.pre_layer);
+        if (rc) return rc;
+        if (d_stage) a.Q = d_stage;        // the descent kernel left a device-resident copy of the (host-resident) queries
+        a.q_limit = b.nq;
+        a.lds_pad = balanced_lds_pad(idx, b.nq, params->ef, semf);
+        launch_priorities(idx, b.nq, params->ef, semf, a);
+    }
+    if (ev) HIP_TRY(hipEventRecord(ev[1], st));
+    rc = launch_search_args(idx, a, st);
+    if (!rc && idx->fb_queries > 0 && b.st && !b.any_flag) {
+        // opt-in exact mode of the device-pointer entry point (option "device_fallback_slab_bytes"): the queries the launch
+        // flagged are listed on the device and searched again with the slab, on the caller's stream, no host round trip.
+        // The re-run rewrites their results, counters and status words (bit 0 clear: a slab slot per node cannot overflow);
+        // with more flagged queries than the slab holds, the ones left over keep their flag.  Two small launches per call.
+        const int32_t cap = (int32_t)idx->fb_queries;
+        hipLaunchKernelGGL(flagged_list_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t *)b.st, b.nq, (int32_t *)idx->dFbMap.p, cap);
+        if (hipGetLastError() != hipSuccess) return fail(HNSW_ERR_HIP, "flagged-query listing failed");
+        KnnBatch read = b;
+        read.Q = a.Q;                       // the queries as the search read them (the staged copy when there is one)
+        // (at most min(cap, nq) queries can be listed: no more blocks than that; the blocks past the count leave at once)
+        rc = launch_rerun(idx, *params, read, (const int32_t *)idx->dFbMap.p, std::min<int64_t>(cap, b.nq), (uint32_t *)idx->dFbSlab.p,
+                          (int32_t)std::min<int64_t>(idx->iv.n, 0x7FFFFFFF), st);
+    }
+    if (ev && !rc) {
+        HIP_TRY(hipEventRecord(ev[2], st));
+        idx->tev_used += 3;                 // an early return above leaves the triple unclaimed: nothing half-recorded is ever read
+        idx->tev_ordered.resize(idx->tev_used / 3);
+        idx->tev_ordered[idx->tev_used / 3 - 1] = block != nullptr;
+    }
+    return rc;
+}
+
+int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st) {
+    return rerun_overflowed(idx, b.nq, b.st, [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
+        return launch_rerun(idx, *p, b, qmap, c, slab, cap, st);
+    });
+}
+
+hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st) {
+    const size_t rbytes = (size_t)b.nq * k * 4, cbytes = (size_t)b.nq * 4;
+    hipError_t e = hipSuccess;
+    if (ids) e = hipMemcpyAsync(ids, b.ids, rbytes, hipMemcpyDeviceToHost, st);
+    if (dist && e == hipSuccess) e = hipMemcpyAsync(dist, b.dist, rbytes, hipMemcpyDeviceToHost, st);
+    if (nd && e == hipSuccess) e = hipMemcpyAsync(nd, b.nd, cbytes, hipMemcpyDeviceToHost, st);
+    if (nh && e == hipSuccess) e = hipMemcpyAsync(nh, b.nh, cbytes, hipMemcpyDeviceToHost, st);
+    return e;
+}
+
 // the handle's stream for the host-buffer call and its page-locked "any query flagged" word
 int ensure_host_call_state(hnsw_index *idx) {
     if (!idx->hs[0]) HIP_TRY(hipStreamCreateWithFlags(&idx->hs[0], hipStreamNonBlocking));
@@ -442,37 +575,40 @@ int ensure_host_call_state(hnsw_index *idx) {
     return HNSW_OK;
 }
 
-// The one-time costs of a process's FIRST search belong to index construction, which the reference's benchmark times on its own
-// (benchmark/benchmark.ml:66-80 before :89-96): the code objects of the search kernels and of the ordering pre-pass (the
-// runtime loads a translation unit's code when its first kernel is launched: 1.4 ms and 5.2 ms, tools/cold_probe.py), the
-// handle's stream and flag word.  One query (node 0's vector, ef 1) through the plain and through the ordered launch; results
-// are discarded.  HNSW_WARM_UP=0 leaves them to the first call (7 ms instead of 0.6 ms for a 10 k batch).
-static int warm_up_steps(hnsw_index *idx);
-int warm_up(hnsw_index *idx) {
-    if (!env_int("HNSW_WARM_UP", 1) || idx->iv.n < 1 || idx->iv.entry_point < 0) return HNSW_OK;
-    // Nothing here is needed for a valid index: a failure (a stream, 64 bytes, a dummy launch) clears the HIP error and leaves the
-    // one-time costs to the first search call, which reports its own errors.  Callers ignore the return value.
-    const int rc = warm_up_steps(idx);
-    if (rc) (void)hipGetLastError();
-    return rc;
-}
-static int warm_up_steps(hnsw_index *idx) {
+// One query (node 0's vector, k 1) through the plain and through the ordered launch on the handle's stream, results discarded:
+// what loads the code objects of the shape of p (and makes the handle's stream and flag word)
+int trial_search(hnsw_index *idx, hnsw_search_params p) {
     int rc = ensure_host_call_state(idx);
     if (rc) return rc;
     DevBuf out;
     if ((rc = out.ensure(64))) return rc;
-    hnsw_search_params p{};
-    p.ef = 1; p.k = 1; p.fill = HNSW_FILL_OHNSW; p.semantics = HNSW_SEM_OHNSW;
+    p.k = 1;
+    const KnnBatch b{idx->iv.X, 1, idx->iv.stride, (int32_t *)out.p, (float *)out.p + 1, nullptr, nullptr, (uint32_t *)out.p + 2, nullptr};
     const int mode = idx->order_mode;
     for (int ordered = 0; ordered < 2 && !rc; ++ordered) {
         idx->order_mode = ordered;
-        rc = search_batch_device_flag(idx, idx->iv.X, 1, idx->iv.stride, &p, (int32_t *)out.p, (float *)out.p + 1,
-                                      nullptr, nullptr, (uint32_t *)out.p + 2, nullptr, idx->hs[0]);
+        rc = knn_search(idx, &p, b, idx->hs[0]);
     }
     idx->order_mode = mode;
     const hipError_t e = hipStreamSynchronize(idx->hs[0]);
     out.release();
-    if (!rc && e != hipSuccess) rc = fail(HNSW_ERR_HIP, "warm-up search failed: %s", hipGetErrorString(e));
+    if (!rc && e != hipSuccess) rc = fail(HNSW_ERR_HIP, "the trial search failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+// The one-time costs of a process's FIRST search belong to index construction, which the reference's benchmark times on its own
+// (benchmark/benchmark.ml:66-80 before :89-96): the code objects of the search kernels and of the ordering pre-pass (the
+// runtime loads a translation unit's code when its first kernel is launched: 1.4 ms and 5.2 ms, tools/cold_probe.py), the
+// handle's stream and flag word: a trial search at ef 1.  HNSW_WARM_UP=0 leaves them to the first call (7 ms instead of
+// 0.6 ms for a 10 k batch).
+int warm_up(hnsw_index *idx) {
+    if (!env_int("HNSW_WARM_UP", 1) || idx->iv.n < 1 || idx->iv.entry_point < 0) return HNSW_OK;
+    // Nothing here is needed for a valid index: a failure (a stream, 64 bytes, a dummy launch) clears the HIP error and leaves the
+    // one-time costs to the first search call, which reports its own errors.  Callers ignore the return value.
+    hnsw_search_params p{};
+    p.ef = 1; p.k = 1; p.fill = HNSW_FILL_OHNSW; p.semantics = HNSW_SEM_OHNSW;
+    const int rc = trial_search(idx, p);
+    if (rc) (void)hipGetLastError();
     return rc;
 }
 
@@ -506,6 +642,35 @@ int finish_index(hnsw_index *idx, int32_t expected_ef, int32_t expected_semantic
     prepare_quietly(idx, expected_ef, expected_semantics);      //  failures are left to the first search) nor for its shape's one-time decisions
     *out = idx;
     return HNSW_OK;
+}
+
+void prepare_quietly(hnsw_index *idx, int32_t ef, int32_t semantics) {
+    if (ef <= 0 || idx->iv.n < 1 || idx->iv.entry_point < 0) return;
+    hnsw_search_params p{};
+    p.ef = ef; p.k = 1; p.fill = HNSW_FILL_OHNSW; p.semantics = semantics;
+    const std::string keep = g_last_error;
+    if (hnsw_index_prepare(idx, &p) != HNSW_OK) { (void)hipGetLastError(); g_last_error = keep; }     // an optimisation: the search reports its own errors
+}
+void adopt_blk_choice(hnsw_index *idx, int32_t ef, int32_t semantics, bool blocks) {
+    if (ef < 1 || ef > 1024) return;
+    const int semf = semantics ? 1 : 0, nslot = pick_nslot_knn(ef, pick_nch(idx->iv.nchunks));
+    if (nslot < 3 || idx->blk_choice[slot_class(nslot)][semf] >= 0) return;
+    int bits = 0;
+    if (blocks && idx->lcode_state == 1 && (bits = blk_capacity_bits(idx, ef, semf)) > 0 && materialise_lcode0(idx) == HNSW_OK && idx->tables.lcode0.p) {
+        idx->blk_choice[slot_class(nslot)][semf] = bits;
+        return;
+    }
+    if (!blocks) idx->blk_choice[slot_class(nslot)][semf] = 0;       // (blocks that cannot be honoured here stay undecided: measured on demand)
+}
+void list_blk_choices(const hnsw_index *idx, std::vector<int32_t> &out3) {
+    static const int rep_ef[SLOT_CLASSES] = {64, 128, 192, 256, 384, 512, 1024};     // an ef of every slot class
+    const bool wide = pick_nch(idx->iv.nchunks) == 2 || pick_nch(idx->iv.nchunks) == 4;
+    for (int c = 0; c < SLOT_CLASSES; ++c)
+        for (int s = 0; s < 2; ++s) {
+            if (idx->blk_choice[c][s] < 0) continue;
+            if (!wide && (c == 2 || c == 4)) continue;              // three / six registers: rows of 65..256 dimensions only
+            out3.push_back(rep_ef[c]); out3.push_back(s); out3.push_back(idx->blk_choice[c][s] > 0 ? 1 : 0);
+        }
 }
 } // namespace hnsw_host
 
@@ -667,59 +832,11 @@ int32_t hnsw_index_prepare(hnsw_index *idx, const hnsw_search_params *params) {
     const int semf = params->semantics ? 1 : 0;
     (void)knn_blk_bits(idx, params->ef, semf);            // the visited structure of this kernel shape (codes, measurement)
     (void)resident_queries(idx, params->ef, semf);        // the shape's residency, cached in the handle
-    // the code object of the shape's translation unit: one query (node 0's vector) through the plain and the ordered launch
-    if ((rc = ensure_host_call_state(idx))) return rc;
-    DevBuf out;
-    if ((rc = out.ensure(64))) return rc;
-    hnsw_search_params p = *params;
-    p.k = 1;
-    const int mode = idx->order_mode;
-    for (int ordered = 0; ordered < 2 && !rc; ++ordered) {
-        idx->order_mode = ordered;
-        rc = search_batch_device_flag(idx, idx->iv.X, 1, idx->iv.stride, &p, (int32_t *)out.p, (float *)out.p + 1,
-                                      nullptr, nullptr, (uint32_t *)out.p + 2, nullptr, idx->hs[0]);
-    }
-    idx->order_mode = mode;
-    const hipError_t e = hipStreamSynchronize(idx->hs[0]);
-    out.release();
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(HNSW_ERR_HIP, "hnsw_index_prepare: the trial search failed: %s", hipGetErrorString(e));
+    // the code object of the shape's translation unit
+    if ((rc = trial_search(idx, *params))) return rc;
     const std::pair<int, int> key(params->ef, params->semantics);
     if (std::find(idx->prepared.begin(), idx->prepared.end(), key) == idx->prepared.end()) idx->prepared.push_back(key);
     return HNSW_OK;
-}
-
-extern "C++" {
-namespace hnsw_host {
-void prepare_quietly(hnsw_index *idx, int32_t ef, int32_t semantics) {
-    if (ef <= 0 || idx->iv.n < 1 || idx->iv.entry_point < 0) return;
-    hnsw_search_params p{};
-    p.ef = ef; p.k = 1; p.fill = HNSW_FILL_OHNSW; p.semantics = semantics;
-    const std::string keep = g_last_error;
-    if (hnsw_index_prepare(idx, &p) != HNSW_OK) { (void)hipGetLastError(); g_last_error = keep; }     // an optimisation: the search reports its own errors
-}
-void adopt_blk_choice(hnsw_index *idx, int32_t ef, int32_t semantics, bool blocks) {
-    if (ef < 1 || ef > 1024) return;
-    const int semf = semantics ? 1 : 0, nslot = pick_nslot_knn(ef, pick_nch(idx->iv.nchunks));
-    if (nslot < 3 || idx->blk_choice[slot_class(nslot)][semf] >= 0) return;
-    int bits = 0;
-    if (blocks && idx->lcode_state == 1 && (bits = blk_capacity_bits(idx, ef, semf)) > 0 && materialise_lcode0(idx) == HNSW_OK && idx->tables.lcode0.p) {
-        idx->blk_choice[slot_class(nslot)][semf] = bits;
-        return;
-    }
-    if (!blocks) idx->blk_choice[slot_class(nslot)][semf] = 0;       // (blocks that cannot be honoured here stay undecided: measured on demand)
-}
-void list_blk_choices(const hnsw_index *idx, std::vector<int32_t> &out3) {
-    static const int rep_ef[SLOT_CLASSES] = {64, 128, 192, 256, 384, 512, 1024};     // an ef of every slot class
-    const bool wide = pick_nch(idx->iv.nchunks) == 2 || pick_nch(idx->iv.nchunks) == 4;
-    for (int c = 0; c < SLOT_CLASSES; ++c)
-        for (int s = 0; s < 2; ++s) {
-            if (idx->blk_choice[c][s] < 0) continue;
-            if (!wide && (c == 2 || c == 4)) continue;              // three / six registers: rows of 65..256 dimensions only
-            out3.push_back(rep_ef[c]); out3.push_back(s); out3.push_back(idx->blk_choice[c][s] > 0 ? 1 : 0);
-        }
-}
-} // namespace hnsw_host
 }
 
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes) {
@@ -803,114 +920,10 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }
 
-extern "C++" {
-namespace {
-int launch_search_args(hnsw_index *idx, SearchArgs &a, hipStream_t st);
-}
-namespace hnsw_host {
-int search_check(const hnsw_index *idx, const hnsw_search_params *p) { return check_params(idx, p); }
-// the exactness fallback's launch: the `c` flagged queries listed in qmap are searched again with a global
-// slab for their tie lists; results overwrite their rows of d_ids / d_dist (launched on the null stream)
-int search_rerun_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride, const hnsw_search_params *p,
-                        int32_t *d_ids, float *d_dist, uint32_t *d_nd, uint32_t *d_nh, uint32_t *d_st,
-                        const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap, hipStream_t st) {
-    SearchArgs a{};
-    a.Q = d_queries; a.q_stride = q_stride; a.nq = c; a.ef = p->ef; a.k = p->k;
-    a.fill = p->fill; a.sem = p->semantics;
-    a.vt_bits = knn_vt_bits(idx, p->ef, p->semantics ? 1 : 0);
-    a.blk_bits = knn_blk_bits(idx, p->ef, p->semantics ? 1 : 0);
-    a.out_ids = d_ids; a.out_dist = d_dist; a.out_ndist = d_nd; a.out_nhops = d_nh; a.out_status = d_st;
-    a.qmap = qmap; a.q_limit = nq; a.ovf_g = slab; a.ovf_gcap = cap; a.prio_tail = 0x7FFFFFFF;
-    return launch_search_args(idx, a, st);
-}
-} // namespace hnsw_host
-} // extern "C++"
-namespace {
-int launch_search_args(hnsw_index *idx, SearchArgs &a, hipStream_t st) {
-    const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(a.ef, nch);
-    hipError_t e = k_launch[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][a.sem ? 1 : 0][variant_full(idx)](nch, nslot, idx->iv, a, st);
-    if (e != hipSuccess) return fail(HNSW_ERR_HIP, "search kernel launch failed: %s", hipGetErrorString(e));
-    return HNSW_OK;
-}
-} // namespace
-
-extern "C++" {
-namespace hnsw_host {
-int search_batch_device_flag(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
-                             const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
-                             uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, uint32_t *d_any_flag, void *stream,
-                             float *d_stage);
-}
-}
 int32_t hnsw_search_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
                                  const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
                                  uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, void *stream) {
-    return search_batch_device_flag(idx, d_queries, nq, q_stride, params, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr, stream);
-}
-extern "C++" int hnsw_host::search_batch_device_flag(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
-                                 const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
-                                 uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, uint32_t *d_any_flag, void *stream,
-                                 float *d_stage) {
-    int rc = check_params(idx, params);
-    if (rc) return rc;
-    if (nq < 0 || nq > 0x7FFFFFFFLL) return fail(HNSW_ERR_BAD_ARG, "nq out of range");
-    if (nq == 0) return HNSW_OK;
-    if (!d_queries || !d_ids || !d_dist) return fail(HNSW_ERR_BAD_ARG, "null buffer");
-    if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
-    HIP_TRY(hipSetDevice(idx->device));
-    SearchArgs a{};
-    a.Q = d_queries; a.q_stride = q_stride; a.nq = nq; a.ef = params->ef; a.k = params->k; a.fill = params->fill; a.sem = params->semantics;
-    a.vt_bits = knn_vt_bits(idx, params->ef, params->semantics ? 1 : 0);
-    a.blk_bits = knn_blk_bits(idx, params->ef, params->semantics ? 1 : 0);
-    a.out_ids = d_ids; a.out_dist = d_dist; a.out_ndist = d_ndist; a.out_nhops = d_nhops; a.out_status = d_status;
-    a.any_flag = d_any_flag;
-    a.prio_tail = 0x7FFFFFFF;
-    // A batch larger than the chip holds at once is searched longest walk first (hnsw_order.hip):
-    // per-query results are unchanged, the launch's drain phase is made of short walks.
-    void *block = nullptr;
-    hipEvent_t *ev = nullptr;
-    if (idx->time_kernels && idx->tev_used + 3 <= 3 * 4096) {
-        while (idx->tev.size() < idx->tev_used + 3) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            idx->tev.push_back(e);
-        }
-        ev = &idx->tev[idx->tev_used];      // claimed (tev_used advanced) only once all three are recorded
-        HIP_TRY(hipEventRecord(ev[0], (hipStream_t)stream));
-    }
-    const int mode = idx->order_mode >= 0 ? idx->order_mode : env_int("HNSW_ORDER_QUERIES", -1);
-    // Ordered when more than half of what the chip holds: a batch that fits is faster too with its long walks
-    // dispatched first and spread over the CUs (C2, 7168 queries: 0.59 -> 0.45 ms byte rows, 0.68 -> 0.65 ms fp32);
-    // below that the pre-pass costs more than it returns.
-    if (mode != 0 && (mode == 1 || 2 * nq > resident_queries(idx, params->ef, params->semantics ? 1 : 0))) {
-        rc = order_longest_first(idx, d_queries, nq, q_stride, d_stage, (hipStream_t)stream, &block, &a.qmap, &a.pre_entry, &a.pre_key, &a.pre_nd, &a.pre_layer);
-        if (rc) return rc;
-        if (d_stage) a.Q = d_stage;        // the descent kernel left a device-resident copy of the (host-resident) queries
-        a.q_limit = nq;
-        a.lds_pad = balanced_lds_pad(idx, nq, params->ef, params->semantics ? 1 : 0);
-        launch_priorities(idx, nq, params->ef, params->semantics ? 1 : 0, a);
-    }
-    if (ev) HIP_TRY(hipEventRecord(ev[1], (hipStream_t)stream));
-    rc = launch_search_args(idx, a, (hipStream_t)stream);
-    if (!rc && idx->fb_queries > 0 && d_status && !d_any_flag) {
-        // opt-in exact mode of the device-pointer entry point (option "device_fallback_slab_bytes"): the queries the launch
-        // flagged are listed on the device and searched again with the slab, on the caller's stream, no host round trip.
-        // The re-run rewrites their results, counters and status words (bit 0 clear: a slab slot per node cannot overflow);
-        // with more flagged queries than the slab holds, the ones left over keep their flag.  Two small launches per call.
-        const int32_t cap = (int32_t)idx->fb_queries;
-        hipLaunchKernelGGL(flagged_list_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const uint32_t *)d_status, nq, (int32_t *)idx->dFbMap.p, cap);
-        if (hipGetLastError() != hipSuccess) return fail(HNSW_ERR_HIP, "flagged-query listing failed");
-        // (at most min(cap, nq) queries can be listed: no more blocks than that; the blocks past the count leave at once)
-        rc = search_rerun_device(idx, a.Q, nq, q_stride, params, d_ids, d_dist, d_ndist, d_nhops, d_status, (const int32_t *)idx->dFbMap.p,
-                                 std::min<int64_t>(cap, nq), (uint32_t *)idx->dFbSlab.p, (int32_t)std::min<int64_t>(idx->iv.n, 0x7FFFFFFF), (hipStream_t)stream);
-    }
-    if (ev && !rc) {
-        HIP_TRY(hipEventRecord(ev[2], (hipStream_t)stream));
-        idx->tev_used += 3;                 // an early return above leaves the triple unclaimed: nothing half-recorded is ever read
-        idx->tev_ordered.resize(idx->tev_used / 3);
-        idx->tev_ordered[idx->tev_used / 3 - 1] = block != nullptr;
-    }
-    return rc;
+    return knn_search(idx, params, {d_queries, nq, q_stride, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr}, (hipStream_t)stream);
 }
 
 int32_t hnsw_index_kernel_times(hnsw_index *idx, double *search_ms, double *prepass_ms, int32_t *calls) {
@@ -936,14 +949,11 @@ int32_t hnsw_index_kernel_times(hnsw_index *idx, double *search_ms, double *prep
 int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
                           const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
                           uint32_t *out_ndist, uint32_t *out_nhops) {
-    int rc = check_params(idx, params);
-    if (rc) return rc;
-    if (nq == 0) return HNSW_OK;
-    if (nq < 0 || !queries || !out_ids || !out_dist) return fail(HNSW_ERR_BAD_ARG, "bad buffers");
-    if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
+    int rc = check_batch(idx, params, nq, q_stride, queries && out_ids && out_dist);
+    if (rc || nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
     const int k = params->k;
-    const size_t qbytes = ((size_t)(nq - 1) * q_stride + idx->iv.d) * sizeof(float);
+    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d), rbytes = (size_t)nq * k * 4;
     if ((rc = idx->scratch.ensure(nq, qbytes, k))) return rc;
     // Upload, search (ordered longest walk first when the batch is larger than the chip holds) and download on one
     // of the handle's streams, ONE stream synchronisation at the end.
@@ -955,27 +965,20 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
     // no download step behind the launch either.  Pageable matrices are staged through hipMemcpyAsync as before.  Whether
     // any query needs the exactness fallback comes back as one word (pinned host memory, the kernel stores it), not as a
     // scan of nq status words.  (Splitting the batch into chunks on two streams to overlap copies and search measured
-    // 1.08 against 1.06 ms in round 1.)  HNSW_ZERO_COPY=0 switches the direct access off.
+    // 1.08 against 1.06 ms in round 1.)
     if ((rc = ensure_host_call_state(idx))) return rc;
     hipStream_t st = idx->hs[0];
-    // device address of a range the caller registered with hnsw_host_register, or nullptr
-    auto mapped = [&](const void *p, size_t bytes) -> void * {
-        static const int enabled = env_int("HNSW_ZERO_COPY", 1);
-        if (!enabled || !p || bytes == 0) return nullptr;
-        return registered_device_address(p, bytes);
-    };
-    const float *zq = (const float *)mapped(queries, qbytes);
-    int32_t *zi = (int32_t *)mapped(out_ids, (size_t)nq * k * 4);
-    float *zd = (float *)mapped(out_dist, (size_t)nq * k * 4);
-    uint32_t *znd = out_ndist ? (uint32_t *)mapped(out_ndist, (size_t)nq * 4) : nullptr;
-    uint32_t *znh = out_nhops ? (uint32_t *)mapped(out_nhops, (size_t)nq * 4) : nullptr;
+    const float *zq = (const float *)registered_device_address(queries, qbytes);
+    int32_t *zi = (int32_t *)registered_device_address(out_ids, rbytes);
+    float *zd = (float *)registered_device_address(out_dist, rbytes);
+    uint32_t *znd = out_ndist ? (uint32_t *)registered_device_address(out_ndist, (size_t)nq * 4) : nullptr;
+    uint32_t *znh = out_nhops ? (uint32_t *)registered_device_address(out_nhops, (size_t)nq * 4) : nullptr;
     if (!zi || !zd) zi = nullptr, zd = nullptr;                      // results: both matrices or neither
     // A SMALL batch from ordinary memory (a single query: Ohnsw.knn, test/test.ml:122) goes through a page-locked block of the
     // handle's own instead of three staged copies: the queries are copied into it by the host, the device reads them and writes
     // the results there, the host copies them out -- what is left of the call is one launch and one synchronisation.
     constexpr size_t SMALL = 32768;
-    const size_t rbytes = (size_t)nq * k * 4;
-    const bool small = !zq && !zi && !znd && !znh && qbytes <= SMALL && rbytes <= SMALL && (size_t)nq * 4 <= SMALL && env_int("HNSW_SMALL_CALLS", 1);
+    const bool small = !zq && !zi && !znd && !znh && qbytes <= SMALL && rbytes <= SMALL && (size_t)nq * 4 <= SMALL;
     if (small) {
         if (!idx->hSmall) {
             HIP_TRY(hipHostMalloc((void **)&idx->hSmall, 5 * SMALL, hipHostMallocMapped));
@@ -987,76 +990,59 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
         if (out_ndist) znd = (uint32_t *)(idx->hSmallDev + 3 * SMALL);
         if (out_nhops) znh = (uint32_t *)(idx->hSmallDev + 4 * SMALL);
     }
-    auto small_out = [&]() {
-        if (!small) return;
+    // the batch on the device: what the kernel reads or writes in place, the scratch buffers for the rest
+    KnnBatch b = idx->scratch.batch(nq, q_stride, k);
+    b.any_flag = idx->hFlagDev;
+    if (zq) b.Q = zq;
+    if (zi) b.ids = zi, b.dist = zd;
+    if (znd) b.nd = znd;
+    if (znh) b.nh = znh;
+    // ... and the caller's arrays the results are downloaded into
+    int32_t *to_ids = zi ? nullptr : out_ids;
+    float *to_dist = zi ? nullptr : out_dist;
+    uint32_t *to_nd = znd ? nullptr : out_ndist, *to_nh = znh ? nullptr : out_nhops;
+    *(volatile uint32_t *)idx->hFlag = 0;
+    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
+    rc = knn_search(idx, params, b, st, zq ? (float *)idx->scratch.q.p : nullptr);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    {   // no return while a copy into the caller's arrays may still be queued
+        const hipError_t ed = knn_download(b, k, to_ids, to_dist, to_nd, to_nh, st), es = hipStreamSynchronize(st);
+        if (ed != hipSuccess) return hip_fail(ed, "result download");
+        if (es != hipSuccess) return fail(HNSW_ERR_HIP, "search failed: %s", hipGetErrorString(es));
+    }
+    if (*(volatile uint32_t *)idx->hFlag & 1u) {      // (the flag: written by the kernel, pinned host memory)
+        // Exactness fallback for queries whose tie-overflow stack outgrew its LDS slots (rare: the rows of the whole batch
+        // are then copied out again)
+        if ((rc = knn_repair(idx, params, b, nullptr))) return rc;
+        const hipError_t ed = knn_download(b, k, to_ids, to_dist, to_nd, to_nh, nullptr), es = hipDeviceSynchronize();
+        if (ed != hipSuccess) return hip_fail(ed, "result download");
+        if (es != hipSuccess) return fail(HNSW_ERR_HIP, "result download failed: %s", hipGetErrorString(es));
+    }
+    if (small) {
         memcpy(out_ids, idx->hSmall + SMALL, rbytes); memcpy(out_dist, idx->hSmall + 2 * SMALL, rbytes);
         if (out_ndist) memcpy(out_ndist, idx->hSmall + 3 * SMALL, (size_t)nq * 4);
         if (out_nhops) memcpy(out_nhops, idx->hSmall + 4 * SMALL, (size_t)nq * 4);
-    };
-    const float *dQ = zq ? zq : (const float *)idx->scratch.q.p;            // where the queries can be read from the device
-    int32_t *dI = zi ? zi : (int32_t *)idx->scratch.ids.p;
-    float *dD = zi ? zd : (float *)idx->scratch.dist.p;
-    uint32_t *dNd = znd ? znd : (uint32_t *)idx->scratch.nd.p, *dNh = znh ? znh : (uint32_t *)idx->scratch.nh.p;
-    *(volatile uint32_t *)idx->hFlag = 0;
-    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
-    rc = search_batch_device_flag(idx, dQ, nq, q_stride, params, dI, dD, dNd, dNh, (uint32_t *)idx->scratch.st.p, idx->hFlagDev, st,
-                                  zq ? (float *)idx->scratch.q.p : nullptr);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    auto copy_out = [&](hipStream_t s_) -> int {
-        if (!zi) {
-            HIP_TRY(hipMemcpyAsync(out_ids, idx->scratch.ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s_));
-            HIP_TRY(hipMemcpyAsync(out_dist, idx->scratch.dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s_));
-        }
-        if (out_ndist && !znd) HIP_TRY(hipMemcpyAsync(out_ndist, idx->scratch.nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s_));
-        if (out_nhops && !znh) HIP_TRY(hipMemcpyAsync(out_nhops, idx->scratch.nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s_));
-        return HNSW_OK;
-    };
-    rc = copy_out(st);
-    {   // no return while a copy into the caller's arrays may still be queued
-        const hipError_t es = hipStreamSynchronize(st);
-        if (rc) return rc;
-        if (es != hipSuccess) return fail(HNSW_ERR_HIP, "search failed: %s", hipGetErrorString(es));
     }
-    if (!(*(volatile uint32_t *)idx->hFlag & 1u)) { small_out(); return HNSW_OK; }      // (the flag: written by the kernel, pinned host memory)
-    // Exactness fallback for queries whose tie-overflow stack outgrew its LDS slots (rare: the rows
-    // of the whole batch are then copied out again)
-    int64_t n_rerun = 0;
-    rc = rerun_overflowed(idx, nq, (const uint32_t *)idx->scratch.st.p,
-                          [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
-                              return search_rerun_device(idx, dQ, nq, q_stride, params, dI, dD, dNd, dNh, (uint32_t *)idx->scratch.st.p,
-                                                         qmap, c, slab, cap, nullptr);
-                          }, &n_rerun);
-    if (rc) return rc;
-    if (n_rerun > 0) {
-        rc = copy_out(nullptr);
-        const hipError_t es = hipDeviceSynchronize();
-        if (rc) return rc;
-        if (es != hipSuccess) return fail(HNSW_ERR_HIP, "result download failed: %s", hipGetErrorString(es));
-    }
-    small_out();
     return HNSW_OK;
 }
 
 int32_t hnsw_search_batch_h2d(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
                               const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
                               uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, void *stream) {
-    int rc = check_params(idx, params);
-    if (rc) return rc;
-    if (nq == 0) return HNSW_OK;
-    if (nq < 0 || nq > 0x7FFFFFFFLL || !queries || !d_ids || !d_dist) return fail(HNSW_ERR_BAD_ARG, "bad buffers");
-    if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
+    int rc = check_batch(idx, params, nq, q_stride, queries && d_ids && d_dist);
+    if (rc || nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
-    const size_t qbytes = ((size_t)(nq - 1) * q_stride + idx->iv.d) * sizeof(float);
+    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d);
     if ((rc = idx->scratch.q.ensure(qbytes))) return rc;
-    static const int zero_copy = env_int("HNSW_ZERO_COPY", 1);
-    const float *zq = zero_copy ? (const float *)registered_device_address(queries, qbytes) : nullptr;
-    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    hipStream_t st = (hipStream_t)stream;
+    const float *zq = (const float *)registered_device_address(queries, qbytes);
+    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
     // registered matrix: read by the device directly, the pre-pass (when there is one) leaves the device copy in sQ
-    rc = search_batch_device_flag(idx, zq ? zq : (const float *)idx->scratch.q.p, nq, q_stride, params, d_ids, d_dist, d_ndist, d_nhops, d_status,
-                                  nullptr, stream, zq ? (float *)idx->scratch.q.p : nullptr);
+    rc = knn_search(idx, params, {zq ? zq : (const float *)idx->scratch.q.p, nq, q_stride, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr},
+                    st, zq ? (float *)idx->scratch.q.p : nullptr);
     // the call returns while the device still reads the caller's matrix (in place, or as the source of the DMA above): the
     // range remembers it, so that hnsw_host_unregister / hnsw_host_free wait instead of pulling the pages from under a kernel
-    range_reader_enqueued(queries, qbytes, (hipStream_t)stream);
+    range_reader_enqueued(queries, qbytes, st);
     return rc;
 }
 
@@ -1064,10 +1050,9 @@ int32_t hnsw_search_submit(hnsw_index *idx, const float *queries, int64_t nq, in
                            const hnsw_search_params *params, hnsw_request **out) {
     if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    int rc = check_params(idx, params);
+    int rc = check_batch(idx, params, nq, q_stride, queries != nullptr);
     if (rc) return rc;
-    if (nq < 1 || nq > 0x7FFFFFFFLL || !queries) return fail(HNSW_ERR_BAD_ARG, "bad buffers (nq=%lld)", (long long)nq);
-    if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
+    if (nq == 0) return fail(HNSW_ERR_BAD_ARG, "nq=0: nothing to submit");
     HIP_TRY(hipSetDevice(idx->device));
     hnsw_request *r;
     if (!idx->free_requests.empty()) { r = idx->free_requests.back(); idx->free_requests.pop_back(); }
@@ -1077,19 +1062,16 @@ int32_t hnsw_search_submit(hnsw_index *idx, const float *queries, int64_t nq, in
     r->stream = idx->next_stream; idx->next_stream = (idx->next_stream + 1) & 3;
     if (!idx->hs[r->stream] && hipStreamCreateWithFlags(&idx->hs[r->stream], hipStreamNonBlocking) != hipSuccess)
         return give_back(fail(HNSW_ERR_HIP, "hipStreamCreate failed"));
-    const int k = params->k;
-    const size_t qbytes = ((size_t)(nq - 1) * q_stride + idx->iv.d) * sizeof(float);
-    if ((rc = r->buf.ensure(nq, qbytes, k))) return give_back(rc);
+    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d);
+    if ((rc = r->buf.ensure(nq, qbytes, params->k))) return give_back(rc);
     hipStream_t st = idx->hs[r->stream];
+    const KnnBatch b = r->buf.batch(nq, q_stride, params->k);
     if (hipMemcpyAsync(r->buf.q.p, queries, qbytes, hipMemcpyHostToDevice, st) != hipSuccess)
         return give_back(fail(HNSW_ERR_HIP, "query upload failed"));
     range_reader_enqueued(queries, qbytes, st);    // page-locked source: the DMA above outlives this call (see hnsw_host_unregister)
-    if (hipMemsetAsync(r->buf.flag.p, 0, 4, st) != hipSuccess) return give_back(fail(HNSW_ERR_HIP, "hipMemsetAsync failed"));
-    rc = search_batch_device_flag(idx, (const float *)r->buf.q.p, nq, q_stride, params, (int32_t *)r->buf.ids.p, (float *)r->buf.dist.p,
-                                  (uint32_t *)r->buf.nd.p, (uint32_t *)r->buf.nh.p, (uint32_t *)r->buf.st.p, (uint32_t *)r->buf.flag.p, st);
-    if (rc) return give_back(rc);
+    if (hipMemsetAsync(b.any_flag, 0, 4, st) != hipSuccess) return give_back(fail(HNSW_ERR_HIP, "hipMemsetAsync failed"));
+    if ((rc = knn_search(idx, params, b, st))) return give_back(rc);
     // the results follow the search on the request's stream: hnsw_search_wait only has to wait for them
-    r->host_flag = 0;
     idx->live_requests++;
     *out = r;
     return HNSW_OK;
@@ -1098,68 +1080,31 @@ int32_t hnsw_search_submit(hnsw_index *idx, const float *queries, int64_t nq, in
 int32_t hnsw_search_wait(hnsw_request *r, int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops) {
     if (!r || !r->idx) return fail(HNSW_ERR_BAD_ARG, "null request");
     hnsw_index *idx = r->idx;
+    // the request goes back to the pool only once its stream is idle, whatever failed: a later submit reuses its buffers
     auto done = [&](int code) { r->idx = nullptr; idx->live_requests--; idx->free_requests.push_back(r); return code; };
-    if (!out_ids || !out_dist) return done(fail(HNSW_ERR_BAD_ARG, "null result buffers"));
+    if (!out_ids || !out_dist) {
+        if (hipSetDevice(idx->device) == hipSuccess) (void)hipStreamSynchronize(idx->hs[r->stream]);
+        return done(fail(HNSW_ERR_BAD_ARG, "null result buffers"));
+    }
     if (hipSetDevice(idx->device) != hipSuccess) return done(fail(HNSW_ERR_HIP, "hipSetDevice failed"));
     hipStream_t st = idx->hs[r->stream];
     const int k = r->params.k;
-    const int64_t nq = r->nq;
+    const KnnBatch b = r->buf.batch(r->nq, r->q_stride, k);
     // results and the "any query flagged" word in one go; the exactness fallback (as in hnsw_search_batch) only if set
     uint32_t flag = 0;
-    {
-        hipError_t e0 = hipMemcpyAsync(out_ids, r->buf.ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
-        if (e0 == hipSuccess) e0 = hipMemcpyAsync(out_dist, r->buf.dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
-        if (e0 == hipSuccess && out_ndist) e0 = hipMemcpyAsync(out_ndist, r->buf.nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-        if (e0 == hipSuccess && out_nhops) e0 = hipMemcpyAsync(out_nhops, r->buf.nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-        if (e0 == hipSuccess) e0 = hipMemcpyAsync(&flag, r->buf.flag.p, 4, hipMemcpyDeviceToHost, st);
-        // synchronise whatever happened: copies already queued target the caller's arrays and `flag` (a stack word),
-        // and the request goes back to the pool only once its stream is idle
-        const hipError_t es = hipStreamSynchronize(st);
-        if (e0 == hipSuccess) e0 = es;
-        if (e0 != hipSuccess) return done(fail(HNSW_ERR_HIP, "search failed: %s", hipGetErrorString(e0)));
-    }
+    hipError_t e = knn_download(b, k, out_ids, out_dist, out_ndist, out_nhops, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, b.any_flag, 4, hipMemcpyDeviceToHost, st);
+    // synchronise whatever happened: copies already queued target the caller's arrays and `flag` (a stack word)
+    { const hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess) e = es; }
+    if (e != hipSuccess) return done(fail(HNSW_ERR_HIP, "search failed: %s", hipGetErrorString(e)));
     if (!(flag & 1u)) return done(HNSW_OK);
-    int rc = rerun_overflowed(idx, nq, (const uint32_t *)r->buf.st.p,
-                              [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
-                                  return search_rerun_device(idx, (const float *)r->buf.q.p, nq, r->q_stride, &r->params, (int32_t *)r->buf.ids.p,
-                                                             (float *)r->buf.dist.p, (uint32_t *)r->buf.nd.p, (uint32_t *)r->buf.nh.p, (uint32_t *)r->buf.st.p,
-                                                             qmap, c, slab, cap, st);
-                              });
+    const int rc = knn_repair(idx, &r->params, b, st);
     if (rc) return done(rc);
-    hipError_t e = hipMemcpyAsync(out_ids, r->buf.ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_dist, r->buf.dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out_ndist) e = hipMemcpyAsync(out_ndist, r->buf.nd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out_nhops) e = hipMemcpyAsync(out_nhops, r->buf.nh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+    e = knn_download(b, k, out_ids, out_dist, out_ndist, out_nhops, st);
     { const hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess) e = es; }
     if (e != hipSuccess) return done(fail(HNSW_ERR_HIP, "result download failed: %s", hipGetErrorString(e)));
     return done(HNSW_OK);
 }
-
-namespace {
-void remember_range(const void *p, size_t bytes, void *dev, int kind) {
-    std::lock_guard<std::mutex> lk(g_ranges_mu);
-    g_ranges.push_back({(const char *)p, bytes, (char *)dev, kind, {}});
-}
-// takes the range that STARTS at p off the list (no launch can pick it for direct access any more) and waits for the
-// readers that earlier asynchronous calls left on it; false: no such range
-bool retire_range(const void *p, int *kind) {
-    std::vector<InFlight> readers;
-    {
-        std::lock_guard<std::mutex> lk(g_ranges_mu);
-        size_t i = 0;
-        while (i < g_ranges.size() && g_ranges[i].p != (const char *)p) ++i;
-        if (i == g_ranges.size()) return false;
-        *kind = g_ranges[i].kind;
-        readers.swap(g_ranges[i].readers);
-        g_ranges.erase(g_ranges.begin() + (long)i);
-    }
-    for (InFlight &f : readers) {
-        if (hipEventSynchronize(f.ev) != hipSuccess) (void)hipGetLastError();
-        (void)hipEventDestroy(f.ev);
-    }
-    return true;
-}
-} // namespace
 
 int32_t hnsw_host_register(void *p, int64_t bytes) {
     if (!p || bytes <= 0) return fail(HNSW_ERR_BAD_ARG, "hnsw_host_register: null buffer or bytes <= 0");
@@ -1290,7 +1235,7 @@ int32_t hnsw_distance_batch(hnsw_index *idx, const float *queries, int64_t nq, i
     }
     HIP_TRY(hipSetDevice(idx->device));
     int rc;
-    const size_t qbytes = ((size_t)(nq - 1) * q_stride + idx->iv.d) * sizeof(float);
+    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d);
     if ((rc = idx->scratch.q.ensure(qbytes)) || (rc = idx->scratch.ids.ensure((size_t)nq * m * 4)) || (rc = idx->scratch.dist.ensure((size_t)nq * m * 4))) return rc;
     HIP_TRY(hipMemcpy(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(idx->scratch.ids.p, ids, (size_t)nq * m * 4, hipMemcpyHostToDevice));

@@ -19,13 +19,15 @@
 namespace hnsw_host {
 
 int fail(int code, const char *fmt, ...);
+// the code and message of a failed HIP call
+inline int hip_fail(hipError_t e, const char *what) {
+    return fail(e == hipErrorOutOfMemory ? HNSW_ERR_OOM : HNSW_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
 
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess)                                                               \
-            return ::hnsw_host::fail(e__ == hipErrorOutOfMemory ? HNSW_ERR_OOM : HNSW_ERR_HIP, \
-                                     "%s failed: %s", #expr, hipGetErrorString(e__));        \
+#define HIP_TRY(expr)                                                       \
+    do {                                                                    \
+        hipError_t e__ = (expr);                                            \
+        if (e__ != hipSuccess) return ::hnsw_host::hip_fail(e__, #expr);    \
     } while (0)
 
 struct DevBuf {
@@ -71,10 +73,27 @@ struct IndexTables {
     size_t bytes() const { size_t s = 0; each(*this, [&](const Table &t) { s += t.bytes; }); return s; }
 };
 
+// where one knn launch reads its queries and writes its results (device addresses; nd / nh / st / any_flag may be null)
+struct KnnBatch {
+    const float *Q;
+    int64_t nq, q_stride;
+    int32_t *ids;
+    float *dist;
+    uint32_t *nd, *nh, *st, *any_flag;
+};
+
+// bytes of a [nq][q_stride] float matrix up to the end of its last query's d values
+inline size_t query_bytes(int64_t nq, int64_t q_stride, int d) { return ((size_t)(nq - 1) * q_stride + d) * sizeof(float); }
+
 // the device buffers of one batch of nq queries: the queries (qbytes), k ids and distances per query, the per-query counters
 // and status words, and the launch's "any query flagged" word
 struct BatchBufs {
     DevBuf q, ids, dist, nd, nh, st, flag;
+    // these buffers as a batch of nq queries whose results go to rows row0.. of ids / dist (a multi shard's slice of the table)
+    KnnBatch batch(int64_t nq, int64_t q_stride, int k, int64_t row0 = 0) const {
+        return {(const float *)q.p, nq, q_stride, (int32_t *)ids.p + row0 * k, (float *)dist.p + row0 * k,
+                (uint32_t *)nd.p, (uint32_t *)nh.p, (uint32_t *)st.p, (uint32_t *)flag.p};
+    }
     int ensure(int64_t nq, size_t qbytes, int k) {
         int rc;
         if ((rc = q.ensure(qbytes)) || (rc = ids.ensure((size_t)nq * k * 4)) || (rc = dist.ensure((size_t)nq * k * 4)) ||
@@ -135,7 +154,6 @@ struct hnsw_request {
     hnsw_search_params params{};
     hnsw_host::BatchBufs buf;
     int stream = 0;
-    uint32_t host_flag = 0;
 };
 
 struct hnsw_index {
@@ -244,19 +262,16 @@ int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, i
                         void **block, const int32_t **qmap, const int32_t **pre_entry, const uint32_t **pre_key,
                         const uint32_t **pre_nd, int32_t *pre_layer);
 
-// hnsw_search_batch_device plus the optional device word that collects status bit 0 of the whole launch
-// d_stage (optional, [nq][q_stride] device floats): d_queries points into registered host memory (see order_longest_first)
-int search_batch_device_flag(::hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
-                             const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
-                             uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, uint32_t *d_any_flag, void *stream,
-                             float *d_stage = nullptr);
-// parameter / handle checks shared by every search entry point (HNSW_ERR_BAD_ARG, HNSW_ERR_EMPTY_INDEX, ...)
-int search_check(const ::hnsw_index *idx, const hnsw_search_params *p);
-// launch of the exactness fallback (see rerun_overflowed): `c` flagged queries, listed in qmap, searched again
-// with a global slab for their tie lists
-int search_rerun_device(::hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride, const hnsw_search_params *p,
-                        int32_t *d_ids, float *d_dist, uint32_t *d_nd, uint32_t *d_nh, uint32_t *d_st,
-                        const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap, hipStream_t st);
+// hnsw_capi.hip: parameter / handle checks shared by every search entry point (HNSW_ERR_BAD_ARG, HNSW_ERR_EMPTY_INDEX, ...)
+int check_params(const ::hnsw_index *idx, const hnsw_search_params *p);
+// hnsw_capi.hip: hnsw_search_batch_device for a KnnBatch, whose any_flag word (optional) collects status bit 0 of the launch.
+// d_stage (optional, [nq][q_stride] device floats): b.Q points into registered host memory (see order_longest_first)
+int knn_search(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, float *d_stage = nullptr);
+// hnsw_capi.hip: the exactness fallback of the host-buffer entry points (see rerun_overflowed) for a batch knn_search ran:
+// rewrites the rows of the queries it flagged in b.st
+int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st);
+// hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
+hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st);
 
 // log2 entries of the per-query LDS visited cache (never changes results)
 inline int search_vt_bits(const hnsw_index *idx, int ef) {
@@ -278,12 +293,11 @@ inline int search_vt_bits(const hnsw_index *idx, int ef) {
 // that can hold every node.  launch(qmap, count, slab, slab_cap) starts the kernel for `count`
 // flagged queries; it is synchronised here.
 template <class Launch>
-int rerun_overflowed(hnsw_index *idx, int64_t nq, const uint32_t *d_status, Launch &&launch, int64_t *n_rerun = nullptr) {
+int rerun_overflowed(hnsw_index *idx, int64_t nq, const uint32_t *d_status, Launch &&launch) {
     std::vector<uint32_t> st((size_t)nq);
     HIP_TRY(hipMemcpy(st.data(), d_status, (size_t)nq * 4, hipMemcpyDeviceToHost));
     std::vector<int32_t> flagged;
     for (int64_t i = 0; i < nq; ++i) if (st[(size_t)i] & 1u) flagged.push_back((int32_t)i);
-    if (n_rerun) *n_rerun = (int64_t)flagged.size();
     if (flagged.empty()) return HNSW_OK;
     const int64_t n = idx->iv.n;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(256, (512ll << 20) / (n * 4 + 1)));

@@ -151,16 +151,15 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
         m->hFlags[g] = 0;
         if (hi <= lo) continue;
         const int64_t ns = hi - lo;
-        const size_t qbytes = ((size_t)(ns - 1) * q_stride + d) * sizeof(float);
+        const size_t qbytes = query_bytes(ns, q_stride, d);
         if ((rc = b.q.ensure(qbytes)) || (rc = b.nd.ensure((size_t)ns * 4)) || (rc = b.nh.ensure((size_t)ns * 4)) || (rc = b.st.ensure((size_t)ns * 4)))
             return rc;
         hipStream_t st = m->streams[(size_t)g];
-        HIP_TRY(hipMemsetAsync(b.flag.p, 0, 4, st));
+        const KnnBatch shard = b.batch(ns, q_stride, k, lo);
+        HIP_TRY(hipMemsetAsync(shard.any_flag, 0, 4, st));
         HIP_TRY(hipMemcpyAsync(b.q.p, queries + lo * q_stride, qbytes, hipMemcpyHostToDevice, st));
-        rc = search_batch_device_flag(idx, (const float *)b.q.p, ns, q_stride, params, (int32_t *)b.ids.p + lo * k, (float *)b.dist.p + lo * k,
-                                      (uint32_t *)b.nd.p, (uint32_t *)b.nh.p, (uint32_t *)b.st.p, (uint32_t *)b.flag.p, st);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(&m->hFlags[g], b.flag.p, 4, hipMemcpyDeviceToHost, st));
+        if ((rc = knn_search(idx, params, shard, st))) return rc;
+        HIP_TRY(hipMemcpyAsync(&m->hFlags[g], shard.any_flag, 4, hipMemcpyDeviceToHost, st));
     }
     // ---- the exchange: every device receives every shard (shards [r_lo, r_hi) only: the whole table, or, after the
     //      fallback, the repaired shards again) ----
@@ -241,22 +240,15 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
     for (int g = 0; g < G; ++g) {
         const int64_t lo = shard_lo(nq, g, G), hi = shard_lo(nq, g + 1, G);
         if (hi <= lo) continue;
-        hnsw_index *idx = m->replicas[(size_t)g];
-        BatchBufs &b = m->buf[(size_t)g];
+        const KnnBatch shard = m->buf[(size_t)g].batch(hi - lo, q_stride, k, lo);
         HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
         if (m->hFlags[g] & 1u) {
-            rc = rerun_overflowed(idx, hi - lo, (const uint32_t *)b.st.p,
-                                  [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
-                                      return search_rerun_device(idx, (const float *)b.q.p, hi - lo, q_stride, params, (int32_t *)b.ids.p + lo * k,
-                                                                 (float *)b.dist.p + lo * k, (uint32_t *)b.nd.p, (uint32_t *)b.nh.p,
-                                                                 (uint32_t *)b.st.p, qmap, c, slab, cap, nullptr);
-                                  });
-            if (rc) return rc;
+            if ((rc = knn_repair(m->replicas[(size_t)g], params, shard, nullptr))) return rc;
             m->n_repaired_shards++;
             if ((rc = exchange(g))) return rc;
         }
-        if (out_ndist) HIP_TRY(hipMemcpyAsync(out_ndist + lo, b.nd.p, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, m->streams[(size_t)g]));
-        if (out_nhops) HIP_TRY(hipMemcpyAsync(out_nhops + lo, b.nh.p, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, m->streams[(size_t)g]));
+        HIP_TRY(knn_download(shard, k, nullptr, nullptr, out_ndist ? out_ndist + lo : nullptr, out_nhops ? out_nhops + lo : nullptr,
+                             m->streams[(size_t)g]));
     }
     m->last_nq = nq; m->last_k = k;
     return HNSW_OK;
@@ -268,6 +260,16 @@ int sync_all(hnsw_multi *m) {
         HIP_TRY(hipStreamSynchronize(m->streams[g]));
     }
     return HNSW_OK;
+}
+
+// the checks of both entry points, in this order: the handle, the params pointer, the batch (nq >= 1, the buffers, q_stride),
+// the params' values (before any allocation sized by them; same text as the single-device call)
+int check_multi(const hnsw_multi *m, const hnsw_search_params *p, int64_t nq, int64_t q_stride, bool buffers) {
+    if (!m || m->replicas.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_multi");
+    if (!p) return fail(HNSW_ERR_BAD_ARG, "null params");
+    if (nq < 1 || !buffers) return fail(HNSW_ERR_BAD_ARG, "bad buffers (nq=%lld)", (long long)nq);
+    if (q_stride < m->replicas[0]->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
+    return check_params(m->replicas[0], p);
 }
 
 } // namespace
@@ -326,16 +328,9 @@ int32_t hnsw_multi_replica(hnsw_multi *m, int32_t g, hnsw_index **out) {
 
 int32_t hnsw_multi_search_batch_device(hnsw_multi *m, const float *queries, int64_t nq, int64_t q_stride,
                                        const hnsw_search_params *params, int32_t **d_ids, float **d_dist) {
-    if (!m || m->replicas.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_multi");
-    if (!params) return fail(HNSW_ERR_BAD_ARG, "null params");
-    if (nq < 1 || !queries) return fail(HNSW_ERR_BAD_ARG, "bad buffers (nq=%lld)", (long long)nq);
-    if (q_stride < m->replicas[0]->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
-    {   // parameter errors are reported before any allocation sized by them
-        int rcp = search_check(m->replicas[0], params);
-        if (rcp) return rcp;
-    }
-    int rc = search_and_gather(m, queries, nq, q_stride, params, nullptr, nullptr);
-    if (rc) { (void)sync_all(m); return rc; }
+    int rc = check_multi(m, params, nq, q_stride, queries != nullptr);
+    if (rc) return rc;
+    if ((rc = search_and_gather(m, queries, nq, q_stride, params, nullptr, nullptr))) { (void)sync_all(m); return rc; }
     if ((rc = sync_all(m))) return rc;
     for (size_t g = 0; g < m->replicas.size(); ++g) {
         if (d_ids) d_ids[g] = (int32_t *)m->buf[g].ids.p;
@@ -364,26 +359,15 @@ int32_t hnsw_multi_copy_result(hnsw_multi *m, int32_t g, int32_t *out_ids, float
 int32_t hnsw_multi_search_batch(hnsw_multi *m, const float *queries, int64_t nq, int64_t q_stride,
                                 const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
                                 uint32_t *out_ndist, uint32_t *out_nhops) {
-    if (!m || m->replicas.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_multi");
-    if (!params) return fail(HNSW_ERR_BAD_ARG, "null params");
-    if (nq < 0) return fail(HNSW_ERR_BAD_ARG, "nq < 0");
-    const int G = (int)m->replicas.size();
-    if (G == 1 || nq == 0)
+    // one replica, or nothing to search: the single-device call (once the handle, the params pointer and nq >= 0 are checked)
+    if (m && !m->replicas.empty() && params && nq >= 0 && (m->replicas.size() == 1 || nq == 0))
         return hnsw_search_batch(m->replicas[0], queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops);
-    if (!queries || !out_ids || !out_dist) return fail(HNSW_ERR_BAD_ARG, "bad buffers");
-    if (q_stride < m->replicas[0]->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
-    {   // parameter errors are reported before any device work (same text as the single-device call)
-        int rcp = search_check(m->replicas[0], params);
-        if (rcp) return rcp;
-    }
-    const int k = params->k;
-    const size_t full = (size_t)nq * k * 4;
-    int rc = search_and_gather(m, queries, nq, q_stride, params, out_ndist, out_nhops);
-    if (rc) { (void)sync_all(m); return rc; }
+    int rc = check_multi(m, params, nq, q_stride, queries && out_ids && out_dist);
+    if (rc) return rc;
+    if ((rc = search_and_gather(m, queries, nq, q_stride, params, out_ndist, out_nhops))) { (void)sync_all(m); return rc; }
     // the host gets the table from ONE device (it is complete everywhere after the exchange)
     HIP_TRY(hipSetDevice(m->devices[0]));
-    HIP_TRY(hipMemcpyAsync(out_ids, m->buf[0].ids.p, full, hipMemcpyDeviceToHost, m->streams[0]));
-    HIP_TRY(hipMemcpyAsync(out_dist, m->buf[0].dist.p, full, hipMemcpyDeviceToHost, m->streams[0]));
+    HIP_TRY(knn_download(m->buf[0].batch(nq, q_stride, params->k), params->k, out_ids, out_dist, nullptr, nullptr, m->streams[0]));
     return sync_all(m);
 }
 

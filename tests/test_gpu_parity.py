@@ -254,6 +254,70 @@ def test_bad_arguments(H, tiny):
     oob = H.Hgraph(X[:3], [1, 0, 0], [[7], [-1], [-1]], entry_point=0)
     with pytest.raises(H.InvalidArgument, match="out of range"):
         oob.to_device()
+    # the codes of the other batch entry points, called raw: every check that can fail, and which one wins when two do
+    import ctypes
+    import torch
+    L = H.load()
+    OK, BAD, UNSUP = H.OK, H.ERR_BAD_ARG, H.ERR_UNSUPPORTED
+    dev = torch.device("cuda", 0)
+    ids = torch.empty((4, 3), dtype=torch.int32, device=dev)
+    dd = torch.empty((4, 3), dtype=torch.float32, device=dev)
+    Q = np.ascontiguousarray(X[:4])
+    q, di, dq = Q.ctypes.data, ids.data_ptr(), dd.data_ptr()
+    good, k_gt_ef, ef_big = H._SearchParams(8, 3, 0, 0), H._SearchParams(3, 5, 0, 0), H._SearchParams(2000, 3, 0, 0)
+
+    def h2d(nq, p=good, queries=q, stride=10, d_ids=di):
+        return L.hnsw_search_batch_h2d(hg.handle, queries, nq, stride, ctypes.byref(p) if p else None, d_ids, dq, None, None, None, None)
+    assert h2d(4, p=None) == BAD
+    assert h2d(4, p=k_gt_ef) == BAD
+    assert h2d(4, p=ef_big) == UNSUP
+    assert h2d(-1, p=ef_big) == UNSUP                  # the params are checked first
+    assert h2d(0, queries=None, stride=1, d_ids=None) == OK
+    assert h2d(-1) == BAD and h2d(2 ** 31) == BAD
+    assert h2d(4, queries=None) == BAD and h2d(4, d_ids=None) == BAD
+    assert h2d(4, stride=9) == BAD
+
+    req = ctypes.c_void_p()
+
+    def submit(nq, p=good, queries=q, stride=10, out=ctypes.byref(req)):
+        return L.hnsw_search_submit(hg.handle, queries, nq, stride, ctypes.byref(p) if p else None, out)
+    assert submit(4, out=None) == BAD
+    assert submit(4, p=None) == BAD and submit(4, p=k_gt_ef) == BAD and submit(4, p=ef_big) == UNSUP
+    assert submit(0, p=ef_big) == UNSUP
+    assert submit(0) == BAD and submit(-1) == BAD and submit(2 ** 31) == BAD
+    assert submit(4, queries=None) == BAD and submit(4, stride=9) == BAD
+    assert L.hnsw_search_wait(None, None, None, None, None) == BAD
+    assert submit(4) == OK                             # a request waited for without result buffers goes back to the pool
+    assert L.hnsw_search_wait(req, None, None, None, None) == BAD
+    assert L.hnsw_search_wait(req, None, None, None, None) == BAD          # ... and cannot be waited for again
+
+    hi, hd = np.empty((4, 3), np.int32), np.empty((4, 3), np.float32)
+    # hnsw_search_batch refuses an nq beyond INT32_MAX, as the other entry points do, before it sizes any buffer by it
+    assert L.hnsw_search_batch(hg.handle, q, 2 ** 31, 10, ctypes.byref(good), hi.ctypes.data, hd.ctypes.data, None, None) == BAD
+    assert "out of range" in L.hnsw_last_error().decode()
+    for devices in ([0], [0, 0]):
+        m = H.MultiHgraph(hg, devices)
+
+        def multi(nq, p=good, queries=q, stride=10, out_ids=hi.ctypes.data):
+            return L.hnsw_multi_search_batch(m._h, queries, nq, stride, ctypes.byref(p) if p else None, out_ids, hd.ctypes.data, None, None)
+
+        def multi_device(nq, p=good, queries=q, stride=10):
+            return L.hnsw_multi_search_batch_device(m._h, queries, nq, stride, ctypes.byref(p) if p else None, None, None)
+        assert L.hnsw_multi_search_batch(None, q, 4, 10, ctypes.byref(good), hi.ctypes.data, hd.ctypes.data, None, None) == BAD
+        assert L.hnsw_multi_search_batch_device(None, q, 4, 10, ctypes.byref(good), None, None) == BAD
+        assert multi(4, p=None) == BAD and multi_device(4, p=None) == BAD
+        assert multi(4, p=k_gt_ef) == BAD and multi_device(4, p=k_gt_ef) == BAD
+        assert multi(4, p=ef_big) == UNSUP and multi_device(4, p=ef_big) == UNSUP
+        assert multi(-1, p=ef_big) == BAD and multi_device(0, p=ef_big) == BAD      # the batch is checked before the params
+        assert multi(-1) == BAD and multi_device(0) == BAD and multi_device(-1) == BAD
+        assert multi(0, queries=None, stride=1, out_ids=None) == OK                 # (handed to hnsw_search_batch)
+        assert multi(0, p=ef_big) == UNSUP
+        assert multi(4, queries=None) == BAD and multi_device(4, queries=None) == BAD
+        assert multi(4, stride=9) == BAD and multi_device(4, stride=9) == BAD
+        # one replica: the call is hnsw_search_batch's (params first); several: the batch is checked before the params
+        assert multi(4, p=ef_big, out_ids=None) == (UNSUP if len(devices) == 1 else BAD)
+        assert multi(4, p=ef_big, stride=9) == (UNSUP if len(devices) == 1 else BAD)
+        m.release()
 
 
 def test_single_node(H):
@@ -312,10 +376,12 @@ def test_reference_select_neighbours_kats(H, case):
     assert sorted(got[0]) == case["expect"]
 
 
-def test_tie_overflow_beyond_lds_stack(H, oracle):
+@pytest.mark.parametrize("order", [0, 1])
+def test_tie_overflow_beyond_lds_stack(H, oracle, order):
     """More than 64 entries evicted while tied with max(W) and still unexpanded (lib/ohnsw.ml:568 keeps
     them poppable): the asynchronous entry point flags the query, the host entry point re-runs it with a
-    global slab and must equal the oracle -- including a node reachable only through such an entry."""
+    global slab and must equal the oracle -- including a node reachable only through such an entry.
+    Every path through the fallback, with the launch ordered (option order_queries 1) and not (0)."""
     import torch
     # 1-D positions, query at 0: E far, 127 identical "shell" points at 10, a chain approaching, Z close
     n = 229
@@ -338,10 +404,20 @@ def test_tie_overflow_beyond_lds_stack(H, oracle):
     g = oracle.Graph(n, 0, deg0, nbr0)
     sp = oracle.Space.l2(X, arith=oracle.TREE16)
     hg = H.Hgraph(X, deg0, nbr0, entry_point=0, max_degree=32)
+    hg.set_option("order_queries", order)
     Q = np.zeros((3, 1), np.float32)
     want = oracle.Ohnsw.knn_batch_bigarray(g, sp, Q, k=10, ef=128, ties=oracle.TIES_CANONICAL, counters=True)
     assert 228 in want[0][0]                       # the oracle does reach Z
     got = H.Ohnsw.knn_batch_bigarray(hg, 10, Q, ef=128, counters=True)
+    np.testing.assert_array_equal(got[0], want[0])
+    np.testing.assert_array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
+    np.testing.assert_array_equal(got[3], want[3])
+    # a pageable batch too large for the small-call block (160 KB of results): staged copies, downloaded again after the re-run
+    got = H.Ohnsw.knn_batch_bigarray(hg, 10, np.zeros((4096, 1), np.float32), ef=128, counters=True)
+    for i, j in ((0, 0), (1, 1), (3, 3)):
+        np.testing.assert_array_equal(got[i].view(np.uint32), np.broadcast_to(want[j][:1], got[i].shape).view(np.uint32))
+    # submit / wait: the re-run on the request's stream
+    got = H.submit(hg, Q, 128, 10).wait(counters=True)
     np.testing.assert_array_equal(got[0], want[0])
     np.testing.assert_array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
     np.testing.assert_array_equal(got[3], want[3])
@@ -378,6 +454,19 @@ def test_tie_overflow_beyond_lds_stack(H, oracle):
         np.testing.assert_array_equal(ids.cpu().numpy()[ok], want[0][ok])
         np.testing.assert_array_equal(dd.cpu().numpy()[ok].view(np.uint32), want[1][ok].view(np.uint32))
         np.testing.assert_array_equal(nh_t.cpu().numpy()[ok], want[3][ok])
+    # hnsw_search_batch_h2d with the slab: the re-run reads the queries the search read -- the staged copy of a pageable matrix;
+    # a page-locked one in place, or the pre-pass's device copy of it when the launch is ordered
+    hg.set_option("device_fallback_slab_bytes", 4 * n * 8)
+    for Qh in (Q, Qp):
+        st.zero_()
+        ids.fill_(-9)
+        keep = H.search_batch_h2d(hg, Qh, 128, 10, ids.data_ptr(), dd.data_ptr(), nd_t.data_ptr(), nh_t.data_ptr(), st.data_ptr(), 0)
+        torch.cuda.synchronize()
+        del keep
+        assert not (st.cpu().numpy() & 1).any()
+        np.testing.assert_array_equal(ids.cpu().numpy(), want[0])
+        np.testing.assert_array_equal(dd.cpu().numpy().view(np.uint32), want[1].view(np.uint32))
+        np.testing.assert_array_equal(nh_t.cpu().numpy().astype(np.uint32), want[3])
     hg.set_option("device_fallback_slab_bytes", 0)                        # freed: flags only again
     st.zero_()
     H.search_batch_device(hg, Qd.data_ptr(), 3, 1, 128, 10, ids.data_ptr(), dd.data_ptr(), 0, 0, st.data_ptr(), 0)

@@ -5,7 +5,6 @@
 # usage: tools/profile_c5_c3.sh <tag> [c5|c3|both]
 set -u
 TAG=${1:-r02}; WHICH=${2:-both}
-export HNSW_ORDER_QUERIES=${HNSW_ORDER_QUERIES:--1}
 if [ "$WHICH" = c5 ] || [ "$WHICH" = both ]; then
   export N=10000000 D=96 M=32 EFC=200 K=10 KIND=unit METRIC=0 INDEX_CACHE=/tmp/hnsw_c5.idx
   tools/profile_cmd.sh ${TAG}_c5 ${PASSES:-trace,inst,wait,fetch,tcc} python3 $PWD/tools/sweep.py 10000,512,0
