@@ -196,7 +196,7 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   searches read that one: each byte is converted back to the float it came from and
  *                   the arithmetic is unchanged, so distances are bit-identical for a quarter of the
  *                   bytes gathered.  1 = use the copy where it exists (default), 0 = read the float32
- *                   rows.  (Environment HNSW_BYTE_ROWS=0 at creation: do not build the copy.)
+ *                   rows.
  *   "split_rows"    a float32 row that ends 1..32 bytes past a 128-byte line (4d mod 128 in 1..32, e.g. d = 100: 400
  *                   bytes) costs one more 128-byte request per evaluation for those last bytes.  For such shapes
  *                   (when there are no byte rows) the index keeps the whole lines of every row in a table of its own
@@ -206,8 +206,7 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   1 = use the copy where it exists (default), 0 = read the plain rows, -1 = read the plain rows and FREE
  *                   the copy (it cannot come back).  The copy is not small: n * (128-byte lines of a row) + n * max_degree0 *
  *                   (16 or 32) bytes -- for a GloVe-shaped index (1.18 M x 100, M 32) 0.45 + 1.2 GB beside 0.47 GB of
- *                   vectors; hnsw_index_info.device_bytes counts it.  (Environment HNSW_SPLIT_ROWS=0 at creation: do not
- *                   build it.)
+ *                   vectors; hnsw_index_info.device_bytes counts it.
  *   "visited_blocks" how the knn kernels with W in four or more registers (ef > 128) remember visited nodes
  *                   (Visited, lib/ohnsw.ml:256-268): 0 = an LDS cache of node tags (all that rounds 1-4 had); 1 = an LDS
  *                   cache of BITMAP BLOCKS over "locality codes" -- a second numbering of the nodes, derived from the

@@ -45,10 +45,6 @@ def build(force=False, verbose=False, resource_log=None):
     base = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize",
             "-Wall", "-Wextra", "-Wno-unused-parameter",        # the sources are clean under these: keep them so
             "-I", os.path.join(ROOT, "include")]
-    if os.environ.get("HNSW_RB_NCH2"):
-        base += ["-DHNSW_RB_NCH2=" + os.environ["HNSW_RB_NCH2"]]
-    if os.environ.get("HNSW_SEARCH_MIN_WAVES"):
-        base += ["-DHNSW_SEARCH_MIN_WAVES(NCH,NSLOT,METRIC,FULL,SEMF)=" + os.environ["HNSW_SEARCH_MIN_WAVES"]]
     extra = os.environ.get("HNSW_EXTRA_CFLAGS", "").split()   # experiments: variant builds
     base += extra
     lib_out = os.environ.get("HNSW_LIB_OUT") or LIB

@@ -46,7 +46,7 @@ template <int METRIC>
 hipError_t dispatch_k1(int nch, int nslot, const BuildView &bv, const BatchView &bt, hipStream_t st) {
     switch (nch) {
     case 1: return launch_k1<1, 8, METRIC>(nslot, bv, bt, st);
-    case 2: return launch_k1<2, HNSW_RB_NCH2, METRIC>(nslot, bv, bt, st);
+    case 2: return launch_k1<2, RB_NCH2, METRIC>(nslot, bv, bt, st);
     case 4: return launch_k1<4, 2, METRIC>(nslot, bv, bt, st);
     case 8: return launch_k1<8, 1, METRIC>(nslot, bv, bt, st);
     default: return launch_k1<16, 1, METRIC>(nslot, bv, bt, st);

@@ -216,9 +216,9 @@ hipError_t dispatch_dist(int nch, const IndexView &iv, const float *Q, int64_t q
     // blockIdx.y strides over a query's ids: enough blocks to fill the chip twice over (8 192 waves: what it holds at four waves
     // per SIMD, twice), no more -- every block starts by loading its query, and a block that then evaluates thirty-two batches
     // amortises that better than one that evaluates four (bench_dist's shape, profiles/r06_dist_ab.txt: 6.07 / 5.77 TB/s at 8 192
-    // waves on two boxes, 5.85 / 5.76 at 65 536 -- rounds 1-5's grid: within the noise of one box; HNSW_DIST_WAVES: tuning)
-    const int64_t want_waves = env_int("HNSW_DIST_WAVES", 8192);
-    const int64_t per_query = std::max<int64_t>(1, (want_waves + std::max<int64_t>(nq, 1) - 1) / std::max<int64_t>(nq, 1));
+    // waves on two boxes, 5.85 / 5.76 at 65 536 -- rounds 1-5's grid: within the noise of one box)
+    constexpr int64_t DIST_WAVES = 8192;
+    const int64_t per_query = std::max<int64_t>(1, (DIST_WAVES + std::max<int64_t>(nq, 1) - 1) / std::max<int64_t>(nq, 1));
     const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(256, (m + 15) / 16), per_query));
     dim3 grid((unsigned)nq, gy), block(64);
     switch (nch) {
@@ -236,10 +236,10 @@ hipError_t dispatch_dist(int nch, const IndexView &iv, const float *Q, int64_t q
 // costs no residency and saves re-evaluations, which on clustered data are many (1.18 M x 100 unit vectors around 256
 // directions, M 32, ef 256: 8239 evaluations per query with 2^11 tags against 5015 in the oracle, 6592 with 2^12: 5.22 ->
 // 4.36 ms per 10 k batch; 2^13 would halve the residency: 5.17 ms).  So: the largest cache (up to 2^14 tags) that keeps the
-// waves per CU the variant reaches with the base size.  Never changes results; "vt_bits" / HNSW_VT_BITS still override.
+// waves per CU the variant reaches with the base size.  Never changes results; "vt_bits" still overrides.
 int knn_vt_bits(hnsw_index *idx, int ef, int semf) {
     const int base = search_vt_bits(idx, ef);
-    if (idx->vt_bits_override || env_int("HNSW_VT_BITS", 0) > 0 || !env_int("HNSW_VT_GROW", 1)) return base;
+    if (idx->vt_bits_override) return base;
     const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(ef, nch);
     const int vkey = ((nslot * 2 + semf) * ROW_VARIANTS + variant_full(idx)) * 32 + base;
     if (idx->vt_grow_key == vkey) return idx->vt_grow_bits;
@@ -276,7 +276,7 @@ SearchArgs knn_args(const hnsw_search_params &p, const KnnBatch &b, int vt_bits,
 // C3's kernels, 16 waves per CU: 2^8 blocks = 65 536 codes).
 // Which of the two forgets less depends on the DATA -- on clustered vectors the blocks end C5's shape's 40 % repeated
 // evaluations (1-4 % left); on structureless vectors no numbering has locality, a block holds one visited node and the tag
-// cache wins -- so unless the caller decides (option "visited_blocks" 0 / 1, HNSW_VISITED_BLOCKS), the handle MEASURES, once
+// cache wins -- so unless the caller decides (option "visited_blocks" 0 / 1), the handle MEASURES, once
 // per kernel shape: 256 of the index's own vectors are searched both ways and the evaluations counted; the blocks are taken
 // when they save at least 5 %.  The measurement (and building the codes: one descent per node per upper layer, a sort) runs
 // inside the first search call that needs the answer and synchronises the device; indices of fewer than 200 000 nodes are
@@ -288,8 +288,7 @@ SearchArgs knn_args(const hnsw_search_params &p, const KnnBatch &b, int vt_bits,
 // synchronises; nothing in flight reads the table when no shape has chosen it).
 void release_unused_lcode0(hnsw_index *idx) {
     if (!idx->tables.lcode0.p) return;
-    const int mode = idx->blk_mode >= 0 ? idx->blk_mode : env_int("HNSW_VISITED_BLOCKS", -1);
-    if (mode == 1) return;                   // the caller asked for blocks wherever they can run: keep the table
+    if (idx->blk_mode == 1) return;                  // the caller asked for blocks wherever they can run: keep the table
     for (auto &c : idx->blk_choice) if (c[0] > 0 || c[1] > 0) return;
     drop_lcode0(idx);
 }
@@ -316,7 +315,7 @@ int blk_capacity_bits(hnsw_index *idx, int ef, int semf) {
 
 // does option "visited_blocks" at -1 consider this shape at all?
 bool blk_auto_eligible(const hnsw_index *idx, int nslot) {
-    if (idx->iv.n < env_int("HNSW_VISITED_BLOCKS_MIN_N", 200000)) return false;
+    if (idx->iv.n < 200000) return false;
     // Left to itself the handle only considers the FLOAT32 shapes whose hand-scheduled loop has the block filter (rows of 65..256
     // dimensions -- full, ragged or split --, W in three to eight registers: C3's and C5's kernels): those kernels are bound by
     // row requests, so fewer evaluations are less time.  The byte-row loops have the filter too (an explicit "visited_blocks" 1
@@ -329,7 +328,7 @@ bool blk_auto_eligible(const hnsw_index *idx, int nslot) {
 int knn_blk_bits(hnsw_index *idx, int ef, int semf) {
     const int nslot = pick_nslot_knn(ef, pick_nch(idx->iv.nchunks));
     const int ls = slot_class(nslot);
-    const int mode = idx->blk_mode >= 0 ? idx->blk_mode : env_int("HNSW_VISITED_BLOCKS", -1);
+    const int mode = idx->blk_mode;
     if (mode == 0 || nslot < 3 || idx->lcode_state < 0) return 0;
     if (mode < 0 && !blk_auto_eligible(idx, nslot)) return 0;
     int &choice = idx->blk_choice[ls][semf];
@@ -397,10 +396,9 @@ int64_t resident_queries(hnsw_index *idx, int ef, int semf) {
 // gfx950 hands LDS out in 1280-byte granules, 128 per CU, so k granules per wave hold floor(128 / k) waves.
 // Chosen: the fewest waves per CU that still cover nq / passes.
 int balanced_lds_pad(hnsw_index *idx, int64_t nq, int ef, int semf) {
-    const int forced = idx->lds_pad >= 0 ? idx->lds_pad : env_int("HNSW_LDS_PAD", -1);
-    if (forced >= 0) {     // an explicit request is clamped to what a workgroup may ask for beside its own scratch
+    if (idx->lds_pad >= 0) {     // option "lds_pad": clamped to what a workgroup may ask for beside its own scratch
         const int64_t base_f = (int64_t)knn_lds_bytes(idx, ef, semf);
-        return (int)std::max<int64_t>(0, std::min<int64_t>(std::min(forced, 32768), 65536 - base_f));
+        return (int)std::max<int64_t>(0, std::min<int64_t>(std::min(idx->lds_pad, 32768), 65536 - base_f));
     }
     const int64_t resident = resident_queries(idx, ef, semf);
     if (nq <= resident || idx->resident_per_cu <= 0) return 0;
@@ -429,9 +427,6 @@ int balanced_lds_pad(hnsw_index *idx, int64_t nq, int ef, int semf) {
         const search_occupancy_fn occ = k_occupancy[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][semf][variant_full(idx)];
         while (pad > 0 && (base + pad > max_lds || occ(nch_, nslot_, (size_t)(base + pad), knn_blk_bits(idx, ef, semf) > 0) < want_per_cu)) pad = pad > GRANULE ? pad - GRANULE : 0;
     }
-    if (idx->debug_last_nq != nq && env_int("HNSW_DEBUG_RESIDENT", 0) && ((idx->debug_last_nq = nq), true))
-        fprintf(stderr, "hnsw: nq %lld, %d waves/CU x %d CUs resident, %lld passes -> want %lld waves/CU: LDS %lld + %lld B\n",
-                (long long)nq, idx->resident_per_cu, idx->cus, (long long)passes, (long long)want_per_cu, (long long)base, (long long)pad);
     return (int)pad;
 }
 

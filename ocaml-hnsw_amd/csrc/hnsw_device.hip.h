@@ -28,17 +28,6 @@ namespace hnsw_dev {
 
 constexpr uint32_t KEY_INF = 0xFFFFFFFFu;
 
-// experiment switches (tools/mkvariant.sh builds variants with -D...=0)
-#ifndef HNSW_INT_TRANSPOSE
-#define HNSW_INT_TRANSPOSE 1     // byte rows + byte query: the NB integer reductions of a round as one transposing reduction
-#endif
-#ifndef HNSW_ASM_LOOP
-#define HNSW_ASM_LOOP 1          // the headline shape's layer-0 loop instruction by instruction (hnsw_hop_asm.hip.h)
-#endif
-#ifndef HNSW_INSERT_ISLAND
-#define HNSW_INSERT_ISLAND 1     // two-slot Ohnsw lists: the accept-and-insert loop of a round as one hand-scheduled block
-#endif
-
 struct IndexView {
     const float *X;          // [n][stride] zero-padded rows
     int64_t stride;          // floats, multiple of 4
@@ -545,9 +534,6 @@ __device__ __forceinline__ void wlist_mark_expanded(WList<NSLOT> &w, int index, 
 // bits spread as well as a hash would, and no multiply sits in front of the LDS read).  The host
 // sizes the cache so that (n-1) div #sets < 0xFFFF: the value 0xFFFF marks an empty way and never
 // equals a real tag.  A miss for a node already evaluated is harmless -- see the header comment.
-#ifndef HNSW_VT_THREE_WAYS
-#define HNSW_VT_THREE_WAYS 1
-#endif
 struct WaveCtx {
     int lane, r, l16;
     uint32_t *vt;        // visited cache, 1 << (vt_bits - 1) words
@@ -812,27 +798,6 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
         // order -- computed here with 4-byte dot products (|x - q|^2 = x.x - 2 x.q + q.q): 4 instructions per 8
         // dimensions where the float path needs 24.
         if (cx.qint) {
-#if !HNSW_INT_TRANSPOSE
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                uint32_t sxq = 0, sxx = 0;
-#pragma unroll
-                for (int i = 0; i < NCH; ++i) {
-                    sxq = __builtin_amdgcn_udot4(v8[b][i], cx.qb[i], sxq, false);
-                    if (METRIC == 0) sxx = __builtin_amdgcn_udot4(v8[b][i], v8[b][i], sxx, false);
-                }
-                int32_t t = METRIC == 0 ? (int32_t)sxx - 2 * (int32_t)sxq : (int32_t)sxq;
-                t = reduce16_i32(t);
-                if (METRIC == 0) t += cx.q2;
-                const uint32_t key = dist_to_key<METRIC>((float)t);
-                const bool here = l16 == b;
-                kk = here ? key : kk;
-                ii = here ? id[b] : ii;
-            }
-            out_key = (mine + l16 < cnt) ? kk : KEY_INF;
-            out_id = ii;
-            return;
-#endif
             constexpr int NBP = NB <= 1 ? 1 : NB <= 2 ? 2 : NB <= 4 ? 4 : 8;   // batches padded to a power of two
             int32_t t[NBP];
 #pragma unroll
@@ -920,16 +885,14 @@ __device__ __forceinline__ int eval_round(const IndexView &iv, const float4 (&qv
 // repeat until no change.  No visited set (argument ignored, :493).  Same row evaluation as the layer
 // search (keys stay in registers: lane order = row order, so the first lane holding the minimum is the
 // first neighbour in row order that attains it); the upper-row lookup is one 8-byte load.
-#if HNSW_ASM_LOOP
 // the same descent instruction by instruction for C2's shape (hnsw_hop_asm.hip.h)
 __device__ __forceinline__ void greedy_descend_bytes_l2_asm(const IndexView &iv, int from, int to, int &cur, uint32_t &cur_key,
                                                             const WaveCtx &cx, uint32_t &n_dist);
-#endif
 template <int NCH, int RB, int METRIC, int ROWS = -1>
 __device__ __forceinline__ void greedy_descend(const IndexView &iv, const float4 (&qv)[NCH], int from,
                                                int to, int &cur, uint32_t &cur_key, const WaveCtx &cx,
                                                uint32_t &n_dist) {
-#if HNSW_ASM_LOOP && !defined(HNSW_PHASE_TIMING)
+#ifndef HNSW_PHASE_TIMING
     if constexpr (NCH == 2 && METRIC == 0 && ROWS == 2) {
         // upper rows of at most 16 neighbours (M <= 16), a byte-valued query, tables the 32-bit offsets reach: the last row
         // ends at byte (rowsU * SU) * 4, and the block multiplies (row + layer - 1) by SU * 4 in 32 bits
@@ -1121,10 +1084,11 @@ __device__ __forceinline__ void hop_eval(const IndexView &iv, const float4 (&qv)
         asm volatile("" :: "s"(pass));
 #endif
         HNSW_PHASE(pc, 2);                                               // ids from LDS, row loads, arithmetic, keys, accept ballot
-#if HNSW_INSERT_ISLAND && !defined(HNSW_PHASE_TIMING)
-        // (not in the kernel that has the hand-written loop: this is then its seldom-taken path, and the block's scalar
-        // temporaries would push that kernel past the 96 SGPRs that eight waves per SIMD allow)
-        if constexpr (NSLOT == 2 && SEM == 0 && !(HNSW_ASM_LOOP && NCH == 2 && METRIC == 0 && ROWS == 2)) {
+#ifndef HNSW_PHASE_TIMING
+        // two-slot Ohnsw lists: the accept-and-insert loop of a round as one hand-scheduled block (not in the kernel that has
+        // the hand-written loop: this is then its seldom-taken path, and the block's scalar temporaries would push that kernel
+        // past the 96 SGPRs that eight waves per SIMD allow)
+        if constexpr (NSLOT == 2 && SEM == 0 && !(NCH == 2 && METRIC == 0 && ROWS == 2)) {
             while (pass) {
                 if (insert_island2(w, ckey, cid, pass)) w.ovf_cnt = 0;
                 if (pass == 0ull) break;
@@ -1176,7 +1140,7 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
                                              uint32_t &n_dist, uint32_t &n_hops, uint32_t &status) {
     const int lane = cx.lane;
     const bool full_rows = ROWS < 0 ? iv.nchunks == 16 * NCH : ROWS == 1;
-#if HNSW_ASM_LOOP && !defined(HNSW_PHASE_TIMING)
+#ifndef HNSW_PHASE_TIMING
     // The hand-scheduled loops (hnsw_hop_asm.hip.h: HopLoop<NCH, NSLOT, METRIC, ROWS, SEM, BLK>, one instantiation per shape from the
     // generated table hnsw_hop_instances.inc), same results.  Shapes: byte rows and a byte-valued query, or float32 rows (full,
     // ragged, split), of 65..128 (NCH 2) or 129..256 (NCH 4) dimensions; W in 1, 2, 3, 4, 6 or 8 registers; either metric, either
@@ -1222,7 +1186,7 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
     pc.mark = clock64();
 #endif
     for (;;) {
-#if HNSW_ASM_LOOP && HNSW_ASM_LOOP_SEM1 && !defined(HNSW_PHASE_TIMING)
+#ifndef HNSW_PHASE_TIMING
         if constexpr (ASM_ANY && SEM != 0) {
             // The functor rule on the same hand-scheduled loops: while the tie set is empty the two rules differ only in the
             // moments an entry would ENTER the set (a neighbour evaluated AT max(W).d with W full; an entry evicted while tied
@@ -1411,19 +1375,14 @@ __device__ __forceinline__ void load_row(float4 (&qv)[NCH], const IndexView &iv,
 // spilling (8 waves would spill); the kernel with the hand-written loop (hnsw_hop_asm.hip.h) is held to 8 waves/SIMD: the
 // loop itself needs 57 VGPRs and ~45 SGPRs, but left alone the allocator spreads the C++ paths around it over all 102
 // SGPRs, which costs the eighth wave (it now parks ~20 scalars of the prologue / epilogue in VGPR lanes instead); the
-// other variants are left to the allocator
-#ifndef HNSW_SEM1_8WAVES       /* the functor-rule kernels of the headline shape at eight waves per SIMD too */
-#define HNSW_SEM1_8WAVES 1
-#endif
-#ifndef HNSW_SEARCH_MIN_WAVES
-#define HNSW_SEARCH_MIN_WAVES(NCH, NSLOT, METRIC, ROWS, SEMF) \
-    (((NCH) <= 2 && (NSLOT) <= 2 && (METRIC) == 0 && (ROWS) == 1) ? 7 : \
-     (HNSW_ASM_LOOP && (NCH) == 2 && (NSLOT) <= 4 && (METRIC) == 0 && (ROWS) == 2 && ((SEMF) == 0 || HNSW_SEM1_8WAVES)) ? 8 : 1)
-#endif
+// other variants are left to the allocator.  (The functor-rule kernels of the headline shape are held to 8 waves too.)
+constexpr int search_min_waves(int NCH, int NSLOT, int METRIC, int ROWS) {
+    return (NCH <= 2 && NSLOT <= 2 && METRIC == 0 && ROWS == 1) ? 7 : (NCH == 2 && NSLOT <= 4 && METRIC == 0 && ROWS == 2) ? 8 : 1;
+}
 // SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3 | 4, see hop_round
 // BLK: 1 = Visited as bitmap blocks (a.blk_bits slots, iv.lcode / lcode0 present), see search_layer
 template <int NCH, int RB, int NSLOT, int METRIC, int SEMF, int ROWS, int BLK = 0>
-__global__ void __launch_bounds__(64, HNSW_SEARCH_MIN_WAVES(NCH, NSLOT, METRIC, ROWS, SEMF))
+__global__ void __launch_bounds__(64, search_min_waves(NCH, NSLOT, METRIC, ROWS))
 hnsw_search_kernel(const IndexView iv, const SearchArgs a) {
     extern __shared__ uint32_t lds[];
     const int lane = threadIdx.x;
@@ -1432,11 +1391,9 @@ hnsw_search_kernel(const IndexView iv, const SearchArgs a) {
     if (a.q_limit && (q < 0 || q >= a.q_limit)) return;     // never follow a bad map entry into memory
     WaveCtx cx = make_ctx(lds, a.vt_bits, lane, BLK ? a.blk_bits : 0);
     if (a.ovf_g) { cx.ovf.g = a.ovf_g + (int64_t)blockIdx.x * a.ovf_gcap; cx.ovf.gcap = a.ovf_gcap; }
-#if HNSW_VT_THREE_WAYS
     // ef > 128: the walk visits several times what the cache holds; float32 rows from ef 65 on (a re-evaluation costs four times a
     // byte row's bytes there, and the two-slot byte-row loop -- the headline -- keeps its branch-free two-way filter)
     if constexpr (NSLOT >= 3 || (NSLOT == 2 && ROWS != 2)) visited_three_ways(cx, iv.n);
-#endif
     // Issue priority inside an ordered launch (blocks run the walks predicted longest first): the launch ends with its
     // longest walk or with the last of the late starters (the blocks that had to wait for a free slot), so those two ends
     // of the order are issued ahead of the waves they share a SIMD with; the middle has slack (C2, 10 k queries: 0.38 ->

@@ -29,27 +29,6 @@
 
 namespace hnsw_dev {
 
-#ifndef HNSW_ASM_LOOP
-#define HNSW_ASM_LOOP 1
-#endif
-#ifndef HNSW_ASM_LOOP_F32       /* the float32-row instantiations (0: those shapes keep search_layer's C++ loop) */
-#define HNSW_ASM_LOOP_F32 1
-#endif
-#ifndef HNSW_ASM_LOOP_SPLIT     /* ... and the split-row ones */
-#define HNSW_ASM_LOOP_SPLIT 1
-#endif
-#ifndef HNSW_ASM_LOOP_8SLOTS    /* ... and W in eight registers (ef 257..512) */
-#define HNSW_ASM_LOOP_8SLOTS 1
-#endif
-#ifndef HNSW_ASM_LOOP_BYTES4    /* ... and byte rows of 129..256 dimensions */
-#define HNSW_ASM_LOOP_BYTES4 1
-#endif
-#ifndef HNSW_ASM_LOOP_F32N4      /* ... and float32 rows of 129..256 dimensions */
-#define HNSW_ASM_LOOP_F32N4 1
-#endif
-#ifndef HNSW_ASM_LOOP_SEM1      /* the instantiations for the functor accept rule (0: that rule keeps the C++ loop) */
-#define HNSW_ASM_LOOP_SEM1 1
-#endif
 // measurement builds (-DHNSW_ASM_PHASE=k, tools/asm_phases.sh): shader-clock cycles spent between probe point k and k + 1 of
 // every hop, summed into the n_dist counter.  Points: 0 hop start, 1 adjacency row in registers, 2 fresh list written,
 // 3 round evaluated and accept mask known, 4 insertions done.  s[90:93] are used by name (declared clobbered).
@@ -92,23 +71,14 @@ namespace hnsw_dev {
 // Where a hop loop starts relative to a 64-byte instruction line: k dwords past one.  A lone wave's query time moves by
 // up to 4 % with k, with a period of 8 dwords (which branch targets end a 32-byte fetch window): two-slot loop on C2 0.1369 ms
 // at k = 2 or 10, 0.141 at 4 / 12, 0.1425-0.1435 at 0 / 6 / 8 / 14; the loaded launches follow by ~1 %.  Pinned per loop so
-// that code added in front of a loop does not move it.  (tools/mkvariant.sh -DHNSW_ASM_ALIGN_PAD[1|4]=k)
-#ifndef HNSW_ASM_ALIGN_PAD
+// that code added in front of a loop does not move it.
 #define HNSW_ASM_ALIGN_PAD 2
-#endif
-#ifndef HNSW_ASM_ALIGN_PAD4
 #define HNSW_ASM_ALIGN_PAD4 6        // four-slot loop, ef 192: 0.2116 ms at 6, 0.214 at 0 / 4, 0.221 at 2
-#endif
-#ifndef HNSW_ASM_ALIGN_PAD1
 #define HNSW_ASM_ALIGN_PAD1 0        // one-slot loop, ef 64: within 1.5 % over k
-#endif
 #define HNSW_STR2(x) #x
 #define HNSW_STR(x) HNSW_STR2(x)
 #define HNSW_ASM_ALIGN_K(K) ".p2align 6\n\t.rept " HNSW_STR(K) "\n\ts_nop 0\n\t.endr\n"
 #define HNSW_ASM_ALIGN HNSW_ASM_ALIGN_K(HNSW_ASM_ALIGN_PAD)
-#ifndef HNSW_ASM_PREFETCH
-#define HNSW_ASM_PREFETCH 1
-#endif
 
 // One hand-scheduled layer-0 loop per shape: an explicit specialisation of this template (hnsw_hop_loop.inc, instantiated by the
 // generated table hnsw_hop_instances.inc) with available = true and
@@ -570,14 +540,11 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
 // Every shape in two halves: ISSUE (ids from LDS, row addresses, the loads) and CONSUME (dot products, the transposing
 // reduction, keys, accept mask, cnt).  A round runs them back to back; a hop with MORE than one round (more than 16 fresh
 // neighbours: four hops in ten on a hard set at ef 176) issues the next round's loads BEFORE the current round's insertions
-// and consumes them behind -- HNSW_ASM_RPIPE, round 6: the next round's memory round trip (400 cycles idle, 1000 loaded) runs
+// and consumes them behind (round pipelining): the next round's memory round trip (400 cycles idle, 1000 loaded) runs
 // under the 1000-1500 cycles of insertions instead of behind them.  Nothing the insertions touch is live in the issued half
 // (rows d0..d7, ids id0..id3, addresses ad0 / ad1; the select into cid belongs to CONSUME: cid still holds the current
 // round's ids), cnt does not change in between (the shape picked at issue is the shape consumed), evaluation and accept
 // order are those of the unpipelined loop: same bits, same counters.
-#ifndef HNSW_ASM_RPIPE
-#define HNSW_ASM_RPIPE 1
-#endif
 #define HNSW_B8_ISSUE_8                                                                                                               \
         HNSW_ID_READ0("%[id0]", 1)                                                                                                  \
         HNSW_ID_READN("%[id1]")                                                                                                  \
@@ -684,12 +651,12 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
         "s_cbranch_scc1 40f\n\t"                                                                                                      \
         "s_cmp_lt_u32 %[cnt], 5\n\t"                                                                                                  \
         "s_cbranch_scc1 25f\n\t"
-// behind the insertions of a round: nothing left -> next hop (1b); else the next round
+// behind the insertions of a round: nothing left -> next hop (1b); else the next round (the unpipelined loops: rows of
+// 129..256 dimensions)
 #define HNSW_HOP_AFTER_INSERT_PLAIN \
         "s_cmp_gt_i32 %[cnt], 0\n\t"  \
         "s_cbranch_scc0 1b\n\t"       \
         HNSW_HOP_NEXT_ROUND
-#if HNSW_ASM_RPIPE
 // (an 8-row or a 4-row round never leaves candidates behind: 5..8 / 1..4 were left when it was picked; only the 16-row round
 // does, and it sits behind the loop: the in-line path is the unpipelined text)
 #define HNSW_HOP_ROUND_COMMON \
@@ -738,26 +705,6 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
         "47:\n\t"                                                                                                                     \
         HNSW_B8_ISSUE_4                                                                                                               \
         "s_branch 50b\n"
-#else
-#define HNSW_HOP_ROUND_COMMON \
-        HNSW_HOP_ROUND_SELECT                                                                                                         \
-  /* ---- 8 rows: two batches */                                                                                                      \
-        "30:\n\t"                                                                                                                     \
-        HNSW_B8_ISSUE_8                                                                                                               \
-        HNSW_B8_CONSUME_8
-#define HNSW_HOP_AFTER_INSERT HNSW_HOP_AFTER_INSERT_PLAIN
-#define HNSW_HOP_ROUNDS_RARE \
-        "25:\n\t"                                                                                                                     \
-  /* ---- 4 rows: one batch */                                                                                                        \
-        HNSW_B8_ISSUE_4                                                                                                               \
-        HNSW_B8_CONSUME_4                                                                                                             \
-        "s_branch 50b\n"                                                                                                              \
-  /* ---- 16 rows: four batches (a list of 9..12 re-reads its last row in the groups past the end) */                                 \
-        "40:\n\t"                                                                                                                     \
-        HNSW_B8_ISSUE_16                                                                                                              \
-        HNSW_B8_CONSUME_16                                                                                                            \
-        "s_branch 50b\n"
-#endif
 
 // ---- the rounds of byte rows of 129..256 dimensions (NCH = 4: four dwords per lane and row at +0, +64, +128, +192; batch b in
 // d[4b .. 4b+3], its sum in d[4b]): the text above with twice the loads and dot products per batch (derived from it mechanically)
@@ -1204,15 +1151,9 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
 // reproduces the four-slot text above instruction for instruction; a test compares them), together with everything else in
 // hnsw_hop_loop.inc that depends on the slot count (pop / peek chains, declarations, operand lists: HNSW_NSX_*_<N>)
 #include "hnsw_hop_slots.inc"
-#ifndef HNSW_ASM_ALIGN_PAD8
 #define HNSW_ASM_ALIGN_PAD8 6
-#endif
-#ifndef HNSW_ASM_ALIGN_PAD3
 #define HNSW_ASM_ALIGN_PAD3 6
-#endif
-#ifndef HNSW_ASM_ALIGN_PAD6
 #define HNSW_ASM_ALIGN_PAD6 6
-#endif
 
 
 // ---- one slot (ef <= 64): no cascade; the same steps as the two-slot loop's upper slot --------------------------------
@@ -1420,7 +1361,7 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
         "s_cmp_gt_u32 %[cnt], 8\n\t"                                                                                                  \
         "s_cbranch_scc1 40f\n\t"
 // The float32 rounds in two halves, ISSUE (ids -- and, split rows, slots -- from LDS, row addresses, the loads) and CONSUME (distances, the
-// folding reduction, keys, accept mask, cnt), as the byte-row rounds (HNSW_B8_ISSUE_* / HNSW_B8_CONSUME_*, HNSW_ASM_RPIPE): a hop of rows of
+// folding reduction, keys, accept mask, cnt), as the byte-row rounds (HNSW_B8_ISSUE_* / HNSW_B8_CONSUME_*, round pipelining): a hop of rows of
 // 65..128 dimensions with more than 16 fresh neighbours -- C5's and C3's graphs have rows of 64 -- issues its next round's loads before the
 // current round's insertions.  (The row registers are named and clobbered, the address pairs of the split rows too: nothing the insertions
 // use.)  Rows of 129..256 dimensions keep the unpipelined flow (their rounds are 4 and 8 rows: HNSW_F32_ROUND_PICK is empty there).
@@ -1522,19 +1463,16 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
   /* ---- 8 rows: two batches */                                                                                                      \
         "30:\n\t"                                                                                                                     \
         HNSW_F32_ISSUE_8                                                                                                              \
-        HNSW_F32_LABEL_31                                                                                                             \
+        "31:\n\t"                                                                                                                     \
         HNSW_F32_CONSUME_8
 
 #define HNSW_F32_ROUND_4ROWS \
         "25:\n\t"                                                                                                                     \
   /* ---- 4 rows: one batch */                                                                                                        \
         HNSW_F32_ISSUE_4                                                                                                              \
-        HNSW_F32_LABEL_26                                                                                                             \
+        "26:\n\t"                                                                                                                     \
         HNSW_F32_CONSUME_4                                                                                                            \
         "s_branch 50b\n"
-#if HNSW_ASM_RPIPE
-#define HNSW_F32_LABEL_31 "31:\n\t"
-#define HNSW_F32_LABEL_26 "26:\n\t"
 #define HNSW_F32_ROUND_16ROWS \
   /* ---- 16 rows: four batches (a list of 9..12 re-reads its last row in the groups past the end) */                                 \
         "40:\n\t"                                                                                                                     \
@@ -1559,16 +1497,6 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
         "47:\n\t"                                                                                                                     \
         HNSW_F32_ISSUE_4                                                                                                              \
         "s_branch 50b\n"
-#else
-#define HNSW_F32_LABEL_31
-#define HNSW_F32_LABEL_26
-#define HNSW_F32_ROUND_16ROWS \
-  /* ---- 16 rows: four batches (a list of 9..12 re-reads its last row in the groups past the end) */                                 \
-        "40:\n\t"                                                                                                                     \
-        HNSW_F32_ISSUE_16                                                                                                             \
-        HNSW_F32_CONSUME_16                                                                                                           \
-        "s_branch 50b\n"
-#endif
 #define HNSW_F32_ROUNDS_RARE HNSW_F32_ROUND_4ROWS HNSW_F32_ROUND_16ROWS
 
 
@@ -1577,7 +1505,7 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
 // including hnsw_hop_loop.inc with the HNSW_LOOP_* macros set.  The table is GENERATED (tools/gen_hop_slots.py ->
 // hnsw_hop_instances.inc): row families bytes (NCH 2) / bytes of 129..256 dimensions (NCH 4) / float32 full, ragged, split
 // (NCH 2 and 4) x metric x accept rule x W in 1, 2, 3, 4, 6, 8 registers x visited structure (bitmap blocks: three or more
-// registers, not the NCH 4 byte rows), under the feature switches at the top of this file, and in a translation unit of
+// registers, not the NCH 4 byte rows), and in a translation unit of
 // hnsw_search_variants.hip only the shapes of that unit's (metric, rule, row format).  search_layer asks
 // HopLoop<...>::available and calls run(); a shape without an instantiation (the primary template) keeps the C++ loop.
 // =====================================================================================================================

@@ -99,7 +99,7 @@
 #define HNSW_X_OUT
 #define HNSW_X_IN [setm] "s"(setm), [setb] "s"(setb), HNSW_LOOP_TSH_OPERAND
 #endif
-#if (HNSW_LOOP_NSLOT >= 3 || (HNSW_LOOP_NSLOT == 2 && HNSW_LOOP_ROWS != 2)) && HNSW_VT_THREE_WAYS && !HNSW_LOOP_BLK
+#if (HNSW_LOOP_NSLOT >= 3 || (HNSW_LOOP_NSLOT == 2 && HNSW_LOOP_ROWS != 2)) && !HNSW_LOOP_BLK
 #define HNSW_LOOP_VT3 1
 #define HNSW_LOOP_TSH_OPERAND [tsh] "s"(cx.tag_shift),
 #define HNSW_VT_WAYS_TEST HNSW_VT_RUNTIME_TEST
@@ -160,7 +160,7 @@
 #else
 #define HNSW_LOOP_ROUND_COMMON HNSW_HOP_ROUND_COMMON
 #define HNSW_LOOP_ROUNDS_RARE HNSW_HOP_ROUNDS_RARE
-#define HNSW_LOOP_AFTER_INSERT HNSW_HOP_AFTER_INSERT      /* (HNSW_ASM_RPIPE: a second round's loads run under the first round's insertions) */
+#define HNSW_LOOP_AFTER_INSERT HNSW_HOP_AFTER_INSERT      /* (round pipelining: a second round's loads run under the first round's insertions) */
 #endif
 #if HNSW_LOOP_METRIC == 0
 #define HNSW_B8_DOTS(DA, DB, TA) HNSW_DOTS(DA, DB, TA)
@@ -183,7 +183,7 @@
 #define HNSW_F32_VM1B "4"
 #define HNSW_FX_BS "16"
 #else
-#define HNSW_LOOP_AFTER_INSERT HNSW_HOP_AFTER_INSERT         /* (HNSW_ASM_RPIPE, as the byte rows) */
+#define HNSW_LOOP_AFTER_INSERT HNSW_HOP_AFTER_INSERT         /* (round pipelining, as the byte rows) */
 #define HNSW_LOOP_ROUNDS_RARE HNSW_F32_ROUNDS_RARE
 #define HNSW_F32_ROUND_PICK HNSW_F32_ROUND_PICK16
 #define HNSW_F32_VM1B "2"
@@ -362,14 +362,12 @@ template <> struct HopLoop<HNSW_LOOP_NCH, 2, HNSW_LOOP_METRIC, HNSW_LOOP_ROWS, H
         HNSW_HOP_ADJACENCY
         HNSW_HOP_FILTER_ISSUE
         HNSW_PROBE(1)
-#if HNSW_ASM_PREFETCH
         // the next nearest unexpanded member of W: its row is fetched now, beside this hop's vectors
         "s_cmp_eq_u64 %[um0], 0\n\t"
         "s_cbranch_scc1 7f\n\t"
         "s_ff1_i32_b64 %[i], %[um0]\n\t"
         "v_readlane_b32 %[pref], %[l0], %[i]\n"
         HNSW_HOP_PREFETCH_LOAD
-#endif
         HNSW_HOP_FILTER_COMPACT
         HNSW_PROBE(2)
         HNSW_LOOP_ROUND_COMMON
@@ -389,7 +387,6 @@ template <> struct HopLoop<HNSW_LOOP_NCH, 2, HNSW_LOOP_METRIC, HNSW_LOOP_ROWS, H
         "s_or_b32 %[t], %[kd], 0x80000000\n\t"
         "v_writelane_b32 %[l1], %[t], m0\n\t"
         "s_branch 3b\n"
-#if HNSW_ASM_PREFETCH
         "7:\n\t"                                                            // the next one is in the upper slot, or there is none
         "s_mov_b32 %[pref], -1\n\t"
         "s_cmp_eq_u64 %[um1], 0\n\t"
@@ -397,7 +394,6 @@ template <> struct HopLoop<HNSW_LOOP_NCH, 2, HNSW_LOOP_METRIC, HNSW_LOOP_ROWS, H
         "s_ff1_i32_b64 %[i], %[um1]\n\t"
         "v_readlane_b32 %[pref], %[l1], %[i]\n\t"
         "s_branch 8b\n"
-#endif
         HNSW_HOP_ADJACENCY_MISS
         HNSW_LOOP_ROUNDS_RARE
         HNSW_INSERT_RARE
@@ -581,11 +577,9 @@ template <> struct HopLoop<HNSW_LOOP_NCH, HNSW_LOOP_NSLOT, HNSW_LOOP_METRIC, HNS
         HNSW_X_ADJACENCY
         HNSW_X_FILTER_ISSUE
         HNSW_PROBE(1)
-#if HNSW_ASM_PREFETCH
         "s_mov_b32 %[pref], -1\n\t"
         HNSW_PEEK_SLOT0("%[um0]", "%[l0]", "71f")
         HNSW_X_PREFETCH_LOAD
-#endif
         HNSW_X_FILTER_COMPACT
         HNSW_PROBE(2)
         HNSW_LOOP_ROUND_COMMON
@@ -596,9 +590,7 @@ template <> struct HopLoop<HNSW_LOOP_NCH, HNSW_LOOP_NSLOT, HNSW_LOOP_METRIC, HNS
         HNSW_LOOP_AFTER_INSERT
         // ---- behind the loop
         HNSW_NS(POP_CHAIN)
-#if HNSW_ASM_PREFETCH
         HNSW_NS(PEEK_CHAIN)
-#endif
         HNSW_X_ADJACENCY_MISS
         HNSW_LOOP_ROUNDS_RARE
         HNSW_NS(INSERT_RARE)
@@ -771,11 +763,9 @@ template <> struct HopLoop<HNSW_LOOP_NCH, 1, HNSW_LOOP_METRIC, HNSW_LOOP_ROWS, H
         "3:\n"                                                          // kd = the node's low key half, id + 1
         HNSW_HOP_ADJACENCY
         HNSW_HOP_FILTER_ISSUE
-#if HNSW_ASM_PREFETCH
         "s_mov_b32 %[pref], -1\n\t"
         HNSW_PEEK_SLOT0("%[um0]", "%[l0]", "9f")
         HNSW_HOP_PREFETCH_LOAD
-#endif
         HNSW_HOP_FILTER_COMPACT
         HNSW_LOOP_ROUND_COMMON
         "50:\n\t"

@@ -11,12 +11,10 @@
 #include <string>
 #include <vector>
 
-// 4-row batches in flight per wave for d <= 128 (NCH = 2): measured on C2: 4 (6 waves/SIMD) >= 3 (7) >= 2 (8): the batch is memory-bound, not occupancy-bound
-#ifndef HNSW_RB_NCH2
-#define HNSW_RB_NCH2 4
-#endif
-
 namespace hnsw_host {
+
+// 4-row batches in flight per wave for d <= 128 (NCH = 2): measured on C2: 4 (6 waves/SIMD) >= 3 (7) >= 2 (8): the batch is memory-bound, not occupancy-bound
+constexpr int RB_NCH2 = 4;
 
 int fail(int code, const char *fmt, ...);
 // the code and message of a failed HIP call
@@ -121,8 +119,7 @@ inline int pick_nslot(int ef) {
 // (ef 129..192) and six (ef 257..384) registers -- a W window that needs three registers pays for three (pop chain, flag masks,
 // registers), not for four; the other row widths, the builder and the layer operators keep powers of two (pick_nslot)
 inline int pick_nslot_knn(int ef, int nch) {
-    static const int pow2 = env_int("HNSW_NSLOT_POW2", 0);      // (A/B: W in powers of two only, as rounds 1-5: profiles/r06_hop_phases.txt)
-    if (!pow2 && (nch == 2 || nch == 4)) { for (int s : {1, 2, 3, 4, 6, 8, 16}) if (ef <= 64 * s) return s; return 0; }
+    if (nch == 2 || nch == 4) { for (int s : {1, 2, 3, 4, 6, 8, 16}) if (ef <= 64 * s) return s; return 0; }
     return pick_nslot(ef);
 }
 // index of a slot count in per-shape tables (hnsw_index::blk_choice)
@@ -179,7 +176,6 @@ struct hnsw_index {
     int live_requests = 0, next_stream = 0;
     int64_t resident_queries = 0;        // how many one-wave workgroups of the search kernel the chip holds (0 = not measured yet)
     int resident_per_cu = 0, cus = 0;    // ... per CU, and the CUs
-    int64_t debug_last_nq = -1;          // HNSW_DEBUG_RESIDENT prints balanced_lds_pad's choice once per batch size
     int resident_nslot = 0; size_t resident_lds = 0;   // ... for this kernel variant / LDS size
     bool time_kernels = false;           // option "time_kernels": event triples around the launches of each device-entry call
     std::vector<hipEvent_t> tev;         // [3 * recorded calls]: before the pre-pass, before the search kernel, after it
@@ -275,7 +271,7 @@ hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uin
 
 // log2 entries of the per-query LDS visited cache (never changes results)
 inline int search_vt_bits(const hnsw_index *idx, int ef) {
-    int b = idx->vt_bits_override ? idx->vt_bits_override : env_int("HNSW_VT_BITS", 0);
+    int b = idx->vt_bits_override;
     if (b <= 0) {
         // Re-encounters of a node come soon after its first evaluation, so the cache need not
         // grow with ef: 2^11 tags (4 KiB, 32 waves/CU) cost 3.5 % re-evaluations on C2 and 2.6 %

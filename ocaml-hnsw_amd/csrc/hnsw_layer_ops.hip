@@ -152,7 +152,7 @@ template <int METRIC>
 hipError_t layer_nch(int nch, int nslot, const IndexView &iv, const LayerSearchArgs &a) {
     switch (nch) {
     case 1: return layer_slot<1, 8, METRIC>(nslot, iv, a);
-    case 2: return layer_slot<2, HNSW_RB_NCH2, METRIC>(nslot, iv, a);
+    case 2: return layer_slot<2, RB_NCH2, METRIC>(nslot, iv, a);
     case 4: return layer_slot<4, 2, METRIC>(nslot, iv, a);
     case 8: return layer_slot<8, 1, METRIC>(nslot, iv, a);
     default: return layer_slot<16, 1, METRIC>(nslot, iv, a);
@@ -172,7 +172,7 @@ hipError_t one_nch(int nch, const IndexView &iv, const float *Q, int64_t qs, int
     dim3 grid((unsigned)nq), block(64);
     switch (nch) {
     case 1: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<1, 8, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<2, HNSW_RB_NCH2, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
+    case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<2, RB_NCH2, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
     case 4: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<4, 2, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
     case 8: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<8, 1, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
     default: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<16, 1, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;

@@ -56,7 +56,7 @@ static int build_codes(::hnsw_index *idx) {
     HIP_TRY(hipSetDevice(idx->device));
     HIP_TRY(hipDeviceSynchronize());
     const int lo = std::min(2, T);
-    const int ef_b = std::max(1, std::min(64, env_int("HNSW_LCODE_EF", 32)));
+    const int ef_b = 32;
     const int id_base = idx->iv.id_base;
     DevBuf entry, scratch, best, bdist, qmap;
     struct Guard { DevBuf &a, &b, &c, &d, &e; ~Guard() { a.release(); b.release(); c.release(); d.release(); e.release(); } } guard{entry, scratch, best, bdist, qmap};

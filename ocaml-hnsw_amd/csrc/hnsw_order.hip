@@ -89,7 +89,7 @@ hipError_t launch_descent_rows(int nch, const IndexView &iv, const float *Q, int
     constexpr bool B = ROWS == 2 || ROWS == 4;   // byte / half rows: a quarter / half of the registers per row in flight
     switch (nch) {
     case 1: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<1, 8, METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<2, (B ? 8 : HNSW_RB_NCH2), METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
+    case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<2, (B ? 8 : RB_NCH2), METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
     case 4: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<4, (B ? 4 : 2), METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
     case 8: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<8, (B ? 2 : 1), METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
     default: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<16, 1, METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
@@ -130,11 +130,11 @@ int descent_entries(::hnsw_index *idx, const float *d_queries, int64_t nq, int64
 int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride, float *d_stage, hipStream_t st,
                         void **block, const int32_t **qmap, const int32_t **pre_entry, const uint32_t **pre_key,
                         const uint32_t **pre_nd, int32_t *pre_layer) {
-    // The pre-pass may stop above layer 1 and leave the rest of the descent to the search kernel: on C2
-    // stopping at layer 2 costs 58 instead of 78 us and orders almost as well (0.827 against 0.835 ms
-    // per step), stopping at layer 3 orders badly (0.885 ms).  Default: the whole descent, so that
-    // the two kernels' shares of the work are the descent and the layer-0 walk.
-    const int32_t to_layer = std::max(1, std::min(idx->iv.max_layer, env_int("HNSW_ORDER_STOP_LAYER", 1)));
+    // The pre-pass runs the whole descent, down to layer 1, so that the two kernels' shares of the work are the descent and
+    // the layer-0 walk.  Stopping higher and leaving the rest of the descent to the search kernel, measured on C2: stopping at
+    // layer 2 costs 58 instead of 78 us and orders almost as well (0.827 against 0.835 ms per step), stopping at layer 3
+    // orders badly (0.885 ms).
+    const int32_t to_layer = 1;
     *pre_layer = to_layer;
     *block = nullptr;
     const size_t n = (size_t)nq, slot = (n * 4 + 255) & ~(size_t)255;
@@ -166,7 +166,7 @@ int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, i
     e = idx->info.metric == HNSW_METRIC_L2 ? launch_descent<0>(idx->info.row_format, nch, idx->iv, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st)
                                            : launch_descent<1>(idx->info.row_format, nch, idx->iv, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st);
     if (e == hipSuccess) {
-        if (nq <= 16 * ORDER_THREADS && !env_int("HNSW_ORDER_FULL_SORT", 0)) {
+        if (nq <= 16 * ORDER_THREADS) {
             static_assert(ORDER_BUCKETS == 2 * ORDER_THREADS, "two counters per thread in the scan");
             hipLaunchKernelGGL(order_bucket_kernel<16>, dim3(1), dim3(ORDER_THREADS), 0, st, (const uint32_t *)sortkey, (int32_t)nq, order);
             e = hipGetLastError();

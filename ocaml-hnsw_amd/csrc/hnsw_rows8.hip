@@ -48,7 +48,6 @@ namespace hnsw_host {
 
 int make_byte_rows(::hnsw_index *idx) {
     if (!idx || !idx->tables.X.p || idx->iv.n <= 0) return HNSW_OK;
-    if (!env_int("HNSW_BYTE_ROWS", 1)) return HNSW_OK;
     HIP_TRY(hipSetDevice(idx->device));
     const int64_t n = idx->iv.n;
     const int32_t d = idx->iv.d;
@@ -67,7 +66,6 @@ int make_byte_rows(::hnsw_index *idx) {
     if (e == hipSuccess) e = hipMemcpy(&ok, dflag, 4, hipMemcpyDeviceToHost);
     (void)hipFree(dflag);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "byte-row check failed: %s", hipGetErrorString(e));
-    if (env_int("HNSW_DEBUG_ROWS", 0)) fprintf(stderr, "hnsw: byte-row check n=%lld d=%d stride=%lld -> %d\n", (long long)n, d, (long long)idx->iv.stride, ok);
     if (!ok) return HNSW_OK;
     Table &X8 = idx->tables.X8;
     if (X8.alloc((size_t)n * (size_t)row_bytes) != hipSuccess) return HNSW_OK;     // no room for the copy: not an error, the fp32 rows serve

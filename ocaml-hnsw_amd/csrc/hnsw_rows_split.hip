@@ -52,7 +52,6 @@ int make_split_rows(::hnsw_index *idx) {
     if (!idx || !idx->tables.X.p || !idx->tables.nbr0.p || idx->iv.n <= 0) return HNSW_OK;
     IndexTables &t = idx->tables;
     if (t.X8.p) return HNSW_OK;                          // byte rows are a single line per vector already
-    if (!env_int("HNSW_SPLIT_ROWS", 1)) return HNSW_OK;
     const int nchunks = idx->iv.nchunks;
     const int T = nchunks % 8;                           // float4 chunks past the last whole 128-byte line
     if ((T != 1 && T != 2) || nchunks < 9) return HNSW_OK;

@@ -19,12 +19,10 @@ namespace {
 constexpr int M_ = HNSW_V_METRIC, S_ = HNSW_V_SEMF;
 constexpr int F_ = HNSW_V_FULL;
 // 4-row batches in flight per wave: a byte row is a quarter of the registers; a half row (F_ 4) half of them, and it takes
-// the byte rows' counts (twice the rows in flight of fp32 rows for the same registers: not measured against other counts)
-#ifndef HNSW_RB_BYTES_NCH2
-#define HNSW_RB_BYTES_NCH2 4
-#endif
+// the byte rows' counts (twice the rows in flight of fp32 rows for the same registers: not measured against other counts);
+// for d <= 128 (NCH = 2) every row format takes RB_NCH2
 constexpr bool COMPACT_ = F_ == 2 || F_ == 4;
-constexpr int RB1 = 8, RB2 = COMPACT_ ? HNSW_RB_BYTES_NCH2 : HNSW_RB_NCH2, RB4 = COMPACT_ ? 4 : 2, RB8 = COMPACT_ ? 2 : 1, RB16 = 1;
+constexpr int RB1 = 8, RB2 = hnsw_host::RB_NCH2, RB4 = COMPACT_ ? 4 : 2, RB8 = COMPACT_ ? 2 : 1, RB16 = 1;
 
 template <int NCH, int RB, int NSLOT>
 hipError_t launch_one(const IndexView &iv, const SearchArgs &a, hipStream_t st) {

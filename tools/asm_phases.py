@@ -16,4 +16,4 @@ for nq in (64, 10000):
         H.search_batch_device(hg, Qd.data_ptr(), nq, d, ef, k, ids.data_ptr(), dist.data_ptr(), nd.data_ptr(), nh.data_ptr(), 0, 0)
         torch.cuda.synchronize()
     c = nd.cpu().numpy().astype(np.uint32).astype(np.float64); h = nh.cpu().numpy().astype(np.float64)
-    print("ef %d%s%s phase %s (%s), nq=%d: %.0f cycles per query (median), %.0f per hop, %.1f hops" % (ef, " hard set" if kw else "", " W in powers of two" if os.environ.get("HNSW_NSLOT_POW2") else "", os.environ.get("PHASE"), names[int(os.environ.get("PHASE", 0))], nq, np.median(c), np.median(c / h), np.median(h)), flush=True)
+    print("ef %d%s phase %s (%s), nq=%d: %.0f cycles per query (median), %.0f per hop, %.1f hops" % (ef, " hard set" if kw else "", os.environ.get("PHASE"), names[int(os.environ.get("PHASE", 0))], nq, np.median(c), np.median(c / h), np.median(h)), flush=True)

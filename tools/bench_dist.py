@@ -11,7 +11,7 @@ import ocaml_hnsw_amd as H
 dev = torch.device("cuda", 0)
 L = H.load()
 SHAPES = ((784, 1_000_000), (128, 4_000_000), (100, 4_000_000), (96, 4_000_000))
-if os.environ.get("DIST_ONLY"):          # one shape only (tools/dist_ab.sh, profiling)
+if os.environ.get("DIST_ONLY"):          # one shape only (profiling)
     SHAPES = tuple(s_ for s_ in SHAPES if s_[0] == int(os.environ["DIST_ONLY"]))
 for d, n in SHAPES:
     g = torch.Generator(device=dev); g.manual_seed(d)

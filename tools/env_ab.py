@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of environment knobs the library reads per call, on C2's shape: host call and device-resident call, eight rotating batches.  (GPU box)
 
-    SETTINGS="HNSW_ORDER_STOP_LAYER=2;HNSW_ORDER_STOP_LAYER=3" python tools/env_ab.py
+    SETTINGS="HNSW_PRIO=0,0;HNSW_PRIO=1024,8192" python tools/env_ab.py
 Each setting is an &-separated list of NAME=VALUE (values may hold commas: HNSW_PRIO=1024,8192); the plain library is measured first and last."""
 import os
 import sys

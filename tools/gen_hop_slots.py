@@ -11,10 +11,10 @@
                           hnsw_hop_loop.inc has ONE body for all of them (HNSW_NS(...) picks the set of HNSW_LOOP_NSLOT); the
                           four-slot insertion stays the hand-written, commented text and the generator must reproduce it.
   hnsw_hop_instances.inc  the table of instantiations: one `#define HNSW_LOOP_* ... #include "hnsw_hop_loop.inc"` stanza per
-                          (row family, metric, accept rule, slot count, visited structure), each under the feature switches of
-                          hnsw_hop_asm.hip.h and -- in the translation units of hnsw_search_variants.hip, which are compiled per
-                          (metric, rule, row format) -- only where the unit can reach it (rounds 2-5 wrote 184 stanzas by hand and
-                          every unit parsed all of them).
+                          (row family, metric, accept rule, slot count, visited structure), grouped under one `#if` per
+                          translation unit of hnsw_search_variants.hip -- compiled per (metric, rule, row format) -- so that a unit
+                          parses only the stanzas it can reach (rounds 2-5 wrote 184 stanzas by hand and every unit parsed all of
+                          them).
 
     python tools/gen_hop_slots.py            # rewrite both files
     python tools/gen_hop_slots.py --check    # exit 1 if a committed file differs from what this script writes
@@ -212,18 +212,18 @@ def slots_text():
 
 
 # ---- the instantiation table ----------------------------------------------------------------------------------------------
-# row families: (name, NCH, ROWS values, feature guard)
-FAMILIES = (("bytes", 2, (2,), "1"),
-            ("bytes4", 4, (2,), "HNSW_ASM_LOOP_BYTES4"),
-            ("f32", 2, (1, 0, 3), "HNSW_ASM_LOOP_F32"),
-            ("f32n4", 4, (1, 0, 3), "HNSW_ASM_LOOP_F32 && HNSW_ASM_LOOP_F32N4"))
+# row families: (name, NCH, ROWS values)
+FAMILIES = (("bytes", 2, (2,)),
+            ("bytes4", 4, (2,)),
+            ("f32", 2, (1, 0, 3)),
+            ("f32n4", 4, (1, 0, 3)))
 NSLOTS = (1, 2, 3, 4, 6, 8)
 
 
 def instances():
-    """(nch, rows, metric, sem, nslot, blk, guard) of every instantiation"""
+    """(nch, rows, metric, sem, nslot, blk) of every instantiation"""
     out = []
-    for fam, nch, rows_list, fguard in FAMILIES:
+    for fam, nch, rows_list in FAMILIES:
         for rows in rows_list:
             for metric in (0, 1):
                 for sem in (0, 1):
@@ -231,25 +231,17 @@ def instances():
                         for blk in (0, 1):
                             if blk and (nslot < 3 or fam == "bytes4"):
                                 continue            # bitmap blocks: W in three or more registers; not for byte rows of 129..256 dimensions
-                            g = [fguard]
-                            if rows == 3:
-                                g.append("HNSW_ASM_LOOP_SPLIT")
-                            if sem:
-                                g.append("HNSW_ASM_LOOP_SEM1")
-                            if nslot > 4:
-                                g.append("HNSW_ASM_LOOP_8SLOTS")
-                            g = [x for x in g if x != "1"]
-                            out.append((nch, rows, metric, sem, nslot, blk, " && ".join(g) if g else "1"))
+                            out.append((nch, rows, metric, sem, nslot, blk))
     return out
 
 
 def instances_text():
     L = ['// hnsw_hop_instances.inc -- GENERATED by tools/gen_hop_slots.py (do not edit; `python tools/gen_hop_slots.py` rewrites it,',
          '// tests/test_asm_hazards.py checks that it is current): the instantiations HopLoop<NCH, NSLOT, METRIC, ROWS, SEM, BLK> of the',
-         '// hand-scheduled layer-0 loop, one stanza each.  A stanza is compiled when the feature switches of hnsw_hop_asm.hip.h allow it',
-         '// and the translation unit can reach it: the units of hnsw_search_variants.hip are compiled per (metric, accept rule, row',
-         '// format) and define HNSW_V_METRIC / HNSW_V_SEMF / HNSW_V_FULL; every other unit (the builder, the layer operators: row format',
-         '// decided at run time) takes search_layer\'s C++ loop and instantiates nothing.',
+         '// hand-scheduled layer-0 loop, one stanza each, grouped by the translation unit that can reach them: the units of',
+         '// hnsw_search_variants.hip are compiled per (metric, accept rule, row format) and define HNSW_V_METRIC / HNSW_V_SEMF /',
+         '// HNSW_V_FULL; every other unit (the builder, the layer operators: row format decided at run time) takes search_layer\'s',
+         '// C++ loop and instantiates nothing.',
          '#if defined(HNSW_HOP_ALL_INSTANCES)      /* (tests: every instantiation in one preprocessed unit) */',
          '#define HNSW_HOP_UNIT(M, S, R) 1',
          '#elif defined(HNSW_V_METRIC)',
@@ -257,16 +249,19 @@ def instances_text():
          '#else',
          '#define HNSW_HOP_UNIT(M, S, R) 0',
          '#endif']
-    for nch, rows, metric, sem, nslot, blk, guard in instances():
-        cond = 'HNSW_HOP_UNIT(%d, %d, %d)' % (metric, sem, rows) + ('' if guard == '1' else ' && ' + guard)
-        L.append('#if %s' % cond)
-        L.append('#define HNSW_LOOP_NCH %d' % nch)
-        L.append('#define HNSW_LOOP_NSLOT %d' % nslot)
-        L.append('#define HNSW_LOOP_ROWS %d' % rows)
-        L.append('#define HNSW_LOOP_METRIC %d' % metric)
-        L.append('#define HNSW_LOOP_SEM %d' % sem)
-        L.append('#define HNSW_LOOP_BLK %d' % blk)
-        L.append('#include "hnsw_hop_loop.inc"')
+    units = {}                  # (metric, rule, row format) -> its stanzas, in table order (the order the unit compiles them in)
+    for inst in instances():
+        units.setdefault((inst[2], inst[3], inst[1]), []).append(inst)
+    for unit, insts in units.items():
+        L.append('#if HNSW_HOP_UNIT(%d, %d, %d)' % unit)
+        for nch, rows, metric, sem, nslot, blk in insts:
+            L.append('#define HNSW_LOOP_NCH %d' % nch)
+            L.append('#define HNSW_LOOP_NSLOT %d' % nslot)
+            L.append('#define HNSW_LOOP_ROWS %d' % rows)
+            L.append('#define HNSW_LOOP_METRIC %d' % metric)
+            L.append('#define HNSW_LOOP_SEM %d' % sem)
+            L.append('#define HNSW_LOOP_BLK %d' % blk)
+            L.append('#include "hnsw_hop_loop.inc"')
         L.append('#endif')
     L.append('#undef HNSW_HOP_UNIT')
     return '\n'.join(L) + '\n'

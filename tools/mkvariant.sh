@@ -1,7 +1,7 @@
 #!/bin/bash
 # Experiment build: exp/<name>.so = the in-tree objects with the headline kernel's translation units
 # (hnsw_search_variants 0_0_2 / 0_0_1 and hnsw_order.hip) recompiled with extra flags.
-# usage: tools/mkvariant.sh <name> [-DHNSW_...=...]...
+# usage: tools/mkvariant.sh <name> [-DHNSW_...=...]...   (measurement builds: -DHNSW_ASM_PHASE=k, -DHNSW_ASM_STATS, ...)
 set -e
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
