@@ -29,6 +29,7 @@
  *                            Hnsw_algo.SelectNeighbours.select_neighbours (lib/hnsw_algo.ml:572-609)
  *   hnsw_build               Ohnsw.build_batch_bigarray (lib/ohnsw.ml:840-857), batched on the device
  *   hnsw_index_insert        Ohnsw.insert (lib/ohnsw.ml:766-837) of m vectors into an index the library holds
+ *   hnsw_brute_force_batch   brute_force_knn_l2 (benchmark/dataset.ml:15-30): the exact scan recall is measured against
  *   hnsw_host_alloc / hnsw_host_register   (nothing in the reference) page-locked query / result matrices,
  *                            which the entry points above read and write from the device in place
  *
@@ -191,6 +192,7 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   on the caller's stream (read back with hnsw_index_kernel_times);
  *   "lds_pad"       LDS bytes a search workgroup asks for beyond its own (how many queries a CU holds
  *                   at once in a batch larger than the device holds): -1 = automatic (default);
+ *   "scan_slabs"    into how many row slabs hnsw_brute_force_batch cuts the table (1..1024; 0 = automatic, the default);
  *   "byte_rows"     when every value of the vectors is an integer in 0..255 (SIFT descriptors stored as
  *                   float32) the index keeps a second, lossless copy of the rows as bytes and the knn
  *                   searches read that one: each byte is converted back to the float it came from and
@@ -341,6 +343,31 @@ int32_t hnsw_distance_batch(hnsw_index *idx, const float *queries, int64_t nq, i
 int32_t hnsw_distance_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq,
                                    int64_t q_stride, const int32_t *d_ids, int32_t m,
                                    float *d_out, void *stream);
+
+/* brute_force_knn_l2 (benchmark/dataset.ml:15-30) over the vectors the index holds, with the index's metric: the exact ("flat")
+ * search, what recall is measured against (Dataset.random, benchmark/dataset.ml:47-58; Recall.compute, :105-127).
+ *   - Result: for each query the k smallest of ALL n stored vectors under the total order (distance, node id), ascending, in
+ *     out_ids [nq][k] (id_base-based) and out_dist [nq][k].  Among equal distances the lowest ids win and come first.  The
+ *     distances are the bits hnsw_distance_batch and the knn searches give for the same pair (same lanes, fmaf order and tree).
+ *   - Rows: always the float32 vectors, whatever hnsw_index_info.row_format says: the scan is the ground truth for X, so the
+ *     options "half_rows", "byte_rows" and "split_rows" do not change it.
+ *   - Graph: none is needed.  An index whose nodes have no edges (deg0 all zero) is scanned like any other; n = 0 gives HNSW_OK
+ *     with every entry filled (not HNSW_ERR_EMPTY_INDEX: nothing is walked); k > n: the first n entries are real, the rest filled.
+ *     fill: HNSW_FILL_OHNSW = id -1 and distance NaN, HNSW_FILL_BA = id -1 and +inf.
+ *   - Limits: k in 1..1024; k < 1 and an unknown fill are HNSW_ERR_BAD_ARG, k > 1024 is HNSW_ERR_UNSUPPORTED.  nq, q_stride and
+ *     null pointers as hnsw_search_batch (nq == 0 is a no-op).  NaN in the data or in a query: no promise.
+ *   - Determinism: the result does not depend on the batch size, on which queries share a call, or on how the table is cut
+ *     into slabs (option "scan_slabs"): no candidate is ever dropped, a full survivor buffer is merged and the scan goes on.
+ *   - Host form: as hnsw_search_batch, matrices of hnsw_host_alloc / hnsw_host_register are read and written in place, others are
+ *     copied; complete on return.  Device form: asynchronous on `stream`; ONE such call in flight per handle (calls on one
+ *     stream are ordered and therefore fine).
+ *   - Scratch: the per-slab candidate lists (at most 256 MiB; larger batches are scanned in pieces) belong to the handle, are sized
+ *     on demand and reused, and -- like the other scratch of the host-buffer calls -- are NOT counted in device_bytes.
+ *   - After hnsw_index_insert the scan covers the grown table.  A replica borrowed from an hnsw_multi may be scanned. */
+int32_t hnsw_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
+                               int32_t k, int32_t fill, int32_t *out_ids, float *out_dist);
+int32_t hnsw_brute_force_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
+                                      int32_t k, int32_t fill, int32_t *d_ids, float *d_dist, void *stream);
 
 /* ---- the layer-level functions of the path, as batched operators -------------------------------
  * hnsw_search_layer_batch = Ohnsw.search_k (lib/ohnsw.ml:543-588; params->semantics = OHNSW) or

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "hnsw_multi_create", "hnsw_multi_destroy", "hnsw_multi_num_replicas", "hnsw_multi_replica", "hnsw_multi_search_batch",
     "hnsw_multi_search_batch_device", "hnsw_multi_copy_result", "hnsw_multi_debug_counters",
     "hnsw_host_register", "hnsw_host_unregister", "hnsw_host_alloc", "hnsw_host_free",
+    "hnsw_brute_force_batch", "hnsw_brute_force_batch_device",
 ]
 
 
@@ -119,6 +120,9 @@ def load():
     L.hnsw_knn.argtypes = [vp, vp, vp, vp, vp, vp]
     L.hnsw_distance_batch.argtypes = [vp, vp, i64, i64, vp, i32, vp]
     L.hnsw_distance_batch_device.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp]
+    L.hnsw_brute_force_batch.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp]
+    L.hnsw_brute_force_batch_device.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp, vp]
+    L.hnsw_brute_force_batch.restype = L.hnsw_brute_force_batch_device.restype = i32
     L.hnsw_build.argtypes = [vp, i64, i32, i64, vp, i32, vp]
     L.hnsw_index_insert.argtypes = [vp, vp, i64, i64, vp]
     L.hnsw_select_neighbours_batch.argtypes = [vp, vp, i64, i64, vp, vp, i32, i32, i32, vp, vp, vp]
@@ -357,6 +361,17 @@ class Hgraph:
         self.deg0 = self.nbr0 = self.upper = None
         return self
 
+    @classmethod
+    def flat(cls, vectors, metric=METRIC_L2, id_base=0):
+        """An edgeless graph over the vectors (zero degrees, row width 1, entry point the first node): for callers who only
+        want the exact scan (Ohnsw.brute_force_knn)."""
+        X, _ = _rows(vectors)
+        if X.ndim != 2:
+            raise InvalidArgument("vectors must be [n][d]")
+        n = X.shape[0]
+        return cls(vectors, _np.zeros(n, _np.int32), _np.full((n, 1), -1, _np.int32), entry_point=id_base if n else None,
+                   id_base=id_base, max_degree=1, metric=metric)
+
     def _desc(self):
         """(hnsw_index_desc, keep-alive) of the host copy of the flattened graph."""
         if self.vectors is None or self.deg0 is None:
@@ -539,6 +554,11 @@ def search_batch_device(hgraph, d_queries, nq, q_stride, ef, k, d_ids, d_dist, d
                                            d_status or None, stream or None))
 
 
+def brute_force_device(hgraph, d_queries, nq, q_stride, k, d_ids, d_dist, fill=FILL_OHNSW, stream=0):
+    """hnsw_brute_force_batch_device: the exact scan on device pointers (ints), asynchronous on HIP stream `stream`."""
+    _check(load().hnsw_brute_force_batch_device(hgraph.handle, d_queries, nq, q_stride, k, fill, d_ids, d_dist, stream or None))
+
+
 def search_batch_h2d(hgraph, batch, ef, k, d_ids, d_dist, d_ndist=0, d_nhops=0, d_status=0, stream=0,
                      fill=FILL_OHNSW, sem=SEM_OHNSW):
     """hnsw_search_batch_h2d: queries from a HOST matrix (read by the device directly when it was registered with pin()),
@@ -569,6 +589,27 @@ class Ohnsw:
         ids [nq][k] (-1 where fewer than k were found), distances [nq][k] fp32 (NaN there).
         out = (ids, distances): write into the caller's matrices instead of fresh ones."""
         return _search(hgraph, batch, k if ef is None else ef, k, FILL_OHNSW, counters, out=out)
+
+    @staticmethod
+    def brute_force_knn(hgraph, k, batch, fill=FILL_OHNSW, out=None):
+        """brute_force_knn_l2 (benchmark/dataset.ml:15-30) over the vectors the index holds, with its metric
+        (hnsw_brute_force_batch) -> (ids, distances): for each query the k smallest of all n vectors under (distance, id),
+        ascending; ids [nq][k] (-1 where k > n), distances [nq][k] fp32 (NaN there; FILL_BA: +inf).  Needs no graph.
+        out = (ids, distances): write into the caller's matrices instead of fresh ones."""
+        Q, qs = _rows(batch)
+        if Q.ndim != 2 or (Q.shape[0] and Q.shape[1] != hgraph.d):
+            raise InvalidArgument("batch must be [nq][d]")
+        nq, k = Q.shape[0], int(k)
+        if out is not None:
+            ids, dist = out
+            if ids.shape != (nq, k) or dist.shape != (nq, k) or ids.dtype != _np.int32 or dist.dtype != _np.float32 \
+                    or not ids.flags["C_CONTIGUOUS"] or not dist.flags["C_CONTIGUOUS"]:
+                raise InvalidArgument("out must be (int32 [nq][k], float32 [nq][k]), C-contiguous")
+        else:
+            ids = _np.empty((nq, max(k, 0)), _np.int32)
+            dist = _np.empty((nq, max(k, 0)), _np.float32)
+        _check(load().hnsw_brute_force_batch(hgraph.handle, _ptr(Q), nq, max(qs, hgraph.d), k, fill, _ptr(ids), _ptr(dist)))
+        return ids, dist
 
     @staticmethod
     def search_k(hgraph, layer, start_nodes, targets, k, ef=None, sem=SEM_OHNSW, counters=False):

@@ -912,6 +912,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         return HNSW_OK;
     }
     if (!strcmp(name, "order_queries")) { idx->order_mode = value < 0 ? -1 : (value ? 1 : 0); return HNSW_OK; }
+    if (!strcmp(name, "scan_slabs")) { idx->scan_slabs = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1024)); return HNSW_OK; }
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }
 

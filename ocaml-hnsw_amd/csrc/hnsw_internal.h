@@ -84,9 +84,10 @@ struct KnnBatch {
 inline size_t query_bytes(int64_t nq, int64_t q_stride, int d) { return ((size_t)(nq - 1) * q_stride + d) * sizeof(float); }
 
 // the device buffers of one batch of nq queries: the queries (qbytes), k ids and distances per query, the per-query counters
-// and status words, and the launch's "any query flagged" word
+// and status words, and the launch's "any query flagged" word; scan: the per-slab lists of the exact scan (hnsw_scan.hip), sized
+// by that call
 struct BatchBufs {
-    DevBuf q, ids, dist, nd, nh, st, flag;
+    DevBuf q, ids, dist, nd, nh, st, flag, scan;
     // these buffers as a batch of nq queries whose results go to rows row0.. of ids / dist (a multi shard's slice of the table)
     KnnBatch batch(int64_t nq, int64_t q_stride, int k, int64_t row0 = 0) const {
         return {(const float *)q.p, nq, q_stride, (int32_t *)ids.p + row0 * k, (float *)dist.p + row0 * k,
@@ -99,7 +100,7 @@ struct BatchBufs {
             return rc;
         return HNSW_OK;
     }
-    void release() { for (DevBuf *b : {&q, &ids, &dist, &nd, &nh, &st, &flag}) b->release(); }
+    void release() { for (DevBuf *b : {&q, &ids, &dist, &nd, &nh, &st, &flag, &scan}) b->release(); }
 };
 
 inline int env_int(const char *name, int dflt) {
@@ -189,6 +190,7 @@ struct hnsw_index {
     int vt_bits_override = 0;
     int vt_grow_key = -1, vt_grow_bits = 0;   // knn_vt_bits' cached choice for (kernel variant, base size)
     int lds_pad = -1;                    // option "lds_pad": extra LDS bytes per search wave (-1 = balanced_lds_pad's choice)
+    int scan_slabs = 0;                  // option "scan_slabs": row slabs of the exact scan (0 = scan_slab_rows' choice)
     std::vector<std::pair<int, int>> prepared;   // (ef, accept rule) of every hnsw_index_prepare: what hnsw_index_save writes down
     // what the options "byte_rows" / "split_rows" asked for (bind_view leaves an unused copy out of the view), so that
     // hnsw_index_insert, which makes the row copies again, keeps their effect: byte_rows 0, split_rows 0 (off), split_rows -1
@@ -268,6 +270,10 @@ int knn_search(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b
 int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st);
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
 hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st);
+// hnsw_capi.hip: the handle's stream (hs[0]) and flag word of the host-buffer calls, made on first use
+int ensure_host_call_state(::hnsw_index *idx);
+// hnsw_capi.hip: the device address of [p, p + bytes) if it lies in a range of hnsw_host_alloc / hnsw_host_register, else null
+void *registered_device_address(const void *p, size_t bytes);
 
 // log2 entries of the per-query LDS visited cache (never changes results)
 inline int search_vt_bits(const hnsw_index *idx, int ef) {

@@ -51,11 +51,11 @@ class Dataset:
         self.distance = distance
 
     @classmethod
-    def random(cls, dim, num_train, num_test, k, seed=0):
+    def random(cls, dim, num_train, num_test, k, seed=0, device=None):
         rng = np.random.default_rng(seed)
         train = rng.uniform(-1, 1, size=(num_train, dim)).astype(np.float32)
         test = rng.uniform(-1, 1, size=(num_test, dim)).astype(np.float32)
-        return cls(train, test, brute_force_knn_l2(train, test, k))
+        return cls(train, test, brute_force_knn_l2(train, test, k, device=device))
 
     @classmethod
     def read(cls, path, limit_train=None, limit_test=None):
@@ -101,21 +101,38 @@ class Dataset:
             f.set_attr("distance", self.distance)
 
     @classmethod
-    def read_texmex(cls, base, query, groundtruth=None, k=10, limit_train=None, limit_test=None):
+    def read_texmex(cls, base, query, groundtruth=None, k=10, limit_train=None, limit_test=None, device=None):
         train = read_fvecs(base, limit_train)
         test = read_fvecs(query, limit_test)
         if groundtruth is not None and limit_train is None:
             gt = read_ivecs(groundtruth, limit_test)[:, :k]
             d = np.sqrt(((train[gt] - test[:, None, :]) ** 2).sum(-1)).astype(np.float32)
         else:
-            d = brute_force_knn_l2(train, test, k)
+            d = brute_force_knn_l2(train, test, k, device=device)
         return cls(train, test, d)
 
 
-def brute_force_knn_l2(train, test, k, block=256):
-    """benchmark/dataset.ml:15-30: for each test vector the k smallest L2 distances, ascending."""
+def brute_force_knn_l2(train, test, k, block=256, device=None):
+    """benchmark/dataset.ml:15-30: for each test vector the k smallest L2 distances, ascending.
+
+    Two routes, which differ in the last bits.  device=None: float64 numpy on the CPU (|a|^2 - 2ab + |b|^2, rounded to
+    float32 at the end).  device=<number>: the library's exact scan (hnsw_brute_force_batch) over a flat index uploaded to
+    that device; its distances are the float32 bits the searches themselves return for the same pairs (same summation
+    order), and where k exceeds the number of train vectors they are NaN.  Recall.compute compares a search's distances
+    with the k-th true distance + 1e-8, far below one float32 step: only against the device route is "<=" exact -- a
+    true neighbour is never a miss, nor a near miss a hit, because the two sides round differently."""
     train = np.ascontiguousarray(train, np.float32)
     test = np.ascontiguousarray(test, np.float32)
+    if device is not None:
+        try:
+            from . import Hgraph, Ohnsw
+        except ImportError:       # imported as a plain module (tools/)
+            from ocaml_hnsw_amd import Hgraph, Ohnsw
+        hg = Hgraph.flat(train).to_device(device)
+        try:
+            return Ohnsw.brute_force_knn(hg, k, test)[1]
+        finally:
+            hg.release()
     tn = (train.astype(np.float64) ** 2).sum(1)
     out = np.empty((test.shape[0], k), np.float32)
     for s in range(0, test.shape[0], block):

@@ -2,6 +2,7 @@
 // over the C ABI of include/hnsw_mi355x.h (header only; link with libhnsw_mi355x.so).
 //
 //   Hnsw::Ohnsw::knn / knn_batch_bigarray / build_batch_bigarray / insert / distance_l2   lib/ohnsw.ml:766-899
+//   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
 //   Hnsw::MultiHgraph (one process, several GPUs)                                SURVEY 8e
@@ -186,6 +187,15 @@ inline value_distance search_one(const Hgraph &g, int layer, int64_t start_node,
     int64_t node = 0; float d = 0.f;
     check(hnsw_search_one_batch(g.handle(), layer, target, 1, g.dim(), &start_node, &node, &d));
     return {(int)node, d};
+}
+
+// brute_force_knn_l2 (benchmark/dataset.ml:15-30) over the vectors the index holds (hnsw_brute_force_batch): for each query the k
+// smallest of all stored vectors under (distance, id), ascending -> (ids, distances), both [nq][k] (-1 / NaN where k > n)
+inline std::pair<std::vector<int32_t>, std::vector<float>> brute_force_knn(const Hgraph &g, int k, const Mat &batch) {
+    std::vector<int32_t> ids((size_t)batch.dim2 * (size_t)(k > 0 ? k : 0));
+    std::vector<float> dist(ids.size());
+    check(hnsw_brute_force_batch(g.handle(), batch.data, batch.dim2, batch.dim1, k, HNSW_FILL_OHNSW, ids.data(), dist.data()));
+    return {std::move(ids), std::move(dist)};
 }
 
 // Ohnsw.distance_l2 a b (lib/ohnsw.ml:899), batched: out[q][j] = distance(batch[q], value ids[q][j])

@@ -122,6 +122,9 @@ let hnsw_knn =
 let hnsw_distance_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_distance_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> int32_t @-> ptr float @-> returning int32_t)
+let hnsw_brute_force_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_brute_force_batch"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float @-> returning int32_t)
 let hnsw_select_neighbours_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_select_neighbours_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> ptr int32_t @-> int32_t @-> int32_t @-> int32_t
@@ -222,6 +225,9 @@ let hnsw_search_batch_h2d =
 let hnsw_distance_batch_device =
   foreign ~from:lib "hnsw_distance_batch_device"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> int32_t @-> ptr float @-> ptr void @-> returning int32_t)
+let hnsw_brute_force_batch_device =
+  foreign ~from:lib "hnsw_brute_force_batch_device"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float @-> ptr void @-> returning int32_t)
 let hnsw_host_register = foreign ~from:lib "hnsw_host_register" (ptr void @-> int64_t @-> returning int32_t)
 let hnsw_host_unregister = foreign ~from:lib "hnsw_host_unregister" (ptr void @-> returning int32_t)
 let hnsw_host_alloc = foreign ~from:lib "hnsw_host_alloc" (ptr (ptr void) @-> int64_t @-> returning int32_t)
@@ -723,6 +729,27 @@ let distance_batch (t : t) (queries : Lacaml.S.mat) (ids : int array array) : fl
   check (hnsw_distance_batch t.handle (bigarray_start array2 queries) (Int64.of_int nq) (Int64.of_int t.dim)
            (CArray.start flat_ids) (Int32.of_int m) (CArray.start out));
   Array.init nq (fun q -> Array.init m (fun j -> CArray.get out (q * m + j)))
+
+(* The exact scan (hnsw_brute_force_batch) over the vectors the index holds, with its metric: for each query (a column of
+   [test]) the k smallest of all stored vectors under (distance, node id), ascending.  -> (ids, distances), both
+   [nq][k]; where k exceeds the number of vectors: id -1, distance nan. *)
+let brute_force_knn (t : t) (test : Lacaml.S.mat) ~k : int array array * float array array =
+  let nq = A2.dim2 test in
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  check (hnsw_brute_force_batch t.handle (bigarray_start array2 test) (Int64.of_int nq) (Int64.of_int t.dim)
+           (Int32.of_int k) 0l (CArray.start ids) (CArray.start dist));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))))
+
+(* brute_force_knn_l2 (benchmark/dataset.ml:15-30) with its body on the device: the distance matrix it returns
+   (k x nq: column q = the ascending distances of test vector q's k nearest train vectors), for an index that holds the
+   train vectors.  The distances are the float32 bits the searches return, so Recall.compute's epsilon (benchmark/dataset.ml:
+   105-127) compares like with like. *)
+let brute_force_knn_l2 (t : t) (test : Lacaml.S.mat) ~k : Lacaml.S.mat =
+  let _, dist = brute_force_knn t test ~k in
+  let out = Lacaml.S.Mat.create k (A2.dim2 test) in
+  Array.iteri (fun q row -> Array.iteri (fun j v -> out.{j + 1, q + 1} <- v) row) dist;
+  out
 
 (* Ohnsw.select_neighbours (lib/ohnsw.ml:647-663) for ONE base value: candidates as node ids (their distances to the
    target are recomputed on the device), at most ~num_neighbours kept, in selection order (nearest first).

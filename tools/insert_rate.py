@@ -30,17 +30,12 @@ def sift_like(n, d, seed, centres):
 
 
 def ground_truth(X, Q, k):
-    dev = torch.device("cuda", 0)
-    Xd, Qd = torch.from_numpy(X).to(dev), torch.from_numpy(Q).to(dev)
-    xn = (Xd * Xd).sum(1)
-    out = []
-    for s in range(0, len(Qd), 256):
-        q = Qd[s:s + 256]
-        dd = xn[None, :] - 2 * q @ Xd.T
-        out.append(torch.topk(dd, k, dim=1, largest=False).indices.cpu().numpy())
-    del Xd, Qd, xn
-    torch.cuda.empty_cache()
-    return np.concatenate(out)
+    """the exact neighbours' ids: the library's own scan over a flat index (hnsw_brute_force_batch)"""
+    flat = H.Hgraph.flat(X)
+    try:
+        return H.Ohnsw.brute_force_knn(flat, k, Q)[0]
+    finally:
+        flat.release()
 
 
 def recall(hg, Q, gt, ef=128, k=10):
