@@ -30,64 +30,31 @@ inline uint64_t splitmix64(uint64_t *s) {
 }
 inline double rng_unit(uint64_t *s) { return ((double)(splitmix64(s) >> 11) + 0.5) * (1.0 / 9007199254740992.0); }
 
-template <int NCH, int RB, int METRIC>
-hipError_t launch_k1(int nslot, const BuildView &bv, const BatchView &bt, hipStream_t st) {
+// The builder's launches.  Its construction search keeps W in 1, 2, 4 or 8 registers (efc <= 512: check_build_params).
+hipError_t launch_search(int metric, int nch, int nslot, const BuildView &bv, const BatchView &bt, hipStream_t st) {
     const size_t lds = hnsw_dev::wave_lds_words(bv.vt_bits) * sizeof(uint32_t);
-    dim3 grid((unsigned)bt.B), block(64);
-    switch (nslot) {
-    case 1: hipLaunchKernelGGL((hnsw_dev::build_search_kernel<NCH, RB, 1, METRIC>), grid, block, lds, st, bv, bt); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::build_search_kernel<NCH, RB, 2, METRIC>), grid, block, lds, st, bv, bt); break;
-    case 4: hipLaunchKernelGGL((hnsw_dev::build_search_kernel<NCH, RB, 4, METRIC>), grid, block, lds, st, bv, bt); break;
-    default: hipLaunchKernelGGL((hnsw_dev::build_search_kernel<NCH, RB, 8, METRIC>), grid, block, lds, st, bv, bt); break;
-    }
+    with_metric(metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) { with_nslot<1, 2, 4, 8>(nslot, [&](auto NSLOT) {
+        hipLaunchKernelGGL((hnsw_dev::build_search_kernel<NCH, rows_in_flight(NCH), NSLOT, METRIC>), dim3((unsigned)bt.B), dim3(64), lds, st, bv, bt);
+    }); }); });
     return hipGetLastError();
 }
-template <int METRIC>
-hipError_t dispatch_k1(int nch, int nslot, const BuildView &bv, const BatchView &bt, hipStream_t st) {
-    switch (nch) {
-    case 1: return launch_k1<1, 8, METRIC>(nslot, bv, bt, st);
-    case 2: return launch_k1<2, RB_NCH2, METRIC>(nslot, bv, bt, st);
-    case 4: return launch_k1<4, 2, METRIC>(nslot, bv, bt, st);
-    case 8: return launch_k1<8, 1, METRIC>(nslot, bv, bt, st);
-    default: return launch_k1<16, 1, METRIC>(nslot, bv, bt, st);
-    }
-}
-template <int METRIC>
-hipError_t dispatch_k2(int nch, const BuildView &bv, const BatchView &bt, const SelectArgs &sa, hipStream_t st) {
+hipError_t launch_select(int metric, int nch, const BuildView &bv, const BatchView &bt, const SelectArgs &sa, hipStream_t st) {
     const size_t lds = (2 * (size_t)bv.cand_stride + 64) * sizeof(uint32_t);
-    dim3 grid((unsigned)(sa.rec_end - sa.rec_begin)), block(64);
-    switch (nch) {
-    case 1: hipLaunchKernelGGL((hnsw_dev::build_select_kernel<1, METRIC>), grid, block, lds, st, bv, bt, sa); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::build_select_kernel<2, METRIC>), grid, block, lds, st, bv, bt, sa); break;
-    case 4: hipLaunchKernelGGL((hnsw_dev::build_select_kernel<4, METRIC>), grid, block, lds, st, bv, bt, sa); break;
-    case 8: hipLaunchKernelGGL((hnsw_dev::build_select_kernel<8, METRIC>), grid, block, lds, st, bv, bt, sa); break;
-    default: hipLaunchKernelGGL((hnsw_dev::build_select_kernel<16, METRIC>), grid, block, lds, st, bv, bt, sa); break;
-    }
+    with_metric(metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {
+        hipLaunchKernelGGL((hnsw_dev::build_select_kernel<NCH, METRIC>), dim3((unsigned)(sa.rec_end - sa.rec_begin)), dim3(64), lds, st, bv, bt, sa);
+    }); });
     return hipGetLastError();
 }
-template <int METRIC>
-hipError_t dispatch_k4(int nch, const BuildView &bv, const MergeArgs &ma, hipStream_t st) {
-    dim3 grid((unsigned)ma.n_edges), block(64);
-    switch (nch) {
-    case 1: hipLaunchKernelGGL((hnsw_dev::build_merge_kernel<1, 8, METRIC>), grid, block, 0, st, bv, ma); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::build_merge_kernel<2, 4, METRIC>), grid, block, 0, st, bv, ma); break;
-    case 4: hipLaunchKernelGGL((hnsw_dev::build_merge_kernel<4, 2, METRIC>), grid, block, 0, st, bv, ma); break;
-    case 8: hipLaunchKernelGGL((hnsw_dev::build_merge_kernel<8, 1, METRIC>), grid, block, 0, st, bv, ma); break;
-    default: hipLaunchKernelGGL((hnsw_dev::build_merge_kernel<16, 1, METRIC>), grid, block, 0, st, bv, ma); break;
-    }
+hipError_t launch_merge(int metric, int nch, const BuildView &bv, const MergeArgs &ma, hipStream_t st) {
+    with_metric(metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {
+        hipLaunchKernelGGL((hnsw_dev::build_merge_kernel<NCH, rows_in_flight(NCH), METRIC>), dim3((unsigned)ma.n_edges), dim3(64), 0, st, bv, ma);
+    }); });
     return hipGetLastError();
 }
-
-template <int METRIC>
-hipError_t dispatch_link(int nch, const BuildView &bv, const hnsw_dev::LinkArgs &la, hipStream_t st) {
-    dim3 grid(1), block(64);
-    switch (nch) {
-    case 1: hipLaunchKernelGGL((hnsw_dev::build_link_sequential_kernel<1, 8, METRIC>), grid, block, 0, st, bv, la); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::build_link_sequential_kernel<2, 4, METRIC>), grid, block, 0, st, bv, la); break;
-    case 4: hipLaunchKernelGGL((hnsw_dev::build_link_sequential_kernel<4, 2, METRIC>), grid, block, 0, st, bv, la); break;
-    case 8: hipLaunchKernelGGL((hnsw_dev::build_link_sequential_kernel<8, 1, METRIC>), grid, block, 0, st, bv, la); break;
-    default: hipLaunchKernelGGL((hnsw_dev::build_link_sequential_kernel<16, 1, METRIC>), grid, block, 0, st, bv, la); break;
-    }
+hipError_t launch_link(int metric, int nch, const BuildView &bv, const hnsw_dev::LinkArgs &la, hipStream_t st) {
+    with_metric(metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {
+        hipLaunchKernelGGL((hnsw_dev::build_link_sequential_kernel<NCH, rows_in_flight(NCH), METRIC>), dim3(1), dim3(64), 0, st, bv, la);
+    }); });
     return hipGetLastError();
 }
 
@@ -207,7 +174,7 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
         bt.cur_max_layer = cur_max; bt.entry = entry;
         bt.cand_id = (int32_t *)dCandId; bt.cand_key = (uint32_t *)dCandKey; bt.cand_cnt = (int32_t *)dCandCnt;
         bv.iv.max_layer = cur_max; bv.iv.entry_point = entry;
-        HIP_TRY_B(p->metric == HNSW_METRIC_L2 ? dispatch_k1<0>(nch, nslot, bv, bt, st) : dispatch_k1<1>(nch, nslot, bv, bt, st));
+        HIP_TRY_B(launch_search(p->metric, nch, nslot, bv, bt, st));
 
         for (int l = cur_max; l >= 0; --l) {
             const int rb = rec_begin[(size_t)l], re = rec_begin[(size_t)l + 1];
@@ -216,12 +183,12 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
             SelectArgs sa{};
             sa.rec_node = (const int32_t *)dRecNode; sa.rec_begin = rb; sa.rec_end = re; sa.layer = l; sa.R = R;
             sa.edges = (uint64_t *)dEdges;
-            HIP_TRY_B(p->metric == HNSW_METRIC_L2 ? dispatch_k2<0>(nch, bv, bt, sa, st) : dispatch_k2<1>(nch, bv, bt, sa, st));
+            HIP_TRY_B(launch_select(p->metric, nch, bv, bt, sa, st));
             if (B == 1) {
                 // a batch of one node: the link step of Ohnsw.insert exactly, neighbour by neighbour (:820-829)
                 hnsw_dev::LinkArgs la{};
                 la.q = (int32_t)pos; la.layer = l; la.R = R;
-                HIP_TRY_B(p->metric == HNSW_METRIC_L2 ? dispatch_link<0>(nch, bv, la, st) : dispatch_link<1>(nch, bv, la, st));
+                HIP_TRY_B(launch_link(p->metric, nch, bv, la, st));
                 continue;
             }
             const int n_edges = (re - rb) * R;
@@ -231,7 +198,7 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
             MergeArgs ma{};
             ma.edges = (const uint64_t *)dEdgesSorted; ma.n_edges = n_edges; ma.layer = l; ma.R = R;
             ma.removals = (uint64_t *)dRem; ma.rem_cnt = (uint32_t *)dRemCnt; ma.rem_cap = (uint32_t)rem_cap;
-            HIP_TRY_B(p->metric == HNSW_METRIC_L2 ? dispatch_k4<0>(nch, bv, ma, st) : dispatch_k4<1>(nch, bv, ma, st));
+            HIP_TRY_B(launch_merge(p->metric, nch, bv, ma, st));
             // one thread per possible removal: the count is only known on the device (clamped to the buffer there)
             const unsigned rem_threads = (unsigned)std::min<int64_t>(std::max<int64_t>((int64_t)n_edges * 2, 4096), rem_cap);
             hipLaunchKernelGGL(hnsw_dev::build_unlink_kernel, dim3((rem_threads + 255) / 256), dim3(256), 0, st, bv,
@@ -508,10 +475,8 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
     bind_view(idx);                                        // the options keep their effect
     idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
     hnsw_index_destroy(nx);
-    // the per-shape choices that follow n or the row format
-    idx->resident_queries = 0; idx->vt_grow_key = -1;
-    if (rows_before != idx->info.row_format)
-        for (auto &c : idx->blk_choice) c[0] = c[1] = -1;
+    // the per-shape decisions that follow n or the row format
+    idx->forget_shapes(/*keep_visited=*/rows_before == idx->info.row_format);
     if (idx->fb_queries > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.cap / (n * 4), 65536);
     // the grown index is searched at the steady-state rate from its first call, as a loaded one
     (void)warm_up(idx);
@@ -572,15 +537,9 @@ int32_t hnsw_select_neighbours_batch(hnsw_index *idx, const float *targets, int6
     sa.cand_stride = cand_stride; sa.nb = (int32_t)nb; sa.R = num_neighbours; sa.keep_all_if_few = keep_all_if_few;
     sa.out = (int32_t *)dO.p; sa.out_cnt = (int32_t *)dOc.p; sa.cand_deg = cand_degree ? (const int32_t *)dDg.p : nullptr;
     const size_t lds = ((size_t)4 * cand_stride + 128) * 4;
-    const int nch = pick_nch(idx->iv.nchunks);
-    dim3 grid((unsigned)nb), block(64);
-#define LAUNCH_SEL(N, R_, M_) hipLaunchKernelGGL((hnsw_dev::select_neighbours_kernel<N, R_, M_>), grid, block, lds, 0, idx->iv, sa)
-    if (idx->info.metric == HNSW_METRIC_L2) {
-        switch (nch) { case 1: LAUNCH_SEL(1, 8, 0); break; case 2: LAUNCH_SEL(2, 4, 0); break; case 4: LAUNCH_SEL(4, 2, 0); break; case 8: LAUNCH_SEL(8, 1, 0); break; default: LAUNCH_SEL(16, 1, 0); }
-    } else {
-        switch (nch) { case 1: LAUNCH_SEL(1, 8, 1); break; case 2: LAUNCH_SEL(2, 4, 1); break; case 4: LAUNCH_SEL(4, 2, 1); break; case 8: LAUNCH_SEL(8, 1, 1); break; default: LAUNCH_SEL(16, 1, 1); }
-    }
-#undef LAUNCH_SEL
+    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(pick_nch(idx->iv.nchunks), [&](auto NCH) {
+        hipLaunchKernelGGL((hnsw_dev::select_neighbours_kernel<NCH, rows_in_flight(NCH), METRIC>), dim3((unsigned)nb), dim3(64), lds, 0, idx->iv, sa);
+    }); });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, dO.p, (size_t)nb * num_neighbours * 4, hipMemcpyDeviceToHost);

@@ -175,28 +175,16 @@ int upload_upper_layout(IndexTables &t, int64_t n0, const std::vector<int2> &ref
 
 // ---- kernel dispatch ---------------------------------------------------------------------------
 // the knn kernel's variants live in hnsw_search_variants.hip, one object per (metric, accept rule, row shape)
-#define HNSW_DECL_VARIANT(m, s, f)                                                                                   \
+#define HNSW_V_DECLARE(m, s, f)                                                                                             \
     hipError_t search_launch_##m##_##s##_##f(int nch, int nslot, const IndexView &iv, const SearchArgs &a, hipStream_t st); \
     int search_occupancy_##m##_##s##_##f(int nch, int nslot, size_t lds, int blk);
-HNSW_DECL_VARIANT(0, 0, 0) HNSW_DECL_VARIANT(0, 0, 1) HNSW_DECL_VARIANT(0, 0, 2) HNSW_DECL_VARIANT(0, 0, 3) HNSW_DECL_VARIANT(0, 0, 4)
-HNSW_DECL_VARIANT(0, 1, 0) HNSW_DECL_VARIANT(0, 1, 1) HNSW_DECL_VARIANT(0, 1, 2) HNSW_DECL_VARIANT(0, 1, 3) HNSW_DECL_VARIANT(0, 1, 4)
-HNSW_DECL_VARIANT(1, 0, 0) HNSW_DECL_VARIANT(1, 0, 1) HNSW_DECL_VARIANT(1, 0, 2) HNSW_DECL_VARIANT(1, 0, 3) HNSW_DECL_VARIANT(1, 0, 4)
-HNSW_DECL_VARIANT(1, 1, 0) HNSW_DECL_VARIANT(1, 1, 1) HNSW_DECL_VARIANT(1, 1, 2) HNSW_DECL_VARIANT(1, 1, 3) HNSW_DECL_VARIANT(1, 1, 4)
-#undef HNSW_DECL_VARIANT
-
+#define HNSW_V_ENTRY(m, s, f) {m, s, f, search_launch_##m##_##s##_##f, search_occupancy_##m##_##s##_##f},
+HNSW_SEARCH_VARIANTS(HNSW_V_DECLARE)
 typedef hipError_t (*search_launch_fn)(int, int, const IndexView &, const SearchArgs &, hipStream_t);
 typedef int (*search_occupancy_fn)(int, int, size_t, int);
-constexpr int ROW_VARIANTS = 5;          // HNSW_V_FULL 0..4, see variant_full
-const search_launch_fn k_launch[2][2][ROW_VARIANTS] = {
-    {{search_launch_0_0_0, search_launch_0_0_1, search_launch_0_0_2, search_launch_0_0_3, search_launch_0_0_4},
-     {search_launch_0_1_0, search_launch_0_1_1, search_launch_0_1_2, search_launch_0_1_3, search_launch_0_1_4}},
-    {{search_launch_1_0_0, search_launch_1_0_1, search_launch_1_0_2, search_launch_1_0_3, search_launch_1_0_4},
-     {search_launch_1_1_0, search_launch_1_1_1, search_launch_1_1_2, search_launch_1_1_3, search_launch_1_1_4}}};
-const search_occupancy_fn k_occupancy[2][2][ROW_VARIANTS] = {
-    {{search_occupancy_0_0_0, search_occupancy_0_0_1, search_occupancy_0_0_2, search_occupancy_0_0_3, search_occupancy_0_0_4},
-     {search_occupancy_0_1_0, search_occupancy_0_1_1, search_occupancy_0_1_2, search_occupancy_0_1_3, search_occupancy_0_1_4}},
-    {{search_occupancy_1_0_0, search_occupancy_1_0_1, search_occupancy_1_0_2, search_occupancy_1_0_3, search_occupancy_1_0_4},
-     {search_occupancy_1_1_0, search_occupancy_1_1_1, search_occupancy_1_1_2, search_occupancy_1_1_3, search_occupancy_1_1_4}}};
+const struct { int metric, semf, rows; search_launch_fn launch; search_occupancy_fn occupancy; } k_variants[] = {HNSW_SEARCH_VARIANTS(HNSW_V_ENTRY)};
+#undef HNSW_V_DECLARE
+#undef HNSW_V_ENTRY
 
 // the knn kernel's row format: 2 = byte rows (hnsw_rows8.hip), 3 = split fp32 rows (hnsw_rows_split.hip), 4 = half rows
 // (hnsw_rows16.hip), else plain fp32 rows, 1 = every chunk of the lane grid inside the row.  (From the record bind_view keeps:
@@ -210,9 +198,28 @@ inline int variant_full(const hnsw_index *idx) {
     }
 }
 
-template <int METRIC>
-hipError_t dispatch_dist(int nch, const IndexView &iv, const float *Q, int64_t qs, int64_t nq,
-                         const int32_t *ids, int32_t m, float *out, hipStream_t st) {
+// The knn kernel a search of (ef, accept rule) on this handle runs: its place on the (NCH, NSLOT) grid, its row of the handle's
+// per-shape decisions (hnsw_index::shape) and the variant object's entry points.  Resolved once per call by the entry points and
+// handed down.
+struct KnnShape {
+    int ef, semf, nch, nslot, slot_class;
+    search_launch_fn launch;
+    search_occupancy_fn occupancy;
+    // waves of the kernel (blk: of its bitmap-block twin) one CU holds when each asks for `lds` bytes, 0 = unknown
+    int waves_per_cu(size_t lds, bool blk = false) const { return occupancy(nch, nslot, lds, blk); }
+    hnsw_index::ShapeChoice &choice(hnsw_index *idx) const { return idx->shape[slot_class][semf]; }
+};
+KnnShape knn_shape(const hnsw_index *idx, int ef, int semantics) {
+    KnnShape sh{};
+    sh.ef = ef; sh.semf = semantics ? 1 : 0;
+    sh.nch = pick_nch(idx->iv.nchunks); sh.nslot = pick_nslot_knn(ef, sh.nch); sh.slot_class = slot_class(sh.nslot);
+    const int metric = idx->info.metric == HNSW_METRIC_L2 ? 0 : 1, rows = variant_full(idx);
+    for (const auto &v : k_variants)
+        if (v.metric == metric && v.semf == sh.semf && v.rows == rows) { sh.launch = v.launch; sh.occupancy = v.occupancy; }
+    return sh;
+}
+
+hipError_t launch_distance(const hnsw_index *idx, const float *Q, int64_t qs, int64_t nq, const int32_t *ids, int32_t m, float *out, hipStream_t st) {
     // blockIdx.y strides over a query's ids: enough blocks to fill the chip twice over (8 192 waves: what it holds at four waves
     // per SIMD, twice), no more -- every block starts by loading its query, and a block that then evaluates thirty-two batches
     // amortises that better than one that evaluates four (bench_dist's shape, profiles/r06_dist_ab.txt: 6.07 / 5.77 TB/s at 8 192
@@ -221,13 +228,11 @@ hipError_t dispatch_dist(int nch, const IndexView &iv, const float *Q, int64_t q
     const int64_t per_query = std::max<int64_t>(1, (DIST_WAVES + std::max<int64_t>(nq, 1) - 1) / std::max<int64_t>(nq, 1));
     const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(256, (m + 15) / 16), per_query));
     dim3 grid((unsigned)nq, gy), block(64);
-    switch (nch) {
-    case 1: hipLaunchKernelGGL((hnsw_dev::hnsw_distance_kernel<1, METRIC>), grid, block, 0, st, iv, Q, qs, nq, ids, m, out); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_distance_kernel<2, METRIC>), grid, block, 0, st, iv, Q, qs, nq, ids, m, out); break;
-    case 4: hipLaunchKernelGGL((hnsw_dev::hnsw_distance_kernel<4, METRIC>), grid, block, 0, st, iv, Q, qs, nq, ids, m, out); break;
-    case 8: hipLaunchKernelGGL((hnsw_dev::hnsw_distance_kernel<8, METRIC>), grid, block, 0, st, iv, Q, qs, nq, ids, m, out); break;
-    default: hipLaunchKernelGGL((hnsw_dev::hnsw_distance_kernel<16, METRIC>), grid, block, 0, st, iv, Q, qs, nq, ids, m, out); break;
-    }
+    with_metric(idx->info.metric, [&](auto METRIC) {
+        with_nch(pick_nch(idx->iv.nchunks), [&](auto NCH) {
+            hipLaunchKernelGGL((hnsw_dev::hnsw_distance_kernel<NCH, METRIC>), grid, block, 0, st, idx->iv, Q, qs, nq, ids, m, out);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -237,23 +242,19 @@ hipError_t dispatch_dist(int nch, const IndexView &iv, const float *Q, int64_t q
 // directions, M 32, ef 256: 8239 evaluations per query with 2^11 tags against 5015 in the oracle, 6592 with 2^12: 5.22 ->
 // 4.36 ms per 10 k batch; 2^13 would halve the residency: 5.17 ms).  So: the largest cache (up to 2^14 tags) that keeps the
 // waves per CU the variant reaches with the base size.  Never changes results; "vt_bits" still overrides.
-int knn_vt_bits(hnsw_index *idx, int ef, int semf) {
-    const int base = search_vt_bits(idx, ef);
+int knn_vt_bits(hnsw_index *idx, const KnnShape &sh) {
+    const int base = search_vt_bits(idx, sh.ef);
     if (idx->vt_bits_override) return base;
-    const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(ef, nch);
-    const int vkey = ((nslot * 2 + semf) * ROW_VARIANTS + variant_full(idx)) * 32 + base;
-    if (idx->vt_grow_key == vkey) return idx->vt_grow_bits;
-    const search_occupancy_fn occ = k_occupancy[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][semf][variant_full(idx)];
-    const int occ0 = occ(nch, nslot, hnsw_dev::wave_lds_words(base) * sizeof(uint32_t), 0);
+    int &grown = sh.choice(idx).vt_bits;      // (a slot class lies on one side of search_vt_bits' ef boundary: one base per entry)
+    if (grown) return grown;
+    const int occ0 = sh.waves_per_cu(hnsw_dev::wave_lds_words(base) * sizeof(uint32_t));
     int b = base;
-    while (occ0 > 0 && b < 14 && occ(nch, nslot, hnsw_dev::wave_lds_words(b + 1) * sizeof(uint32_t), 0) >= occ0) ++b;
-    idx->vt_grow_key = vkey; idx->vt_grow_bits = b;
-    return b;
+    while (occ0 > 0 && b < 14 && sh.waves_per_cu(hnsw_dev::wave_lds_words(b + 1) * sizeof(uint32_t)) >= occ0) ++b;
+    return grown = b;
 }
 
-int launch_search_args(hnsw_index *idx, SearchArgs &a, hipStream_t st) {
-    const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(a.ef, nch);
-    hipError_t e = k_launch[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][a.sem ? 1 : 0][variant_full(idx)](nch, nslot, idx->iv, a, st);
+int launch_search_args(hnsw_index *idx, const KnnShape &sh, const SearchArgs &a, hipStream_t st) {
+    hipError_t e = sh.launch(sh.nch, sh.nslot, idx->iv, a, st);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "search kernel launch failed: %s", hipGetErrorString(e));
     return HNSW_OK;
 }
@@ -289,22 +290,21 @@ SearchArgs knn_args(const hnsw_search_params &p, const KnnBatch &b, int vt_bits,
 void release_unused_lcode0(hnsw_index *idx) {
     if (!idx->tables.lcode0.p) return;
     if (idx->blk_mode == 1) return;                  // the caller asked for blocks wherever they can run: keep the table
-    for (auto &c : idx->blk_choice) if (c[0] > 0 || c[1] > 0) return;
+    for (auto &c : idx->shape) if (c[0].blk > 0 || c[1].blk > 0) return;
     drop_lcode0(idx);
 }
 
 // the largest block directory (log2 slots) that keeps the waves per CU of this shape's kernel, 0 = the shape cannot run the blocks
-int blk_capacity_bits(hnsw_index *idx, int ef, int semf) {
-    const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(ef, nch), vt = knn_vt_bits(idx, ef, semf);
-    if (nslot < 3) return 0;
-    const search_occupancy_fn occ = k_occupancy[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][semf][variant_full(idx)];
+int blk_capacity_bits(hnsw_index *idx, const KnnShape &sh) {
+    if (sh.nslot < 3) return 0;
+    const int vt = knn_vt_bits(idx, sh);
     // (the waves per CU of the tag-cache kernel, or of the block kernel at its smallest directory if its registers allow fewer)
-    const int occ0 = std::min(occ(nch, nslot, hnsw_dev::wave_lds_words(vt) * sizeof(uint32_t), 0),
-                              occ(nch, nslot, hnsw_dev::search_lds_words(vt, 6) * sizeof(uint32_t), 1));
+    const int occ0 = std::min(sh.waves_per_cu(hnsw_dev::wave_lds_words(vt) * sizeof(uint32_t)),
+                              sh.waves_per_cu(hnsw_dev::search_lds_words(vt, 6) * sizeof(uint32_t), true));
     int bits = 0;
     for (int b = 6; b <= 10; ++b)
         if (hnsw_dev::wave_lds_words_blocks(b) * sizeof(uint32_t) <= 65536 && occ0 > 0 &&
-            occ(nch, nslot, hnsw_dev::search_lds_words(vt, b) * sizeof(uint32_t), 1) >= occ0) bits = b;
+            sh.waves_per_cu(hnsw_dev::search_lds_words(vt, b) * sizeof(uint32_t), true) >= occ0) bits = b;
     if (bits == 0) return 0;
     {   // HNSW_BLK_BITS (tests): a smaller directory than fits, down to one set of eight slots -- evictions and contested slots on small graphs
         const int forced = env_int("HNSW_BLK_BITS", 0);
@@ -322,18 +322,17 @@ bool blk_auto_eligible(const hnsw_index *idx, int nslot) {
     // runs it, and the C++ loop of every other shape), but a byte-row kernel is bound by the LATENCY of a hop, and the filter's
     // four dependent LDS round trips and ~90 vector instructions cost a hop more than the evaluations it saves: the harder
     // SIFT-like set at ef 192, 8 % fewer evaluations, 0.98 -> 1.10 ms per 10 k batch (profiles/r05_ab_bytes_blocks.txt).
-    return variant_full(idx) != 2 && idx->iv.nchunks > 16 && idx->iv.nchunks <= 64 && nslot <= 8;
+    return idx->info.row_format != HNSW_ROWS_BYTES && idx->iv.nchunks > 16 && idx->iv.nchunks <= 64 && nslot <= 8;
 }
 
-int knn_blk_bits(hnsw_index *idx, int ef, int semf) {
-    const int nslot = pick_nslot_knn(ef, pick_nch(idx->iv.nchunks));
-    const int ls = slot_class(nslot);
+int knn_blk_bits(hnsw_index *idx, const KnnShape &sh) {
+    const int ef = sh.ef, semf = sh.semf, nslot = sh.nslot;
     const int mode = idx->blk_mode;
     if (mode == 0 || nslot < 3 || idx->lcode_state < 0) return 0;
     if (mode < 0 && !blk_auto_eligible(idx, nslot)) return 0;
-    int &choice = idx->blk_choice[ls][semf];
+    int &choice = sh.choice(idx).blk;
     if (choice >= 0) return choice;
-    const int bits = blk_capacity_bits(idx, ef, semf), vt = knn_vt_bits(idx, ef, semf);
+    const int bits = blk_capacity_bits(idx, sh), vt = knn_vt_bits(idx, sh);
     if (bits == 0) return choice = 0;
     if (build_locality_codes(idx) != HNSW_OK || idx->lcode_state != 1 || !idx->tables.lcode0.p) return choice = 0;
     if (mode == 1) return choice = bits;
@@ -353,7 +352,7 @@ int knn_blk_bits(hnsw_index *idx, int ef, int semf) {
     for (int pass = 0; pass < 2 && ok; ++pass) {
         SearchArgs a = knn_args(p, b, vt, pass ? bits : 0);
         std::vector<uint32_t> nd((size_t)nq);
-        ok = launch_search_args(idx, a, nullptr) == HNSW_OK && hipDeviceSynchronize() == hipSuccess &&
+        ok = launch_search_args(idx, sh, a, nullptr) == HNSW_OK && hipDeviceSynchronize() == hipSuccess &&
              hipMemcpy(nd.data(), b.nd, (size_t)nq * 4, hipMemcpyDeviceToHost) == hipSuccess;
         for (uint32_t v : nd) sum[pass] += v;
     }
@@ -366,25 +365,22 @@ int knn_blk_bits(hnsw_index *idx, int ef, int semf) {
                 ef, nslot, semf, (double)sum[0] / (double)nq, bits, (double)sum[1] / (double)nq, choice ? "blocks" : "tags");
     return choice;
 }
-// LDS bytes of one search wave of this index at this ef (no padding)
-size_t knn_lds_bytes(hnsw_index *idx, int ef, int semf) {
-    return hnsw_dev::search_lds_words(knn_vt_bits(idx, ef, semf), knn_blk_bits(idx, ef, semf)) * sizeof(uint32_t);
+// LDS bytes of one search wave of this shape (no padding)
+size_t knn_lds_bytes(hnsw_index *idx, const KnnShape &sh) {
+    return hnsw_dev::search_lds_words(knn_vt_bits(idx, sh), knn_blk_bits(idx, sh)) * sizeof(uint32_t);
 }
 
-// how many one-wave workgroups of the search kernel for this ef are resident on the device at once (no LDS padding)
-int64_t resident_queries(hnsw_index *idx, int ef, int semf) {
-    // cached in the handle; the answer depends on the kernel variant's registers and LDS
-    const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot_knn(ef, nch);
-    const size_t lds = knn_lds_bytes(idx, ef, semf);
-    const int vkey = (nslot * 2 + semf) * ROW_VARIANTS + variant_full(idx);
-    if (idx->resident_queries && idx->resident_nslot == vkey && idx->resident_lds == lds) return idx->resident_queries;
-    const int per_cu = k_occupancy[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][semf][variant_full(idx)](nch, nslot, lds, knn_blk_bits(idx, ef, semf) > 0);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, idx->device) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
-    const int64_t v = (per_cu > 0 && cus > 0) ? (int64_t)per_cu * cus : (int64_t)1 << 40;   // unknown: never reorder
-    idx->resident_queries = v; idx->resident_nslot = vkey; idx->resident_lds = lds;
-    idx->resident_per_cu = (per_cu > 0 && cus > 0) ? per_cu : 0; idx->cus = cus;
-    return v;
+// how many one-wave workgroups of this shape's kernel are resident at once (no LDS padding): on the device (1 << 40 when that is
+// unknown: never reorder) and on one CU (0 when unknown)
+struct Residency { int64_t queries; int per_cu; };
+Residency resident_queries(hnsw_index *idx, const KnnShape &sh) {
+    // the answer depends on the kernel's registers and LDS: asked once per shape (hnsw_index::shape)
+    const size_t lds = knn_lds_bytes(idx, sh);
+    if (idx->cus <= 0 && hipDeviceGetAttribute(&idx->cus, hipDeviceAttributeMultiprocessorCount, idx->device) != hipSuccess) { (void)hipGetLastError(); idx->cus = 0; }
+    hnsw_index::ShapeChoice &c = sh.choice(idx);
+    if (c.per_cu < 0 || c.lds != lds) { c.per_cu = std::max(0, sh.waves_per_cu(lds, knn_blk_bits(idx, sh) > 0)); c.lds = lds; }
+    if (c.per_cu > 0 && idx->cus > 0) return {(int64_t)c.per_cu * idx->cus, c.per_cu};
+    return {(int64_t)1 << 40, 0};
 }
 
 // LDS bytes to request beyond what a search wave uses, for a launch of nq > resident queries (longest first).
@@ -395,24 +391,23 @@ int64_t resident_queries(hnsw_index *idx, int ef, int semf) {
 // (C2: 0.78 -> 0.74 ms per call).  The only per-launch handle on residency is the LDS a workgroup asks for:
 // gfx950 hands LDS out in 1280-byte granules, 128 per CU, so k granules per wave hold floor(128 / k) waves.
 // Chosen: the fewest waves per CU that still cover nq / passes.
-int balanced_lds_pad(hnsw_index *idx, int64_t nq, int ef, int semf) {
-    if (idx->lds_pad >= 0) {     // option "lds_pad": clamped to what a workgroup may ask for beside its own scratch
-        const int64_t base_f = (int64_t)knn_lds_bytes(idx, ef, semf);
-        return (int)std::max<int64_t>(0, std::min<int64_t>(std::min(idx->lds_pad, 32768), 65536 - base_f));
-    }
-    const int64_t resident = resident_queries(idx, ef, semf);
-    if (nq <= resident || idx->resident_per_cu <= 0) return 0;
+int balanced_lds_pad(hnsw_index *idx, const KnnShape &sh, int64_t nq) {
+    const int64_t base = (int64_t)knn_lds_bytes(idx, sh);
+    if (idx->lds_pad >= 0)       // option "lds_pad": clamped to what a workgroup may ask for beside its own scratch
+        return (int)std::max<int64_t>(0, std::min<int64_t>(std::min(idx->lds_pad, 32768), 65536 - base));
+    const Residency res = resident_queries(idx, sh);
+    const int64_t resident = res.queries;
+    if (nq <= resident || res.per_cu <= 0) return 0;
     // byte rows: a quarter of the bytes per evaluation, the launch is bound by the latency of a hop, not by the
     // memory system, and holds as many queries as the registers allow (C2: 0.60 ms per call at 8192 held, 0.65 at 5376)
-    if (variant_full(idx) == 2) return 0;
+    if (idx->info.row_format == HNSW_ROWS_BYTES) return 0;
     constexpr int64_t GRANULE = 1280, GRANULES_PER_CU = 128;
-    const int64_t base = (int64_t)knn_lds_bytes(idx, ef, semf);
     const int64_t passes = (nq + resident - 1) / resident;
     const int64_t want_per_cu = (nq + passes * idx->cus - 1) / (passes * idx->cus);
     const int64_t k0 = (base + GRANULE - 1) / GRANULE;
     int64_t best = k0;
     for (int64_t k = k0; k * GRANULE <= 65536; ++k) {         // a workgroup may ask for 64 KiB at most
-        const int64_t w = std::min<int64_t>(idx->resident_per_cu, GRANULES_PER_CU / k);
+        const int64_t w = std::min<int64_t>(res.per_cu, GRANULES_PER_CU / k);
         if (w < want_per_cu) break;
         best = k;
     }
@@ -423,9 +418,8 @@ int balanced_lds_pad(hnsw_index *idx, int64_t nq, int ef, int semf) {
     if (pad > 0) {
         int max_lds = 0;
         if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, idx->device) != hipSuccess) { (void)hipGetLastError(); max_lds = 65536; }
-        const int nch_ = pick_nch(idx->iv.nchunks), nslot_ = pick_nslot_knn(ef, nch_);
-        const search_occupancy_fn occ = k_occupancy[idx->info.metric == HNSW_METRIC_L2 ? 0 : 1][semf][variant_full(idx)];
-        while (pad > 0 && (base + pad > max_lds || occ(nch_, nslot_, (size_t)(base + pad), knn_blk_bits(idx, ef, semf) > 0) < want_per_cu)) pad = pad > GRANULE ? pad - GRANULE : 0;
+        const bool blk = knn_blk_bits(idx, sh) > 0;
+        while (pad > 0 && (base + pad > max_lds || sh.waves_per_cu((size_t)(base + pad), blk) < want_per_cu)) pad = pad > GRANULE ? pad - GRANULE : 0;
     }
     return (int)pad;
 }
@@ -433,15 +427,16 @@ int balanced_lds_pad(hnsw_index *idx, int64_t nq, int ef, int semf) {
 // Issue priorities of an ordered launch (SearchArgs::prio_head / prio_tail; the kernel's comment says why): the first
 // eighth of the blocks that start at once (the walks predicted longest) and, when the launch is one full pass and a
 // partial second one, the blocks that have to wait for a slot.  HNSW_PRIO="head,tail" overrides the bounds (tuning).
-void launch_priorities(hnsw_index *idx, int64_t nq, int ef, int semf, SearchArgs &a) {
+void launch_priorities(hnsw_index *idx, const KnnShape &sh, int64_t nq, SearchArgs &a) {
     a.prio_head = 0; a.prio_tail = 0x7FFFFFFF;
     if (const char *e = getenv("HNSW_PRIO")) {
         int h = 0, t = 0x7FFFFFFF;
         if (sscanf(e, "%d,%d", &h, &t) >= 1) { a.prio_head = h; a.prio_tail = t; }
         return;
     }
-    const int64_t resident = resident_queries(idx, ef, semf);
-    if (idx->resident_per_cu <= 0) return;
+    const Residency res = resident_queries(idx, sh);
+    const int64_t resident = res.queries;
+    if (res.per_cu <= 0) return;
     a.prio_head = (int32_t)(std::min(nq, resident) / 8);
     if (nq > resident && nq < 2 * resident) a.prio_tail = (int32_t)resident;
 }
@@ -479,21 +474,19 @@ int check_batch(const hnsw_index *idx, const hnsw_search_params *p, int64_t nq, 
 // of all nq queries in the first launch, not of this list.
 int launch_rerun(hnsw_index *idx, const hnsw_search_params &p, const KnnBatch &b, const int32_t *qmap, int64_t c, uint32_t *slab,
                  int32_t cap, hipStream_t st) {
-    const int semf = p.semantics ? 1 : 0;
-    const int vt = knn_vt_bits(idx, p.ef, semf), blk = knn_blk_bits(idx, p.ef, semf);
-    SearchArgs a = knn_args(p, b, vt, blk);
+    const KnnShape sh = knn_shape(idx, p.ef, p.semantics);
+    SearchArgs a = knn_args(p, b, knn_vt_bits(idx, sh), knn_blk_bits(idx, sh));
     a.nq = c; a.qmap = qmap; a.q_limit = b.nq; a.ovf_g = slab; a.ovf_gcap = cap;
     a.any_flag = nullptr;                   // (the host has read the word already; a re-run query cannot overflow)
-    return launch_search_args(idx, a, st);
+    return launch_search_args(idx, sh, a, st);
 }
 
 int knn_search(hnsw_index *idx, const hnsw_search_params *params, const KnnBatch &b, hipStream_t st, float *d_stage) {
     int rc = check_batch(idx, params, b.nq, b.q_stride, b.Q && b.ids && b.dist);
     if (rc || b.nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
-    const int semf = params->semantics ? 1 : 0;
-    const int vt = knn_vt_bits(idx, params->ef, semf), blk = knn_blk_bits(idx, params->ef, semf);
-    SearchArgs a = knn_args(*params, b, vt, blk);
+    const KnnShape sh = knn_shape(idx, params->ef, params->semantics);
+    SearchArgs a = knn_args(*params, b, knn_vt_bits(idx, sh), knn_blk_bits(idx, sh));
     // A batch larger than the chip holds at once is searched longest walk first (hnsw_order.hip):
     // per-query results are unchanged, the launch's drain phase is made of short walks.
     void *block = nullptr;
@@ -511,16 +504,16 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *params, const KnnBatch
     // Ordered when more than half of what the chip holds: a batch that fits is faster too with its long walks
     // dispatched first and spread over the CUs (C2, 7168 queries: 0.59 -> 0.45 ms byte rows, 0.68 -> 0.65 ms fp32);
     // below that the pre-pass costs more than it returns.
-    if (mode != 0 && (mode == 1 || 2 * b.nq > resident_queries(idx, params->ef, semf))) {
+    if (mode != 0 && (mode == 1 || 2 * b.nq > resident_queries(idx, sh).queries)) {
         rc = order_longest_first(idx, b.Q, b.nq, b.q_stride, d_stage, st, &block, &a.qmap, &a.pre_entry, &a.pre_key, &a.pre_nd, &a.pre_layer);
         if (rc) return rc;
         if (d_stage) a.Q = d_stage;        // the descent kernel left a device-resident copy of the (host-resident) queries
         a.q_limit = b.nq;
-        a.lds_pad = balanced_lds_pad(idx, b.nq, params->ef, semf);
-        launch_priorities(idx, b.nq, params->ef, semf, a);
+        a.lds_pad = balanced_lds_pad(idx, sh, b.nq);
+        launch_priorities(idx, sh, b.nq, a);
     }
     if (ev) HIP_TRY(hipEventRecord(ev[1], st));
-    rc = launch_search_args(idx, a, st);
+    rc = launch_search_args(idx, sh, a, st);
     if (!rc && idx->fb_queries > 0 && b.st && !b.any_flag) {
         // opt-in exact mode of the device-pointer entry point (option "device_fallback_slab_bytes"): the queries the launch
         // flagged are listed on the device and searched again with the slab, on the caller's stream, no host round trip.
@@ -648,23 +641,24 @@ void prepare_quietly(hnsw_index *idx, int32_t ef, int32_t semantics) {
 }
 void adopt_blk_choice(hnsw_index *idx, int32_t ef, int32_t semantics, bool blocks) {
     if (ef < 1 || ef > 1024) return;
-    const int semf = semantics ? 1 : 0, nslot = pick_nslot_knn(ef, pick_nch(idx->iv.nchunks));
-    if (nslot < 3 || idx->blk_choice[slot_class(nslot)][semf] >= 0) return;
+    const KnnShape sh = knn_shape(idx, ef, semantics);
+    int &choice = sh.choice(idx).blk;
+    if (sh.nslot < 3 || choice >= 0) return;
     int bits = 0;
-    if (blocks && idx->lcode_state == 1 && (bits = blk_capacity_bits(idx, ef, semf)) > 0 && materialise_lcode0(idx) == HNSW_OK && idx->tables.lcode0.p) {
-        idx->blk_choice[slot_class(nslot)][semf] = bits;
+    if (blocks && idx->lcode_state == 1 && (bits = blk_capacity_bits(idx, sh)) > 0 && materialise_lcode0(idx) == HNSW_OK && idx->tables.lcode0.p) {
+        choice = bits;
         return;
     }
-    if (!blocks) idx->blk_choice[slot_class(nslot)][semf] = 0;       // (blocks that cannot be honoured here stay undecided: measured on demand)
+    if (!blocks) choice = 0;       // (blocks that cannot be honoured here stay undecided: measured on demand)
 }
 void list_blk_choices(const hnsw_index *idx, std::vector<int32_t> &out3) {
     static const int rep_ef[SLOT_CLASSES] = {64, 128, 192, 256, 384, 512, 1024};     // an ef of every slot class
-    const bool wide = pick_nch(idx->iv.nchunks) == 2 || pick_nch(idx->iv.nchunks) == 4;
+    const int nch = pick_nch(idx->iv.nchunks);
     for (int c = 0; c < SLOT_CLASSES; ++c)
         for (int s = 0; s < 2; ++s) {
-            if (idx->blk_choice[c][s] < 0) continue;
-            if (!wide && (c == 2 || c == 4)) continue;              // three / six registers: rows of 65..256 dimensions only
-            out3.push_back(rep_ef[c]); out3.push_back(s); out3.push_back(idx->blk_choice[c][s] > 0 ? 1 : 0);
+            const int blk = idx->shape[c][s].blk;
+            if (blk < 0 || slot_class(pick_nslot_knn(rep_ef[c], nch)) != c) continue;    // (undecided, or no such slot count for these rows)
+            out3.push_back(rep_ef[c]); out3.push_back(s); out3.push_back(blk > 0 ? 1 : 0);
         }
 }
 } // namespace hnsw_host
@@ -816,7 +810,7 @@ int32_t hnsw_index_visited_blocks(hnsw_index *idx, const hnsw_search_params *par
     int rc = check_params(idx, params);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(idx->device));
-    *log2_slots = knn_blk_bits(idx, params->ef, params->semantics ? 1 : 0);
+    *log2_slots = knn_blk_bits(idx, knn_shape(idx, params->ef, params->semantics));
     return HNSW_OK;
 }
 
@@ -824,9 +818,8 @@ int32_t hnsw_index_prepare(hnsw_index *idx, const hnsw_search_params *params) {
     int rc = check_params(idx, params);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(idx->device));
-    const int semf = params->semantics ? 1 : 0;
-    (void)knn_blk_bits(idx, params->ef, semf);            // the visited structure of this kernel shape (codes, measurement)
-    (void)resident_queries(idx, params->ef, semf);        // the shape's residency, cached in the handle
+    // the visited structure of this kernel shape (codes, measurement) and its residency, kept in the handle
+    (void)resident_queries(idx, knn_shape(idx, params->ef, params->semantics));
     // the code object of the shape's translation unit
     if ((rc = trial_search(idx, *params))) return rc;
     const std::pair<int, int> key(params->ef, params->semantics);
@@ -843,18 +836,14 @@ int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes) {
 
 int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) {
     if (!idx || !name) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    // (an option that changes the kernel variant or its LDS makes the cached per-shape choices stale: the visited structure's
-    // directory size follows the variant's occupancy, the residency follows the LDS)
-    auto forget_shape_choices = [&]() {
-        for (auto &c : idx->blk_choice) c[0] = c[1] = -1;
-        idx->resident_queries = 0; idx->vt_grow_key = -1;
-    };
-    if (!strcmp(name, "vt_bits")) { idx->vt_bits_override = (int)value; forget_shape_choices(); return HNSW_OK; }
+    // (an option that changes the kernel variant or its LDS makes the per-shape decisions stale -- forget_shapes --: the visited
+    // structure's directory size follows the variant's occupancy, the residency follows the LDS)
+    if (!strcmp(name, "vt_bits")) { idx->vt_bits_override = (int)value; idx->forget_shapes(); return HNSW_OK; }
     if (!strcmp(name, "lds_pad")) { idx->lds_pad = value < 0 ? -1 : (int)std::min<int64_t>(value, 32768); return HNSW_OK; }
     if (!strcmp(name, "byte_rows")) {     // 0: search the fp32 rows even where a byte copy exists; otherwise: use it where it exists
         idx->byte_rows_off = value == 0;
         bind_view(idx);
-        forget_shape_choices();
+        idx->forget_shapes();
         return HNSW_OK;
     }
     if (!strcmp(name, "split_rows")) {    // 0: search the plain fp32 rows even where a split copy exists; -1: ... and free the copy; otherwise: use it where it exists
@@ -866,7 +855,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         idx->split_rows_off = value <= 0;
         idx->split_rows_freed = idx->split_rows_freed || value < 0;
         bind_view(idx);
-        forget_shape_choices();
+        idx->forget_shapes();
         return HNSW_OK;
     }
     if (!strcmp(name, "half_rows")) {     // 1: search the fp16 copy (made now if missing); 0: the fp32 / split rows again, the copy kept; -1: ... and freed
@@ -888,13 +877,13 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
             idx->half_rows_on = false;
         }
         bind_view(idx);
-        forget_shape_choices();
+        idx->forget_shapes();
         return HNSW_OK;
     }
     if (!strcmp(name, "time_kernels")) { idx->time_kernels = value != 0; return HNSW_OK; }
     if (!strcmp(name, "visited_blocks")) {   // -1: measured per kernel shape (default); 0: the tag cache; 1: bitmap blocks wherever the codes can be built
         idx->blk_mode = value < 0 ? -1 : (value ? 1 : 0);
-        forget_shape_choices();               // (the LDS per wave, hence the residency, may differ)
+        idx->forget_shapes();               // (the LDS per wave, hence the residency, may differ)
         return HNSW_OK;
     }
     if (!strcmp(name, "device_fallback_slab_bytes")) {
@@ -1212,10 +1201,7 @@ int32_t hnsw_distance_batch_device(hnsw_index *idx, const float *d_queries, int6
     if (nq < 0 || m < 0 || !d_queries || !d_ids || !d_out) return fail(HNSW_ERR_BAD_ARG, "bad buffers");
     if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
     HIP_TRY(hipSetDevice(idx->device));
-    const int nch = pick_nch(idx->iv.nchunks);
-    hipError_t e = idx->info.metric == HNSW_METRIC_L2
-                       ? dispatch_dist<0>(nch, idx->iv, d_queries, q_stride, nq, d_ids, m, d_out, (hipStream_t)stream)
-                       : dispatch_dist<1>(nch, idx->iv, d_queries, q_stride, nq, d_ids, m, d_out, (hipStream_t)stream);
+    const hipError_t e = launch_distance(idx, d_queries, q_stride, nq, d_ids, m, d_out, (hipStream_t)stream);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "distance kernel launch failed: %s", hipGetErrorString(e));
     return HNSW_OK;
 }

@@ -9,12 +9,58 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace hnsw_host {
 
-// 4-row batches in flight per wave for d <= 128 (NCH = 2): measured on C2: 4 (6 waves/SIMD) >= 3 (7) >= 2 (8): the batch is memory-bound, not occupancy-bound
+// ---- a kernel's compile-time shape from run-time numbers ----------------------------------------------------------------
+// NCH = float4 chunks per lane (pick_nch), RB = 4-row batches in flight per wave, NSLOT = key registers per lane that hold W
+// (pick_nslot / pick_nslot_knn).  Every launch site goes through with_nch / with_nslot / with_metric, which hand the run-time
+// number to a generic lambda as a std::integral_constant, and takes its RB from rows_in_flight.
+
+// RB for d <= 128 (NCH = 2): measured on C2: 4 (6 waves/SIMD) >= 3 (7) >= 2 (8): the batch is memory-bound, not occupancy-bound
 constexpr int RB_NCH2 = 4;
+// RB by NCH, for float32 rows and for the compact rows (bytes: a quarter of the registers per row; halves: half of them, and
+// they take the byte rows' counts: not measured against other counts).  NCH 2 takes RB_NCH2 whatever the row format.
+constexpr int rows_in_flight(int nch, bool compact = false) {
+    return nch == 1 ? 8 : nch == 2 ? RB_NCH2 : nch == 4 ? (compact ? 4 : 2) : nch == 8 ? (compact ? 2 : 1) : 1;
+}
+// rows of 65..256 dimensions (NCH 2 and 4: the shapes with hand-scheduled loops) also have the knn kernel's W in three and six
+// registers (pick_nslot_knn)
+constexpr bool has_odd_nslot(int nch) { return nch == 2 || nch == 4; }
+
+template <int V> using Int = std::integral_constant<int, V>;
+// f(Int<NCH>) for the NCH that pick_nch returned
+template <class F> auto with_nch(int nch, F &&f) {
+    switch (nch) {
+    case 1: return f(Int<1>{});
+    case 2: return f(Int<2>{});
+    case 4: return f(Int<4>{});
+    case 8: return f(Int<8>{});
+    default: return f(Int<16>{});
+    }
+}
+// f(Int<NSLOT>) for nslot out of the kernel family's own list S0, S...; the last of the list also takes what is not listed
+template <int S0, int... S, class F> auto with_nslot(int nslot, F &&f) {
+    if constexpr (sizeof...(S) > 0) { if (nslot != S0) return with_nslot<S...>(nslot, f); }
+    return f(Int<S0>{});
+}
+// ... the knn kernel's list for rows of NCH chunks per lane
+template <int NCH, class F> auto with_nslot_knn(int nslot, F &&f) {
+    if constexpr (has_odd_nslot(NCH)) return with_nslot<1, 2, 3, 4, 6, 8, 16>(nslot, f);
+    else return with_nslot<1, 2, 4, 8, 16>(nslot, f);
+}
+// f(Int<0>) for HNSW_METRIC_L2, f(Int<1>) for the inner product
+template <class F> auto with_metric(int metric, F &&f) { return metric == HNSW_METRIC_L2 ? f(Int<0>{}) : f(Int<1>{}); }
+
+// The knn kernel's variant objects (hnsw_search_variants.hip compiled once per line): X(metric, accept rule, row format -- see
+// variant_full).  build.py's VARIANTS is the same list (tests/test_abi_load.py compares them).
+#define HNSW_SEARCH_VARIANTS(X) \
+    X(0, 0, 0) X(0, 0, 1) X(0, 0, 2) X(0, 0, 3) X(0, 0, 4) \
+    X(0, 1, 0) X(0, 1, 1) X(0, 1, 2) X(0, 1, 3) X(0, 1, 4) \
+    X(1, 0, 0) X(1, 0, 1) X(1, 0, 2) X(1, 0, 3) X(1, 0, 4) \
+    X(1, 1, 0) X(1, 1, 1) X(1, 1, 2) X(1, 1, 3) X(1, 1, 4)
 
 int fail(int code, const char *fmt, ...);
 // the code and message of a failed HIP call
@@ -116,14 +162,14 @@ inline int pick_nslot(int ef) {
     for (int s : {1, 2, 4, 8, 16}) if (ef <= 64 * s) return s;
     return 0;
 }
-// ... of the knn kernel: rows of 65..256 dimensions (NCH 2 and 4: the shapes with hand-scheduled loops) also have W in three
-// (ef 129..192) and six (ef 257..384) registers -- a W window that needs three registers pays for three (pop chain, flag masks,
-// registers), not for four; the other row widths, the builder and the layer operators keep powers of two (pick_nslot)
+// ... of the knn kernel: where has_odd_nslot, W also comes in three (ef 129..192) and six (ef 257..384) registers -- a W window
+// that needs three registers pays for three (pop chain, flag masks, registers), not for four; the other row widths, the builder
+// and the layer operators keep powers of two (pick_nslot)
 inline int pick_nslot_knn(int ef, int nch) {
-    if (nch == 2 || nch == 4) { for (int s : {1, 2, 3, 4, 6, 8, 16}) if (ef <= 64 * s) return s; return 0; }
+    if (has_odd_nslot(nch)) { for (int s : {1, 2, 3, 4, 6, 8, 16}) if (ef <= 64 * s) return s; return 0; }
     return pick_nslot(ef);
 }
-// index of a slot count in per-shape tables (hnsw_index::blk_choice)
+// index of a slot count in per-shape tables (hnsw_index::shape)
 inline int slot_class(int nslot) {
     switch (nslot) { case 1: return 0; case 2: return 1; case 3: return 2; case 4: return 3; case 6: return 4; case 8: return 5; default: return 6; }
 }
@@ -163,7 +209,19 @@ struct hnsw_index {
     // yet, 1 built, -1 cannot be built (no upper layer to derive an order from)
     int lcode_state = 0;
     int blk_mode = -1;                   // option "visited_blocks": -1 automatic (measured per kernel shape on the index's own vectors), 0 never, 1 always
-    int blk_choice[7][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};   // [slot_class(NSLOT)][accept rule]: -1 undecided, 0 tag cache, else log2 of the block slots
+    // What the handle decided for each shape of the knn kernel, [slot_class(NSLOT)][accept rule]; everything else a shape depends
+    // on (n, row format, options "vt_bits" / "visited_blocks") forgets them when it changes (forget_shapes)
+    struct ShapeChoice {
+        int blk = -1;                    // the visited structure (knn_blk_bits): -1 undecided, 0 tag cache, else log2 of the block slots
+        int vt_bits = 0;                 // log2 tags of the grown tag cache (knn_vt_bits), 0 = not computed yet
+        int per_cu = -1;                 // waves of the kernel one CU holds when each asks for `lds` bytes (resident_queries): -1 not
+        size_t lds = 0;                  //  asked yet, 0 unknown.  lds is compared: the blocks can be lost to a failed allocation
+    } shape[hnsw_host::SLOT_CLASSES][2];
+    // keep_visited: all but the visited-structure choices (what survives an insert that kept the row format)
+    void forget_shapes(bool keep_visited = false) {
+        for (auto &c : shape) for (ShapeChoice &s : c) s = ShapeChoice{keep_visited ? s.blk : -1};
+    }
+    int cus = 0;                         // the device's CUs (0 = not read yet)
     hnsw_host::BatchBufs scratch;                            // scratch for the host-buffer entry points
     uint32_t *hFlag = nullptr, *hFlagDev = nullptr;          // the same word in pinned host memory (zero-copy calls) and its device address
     char *hSmall = nullptr, *hSmallDev = nullptr;            // page-locked block for small host-buffer calls (hnsw_search_batch: queries, ids, distances, counters)
@@ -175,9 +233,6 @@ struct hnsw_index {
     std::vector<hnsw_request *> free_requests;               // finished requests keep their buffers for the next submit
     std::vector<hnsw_request *> all_requests;                // every request ever created (released with the index)
     int live_requests = 0, next_stream = 0;
-    int64_t resident_queries = 0;        // how many one-wave workgroups of the search kernel the chip holds (0 = not measured yet)
-    int resident_per_cu = 0, cus = 0;    // ... per CU, and the CUs
-    int resident_nslot = 0; size_t resident_lds = 0;   // ... for this kernel variant / LDS size
     bool time_kernels = false;           // option "time_kernels": event triples around the launches of each device-entry call
     std::vector<hipEvent_t> tev;         // [3 * recorded calls]: before the pre-pass, before the search kernel, after it
     size_t tev_used = 0;
@@ -186,9 +241,8 @@ struct hnsw_index {
     // stream is ordered, so the block is free again when the next call on that stream needs it)
     struct OrderScratch { hipStream_t st; void *p; size_t bytes; };
     std::vector<OrderScratch> order_scratch;
-    int order_mode = -1;                 // option "order_queries": -1 automatic (batches larger than half of resident_queries), 0 never, 1 always
+    int order_mode = -1;                 // option "order_queries": -1 automatic (batches larger than half of what the chip holds: resident_queries), 0 never, 1 always
     int vt_bits_override = 0;
-    int vt_grow_key = -1, vt_grow_bits = 0;   // knn_vt_bits' cached choice for (kernel variant, base size)
     int lds_pad = -1;                    // option "lds_pad": extra LDS bytes per search wave (-1 = balanced_lds_pad's choice)
     int scan_slabs = 0;                  // option "scan_slabs": row slabs of the exact scan (0 = scan_slab_rows' choice)
     std::vector<std::pair<int, int>> prepared;   // (ef, accept rule) of every hnsw_index_prepare: what hnsw_index_save writes down

@@ -131,52 +131,23 @@ namespace {
 
 using hnsw_dev::LayerSearchArgs;
 
-template <int NCH, int RB, int NSLOT, int METRIC>
-hipError_t launch_layer(const IndexView &iv, const LayerSearchArgs &a) {
-    const size_t lds = hnsw_dev::wave_lds_words(a.vt_bits) * sizeof(uint32_t);
-    hipLaunchKernelGGL((hnsw_dev::hnsw_layer_search_kernel<NCH, RB, NSLOT, METRIC>), dim3((unsigned)a.nq),
-                       dim3(64), lds, nullptr, iv, a);
-    return hipGetLastError();
-}
-template <int NCH, int RB, int METRIC>
-hipError_t layer_slot(int nslot, const IndexView &iv, const LayerSearchArgs &a) {
-    switch (nslot) {
-    case 1: return launch_layer<NCH, RB, 1, METRIC>(iv, a);
-    case 2: return launch_layer<NCH, RB, 2, METRIC>(iv, a);
-    case 4: return launch_layer<NCH, RB, 4, METRIC>(iv, a);
-    case 8: return launch_layer<NCH, RB, 8, METRIC>(iv, a);
-    default: return launch_layer<NCH, RB, 16, METRIC>(iv, a);
-    }
-}
-template <int METRIC>
-hipError_t layer_nch(int nch, int nslot, const IndexView &iv, const LayerSearchArgs &a) {
-    switch (nch) {
-    case 1: return layer_slot<1, 8, METRIC>(nslot, iv, a);
-    case 2: return layer_slot<2, RB_NCH2, METRIC>(nslot, iv, a);
-    case 4: return layer_slot<4, 2, METRIC>(nslot, iv, a);
-    case 8: return layer_slot<8, 1, METRIC>(nslot, iv, a);
-    default: return layer_slot<16, 1, METRIC>(nslot, iv, a);
-    }
-}
 int launch_layer_args(hnsw_index *idx, const LayerSearchArgs &a) {
-    const int nch = pick_nch(idx->iv.nchunks), nslot = pick_nslot(a.ef);
-    hipError_t e = idx->info.metric == HNSW_METRIC_L2 ? layer_nch<0>(nch, nslot, idx->iv, a) : layer_nch<1>(nch, nslot, idx->iv, a);
+    const size_t lds = hnsw_dev::wave_lds_words(a.vt_bits) * sizeof(uint32_t);
+    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(pick_nch(idx->iv.nchunks), [&](auto NCH) { with_nslot<1, 2, 4, 8, 16>(pick_nslot(a.ef), [&](auto NSLOT) {
+        hipLaunchKernelGGL((hnsw_dev::hnsw_layer_search_kernel<NCH, rows_in_flight(NCH), NSLOT, METRIC>), dim3((unsigned)a.nq), dim3(64), lds, nullptr, idx->iv, a);
+    }); }); });
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "layer search kernel launch failed: %s", hipGetErrorString(e));
     return HNSW_OK;
 }
 
-template <int METRIC>
-hipError_t one_nch(int nch, const IndexView &iv, const float *Q, int64_t qs, int64_t nq, int32_t layer,
-                   const int32_t *start, int32_t *out_node, float *out_dist) {
+hipError_t launch_search_one(const hnsw_index *idx, const float *Q, int64_t qs, int64_t nq, int32_t layer, const int32_t *start, int32_t *out_node,
+                             float *out_dist) {
     const size_t lds = hnsw_dev::wave_lds_words(4) * sizeof(uint32_t);
-    dim3 grid((unsigned)nq), block(64);
-    switch (nch) {
-    case 1: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<1, 8, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<2, RB_NCH2, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
-    case 4: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<4, 2, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
-    case 8: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<8, 1, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
-    default: hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<16, 1, METRIC>), grid, block, lds, nullptr, iv, Q, qs, nq, layer, start, out_node, out_dist); break;
-    }
+    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(pick_nch(idx->iv.nchunks), [&](auto NCH) {
+        hipLaunchKernelGGL((hnsw_dev::hnsw_search_one_kernel<NCH, rows_in_flight(NCH), METRIC>), dim3((unsigned)nq), dim3(64), lds, nullptr,
+                           idx->iv, Q, qs, nq, layer, start, out_node, out_dist);
+    }); });
     return hipGetLastError();
 }
 
@@ -290,10 +261,8 @@ int32_t hnsw_search_one_batch(hnsw_index *idx, int32_t layer, const float *targe
         return rc;
     HIP_TRY(hipMemcpy(idx->scratch.q.p, targets, qbytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(idx->scratch.nd.p, st.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
-    const int nch = pick_nch(idx->iv.nchunks);
-    hipError_t e = idx->info.metric == HNSW_METRIC_L2
-                       ? one_nch<0>(nch, idx->iv, (const float *)idx->scratch.q.p, t_stride, nq, layer, (const int32_t *)idx->scratch.nd.p, (int32_t *)idx->scratch.ids.p, (float *)idx->scratch.dist.p)
-                       : one_nch<1>(nch, idx->iv, (const float *)idx->scratch.q.p, t_stride, nq, layer, (const int32_t *)idx->scratch.nd.p, (int32_t *)idx->scratch.ids.p, (float *)idx->scratch.dist.p);
+    const hipError_t e = launch_search_one(idx, (const float *)idx->scratch.q.p, t_stride, nq, layer, (const int32_t *)idx->scratch.nd.p, (int32_t *)idx->scratch.ids.p,
+                                           (float *)idx->scratch.dist.p);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "search_one kernel launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipDeviceSynchronize());
     std::vector<int32_t> nodes((size_t)nq);

@@ -81,31 +81,26 @@ order_bucket_kernel(const uint32_t *sortkey, int32_t n, int32_t *order) {
     }
 }
 
-template <int METRIC, int ROWS>
-hipError_t launch_descent_rows(int nch, const IndexView &iv, const float *Q, int64_t qs, int64_t nq, int32_t to_layer, int32_t *entry, uint32_t *key,
-                               uint32_t *nd, uint32_t *sortkey, int32_t *index, float *stage, hipStream_t st) {
+// The descent reads what the knn kernel reads on the upper layers (row_format: hnsw_index_info.row_format; split rows serve
+// layer 0 only).  The greedy descent keeps no W in registers, so what a compact row (bytes, halves) saves goes to rows in flight
+// at NCH 2 as well: 8 there, where rows_in_flight keeps the knn loop's RB_NCH2 for every row format.
+constexpr int descent_rows_in_flight(int nch, bool compact) { return compact && nch == 2 ? 8 : rows_in_flight(nch, compact); }
+hipError_t launch_descent(const hnsw_index *idx, int row_format, const float *Q, int64_t qs, int64_t nq, int32_t to_layer, int32_t *entry,
+                          uint32_t *key, uint32_t *nd, uint32_t *sortkey, int32_t *index, float *stage, hipStream_t st) {
     const size_t lds = hnsw_dev::wave_lds_words(4) * sizeof(uint32_t);
-    dim3 grid((unsigned)nq), block(64);
-    constexpr bool B = ROWS == 2 || ROWS == 4;   // byte / half rows: a quarter / half of the registers per row in flight
-    switch (nch) {
-    case 1: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<1, 8, METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<2, (B ? 8 : RB_NCH2), METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
-    case 4: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<4, (B ? 4 : 2), METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
-    case 8: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<8, (B ? 2 : 1), METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
-    default: hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<16, 1, METRIC, ROWS>), grid, block, lds, st, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage); break;
+    auto rows = [&](auto ROWS) {      // the kernel's ROWS: 2 bytes, 4 halves, -1 float32
+        constexpr bool compact = ROWS == 2 || ROWS == 4;
+        with_metric(idx->info.metric, [&](auto METRIC) { with_nch(pick_nch(idx->iv.nchunks), [&](auto NCH) {
+            hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<NCH, descent_rows_in_flight(NCH, compact), METRIC, ROWS>), dim3((unsigned)nq), dim3(64), lds, st,
+                               idx->iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage);
+        }); });
+    };
+    switch (row_format) {
+    case HNSW_ROWS_BYTES: rows(Int<2>{}); break;
+    case HNSW_ROWS_HALF: rows(Int<4>{}); break;
+    default: rows(Int<-1>{}); break;
     }
     return hipGetLastError();
-}
-// the descent reads what the knn kernel reads on the upper layers (row_format: hnsw_index_info.row_format; split rows serve
-// layer 0 only)
-template <int METRIC>
-hipError_t launch_descent(int row_format, int nch, const IndexView &iv, const float *Q, int64_t qs, int64_t nq, int32_t to_layer, int32_t *entry,
-                          uint32_t *key, uint32_t *nd, uint32_t *sortkey, int32_t *index, float *stage, hipStream_t st) {
-    switch (row_format) {
-    case HNSW_ROWS_BYTES: return launch_descent_rows<METRIC, 2>(nch, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage, st);
-    case HNSW_ROWS_HALF: return launch_descent_rows<METRIC, 4>(nch, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage, st);
-    default: return launch_descent_rows<METRIC, -1>(nch, iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage, st);
-    }
 }
 } // namespace
 
@@ -114,15 +109,12 @@ namespace hnsw_host {
 int descent_entries(::hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride, int32_t to_layer, int32_t *d_entry,
                     uint32_t *d_scratch, hipStream_t st) {
     if (nq <= 0) return HNSW_OK;
-    const int nch = pick_nch(idx->iv.nchunks);
     uint32_t *key = d_scratch, *nd = d_scratch + nq, *sortkey = d_scratch + 2 * nq;
     int32_t *index = (int32_t *)(d_scratch + 3 * nq);
     // (the locality codes' descents: over X whatever option half_rows says -- byte rows are X itself -- so that the codes do not
     // depend on it)
     const int rows = idx->info.row_format == HNSW_ROWS_BYTES ? HNSW_ROWS_BYTES : HNSW_ROWS_F32;
-    const hipError_t e = idx->info.metric == HNSW_METRIC_L2
-        ? launch_descent<0>(rows, nch, idx->iv, d_queries, q_stride, nq, to_layer, d_entry, key, nd, sortkey, index, nullptr, st)
-        : launch_descent<1>(rows, nch, idx->iv, d_queries, q_stride, nq, to_layer, d_entry, key, nd, sortkey, index, nullptr, st);
+    const hipError_t e = launch_descent(idx, rows, d_queries, q_stride, nq, to_layer, d_entry, key, nd, sortkey, index, nullptr, st);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "descent launch failed: %s", hipGetErrorString(e));
     return HNSW_OK;
 }
@@ -162,9 +154,7 @@ int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, i
     uint32_t *sortkey = (uint32_t *)(base + 3 * slot), *sorted = (uint32_t *)(base + 4 * slot);
     int32_t *index = (int32_t *)(base + 5 * slot), *order = (int32_t *)(base + 6 * slot);
     void *temp = base + 7 * slot;
-    const int nch = pick_nch(idx->iv.nchunks);
-    e = idx->info.metric == HNSW_METRIC_L2 ? launch_descent<0>(idx->info.row_format, nch, idx->iv, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st)
-                                           : launch_descent<1>(idx->info.row_format, nch, idx->iv, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st);
+    e = launch_descent(idx, idx->info.row_format, d_queries, q_stride, nq, to_layer, entry, key, nd, sortkey, index, d_stage, st);
     if (e == hipSuccess) {
         if (nq <= 16 * ORDER_THREADS) {
             static_assert(ORDER_BUCKETS == 2 * ORDER_THREADS, "two counters per thread in the scan");

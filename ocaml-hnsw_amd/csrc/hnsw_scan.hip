@@ -270,16 +270,10 @@ namespace hnsw_host {
 using hnsw_dev::IndexView;
 using hnsw_dev::ScanArgs;
 
-template <int METRIC>
-hipError_t dispatch_scan(int nch, dim3 grid, const IndexView &iv, const ScanArgs &a, hipStream_t st) {
-    const dim3 block(64 * hnsw_dev::SCAN_WAVES);
-    switch (nch) {
-    case 1: hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<1, METRIC>), grid, block, 0, st, iv, a); break;
-    case 2: hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<2, METRIC>), grid, block, 0, st, iv, a); break;
-    case 4: hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<4, METRIC>), grid, block, 0, st, iv, a); break;
-    case 8: hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<8, METRIC>), grid, block, 0, st, iv, a); break;
-    default: hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<16, METRIC>), grid, block, 0, st, iv, a); break;
-    }
+hipError_t launch_scan(int metric, int nch, dim3 grid, const IndexView &iv, const ScanArgs &a, hipStream_t st) {
+    with_metric(metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {
+        hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<NCH, METRIC>), grid, dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a);
+    }); });
     return hipGetLastError();
 }
 
@@ -315,7 +309,6 @@ int scan_search(hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hip
     constexpr int64_t SCAN_SCRATCH = 256ll << 20;
     const IndexView &iv = idx->iv;
     const int nch = pick_nch(iv.nchunks), T = hnsw_dev::scan_tile(nch);
-    const bool l2 = idx->info.metric == HNSW_METRIC_L2;
     int64_t piece = std::min<int64_t>(b.nq, 16384);
     int64_t slab_rows = 0, slabs = 0;
     for (;;) {      // (a smaller piece has fewer tiles and may be cut into more slabs: settle on a piece that fits)
@@ -331,11 +324,12 @@ int scan_search(hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hip
         ScanArgs a{b.Q + q0 * b.q_stride, b.q_stride, nq, k, (int32_t)slabs, slab_rows, (uint64_t *)idx->scratch.scan.p};
         if (slabs > 0) {
             const dim3 grid((unsigned)((nq + T - 1) / T), (unsigned)((slabs + hnsw_dev::SCAN_WAVES - 1) / hnsw_dev::SCAN_WAVES));
-            const hipError_t e = l2 ? dispatch_scan<0>(nch, grid, iv, a, st) : dispatch_scan<1>(nch, grid, iv, a, st);
+            const hipError_t e = launch_scan(idx->info.metric, nch, grid, iv, a, st);
             if (e != hipSuccess) return fail(HNSW_ERR_HIP, "scan kernel launch failed: %s", hipGetErrorString(e));
         }
-        if (l2) hipLaunchKernelGGL(hnsw_dev::hnsw_scan_merge_kernel<0>, dim3((unsigned)nq), dim3(256), 0, st, a.lists, a.n_slabs, k, fill, iv.id_base, b.ids + q0 * k, b.dist + q0 * k);
-        else hipLaunchKernelGGL(hnsw_dev::hnsw_scan_merge_kernel<1>, dim3((unsigned)nq), dim3(256), 0, st, a.lists, a.n_slabs, k, fill, iv.id_base, b.ids + q0 * k, b.dist + q0 * k);
+        with_metric(idx->info.metric, [&](auto METRIC) {
+            hipLaunchKernelGGL(hnsw_dev::hnsw_scan_merge_kernel<METRIC>, dim3((unsigned)nq), dim3(256), 0, st, a.lists, a.n_slabs, k, fill, iv.id_base, b.ids + q0 * k, b.dist + q0 * k);
+        });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(HNSW_ERR_HIP, "scan merge kernel launch failed: %s", hipGetErrorString(e));
     }

@@ -18,11 +18,8 @@ namespace {
 
 constexpr int M_ = HNSW_V_METRIC, S_ = HNSW_V_SEMF;
 constexpr int F_ = HNSW_V_FULL;
-// 4-row batches in flight per wave: a byte row is a quarter of the registers; a half row (F_ 4) half of them, and it takes
-// the byte rows' counts (twice the rows in flight of fp32 rows for the same registers: not measured against other counts);
-// for d <= 128 (NCH = 2) every row format takes RB_NCH2
+// the compact rows (bytes, halves) take rows_in_flight's other column
 constexpr bool COMPACT_ = F_ == 2 || F_ == 4;
-constexpr int RB1 = 8, RB2 = hnsw_host::RB_NCH2, RB4 = COMPACT_ ? 4 : 2, RB8 = COMPACT_ ? 2 : 1, RB16 = 1;
 
 template <int NCH, int RB, int NSLOT>
 hipError_t launch_one(const IndexView &iv, const SearchArgs &a, hipStream_t st) {
@@ -55,30 +52,11 @@ int occupancy_one(size_t lds, int blk) {
     return nb;
 }
 
-template <int NCH, int RB>
-hipError_t launch_slot(int nslot, const IndexView &iv, const SearchArgs &a, hipStream_t st) {
-    switch (nslot) {
-    case 1: return launch_one<NCH, RB, 1>(iv, a, st);
-    case 2: return launch_one<NCH, RB, 2>(iv, a, st);
-    case 4: return launch_one<NCH, RB, 4>(iv, a, st);
-    case 8: return launch_one<NCH, RB, 8>(iv, a, st);
-    // three and six registers: rows of 65..256 dimensions only (pick_nslot_knn never asks for them elsewhere)
-    case 3: if constexpr (NCH == 2 || NCH == 4) return launch_one<NCH, RB, 3>(iv, a, st); else return hipErrorInvalidValue;
-    case 6: if constexpr (NCH == 2 || NCH == 4) return launch_one<NCH, RB, 6>(iv, a, st); else return hipErrorInvalidValue;
-    default: return launch_one<NCH, RB, 16>(iv, a, st);
-    }
-}
-template <int NCH, int RB>
-int occupancy_slot(int nslot, size_t lds, int blk) {
-    switch (nslot) {
-    case 1: return occupancy_one<NCH, RB, 1>(lds, blk);
-    case 2: return occupancy_one<NCH, RB, 2>(lds, blk);
-    case 4: return occupancy_one<NCH, RB, 4>(lds, blk);
-    case 8: return occupancy_one<NCH, RB, 8>(lds, blk);
-    case 3: if constexpr (NCH == 2 || NCH == 4) return occupancy_one<NCH, RB, 3>(lds, blk); else return 0;
-    case 6: if constexpr (NCH == 2 || NCH == 4) return occupancy_one<NCH, RB, 6>(lds, blk); else return 0;
-    default: return occupancy_one<NCH, RB, 16>(lds, blk);
-    }
+// f(Int<NCH>, Int<RB>, Int<NSLOT>) for this unit's kernel of the shape (nch, nslot)
+template <class F> auto with_shape(int nch, int nslot, F &&f) {
+    return hnsw_host::with_nch(nch, [&](auto NCH) {
+        return hnsw_host::with_nslot_knn<NCH>(nslot, [&](auto NSLOT) { return f(NCH, hnsw_host::Int<hnsw_host::rows_in_flight(NCH, COMPACT_)>{}, NSLOT); });
+    });
 }
 
 } // namespace
@@ -89,22 +67,10 @@ int occupancy_slot(int nslot, size_t lds, int blk) {
 namespace hnsw_host {
 
 hipError_t HNSW_V_CAT(search_launch_, HNSW_V_METRIC, HNSW_V_SEMF, HNSW_V_FULL)(int nch, int nslot, const IndexView &iv, const SearchArgs &a, hipStream_t st) {
-    switch (nch) {
-    case 1: return launch_slot<1, RB1>(nslot, iv, a, st);
-    case 2: return launch_slot<2, RB2>(nslot, iv, a, st);
-    case 4: return launch_slot<4, RB4>(nslot, iv, a, st);
-    case 8: return launch_slot<8, RB8>(nslot, iv, a, st);
-    default: return launch_slot<16, RB16>(nslot, iv, a, st);
-    }
+    return with_shape(nch, nslot, [&](auto NCH, auto RB, auto NSLOT) { return launch_one<NCH, RB, NSLOT>(iv, a, st); });
 }
 int HNSW_V_CAT(search_occupancy_, HNSW_V_METRIC, HNSW_V_SEMF, HNSW_V_FULL)(int nch, int nslot, size_t lds, int blk) {
-    switch (nch) {
-    case 1: return occupancy_slot<1, RB1>(nslot, lds, blk);
-    case 2: return occupancy_slot<2, RB2>(nslot, lds, blk);
-    case 4: return occupancy_slot<4, RB4>(nslot, lds, blk);
-    case 8: return occupancy_slot<8, RB8>(nslot, lds, blk);
-    default: return occupancy_slot<16, RB16>(nslot, lds, blk);
-    }
+    return with_shape(nch, nslot, [&](auto NCH, auto RB, auto NSLOT) { return occupancy_one<NCH, RB, NSLOT>(lds, blk); });
 }
 
 } // namespace hnsw_host

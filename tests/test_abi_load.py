@@ -50,6 +50,21 @@ def test_ctypes_mirror_declares_every_argument_list(H):
         assert len(fn.argtypes) == n_args, "%s: %d argtypes, the header declares %d arguments" % (name, len(fn.argtypes), n_args)
 
 
+def test_variant_list_matches_build_script():
+    """The knn kernel's variant objects are listed once for the compiler (HNSW_SEARCH_VARIANTS in csrc/hnsw_internal.h: the
+    declarations and the host's table come from it) and once for the build (VARIANTS in build.py: one object per entry): a
+    variant in one list and not the other is an undefined symbol at best, a row format that is never picked at worst."""
+    import __graft_entry__ as ge
+    src = open(os.path.join(ROOT, "ocaml-hnsw_amd", "csrc", "hnsw_internal.h")).read()
+    body = re.search(r"#define HNSW_SEARCH_VARIANTS\(X\)((?:.*\\\n)*.*)\n", src).group(1)
+    listed = [tuple(int(v) for v in t) for t in re.findall(r"X\((\d+), (\d+), (\d+)\)", body)]
+    assert len(listed) == len(set(listed)) >= 20, listed
+    assert sorted(listed) == sorted(ge._load_build_module().VARIANTS)
+    # nothing else declares a variant: the macro is the only place that spells the triples out
+    capi = open(os.path.join(ROOT, "ocaml-hnsw_amd", "csrc", "hnsw_capi.hip")).read()
+    assert not re.search(r"search_(launch|occupancy)_\d", capi)
+
+
 def test_no_torch_types_in_abi():
     hdr = open(os.path.join(ROOT, "include", "hnsw_mi355x.h")).read()
     assert "torch" not in hdr and "at::" not in hdr and "std::" not in hdr
