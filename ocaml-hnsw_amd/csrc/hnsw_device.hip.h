@@ -1141,10 +1141,8 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
     const int lane = cx.lane;
     const bool full_rows = ROWS < 0 ? iv.nchunks == 16 * NCH : ROWS == 1;
 #ifndef HNSW_PHASE_TIMING
-    // The hand-scheduled loops (hnsw_hop_asm.hip.h: HopLoop<NCH, NSLOT, METRIC, ROWS, SEM, BLK>, one instantiation per shape from the
-    // generated table hnsw_hop_instances.inc), same results.  Shapes: byte rows and a byte-valued query, or float32 rows (full,
-    // ragged, split), of 65..128 (NCH 2) or 129..256 (NCH 4) dimensions; W in 1, 2, 3, 4, 6 or 8 registers; either metric, either
-    // rule; Visited as the tag cache or (W in three or more registers; not the NCH 4 byte rows) as bitmap blocks.
+    // The hand-scheduled loops (hnsw_hop_asm.hip.h: HopLoop<NCH, NSLOT, METRIC, ROWS, SEM, BLK>, one instantiation per shape of the
+    // table hnsw_hop_instances.inc, which says what shapes there are), same results.
     // (The blocks form the byte offset (id + 1) * S0 * 4 + lane * 4 of an adjacency row in 32 bits, one row ahead of the node
     // they fetch: the row AFTER the last node's must still be below 2^32 bytes whatever S0 is; and they restore EXEC with
     // s_mov_b64 exec, -1: they are entered with all 64 lanes on -- the kernel runs one full wave per query and reaches this

@@ -1,16 +1,13 @@
 // hnsw_hop_asm.hip.h -- the layer-0 loop of Ohnsw.search_k (lib/ohnsw.ml:543-588) and the descent above it
 // (Ohnsw.search_one, :492-508), written instruction by instruction for gfx950.
 //
-// Shapes: rows of 65..128 dimensions (NCH = 2) -- and, for byte rows and for full / ragged float32 rows, of 129..256 (NCH = 4:
-// the rounds with twice the loads and arithmetic per batch) --, ef <= 64 / 65..128 / 129..256 / 257..512 (W in one / two / four / eight key
-// registers per lane -- and three / six for ef 129..192 / 257..384; hnsw_hop_loop.inc has one body for one register, one for two
-// and one for three and more, included once per shape by the generated table hnsw_hop_instances.inc; what depends on the slot
-// count above two is generated too: hnsw_hop_slots.inc):
-//   * byte rows and a byte-valued query (exact integer arithmetic, see hop_round), L2 -- the headline shape; its descent too --
-//     and inner product;
-//   * float32 rows, L2 and inner product: full, ragged and split rows ("The same loops over FLOAT32 rows" below);
-//   * each of them for the Ohnsw accept rule and for the functor rule (Hnsw_algo.Search: the loop then leaves a hop when an
-//     entry would enter the tie set, see HNSW_LOOP_SEM in hnsw_hop_loop.inc and search_layer).
+// Shapes: the table hnsw_hop_instances.inc (included below) says which there are: rows of 65..128 and of 129..256 dimensions
+// (NCH 2 / 4); W in one, two, three, four, six or eight key registers per lane (hnsw_hop_loop.inc has one assembler text for one
+// register, one for two and one for three and more, inside one frame of constants and operand lists; what depends on the slot
+// count above two is generated: hnsw_hop_slots.inc); byte rows with a byte-valued query (exact integer arithmetic, see
+// hop_round; the headline shape, its descent too) and float32 rows full, ragged and split ("The same loops over FLOAT32 rows"
+// below); L2 and inner product; the Ohnsw accept rule and the functor rule (Hnsw_algo.Search: the loop then leaves a hop when
+// an entry would enter the tie set, see HNSW_LOOP_SEM in hnsw_hop_loop.inc and search_layer).
 // Everything else takes search_layer's C++ loop; the blocks compute exactly what that loop computes (same pops, same
 // evaluations, same insertions, same counters), so the two are interchangeable and tests/ compare both against the oracle.
 //
@@ -81,7 +78,7 @@ namespace hnsw_dev {
 #define HNSW_ASM_ALIGN HNSW_ASM_ALIGN_K(HNSW_ASM_ALIGN_PAD)
 
 // One hand-scheduled layer-0 loop per shape: an explicit specialisation of this template (hnsw_hop_loop.inc, instantiated by the
-// generated table hnsw_hop_instances.inc) with available = true and
+// table hnsw_hop_instances.inc) with available = true and
 //     static bool run(iv, w, cx, rs, qv, n_dist, n_hops, status [, maxhops])
 // which runs the layer-0 search to completion (false) or -- functor rule, SEM 1 -- until an entry would enter the tie set (true:
 // the hop is finished by search_layer from `rs`).  On entry W holds the start node (unexpanded) and the visited set knows it.
@@ -961,13 +958,13 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
 #define HNSW_RANK_GENERAL_SLOT(HS, LS)                              \
     "v_cmp_gt_u32_e32 vcc, %[kd], " HS "\n\t"                       \
     "s_bcnt1_i32_b64 %[t], vcc\n\t"                                 \
-    "s_add_u32 %[P], %[P], %[t]\n\t"                                \
+    "s_add_u32 %[p], %[p], %[t]\n\t"                                \
     "v_cmp_eq_u32_e64 %[um0], %[kd], " HS "\n\t"                    \
     "v_and_b32_e32 %[t0], 0x7fffffff, " LS "\n\t"                   \
     "v_cmp_gt_u32_e32 vcc, %[klo], %[t0]\n\t"                       \
     "s_and_b64 vcc, vcc, %[um0]\n\t"                                \
     "s_bcnt1_i32_b64 %[t], vcc\n\t"                                 \
-    "s_add_u32 %[P], %[P], %[t]\n\t"                                \
+    "s_add_u32 %[p], %[p], %[t]\n\t"                                \
     "v_cmp_eq_u32_e32 vcc, %[klo], %[t0]\n\t"                       \
     "s_and_b64 vcc, vcc, %[um0]\n\t"                                \
     "s_or_b64 %[um1], %[um1], vcc\n\t"
@@ -1120,7 +1117,7 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
     "s_branch 19b\n"                                                                                                        \
     /* rare: a member of W at exactly this distance: rank over all four slots, ids decide; the node itself in W: ignored */ \
     "14:\n\t"                                                                                                               \
-    "s_mov_b32 %[P], 0\n\t"                                                                                                 \
+    "s_mov_b32 %[p], 0\n\t"                                                                                                 \
     "s_mov_b64 %[um1], 0\n\t"                                                                                               \
     HNSW_RANK_GENERAL_SLOT("%[h0]", "%[l0]")                                                                               \
     HNSW_RANK_GENERAL_SLOT("%[h1]", "%[l1]")                                                                               \
@@ -1132,12 +1129,12 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
     "s_cmp_eq_u32 %[nw], %[wmax]\n\t"                                                                                       \
     "s_cbranch_scc1 154f\n"                                                                                                 \
     "141:\n\t"                                                                                                              \
-    "s_and_b32 m0, %[P], 63\n\t"                                                                                            \
-    "s_cmp_ge_u32 %[P], 192\n\t"                                                                                            \
+    "s_and_b32 m0, %[p], 63\n\t"                                                                                            \
+    "s_cmp_ge_u32 %[p], 192\n\t"                                                                                            \
     "s_cbranch_scc1 831b\n\t"                                                                                               \
-    "s_cmp_ge_u32 %[P], 128\n\t"                                                                                            \
+    "s_cmp_ge_u32 %[p], 128\n\t"                                                                                            \
     "s_cbranch_scc1 821b\n\t"                                                                                               \
-    "s_cmp_ge_u32 %[P], 64\n\t"                                                                                             \
+    "s_cmp_ge_u32 %[p], 64\n\t"                                                                                             \
     "s_cbranch_scc1 811b\n\t"                                                                                               \
     "s_branch 801b\n"                                                                                                       \
     /* rare: the entry that falls off is at the new maximum's distance (see the two-slot loop); one copy per way back */     \
@@ -1502,12 +1499,9 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p) {
 
 // =====================================================================================================================
 // The instantiations: HopLoop<NCH, NSLOT, METRIC, ROWS, SEM, BLK>::run, one explicit specialisation per shape, each made by
-// including hnsw_hop_loop.inc with the HNSW_LOOP_* macros set.  The table is GENERATED (tools/gen_hop_slots.py ->
-// hnsw_hop_instances.inc): row families bytes (NCH 2) / bytes of 129..256 dimensions (NCH 4) / float32 full, ragged, split
-// (NCH 2 and 4) x metric x accept rule x W in 1, 2, 3, 4, 6, 8 registers x visited structure (bitmap blocks: three or more
-// registers, not the NCH 4 byte rows), and in a translation unit of
-// hnsw_search_variants.hip only the shapes of that unit's (metric, rule, row format).  search_layer asks
-// HopLoop<...>::available and calls run(); a shape without an instantiation (the primary template) keeps the C++ loop.
+// including hnsw_hop_loop.inc with the HNSW_LOOP_* macros set.  Which shapes: the table says, and in a translation unit of
+// hnsw_search_variants.hip only those of that unit's (metric, rule, row format).  search_layer asks HopLoop<...>::available and
+// calls run(); a shape without an instantiation (the primary template) keeps the C++ loop.
 // =====================================================================================================================
 #include "hnsw_hop_instances.inc"
 

@@ -1,2174 +1,98 @@
-// hnsw_hop_instances.inc -- GENERATED by tools/gen_hop_slots.py (do not edit; `python tools/gen_hop_slots.py` rewrites it,
-// tests/test_asm_hazards.py checks that it is current): the instantiations HopLoop<NCH, NSLOT, METRIC, ROWS, SEM, BLK> of the
-// hand-scheduled layer-0 loop, one stanza each, grouped by the translation unit that can reach them: the units of
-// hnsw_search_variants.hip are compiled per (metric, accept rule, row format) and define HNSW_V_METRIC / HNSW_V_SEMF /
-// HNSW_V_FULL; every other unit (the builder, the layer operators: row format decided at run time) takes search_layer's
-// C++ loop and instantiates nothing.
-#if defined(HNSW_HOP_ALL_INSTANCES)      /* (tests: every instantiation in one preprocessed unit) */
-#define HNSW_HOP_UNIT(M, S, R) 1
-#elif defined(HNSW_V_METRIC)
-#define HNSW_HOP_UNIT(M, S, R) (HNSW_V_METRIC == (M) && HNSW_V_SEMF == (S) && HNSW_V_FULL == (R))
-#else
-#define HNSW_HOP_UNIT(M, S, R) 0
-#endif
-#if HNSW_HOP_UNIT(0, 0, 2)
+// hnsw_hop_instances.inc -- WHICH shapes have a hand-scheduled layer-0 loop: the explicit specialisations
+// HopLoop<NCH, NSLOT, METRIC, ROWS, SEM, BLK> (hnsw_hop_asm.hip.h), one stanza each, written by hand; every other shape is the
+// primary template and keeps search_layer's C++ loop.  This table is the statement: comments elsewhere point here.
+//
+// A translation unit of hnsw_search_variants.hip is compiled per (metric, accept rule, row format), and hnsw_hop_loop.inc takes
+// METRIC, SEM and ROWS from that unit's HNSW_V_METRIC / HNSW_V_SEMF / HNSW_V_FULL: a stanza states what varies inside a unit.
+//   NCH    2: rows of 65..128 dimensions; 4: rows of 129..256
+//   NSLOT  1, 2, 3, 4, 6, 8 key registers per lane that hold W (ef <= 64 / 128 / 192 / 256 / 384 / 512)
+//   BLK    1: Visited as bitmap blocks instead of the tag cache (left out: 0) -- W in three or more registers only, and not the
+//          byte rows of 129..256 dimensions
+// Per unit: byte rows (HNSW_V_FULL 2) 16 shapes; float32 rows ragged / full / split (0 / 1 / 3) 20 each; half rows (4) and every
+// unit without HNSW_V_METRIC (builder, layer operators, ordering, scan: row format decided at run time) none.  Over two metrics
+// and two rules that is 4 x (16 + 3 x 20) = 304.  A new slot count is one stanza (two with its BLK 1) under each NCH; a new row
+// format is a value of HNSW_V_FULL that hnsw_hop_loop.inc knows as HNSW_LOOP_ROWS.  The order is the order the kernels are
+// compiled in: keep it.
+#if defined(HNSW_V_METRIC) && HNSW_V_FULL != 4
+
+// ---- rows of 65..128 dimensions
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
 #define HNSW_LOOP_BLK 1
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
 #define HNSW_LOOP_BLK 1
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
 #define HNSW_LOOP_BLK 1
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 2
 #define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
 #define HNSW_LOOP_BLK 1
 #include "hnsw_hop_loop.inc"
+
+// ---- rows of 129..256 dimensions (bitmap blocks: the float32 rows only)
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(0, 1, 2)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
+#if HNSW_V_FULL != 2
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(1, 0, 2)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(1, 1, 2)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 2
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(0, 0, 1)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
 #define HNSW_LOOP_BLK 1
 #include "hnsw_hop_loop.inc"
 #endif
-#if HNSW_HOP_UNIT(0, 1, 1)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
+#if HNSW_V_FULL != 2
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
 #define HNSW_LOOP_BLK 1
 #include "hnsw_hop_loop.inc"
 #endif
-#if HNSW_HOP_UNIT(1, 0, 1)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
+#if HNSW_V_FULL != 2
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
 #define HNSW_LOOP_BLK 1
 #include "hnsw_hop_loop.inc"
 #endif
-#if HNSW_HOP_UNIT(1, 1, 1)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
 #include "hnsw_hop_loop.inc"
+#if HNSW_V_FULL != 2
 #define HNSW_LOOP_NCH 4
 #define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 1
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
 #define HNSW_LOOP_BLK 1
 #include "hnsw_hop_loop.inc"
 #endif
-#if HNSW_HOP_UNIT(0, 0, 0)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
+
 #endif
-#if HNSW_HOP_UNIT(0, 1, 0)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(1, 0, 0)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(1, 1, 0)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 0
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(0, 0, 3)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(0, 1, 3)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 0
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(1, 0, 3)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 0
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#endif
-#if HNSW_HOP_UNIT(1, 1, 3)
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 2
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 1
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 2
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 3
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 4
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 6
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 0
-#include "hnsw_hop_loop.inc"
-#define HNSW_LOOP_NCH 4
-#define HNSW_LOOP_NSLOT 8
-#define HNSW_LOOP_ROWS 3
-#define HNSW_LOOP_METRIC 1
-#define HNSW_LOOP_SEM 1
-#define HNSW_LOOP_BLK 1
-#include "hnsw_hop_loop.inc"
-#endif
-#undef HNSW_HOP_UNIT

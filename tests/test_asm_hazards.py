@@ -174,49 +174,60 @@ def _owned_nops(body):
 
 
 def test_labels_are_unique_within_every_block(tmp_path):
-    """The blocks use numeric local labels and assume each is defined once per asm statement ("66f" must mean THE 66): the
-    preprocessed text of one translation unit built with HNSW_HOP_ALL_INSTANCES holds every instantiation of the generated
-    table (a unit normally holds its own (metric, rule, row format) only); a label defined twice in one statement -- an
-    eight-slot pop label reused by a later addition, say -- fails here, not on the GPU."""
+    """The blocks use numeric local labels and assume each is defined once per asm statement ("66f" must mean THE 66).  A translation
+    unit of hnsw_search_variants.hip holds the instantiations of its own (metric, rule, row format) only (the hand-written table
+    csrc/hnsw_hop_instances.inc), so the sixteen loop-bearing units are preprocessed, and a half-row unit for the count; a label
+    defined twice in one statement -- an eight-slot pop label reused by a later addition, say -- fails here, not on the GPU."""
     import re
     import subprocess
+    from concurrent.futures import ThreadPoolExecutor
     hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
     if not hipcc:
         pytest.skip("hipcc not available")
-    out = str(tmp_path / "pp.ii")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-DHNSW_V_METRIC=0", "-DHNSW_V_SEMF=0",
-                    "-DHNSW_V_FULL=0", "-DHNSW_HOP_ALL_INSTANCES", "--cuda-device-only", "-E", "-P", os.path.join(ROOT, "ocaml-hnsw_amd", "csrc", "hnsw_search_variants.hip"),
-                    "-o", out], check=True, capture_output=True)
-    text = open(out).read()
-    blocks = []
     lit = re.compile(r'\s*"((?:[^"\\]|\\.)*)"')
-    for m in re.finditer(r"asm volatile\(", text):
-        j, parts = m.end(), []
-        while True:
-            mm = lit.match(text, j)                    # (no slicing: the preprocessed unit is tens of megabytes)
-            if not mm:
-                break
-            parts.append(bytes(mm.group(1), "utf-8").decode("unicode_escape"))
-            j = mm.end()
-        body = "".join(parts)
-        if re.search(r"^\s*\d+:", body, flags=re.M):
-            blocks.append(body)
-    spec = importlib.util.spec_from_file_location("gen_hop_slots", os.path.join(ROOT, "tools", "gen_hop_slots.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    n_inst = len(gen.instances())
-    assert n_inst == 304                             # 4 row families x rows x 2 metrics x 2 rules x 6 slot counts (+ 4 with bitmap blocks)
-    assert len(blocks) >= n_inst + 2, len(blocks)    # ... the descent, the island
-    for body in blocks:
-        labels = re.findall(r"^\s*(\d+):", body, flags=re.M)
-        dup = sorted({x for x in labels if labels.count(x) > 1})
-        assert not dup, "labels defined twice in one block: %s" % dup
+
+    def unit(msf):
+        """(number of HopLoop specialisations, the texts of the asm blocks that define labels) of one preprocessed unit"""
+        out = str(tmp_path / ("pp_%d_%d_%d.ii" % msf))
+        subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-DHNSW_V_METRIC=%d" % msf[0],
+                        "-DHNSW_V_SEMF=%d" % msf[1], "-DHNSW_V_FULL=%d" % msf[2], "--cuda-device-only", "-E", "-P",
+                        os.path.join(ROOT, "ocaml-hnsw_amd", "csrc", "hnsw_search_variants.hip"), "-o", out], check=True, capture_output=True)
+        text = open(out).read()
+        os.remove(out)
+        blocks = []
+        for m in re.finditer(r"asm volatile\(", text):
+            j, parts = m.end(), []
+            while True:
+                mm = lit.match(text, j)                    # (no slicing: a preprocessed unit is megabytes)
+                if not mm:
+                    break
+                parts.append(bytes(mm.group(1), "utf-8").decode("unicode_escape"))
+                j = mm.end()
+            body = "".join(parts)
+            if re.search(r"^\s*\d+:", body, flags=re.M):
+                blocks.append(body)
+        return len(re.findall(r"template\s*<>\s*struct\s+HopLoop\s*<", text)), blocks
+
+    units = [(m, s, f) for m in (0, 1) for s in (0, 1) for f in (0, 1, 2, 3)]
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 2)) as ex:
+        scanned = list(ex.map(unit, units))
+    n_inst = sum(n for n, _ in scanned)
+    # 2 metrics x 2 rules x (byte rows: 10 shapes of 65..128 dimensions + 6 of 129..256; float32 rows full, ragged, split: 10 + 10 each)
+    assert n_inst == 304                             # 4 x (16 + 3 x 20)
+    for msf, (n, blocks) in zip(units, scanned):
+        assert n == (16 if msf[2] == 2 else 20), (msf, n)
+        assert len(blocks) >= n + 2, (msf, len(blocks))     # ... the descent, the island
+        for body in blocks:
+            labels = re.findall(r"^\s*(\d+):", body, flags=re.M)
+            dup = sorted({x for x in labels if labels.count(x) > 1})
+            assert not dup, "%s: labels defined twice in one block: %s" % (msf, dup)
+    assert unit((0, 0, 4))[0] == 0                   # half rows: no hand-scheduled loop
 
 
 def test_generated_insertion_is_current_and_equals_the_hand_written_one():
-    """csrc/hnsw_hop_slots.inc (what depends on the slot count: W in 3, 4, 6, 8 registers) and csrc/hnsw_hop_instances.inc (the
-    table of instantiations) are what tools/gen_hop_slots.py writes, and the generator, asked for FOUR slots, reproduces the
-    hand-written HNSW_INSERT_LOOP4 / HNSW_INSERT_RARE4 of hnsw_hop_asm.hip.h instruction for instruction"""
+    """csrc/hnsw_hop_slots.inc (what depends on the slot count: W in 3, 4, 6, 8 registers) is what tools/gen_hop_slots.py writes,
+    and the generator, asked for FOUR slots, reproduces the hand-written HNSW_INSERT_LOOP4 / HNSW_INSERT_RARE4 of
+    hnsw_hop_asm.hip.h instruction for instruction"""
     import re
     spec = importlib.util.spec_from_file_location("gen_hop_slots", os.path.join(ROOT, "tools", "gen_hop_slots.py"))
     gen = importlib.util.module_from_spec(spec)
@@ -279,13 +290,17 @@ def test_hand_scheduled_blocks_hand_m0_back():
     csrc = os.path.join(ROOT, "ocaml-hnsw_amd", "csrc")
     inc = open(os.path.join(csrc, "hnsw_hop_loop.inc")).read()
     blocks = inc.split("asm volatile(")[1:]
-    assert len(blocks) == 3                                   # W in 2 / three and more / 1 registers
+    assert len(blocks) == 3                                   # W in 1 / 2 / three and more registers
+    # the operand lists are written once in front of the three blocks; the piece HNSW_LOOP_OUT_B declares the register m0 is kept in
+    out_b = inc[inc.index("#define HNSW_LOOP_OUT_B "):inc.index("#if HNSW_LOOP_SEM\n#define HNSW_LOOP_OUT_BAIL")]
+    assert inc.count('[sm0] "=&s"(sm0)') == 1 and '[sm0] "=&s"(sm0)' in out_b
     for b in blocks:
-        body = b.split("    w.wmax = wmax;")[0]
+        body = b[:b.index(");\n", b.index('\n        : "vcc"')) + 2]       # the statement: its text, its operand lists, its clobbers
+        assert body.rstrip().endswith(");") and "w.wmax = wmax;" not in body
         assert body.count('"s_mov_b32 %[sm0], m0\\n\\t"') == 1 and body.count('s_mov_b32 m0, %[sm0]') == 1
         first = "v_alignbit_b32" if "v_alignbit_b32" in body else "HNSW_NS(ALIGN_IN)"      # (the generic body: the slot set's macro)
         assert body.index("s_mov_b32 %[sm0], m0") < body.index(first) < body.rindex("s_mov_b32 m0, %[sm0]")
-        assert '[sm0] "=&s"(sm0)' in body
+        assert len(re.findall(r"\bHNSW_LOOP_OUT_B\b", body)) == 1 and body.index("s_mov_b32 m0, %[sm0]") < body.index("HNSW_LOOP_OUT_B")
     for f in os.listdir(csrc):
         txt = open(os.path.join(csrc, f)).read()
         for clob in re.findall(r'\n\s*: ((?:"[a-z0-9]+",? ?)+)(?:HNSW_[A-Z0-9_]+ ?)*\);', txt):

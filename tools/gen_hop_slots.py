@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Writes the two GENERATED includes of the hand-scheduled layer-0 loop (ocaml-hnsw_amd/csrc/hnsw_hop_asm.hip.h):
+"""Writes the GENERATED include of the hand-scheduled layer-0 loop (ocaml-hnsw_amd/csrc/hnsw_hop_asm.hip.h):
 
   hnsw_hop_slots.inc      everything in hnsw_hop_loop.inc that depends on HOW MANY key registers per lane hold W, as one macro set
                           per slot count N in SLOTS = 3, 4, 6, 8 (ef 129..192 / 193..256 / 257..384 / 385..512): the insertion
@@ -10,14 +10,11 @@
                           the pop / peek chains over the slots' unexpanded masks, the register declarations and operand lists.
                           hnsw_hop_loop.inc has ONE body for all of them (HNSW_NS(...) picks the set of HNSW_LOOP_NSLOT); the
                           four-slot insertion stays the hand-written, commented text and the generator must reproduce it.
-  hnsw_hop_instances.inc  the table of instantiations: one `#define HNSW_LOOP_* ... #include "hnsw_hop_loop.inc"` stanza per
-                          (row family, metric, accept rule, slot count, visited structure), grouped under one `#if` per
-                          translation unit of hnsw_search_variants.hip -- compiled per (metric, rule, row format) -- so that a unit
-                          parses only the stanzas it can reach (rounds 2-5 wrote 184 stanzas by hand and every unit parsed all of
-                          them).
 
-    python tools/gen_hop_slots.py            # rewrite both files
-    python tools/gen_hop_slots.py --check    # exit 1 if a committed file differs from what this script writes
+(Which shapes are instantiated is not generated: the hand-written table csrc/hnsw_hop_instances.inc.)
+
+    python tools/gen_hop_slots.py            # rewrite the file
+    python tools/gen_hop_slots.py --check    # exit 1 if the committed file differs from what this script writes
     python tools/gen_hop_slots.py --n 4      # print the insertion for four slots (compared with the hand-written macros by
                                              # tests/test_asm_hazards.py::test_generated_insertion_is_current_and_equals_the_hand_written_one)
 """
@@ -27,7 +24,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ocaml-hnsw_amd", "csrc")
 OUT_SLOTS = os.path.join(CSRC, "hnsw_hop_slots.inc")
-OUT_INST = os.path.join(CSRC, "hnsw_hop_instances.inc")
 SLOTS = (3, 4, 6, 8)            # slot counts served by the generic body of hnsw_hop_loop.inc (1 and 2 have bodies of their own)
 HAND_WRITTEN = (4,)             # ... whose insertion is the hand-written text of hnsw_hop_asm.hip.h
 DPP = '" HNSW_DPP_ALL "'
@@ -112,7 +108,7 @@ def lines_rare(n):
         a('\ts_branch 19b')
     # a member of W at exactly this distance: rank over all slots, ids decide; the node itself in W: ignored
     a('14:')
-    a('\ts_mov_b32 %[P], 0')
+    a('\ts_mov_b32 %[p], 0')
     a('\ts_mov_b64 %[um1], 0')
     for s in range(n):
         a('@RANK%d@' % s)
@@ -122,9 +118,9 @@ def lines_rare(n):
     a('\ts_cmp_eq_u32 %[nw], %[wmax]')
     a('\ts_cbranch_scc1 15%df' % n)
     a('141:')
-    a('\ts_and_b32 m0, %[P], 63')
+    a('\ts_and_b32 m0, %[p], 63')
     for k in range(t, 0, -1):
-        a('\ts_cmp_ge_u32 %%[P], %d' % (64 * k))
+        a('\ts_cmp_ge_u32 %%[p], %d' % (64 * k))
         a('\ts_cbranch_scc1 8%d1b' % k)
     a('\ts_branch 801b')
     for k in range(t, -1, -1):
@@ -211,68 +207,12 @@ def slots_text():
     return '\n'.join(parts)
 
 
-# ---- the instantiation table ----------------------------------------------------------------------------------------------
-# row families: (name, NCH, ROWS values)
-FAMILIES = (("bytes", 2, (2,)),
-            ("bytes4", 4, (2,)),
-            ("f32", 2, (1, 0, 3)),
-            ("f32n4", 4, (1, 0, 3)))
-NSLOTS = (1, 2, 3, 4, 6, 8)
-
-
-def instances():
-    """(nch, rows, metric, sem, nslot, blk) of every instantiation"""
-    out = []
-    for fam, nch, rows_list in FAMILIES:
-        for rows in rows_list:
-            for metric in (0, 1):
-                for sem in (0, 1):
-                    for nslot in NSLOTS:
-                        for blk in (0, 1):
-                            if blk and (nslot < 3 or fam == "bytes4"):
-                                continue            # bitmap blocks: W in three or more registers; not for byte rows of 129..256 dimensions
-                            out.append((nch, rows, metric, sem, nslot, blk))
-    return out
-
-
-def instances_text():
-    L = ['// hnsw_hop_instances.inc -- GENERATED by tools/gen_hop_slots.py (do not edit; `python tools/gen_hop_slots.py` rewrites it,',
-         '// tests/test_asm_hazards.py checks that it is current): the instantiations HopLoop<NCH, NSLOT, METRIC, ROWS, SEM, BLK> of the',
-         '// hand-scheduled layer-0 loop, one stanza each, grouped by the translation unit that can reach them: the units of',
-         '// hnsw_search_variants.hip are compiled per (metric, accept rule, row format) and define HNSW_V_METRIC / HNSW_V_SEMF /',
-         '// HNSW_V_FULL; every other unit (the builder, the layer operators: row format decided at run time) takes search_layer\'s',
-         '// C++ loop and instantiates nothing.',
-         '#if defined(HNSW_HOP_ALL_INSTANCES)      /* (tests: every instantiation in one preprocessed unit) */',
-         '#define HNSW_HOP_UNIT(M, S, R) 1',
-         '#elif defined(HNSW_V_METRIC)',
-         '#define HNSW_HOP_UNIT(M, S, R) (HNSW_V_METRIC == (M) && HNSW_V_SEMF == (S) && HNSW_V_FULL == (R))',
-         '#else',
-         '#define HNSW_HOP_UNIT(M, S, R) 0',
-         '#endif']
-    units = {}                  # (metric, rule, row format) -> its stanzas, in table order (the order the unit compiles them in)
-    for inst in instances():
-        units.setdefault((inst[2], inst[3], inst[1]), []).append(inst)
-    for unit, insts in units.items():
-        L.append('#if HNSW_HOP_UNIT(%d, %d, %d)' % unit)
-        for nch, rows, metric, sem, nslot, blk in insts:
-            L.append('#define HNSW_LOOP_NCH %d' % nch)
-            L.append('#define HNSW_LOOP_NSLOT %d' % nslot)
-            L.append('#define HNSW_LOOP_ROWS %d' % rows)
-            L.append('#define HNSW_LOOP_METRIC %d' % metric)
-            L.append('#define HNSW_LOOP_SEM %d' % sem)
-            L.append('#define HNSW_LOOP_BLK %d' % blk)
-            L.append('#include "hnsw_hop_loop.inc"')
-        L.append('#endif')
-    L.append('#undef HNSW_HOP_UNIT')
-    return '\n'.join(L) + '\n'
-
-
 def main(argv):
     if '--n' in argv:
         n = int(argv[argv.index('--n') + 1])
         sys.stdout.write(text(n))
         return 0
-    want = {OUT_SLOTS: slots_text(), OUT_INST: instances_text()}
+    want = {OUT_SLOTS: slots_text()}
     if '--check' in argv:
         rc = 0
         for path, t in want.items():

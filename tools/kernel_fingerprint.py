@@ -2,7 +2,7 @@
 """Fingerprint of every gfx950 kernel of the in-tree build: one line per kernel symbol with the number of instructions and a
 hash of its instruction stream (mnemonics and operands as llvm-objdump prints them; addresses and encodings dropped, branch
 targets reduced to their distance).  Two builds whose lists are equal run the same code -- what a refactoring of the
-hand-scheduled loops' instantiation (hnsw_hop_loop.inc, tools/gen_hop_slots.py) is checked with.
+hand-scheduled loops' instantiation (hnsw_hop_loop.inc, hnsw_hop_instances.inc, tools/gen_hop_slots.py) is checked with.
 
     python tools/kernel_fingerprint.py [objects ...] > before.txt      (default: every ocaml-hnsw_amd/build/*.o)
     python tools/kernel_fingerprint.py --diff before.txt after.txt     kernels added / removed / changed
