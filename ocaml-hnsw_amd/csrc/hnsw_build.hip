@@ -58,15 +58,6 @@ hipError_t launch_link(int metric, int nch, const BuildView &bv, const hnsw_dev:
     return hipGetLastError();
 }
 
-#define HIP_TRY_B(expr)                                                                      \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            rc = fail(e__ == hipErrorOutOfMemory ? HNSW_ERR_OOM : HNSW_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
-            goto done;                                                                       \
-        }                                                                                    \
-    } while (0)
-
 } // namespace
 
 // ---- levels (lib/ohnsw.ml:781): node i's draw is the i-th of one splitmix64 stream, i.e. the mix of the state
@@ -98,7 +89,6 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
     *rem_overflow = false;
     const int M = p->num_connections, efc = p->num_nodes_search_construction;
     const int nch = pick_nch(bv.iv.nchunks);
-    int rc = HNSW_OK;
     const int S0 = 2 * M, SU = M;
     const int bdiv = p->batch_div > 0 ? p->batch_div : 16;
     const int bmax = p->max_batch > 0 ? p->max_batch : 8192;
@@ -109,38 +99,37 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
     const int64_t rem_cap = max_edges * 2 * rem_scale;
     const int64_t rowsU = bv.iv.rowsU;
     uint32_t rem_over = 0;
-    hipStream_t st = nullptr;
-    void *dNodes = nullptr, *dRecOf = nullptr, *dRecNode = nullptr, *dCandId = nullptr, *dCandKey = nullptr,
-         *dCandCnt = nullptr, *dEdges = nullptr, *dEdgesSorted = nullptr, *dRem = nullptr, *dRemCnt = nullptr, *dTemp = nullptr;
+    Stream st;
+    Table dNodes, dRecOf, dRecNode, dCandId, dCandKey, dCandCnt, dEdges, dEdgesSorted, dRem, dRemCnt, dTemp;
     size_t temp_bytes = 0;
-    int32_t *hp_nodes[2] = {nullptr, nullptr}, *hp_rec_of[2] = {nullptr, nullptr}, *hp_rec_node[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Pinned<int32_t> hp_nodes[2], hp_rec_of[2], hp_rec_node[2];
+    Event ev[2];
     int64_t batch_no = 0;
     std::vector<int32_t> rec_begin((size_t)lcap + 1, 0);
     int cur_max = *cur_max_io, entry = *entry_io;
     bv.efc = efc; bv.cand_stride = cand_stride;
     bv.vt_bits = build_vt_bits(efc, n);
 
-    HIP_TRY_B(hipStreamCreate(&st));
-    HIP_TRY_B(hipMalloc(&dNodes, (size_t)bmax * 4));
-    HIP_TRY_B(hipMalloc(&dRecOf, (size_t)bmax * lcap * 4));
-    HIP_TRY_B(hipMalloc(&dRecNode, (size_t)maxrec * 4));
-    HIP_TRY_B(hipMalloc(&dCandId, (size_t)maxrec * cand_stride * 4));
-    HIP_TRY_B(hipMalloc(&dCandKey, (size_t)maxrec * cand_stride * 4));
-    HIP_TRY_B(hipMalloc(&dCandCnt, (size_t)maxrec * 4));
-    HIP_TRY_B(hipMalloc(&dEdges, (size_t)max_edges * 8));
-    HIP_TRY_B(hipMalloc(&dEdgesSorted, (size_t)max_edges * 8));
-    HIP_TRY_B(hipMalloc(&dRem, (size_t)rem_cap * 8));
-    HIP_TRY_B(hipMalloc(&dRemCnt, 16));
-    HIP_TRY_B(hipMemset(dRemCnt, 0, 16));
-    HIP_TRY_B(hipcub::DeviceRadixSort::SortKeys(nullptr, temp_bytes, (uint64_t *)dEdges, (uint64_t *)dEdgesSorted, (int)max_edges, 0, 64, st));
-    HIP_TRY_B(hipMalloc(&dTemp, std::max<size_t>(temp_bytes, 16)));
+    HIP_TRY(hipStreamCreate(&st.h));
+    HIP_TRY(dNodes.alloc((size_t)bmax * 4));
+    HIP_TRY(dRecOf.alloc((size_t)bmax * lcap * 4));
+    HIP_TRY(dRecNode.alloc((size_t)maxrec * 4));
+    HIP_TRY(dCandId.alloc((size_t)maxrec * cand_stride * 4));
+    HIP_TRY(dCandKey.alloc((size_t)maxrec * cand_stride * 4));
+    HIP_TRY(dCandCnt.alloc((size_t)maxrec * 4));
+    HIP_TRY(dEdges.alloc((size_t)max_edges * 8));
+    HIP_TRY(dEdgesSorted.alloc((size_t)max_edges * 8));
+    HIP_TRY(dRem.alloc((size_t)rem_cap * 8));
+    HIP_TRY(dRemCnt.alloc(16));
+    HIP_TRY(hipMemset(dRemCnt.p, 0, 16));
+    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, temp_bytes, (uint64_t *)dEdges.p, (uint64_t *)dEdgesSorted.p, (int)max_edges, 0, 64, st));
+    HIP_TRY(dTemp.alloc(temp_bytes));
 
     for (int k = 0; k < 2; ++k) {   // pinned, double buffered: batch b+2 waits for batch b's uploads
-        HIP_TRY_B(hipHostMalloc((void **)&hp_nodes[k], (size_t)bmax * 4, hipHostMallocDefault));
-        HIP_TRY_B(hipHostMalloc((void **)&hp_rec_of[k], (size_t)bmax * lcap * 4, hipHostMallocDefault));
-        HIP_TRY_B(hipHostMalloc((void **)&hp_rec_node[k], (size_t)maxrec * 4, hipHostMallocDefault));
-        HIP_TRY_B(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+        HIP_TRY(hp_nodes[k].alloc((size_t)bmax * 4, hipHostMallocDefault));
+        HIP_TRY(hp_rec_of[k].alloc((size_t)bmax * lcap * 4, hipHostMallocDefault));
+        HIP_TRY(hp_rec_node[k].alloc((size_t)maxrec * 4, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&ev[k].h, hipEventDisableTiming));
     }
 
     // ---- batches, in node order (fold_cols, lib/ohnsw.ml:848) ----
@@ -151,7 +140,7 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
             if ((int)lvl[(size_t)(j - pos0)] > cur_max) { end = j + 1; break; }       // :832-836
         const int B = (int)(end - pos);
         const int kb = (int)(batch_no & 1);
-        if (batch_no >= 2) HIP_TRY_B(hipEventSynchronize(ev[kb]));
+        if (batch_no >= 2) HIP_TRY(hipEventSynchronize(ev[kb]));
         int32_t *h_nodes = hp_nodes[kb], *h_rec_of = hp_rec_of[kb], *h_rec_node = hp_rec_node[kb];
         // records: (layer, batch slot) for layer <= min(level, cur_max), ordered by layer then slot
         int nrec = 0;
@@ -164,46 +153,46 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
             }
         }
         rec_begin[(size_t)cur_max + 1] = nrec;
-        HIP_TRY_B(hipMemcpyAsync(dNodes, h_nodes, (size_t)B * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY_B(hipMemcpyAsync(dRecOf, h_rec_of, (size_t)B * lcap * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY_B(hipMemcpyAsync(dRecNode, h_rec_node, (size_t)nrec * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY_B(hipEventRecord(ev[kb], st));
+        HIP_TRY(hipMemcpyAsync(dNodes.p, h_nodes, (size_t)B * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dRecOf.p, h_rec_of, (size_t)B * lcap * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dRecNode.p, h_rec_node, (size_t)nrec * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(ev[kb], st));
 
         BatchView bt{};
-        bt.nodes = (const int32_t *)dNodes; bt.rec_of = (const int32_t *)dRecOf; bt.B = B; bt.lcap = lcap;
+        bt.nodes = (const int32_t *)dNodes.p; bt.rec_of = (const int32_t *)dRecOf.p; bt.B = B; bt.lcap = lcap;
         bt.cur_max_layer = cur_max; bt.entry = entry;
-        bt.cand_id = (int32_t *)dCandId; bt.cand_key = (uint32_t *)dCandKey; bt.cand_cnt = (int32_t *)dCandCnt;
+        bt.cand_id = (int32_t *)dCandId.p; bt.cand_key = (uint32_t *)dCandKey.p; bt.cand_cnt = (int32_t *)dCandCnt.p;
         bv.iv.max_layer = cur_max; bv.iv.entry_point = entry;
-        HIP_TRY_B(launch_search(p->metric, nch, nslot, bv, bt, st));
+        HIP_TRY(launch_search(p->metric, nch, nslot, bv, bt, st));
 
         for (int l = cur_max; l >= 0; --l) {
             const int rb = rec_begin[(size_t)l], re = rec_begin[(size_t)l + 1];
             if (re == rb) continue;
             const int R = l == 0 ? S0 : SU;                                    // :818
             SelectArgs sa{};
-            sa.rec_node = (const int32_t *)dRecNode; sa.rec_begin = rb; sa.rec_end = re; sa.layer = l; sa.R = R;
-            sa.edges = (uint64_t *)dEdges;
-            HIP_TRY_B(launch_select(p->metric, nch, bv, bt, sa, st));
+            sa.rec_node = (const int32_t *)dRecNode.p; sa.rec_begin = rb; sa.rec_end = re; sa.layer = l; sa.R = R;
+            sa.edges = (uint64_t *)dEdges.p;
+            HIP_TRY(launch_select(p->metric, nch, bv, bt, sa, st));
             if (B == 1) {
                 // a batch of one node: the link step of Ohnsw.insert exactly, neighbour by neighbour (:820-829)
                 hnsw_dev::LinkArgs la{};
                 la.q = (int32_t)pos; la.layer = l; la.R = R;
-                HIP_TRY_B(launch_link(p->metric, nch, bv, la, st));
+                HIP_TRY(launch_link(p->metric, nch, bv, la, st));
                 continue;
             }
             const int n_edges = (re - rb) * R;
             size_t tb = temp_bytes;
-            HIP_TRY_B(hipcub::DeviceRadixSort::SortKeys(dTemp, tb, (uint64_t *)dEdges, (uint64_t *)dEdgesSorted, n_edges, 0, 64, st));
-            HIP_TRY_B(hipMemsetAsync(dRemCnt, 0, 4, st));
+            HIP_TRY(hipcub::DeviceRadixSort::SortKeys(dTemp.p, tb, (uint64_t *)dEdges.p, (uint64_t *)dEdgesSorted.p, n_edges, 0, 64, st));
+            HIP_TRY(hipMemsetAsync(dRemCnt.p, 0, 4, st));
             MergeArgs ma{};
-            ma.edges = (const uint64_t *)dEdgesSorted; ma.n_edges = n_edges; ma.layer = l; ma.R = R;
-            ma.removals = (uint64_t *)dRem; ma.rem_cnt = (uint32_t *)dRemCnt; ma.rem_cap = (uint32_t)rem_cap;
-            HIP_TRY_B(launch_merge(p->metric, nch, bv, ma, st));
+            ma.edges = (const uint64_t *)dEdgesSorted.p; ma.n_edges = n_edges; ma.layer = l; ma.R = R;
+            ma.removals = (uint64_t *)dRem.p; ma.rem_cnt = (uint32_t *)dRemCnt.p; ma.rem_cap = (uint32_t)rem_cap;
+            HIP_TRY(launch_merge(p->metric, nch, bv, ma, st));
             // one thread per possible removal: the count is only known on the device (clamped to the buffer there)
             const unsigned rem_threads = (unsigned)std::min<int64_t>(std::max<int64_t>((int64_t)n_edges * 2, 4096), rem_cap);
             hipLaunchKernelGGL(hnsw_dev::build_unlink_kernel, dim3((rem_threads + 255) / 256), dim3(256), 0, st, bv,
-                               (const uint64_t *)dRem, (const uint32_t *)dRemCnt, (uint32_t)rem_cap, l);
-            HIP_TRY_B(hipGetLastError());
+                               (const uint64_t *)dRem.p, (const uint32_t *)dRemCnt.p, (uint32_t)rem_cap, l);
+            HIP_TRY(hipGetLastError());
         }
         if ((int)lvl[(size_t)(end - 1 - pos0)] > cur_max) { cur_max = lvl[(size_t)(end - 1 - pos0)]; entry = (int)(end - 1); } // :832-836
         pos = end;
@@ -212,21 +201,12 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
     hipLaunchKernelGGL(hnsw_dev::build_compact_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, bv.nbr0_w, n, S0);
     if (rowsU > 0)
         hipLaunchKernelGGL(hnsw_dev::build_compact_kernel, dim3((unsigned)((rowsU + 3) / 4)), dim3(256), 0, st, bv.nbrU_w, rowsU, SU);
-    HIP_TRY_B(hipGetLastError());
-    HIP_TRY_B(hipStreamSynchronize(st));
-    HIP_TRY_B(hipMemcpy(&rem_over, (const uint32_t *)dRemCnt + 1, 4, hipMemcpyDeviceToHost));
-    if (rem_over) { *rem_overflow = true; rc = fail(HNSW_ERR_DEGREE_OVERFLOW, "a build step produced %u symmetric removals, more than the %lld the buffer holds", rem_over, (long long)rem_cap); goto done; }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(&rem_over, (const uint32_t *)dRemCnt.p + 1, 4, hipMemcpyDeviceToHost));
+    if (rem_over) { *rem_overflow = true; return fail(HNSW_ERR_DEGREE_OVERFLOW, "a build step produced %u symmetric removals, more than the %lld the buffer holds", rem_over, (long long)rem_cap); }
     *cur_max_io = cur_max; *entry_io = entry;
-done:
-    for (void *q : {dNodes, dRecOf, dRecNode, dCandId, dCandKey, dCandCnt, dEdges, dEdgesSorted, dRem, dRemCnt, dTemp}) if (q) (void)hipFree(q);
-    for (int k = 0; k < 2; ++k) {
-        if (hp_nodes[k]) (void)hipHostFree(hp_nodes[k]);
-        if (hp_rec_of[k]) (void)hipHostFree(hp_rec_of[k]);
-        if (hp_rec_node[k]) (void)hipHostFree(hp_rec_node[k]);
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
-    }
-    if (st) (void)hipStreamDestroy(st);
-    return rc;
+    return HNSW_OK;
 }
 
 // the builder's parameter checks, shared by hnsw_build and hnsw_index_insert
@@ -265,9 +245,9 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
     std::vector<int2> ref;
     const int64_t rowsU = upper_layout(lvl.data(), n, 0, ref);
 
-    hnsw_index *idx = new hnsw_index();
+    IndexPtr idx(new hnsw_index());
     idx->device = device;
-    int rc = HNSW_OK;
+    int rc;
     const int S0 = 2 * M, SU = M;
     const int64_t stride = padded_stride(d);
     BuildView bv{};
@@ -275,20 +255,16 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
     IndexView &iv = idx->iv;
 
     if ((rc = alloc_graph_tables(idx->tables, n, stride, S0, SU, rowsU)) ||
-        (rc = upload_rows(vectors, n, d, row_stride, (float *)idx->tables.X.p)) || (rc = upload_upper_layout(idx->tables, 0, ref))) goto done;
+        (rc = upload_rows(vectors, n, d, row_stride, (float *)idx->tables.X.p)) || (rc = upload_upper_layout(idx->tables, 0, ref))) return rc;
     iv.stride = stride; iv.n = n; iv.d = d; iv.nchunks = nchunks; iv.S0 = S0; iv.SU = SU; iv.rowsU = rowsU;
     iv.max_layer = 0; iv.entry_point = 0; iv.id_base = p->id_base;
-    bind_view(idx);
+    bind_view(idx.get());
     bv.iv = iv; bv.nbr0_w = (int32_t *)idx->tables.nbr0.p; bv.nbrU_w = (int32_t *)idx->tables.nbrU.p;
-    if ((rc = run_batches(bv, lvl.data() + 1, 1, n, lcap, p, rem_scale, rem_overflow, &cur_max, &entry))) goto done;
+    if ((rc = run_batches(bv, lvl.data() + 1, 1, n, lcap, p, rem_scale, rem_overflow, &cur_max, &entry))) return rc;
     iv.max_layer = cur_max; iv.entry_point = entry;
-    {
-        hnsw_index_info &inf = idx->info;
-        inf.d = d; inf.metric = p->metric; inf.id_base = p->id_base; inf.max_degree = SU; inf.device = device;
-    }
-done:
-    if (rc) { hnsw_index_destroy(idx); return rc; }
-    return finish_index(idx, p->expected_ef, p->expected_semantics, out);
+    hnsw_index_info &inf = idx->info;
+    inf.d = d; inf.metric = p->metric; inf.id_base = p->id_base; inf.max_degree = SU; inf.device = device;
+    return finish_index(std::move(idx), p->expected_ef, p->expected_semantics, out);
 }
 
 namespace {
@@ -331,13 +307,13 @@ hipError_t widen_rows(const void *src, int64_t rows, int ws, void *dst, int wd) 
 }
 } // namespace
 
-// One attempt of hnsw_index_insert: a new handle `*out` with the graph of idx grown by the m vectors -- idx's tables copied
+// One attempt of hnsw_index_insert: a new handle `out` with the graph of idx grown by the m vectors -- idx's tables copied
 // (rows widened to 2M / M) into tables sized for n_old + m nodes, then run_batches from position n_old.  idx is only read.
 // The derived tables (byte / split rows, locality codes) are the caller's.
 static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p,
-                              int64_t rem_scale, bool *rem_overflow, hnsw_index **out) {
+                              int64_t rem_scale, bool *rem_overflow, IndexPtr &out) {
     *rem_overflow = false;
-    *out = nullptr;
+    out.reset();
     const IndexView &ov = idx->iv;
     const int64_t n_old = ov.n, n = n_old + m;
     const int M = p->num_connections, S0 = 2 * M, SU = M;
@@ -353,37 +329,35 @@ static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64
     const int64_t rowsU = upper_layout(lvl.data(), m, rowsU_old, ref);
     if (rowsU > 0x7FFFFFF0LL) return fail(HNSW_ERR_UNSUPPORTED, "too many upper rows");
 
-    hnsw_index *nx = new hnsw_index();
+    IndexPtr nx(new hnsw_index());
     nx->device = idx->device;
-    int rc = HNSW_OK;
+    int rc;
     const IndexTables &ot = idx->tables;
     IndexTables &t = nx->tables;
     IndexView &iv = nx->iv;
     BuildView bv{};
-    if ((rc = alloc_graph_tables(t, n, stride, S0, SU, rowsU))) goto done;
+    if ((rc = alloc_graph_tables(t, n, stride, S0, SU, rowsU))) return rc;
     if (n_old > 0) {
-        HIP_TRY_B(hipMemcpy(t.X.p, ot.X.p, (size_t)n_old * stride * 4, hipMemcpyDeviceToDevice));
-        HIP_TRY_B(hipMemcpy(t.off.p, ot.off.p, (size_t)n_old * 4, hipMemcpyDeviceToDevice));
-        HIP_TRY_B(hipMemcpy(t.lvl.p, ot.lvl.p, (size_t)n_old, hipMemcpyDeviceToDevice));
-        HIP_TRY_B(hipMemcpy(t.ref.p, ot.ref.p, (size_t)n_old * sizeof(int2), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(t.X.p, ot.X.p, (size_t)n_old * stride * 4, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(t.off.p, ot.off.p, (size_t)n_old * 4, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(t.lvl.p, ot.lvl.p, (size_t)n_old, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(t.ref.p, ot.ref.p, (size_t)n_old * sizeof(int2), hipMemcpyDeviceToDevice));
     }
-    if ((rc = upload_rows(vectors, m, ov.d, row_stride, (float *)t.X.p + n_old * stride))) goto done;
-    HIP_TRY_B(widen_rows(ot.nbr0.p, n_old, S0o, t.nbr0.p, S0));
-    HIP_TRY_B(widen_rows(ot.nbrU.p, rowsU_old, SUo, t.nbrU.p, SU));
-    if ((rc = upload_upper_layout(t, n_old, ref))) goto done;
+    if ((rc = upload_rows(vectors, m, ov.d, row_stride, (float *)t.X.p + n_old * stride))) return rc;
+    HIP_TRY(widen_rows(ot.nbr0.p, n_old, S0o, t.nbr0.p, S0));
+    HIP_TRY(widen_rows(ot.nbrU.p, rowsU_old, SUo, t.nbrU.p, SU));
+    if ((rc = upload_upper_layout(t, n_old, ref))) return rc;
     iv = ov;                                                            // d, stride, nchunks, id_base
     iv.n = n; iv.S0 = S0; iv.SU = SU; iv.rowsU = rowsU; iv.max_layer = cur_max; iv.entry_point = entry;
-    bind_view(nx);                                                      // (the derived tables are the caller's)
+    bind_view(nx.get());                                                // (the derived tables are the caller's)
     bv.iv = iv; bv.nbr0_w = (int32_t *)t.nbr0.p; bv.nbrU_w = (int32_t *)t.nbrU.p;
     if (n > 1 && (rc = run_batches(bv, lvl.data() + (n_old > 0 ? 0 : 1), std::max<int64_t>(n_old, 1), n, lcap, p, rem_scale,
-                                   rem_overflow, &cur_max, &entry))) goto done;
+                                   rem_overflow, &cur_max, &entry))) return rc;
     iv.max_layer = cur_max; iv.entry_point = entry;
     nx->info = idx->info;                                               // d, metric, id_base, device
     nx->info.max_degree = SU;
-    bind_view(nx);
-done:
-    if (rc) { hnsw_index_destroy(nx); return rc; }
-    *out = nx;
+    bind_view(nx.get());
+    out = std::move(nx);
     return HNSW_OK;
 }
 
@@ -423,50 +397,50 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
     if (n_old > 0 && idx->iv.entry_point < 0) return fail(HNSW_ERR_BAD_ARG, "the index has nodes but no entry point");
     if (idx->live_requests > 0) return fail(HNSW_ERR_BAD_ARG, "%d submitted requests not waited for (hnsw_search_wait first)", idx->live_requests);
     if (idx->multi_replica) return fail(HNSW_ERR_BAD_ARG, "the index is a replica of an hnsw_multi: inserting into one replica would desynchronise the others");
-    if (idx->fb_queries > 0 && (int64_t)idx->dFbSlab.cap / (n * 4) < 1)
+    if (idx->fb_queries > 0 && (int64_t)idx->dFbSlab.bytes / (n * 4) < 1)
         return fail(HNSW_ERR_BAD_ARG, "device_fallback_slab_bytes=%lld holds no query of the grown index: one needs 4 n = %lld bytes",
-                    (long long)idx->dFbSlab.cap, (long long)(n * 4));
+                    (long long)idx->dFbSlab.bytes, (long long)(n * 4));
     HIP_TRY(hipSetDevice(idx->device));
     if (n_old > 0) {
-        int32_t *dflag = nullptr, bad = 0;
-        HIP_TRY(hipMalloc((void **)&dflag, 4));
-        hipError_t e = hipMemset(dflag, 0, 4);
+        DevFlag flag;
+        int32_t bad = 0;
+        HIP_TRY(flag.alloc());
+        hipError_t e = flag.set(0);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(upper_rows_check_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, nullptr, idx->iv.upper_ref,
-                               idx->iv.nbrU, idx->iv.SU, n_old, idx->iv.entry_point, idx->iv.max_layer, dflag);
+                               idx->iv.nbrU, idx->iv.SU, n_old, idx->iv.entry_point, idx->iv.max_layer, (int32_t *)flag.p);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipMemcpy(&bad, dflag, 4, hipMemcpyDeviceToHost);
-        (void)hipFree(dflag);
+        if (e == hipSuccess) e = flag.get(&bad);
         if (e != hipSuccess) return fail(HNSW_ERR_HIP, "upper-row check failed: %s", hipGetErrorString(e));
         if (bad) return fail(HNSW_ERR_BAD_ARG, "the graph lists a node on a layer it is not on (or its entry point is not on the top layer): not grown");
     }
 
     // the grown graph, in tables of its own: on any error idx is as it was (overflow: again from idx's tables, 4x the room)
-    hnsw_index *nx = nullptr;
+    IndexPtr nx;
     int32_t rc = HNSW_OK;
     for (int64_t scale = 1; scale <= 64; scale *= 4) {
         bool overflow = false;
-        rc = insert_attempt(idx, vectors, m, row_stride, p, scale, &overflow, &nx);
+        rc = insert_attempt(idx, vectors, m, row_stride, p, scale, &overflow, nx);
         if (!overflow) break;
     }
     // ... and what the handle derives from the graph, made again for it: the byte rows if ALL vectors are byte-valued, the split
     // rows (per-slot tails follow the changed adjacency) unless option split_rows -1 freed them for good, the half rows while
     // option half_rows is 1 (new vectors that do not fit fp16 refuse the whole insert; at 0 the copy is not carried over), the
     // locality codes
-    if (!rc) rc = make_byte_rows(nx);
-    if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx);
-    if (!rc && idx->half_rows_on) rc = make_half_rows(nx);
-    if (!rc) rc = extend_locality_codes(idx, nx);
+    if (!rc) rc = make_byte_rows(nx.get());
+    if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx.get());
+    if (!rc && idx->half_rows_on) rc = make_half_rows(nx.get());
+    if (!rc) rc = extend_locality_codes(idx, nx.get());
     if (rc) {
-        if (nx) hnsw_index_destroy(nx);
+        nx.reset();
         (void)hipGetLastError();                    // (a failed allocation must not surface in the next call on this handle)
         return rc;
     }
     // swap: work still in flight on caller streams (hnsw_search_batch_device) reads the old tables
     {
         const hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) { hnsw_index_destroy(nx); return fail(HNSW_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(HNSW_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e));
     }
     const int rows_before = idx->info.row_format;
     std::swap(idx->tables, nx->tables);                    // (nx takes the old tables with it)
@@ -474,10 +448,10 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
     idx->info = nx->info;
     bind_view(idx);                                        // the options keep their effect
     idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
-    hnsw_index_destroy(nx);
+    nx.reset();
     // the per-shape decisions that follow n or the row format
     idx->forget_shapes(/*keep_visited=*/rows_before == idx->info.row_format);
-    if (idx->fb_queries > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.cap / (n * 4), 65536);
+    if (idx->fb_queries > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.bytes / (n * 4), 65536);
     // the grown index is searched at the steady-state rate from its first call, as a loaded one
     (void)warm_up(idx);
     const std::vector<std::pair<int, int>> shapes = idx->prepared;
@@ -521,17 +495,13 @@ int32_t hnsw_select_neighbours_batch(hnsw_index *idx, const float *targets, int6
     int rc;
     const size_t tbytes = ((size_t)(nb - 1) * t_stride + idx->iv.d) * 4;
     if ((rc = dT.ensure(tbytes)) || (rc = dC.ensure(c0.size() * 4)) || (rc = dN.ensure((size_t)nb * 4)) ||
-        (rc = dO.ensure((size_t)nb * num_neighbours * 4)) || (rc = dOc.ensure((size_t)nb * 4))) {
-        dT.release(); dC.release(); dN.release(); dO.release(); dOc.release();
-        return rc;
-    }
-    auto cleanup = [&]() { dT.release(); dC.release(); dN.release(); dO.release(); dOc.release(); dDg.release(); };
+        (rc = dO.ensure((size_t)nb * num_neighbours * 4)) || (rc = dOc.ensure((size_t)nb * 4))) return rc;
     if (cand_degree) {
-        if ((rc = dDg.ensure((size_t)nb * cand_stride * 4))) { cleanup(); return rc; }
-        if (hipMemcpy(dDg.p, cand_degree, (size_t)nb * cand_stride * 4, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(HNSW_ERR_HIP, "upload failed"); }
+        if ((rc = dDg.ensure((size_t)nb * cand_stride * 4))) return rc;
+        if (hipMemcpy(dDg.p, cand_degree, (size_t)nb * cand_stride * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(HNSW_ERR_HIP, "upload failed");
     }
     if (hipMemcpy(dT.p, targets, tbytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dC.p, c0.data(), c0.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dN.p, cand_cnt, (size_t)nb * 4, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(HNSW_ERR_HIP, "upload failed"); }
+        hipMemcpy(dN.p, cand_cnt, (size_t)nb * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(HNSW_ERR_HIP, "upload failed");
     SelectOpArgs sa{};
     sa.targets = (const float *)dT.p; sa.t_stride = t_stride; sa.cand = (const int32_t *)dC.p; sa.cand_cnt = (const int32_t *)dN.p;
     sa.cand_stride = cand_stride; sa.nb = (int32_t)nb; sa.R = num_neighbours; sa.keep_all_if_few = keep_all_if_few;
@@ -544,7 +514,6 @@ int32_t hnsw_select_neighbours_batch(hnsw_index *idx, const float *targets, int6
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, dO.p, (size_t)nb * num_neighbours * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(out_cnt, dOc.p, (size_t)nb * 4, hipMemcpyDeviceToHost);
-    cleanup();
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "select_neighbours failed: %s", hipGetErrorString(e));
     for (int64_t i = 0; i < nb * num_neighbours; ++i) if (out[i] >= 0) out[i] += base;
     return HNSW_OK;
@@ -639,7 +608,6 @@ int layer_stats_device(const hnsw_index *idx, int32_t layer, StatsAcc *out, std:
     StatsAcc h{0, 0, 0, 1000000, -1};
     if (n == 0) { *out = h; if (iso) iso->clear(); return HNSW_OK; }
     DevBuf dAcc, dIso;
-    struct Guard { DevBuf &a, &b; ~Guard() { a.release(); b.release(); } } guard{dAcc, dIso};
     int rc;
     if ((rc = dAcc.ensure(sizeof(StatsAcc)))) return rc;
     unsigned long long cap = 0;

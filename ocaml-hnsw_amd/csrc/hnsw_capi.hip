@@ -341,7 +341,7 @@ int knn_blk_bits(hnsw_index *idx, const KnnShape &sh) {
     // at distance 0 and its walk is shorter than a real query's) -- searched both ways, k = 1, evaluations counted
     const int64_t nq = std::min<int64_t>(256, idx->iv.n), step = idx->iv.n / nq;
     DevBuf out, probes;
-    if (out.ensure((size_t)nq * 16) != HNSW_OK || probes.ensure((size_t)nq * idx->iv.stride * 4) != HNSW_OK) { out.release(); probes.release(); return choice = 0; }
+    if (out.ensure((size_t)nq * 16) != HNSW_OK || probes.ensure((size_t)nq * idx->iv.stride * 4) != HNSW_OK) return choice = 0;
     hipLaunchKernelGGL(probe_queries_kernel, dim3((unsigned)nq), dim3(64), 0, nullptr, idx->iv, step, (float *)probes.p);
     uint64_t sum[2] = {0, 0};
     bool ok = hipGetLastError() == hipSuccess;
@@ -356,7 +356,6 @@ int knn_blk_bits(hnsw_index *idx, const KnnShape &sh) {
              hipMemcpy(nd.data(), b.nd, (size_t)nq * 4, hipMemcpyDeviceToHost) == hipSuccess;
         for (uint32_t v : nd) sum[pass] += v;
     }
-    out.release(); probes.release();
     if (!ok) { (void)hipGetLastError(); choice = 0; release_unused_lcode0(idx); return 0; }
     choice = (double)sum[1] <= 0.95 * (double)sum[0] ? bits : 0;
     release_unused_lcode0(idx);     // the tags won and no other shape uses the blocks: the per-slot table (GBs at 10 M nodes) goes again
@@ -490,12 +489,12 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *params, const KnnBatch
     // A batch larger than the chip holds at once is searched longest walk first (hnsw_order.hip):
     // per-query results are unchanged, the launch's drain phase is made of short walks.
     void *block = nullptr;
-    hipEvent_t *ev = nullptr;
+    Event *ev = nullptr;
     if (idx->time_kernels && idx->tev_used + 3 <= 3 * 4096) {
         while (idx->tev.size() < idx->tev_used + 3) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            idx->tev.push_back(e);
+            Event e;
+            HIP_TRY(hipEventCreate(&e.h));
+            idx->tev.push_back(std::move(e));
         }
         ev = &idx->tev[idx->tev_used];      // claimed (tev_used advanced) only once all three are recorded
         HIP_TRY(hipEventRecord(ev[0], st));
@@ -555,9 +554,9 @@ hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uin
 
 // the handle's stream for the host-buffer call and its page-locked "any query flagged" word
 int ensure_host_call_state(hnsw_index *idx) {
-    if (!idx->hs[0]) HIP_TRY(hipStreamCreateWithFlags(&idx->hs[0], hipStreamNonBlocking));
+    if (!idx->hs[0]) HIP_TRY(hipStreamCreateWithFlags(&idx->hs[0].h, hipStreamNonBlocking));
     if (!idx->hFlag) {
-        HIP_TRY(hipHostMalloc((void **)&idx->hFlag, 64, hipHostMallocMapped));
+        HIP_TRY(idx->hFlag.alloc(64, hipHostMallocMapped));
         HIP_TRY(hipHostGetDevicePointer((void **)&idx->hFlagDev, idx->hFlag, 0));
     }
     return HNSW_OK;
@@ -579,7 +578,6 @@ int trial_search(hnsw_index *idx, hnsw_search_params p) {
     }
     idx->order_mode = mode;
     const hipError_t e = hipStreamSynchronize(idx->hs[0]);
-    out.release();
     if (!rc && e != hipSuccess) rc = fail(HNSW_ERR_HIP, "the trial search failed: %s", hipGetErrorString(e));
     return rc;
 }
@@ -621,14 +619,15 @@ void bind_view(hnsw_index *idx) {
     inf.row_format = bytes ? HNSW_ROWS_BYTES : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
 }
 
-int finish_index(hnsw_index *idx, int32_t expected_ef, int32_t expected_semantics, hnsw_index **out) {
+int finish_index(IndexPtr owned, int32_t expected_ef, int32_t expected_semantics, hnsw_index **out) {
+    hnsw_index *idx = owned.get();
     bind_view(idx);
     int rc = make_byte_rows(idx);           // the index serves searches from the byte copy where the data allows
     if (!rc) rc = make_split_rows(idx);     // ... or from split rows where a row ends just past a 128-byte line
-    if (rc) { hnsw_index_destroy(idx); return rc; }
+    if (rc) return rc;
     (void)warm_up(idx);                     // ... and its first search call does not pay for the process's code loading (an optimisation:
     prepare_quietly(idx, expected_ef, expected_semantics);      //  failures are left to the first search) nor for its shape's one-time decisions
-    *out = idx;
+    *out = owned.release();
     return HNSW_OK;
 }
 
@@ -748,7 +747,7 @@ int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index *
     }
 
     HIP_TRY(hipSetDevice(device));
-    hnsw_index *idx = new hnsw_index();
+    IndexPtr idx(new hnsw_index());
     idx->device = device;
     IndexTables &t = idx->tables;
     // ---- vectors: rows zero-padded to a multiple of 64 B so every float4 chunk is in bounds ----
@@ -758,31 +757,19 @@ int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index *
     if (!rc && hipMemcpy(t.nbr0.p, nbr0.data(), nbr0.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNSW_ERR_OOM, "graph upload failed");
     if (!rc && hipMemcpy(t.nbrU.p, nbrU.data(), nbrU.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNSW_ERR_OOM, "graph upload failed");
     if (!rc) rc = upload_upper_layout(t, 0, ref);
-    if (rc) { hnsw_index_destroy(idx); return rc; }
+    if (rc) return rc;
     IndexView &iv = idx->iv;
     iv.stride = stride; iv.n = n; iv.d = d->d; iv.nchunks = nchunks; iv.S0 = S0; iv.SU = SU; iv.rowsU = rowsU;
     iv.max_layer = d->max_layer; iv.entry_point = (int32_t)ep; iv.id_base = base;
     hnsw_index_info &inf = idx->info;
     inf.d = d->d; inf.metric = d->metric; inf.id_base = base; inf.max_degree = d->max_degree; inf.device = device;
-    return finish_index(idx, d->expected_ef, d->expected_semantics, out);
+    return finish_index(std::move(idx), d->expected_ef, d->expected_semantics, out);
 }
 
 int32_t hnsw_index_destroy(hnsw_index *idx) {
     if (!idx) return HNSW_OK;
-    if (idx->device >= 0) (void)hipSetDevice(idx->device);
-    idx->tables.release();
-    idx->dFbSlab.release(); idx->dFbMap.release();
-    idx->scratch.release();
-    (void)hipDeviceSynchronize();                      // requests never waited for
-    for (hnsw_request *r : idx->all_requests) {
-        r->buf.release();
-        delete r;
-    }
-    for (hipStream_t st : idx->hs) if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t e : idx->tev) (void)hipEventDestroy(e);
-    for (auto &o : idx->order_scratch) if (o.p) (void)hipFree(o.p);
-    if (idx->hFlag) (void)hipHostFree(idx->hFlag);
-    if (idx->hSmall) (void)hipHostFree(idx->hSmall);
+    if (idx->device >= 0) (void)hipSetDevice(idx->device);     // current before any member is freed
+    (void)hipDeviceSynchronize();                               // requests never waited for
     delete idx;
     return HNSW_OK;
 }
@@ -896,7 +883,9 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         const int64_t q = std::min<int64_t>(value / per_query, 65536);
         if (q < 1) return fail(HNSW_ERR_BAD_ARG, "device_fallback_slab_bytes=%lld holds no query: one needs 4 n = %lld bytes", (long long)value, (long long)per_query);
         int rc;
-        if ((rc = idx->dFbSlab.ensure((size_t)(q * per_query))) || (rc = idx->dFbMap.ensure((size_t)(q + 1) * 4))) { idx->dFbSlab.release(); idx->dFbMap.release(); return rc; }
+        DevBuf slab, map;                    // (members only once both exist: a failed allocation leaves both empty)
+        if ((rc = slab.ensure((size_t)(q * per_query))) || (rc = map.ensure((size_t)(q + 1) * 4))) return rc;
+        idx->dFbSlab = std::move(slab); idx->dFbMap = std::move(map);
         idx->fb_queries = q;
         return HNSW_OK;
     }
@@ -966,7 +955,7 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
     const bool small = !zq && !zi && !znd && !znh && qbytes <= SMALL && rbytes <= SMALL && (size_t)nq * 4 <= SMALL;
     if (small) {
         if (!idx->hSmall) {
-            HIP_TRY(hipHostMalloc((void **)&idx->hSmall, 5 * SMALL, hipHostMallocMapped));
+            HIP_TRY(idx->hSmall.alloc(5 * SMALL, hipHostMallocMapped));
             HIP_TRY(hipHostGetDevicePointer((void **)&idx->hSmallDev, idx->hSmall, 0));
         }
         memcpy(idx->hSmall, queries, qbytes);
@@ -1041,11 +1030,11 @@ int32_t hnsw_search_submit(hnsw_index *idx, const float *queries, int64_t nq, in
     HIP_TRY(hipSetDevice(idx->device));
     hnsw_request *r;
     if (!idx->free_requests.empty()) { r = idx->free_requests.back(); idx->free_requests.pop_back(); }
-    else { r = new hnsw_request(); idx->all_requests.push_back(r); }
+    else { idx->all_requests.emplace_back(new hnsw_request()); r = idx->all_requests.back().get(); }
     auto give_back = [&](int code) { idx->free_requests.push_back(r); return code; };
     r->idx = idx; r->nq = nq; r->q_stride = q_stride; r->params = *params;
     r->stream = idx->next_stream; idx->next_stream = (idx->next_stream + 1) & 3;
-    if (!idx->hs[r->stream] && hipStreamCreateWithFlags(&idx->hs[r->stream], hipStreamNonBlocking) != hipSuccess)
+    if (!idx->hs[r->stream] && hipStreamCreateWithFlags(&idx->hs[r->stream].h, hipStreamNonBlocking) != hipSuccess)
         return give_back(fail(HNSW_ERR_HIP, "hipStreamCreate failed"));
     const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d);
     if ((rc = r->buf.ensure(nq, qbytes, params->k))) return give_back(rc);
@@ -1159,7 +1148,7 @@ int32_t hnsw_host_alloc(void **out, int64_t bytes) {
     *out = nullptr;
     void *p = nullptr, *dev = nullptr;
     hipError_t e = hipHostMalloc(&p, (size_t)bytes, hipHostMallocPortable | hipHostMallocMapped);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(e == hipErrorOutOfMemory ? HNSW_ERR_OOM : HNSW_ERR_HIP, "hipHostMalloc(%lld bytes) failed: %s", (long long)bytes, hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipGetLastError(); return hip_fail(e, ("hipHostMalloc(" + std::to_string(bytes) + " bytes)").c_str()); }
     if (hipHostGetDevicePointer(&dev, p, 0) != hipSuccess) { (void)hipGetLastError(); dev = nullptr; }
     remember_range(p, (size_t)bytes, dev, RANGE_ALLOCATED);
     *out = p;

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -74,24 +75,38 @@ inline int hip_fail(hipError_t e, const char *what) {
         if (e__ != hipSuccess) return ::hnsw_host::hip_fail(e__, #expr);    \
     } while (0)
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return HNSW_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        HIP_TRY(hipMalloc(&p, bytes));
-        cap = bytes;
-        return HNSW_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
+// ---- owners ---------------------------------------------------------------------------------------------------------------
+// Every device allocation, page-locked block, stream and event of the host side is held by one of these move-only types, whose
+// destructor frees it (swallowing HIP's answer: a destructor reports nothing and never calls fail()).  A function's scratch is a
+// local owner, so any return frees it; the handles' resources are members.  None may have static or thread-local storage: the
+// runtime can be gone when such a destructor runs.
 
-// One device table of an index and the bytes hnsw_index_info.device_bytes counts for it.  An empty table still gets an
-// allocation (16 bytes at least: kernels may be handed its pointer), which is not counted.
-struct Table {
+// a device allocation and its byte count
+struct DevMem {
     void *p = nullptr;
     size_t bytes = 0;
+    DevMem() = default;
+    DevMem(DevMem &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevMem &operator=(DevMem &&o) noexcept {
+        if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DevMem() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+// ... that grows on demand and is reused (bytes: its capacity)
+struct DevBuf : DevMem {
+    int ensure(size_t need) {
+        if (need <= bytes) return HNSW_OK;
+        release();
+        HIP_TRY(hipMalloc(&p, need));
+        bytes = need;
+        return HNSW_OK;
+    }
+};
+// ... of an exact size, such as one device table of an index: bytes is what hnsw_index_info.device_bytes counts for it.  An empty
+// table still gets an allocation (16 bytes at least: kernels may be handed its pointer), which is not counted.
+struct Table : DevMem {
     hipError_t alloc(size_t b) {
         release();
         const hipError_t e = hipMalloc(&p, std::max<size_t>(b, 16));
@@ -99,7 +114,30 @@ struct Table {
         bytes = b;
         return hipSuccess;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+// ... of one word that a checking kernel sets or clears
+struct DevFlag : DevMem {
+    hipError_t alloc() { release(); return hipMalloc(&p, 16); }
+    hipError_t set(int32_t v) { return hipMemcpy(p, &v, 4, hipMemcpyHostToDevice); }
+    hipError_t get(int32_t *v) const { return hipMemcpy(v, p, 4, hipMemcpyDeviceToHost); }
+};
+// a stream, an event or a page-locked block: the handle h and the call that gives it back
+template <class T, auto Free> struct Owned {
+    T h{};
+    Owned() = default;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = T{}; }
+    Owned &operator=(Owned &&o) noexcept {
+        if (this != &o) { reset(); h = o.h; o.h = T{}; }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void reset() { if (h) (void)Free(h); h = T{}; }
+    operator T() const { return h; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+template <class T> struct Pinned : Owned<T *, hipHostFree> {
+    hipError_t alloc(size_t bytes, unsigned flags) { this->reset(); return hipHostMalloc((void **)&this->h, bytes, flags); }
 };
 
 // Every device table an index holds: the vectors and the graph, and the copies derived from them -- byte rows (X8, hnsw_rows8.hip),
@@ -223,23 +261,25 @@ struct hnsw_index {
     }
     int cus = 0;                         // the device's CUs (0 = not read yet)
     hnsw_host::BatchBufs scratch;                            // scratch for the host-buffer entry points
-    uint32_t *hFlag = nullptr, *hFlagDev = nullptr;          // the same word in pinned host memory (zero-copy calls) and its device address
-    char *hSmall = nullptr, *hSmallDev = nullptr;            // page-locked block for small host-buffer calls (hnsw_search_batch: queries, ids, distances, counters)
+    hnsw_host::Pinned<uint32_t> hFlag;                       // the "any query flagged" word in pinned host memory (zero-copy calls)
+    uint32_t *hFlagDev = nullptr;                            //  and its device address
+    hnsw_host::Pinned<char> hSmall;                          // page-locked block for small host-buffer calls (hnsw_search_batch: queries, ids, distances, counters)
+    char *hSmallDev = nullptr;
     // option "device_fallback_slab_bytes": a slab of the caller's chosen size for the exactness fallback of
     // hnsw_search_batch_device, run on the caller's stream without a host round trip (dFbMap: the flagged queries' list)
     hnsw_host::DevBuf dFbSlab, dFbMap;
     int64_t fb_queries = 0;                                  // how many flagged queries one launch can repair (slab bytes / (4 n))
-    hipStream_t hs[4] = {nullptr, nullptr, nullptr, nullptr}; // streams of the chunked host-buffer search and of requests (lazy)
+    hnsw_host::Stream hs[4];                                 // streams of the chunked host-buffer search and of requests (lazy)
     std::vector<hnsw_request *> free_requests;               // finished requests keep their buffers for the next submit
-    std::vector<hnsw_request *> all_requests;                // every request ever created (released with the index)
+    std::vector<std::unique_ptr<hnsw_request>> all_requests; // every request ever created (released with the index)
     int live_requests = 0, next_stream = 0;
     bool time_kernels = false;           // option "time_kernels": event triples around the launches of each device-entry call
-    std::vector<hipEvent_t> tev;         // [3 * recorded calls]: before the pre-pass, before the search kernel, after it
+    std::vector<hnsw_host::Event> tev;        // [3 * recorded calls]: before the pre-pass, before the search kernel, after it
     size_t tev_used = 0;
     std::vector<char> tev_ordered;       // per recorded call: did the ordering pre-pass run
     // scratch of the ordering pre-pass, one block per caller stream (kept between calls: work on one
     // stream is ordered, so the block is free again when the next call on that stream needs it)
-    struct OrderScratch { hipStream_t st; void *p; size_t bytes; };
+    struct OrderScratch { hipStream_t st; hnsw_host::Table block; };
     std::vector<OrderScratch> order_scratch;
     int order_mode = -1;                 // option "order_queries": -1 automatic (batches larger than half of what the chip holds: resident_queries), 0 never, 1 always
     int vt_bits_override = 0;
@@ -258,14 +298,18 @@ struct hnsw_index {
 
 namespace hnsw_host {
 
+// a handle under construction: destroyed unless released to the caller
+struct IndexDeleter { void operator()(::hnsw_index *idx) const { (void)hnsw_index_destroy(idx); } };
+using IndexPtr = std::unique_ptr<::hnsw_index, IndexDeleter>;
+
 // hnsw_capi.hip: IndexView's table pointers from idx->tables (X8 / Xm left out while option byte_rows / split_rows is 0; Xh in
 // the view while option half_rows is 1 and no byte rows are: it takes the place of Xm), and the hnsw_index_info fields that
 // restate the view (n, max_degree0, max_layer, entry_point, row_stride_bytes, row_format).  Called by every change of the tables
 // or of those options.
 void bind_view(::hnsw_index *idx);
 // hnsw_capi.hip: the end of hnsw_index_create and hnsw_build, once the graph tables are complete: the view bound, the row copies
-// made, the first search's one-time costs paid.  *out = idx on success; on an error idx is destroyed.
-int finish_index(::hnsw_index *idx, int32_t expected_ef, int32_t expected_semantics, ::hnsw_index **out);
+// made, the first search's one-time costs paid.  *out = idx on success.
+int finish_index(IndexPtr idx, int32_t expected_ef, int32_t expected_semantics, ::hnsw_index **out);
 
 // hnsw_rows8.hip: if every value of tables.X is an integer in 0..255, build the byte copy (tables.X8, iv.stride8)
 int make_byte_rows(::hnsw_index *idx);
@@ -358,7 +402,6 @@ int rerun_overflowed(hnsw_index *idx, int64_t nq, const uint32_t *d_status, Laun
     const int64_t n = idx->iv.n;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(256, (512ll << 20) / (n * 4 + 1)));
     DevBuf dMap, dSlab;
-    struct Guard { DevBuf &a, &b; ~Guard() { a.release(); b.release(); } } guard{dMap, dSlab};
     int rc;
     if ((rc = dMap.ensure((size_t)chunk * 4)) || (rc = dSlab.ensure((size_t)chunk * n * 4))) return rc;
     for (size_t f0 = 0; f0 < flagged.size(); f0 += (size_t)chunk) {

@@ -213,7 +213,6 @@ int32_t hnsw_search_layer_batch(hnsw_index *idx, int32_t layer, const float *tar
     const int k = p->k;
     const size_t qbytes = ((size_t)(nq - 1) * t_stride + idx->iv.d) * sizeof(float);
     DevBuf dStart, dCnt;
-    struct Guard { DevBuf &a, &b; ~Guard() { a.release(); b.release(); } } guard{dStart, dCnt};
     if ((rc = idx->scratch.ensure(nq, qbytes, k)) || (rc = dStart.ensure(st.size() * 4)) || (rc = dCnt.ensure((size_t)nq * 4)))
         return rc;
     HIP_TRY(hipMemcpy(idx->scratch.q.p, targets, qbytes, hipMemcpyHostToDevice));

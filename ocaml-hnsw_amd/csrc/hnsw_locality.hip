@@ -59,7 +59,6 @@ static int build_codes(::hnsw_index *idx) {
     const int ef_b = 32;
     const int id_base = idx->iv.id_base;
     DevBuf entry, scratch, best, bdist, qmap;
-    struct Guard { DevBuf &a, &b, &c, &d, &e; ~Guard() { a.release(); b.release(); c.release(); d.release(); e.release(); } } guard{entry, scratch, best, bdist, qmap};
     int rc;
     if ((rc = entry.ensure((size_t)n * 4)) || (rc = scratch.ensure((size_t)n * 16)) || (rc = best.ensure((size_t)n * 4)) ||
         (rc = bdist.ensure((size_t)n * 4)) || (rc = qmap.ensure((size_t)n * 4)))

@@ -65,13 +65,13 @@ struct hnsw_multi {
                                           // one device: tests) the gather is device-to-device copies
     RcclApi rccl;
     std::vector<ncclComm_t> comms;        // [G], created at the first device-resident search
-    std::vector<hipStream_t> streams;     // [G]
-    std::vector<hipEvent_t> done;         // [G] "this device's search is enqueued up to here" (the same-device copy arrangement)
+    std::vector<Stream> streams;          // [G]
+    std::vector<Event> done;              // [G] "this device's search is enqueued up to here" (the same-device copy arrangement)
     // per device: its query shard; the FULL [nq][k] result; per-shard counters; the launch's "any query flagged" word (see
     // hnsw_search_batch)
     std::vector<BatchBufs> buf;
     int64_t last_nq = 0; int last_k = 0;
-    uint32_t *hFlags = nullptr;           // [G] pinned host words the flags are copied into
+    Pinned<uint32_t> hFlags;              // [G] pinned host words the flags are copied into
     // what the exchanges of this handle were made of (hnsw_multi_debug_counters): calls issued, summed over the devices
     int64_t n_allgather = 0, n_broadcast = 0, n_peer_copies = 0, n_repaired_shards = 0;
 };
@@ -87,15 +87,15 @@ namespace {
 int ensure_streams(hnsw_multi *m) {
     const size_t G = m->replicas.size();
     if (m->streams.size() == G) return HNSW_OK;
-    m->streams.assign(G, nullptr);
+    m->streams.resize(G);
     m->buf.resize(G);
-    if (!m->hFlags) HIP_TRY(hipHostMalloc((void **)&m->hFlags, G * sizeof(uint32_t), hipHostMallocPortable));
+    if (!m->hFlags) HIP_TRY(m->hFlags.alloc(G * sizeof(uint32_t), hipHostMallocPortable));
     for (size_t g = 0; g < G; ++g) {
         HIP_TRY(hipSetDevice(m->devices[g]));
-        HIP_TRY(hipStreamCreateWithFlags(&m->streams[g], hipStreamNonBlocking));
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        m->done.push_back(e);
+        HIP_TRY(hipStreamCreateWithFlags(&m->streams[g].h, hipStreamNonBlocking));
+        Event e;
+        HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+        m->done.push_back(std::move(e));
     }
     return HNSW_OK;
 }
@@ -304,10 +304,9 @@ int32_t hnsw_multi_destroy(hnsw_multi *m) {
     for (size_t g = 0; g < m->streams.size(); ++g) {
         (void)hipSetDevice(m->devices[g]);
         m->buf[g].release();
-        if (m->streams[g]) (void)hipStreamDestroy(m->streams[g]);
-        if (g < m->done.size()) (void)hipEventDestroy(m->done[g]);
+        m->streams[g].reset();
+        if (g < m->done.size()) m->done[g].reset();
     }
-    if (m->hFlags) (void)hipHostFree(m->hFlags);
     for (hnsw_index *idx : m->replicas) (void)hnsw_index_destroy(idx);
     delete m;
     return HNSW_OK;

@@ -139,15 +139,14 @@ int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, i
     // the handle keeps one scratch block per caller stream; it only ever grows
     hnsw_index::OrderScratch *sc = nullptr;
     for (auto &o : idx->order_scratch) if (o.st == st) sc = &o;
-    if (!sc) { idx->order_scratch.push_back({st, nullptr, 0}); sc = &idx->order_scratch.back(); }
-    if (sc->bytes < need) {
-        if (sc->p) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(sc->p); sc->p = nullptr; sc->bytes = 0; }
+    if (!sc) { idx->order_scratch.push_back({st, {}}); sc = &idx->order_scratch.back(); }
+    if (sc->block.bytes < need) {
+        if (sc->block.p) HIP_TRY(hipStreamSynchronize(st));      // (the block is freed by alloc)
         const size_t grow = need + need / 4;
-        hipError_t me = hipMalloc(&sc->p, grow);
-        if (me != hipSuccess) { (void)hipGetLastError(); sc->p = nullptr; return fail(me == hipErrorOutOfMemory ? HNSW_ERR_OOM : HNSW_ERR_HIP, "hipMalloc(%zu) for the ordering pre-pass failed", grow); }
-        sc->bytes = grow;
+        const hipError_t me = sc->block.alloc(grow);
+        if (me != hipSuccess) return fail(me == hipErrorOutOfMemory ? HNSW_ERR_OOM : HNSW_ERR_HIP, "hipMalloc(%zu) for the ordering pre-pass failed", grow);
     }
-    char *base = (char *)sc->p;
+    char *base = (char *)sc->block.p;
     hipError_t e;
     int32_t *entry = (int32_t *)(base + 0 * slot);
     uint32_t *key = (uint32_t *)(base + 1 * slot), *nd = (uint32_t *)(base + 2 * slot);

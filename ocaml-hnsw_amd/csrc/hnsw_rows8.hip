@@ -52,19 +52,17 @@ int make_byte_rows(::hnsw_index *idx) {
     const int64_t n = idx->iv.n;
     const int32_t d = idx->iv.d;
     const int32_t row_bytes = 64 * pick_nch(idx->iv.nchunks);     // the lane grid of the kernel: 16 lanes x NCH dwords
-    int32_t *dflag = nullptr;
-    HIP_TRY(hipMalloc((void **)&dflag, 16));
-    const int32_t one = 1;
+    DevFlag flag;
     int32_t ok = 0;
-    hipError_t e = hipMemcpy(dflag, &one, 4, hipMemcpyHostToDevice);
+    HIP_TRY(flag.alloc());
+    hipError_t e = flag.set(1);
     if (e == hipSuccess) {
         const int blocks = (int)std::min<int64_t>(65536, (n * (int64_t)d + 255) / 256);
         hipLaunchKernelGGL(rows_are_bytes_kernel, dim3((unsigned)std::max(1, blocks)), dim3(256), 0, 0,
-                           (const float *)idx->tables.X.p, idx->iv.stride, n, d, dflag);
+                           (const float *)idx->tables.X.p, idx->iv.stride, n, d, (int32_t *)flag.p);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpy(&ok, dflag, 4, hipMemcpyDeviceToHost);
-    (void)hipFree(dflag);
+    if (e == hipSuccess) e = flag.get(&ok);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "byte-row check failed: %s", hipGetErrorString(e));
     if (!ok) return HNSW_OK;
     Table &X8 = idx->tables.X8;
