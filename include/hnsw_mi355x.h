@@ -30,6 +30,8 @@
  *   hnsw_build               Ohnsw.build_batch_bigarray (lib/ohnsw.ml:840-857), batched on the device
  *   hnsw_index_insert        Ohnsw.insert (lib/ohnsw.ml:766-837) of m vectors into an index the library holds
  *   hnsw_brute_force_batch   brute_force_knn_l2 (benchmark/dataset.ml:15-30): the exact scan recall is measured against
+ *   hnsw_rerank_batch        (nothing in the reference) the k nearest of caller-given candidates over the float32 vectors:
+ *                            the refine step of the half-row searches (option "refine")
  *   hnsw_host_alloc / hnsw_host_register   (nothing in the reference) page-locked query / result matrices,
  *                            which the entry points above read and write from the device in place
  *
@@ -249,7 +251,33 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   The builder, hnsw_index_insert's searches, the layer operators and hnsw_distance_batch keep reading
  *                   the float32 rows.  hnsw_index_insert makes the copy again for the grown index (new vectors out of
  *                   range: the whole insert is refused).  Not saved: a loaded index starts without half rows.
- *                   (Hand-scheduled loops exist for the other row formats only: half rows run the C++ hop loop.) */
+ *                   (Hand-scheduled loops exist for the other row formats only: half rows run the C++ hop loop.)
+ * and one that gives the half-row searches float32 answers again (off by default):
+ *   "refine"        0 = off (default: behaviour is exactly as without the option); R in 1..1024 = a candidate count; -1 = all
+ *                   of W; anything else is HNSW_ERR_BAD_ARG.  While the knn searches read the half rows, a search of (ef, k)
+ *                     1. runs the half-row search unchanged,
+ *                     2. takes the first c = min(ef, max(k, R)) members of W (c = ef for -1) -- W holds ef candidates where the
+ *                        caller asked for k --,
+ *                     3. re-ranks those c over the FLOAT32 rows (hnsw_rerank_batch's kernel: the summation order every
+ *                        distance-returning entry point shares) and
+ *                     4. returns the first k under (distance, node id).
+ *                   So: the candidate set is the half-row search's (the search over Xh with k := c), the returned distances
+ *                   are the bits of hnsw_distance_batch for their own vectors, equal distances come lowest id first, and no
+ *                   query's id-set recall over X is below that of its unrefined half-row answer (with -1 it is
+ *                   |truth and W| / k).  out_nhops is unchanged; out_ndist is the walk's count PLUS the number of
+ *                   candidates re-evaluated.  The re-rank runs behind the tie-overflow repair (host forms) or the device
+ *                   fallback slab.  It applies to hnsw_search_batch, _device, _h2d, hnsw_search_submit / _wait, hnsw_knn and,
+ *                   through a replica's handle (hnsw_multi_replica: where "half_rows" is set too), to hnsw_multi_search_batch.
+ *                   The walk's [nq][c] results live in scratch the handle owns (per request for submit / wait), sized on
+ *                   demand and not counted in device_bytes: with refine active ONE hnsw_search_batch_device /
+ *                   hnsw_search_batch_h2d call in flight per handle (calls on one stream are ordered and therefore fine).
+ *                   While the searches read any other rows (bytes, split, float32) the option is accepted and does nothing:
+ *                   those distances are exact over X already, results and out_ndist are bit-identical to refine 0; set
+ *                   before "half_rows" it takes effect when half rows are turned on.  HNSW_SEM_FUNCTOR_NEAREST_K with refine
+ *                   active is HNSW_ERR_BAD_ARG ("the k farthest of W" has no refined meaning).  hnsw_index_insert keeps the
+ *                   setting; it is not saved (neither is "half_rows").  COST: c float32 rows per query on top of the walk's
+ *                   roughly 950 to 2400 half-row evaluations (the benchmark's float shapes); the rate has not been measured
+ *                   yet (tools/refine_rate.py prints the table that belongs beside profiles/half_rows.txt). */
 int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value);
 /* Bytes of one vector as the knn searches read it: d for byte rows, 2 * d for half rows, 4 * d for float32 rows. */
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes);
@@ -368,6 +396,28 @@ int32_t hnsw_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq
                                int32_t k, int32_t fill, int32_t *out_ids, float *out_dist);
 int32_t hnsw_brute_force_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
                                       int32_t k, int32_t fill, int32_t *d_ids, float *d_dist, void *stream);
+
+/* Exact re-ranking of caller-given candidates (the refine step of option "refine" as an operator of its own): for query q the
+ * candidates cand[q][0 .. cand_stride) (id_base-based) are evaluated against the FLOAT32 vectors -- whatever
+ * hnsw_index_info.row_format says -- and the k smallest under the total order (distance, node id) come back ascending in
+ * out_ids [nq][k] (id_base-based) and out_dist [nq][k]: the order of hnsw_brute_force_batch restricted to the candidates, the
+ * distance bits of hnsw_distance_batch for the same pair (same lanes, fmaf order and tree).
+ *   - Candidates: entries < id_base are padding and skipped (lists may be ragged), as hnsw_search_layer_batch treats start
+ *     nodes; the ids of a row must be distinct.  With fewer than k real candidates the first entries are real and the rest
+ *     filled: HNSW_FILL_OHNSW = id -1 and distance NaN, HNSW_FILL_BA = id -1 and +inf.
+ *   - Limits: cand_stride in 1..1024 (> 1024: HNSW_ERR_UNSUPPORTED), k in 1..cand_stride; k < 1, k > cand_stride and an unknown
+ *     fill are HNSW_ERR_BAD_ARG.  nq, q_stride and null pointers as hnsw_search_batch (nq == 0 is a no-op).
+ *   - Host form: an id >= id_base + n is HNSW_ERR_BAD_ARG, checked before any launch; matrices of hnsw_host_alloc /
+ *     hnsw_host_register are read and written in place, others are copied; complete on return.  Device form: asynchronous on
+ *     `stream`, uses no scratch of the handle; an id >= id_base + n is skipped like padding.
+ *   - Graph: none is needed (a flat index can be re-ranked); after hnsw_index_insert the new nodes are candidates like any other.
+ *   - Determinism: a query's result depends on its own candidates only, not on the batch it is in. */
+int32_t hnsw_rerank_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
+                          const int32_t *cand, int32_t cand_stride, int32_t k, int32_t fill,
+                          int32_t *out_ids, float *out_dist);
+int32_t hnsw_rerank_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
+                                 const int32_t *d_cand, int32_t cand_stride, int32_t k, int32_t fill,
+                                 int32_t *d_ids, float *d_dist, void *stream);
 
 /* ---- the layer-level functions of the path, as batched operators -------------------------------
  * hnsw_search_layer_batch = Ohnsw.search_k (lib/ohnsw.ml:543-588; params->semantics = OHNSW) or

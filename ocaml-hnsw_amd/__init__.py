@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "hnsw_multi_search_batch_device", "hnsw_multi_copy_result", "hnsw_multi_debug_counters",
     "hnsw_host_register", "hnsw_host_unregister", "hnsw_host_alloc", "hnsw_host_free",
     "hnsw_brute_force_batch", "hnsw_brute_force_batch_device",
+    "hnsw_rerank_batch", "hnsw_rerank_batch_device",
 ]
 
 
@@ -123,6 +124,9 @@ def load():
     L.hnsw_brute_force_batch.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp]
     L.hnsw_brute_force_batch_device.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp, vp]
     L.hnsw_brute_force_batch.restype = L.hnsw_brute_force_batch_device.restype = i32
+    L.hnsw_rerank_batch.argtypes = [vp, vp, i64, i64, vp, i32, i32, i32, vp, vp]
+    L.hnsw_rerank_batch_device.argtypes = [vp, vp, i64, i64, vp, i32, i32, i32, vp, vp, vp]
+    L.hnsw_rerank_batch.restype = L.hnsw_rerank_batch_device.restype = i32
     L.hnsw_build.argtypes = [vp, i64, i32, i64, vp, i32, vp]
     L.hnsw_index_insert.argtypes = [vp, vp, i64, i64, vp]
     L.hnsw_select_neighbours_batch.argtypes = [vp, vp, i64, i64, vp, vp, i32, i32, i32, vp, vp, vp]
@@ -559,6 +563,13 @@ def brute_force_device(hgraph, d_queries, nq, q_stride, k, d_ids, d_dist, fill=F
     _check(load().hnsw_brute_force_batch_device(hgraph.handle, d_queries, nq, q_stride, k, fill, d_ids, d_dist, stream or None))
 
 
+def rerank_device(hgraph, d_queries, nq, q_stride, d_cand, cand_stride, k, d_ids, d_dist, fill=FILL_OHNSW, stream=0):
+    """hnsw_rerank_batch_device: the exact re-rank of given candidates on device pointers (ints), asynchronous on HIP stream
+    `stream`."""
+    _check(load().hnsw_rerank_batch_device(hgraph.handle, d_queries, nq, q_stride, d_cand, cand_stride, k, fill, d_ids, d_dist,
+                                           stream or None))
+
+
 def search_batch_h2d(hgraph, batch, ef, k, d_ids, d_dist, d_ndist=0, d_nhops=0, d_status=0, stream=0,
                      fill=FILL_OHNSW, sem=SEM_OHNSW):
     """hnsw_search_batch_h2d: queries from a HOST matrix (read by the device directly when it was registered with pin()),
@@ -609,6 +620,31 @@ class Ohnsw:
             ids = _np.empty((nq, max(k, 0)), _np.int32)
             dist = _np.empty((nq, max(k, 0)), _np.float32)
         _check(load().hnsw_brute_force_batch(hgraph.handle, _ptr(Q), nq, max(qs, hgraph.d), k, fill, _ptr(ids), _ptr(dist)))
+        return ids, dist
+
+    @staticmethod
+    def rerank(hgraph, k, batch, cand, fill=FILL_OHNSW, out=None):
+        """hnsw_rerank_batch -> (ids, distances): for each query the k nearest of ITS candidates cand[q] (int32 [nq][cand_stride],
+        entries below id_base are padding) over the float32 vectors, under (distance, id), ascending; ids [nq][k] (-1 past the
+        real candidates), distances [nq][k] fp32 (NaN there; FILL_BA: +inf).  What option "refine" does to the half-row
+        searches' candidates.  Needs no graph.  out = (ids, distances): write into the caller's matrices instead of fresh ones."""
+        Q, qs = _rows(batch)
+        if Q.ndim != 2 or (Q.shape[0] and Q.shape[1] != hgraph.d):
+            raise InvalidArgument("batch must be [nq][d]")
+        nq, k = Q.shape[0], int(k)
+        C = _np.ascontiguousarray(cand, _np.int32)
+        if C.ndim != 2 or C.shape[0] != nq:
+            raise InvalidArgument("cand must be [nq][cand_stride]")
+        if out is not None:
+            ids, dist = out
+            if ids.shape != (nq, k) or dist.shape != (nq, k) or ids.dtype != _np.int32 or dist.dtype != _np.float32 \
+                    or not ids.flags["C_CONTIGUOUS"] or not dist.flags["C_CONTIGUOUS"]:
+                raise InvalidArgument("out must be (int32 [nq][k], float32 [nq][k]), C-contiguous")
+        else:
+            ids = _np.empty((nq, max(k, 0)), _np.int32)
+            dist = _np.empty((nq, max(k, 0)), _np.float32)
+        _check(load().hnsw_rerank_batch(hgraph.handle, _ptr(Q), nq, max(qs, hgraph.d), _ptr(C), C.shape[1], k, fill,
+                                        _ptr(ids), _ptr(dist)))
         return ids, dist
 
     @staticmethod

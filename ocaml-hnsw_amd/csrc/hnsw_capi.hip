@@ -440,6 +440,26 @@ void launch_priorities(hnsw_index *idx, const KnnShape &sh, int64_t nq, SearchAr
     if (nq > resident && nq < 2 * resident) a.prio_tail = (int32_t)resident;
 }
 
+// Option "refine": how many members of W a search of (ef, k) re-ranks over the float32 rows, 0 = none -- the option is off, or the
+// searches read rows whose distances are exact over X already (bytes, split, float32)
+int refine_count(const hnsw_index *idx, const hnsw_search_params *p) {
+    if (idx->refine == 0 || idx->info.row_format != HNSW_ROWS_HALF) return 0;
+    return idx->refine < 0 ? p->ef : std::min(p->ef, std::max(p->k, idx->refine));
+}
+// ... the walk of such a search: b with k := c, its results and evaluation counts in `walk`
+int refine_walk(const KnnBatch &b, int c, RefineBufs &walk, KnnBatch *wb) {
+    const int rc = walk.ensure(b.nq, c);
+    if (rc) return rc;
+    *wb = b;
+    wb->ids = (int32_t *)walk.ids.p; wb->dist = (float *)walk.dist.p;
+    if (b.nd) wb->nd = (uint32_t *)walk.nd.p;
+    return HNSW_OK;
+}
+// ... and its second half: the c candidates per query re-ranked into b's [nq][k] arrays, b.nd = the walk's count + the candidates
+int refine_rerank(hnsw_index *idx, const hnsw_search_params &p, const KnnBatch &b, const KnnBatch &wb, int c, hipStream_t st) {
+    return launch_rerank(idx, b.Q, b.nq, b.q_stride, wb.ids, c, p.k, p.fill, b.ids, b.dist, b.nd ? wb.nd : nullptr, b.nd, st);
+}
+
 int check_params(const hnsw_index *idx, const hnsw_search_params *p) {
     if (!idx) return fail(HNSW_ERR_BAD_ARG, "null index");
     if (!p) return fail(HNSW_ERR_BAD_ARG, "null params");
@@ -451,6 +471,8 @@ int check_params(const hnsw_index *idx, const hnsw_search_params *p) {
     if (p->fill != HNSW_FILL_OHNSW && p->fill != HNSW_FILL_BA) return fail(HNSW_ERR_BAD_ARG, "bad fill %d", p->fill);
     if (p->semantics != HNSW_SEM_OHNSW && p->semantics != HNSW_SEM_FUNCTOR && p->semantics != HNSW_SEM_FUNCTOR_NEAREST_K)
         return fail(HNSW_ERR_BAD_ARG, "bad semantics %d", p->semantics);
+    if (p->semantics == HNSW_SEM_FUNCTOR_NEAREST_K && refine_count(idx, p) > 0)
+        return fail(HNSW_ERR_BAD_ARG, "option refine is active: the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no refined meaning");
     if (idx->iv.entry_point < 0) return fail(HNSW_ERR_EMPTY_INDEX, "knn: empty hgraph");
     return HNSW_OK;
 }
@@ -480,10 +502,20 @@ int launch_rerun(hnsw_index *idx, const hnsw_search_params &p, const KnnBatch &b
     return launch_search_args(idx, sh, a, st);
 }
 
-int knn_search(hnsw_index *idx, const hnsw_search_params *params, const KnnBatch &b, hipStream_t st, float *d_stage) {
-    int rc = check_batch(idx, params, b.nq, b.q_stride, b.Q && b.ids && b.dist);
-    if (rc || b.nq == 0) return rc;
+int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const KnnBatch &caller_b, hipStream_t st, float *d_stage,
+               RefineBufs *walk) {
+    int rc = check_batch(idx, caller_params, caller_b.nq, caller_b.q_stride, caller_b.Q && caller_b.ids && caller_b.dist);
+    if (rc || caller_b.nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
+    // refine active: everything below is today's search with k := c into the walk's scratch; the re-rank at the end answers the caller
+    const int refine_c = refine_count(idx, caller_params);
+    hnsw_search_params walk_params = *caller_params;
+    KnnBatch b = caller_b;
+    if (refine_c > 0) {
+        walk_params.k = refine_c;
+        if ((rc = refine_walk(caller_b, refine_c, walk ? *walk : idx->refine_scratch, &b))) return rc;
+    }
+    const hnsw_search_params *params = &walk_params;
     const KnnShape sh = knn_shape(idx, params->ef, params->semantics);
     SearchArgs a = knn_args(*params, b, knn_vt_bits(idx, sh), knn_blk_bits(idx, sh));
     // A batch larger than the chip holds at once is searched longest walk first (hnsw_order.hip):
@@ -527,6 +559,11 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *params, const KnnBatch
         rc = launch_rerun(idx, *params, read, (const int32_t *)idx->dFbMap.p, std::min<int64_t>(cap, b.nq), (uint32_t *)idx->dFbSlab.p,
                           (int32_t)std::min<int64_t>(idx->iv.n, 0x7FFFFFFF), st);
     }
+    if (!rc && refine_c > 0) {              // (behind the device fallback; reads the queries as the search read them)
+        KnnBatch to = caller_b;
+        to.Q = a.Q;
+        rc = refine_rerank(idx, *caller_params, to, b, refine_c, st);
+    }
     if (ev && !rc) {
         HIP_TRY(hipEventRecord(ev[2], st));
         idx->tev_used += 3;                 // an early return above leaves the triple unclaimed: nothing half-recorded is ever read
@@ -536,10 +573,25 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *params, const KnnBatch
     return rc;
 }
 
-int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st) {
-    return rerun_overflowed(idx, b.nq, b.st, [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
-        return launch_rerun(idx, *p, b, qmap, c, slab, cap, st);
+int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk) {
+    const int refine_c = refine_count(idx, p);
+    hnsw_search_params wp = *p;
+    KnnBatch wb = b;
+    if (refine_c > 0) {                     // the walk's results are where knn_search left them: its flagged rows are rewritten there
+        wp.k = refine_c;
+        const int rc = refine_walk(b, refine_c, walk ? *walk : idx->refine_scratch, &wb);
+        if (rc) return rc;
+    }
+    const int rc = rerun_overflowed(idx, b.nq, b.st, [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
+        return launch_rerun(idx, wp, wb, qmap, c, slab, cap, st);
     });
+    if (rc || refine_c == 0) return rc;
+    // every query again (the same answer for those not repaired), and complete on return as the re-run is: callers go on to
+    // other streams (hnsw_multi's exchange)
+    const int rr = refine_rerank(idx, *p, b, wb, refine_c, st);
+    if (rr) return rr;
+    HIP_TRY(hipStreamSynchronize(st));
+    return HNSW_OK;
 }
 
 hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st) {
@@ -867,6 +919,11 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         idx->forget_shapes();
         return HNSW_OK;
     }
+    if (!strcmp(name, "refine")) {        // 0: off; 1..1024: re-rank max(k, value) members of W over the float32 rows; -1: all ef (half rows only)
+        if (value < -1 || value > 1024) return fail(HNSW_ERR_BAD_ARG, "refine=%lld: 0 (off), 1..1024 candidates or -1 (all of W)", (long long)value);
+        idx->refine = (int)value;
+        return HNSW_OK;
+    }
     if (!strcmp(name, "time_kernels")) { idx->time_kernels = value != 0; return HNSW_OK; }
     if (!strcmp(name, "visited_blocks")) {   // -1: measured per kernel shape (default); 0: the tag cache; 1: bitmap blocks wherever the codes can be built
         idx->blk_mode = value < 0 ? -1 : (value ? 1 : 0);
@@ -1044,7 +1101,7 @@ int32_t hnsw_search_submit(hnsw_index *idx, const float *queries, int64_t nq, in
         return give_back(fail(HNSW_ERR_HIP, "query upload failed"));
     range_reader_enqueued(queries, qbytes, st);    // page-locked source: the DMA above outlives this call (see hnsw_host_unregister)
     if (hipMemsetAsync(b.any_flag, 0, 4, st) != hipSuccess) return give_back(fail(HNSW_ERR_HIP, "hipMemsetAsync failed"));
-    if ((rc = knn_search(idx, params, b, st))) return give_back(rc);
+    if ((rc = knn_search(idx, params, b, st, nullptr, &r->refine))) return give_back(rc);
     // the results follow the search on the request's stream: hnsw_search_wait only has to wait for them
     idx->live_requests++;
     *out = r;
@@ -1072,7 +1129,7 @@ int32_t hnsw_search_wait(hnsw_request *r, int32_t *out_ids, float *out_dist, uin
     { const hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess) e = es; }
     if (e != hipSuccess) return done(fail(HNSW_ERR_HIP, "search failed: %s", hipGetErrorString(e)));
     if (!(flag & 1u)) return done(HNSW_OK);
-    const int rc = knn_repair(idx, &r->params, b, st);
+    const int rc = knn_repair(idx, &r->params, b, st, &r->refine);
     if (rc) return done(rc);
     e = knn_download(b, k, out_ids, out_dist, out_ndist, out_nhops, st);
     { const hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess) e = es; }

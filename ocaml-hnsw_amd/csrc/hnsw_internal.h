@@ -187,6 +187,18 @@ struct BatchBufs {
     void release() { for (DevBuf *b : {&q, &ids, &dist, &nd, &nh, &st, &flag, &scan}) b->release(); }
 };
 
+// the walk's side of a refined search (option "refine"): the first c members of W per query -- ids and distances [nq][c] -- and the
+// walk's evaluation counts [nq], which the re-rank reads; ids also stages hnsw_rerank_batch's candidates.  Not index tables: not
+// counted in device_bytes.
+struct RefineBufs {
+    DevBuf ids, dist, nd;
+    int ensure(int64_t nq, int c) {
+        int rc;
+        if ((rc = ids.ensure((size_t)nq * c * 4)) || (rc = dist.ensure((size_t)nq * c * 4)) || (rc = nd.ensure((size_t)nq * 4))) return rc;
+        return HNSW_OK;
+    }
+};
+
 inline int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
     return (s && *s) ? atoi(s) : dflt;
@@ -235,6 +247,7 @@ struct hnsw_request {
     int64_t nq = 0, q_stride = 0;
     hnsw_search_params params{};
     hnsw_host::BatchBufs buf;
+    hnsw_host::RefineBufs refine;        // its walk's results while option "refine" is active
     int stream = 0;
 };
 
@@ -293,6 +306,11 @@ struct hnsw_index {
     // option "half_rows": the knn searches read tables.Xh (1), or it is off (0, -1).  Not a default: half rows change results.
     // hnsw_index_insert makes the copy again while it is on.
     bool half_rows_on = false;
+    // option "refine": 0 off; 1..1024 / -1: while the knn searches read the half rows, the head of W (max(k, refine) members, -1: all
+    // ef) is re-ranked over the float32 rows (refine_count, hnsw_rerank.hip).  refine_scratch: the walk's results of the calls that
+    // bring no scratch of their own (every entry point but submit / wait).
+    int refine = 0;
+    hnsw_host::RefineBufs refine_scratch;
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
 };
 
@@ -361,11 +379,18 @@ int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, i
 // hnsw_capi.hip: parameter / handle checks shared by every search entry point (HNSW_ERR_BAD_ARG, HNSW_ERR_EMPTY_INDEX, ...)
 int check_params(const ::hnsw_index *idx, const hnsw_search_params *p);
 // hnsw_capi.hip: hnsw_search_batch_device for a KnnBatch, whose any_flag word (optional) collects status bit 0 of the launch.
-// d_stage (optional, [nq][q_stride] device floats): b.Q points into registered host memory (see order_longest_first)
-int knn_search(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, float *d_stage = nullptr);
+// d_stage (optional, [nq][q_stride] device floats): b.Q points into registered host memory (see order_longest_first).
+// While option "refine" is active (refine_count) the walk writes its first c members of W into `walk` (null: the handle's
+// refine_scratch) and the re-rank kernel, queued behind it, writes b's ids, distances and evaluation counts.
+int knn_search(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, float *d_stage = nullptr,
+               RefineBufs *walk = nullptr);
 // hnsw_capi.hip: the exactness fallback of the host-buffer entry points (see rerun_overflowed) for a batch knn_search ran:
-// rewrites the rows of the queries it flagged in b.st
-int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st);
+// rewrites the rows of the queries it flagged in b.st (refine active: their rows of `walk`, then the batch is re-ranked again)
+int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk = nullptr);
+// hnsw_rerank.hip: the re-rank kernel on `st` for device-resident arguments (hnsw_rerank_batch_device, unchecked); nd_out
+// (optional): nd_out[q] = (nd_in ? nd_in[q] : 0) + the number of candidates evaluated
+int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, const int32_t *cand, int32_t cand_stride, int32_t k,
+                  int32_t fill, int32_t *out_ids, float *out_dist, const uint32_t *nd_in, uint32_t *nd_out, hipStream_t st);
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
 hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st);
 // hnsw_capi.hip: the handle's stream (hs[0]) and flag word of the host-buffer calls, made on first use

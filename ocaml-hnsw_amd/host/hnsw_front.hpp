@@ -2,6 +2,7 @@
 // over the C ABI of include/hnsw_mi355x.h (header only; link with libhnsw_mi355x.so).
 //
 //   Hnsw::Ohnsw::knn / knn_batch_bigarray / build_batch_bigarray / insert / distance_l2   lib/ohnsw.ml:766-899
+//   Hnsw::Ohnsw::rerank                                                                    (hnsw_rerank_batch; nothing in the reference)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
@@ -195,6 +196,16 @@ inline std::pair<std::vector<int32_t>, std::vector<float>> brute_force_knn(const
     std::vector<int32_t> ids((size_t)batch.dim2 * (size_t)(k > 0 ? k : 0));
     std::vector<float> dist(ids.size());
     check(hnsw_brute_force_batch(g.handle(), batch.data, batch.dim2, batch.dim1, k, HNSW_FILL_OHNSW, ids.data(), dist.data()));
+    return {std::move(ids), std::move(dist)};
+}
+
+// The exact re-rank (hnsw_rerank_batch): for each query the k nearest of ITS candidates cand[q][0 .. cand_stride) (entries below
+// id_base are padding) over the float32 vectors, under (distance, id), ascending -> (ids, distances), both [nq][k] (-1 / NaN past
+// a query's real candidates).  What option "refine" does to the half-row searches' candidates.
+inline std::pair<std::vector<int32_t>, std::vector<float>> rerank(const Hgraph &g, int k, const Mat &batch, const int32_t *cand, int cand_stride) {
+    std::vector<int32_t> ids((size_t)batch.dim2 * (size_t)(k > 0 ? k : 0));
+    std::vector<float> dist(ids.size());
+    check(hnsw_rerank_batch(g.handle(), batch.data, batch.dim2, batch.dim1, cand, cand_stride, k, HNSW_FILL_OHNSW, ids.data(), dist.data()));
     return {std::move(ids), std::move(dist)};
 }
 

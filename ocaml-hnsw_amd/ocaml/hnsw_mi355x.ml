@@ -125,6 +125,10 @@ let hnsw_distance_batch =
 let hnsw_brute_force_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_brute_force_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float @-> returning int32_t)
+let hnsw_rerank_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_rerank_batch"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> int32_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float
+     @-> returning int32_t)
 let hnsw_select_neighbours_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_select_neighbours_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> ptr int32_t @-> int32_t @-> int32_t @-> int32_t
@@ -228,6 +232,10 @@ let hnsw_distance_batch_device =
 let hnsw_brute_force_batch_device =
   foreign ~from:lib "hnsw_brute_force_batch_device"
     (index @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float @-> ptr void @-> returning int32_t)
+let hnsw_rerank_batch_device =
+  foreign ~from:lib "hnsw_rerank_batch_device"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> int32_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float
+     @-> ptr void @-> returning int32_t)
 let hnsw_host_register = foreign ~from:lib "hnsw_host_register" (ptr void @-> int64_t @-> returning int32_t)
 let hnsw_host_unregister = foreign ~from:lib "hnsw_host_unregister" (ptr void @-> returning int32_t)
 let hnsw_host_alloc = foreign ~from:lib "hnsw_host_alloc" (ptr (ptr void) @-> int64_t @-> returning int32_t)
@@ -738,6 +746,22 @@ let brute_force_knn (t : t) (test : Lacaml.S.mat) ~k : int array array * float a
   let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
   check (hnsw_brute_force_batch t.handle (bigarray_start array2 test) (Int64.of_int nq) (Int64.of_int t.dim)
            (Int32.of_int k) 0l (CArray.start ids) (CArray.start dist));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))))
+
+(* The exact re-rank (hnsw_rerank_batch): for each query (a column of [queries]) the k nearest of ITS candidates
+   [candidates.(q)] (node ids; lists may differ in length) over the float32 vectors the index holds, under (distance, node id),
+   ascending -- what `hnsw_index_set_option idx "refine" r` does to the half-row searches' candidates.  -> (ids, distances), both
+   [nq][k]; past a query's candidates: id -1, distance nan. *)
+let rerank (t : t) (queries : Lacaml.S.mat) ~(candidates : int array array) ~k : int array array * float array array =
+  let nq = A2.dim2 queries in
+  if Array.length candidates <> nq then invalid_arg "rerank: one candidate list per query";
+  let stride = Array.fold_left (fun m row -> max m (Array.length row)) 1 candidates in
+  let cand = CArray.make int32_t ~initial:(Int32.of_int (t.k_base - 1)) (max 1 (nq * stride)) in
+  Array.iteri (fun q row -> Array.iteri (fun j v -> CArray.set cand (q * stride + j) (Int32.of_int v)) row) candidates;
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  check (hnsw_rerank_batch t.handle (bigarray_start array2 queries) (Int64.of_int nq) (Int64.of_int t.dim)
+           (CArray.start cand) (Int32.of_int stride) (Int32.of_int k) 0l (CArray.start ids) (CArray.start dist));
   (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
    Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))))
 
