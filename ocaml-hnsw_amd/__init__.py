@@ -29,23 +29,62 @@ SEM_OHNSW, SEM_FUNCTOR, SEM_FUNCTOR_NEAREST_K = 0, 1, 2
 # IndexInfo.row_format: what the knn searches read (HNSW_ROWS_*); ROWS_HALF only after set_option("half_rows", 1)
 ROWS_F32, ROWS_BYTES, ROWS_SPLIT, ROWS_HALF = 0, 2, 3, 4
 
-# every symbol include/hnsw_mi355x.h declares (tests check the .so exports all of them)
 ABI_VERSION = 3          # HNSW_ABI_VERSION of include/hnsw_mi355x.h this mirror was written against
 
-ABI_SYMBOLS = [
-    "hnsw_abi_version", "hnsw_last_error", "hnsw_device_count", "hnsw_index_create",
-    "hnsw_index_destroy", "hnsw_index_get_info", "hnsw_index_set_option", "hnsw_index_row_bytes", "hnsw_search_batch",
-    "hnsw_search_batch_device", "hnsw_search_batch_h2d", "hnsw_knn", "hnsw_distance_batch", "hnsw_distance_batch_device",
-    "hnsw_build", "hnsw_index_insert", "hnsw_select_neighbours_batch", "hnsw_index_export_layer0", "hnsw_index_export_upper_count", "hnsw_index_export_upper",
-    "hnsw_index_layer_stats", "hnsw_index_layer_isolated", "hnsw_index_locality_codes", "hnsw_index_visited_blocks", "hnsw_index_prepare", "hnsw_index_save", "hnsw_index_load",
-    "hnsw_search_layer_batch", "hnsw_search_one_batch",
-    "hnsw_search_submit", "hnsw_search_wait", "hnsw_index_kernel_times",
-    "hnsw_multi_create", "hnsw_multi_destroy", "hnsw_multi_num_replicas", "hnsw_multi_replica", "hnsw_multi_search_batch",
-    "hnsw_multi_search_batch_device", "hnsw_multi_copy_result", "hnsw_multi_debug_counters",
-    "hnsw_host_register", "hnsw_host_unregister", "hnsw_host_alloc", "hnsw_host_free",
-    "hnsw_brute_force_batch", "hnsw_brute_force_batch_device",
-    "hnsw_rerank_batch", "hnsw_rerank_batch_device",
-]
+# Every symbol include/hnsw_mi355x.h declares (tests check the .so exports all of them and compare the arities): name -> argument
+# types, the result an int32 status unless spelled out as (argument types, result type).  load() applies the table.
+_vp, _i32, _i64, _str = _C.c_void_p, _C.c_int32, _C.c_int64, _C.c_char_p
+_ABI = {
+    "hnsw_abi_version": (None, _i32),
+    "hnsw_last_error": (None, _str),
+    "hnsw_device_count": [_vp],
+    "hnsw_index_create": [_vp, _i32, _vp],
+    "hnsw_index_destroy": [_vp],
+    "hnsw_index_get_info": [_vp, _vp],
+    "hnsw_index_set_option": [_vp, _str, _i64],
+    "hnsw_index_row_bytes": [_vp, _vp],
+    "hnsw_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_search_batch_device": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_search_batch_h2d": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_knn": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_distance_batch": [_vp, _vp, _i64, _i64, _vp, _i32, _vp],
+    "hnsw_distance_batch_device": [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp],
+    "hnsw_brute_force_batch": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp],
+    "hnsw_brute_force_batch_device": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
+    "hnsw_rerank_batch": [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
+    "hnsw_rerank_batch_device": [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "hnsw_build": [_vp, _i64, _i32, _i64, _vp, _i32, _vp],
+    "hnsw_index_insert": [_vp, _vp, _i64, _i64, _vp],
+    "hnsw_select_neighbours_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "hnsw_index_layer_stats": [_vp, _i32, _vp],
+    "hnsw_index_layer_isolated": [_vp, _i32, _vp, _i64, _vp],
+    "hnsw_index_locality_codes": [_vp, _vp],
+    "hnsw_index_visited_blocks": [_vp, _vp, _vp],
+    "hnsw_index_prepare": [_vp, _vp],
+    "hnsw_index_save": [_vp, _str],
+    "hnsw_index_load": [_str, _i32, _vp],
+    "hnsw_index_export_layer0": [_vp, _vp, _vp],
+    "hnsw_index_export_upper_count": [_vp, _i32, _vp],
+    "hnsw_index_export_upper": [_vp, _i32, _vp, _vp, _vp],
+    "hnsw_search_layer_batch": [_vp, _i32, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_search_one_batch": [_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp],
+    "hnsw_index_kernel_times": [_vp, _vp, _vp, _vp],
+    "hnsw_search_submit": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "hnsw_search_wait": [_vp, _vp, _vp, _vp, _vp],
+    "hnsw_multi_create": [_vp, _vp, _i32, _vp],
+    "hnsw_multi_destroy": [_vp],
+    "hnsw_multi_num_replicas": [_vp, _vp],
+    "hnsw_multi_replica": [_vp, _i32, _vp],
+    "hnsw_multi_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_multi_search_batch_device": [_vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "hnsw_multi_copy_result": [_vp, _i32, _vp, _vp],
+    "hnsw_multi_debug_counters": [_vp, _vp],
+    "hnsw_host_register": [_vp, _i64],
+    "hnsw_host_unregister": [_vp],
+    "hnsw_host_alloc": [_vp, _i64],
+    "hnsw_host_free": [_vp],
+}
+ABI_SYMBOLS = list(_ABI)
 
 
 class InvalidArgument(ValueError):
@@ -103,83 +142,12 @@ def load():
         raise Failure("%s is missing: run `python __graft_entry__.py` (hipcc --offload-arch=gfx950); "
                       "there is no CPU fallback" % LIB_PATH)
     L = _C.CDLL(LIB_PATH)
-    vp, i32, i64 = _C.c_void_p, _C.c_int32, _C.c_int64
-    L.hnsw_abi_version.restype = i32
+    L.hnsw_abi_version.restype = _i32
     if L.hnsw_abi_version() != ABI_VERSION:
         raise Failure("%s speaks ABI version %d, this binding %d: rebuild it (python __graft_entry__.py)" % (LIB_PATH, L.hnsw_abi_version(), ABI_VERSION))
-    L.hnsw_last_error.restype = _C.c_char_p
-    L.hnsw_device_count.argtypes = [vp]
-    L.hnsw_index_create.argtypes = [vp, i32, vp]
-    L.hnsw_index_destroy.argtypes = [vp]
-    L.hnsw_index_get_info.argtypes = [vp, vp]
-    L.hnsw_index_set_option.argtypes = [vp, _C.c_char_p, i64]
-    L.hnsw_index_row_bytes.argtypes = [vp, vp]
-    L.hnsw_index_row_bytes.restype = i32
-    L.hnsw_search_batch.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp]
-    L.hnsw_search_batch_device.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.hnsw_search_batch_h2d.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.hnsw_knn.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.hnsw_distance_batch.argtypes = [vp, vp, i64, i64, vp, i32, vp]
-    L.hnsw_distance_batch_device.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp]
-    L.hnsw_brute_force_batch.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp]
-    L.hnsw_brute_force_batch_device.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp, vp]
-    L.hnsw_brute_force_batch.restype = L.hnsw_brute_force_batch_device.restype = i32
-    L.hnsw_rerank_batch.argtypes = [vp, vp, i64, i64, vp, i32, i32, i32, vp, vp]
-    L.hnsw_rerank_batch_device.argtypes = [vp, vp, i64, i64, vp, i32, i32, i32, vp, vp, vp]
-    L.hnsw_rerank_batch.restype = L.hnsw_rerank_batch_device.restype = i32
-    L.hnsw_build.argtypes = [vp, i64, i32, i64, vp, i32, vp]
-    L.hnsw_index_insert.argtypes = [vp, vp, i64, i64, vp]
-    L.hnsw_select_neighbours_batch.argtypes = [vp, vp, i64, i64, vp, vp, i32, i32, i32, vp, vp, vp]
-    L.hnsw_select_neighbours_batch.restype = i32
-    L.hnsw_index_layer_stats.argtypes = [vp, i32, vp]
-    L.hnsw_index_layer_isolated.argtypes = [vp, i32, vp, i64, vp]
-    L.hnsw_index_locality_codes.argtypes = [vp, vp]
-    L.hnsw_index_locality_codes.restype = i32
-    L.hnsw_index_visited_blocks.argtypes = [vp, vp, vp]
-    L.hnsw_index_visited_blocks.restype = i32
-    L.hnsw_index_prepare.argtypes = [vp, vp]
-    L.hnsw_index_prepare.restype = i32
-    L.hnsw_index_save.argtypes = [vp, _C.c_char_p]
-    L.hnsw_index_load.argtypes = [_C.c_char_p, i32, vp]
-    for f in ("hnsw_index_layer_stats", "hnsw_index_layer_isolated", "hnsw_index_save", "hnsw_index_load"):
-        getattr(L, f).restype = i32
-    L.hnsw_index_export_layer0.argtypes = [vp, vp, vp]
-    L.hnsw_index_export_upper_count.argtypes = [vp, i32, vp]
-    L.hnsw_index_export_upper.argtypes = [vp, i32, vp, vp, vp]
-    for f in ("hnsw_build", "hnsw_index_insert", "hnsw_select_neighbours_batch", "hnsw_index_export_layer0", "hnsw_index_export_upper_count",
-              "hnsw_index_export_upper"):
-        getattr(L, f).restype = i32
-    for f in ("hnsw_device_count", "hnsw_index_create", "hnsw_index_destroy", "hnsw_index_get_info",
-              "hnsw_index_set_option", "hnsw_search_batch", "hnsw_search_batch_device", "hnsw_search_batch_h2d", "hnsw_knn",
-              "hnsw_distance_batch", "hnsw_distance_batch_device"):
-        getattr(L, f).restype = i32
-    L.hnsw_search_layer_batch.argtypes = [vp, i32, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp]
-    L.hnsw_search_one_batch.argtypes = [vp, i32, vp, i64, i64, vp, vp, vp]
-    L.hnsw_index_kernel_times.argtypes = [vp, vp, vp, vp]
-    L.hnsw_index_kernel_times.restype = i32
-    L.hnsw_search_submit.argtypes = [vp, vp, i64, i64, vp, vp]
-    L.hnsw_search_wait.argtypes = [vp, vp, vp, vp, vp]
-    L.hnsw_search_submit.restype = L.hnsw_search_wait.restype = i32
-    L.hnsw_multi_create.argtypes = [vp, vp, i32, vp]
-    L.hnsw_multi_destroy.argtypes = [vp]
-    L.hnsw_multi_num_replicas.argtypes = [vp, vp]
-    L.hnsw_multi_replica.argtypes = [vp, i32, vp]
-    L.hnsw_multi_search_batch.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp]
-    L.hnsw_multi_search_batch_device.argtypes = [vp, vp, i64, i64, vp, vp, vp]
-    L.hnsw_multi_copy_result.argtypes = [vp, i32, vp, vp]
-    L.hnsw_multi_debug_counters.argtypes = [vp, vp]
-    if hasattr(L, "hnsw_host_register"):      # (an older build of the library, loaded by tools/ab.py for comparison, lacks them)
-        L.hnsw_host_register.argtypes = [vp, i64]
-        L.hnsw_host_unregister.argtypes = [vp]
-        L.hnsw_host_register.restype = L.hnsw_host_unregister.restype = i32
-    if hasattr(L, "hnsw_host_alloc"):
-        L.hnsw_host_alloc.argtypes = [vp, i64]
-        L.hnsw_host_free.argtypes = [vp]
-        L.hnsw_host_alloc.restype = L.hnsw_host_free.restype = i32
-    for f in ("hnsw_search_layer_batch", "hnsw_search_one_batch", "hnsw_multi_create", "hnsw_multi_destroy",
-              "hnsw_multi_num_replicas", "hnsw_multi_replica", "hnsw_multi_search_batch",
-              "hnsw_multi_search_batch_device", "hnsw_multi_copy_result", "hnsw_multi_debug_counters"):
-        getattr(L, f).restype = i32
+    for name, sig in _ABI.items():
+        f = getattr(L, name)
+        f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, _i32)
     _lib = L
     return L
 
@@ -212,6 +180,26 @@ def _rows(a):
         return a, a.strides[0] // 4
     a = _np.ascontiguousarray(a, dtype=_np.float32)
     return a, (a.shape[1] if a.ndim == 2 else 0)
+
+
+def _batch(hgraph_d, batch, min_rows=0):
+    """A query batch for an index of hgraph_d dimensions -> (Q, q_stride, nq) as the library takes them (see _rows)."""
+    Q, qs = _rows(batch)
+    if Q.ndim != 2 or Q.shape[0] < min_rows or (Q.shape[0] and Q.shape[1] != hgraph_d):
+        raise InvalidArgument("batch must be [nq][d], nq >= 1" if min_rows else "batch must be [nq][d]")
+    return Q, max(qs, hgraph_d), Q.shape[0]
+
+
+def _out_pair(nq, k, out):
+    """The result matrices (ids, dist) of nq queries: fresh ones, or out = the caller's pair (e.g. pinned matrices it reuses
+    batch after batch), which the library fills as nq * k contiguous words each."""
+    if out is None:
+        return _np.empty((nq, max(k, 0)), _np.int32), _np.empty((nq, max(k, 0)), _np.float32)
+    ids, dist = out
+    if ids.shape != (nq, k) or dist.shape != (nq, k) or ids.dtype != _np.int32 or dist.dtype != _np.float32 \
+            or not ids.flags["C_CONTIGUOUS"] or not dist.flags["C_CONTIGUOUS"]:
+        raise InvalidArgument("out must be (int32 [nq][k], float32 [nq][k]), C-contiguous")
+    return ids, dist
 
 
 class Hgraph:
@@ -264,6 +252,7 @@ class Hgraph:
     @vectors.setter
     def vectors(self, value):
         self._vparts = None if value is None else [value]
+        self.row_stride = 0 if value is None else value.strides[0] // 4      # (floats; __init__ and _append_vectors know better)
 
     def _append_vectors(self, rows):
         parts = self.__dict__.get("_vparts")
@@ -275,21 +264,25 @@ class Hgraph:
         self.row_stride = self.d
 
     @classmethod
-    def _from_handle(cls, handle, device, vectors, id_base, metric):
-        """Wrap an index that already lives on the device (hnsw_build); the host copy of the
-        graph is fetched on demand by export()."""
+    def _from_handle(cls, handle, device, vectors=None):
+        """Wrap an index that already lives on the device (hnsw_build, hnsw_index_load), leaving every field __init__ sets; the
+        host copy of the graph is fetched on demand by export()."""
         self = cls.__new__(cls)
         self.vectors = vectors
-        self.n, self.d = vectors.shape
         self._index, self._device = handle, device
-        self.id_base, self.metric = int(id_base), int(metric)
-        inf = IndexInfo()
-        _check(load().hnsw_index_get_info(handle, _C.byref(inf)))
-        self.max_degree0, self.max_degree, self.max_layer = inf.max_degree0, inf.max_degree, inf.max_layer
-        self.entry_point = int(inf.entry_point) if inf.entry_point >= id_base else None
-        self.deg0 = self.nbr0 = None
-        self.upper = None
+        self.expected_ef, self.expected_sem = 0, SEM_OHNSW
+        inf = self.info()
+        self.d, self.id_base, self.metric = int(inf.d), int(inf.id_base), int(inf.metric)
+        self._adopt(inf)
         return self
+
+    def _adopt(self, info):
+        """Follow the device index: n, widths, max_layer and entry_point from its hnsw_index_info; the host copy of the graph,
+        if there was one, is stale (export() fetches it)."""
+        self.n = int(info.n)
+        self.max_degree0, self.max_degree, self.max_layer = info.max_degree0, info.max_degree, info.max_layer
+        self.entry_point = int(info.entry_point) if info.entry_point >= self.id_base else None
+        self.deg0 = self.nbr0 = self.upper = None
 
     def export(self):
         """Fetch the flattened graph from the device: fills deg0, nbr0, upper (ids id_base-based)."""
@@ -353,17 +346,7 @@ class Hgraph:
         """Read a flattened index file straight into HBM (hnsw_index_load)."""
         h = _C.c_void_p()
         _check(load().hnsw_index_load(str(path).encode(), device, _C.byref(h)))
-        inf = IndexInfo()
-        _check(load().hnsw_index_get_info(h, _C.byref(inf)))
-        self = cls.__new__(cls)
-        self.vectors = None
-        self.n, self.d = int(inf.n), int(inf.d)
-        self._index, self._device = h, device
-        self.id_base, self.metric = int(inf.id_base), int(inf.metric)
-        self.max_degree0, self.max_degree, self.max_layer = inf.max_degree0, inf.max_degree, inf.max_layer
-        self.entry_point = int(inf.entry_point) if inf.entry_point >= inf.id_base else None
-        self.deg0 = self.nbr0 = self.upper = None
-        return self
+        return cls._from_handle(h, device)
 
     @classmethod
     def flat(cls, vectors, metric=METRIC_L2, id_base=0):
@@ -389,13 +372,13 @@ class Hgraph:
             layers[i].nodes, layers[i].deg, layers[i].nbr = nodes.ctypes.data, deg.ctypes.data, nbr.ctypes.data
         d = _IndexDesc()
         d.vectors = self.vectors.ctypes.data
-        d.n, d.d, d.row_stride = self.n, self.d, getattr(self, "row_stride", self.vectors.strides[0] // 4)
+        d.n, d.d, d.row_stride = self.n, self.d, self.row_stride
         d.metric, d.id_base = self.metric, self.id_base
         d.max_degree0, d.max_degree, d.max_layer = self.max_degree0, self.max_degree, nl
         d.entry_point = self.id_base - 1 if self.entry_point is None else self.entry_point
         d.deg0, d.nbr0 = self.deg0.ctypes.data, self.nbr0.ctypes.data
         d.upper = _C.cast(layers, _C.c_void_p)
-        d.expected_ef, d.expected_semantics = getattr(self, "expected_ef", 0), getattr(self, "expected_sem", 0)
+        d.expected_ef, d.expected_semantics = self.expected_ef, self.expected_sem
         return d, layers
 
     def to_device(self, device=0):
@@ -492,23 +475,12 @@ def unpin(array):
 
 
 def _search(hgraph, batch, ef, k, fill, counters=False, sem=0, out=None):
-    Q, qs = _rows(batch)
-    if Q.ndim != 2 or (Q.shape[0] and Q.shape[1] != hgraph.d):
-        raise InvalidArgument("batch must be [nq][d]")
-    nq = Q.shape[0]
-    if out is not None:      # result matrices of the caller (e.g. pinned ones it reuses batch after batch)
-        ids, dist = out
-        if ids.shape != (nq, k) or dist.shape != (nq, k) or ids.dtype != _np.int32 or dist.dtype != _np.float32 \
-                or not ids.flags["C_CONTIGUOUS"] or not dist.flags["C_CONTIGUOUS"]:
-            raise InvalidArgument("out must be (int32 [nq][k], float32 [nq][k]), C-contiguous")
-    else:
-        ids = _np.empty((nq, k), _np.int32)
-        dist = _np.empty((nq, k), _np.float32)
+    Q, qs, nq = _batch(hgraph.d, batch)
+    ids, dist = _out_pair(nq, k, out)
     nd = _np.zeros(nq, _np.uint32) if counters else None
     nh = _np.zeros(nq, _np.uint32) if counters else None
     p = _SearchParams(ef, k, fill, sem)
-    _check(load().hnsw_search_batch(hgraph.handle, _ptr(Q), nq, max(qs, hgraph.d), _C.byref(p), _ptr(ids),
-                                    _ptr(dist), _ptr(nd), _ptr(nh)))
+    _check(load().hnsw_search_batch(hgraph.handle, _ptr(Q), nq, qs, _C.byref(p), _ptr(ids), _ptr(dist), _ptr(nd), _ptr(nh)))
     return (ids, dist, nd, nh) if counters else (ids, dist)
 
 
@@ -523,14 +495,7 @@ class Request:
     def wait(self, counters=False, out=None):
         if self._h is None:
             raise InvalidArgument("request already waited for")
-        if out is not None:
-            ids, dist = out
-            if (ids.shape != (self.nq, self.k) or dist.shape != (self.nq, self.k) or ids.dtype != _np.int32 or dist.dtype != _np.float32
-                    or not ids.flags["C_CONTIGUOUS"] or not dist.flags["C_CONTIGUOUS"]):   # the library writes nq * k contiguous words
-                raise InvalidArgument("out must be (int32 [nq][k], float32 [nq][k]), C-contiguous")
-        else:
-            ids = _np.empty((self.nq, self.k), _np.int32)
-            dist = _np.empty((self.nq, self.k), _np.float32)
+        ids, dist = _out_pair(self.nq, self.k, out)
         nd = _np.zeros(self.nq, _np.uint32) if counters else None
         nh = _np.zeros(self.nq, _np.uint32) if counters else None
         h, self._h, self._keep = self._h, None, None
@@ -540,13 +505,11 @@ class Request:
 
 def submit(hgraph, batch, ef, k, fill=FILL_OHNSW, sem=SEM_OHNSW):
     """hnsw_search_submit: copy the batch in, start the search, return at once."""
-    Q, qs = _rows(batch)
-    if Q.ndim != 2 or Q.shape[0] < 1 or Q.shape[1] != hgraph.d:
-        raise InvalidArgument("batch must be [nq][d], nq >= 1")
+    Q, qs, nq = _batch(hgraph.d, batch, 1)
     p = _SearchParams(ef, k, fill, sem)
     h = _C.c_void_p()
-    _check(load().hnsw_search_submit(hgraph.handle, _ptr(Q), Q.shape[0], max(qs, hgraph.d), _C.byref(p), _C.byref(h)))
-    return Request(hgraph, h, Q.shape[0], k, Q)
+    _check(load().hnsw_search_submit(hgraph.handle, _ptr(Q), nq, qs, _C.byref(p), _C.byref(h)))
+    return Request(hgraph, h, nq, k, Q)
 
 
 def search_batch_device(hgraph, d_queries, nq, q_stride, ef, k, d_ids, d_dist, d_ndist=0, d_nhops=0,
@@ -575,11 +538,9 @@ def search_batch_h2d(hgraph, batch, ef, k, d_ids, d_dist, d_ndist=0, d_nhops=0, 
     """hnsw_search_batch_h2d: queries from a HOST matrix (read by the device directly when it was registered with pin()),
     results left in device buffers (pointers as ints), asynchronous on HIP stream `stream`.  The matrix must stay alive
     until the stream has passed the call."""
-    Q, qs = _rows(batch)
-    if Q.ndim != 2 or Q.shape[0] < 1 or Q.shape[1] != hgraph.d:
-        raise InvalidArgument("batch must be [nq][d], nq >= 1")
+    Q, qs, nq = _batch(hgraph.d, batch, 1)
     p = _SearchParams(ef, k, fill, sem)
-    _check(load().hnsw_search_batch_h2d(hgraph.handle, _ptr(Q), Q.shape[0], max(qs, hgraph.d), _C.byref(p), d_ids, d_dist,
+    _check(load().hnsw_search_batch_h2d(hgraph.handle, _ptr(Q), nq, qs, _C.byref(p), d_ids, d_dist,
                                         d_ndist or None, d_nhops or None, d_status or None, stream or None))
     return Q          # the array the device reads: keep it alive until the stream is synchronised
 
@@ -607,19 +568,9 @@ class Ohnsw:
         (hnsw_brute_force_batch) -> (ids, distances): for each query the k smallest of all n vectors under (distance, id),
         ascending; ids [nq][k] (-1 where k > n), distances [nq][k] fp32 (NaN there; FILL_BA: +inf).  Needs no graph.
         out = (ids, distances): write into the caller's matrices instead of fresh ones."""
-        Q, qs = _rows(batch)
-        if Q.ndim != 2 or (Q.shape[0] and Q.shape[1] != hgraph.d):
-            raise InvalidArgument("batch must be [nq][d]")
-        nq, k = Q.shape[0], int(k)
-        if out is not None:
-            ids, dist = out
-            if ids.shape != (nq, k) or dist.shape != (nq, k) or ids.dtype != _np.int32 or dist.dtype != _np.float32 \
-                    or not ids.flags["C_CONTIGUOUS"] or not dist.flags["C_CONTIGUOUS"]:
-                raise InvalidArgument("out must be (int32 [nq][k], float32 [nq][k]), C-contiguous")
-        else:
-            ids = _np.empty((nq, max(k, 0)), _np.int32)
-            dist = _np.empty((nq, max(k, 0)), _np.float32)
-        _check(load().hnsw_brute_force_batch(hgraph.handle, _ptr(Q), nq, max(qs, hgraph.d), k, fill, _ptr(ids), _ptr(dist)))
+        Q, qs, nq = _batch(hgraph.d, batch)
+        ids, dist = _out_pair(nq, int(k), out)
+        _check(load().hnsw_brute_force_batch(hgraph.handle, _ptr(Q), nq, qs, int(k), fill, _ptr(ids), _ptr(dist)))
         return ids, dist
 
     @staticmethod
@@ -628,23 +579,12 @@ class Ohnsw:
         entries below id_base are padding) over the float32 vectors, under (distance, id), ascending; ids [nq][k] (-1 past the
         real candidates), distances [nq][k] fp32 (NaN there; FILL_BA: +inf).  What option "refine" does to the half-row
         searches' candidates.  Needs no graph.  out = (ids, distances): write into the caller's matrices instead of fresh ones."""
-        Q, qs = _rows(batch)
-        if Q.ndim != 2 or (Q.shape[0] and Q.shape[1] != hgraph.d):
-            raise InvalidArgument("batch must be [nq][d]")
-        nq, k = Q.shape[0], int(k)
+        Q, qs, nq = _batch(hgraph.d, batch)
         C = _np.ascontiguousarray(cand, _np.int32)
         if C.ndim != 2 or C.shape[0] != nq:
             raise InvalidArgument("cand must be [nq][cand_stride]")
-        if out is not None:
-            ids, dist = out
-            if ids.shape != (nq, k) or dist.shape != (nq, k) or ids.dtype != _np.int32 or dist.dtype != _np.float32 \
-                    or not ids.flags["C_CONTIGUOUS"] or not dist.flags["C_CONTIGUOUS"]:
-                raise InvalidArgument("out must be (int32 [nq][k], float32 [nq][k]), C-contiguous")
-        else:
-            ids = _np.empty((nq, max(k, 0)), _np.int32)
-            dist = _np.empty((nq, max(k, 0)), _np.float32)
-        _check(load().hnsw_rerank_batch(hgraph.handle, _ptr(Q), nq, max(qs, hgraph.d), _ptr(C), C.shape[1], k, fill,
-                                        _ptr(ids), _ptr(dist)))
+        ids, dist = _out_pair(nq, int(k), out)
+        _check(load().hnsw_rerank_batch(hgraph.handle, _ptr(Q), nq, qs, _ptr(C), C.shape[1], int(k), fill, _ptr(ids), _ptr(dist)))
         return ids, dist
 
     @staticmethod
@@ -699,7 +639,7 @@ class Ohnsw:
         p = _BuildParams(num_connections, num_nodes_search_construction, metric, 0, seed, max_batch, batch_div, expected_ef, expected_sem)
         h = _C.c_void_p()
         _check(load().hnsw_build(_ptr(X), X.shape[0], X.shape[1], X.shape[1], _C.byref(p), device, _C.byref(h)))
-        return Hgraph._from_handle(h, device, X, 0, metric)
+        return Hgraph._from_handle(h, device, X)
 
     @staticmethod
     def insert_batch(hgraph, batch, num_connections, num_nodes_search_construction, seed=0, max_batch=0, batch_div=0,
@@ -719,13 +659,8 @@ class Ohnsw:
         _check(load().hnsw_index_insert(hgraph.handle, _ptr(X), m, max(xs, hgraph.d), _C.byref(p)))
         if m == 0:
             return _np.arange(0, dtype=_np.int64)
-        inf = IndexInfo()
-        _check(load().hnsw_index_get_info(hgraph.handle, _C.byref(inf)))
         hgraph._append_vectors(X)
-        hgraph.n = int(inf.n)
-        hgraph.max_degree0, hgraph.max_degree, hgraph.max_layer = inf.max_degree0, inf.max_degree, inf.max_layer
-        hgraph.entry_point = int(inf.entry_point) if inf.entry_point >= hgraph.id_base else None
-        hgraph.deg0 = hgraph.nbr0 = hgraph.upper = None
+        hgraph._adopt(hgraph.info())
         return _np.arange(n_old + hgraph.id_base, n_old + m + hgraph.id_base, dtype=_np.int64)
 
     @staticmethod
@@ -808,6 +743,7 @@ class MultiHgraph:
         h = _C.c_void_p()
         _check(load().hnsw_multi_create(_C.byref(d), _ptr(dev), len(dev), _C.byref(h)))
         self._h = h
+        self._last = None            # (nq, k) of the last search_device, for copy_result
 
     def num_replicas(self):
         c = _C.c_int32(0)
@@ -815,17 +751,12 @@ class MultiHgraph:
         return c.value
 
     def _search(self, batch, ef, k, fill, sem, counters=False):
-        Q, qs = _rows(batch)
-        if Q.ndim != 2 or (Q.shape[0] and Q.shape[1] != self.hgraph.d):
-            raise InvalidArgument("batch must be [nq][d]")
-        nq = Q.shape[0]
-        ids = _np.empty((nq, k), _np.int32)
-        dist = _np.empty((nq, k), _np.float32)
+        Q, qs, nq = _batch(self.hgraph.d, batch)
+        ids, dist = _out_pair(nq, k, None)
         nd = _np.zeros(nq, _np.uint32) if counters else None
         nh = _np.zeros(nq, _np.uint32) if counters else None
         p = _SearchParams(ef, k, fill, sem)
-        _check(load().hnsw_multi_search_batch(self._h, _ptr(Q), nq, max(qs, self.hgraph.d), _C.byref(p), _ptr(ids),
-                                              _ptr(dist), _ptr(nd), _ptr(nh)))
+        _check(load().hnsw_multi_search_batch(self._h, _ptr(Q), nq, qs, _C.byref(p), _ptr(ids), _ptr(dist), _ptr(nd), _ptr(nh)))
         return (ids, dist, nd, nh) if counters else (ids, dist)
 
     def knn_batch_bigarray(self, k, batch, ef=None, counters=False):
@@ -835,15 +766,13 @@ class MultiHgraph:
     def search_device(self, batch, ef, k, fill=FILL_OHNSW, sem=SEM_OHNSW):
         """hnsw_multi_search_batch_device: sharded search + RCCL all-gather, results left on the devices.
         -> (d_ids, d_dist): per-device pointers (ints) to each device's full [nq][k] table."""
-        Q, qs = _rows(batch)
-        if Q.ndim != 2 or Q.shape[0] < 1 or Q.shape[1] != self.hgraph.d:
-            raise InvalidArgument("batch must be [nq][d], nq >= 1")
+        Q, qs, nq = _batch(self.hgraph.d, batch, 1)
         G = len(self.devices)
         pi = (_C.c_void_p * G)()
         pd = (_C.c_void_p * G)()
         p = _SearchParams(ef, k, fill, sem)
-        _check(load().hnsw_multi_search_batch_device(self._h, _ptr(Q), Q.shape[0], max(qs, self.hgraph.d), _C.byref(p), pi, pd))
-        self._last = (Q.shape[0], k)
+        _check(load().hnsw_multi_search_batch_device(self._h, _ptr(Q), nq, qs, _C.byref(p), pi, pd))
+        self._last = (nq, k)
         return [int(x or 0) for x in pi], [int(x or 0) for x in pd]
 
     def debug_counters(self):
@@ -854,9 +783,7 @@ class MultiHgraph:
 
     def copy_result(self, g):
         """device g's copy of the last search_device result -> (ids, dist) host arrays"""
-        nq, k = self._last
-        ids = _np.empty((nq, k), _np.int32)
-        dist = _np.empty((nq, k), _np.float32)
+        ids, dist = _out_pair(*self._last, None)
         _check(load().hnsw_multi_copy_result(self._h, int(g), _ptr(ids), _ptr(dist)))
         return ids, dist
 

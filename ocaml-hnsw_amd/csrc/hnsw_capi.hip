@@ -57,7 +57,9 @@ struct HostRange { const char *p; size_t bytes; char *dev; int kind; std::vector
 std::mutex g_ranges_mu;
 std::vector<HostRange> g_ranges;
 
+// the device address of [p, p + bytes) if it lies in one of these ranges, else null (as for a null p)
 void *registered_device_address(const void *p, size_t bytes) {
+    if (!p) return nullptr;
     std::lock_guard<std::mutex> lk(g_ranges_mu);
     for (const HostRange &r : g_ranges)
         if (r.dev && (const char *)p >= r.p && (const char *)p + bytes <= r.p + r.bytes) return r.dev + ((const char *)p - r.p);
@@ -614,6 +616,86 @@ int ensure_host_call_state(hnsw_index *idx) {
     return HNSW_OK;
 }
 
+int HostInput::resolve(const void *p, size_t n, DevBuf &stage) {
+    bytes = n; from = nullptr;
+    if ((dev = registered_device_address(p, n))) return HNSW_OK;
+    const int rc = stage.ensure(n);
+    dev = stage.p; from = p;
+    return rc;
+}
+int HostInput::upload(hipStream_t st) const {
+    if (from) HIP_TRY(hipMemcpyAsync(const_cast<void *>(dev), from, bytes, hipMemcpyHostToDevice, st));
+    return HNSW_OK;
+}
+
+// A synchronous host-buffer call uploads, runs and downloads on the handle's stream hs[0], with ONE stream synchronisation at
+// the end.  Each matrix of the caller is in place, in the small block or staged:
+//  * IN PLACE: a page-locked matrix (hnsw_host_alloc / hnsw_host_register) is not copied at all.  The device reads the queries
+//    straight from it -- each query once, by the wave that searches it (the descent pre-pass keeps a device copy for the search
+//    kernel), so the 5 MB of a 10 k x 128 batch cross PCIe UNDER the descent instead of before it -- and writes each query's
+//    results straight into the caller's matrices as the query finishes: no download step.  Ids and distances: both or neither.
+//  * SMALL BLOCK (allow_small: the knn call): a small batch from ordinary memory (a single query: Ohnsw.knn, test/test.ml:122)
+//    -- nothing registered; queries, results, counters of at most SMALL_BLOCK bytes each -- goes through a page-locked block of
+//    the handle's own: the host copies the queries in, the device reads them and writes the results there, the host copies them
+//    out.  What is left of the call is one launch and one synchronisation.
+//  * STAGED: the rest goes through the handle's scratch by hipMemcpyAsync.  (Chunks on two streams to overlap copies and search
+//    measured 1.08 against 1.06 ms in round 1.)
+// Every allocation is made before the first asynchronous copy is queued (a further input, as hnsw_rerank_batch's candidates, is
+// resolved before begin and uploaded after it); once one is queued no return without a synchronisation: it reads or writes the
+// caller's arrays.
+constexpr size_t SMALL_BLOCK = 32768;
+
+int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int k_, int32_t *out_ids, float *out_dist,
+                    uint32_t *out_nd, uint32_t *out_nh, bool allow_small, bool *q_in_place) {
+    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d), rbytes = (size_t)nq * k_ * 4, cbytes = (size_t)nq * 4;
+    int rc;
+    HostInput q;
+    if ((rc = idx->scratch.ensure(nq, qbytes, k_)) || (rc = ensure_host_call_state(idx)) || (rc = q.resolve(queries, qbytes, idx->scratch.q)))
+        return rc;
+    int32_t *zi = (int32_t *)registered_device_address(out_ids, rbytes);
+    float *zd = (float *)registered_device_address(out_dist, rbytes);
+    uint32_t *znd = (uint32_t *)registered_device_address(out_nd, cbytes), *znh = (uint32_t *)registered_device_address(out_nh, cbytes);
+    if (!zi || !zd) zi = nullptr, zd = nullptr;
+    small = allow_small && q.from && !zi && !znd && !znh && qbytes <= SMALL_BLOCK && rbytes <= SMALL_BLOCK && cbytes <= SMALL_BLOCK;
+    if (small) {
+        if (!idx->hSmall) {
+            HIP_TRY(idx->hSmall.alloc(5 * SMALL_BLOCK, hipHostMallocMapped));
+            HIP_TRY(hipHostGetDevicePointer((void **)&idx->hSmallDev, idx->hSmall, 0));
+        }
+        memcpy(idx->hSmall, queries, qbytes);
+        char *s = idx->hSmallDev;
+        q = HostInput{s};
+        zi = (int32_t *)(s + SMALL_BLOCK); zd = (float *)(s + 2 * SMALL_BLOCK);
+        if (out_nd) znd = (uint32_t *)(s + 3 * SMALL_BLOCK);
+        if (out_nh) znh = (uint32_t *)(s + 4 * SMALL_BLOCK);
+    }
+    // the batch on the device: the scratch buffers, but for what the kernels read or write in place (or in the block) ...
+    k = k_;
+    b = idx->scratch.batch(nq, q_stride, k);
+    b.Q = (const float *)q.dev;
+    if (zi) b.ids = zi, b.dist = zd;
+    if (znd) b.nd = znd;
+    if (znh) b.nh = znh;
+    // ... and the caller's arrays that are not complete when the kernels are
+    ids = zi && !small ? nullptr : out_ids; dist = zi && !small ? nullptr : out_dist;
+    nd = znd && !small ? nullptr : out_nd; nh = znh && !small ? nullptr : out_nh;
+    if (q_in_place) *q_in_place = !q.from;
+    return q.upload(idx->hs[0]);
+}
+
+int HostCall::finish(hnsw_index *idx, const char *what, hipStream_t st) {
+    const hipError_t ed = small ? hipSuccess : knn_download(b, k, ids, dist, nd, nh, st), es = st ? hipStreamSynchronize(st) : hipDeviceSynchronize();
+    if (ed != hipSuccess) return hip_fail(ed, "result download");
+    if (es != hipSuccess) return fail(HNSW_ERR_HIP, "%s failed: %s", what, hipGetErrorString(es));
+    if (small) {
+        const size_t rbytes = (size_t)b.nq * k * 4, cbytes = (size_t)b.nq * 4;
+        memcpy(ids, idx->hSmall + SMALL_BLOCK, rbytes); memcpy(dist, idx->hSmall + 2 * SMALL_BLOCK, rbytes);
+        if (nd) memcpy(nd, idx->hSmall + 3 * SMALL_BLOCK, cbytes);
+        if (nh) memcpy(nh, idx->hSmall + 4 * SMALL_BLOCK, cbytes);
+    }
+    return HNSW_OK;
+}
+
 // One query (node 0's vector, k 1) through the plain and through the ordered launch on the handle's stream, results discarded:
 // what loads the code objects of the shape of p (and makes the handle's stream and flag word)
 int trial_search(hnsw_index *idx, hnsw_search_params p) {
@@ -983,76 +1065,23 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
     int rc = check_batch(idx, params, nq, q_stride, queries && out_ids && out_dist);
     if (rc || nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
-    const int k = params->k;
-    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d), rbytes = (size_t)nq * k * 4;
-    if ((rc = idx->scratch.ensure(nq, qbytes, k))) return rc;
-    // Upload, search (ordered longest walk first when the batch is larger than the chip holds) and download on one
-    // of the handle's streams, ONE stream synchronisation at the end.
-    //
-    // Page-locked matrices of the caller (hnsw_host_alloc / hnsw_host_register) are not copied at all: the device reads the queries straight
-    // from the caller's matrix -- each query once, by the wave that searches it (the descent pre-pass keeps a device copy
-    // for the search kernel), so the 5 MB of a 10 k x 128 batch cross PCIe UNDER the descent instead of before it -- and
-    // the kernel writes each query's results straight into the caller's result matrices as the query finishes, so there is
-    // no download step behind the launch either.  Pageable matrices are staged through hipMemcpyAsync as before.  Whether
-    // any query needs the exactness fallback comes back as one word (pinned host memory, the kernel stores it), not as a
-    // scan of nq status words.  (Splitting the batch into chunks on two streams to overlap copies and search measured
-    // 1.08 against 1.06 ms in round 1.)
-    if ((rc = ensure_host_call_state(idx))) return rc;
+    // Where the matrices live: HostCall::begin.  The search is ordered longest walk first when the batch is larger than the chip
+    // holds; whether any query needs the exactness fallback comes back as one word (pinned host memory, the kernel stores it),
+    // not as a scan of nq status words.
+    HostCall c;
+    bool q_in_place = false;
+    if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
     hipStream_t st = idx->hs[0];
-    const float *zq = (const float *)registered_device_address(queries, qbytes);
-    int32_t *zi = (int32_t *)registered_device_address(out_ids, rbytes);
-    float *zd = (float *)registered_device_address(out_dist, rbytes);
-    uint32_t *znd = out_ndist ? (uint32_t *)registered_device_address(out_ndist, (size_t)nq * 4) : nullptr;
-    uint32_t *znh = out_nhops ? (uint32_t *)registered_device_address(out_nhops, (size_t)nq * 4) : nullptr;
-    if (!zi || !zd) zi = nullptr, zd = nullptr;                      // results: both matrices or neither
-    // A SMALL batch from ordinary memory (a single query: Ohnsw.knn, test/test.ml:122) goes through a page-locked block of the
-    // handle's own instead of three staged copies: the queries are copied into it by the host, the device reads them and writes
-    // the results there, the host copies them out -- what is left of the call is one launch and one synchronisation.
-    constexpr size_t SMALL = 32768;
-    const bool small = !zq && !zi && !znd && !znh && qbytes <= SMALL && rbytes <= SMALL && (size_t)nq * 4 <= SMALL;
-    if (small) {
-        if (!idx->hSmall) {
-            HIP_TRY(idx->hSmall.alloc(5 * SMALL, hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer((void **)&idx->hSmallDev, idx->hSmall, 0));
-        }
-        memcpy(idx->hSmall, queries, qbytes);
-        zq = (const float *)idx->hSmallDev;
-        zi = (int32_t *)(idx->hSmallDev + SMALL); zd = (float *)(idx->hSmallDev + 2 * SMALL);
-        if (out_ndist) znd = (uint32_t *)(idx->hSmallDev + 3 * SMALL);
-        if (out_nhops) znh = (uint32_t *)(idx->hSmallDev + 4 * SMALL);
-    }
-    // the batch on the device: what the kernel reads or writes in place, the scratch buffers for the rest
-    KnnBatch b = idx->scratch.batch(nq, q_stride, k);
-    b.any_flag = idx->hFlagDev;
-    if (zq) b.Q = zq;
-    if (zi) b.ids = zi, b.dist = zd;
-    if (znd) b.nd = znd;
-    if (znh) b.nh = znh;
-    // ... and the caller's arrays the results are downloaded into
-    int32_t *to_ids = zi ? nullptr : out_ids;
-    float *to_dist = zi ? nullptr : out_dist;
-    uint32_t *to_nd = znd ? nullptr : out_ndist, *to_nh = znh ? nullptr : out_nhops;
+    c.b.any_flag = idx->hFlagDev;
     *(volatile uint32_t *)idx->hFlag = 0;
-    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
-    rc = knn_search(idx, params, b, st, zq ? (float *)idx->scratch.q.p : nullptr);
+    rc = knn_search(idx, params, c.b, st, q_in_place ? (float *)idx->scratch.q.p : nullptr);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    {   // no return while a copy into the caller's arrays may still be queued
-        const hipError_t ed = knn_download(b, k, to_ids, to_dist, to_nd, to_nh, st), es = hipStreamSynchronize(st);
-        if (ed != hipSuccess) return hip_fail(ed, "result download");
-        if (es != hipSuccess) return fail(HNSW_ERR_HIP, "search failed: %s", hipGetErrorString(es));
-    }
+    if ((rc = c.finish(idx, "search", st))) return rc;
     if (*(volatile uint32_t *)idx->hFlag & 1u) {      // (the flag: written by the kernel, pinned host memory)
         // Exactness fallback for queries whose tie-overflow stack outgrew its LDS slots (rare: the rows of the whole batch
-        // are then copied out again)
-        if ((rc = knn_repair(idx, params, b, nullptr))) return rc;
-        const hipError_t ed = knn_download(b, k, to_ids, to_dist, to_nd, to_nh, nullptr), es = hipDeviceSynchronize();
-        if (ed != hipSuccess) return hip_fail(ed, "result download");
-        if (es != hipSuccess) return fail(HNSW_ERR_HIP, "result download failed: %s", hipGetErrorString(es));
-    }
-    if (small) {
-        memcpy(out_ids, idx->hSmall + SMALL, rbytes); memcpy(out_dist, idx->hSmall + 2 * SMALL, rbytes);
-        if (out_ndist) memcpy(out_ndist, idx->hSmall + 3 * SMALL, (size_t)nq * 4);
-        if (out_nhops) memcpy(out_nhops, idx->hSmall + 4 * SMALL, (size_t)nq * 4);
+        // are then copied out again, on the null stream)
+        if ((rc = knn_repair(idx, params, c.b, nullptr))) return rc;
+        return c.finish(idx, "result download", nullptr);
     }
     return HNSW_OK;
 }
@@ -1066,11 +1095,11 @@ int32_t hnsw_search_batch_h2d(hnsw_index *idx, const float *queries, int64_t nq,
     const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d);
     if ((rc = idx->scratch.q.ensure(qbytes))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const float *zq = (const float *)registered_device_address(queries, qbytes);
-    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
+    HostInput q;
+    if ((rc = q.resolve(queries, qbytes, idx->scratch.q)) || (rc = q.upload(st))) return rc;
     // registered matrix: read by the device directly, the pre-pass (when there is one) leaves the device copy in sQ
-    rc = knn_search(idx, params, {zq ? zq : (const float *)idx->scratch.q.p, nq, q_stride, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr},
-                    st, zq ? (float *)idx->scratch.q.p : nullptr);
+    rc = knn_search(idx, params, {(const float *)q.dev, nq, q_stride, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr},
+                    st, q.from ? nullptr : (float *)idx->scratch.q.p);
     // the call returns while the device still reads the caller's matrix (in place, or as the source of the DMA above): the
     // range remembers it, so that hnsw_host_unregister / hnsw_host_free wait instead of pulling the pages from under a kernel
     range_reader_enqueued(queries, qbytes, st);

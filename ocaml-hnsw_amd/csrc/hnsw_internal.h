@@ -395,8 +395,32 @@ int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_strid
 hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st);
 // hnsw_capi.hip: the handle's stream (hs[0]) and flag word of the host-buffer calls, made on first use
 int ensure_host_call_state(::hnsw_index *idx);
-// hnsw_capi.hip: the device address of [p, p + bytes) if it lies in a range of hnsw_host_alloc / hnsw_host_register, else null
-void *registered_device_address(const void *p, size_t bytes);
+
+// hnsw_capi.hip: where the device reads the host array [p, p + bytes): in place when it lies in a range of hnsw_host_alloc /
+// hnsw_host_register, else in `stage`, grown to hold it (resolve: allocates, queues nothing), after upload has queued the copy
+struct HostInput {
+    const void *dev = nullptr, *from = nullptr;     // from: the host array while it still has to be copied to dev, else null
+    size_t bytes = 0;
+    int resolve(const void *p, size_t n, DevBuf &stage);
+    int upload(hipStream_t st) const;
+};
+// hnsw_capi.hip: the matrices of one synchronous host-buffer call on the handle's stream hs[0] (rules: beside HostCall::begin)
+struct HostCall {
+    KnnBatch b{};                                   // what the kernels read and write
+    int k = 0;
+    bool small = false;                             // the handle's page-locked block holds the queries and every result
+    // the caller's arrays that finish still has to fill -- by download, `small`: out of the block --, null where the device
+    // writes in place (or the caller passed none)
+    int32_t *ids = nullptr;
+    float *dist = nullptr;
+    uint32_t *nd = nullptr, *nh = nullptr;
+    // *q_in_place: the device reads the queries from host memory (the knn call then hands knn_search scratch.q to stage them in)
+    int begin(::hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int k, int32_t *out_ids, float *out_dist,
+              uint32_t *out_nd, uint32_t *out_nh, bool allow_small, bool *q_in_place = nullptr);
+    // the results into those arrays: the download queued on st, ONE synchronisation (of st; null: of the device), the copy out of
+    // the block; a failed synchronisation reads "<what> failed: ..."
+    int finish(::hnsw_index *idx, const char *what, hipStream_t st);
+};
 
 // log2 entries of the per-query LDS visited cache (never changes results)
 inline int search_vt_bits(const hnsw_index *idx, int ef) {

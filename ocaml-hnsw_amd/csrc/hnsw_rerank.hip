@@ -151,31 +151,15 @@ int32_t hnsw_rerank_batch(hnsw_index *idx, const float *queries, int64_t nq, int
     for (int64_t i = 0; i < nq * cand_stride; ++i)         // (below id_base: padding)
         if (cand[i] >= top) return fail(HNSW_ERR_BAD_ARG, "Vector.get: candidate id %d out of range", cand[i]);
     HIP_TRY(hipSetDevice(idx->device));
-    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d), cbytes = (size_t)nq * cand_stride * 4, rbytes = (size_t)nq * k * 4;
-    if ((rc = idx->scratch.ensure(nq, qbytes, k)) || (rc = ensure_host_call_state(idx))) return rc;
+    HostInput cd;                                          // the candidates: in place, or staged in refine_scratch.ids
+    HostCall c;
+    if ((rc = cd.resolve(cand, (size_t)nq * cand_stride * 4, idx->refine_scratch.ids)) ||
+        (rc = c.begin(idx, queries, nq, q_stride, k, out_ids, out_dist, nullptr, nullptr, false))) return rc;
     hipStream_t st = idx->hs[0];
-    // as hnsw_search_batch: the caller's page-locked matrices are read and written in place, others go through the scratch
-    const float *zq = (const float *)registered_device_address(queries, qbytes);
-    const int32_t *zc = (const int32_t *)registered_device_address(cand, cbytes);
-    int32_t *zi = (int32_t *)registered_device_address(out_ids, rbytes);
-    float *zd = (float *)registered_device_address(out_dist, rbytes);
-    if (!zi || !zd) zi = nullptr, zd = nullptr;                      // results: both matrices or neither
-    KnnBatch b = idx->scratch.batch(nq, q_stride, k);
-    if (zq) b.Q = zq;
-    if (zi) b.ids = zi, b.dist = zd;
-    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
-    if (!zc) {
-        if ((rc = idx->refine_scratch.ids.ensure(cbytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(idx->refine_scratch.ids.p, cand, cbytes, hipMemcpyHostToDevice, st));
-        zc = (const int32_t *)idx->refine_scratch.ids.p;
-    }
-    rc = launch_rerank(idx, b.Q, nq, q_stride, zc, cand_stride, k, fill, b.ids, b.dist, nullptr, nullptr, st);
+    if (!(rc = cd.upload(st)))
+        rc = launch_rerank(idx, c.b.Q, nq, q_stride, (const int32_t *)cd.dev, cand_stride, k, fill, c.b.ids, c.b.dist, nullptr, nullptr, st);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    // no return while a copy into the caller's arrays may still be queued
-    const hipError_t ed = knn_download(b, k, zi ? nullptr : out_ids, zi ? nullptr : out_dist, nullptr, nullptr, st), es = hipStreamSynchronize(st);
-    if (ed != hipSuccess) return hip_fail(ed, "result download");
-    if (es != hipSuccess) return fail(HNSW_ERR_HIP, "re-rank failed: %s", hipGetErrorString(es));
-    return HNSW_OK;
+    return c.finish(idx, "re-rank", st);
 }
 
 } // extern "C"

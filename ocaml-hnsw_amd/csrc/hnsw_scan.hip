@@ -352,25 +352,11 @@ int32_t hnsw_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq
     int rc = check_scan(idx, nq, q_stride, k, fill, queries && out_ids && out_dist);
     if (rc || nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
-    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d), rbytes = (size_t)nq * k * 4;
-    if ((rc = idx->scratch.ensure(nq, qbytes, k)) || (rc = ensure_host_call_state(idx))) return rc;
-    hipStream_t st = idx->hs[0];
-    // as hnsw_search_batch: the caller's page-locked matrices are read and written in place, others go through the scratch
-    const float *zq = (const float *)registered_device_address(queries, qbytes);
-    int32_t *zi = (int32_t *)registered_device_address(out_ids, rbytes);
-    float *zd = (float *)registered_device_address(out_dist, rbytes);
-    if (!zi || !zd) zi = nullptr, zd = nullptr;                      // results: both matrices or neither
-    KnnBatch b = idx->scratch.batch(nq, q_stride, k);
-    if (zq) b.Q = zq;
-    if (zi) b.ids = zi, b.dist = zd;
-    if (!zq) HIP_TRY(hipMemcpyAsync(idx->scratch.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
-    rc = scan_search(idx, b, k, fill, st);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    // no return while a copy into the caller's arrays may still be queued
-    const hipError_t ed = knn_download(b, k, zi ? nullptr : out_ids, zi ? nullptr : out_dist, nullptr, nullptr, st), es = hipStreamSynchronize(st);
-    if (ed != hipSuccess) return hip_fail(ed, "result download");
-    if (es != hipSuccess) return fail(HNSW_ERR_HIP, "scan failed: %s", hipGetErrorString(es));
-    return HNSW_OK;
+    HostCall c;
+    if ((rc = c.begin(idx, queries, nq, q_stride, k, out_ids, out_dist, nullptr, nullptr, false))) return rc;
+    rc = scan_search(idx, c.b, k, fill, idx->hs[0]);
+    if (rc) { (void)hipStreamSynchronize(idx->hs[0]); return rc; }
+    return c.finish(idx, "scan", idx->hs[0]);
 }
 
 } // extern "C"
