@@ -160,8 +160,10 @@ enum { HNSW_ROWS_F32 = 0,   /* the float32 rows as handed over                  
        HNSW_ROWS_BYTES = 2, /* lossless byte copy (every value an integer in 0..255)                         */
        HNSW_ROWS_SPLIT = 3, /* float32 rows whose last 16 / 32 bytes past a 128-byte line are stored beside the
                                neighbour in the layer-0 adjacency (option "split_rows")                      */
-       HNSW_ROWS_HALF = 4 };/* the values rounded to fp16 (option "half_rows"): NOT the search over the float32
+       HNSW_ROWS_HALF = 4,  /* the values rounded to fp16 (option "half_rows"): NOT the search over the float32
                                vectors but the exact search over X rounded to fp16                          */
+       HNSW_ROWS_SQ8 = 5 }; /* 8-bit codes under one affine map (option "sq8_rows"): the walk is the exact search
+                               over the codes, the answer its candidates re-ranked over the float32 vectors  */
 
 typedef struct hnsw_index_info {
     int64_t n;
@@ -171,7 +173,7 @@ typedef struct hnsw_index_info {
     int64_t row_stride_bytes;  /* padded vector row on the device                             */
     int32_t device;
     int32_t row_format;        /* HNSW_ROWS_*: what the knn searches read right now (options "byte_rows", "split_rows",
-                                  "half_rows") */
+                                  "half_rows", "sq8_rows") */
 } hnsw_index_info;
 
 int32_t hnsw_abi_version(void);
@@ -252,6 +254,48 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   the float32 rows.  hnsw_index_insert makes the copy again for the grown index (new vectors out of
  *                   range: the whole insert is refused).  Not saved: a loaded index starts without half rows.
  *                   (Hand-scheduled loops exist for the other row formats only: half rows run the C++ hop loop.)
+ *                   HNSW_ERR_BAD_ARG while option "sq8_rows" is on.
+ *   "sq8_rows"      the knn searches WALK a copy of the vectors quantised to 8 bits under one affine map for the whole table and
+ *                   answer from the float32 rows: the byte-row kernels (a quarter of the bytes of float32 rows per evaluation,
+ *                   the hand-scheduled loops for 65..256 dimensions) for float data that is not byte-valued.
+ *                   1 = make the copy if it is missing and search it, 0 = read the previous rows again (the copy is kept),
+ *                   -1 = ... and FREE the copy (after a device synchronisation).
+ *                   QUANTISER (float32, round to nearest even, no contraction: numpy reproduces the bits): lo = min, hi = max
+ *                   over the n * d stored values; s = (hi - lo) / 255, s = 1 when hi == lo (a bound of -0 counts as +0);
+ *                   code(x) = min(255, max(0, rint((x - lo) / s))), ties to even.  Rows lie in the byte kernels' lane grid:
+ *                   64 * NCH bytes per row, zero padded.  A NaN or infinity in X, hi - lo overflowing, or a range so narrow
+ *                   (subnormal) that (hi - lo) / 255 rounds to 0, is HNSW_ERR_UNSUPPORTED and leaves the index unchanged.
+ *                   QUERY: L2: q' = (q - lo) / s, the same operations on the d real values (zero beyond d, matching the rows'
+ *                   padding); inner product: q' = q.  q' is NOT checked: a finite query value so large that (q - lo) / s
+ *                   overflows float32 walks with infinite or NaN distances in code space (the re-rank still returns exact
+ *                   distances for whatever the walk found); a NaN in a query behaves as it does on every other row format.
+ *                   With ONE map x^ = lo + s * code(x), |x^ - q|^2 = s^2 |code(x) - q'|^2 and
+ *                   <x^, q> = lo * sum(q) + s * <code(x), q>: the search over X^ orders exactly as the search over the codes.
+ *                   A SEARCH of (ef, k) while sq8 rows are read
+ *                     1. walks the codes B with q': the unchanged byte-row kernels, descent included -- bit for bit the search
+ *                        over B.astype(float32) with q' (the integer path runs when q' is byte-valued),
+ *                     2. takes the first c = min(ef, max(k, R)) members of W, R = option "refine" (0 gives c = k, -1 gives c = ef),
+ *                     3. re-ranks those c over the FLOAT32 rows with hnsw_rerank_batch's kernel and
+ *                     4. returns the first k under (distance, node id).
+ *                   The walk's distances live in code space and mean nothing to a caller, so the re-rank is unconditional: the
+ *                   returned distances are always the bits of hnsw_distance_batch over X.  out_nhops is the walk's count,
+ *                   out_ndist the walk's count plus c.  HNSW_SEM_FUNCTOR_NEAREST_K is HNSW_ERR_BAD_ARG, as with refine active.
+ *                   Applies to every knn form: hnsw_search_batch, _device, _h2d, hnsw_search_submit / _wait, hnsw_knn, and
+ *                   hnsw_multi_search_batch* through a replica's handle (hnsw_multi_replica).  Does NOT apply to the builder,
+ *                   hnsw_index_insert's searches, the layer operators, hnsw_distance_batch, hnsw_brute_force_batch and
+ *                   hnsw_rerank_batch, which keep reading the float32 rows.
+ *                   EXCLUSIONS: HNSW_ERR_BAD_ARG while byte rows are in use (they are exact and the same size: "byte_rows" 0
+ *                   first) and while "half_rows" is on; the split rows step aside as they do for half rows.
+ *                   hnsw_index_info.row_format reports HNSW_ROWS_SQ8, hnsw_index_row_bytes gives d, and the copy's
+ *                   n * 64 * NCH bytes count in device_bytes.  Not saved: a loaded index starts without it.  hnsw_index_insert
+ *                   quantises the WHOLE grown table again (the range may widen); a new vector that is not finite refuses the
+ *                   whole insert and leaves the index, the copy and its parameters as before.
+ *                   SCRATCH: q' ([nq][d padded to 16] floats) lives beside the refine scratch -- owned by the handle, by the
+ *                   request for submit / wait, sized on demand, not counted in device_bytes --: the same ONE
+ *                   hnsw_search_batch_device / hnsw_search_batch_h2d call in flight per handle as with refine active.
+ *                   hnsw_index_sq8_params / hnsw_index_sq8_codes give lo, s and the codes.  A scale per dimension would need a
+ *                   weighted distance in a kernel family of its own: not built.  Rate and recall: not measured yet
+ *                   (tools/sq8_rate.py prints the table for profiles/sq8_rows.txt).
  * and one that gives the half-row searches float32 answers again (off by default):
  *   "refine"        0 = off (default: behaviour is exactly as without the option); R in 1..1024 = a candidate count; -1 = all
  *                   of W; anything else is HNSW_ERR_BAD_ARG.  While the knn searches read the half rows, a search of (ef, k)
@@ -271,7 +315,8 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   The walk's [nq][c] results live in scratch the handle owns (per request for submit / wait), sized on
  *                   demand and not counted in device_bytes: with refine active ONE hnsw_search_batch_device /
  *                   hnsw_search_batch_h2d call in flight per handle (calls on one stream are ordered and therefore fine).
- *                   While the searches read any other rows (bytes, split, float32) the option is accepted and does nothing:
+ *                   While the searches read any other rows (bytes, split, float32) the option is accepted and does nothing
+ *                   -- except over sq8 rows (option "sq8_rows"), whose searches are always re-ranked and take c from it --:
  *                   those distances are exact over X already, results and out_ndist are bit-identical to refine 0; set
  *                   before "half_rows" it takes effect when half rows are turned on.  HNSW_SEM_FUNCTOR_NEAREST_K with refine
  *                   active is HNSW_ERR_BAD_ARG ("the k farthest of W" has no refined meaning).  hnsw_index_insert keeps the
@@ -279,8 +324,12 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   roughly 950 to 2400 half-row evaluations (the benchmark's float shapes); the rate has not been measured
  *                   yet (tools/refine_rate.py prints the table that belongs beside profiles/half_rows.txt). */
 int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value);
-/* Bytes of one vector as the knn searches read it: d for byte rows, 2 * d for half rows, 4 * d for float32 rows. */
+/* Bytes of one vector as the knn searches read it: d for byte and sq8 rows, 2 * d for half rows, 4 * d for float32 rows. */
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes);
+/* The sq8 copy (option "sq8_rows"), for callers who want X^ = lo + scale * codes: its two parameters, and its codes as
+ * [n][d] bytes (the rows' padding is not exported).  HNSW_ERR_BAD_ARG when no copy exists (never made, or freed by -1). */
+int32_t hnsw_index_sq8_params(const hnsw_index *idx, float *lo, float *scale);
+int32_t hnsw_index_sq8_codes(const hnsw_index *idx, uint8_t *out);
 /* Mean durations (ms) over the device-entry calls recorded since the last call of this function
  * (option "time_kernels"): the search kernel itself, and the ordering pre-pass (descent kernel +
  * sort; 0 when the batch was searched in the given order).  Waits for the recorded calls. */

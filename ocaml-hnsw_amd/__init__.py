@@ -26,8 +26,9 @@ ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED = -4, -5, -6, -7
 METRIC_L2, METRIC_IP = 0, 1
 FILL_OHNSW, FILL_BA = 0, 1
 SEM_OHNSW, SEM_FUNCTOR, SEM_FUNCTOR_NEAREST_K = 0, 1, 2
-# IndexInfo.row_format: what the knn searches read (HNSW_ROWS_*); ROWS_HALF only after set_option("half_rows", 1)
-ROWS_F32, ROWS_BYTES, ROWS_SPLIT, ROWS_HALF = 0, 2, 3, 4
+# IndexInfo.row_format: what the knn searches read (HNSW_ROWS_*); ROWS_HALF only after set_option("half_rows", 1), ROWS_SQ8 only
+# after set_option("sq8_rows", 1)
+ROWS_F32, ROWS_BYTES, ROWS_SPLIT, ROWS_HALF, ROWS_SQ8 = 0, 2, 3, 4, 5
 
 ABI_VERSION = 3          # HNSW_ABI_VERSION of include/hnsw_mi355x.h this mirror was written against
 
@@ -43,6 +44,8 @@ _ABI = {
     "hnsw_index_get_info": [_vp, _vp],
     "hnsw_index_set_option": [_vp, _str, _i64],
     "hnsw_index_row_bytes": [_vp, _vp],
+    "hnsw_index_sq8_params": [_vp, _vp, _vp],
+    "hnsw_index_sq8_codes": [_vp, _vp],
     "hnsw_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_device": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_h2d": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -404,13 +407,26 @@ class Hgraph:
         return inf
 
     def set_option(self, name, value):
+        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "refine", ...)"""
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
 
     def row_bytes(self):
-        """Bytes of one vector as the knn searches read it (d: byte rows, 2 d: half rows, 4 d: float32 rows)."""
+        """Bytes of one vector as the knn searches read it (d: byte and sq8 rows, 2 d: half rows, 4 d: float32 rows)."""
         v = _C.c_int64(0)
         _check(load().hnsw_index_row_bytes(self.handle, _C.byref(v)))
         return v.value
+
+    def sq8_params(self):
+        """hnsw_index_sq8_params -> (lo, scale) as float32 of the sq8 copy (set_option("sq8_rows", 1)): x ~ lo + scale * code"""
+        lo, s = _C.c_float(0), _C.c_float(0)
+        _check(load().hnsw_index_sq8_params(self.handle, _C.byref(lo), _C.byref(s)))
+        return _np.float32(lo.value), _np.float32(s.value)
+
+    def sq8_codes(self):
+        """hnsw_index_sq8_codes -> the codes of the sq8 copy, uint8 [n][d] (the rows' padding is not exported)"""
+        out = _np.empty((self.info().n, self.d), _np.uint8)
+        _check(load().hnsw_index_sq8_codes(self.handle, _ptr(out)))
+        return out
 
     def kernel_times(self):
         """(search kernel ms, ordering pre-pass ms, calls) averaged over the device-entry calls since the
@@ -749,6 +765,14 @@ class MultiHgraph:
         c = _C.c_int32(0)
         _check(load().hnsw_multi_num_replicas(self._h, _C.byref(c)))
         return c.value
+
+    def set_option(self, name, value):
+        """hnsw_index_set_option on every replica's handle (hnsw_multi_replica): the options that change results ("half_rows",
+        "sq8_rows", "refine") reach the sharded search this way"""
+        for g in range(self.num_replicas()):
+            h = _C.c_void_p()
+            _check(load().hnsw_multi_replica(self._h, g, _C.byref(h)))
+            _check(load().hnsw_index_set_option(h, name.encode(), int(value)))
 
     def _search(self, batch, ef, k, fill, sem, counters=False):
         Q, qs, nq = _batch(self.hgraph.d, batch)

@@ -400,6 +400,13 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
     if (idx->fb_queries > 0 && (int64_t)idx->dFbSlab.bytes / (n * 4) < 1)
         return fail(HNSW_ERR_BAD_ARG, "device_fallback_slab_bytes=%lld holds no query of the grown index: one needs 4 n = %lld bytes",
                     (long long)idx->dFbSlab.bytes, (long long)(n * 4));
+    // option sq8_rows is on: the codes are made again over the grown table, which needs every value finite -- asked before the
+    // graph is grown, not after
+    if (idx->sq8_on)
+        for (int64_t i = 0; i < m; ++i)
+            for (int32_t j = 0; j < idx->iv.d; ++j)
+                if (!std::isfinite(vectors[i * row_stride + j]))
+                    return fail(HNSW_ERR_UNSUPPORTED, "sq8 rows: value %d of new vector %lld is NaN or infinite: nothing inserted", j, (long long)i);
     HIP_TRY(hipSetDevice(idx->device));
     if (n_old > 0) {
         DevFlag flag;
@@ -427,10 +434,12 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
     // ... and what the handle derives from the graph, made again for it: the byte rows if ALL vectors are byte-valued, the split
     // rows (per-slot tails follow the changed adjacency) unless option split_rows -1 freed them for good, the half rows while
     // option half_rows is 1 (new vectors that do not fit fp16 refuse the whole insert; at 0 the copy is not carried over), the
-    // locality codes
+    // sq8 rows while option sq8_rows is 1 (the WHOLE table is quantised again: new vectors may widen the range; a range that
+    // overflows refuses the whole insert), the locality codes
     if (!rc) rc = make_byte_rows(nx.get());
     if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx.get());
     if (!rc && idx->half_rows_on) rc = make_half_rows(nx.get());
+    if (!rc && idx->sq8_on) rc = make_sq8_rows(nx.get());
     if (!rc) rc = extend_locality_codes(idx, nx.get());
     if (rc) {
         nx.reset();
@@ -446,6 +455,7 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
     std::swap(idx->tables, nx->tables);                    // (nx takes the old tables with it)
     idx->iv = nx->iv;
     idx->info = nx->info;
+    idx->sq8_lo = nx->sq8_lo; idx->sq8_scale = nx->sq8_scale;   // (of the swapped-in codes, if any)
     bind_view(idx);                                        // the options keep their effect
     idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
     nx.reset();

@@ -188,12 +188,12 @@ const struct { int metric, semf, rows; search_launch_fn launch; search_occupancy
 #undef HNSW_V_DECLARE
 #undef HNSW_V_ENTRY
 
-// the knn kernel's row format: 2 = byte rows (hnsw_rows8.hip), 3 = split fp32 rows (hnsw_rows_split.hip), 4 = half rows
-// (hnsw_rows16.hip), else plain fp32 rows, 1 = every chunk of the lane grid inside the row.  (From the record bind_view keeps:
-// byte and half rows share IndexView's pointer.)
+// the knn kernel's row format: 2 = byte rows (hnsw_rows8.hip) and the sq8 codes (hnsw_rows_sq8.hip: the same kernels), 3 = split
+// fp32 rows (hnsw_rows_split.hip), 4 = half rows (hnsw_rows16.hip), else plain fp32 rows, 1 = every chunk of the lane grid inside
+// the row.  (From the record bind_view keeps: byte, sq8 and half rows share IndexView's pointer.)
 inline int variant_full(const hnsw_index *idx) {
     switch (idx->info.row_format) {
-    case HNSW_ROWS_BYTES: return 2;
+    case HNSW_ROWS_BYTES: case HNSW_ROWS_SQ8: return 2;
     case HNSW_ROWS_SPLIT: return 3;
     case HNSW_ROWS_HALF: return 4;
     default: return idx->iv.nchunks == 16 * pick_nch(idx->iv.nchunks) ? 1 : 0;
@@ -315,6 +315,9 @@ int blk_capacity_bits(hnsw_index *idx, const KnnShape &sh) {
     return bits;
 }
 
+// do the knn searches run the byte-row kernels (over the byte rows, or over the sq8 codes)?
+inline bool walks_bytes(const hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_BYTES || idx->info.row_format == HNSW_ROWS_SQ8; }
+
 // does option "visited_blocks" at -1 consider this shape at all?
 bool blk_auto_eligible(const hnsw_index *idx, int nslot) {
     if (idx->iv.n < 200000) return false;
@@ -324,7 +327,8 @@ bool blk_auto_eligible(const hnsw_index *idx, int nslot) {
     // runs it, and the C++ loop of every other shape), but a byte-row kernel is bound by the LATENCY of a hop, and the filter's
     // four dependent LDS round trips and ~90 vector instructions cost a hop more than the evaluations it saves: the harder
     // SIFT-like set at ef 192, 8 % fewer evaluations, 0.98 -> 1.10 ms per 10 k batch (profiles/r05_ab_bytes_blocks.txt).
-    return idx->info.row_format != HNSW_ROWS_BYTES && idx->iv.nchunks > 16 && idx->iv.nchunks <= 64 && nslot <= 8;
+    // (The sq8 codes run the byte-row kernels.)
+    return !walks_bytes(idx) && idx->iv.nchunks > 16 && idx->iv.nchunks <= 64 && nslot <= 8;
 }
 
 int knn_blk_bits(hnsw_index *idx, const KnnShape &sh) {
@@ -347,6 +351,11 @@ int knn_blk_bits(hnsw_index *idx, const KnnShape &sh) {
     hipLaunchKernelGGL(probe_queries_kernel, dim3((unsigned)nq), dim3(64), 0, nullptr, idx->iv, step, (float *)probes.p);
     uint64_t sum[2] = {0, 0};
     bool ok = hipGetLastError() == hipSuccess;
+    // (sq8 rows: the probes are midpoints of float32 vectors and the walk reads code space -- moved there in place.  Not reached
+    // today: blk_auto_eligible leaves the byte-row kernels, sq8's among them, out of the measurement, and "visited_blocks" 1
+    // returns above.  Kept so that measuring them one day does not search float32 probes in code space.)
+    if (ok && idx->info.row_format == HNSW_ROWS_SQ8)
+        ok = sq8_transform_queries(idx, (const float *)probes.p, nq, idx->iv.stride, (float *)probes.p, nullptr, nullptr) == HNSW_OK;
     hnsw_search_params p{};
     p.ef = ef; p.k = 1; p.fill = HNSW_FILL_OHNSW; p.semantics = semf;
     const KnnBatch b{(const float *)probes.p, nq, idx->iv.stride, (int32_t *)out.p, (float *)out.p + nq, (uint32_t *)out.p + 2 * nq,
@@ -401,7 +410,7 @@ int balanced_lds_pad(hnsw_index *idx, const KnnShape &sh, int64_t nq) {
     if (nq <= resident || res.per_cu <= 0) return 0;
     // byte rows: a quarter of the bytes per evaluation, the launch is bound by the latency of a hop, not by the
     // memory system, and holds as many queries as the registers allow (C2: 0.60 ms per call at 8192 held, 0.65 at 5376)
-    if (idx->info.row_format == HNSW_ROWS_BYTES) return 0;
+    if (walks_bytes(idx)) return 0;
     constexpr int64_t GRANULE = 1280, GRANULES_PER_CU = 128;
     const int64_t passes = (nq + resident - 1) / resident;
     const int64_t want_per_cu = (nq + passes * idx->cus - 1) / (passes * idx->cus);
@@ -443,10 +452,25 @@ void launch_priorities(hnsw_index *idx, const KnnShape &sh, int64_t nq, SearchAr
 }
 
 // Option "refine": how many members of W a search of (ef, k) re-ranks over the float32 rows, 0 = none -- the option is off, or the
-// searches read rows whose distances are exact over X already (bytes, split, float32)
+// searches read rows whose distances are exact over X already (bytes, split, float32).  Over sq8 rows the walk's distances are
+// those of code space, which mean nothing to a caller: such a search is ALWAYS re-ranked, refine 0 takes the k first of W.
 int refine_count(const hnsw_index *idx, const hnsw_search_params *p) {
-    if (idx->refine == 0 || idx->info.row_format != HNSW_ROWS_HALF) return 0;
+    const int format = idx->info.row_format;
+    if (format != HNSW_ROWS_SQ8 && (idx->refine == 0 || format != HNSW_ROWS_HALF)) return 0;
     return idx->refine < 0 ? p->ef : std::min(p->ef, std::max(p->k, idx->refine));
+}
+// The queries a walk over sq8 rows reads: b's moved to code space in walk.qt (made here when `transform`: Q' = (Q - lo) / scale for
+// L2, Q for the inner product; stage: see sq8_transform_queries), at the padded stride.  Every launch that walks the codes -- the
+// ordering pre-pass, the search, the device fallback, knn_repair's re-run -- goes through here; the re-rank keeps the caller's.
+int sq8_walk_queries(hnsw_index *idx, RefineBufs &walk, KnnBatch *wb, bool transform, float *stage, hipStream_t st) {
+    const int64_t stride = padded_stride(idx->iv.d);
+    if (transform) {
+        int rc;
+        if ((rc = walk.qt.ensure((size_t)wb->nq * stride * sizeof(float))) ||
+            (rc = sq8_transform_queries(idx, wb->Q, wb->nq, wb->q_stride, (float *)walk.qt.p, stage, st))) return rc;
+    }
+    wb->Q = (const float *)walk.qt.p; wb->q_stride = stride;
+    return HNSW_OK;
 }
 // ... the walk of such a search: b with k := c, its results and evaluation counts in `walk`
 int refine_walk(const KnnBatch &b, int c, RefineBufs &walk, KnnBatch *wb) {
@@ -474,7 +498,8 @@ int check_params(const hnsw_index *idx, const hnsw_search_params *p) {
     if (p->semantics != HNSW_SEM_OHNSW && p->semantics != HNSW_SEM_FUNCTOR && p->semantics != HNSW_SEM_FUNCTOR_NEAREST_K)
         return fail(HNSW_ERR_BAD_ARG, "bad semantics %d", p->semantics);
     if (p->semantics == HNSW_SEM_FUNCTOR_NEAREST_K && refine_count(idx, p) > 0)
-        return fail(HNSW_ERR_BAD_ARG, "option refine is active: the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no refined meaning");
+        return fail(HNSW_ERR_BAD_ARG, "option %s is active: the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no refined meaning",
+                    idx->info.row_format == HNSW_ROWS_SQ8 ? "sq8_rows" : "refine");
     if (idx->iv.entry_point < 0) return fail(HNSW_ERR_EMPTY_INDEX, "knn: empty hgraph");
     return HNSW_OK;
 }
@@ -519,7 +544,6 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
     }
     const hnsw_search_params *params = &walk_params;
     const KnnShape sh = knn_shape(idx, params->ef, params->semantics);
-    SearchArgs a = knn_args(*params, b, knn_vt_bits(idx, sh), knn_blk_bits(idx, sh));
     // A batch larger than the chip holds at once is searched longest walk first (hnsw_order.hip):
     // per-query results are unchanged, the launch's drain phase is made of short walks.
     void *block = nullptr;
@@ -533,6 +557,14 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
         ev = &idx->tev[idx->tev_used];      // claimed (tev_used advanced) only once all three are recorded
         HIP_TRY(hipEventRecord(ev[0], st));
     }
+    const bool sq8 = idx->info.row_format == HNSW_ROWS_SQ8;      // (then refine_c > 0)
+    const float *rerank_Q = nullptr;                              // sq8: the caller's queries, which the re-rank reads
+    if (sq8) {                                                    // (behind ev[0]: timed with the pre-pass, or with the search when there is none)
+        if ((rc = sq8_walk_queries(idx, walk ? *walk : idx->refine_scratch, &b, true, d_stage, st))) return rc;
+        rerank_Q = d_stage ? d_stage : caller_b.Q;               // (the transform left a device copy of a host-resident matrix)
+        d_stage = nullptr;                                        // Q' is device-resident
+    }
+    SearchArgs a = knn_args(*params, b, knn_vt_bits(idx, sh), knn_blk_bits(idx, sh));
     const int mode = idx->order_mode;
     // Ordered when more than half of what the chip holds: a batch that fits is faster too with its long walks
     // dispatched first and spread over the CUs (C2, 7168 queries: 0.59 -> 0.45 ms byte rows, 0.68 -> 0.65 ms fp32);
@@ -561,9 +593,9 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
         rc = launch_rerun(idx, *params, read, (const int32_t *)idx->dFbMap.p, std::min<int64_t>(cap, b.nq), (uint32_t *)idx->dFbSlab.p,
                           (int32_t)std::min<int64_t>(idx->iv.n, 0x7FFFFFFF), st);
     }
-    if (!rc && refine_c > 0) {              // (behind the device fallback; reads the queries as the search read them)
+    if (!rc && refine_c > 0) {              // (behind the device fallback; reads the queries as the search read them, sq8: the caller's)
         KnnBatch to = caller_b;
-        to.Q = a.Q;
+        to.Q = sq8 ? rerank_Q : a.Q;
         rc = refine_rerank(idx, *caller_params, to, b, refine_c, st);
     }
     if (ev && !rc) {
@@ -581,7 +613,9 @@ int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, 
     KnnBatch wb = b;
     if (refine_c > 0) {                     // the walk's results are where knn_search left them: its flagged rows are rewritten there
         wp.k = refine_c;
-        const int rc = refine_walk(b, refine_c, walk ? *walk : idx->refine_scratch, &wb);
+        int rc = refine_walk(b, refine_c, walk ? *walk : idx->refine_scratch, &wb);
+        // (sq8 rows: the re-run walks the codes with the queries knn_search moved to code space)
+        if (!rc && idx->info.row_format == HNSW_ROWS_SQ8) rc = sq8_walk_queries(idx, walk ? *walk : idx->refine_scratch, &wb, false, nullptr, st);
         if (rc) return rc;
     }
     const int rc = rerun_overflowed(idx, b.nq, b.st, [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
@@ -735,14 +769,15 @@ int warm_up(hnsw_index *idx) {
 void bind_view(hnsw_index *idx) {
     const IndexTables &t = idx->tables;
     IndexView &iv = idx->iv;
-    // the knn searches read, in this order of precedence: byte rows (exact, the smallest), half rows (option half_rows 1),
-    // split rows, the plain float32 rows
-    const bool bytes = !idx->byte_rows_off && t.X8.p, half = !bytes && idx->half_rows_on && t.Xh.p;
+    // the knn searches read, in this order of precedence: byte rows (exact, the smallest), sq8 rows (option sq8_rows 1: in the
+    // byte rows' place, for the same kernels) or half rows (option half_rows 1; the two options exclude each other), split rows, the
+    // plain float32 rows
+    const bool bytes = !idx->byte_rows_off && t.X8.p, sq8 = !bytes && idx->sq8_on && t.Xq.p, half = !bytes && !sq8 && idx->half_rows_on && t.Xh.p;
     iv.X = (const float *)t.X.p;
-    iv.X8 = bytes ? (const uint8_t *)t.X8.p : nullptr;
+    iv.X8 = bytes ? (const uint8_t *)t.X8.p : sq8 ? (const uint8_t *)t.Xq.p : nullptr;
     if (half) iv.Xh = (const uint2 *)t.Xh.p;
     iv.stride8 = (half ? 128 : 64) * pick_nch(iv.nchunks);
-    iv.Xm = idx->split_rows_off || half ? nullptr : (const float *)t.Xm.p;
+    iv.Xm = idx->split_rows_off || half || sq8 ? nullptr : (const float *)t.Xm.p;
     iv.tail0 = (const float *)t.tail0.p;
     iv.nbr0 = (const int32_t *)t.nbr0.p; iv.nbrU = (const int32_t *)t.nbrU.p;
     iv.upper_off = (const int32_t *)t.off.p; iv.upper_lvl = (const uint8_t *)t.lvl.p; iv.upper_ref = (const int2 *)t.ref.p;
@@ -750,7 +785,7 @@ void bind_view(hnsw_index *idx) {
     hnsw_index_info &inf = idx->info;
     inf.n = iv.n; inf.max_degree0 = iv.S0; inf.max_layer = iv.max_layer; inf.entry_point = (int64_t)iv.entry_point + iv.id_base;
     inf.row_stride_bytes = iv.stride * 4;
-    inf.row_format = bytes ? HNSW_ROWS_BYTES : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
+    inf.row_format = bytes ? HNSW_ROWS_BYTES : sq8 ? HNSW_ROWS_SQ8 : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
 }
 
 int finish_index(IndexPtr owned, int32_t expected_ef, int32_t expected_semantics, hnsw_index **out) {
@@ -951,7 +986,7 @@ int32_t hnsw_index_prepare(hnsw_index *idx, const hnsw_search_params *params) {
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes) {
     if (!idx || !row_bytes) return fail(HNSW_ERR_BAD_ARG, "null argument");
     const int f = idx->info.row_format;
-    *row_bytes = (int64_t)idx->iv.d * (f == HNSW_ROWS_BYTES ? 1 : f == HNSW_ROWS_HALF ? 2 : 4);
+    *row_bytes = (int64_t)idx->iv.d * (f == HNSW_ROWS_BYTES || f == HNSW_ROWS_SQ8 ? 1 : f == HNSW_ROWS_HALF ? 2 : 4);
     return HNSW_OK;
 }
 
@@ -984,6 +1019,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
             if (idx->info.row_format == HNSW_ROWS_BYTES)
                 return fail(HNSW_ERR_BAD_ARG, "half_rows: the index searches its byte rows, which are exact and half the size of half rows "
                                               "(set byte_rows 0 first)");
+            if (idx->sq8_on) return fail(HNSW_ERR_BAD_ARG, "half_rows: option sq8_rows is on (set sq8_rows 0 first)");
             if (!idx->tables.Xh.p) {
                 const int rc = make_half_rows(idx);     // (a refusal -- NaN, fp16 overflow -- leaves the index as it was)
                 if (rc) return rc;
@@ -1001,7 +1037,29 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         idx->forget_shapes();
         return HNSW_OK;
     }
-    if (!strcmp(name, "refine")) {        // 0: off; 1..1024: re-rank max(k, value) members of W over the float32 rows; -1: all ef (half rows only)
+    if (!strcmp(name, "sq8_rows")) {      // 1: walk the 8-bit codes (made now if missing), re-rank over the fp32 rows; 0: the previous rows again, the codes kept; -1: ... and freed
+        if (value > 0) {
+            if (idx->info.row_format == HNSW_ROWS_BYTES)
+                return fail(HNSW_ERR_BAD_ARG, "sq8_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)");
+            if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option half_rows is on (set half_rows 0 first)");
+            if (!idx->tables.Xq.p) {
+                const int rc = make_sq8_rows(idx);      // (a refusal -- NaN, infinity, range overflow -- leaves the index as it was)
+                if (rc) return rc;
+            }
+            idx->sq8_on = true;
+        } else {
+            if (value < 0 && idx->tables.Xq.p) {
+                HIP_TRY(hipSetDevice(idx->device));
+                HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy
+                idx->tables.Xq.release();
+            }
+            idx->sq8_on = false;
+        }
+        bind_view(idx);
+        idx->forget_shapes();
+        return HNSW_OK;
+    }
+    if (!strcmp(name, "refine")) {        // 0: off; 1..1024: re-rank max(k, value) members of W over the float32 rows; -1: all ef (half and sq8 rows only)
         if (value < -1 || value > 1024) return fail(HNSW_ERR_BAD_ARG, "refine=%lld: 0 (off), 1..1024 candidates or -1 (all of W)", (long long)value);
         idx->refine = (int)value;
         return HNSW_OK;

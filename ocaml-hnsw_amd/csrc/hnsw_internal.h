@@ -4,6 +4,7 @@
 #include "hnsw_device.hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -141,13 +142,13 @@ template <class T> struct Pinned : Owned<T *, hipHostFree> {
 };
 
 // Every device table an index holds: the vectors and the graph, and the copies derived from them -- byte rows (X8, hnsw_rows8.hip),
-// half rows (Xh, hnsw_rows16.hip), split rows (Xm / tail0, hnsw_rows_split.hip), locality codes (lcode / lcode0, hnsw_locality.hip);
-// a derived table that does not exist has p == nullptr.  bind_view points the handle's IndexView at them.
+// half rows (Xh, hnsw_rows16.hip), sq8 rows (Xq, hnsw_rows_sq8.hip), split rows (Xm / tail0, hnsw_rows_split.hip), locality codes
+// (lcode / lcode0, hnsw_locality.hip); a derived table that does not exist has p == nullptr.  bind_view points the handle's IndexView at them.
 struct IndexTables {
-    Table X, X8, Xh, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
+    Table X, X8, Xh, Xq, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
     template <class Self, class F> static void each(Self &t, F f) {
-        static constexpr Table IndexTables::*all[] = {&IndexTables::X, &IndexTables::X8, &IndexTables::Xh, &IndexTables::Xm, &IndexTables::tail0,
-                                                      &IndexTables::lcode, &IndexTables::lcode0, &IndexTables::nbr0, &IndexTables::nbrU,
+        static constexpr Table IndexTables::*all[] = {&IndexTables::X, &IndexTables::X8, &IndexTables::Xh, &IndexTables::Xq, &IndexTables::Xm,
+                                                      &IndexTables::tail0, &IndexTables::lcode, &IndexTables::lcode0, &IndexTables::nbr0, &IndexTables::nbrU,
                                                       &IndexTables::off, &IndexTables::lvl, &IndexTables::ref};
         for (Table IndexTables::*m : all) f(t.*m);
     }
@@ -188,10 +189,11 @@ struct BatchBufs {
 };
 
 // the walk's side of a refined search (option "refine"): the first c members of W per query -- ids and distances [nq][c] -- and the
-// walk's evaluation counts [nq], which the re-rank reads; ids also stages hnsw_rerank_batch's candidates.  Not index tables: not
-// counted in device_bytes.
+// walk's evaluation counts [nq], which the re-rank reads; ids also stages hnsw_rerank_batch's candidates.  Beside them qt: the
+// queries the walk reads while the index searches its sq8 rows (Q', [nq][padded_stride(d)] floats: sq8_transform_queries), sized by
+// knn_search.  Not index tables: not counted in device_bytes.
 struct RefineBufs {
-    DevBuf ids, dist, nd;
+    DevBuf ids, dist, nd, qt;
     int ensure(int64_t nq, int c) {
         int rc;
         if ((rc = ids.ensure((size_t)nq * c * 4)) || (rc = dist.ensure((size_t)nq * c * 4)) || (rc = nd.ensure((size_t)nq * 4))) return rc;
@@ -311,6 +313,10 @@ struct hnsw_index {
     // bring no scratch of their own (every entry point but submit / wait).
     int refine = 0;
     hnsw_host::RefineBufs refine_scratch;
+    // option "sq8_rows": the knn searches walk tables.Xq, the 8-bit codes of x ~ sq8_lo + sq8_scale * code (1), or it is off (0, -1).
+    // sq8_lo / sq8_scale describe tables.Xq whenever it exists.  hnsw_index_insert quantises the whole grown table again while it is on.
+    bool sq8_on = false;
+    float sq8_lo = 0.0f, sq8_scale = 1.0f;
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
 };
 
@@ -321,7 +327,8 @@ struct IndexDeleter { void operator()(::hnsw_index *idx) const { (void)hnsw_inde
 using IndexPtr = std::unique_ptr<::hnsw_index, IndexDeleter>;
 
 // hnsw_capi.hip: IndexView's table pointers from idx->tables (X8 / Xm left out while option byte_rows / split_rows is 0; Xh in
-// the view while option half_rows is 1 and no byte rows are: it takes the place of Xm), and the hnsw_index_info fields that
+// the view while option half_rows is 1 and no byte rows are: it takes the place of Xm; Xq in the byte rows' place while option
+// sq8_rows is 1 and no byte rows are: Xm steps aside too), and the hnsw_index_info fields that
 // restate the view (n, max_degree0, max_layer, entry_point, row_stride_bytes, row_format).  Called by every change of the tables
 // or of those options.
 void bind_view(::hnsw_index *idx);
@@ -334,6 +341,14 @@ int make_byte_rows(::hnsw_index *idx);
 // hnsw_rows16.hip: the half copy of tables.X (tables.Xh): HNSW_ERR_UNSUPPORTED, nothing allocated, when a value is NaN or
 // rounds to an fp16 infinity; HNSW_ERR_OOM when there is no room for it.  Leaves the view to the caller (bind_view).
 int make_half_rows(::hnsw_index *idx);
+// hnsw_rows_sq8.hip: the 8-bit codes of tables.X under one affine map (tables.Xq, sq8_lo, sq8_scale), all or nothing:
+// HNSW_ERR_UNSUPPORTED when a value is NaN or infinite or max - min overflows; HNSW_ERR_OOM when there is no room.  Leaves the
+// view to the caller (bind_view).
+int make_sq8_rows(::hnsw_index *idx);
+// ... and nq queries moved to the codes' space on `st`: Qt ([nq][padded_stride(d)] floats) = (Q - lo) / scale for L2, Q for the
+// inner product, zero beyond d.  Q may be a registered host matrix seen from the device; stage (optional, [nq][q_stride] device
+// floats) then receives the queries as they were read.  Q == Qt (same stride) is allowed.
+int sq8_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st);
 // hnsw_rows_split.hip: if a row ends 1..32 bytes past a 128-byte line (and there are no byte rows), build the split copy
 // (tables.Xm / tail0, iv.stride_m / main_chunks / tail_chunks); call after make_byte_rows, graph in place
 int make_split_rows(::hnsw_index *idx);
@@ -380,8 +395,10 @@ int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, i
 int check_params(const ::hnsw_index *idx, const hnsw_search_params *p);
 // hnsw_capi.hip: hnsw_search_batch_device for a KnnBatch, whose any_flag word (optional) collects status bit 0 of the launch.
 // d_stage (optional, [nq][q_stride] device floats): b.Q points into registered host memory (see order_longest_first).
-// While option "refine" is active (refine_count) the walk writes its first c members of W into `walk` (null: the handle's
-// refine_scratch) and the re-rank kernel, queued behind it, writes b's ids, distances and evaluation counts.
+// While option "refine" is active or the index searches its sq8 rows (refine_count) the walk writes its first c members of W into
+// `walk` (null: the handle's refine_scratch) and the re-rank kernel, queued behind it, writes b's ids, distances and evaluation
+// counts.  Over sq8 rows the walk -- ordering pre-pass, device fallback and knn_repair's re-run included -- reads the queries in
+// code space (walk->qt), the re-rank the caller's.
 int knn_search(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, float *d_stage = nullptr,
                RefineBufs *walk = nullptr);
 // hnsw_capi.hip: the exactness fallback of the host-buffer entry points (see rerun_overflowed) for a batch knn_search ran:

@@ -96,7 +96,7 @@ hipError_t launch_descent(const hnsw_index *idx, int row_format, const float *Q,
         }); });
     };
     switch (row_format) {
-    case HNSW_ROWS_BYTES: rows(Int<2>{}); break;
+    case HNSW_ROWS_BYTES: case HNSW_ROWS_SQ8: rows(Int<2>{}); break;       // (sq8: the codes in the byte rows' place, the queries in code space)
     case HNSW_ROWS_HALF: rows(Int<4>{}); break;
     default: rows(Int<-1>{}); break;
     }
@@ -111,8 +111,8 @@ int descent_entries(::hnsw_index *idx, const float *d_queries, int64_t nq, int64
     if (nq <= 0) return HNSW_OK;
     uint32_t *key = d_scratch, *nd = d_scratch + nq, *sortkey = d_scratch + 2 * nq;
     int32_t *index = (int32_t *)(d_scratch + 3 * nq);
-    // (the locality codes' descents: over X whatever option half_rows says -- byte rows are X itself -- so that the codes do not
-    // depend on it)
+    // (the locality codes' descents: over X whatever options half_rows / sq8_rows say -- byte rows are X itself -- so that the
+    // codes do not depend on them)
     const int rows = idx->info.row_format == HNSW_ROWS_BYTES ? HNSW_ROWS_BYTES : HNSW_ROWS_F32;
     const hipError_t e = launch_descent(idx, rows, d_queries, q_stride, nq, to_layer, d_entry, key, nd, sortkey, index, nullptr, st);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "descent launch failed: %s", hipGetErrorString(e));

@@ -38,9 +38,10 @@ inline void check(int rc) {
 }
 
 // hnsw_index_info.row_format: what the knn searches read (HNSW_ROWS_*); HALF only after hnsw_index_set_option(h, "half_rows", 1),
-// which makes them search the vectors rounded to fp16
+// which makes them search the vectors rounded to fp16; SQ8 only after hnsw_index_set_option(h, "sq8_rows", 1), which makes them
+// walk 8-bit codes of the vectors and re-rank over the float32 rows
 namespace Rows {
-constexpr int F32 = HNSW_ROWS_F32, BYTES = HNSW_ROWS_BYTES, SPLIT = HNSW_ROWS_SPLIT, HALF = HNSW_ROWS_HALF;
+constexpr int F32 = HNSW_ROWS_F32, BYTES = HNSW_ROWS_BYTES, SPLIT = HNSW_ROWS_SPLIT, HALF = HNSW_ROWS_HALF, SQ8 = HNSW_ROWS_SQ8;
 }
 
 // Flattened Ohnsw.Hgraph.t / Hnsw.Ba.Hgraph.t resident on the device.
@@ -72,6 +73,18 @@ public:
 };
 
 struct value_distance { int node; float distance_to_target; }; // lib/hnsw_algo.ml:85
+
+// The sq8 copy of an index (hnsw_index_set_option(h, "sq8_rows", 1)): x ~ lo + scale * code; codes: [n][d] bytes.  Throws
+// std::invalid_argument when the index has no such copy.
+struct Sq8 { float lo, scale; std::vector<uint8_t> codes; };
+inline Sq8 sq8(const Hgraph &g) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    Sq8 out{0.0f, 1.0f, std::vector<uint8_t>((size_t)inf.n * (size_t)inf.d)};
+    check(hnsw_index_sq8_params(g.handle(), &out.lo, &out.scale));
+    check(hnsw_index_sq8_codes(g.handle(), out.codes.data()));
+    return out;
+}
 
 // A Lacaml-shaped float32 matrix (dim x n) in page-locked memory the library allocates (hnsw_host_alloc): knn_batch*
 // reads such a query matrix straight from the device, without an upload step.

@@ -81,6 +81,12 @@ let hnsw_index_set_option =
    `hnsw_index_set_option idx "half_rows" 1L` (the vectors rounded to fp16: results change, see the C header). *)
 let hnsw_index_row_bytes =
   foreign ~from:lib "hnsw_index_row_bytes" (index @-> ptr int64_t @-> returning int32_t)
+(* the sq8 copy (`hnsw_index_set_option idx "sq8_rows" 1L`: the knn searches walk 8-bit codes of the vectors and answer from the
+   float32 rows, see the C header): its parameters lo and scale (x ~ lo + scale * code), and its codes, [n][d] bytes *)
+let hnsw_index_sq8_params =
+  foreign ~from:lib "hnsw_index_sq8_params" (index @-> ptr float @-> ptr float @-> returning int32_t)
+let hnsw_index_sq8_codes =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_sq8_codes" (index @-> ptr void @-> returning int32_t)
 let hnsw_index_kernel_times =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_kernel_times"
     (index @-> ptr double @-> ptr double @-> ptr int32_t @-> returning int32_t)
@@ -199,11 +205,13 @@ let ii_row_stride_bytes = field index_info "row_stride_bytes" int64_t
 let ii_device = field index_info "device" int32_t
 let ii_row_format = field index_info "row_format" int32_t
 (* its values, HNSW_ROWS_*: float32 rows, byte rows, split rows, half rows (only after `hnsw_index_set_option idx
-   "half_rows" 1L`: the search over the vectors rounded to fp16) *)
+   "half_rows" 1L`: the search over the vectors rounded to fp16), sq8 rows (only after `hnsw_index_set_option idx "sq8_rows" 1L`:
+   the walk over 8-bit codes, re-ranked over the float32 rows) *)
 let rows_f32 = 0l
 let rows_bytes = 2l
 let rows_split = 3l
 let rows_half = 4l
+let rows_sq8 = 5l
 let () = seal index_info
 let hnsw_index_get_info = foreign ~from:lib "hnsw_index_get_info" (index @-> ptr index_info @-> returning int32_t)
 (* the flattened graph of a device index (built there by hnsw_build, or loaded from a file) back to the host *)
@@ -864,6 +872,19 @@ let locality_codes (t : t) : (int32, Bigarray.int32_elt, Bigarray.c_layout) A1.t
   check (hnsw_index_get_info t.handle (addr inf));
   let out = A1.create Bigarray.int32 Bigarray.c_layout (max 1 (Int64.to_int (getf inf ii_n))) in
   check (hnsw_index_locality_codes t.handle (bigarray_start array1 out));
+  out
+
+(* the sq8 copy of the index (option "sq8_rows"): (lo, scale) and the codes, one row of d bytes per node; Invalid_argument when
+   the index has no such copy *)
+let sq8_params (t : t) : float * float =
+  let lo = allocate float 0.0 and scale = allocate float 0.0 in
+  check (hnsw_index_sq8_params t.handle lo scale);
+  (!@ lo, !@ scale)
+let sq8_codes (t : t) : (int, Bigarray.int8_unsigned_elt, Bigarray.c_layout) Bigarray.Array2.t =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let out = Bigarray.Array2.create Bigarray.int8_unsigned Bigarray.c_layout (max 1 (Int64.to_int (getf inf ii_n))) t.dim in
+  check (hnsw_index_sq8_codes t.handle (to_voidp (bigarray_start array2 out)));
   out
 
 (* everything the first search with this ef (and accept rule) would do once -- the visited-structure decision, the kernel's
