@@ -32,6 +32,8 @@
  *   hnsw_brute_force_batch   brute_force_knn_l2 (benchmark/dataset.ml:15-30): the exact scan recall is measured against
  *   hnsw_rerank_batch        (nothing in the reference) the k nearest of caller-given candidates over the float32 vectors:
  *                            the refine step of the half-row searches (option "refine")
+ *   hnsw_search_batch_filtered  (nothing in the reference) the k nearest AMONG the nodes an allow-mask names (hnsw_filter_create):
+ *                            several tenants, categories or time windows in one index; a mask of live nodes = soft deletes
  *   hnsw_host_alloc / hnsw_host_register   (nothing in the reference) page-locked query / result matrices,
  *                            which the entry points above read and write from the device in place
  *
@@ -467,6 +469,57 @@ int32_t hnsw_rerank_batch(hnsw_index *idx, const float *queries, int64_t nq, int
 int32_t hnsw_rerank_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
                                  const int32_t *d_cand, int32_t cand_stride, int32_t k, int32_t fill,
                                  int32_t *d_ids, float *d_dist, void *stream);
+
+/* ---- filtered search: the k nearest among the nodes an allow-mask names -------------------------------------------------------
+ * THE FILTER.  hnsw_filter_create uploads `bits`, a host array of ceil(n_bits / 32) words (not retained): bit (v & 31) of word
+ * (v >> 5) set = the 0-based node v is allowed, whatever id_base is (the node the searches report as v + id_base).  n_bits must be
+ * the index's current n (HNSW_ERR_BAD_ARG otherwise); bits at positions >= n in the last word are ignored (the device copy has
+ * them clear).  The filter is uploaded once and belongs to the index and the device it was made for; hnsw_filter_count gives the
+ * number of allowed nodes (counted on the device at creation).  A filter is refused by the search (HNSW_ERR_BAD_ARG) when it was
+ * made for another handle, or when hnsw_index_insert has grown the index since it was made: make a new one.  Destroying the index
+ * before its filters is the caller's error, as with requests (hnsw_filter_destroy itself stays valid: it only frees the mask).
+ * The mask's bytes are NOT counted in hnsw_index_info.device_bytes.  A filter is not saved with the index.  Any number of
+ * filters per index; a filter is never modified by a search.  A mask of the live nodes gives soft deletes without touching a
+ * graph table.
+ *
+ * THE RESULT of hnsw_search_batch_filtered, in terms of public calls only.  Let W_e(q) be the ids hnsw_search_batch returns for
+ * (ef = e, k = e) with the caller's semantics (HNSW_SEM_OHNSW / HNSW_SEM_FUNCTOR) -- the host form: exact, tie-overflow repair
+ * included; under half or sq8 rows that is the walk over those rows --, and A_e(q) the allowed members of W_e(q), in order.
+ *   1. LADDER.  e_0 = ef, e_{j+1} = min(1024, 2 * e_j).  A query is served at the first stage j with |A_{e_j}(q)| >= k.  Only the
+ *      queries still short are searched again at the next stage, as one compacted batch.  The walk itself is never filtered: it
+ *      is the walk every other entry point runs, over all nodes.
+ *   2. EXACT STAGE.  A query still short at e = 1024, and EVERY query when fewer than k nodes are allowed (n_allowed < k: no walk
+ *      is made), is answered by the exact scan restricted to the allowed nodes: the k smallest allowed nodes under the total order
+ *      (distance, node id), as hnsw_brute_force_batch defines its order and its bits; with fewer than k allowed nodes the first
+ *      entries are real and the rest filled per params->fill (HNSW_FILL_OHNSW: id -1, NaN; HNSW_FILL_BA: id -1, +inf).
+ *   3. DISTANCES ARE ALWAYS OVER THE FLOAT32 ROWS: the bits of hnsw_distance_batch for the returned ids, whatever
+ *      hnsw_index_info.row_format says.
+ *        - byte, split and float32 rows: the walk's distances are those bits already: the answer is the first k of A_e(q).
+ *        - HNSW_ROWS_HALF and HNSW_ROWS_SQ8: ALL members of A_e(q) are re-ranked over the float32 rows by hnsw_rerank_batch's
+ *          kernel and the first k under (distance, node id) are returned; option "refine" does not shorten the list here.  (The
+ *          disallowed members of W are handed to that kernel as padding, id_base - 1.)  The stage test is unchanged: at least k
+ *          allowed members in W.
+ *   4. OUTPUTS.  out_ids [nq][k] (id_base-based), out_dist [nq][k], ascending.  out_stage (optional, [nq]): j for a query served
+ *      at ladder stage j, 0xFFFFFFFF for the exact stage.  out_nhops (optional): the sum of the hops of the walks the query took
+ *      (0 without a walk).  out_ndist (optional): the sum of those walks' evaluations plus the candidates re-ranked (half / sq8
+ *      rows: |A_e(q)| at the stage that served it); for the exact stage that sum plus n_allowed.
+ *   5. ERRORS.  k > ef: HNSW_ERR_BAD_ARG; ef > 1024: HNSW_ERR_UNSUPPORTED; HNSW_SEM_FUNCTOR_NEAREST_K: HNSW_ERR_BAD_ARG; an empty
+ *      index: HNSW_ERR_EMPTY_INDEX; a null, foreign or outgrown filter: HNSW_ERR_BAD_ARG; nq == 0 is a no-op; null pointers,
+ *      q_stride and nq as hnsw_search_batch.  An error leaves the outputs untouched.  Matrices of hnsw_host_alloc /
+ *      hnsw_host_register are read and written in place, others are copied, as by the other host forms; complete on return.
+ *   6. DETERMINISM.  A query's answer depends on its own vector, the mask and (ef, k, semantics) only: not on the batch it is in,
+ *      and not on which stage other queries reached.
+ * Scratch (a stage's W, the short list, the gathered queries) belongs to the handle, is sized on demand and not counted in
+ * device_bytes: ONE filtered call in flight per handle.  There is no device-pointer form: the ladder needs the number of short
+ * queries on the host.  Cost: a mask that allows a fraction s of the nodes leaves about s * e members of W; below s ~ k / 1024 most
+ * queries end in the exact stage after walking the whole ladder (no threshold skips it: tools/filter_rate.py prints the rates). */
+typedef struct hnsw_filter hnsw_filter;
+int32_t hnsw_filter_create(hnsw_index *idx, const uint32_t *bits, int64_t n_bits, hnsw_filter **out);
+int32_t hnsw_filter_destroy(hnsw_filter *f);
+int32_t hnsw_filter_count(const hnsw_filter *f, int64_t *n_allowed);
+int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                   const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
+                                   uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage);
 
 /* ---- the layer-level functions of the path, as batched operators -------------------------------
  * hnsw_search_layer_batch = Ohnsw.search_k (lib/ohnsw.ml:543-588; params->semantics = OHNSW) or

@@ -56,6 +56,10 @@ _ABI = {
     "hnsw_brute_force_batch_device": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
     "hnsw_rerank_batch": [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
     "hnsw_rerank_batch_device": [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "hnsw_filter_create": [_vp, _vp, _i64, _vp],
+    "hnsw_filter_destroy": [_vp],
+    "hnsw_filter_count": [_vp, _vp],
+    "hnsw_search_batch_filtered": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_build": [_vp, _i64, _i32, _i64, _vp, _i32, _vp],
     "hnsw_index_insert": [_vp, _vp, _i64, _i64, _vp],
     "hnsw_select_neighbours_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
@@ -428,6 +432,11 @@ class Hgraph:
         _check(load().hnsw_index_sq8_codes(self.handle, _ptr(out)))
         return out
 
+    def filter(self, allow):
+        """hnsw_filter_create -> Filter: an allow-mask over this index's nodes.  allow: a boolean array of length n (entry v = node
+        v + id_base may be returned), or an array of node ids (id_base-based).  Valid until the index grows (insert_batch)."""
+        return Filter(self, allow)
+
     def kernel_times(self):
         """(search kernel ms, ordering pre-pass ms, calls) averaged over the device-entry calls since the
         last call (needs set_option("time_kernels", 1)); waits for them."""
@@ -488,6 +497,83 @@ def pin(array):
 def unpin(array):
     """hnsw_host_unregister"""
     _check(load().hnsw_host_unregister(_ptr(_np.asarray(array))))
+
+
+STAGE_EXACT = 0xFFFFFFFF   # out_stage of a query hnsw_search_batch_filtered answered by the masked exact scan
+
+
+def pack_allow(allow, n, id_base=0):
+    """The words hnsw_filter_create takes (uint32 [ceil(n / 32)], bit v & 31 of word v >> 5 = 0-based node v) from a boolean array
+    of length n, or from an array of node ids (id_base-based; an id twice is not an error)."""
+    a = _np.asarray(allow)
+    if a.dtype == _np.bool_:
+        if a.shape != (n,):
+            raise InvalidArgument("a boolean mask must have the index's n = %d entries" % n)
+        mask = a
+    else:
+        ids = a.astype(_np.int64).reshape(-1) - id_base
+        if a.size and (a.dtype.kind not in "iu" or ids.min() < 0 or ids.max() >= n):
+            raise InvalidArgument("allowed ids must be integers in id_base .. id_base + n - 1")
+        mask = _np.zeros(n, _np.bool_)
+        mask[ids] = True
+    words = (n + 31) // 32
+    padded = _np.zeros(words * 32, _np.uint8)
+    padded[:n] = mask
+    return _np.packbits(padded, bitorder="little").view("<u4").astype(_np.uint32) if words else _np.zeros(0, _np.uint32)
+
+
+class Filter:
+    """An allow-mask over the nodes of one index, resident on its device (hnsw_filter_create); see Hgraph.filter."""
+
+    def __init__(self, hgraph, allow):
+        self._f = None
+        n = hgraph.info().n
+        bits = pack_allow(allow, n, hgraph.id_base)
+        f = _C.c_void_p()
+        _check(load().hnsw_filter_create(hgraph.handle, _ptr(bits) if len(bits) else None, n, _C.byref(f)))
+        self._f, self._hg, self.n = f, hgraph, n
+
+    @property
+    def handle(self):
+        if self._f is None:
+            raise InvalidArgument("filter already released")
+        return self._f
+
+    def count(self):
+        """hnsw_filter_count: the number of allowed nodes"""
+        c = _C.c_int64(0)
+        _check(load().hnsw_filter_count(self.handle, _C.byref(c)))
+        return c.value
+
+    def release(self):
+        if self._f is not None:
+            load().hnsw_filter_destroy(self._f)
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _search_filtered(hgraph, flt, batch, ef, k, fill, counters=False, sem=0, out=None):
+    """hnsw_search_batch_filtered; flt: a Filter, or what Hgraph.filter takes (a mask made for this call)
+    -> (ids, dist), with counters (ids, dist, ndist, nhops, stage)."""
+    own = None if isinstance(flt, Filter) else Filter(hgraph, flt)
+    try:
+        Q, qs, nq = _batch(hgraph.d, batch)
+        ids, dist = _out_pair(nq, k, out)
+        nd = _np.zeros(nq, _np.uint32) if counters else None
+        nh = _np.zeros(nq, _np.uint32) if counters else None
+        stage = _np.zeros(nq, _np.uint32) if counters else None
+        p = _SearchParams(ef, k, fill, sem)
+        _check(load().hnsw_search_batch_filtered(hgraph.handle, (own or flt).handle, _ptr(Q), nq, qs, _C.byref(p), _ptr(ids), _ptr(dist),
+                                                 _ptr(nd), _ptr(nh), _ptr(stage)))
+    finally:
+        if own is not None:
+            own.release()
+    return (ids, dist, nd, nh, stage) if counters else (ids, dist)
 
 
 def _search(hgraph, batch, ef, k, fill, counters=False, sem=0, out=None):
@@ -577,6 +663,15 @@ class Ohnsw:
         ids [nq][k] (-1 where fewer than k were found), distances [nq][k] fp32 (NaN there).
         out = (ids, distances): write into the caller's matrices instead of fresh ones."""
         return _search(hgraph, batch, k if ef is None else ef, k, FILL_OHNSW, counters, out=out)
+
+    @staticmethod
+    def knn_batch_filtered(hgraph, k, batch, allow, ef=None, counters=False, out=None):
+        """knn_batch_bigarray among the nodes `allow` names (hnsw_search_batch_filtered) -> (ids, distances), with counters
+        (ids, distances, ndist, nhops, stage).  allow: a Filter (Hgraph.filter: uploaded once, reused), a boolean array of length
+        n or an array of ids.  W grows ef, 2 ef, ... 1024 until it holds k allowed nodes (stage = how often it doubled); a query
+        still short gets the exact scan over the allowed nodes (stage = STAGE_EXACT).  Distances are over the float32 vectors
+        whatever rows the index searches; ids -1 / NaN where fewer than k nodes are allowed."""
+        return _search_filtered(hgraph, allow, batch, k if ef is None else ef, k, FILL_OHNSW, counters, out=out)
 
     @staticmethod
     def brute_force_knn(hgraph, k, batch, fill=FILL_OHNSW, out=None):
@@ -732,6 +827,12 @@ class Ba:
         """-> distances [nq][k] fp32, +inf where fewer than k were found (lib/hnsw.ml:769-777)."""
         return _search(hgraph, batch, num_neighbours_search, num_neighbours, FILL_BA,
                        sem=SEM_FUNCTOR_NEAREST_K if nearest_k_compat else SEM_FUNCTOR)[1]
+
+    @staticmethod
+    def knn_batch_filtered(hgraph, batch, num_neighbours_search, num_neighbours, allow, counters=False):
+        """knn_batch among the nodes `allow` names (see Ohnsw.knn_batch_filtered; the functor accept rule, 1-based ids in a
+        1-based index, +inf / -1 where fewer than k nodes are allowed) -> (ids, distances), with counters (..., ndist, nhops, stage)."""
+        return _search_filtered(hgraph, allow, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR)
 
     @staticmethod
     def search(hgraph, layer, start_nodes, targets, size_nearest):

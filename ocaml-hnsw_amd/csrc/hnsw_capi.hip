@@ -530,12 +530,12 @@ int launch_rerun(hnsw_index *idx, const hnsw_search_params &p, const KnnBatch &b
 }
 
 int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const KnnBatch &caller_b, hipStream_t st, float *d_stage,
-               RefineBufs *walk) {
+               RefineBufs *walk, bool raw_walk) {
     int rc = check_batch(idx, caller_params, caller_b.nq, caller_b.q_stride, caller_b.Q && caller_b.ids && caller_b.dist);
     if (rc || caller_b.nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
     // refine active: everything below is today's search with k := c into the walk's scratch; the re-rank at the end answers the caller
-    const int refine_c = refine_count(idx, caller_params);
+    const int refine_c = raw_walk ? 0 : refine_count(idx, caller_params);
     hnsw_search_params walk_params = *caller_params;
     KnnBatch b = caller_b;
     if (refine_c > 0) {
@@ -557,7 +557,7 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
         ev = &idx->tev[idx->tev_used];      // claimed (tev_used advanced) only once all three are recorded
         HIP_TRY(hipEventRecord(ev[0], st));
     }
-    const bool sq8 = idx->info.row_format == HNSW_ROWS_SQ8;      // (then refine_c > 0)
+    const bool sq8 = idx->info.row_format == HNSW_ROWS_SQ8;      // (then refine_c > 0, unless raw_walk)
     const float *rerank_Q = nullptr;                              // sq8: the caller's queries, which the re-rank reads
     if (sq8) {                                                    // (behind ev[0]: timed with the pre-pass, or with the search when there is none)
         if ((rc = sq8_walk_queries(idx, walk ? *walk : idx->refine_scratch, &b, true, d_stage, st))) return rc;
@@ -607,13 +607,17 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
     return rc;
 }
 
-int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk) {
-    const int refine_c = refine_count(idx, p);
+int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk, bool raw_walk) {
+    const int refine_c = raw_walk ? 0 : refine_count(idx, p);
     hnsw_search_params wp = *p;
     KnnBatch wb = b;
-    if (refine_c > 0) {                     // the walk's results are where knn_search left them: its flagged rows are rewritten there
-        wp.k = refine_c;
-        int rc = refine_walk(b, refine_c, walk ? *walk : idx->refine_scratch, &wb);
+    if (refine_c > 0 || idx->info.row_format == HNSW_ROWS_SQ8) {
+        // the walk's results are where knn_search left them (raw_walk: in b itself): its flagged rows are rewritten there
+        int rc = HNSW_OK;
+        if (refine_c > 0) {
+            wp.k = refine_c;
+            rc = refine_walk(b, refine_c, walk ? *walk : idx->refine_scratch, &wb);
+        }
         // (sq8 rows: the re-run walks the codes with the queries knn_search moved to code space)
         if (!rc && idx->info.row_format == HNSW_ROWS_SQ8) rc = sq8_walk_queries(idx, walk ? *walk : idx->refine_scratch, &wb, false, nullptr, st);
         if (rc) return rc;

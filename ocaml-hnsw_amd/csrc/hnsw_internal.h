@@ -201,6 +201,16 @@ struct RefineBufs {
     }
 };
 
+// scratch of hnsw_search_batch_filtered (hnsw_filter.hip), sized on demand by the call; not index tables: not counted in device_bytes
+struct FilterBufs {
+    DevBuf wids, wdist, wnd, wnh, wst;   // one stage's walk: W ([m][e] ids and distances), evaluations, hops, status of its m queries
+    DevBuf cnt, cand;                    // per walked query its allowed members of W; half / sq8 rows: the masked W the re-rank reads
+    DevBuf rids, rdist, rnd;             // a compact [m][k] result (re-rank, exact scan) before its rows go to their queries
+    DevBuf list[2], count;               // the queries still short, written by one stage and read by the next; how many
+    DevBuf q;                            // their vectors, gathered ([m][padded_stride(d)])
+    DevBuf stage;                        // out_stage [nq]
+};
+
 inline int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
     return (s && *s) ? atoi(s) : dflt;
@@ -317,7 +327,16 @@ struct hnsw_index {
     // sq8_lo / sq8_scale describe tables.Xq whenever it exists.  hnsw_index_insert quantises the whole grown table again while it is on.
     bool sq8_on = false;
     float sq8_lo = 0.0f, sq8_scale = 1.0f;
+    hnsw_host::FilterBufs filter_scratch;   // hnsw_search_batch_filtered's stages: ONE such call in flight per handle
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
+};
+
+// an allow-mask over the nodes of one index (hnsw_filter_create): bit v of the device copy = node v (0-based) may be returned
+struct hnsw_filter {
+    const hnsw_index *idx = nullptr;     // the handle it was made for ...
+    int64_t n = 0;                       // ... and that handle's n then: a grown index refuses it
+    int64_t n_allowed = 0;               // set bits below n (filter_popcount_kernel)
+    hnsw_host::DevBuf bits;              // ceil(n / 32) words, the positions >= n of the last one clear
 };
 
 namespace hnsw_host {
@@ -393,21 +412,30 @@ int order_longest_first(::hnsw_index *idx, const float *d_queries, int64_t nq, i
 
 // hnsw_capi.hip: parameter / handle checks shared by every search entry point (HNSW_ERR_BAD_ARG, HNSW_ERR_EMPTY_INDEX, ...)
 int check_params(const ::hnsw_index *idx, const hnsw_search_params *p);
+// ... and of the batch entry points, in this order: the params and the handle, 0 <= nq <= INT32_MAX, then -- unless nq is 0, which
+// passes -- the buffers (`buffers`: none of the required ones is null) and q_stride >= d
+int check_batch(const ::hnsw_index *idx, const hnsw_search_params *p, int64_t nq, int64_t q_stride, bool buffers);
 // hnsw_capi.hip: hnsw_search_batch_device for a KnnBatch, whose any_flag word (optional) collects status bit 0 of the launch.
 // d_stage (optional, [nq][q_stride] device floats): b.Q points into registered host memory (see order_longest_first).
 // While option "refine" is active or the index searches its sq8 rows (refine_count) the walk writes its first c members of W into
 // `walk` (null: the handle's refine_scratch) and the re-rank kernel, queued behind it, writes b's ids, distances and evaluation
 // counts.  Over sq8 rows the walk -- ordering pre-pass, device fallback and knn_repair's re-run included -- reads the queries in
 // code space (walk->qt), the re-rank the caller's.
+// raw_walk: no re-rank whatever the options say -- b receives the walk's own W[0..k) and counters (sq8 rows: the queries still go
+// through walk->qt); what hnsw_search_batch_filtered masks and re-ranks itself (hnsw_filter.hip).
 int knn_search(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, float *d_stage = nullptr,
-               RefineBufs *walk = nullptr);
+               RefineBufs *walk = nullptr, bool raw_walk = false);
 // hnsw_capi.hip: the exactness fallback of the host-buffer entry points (see rerun_overflowed) for a batch knn_search ran:
 // rewrites the rows of the queries it flagged in b.st (refine active: their rows of `walk`, then the batch is re-ranked again)
-int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk = nullptr);
+int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk = nullptr,
+               bool raw_walk = false);
 // hnsw_rerank.hip: the re-rank kernel on `st` for device-resident arguments (hnsw_rerank_batch_device, unchecked); nd_out
 // (optional): nd_out[q] = (nd_in ? nd_in[q] : 0) + the number of candidates evaluated
 int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, const int32_t *cand, int32_t cand_stride, int32_t k,
                   int32_t fill, int32_t *out_ids, float *out_dist, const uint32_t *nd_in, uint32_t *nd_out, hipStream_t st);
+// hnsw_scan.hip: the exact scan of b's queries on `st` into b.ids / b.dist (hnsw_brute_force_batch_device, with its checks); mask
+// (optional, ceil(n / 32) device words): only the rows whose bit is set are candidates
+int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *mask = nullptr);
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
 hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st);
 // hnsw_capi.hip: the handle's stream (hs[0]) and flag word of the host-buffer calls, made on first use

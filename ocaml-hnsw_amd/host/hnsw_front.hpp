@@ -3,6 +3,7 @@
 //
 //   Hnsw::Ohnsw::knn / knn_batch_bigarray / build_batch_bigarray / insert / distance_l2   lib/ohnsw.ml:766-899
 //   Hnsw::Ohnsw::rerank                                                                    (hnsw_rerank_batch; nothing in the reference)
+//   Hnsw::Filter, Hnsw::Ohnsw::knn_filtered                                                (hnsw_filter_*, hnsw_search_batch_filtered)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
@@ -73,6 +74,28 @@ public:
 };
 
 struct value_distance { int node; float distance_to_target; }; // lib/hnsw_algo.ml:85
+
+// An allow-mask over the nodes of one index, resident on its device (hnsw_filter_create): allow[v] = node v + id_base may be
+// returned by Ohnsw::knn_filtered.  One entry per node; refused by the search once the index has grown (Ohnsw::insert).  Destroy
+// it before its index.
+class Filter {
+public:
+    Filter(const Hgraph &g, const std::vector<bool> &allow) {
+        std::vector<uint32_t> bits((allow.size() + 31) / 32, 0u);
+        for (size_t v = 0; v < allow.size(); ++v) if (allow[v]) bits[v >> 5] |= 1u << (v & 31);
+        check(hnsw_filter_create(g.handle(), bits.data(), (int64_t)allow.size(), &f_));
+    }
+    // ... from the packed words themselves: bit (v & 31) of word (v >> 5) = node v, n_bits = the index's n
+    Filter(const Hgraph &g, const uint32_t *bits, int64_t n_bits) { check(hnsw_filter_create(g.handle(), bits, n_bits, &f_)); }
+    Filter(const Filter &) = delete;
+    Filter &operator=(const Filter &) = delete;
+    Filter(Filter &&o) noexcept : f_(o.f_) { o.f_ = nullptr; }
+    ~Filter() { if (f_) hnsw_filter_destroy(f_); }
+    const hnsw_filter *handle() const { return f_; }
+    int64_t count() const { int64_t c = 0; check(hnsw_filter_count(f_, &c)); return c; }   // the allowed nodes
+private:
+    hnsw_filter *f_ = nullptr;
+};
 
 // The sq8 copy of an index (hnsw_index_set_option(h, "sq8_rows", 1)): x ~ lo + scale * code; codes: [n][d] bytes.  Throws
 // std::invalid_argument when the index has no such copy.
@@ -210,6 +233,25 @@ inline std::pair<std::vector<int32_t>, std::vector<float>> brute_force_knn(const
     std::vector<float> dist(ids.size());
     check(hnsw_brute_force_batch(g.handle(), batch.data, batch.dim2, batch.dim1, k, HNSW_FILL_OHNSW, ids.data(), dist.data()));
     return {std::move(ids), std::move(dist)};
+}
+
+// knn_batch_bigarray among the nodes a Filter allows (hnsw_search_batch_filtered): W grows ef, 2 ef, ... 1024 until it holds k
+// allowed nodes, a query still short gets the exact scan over the allowed nodes; distances are over the float32 vectors whatever
+// rows the index searches.  ids / distances [nq][k] (-1 / NaN where fewer than k nodes are allowed); stage[q] = how often W
+// doubled for query q, exact_stage = the exact scan.
+struct Filtered {
+    static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
+    std::vector<int32_t> ids; std::vector<float> dist; std::vector<uint32_t> stage;
+};
+inline Filtered knn_filtered(const Hgraph &g, const Filter &f, int k, const Mat &batch, int ef = 0, int sem = HNSW_SEM_OHNSW,
+                             int fill = HNSW_FILL_OHNSW) {
+    const size_t nq = (size_t)batch.dim2;
+    Filtered out{std::vector<int32_t>(nq * (size_t)(k > 0 ? k : 0), -1), std::vector<float>(nq * (size_t)(k > 0 ? k : 0), 0.f),
+                 std::vector<uint32_t>(nq, 0u)};
+    hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
+    check(hnsw_search_batch_filtered(g.handle(), f.handle(), batch.data, batch.dim2, batch.dim1, &p, out.ids.data(), out.dist.data(),
+                                     nullptr, nullptr, out.stage.data()));
+    return out;
 }
 
 // The exact re-rank (hnsw_rerank_batch): for each query the k nearest of ITS candidates cand[q][0 .. cand_stride) (entries below

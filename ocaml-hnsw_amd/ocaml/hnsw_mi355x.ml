@@ -135,6 +135,18 @@ let hnsw_rerank_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_rerank_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> int32_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float
      @-> returning int32_t)
+(* filtered search (see the C header): an allow-mask over the nodes, uploaded once, and the batch search among the nodes it names *)
+type filter_handle = unit ptr
+let filter_handle : filter_handle typ = ptr void
+let hnsw_filter_create =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_filter_create"
+    (index @-> ptr uint32_t @-> int64_t @-> ptr filter_handle @-> returning int32_t)
+let hnsw_filter_destroy = foreign ~from:lib "hnsw_filter_destroy" (filter_handle @-> returning int32_t)
+let hnsw_filter_count = foreign ~from:lib "hnsw_filter_count" (filter_handle @-> ptr int64_t @-> returning int32_t)
+let hnsw_search_batch_filtered =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_filtered"
+    (index @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> ptr int32_t @-> ptr float
+     @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
 let hnsw_select_neighbours_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_select_neighbours_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> ptr int32_t @-> int32_t @-> int32_t @-> int32_t
@@ -772,6 +784,52 @@ let rerank (t : t) (queries : Lacaml.S.mat) ~(candidates : int array array) ~k :
            (CArray.start cand) (Int32.of_int stride) (Int32.of_int k) 0l (CArray.start ids) (CArray.start dist));
   (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
    Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))))
+
+(* Filtered search (hnsw_filter_create / hnsw_search_batch_filtered): the k nearest AMONG the nodes a mask allows.
+   [filter_create t allow]: allow.(v) = node v + id_base may be returned; one entry per node of the index (the library refuses
+   any other length).  The mask is uploaded once and reused; it is refused once the index has grown ([insert]).  The filter keeps
+   its index alive; it is freed with the value. *)
+type filter = { f_handle : filter_handle; f_index : t }
+
+let filter_create (t : t) (allow : bool array) : filter =
+  let n = Array.length allow in
+  let words = (n + 31) / 32 in
+  let bits = CArray.make uint32_t ~initial:Unsigned.UInt32.zero (max 1 words) in
+  Array.iteri (fun v a ->
+      if a then CArray.set bits (v lsr 5) (Unsigned.UInt32.logor (CArray.get bits (v lsr 5)) (Unsigned.UInt32.shift_left Unsigned.UInt32.one (v land 31))))
+    allow;
+  let out = allocate filter_handle null in
+  check (hnsw_filter_create t.handle (CArray.start bits) (Int64.of_int n) out);
+  let f = { f_handle = !@out; f_index = t } in
+  Gc.finalise (fun f -> ignore (hnsw_filter_destroy f.f_handle)) f;
+  f
+
+(* the number of allowed nodes *)
+let filter_count (f : filter) : int =
+  let c = allocate int64_t 0L in
+  check (hnsw_filter_count f.f_handle c);
+  Int64.to_int !@c
+
+(* [knn_batch_filtered f batch ~ef ~k]: for each query (a column of [batch]) the k nearest allowed nodes.  W grows ef, 2 ef, ...
+   1024 until it holds k allowed nodes; a query still short is answered by the exact scan over the allowed nodes.  Distances are
+   over the float32 vectors whatever rows the index searches.  -> (ids, distances, stages), ids and distances [nq][k] (id -1,
+   distance nan -- ~fill:1: infinity -- where fewer than k nodes are allowed), stages.(q) = how often W doubled, -1 = exact scan.
+   ~semantics: 0 Ohnsw's accept rule, 1 the functor's (2 is refused). *)
+let knn_batch_filtered ?(semantics = 0) ?(fill = 0) (f : filter) (batch : Lacaml.S.mat) ~ef ~k :
+  int array array * float array array * int array =
+  let t = f.f_index in
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let stage = CArray.make uint32_t (max 1 nq) in
+  let p = make search_params in
+  setf p p_ef (Int32.of_int ef); setf p p_k (Int32.of_int k); setf p p_fill (Int32.of_int fill);
+  setf p p_semantics (Int32.of_int semantics);
+  check (hnsw_search_batch_filtered t.handle f.f_handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim)
+           (addr p) (CArray.start ids) (CArray.start dist) (from_voidp uint32_t null) (from_voidp uint32_t null)
+           (CArray.start stage));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
+   Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))
 
 (* brute_force_knn_l2 (benchmark/dataset.ml:15-30) with its body on the device: the distance matrix it returns
    (k x nq: column q = the ascending distances of test vector q's k nearest train vectors), for an index that holds the
