@@ -34,6 +34,8 @@
  *                            the refine step of the half-row searches (option "refine")
  *   hnsw_search_batch_filtered  (nothing in the reference) the k nearest AMONG the nodes an allow-mask names (hnsw_filter_create):
  *                            several tenants, categories or time windows in one index; a mask of live nodes = soft deletes
+ *   hnsw_range_search_batch  (nothing in the reference) EVERY node within a radius of the query, a result of variable length;
+ *                            hnsw_range_brute_force_batch is its exact form
  *   hnsw_host_alloc / hnsw_host_register   (nothing in the reference) page-locked query / result matrices,
  *                            which the entry points above read and write from the device in place
  *
@@ -520,6 +522,72 @@ int32_t hnsw_filter_count(const hnsw_filter *f, int64_t *n_allowed);
 int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
                                    const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
                                    uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage);
+
+/* ---- range search: every stored vector within a radius of the query -----------------------------------------------------------
+ * The other standard question of a vector index: not "the k nearest" but ALL nodes within distance `radius` (de-duplication,
+ * similarity thresholds, density queries, range recall).  The result has no fixed k -- 0 to n ids per query -- and is an object
+ * that owns its device buffers (hnsw_range_result): lims [nq + 1] (lims[0] = 0, lims[nq] = total), ids and distances [total];
+ * query q's SEGMENT is ids / dist [lims[q], lims[q + 1]).
+ *
+ * THE RESULT of the range calls, in terms of public calls only.
+ *   1. IN RANGE.  Node v is in range of q iff the float distance the library returns for the pair is <= radius: the bits of
+ *      hnsw_distance_batch (L2 after the square root, inner product as 1 - <a,b>), for both entry points.  Keys are monotone in
+ *      distance, so under the scan's order the in-range nodes are a prefix.  A NaN radius is HNSW_ERR_BAD_ARG; a radius below every
+ *      distance gives empty segments (lims[q + 1] == lims[q]); +inf gives everything.
+ *   2. ORDER.  Every segment is ascending in the order hnsw_brute_force_batch returns: ordered distance key, then node id --
+ *      (distance, node id).  Ids are id_base-based.  DISTANCES ARE ALWAYS OVER THE FLOAT32 ROWS, whatever
+ *      hnsw_index_info.row_format says.
+ *   3. hnsw_range_brute_force_batch.  The segment of q is exactly the in-range prefix of the full order over all n rows (what
+ *      hnsw_brute_force_batch would return for k = n).  No graph is needed; n = 0 gives HNSW_OK with all segments empty; row formats
+ *      and options never change it (option "scan_slabs" cuts the table, results do not depend on it).  out_stage is 0xFFFFFFFF,
+ *      out_ndist is n, out_nhops is 0.
+ *   4. hnsw_range_search_batch.  Let W_e(q) be what hnsw_search_batch returns for (ef = e, k = e) under the caller's rule
+ *      (HNSW_SEM_OHNSW / HNSW_SEM_FUNCTOR) -- the host form: exact, tie-overflow repair included.  Under HNSW_ROWS_HALF and
+ *      HNSW_ROWS_SQ8 W_e is the walk over those rows, and then ALL its members are re-ranked over the float32 rows by
+ *      hnsw_rerank_batch's kernel with k := e; option "refine" does not shorten the list.
+ *        LADDER.  e_0 = ef, e_{j+1} = min(1024, 2 * e_j).  A query is SERVED at the first stage j where W_{e_j}(q) is not saturated:
+ *      |W| < e_j (the walk ran out of graph), or its last member's distance is > radius.  The segment of a served query is the
+ *      in-range prefix of that W.  Only the queries still saturated are walked again, as one compacted batch in ascending query
+ *      order.  The walk is never modified: it is the walk every other entry point runs.
+ *        EXACT STAGE.  A query saturated at e = 1024 gets the exact segment of hnsw_range_brute_force_batch; its stage is 0xFFFFFFFF.
+ *   5. COUNTERS (hnsw_range_result_fetch, each optional, [nq]).  out_stage: j for a query served at ladder stage j, 0xFFFFFFFF for
+ *      the exact stage.  out_nhops: the sum of the hops of the walks taken.  out_ndist: the sum of those walks' evaluations, plus
+ *      |W_e| for every stage that re-ranked (half and sq8 rows), plus n for the exact stage.
+ *   6. ERRORS.  An error leaves *out NULL and nothing allocated.  ef < 1: HNSW_ERR_BAD_ARG; ef > 1024: HNSW_ERR_UNSUPPORTED;
+ *      HNSW_SEM_FUNCTOR_NEAREST_K: HNSW_ERR_BAD_ARG; an empty graph: HNSW_ERR_EMPTY_INDEX (the search only, not the brute-force form);
+ *      nq == 0: HNSW_OK with a valid empty result; null pointers, q_stride and nq as hnsw_search_batch.  A call whose total exceeds
+ *      2^31 - 1 results: HNSW_ERR_UNSUPPORTED, found after counting and before any result buffer is allocated.  Allocation failure:
+ *      HNSW_ERR_OOM.
+ *   7. DETERMINISM.  A query's answer depends on its own vector and (radius, ef, semantics) only: not on the batch it is in, and not
+ *      on which stage other queries reached.
+ * Buffers.  Query matrices of hnsw_host_alloc / hnsw_host_register are read in place, others are staged; complete on return.  Scratch
+ * (every stage's W, the saturated list, the gathered queries, the scan's counts, offsets and unsorted hits: 16 bytes per hit of the
+ * exact stage) belongs to the handle, is sized on demand and not counted in device_bytes: ONE range call in flight per handle.  The
+ * result's own buffers belong to the result: any number of results may be alive, and a result outlives later calls (destroy it before
+ * or after the index, as convenient: it holds no reference to the handle).  There is no device-pointer form: the ladder needs the
+ * number of saturated queries, and the result its total, on the host.  A replica of an hnsw_multi may be searched through its handle
+ * (hnsw_multi_replica).  After hnsw_index_insert the new nodes are found like any other.
+ * Cost: the exact stage reads the table twice (count, then fill) and sorts only its hits; a batch so large that its per-(query,
+ * slab) counts exceed the scan's 256 MiB of scratch is scanned in pieces, and then counts each piece once more before filling it
+ * (tools/range_rate.py prints the rates). */
+typedef struct hnsw_range_params {
+    float radius;      /* in range: distance <= radius                                              */
+    int32_t ef;        /* the ladder's first stage, 1..1024                                         */
+    int32_t semantics; /* HNSW_SEM_OHNSW or HNSW_SEM_FUNCTOR                                        */
+} hnsw_range_params;
+typedef struct hnsw_range_result hnsw_range_result;   /* owns its device buffers; any number may be alive */
+int32_t hnsw_range_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
+                                const hnsw_range_params *params, hnsw_range_result **out);
+/* exact; no graph needed */
+int32_t hnsw_range_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
+                                     float radius, hnsw_range_result **out);
+int32_t hnsw_range_result_size(const hnsw_range_result *r, int64_t *nq, int64_t *total);
+/* lims [nq + 1] (lims[0] = 0, lims[nq] = total), ids / dist [total], counters [nq]; every pointer may be NULL */
+int32_t hnsw_range_result_fetch(hnsw_range_result *r, int64_t *lims, int32_t *ids, float *dist,
+                                uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage);
+/* borrowed device pointers, valid until destroy (for callers that go on working on the device); each may be NULL */
+int32_t hnsw_range_result_device(hnsw_range_result *r, const int64_t **d_lims, const int32_t **d_ids, const float **d_dist);
+int32_t hnsw_range_result_destroy(hnsw_range_result *r);   /* NULL is HNSW_OK */
 
 /* ---- the layer-level functions of the path, as batched operators -------------------------------
  * hnsw_search_layer_batch = Ohnsw.search_k (lib/ohnsw.ml:543-588; params->semantics = OHNSW) or

@@ -34,7 +34,7 @@ ABI_VERSION = 3          # HNSW_ABI_VERSION of include/hnsw_mi355x.h this mirror
 
 # Every symbol include/hnsw_mi355x.h declares (tests check the .so exports all of them and compare the arities): name -> argument
 # types, the result an int32 status unless spelled out as (argument types, result type).  load() applies the table.
-_vp, _i32, _i64, _str = _C.c_void_p, _C.c_int32, _C.c_int64, _C.c_char_p
+_vp, _i32, _i64, _str, _f32 = _C.c_void_p, _C.c_int32, _C.c_int64, _C.c_char_p, _C.c_float
 _ABI = {
     "hnsw_abi_version": (None, _i32),
     "hnsw_last_error": (None, _str),
@@ -60,6 +60,12 @@ _ABI = {
     "hnsw_filter_destroy": [_vp],
     "hnsw_filter_count": [_vp, _vp],
     "hnsw_search_batch_filtered": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_range_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "hnsw_range_brute_force_batch": [_vp, _vp, _i64, _i64, _f32, _vp],
+    "hnsw_range_result_size": [_vp, _vp, _vp],
+    "hnsw_range_result_fetch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_range_result_device": [_vp, _vp, _vp, _vp],
+    "hnsw_range_result_destroy": [_vp],
     "hnsw_build": [_vp, _i64, _i32, _i64, _vp, _i32, _vp],
     "hnsw_index_insert": [_vp, _vp, _i64, _i64, _vp],
     "hnsw_select_neighbours_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
@@ -117,6 +123,10 @@ class _IndexDesc(_C.Structure):
 
 class _SearchParams(_C.Structure):
     _fields_ = [("ef", _C.c_int32), ("k", _C.c_int32), ("fill", _C.c_int32), ("semantics", _C.c_int32)]
+
+
+class _RangeParams(_C.Structure):
+    _fields_ = [("radius", _C.c_float), ("ef", _C.c_int32), ("semantics", _C.c_int32)]
 
 
 class _BuildParams(_C.Structure):
@@ -576,6 +586,71 @@ def _search_filtered(hgraph, flt, batch, ef, k, fill, counters=False, sem=0, out
     return (ids, dist, nd, nh, stage) if counters else (ids, dist)
 
 
+class RangeResult:
+    """What a range call returns, resident on the index's device (hnsw_range_result): lims [nq + 1], ids and distances [total];
+    query q's segment is [lims[q], lims[q + 1]).  For callers who keep the result on the device (device_pointers) or fetch parts
+    of it; Ohnsw.range_search and its kin fetch everything and release it."""
+
+    def __init__(self, handle):
+        self._r = handle
+
+    @property
+    def handle(self):
+        if self._r is None:
+            raise InvalidArgument("range result already released")
+        return self._r
+
+    def size(self):
+        """hnsw_range_result_size -> (nq, total)"""
+        nq, total = _C.c_int64(0), _C.c_int64(0)
+        _check(load().hnsw_range_result_size(self.handle, _C.byref(nq), _C.byref(total)))
+        return nq.value, total.value
+
+    def fetch(self, counters=False):
+        """hnsw_range_result_fetch -> (lims int64 [nq + 1], ids int32 [total], distances float32 [total]), with counters also
+        (ndist, nhops, stage), uint32 [nq] each"""
+        nq, total = self.size()
+        lims, ids, dist = _np.zeros(nq + 1, _np.int64), _np.empty(total, _np.int32), _np.empty(total, _np.float32)
+        cnt = [_np.zeros(nq, _np.uint32) for _ in range(3)] if counters else [None] * 3
+        _check(load().hnsw_range_result_fetch(self.handle, _ptr(lims), _ptr(ids), _ptr(dist), _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2])))
+        return (lims, ids, dist) + tuple(cnt) if counters else (lims, ids, dist)
+
+    def device_pointers(self):
+        """hnsw_range_result_device -> the device addresses (lims, ids, distances) as integers, valid until release"""
+        p = [_C.c_void_p() for _ in range(3)]
+        _check(load().hnsw_range_result_device(self.handle, _C.byref(p[0]), _C.byref(p[1]), _C.byref(p[2])))
+        return tuple(x.value or 0 for x in p)
+
+    def release(self):
+        if self._r is not None:
+            load().hnsw_range_result_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _range_search(hgraph, batch, radius, ef, sem=0, counters=False, keep=False):
+    """hnsw_range_search_batch (ef None: hnsw_range_brute_force_batch) -> what RangeResult.fetch gives; keep: the RangeResult"""
+    Q, qs, nq = _batch(hgraph.d, batch)
+    r = _C.c_void_p()
+    if ef is None:
+        _check(load().hnsw_range_brute_force_batch(hgraph.handle, _ptr(Q), nq, qs, float(radius), _C.byref(r)))
+    else:
+        p = _RangeParams(float(radius), int(ef), sem)
+        _check(load().hnsw_range_search_batch(hgraph.handle, _ptr(Q), nq, qs, _C.byref(p), _C.byref(r)))
+    res = RangeResult(r)
+    if keep:
+        return res
+    try:
+        return res.fetch(counters)
+    finally:
+        res.release()
+
+
 def _search(hgraph, batch, ef, k, fill, counters=False, sem=0, out=None):
     Q, qs, nq = _batch(hgraph.d, batch)
     ids, dist = _out_pair(nq, k, out)
@@ -672,6 +747,22 @@ class Ohnsw:
         still short gets the exact scan over the allowed nodes (stage = STAGE_EXACT).  Distances are over the float32 vectors
         whatever rows the index searches; ids -1 / NaN where fewer than k nodes are allowed."""
         return _search_filtered(hgraph, allow, batch, k if ef is None else ef, k, FILL_OHNSW, counters, out=out)
+
+    @staticmethod
+    def range_search(hgraph, radius, batch, ef=64, counters=False, keep=False):
+        """EVERY node within `radius` of each query (hnsw_range_search_batch) -> (lims, ids, distances), with counters (lims, ids,
+        distances, ndist, nhops, stage): query q's segment is ids / distances [lims[q], lims[q + 1]), ascending under (distance,
+        id).  A query is served by the first search of the ladder e = ef, 2 ef, ... 1024 whose W is not saturated (fewer than e
+        members, or the last one out of range): W's in-range prefix; a query saturated at 1024 gets the exact range scan (stage =
+        STAGE_EXACT).  Distances are over the float32 vectors whatever rows the index searches.  keep: the RangeResult itself,
+        left on the device."""
+        return _range_search(hgraph, batch, radius, ef, SEM_OHNSW, counters, keep)
+
+    @staticmethod
+    def brute_force_range(hgraph, radius, batch, counters=False, keep=False):
+        """The exact range search (hnsw_range_brute_force_batch) -> (lims, ids, distances): per query the in-range prefix of the
+        full order (distance, id) over all n vectors.  Needs no graph."""
+        return _range_search(hgraph, batch, radius, None, SEM_OHNSW, counters, keep)
 
     @staticmethod
     def brute_force_knn(hgraph, k, batch, fill=FILL_OHNSW, out=None):
@@ -833,6 +924,12 @@ class Ba:
         """knn_batch among the nodes `allow` names (see Ohnsw.knn_batch_filtered; the functor accept rule, 1-based ids in a
         1-based index, +inf / -1 where fewer than k nodes are allowed) -> (ids, distances), with counters (..., ndist, nhops, stage)."""
         return _search_filtered(hgraph, allow, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR)
+
+    @staticmethod
+    def range_search(hgraph, batch, num_neighbours_search, radius, counters=False):
+        """Ohnsw.range_search under the functor accept rule (1-based ids in a Hnsw.Ba-style index), the ladder starting at
+        ~num_neighbours_search"""
+        return _range_search(hgraph, batch, radius, num_neighbours_search, SEM_FUNCTOR, counters)
 
     @staticmethod
     def search(hgraph, layer, start_nodes, targets, size_nearest):

@@ -211,6 +211,20 @@ struct FilterBufs {
     DevBuf stage;                        // out_stage [nq]
 };
 
+// scratch of hnsw_range_search_batch / hnsw_range_brute_force_batch (hnsw_range.hip), sized on demand by the call; not index tables:
+// not counted in device_bytes.  What a caller keeps (lims, ids, distances, counters) belongs to the hnsw_range_result instead.
+constexpr int RANGE_STAGES = 11;         // the longest ladder: ef = 1, 2, 4, ... 1024
+struct RangeBufs {
+    DevBuf wids[RANGE_STAGES], wdist[RANGE_STAGES];  // every stage's W ([m][e], half / sq8 rows: re-ranked), kept until the fill
+    DevBuf cand, cdist, wnd, wnh, wst, rnd;          // one stage's walk before its re-rank; evaluations, hops, status of its m queries
+    DevBuf list[2], count;                           // the queries still saturated, written by one stage and read by the next; how many
+    DevBuf q;                                        // their vectors, gathered ([m][padded_stride(d)])
+    DevBuf cnt, src, stage, nd, nh;                  // per query: segment length (int64 [nq + 1]), its row of its stage's W, counters
+    DevBuf counts, offs;                             // the exact scan: hits per (query, slab) (uint64 [m][slabs] + 1) and their exclusive sum
+    DevBuf xcnt, xoff;                               // ... segment lengths of the exact-stage queries and where their words start ([m + 1])
+    DevBuf words[2], cub;                            // ... the hits as (key << 32 | row), unsorted and sorted; hipcub's temporary storage
+};
+
 inline int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
     return (s && *s) ? atoi(s) : dflt;
@@ -328,6 +342,7 @@ struct hnsw_index {
     bool sq8_on = false;
     float sq8_lo = 0.0f, sq8_scale = 1.0f;
     hnsw_host::FilterBufs filter_scratch;   // hnsw_search_batch_filtered's stages: ONE such call in flight per handle
+    hnsw_host::RangeBufs range_scratch;     // the range calls' stages and exact scan: ONE such call in flight per handle
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
 };
 
@@ -436,6 +451,8 @@ int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_strid
 // hnsw_scan.hip: the exact scan of b's queries on `st` into b.ids / b.dist (hnsw_brute_force_batch_device, with its checks); mask
 // (optional, ceil(n / 32) device words): only the rows whose bit is set are candidates
 int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *mask = nullptr);
+// hnsw_scan.hip: rows per slab of the exact scan for a launch of `tiles` query tiles (option "scan_slabs" overrides the count)
+int64_t scan_slab_rows(const ::hnsw_index *idx, int64_t tiles, int k);
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
 hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st);
 // hnsw_capi.hip: the handle's stream (hs[0]) and flag word of the host-buffer calls, made on first use

@@ -1,0 +1,666 @@
+// hnsw_range.hip -- range search: every stored vector within distance `radius` of a query (hnsw_range_search_batch,
+// hnsw_range_brute_force_batch, hnsw_range_result_*).  The result has no fixed k: per query a segment of (id, distance) pairs,
+// ascending under the exact scan's order, found through lims [nq + 1].  The search composes pieces that exist already -- the
+// unchanged walk (knn_search with k := ef: W stays on the device), the re-rank kernel (hnsw_rerank.hip) -- with a scan that selects
+// by a distance bound instead of by rank:
+//   ladder   e = ef, 2 ef, ... 1024: a query is served at the first e whose W is not saturated (the walk ran out of graph, or W's
+//            last member is out of range); its segment is W's in-range prefix.  Only the queries still saturated are walked again,
+//            gathered into one compact batch;
+//   exact    a query saturated at e = 1024, and every query of the brute-force form, gets the exact range scan.
+//
+// Kernels.
+//   hnsw_range_scan_kernel<NCH, METRIC, PASS>  the exact scan's grid, roles and arithmetic (hnsw_scan.hip: query tiles x groups of
+//                           row slabs, one wave per (tile, slab), scan_tile / scan_rows, the lane grid, the fmaf chain, reduce16,
+//                           dist_to_key: the bits of hnsw_distance_batch) without any selection state.  A row is a hit iff
+//                           key_to_dist(key) <= radius; keys are monotone in distance, so that is lo <= key <= hi for two keys the
+//                           wave finds first (range_key_bounds).  PASS 0 counts the hits per (query, slab); PASS 1 runs the same
+//                           loop and writes the word (key << 32 | row) of each hit at the (query, slab)'s offset plus the hit's
+//                           position among the slab's hits in id order (ballot, prefix count): the layout is deterministic.
+//   range_count_kernel      per exact-stage query the sum of its slabs' counts (from the exclusive sum), its counters and stage.
+//   range_unpack_kernel     the sorted words of an exact-stage query as ids (+ id_base) and key_to_dist.
+//   range_select_kernel     one wave per walked query: |W| and the length of W's in-range prefix, 64 entries per pass (ballot).
+//                           Served: its count, stage and row.  Saturated: appended to the short list through one atomic counter
+//                           (the host sorts the list, as filtered search does).
+//   range_gather_kernel     the saturated queries' vectors as one compact, zero-padded matrix (filter_gather_kernel's job).
+//   range_fill_kernel       the served queries' prefixes from their stages' W to lims[q], once every size is known.
+// Between the scan's passes: an exclusive sum of the counts (hipcub::DeviceScan), the grand total read on the host, the result
+// allocated.  After the fill hipcub::DeviceSegmentedRadixSort orders each exact-stage segment by its 64-bit words: ascending words
+// = the total order (distance key, node id), no drops however many ties.  Vector stores only.  All scratch is the handle's
+// (RangeBufs): one range call in flight per handle; lims, ids, distances and counters belong to the hnsw_range_result.
+#include "hnsw_internal.h"
+
+#include <hipcub/hipcub.hpp>
+
+namespace hnsw_dev {
+
+// ---- the exact scan's shape, restated (hnsw_scan.hip keeps its own: that file stays the code it was) ------------------------------
+constexpr int RANGE_WAVES = 4;         // = SCAN_WAVES: waves per workgroup, one slab each
+// = scan_tile: queries per tile (T * NCH * 4 VGPRs hold them for NCH <= 4; through LDS the tile costs T * NCH * 256 bytes)
+__host__ __device__ constexpr int range_scan_tile(int nch) { return nch <= 2 ? 8 : nch == 4 ? 4 : 8; }
+// = scan_rows: batches of four rows in flight per wave (UB * NCH * 4 VGPRs)
+__host__ __device__ constexpr int range_scan_rows(int nch) { return nch == 1 ? 4 : nch <= 4 ? 2 : 1; }
+// = scan_min_waves: waves per SIMD the register allocator must leave room for
+__host__ __device__ constexpr int range_min_waves(int nch) { return nch == 1 || nch == 8 ? 4 : nch == 16 ? 2 : 3; }
+
+struct RangeScanArgs {
+    const float *Q;            // the queries of this launch
+    int64_t q_stride, nq;
+    int32_t n_slabs;
+    int64_t slab_rows;         // slab s = rows [s * slab_rows, min(n, (s + 1) * slab_rows))
+    float radius;
+    uint64_t *counts;          // PASS 0: [nq][n_slabs] hits
+    const uint64_t *offs;      // PASS 1: [nq * n_slabs + 1] the exclusive sum of counts
+    const int64_t *xoff;       // PASS 1: [nq] where query i's words start ...
+    uint64_t *words;           // ... in here
+};
+
+// The keys [lo, hi] whose distance is <= radius (hi < lo: none).  key_to_dist is monotone over the keys of real distances -- [0,
+// +inf] for L2, [-inf, +inf] for the inner product; the keys outside are NaNs, never in range -- so the hits are an interval, found
+// with the comparison the definition names: 32 steps of uniform work per wave instead of a square root per evaluation.
+template <int METRIC> __device__ __forceinline__ void range_key_bounds(float radius, uint32_t &lo, uint32_t &hi) {
+    const uint32_t first = METRIC == 0 ? 0u : 0x007FFFFFu, last = METRIC == 0 ? 0x7F800000u : 0xFF800000u;
+    lo = first;
+    if (!(key_to_dist<METRIC>(first) <= radius)) { lo = 1u; hi = 0u; return; }
+    uint32_t a = first, b = last;              // a is in range; the answer lies in [a, b]
+    while (a < b) {
+        const uint32_t mid = a + ((b - a) >> 1) + 1u;
+        if (key_to_dist<METRIC>(mid) <= radius) a = mid; else b = mid - 1u;
+    }
+    hi = a;
+}
+
+template <int NCH, int METRIC, int PASS>
+__global__ void __launch_bounds__(64 * RANGE_WAVES, range_min_waves(NCH))
+hnsw_range_scan_kernel(const IndexView iv, const RangeScanArgs a) {
+    constexpr int T = range_scan_tile(NCH), UB = range_scan_rows(NCH);
+    constexpr bool QLDS = NCH >= 8;
+    __shared__ float4 qs[QLDS ? T * 16 * NCH : 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane >> 4, l16 = lane & 15;
+    const int64_t q0 = (int64_t)blockIdx.x * T;
+    const int tq = (int)(a.nq - q0 < T ? a.nq - q0 : T);       // queries of this tile (>= 1: the grid has no empty tile)
+
+    float4 qv[QLDS ? 1 : T][QLDS ? 1 : NCH];
+    if constexpr (QLDS) {       // the workgroup loads the tile once, zero beyond d and beyond the tile's last query
+        for (int c = threadIdx.x; c < T * 16 * NCH; c += 64 * RANGE_WAVES) {
+            const int t = c / (16 * NCH), e0 = 4 * (c % (16 * NCH));
+            const float *qp = a.Q + (q0 + (t < tq ? t : 0)) * a.q_stride;
+            float4 v;
+            v.x = (t < tq && e0 + 0 < iv.d) ? qp[e0 + 0] : 0.f; v.y = (t < tq && e0 + 1 < iv.d) ? qp[e0 + 1] : 0.f;
+            v.z = (t < tq && e0 + 2 < iv.d) ? qp[e0 + 2] : 0.f; v.w = (t < tq && e0 + 3 < iv.d) ? qp[e0 + 3] : 0.f;
+            qs[c] = v;
+        }
+        __syncthreads();
+    } else {
+#pragma unroll
+        for (int t = 0; t < T; ++t) load_query<NCH>(qv[t], a.Q + (q0 + (t < tq ? t : 0)) * a.q_stride, iv.d, l16);
+    }
+    const int64_t slab = (int64_t)blockIdx.y * RANGE_WAVES + wave;
+    if (slab >= a.n_slabs) return;                  // (after the only workgroup barrier)
+    const int64_t r0 = slab * a.slab_rows, r1 = r0 + a.slab_rows < iv.n ? r0 + a.slab_rows : iv.n;
+    uint32_t klo, khi;
+    range_key_bounds<METRIC>(a.radius, klo, khi);
+    klo = (uint32_t)uniform((int)klo); khi = (uint32_t)uniform((int)khi);
+
+    // per query of the tile: its hits so far in this slab (wave-uniform); PASS 1: where its words go and how many PASS 0 counted
+    int cnt[T];
+    uint64_t *dst[T];
+    int lim[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        cnt[t] = 0;
+        dst[t] = nullptr;
+        lim[t] = 0;
+        if (PASS == 1 && t < tq) {
+            const int64_t at = (q0 + t) * a.n_slabs;
+            dst[t] = a.words + a.xoff[q0 + t] + (int64_t)(a.offs[at + slab] - a.offs[at]);
+            lim[t] = (int)(a.offs[at + slab + 1] - a.offs[at + slab]);
+        }
+    }
+
+    const uint32_t stride_b = (uint32_t)iv.stride * 4u;
+    for (int64_t base = r0; base < r1; base += 4 * UB) {
+        float4 v[UB][NCH];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {              // past the slab's end: its last row again, dropped below
+            const int64_t row = base + 4 * u + r;
+            const char *rp = reinterpret_cast<const char *>(iv.X) + (uint64_t)(row < r1 ? row : r1 - 1) * stride_b;
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const int c = i * 16 + l16;
+                v[u][i] = *reinterpret_cast<const float4 *>(rp + 16u * (uint32_t)(c < iv.nchunks ? c : 0));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {         // lanes past the row end add exactly 0 (their query chunk is 0)
+                const bool cv = (i * 16 + l16) < iv.nchunks;
+                v[u][i].x = cv ? v[u][i].x : 0.f; v[u][i].y = cv ? v[u][i].y : 0.f;
+                v[u][i].z = cv ? v[u][i].z : 0.f; v[u][i].w = cv ? v[u][i].w : 0.f;
+            }
+            const int64_t row = base + 4 * u + r;
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                // (the tile in LDS is read here, every time: left alone the compiler hoists T * NCH float4 reads out of the loops)
+                if constexpr (QLDS) asm volatile("" ::: "memory");
+                float acc = 0.f;
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) {
+                    const float4 z = v[u][i];
+                    const float4 qi = QLDS ? qs[(t * NCH + i) * 16 + l16] : qv[QLDS ? 0 : t][QLDS ? 0 : i];
+                    if (METRIC == 0) {
+                        float dx = z.x - qi.x; acc = __builtin_fmaf(dx, dx, acc);
+                        float dy = z.y - qi.y; acc = __builtin_fmaf(dy, dy, acc);
+                        float dz = z.z - qi.z; acc = __builtin_fmaf(dz, dz, acc);
+                        float dw = z.w - qi.w; acc = __builtin_fmaf(dw, dw, acc);
+                    } else {
+                        acc = __builtin_fmaf(z.x, qi.x, acc);
+                        acc = __builtin_fmaf(z.y, qi.y, acc);
+                        acc = __builtin_fmaf(z.z, qi.z, acc);
+                        acc = __builtin_fmaf(z.w, qi.w, acc);
+                    }
+                }
+                acc = reduce16(acc);
+                const uint32_t key = dist_to_key<METRIC>(acc);
+                // a query past the tile's end has no hits; the rows of a batch lie in lane order: r ascending = id ascending
+                const bool hit = l16 == 0 && row < r1 && t < tq && key >= klo && key <= khi;
+                const uint64_t m = ballot(hit);
+                if (m) {
+                    if (PASS == 1) {
+                        const int pos = cnt[t] + popc(m & ((1ull << lane) - 1ull));
+                        if (hit && pos < lim[t]) dst[t][pos] = ((uint64_t)key << 32) | (uint32_t)row;
+                    }
+                    cnt[t] += popc(m);
+                }
+            }
+        }
+    }
+    if (PASS == 0 && lane == 0) {
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+            if (t < tq) a.counts[(q0 + t) * a.n_slabs + slab] = (uint64_t)cnt[t];
+    }
+}
+
+struct RangeCountArgs {
+    const uint64_t *offs;      // [m * n_slabs + 1]
+    int64_t m;
+    int32_t n_slabs;
+    const int32_t *map;        // [m] row i belongs to query map[i]; null: to query i
+    uint32_t n;                // the rows scanned
+    int32_t fresh;             // 1: the query took no walk: out_nd starts from 0 and out_nh is 0
+    int64_t *cnt, *xcnt;       // [nq] by query, [m] by row
+    uint32_t *out_nd, *out_nh, *out_stage;
+};
+
+__global__ void __launch_bounds__(256)
+range_count_kernel(const RangeCountArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.m) return;
+    const int64_t q = a.map ? a.map[i] : i;
+    const int64_t c = (int64_t)(a.offs[(i + 1) * a.n_slabs] - a.offs[i * a.n_slabs]);
+    a.cnt[q] = c;
+    a.xcnt[i] = c;
+    a.out_nd[q] = (a.fresh ? 0u : a.out_nd[q]) + a.n;
+    if (a.fresh) a.out_nh[q] = 0u;
+    a.out_stage[q] = 0xFFFFFFFFu;
+}
+
+// one wave per exact-stage query: sorted words -> ids and distances at lims[q]
+template <int METRIC>
+__global__ void __launch_bounds__(64)
+range_unpack_kernel(const uint64_t *words, const int64_t *xoff, int64_t m, const int32_t *map, const int64_t *lims, int32_t id_base,
+                    int32_t *ids, float *dist) {
+    const int64_t i = blockIdx.x;
+    if (i >= m) return;
+    const int64_t q = map ? map[i] : i;
+    const int64_t from = xoff[i], c = xoff[i + 1] - from, to = lims[q];
+    for (int64_t j = threadIdx.x; j < c; j += 64) {
+        const uint64_t e = words[from + j];
+        ids[to + j] = (int32_t)(uint32_t)e + id_base;
+        dist[to + j] = key_to_dist<METRIC>((uint32_t)(e >> 32));
+    }
+}
+
+struct RangeSelectArgs {
+    const int32_t *wids;       // [m][e] the stage's W per query, id_base-based, ascending, filled entries < id_base
+    const float *wdist;        // [m][e]
+    const uint32_t *wnd, *wnh; // [m] evaluations (the re-rank's included) and hops
+    int64_t m;
+    int32_t e;
+    const int32_t *map;        // [m] row i belongs to query map[i]; null: to query i
+    float radius;
+    int32_t id_base;
+    uint32_t stage;            // what a served query's out_stage becomes
+    int32_t accumulate;        // out_nd / out_nh: 0 = set (the first walk), 1 = add
+    int64_t *cnt;              // [nq] a served query's segment length
+    int32_t *src;              // [nq] ... and its row of this stage's W
+    uint32_t *out_nd, *out_nh, *out_stage;   // [nq]
+    int32_t *short_list;       // the queries (map's numbering) that are saturated ...
+    uint32_t *short_count;     // ... and how many
+};
+
+__global__ void __launch_bounds__(64)
+range_select_kernel(const RangeSelectArgs a) {
+    const int lane = threadIdx.x;
+    const int64_t i = blockIdx.x;
+    if (i >= a.m) return;
+    const int64_t q = a.map ? a.map[i] : i;
+    int in = 0;                // W is ascending: its members in range are a prefix
+    for (int j0 = 0; j0 < a.e; j0 += 64) {
+        const int j = j0 + lane;
+        in += popc(ballot(j < a.e && a.wids[i * a.e + j] >= a.id_base && a.wdist[i * a.e + j] <= a.radius));
+    }
+    // saturated: |W| = e and its last member is in range, that is all e entries are
+    if (lane == 0) {
+        a.out_nd[q] = (a.accumulate ? a.out_nd[q] : 0u) + a.wnd[i];
+        a.out_nh[q] = (a.accumulate ? a.out_nh[q] : 0u) + a.wnh[i];
+        if (in < a.e) {
+            a.cnt[q] = in;
+            a.src[q] = (int32_t)i;
+            a.out_stage[q] = a.stage;
+        } else {
+            a.short_list[atomicAdd(a.short_count, 1u)] = (int32_t)q;     // (at most m entries: one per block)
+        }
+    }
+}
+
+// out[i] = Q[list[i]], rows of out_stride floats, zero beyond d
+__global__ void __launch_bounds__(64)
+range_gather_kernel(const float *Q, int64_t q_stride, int32_t d, const int32_t *list, int64_t m, float *out, int64_t out_stride) {
+    const int64_t i = blockIdx.x;
+    if (i >= m) return;
+    const float *qp = Q + (int64_t)list[i] * q_stride;
+    for (int64_t c = threadIdx.x; c < out_stride; c += 64) out[i * out_stride + c] = c < d ? qp[c] : 0.f;
+}
+
+struct RangeFillArgs {
+    const int32_t *wids[hnsw_host::RANGE_STAGES];    // per stage its W ...
+    const float *wdist[hnsw_host::RANGE_STAGES];
+    int32_t e[hnsw_host::RANGE_STAGES];              // ... and its row length
+    int32_t n_stages;
+    int64_t nq;
+    const uint32_t *stage;     // [nq]
+    const int32_t *src;        // [nq]
+    const int64_t *lims;       // [nq + 1]
+    int32_t *ids;
+    float *dist;
+};
+
+__global__ void __launch_bounds__(64)
+range_fill_kernel(const RangeFillArgs a) {
+    const int64_t q = blockIdx.x;
+    if (q >= a.nq) return;
+    const uint32_t s = a.stage[q];
+    if (s >= (uint32_t)a.n_stages) return;          // the exact stage writes its own
+    const int64_t to = a.lims[q], c = a.lims[q + 1] - to, from = (int64_t)a.src[q] * a.e[s];
+    for (int64_t j = threadIdx.x; j < c; j += 64) {
+        a.ids[to + j] = a.wids[s][from + j];
+        a.dist[to + j] = a.wdist[s][from + j];
+    }
+}
+
+} // namespace hnsw_dev
+
+using hnsw_dev::IndexView;
+using namespace hnsw_host;
+
+// what a range call returns: lims, ids, distances and the per-query counters on the device of the index they came from
+struct hnsw_range_result {
+    int device = -1;
+    int64_t nq = 0, total = 0;
+    DevBuf lims, ids, dist, nd, nh, stage;
+};
+
+namespace {
+
+int launched(const char *what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? HNSW_OK : fail(HNSW_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+}
+
+int synced(hipStream_t st, const char *what) {
+    const hipError_t e = hipStreamSynchronize(st);
+    return e == hipSuccess ? HNSW_OK : fail(HNSW_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
+
+// out[0 .. count) = the exclusive sum of in[0 .. count) on st (count >= 1), through the handle's temporary storage
+template <class T, class U>
+int exclusive_sum(RangeBufs &rb, const T *in, U *out, int64_t count, hipStream_t st) {
+    if (count > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "%lld counts to sum: too many for one range call", (long long)count);
+    size_t bytes = 0;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)count, st) != hipSuccess) return fail(HNSW_ERR_HIP, "scan sizing failed");
+    int rc;
+    if ((rc = rb.cub.ensure(std::max<size_t>(bytes, 16)))) return rc;
+    bytes = rb.cub.bytes;
+    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(rb.cub.p, bytes, in, out, (int)count, st);
+    return e == hipSuccess ? HNSW_OK : fail(HNSW_ERR_HIP, "exclusive sum failed: %s", hipGetErrorString(e));
+}
+
+// The queries of the exact stage -- (Q, map): m rows, row i belonging to query map[i] (null: to query i) -- and how they are cut.
+// A piece's counts and offsets fit SCAN_SCRATCH bytes of the handle's scratch, as the k-scan's lists do.
+struct ExactPlan {
+    const float *Q = nullptr;
+    int64_t m = 0, q_stride = 0;
+    const int32_t *map = nullptr;
+    int nch = 0, T = 0;
+    int64_t piece = 0, slab_rows = 0, slabs = 0;
+};
+
+void plan_exact(const hnsw_index *idx, ExactPlan &x) {
+    constexpr int64_t SCAN_SCRATCH = 256ll << 20;
+    x.nch = pick_nch(idx->iv.nchunks);
+    x.T = hnsw_dev::range_scan_tile(x.nch);
+    x.piece = x.m;
+    for (;;) {      // (a smaller piece has fewer tiles and may be cut into more slabs: settle on a piece that fits)
+        x.slab_rows = scan_slab_rows(idx, (x.piece + x.T - 1) / x.T, 1);
+        x.slabs = idx->iv.n > 0 ? (idx->iv.n + x.slab_rows - 1) / x.slab_rows : 0;
+        const int64_t per_query = std::max<int64_t>(x.slabs, 1) * 16;
+        if (x.piece * per_query <= SCAN_SCRATCH || x.piece <= x.T) break;
+        x.piece = std::max<int64_t>(x.T, SCAN_SCRATCH / per_query / x.T * x.T);
+    }
+}
+
+hipError_t launch_range_scan(const hnsw_index *idx, const ExactPlan &x, int pass, int64_t nq, const hnsw_dev::RangeScanArgs &a, hipStream_t st) {
+    const dim3 grid((unsigned)((nq + x.T - 1) / x.T), (unsigned)((x.slabs + hnsw_dev::RANGE_WAVES - 1) / hnsw_dev::RANGE_WAVES));
+    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(x.nch, [&](auto NCH) {
+        if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 0>), grid, dim3(64 * hnsw_dev::RANGE_WAVES), 0, st, idx->iv, a);
+        else hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 1>), grid, dim3(64 * hnsw_dev::RANGE_WAVES), 0, st, idx->iv, a);
+    }); });
+    return hipGetLastError();
+}
+
+// PASS 0 for the rows [i0, i0 + mp) of x and the exclusive sum of its counts (rb.offs: [mp * slabs + 1])
+int exact_count_piece(hnsw_index *idx, const ExactPlan &x, float radius, int64_t i0, int64_t mp, hipStream_t st) {
+    RangeBufs &rb = idx->range_scratch;
+    const int64_t cells = mp * x.slabs;
+    hnsw_dev::RangeScanArgs a{x.Q + i0 * x.q_stride, x.q_stride, mp, (int32_t)x.slabs, x.slab_rows, radius, (uint64_t *)rb.counts.p, nullptr, nullptr, nullptr};
+    HIP_TRY(hipMemsetAsync((uint64_t *)rb.counts.p + cells, 0, 8, st));       // (the sum's last entry is the piece's total)
+    const hipError_t e = launch_range_scan(idx, x, 0, mp, a, st);
+    if (e != hipSuccess) return fail(HNSW_ERR_HIP, "range scan kernel launch failed: %s", hipGetErrorString(e));
+    return exclusive_sum(rb, (const uint64_t *)rb.counts.p, (uint64_t *)rb.offs.p, cells + 1, st);
+}
+
+// The sizes of the exact stage's segments: cnt[q] and xcnt[i] for every row of x, the queries' counters and stage
+int exact_count(hnsw_index *idx, const ExactPlan &x, float radius, bool fresh, hipStream_t st) {
+    RangeBufs &rb = idx->range_scratch;
+    int rc;
+    if ((rc = rb.xcnt.ensure((size_t)(x.m + 1) * 8)) || (rc = rb.xoff.ensure((size_t)(x.m + 1) * 8))) return rc;
+    if (x.slabs == 0) {         // no rows: every segment is empty (a sum of one zero stands for the offsets)
+        if ((rc = rb.offs.ensure(16))) return rc;
+        HIP_TRY(hipMemsetAsync(rb.offs.p, 0, 16, st));
+        const hnsw_dev::RangeCountArgs ca{(const uint64_t *)rb.offs.p, x.m, 0, x.map, 0u, fresh, (int64_t *)rb.cnt.p, (int64_t *)rb.xcnt.p,
+                                          (uint32_t *)rb.nd.p, (uint32_t *)rb.nh.p, (uint32_t *)rb.stage.p};
+        hipLaunchKernelGGL(hnsw_dev::range_count_kernel, dim3((unsigned)((x.m + 255) / 256)), dim3(256), 0, st, ca);
+        return launched("range count kernel");
+    }
+    if ((rc = rb.counts.ensure((size_t)(x.piece * x.slabs + 1) * 8)) || (rc = rb.offs.ensure((size_t)(x.piece * x.slabs + 1) * 8))) return rc;
+    for (int64_t i0 = 0; i0 < x.m; i0 += x.piece) {
+        const int64_t mp = std::min(x.piece, x.m - i0);
+        if ((rc = exact_count_piece(idx, x, radius, i0, mp, st))) return rc;
+        const hnsw_dev::RangeCountArgs ca{(const uint64_t *)rb.offs.p, mp, (int32_t)x.slabs, x.map ? x.map + i0 : nullptr, (uint32_t)idx->iv.n, fresh,
+                                          x.map ? (int64_t *)rb.cnt.p : (int64_t *)rb.cnt.p + i0, (int64_t *)rb.xcnt.p + i0,
+                                          x.map ? (uint32_t *)rb.nd.p : (uint32_t *)rb.nd.p + i0, x.map ? (uint32_t *)rb.nh.p : (uint32_t *)rb.nh.p + i0,
+                                          x.map ? (uint32_t *)rb.stage.p : (uint32_t *)rb.stage.p + i0};
+        hipLaunchKernelGGL(hnsw_dev::range_count_kernel, dim3((unsigned)((mp + 255) / 256)), dim3(256), 0, st, ca);
+        if ((rc = launched("range count kernel"))) return rc;
+    }
+    return HNSW_OK;
+}
+
+// PASS 1, the sort and the unpacking for the rows of x, whose sizes exact_count found: ids and distances at r's lims
+int exact_fill(hnsw_index *idx, const ExactPlan &x, float radius, hnsw_range_result *r, hipStream_t st) {
+    RangeBufs &rb = idx->range_scratch;
+    int rc;
+    HIP_TRY(hipMemsetAsync((int64_t *)rb.xcnt.p + x.m, 0, 8, st));
+    if ((rc = exclusive_sum(rb, (const int64_t *)rb.xcnt.p, (int64_t *)rb.xoff.p, x.m + 1, st))) return rc;
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, (const int64_t *)rb.xoff.p + x.m, 8, hipMemcpyDeviceToHost, st));
+    if ((rc = synced(st, "range scan"))) return rc;
+    if (total == 0) return HNSW_OK;     // (at most r->total: within int)
+    if ((rc = rb.words[0].ensure((size_t)total * 8)) || (rc = rb.words[1].ensure((size_t)total * 8))) return rc;
+    for (int64_t i0 = 0; i0 < x.m; i0 += x.piece) {
+        const int64_t mp = std::min(x.piece, x.m - i0);
+        // (one piece: its offsets are still in place)
+        if (x.piece < x.m && (rc = exact_count_piece(idx, x, radius, i0, mp, st))) return rc;
+        const hnsw_dev::RangeScanArgs a{x.Q + i0 * x.q_stride, x.q_stride, mp, (int32_t)x.slabs, x.slab_rows, radius, nullptr,
+                                        (const uint64_t *)rb.offs.p, (const int64_t *)rb.xoff.p + i0, (uint64_t *)rb.words[0].p};
+        const hipError_t e = launch_range_scan(idx, x, 1, mp, a, st);
+        if (e != hipSuccess) return fail(HNSW_ERR_HIP, "range scan kernel launch failed: %s", hipGetErrorString(e));
+    }
+    // each segment by its words: (distance key, node id) ascending
+    size_t bytes = 0;
+    const int64_t *xo = (const int64_t *)rb.xoff.p;
+    if (hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)total, (int)x.m, xo, xo + 1, 0, 64,
+                                                   st) != hipSuccess)
+        return fail(HNSW_ERR_HIP, "segmented sort sizing failed");
+    if ((rc = rb.cub.ensure(std::max<size_t>(bytes, 16)))) return rc;
+    bytes = rb.cub.bytes;
+    const hipError_t e = hipcub::DeviceSegmentedRadixSort::SortKeys(rb.cub.p, bytes, (const uint64_t *)rb.words[0].p, (uint64_t *)rb.words[1].p, (int)total,
+                                                                    (int)x.m, xo, xo + 1, 0, 64, st);
+    if (e != hipSuccess) return fail(HNSW_ERR_HIP, "segmented sort failed: %s", hipGetErrorString(e));
+    with_metric(idx->info.metric, [&](auto METRIC) {
+        hipLaunchKernelGGL(hnsw_dev::range_unpack_kernel<METRIC>, dim3((unsigned)x.m), dim3(64), 0, st, (const uint64_t *)rb.words[1].p, xo, x.m, x.map,
+                           (const int64_t *)r->lims.p, idx->iv.id_base, (int32_t *)r->ids.p, (float *)r->dist.p);
+    });
+    return launched("range unpack kernel");
+}
+
+// The ladder for the batch (Q, nq, q_stride) on st: cnt / src / stage / nd / nh of the served queries in the handle's scratch,
+// the saturated ones left in x (gathered); e_of: the row length of each stage walked.  d_stage: see knn_search.
+int range_ladder(hnsw_index *idx, const hnsw_range_params &p, const float *Q, int64_t nq, int64_t q_stride, float *d_stage, hipStream_t st,
+                 ExactPlan &x, std::vector<int32_t> &e_of) {
+    RangeBufs &rb = idx->range_scratch;
+    const IndexView &iv = idx->iv;
+    const bool rerank = idx->info.row_format == HNSW_ROWS_HALF || idx->info.row_format == HNSW_ROWS_SQ8;
+    const int64_t pad = padded_stride(iv.d);
+    int rc;
+    if ((rc = rb.list[0].ensure((size_t)nq * 4)) || (rc = rb.list[1].ensure((size_t)nq * 4)) || (rc = rb.count.ensure(16))) return rc;
+
+    // the batch of the current stage: at first the caller's, later the saturated queries of the stage before (rb.q, rb.list[cur])
+    int64_t m = nq;
+    const float *Qj = Q;
+    int64_t qs = q_stride;
+    const int32_t *map = nullptr;
+    int cur = 0;                 // which list buffer `map` is
+    std::vector<int32_t> shorts;
+    x.m = 0;
+    for (int e = p.ef, stage = 0;; ++stage) {
+        DevBuf &Wi = rb.wids[stage], &Wd = rb.wdist[stage];
+        if ((rc = Wi.ensure((size_t)m * e * 4)) || (rc = Wd.ensure((size_t)m * e * 4)) || (rc = rb.wnd.ensure((size_t)m * 4)) ||
+            (rc = rb.wnh.ensure((size_t)m * 4)) || (rc = rb.wst.ensure((size_t)m * 4)) ||
+            (rerank && ((rc = rb.cand.ensure((size_t)m * e * 4)) || (rc = rb.cdist.ensure((size_t)m * e * 4)) || (rc = rb.rnd.ensure((size_t)m * 4)))))
+            return rc;
+        e_of.push_back(e);
+        // W_e: the host form's search of (ef = e, k = e), its tie-overflow repair included, without a re-rank
+        const hnsw_search_params wp{e, e, HNSW_FILL_OHNSW, p.semantics};
+        const KnnBatch wb{Qj, m, qs, (int32_t *)(rerank ? rb.cand.p : Wi.p), (float *)(rerank ? rb.cdist.p : Wd.p), (uint32_t *)rb.wnd.p,
+                          (uint32_t *)rb.wnh.p, (uint32_t *)rb.wst.p, idx->hFlagDev};
+        *(volatile uint32_t *)idx->hFlag = 0;
+        if ((rc = knn_search(idx, &wp, wb, st, stage == 0 ? d_stage : nullptr, nullptr, true))) return rc;
+        if ((rc = synced(st, "range search"))) return rc;
+        if ((*(volatile uint32_t *)idx->hFlag & 1u) && (rc = knn_repair(idx, &wp, wb, st, nullptr, true))) return rc;
+        // half / sq8 rows: all members of W over the float32 rows, k := e
+        if (rerank && (rc = launch_rerank(idx, Qj, m, qs, wb.ids, e, e, HNSW_FILL_OHNSW, (int32_t *)Wi.p, (float *)Wd.p, wb.nd, (uint32_t *)rb.rnd.p, st)))
+            return rc;
+
+        HIP_TRY(hipMemsetAsync(rb.count.p, 0, 4, st));
+        const hnsw_dev::RangeSelectArgs sa{(const int32_t *)Wi.p, (const float *)Wd.p, (const uint32_t *)(rerank ? rb.rnd.p : rb.wnd.p), wb.nh, m, e, map,
+                                           p.radius, iv.id_base, (uint32_t)stage, stage > 0, (int64_t *)rb.cnt.p, (int32_t *)rb.src.p,
+                                           (uint32_t *)rb.nd.p, (uint32_t *)rb.nh.p, (uint32_t *)rb.stage.p, (int32_t *)rb.list[cur ^ 1].p,
+                                           (uint32_t *)rb.count.p};
+        hipLaunchKernelGGL(hnsw_dev::range_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
+        if ((rc = launched("range select kernel"))) { (void)hipStreamSynchronize(st); return rc; }
+        uint32_t n_short = 0;
+        HIP_TRY(hipMemcpyAsync(&n_short, rb.count.p, 4, hipMemcpyDeviceToHost, st));
+        if ((rc = synced(st, "range search"))) return rc;
+        if (n_short == 0) return HNSW_OK;
+        // the saturated queries in ascending order: the next stage's batch
+        shorts.resize(n_short);
+        HIP_TRY(hipMemcpy(shorts.data(), rb.list[cur ^ 1].p, (size_t)n_short * 4, hipMemcpyDeviceToHost));
+        std::sort(shorts.begin(), shorts.end());
+        HIP_TRY(hipMemcpy(rb.list[cur ^ 1].p, shorts.data(), (size_t)n_short * 4, hipMemcpyHostToDevice));
+        cur ^= 1;
+        map = (const int32_t *)rb.list[cur].p;
+        m = n_short;
+        if ((rc = rb.q.ensure((size_t)m * pad * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(hnsw_dev::range_gather_kernel, dim3((unsigned)m), dim3(64), 0, st, Q, q_stride, iv.d, map, m, (float *)rb.q.p, pad);
+        if ((rc = launched("range gather kernel"))) { (void)hipStreamSynchronize(st); return rc; }
+        Qj = (const float *)rb.q.p;
+        qs = pad;
+        if (e >= 1024) break;           // still saturated with the largest W the library walks
+        e = std::min(1024, 2 * e);
+    }
+    x.Q = Qj; x.m = m; x.q_stride = qs; x.map = map;
+    return HNSW_OK;
+}
+
+// Both entry points: p null = the brute-force form (every query is the exact stage's).  *out is set on success only.
+int range_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_range_params *p, float radius, hnsw_range_result **out) {
+    HIP_TRY(hipSetDevice(idx->device));
+    std::unique_ptr<hnsw_range_result> r(new hnsw_range_result());
+    r->device = idx->device;
+    r->nq = nq;
+    int rc;
+    if ((rc = r->lims.ensure((size_t)(nq + 1) * 8))) return rc;
+    if (nq == 0) {
+        HIP_TRY(hipMemset(r->lims.p, 0, 8));
+        *out = r.release();
+        return HNSW_OK;
+    }
+    RangeBufs &rb = idx->range_scratch;
+    if ((rc = rb.cnt.ensure((size_t)(nq + 1) * 8)) || (rc = rb.src.ensure((size_t)nq * 4)) || (rc = rb.stage.ensure((size_t)nq * 4)) ||
+        (rc = rb.nd.ensure((size_t)nq * 4)) || (rc = rb.nh.ensure((size_t)nq * 4)) || (rc = r->nd.ensure((size_t)nq * 4)) ||
+        (rc = r->nh.ensure((size_t)nq * 4)) || (rc = r->stage.ensure((size_t)nq * 4)))
+        return rc;
+    HostCall c;
+    bool q_in_place = false;
+    if ((rc = c.begin(idx, queries, nq, q_stride, 1, nullptr, nullptr, nullptr, nullptr, false, &q_in_place))) return rc;
+    hipStream_t st = idx->hs[0];
+    // from here on work is queued that reads the caller's queries: no return without a synchronisation
+    ExactPlan x;
+    std::vector<int32_t> e_of;
+    if (p) {
+        rc = range_ladder(idx, *p, c.b.Q, nq, q_stride, q_in_place ? (float *)idx->scratch.q.p : nullptr, st, x, e_of);
+    } else {
+        x.Q = c.b.Q; x.m = nq; x.q_stride = q_stride; x.map = nullptr;
+    }
+    if (!rc && x.m > 0) {
+        plan_exact(idx, x);
+        rc = exact_count(idx, x, radius, !p, st);
+    }
+    // every query's size is known: lims, the grand total, the result's buffers
+    int64_t total = 0;
+    if (!rc && hipMemsetAsync((int64_t *)rb.cnt.p + nq, 0, 8, st) != hipSuccess) rc = fail(HNSW_ERR_HIP, "memset failed");
+    if (!rc) rc = exclusive_sum(rb, (const int64_t *)rb.cnt.p, (int64_t *)r->lims.p, nq + 1, st);
+    if (!rc && hipMemcpyAsync(&total, (const int64_t *)r->lims.p + nq, 8, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(HNSW_ERR_HIP, "total download failed");
+    if (!rc) rc = synced(st, "range search");
+    if (!rc && total > 0x7FFFFFFFLL) rc = fail(HNSW_ERR_UNSUPPORTED, "%lld results: more than 2^31 - 1 in one call", (long long)total);
+    if (!rc) {
+        r->total = total;
+        if (!(rc = r->ids.ensure((size_t)std::max<int64_t>(total, 1) * 4))) rc = r->dist.ensure((size_t)std::max<int64_t>(total, 1) * 4);
+    }
+    if (!rc && p && total > 0) {
+        hnsw_dev::RangeFillArgs fa{};
+        fa.n_stages = (int32_t)e_of.size();
+        for (int s = 0; s < fa.n_stages; ++s) {
+            fa.wids[s] = (const int32_t *)rb.wids[s].p; fa.wdist[s] = (const float *)rb.wdist[s].p; fa.e[s] = e_of[(size_t)s];
+        }
+        fa.nq = nq; fa.stage = (const uint32_t *)rb.stage.p; fa.src = (const int32_t *)rb.src.p; fa.lims = (const int64_t *)r->lims.p;
+        fa.ids = (int32_t *)r->ids.p; fa.dist = (float *)r->dist.p;
+        hipLaunchKernelGGL(hnsw_dev::range_fill_kernel, dim3((unsigned)nq), dim3(64), 0, st, fa);
+        rc = launched("range fill kernel");
+    }
+    if (!rc && x.m > 0 && total > 0) rc = exact_fill(idx, x, radius, r.get(), st);
+    if (!rc) {
+        hipError_t e = hipMemcpyAsync(r->nd.p, rb.nd.p, (size_t)nq * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(r->nh.p, rb.nh.p, (size_t)nq * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(r->stage.p, rb.stage.p, (size_t)nq * 4, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) rc = hip_fail(e, "counter copy");
+    }
+    const int rs = synced(st, p ? "range search" : "range scan");
+    if (rc || rs) return rc ? rc : rs;
+    *out = r.release();
+    return HNSW_OK;
+}
+
+int check_range(const hnsw_index *idx, int64_t nq, int64_t q_stride, const float *queries, float radius) {
+    if (std::isnan(radius)) return fail(HNSW_ERR_BAD_ARG, "the radius is NaN");
+    if (nq < 0 || nq > 0x7FFFFFFFLL) return fail(HNSW_ERR_BAD_ARG, "nq=%lld out of range", (long long)nq);
+    if (nq == 0) return HNSW_OK;
+    if (!queries) return fail(HNSW_ERR_BAD_ARG, "null buffer");
+    if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
+    return HNSW_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t hnsw_range_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_range_params *params,
+                                hnsw_range_result **out) {
+    if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
+    *out = nullptr;
+    if (!params) return fail(HNSW_ERR_BAD_ARG, "null params");
+    if (std::isnan(params->radius)) return fail(HNSW_ERR_BAD_ARG, "the radius is NaN");
+    if (!idx) return fail(HNSW_ERR_BAD_ARG, "null index");
+    if (params->ef < 1) return fail(HNSW_ERR_BAD_ARG, "ef must be >= 1 (ef=%d)", params->ef);
+    if (params->ef > 1024) return fail(HNSW_ERR_UNSUPPORTED, "ef=%d > 1024 not supported", params->ef);
+    if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
+        return fail(HNSW_ERR_BAD_ARG, "the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no range meaning");
+    if (params->semantics != HNSW_SEM_OHNSW && params->semantics != HNSW_SEM_FUNCTOR) return fail(HNSW_ERR_BAD_ARG, "bad semantics %d", params->semantics);
+    if (idx->iv.entry_point < 0) return fail(HNSW_ERR_EMPTY_INDEX, "range search: empty hgraph");
+    const int rc = check_range(idx, nq, q_stride, queries, params->radius);
+    if (rc) return rc;
+    return range_call(idx, queries, nq, q_stride, params, params->radius, out);
+}
+
+int32_t hnsw_range_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, float radius, hnsw_range_result **out) {
+    if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
+    *out = nullptr;
+    if (std::isnan(radius)) return fail(HNSW_ERR_BAD_ARG, "the radius is NaN");
+    if (!idx) return fail(HNSW_ERR_BAD_ARG, "null index");
+    const int rc = check_range(idx, nq, q_stride, queries, radius);
+    if (rc) return rc;
+    return range_call(idx, queries, nq, q_stride, nullptr, radius, out);
+}
+
+int32_t hnsw_range_result_size(const hnsw_range_result *r, int64_t *nq, int64_t *total) {
+    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+    if (nq) *nq = r->nq;
+    if (total) *total = r->total;
+    return HNSW_OK;
+}
+
+int32_t hnsw_range_result_fetch(hnsw_range_result *r, int64_t *lims, int32_t *ids, float *dist, uint32_t *out_ndist, uint32_t *out_nhops,
+                                uint32_t *out_stage) {
+    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+    if (!lims && !ids && !dist && !out_ndist && !out_nhops && !out_stage) return HNSW_OK;
+    HIP_TRY(hipSetDevice(r->device));
+    if (lims) HIP_TRY(hipMemcpy(lims, r->lims.p, (size_t)(r->nq + 1) * 8, hipMemcpyDeviceToHost));
+    if (ids && r->total > 0) HIP_TRY(hipMemcpy(ids, r->ids.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
+    if (dist && r->total > 0) HIP_TRY(hipMemcpy(dist, r->dist.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
+    if (r->nq > 0) {
+        if (out_ndist) HIP_TRY(hipMemcpy(out_ndist, r->nd.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+        if (out_nhops) HIP_TRY(hipMemcpy(out_nhops, r->nh.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+        if (out_stage) HIP_TRY(hipMemcpy(out_stage, r->stage.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+    }
+    return HNSW_OK;
+}
+
+int32_t hnsw_range_result_device(hnsw_range_result *r, const int64_t **d_lims, const int32_t **d_ids, const float **d_dist) {
+    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+    if (d_lims) *d_lims = (const int64_t *)r->lims.p;
+    if (d_ids) *d_ids = (const int32_t *)r->ids.p;
+    if (d_dist) *d_dist = (const float *)r->dist.p;
+    return HNSW_OK;
+}
+
+int32_t hnsw_range_result_destroy(hnsw_range_result *r) {
+    if (!r) return HNSW_OK;
+    delete r;
+    return HNSW_OK;
+}
+
+} // extern "C"

@@ -4,6 +4,7 @@
 //   Hnsw::Ohnsw::knn / knn_batch_bigarray / build_batch_bigarray / insert / distance_l2   lib/ohnsw.ml:766-899
 //   Hnsw::Ohnsw::rerank                                                                    (hnsw_rerank_batch; nothing in the reference)
 //   Hnsw::Filter, Hnsw::Ohnsw::knn_filtered                                                (hnsw_filter_*, hnsw_search_batch_filtered)
+//   Hnsw::RangeResult, Hnsw::Ohnsw::range_search / brute_force_range                       (hnsw_range_*)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
@@ -95,6 +96,34 @@ public:
     int64_t count() const { int64_t c = 0; check(hnsw_filter_count(f_, &c)); return c; }   // the allowed nodes
 private:
     hnsw_filter *f_ = nullptr;
+};
+
+// What a range call returns (hnsw_range_result), resident on the device of its index: lims [nq + 1], ids and distances [total];
+// query q's segment is [lims[q], lims[q + 1]), ascending under (distance, id).  Owns its device buffers; any number may be alive.
+class RangeResult {
+public:
+    static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
+    struct Host { std::vector<int64_t> lims; std::vector<int32_t> ids; std::vector<float> dist; std::vector<uint32_t> ndist, nhops, stage; };
+    explicit RangeResult(hnsw_range_result *r) : r_(r) {}
+    RangeResult(const RangeResult &) = delete;
+    RangeResult &operator=(const RangeResult &) = delete;
+    RangeResult(RangeResult &&o) noexcept : r_(o.r_) { o.r_ = nullptr; }
+    ~RangeResult() { if (r_) hnsw_range_result_destroy(r_); }
+    hnsw_range_result *handle() const { return r_; }
+    int64_t nq() const { int64_t a = 0, b = 0; check(hnsw_range_result_size(r_, &a, &b)); return a; }
+    int64_t total() const { int64_t a = 0, b = 0; check(hnsw_range_result_size(r_, &a, &b)); return b; }
+    // everything on the host (hnsw_range_result_fetch)
+    Host fetch() const {
+        const size_t n = (size_t)nq(), t = (size_t)total();
+        Host h{std::vector<int64_t>(n + 1, 0), std::vector<int32_t>(t), std::vector<float>(t), std::vector<uint32_t>(n), std::vector<uint32_t>(n),
+               std::vector<uint32_t>(n)};
+        check(hnsw_range_result_fetch(r_, h.lims.data(), h.ids.data(), h.dist.data(), h.ndist.data(), h.nhops.data(), h.stage.data()));
+        return h;
+    }
+    // borrowed device pointers, valid while this object lives (hnsw_range_result_device)
+    void device(const int64_t **d_lims, const int32_t **d_ids, const float **d_dist) const { check(hnsw_range_result_device(r_, d_lims, d_ids, d_dist)); }
+private:
+    hnsw_range_result *r_ = nullptr;
 };
 
 // The sq8 copy of an index (hnsw_index_set_option(h, "sq8_rows", 1)): x ~ lo + scale * code; codes: [n][d] bytes.  Throws
@@ -233,6 +262,23 @@ inline std::pair<std::vector<int32_t>, std::vector<float>> brute_force_knn(const
     std::vector<float> dist(ids.size());
     check(hnsw_brute_force_batch(g.handle(), batch.data, batch.dim2, batch.dim1, k, HNSW_FILL_OHNSW, ids.data(), dist.data()));
     return {std::move(ids), std::move(dist)};
+}
+
+// EVERY node within `radius` of each query (hnsw_range_search_batch): W grows ef, 2 ef, ... 1024 until it is not saturated (fewer
+// than e members, or the last one out of range) and its in-range prefix is the answer; a query saturated at 1024 gets the exact
+// range scan (stage == RangeResult::exact_stage).  Distances are over the float32 vectors whatever rows the index searches.
+inline RangeResult range_search(const Hgraph &g, float radius, const Mat &batch, int ef = 64, int sem = HNSW_SEM_OHNSW) {
+    hnsw_range_params p{radius, ef, sem};
+    hnsw_range_result *r = nullptr;
+    check(hnsw_range_search_batch(g.handle(), batch.data, batch.dim2, batch.dim1, &p, &r));
+    return RangeResult(r);
+}
+
+// ... its exact form (hnsw_range_brute_force_batch): per query the in-range prefix of the full order over all stored vectors
+inline RangeResult brute_force_range(const Hgraph &g, float radius, const Mat &batch) {
+    hnsw_range_result *r = nullptr;
+    check(hnsw_range_brute_force_batch(g.handle(), batch.data, batch.dim2, batch.dim1, radius, &r));
+    return RangeResult(r);
 }
 
 // knn_batch_bigarray among the nodes a Filter allows (hnsw_search_batch_filtered): W grows ef, 2 ef, ... 1024 until it holds k

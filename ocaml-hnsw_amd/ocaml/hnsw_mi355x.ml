@@ -147,6 +147,31 @@ let hnsw_search_batch_filtered =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_filtered"
     (index @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> ptr int32_t @-> ptr float
      @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+(* range search (see the C header): every node within a radius of the query; the result is an object that owns its device buffers *)
+type range_params
+let range_params : range_params structure typ = structure "hnsw_range_params"
+let r_radius = field range_params "radius" float
+let r_ef = field range_params "ef" int32_t
+let r_semantics = field range_params "semantics" int32_t
+let () = seal range_params
+type range_handle = unit ptr
+let range_handle : range_handle typ = ptr void
+let hnsw_range_search_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_range_search_batch"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> ptr range_params @-> ptr range_handle @-> returning int32_t)
+let hnsw_range_brute_force_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_range_brute_force_batch"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> float @-> ptr range_handle @-> returning int32_t)
+let hnsw_range_result_size =
+  foreign ~from:lib "hnsw_range_result_size" (range_handle @-> ptr int64_t @-> ptr int64_t @-> returning int32_t)
+let hnsw_range_result_fetch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_range_result_fetch"
+    (range_handle @-> ptr int64_t @-> ptr int32_t @-> ptr float @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t
+     @-> returning int32_t)
+let hnsw_range_result_device =
+  foreign ~from:lib "hnsw_range_result_device"
+    (range_handle @-> ptr (ptr int64_t) @-> ptr (ptr int32_t) @-> ptr (ptr float) @-> returning int32_t)
+let hnsw_range_result_destroy = foreign ~from:lib "hnsw_range_result_destroy" (range_handle @-> returning int32_t)
 let hnsw_select_neighbours_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_select_neighbours_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> ptr int32_t @-> int32_t @-> int32_t @-> int32_t
@@ -830,6 +855,41 @@ let knn_batch_filtered ?(semantics = 0) ?(fill = 0) (f : filter) (batch : Lacaml
   (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
    Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
    Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))
+
+(* Range search (hnsw_range_search_batch / hnsw_range_brute_force_batch): EVERY node within [radius] of each query (a column of
+   [batch]).  -> per query its (node id, distance) pairs, ascending under (distance, node id), and its stage: how often W doubled
+   before it was no longer saturated, -1 = the exact range scan.  Distances are over the float32 vectors whatever rows the index
+   searches.  The device-side result is fetched whole and freed before the call returns. *)
+let fetch_range (r : range_handle) : (int * float) array array * int array =
+  Fun.protect ~finally:(fun () -> ignore (hnsw_range_result_destroy r)) (fun () ->
+      let nq = allocate int64_t 0L and total = allocate int64_t 0L in
+      check (hnsw_range_result_size r nq total);
+      let nq = Int64.to_int !@nq and total = Int64.to_int !@total in
+      let lims = CArray.make int64_t (nq + 1) in
+      let ids = CArray.make int32_t (max 1 total) and dist = CArray.make float (max 1 total) in
+      let stage = CArray.make uint32_t (max 1 nq) in
+      check (hnsw_range_result_fetch r (CArray.start lims) (CArray.start ids) (CArray.start dist) (from_voidp uint32_t null)
+               (from_voidp uint32_t null) (CArray.start stage));
+      (Array.init nq (fun q ->
+           let a = Int64.to_int (CArray.get lims q) and b = Int64.to_int (CArray.get lims (q + 1)) in
+           Array.init (b - a) (fun j -> (Int32.to_int (CArray.get ids (a + j)), CArray.get dist (a + j)))),
+       Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s)))
+
+(* ~semantics: 0 Ohnsw's accept rule, 1 the functor's (2 is refused); ~ef: the ladder's first stage, 1..1024 *)
+let range_search ?(semantics = 0) (t : t) (batch : Lacaml.S.mat) ~radius ~ef : (int * float) array array * int array =
+  let nq = A2.dim2 batch in
+  let p = make range_params in
+  setf p r_radius radius; setf p r_ef (Int32.of_int ef); setf p r_semantics (Int32.of_int semantics);
+  let out = allocate range_handle null in
+  check (hnsw_range_search_batch t.handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) (addr p) out);
+  fetch_range !@out
+
+(* the exact form: per query the in-range prefix of the full order over all stored vectors; needs no graph *)
+let brute_force_range (t : t) (batch : Lacaml.S.mat) ~radius : (int * float) array array =
+  let nq = A2.dim2 batch in
+  let out = allocate range_handle null in
+  check (hnsw_range_brute_force_batch t.handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) radius out);
+  fst (fetch_range !@out)
 
 (* brute_force_knn_l2 (benchmark/dataset.ml:15-30) with its body on the device: the distance matrix it returns
    (k x nq: column q = the ascending distances of test vector q's k nearest train vectors), for an index that holds the
