@@ -512,7 +512,8 @@ int32_t hnsw_rerank_batch_device(hnsw_index *idx, const float *d_queries, int64_
  *   6. DETERMINISM.  A query's answer depends on its own vector, the mask and (ef, k, semantics) only: not on the batch it is in,
  *      and not on which stage other queries reached.
  * Scratch (a stage's W, the short list, the gathered queries) belongs to the handle, is sized on demand and not counted in
- * device_bytes: ONE filtered call in flight per handle.  There is no device-pointer form: the ladder needs the number of short
+ * device_bytes: ONE filtered call in flight per handle, and no range call beside it (the short list and the gathered queries are
+ * shared between the filtered and the range calls).  There is no device-pointer form: the ladder needs the number of short
  * queries on the host.  Cost: a mask that allows a fraction s of the nodes leaves about s * e members of W; below s ~ k / 1024 most
  * queries end in the exact stage after walking the whole ladder (no threshold skips it: tools/filter_rate.py prints the rates). */
 typedef struct hnsw_filter hnsw_filter;
@@ -562,7 +563,8 @@ int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const 
  *      on which stage other queries reached.
  * Buffers.  Query matrices of hnsw_host_alloc / hnsw_host_register are read in place, others are staged; complete on return.  Scratch
  * (every stage's W, the saturated list, the gathered queries, the scan's counts, offsets and unsorted hits: 16 bytes per hit of the
- * exact stage) belongs to the handle, is sized on demand and not counted in device_bytes: ONE range call in flight per handle.  The
+ * exact stage) belongs to the handle, is sized on demand and not counted in device_bytes: ONE range call in flight per handle, and no
+ * filtered call beside it (the list and the gathered queries are shared between the range and the filtered calls).  The
  * result's own buffers belong to the result: any number of results may be alive, and a result outlives later calls (destroy it before
  * or after the index, as convenient: it holds no reference to the handle).  There is no device-pointer form: the ladder needs the
  * number of saturated queries, and the result its total, on the host.  A replica of an hnsw_multi may be searched through its handle

@@ -4,6 +4,8 @@
 //   ladder   e = ef, 2 ef, ... 1024: a query is served at the first e whose W holds k allowed nodes; only the queries still short
 //            are walked again, gathered into one compact batch;
 //   exact    a query still short at e = 1024, and every query when fewer than k nodes are allowed, gets the masked exact scan.
+// The ladder itself (Ladder: the walk of a stage, the short list, the gathered batch) is here too; the range search
+// (hnsw_range.hip) runs the same one with its own select rule.
 //
 // Kernels.
 //   filter_popcount_kernel  the uploaded mask: clears the bits past n in its last word and counts the rest.
@@ -11,11 +13,10 @@
 //                           count).  A query with k allowed members is SERVED: its first k allowed (id, distance) pairs go to its
 //                           output row (rows whose walk distances are exact over X: float32, bytes, split), or its W with the
 //                           disallowed entries turned into padding goes to the re-rank's candidate matrix (half, sq8).  Others
-//                           are appended to the short list through one atomic counter (the host sorts the list: the next stage's
-//                           order, and with it nothing a caller can see, depends on who came first).
-//   filter_gather_kernel    the short queries' vectors as one compact, zero-padded matrix: the next walk's / the scan's batch.
+//                           are appended to the short list (ladder_settle).
+//   ladder_gather_kernel    the short queries' vectors as one compact, zero-padded matrix: the next walk's / the exact stage's batch.
 //   filter_scatter_kernel   rows of a compact result (re-rank, scan) to the rows of the queries they belong to.
-// No LDS, vector stores only.  All scratch is the handle's (FilterBufs): one filtered call in flight per handle.
+// No LDS, vector stores only.  All scratch is the handle's (LadderBufs, FilterBufs): one filtered or range call in flight per handle.
 #include "hnsw_internal.h"
 
 namespace hnsw_dev {
@@ -38,22 +39,17 @@ filter_popcount_kernel(uint32_t *bits, int64_t words, int64_t n, unsigned long l
 struct SelectArgs {
     const int32_t *wids;       // [m][e] the walk's W per query, id_base-based, filled entries < id_base
     const float *wdist;        // [m][e]
-    const uint32_t *wnd, *wnh; // [m] the walk's evaluations and hops
     int64_t m;
     int32_t e, k;
     const int32_t *map;        // [m] row i belongs to query map[i]; null: to query i
     const uint32_t *bits;      // the mask
     int64_t n;
     int32_t id_base;
-    uint32_t stage;            // what a served query's out_stage becomes
-    int32_t accumulate;        // out_nd / out_nh: 0 = set (the first walk), 1 = add
     int32_t *out_ids;          // [nq][k]
     float *out_dist;
-    uint32_t *out_nd, *out_nh, *out_stage;   // [nq]
     int32_t *cand;             // null, or [m][e]: the re-rank's candidates instead of out_ids / out_dist
     int32_t *cnt;              // [m] allowed members of W
-    int32_t *short_list;       // the queries (map's numbering) that are not served ...
-    uint32_t *short_count;     // ... and how many
+    LadderOut out;
 };
 
 __device__ __forceinline__ bool filter_allows(const SelectArgs &a, int32_t id) {
@@ -96,16 +92,13 @@ filter_select_kernel(const SelectArgs a) {
     }
     if (lane == 0) {
         a.cnt[i] = cnt;
-        a.out_nd[q] = (a.accumulate ? a.out_nd[q] : 0u) + a.wnd[i];
-        a.out_nh[q] = (a.accumulate ? a.out_nh[q] : 0u) + a.wnh[i];
-        if (served) a.out_stage[q] = a.stage;
-        else a.short_list[atomicAdd(a.short_count, 1u)] = (int32_t)q;     // (at most m entries: one per block)
+        ladder_settle(a.out, i, q, served);
     }
 }
 
 // out[i] = Q[list[i]], rows of out_stride floats, zero beyond d
 __global__ void __launch_bounds__(64)
-filter_gather_kernel(const float *Q, int64_t q_stride, int32_t d, const int32_t *list, int64_t m, float *out, int64_t out_stride) {
+ladder_gather_kernel(const float *Q, int64_t q_stride, int32_t d, const int32_t *list, int64_t m, float *out, int64_t out_stride) {
     const int64_t i = blockIdx.x;
     if (i >= m) return;
     const float *qp = Q + (int64_t)list[i] * q_stride;
@@ -150,102 +143,104 @@ filter_scatter_kernel(const ScatterArgs a) {
 using hnsw_dev::IndexView;
 using namespace hnsw_host;
 
-namespace {
+namespace hnsw_host {
 
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HNSW_OK : fail(HNSW_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+int Ladder::walk(int32_t *wids, float *wdist, int32_t fill) {
+    LadderBufs &lb = idx->ladder_scratch;
+    int rc;
+    if ((rc = lb.wnd.ensure((size_t)m * 4)) || (rc = lb.wnh.ensure((size_t)m * 4)) || (rc = lb.wst.ensure((size_t)m * 4)) ||
+        (rc = lb.list[0].ensure((size_t)nq * 4)) || (rc = lb.list[1].ensure((size_t)nq * 4)) || (rc = lb.count.ensure(16)))
+        return rc;
+    const hnsw_search_params wp{e, e, fill, semantics};
+    wb = KnnBatch{Qj, m, qs, wids, wdist, (uint32_t *)lb.wnd.p, (uint32_t *)lb.wnh.p, (uint32_t *)lb.wst.p, idx->hFlagDev};
+    *(volatile uint32_t *)idx->hFlag = 0;
+    if ((rc = knn_search(idx, &wp, wb, st, stage == 0 ? d_stage : nullptr, nullptr, true))) return rc;
+    if ((rc = synced(st, what))) return rc;
+    if ((*(volatile uint32_t *)idx->hFlag & 1u) && (rc = knn_repair(idx, &wp, wb, st, nullptr, true))) return rc;
+    HIP_TRY(hipMemsetAsync(lb.count.p, 0, 4, st));
+    return HNSW_OK;
 }
 
-// The ladder and the exact stage for a batch HostCall::begin has placed (c.b): everything queued on st and waited for where the
-// host needs a number (the tie-overflow word, the short count); the results are in c.b's rows and fb.stage on return.
+hnsw_dev::LadderOut Ladder::out(const uint32_t *wnd, uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage) const {
+    const LadderBufs &lb = idx->ladder_scratch;
+    return {wnd, wb.nh, (uint32_t)stage, stage > 0, out_nd, out_nh, out_stage, (int32_t *)lb.list[cur ^ 1].p, (uint32_t *)lb.count.p};
+}
+
+int Ladder::count_short() {
+    HIP_TRY(hipMemcpyAsync(&n_short, idx->ladder_scratch.count.p, 4, hipMemcpyDeviceToHost, st));
+    return synced(st, what);
+}
+
+int Ladder::advance(bool &more) {
+    LadderBufs &lb = idx->ladder_scratch;
+    const int64_t pad = padded_stride(idx->iv.d);
+    int rc;
+    shorts.resize(n_short);
+    HIP_TRY(hipMemcpy(shorts.data(), lb.list[cur ^ 1].p, (size_t)n_short * 4, hipMemcpyDeviceToHost));
+    std::sort(shorts.begin(), shorts.end());
+    HIP_TRY(hipMemcpy(lb.list[cur ^ 1].p, shorts.data(), (size_t)n_short * 4, hipMemcpyHostToDevice));
+    cur ^= 1;
+    map = (const int32_t *)lb.list[cur].p;
+    m = n_short;
+    if ((rc = lb.q.ensure((size_t)m * pad * sizeof(float)))) return rc;
+    hipLaunchKernelGGL(hnsw_dev::ladder_gather_kernel, dim3((unsigned)m), dim3(64), 0, st, Q, q_stride, idx->iv.d, map, m, (float *)lb.q.p, pad);
+    if ((rc = launched("ladder gather kernel"))) return rc;
+    Qj = (const float *)lb.q.p;
+    qs = pad;
+    more = e < 1024;                    // else: still short with the largest W the library walks
+    e = std::min(1024, 2 * e);
+    ++stage;
+    return HNSW_OK;
+}
+
+} // namespace hnsw_host
+
+namespace {
+
+// The ladder and the exact stage for a batch HostCall::begin has placed (c.b): the results are in c.b's rows and fb.stage on return.
 int filtered_search(hnsw_index *idx, const hnsw_filter *f, const hnsw_search_params &p, const KnnBatch &b, float *d_stage, hipStream_t st) {
     FilterBufs &fb = idx->filter_scratch;
-    const IndexView &iv = idx->iv;
     const int k = p.k;
-    const bool rerank = idx->info.row_format == HNSW_ROWS_HALF || idx->info.row_format == HNSW_ROWS_SQ8;
-    const int64_t pad = padded_stride(iv.d);
+    const bool rerank = walk_is_inexact(idx);
     int rc;
-    if ((rc = fb.stage.ensure((size_t)b.nq * 4)) || (rc = fb.list[0].ensure((size_t)b.nq * 4)) || (rc = fb.list[1].ensure((size_t)b.nq * 4)) ||
-        (rc = fb.count.ensure(16)) || (rc = fb.rids.ensure((size_t)b.nq * k * 4)) || (rc = fb.rdist.ensure((size_t)b.nq * k * 4)) ||
+    if ((rc = fb.stage.ensure((size_t)b.nq * 4)) || (rc = fb.rids.ensure((size_t)b.nq * k * 4)) || (rc = fb.rdist.ensure((size_t)b.nq * k * 4)) ||
         (rc = fb.rnd.ensure((size_t)b.nq * 4)))
         return rc;
     uint32_t *const d_stage_out = (uint32_t *)fb.stage.p;
-
-    // the batch of the current stage: at first the caller's, later the short queries of the stage before (fb.q, fb.list[cur])
-    int64_t m = b.nq;
-    const float *Qj = b.Q;
-    int64_t qs = b.q_stride;
-    const int32_t *map = nullptr;
-    int cur = 0;                 // which list buffer `map` is
-    bool walked = false;
-    std::vector<int32_t> shorts;
-
-    if (f->n_allowed >= k) {
-        for (int e = p.ef, stage = 0;; ++stage) {
-            if ((rc = fb.wids.ensure((size_t)m * e * 4)) || (rc = fb.wdist.ensure((size_t)m * e * 4)) || (rc = fb.wnd.ensure((size_t)m * 4)) ||
-                (rc = fb.wnh.ensure((size_t)m * 4)) || (rc = fb.wst.ensure((size_t)m * 4)) || (rc = fb.cnt.ensure((size_t)m * 4)) ||
-                (rerank && (rc = fb.cand.ensure((size_t)m * e * 4))))
+    Ladder L(idx, b.Q, b.nq, b.q_stride, p.ef, p.semantics, d_stage, st, "filtered search");
+    const bool walked = f->n_allowed >= k;
+    for (bool more = walked; more;) {
+        const int64_t m = L.m;
+        const int e = L.e;
+        if ((rc = fb.wids.ensure((size_t)m * e * 4)) || (rc = fb.wdist.ensure((size_t)m * e * 4)) || (rc = fb.cnt.ensure((size_t)m * 4)) ||
+            (rerank && (rc = fb.cand.ensure((size_t)m * e * 4))))
+            return rc;
+        if ((rc = L.walk((int32_t *)fb.wids.p, (float *)fb.wdist.p, p.fill))) return rc;
+        const hnsw_dev::SelectArgs sa{L.wb.ids, L.wb.dist, m, e, k, L.map, (const uint32_t *)f->bits.p, f->n, idx->iv.id_base, b.ids, b.dist,
+                                      rerank ? (int32_t *)fb.cand.p : nullptr, (int32_t *)fb.cnt.p, L.out(L.wb.nd, b.nd, b.nh, d_stage_out)};
+        hipLaunchKernelGGL(hnsw_dev::filter_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
+        if ((rc = launched("filter select kernel")) || (rc = L.count_short())) return rc;
+        if (rerank && (int64_t)L.n_short < m) {
+            // the served queries' allowed members over the float32 rows, then their rows to where they belong
+            if ((rc = launch_rerank(idx, L.Qj, m, L.qs, (const int32_t *)fb.cand.p, e, k, p.fill, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr,
+                                    (uint32_t *)fb.rnd.p, st)))
                 return rc;
-            // W_e: the host form's search of (ef = e, k = e), its tie-overflow repair included, without a re-rank
-            const hnsw_search_params wp{e, e, p.fill, p.semantics};
-            const KnnBatch wb{Qj, m, qs, (int32_t *)fb.wids.p, (float *)fb.wdist.p, (uint32_t *)fb.wnd.p, (uint32_t *)fb.wnh.p,
-                              (uint32_t *)fb.wst.p, idx->hFlagDev};
-            *(volatile uint32_t *)idx->hFlag = 0;
-            if ((rc = knn_search(idx, &wp, wb, st, stage == 0 ? d_stage : nullptr, nullptr, true))) return rc;
-            {
-                const hipError_t es = hipStreamSynchronize(st);
-                if (es != hipSuccess) return fail(HNSW_ERR_HIP, "filtered search failed: %s", hipGetErrorString(es));
-            }
-            if ((*(volatile uint32_t *)idx->hFlag & 1u) && (rc = knn_repair(idx, &wp, wb, st, nullptr, true))) return rc;
-            walked = true;
-
-            HIP_TRY(hipMemsetAsync(fb.count.p, 0, 4, st));
-            const hnsw_dev::SelectArgs sa{wb.ids, wb.dist, wb.nd, wb.nh, m, e, k, map, (const uint32_t *)f->bits.p, f->n, iv.id_base,
-                                          (uint32_t)stage, stage > 0, b.ids, b.dist, b.nd, b.nh, d_stage_out,
-                                          rerank ? (int32_t *)fb.cand.p : nullptr, (int32_t *)fb.cnt.p, (int32_t *)fb.list[cur ^ 1].p,
-                                          (uint32_t *)fb.count.p};
-            hipLaunchKernelGGL(hnsw_dev::filter_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
-            if ((rc = launched("filter select kernel"))) return rc;
-            uint32_t n_short = 0;
-            HIP_TRY(hipMemcpyAsync(&n_short, fb.count.p, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (rerank && (int64_t)n_short < m) {
-                // the served queries' allowed members over the float32 rows, then their rows to where they belong
-                if ((rc = launch_rerank(idx, Qj, m, qs, (const int32_t *)fb.cand.p, e, k, p.fill, (int32_t *)fb.rids.p, (float *)fb.rdist.p,
-                                        nullptr, (uint32_t *)fb.rnd.p, st)))
-                    return rc;
-                const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, m, k, map, (const int32_t *)fb.cnt.p,
-                                               (const uint32_t *)fb.rnd.p, 0u, 0, 0, 0u, b.ids, b.dist, b.nd, b.nh, d_stage_out};
-                hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)m), dim3(64), 0, st, sc);
-                if ((rc = launched("filter scatter kernel"))) return rc;
-            }
-            if (n_short == 0) return HNSW_OK;
-            // the short queries in ascending order: the next stage's batch
-            shorts.resize(n_short);
-            HIP_TRY(hipStreamSynchronize(st));       // (the re-rank and its scatter; the copies below are complete when they return)
-            HIP_TRY(hipMemcpy(shorts.data(), fb.list[cur ^ 1].p, (size_t)n_short * 4, hipMemcpyDeviceToHost));
-            std::sort(shorts.begin(), shorts.end());
-            HIP_TRY(hipMemcpy(fb.list[cur ^ 1].p, shorts.data(), (size_t)n_short * 4, hipMemcpyHostToDevice));
-            cur ^= 1;
-            map = (const int32_t *)fb.list[cur].p;
-            m = n_short;
-            if ((rc = fb.q.ensure((size_t)m * pad * sizeof(float)))) { (void)hipStreamSynchronize(st); return rc; }
-            hipLaunchKernelGGL(hnsw_dev::filter_gather_kernel, dim3((unsigned)m), dim3(64), 0, st, b.Q, b.q_stride, iv.d, map, m, (float *)fb.q.p, pad);
-            if ((rc = launched("filter gather kernel"))) { (void)hipStreamSynchronize(st); return rc; }
-            Qj = (const float *)fb.q.p;
-            qs = pad;
-            if (e >= 1024) break;           // still short with the largest W the library walks
-            e = std::min(1024, 2 * e);
+            const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, m, k, L.map, (const int32_t *)fb.cnt.p,
+                                           (const uint32_t *)fb.rnd.p, 0u, 0, 0, 0u, b.ids, b.dist, b.nd, b.nh, d_stage_out};
+            hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)m), dim3(64), 0, st, sc);
+            // (waited for here: a failure of theirs is this stage's, not the next walk's)
+            if ((rc = launched("filter scatter kernel")) || (rc = synced(st, "filtered search"))) return rc;
         }
+        if (L.n_short == 0) return HNSW_OK;
+        if ((rc = L.advance(more))) return rc;
     }
-    // the exact stage: the k smallest allowed nodes under (distance, id) for the m queries of (Qj, map)
-    if ((rc = scan_search(idx, {Qj, m, qs, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr, nullptr, nullptr, nullptr}, k, p.fill, st,
+    // the exact stage: the k smallest allowed nodes under (distance, id) for the L.m queries of (L.Qj, L.map)
+    if ((rc = scan_search(idx, {L.Qj, L.m, L.qs, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr, nullptr, nullptr, nullptr}, k, p.fill, st,
                           (const uint32_t *)f->bits.p)))
         return rc;
-    const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, m, k, map, nullptr, nullptr, (uint32_t)f->n_allowed,
+    const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, L.m, k, L.map, nullptr, nullptr, (uint32_t)f->n_allowed,
                                    !walked, 1, 0xFFFFFFFFu, b.ids, b.dist, b.nd, b.nh, d_stage_out};
-    hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)m), dim3(64), 0, st, sc);
+    hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)L.m), dim3(64), 0, st, sc);
     return launched("filter scatter kernel");
 }
 

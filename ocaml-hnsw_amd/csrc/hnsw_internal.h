@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/hnsw_mi355x.h"
 #include "hnsw_device.hip.h"
+#include "hnsw_scan_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -75,6 +76,16 @@ inline int hip_fail(hipError_t e, const char *what) {
         hipError_t e__ = (expr);                                            \
         if (e__ != hipSuccess) return ::hnsw_host::hip_fail(e__, #expr);    \
     } while (0)
+
+// the answer of the kernel launch just made / of waiting for st
+inline int launched(const char *what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? HNSW_OK : fail(HNSW_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+}
+inline int synced(hipStream_t st, const char *what) {
+    const hipError_t e = hipStreamSynchronize(st);
+    return e == hipSuccess ? HNSW_OK : fail(HNSW_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
 
 // ---- owners ---------------------------------------------------------------------------------------------------------------
 // Every device allocation, page-locked block, stream and event of the host side is held by one of these move-only types, whose
@@ -201,24 +212,25 @@ struct RefineBufs {
     }
 };
 
-// scratch of hnsw_search_batch_filtered (hnsw_filter.hip), sized on demand by the call; not index tables: not counted in device_bytes
+// Scratch of the ladder that the filtered and the range search share (Ladder, hnsw_filter.hip) and of what each does around it,
+// sized on demand by the call; not index tables: not counted in device_bytes.  One host thread uses a handle and both calls are
+// synchronous, so one LadderBufs serves both.
+struct LadderBufs {
+    DevBuf wnd, wnh, wst;                // one stage's walk: evaluations, hops, status of its m queries
+    DevBuf list[2], count;               // the queries still unserved, written by one stage and read by the next; how many
+    DevBuf q;                            // their vectors, gathered ([m][padded_stride(d)])
+};
 struct FilterBufs {
-    DevBuf wids, wdist, wnd, wnh, wst;   // one stage's walk: W ([m][e] ids and distances), evaluations, hops, status of its m queries
+    DevBuf wids, wdist;                  // one stage's W ([m][e] ids and distances)
     DevBuf cnt, cand;                    // per walked query its allowed members of W; half / sq8 rows: the masked W the re-rank reads
     DevBuf rids, rdist, rnd;             // a compact [m][k] result (re-rank, exact scan) before its rows go to their queries
-    DevBuf list[2], count;               // the queries still short, written by one stage and read by the next; how many
-    DevBuf q;                            // their vectors, gathered ([m][padded_stride(d)])
     DevBuf stage;                        // out_stage [nq]
 };
-
-// scratch of hnsw_range_search_batch / hnsw_range_brute_force_batch (hnsw_range.hip), sized on demand by the call; not index tables:
-// not counted in device_bytes.  What a caller keeps (lims, ids, distances, counters) belongs to the hnsw_range_result instead.
+// ... of the range calls.  What a caller keeps (lims, ids, distances, counters) belongs to the hnsw_range_result instead.
 constexpr int RANGE_STAGES = 11;         // the longest ladder: ef = 1, 2, 4, ... 1024
 struct RangeBufs {
     DevBuf wids[RANGE_STAGES], wdist[RANGE_STAGES];  // every stage's W ([m][e], half / sq8 rows: re-ranked), kept until the fill
-    DevBuf cand, cdist, wnd, wnh, wst, rnd;          // one stage's walk before its re-rank; evaluations, hops, status of its m queries
-    DevBuf list[2], count;                           // the queries still saturated, written by one stage and read by the next; how many
-    DevBuf q;                                        // their vectors, gathered ([m][padded_stride(d)])
+    DevBuf cand, cdist, rnd;                         // one stage's walk before its re-rank; its evaluations after it
     DevBuf cnt, src, stage, nd, nh;                  // per query: segment length (int64 [nq + 1]), its row of its stage's W, counters
     DevBuf counts, offs;                             // the exact scan: hits per (query, slab) (uint64 [m][slabs] + 1) and their exclusive sum
     DevBuf xcnt, xoff;                               // ... segment lengths of the exact-stage queries and where their words start ([m + 1])
@@ -323,7 +335,7 @@ struct hnsw_index {
     int order_mode = -1;                 // option "order_queries": -1 automatic (batches larger than half of what the chip holds: resident_queries), 0 never, 1 always
     int vt_bits_override = 0;
     int lds_pad = -1;                    // option "lds_pad": extra LDS bytes per search wave (-1 = balanced_lds_pad's choice)
-    int scan_slabs = 0;                  // option "scan_slabs": row slabs of the exact scan (0 = scan_slab_rows' choice)
+    int scan_slabs = 0;                  // option "scan_slabs": row slabs of the exact scans (0 = scan_slab_rows' choice)
     std::vector<std::pair<int, int>> prepared;   // (ef, accept rule) of every hnsw_index_prepare: what hnsw_index_save writes down
     // what the options "byte_rows" / "split_rows" asked for (bind_view leaves an unused copy out of the view), so that
     // hnsw_index_insert, which makes the row copies again, keeps their effect: byte_rows 0, split_rows 0 (off), split_rows -1
@@ -341,8 +353,11 @@ struct hnsw_index {
     // sq8_lo / sq8_scale describe tables.Xq whenever it exists.  hnsw_index_insert quantises the whole grown table again while it is on.
     bool sq8_on = false;
     float sq8_lo = 0.0f, sq8_scale = 1.0f;
-    hnsw_host::FilterBufs filter_scratch;   // hnsw_search_batch_filtered's stages: ONE such call in flight per handle
-    hnsw_host::RangeBufs range_scratch;     // the range calls' stages and exact scan: ONE such call in flight per handle
+    // the stages of hnsw_search_batch_filtered and of the range calls (ladder_scratch: of both), the range calls' exact scan: ONE
+    // such call in flight per handle
+    hnsw_host::LadderBufs ladder_scratch;
+    hnsw_host::FilterBufs filter_scratch;
+    hnsw_host::RangeBufs range_scratch;
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
 };
 
@@ -353,6 +368,29 @@ struct hnsw_filter {
     int64_t n_allowed = 0;               // set bits below n (filter_popcount_kernel)
     hnsw_host::DevBuf bits;              // ceil(n / 32) words, the positions >= n of the last one clear
 };
+
+namespace hnsw_dev {
+
+// The end of a ladder stage's select kernel (filter_select_kernel, range_select_kernel), one lane per walked query: row i of the
+// stage's batch belongs to query q.  Its walk's counters go to the query's; served, it gets the stage's number, else a place in
+// the short list through one atomic counter (the host sorts the list: the next stage's order, and with it nothing a caller can
+// see, depends on who came first).
+struct LadderOut {
+    const uint32_t *wnd, *wnh; // [m] the stage's evaluations and hops
+    uint32_t stage;            // what a served query's out_stage becomes
+    int32_t accumulate;        // out_nd / out_nh: 0 = set (the first walk), 1 = add
+    uint32_t *out_nd, *out_nh, *out_stage;   // [nq]
+    int32_t *short_list;       // the queries (map's numbering) that are not served ...
+    uint32_t *short_count;     // ... and how many
+};
+__device__ __forceinline__ void ladder_settle(const LadderOut &o, int64_t i, int64_t q, bool served) {
+    o.out_nd[q] = (o.accumulate ? o.out_nd[q] : 0u) + o.wnd[i];
+    o.out_nh[q] = (o.accumulate ? o.out_nh[q] : 0u) + o.wnh[i];
+    if (served) o.out_stage[q] = o.stage;
+    else o.short_list[atomicAdd(o.short_count, 1u)] = (int32_t)q;     // (at most m entries: one per block)
+}
+
+} // namespace hnsw_dev
 
 namespace hnsw_host {
 
@@ -451,8 +489,55 @@ int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_strid
 // hnsw_scan.hip: the exact scan of b's queries on `st` into b.ids / b.dist (hnsw_brute_force_batch_device, with its checks); mask
 // (optional, ceil(n / 32) device words): only the rows whose bit is set are candidates
 int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *mask = nullptr);
-// hnsw_scan.hip: rows per slab of the exact scan for a launch of `tiles` query tiles (option "scan_slabs" overrides the count)
-int64_t scan_slab_rows(const ::hnsw_index *idx, int64_t tiles, int k);
+// hnsw_scan.hip: how an exact scan of m queries of this index is cut (scan_plan: k for the slab rule, bytes per (query, slab)
+// cell, the first piece's cap), the kernels' NCH and tile, and the grid of a launch of nq <= piece queries
+struct ScanCut : ScanPlan {
+    int nch = 0, T = 0;
+    dim3 grid(int64_t nq) const;
+};
+ScanCut scan_cut(const ::hnsw_index *idx, int64_t m, int k, int64_t cell_bytes, int64_t cap);
+// the walk's distances are not exact over X (half, sq8 rows): what is kept of W is re-ranked over the float32 rows
+inline bool walk_is_inexact(const ::hnsw_index *idx) {
+    return idx->info.row_format == HNSW_ROWS_HALF || idx->info.row_format == HNSW_ROWS_SQ8;
+}
+// hnsw_filter.hip: the escalation both the filtered and the range search run -- e = ef, 2 ef, ... 1024: the batch is walked with
+// (ef = k = e, raw_walk), the caller's select kernel serves what it can and appends the other queries to the short list
+// (ladder_settle) and only those, gathered into one compact batch, are walked again.  Everything is queued on st and waited for
+// where the host needs a number (the tie-overflow word, the short count).  A failure returns with work queued: the entry points
+// synchronise st before they return it.
+struct Ladder {
+    ::hnsw_index *idx;
+    const float *Q;                      // the caller's batch (device address) ...
+    int64_t nq, q_stride;
+    int32_t semantics;
+    float *d_stage;                      // ... see knn_search
+    hipStream_t st;
+    const char *what;                    // the call's name in messages
+    // the batch of the current stage: at first the caller's, later the short queries of the stage before, row i belonging to
+    // query map[i] (null: to query i); after the ladder what is left for the exact stage
+    const float *Qj;
+    int64_t m, qs;
+    const int32_t *map = nullptr;
+    int e, stage = 0;
+    KnnBatch wb{};                       // the stage's walk: W where the caller wants it, counters and status in the ladder's scratch
+    uint32_t n_short = 0;
+    Ladder(::hnsw_index *idx_, const float *Q_, int64_t nq_, int64_t q_stride_, int ef, int32_t semantics_, float *d_stage_, hipStream_t st_,
+           const char *what_)
+        : idx(idx_), Q(Q_), nq(nq_), q_stride(q_stride_), semantics(semantics_), d_stage(d_stage_), st(st_), what(what_), Qj(Q_), m(nq_),
+          qs(q_stride_), e(ef) {}
+    // W_e of the batch into wids / wdist ([m][e]): the host form's search of (ef = e, k = e), its tie-overflow repair included,
+    // without a re-rank; the short counter zeroed
+    int walk(int32_t *wids, float *wdist, int32_t fill);
+    // what the select kernel's ladder_settle takes: wnd = the evaluations to add (the walk's, or the re-rank's sum)
+    hnsw_dev::LadderOut out(const uint32_t *wnd, uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage) const;
+    // after the select kernel: n_short
+    int count_short();
+    // the n_short > 0 short queries, ascending, become the batch; false: they were short at e = 1024, the ladder is over
+    int advance(bool &more);
+private:
+    int cur = 0;                         // which list buffer `map` is
+    std::vector<int32_t> shorts;
+};
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
 hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st);
 // hnsw_capi.hip: the handle's stream (hs[0]) and flag word of the host-buffer calls, made on first use

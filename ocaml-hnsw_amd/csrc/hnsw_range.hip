@@ -9,9 +9,8 @@
 //   exact    a query saturated at e = 1024, and every query of the brute-force form, gets the exact range scan.
 //
 // Kernels.
-//   hnsw_range_scan_kernel<NCH, METRIC, PASS>  the exact scan's grid, roles and arithmetic (hnsw_scan.hip: query tiles x groups of
-//                           row slabs, one wave per (tile, slab), scan_tile / scan_rows, the lane grid, the fmaf chain, reduce16,
-//                           dist_to_key: the bits of hnsw_distance_batch) without any selection state.  A row is a hit iff
+//   hnsw_range_scan_kernel<NCH, METRIC, PASS>  the exact scan's body (hnsw_scan_device.hip.h: grid, tile, rows in flight, the bits of
+//                           hnsw_distance_batch) with a selection that keeps no order (RangeHits).  A row is a hit iff
 //                           key_to_dist(key) <= radius; keys are monotone in distance, so that is lo <= key <= hi for two keys the
 //                           wave finds first (range_key_bounds).  PASS 0 counts the hits per (query, slab); PASS 1 runs the same
 //                           loop and writes the word (key << 32 | row) of each hit at the (query, slab)'s offset plus the hit's
@@ -19,28 +18,20 @@
 //   range_count_kernel      per exact-stage query the sum of its slabs' counts (from the exclusive sum), its counters and stage.
 //   range_unpack_kernel     the sorted words of an exact-stage query as ids (+ id_base) and key_to_dist.
 //   range_select_kernel     one wave per walked query: |W| and the length of W's in-range prefix, 64 entries per pass (ballot).
-//                           Served: its count, stage and row.  Saturated: appended to the short list through one atomic counter
-//                           (the host sorts the list, as filtered search does).
-//   range_gather_kernel     the saturated queries' vectors as one compact, zero-padded matrix (filter_gather_kernel's job).
+//                           Served: its count, stage and row.  Saturated: appended to the short list (ladder_settle); the ladder
+//                           (Ladder, hnsw_filter.hip) gathers them for the next walk.
 //   range_fill_kernel       the served queries' prefixes from their stages' W to lims[q], once every size is known.
 // Between the scan's passes: an exclusive sum of the counts (hipcub::DeviceScan), the grand total read on the host, the result
 // allocated.  After the fill hipcub::DeviceSegmentedRadixSort orders each exact-stage segment by its 64-bit words: ascending words
 // = the total order (distance key, node id), no drops however many ties.  Vector stores only.  All scratch is the handle's
-// (RangeBufs): one range call in flight per handle; lims, ids, distances and counters belong to the hnsw_range_result.
+// (LadderBufs, RangeBufs): one range or filtered call in flight per handle; lims, ids, distances and counters belong to the
+// hnsw_range_result.
 #include "hnsw_internal.h"
+#include "hnsw_scan_device.hip.h"
 
 #include <hipcub/hipcub.hpp>
 
 namespace hnsw_dev {
-
-// ---- the exact scan's shape, restated (hnsw_scan.hip keeps its own: that file stays the code it was) ------------------------------
-constexpr int RANGE_WAVES = 4;         // = SCAN_WAVES: waves per workgroup, one slab each
-// = scan_tile: queries per tile (T * NCH * 4 VGPRs hold them for NCH <= 4; through LDS the tile costs T * NCH * 256 bytes)
-__host__ __device__ constexpr int range_scan_tile(int nch) { return nch <= 2 ? 8 : nch == 4 ? 4 : 8; }
-// = scan_rows: batches of four rows in flight per wave (UB * NCH * 4 VGPRs)
-__host__ __device__ constexpr int range_scan_rows(int nch) { return nch == 1 ? 4 : nch <= 4 ? 2 : 1; }
-// = scan_min_waves: waves per SIMD the register allocator must leave room for
-__host__ __device__ constexpr int range_min_waves(int nch) { return nch == 1 || nch == 8 ? 4 : nch == 16 ? 2 : 3; }
 
 struct RangeScanArgs {
     const float *Q;            // the queries of this launch
@@ -69,118 +60,64 @@ template <int METRIC> __device__ __forceinline__ void range_key_bounds(float rad
     hi = a;
 }
 
-template <int NCH, int METRIC, int PASS>
-__global__ void __launch_bounds__(64 * RANGE_WAVES, range_min_waves(NCH))
-hnsw_range_scan_kernel(const IndexView iv, const RangeScanArgs a) {
-    constexpr int T = range_scan_tile(NCH), UB = range_scan_rows(NCH);
-    constexpr bool QLDS = NCH >= 8;
-    __shared__ float4 qs[QLDS ? T * 16 * NCH : 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane >> 4, l16 = lane & 15;
-    const int64_t q0 = (int64_t)blockIdx.x * T;
-    const int tq = (int)(a.nq - q0 < T ? a.nq - q0 : T);       // queries of this tile (>= 1: the grid has no empty tile)
-
-    float4 qv[QLDS ? 1 : T][QLDS ? 1 : NCH];
-    if constexpr (QLDS) {       // the workgroup loads the tile once, zero beyond d and beyond the tile's last query
-        for (int c = threadIdx.x; c < T * 16 * NCH; c += 64 * RANGE_WAVES) {
-            const int t = c / (16 * NCH), e0 = 4 * (c % (16 * NCH));
-            const float *qp = a.Q + (q0 + (t < tq ? t : 0)) * a.q_stride;
-            float4 v;
-            v.x = (t < tq && e0 + 0 < iv.d) ? qp[e0 + 0] : 0.f; v.y = (t < tq && e0 + 1 < iv.d) ? qp[e0 + 1] : 0.f;
-            v.z = (t < tq && e0 + 2 < iv.d) ? qp[e0 + 2] : 0.f; v.w = (t < tq && e0 + 3 < iv.d) ? qp[e0 + 3] : 0.f;
-            qs[c] = v;
-        }
-        __syncthreads();
-    } else {
-#pragma unroll
-        for (int t = 0; t < T; ++t) load_query<NCH>(qv[t], a.Q + (q0 + (t < tq ? t : 0)) * a.q_stride, iv.d, l16);
-    }
-    const int64_t slab = (int64_t)blockIdx.y * RANGE_WAVES + wave;
-    if (slab >= a.n_slabs) return;                  // (after the only workgroup barrier)
-    const int64_t r0 = slab * a.slab_rows, r1 = r0 + a.slab_rows < iv.n ? r0 + a.slab_rows : iv.n;
+// The hits of one (tile, slab) wave (scan_slab's Select): counted (PASS 0), or written where PASS 0's counts say (PASS 1)
+template <int NCH, int METRIC, int PASS> struct RangeHits {
+    static constexpr int T = scan_tile(NCH);
+    const RangeScanArgs &a;
     uint32_t klo, khi;
-    range_key_bounds<METRIC>(a.radius, klo, khi);
-    klo = (uint32_t)uniform((int)klo); khi = (uint32_t)uniform((int)khi);
-
+    int64_t q0, slab;
+    int tq, lane;
     // per query of the tile: its hits so far in this slab (wave-uniform); PASS 1: where its words go and how many PASS 0 counted
-    int cnt[T];
+    int cnt[T], lim[T];
     uint64_t *dst[T];
-    int lim[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        cnt[t] = 0;
-        dst[t] = nullptr;
-        lim[t] = 0;
-        if (PASS == 1 && t < tq) {
-            const int64_t at = (q0 + t) * a.n_slabs;
-            dst[t] = a.words + a.xoff[q0 + t] + (int64_t)(a.offs[at + slab] - a.offs[at]);
-            lim[t] = (int)(a.offs[at + slab + 1] - a.offs[at + slab]);
-        }
-    }
 
-    const uint32_t stride_b = (uint32_t)iv.stride * 4u;
-    for (int64_t base = r0; base < r1; base += 4 * UB) {
-        float4 v[UB][NCH];
+    __device__ __forceinline__ explicit RangeHits(const RangeScanArgs &a_) : a(a_) {}
+    __device__ __forceinline__ void begin(int64_t q0_, int tq_, int64_t slab_) {
+        q0 = q0_; tq = tq_; slab = slab_;
+        lane = threadIdx.x & 63;
+        range_key_bounds<METRIC>(a.radius, klo, khi);
+        klo = (uint32_t)uniform((int)klo); khi = (uint32_t)uniform((int)khi);
 #pragma unroll
-        for (int u = 0; u < UB; ++u) {              // past the slab's end: its last row again, dropped below
-            const int64_t row = base + 4 * u + r;
-            const char *rp = reinterpret_cast<const char *>(iv.X) + (uint64_t)(row < r1 ? row : r1 - 1) * stride_b;
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int c = i * 16 + l16;
-                v[u][i] = *reinterpret_cast<const float4 *>(rp + 16u * (uint32_t)(c < iv.nchunks ? c : 0));
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {         // lanes past the row end add exactly 0 (their query chunk is 0)
-                const bool cv = (i * 16 + l16) < iv.nchunks;
-                v[u][i].x = cv ? v[u][i].x : 0.f; v[u][i].y = cv ? v[u][i].y : 0.f;
-                v[u][i].z = cv ? v[u][i].z : 0.f; v[u][i].w = cv ? v[u][i].w : 0.f;
-            }
-            const int64_t row = base + 4 * u + r;
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                // (the tile in LDS is read here, every time: left alone the compiler hoists T * NCH float4 reads out of the loops)
-                if constexpr (QLDS) asm volatile("" ::: "memory");
-                float acc = 0.f;
-#pragma unroll
-                for (int i = 0; i < NCH; ++i) {
-                    const float4 z = v[u][i];
-                    const float4 qi = QLDS ? qs[(t * NCH + i) * 16 + l16] : qv[QLDS ? 0 : t][QLDS ? 0 : i];
-                    if (METRIC == 0) {
-                        float dx = z.x - qi.x; acc = __builtin_fmaf(dx, dx, acc);
-                        float dy = z.y - qi.y; acc = __builtin_fmaf(dy, dy, acc);
-                        float dz = z.z - qi.z; acc = __builtin_fmaf(dz, dz, acc);
-                        float dw = z.w - qi.w; acc = __builtin_fmaf(dw, dw, acc);
-                    } else {
-                        acc = __builtin_fmaf(z.x, qi.x, acc);
-                        acc = __builtin_fmaf(z.y, qi.y, acc);
-                        acc = __builtin_fmaf(z.z, qi.z, acc);
-                        acc = __builtin_fmaf(z.w, qi.w, acc);
-                    }
-                }
-                acc = reduce16(acc);
-                const uint32_t key = dist_to_key<METRIC>(acc);
-                // a query past the tile's end has no hits; the rows of a batch lie in lane order: r ascending = id ascending
-                const bool hit = l16 == 0 && row < r1 && t < tq && key >= klo && key <= khi;
-                const uint64_t m = ballot(hit);
-                if (m) {
-                    if (PASS == 1) {
-                        const int pos = cnt[t] + popc(m & ((1ull << lane) - 1ull));
-                        if (hit && pos < lim[t]) dst[t][pos] = ((uint64_t)key << 32) | (uint32_t)row;
-                    }
-                    cnt[t] += popc(m);
-                }
+        for (int t = 0; t < T; ++t) {
+            cnt[t] = 0;
+            dst[t] = nullptr;
+            lim[t] = 0;
+            if (PASS == 1 && t < tq) {
+                const int64_t at = (q0 + t) * a.n_slabs;
+                dst[t] = a.words + a.xoff[q0 + t] + (int64_t)(a.offs[at + slab] - a.offs[at]);
+                lim[t] = (int)(a.offs[at + slab + 1] - a.offs[at + slab]);
             }
         }
     }
-    if (PASS == 0 && lane == 0) {
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-            if (t < tq) a.counts[(q0 + t) * a.n_slabs + slab] = (uint64_t)cnt[t];
+    __device__ __forceinline__ bool skip(int64_t) const { return false; }
+    __device__ __forceinline__ bool admits(int64_t, bool in_slab) const { return in_slab; }
+    __device__ __forceinline__ void take(int t, uint32_t key, int64_t row, bool ok) {
+        // a query past the tile's end has no hits; the rows of a batch lie in lane order: r ascending = id ascending
+        const bool hit = (lane & 15) == 0 && ok && t < tq && key >= klo && key <= khi;
+        const uint64_t m = ballot(hit);
+        if (m) {
+            if (PASS == 1) {
+                const int pos = cnt[t] + popc(m & ((1ull << lane) - 1ull));
+                if (hit && pos < lim[t]) dst[t][pos] = ((uint64_t)key << 32) | (uint32_t)row;
+            }
+            cnt[t] += popc(m);
+        }
     }
+    __device__ __forceinline__ void batch_end() {}
+    __device__ __forceinline__ void end() {
+        if (PASS == 0 && lane == 0) {
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+                if (t < tq) a.counts[(q0 + t) * a.n_slabs + slab] = (uint64_t)cnt[t];
+        }
+    }
+};
+
+template <int NCH, int METRIC, int PASS>
+__global__ void __launch_bounds__(64 * SCAN_WAVES, scan_min_waves(NCH))
+hnsw_range_scan_kernel(const IndexView iv, const RangeScanArgs a) {
+    RangeHits<NCH, METRIC, PASS> sel(a);
+    scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
 
 struct RangeCountArgs {
@@ -226,19 +163,14 @@ range_unpack_kernel(const uint64_t *words, const int64_t *xoff, int64_t m, const
 struct RangeSelectArgs {
     const int32_t *wids;       // [m][e] the stage's W per query, id_base-based, ascending, filled entries < id_base
     const float *wdist;        // [m][e]
-    const uint32_t *wnd, *wnh; // [m] evaluations (the re-rank's included) and hops
     int64_t m;
     int32_t e;
     const int32_t *map;        // [m] row i belongs to query map[i]; null: to query i
     float radius;
     int32_t id_base;
-    uint32_t stage;            // what a served query's out_stage becomes
-    int32_t accumulate;        // out_nd / out_nh: 0 = set (the first walk), 1 = add
     int64_t *cnt;              // [nq] a served query's segment length
     int32_t *src;              // [nq] ... and its row of this stage's W
-    uint32_t *out_nd, *out_nh, *out_stage;   // [nq]
-    int32_t *short_list;       // the queries (map's numbering) that are saturated ...
-    uint32_t *short_count;     // ... and how many
+    LadderOut out;             // (its evaluations: the re-rank's included)
 };
 
 __global__ void __launch_bounds__(64)
@@ -254,25 +186,12 @@ range_select_kernel(const RangeSelectArgs a) {
     }
     // saturated: |W| = e and its last member is in range, that is all e entries are
     if (lane == 0) {
-        a.out_nd[q] = (a.accumulate ? a.out_nd[q] : 0u) + a.wnd[i];
-        a.out_nh[q] = (a.accumulate ? a.out_nh[q] : 0u) + a.wnh[i];
         if (in < a.e) {
             a.cnt[q] = in;
             a.src[q] = (int32_t)i;
-            a.out_stage[q] = a.stage;
-        } else {
-            a.short_list[atomicAdd(a.short_count, 1u)] = (int32_t)q;     // (at most m entries: one per block)
         }
+        ladder_settle(a.out, i, q, in < a.e);
     }
-}
-
-// out[i] = Q[list[i]], rows of out_stride floats, zero beyond d
-__global__ void __launch_bounds__(64)
-range_gather_kernel(const float *Q, int64_t q_stride, int32_t d, const int32_t *list, int64_t m, float *out, int64_t out_stride) {
-    const int64_t i = blockIdx.x;
-    if (i >= m) return;
-    const float *qp = Q + (int64_t)list[i] * q_stride;
-    for (int64_t c = threadIdx.x; c < out_stride; c += 64) out[i * out_stride + c] = c < d ? qp[c] : 0.f;
 }
 
 struct RangeFillArgs {
@@ -315,16 +234,6 @@ struct hnsw_range_result {
 
 namespace {
 
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HNSW_OK : fail(HNSW_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-}
-
-int synced(hipStream_t st, const char *what) {
-    const hipError_t e = hipStreamSynchronize(st);
-    return e == hipSuccess ? HNSW_OK : fail(HNSW_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-}
-
 // out[0 .. count) = the exclusive sum of in[0 .. count) on st (count >= 1), through the handle's temporary storage
 template <class T, class U>
 int exclusive_sum(RangeBufs &rb, const T *in, U *out, int64_t count, hipStream_t st) {
@@ -340,35 +249,20 @@ int exclusive_sum(RangeBufs &rb, const T *in, U *out, int64_t count, hipStream_t
 
 // The queries of the exact stage -- (Q, map): m rows, row i belonging to query map[i] (null: to query i) -- and how they are cut.
 // A piece's counts and offsets fit SCAN_SCRATCH bytes of the handle's scratch, as the k-scan's lists do.
-struct ExactPlan {
+struct ExactPlan : ScanCut {
     const float *Q = nullptr;
     int64_t m = 0, q_stride = 0;
     const int32_t *map = nullptr;
-    int nch = 0, T = 0;
-    int64_t piece = 0, slab_rows = 0, slabs = 0;
+    // (a count and an offset per (query, slab) cell)
+    void cut(const hnsw_index *idx) { static_cast<ScanCut &>(*this) = scan_cut(idx, m, 1, 16, m); }
 };
 
-void plan_exact(const hnsw_index *idx, ExactPlan &x) {
-    constexpr int64_t SCAN_SCRATCH = 256ll << 20;
-    x.nch = pick_nch(idx->iv.nchunks);
-    x.T = hnsw_dev::range_scan_tile(x.nch);
-    x.piece = x.m;
-    for (;;) {      // (a smaller piece has fewer tiles and may be cut into more slabs: settle on a piece that fits)
-        x.slab_rows = scan_slab_rows(idx, (x.piece + x.T - 1) / x.T, 1);
-        x.slabs = idx->iv.n > 0 ? (idx->iv.n + x.slab_rows - 1) / x.slab_rows : 0;
-        const int64_t per_query = std::max<int64_t>(x.slabs, 1) * 16;
-        if (x.piece * per_query <= SCAN_SCRATCH || x.piece <= x.T) break;
-        x.piece = std::max<int64_t>(x.T, SCAN_SCRATCH / per_query / x.T * x.T);
-    }
-}
-
-hipError_t launch_range_scan(const hnsw_index *idx, const ExactPlan &x, int pass, int64_t nq, const hnsw_dev::RangeScanArgs &a, hipStream_t st) {
-    const dim3 grid((unsigned)((nq + x.T - 1) / x.T), (unsigned)((x.slabs + hnsw_dev::RANGE_WAVES - 1) / hnsw_dev::RANGE_WAVES));
+int launch_range_scan(const hnsw_index *idx, const ExactPlan &x, int pass, int64_t nq, const hnsw_dev::RangeScanArgs &a, hipStream_t st) {
     with_metric(idx->info.metric, [&](auto METRIC) { with_nch(x.nch, [&](auto NCH) {
-        if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 0>), grid, dim3(64 * hnsw_dev::RANGE_WAVES), 0, st, idx->iv, a);
-        else hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 1>), grid, dim3(64 * hnsw_dev::RANGE_WAVES), 0, st, idx->iv, a);
+        if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 0>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a);
+        else hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 1>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a);
     }); });
-    return hipGetLastError();
+    return launched("range scan kernel");
 }
 
 // PASS 0 for the rows [i0, i0 + mp) of x and the exclusive sum of its counts (rb.offs: [mp * slabs + 1])
@@ -377,8 +271,8 @@ int exact_count_piece(hnsw_index *idx, const ExactPlan &x, float radius, int64_t
     const int64_t cells = mp * x.slabs;
     hnsw_dev::RangeScanArgs a{x.Q + i0 * x.q_stride, x.q_stride, mp, (int32_t)x.slabs, x.slab_rows, radius, (uint64_t *)rb.counts.p, nullptr, nullptr, nullptr};
     HIP_TRY(hipMemsetAsync((uint64_t *)rb.counts.p + cells, 0, 8, st));       // (the sum's last entry is the piece's total)
-    const hipError_t e = launch_range_scan(idx, x, 0, mp, a, st);
-    if (e != hipSuccess) return fail(HNSW_ERR_HIP, "range scan kernel launch failed: %s", hipGetErrorString(e));
+    int rc;
+    if ((rc = launch_range_scan(idx, x, 0, mp, a, st))) return rc;
     return exclusive_sum(rb, (const uint64_t *)rb.counts.p, (uint64_t *)rb.offs.p, cells + 1, st);
 }
 
@@ -426,8 +320,7 @@ int exact_fill(hnsw_index *idx, const ExactPlan &x, float radius, hnsw_range_res
         if (x.piece < x.m && (rc = exact_count_piece(idx, x, radius, i0, mp, st))) return rc;
         const hnsw_dev::RangeScanArgs a{x.Q + i0 * x.q_stride, x.q_stride, mp, (int32_t)x.slabs, x.slab_rows, radius, nullptr,
                                         (const uint64_t *)rb.offs.p, (const int64_t *)rb.xoff.p + i0, (uint64_t *)rb.words[0].p};
-        const hipError_t e = launch_range_scan(idx, x, 1, mp, a, st);
-        if (e != hipSuccess) return fail(HNSW_ERR_HIP, "range scan kernel launch failed: %s", hipGetErrorString(e));
+        if ((rc = launch_range_scan(idx, x, 1, mp, a, st))) return rc;
     }
     // each segment by its words: (distance key, node id) ascending
     size_t bytes = 0;
@@ -452,67 +345,31 @@ int exact_fill(hnsw_index *idx, const ExactPlan &x, float radius, hnsw_range_res
 int range_ladder(hnsw_index *idx, const hnsw_range_params &p, const float *Q, int64_t nq, int64_t q_stride, float *d_stage, hipStream_t st,
                  ExactPlan &x, std::vector<int32_t> &e_of) {
     RangeBufs &rb = idx->range_scratch;
-    const IndexView &iv = idx->iv;
-    const bool rerank = idx->info.row_format == HNSW_ROWS_HALF || idx->info.row_format == HNSW_ROWS_SQ8;
-    const int64_t pad = padded_stride(iv.d);
+    const bool rerank = walk_is_inexact(idx);
     int rc;
-    if ((rc = rb.list[0].ensure((size_t)nq * 4)) || (rc = rb.list[1].ensure((size_t)nq * 4)) || (rc = rb.count.ensure(16))) return rc;
-
-    // the batch of the current stage: at first the caller's, later the saturated queries of the stage before (rb.q, rb.list[cur])
-    int64_t m = nq;
-    const float *Qj = Q;
-    int64_t qs = q_stride;
-    const int32_t *map = nullptr;
-    int cur = 0;                 // which list buffer `map` is
-    std::vector<int32_t> shorts;
+    Ladder L(idx, Q, nq, q_stride, p.ef, p.semantics, d_stage, st, "range search");
     x.m = 0;
-    for (int e = p.ef, stage = 0;; ++stage) {
-        DevBuf &Wi = rb.wids[stage], &Wd = rb.wdist[stage];
-        if ((rc = Wi.ensure((size_t)m * e * 4)) || (rc = Wd.ensure((size_t)m * e * 4)) || (rc = rb.wnd.ensure((size_t)m * 4)) ||
-            (rc = rb.wnh.ensure((size_t)m * 4)) || (rc = rb.wst.ensure((size_t)m * 4)) ||
+    for (bool more = true; more;) {
+        const int64_t m = L.m;
+        const int e = L.e;
+        DevBuf &Wi = rb.wids[L.stage], &Wd = rb.wdist[L.stage];
+        if ((rc = Wi.ensure((size_t)m * e * 4)) || (rc = Wd.ensure((size_t)m * e * 4)) ||
             (rerank && ((rc = rb.cand.ensure((size_t)m * e * 4)) || (rc = rb.cdist.ensure((size_t)m * e * 4)) || (rc = rb.rnd.ensure((size_t)m * 4)))))
             return rc;
         e_of.push_back(e);
-        // W_e: the host form's search of (ef = e, k = e), its tie-overflow repair included, without a re-rank
-        const hnsw_search_params wp{e, e, HNSW_FILL_OHNSW, p.semantics};
-        const KnnBatch wb{Qj, m, qs, (int32_t *)(rerank ? rb.cand.p : Wi.p), (float *)(rerank ? rb.cdist.p : Wd.p), (uint32_t *)rb.wnd.p,
-                          (uint32_t *)rb.wnh.p, (uint32_t *)rb.wst.p, idx->hFlagDev};
-        *(volatile uint32_t *)idx->hFlag = 0;
-        if ((rc = knn_search(idx, &wp, wb, st, stage == 0 ? d_stage : nullptr, nullptr, true))) return rc;
-        if ((rc = synced(st, "range search"))) return rc;
-        if ((*(volatile uint32_t *)idx->hFlag & 1u) && (rc = knn_repair(idx, &wp, wb, st, nullptr, true))) return rc;
+        if ((rc = L.walk((int32_t *)(rerank ? rb.cand.p : Wi.p), (float *)(rerank ? rb.cdist.p : Wd.p), HNSW_FILL_OHNSW))) return rc;
         // half / sq8 rows: all members of W over the float32 rows, k := e
-        if (rerank && (rc = launch_rerank(idx, Qj, m, qs, wb.ids, e, e, HNSW_FILL_OHNSW, (int32_t *)Wi.p, (float *)Wd.p, wb.nd, (uint32_t *)rb.rnd.p, st)))
+        if (rerank && (rc = launch_rerank(idx, L.Qj, m, L.qs, L.wb.ids, e, e, HNSW_FILL_OHNSW, (int32_t *)Wi.p, (float *)Wd.p, L.wb.nd, (uint32_t *)rb.rnd.p, st)))
             return rc;
-
-        HIP_TRY(hipMemsetAsync(rb.count.p, 0, 4, st));
-        const hnsw_dev::RangeSelectArgs sa{(const int32_t *)Wi.p, (const float *)Wd.p, (const uint32_t *)(rerank ? rb.rnd.p : rb.wnd.p), wb.nh, m, e, map,
-                                           p.radius, iv.id_base, (uint32_t)stage, stage > 0, (int64_t *)rb.cnt.p, (int32_t *)rb.src.p,
-                                           (uint32_t *)rb.nd.p, (uint32_t *)rb.nh.p, (uint32_t *)rb.stage.p, (int32_t *)rb.list[cur ^ 1].p,
-                                           (uint32_t *)rb.count.p};
+        const hnsw_dev::RangeSelectArgs sa{(const int32_t *)Wi.p, (const float *)Wd.p, m, e, L.map, p.radius, idx->iv.id_base, (int64_t *)rb.cnt.p,
+                                           (int32_t *)rb.src.p,
+                                           L.out(rerank ? (const uint32_t *)rb.rnd.p : L.wb.nd, (uint32_t *)rb.nd.p, (uint32_t *)rb.nh.p, (uint32_t *)rb.stage.p)};
         hipLaunchKernelGGL(hnsw_dev::range_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
-        if ((rc = launched("range select kernel"))) { (void)hipStreamSynchronize(st); return rc; }
-        uint32_t n_short = 0;
-        HIP_TRY(hipMemcpyAsync(&n_short, rb.count.p, 4, hipMemcpyDeviceToHost, st));
-        if ((rc = synced(st, "range search"))) return rc;
-        if (n_short == 0) return HNSW_OK;
-        // the saturated queries in ascending order: the next stage's batch
-        shorts.resize(n_short);
-        HIP_TRY(hipMemcpy(shorts.data(), rb.list[cur ^ 1].p, (size_t)n_short * 4, hipMemcpyDeviceToHost));
-        std::sort(shorts.begin(), shorts.end());
-        HIP_TRY(hipMemcpy(rb.list[cur ^ 1].p, shorts.data(), (size_t)n_short * 4, hipMemcpyHostToDevice));
-        cur ^= 1;
-        map = (const int32_t *)rb.list[cur].p;
-        m = n_short;
-        if ((rc = rb.q.ensure((size_t)m * pad * sizeof(float)))) return rc;
-        hipLaunchKernelGGL(hnsw_dev::range_gather_kernel, dim3((unsigned)m), dim3(64), 0, st, Q, q_stride, iv.d, map, m, (float *)rb.q.p, pad);
-        if ((rc = launched("range gather kernel"))) { (void)hipStreamSynchronize(st); return rc; }
-        Qj = (const float *)rb.q.p;
-        qs = pad;
-        if (e >= 1024) break;           // still saturated with the largest W the library walks
-        e = std::min(1024, 2 * e);
+        if ((rc = launched("range select kernel")) || (rc = L.count_short())) return rc;
+        if (L.n_short == 0) return HNSW_OK;
+        if ((rc = L.advance(more))) return rc;
     }
-    x.Q = Qj; x.m = m; x.q_stride = qs; x.map = map;
+    x.Q = L.Qj; x.m = L.m; x.q_stride = L.qs; x.map = L.map;
     return HNSW_OK;
 }
 
@@ -547,7 +404,7 @@ int range_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stri
         x.Q = c.b.Q; x.m = nq; x.q_stride = q_stride; x.map = nullptr;
     }
     if (!rc && x.m > 0) {
-        plan_exact(idx, x);
+        x.cut(idx);
         rc = exact_count(idx, x, radius, !p, st);
     }
     // every query's size is known: lims, the grand total, the result's buffers

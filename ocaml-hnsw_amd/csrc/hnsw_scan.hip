@@ -2,40 +2,27 @@
 // holds, with the index's metric and the search kernels' own arithmetic (hnsw_brute_force_batch / _device).
 //
 // Three kernels.
-//   hnsw_scan_kernel<NCH, METRIC>: grid (query tiles) x (groups of SCAN_WAVES row slabs), one wave per (tile, slab).  A wave
-//     keeps the chunks of the T queries of its tile in registers (NCH <= 4) or shares them with the other waves of its
-//     workgroup through LDS (NCH >= 8, as hnsw_distance_kernel does) and walks the rows of its slab in id order, 4 * UB rows
-//     in flight: one 16-lane group per row, lane l16 on the float4 chunks l16, l16 + 16, ... -- the lane grid, the fmaf chain
-//     and the reduce16 tree of every other kernel here, so the sums are the same bits.  Every row chunk loaded is used for all
-//     T queries.  The workgroups of one slab group are consecutive in dispatch order (blockIdx.x is the tile), so the rows of
-//     a slab are fetched from HBM once per XCD and otherwise come out of L2.
-//     Selection: a candidate is the 64-bit word (ordered distance key << 32 | node): ascending words = the total order
-//     (distance, id).  Per query the wave holds the word of the k-th smallest candidate its slab has shown so far (all ones
-//     until there are k); the common path is ONE compare of the new key against that word's upper half, for the wave's four
-//     rows at once.  Survivors are appended to the query's 64-entry LDS buffer; a buffer that may not take another round
-//     is merged into the query's sorted list of k words in global memory (scan_flush: never drops a word that is among the
-//     k smallest, never gives up), which lowers the threshold.  The list lives in two halves, read from one and written
-//     to the other.
+//   hnsw_scan_kernel<NCH, METRIC>: the scan body of hnsw_scan_device.hip.h (grid, tile, rows in flight, the distance bits) with
+//     the top-k selection below (ScanTopK).  A candidate is the 64-bit word (ordered distance key << 32 | node): ascending words
+//     = the total order (distance, id).  Per query the wave holds the word of the k-th smallest candidate its slab has shown so
+//     far (all ones until there are k); the common path is ONE compare of the new key against that word's upper half, for the
+//     wave's four rows at once.  Survivors are appended to the query's 64-entry LDS buffer; a buffer that may not take another
+//     round is merged into the query's sorted list of k words in global memory (scan_flush: never drops a word that is among the
+//     k smallest, never gives up), which lowers the threshold.  The list lives in two halves, read from one and written to the
+//     other.
 //   hnsw_scan_masked_kernel<NCH, METRIC>: the same scan over the rows an allow-mask names (hnsw_search_batch_filtered's exact
-//     stage, hnsw_filter.hip).  Both kernels are the one body of hnsw_scan_slab.inc, so that the unmasked one stays the code it was.
+//     stage, hnsw_filter.hip): ScanTopK<NCH, true>.
 //   hnsw_scan_merge_kernel<METRIC>: one workgroup per query merges the slabs' lists under the same order and writes ids
 //     (+ id_base), distances (key_to_dist) and the fill.
 // Nothing here depends on how the rows are cut into slabs or the queries into tiles: every list is the exact k smallest of its
 // slab, and the merge takes the exact k smallest of their union.
 #include "hnsw_internal.h"
+#include "hnsw_scan_device.hip.h"
 
 namespace hnsw_dev {
 
-constexpr int SCAN_WAVES = 4;          // waves per workgroup, one slab each
 constexpr int SCAN_BUF = 64;           // survivor words per query and wave (LDS)
 constexpr uint64_t SCAN_EMPTY = ~0ull; // no candidate: above every real word
-// queries per tile: T * NCH * 4 VGPRs hold them for NCH <= 4 (64 at most); through LDS the tile costs T * NCH * 256 bytes
-__host__ __device__ constexpr int scan_tile(int nch) { return nch <= 2 ? 8 : nch == 4 ? 4 : 8; }
-// batches of four rows in flight per wave: UB * NCH * 4 VGPRs
-__host__ __device__ constexpr int scan_rows(int nch) { return nch == 1 ? 4 : nch <= 4 ? 2 : 1; }
-
-// waves per SIMD the register allocator must leave room for
-__host__ __device__ constexpr int scan_min_waves(int nch) { return nch == 1 || nch == 8 ? 4 : nch == 16 ? 2 : 3; }
 
 struct ScanArgs {
     const float *Q;        // the queries of this launch
@@ -86,21 +73,97 @@ __device__ __forceinline__ void scan_flush(const uint64_t *buf, uint64_t *sorted
     scan_wave_sync();
 }
 
+// The top-k selection of one (tile, slab) wave (scan_slab's Select).  MASKED: `mask` holds one bit per row, bit row & 31 of word
+// row >> 5, ceil(n / 32) words; a row whose bit is clear contributes no candidate, and a 32-row word without a set bit is stepped
+// over without loading its rows.
+template <int NCH, bool MASKED> struct ScanTopK {
+    static constexpr int T = scan_tile(NCH);
+    static constexpr int LIMIT = SCAN_BUF - 4 * scan_rows(NCH);   // a buffer up to here takes the survivors of one more pass over the UB batches
+    const ScanArgs &a;
+    const uint32_t *mask;
+    // per query of the tile: its list's two halves, which half is current (bit t of par), the threshold word, the buffer's fill
+    uint64_t (*bufs)[SCAN_BUF], *sorted, *lists0;
+    int64_t list_step;
+    uint64_t thr[T];
+    int cnt[T], tq, lane;
+    uint32_t par;
+    bool full;
+
+    __device__ __forceinline__ ScanTopK(const ScanArgs &a_, const uint32_t *mask_) : a(a_), mask(mask_) {}
+    __device__ __forceinline__ void begin(int64_t q0, int tq_, int64_t slab) {
+        __shared__ uint64_t bufs_all[SCAN_WAVES][T][SCAN_BUF];
+        __shared__ uint64_t sorted_all[SCAN_WAVES][SCAN_BUF];
+        lane = threadIdx.x & 63;
+        bufs = bufs_all[threadIdx.x >> 6];
+        sorted = sorted_all[threadIdx.x >> 6];
+        tq = tq_;
+        lists0 = a.lists + ((q0 * a.n_slabs + slab) * 2) * (int64_t)a.k;
+        list_step = (int64_t)a.n_slabs * 2 * a.k;
+        par = 0;
+        full = false;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            // a query past the tile's end never has a survivor (no word is below 0)
+            thr[t] = t < tq ? SCAN_EMPTY : 0ull;
+            cnt[t] = 0;
+            if (t < tq) for (int j = lane; j < a.k; j += 64) lists0[t * list_step + j] = SCAN_EMPTY;
+        }
+        scan_wave_sync();
+    }
+    __device__ __forceinline__ bool skip(int64_t base) const { return MASKED && uniform((int)mask[base >> 5]) == 0; }
+    __device__ __forceinline__ bool admits(int64_t row, bool in_slab) const {
+        return in_slab && (!MASKED || ((mask[row >> 5] >> (row & 31)) & 1u));
+    }
+    __device__ __forceinline__ void take(int t, uint32_t key, int64_t row, bool ok) {
+        if (ballot(key <= (uint32_t)(thr[t] >> 32))) {           // rare: some row of the four may be among the k smallest
+            const uint64_t e = ((uint64_t)key << 32) | (uint32_t)row;
+            const bool in = (lane & 15) == 0 && ok && e < thr[t];
+            const uint64_t m = ballot(in);
+            if (in) bufs[t][cnt[t] + popc(m & ((1ull << lane) - 1ull))] = e;
+            cnt[t] += popc(m);
+            full = full || cnt[t] > LIMIT;
+        }
+    }
+    // merges query t's buffer into its list, which lowers its threshold
+    __device__ __forceinline__ void flush(int t) {
+        uint64_t *const A = lists0 + t * list_step;
+        const bool p = (par >> t) & 1u;
+        scan_flush(bufs[t], sorted, cnt[t], A + (p ? a.k : 0), A + (p ? 0 : a.k), a.k, lane);
+        par ^= 1u << t;
+        cnt[t] = 0;
+        thr[t] = scan_uniform64((A + (p ? 0 : a.k))[a.k - 1]);
+    }
+    __device__ __forceinline__ void batch_end() {
+        if (!full) return;
+        full = false;
+#pragma unroll
+        for (int t = 0; t < T; ++t) if (cnt[t] > LIMIT) flush(t);
+    }
+    // what is left in the buffers; the result belongs in the first half
+    __device__ __forceinline__ void end() {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            if (t >= tq) continue;
+            if (cnt[t] > 0) flush(t);
+            uint64_t *const A = lists0 + t * list_step;
+            if ((par >> t) & 1u) for (int j = lane; j < a.k; j += 64) A[j] = A[a.k + j];
+        }
+    }
+};
+
 template <int NCH, int METRIC>
 __global__ void __launch_bounds__(64 * SCAN_WAVES, scan_min_waves(NCH))
 hnsw_scan_kernel(const IndexView iv, const ScanArgs a) {
-#define SCAN_MASKED 0
-#include "hnsw_scan_slab.inc"
-#undef SCAN_MASKED
+    ScanTopK<NCH, false> sel(a, nullptr);
+    scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
 
 // ... restricted to the rows a mask allows (hnsw_search_batch_filtered's exact stage)
 template <int NCH, int METRIC>
 __global__ void __launch_bounds__(64 * SCAN_WAVES, scan_min_waves(NCH))
 hnsw_scan_masked_kernel(const IndexView iv, const ScanArgs a, const uint32_t *mask) {
-#define SCAN_MASKED 1
-#include "hnsw_scan_slab.inc"
-#undef SCAN_MASKED
+    ScanTopK<NCH, true> sel(a, mask);
+    scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
 
 // One workgroup per query.  lists: [nq][n_slabs][2][k], the first half of each the slab's k smallest words, ascending, padded.
@@ -155,24 +218,13 @@ namespace hnsw_host {
 using hnsw_dev::IndexView;
 using hnsw_dev::ScanArgs;
 
-hipError_t launch_scan(int metric, int nch, dim3 grid, const IndexView &iv, const ScanArgs &a, const uint32_t *mask, hipStream_t st) {
-    with_metric(metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {
-        if (mask) hipLaunchKernelGGL((hnsw_dev::hnsw_scan_masked_kernel<NCH, METRIC>), grid, dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a, mask);
-        else hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<NCH, METRIC>), grid, dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a);
-    }); });
-    return hipGetLastError();
+// the cut of an exact scan of m queries of this index (scan_plan) and the tile its kernels take; grid: a launch of nq <= piece queries
+ScanCut scan_cut(const hnsw_index *idx, int64_t m, int k, int64_t cell_bytes, int64_t cap) {
+    const int nch = pick_nch(idx->iv.nchunks), T = hnsw_dev::scan_tile(nch);
+    return {scan_plan(idx->iv.n, idx->scan_slabs, T, m, k, cell_bytes, cap), nch, T};
 }
-
-// How the table is cut for a launch of `tiles` query tiles: enough (tile, slab) waves to fill the chip twice over, slabs of 256
-// rows at least, no more lists per query than the merge reads quickly (slabs * k <= 65 536, 1024 slabs).  Option "scan_slabs"
-// overrides the count.  Results do not depend on it.
-int64_t scan_slab_rows(const hnsw_index *idx, int64_t tiles, int k) {
-    constexpr int64_t SCAN_TARGET_WAVES = 8192;
-    const int64_t n = idx->iv.n;
-    int64_t slabs = idx->scan_slabs > 0 ? idx->scan_slabs : (SCAN_TARGET_WAVES + tiles - 1) / tiles;
-    if (idx->scan_slabs <= 0) slabs = std::min(slabs, std::max<int64_t>(1, n / 256));
-    slabs = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(slabs, 1024), std::max<int64_t>(1, 65536 / k)));
-    return std::max<int64_t>(1, (n + slabs - 1) / slabs);
+dim3 ScanCut::grid(int64_t nq) const {
+    return dim3((unsigned)((nq + T - 1) / T), (unsigned)((slabs + hnsw_dev::SCAN_WAVES - 1) / hnsw_dev::SCAN_WAVES));
 }
 
 int check_scan(const hnsw_index *idx, int64_t nq, int64_t q_stride, int32_t k, int32_t fill, bool buffers) {
@@ -187,37 +239,28 @@ int check_scan(const hnsw_index *idx, int64_t nq, int64_t q_stride, int32_t k, i
     return HNSW_OK;
 }
 
-// the scan of b's queries on `st`: the queries in pieces whose lists fit SCAN_SCRATCH bytes of the handle's scratch
+// the scan of b's queries on `st`: the queries in pieces whose lists (two halves of k words per cell) fit SCAN_SCRATCH
 int scan_search(hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *mask) {
     int rc = check_scan(idx, b.nq, b.q_stride, k, fill, b.Q && b.ids && b.dist);
     if (rc || b.nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
-    constexpr int64_t SCAN_SCRATCH = 256ll << 20;
     const IndexView &iv = idx->iv;
-    const int nch = pick_nch(iv.nchunks), T = hnsw_dev::scan_tile(nch);
-    int64_t piece = std::min<int64_t>(b.nq, 16384);
-    int64_t slab_rows = 0, slabs = 0;
-    for (;;) {      // (a smaller piece has fewer tiles and may be cut into more slabs: settle on a piece that fits)
-        slab_rows = scan_slab_rows(idx, (piece + T - 1) / T, k);
-        slabs = iv.n > 0 ? (iv.n + slab_rows - 1) / slab_rows : 0;
-        const int64_t per_query = std::max<int64_t>(slabs, 1) * 2 * k * 8;
-        if (piece * per_query <= SCAN_SCRATCH || piece <= T) break;
-        piece = std::max<int64_t>(T, SCAN_SCRATCH / per_query / T * T);
-    }
-    if ((rc = idx->scratch.scan.ensure((size_t)(piece * std::max<int64_t>(slabs, 1) * 2 * k * 8)))) return rc;
-    for (int64_t q0 = 0; q0 < b.nq; q0 += piece) {
-        const int64_t nq = std::min(piece, b.nq - q0);
-        ScanArgs a{b.Q + q0 * b.q_stride, b.q_stride, nq, k, (int32_t)slabs, slab_rows, (uint64_t *)idx->scratch.scan.p};
-        if (slabs > 0) {
-            const dim3 grid((unsigned)((nq + T - 1) / T), (unsigned)((slabs + hnsw_dev::SCAN_WAVES - 1) / hnsw_dev::SCAN_WAVES));
-            const hipError_t e = launch_scan(idx->info.metric, nch, grid, iv, a, mask, st);
-            if (e != hipSuccess) return fail(HNSW_ERR_HIP, "scan kernel launch failed: %s", hipGetErrorString(e));
+    const ScanCut c = scan_cut(idx, b.nq, k, 2 * (int64_t)k * 8, 16384);
+    if ((rc = idx->scratch.scan.ensure((size_t)(c.piece * std::max<int64_t>(c.slabs, 1) * 2 * k * 8)))) return rc;
+    for (int64_t q0 = 0; q0 < b.nq; q0 += c.piece) {
+        const int64_t nq = std::min(c.piece, b.nq - q0);
+        ScanArgs a{b.Q + q0 * b.q_stride, b.q_stride, nq, k, (int32_t)c.slabs, c.slab_rows, (uint64_t *)idx->scratch.scan.p};
+        if (c.slabs > 0) {
+            with_metric(idx->info.metric, [&](auto METRIC) { with_nch(c.nch, [&](auto NCH) {
+                if (mask) hipLaunchKernelGGL((hnsw_dev::hnsw_scan_masked_kernel<NCH, METRIC>), c.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a, mask);
+                else hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<NCH, METRIC>), c.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a);
+            }); });
+            if ((rc = launched("scan kernel"))) return rc;
         }
         with_metric(idx->info.metric, [&](auto METRIC) {
             hipLaunchKernelGGL(hnsw_dev::hnsw_scan_merge_kernel<METRIC>, dim3((unsigned)nq), dim3(256), 0, st, a.lists, a.n_slabs, k, fill, iv.id_base, b.ids + q0 * k, b.dist + q0 * k);
         });
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(HNSW_ERR_HIP, "scan merge kernel launch failed: %s", hipGetErrorString(e));
+        if ((rc = launched("scan merge kernel"))) return rc;
     }
     return HNSW_OK;
 }

@@ -92,3 +92,15 @@ def test_dataset_route_without_device_is_unchanged():
         assert inspect.signature(f).parameters["device"].default is None
     ds = dataset.Dataset.random(8, 50, 5, 3, seed=2)
     np.testing.assert_array_equal(ds.test_distances.view(np.uint32), _brute_force_knn_l2_before(ds.train, ds.test, 3).view(np.uint32))
+
+
+def test_scan_plan_is_the_arithmetic_it_replaced(tmp_path):
+    """scan_plan (the cut of the k-scan and of the range scan into pieces and slabs) against the two loops it replaced, over a grid
+    of (n, m, k, scan_slabs): tests/cpp/test_scan_plan.cpp, a host program, under AddressSanitizer and UndefinedBehaviorSanitizer"""
+    import subprocess
+    exe = str(tmp_path / "test_scan_plan")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "cpp", "test_scan_plan.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    done = re.search(r"scan plan ok: (\d+) cases, 0 differ", out.stdout)
+    assert out.returncode == 0 and done and int(done.group(1)) > 0, out.stdout + out.stderr
