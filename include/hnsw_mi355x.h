@@ -34,6 +34,8 @@
  *                            the refine step of the half-row searches (option "refine")
  *   hnsw_search_batch_filtered  (nothing in the reference) the k nearest AMONG the nodes an allow-mask names (hnsw_filter_create):
  *                            several tenants, categories or time windows in one index; a mask of live nodes = soft deletes
+ *   hnsw_search_batch_filtered_each  ... with one filter per query: a mixed batch of many tenants in one call
+ *                            (hnsw_filter_create_by_label: the tenants' filters from one label per node)
  *   hnsw_range_search_batch  (nothing in the reference) EVERY node within a radius of the query, a result of variable length;
  *                            hnsw_range_brute_force_batch is its exact form
  *   hnsw_host_alloc / hnsw_host_register   (nothing in the reference) page-locked query / result matrices,
@@ -523,6 +525,46 @@ int32_t hnsw_filter_count(const hnsw_filter *f, int64_t *n_allowed);
 int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
                                    const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
                                    uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage);
+
+/* ---- one filter per query: a mixed batch of many tenants, categories or time windows in one call ------------------------------
+ * THE RESULT of hnsw_search_batch_filtered_each.  Query q is answered under filters[query_filter[q]] (query_filter: a host array
+ * of nq values in 0 .. n_filters - 1).  Row q of all five outputs is bit for bit the row a hnsw_search_batch_filtered call with
+ * filters[query_filter[q]] and the same params gives that query -- by point 6 (DETERMINISM) of that definition such a row depends on
+ * the query's own vector, its mask and (ef, k, semantics) only, so the result is fully defined by public calls.  Everything in
+ * points 1 - 6 holds per query, with "the filter" read as "the query's filter":
+ *   - A query whose filter allows fewer than k nodes (n_allowed < k) takes no walk and goes to the exact stage: out_stage
+ *     0xFFFFFFFF, out_nhops 0, out_ndist = that filter's n_allowed.  The other queries of the batch are not affected by it.
+ *   - LADDER.  At each stage, all queries still short, whatever their filters, are walked as ONE compacted batch in ascending
+ *     query order, by the same ladder: one launch over all of them per stage, not one per filter.
+ *   - EXACT STAGE.  out_ndist adds the n_allowed of the query's own filter.  One masked scan serves all filters: the queries left
+ *     are ordered by (filter index, query) and each filter's group is padded to whole tiles of the scan.
+ *   - ERRORS (outputs untouched, nothing walked, all checked on the host before any launch).  n_filters < 1, null `filters`, or
+ *     null `query_filter` with nq > 0: HNSW_ERR_BAD_ARG.  ANY entry of `filters` null, made for another handle, or outgrown by
+ *     hnsw_index_insert: HNSW_ERR_BAD_ARG, whether or not a query names it.  A query_filter value outside 0 .. n_filters - 1:
+ *     HNSW_ERR_BAD_ARG.  Everything else as hnsw_search_batch_filtered: k > ef, ef > 1024 (HNSW_ERR_UNSUPPORTED),
+ *     HNSW_SEM_FUNCTOR_NEAREST_K, an empty index (HNSW_ERR_EMPTY_INDEX), nq == 0 is a no-op (then query_filter may be null),
+ *     strides, null buffers.
+ *   - A handle may appear twice in `filters`.  There is no upper limit on n_filters beyond memory.
+ * Scratch and the rule "ONE filtered call in flight per handle, no range call beside it" are unchanged.  hnsw_search_batch_filtered
+ * is the case "table of one filter, no query_filter" of the same driver.
+ *
+ * FILTERS FROM LABELS.  hnsw_filter_create_by_label makes n_labels filters from one label per node (labels: a host array of n
+ * values, not retained): out[l] allows node v (0-based, whatever id_base is) iff labels[v] == l.  n must be the index's current n,
+ * n_labels >= 1, each label in -1 .. n_labels - 1, where -1 means the node is in no filter; any other value is HNSW_ERR_BAD_ARG,
+ * found on the host before anything is allocated.  All or nothing: on any error out[0 .. n_labels) are all NULL and nothing stays
+ * allocated.  On success every out[l] is an ordinary hnsw_filter: its own object, destroyed on its own with hnsw_filter_destroy,
+ * counted (hnsw_filter_count), accepted by both filtered entry points, bound to the handle and its n like any other.  A label no
+ * node carries gives a filter of count 0.  The labels are uploaded once and one pass over them on the device builds all masks and
+ * counts.  Cost: n_labels * ceil(n / 32) * 4 bytes on the device, NOT counted in hnsw_index_info.device_bytes.
+ *
+ * hnsw_filter_bits copies the mask of a filter made either way back to the host: ceil(n / 32) words in hnsw_filter_create's layout,
+ * the bits past n clear (for tests and for callers that persist masks).  Null arguments: HNSW_ERR_BAD_ARG. */
+int32_t hnsw_search_batch_filtered_each(hnsw_index *idx, const hnsw_filter *const *filters, int32_t n_filters,
+                                        const int32_t *query_filter, const float *queries, int64_t nq, int64_t q_stride,
+                                        const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
+                                        uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage);
+int32_t hnsw_filter_create_by_label(hnsw_index *idx, const int32_t *labels, int64_t n, int32_t n_labels, hnsw_filter **out);
+int32_t hnsw_filter_bits(const hnsw_filter *f, uint32_t *out);
 
 /* ---- range search: every stored vector within a radius of the query -----------------------------------------------------------
  * The other standard question of a vector index: not "the k nearest" but ALL nodes within distance `radius` (de-duplication,

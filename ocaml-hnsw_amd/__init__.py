@@ -60,6 +60,9 @@ _ABI = {
     "hnsw_filter_destroy": [_vp],
     "hnsw_filter_count": [_vp, _vp],
     "hnsw_search_batch_filtered": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_search_batch_filtered_each": [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_filter_create_by_label": [_vp, _vp, _i64, _i32, _vp],
+    "hnsw_filter_bits": [_vp, _vp],
     "hnsw_range_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp],
     "hnsw_range_brute_force_batch": [_vp, _vp, _i64, _i64, _f32, _vp],
     "hnsw_range_result_size": [_vp, _vp, _vp],
@@ -447,6 +450,24 @@ class Hgraph:
         v + id_base may be returned), or an array of node ids (id_base-based).  Valid until the index grows (insert_batch)."""
         return Filter(self, allow)
 
+    def filters_by_label(self, labels, n_labels=None):
+        """hnsw_filter_create_by_label -> [Filter] * n_labels: filter l allows node v (0-based position in `labels`, one integer per
+        node) iff labels[v] == l; a label of -1 puts the node in no filter.  n_labels defaults to max label + 1.  One upload of the
+        labels and one pass over them on the device, not n_labels host-built masks."""
+        lab = _np.asarray(labels)
+        if lab.dtype.kind not in "iu" or lab.ndim != 1:
+            raise InvalidArgument("labels must be a vector of integers, one per node")
+        if lab.size and (lab.min() < -(2 ** 31) or lab.max() >= 2 ** 31):
+            raise InvalidArgument("labels must fit 32 bits")
+        lab = _np.ascontiguousarray(lab, _np.int32)
+        if n_labels is None:
+            n_labels = int(lab.max()) + 1 if lab.size else 0
+        if n_labels < 1:
+            raise InvalidArgument("n_labels must be >= 1")
+        out = (_C.c_void_p * n_labels)()
+        _check(load().hnsw_filter_create_by_label(self.handle, _ptr(lab) if lab.size else None, lab.size, n_labels, out))
+        return [Filter._adopt(self, _C.c_void_p(out[l]), lab.size) for l in range(n_labels)]
+
     def kernel_times(self):
         """(search kernel ms, ordering pre-pass ms, calls) averaged over the device-entry calls since the
         last call (needs set_option("time_kernels", 1)); waits for them."""
@@ -543,6 +564,13 @@ class Filter:
         _check(load().hnsw_filter_create(hgraph.handle, _ptr(bits) if len(bits) else None, n, _C.byref(f)))
         self._f, self._hg, self.n = f, hgraph, n
 
+    @classmethod
+    def _adopt(cls, hgraph, f, n):
+        """a Filter around a handle the library made (hnsw_filter_create_by_label)"""
+        self = cls.__new__(cls)
+        self._f, self._hg, self.n = f, hgraph, n
+        return self
+
     @property
     def handle(self):
         if self._f is None:
@@ -554,6 +582,12 @@ class Filter:
         c = _C.c_int64(0)
         _check(load().hnsw_filter_count(self.handle, _C.byref(c)))
         return c.value
+
+    def bits(self):
+        """hnsw_filter_bits: the mask as the device holds it, in pack_allow's layout (uint32 [ceil(n / 32)], bits past n clear)"""
+        out = _np.zeros((self.n + 31) // 32, _np.uint32)
+        _check(load().hnsw_filter_bits(self.handle, _ptr(out) if len(out) else _C.byref(_C.c_uint32())))
+        return out
 
     def release(self):
         if self._f is not None:
@@ -583,6 +617,31 @@ def _search_filtered(hgraph, flt, batch, ef, k, fill, counters=False, sem=0, out
     finally:
         if own is not None:
             own.release()
+    return (ids, dist, nd, nh, stage) if counters else (ids, dist)
+
+
+def _search_filtered_each(hgraph, filters, which, batch, ef, k, fill, counters=False, sem=0, out=None):
+    """hnsw_search_batch_filtered_each; filters: a sequence of Filter, which: per query the position of its filter in it
+    -> (ids, dist), with counters (ids, dist, ndist, nhops, stage)."""
+    filters = list(filters)
+    for f in filters:
+        if not isinstance(f, Filter):
+            raise InvalidArgument("filters must be Filter objects (Hgraph.filter, Hgraph.filters_by_label)")
+    Q, qs, nq = _batch(hgraph.d, batch)
+    w = _np.asarray(which)
+    if w.shape != (nq,) or (nq and w.dtype.kind not in "iu"):
+        raise InvalidArgument("which must hold one filter position per query")
+    if nq and (w.min() < 0 or w.max() >= len(filters)):
+        raise InvalidArgument("which must name positions 0 .. %d of filters" % (len(filters) - 1))
+    w = _np.ascontiguousarray(w, _np.int32)
+    table = (_C.c_void_p * max(len(filters), 1))(*[f.handle for f in filters])
+    ids, dist = _out_pair(nq, k, out)
+    nd = _np.zeros(nq, _np.uint32) if counters else None
+    nh = _np.zeros(nq, _np.uint32) if counters else None
+    stage = _np.zeros(nq, _np.uint32) if counters else None
+    p = _SearchParams(ef, k, fill, sem)
+    _check(load().hnsw_search_batch_filtered_each(hgraph.handle, table, len(filters), _ptr(w) if nq else None, _ptr(Q), nq, qs, _C.byref(p),
+                                                  _ptr(ids), _ptr(dist), _ptr(nd), _ptr(nh), _ptr(stage)))
     return (ids, dist, nd, nh, stage) if counters else (ids, dist)
 
 
@@ -747,6 +806,14 @@ class Ohnsw:
         still short gets the exact scan over the allowed nodes (stage = STAGE_EXACT).  Distances are over the float32 vectors
         whatever rows the index searches; ids -1 / NaN where fewer than k nodes are allowed."""
         return _search_filtered(hgraph, allow, batch, k if ef is None else ef, k, FILL_OHNSW, counters, out=out)
+
+    @staticmethod
+    def knn_batch_filtered_each(hgraph, k, batch, filters, which, ef=None, counters=False, out=None):
+        """knn_batch_filtered with one filter per query (hnsw_search_batch_filtered_each): query q is answered under
+        filters[which[q]], and its row is the row knn_batch_filtered gives it under that filter.  filters: Filter objects
+        (Hgraph.filter, Hgraph.filters_by_label); which: one position in `filters` per query.  A mixed batch of many tenants is ONE
+        call: every ladder stage walks all queries still short in one launch, whatever their filters."""
+        return _search_filtered_each(hgraph, filters, which, batch, k if ef is None else ef, k, FILL_OHNSW, counters, out=out)
 
     @staticmethod
     def range_search(hgraph, radius, batch, ef=64, counters=False, keep=False):
@@ -924,6 +991,11 @@ class Ba:
         """knn_batch among the nodes `allow` names (see Ohnsw.knn_batch_filtered; the functor accept rule, 1-based ids in a
         1-based index, +inf / -1 where fewer than k nodes are allowed) -> (ids, distances), with counters (..., ndist, nhops, stage)."""
         return _search_filtered(hgraph, allow, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR)
+
+    @staticmethod
+    def knn_batch_filtered_each(hgraph, batch, num_neighbours_search, num_neighbours, filters, which, counters=False):
+        """knn_batch_filtered with one filter per query (see Ohnsw.knn_batch_filtered_each; the functor accept rule, +inf fill)."""
+        return _search_filtered_each(hgraph, filters, which, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR)
 
     @staticmethod
     def range_search(hgraph, batch, num_neighbours_search, radius, counters=False):

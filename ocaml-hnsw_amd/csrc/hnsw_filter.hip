@@ -1,21 +1,25 @@
-// hnsw_filter.hip -- filtered k-NN search: an allow-mask over the nodes (hnsw_filter_*) and hnsw_search_batch_filtered, which
-// composes pieces that exist already -- the unchanged walk (knn_search with k := ef: W stays on the device), the re-rank kernel
+// hnsw_filter.hip -- filtered k-NN search: an allow-mask over the nodes (hnsw_filter_*), hnsw_search_batch_filtered and its
+// one-filter-per-query form hnsw_search_batch_filtered_each (one driver: the first is the table of one filter), which compose pieces that exist already -- the unchanged walk (knn_search with k := ef: W stays on the device), the re-rank kernel
 // (hnsw_rerank.hip) and the exact scan (hnsw_scan.hip, its masked form) -- into the definition the header gives:
 //   ladder   e = ef, 2 ef, ... 1024: a query is served at the first e whose W holds k allowed nodes; only the queries still short
 //            are walked again, gathered into one compact batch;
-//   exact    a query still short at e = 1024, and every query when fewer than k nodes are allowed, gets the masked exact scan.
+//   exact    a query still short at e = 1024, and every query whose filter allows fewer than k nodes, gets the masked exact scan:
+//            one launch sequence for all filters, the queries ordered by (filter, query) and laid out so that no scan tile spans
+//            two filters (hnsw_filter_plan.h).
 // The ladder itself (Ladder: the walk of a stage, the short list, the gathered batch) is here too; the range search
 // (hnsw_range.hip) runs the same one with its own select rule.
 //
 // Kernels.
 //   filter_popcount_kernel  the uploaded mask: clears the bits past n in its last word and counts the rest.
-//   filter_select_kernel    one wave per walked query: tests the bit of each member of W, 64 entries per pass (ballot, prefix
+//   filter_label_kernel     hnsw_filter_create_by_label: all masks and their counts in one pass over the nodes' labels.
+//   filter_select_kernel    one wave per walked query: tests the bit of each member of W in the query's own mask, 64 entries per pass (ballot, prefix
 //                           count).  A query with k allowed members is SERVED: its first k allowed (id, distance) pairs go to its
 //                           output row (rows whose walk distances are exact over X: float32, bytes, split), or its W with the
 //                           disallowed entries turned into padding goes to the re-rank's candidate matrix (half, sq8).  Others
 //                           are appended to the short list (ladder_settle).
-//   ladder_gather_kernel    the short queries' vectors as one compact, zero-padded matrix: the next walk's / the exact stage's batch.
-//   filter_scatter_kernel   rows of a compact result (re-rank, scan) to the rows of the queries they belong to.
+//   ladder_gather_kernel    the short queries' vectors as one compact, zero-padded matrix: the next walk's / the exact stage's batch
+//                           (a padding row of the exact stage's layout: the zero vector).
+//   filter_scatter_kernel   rows of a compact result (re-rank, scan) to the rows of the queries they belong to; padding rows are dropped.
 // No LDS, vector stores only.  All scratch is the handle's (LadderBufs, FilterBufs): one filtered or range call in flight per handle.
 #include "hnsw_internal.h"
 
@@ -36,13 +40,38 @@ filter_popcount_kernel(uint32_t *bits, int64_t words, int64_t n, unsigned long l
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, (unsigned long long)c);
 }
 
+// One pass over the labels builds every label's mask and count: masks[l] (ceil(n / 32) words, zeroed before) gets bit v iff
+// labels[v] == l; a label of -1 is in no mask.  A wave takes 64 consecutive nodes, that is two whole words of every mask, and
+// loops over the distinct labels among them: the label of the first lane not yet done (readlane), the ballot of the lanes that
+// carry it -- its two halves are those two words of that label's mask, stored by lanes 0 and 32.  A (label, word) pair has one
+// writer, this wave, so the masks need no atomics; the counts take one atomicAdd per (wave, label).  Nodes >= n carry no label.
+__global__ void __launch_bounds__(256)
+filter_label_kernel(const int32_t *labels, int64_t n, int64_t words, uint32_t *const *masks, unsigned long long *counts) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t v = base + lane;
+        const int32_t lab = v < n ? labels[v] : -1;
+        uint64_t todo = ballot(lab >= 0);
+        while (todo) {
+            const int32_t l = __builtin_amdgcn_readlane(lab, (int)__builtin_ctzll(todo));
+            const uint64_t m = ballot(lab == l);
+            todo &= ~m;
+            const int64_t w = (base >> 5) + (lane >> 5);
+            const uint32_t half = (uint32_t)(m >> (lane & 32));
+            if ((lane & 31) == 0 && half && w < words) masks[l][w] = half;
+            if (lane == 0) atomicAdd(counts + l, (unsigned long long)popc(m));
+        }
+    }
+}
+
 struct SelectArgs {
     const int32_t *wids;       // [m][e] the walk's W per query, id_base-based, filled entries < id_base
     const float *wdist;        // [m][e]
     int64_t m;
     int32_t e, k;
     const int32_t *map;        // [m] row i belongs to query map[i]; null: to query i
-    const uint32_t *bits;      // the mask
+    const uint32_t *const *masks;  // the masks; query q's is masks[which[q]], masks[0] when which is null
+    const int32_t *which;      // [nq], by query (map's numbering), not by row
     int64_t n;
     int32_t id_base;
     int32_t *out_ids;          // [nq][k]
@@ -52,9 +81,9 @@ struct SelectArgs {
     LadderOut out;
 };
 
-__device__ __forceinline__ bool filter_allows(const SelectArgs &a, int32_t id) {
+__device__ __forceinline__ bool filter_allows(const SelectArgs &a, MaskWords bits, int32_t id) {
     const int64_t v = (int64_t)id - a.id_base;
-    return v >= 0 && v < a.n && ((a.bits[v >> 5] >> (v & 31)) & 1u);
+    return v >= 0 && v < a.n && ((bits[v >> 5] >> (v & 31)) & 1u);
 }
 
 __global__ void __launch_bounds__(64)
@@ -63,24 +92,25 @@ filter_select_kernel(const SelectArgs a) {
     const int64_t i = blockIdx.x;
     if (i >= a.m) return;
     const int64_t q = a.map ? a.map[i] : i;
+    const MaskWords bits = mask_words(a.masks[a.which ? a.which[q] : 0]);
     const int32_t *const wi = a.wids + i * a.e;
     int cnt = 0;
     for (int j0 = 0; j0 < a.e; j0 += 64) {
         const int j = j0 + lane;
-        cnt += popc(ballot(j < a.e && filter_allows(a, wi[j])));
+        cnt += popc(ballot(j < a.e && filter_allows(a, bits, wi[j])));
     }
     const bool served = cnt >= a.k;
     if (a.cand) {               // W with everything but a served query's allowed members as padding
         for (int j = lane; j < a.e; j += 64) {
             const int32_t id = wi[j];
-            a.cand[i * a.e + j] = served && filter_allows(a, id) ? id : a.id_base - 1;
+            a.cand[i * a.e + j] = served && filter_allows(a, bits, id) ? id : a.id_base - 1;
         }
     } else if (served) {        // the first k allowed members, in W's order
         int at = 0;
         for (int j0 = 0; j0 < a.e && at < a.k; j0 += 64) {
             const int j = j0 + lane;
             const int32_t id = j < a.e ? wi[j] : a.id_base - 1;
-            const bool ok = j < a.e && filter_allows(a, id);
+            const bool ok = j < a.e && filter_allows(a, bits, id);
             const uint64_t m = ballot(ok);
             const int pos = at + popc(m & ((1ull << lane) - 1ull));
             if (ok && pos < a.k) {
@@ -96,13 +126,14 @@ filter_select_kernel(const SelectArgs a) {
     }
 }
 
-// out[i] = Q[list[i]], rows of out_stride floats, zero beyond d
+// out[i] = Q[list[i]], rows of out_stride floats, zero beyond d; list[i] < 0 (a padding row): all zero
 __global__ void __launch_bounds__(64)
 ladder_gather_kernel(const float *Q, int64_t q_stride, int32_t d, const int32_t *list, int64_t m, float *out, int64_t out_stride) {
     const int64_t i = blockIdx.x;
     if (i >= m) return;
-    const float *qp = Q + (int64_t)list[i] * q_stride;
-    for (int64_t c = threadIdx.x; c < out_stride; c += 64) out[i * out_stride + c] = c < d ? qp[c] : 0.f;
+    const int64_t q = list[i];
+    const float *qp = Q + (q < 0 ? 0 : q) * q_stride;
+    for (int64_t c = threadIdx.x; c < out_stride; c += 64) out[i * out_stride + c] = q >= 0 && c < d ? qp[c] : 0.f;
 }
 
 struct ScatterArgs {
@@ -110,10 +141,11 @@ struct ScatterArgs {
     const float *rdist;
     int64_t m;
     int32_t k;
-    const int32_t *map;        // [m] row i belongs to query map[i]; null: to query i
+    const int32_t *map;        // [m] row i belongs to query map[i] (< 0: a padding row, dropped); null: to query i
     const int32_t *cnt;        // null: every row; else only the rows with cnt[i] >= k (the served ones)
     const uint32_t *add;       // null, or [m]: evaluations to add to out_nd
     uint32_t add_const;        // ... plus this many
+    const int32_t *fresh_of;   // null, or [m]: `fresh` per row
     int32_t fresh;             // 1: the query took no walk: out_nd starts from 0 and out_nh is 0
     int32_t set_stage;         // 1: out_stage[q] = stage
     uint32_t stage;
@@ -127,13 +159,15 @@ filter_scatter_kernel(const ScatterArgs a) {
     const int64_t i = blockIdx.x;
     if (i >= a.m || (a.cnt && a.cnt[i] < a.k)) return;
     const int64_t q = a.map ? a.map[i] : i;
+    if (q < 0) return;
     for (int j = threadIdx.x; j < a.k; j += 64) {
         a.out_ids[q * a.k + j] = a.rids[i * a.k + j];
         a.out_dist[q * a.k + j] = a.rdist[i * a.k + j];
     }
     if (threadIdx.x == 0) {
-        a.out_nd[q] = (a.fresh ? 0u : a.out_nd[q]) + (a.add ? a.add[i] : 0u) + a.add_const;
-        if (a.fresh) a.out_nh[q] = 0u;
+        const bool fresh = a.fresh_of ? a.fresh_of[i] != 0 : a.fresh != 0;
+        a.out_nd[q] = (fresh ? 0u : a.out_nd[q]) + (a.add ? a.add[i] : 0u) + a.add_const;
+        if (fresh) a.out_nh[q] = 0u;
         if (a.set_stage) a.out_stage[q] = a.stage;
     }
 }
@@ -154,7 +188,8 @@ int Ladder::walk(int32_t *wids, float *wdist, int32_t fill) {
     const hnsw_search_params wp{e, e, fill, semantics};
     wb = KnnBatch{Qj, m, qs, wids, wdist, (uint32_t *)lb.wnd.p, (uint32_t *)lb.wnh.p, (uint32_t *)lb.wst.p, idx->hFlagDev};
     *(volatile uint32_t *)idx->hFlag = 0;
-    if ((rc = knn_search(idx, &wp, wb, st, stage == 0 ? d_stage : nullptr, nullptr, true))) return rc;
+    // (d_stage: only the caller's own matrix can lie in host memory, never a gathered batch)
+    if ((rc = knn_search(idx, &wp, wb, st, map ? nullptr : d_stage, nullptr, true))) return rc;
     if ((rc = synced(st, what))) return rc;
     if ((*(volatile uint32_t *)idx->hFlag & 1u) && (rc = knn_repair(idx, &wp, wb, st, nullptr, true))) return rc;
     HIP_TRY(hipMemsetAsync(lb.count.p, 0, 4, st));
@@ -171,9 +206,30 @@ int Ladder::count_short() {
     return synced(st, what);
 }
 
-int Ladder::advance(bool &more) {
+int Ladder::gather() {
     LadderBufs &lb = idx->ladder_scratch;
     const int64_t pad = padded_stride(idx->iv.d);
+    int rc;
+    if ((rc = lb.q.ensure((size_t)m * pad * sizeof(float)))) return rc;
+    hipLaunchKernelGGL(hnsw_dev::ladder_gather_kernel, dim3((unsigned)m), dim3(64), 0, st, Q, q_stride, idx->iv.d, map, m, (float *)lb.q.p, pad);
+    if ((rc = launched("ladder gather kernel"))) return rc;
+    Qj = (const float *)lb.q.p;
+    qs = pad;
+    return HNSW_OK;
+}
+
+int Ladder::start_from(const int32_t *list, int64_t count) {
+    LadderBufs &lb = idx->ladder_scratch;
+    int rc;
+    if ((rc = lb.list[0].ensure((size_t)nq * 4)) || (rc = lb.list[1].ensure((size_t)nq * 4))) return rc;
+    HIP_TRY(hipMemcpy(lb.list[cur].p, list, (size_t)count * 4, hipMemcpyHostToDevice));
+    map = (const int32_t *)lb.list[cur].p;
+    m = count;
+    return gather();
+}
+
+int Ladder::advance(bool &more) {
+    LadderBufs &lb = idx->ladder_scratch;
     int rc;
     shorts.resize(n_short);
     HIP_TRY(hipMemcpy(shorts.data(), lb.list[cur ^ 1].p, (size_t)n_short * 4, hipMemcpyDeviceToHost));
@@ -182,11 +238,7 @@ int Ladder::advance(bool &more) {
     cur ^= 1;
     map = (const int32_t *)lb.list[cur].p;
     m = n_short;
-    if ((rc = lb.q.ensure((size_t)m * pad * sizeof(float)))) return rc;
-    hipLaunchKernelGGL(hnsw_dev::ladder_gather_kernel, dim3((unsigned)m), dim3(64), 0, st, Q, q_stride, idx->iv.d, map, m, (float *)lb.q.p, pad);
-    if ((rc = launched("ladder gather kernel"))) return rc;
-    Qj = (const float *)lb.q.p;
-    qs = pad;
+    if ((rc = gather())) return rc;
     more = e < 1024;                    // else: still short with the largest W the library walks
     e = std::min(1024, 2 * e);
     ++stage;
@@ -197,8 +249,64 @@ int Ladder::advance(bool &more) {
 
 namespace {
 
+// The filters of one call: a table of n filters and, per query, which of them it is answered under (host: which, device: d_which;
+// both null: every query under filters[0], the single-filter call).  d_masks: the masks' device addresses [n].
+struct FilterSet {
+    const hnsw_filter *const *filters;
+    int32_t n;
+    const int32_t *which;
+    const uint32_t *const *d_masks;
+    const int32_t *d_which;
+    int32_t index_of(int64_t q) const { return which ? which[q] : 0; }
+    const hnsw_filter &of(int64_t q) const { return *filters[index_of(q)]; }
+};
+
+// The exact stage for the queries of `rest` (short at the ladder's end) and of `fresh` (no walk: their filters allow fewer than k
+// nodes), whatever their filters: the rows by (filter, query) with no tile of the scan spanning two filters (filter_plan), gathered
+// from the caller's batch, ONE masked scan, and the rows back to their queries.
+int exact_stage_each(hnsw_index *idx, const FilterSet &fs, const hnsw_search_params &p, const KnnBatch &b, const std::vector<int32_t> &rest,
+                     const std::vector<int32_t> &fresh, uint32_t *d_stage_out, hipStream_t st) {
+    FilterBufs &fb = idx->filter_scratch;
+    LadderBufs &lb = idx->ladder_scratch;
+    const int k = p.k, T = scan_cut(idx, 1, k, 2 * (int64_t)k * 8, 16384).T;      // (the tile of the scan's kernels)
+    std::vector<std::pair<int32_t, int32_t>> pairs;
+    pairs.reserve(rest.size() + fresh.size());
+    for (const std::vector<int32_t> *list : {&rest, &fresh})
+        for (int32_t q : *list) pairs.emplace_back(fs.index_of(q), q);
+    const FilterRows rows = filter_plan(std::move(pairs), T);
+    const int64_t R = (int64_t)rows.row_query.size(), tiles = (int64_t)rows.tile_filter.size();
+    // one upload: row -> query, tile -> filter, per row the evaluations to add (its filter's n_allowed) and whether it took no walk
+    std::vector<int32_t> up((size_t)(3 * R + tiles), 0);
+    std::vector<char> is_fresh((size_t)b.nq, 0);
+    for (int32_t q : fresh) is_fresh[(size_t)q] = 1;
+    for (int64_t i = 0; i < R; ++i) {
+        const int32_t q = rows.row_query[(size_t)i];
+        up[(size_t)i] = q;
+        if (q < 0) continue;
+        up[(size_t)(R + i)] = (int32_t)(uint32_t)fs.of(q).n_allowed;
+        up[(size_t)(2 * R + i)] = is_fresh[(size_t)q];
+    }
+    std::copy(rows.tile_filter.begin(), rows.tile_filter.end(), up.begin() + 3 * R);
+    const int64_t pad = padded_stride(idx->iv.d);
+    int rc;
+    if ((rc = fb.rows.ensure(up.size() * 4)) || (rc = lb.q.ensure((size_t)R * pad * sizeof(float))) || (rc = fb.rids.ensure((size_t)R * k * 4)) ||
+        (rc = fb.rdist.ensure((size_t)R * k * 4)))
+        return rc;
+    HIP_TRY(hipMemcpy(fb.rows.p, up.data(), up.size() * 4, hipMemcpyHostToDevice));
+    const int32_t *const d_rows = (const int32_t *)fb.rows.p;
+    hipLaunchKernelGGL(hnsw_dev::ladder_gather_kernel, dim3((unsigned)R), dim3(64), 0, st, b.Q, b.q_stride, idx->iv.d, d_rows, R, (float *)lb.q.p, pad);
+    if ((rc = launched("ladder gather kernel"))) return rc;
+    if ((rc = scan_search(idx, {(const float *)lb.q.p, R, pad, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr, nullptr, nullptr, nullptr}, k, p.fill, st,
+                          fs.d_masks, d_rows + 3 * R, d_rows)))
+        return rc;
+    const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, R, k, d_rows, nullptr, (const uint32_t *)(d_rows + R), 0u,
+                                   d_rows + 2 * R, 0, 1, 0xFFFFFFFFu, b.ids, b.dist, b.nd, b.nh, d_stage_out};
+    hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)R), dim3(64), 0, st, sc);
+    return launched("filter scatter kernel");
+}
+
 // The ladder and the exact stage for a batch HostCall::begin has placed (c.b): the results are in c.b's rows and fb.stage on return.
-int filtered_search(hnsw_index *idx, const hnsw_filter *f, const hnsw_search_params &p, const KnnBatch &b, float *d_stage, hipStream_t st) {
+int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_params &p, const KnnBatch &b, float *d_stage, hipStream_t st) {
     FilterBufs &fb = idx->filter_scratch;
     const int k = p.k;
     const bool rerank = walk_is_inexact(idx);
@@ -208,7 +316,13 @@ int filtered_search(hnsw_index *idx, const hnsw_filter *f, const hnsw_search_par
         return rc;
     uint32_t *const d_stage_out = (uint32_t *)fb.stage.p;
     Ladder L(idx, b.Q, b.nq, b.q_stride, p.ef, p.semantics, d_stage, st, "filtered search");
-    const bool walked = f->n_allowed >= k;
+    // who walks: the queries whose filter allows k nodes.  Everybody (the common case, and either all or none of a single-filter
+    // call): stage 0 is the caller's batch in place; some: stage 0 starts from their list, the others wait for the exact stage
+    std::vector<int32_t> walkers, fresh;
+    if (fs.which) for (int64_t q = 0; q < b.nq; ++q) (fs.of(q).n_allowed >= k ? walkers : fresh).push_back((int32_t)q);
+    const bool walked = fs.which ? !walkers.empty() : fs.filters[0]->n_allowed >= k;
+    if (walked && !fresh.empty() && (rc = L.start_from(walkers.data(), (int64_t)walkers.size()))) return rc;
+    bool short_at_end = false;
     for (bool more = walked; more;) {
         const int64_t m = L.m;
         const int e = L.e;
@@ -216,7 +330,7 @@ int filtered_search(hnsw_index *idx, const hnsw_filter *f, const hnsw_search_par
             (rerank && (rc = fb.cand.ensure((size_t)m * e * 4))))
             return rc;
         if ((rc = L.walk((int32_t *)fb.wids.p, (float *)fb.wdist.p, p.fill))) return rc;
-        const hnsw_dev::SelectArgs sa{L.wb.ids, L.wb.dist, m, e, k, L.map, (const uint32_t *)f->bits.p, f->n, idx->iv.id_base, b.ids, b.dist,
+        const hnsw_dev::SelectArgs sa{L.wb.ids, L.wb.dist, m, e, k, L.map, fs.d_masks, fs.d_which, idx->iv.n, idx->iv.id_base, b.ids, b.dist,
                                       rerank ? (int32_t *)fb.cand.p : nullptr, (int32_t *)fb.cnt.p, L.out(L.wb.nd, b.nd, b.nh, d_stage_out)};
         hipLaunchKernelGGL(hnsw_dev::filter_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
         if ((rc = launched("filter select kernel")) || (rc = L.count_short())) return rc;
@@ -226,22 +340,70 @@ int filtered_search(hnsw_index *idx, const hnsw_filter *f, const hnsw_search_par
                                     (uint32_t *)fb.rnd.p, st)))
                 return rc;
             const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, m, k, L.map, (const int32_t *)fb.cnt.p,
-                                           (const uint32_t *)fb.rnd.p, 0u, 0, 0, 0u, b.ids, b.dist, b.nd, b.nh, d_stage_out};
+                                           (const uint32_t *)fb.rnd.p, 0u, nullptr, 0, 0, 0u, b.ids, b.dist, b.nd, b.nh, d_stage_out};
             hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)m), dim3(64), 0, st, sc);
             // (waited for here: a failure of theirs is this stage's, not the next walk's)
             if ((rc = launched("filter scatter kernel")) || (rc = synced(st, "filtered search"))) return rc;
         }
-        if (L.n_short == 0) return HNSW_OK;
+        if (L.n_short == 0) break;
         if ((rc = L.advance(more))) return rc;
+        short_at_end = !more;
     }
-    // the exact stage: the k smallest allowed nodes under (distance, id) for the L.m queries of (L.Qj, L.map)
-    if ((rc = scan_search(idx, {L.Qj, L.m, L.qs, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr, nullptr, nullptr, nullptr}, k, p.fill, st,
-                          (const uint32_t *)f->bits.p)))
+    if (walked && !short_at_end && fresh.empty()) return HNSW_OK;
+    if (fs.which) return exact_stage_each(idx, fs, p, b, short_at_end ? L.batch_queries() : std::vector<int32_t>(), fresh, d_stage_out, st);
+    // the exact stage under one filter: the k smallest allowed nodes under (distance, id) for the L.m queries of (L.Qj, L.map) -- the
+    // ladder's last batch, or the caller's own when nobody walked --, which need no other layout
+    const hnsw_filter *const f = fs.filters[0];
+    if ((rc = scan_search(idx, {L.Qj, L.m, L.qs, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr, nullptr, nullptr, nullptr}, k, p.fill, st, fs.d_masks)))
         return rc;
     const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, L.m, k, L.map, nullptr, nullptr, (uint32_t)f->n_allowed,
-                                   !walked, 1, 0xFFFFFFFFu, b.ids, b.dist, b.nd, b.nh, d_stage_out};
+                                   nullptr, !walked, 1, 0xFFFFFFFFu, b.ids, b.dist, b.nd, b.nh, d_stage_out};
     hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)L.m), dim3(64), 0, st, sc);
     return launched("filter scatter kernel");
+}
+
+// what both search entry points check of one filter of the call
+int check_filter(const hnsw_index *idx, const hnsw_filter *f) {
+    if (!f) return fail(HNSW_ERR_BAD_ARG, "null filter");
+    if (f->idx != idx) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another index");
+    if (f->n != idx->iv.n)
+        return fail(HNSW_ERR_BAD_ARG, "the filter was made for %lld nodes, the index has grown to %lld", (long long)f->n, (long long)idx->iv.n);
+    return HNSW_OK;
+}
+
+// both search entry points once their arguments are checked (nq > 0).  fs.d_masks / fs.d_which are allocated; host_masks (the
+// per-query form): what they hold is still to be uploaded, from there and from fs.which, on the call's stream
+int filtered_call(hnsw_index *idx, const FilterSet &fs, const uint32_t *const *host_masks, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
+                  int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage) {
+    HostCall c;
+    bool q_in_place = false;
+    int rc;
+    if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
+    hipStream_t st = idx->hs[0];
+    // (from here on copies are queued that read the caller's arrays: no return without a synchronisation)
+    if (host_masks) {
+        hipError_t e = hipMemcpyAsync(const_cast<uint32_t **>(fs.d_masks), host_masks, (size_t)fs.n * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(const_cast<int32_t *>(fs.d_which), fs.which, (size_t)nq * 4, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) rc = hip_fail(e, "filter table upload");
+    }
+    if (!rc) rc = filtered_search(idx, fs, *params, c.b, q_in_place ? (float *)idx->scratch.q.p : nullptr, st);
+    if (!rc && out_stage && hipMemcpyAsync(out_stage, idx->filter_scratch.stage.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = fail(HNSW_ERR_HIP, "stage download failed");
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    return c.finish(idx, "filtered search", st);
+}
+
+// a filter of idx's n nodes with its mask allocated (not initialised) and the mask's own address behind it
+int new_filter(hnsw_index *idx, std::unique_ptr<hnsw_filter> &f) {
+    f.reset(new hnsw_filter());
+    f->idx = idx;
+    f->n = idx->iv.n;
+    const size_t off = hnsw_filter::table_offset(f->n);
+    int rc;
+    if ((rc = f->bits.ensure(off + 8))) return rc;
+    const void *self = f->bits.p;
+    HIP_TRY(hipMemcpy((char *)f->bits.p + off, &self, 8, hipMemcpyHostToDevice));
+    return HNSW_OK;
 }
 
 } // namespace
@@ -255,12 +417,10 @@ int32_t hnsw_filter_create(hnsw_index *idx, const uint32_t *bits, int64_t n_bits
     if (n_bits != idx->iv.n) return fail(HNSW_ERR_BAD_ARG, "the filter has %lld bits, the index %lld nodes", (long long)n_bits, (long long)idx->iv.n);
     if (n_bits > 0 && !bits) return fail(HNSW_ERR_BAD_ARG, "null bits");
     HIP_TRY(hipSetDevice(idx->device));
-    std::unique_ptr<hnsw_filter> f(new hnsw_filter());
-    f->idx = idx;
-    f->n = n_bits;
-    const int64_t words = (n_bits + 31) / 32;
+    std::unique_ptr<hnsw_filter> f;
     int rc;
-    if ((rc = f->bits.ensure((size_t)std::max<int64_t>(words, 1) * 4))) return rc;
+    if ((rc = new_filter(idx, f))) return rc;
+    const int64_t words = (n_bits + 31) / 32;
     if (words > 0) {
         DevBuf count;
         if ((rc = count.ensure(8))) return rc;
@@ -275,6 +435,54 @@ int32_t hnsw_filter_create(hnsw_index *idx, const uint32_t *bits, int64_t n_bits
         f->n_allowed = (int64_t)c;
     }
     *out = f.release();
+    return HNSW_OK;
+}
+
+int32_t hnsw_filter_create_by_label(hnsw_index *idx, const int32_t *labels, int64_t n, int32_t n_labels, hnsw_filter **out) {
+    if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
+    if (n_labels < 1) return fail(HNSW_ERR_BAD_ARG, "n_labels must be >= 1 (n_labels=%d)", n_labels);
+    for (int32_t l = 0; l < n_labels; ++l) out[l] = nullptr;
+    if (!idx) return fail(HNSW_ERR_BAD_ARG, "null index");
+    if (n != idx->iv.n) return fail(HNSW_ERR_BAD_ARG, "%lld labels, the index has %lld nodes", (long long)n, (long long)idx->iv.n);
+    if (n > 0 && !labels) return fail(HNSW_ERR_BAD_ARG, "null labels");
+    for (int64_t v = 0; v < n; ++v)
+        if (labels[v] < -1 || labels[v] >= n_labels)
+            return fail(HNSW_ERR_BAD_ARG, "label %d of node %lld is outside -1 .. %d", labels[v], (long long)v, n_labels - 1);
+    HIP_TRY(hipSetDevice(idx->device));
+    // (owners until the end: any return before it frees them all)
+    std::vector<std::unique_ptr<hnsw_filter>> fs((size_t)n_labels);
+    std::vector<uint32_t *> masks((size_t)n_labels);
+    const int64_t words = (n + 31) / 32;
+    int rc;
+    for (int32_t l = 0; l < n_labels; ++l) {
+        if ((rc = new_filter(idx, fs[(size_t)l]))) return rc;
+        masks[(size_t)l] = (uint32_t *)fs[(size_t)l]->bits.p;
+        if (words > 0) HIP_TRY(hipMemsetAsync(masks[(size_t)l], 0, (size_t)words * 4, nullptr));
+    }
+    if (n > 0) {
+        DevBuf d_labels, d_masks, d_counts;
+        if ((rc = d_labels.ensure((size_t)n * 4)) || (rc = d_masks.ensure((size_t)n_labels * 8)) || (rc = d_counts.ensure((size_t)n_labels * 8))) return rc;
+        HIP_TRY(hipMemcpy(d_labels.p, labels, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_masks.p, masks.data(), (size_t)n_labels * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(d_counts.p, 0, (size_t)n_labels * 8));
+        const unsigned blocks = (unsigned)std::min<int64_t>(4096, (n + 255) / 256);
+        hipLaunchKernelGGL(hnsw_dev::filter_label_kernel, dim3(blocks), dim3(256), 0, nullptr, (const int32_t *)d_labels.p, n, words,
+                           (uint32_t *const *)d_masks.p, (unsigned long long *)d_counts.p);
+        if ((rc = launched("filter label kernel"))) return rc;
+        std::vector<unsigned long long> counts((size_t)n_labels);
+        HIP_TRY(hipMemcpy(counts.data(), d_counts.p, (size_t)n_labels * 8, hipMemcpyDeviceToHost));
+        for (int32_t l = 0; l < n_labels; ++l) fs[(size_t)l]->n_allowed = (int64_t)counts[(size_t)l];
+    }
+    for (int32_t l = 0; l < n_labels; ++l) out[l] = fs[(size_t)l].release();
+    return HNSW_OK;
+}
+
+int32_t hnsw_filter_bits(const hnsw_filter *f, uint32_t *out) {
+    if (!f || !out) return fail(HNSW_ERR_BAD_ARG, "null filter or null out");
+    const int64_t words = (f->n + 31) / 32;
+    if (words == 0) return HNSW_OK;
+    HIP_TRY(hipSetDevice(f->idx->device));
+    HIP_TRY(hipMemcpy(out, f->bits.p, (size_t)words * 4, hipMemcpyDeviceToHost));
     return HNSW_OK;
 }
 
@@ -297,21 +505,37 @@ int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const 
     if (rc) return rc;
     if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
         return fail(HNSW_ERR_BAD_ARG, "the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no filtered meaning");
-    if (!f) return fail(HNSW_ERR_BAD_ARG, "null filter");
-    if (f->idx != idx) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another index");
-    if (f->n != idx->iv.n)
-        return fail(HNSW_ERR_BAD_ARG, "the filter was made for %lld nodes, the index has grown to %lld", (long long)f->n, (long long)idx->iv.n);
+    if ((rc = check_filter(idx, f))) return rc;
     if (nq == 0) return HNSW_OK;
     HIP_TRY(hipSetDevice(idx->device));
-    HostCall c;
-    bool q_in_place = false;
-    if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
-    hipStream_t st = idx->hs[0];
-    rc = filtered_search(idx, f, *params, c.b, q_in_place ? (float *)idx->scratch.q.p : nullptr, st);
-    if (!rc && out_stage && hipMemcpyAsync(out_stage, idx->filter_scratch.stage.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(HNSW_ERR_HIP, "stage download failed");
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    return c.finish(idx, "filtered search", st);
+    // the table of one filter: the mask's own address, on the device since the filter was made
+    return filtered_call(idx, FilterSet{&f, 1, nullptr, f->table(), nullptr}, nullptr, queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops,
+                         out_stage);
+}
+
+int32_t hnsw_search_batch_filtered_each(hnsw_index *idx, const hnsw_filter *const *filters, int32_t n_filters, const int32_t *query_filter,
+                                        const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params, int32_t *out_ids,
+                                        float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage) {
+    int rc = check_batch(idx, params, nq, q_stride, queries && out_ids && out_dist);
+    if (rc) return rc;
+    if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
+        return fail(HNSW_ERR_BAD_ARG, "the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no filtered meaning");
+    if (n_filters < 1) return fail(HNSW_ERR_BAD_ARG, "n_filters must be >= 1 (n_filters=%d)", n_filters);
+    if (!filters) return fail(HNSW_ERR_BAD_ARG, "null filters");
+    for (int32_t l = 0; l < n_filters; ++l)
+        if ((rc = check_filter(idx, filters[l]))) return rc;
+    if (nq == 0) return HNSW_OK;
+    if (!query_filter) return fail(HNSW_ERR_BAD_ARG, "null query_filter");
+    for (int64_t q = 0; q < nq; ++q)
+        if (query_filter[q] < 0 || query_filter[q] >= n_filters)
+            return fail(HNSW_ERR_BAD_ARG, "query_filter[%lld] = %d is outside 0 .. %d", (long long)q, query_filter[q], n_filters - 1);
+    HIP_TRY(hipSetDevice(idx->device));
+    FilterBufs &fb = idx->filter_scratch;
+    std::vector<const uint32_t *> masks((size_t)n_filters);
+    for (int32_t l = 0; l < n_filters; ++l) masks[(size_t)l] = (const uint32_t *)filters[l]->bits.p;
+    if ((rc = fb.masks.ensure((size_t)n_filters * 8)) || (rc = fb.which.ensure((size_t)nq * 4))) return rc;
+    return filtered_call(idx, FilterSet{filters, n_filters, query_filter, (const uint32_t *const *)fb.masks.p, (const int32_t *)fb.which.p}, masks.data(),
+                         queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, out_stage);
 }
 
 } // extern "C"

@@ -3,6 +3,7 @@
 #include "../../include/hnsw_mi355x.h"
 #include "hnsw_device.hip.h"
 #include "hnsw_scan_plan.h"
+#include "hnsw_filter_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -225,6 +226,9 @@ struct FilterBufs {
     DevBuf cnt, cand;                    // per walked query its allowed members of W; half / sq8 rows: the masked W the re-rank reads
     DevBuf rids, rdist, rnd;             // a compact [m][k] result (re-rank, exact scan) before its rows go to their queries
     DevBuf stage;                        // out_stage [nq]
+    // hnsw_search_batch_filtered_each: the masks' device addresses [n_filters], query_filter [nq]; the exact stage's rows
+    // (filter_plan): row -> query, tile -> filter, and per row the evaluations to add and whether the query took no walk
+    DevBuf masks, which, rows;
 };
 // ... of the range calls.  What a caller keeps (lims, ids, distances, counters) belongs to the hnsw_range_result instead.
 constexpr int RANGE_STAGES = 11;         // the longest ladder: ef = 1, 2, 4, ... 1024
@@ -366,10 +370,20 @@ struct hnsw_filter {
     const hnsw_index *idx = nullptr;     // the handle it was made for ...
     int64_t n = 0;                       // ... and that handle's n then: a grown index refuses it
     int64_t n_allowed = 0;               // set bits below n (filter_popcount_kernel)
-    hnsw_host::DevBuf bits;              // ceil(n / 32) words, the positions >= n of the last one clear
+    // ceil(n / 32) words, the positions >= n of the last one clear; behind them (8-byte aligned) the mask's own device address:
+    // the table of one filter that the single-filter call hands the kernels
+    hnsw_host::DevBuf bits;
+    static size_t table_offset(int64_t n) { return ((size_t)std::max<int64_t>((n + 31) / 32, 1) * 4 + 7) / 8 * 8; }
+    const uint32_t *const *table() const { return (const uint32_t *const *)((const char *)bits.p + table_offset(n)); }
 };
 
 namespace hnsw_dev {
+
+// A mask's words as a kernel reads them once it has taken the mask's address out of a table of masks: a pointer loaded from memory
+// is a generic one to the compiler (flat loads, no scalar loads); every mask lies in device memory, and saying so keeps the loads
+// what they were when the mask was a kernel argument.
+using MaskWords = const __attribute__((address_space(1))) uint32_t *;
+__device__ __forceinline__ MaskWords mask_words(const uint32_t *p) { return (MaskWords)p; }
 
 // The end of a ladder stage's select kernel (filter_select_kernel, range_select_kernel), one lane per walked query: row i of the
 // stage's batch belongs to query q.  Its walk's counters go to the query's; served, it gets the stage's number, else a place in
@@ -486,9 +500,13 @@ int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b
 // (optional): nd_out[q] = (nd_in ? nd_in[q] : 0) + the number of candidates evaluated
 int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, const int32_t *cand, int32_t cand_stride, int32_t k,
                   int32_t fill, int32_t *out_ids, float *out_dist, const uint32_t *nd_in, uint32_t *nd_out, hipStream_t st);
-// hnsw_scan.hip: the exact scan of b's queries on `st` into b.ids / b.dist (hnsw_brute_force_batch_device, with its checks); mask
-// (optional, ceil(n / 32) device words): only the rows whose bit is set are candidates
-int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *mask = nullptr);
+// hnsw_scan.hip: the exact scan of b's queries on `st` into b.ids / b.dist (hnsw_brute_force_batch_device, with its checks).  masks
+// (optional, a device table of masks of ceil(n / 32) device words each): only the rows whose bit is set are candidates, in the mask
+// of the query's tile -- masks[tile_filter[t]] for the t-th tile of scan_tile(NCH) queries (tile_filter: device, one entry per
+// tile), masks[0] for every tile when tile_filter is null.  row_query (optional, device, [b.nq]): rows whose entry is negative are
+// padding of the caller's layout; their rows of b.ids / b.dist are left unwritten.
+int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *const *masks = nullptr,
+                const int32_t *tile_filter = nullptr, const int32_t *row_query = nullptr);
 // hnsw_scan.hip: how an exact scan of m queries of this index is cut (scan_plan: k for the slab rule, bytes per (query, slab)
 // cell, the first piece's cap), the kernels' NCH and tile, and the grid of a launch of nq <= piece queries
 struct ScanCut : ScanPlan {
@@ -525,6 +543,8 @@ struct Ladder {
            const char *what_)
         : idx(idx_), Q(Q_), nq(nq_), q_stride(q_stride_), semantics(semantics_), d_stage(d_stage_), st(st_), what(what_), Qj(Q_), m(nq_),
           qs(q_stride_), e(ef) {}
+    // stage 0 for the `count` queries of `list` only (host, ascending): gathered, as a later stage's batch is
+    int start_from(const int32_t *list, int64_t count);
     // W_e of the batch into wids / wdist ([m][e]): the host form's search of (ef = e, k = e), its tie-overflow repair included,
     // without a re-rank; the short counter zeroed
     int walk(int32_t *wids, float *wdist, int32_t fill);
@@ -534,7 +554,10 @@ struct Ladder {
     int count_short();
     // the n_short > 0 short queries, ascending, become the batch; false: they were short at e = 1024, the ladder is over
     int advance(bool &more);
+    // the queries of the batch advance made (host, ascending)
+    const std::vector<int32_t> &batch_queries() const { return shorts; }
 private:
+    int gather();                        // the m queries of `map` become the rows of the ladder's own matrix
     int cur = 0;                         // which list buffer `map` is
     std::vector<int32_t> shorts;
 };

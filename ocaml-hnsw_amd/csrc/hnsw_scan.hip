@@ -10,8 +10,9 @@
 //     round is merged into the query's sorted list of k words in global memory (scan_flush: never drops a word that is among the
 //     k smallest, never gives up), which lowers the threshold.  The list lives in two halves, read from one and written to the
 //     other.
-//   hnsw_scan_masked_kernel<NCH, METRIC>: the same scan over the rows an allow-mask names (hnsw_search_batch_filtered's exact
-//     stage, hnsw_filter.hip): ScanTopK<NCH, true>.
+//   hnsw_scan_masked_kernel<NCH, METRIC>: the same scan over the rows an allow-mask names (the exact stage of the filtered
+//     searches, hnsw_filter.hip): ScanTopK<NCH, true>, its mask taken per tile of queries from a table of masks (a table of one
+//     for hnsw_search_batch_filtered; hnsw_search_batch_filtered_each lays its queries out so that no tile spans two filters).
 //   hnsw_scan_merge_kernel<METRIC>: one workgroup per query merges the slabs' lists under the same order and writes ids
 //     (+ id_base), distances (key_to_dist) and the fill.
 // Nothing here depends on how the rows are cut into slabs or the queries into tiles: every list is the exact k smallest of its
@@ -80,7 +81,7 @@ template <int NCH, bool MASKED> struct ScanTopK {
     static constexpr int T = scan_tile(NCH);
     static constexpr int LIMIT = SCAN_BUF - 4 * scan_rows(NCH);   // a buffer up to here takes the survivors of one more pass over the UB batches
     const ScanArgs &a;
-    const uint32_t *mask;
+    MaskWords mask;
     // per query of the tile: its list's two halves, which half is current (bit t of par), the threshold word, the buffer's fill
     uint64_t (*bufs)[SCAN_BUF], *sorted, *lists0;
     int64_t list_step;
@@ -89,7 +90,7 @@ template <int NCH, bool MASKED> struct ScanTopK {
     uint32_t par;
     bool full;
 
-    __device__ __forceinline__ ScanTopK(const ScanArgs &a_, const uint32_t *mask_) : a(a_), mask(mask_) {}
+    __device__ __forceinline__ ScanTopK(const ScanArgs &a_, const uint32_t *mask_) : a(a_), mask(mask_words(mask_)) {}
     __device__ __forceinline__ void begin(int64_t q0, int tq_, int64_t slab) {
         __shared__ uint64_t bufs_all[SCAN_WAVES][T][SCAN_BUF];
         __shared__ uint64_t sorted_all[SCAN_WAVES][SCAN_BUF];
@@ -158,23 +159,28 @@ hnsw_scan_kernel(const IndexView iv, const ScanArgs a) {
     scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
 
-// ... restricted to the rows a mask allows (hnsw_search_batch_filtered's exact stage)
+// ... restricted to the rows a mask allows (the filtered searches' exact stage).  The mask is the tile's: masks[tile_filter[tile0 +
+// blockIdx.x]], masks[0] without a tile_filter; tile0 = the number of the launch's first tile among the call's.  Both loads are
+// scalar (blockIdx.x is the tile), so skip and admits stay wave-uniform tests of one mask.
 template <int NCH, int METRIC>
 __global__ void __launch_bounds__(64 * SCAN_WAVES, scan_min_waves(NCH))
-hnsw_scan_masked_kernel(const IndexView iv, const ScanArgs a, const uint32_t *mask) {
-    ScanTopK<NCH, true> sel(a, mask);
+hnsw_scan_masked_kernel(const IndexView iv, const ScanArgs a, const uint32_t *const *masks, const int32_t *tile_filter, int64_t tile0) {
+    ScanTopK<NCH, true> sel(a, masks[tile_filter ? tile_filter[tile0 + blockIdx.x] : 0]);
     scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
 
 // One workgroup per query.  lists: [nq][n_slabs][2][k], the first half of each the slab's k smallest words, ascending, padded.
 // No word above the smallest of the lists' k-th words can be among the k smallest of the union (that list alone has k words
 // not above it), so only the words up to it are ranked: a word's place is the number of smaller words over all lists.
+// row_query (optional, [nq]): a query whose entry is negative is a padding row of the caller's layout: nothing is merged or written.
 template <int METRIC>
 __global__ void __launch_bounds__(256)
-hnsw_scan_merge_kernel(const uint64_t *lists, int32_t n_slabs, int32_t k, int32_t fill, int32_t id_base, int32_t *out_ids, float *out_dist) {
+hnsw_scan_merge_kernel(const uint64_t *lists, int32_t n_slabs, int32_t k, int32_t fill, int32_t id_base, int32_t *out_ids, float *out_dist,
+                       const int32_t *row_query) {
     __shared__ unsigned long long bound;
     __shared__ int total;
     const int64_t q = blockIdx.x;
+    if (row_query && row_query[q] < 0) return;      // (the whole workgroup: before the first barrier)
     const uint64_t *L = lists + q * n_slabs * 2 * (int64_t)k;
     const int64_t step = 2 * (int64_t)k;
     if (threadIdx.x == 0) { bound = SCAN_EMPTY; total = 0; }
@@ -240,7 +246,8 @@ int check_scan(const hnsw_index *idx, int64_t nq, int64_t q_stride, int32_t k, i
 }
 
 // the scan of b's queries on `st`: the queries in pieces whose lists (two halves of k words per cell) fit SCAN_SCRATCH
-int scan_search(hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *mask) {
+int scan_search(hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *const *masks, const int32_t *tile_filter,
+                const int32_t *row_query) {
     int rc = check_scan(idx, b.nq, b.q_stride, k, fill, b.Q && b.ids && b.dist);
     if (rc || b.nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
@@ -249,16 +256,20 @@ int scan_search(hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hip
     if ((rc = idx->scratch.scan.ensure((size_t)(c.piece * std::max<int64_t>(c.slabs, 1) * 2 * k * 8)))) return rc;
     for (int64_t q0 = 0; q0 < b.nq; q0 += c.piece) {
         const int64_t nq = std::min(c.piece, b.nq - q0);
+        // a piece's first query is its first tile's first: scan_plan cuts pieces of a multiple of T queries (or makes one piece), so
+        // tile q0 / T of the call is tile 0 of this launch and tile_filter, numbered over the call's tiles, can be read from there
+        if (q0 % c.T) return fail(HNSW_ERR_HIP, "scan piece of %lld queries is no multiple of the tile (%d)", (long long)c.piece, c.T);
         ScanArgs a{b.Q + q0 * b.q_stride, b.q_stride, nq, k, (int32_t)c.slabs, c.slab_rows, (uint64_t *)idx->scratch.scan.p};
         if (c.slabs > 0) {
             with_metric(idx->info.metric, [&](auto METRIC) { with_nch(c.nch, [&](auto NCH) {
-                if (mask) hipLaunchKernelGGL((hnsw_dev::hnsw_scan_masked_kernel<NCH, METRIC>), c.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a, mask);
+                if (masks) hipLaunchKernelGGL((hnsw_dev::hnsw_scan_masked_kernel<NCH, METRIC>), c.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a, masks, tile_filter, q0 / c.T);
                 else hipLaunchKernelGGL((hnsw_dev::hnsw_scan_kernel<NCH, METRIC>), c.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a);
             }); });
             if ((rc = launched("scan kernel"))) return rc;
         }
         with_metric(idx->info.metric, [&](auto METRIC) {
-            hipLaunchKernelGGL(hnsw_dev::hnsw_scan_merge_kernel<METRIC>, dim3((unsigned)nq), dim3(256), 0, st, a.lists, a.n_slabs, k, fill, iv.id_base, b.ids + q0 * k, b.dist + q0 * k);
+            hipLaunchKernelGGL(hnsw_dev::hnsw_scan_merge_kernel<METRIC>, dim3((unsigned)nq), dim3(256), 0, st, a.lists, a.n_slabs, k, fill, iv.id_base, b.ids + q0 * k, b.dist + q0 * k,
+                               row_query ? row_query + q0 : nullptr);
         });
         if ((rc = launched("scan merge kernel"))) return rc;
     }

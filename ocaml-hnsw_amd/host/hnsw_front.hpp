@@ -4,6 +4,8 @@
 //   Hnsw::Ohnsw::knn / knn_batch_bigarray / build_batch_bigarray / insert / distance_l2   lib/ohnsw.ml:766-899
 //   Hnsw::Ohnsw::rerank                                                                    (hnsw_rerank_batch; nothing in the reference)
 //   Hnsw::Filter, Hnsw::Ohnsw::knn_filtered                                                (hnsw_filter_*, hnsw_search_batch_filtered)
+//   Hnsw::Filter::by_label / bits, Hnsw::Ohnsw::knn_filtered_each                          (hnsw_filter_create_by_label, hnsw_filter_bits,
+//                                                                                           hnsw_search_batch_filtered_each)
 //   Hnsw::RangeResult, Hnsw::Ohnsw::range_search / brute_force_range                       (hnsw_range_*)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
@@ -85,17 +87,37 @@ public:
         std::vector<uint32_t> bits((allow.size() + 31) / 32, 0u);
         for (size_t v = 0; v < allow.size(); ++v) if (allow[v]) bits[v >> 5] |= 1u << (v & 31);
         check(hnsw_filter_create(g.handle(), bits.data(), (int64_t)allow.size(), &f_));
+        n_ = (int64_t)allow.size();
     }
     // ... from the packed words themselves: bit (v & 31) of word (v >> 5) = node v, n_bits = the index's n
-    Filter(const Hgraph &g, const uint32_t *bits, int64_t n_bits) { check(hnsw_filter_create(g.handle(), bits, n_bits, &f_)); }
+    Filter(const Hgraph &g, const uint32_t *bits, int64_t n_bits) : n_(n_bits) { check(hnsw_filter_create(g.handle(), bits, n_bits, &f_)); }
     Filter(const Filter &) = delete;
     Filter &operator=(const Filter &) = delete;
-    Filter(Filter &&o) noexcept : f_(o.f_) { o.f_ = nullptr; }
+    Filter(Filter &&o) noexcept : f_(o.f_), n_(o.n_) { o.f_ = nullptr; }
     ~Filter() { if (f_) hnsw_filter_destroy(f_); }
     const hnsw_filter *handle() const { return f_; }
     int64_t count() const { int64_t c = 0; check(hnsw_filter_count(f_, &c)); return c; }   // the allowed nodes
+    // n_labels filters from one label per node (hnsw_filter_create_by_label): filter l allows node v iff labels[v] == l; a label
+    // of -1 puts the node in no filter.  One entry per node of the index; all or nothing.
+    static std::vector<Filter> by_label(const Hgraph &g, const std::vector<int32_t> &labels, int n_labels) {
+        std::vector<hnsw_filter *> raw((size_t)(n_labels > 0 ? n_labels : 0), nullptr);
+        check(hnsw_filter_create_by_label(g.handle(), labels.data(), (int64_t)labels.size(), n_labels, raw.data()));
+        std::vector<Filter> out;
+        out.reserve(raw.size());
+        for (hnsw_filter *f : raw) out.push_back(Filter(f, (int64_t)labels.size()));
+        return out;
+    }
+    // the mask as the device holds it (hnsw_filter_bits): ceil(n / 32) words, bit (v & 31) of word (v >> 5) = node v
+    std::vector<uint32_t> bits() const {
+        std::vector<uint32_t> w((size_t)((n_ + 31) / 32) + 1, 0u);
+        check(hnsw_filter_bits(f_, w.data()));
+        w.pop_back();
+        return w;
+    }
 private:
+    Filter(hnsw_filter *f, int64_t n) : f_(f), n_(n) {}
     hnsw_filter *f_ = nullptr;
+    int64_t n_ = 0;
 };
 
 // What a range call returns (hnsw_range_result), resident on the device of its index: lims [nq + 1], ids and distances [total];
@@ -297,6 +319,22 @@ inline Filtered knn_filtered(const Hgraph &g, const Filter &f, int k, const Mat 
     hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
     check(hnsw_search_batch_filtered(g.handle(), f.handle(), batch.data, batch.dim2, batch.dim1, &p, out.ids.data(), out.dist.data(),
                                      nullptr, nullptr, out.stage.data()));
+    return out;
+}
+
+// ... with one filter per query (hnsw_search_batch_filtered_each): query q is answered under filters[which[q]], its row the row
+// knn_filtered gives it under that filter; a mixed batch of many tenants in one call.
+inline Filtered knn_filtered_each(const Hgraph &g, const std::vector<Filter> &filters, const std::vector<int32_t> &which, int k, const Mat &batch,
+                                  int ef = 0, int sem = HNSW_SEM_OHNSW, int fill = HNSW_FILL_OHNSW) {
+    const size_t nq = (size_t)batch.dim2;
+    if (which.size() != nq) throw std::invalid_argument("knn_filtered_each: one filter position per query");
+    std::vector<const hnsw_filter *> table;
+    for (const Filter &f : filters) table.push_back(f.handle());
+    Filtered out{std::vector<int32_t>(nq * (size_t)(k > 0 ? k : 0), -1), std::vector<float>(nq * (size_t)(k > 0 ? k : 0), 0.f),
+                 std::vector<uint32_t>(nq, 0u)};
+    hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
+    check(hnsw_search_batch_filtered_each(g.handle(), table.data(), (int32_t)table.size(), which.data(), batch.data, batch.dim2, batch.dim1, &p,
+                                          out.ids.data(), out.dist.data(), nullptr, nullptr, out.stage.data()));
     return out;
 }
 

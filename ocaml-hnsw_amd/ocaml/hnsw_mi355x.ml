@@ -147,6 +147,15 @@ let hnsw_search_batch_filtered =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_filtered"
     (index @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> ptr int32_t @-> ptr float
      @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+(* ... with one filter per query; the filters of n_labels labels from one label per node; a filter's mask back on the host *)
+let hnsw_search_batch_filtered_each =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_filtered_each"
+    (index @-> ptr filter_handle @-> int32_t @-> ptr int32_t @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params
+     @-> ptr int32_t @-> ptr float @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+let hnsw_filter_create_by_label =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_filter_create_by_label"
+    (index @-> ptr int32_t @-> int64_t @-> int32_t @-> ptr filter_handle @-> returning int32_t)
+let hnsw_filter_bits = foreign ~from:lib "hnsw_filter_bits" (filter_handle @-> ptr uint32_t @-> returning int32_t)
 (* range search (see the C header): every node within a radius of the query; the result is an object that owns its device buffers *)
 type range_params
 let range_params : range_params structure typ = structure "hnsw_range_params"
@@ -852,6 +861,54 @@ let knn_batch_filtered ?(semantics = 0) ?(fill = 0) (f : filter) (batch : Lacaml
   check (hnsw_search_batch_filtered t.handle f.f_handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim)
            (addr p) (CArray.start ids) (CArray.start dist) (from_voidp uint32_t null) (from_voidp uint32_t null)
            (CArray.start stage));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
+   Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))
+
+(* [filters_by_label t labels ~n_labels] (hnsw_filter_create_by_label): n_labels filters from one label per node of the index;
+   filter l allows node v iff labels.(v) = l, a label of -1 puts the node in no filter.  The labels are uploaded once and one
+   pass over them on the device builds every mask.  Each filter is an ordinary [filter], freed with its own value. *)
+let filters_by_label (t : t) (labels : int array) ~n_labels : filter array =
+  let n = Array.length labels in
+  let lab = CArray.make int32_t (max 1 n) in
+  Array.iteri (fun v l -> CArray.set lab v (Int32.of_int l)) labels;
+  let out = CArray.make filter_handle ~initial:null (max 1 n_labels) in
+  check (hnsw_filter_create_by_label t.handle (CArray.start lab) (Int64.of_int n) (Int32.of_int n_labels) (CArray.start out));
+  Array.init n_labels (fun l ->
+      let f = { f_handle = CArray.get out l; f_index = t } in
+      Gc.finalise (fun f -> ignore (hnsw_filter_destroy f.f_handle)) f;
+      f)
+
+(* [filter_bits f ~n] (hnsw_filter_bits): the mask of a filter of an index of n nodes as the device holds it, one bool per node *)
+let filter_bits (f : filter) ~n : bool array =
+  let words = CArray.make uint32_t ~initial:Unsigned.UInt32.zero (max 1 ((n + 31) / 32)) in
+  check (hnsw_filter_bits f.f_handle (CArray.start words));
+  Array.init n (fun v ->
+      Unsigned.UInt32.logand (Unsigned.UInt32.shift_right (CArray.get words (v lsr 5)) (v land 31)) Unsigned.UInt32.one
+      <> Unsigned.UInt32.zero)
+
+(* [knn_batch_filtered_each filters which batch ~ef ~k] (hnsw_search_batch_filtered_each): query q (column q of [batch]) is
+   answered under filters.(which.(q)); its row is the row [knn_batch_filtered] gives it under that filter.  A mixed batch of many
+   tenants is one call.  All filters belong to one index.  -> as [knn_batch_filtered]. *)
+let knn_batch_filtered_each ?(semantics = 0) ?(fill = 0) (filters : filter array) (which : int array) (batch : Lacaml.S.mat)
+    ~ef ~k : int array array * float array array * int array =
+  if Array.length filters = 0 then invalid_arg "knn_batch_filtered_each: no filters";
+  let t = filters.(0).f_index in
+  let nq = A2.dim2 batch in
+  if Array.length which <> nq then invalid_arg "knn_batch_filtered_each: one filter position per query";
+  let table = CArray.make filter_handle ~initial:null (Array.length filters) in
+  Array.iteri (fun l f -> CArray.set table l f.f_handle) filters;
+  let w = CArray.make int32_t (max 1 nq) in
+  Array.iteri (fun q l -> CArray.set w q (Int32.of_int l)) which;
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let stage = CArray.make uint32_t (max 1 nq) in
+  let p = make search_params in
+  setf p p_ef (Int32.of_int ef); setf p p_k (Int32.of_int k); setf p p_fill (Int32.of_int fill);
+  setf p p_semantics (Int32.of_int semantics);
+  check (hnsw_search_batch_filtered_each t.handle (CArray.start table) (Int32.of_int (Array.length filters)) (CArray.start w)
+           (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) (addr p) (CArray.start ids) (CArray.start dist)
+           (from_voidp uint32_t null) (from_voidp uint32_t null) (CArray.start stage));
+  ignore (Sys.opaque_identity filters);      (* (alive until the call has returned) *)
   (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
    Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
    Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))

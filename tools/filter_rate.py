@@ -6,7 +6,14 @@ the host call (pageable matrices, host clock, median of --steps calls after a wa
 exact scan over the allowed vectors alone (a flat index of X[mask]: the same order, ids mapped back).  Beside them the unfiltered
 hnsw_search_batch rate of the same handle.  Informational: nothing gates on it.  The table printed here is what
 profiles/filtered_search.txt holds.
-Usage: python tools/filter_rate.py [--n 1000000] [--nq 10000] [--steps 5] [--out profiles/filtered_search.txt]"""
+
+--tenants L[,L...]: the mixed batch of a multi-tenant caller instead.  Uniform random labels 0 .. L-1 over the nodes
+(Hgraph.filters_by_label), a uniform random tenant per query.  Per L the time of the ONE hnsw_search_batch_filtered_each call over
+all queries against the loop of single-filter calls over each tenant's queries (sorted by tenant before the clock starts), the two
+alternating in one run, medians of --steps repetitions (20 at least) after a warm round of both, and the stage histogram.  The rows
+of the two are compared once (they are the same bits).  --loop-only times the loop alone, with per-tenant masks built on the host:
+what a build without the per-query call offers.
+Usage: python tools/filter_rate.py [--n 1000000] [--nq 10000] [--steps 5] [--tenants 1,10,100,1000] [--out profiles/filtered_search.txt]"""
 import argparse
 import os
 import sys
@@ -33,12 +40,66 @@ def median_ms(fn, steps):
     return float(np.median(out))
 
 
+def stage_shares(stage, nq):
+    values, counts = np.unique(stage, return_counts=True)
+    return ", ".join("%s %.1f %%" % ("exact" if v == H.STAGE_EXACT else "stage %d" % v, 100.0 * c / nq) for v, c in zip(values, counts))
+
+
+def tenants(hg, Q, n, ef, k, counts, steps, loop_only, say):
+    nq = len(Q)
+    steps = max(steps, 20)
+    for L in counts:
+        labels = np.random.default_rng(1000 + L).integers(0, L, n)
+        which = np.random.default_rng(2000 + L).integers(0, L, nq).astype(np.int32)
+        t0 = time.perf_counter()
+        filters = [hg.filter(labels == t) for t in range(L)] if loop_only else hg.filters_by_label(labels, L)
+        made = (time.perf_counter() - t0) * 1e3
+        groups = [np.flatnonzero(which == t) for t in range(L)]
+        groups = [(t, g, np.ascontiguousarray(Q[g])) for t, g in enumerate(groups) if len(g)]
+
+        def loop(counters=False):
+            return [H.Ohnsw.knn_batch_filtered(hg, k, Qt, filters[t], ef=ef, counters=counters) for t, _, Qt in groups]
+
+        def one(counters=False):
+            return H.Ohnsw.knn_batch_filtered_each(hg, k, Q, filters, which, ef=ef, counters=counters)
+
+        parts = loop(True)
+        stage = np.zeros(nq, np.uint32)
+        for (t, g, _), r in zip(groups, parts):
+            stage[g] = r[4]
+        same = ""
+        if not loop_only:
+            whole = one(True)
+            ok = all(np.array_equal(whole[j][g].view(np.uint32), r[j].view(np.uint32)) for (t, g, _), r in zip(groups, parts) for j in range(5))
+            same = "; rows of the two %s" % ("equal" if ok else "DIFFER")
+        t_loop, t_one = [], []
+        for _ in range(steps):          # alternating: drift of the machine lands on both
+            t0 = time.perf_counter()
+            loop()
+            t_loop.append((time.perf_counter() - t0) * 1e3)
+            if not loop_only:
+                t0 = time.perf_counter()
+                one()
+                t_one.append((time.perf_counter() - t0) * 1e3)
+        ml = float(np.median(t_loop))
+        line = "tenants %-4d (%d in use, filters made in %.1f ms): loop of single-filter calls %9.3f ms (min %.3f), %7.3f M q/s" % (
+            L, len(groups), made, ml, min(t_loop), nq / ml / 1e3)
+        if not loop_only:
+            mo = float(np.median(t_one))
+            line += "; ONE per-query call %9.3f ms (min %.3f), %7.3f M q/s; loop / one call %.2fx" % (mo, min(t_one), nq / mo / 1e3, ml / mo)
+        say(line + "; " + stage_shares(stage, nq) + same)
+        for f in filters:
+            f.release()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--nq", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--recall-queries", type=int, default=1000)
+    ap.add_argument("--tenants", default=None, help="comma-separated tenant counts: time the mixed batch instead of the selectivity table")
+    ap.add_argument("--loop-only", action="store_true", help="with --tenants: the loop of single-filter calls alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if H.device_count() < 1:
@@ -61,7 +122,11 @@ def main():
     plain = median_ms(lambda: H.Ohnsw.knn_batch_bigarray(hg, k, Q, ef=ef), a.steps)
     say("unfiltered hnsw_search_batch: %.3f ms per batch, %.3f M q/s" % (plain, a.nq / plain / 1e3))
     nr = min(a.recall_queries, a.nq)
-    for sel in (1.0, 0.5, 0.1, 0.01, 0.001):
+    if a.tenants:
+        say("mixed batch of %d queries, uniform random labels over the nodes, a uniform random tenant per query; medians of %d alternating repetitions"
+            % (a.nq, max(a.steps, 20)))
+        tenants(hg, Q, a.n, ef, k, [int(x) for x in a.tenants.split(",")], a.steps, a.loop_only, say)
+    for sel in (() if a.tenants else (1.0, 0.5, 0.1, 0.01, 0.001)):
         mask = np.ones(a.n, bool) if sel >= 1.0 else np.random.default_rng(int(sel * 1e6)).random(a.n) < sel
         flt = hg.filter(mask)
         ms = median_ms(lambda: H.Ohnsw.knn_batch_filtered(hg, k, Q, flt, ef=ef), a.steps)
@@ -71,8 +136,7 @@ def main():
         truth = allowed[H.Ohnsw.brute_force_knn(sub, k, Q[:nr])[0]]
         sub.release()
         hits = np.mean([len(set(x) & set(y)) for x, y in zip(ids[:nr], truth)]) / k
-        values, counts = np.unique(stage, return_counts=True)
-        shares = ", ".join("%s %.1f %%" % ("exact" if v == H.STAGE_EXACT else "stage %d" % v, 100.0 * c / a.nq) for v, c in zip(values, counts))
+        shares = stage_shares(stage, a.nq)
         say("selectivity %-5g (%7d allowed): %8.3f ms per batch, %7.3f M q/s (%.2fx the unfiltered call); %s; recall@%d %.4f"
             % (sel, flt.count(), ms, a.nq / ms / 1e3, plain / ms, shares, k, hits))
         flt.release()
