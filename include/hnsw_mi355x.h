@@ -29,6 +29,7 @@
  *                            Hnsw_algo.SelectNeighbours.select_neighbours (lib/hnsw_algo.ml:572-609)
  *   hnsw_build               Ohnsw.build_batch_bigarray (lib/ohnsw.ml:840-857), batched on the device
  *   hnsw_index_insert        Ohnsw.insert (lib/ohnsw.ml:766-837) of m vectors into an index the library holds
+ *   hnsw_index_remove        hard deletion (new: the reference never forgets a vector): nodes out, graph repaired on the device
  *   hnsw_brute_force_batch   brute_force_knn_l2 (benchmark/dataset.ml:15-30): the exact scan recall is measured against
  *   hnsw_rerank_batch        (nothing in the reference) the k nearest of caller-given candidates over the float32 vectors:
  *                            the refine step of the half-row searches (option "refine")
@@ -484,7 +485,7 @@ int32_t hnsw_rerank_batch_device(hnsw_index *idx, const float *d_queries, int64_
  * before its filters is the caller's error, as with requests (hnsw_filter_destroy itself stays valid: it only frees the mask).
  * The mask's bytes are NOT counted in hnsw_index_info.device_bytes.  A filter is not saved with the index.  Any number of
  * filters per index; a filter is never modified by a search.  A mask of the live nodes gives soft deletes without touching a
- * graph table.
+ * graph table (hnsw_index_remove is the hard deletion; it, like every hnsw_index_insert, makes the filters made before it stale).
  *
  * THE RESULT of hnsw_search_batch_filtered, in terms of public calls only.  Let W_e(q) be the ids hnsw_search_batch returns for
  * (ef = e, k = e) with the caller's semantics (HNSW_SEM_OHNSW / HNSW_SEM_FUNCTOR) -- the host form: exact, tie-overflow repair
@@ -750,6 +751,56 @@ int32_t hnsw_build(const float *vectors, int64_t n, int32_t d, int64_t row_strid
  *     the old ones and swapped in at the end, so at its peak the call holds two copies of the index on the device. */
 int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride,
                           const hnsw_build_params *params);
+
+/* ---- hard deletion: hnsw_index_remove takes nodes out of the index and repairs the graph on the device --------------------------
+ * A mask of the live nodes (hnsw_filter_create) is the soft half of deletion: the dead rows stay in device memory and every walk
+ * still pays for them.  hnsw_index_remove is the hard half: the m stored nodes `ids` (id_base-based, distinct; m == 0 is a no-op
+ * that only fills out_new_id with the identity) leave the index, which afterwards holds n = n_old - m nodes, the graph repaired as
+ * defined below -- in terms of hnsw_select_neighbours_batch and hnsw_distance_batch, so the result can be checked link for link.
+ * out_new_id (optional, [n_old]): the new id_base-based id of old node v; for a removed node id_base - 1.
+ *
+ *   NUMBERING.  D is the removed set, L the rest.  Live nodes keep their order: new(v) = v - |{d in D : d < v}|.  Vectors,
+ *     levels and every row move accordingly.
+ *   REPAIR, per layer l (layer 0 with cap = max_degree0, layers >= 1 with cap = max_degree).  It reads the OLD tables only, so
+ *     the result depends on no processing order (and on no atomic arrival order).  A live node u on layer l is TOUCHED when its
+ *     row on l lists a removed node.  An untouched live row is copied, renumbered, order kept.  For a touched u:
+ *       live(u) = the live entries of u's row, in row order.
+ *       C(u)    = u's removed neighbours walked in row order, each one's row on l in row order: every live w that is not u, not
+ *                 in live(u) and not already taken (the first occurrence counts).  The walk stops once |live(u)| + |C(u)| = 1024.
+ *                 Removed neighbours of removed neighbours are not followed.
+ *     1. PROPOSE.  S(u) = what hnsw_select_neighbours_batch returns after the forced entries for: target = u's vector,
+ *        candidates = live(u) then C(u), num_neighbours = cap, keep_all_if_few = 0, cand_degree = 0 for live(u) (forced, kept in
+ *        order) and 2 for C(u).  (The heuristic with live(u) already kept: C(u) is taken in (distance, id) order, the test is
+ *        strict and is made against the forced entries too.)
+ *     2. OFFER.  U(u) = S(u) united with { touched w on l : u in S(w), w not in live(u) }, ordered by
+ *        (hnsw_distance_batch(u's vector, w), id); T(u) = its first cap - |live(u)| entries.
+ *     3. AGREE.  new(u) = the w in T(u) with u in T(w), in T's order.  (An untouched w has no T: it takes no new link.  In a
+ *        symmetric graph every member of C(u) is touched.)
+ *     The new row of u is live(u) followed by new(u), renumbered.  Consequences: no live link is ever dropped; degrees stay within
+ *     the caps; a symmetric graph stays symmetric (Graph.Test.invariant, which hnsw_index_insert relies on); a node whose
+ *     neighbours all die, and whose dead neighbours had no other live neighbour, is left with degree 0 and shows up in
+ *     hnsw_index_layer_isolated.
+ *   LEVELS, TOP, ENTRY.  Live nodes keep their levels.  max_layer becomes the highest live level.  The entry point is the old one
+ *     if it is live, else the lowest-id live node of the highest live level.  The upper tables are laid out again for the live
+ *     nodes.  Removing every node gives the empty index: searches answer HNSW_ERR_EMPTY_INDEX, and an insert into it equals
+ *     hnsw_build of the same vectors.  Later inserts draw levels for positions n.. as documented there: numbering continues from
+ *     the shrunk n.
+ *   REFUSALS, each checked before anything is built, the index untouched: HNSW_ERR_BAD_ARG for null ids with m > 0, m < 0, an id
+ *     out of range or a duplicate id; for a handle with submitted requests not yet waited for; for a replica of an hnsw_multi;
+ *     for a graph whose upper rows list a node that is not on that layer or whose entry point is not on the top layer (the check
+ *     hnsw_index_insert makes).  A null handle: HNSW_ERR_BAD_ARG, out_new_id untouched.
+ *   ALL OR NOTHING, as hnsw_index_insert: the new tables are built beside the old ones, then hipDeviceSynchronize, then swapped.
+ *     On any error (HNSW_ERR_OOM included) the index is exactly as before; at its peak the call holds two copies of the index and
+ *     the repair's scratch (per touched node of a layer: two rows of 64 ids and 2 * cap proposal keys of 8 bytes).
+ *   WHAT FOLLOWS THE GRAPH, as after an insert: byte rows (they may now APPEAR, if only byte-valued vectors are left), split rows,
+ *     half rows and sq8 rows while their option is on (sq8 quantises the whole remaining table again: lo and scale may change);
+ *     the locality codes are dropped and rebuilt on demand; prepared shapes are prepared again; the device fallback slab holds
+ *     bytes / (4 n) queries of the smaller n; device_bytes follows the new tables.
+ *   FILTERS.  The handle has a graph epoch that every successful hnsw_index_insert and hnsw_index_remove moves on; a filter
+ *     records the epoch it was made in and is refused (HNSW_ERR_BAD_ARG) once it differs -- also after "remove 5, insert 5", where
+ *     n alone would let a stale mask through.  Make a new one.  Range results (hnsw_range_result) alive across a remove keep the
+ *     OLD ids; out_new_id translates them. */
+int32_t hnsw_index_remove(hnsw_index *idx, const int64_t *ids, int64_t m, int32_t *out_new_id);
 
 /* select_neighbours as a batched operator (Ohnsw.select_neighbours lib/ohnsw.ml:647-663;
  * keep_all_if_few = 1 adds the functor path's "#candidates <= M returns them all" shortcut,

@@ -71,6 +71,7 @@ _ABI = {
     "hnsw_range_result_destroy": [_vp],
     "hnsw_build": [_vp, _i64, _i32, _i64, _vp, _i32, _vp],
     "hnsw_index_insert": [_vp, _vp, _i64, _i64, _vp],
+    "hnsw_index_remove": [_vp, _vp, _i64, _vp],
     "hnsw_select_neighbours_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "hnsw_index_layer_stats": [_vp, _i32, _vp],
     "hnsw_index_layer_isolated": [_vp, _i32, _vp, _i64, _vp],
@@ -447,7 +448,8 @@ class Hgraph:
 
     def filter(self, allow):
         """hnsw_filter_create -> Filter: an allow-mask over this index's nodes.  allow: a boolean array of length n (entry v = node
-        v + id_base may be returned), or an array of node ids (id_base-based).  Valid until the index grows (insert_batch)."""
+        v + id_base may be returned), or an array of node ids (id_base-based).  Valid until the index grows or shrinks (insert_batch,
+        remove_batch)."""
         return Filter(self, allow)
 
     def filters_by_label(self, labels, n_labels=None):
@@ -931,6 +933,25 @@ class Ohnsw:
         hgraph._append_vectors(X)
         hgraph._adopt(hgraph.info())
         return _np.arange(n_old + hgraph.id_base, n_old + m + hgraph.id_base, dtype=_np.int64)
+
+    @staticmethod
+    def remove_batch(hgraph, ids):
+        """Hard deletion on the device (hnsw_index_remove): the stored nodes `ids` (id_base-based, distinct) leave the index, the
+        others keep their order and are renumbered, and the graph is repaired by the three-pass rule the header defines.  -> the
+        new id of every old node (np.int32 [n_old], id_base - 1 for a removed one).  Afterwards the Hgraph follows the device
+        index as after insert_batch; the host vectors (if any) lose the removed rows."""
+        ids = _np.ascontiguousarray(ids, dtype=_np.int64).reshape(-1)
+        n_old = hgraph.n
+        new_id = _np.empty(n_old, _np.int32)
+        _check(load().hnsw_index_remove(hgraph.handle, _ptr(ids), len(ids), _ptr(new_id)))
+        if len(ids) == 0:
+            return new_id
+        X = hgraph.vectors
+        if X is not None:
+            hgraph.vectors = _np.ascontiguousarray(_np.asarray(X, dtype=_np.float32)[new_id >= hgraph.id_base])
+            hgraph.row_stride = hgraph.d
+        hgraph._adopt(hgraph.info())
+        return new_id
 
     @staticmethod
     def select_neighbours(hgraph, targets, candidates, num_neighbours, keep_all_if_few=False, degrees=None):

@@ -307,6 +307,71 @@ hipError_t widen_rows(const void *src, int64_t rows, int ws, void *dst, int wd) 
 }
 } // namespace
 
+namespace hnsw_host {
+
+// insert's and remove's check of a graph they are about to read layer by layer (upper_rows_check_kernel)
+int check_upper_rows(const hnsw_index *idx, const char *verb) {
+    DevFlag flag;
+    int32_t bad = 0;
+    HIP_TRY(flag.alloc());
+    hipError_t e = flag.set(0);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(upper_rows_check_kernel, dim3((unsigned)((idx->iv.n + 255) / 256)), dim3(256), 0, nullptr, idx->iv.upper_ref,
+                           idx->iv.nbrU, idx->iv.SU, idx->iv.n, idx->iv.entry_point, idx->iv.max_layer, (int32_t *)flag.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = flag.get(&bad);
+    if (e != hipSuccess) return fail(HNSW_ERR_HIP, "upper-row check failed: %s", hipGetErrorString(e));
+    if (bad) return fail(HNSW_ERR_BAD_ARG, "the graph lists a node on a layer it is not on (or its entry point is not on the top layer): %s", verb);
+    return HNSW_OK;
+}
+
+// The tail hnsw_index_insert and hnsw_index_remove share: nx holds the new graph (vectors, rows, layout, view) built beside idx's.
+// What the handle derives from the graph is made again for it: the byte rows if ALL vectors are byte-valued, the split
+// rows (per-slot tails follow the changed adjacency) unless option split_rows -1 freed them for good, the half rows while
+// option half_rows is 1 (new vectors that do not fit fp16 refuse the whole insert; at 0 the copy is not carried over), the
+// sq8 rows while option sq8_rows is 1 (the WHOLE table is quantised again: new vectors may widen the range; a range that
+// overflows refuses the whole insert), the locality codes (carry_codes: carried over as extend_locality_codes does; else dropped
+// and built on demand).  Then the tables are swapped in and the graph epoch moves on.  On any error idx is as it was.
+int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics) {
+    int32_t rc = make_byte_rows(nx.get());
+    if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx.get());
+    if (!rc && idx->half_rows_on && nx->iv.n > 0) rc = make_half_rows(nx.get());
+    if (!rc && idx->sq8_on && nx->iv.n > 0) rc = make_sq8_rows(nx.get());
+    if (!rc && carry_codes) rc = extend_locality_codes(idx, nx.get());
+    if (rc) {
+        nx.reset();
+        (void)hipGetLastError();                    // (a failed allocation must not surface in the next call on this handle)
+        return rc;
+    }
+    // swap: work still in flight on caller streams (hnsw_search_batch_device) reads the old tables
+    {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) return fail(HNSW_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e));
+    }
+    const int rows_before = idx->info.row_format;
+    const int64_t n = nx->iv.n;
+    std::swap(idx->tables, nx->tables);                    // (nx takes the old tables with it)
+    idx->iv = nx->iv;
+    idx->info = nx->info;
+    idx->sq8_lo = nx->sq8_lo; idx->sq8_scale = nx->sq8_scale;   // (of the swapped-in codes, if any)
+    bind_view(idx);                                        // the options keep their effect
+    idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
+    nx.reset();
+    idx->epoch++;                                          // filters made for the graph before are refused from now on
+    // the per-shape decisions that follow n or the row format
+    idx->forget_shapes(/*keep_visited=*/carry_codes && rows_before == idx->info.row_format);
+    if (idx->fb_queries > 0 && n > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.bytes / (n * 4), 65536);
+    // the new index is searched at the steady-state rate from its first call, as a loaded one
+    (void)warm_up(idx);
+    const std::vector<std::pair<int, int>> shapes = idx->prepared;
+    for (const auto &pr : shapes) prepare_quietly(idx, pr.first, pr.second);
+    prepare_quietly(idx, expected_ef, expected_semantics);
+    return HNSW_OK;
+}
+
+} // namespace hnsw_host
+
 // One attempt of hnsw_index_insert: a new handle `out` with the graph of idx grown by the m vectors -- idx's tables copied
 // (rows widened to 2M / M) into tables sized for n_old + m nodes, then run_batches from position n_old.  idx is only read.
 // The derived tables (byte / split rows, locality codes) are the caller's.
@@ -408,20 +473,7 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
                 if (!std::isfinite(vectors[i * row_stride + j]))
                     return fail(HNSW_ERR_UNSUPPORTED, "sq8 rows: value %d of new vector %lld is NaN or infinite: nothing inserted", j, (long long)i);
     HIP_TRY(hipSetDevice(idx->device));
-    if (n_old > 0) {
-        DevFlag flag;
-        int32_t bad = 0;
-        HIP_TRY(flag.alloc());
-        hipError_t e = flag.set(0);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(upper_rows_check_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, nullptr, idx->iv.upper_ref,
-                               idx->iv.nbrU, idx->iv.SU, n_old, idx->iv.entry_point, idx->iv.max_layer, (int32_t *)flag.p);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = flag.get(&bad);
-        if (e != hipSuccess) return fail(HNSW_ERR_HIP, "upper-row check failed: %s", hipGetErrorString(e));
-        if (bad) return fail(HNSW_ERR_BAD_ARG, "the graph lists a node on a layer it is not on (or its entry point is not on the top layer): not grown");
-    }
+    if (n_old > 0) { const int32_t rcu = check_upper_rows(idx, "not grown"); if (rcu) return rcu; }
 
     // the grown graph, in tables of its own: on any error idx is as it was (overflow: again from idx's tables, 4x the room)
     IndexPtr nx;
@@ -431,43 +483,12 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
         rc = insert_attempt(idx, vectors, m, row_stride, p, scale, &overflow, nx);
         if (!overflow) break;
     }
-    // ... and what the handle derives from the graph, made again for it: the byte rows if ALL vectors are byte-valued, the split
-    // rows (per-slot tails follow the changed adjacency) unless option split_rows -1 freed them for good, the half rows while
-    // option half_rows is 1 (new vectors that do not fit fp16 refuse the whole insert; at 0 the copy is not carried over), the
-    // sq8 rows while option sq8_rows is 1 (the WHOLE table is quantised again: new vectors may widen the range; a range that
-    // overflows refuses the whole insert), the locality codes
-    if (!rc) rc = make_byte_rows(nx.get());
-    if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx.get());
-    if (!rc && idx->half_rows_on) rc = make_half_rows(nx.get());
-    if (!rc && idx->sq8_on) rc = make_sq8_rows(nx.get());
-    if (!rc) rc = extend_locality_codes(idx, nx.get());
     if (rc) {
         nx.reset();
-        (void)hipGetLastError();                    // (a failed allocation must not surface in the next call on this handle)
+        (void)hipGetLastError();
         return rc;
     }
-    // swap: work still in flight on caller streams (hnsw_search_batch_device) reads the old tables
-    {
-        const hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) return fail(HNSW_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e));
-    }
-    const int rows_before = idx->info.row_format;
-    std::swap(idx->tables, nx->tables);                    // (nx takes the old tables with it)
-    idx->iv = nx->iv;
-    idx->info = nx->info;
-    idx->sq8_lo = nx->sq8_lo; idx->sq8_scale = nx->sq8_scale;   // (of the swapped-in codes, if any)
-    bind_view(idx);                                        // the options keep their effect
-    idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
-    nx.reset();
-    // the per-shape decisions that follow n or the row format
-    idx->forget_shapes(/*keep_visited=*/rows_before == idx->info.row_format);
-    if (idx->fb_queries > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.bytes / (n * 4), 65536);
-    // the grown index is searched at the steady-state rate from its first call, as a loaded one
-    (void)warm_up(idx);
-    const std::vector<std::pair<int, int>> shapes = idx->prepared;
-    for (const auto &pr : shapes) prepare_quietly(idx, pr.first, pr.second);
-    prepare_quietly(idx, p->expected_ef, p->expected_semantics);
-    return HNSW_OK;
+    return adopt_graph(idx, nx, /*carry_codes=*/true, p->expected_ef, p->expected_semantics);
 }
 
 // ---- select_neighbours operator ----------------------------------------------------------------------

@@ -506,7 +506,8 @@ select_neighbours_kernel(const IndexView iv, const SelectOpArgs sa) {
 }
 
 // ---- K5: symmetric removals -------------------------------------------------------------------------
-__global__ void build_unlink_kernel(const BuildView bv, const uint64_t *removals, const uint32_t *rem_cnt,
+// (static, as the compaction below: this header is part of more than one translation unit)
+[[maybe_unused]] static __global__ void build_unlink_kernel(const BuildView bv, const uint64_t *removals, const uint32_t *rem_cnt,
                                     uint32_t rem_cap, int layer) {
     uint32_t n = *rem_cnt;
     if (n > rem_cap) n = rem_cap;      // the excess was counted in rem_cnt[1]: the host discards this attempt
@@ -521,7 +522,7 @@ __global__ void build_unlink_kernel(const BuildView bv, const uint64_t *removals
 }
 
 // ---- final: close the holes, keep row order ----------------------------------------------------------
-__global__ void __launch_bounds__(256) build_compact_kernel(int32_t *rows, int64_t nrows, int width) {
+[[maybe_unused]] static __global__ void __launch_bounds__(256) build_compact_kernel(int32_t *rows, int64_t nrows, int width) {
     __shared__ int32_t tmp[4][64];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t rrow = (int64_t)blockIdx.x * 4 + wv;

@@ -368,6 +368,8 @@ int check_filter(const hnsw_index *idx, const hnsw_filter *f) {
     if (f->idx != idx) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another index");
     if (f->n != idx->iv.n)
         return fail(HNSW_ERR_BAD_ARG, "the filter was made for %lld nodes, the index has grown to %lld", (long long)f->n, (long long)idx->iv.n);
+    if (f->epoch != idx->epoch)
+        return fail(HNSW_ERR_BAD_ARG, "the filter was made before the index last changed (hnsw_index_insert / hnsw_index_remove): its ids are stale");
     return HNSW_OK;
 }
 
@@ -398,6 +400,7 @@ int new_filter(hnsw_index *idx, std::unique_ptr<hnsw_filter> &f) {
     f.reset(new hnsw_filter());
     f->idx = idx;
     f->n = idx->iv.n;
+    f->epoch = idx->epoch;
     const size_t off = hnsw_filter::table_offset(f->n);
     int rc;
     if ((rc = f->bits.ensure(off + 8))) return rc;

@@ -4,6 +4,7 @@
 #include "hnsw_device.hip.h"
 #include "hnsw_scan_plan.h"
 #include "hnsw_filter_plan.h"
+#include "hnsw_remove_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -362,13 +363,17 @@ struct hnsw_index {
     hnsw_host::LadderBufs ladder_scratch;
     hnsw_host::FilterBufs filter_scratch;
     hnsw_host::RangeBufs range_scratch;
-    bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown on its own (hnsw_index_insert)
+    bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown or shrunk on its own (hnsw_index_insert, hnsw_index_remove)
+    // the graph epoch: every successful hnsw_index_insert and hnsw_index_remove moves it on (adopt_graph).  A filter records the
+    // epoch it was made in: n alone would let a mask through after "remove 5, insert 5"
+    uint64_t epoch = 0;
 };
 
 // an allow-mask over the nodes of one index (hnsw_filter_create): bit v of the device copy = node v (0-based) may be returned
 struct hnsw_filter {
     const hnsw_index *idx = nullptr;     // the handle it was made for ...
     int64_t n = 0;                       // ... and that handle's n then: a grown index refuses it
+    uint64_t epoch = 0;                  // ... and its graph epoch then: an index changed since refuses it
     int64_t n_allowed = 0;               // set bits below n (filter_popcount_kernel)
     // ceil(n / 32) words, the positions >= n of the last one clear; behind them (8-byte aligned) the mask's own device address:
     // the table of one filter that the single-filter call hands the kernels
@@ -421,6 +426,12 @@ void bind_view(::hnsw_index *idx);
 // hnsw_capi.hip: the end of hnsw_index_create and hnsw_build, once the graph tables are complete: the view bound, the row copies
 // made, the first search's one-time costs paid.  *out = idx on success.
 int finish_index(IndexPtr idx, int32_t expected_ef, int32_t expected_semantics, ::hnsw_index **out);
+
+// hnsw_build.hip: HNSW_ERR_BAD_ARG ("...: <verb>") for a graph whose upper rows list a node that is not on that layer, or whose
+// entry point is not on the top layer: what hnsw_index_insert and hnsw_index_remove ask before they follow the rows (n > 0)
+int check_upper_rows(const ::hnsw_index *idx, const char *verb);
+// hnsw_build.hip: the end of hnsw_index_insert and hnsw_index_remove: nx's graph tables become idx's (see there)
+int adopt_graph(::hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics);
 
 // hnsw_rows8.hip: if every value of tables.X is an integer in 0..255, build the byte copy (tables.X8, iv.stride8)
 int make_byte_rows(::hnsw_index *idx);

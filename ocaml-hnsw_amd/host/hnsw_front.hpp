@@ -79,7 +79,7 @@ public:
 struct value_distance { int node; float distance_to_target; }; // lib/hnsw_algo.ml:85
 
 // An allow-mask over the nodes of one index, resident on its device (hnsw_filter_create): allow[v] = node v + id_base may be
-// returned by Ohnsw::knn_filtered.  One entry per node; refused by the search once the index has grown (Ohnsw::insert).  Destroy
+// returned by Ohnsw::knn_filtered.  One entry per node; refused by the search once the index has grown or shrunk (Ohnsw::insert, Ohnsw::remove).  Destroy
 // it before its index.
 class Filter {
 public:
@@ -234,6 +234,17 @@ inline int64_t insert(Hgraph &g, const Mat &batch, int num_connections, int num_
     hnsw_build_params p{num_connections, num_nodes_search_construction, inf.metric, inf.id_base, seed, max_batch, 0, expected_ef, HNSW_SEM_OHNSW};
     check(hnsw_index_insert(g.handle(), batch.data, batch.dim2, batch.dim1, &p));
     return inf.n + inf.id_base;
+}
+
+// Hard deletion on the device (hnsw_index_remove): the stored nodes `ids` (id_base-based, distinct) leave g, the others keep
+// their order and are renumbered, the graph is repaired by the three-pass rule the header defines.  Returns the new id of every
+// old node (id_base - 1 for a removed one).
+inline std::vector<int32_t> remove(Hgraph &g, const std::vector<int64_t> &ids) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    std::vector<int32_t> new_id((size_t)inf.n);
+    check(hnsw_index_remove(g.handle(), ids.data(), (int64_t)ids.size(), new_id.data()));
+    return new_id;
 }
 
 // Ohnsw.knn hgraph visited ~k target (lib/ohnsw.ml:859-875): the MinQueue popped ascending.

@@ -203,6 +203,9 @@ let hnsw_build =
 let hnsw_index_insert =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_insert"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr build_params @-> returning int32_t)
+let hnsw_index_remove =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_remove"
+    (index @-> ptr int64_t @-> int64_t @-> ptr int32_t @-> returning int32_t)
 let hnsw_index_save = foreign ~from:lib ~release_runtime_lock:true "hnsw_index_save" (index @-> string @-> returning int32_t)
 let hnsw_index_load =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_load" (string @-> int32_t @-> ptr index @-> returning int32_t)
@@ -1011,6 +1014,18 @@ let insert_batch t (batch : Lacaml.S.mat) ~num_connections ~num_nodes_search_con
   setf b b_expected_ef (Int32.of_int expected_ef); setf b b_expected_semantics (Int32.of_int expected_semantics);
   check (hnsw_index_insert t.handle (bigarray_start array2 batch) (Int64.of_int (A2.dim2 batch)) (Int64.of_int t.dim) (addr b));
   Int64.to_int (getf inf ii_n) + Int32.to_int (getf inf ii_id_base)
+
+(* Hard deletion on the device (hnsw_index_remove): the stored nodes [ids] (id_base-based, distinct) leave the index, the others
+   keep their order and are renumbered, the graph is repaired by the three-pass rule the header defines.  Returns the new id of
+   every old node (id_base - 1 for a removed one).  As [insert_batch], for an index the device owns. *)
+let remove_batch t (ids : int array) : int array =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let n_old = Int64.to_int (getf inf ii_n) and m = Array.length ids in
+  let c_ids = CArray.make int64_t (max m 1) and c_new = CArray.make int32_t (max n_old 1) in
+  Array.iteri (fun i v -> CArray.set c_ids i (Int64.of_int v)) ids;
+  check (hnsw_index_remove t.handle (CArray.start c_ids) (Int64.of_int m) (CArray.start c_new));
+  Array.init n_old (fun v -> Int32.to_int (CArray.get c_new v))
 
 (* flattened-index file (the reference has no persistence: lib/hnsw.ml:348, lib/ohnsw.ml:312 derive sexp with opaque values) *)
 let save (t : t) (path : string) = check (hnsw_index_save t.handle path)
