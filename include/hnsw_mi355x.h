@@ -38,7 +38,9 @@
  *   hnsw_search_batch_filtered_each  ... with one filter per query: a mixed batch of many tenants in one call
  *                            (hnsw_filter_create_by_label: the tenants' filters from one label per node)
  *   hnsw_range_search_batch  (nothing in the reference) EVERY node within a radius of the query, a result of variable length;
- *                            hnsw_range_brute_force_batch is its exact form
+ *                            hnsw_range_brute_force_batch is its exact form; the _filtered forms of both answer under an allow-mask
+ *   hnsw_index_mark_deleted  (nothing in the reference) soft deletion owned by the index: mark a node now, every search goes
+ *                            around it; hnsw_index_compact pays for the repair (hnsw_index_remove of the marked nodes) later
  *   hnsw_host_alloc / hnsw_host_register   (nothing in the reference) page-locked query / result matrices,
  *                            which the entry points above read and write from the device in place
  *
@@ -485,7 +487,8 @@ int32_t hnsw_rerank_batch_device(hnsw_index *idx, const float *d_queries, int64_
  * before its filters is the caller's error, as with requests (hnsw_filter_destroy itself stays valid: it only frees the mask).
  * The mask's bytes are NOT counted in hnsw_index_info.device_bytes.  A filter is not saved with the index.  Any number of
  * filters per index; a filter is never modified by a search.  A mask of the live nodes gives soft deletes without touching a
- * graph table (hnsw_index_remove is the hard deletion; it, like every hnsw_index_insert, makes the filters made before it stale).
+ * graph table (hnsw_index_remove is the hard deletion; it, like every hnsw_index_insert, makes the filters made before it stale;
+ * hnsw_index_mark_deleted is the soft deletion the index keeps itself, across inserts and removals).
  *
  * THE RESULT of hnsw_search_batch_filtered, in terms of public calls only.  Let W_e(q) be the ids hnsw_search_batch returns for
  * (ef = e, k = e) with the caller's semantics (HNSW_SEM_OHNSW / HNSW_SEM_FUNCTOR) -- the host form: exact, tie-overflow repair
@@ -633,6 +636,31 @@ int32_t hnsw_range_result_fetch(hnsw_range_result *r, int64_t *lims, int32_t *id
 /* borrowed device pointers, valid until destroy (for callers that go on working on the device); each may be NULL */
 int32_t hnsw_range_result_device(hnsw_range_result *r, const int64_t **d_lims, const int32_t **d_ids, const float **d_dist);
 int32_t hnsw_range_result_destroy(hnsw_range_result *r);   /* NULL is HNSW_OK */
+
+/* ---- range search under an allow-mask -------------------------------------------------------------------------------------------
+ * THE RESULT of the filtered range calls, in terms of public calls only.  f is a filter of hnsw_filter_create /
+ * hnsw_filter_create_by_label; "the unfiltered call" is hnsw_range_search_batch for hnsw_range_search_batch_filtered and
+ * hnsw_range_brute_force_batch for hnsw_range_brute_force_batch_filtered, with the same other arguments.
+ *   1. SEGMENT.  Query q's segment is the segment the unfiltered call gives q, with the nodes f does not allow left out and the
+ *      order kept: ids and distance bits of the allowed members are those of the unfiltered call.
+ *   2. STAGE AND HOPS.  The ladder's stage test is the unfiltered one: W_e(q) is saturated iff all e entries are real and in range,
+ *      whatever the mask says.  So out_stage and out_nhops equal the unfiltered call's.  Under HNSW_ROWS_HALF and HNSW_ROWS_SQ8 all
+ *      of W is re-ranked first, as in the unfiltered call; the mask is applied after.
+ *   3. EVALUATIONS.  out_ndist equals the unfiltered call's, except that the exact stage adds the filter's n_allowed instead of n
+ *      (the brute-force form: out_ndist is n_allowed).
+ *   4. NO WALK.  A filter that allows no node takes no walk: every segment is empty, out_stage is 0xFFFFFFFF, and both counters are 0.
+ *   5. ERRORS as the unfiltered call (NaN radius, ef, semantics, HNSW_ERR_EMPTY_INDEX for the search form, nq == 0, the 2^31 - 1
+ *      cap), plus the filtered search's filter checks: a null, foreign or stale filter (made for another handle, or before the
+ *      index last changed) is HNSW_ERR_BAD_ARG.  An error leaves *out NULL.
+ *   6. SINGLE FILTER ONLY: per-query filters and per-query radii are not built.
+ * This is done on the device, not as a host post-filter: a disallowed hit is never counted, stored, sorted or held against the
+ * 2^31 - 1 cap, and the exact stage steps over a mask word without a set bit without loading its 32 rows, as the masked k-scan
+ * does.  Scratch, "ONE range call in flight per handle" and the result object are those of the unfiltered calls, which are the case
+ * "no mask" of the same driver. */
+int32_t hnsw_range_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                         const hnsw_range_params *params, hnsw_range_result **out);
+int32_t hnsw_range_brute_force_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq,
+                                              int64_t q_stride, float radius, hnsw_range_result **out);
 
 /* ---- the layer-level functions of the path, as batched operators -------------------------------
  * hnsw_search_layer_batch = Ohnsw.search_k (lib/ohnsw.ml:543-588; params->semantics = OHNSW) or
@@ -801,6 +829,58 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
  *     n alone would let a stale mask through.  Make a new one.  Range results (hnsw_range_result) alive across a remove keep the
  *     OLD ids; out_new_id translates them. */
 int32_t hnsw_index_remove(hnsw_index *idx, const int64_t *ids, int64_t m, int32_t *out_new_id);
+
+/* ---- soft deletion owned by the index: mark, search around, compact -------------------------------------------------------------
+ * hnsw_index_remove is a rebuild-sized call; nobody makes it per deleted item.  hnsw_index_mark_deleted deletes cheaply now --
+ * a few bits on the device -- and hnsw_index_compact pays for the repair later.  Unlike a caller-made mask of the live nodes, the
+ * marks survive hnsw_index_insert and hnsw_index_remove, and the plain entry points honour them without being told.
+ *
+ *   THE MARKS.  The handle owns a device mask of the LIVE (not marked) nodes and an internal filter over it, both allocated on the
+ *     first mark and NOT counted in hnsw_index_info.device_bytes, as no filter is.  hnsw_index_mark_deleted marks the m stored
+ *     nodes `ids` (id_base-based); hnsw_index_unmark_deleted makes them live again.  Marking a marked node or unmarking a live one is
+ *     allowed and does nothing; m == 0 is a no-op.  Refused with HNSW_ERR_BAD_ARG, the index untouched, everything checked on the host
+ *     first: an id out of range, a duplicate within the call, null ids with m > 0, m < 0; a handle with submitted requests not yet
+ *     waited for; a replica of an hnsw_multi (as hnsw_index_insert refuses them).  hnsw_index_deleted_count gives the number of
+ *     marked nodes; hnsw_index_deleted_bits copies the marks to the host: ceil(n / 32) words, bit (v & 31) of word (v >> 5) set =
+ *     the 0-based node v is marked, the bits past n clear.
+ *   EPOCH.  A successful call that changes at least one bit moves the handle's graph epoch on: filters made before it are refused
+ *     (HNSW_ERR_BAD_ARG) like filters made before an insert -- their masks may allow a node that is marked now.
+ *   GRAPH.  Marked nodes stay in the graph.  Every walk still goes through them, so no region is cut off; they are only never
+ *     returned.
+ *   WHAT HONOURS THE MARKS, only while n_deleted > 0.  Let LIVE be the filter of the unmarked nodes.
+ *     - hnsw_search_batch, hnsw_knn: rows (ids, distances, out_ndist, out_nhops) are bit for bit those of
+ *       hnsw_search_batch_filtered under LIVE with the same params: ladder, exact stage, fill, half / sq8 rule and all.
+ *       HNSW_SEM_FUNCTOR_NEAREST_K: HNSW_ERR_BAD_ARG.  hnsw_knn's *out_count = the real entries.
+ *     - hnsw_brute_force_batch, hnsw_brute_force_batch_device: the k smallest LIVE nodes under (distance, node id), the rest filled.
+ *     - hnsw_range_search_batch, hnsw_range_brute_force_batch: their _filtered forms under LIVE.
+ *     - hnsw_filter_create, hnsw_filter_create_by_label: the mask is ANDed with the live mask at creation, on the device (a marked
+ *       node's label counts as -1); hnsw_filter_count and hnsw_filter_bits report the ANDed mask.  So a current filter already
+ *       excludes the marked nodes, and hnsw_search_batch_filtered, hnsw_search_batch_filtered_each and the filtered range calls run
+ *       unchanged code.
+ *     - hnsw_index_insert: accepted.  Marks keep their positions, the new nodes are live, and the live mask grows inside the
+ *       all-or-nothing swap.
+ *     - hnsw_index_remove: accepted.  The marks move with their nodes under out_new_id's numbering, a removed marked node is gone,
+ *       and the new mask is built before the swap.
+ *     - hnsw_search_batch_device, hnsw_search_batch_h2d, hnsw_search_submit: HNSW_ERR_UNSUPPORTED ("compact or unmark first"):
+ *       these forms cannot run the ladder.
+ *     - hnsw_index_save: HNSW_ERR_BAD_ARG ("marked nodes are not saved: compact or unmark first").  A file that resurrects deleted
+ *       vectors is the one outcome to rule out, and the format does not change.
+ *   NOT AFFECTED: the calls that take explicit ids (hnsw_distance_batch, hnsw_rerank_batch, hnsw_select_neighbours_batch), the
+ *     layer operators (hnsw_search_layer_batch, hnsw_search_one_batch), the exports, hnsw_index_get_info (n stays the stored
+ *     count), the layer stats and the locality codes; hnsw_multi searches (a replica cannot be marked).
+ *   EVERY NODE MARKED: the searches fill every row and the range segments are empty; this is not HNSW_ERR_EMPTY_INDEX.
+ *   COUNT BACK AT 0 (unmark, or compact): the handle takes the plain paths again, results are bit for bit those of a handle never
+ *     marked, and the device forms and hnsw_index_save are accepted again.
+ *   hnsw_index_compact is hnsw_index_remove(idx, the marked ids ascending, n_deleted, out_new_id): same repair, same refusals, all
+ *     or nothing.  Afterwards nothing is marked.  With nothing marked it fills out_new_id (optional, [n]) with the identity.
+ *   NOT BUILT: device forms under marks, saved marks, filters that survive a mark.
+ * Cost: a marked index is searched by the filtered ladder, several times slower than the plain call until compacted
+ * (tools/soft_delete_rate.py prints the rates). */
+int32_t hnsw_index_mark_deleted(hnsw_index *idx, const int64_t *ids, int64_t m);
+int32_t hnsw_index_unmark_deleted(hnsw_index *idx, const int64_t *ids, int64_t m);
+int32_t hnsw_index_deleted_count(const hnsw_index *idx, int64_t *n_deleted);
+int32_t hnsw_index_deleted_bits(const hnsw_index *idx, uint32_t *out);   /* ceil(n/32) words, bit v = node v is marked */
+int32_t hnsw_index_compact(hnsw_index *idx, int32_t *out_new_id);        /* hnsw_index_remove of the marked nodes */
 
 /* select_neighbours as a batched operator (Ohnsw.select_neighbours lib/ohnsw.ml:647-663;
  * keep_all_if_few = 1 adds the functor path's "#candidates <= M returns them all" shortcut,

@@ -65,6 +65,8 @@ _ABI = {
     "hnsw_filter_bits": [_vp, _vp],
     "hnsw_range_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp],
     "hnsw_range_brute_force_batch": [_vp, _vp, _i64, _i64, _f32, _vp],
+    "hnsw_range_search_batch_filtered": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "hnsw_range_brute_force_batch_filtered": [_vp, _vp, _vp, _i64, _i64, _f32, _vp],
     "hnsw_range_result_size": [_vp, _vp, _vp],
     "hnsw_range_result_fetch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_range_result_device": [_vp, _vp, _vp, _vp],
@@ -72,6 +74,11 @@ _ABI = {
     "hnsw_build": [_vp, _i64, _i32, _i64, _vp, _i32, _vp],
     "hnsw_index_insert": [_vp, _vp, _i64, _i64, _vp],
     "hnsw_index_remove": [_vp, _vp, _i64, _vp],
+    "hnsw_index_mark_deleted": [_vp, _vp, _i64],
+    "hnsw_index_unmark_deleted": [_vp, _vp, _i64],
+    "hnsw_index_deleted_count": [_vp, _vp],
+    "hnsw_index_deleted_bits": [_vp, _vp],
+    "hnsw_index_compact": [_vp, _vp],
     "hnsw_select_neighbours_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "hnsw_index_layer_stats": [_vp, _i32, _vp],
     "hnsw_index_layer_isolated": [_vp, _i32, _vp, _i64, _vp],
@@ -470,6 +477,47 @@ class Hgraph:
         _check(load().hnsw_filter_create_by_label(self.handle, _ptr(lab) if lab.size else None, lab.size, n_labels, out))
         return [Filter._adopt(self, _C.c_void_p(out[l]), lab.size) for l in range(n_labels)]
 
+    def mark_deleted(self, ids):
+        """hnsw_index_mark_deleted: soft deletion.  The stored nodes `ids` (id_base-based, distinct) stay in the graph -- every walk
+        still goes through them -- but no search returns them any more: while any node is marked, the knn, brute-force and range
+        searches answer under the mask of the live nodes, and new filters are ANDed with it.  Filters made before are refused
+        afterwards.  Cheap (a few bits on the device); compact() pays for the repair later."""
+        ids = _np.ascontiguousarray(ids, dtype=_np.int64).reshape(-1)
+        _check(load().hnsw_index_mark_deleted(self.handle, _ptr(ids) if len(ids) else None, len(ids)))
+
+    def unmark_deleted(self, ids):
+        """hnsw_index_unmark_deleted: the nodes `ids` are live again (a node that is not marked stays as it is)"""
+        ids = _np.ascontiguousarray(ids, dtype=_np.int64).reshape(-1)
+        _check(load().hnsw_index_unmark_deleted(self.handle, _ptr(ids) if len(ids) else None, len(ids)))
+
+    def deleted_count(self):
+        """hnsw_index_deleted_count: how many nodes are marked"""
+        c = _C.c_int64(0)
+        _check(load().hnsw_index_deleted_count(self.handle, _C.byref(c)))
+        return c.value
+
+    def deleted_mask(self):
+        """hnsw_index_deleted_bits -> a boolean array of length n: entry v = node v + id_base is marked"""
+        n = self.info().n
+        words = _np.zeros(max((n + 31) // 32, 1), _np.uint32)
+        _check(load().hnsw_index_deleted_bits(self.handle, _ptr(words)))
+        return _np.unpackbits(words.view(_np.uint8), bitorder="little")[:n].astype(bool)
+
+    def compact(self):
+        """hnsw_index_compact: hnsw_index_remove of the marked nodes (see Ohnsw.remove_batch) -> the new id of every old node
+        (np.int32 [n_old], id_base - 1 for a removed one).  Afterwards nothing is marked."""
+        n_old = self.info().n
+        gone = self.deleted_count()
+        new_id = _np.empty(n_old, _np.int32)
+        _check(load().hnsw_index_compact(self.handle, _ptr(new_id)))
+        if gone:
+            X = self.vectors
+            if X is not None:
+                self.vectors = _np.ascontiguousarray(_np.asarray(X, dtype=_np.float32)[new_id >= self.id_base])
+                self.row_stride = self.d
+            self._adopt(self.info())
+        return new_id
+
     def kernel_times(self):
         """(search kernel ms, ordering pre-pass ms, calls) averaged over the device-entry calls since the
         last call (needs set_option("time_kernels", 1)); waits for them."""
@@ -694,15 +742,27 @@ class RangeResult:
             pass
 
 
-def _range_search(hgraph, batch, radius, ef, sem=0, counters=False, keep=False):
-    """hnsw_range_search_batch (ef None: hnsw_range_brute_force_batch) -> what RangeResult.fetch gives; keep: the RangeResult"""
+def _range_search(hgraph, batch, radius, ef, sem=0, counters=False, keep=False, filter=None):
+    """hnsw_range_search_batch (ef None: hnsw_range_brute_force_batch) -> what RangeResult.fetch gives; keep: the RangeResult.
+    filter: a Filter, or what Hgraph.filter takes (a mask made for this call): the _filtered forms of the two calls"""
     Q, qs, nq = _batch(hgraph.d, batch)
     r = _C.c_void_p()
-    if ef is None:
-        _check(load().hnsw_range_brute_force_batch(hgraph.handle, _ptr(Q), nq, qs, float(radius), _C.byref(r)))
-    else:
-        p = _RangeParams(float(radius), int(ef), sem)
-        _check(load().hnsw_range_search_batch(hgraph.handle, _ptr(Q), nq, qs, _C.byref(p), _C.byref(r)))
+    own = None if filter is None or isinstance(filter, Filter) else Filter(hgraph, filter)
+    try:
+        f = None if filter is None else (own or filter).handle
+        if ef is None and f is None:
+            _check(load().hnsw_range_brute_force_batch(hgraph.handle, _ptr(Q), nq, qs, float(radius), _C.byref(r)))
+        elif ef is None:
+            _check(load().hnsw_range_brute_force_batch_filtered(hgraph.handle, f, _ptr(Q), nq, qs, float(radius), _C.byref(r)))
+        else:
+            p = _RangeParams(float(radius), int(ef), sem)
+            if f is None:
+                _check(load().hnsw_range_search_batch(hgraph.handle, _ptr(Q), nq, qs, _C.byref(p), _C.byref(r)))
+            else:
+                _check(load().hnsw_range_search_batch_filtered(hgraph.handle, f, _ptr(Q), nq, qs, _C.byref(p), _C.byref(r)))
+    finally:
+        if own is not None:
+            own.release()
     res = RangeResult(r)
     if keep:
         return res
@@ -818,20 +878,22 @@ class Ohnsw:
         return _search_filtered_each(hgraph, filters, which, batch, k if ef is None else ef, k, FILL_OHNSW, counters, out=out)
 
     @staticmethod
-    def range_search(hgraph, radius, batch, ef=64, counters=False, keep=False):
+    def range_search(hgraph, radius, batch, ef=64, counters=False, keep=False, filter=None):
         """EVERY node within `radius` of each query (hnsw_range_search_batch) -> (lims, ids, distances), with counters (lims, ids,
         distances, ndist, nhops, stage): query q's segment is ids / distances [lims[q], lims[q + 1]), ascending under (distance,
         id).  A query is served by the first search of the ladder e = ef, 2 ef, ... 1024 whose W is not saturated (fewer than e
         members, or the last one out of range): W's in-range prefix; a query saturated at 1024 gets the exact range scan (stage =
         STAGE_EXACT).  Distances are over the float32 vectors whatever rows the index searches.  keep: the RangeResult itself,
-        left on the device."""
-        return _range_search(hgraph, batch, radius, ef, SEM_OHNSW, counters, keep)
+        left on the device.  filter (a Filter, or what Hgraph.filter takes): hnsw_range_search_batch_filtered -- each segment is the
+        unfiltered one with the nodes the filter does not allow left out; stage and hops are the unfiltered call's."""
+        return _range_search(hgraph, batch, radius, ef, SEM_OHNSW, counters, keep, filter)
 
     @staticmethod
-    def brute_force_range(hgraph, radius, batch, counters=False, keep=False):
+    def brute_force_range(hgraph, radius, batch, counters=False, keep=False, filter=None):
         """The exact range search (hnsw_range_brute_force_batch) -> (lims, ids, distances): per query the in-range prefix of the
-        full order (distance, id) over all n vectors.  Needs no graph."""
-        return _range_search(hgraph, batch, radius, None, SEM_OHNSW, counters, keep)
+        full order (distance, id) over all n vectors.  Needs no graph.  filter: over the allowed vectors only
+        (hnsw_range_brute_force_batch_filtered)."""
+        return _range_search(hgraph, batch, radius, None, SEM_OHNSW, counters, keep, filter)
 
     @staticmethod
     def brute_force_knn(hgraph, k, batch, fill=FILL_OHNSW, out=None):
@@ -1019,10 +1081,10 @@ class Ba:
         return _search_filtered_each(hgraph, filters, which, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR)
 
     @staticmethod
-    def range_search(hgraph, batch, num_neighbours_search, radius, counters=False):
+    def range_search(hgraph, batch, num_neighbours_search, radius, counters=False, filter=None):
         """Ohnsw.range_search under the functor accept rule (1-based ids in a Hnsw.Ba-style index), the ladder starting at
-        ~num_neighbours_search"""
-        return _range_search(hgraph, batch, radius, num_neighbours_search, SEM_FUNCTOR, counters)
+        ~num_neighbours_search; filter: as Ohnsw.range_search"""
+        return _range_search(hgraph, batch, radius, num_neighbours_search, SEM_FUNCTOR, counters, filter=filter)
 
     @staticmethod
     def search(hgraph, layer, start_nodes, targets, size_nearest):

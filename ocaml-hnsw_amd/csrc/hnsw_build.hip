@@ -333,12 +333,15 @@ int check_upper_rows(const hnsw_index *idx, const char *verb) {
 // sq8 rows while option sq8_rows is 1 (the WHOLE table is quantised again: new vectors may widen the range; a range that
 // overflows refuses the whole insert), the locality codes (carry_codes: carried over as extend_locality_codes does; else dropped
 // and built on demand).  Then the tables are swapped in and the graph epoch moves on.  On any error idx is as it was.
-int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics) {
+int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics, const int32_t *new_id) {
     int32_t rc = make_byte_rows(nx.get());
     if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx.get());
     if (!rc && idx->half_rows_on && nx->iv.n > 0) rc = make_half_rows(nx.get());
     if (!rc && idx->sq8_on && nx->iv.n > 0) rc = make_sq8_rows(nx.get());
     if (!rc && carry_codes) rc = extend_locality_codes(idx, nx.get());
+    // soft deletion: the marks move with their nodes; the new live mask is complete before anything is swapped
+    std::unique_ptr<hnsw_filter> live;
+    if (!rc) rc = renumbered_live_filter(idx, new_id, nx->iv.n, live);
     if (rc) {
         nx.reset();
         (void)hipGetLastError();                    // (a failed allocation must not surface in the next call on this handle)
@@ -359,6 +362,9 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
     idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
     nx.reset();
     idx->epoch++;                                          // filters made for the graph before are refused from now on
+    idx->n_deleted = live ? n - live->n_allowed : 0;
+    if (live) live->epoch = idx->epoch;
+    idx->live = std::move(live);                           // (null when nothing is marked any more)
     // the per-shape decisions that follow n or the row format
     idx->forget_shapes(/*keep_visited=*/carry_codes && rows_before == idx->info.row_format);
     if (idx->fb_queries > 0 && n > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.bytes / (n * 4), 65536);
@@ -697,6 +703,9 @@ bool rd(FILE *f, void *p, size_t bytes) { return bytes == 0 || fread(p, 1, bytes
 
 int32_t hnsw_index_save(const hnsw_index *idx, const char *path) {
     if (!idx || !path) return fail(HNSW_ERR_BAD_ARG, "null argument");
+    // (a file that brings deleted vectors back is the one outcome to rule out; the format has no place for the marks)
+    if (idx->n_deleted > 0)
+        return fail(HNSW_ERR_BAD_ARG, "%lld marked nodes are not saved: compact or unmark first", (long long)idx->n_deleted);
     HIP_TRY(hipSetDevice(idx->device));
     const int64_t n = idx->iv.n; const int d = idx->iv.d; const int S0 = idx->iv.S0, SU = idx->iv.SU;
     FILE *f = fopen(path, "wb");

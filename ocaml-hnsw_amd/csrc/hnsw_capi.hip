@@ -838,6 +838,12 @@ void list_blk_choices(const hnsw_index *idx, std::vector<int32_t> &out3) {
 // ---- ABI ---------------------------------------------------------------------------------------
 extern "C" {
 
+// the forms that cannot run the ladder (device buffers, h2d, submit) on a handle with nodes marked deleted
+static int marked_unsupported(const hnsw_index *idx, const char *call) {
+    return fail(HNSW_ERR_UNSUPPORTED, "%s: %lld nodes are marked deleted and this form cannot search around them: compact or unmark first", call,
+                (long long)idx->n_deleted);
+}
+
 int32_t hnsw_abi_version(void) { return HNSW_ABI_VERSION; }
 const char *hnsw_last_error(void) { return hnsw_host::g_last_error.c_str(); }
 
@@ -1098,6 +1104,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
 int32_t hnsw_search_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
                                  const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
                                  uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, void *stream) {
+    if (idx && idx->n_deleted > 0) return marked_unsupported(idx, "hnsw_search_batch_device");
     return knn_search(idx, params, {d_queries, nq, q_stride, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr}, (hipStream_t)stream);
 }
 
@@ -1125,7 +1132,11 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
                           const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
                           uint32_t *out_ndist, uint32_t *out_nhops) {
     int rc = check_batch(idx, params, nq, q_stride, queries && out_ids && out_dist);
-    if (rc || nq == 0) return rc;
+    if (rc) return rc;
+    // nodes are marked deleted: the filtered search under the handle's live mask, ladder, exact stage and all
+    if (idx->n_deleted > 0)
+        return hnsw_search_batch_filtered(idx, idx->live.get(), queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, nullptr);
+    if (nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
     // Where the matrices live: HostCall::begin.  The search is ordered longest walk first when the batch is larger than the chip
     // holds; whether any query needs the exactness fallback comes back as one word (pinned host memory, the kernel stores it),
@@ -1152,7 +1163,9 @@ int32_t hnsw_search_batch_h2d(hnsw_index *idx, const float *queries, int64_t nq,
                               const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
                               uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, void *stream) {
     int rc = check_batch(idx, params, nq, q_stride, queries && d_ids && d_dist);
-    if (rc || nq == 0) return rc;
+    if (rc) return rc;
+    if (idx->n_deleted > 0) return marked_unsupported(idx, "hnsw_search_batch_h2d");
+    if (nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
     const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d);
     if ((rc = idx->scratch.q.ensure(qbytes))) return rc;
@@ -1174,6 +1187,7 @@ int32_t hnsw_search_submit(hnsw_index *idx, const float *queries, int64_t nq, in
     *out = nullptr;
     int rc = check_batch(idx, params, nq, q_stride, queries != nullptr);
     if (rc) return rc;
+    if (idx->n_deleted > 0) return marked_unsupported(idx, "hnsw_search_submit");
     if (nq == 0) return fail(HNSW_ERR_BAD_ARG, "nq=0: nothing to submit");
     HIP_TRY(hipSetDevice(idx->device));
     hnsw_request *r;

@@ -10,8 +10,10 @@
 // (hnsw_range.hip) runs the same one with its own select rule.
 //
 // Kernels.
-//   filter_popcount_kernel  the uploaded mask: clears the bits past n in its last word and counts the rest.
-//   filter_label_kernel     hnsw_filter_create_by_label: all masks and their counts in one pass over the nodes' labels.
+//   filter_popcount_kernel  the uploaded mask: clears the bits past n in its last word and counts the rest; with a second operand
+//                           (the live mask of a handle with nodes marked deleted) the mask is ANDed with it first.
+//   filter_label_kernel     hnsw_filter_create_by_label: all masks and their counts in one pass over the nodes' labels; a node
+//                           marked deleted counts as label -1.
 //   filter_select_kernel    one wave per walked query: tests the bit of each member of W in the query's own mask, 64 entries per pass (ballot, prefix
 //                           count).  A query with k allowed members is SERVED: its first k allowed (id, distance) pairs go to its
 //                           output row (rows whose walk distances are exact over X: float32, bytes, split), or its W with the
@@ -26,12 +28,14 @@
 namespace hnsw_dev {
 
 __global__ void __launch_bounds__(256)
-filter_popcount_kernel(uint32_t *bits, int64_t words, int64_t n, unsigned long long *count) {
+filter_popcount_kernel(uint32_t *bits, int64_t words, int64_t n, unsigned long long *count, const uint32_t *and_with) {
     int c = 0;
     for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (int64_t)gridDim.x * blockDim.x) {
         uint32_t v = bits[w];
-        if (w == words - 1 && (n & 31)) {           // positions >= n of the last word are not nodes
-            v &= (1u << (n & 31)) - 1u;
+        const uint32_t keep = (and_with ? and_with[w] : ~0u) &
+                              (w == words - 1 && (n & 31) ? (1u << (n & 31)) - 1u : ~0u);     // positions >= n of the last word are not nodes
+        if ((v & keep) != v) {
+            v &= keep;
             bits[w] = v;
         }
         c += __builtin_popcount(v);
@@ -44,13 +48,14 @@ filter_popcount_kernel(uint32_t *bits, int64_t words, int64_t n, unsigned long l
 // labels[v] == l; a label of -1 is in no mask.  A wave takes 64 consecutive nodes, that is two whole words of every mask, and
 // loops over the distinct labels among them: the label of the first lane not yet done (readlane), the ballot of the lanes that
 // carry it -- its two halves are those two words of that label's mask, stored by lanes 0 and 32.  A (label, word) pair has one
-// writer, this wave, so the masks need no atomics; the counts take one atomicAdd per (wave, label).  Nodes >= n carry no label.
+// writer, this wave, so the masks need no atomics; the counts take one atomicAdd per (wave, label).  Nodes >= n carry no label,
+// and neither does a node whose bit of `live` (optional: the live mask of a handle with nodes marked deleted) is clear.
 __global__ void __launch_bounds__(256)
-filter_label_kernel(const int32_t *labels, int64_t n, int64_t words, uint32_t *const *masks, unsigned long long *counts) {
+filter_label_kernel(const int32_t *labels, int64_t n, int64_t words, uint32_t *const *masks, unsigned long long *counts, const uint32_t *live) {
     const int lane = threadIdx.x & 63;
     for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n; base += (int64_t)gridDim.x * blockDim.x) {
         const int64_t v = base + lane;
-        const int32_t lab = v < n ? labels[v] : -1;
+        const int32_t lab = v < n && (!live || ((live[v >> 5] >> (v & 31)) & 1u)) ? labels[v] : -1;
         uint64_t todo = ballot(lab >= 0);
         while (todo) {
             const int32_t l = __builtin_amdgcn_readlane(lab, (int)__builtin_ctzll(todo));
@@ -245,6 +250,50 @@ int Ladder::advance(bool &more) {
     return HNSW_OK;
 }
 
+// what every filtered entry point checks of one filter of the call
+int check_filter(const hnsw_index *idx, const hnsw_filter *f) {
+    if (!f) return fail(HNSW_ERR_BAD_ARG, "null filter");
+    if (f->idx != idx) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another index");
+    if (f->n != idx->iv.n)
+        return fail(HNSW_ERR_BAD_ARG, "the filter was made for %lld nodes, the index has grown to %lld", (long long)f->n, (long long)idx->iv.n);
+    if (f->epoch != idx->epoch)
+        return fail(HNSW_ERR_BAD_ARG, "the filter was made before the index last changed (hnsw_index_insert / hnsw_index_remove / hnsw_index_mark_deleted): it is stale");
+    return HNSW_OK;
+}
+
+// a filter of n nodes for idx (its epoch) with its mask allocated (not initialised) and the mask's own address behind it
+int new_filter(const hnsw_index *idx, int64_t n, std::unique_ptr<hnsw_filter> &f) {
+    f.reset(new hnsw_filter());
+    f->idx = idx;
+    f->n = n;
+    f->epoch = idx->epoch;
+    const size_t off = hnsw_filter::table_offset(f->n);
+    int rc;
+    if ((rc = f->bits.ensure(off + 8))) return rc;
+    const void *self = f->bits.p;
+    HIP_TRY(hipMemcpy((char *)f->bits.p + off, &self, 8, hipMemcpyHostToDevice));
+    return HNSW_OK;
+}
+
+// n_allowed of f's mask, ANDed with and_with first (optional)
+int count_filter(hnsw_filter *f, const uint32_t *and_with) {
+    const int64_t words = (f->n + 31) / 32;
+    f->n_allowed = 0;
+    if (words == 0) return HNSW_OK;
+    DevBuf count;
+    int rc;
+    if ((rc = count.ensure(8))) return rc;
+    HIP_TRY(hipMemset(count.p, 0, 8));
+    const unsigned blocks = (unsigned)std::min<int64_t>(1024, (words + 255) / 256);
+    hipLaunchKernelGGL(hnsw_dev::filter_popcount_kernel, dim3(blocks), dim3(256), 0, nullptr, (uint32_t *)f->bits.p, words, f->n,
+                       (unsigned long long *)count.p, and_with);
+    if ((rc = launched("filter popcount kernel"))) return rc;
+    unsigned long long c = 0;
+    HIP_TRY(hipMemcpy(&c, count.p, 8, hipMemcpyDeviceToHost));
+    f->n_allowed = (int64_t)c;
+    return HNSW_OK;
+}
+
 } // namespace hnsw_host
 
 namespace {
@@ -362,17 +411,6 @@ int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_para
     return launched("filter scatter kernel");
 }
 
-// what both search entry points check of one filter of the call
-int check_filter(const hnsw_index *idx, const hnsw_filter *f) {
-    if (!f) return fail(HNSW_ERR_BAD_ARG, "null filter");
-    if (f->idx != idx) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another index");
-    if (f->n != idx->iv.n)
-        return fail(HNSW_ERR_BAD_ARG, "the filter was made for %lld nodes, the index has grown to %lld", (long long)f->n, (long long)idx->iv.n);
-    if (f->epoch != idx->epoch)
-        return fail(HNSW_ERR_BAD_ARG, "the filter was made before the index last changed (hnsw_index_insert / hnsw_index_remove): its ids are stale");
-    return HNSW_OK;
-}
-
 // both search entry points once their arguments are checked (nq > 0).  fs.d_masks / fs.d_which are allocated; host_masks (the
 // per-query form): what they hold is still to be uploaded, from there and from fs.which, on the call's stream
 int filtered_call(hnsw_index *idx, const FilterSet &fs, const uint32_t *const *host_masks, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
@@ -395,20 +433,6 @@ int filtered_call(hnsw_index *idx, const FilterSet &fs, const uint32_t *const *h
     return c.finish(idx, "filtered search", st);
 }
 
-// a filter of idx's n nodes with its mask allocated (not initialised) and the mask's own address behind it
-int new_filter(hnsw_index *idx, std::unique_ptr<hnsw_filter> &f) {
-    f.reset(new hnsw_filter());
-    f->idx = idx;
-    f->n = idx->iv.n;
-    f->epoch = idx->epoch;
-    const size_t off = hnsw_filter::table_offset(f->n);
-    int rc;
-    if ((rc = f->bits.ensure(off + 8))) return rc;
-    const void *self = f->bits.p;
-    HIP_TRY(hipMemcpy((char *)f->bits.p + off, &self, 8, hipMemcpyHostToDevice));
-    return HNSW_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -422,20 +446,13 @@ int32_t hnsw_filter_create(hnsw_index *idx, const uint32_t *bits, int64_t n_bits
     HIP_TRY(hipSetDevice(idx->device));
     std::unique_ptr<hnsw_filter> f;
     int rc;
-    if ((rc = new_filter(idx, f))) return rc;
+    if ((rc = new_filter(idx, idx->iv.n, f))) return rc;
     const int64_t words = (n_bits + 31) / 32;
     if (words > 0) {
-        DevBuf count;
-        if ((rc = count.ensure(8))) return rc;
         HIP_TRY(hipMemcpy(f->bits.p, bits, (size_t)words * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(count.p, 0, 8));
-        const unsigned blocks = (unsigned)std::min<int64_t>(1024, (words + 255) / 256);
-        hipLaunchKernelGGL(hnsw_dev::filter_popcount_kernel, dim3(blocks), dim3(256), 0, nullptr, (uint32_t *)f->bits.p, words, n_bits,
-                           (unsigned long long *)count.p);
-        if ((rc = launched("filter popcount kernel"))) return rc;
-        unsigned long long c = 0;
-        HIP_TRY(hipMemcpy(&c, count.p, 8, hipMemcpyDeviceToHost));
-        f->n_allowed = (int64_t)c;
+        // (while nodes are marked deleted the mask is ANDed with the live mask: a current filter never allows a marked node)
+        const hnsw_filter *const live = live_filter(idx);
+        if ((rc = count_filter(f.get(), live ? (const uint32_t *)live->bits.p : nullptr))) return rc;
     }
     *out = f.release();
     return HNSW_OK;
@@ -458,7 +475,7 @@ int32_t hnsw_filter_create_by_label(hnsw_index *idx, const int32_t *labels, int6
     const int64_t words = (n + 31) / 32;
     int rc;
     for (int32_t l = 0; l < n_labels; ++l) {
-        if ((rc = new_filter(idx, fs[(size_t)l]))) return rc;
+        if ((rc = new_filter(idx, idx->iv.n, fs[(size_t)l]))) return rc;
         masks[(size_t)l] = (uint32_t *)fs[(size_t)l]->bits.p;
         if (words > 0) HIP_TRY(hipMemsetAsync(masks[(size_t)l], 0, (size_t)words * 4, nullptr));
     }
@@ -470,7 +487,8 @@ int32_t hnsw_filter_create_by_label(hnsw_index *idx, const int32_t *labels, int6
         HIP_TRY(hipMemset(d_counts.p, 0, (size_t)n_labels * 8));
         const unsigned blocks = (unsigned)std::min<int64_t>(4096, (n + 255) / 256);
         hipLaunchKernelGGL(hnsw_dev::filter_label_kernel, dim3(blocks), dim3(256), 0, nullptr, (const int32_t *)d_labels.p, n, words,
-                           (uint32_t *const *)d_masks.p, (unsigned long long *)d_counts.p);
+                           (uint32_t *const *)d_masks.p, (unsigned long long *)d_counts.p,
+                           live_filter(idx) ? (const uint32_t *)live_filter(idx)->bits.p : nullptr);
         if ((rc = launched("filter label kernel"))) return rc;
         std::vector<unsigned long long> counts((size_t)n_labels);
         HIP_TRY(hipMemcpy(counts.data(), d_counts.p, (size_t)n_labels * 8, hipMemcpyDeviceToHost));

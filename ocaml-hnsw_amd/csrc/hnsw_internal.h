@@ -5,6 +5,7 @@
 #include "hnsw_scan_plan.h"
 #include "hnsw_filter_plan.h"
 #include "hnsw_remove_plan.h"
+#include "hnsw_mark_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -237,6 +238,7 @@ struct RangeBufs {
     DevBuf wids[RANGE_STAGES], wdist[RANGE_STAGES];  // every stage's W ([m][e], half / sq8 rows: re-ranked), kept until the fill
     DevBuf cand, cdist, rnd;                         // one stage's walk before its re-rank; its evaluations after it
     DevBuf cnt, src, stage, nd, nh;                  // per query: segment length (int64 [nq + 1]), its row of its stage's W, counters
+    DevBuf pre;                                      // ... under a mask: the length of the in-range prefix the segment was taken from
     DevBuf counts, offs;                             // the exact scan: hits per (query, slab) (uint64 [m][slabs] + 1) and their exclusive sum
     DevBuf xcnt, xoff;                               // ... segment lengths of the exact-stage queries and where their words start ([m + 1])
     DevBuf words[2], cub;                            // ... the hits as (key << 32 | row), unsorted and sorted; hipcub's temporary storage
@@ -292,6 +294,19 @@ struct hnsw_request {
     hnsw_host::BatchBufs buf;
     hnsw_host::RefineBufs refine;        // its walk's results while option "refine" is active
     int stream = 0;
+};
+
+// an allow-mask over the nodes of one index (hnsw_filter_create): bit v of the device copy = node v (0-based) may be returned
+struct hnsw_filter {
+    const hnsw_index *idx = nullptr;     // the handle it was made for ...
+    int64_t n = 0;                       // ... and that handle's n then: a grown index refuses it
+    uint64_t epoch = 0;                  // ... and its graph epoch then: an index changed since refuses it
+    int64_t n_allowed = 0;               // set bits below n (filter_popcount_kernel)
+    // ceil(n / 32) words, the positions >= n of the last one clear; behind them (8-byte aligned) the mask's own device address:
+    // the table of one filter that the single-filter call hands the kernels
+    hnsw_host::DevBuf bits;
+    static size_t table_offset(int64_t n) { return ((size_t)std::max<int64_t>((n + 31) / 32, 1) * 4 + 7) / 8 * 8; }
+    const uint32_t *const *table() const { return (const uint32_t *const *)((const char *)bits.p + table_offset(n)); }
 };
 
 struct hnsw_index {
@@ -367,19 +382,12 @@ struct hnsw_index {
     // the graph epoch: every successful hnsw_index_insert and hnsw_index_remove moves it on (adopt_graph).  A filter records the
     // epoch it was made in: n alone would let a mask through after "remove 5, insert 5"
     uint64_t epoch = 0;
-};
-
-// an allow-mask over the nodes of one index (hnsw_filter_create): bit v of the device copy = node v (0-based) may be returned
-struct hnsw_filter {
-    const hnsw_index *idx = nullptr;     // the handle it was made for ...
-    int64_t n = 0;                       // ... and that handle's n then: a grown index refuses it
-    uint64_t epoch = 0;                  // ... and its graph epoch then: an index changed since refuses it
-    int64_t n_allowed = 0;               // set bits below n (filter_popcount_kernel)
-    // ceil(n / 32) words, the positions >= n of the last one clear; behind them (8-byte aligned) the mask's own device address:
-    // the table of one filter that the single-filter call hands the kernels
-    hnsw_host::DevBuf bits;
-    static size_t table_offset(int64_t n) { return ((size_t)std::max<int64_t>((n + 31) / 32, 1) * 4 + 7) / 8 * 8; }
-    const uint32_t *const *table() const { return (const uint32_t *const *)((const char *)bits.p + table_offset(n)); }
+    // Soft deletion (hnsw_soft_delete.hip).  live: a filter this handle owns over the mask of the nodes NOT marked deleted, made by
+    // the first hnsw_index_mark_deleted and kept current (its n and epoch are the handle's; its n_allowed is n - n_deleted); null
+    // on a handle never marked.  While n_deleted > 0 the searches answer under it (live_filter); at 0 every call takes its plain
+    // path.  Not an index table: not counted in device_bytes.
+    std::unique_ptr<hnsw_filter> live;
+    int64_t n_deleted = 0;
 };
 
 namespace hnsw_dev {
@@ -431,7 +439,10 @@ int finish_index(IndexPtr idx, int32_t expected_ef, int32_t expected_semantics, 
 // entry point is not on the top layer: what hnsw_index_insert and hnsw_index_remove ask before they follow the rows (n > 0)
 int check_upper_rows(const ::hnsw_index *idx, const char *verb);
 // hnsw_build.hip: the end of hnsw_index_insert and hnsw_index_remove: nx's graph tables become idx's (see there)
-int adopt_graph(::hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics);
+// new_id: how the nodes were renumbered (hnsw_index_remove: RemovePlan::new_id; null: ids kept, hnsw_index_insert) -- what the
+// marks of soft deletion follow
+int adopt_graph(::hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics,
+                const int32_t *new_id = nullptr);
 
 // hnsw_rows8.hip: if every value of tables.X is an integer in 0..255, build the byte copy (tables.X8, iv.stride8)
 int make_byte_rows(::hnsw_index *idx);
@@ -529,6 +540,19 @@ ScanCut scan_cut(const ::hnsw_index *idx, int64_t m, int k, int64_t cell_bytes, 
 inline bool walk_is_inexact(const ::hnsw_index *idx) {
     return idx->info.row_format == HNSW_ROWS_HALF || idx->info.row_format == HNSW_ROWS_SQ8;
 }
+// the filter the unfiltered searches answer under: the live nodes while some are marked deleted, else none
+inline const ::hnsw_filter *live_filter(const ::hnsw_index *idx) { return idx->n_deleted > 0 ? idx->live.get() : nullptr; }
+// hnsw_filter.hip: what every filtered entry point checks of one filter of the call (null, foreign, outgrown, stale: HNSW_ERR_BAD_ARG)
+int check_filter(const ::hnsw_index *idx, const ::hnsw_filter *f);
+// hnsw_filter.hip: a filter of idx's n nodes (and epoch) with its mask allocated (not initialised) and the mask's own address behind it
+int new_filter(const ::hnsw_index *idx, int64_t n, std::unique_ptr<::hnsw_filter> &f);
+// hnsw_filter.hip: f's n_allowed counted on the device (filter_popcount_kernel; the bits past n cleared); and_with (optional, device
+// words): the mask is ANDed with it first
+int count_filter(::hnsw_filter *f, const uint32_t *and_with);
+// hnsw_soft_delete.hip: the live mask an index of n_new nodes gets when nx replaces idx's graph (adopt_graph, before the swap):
+// new_id (host, [idx->iv.n], 0-based, -1 = removed; null: every node keeps its id and the nodes from idx->iv.n on are new and live).
+// out stays null when idx has no marked node.
+int renumbered_live_filter(const ::hnsw_index *idx, const int32_t *new_id, int64_t n_new, std::unique_ptr<::hnsw_filter> &out);
 // hnsw_filter.hip: the escalation both the filtered and the range search run -- e = ef, 2 ef, ... 1024: the batch is walked with
 // (ef = k = e, raw_walk), the caller's select kernel serves what it can and appends the other queries to the short list
 // (ladder_settle) and only those, gathered into one compact batch, are walked again.  Everything is queued on st and waited for

@@ -15,12 +15,19 @@
 //                           wave finds first (range_key_bounds).  PASS 0 counts the hits per (query, slab); PASS 1 runs the same
 //                           loop and writes the word (key << 32 | row) of each hit at the (query, slab)'s offset plus the hit's
 //                           position among the slab's hits in id order (ballot, prefix count): the layout is deterministic.
+//   hnsw_range_scan_masked_kernel<NCH, METRIC, PASS>  the same two passes over the rows an allow-mask names (the filtered range
+//                           calls; the plain ones while nodes are marked deleted): RangeHits<.., MASKED = true>, whose skip / admits
+//                           are those of ScanTopK<NCH, true> -- a disallowed row is never counted, stored or sorted, and a mask
+//                           word without a set bit is stepped over unloaded.
 //   range_count_kernel      per exact-stage query the sum of its slabs' counts (from the exclusive sum), its counters and stage.
 //   range_unpack_kernel     the sorted words of an exact-stage query as ids (+ id_base) and key_to_dist.
 //   range_select_kernel     one wave per walked query: |W| and the length of W's in-range prefix, 64 entries per pass (ballot).
-//                           Served: its count, stage and row.  Saturated: appended to the short list (ladder_settle); the ladder
+//                           Served: its count, stage and row.  Under a mask the stage test is the same one (the mask has no say in
+//                           "saturated"); a served query records the prefix length and the number of allowed members in it: the
+//                           second is its segment length.  Saturated: appended to the short list (ladder_settle); the ladder
 //                           (Ladder, hnsw_filter.hip) gathers them for the next walk.
-//   range_fill_kernel       the served queries' prefixes from their stages' W to lims[q], once every size is known.
+//   range_fill_kernel       the served queries' prefixes from their stages' W to lims[q], once every size is known.  Under a mask:
+//                           the allowed members of the prefix, compacted by ballot and prefix count, 64 entries per pass, in W's order.
 // Between the scan's passes: an exclusive sum of the counts (hipcub::DeviceScan), the grand total read on the host, the result
 // allocated.  After the fill hipcub::DeviceSegmentedRadixSort orders each exact-stage segment by its 64-bit words: ascending words
 // = the total order (distance key, node id), no drops however many ties.  Vector stores only.  All scratch is the handle's
@@ -61,7 +68,21 @@ template <int METRIC> __device__ __forceinline__ void range_key_bounds(float rad
 }
 
 // The hits of one (tile, slab) wave (scan_slab's Select): counted (PASS 0), or written where PASS 0's counts say (PASS 1)
-template <int NCH, int METRIC, int PASS> struct RangeHits {
+// MASKED: as ScanTopK<NCH, true> -- one bit per row, bit row & 31 of word row >> 5, ceil(n / 32) words; a row whose bit is clear is
+// no hit, and a 32-row word without a set bit is stepped over without loading its rows.  (The mask is a base the unmasked form does
+// not have: its kernels are what they were before there was a mask.)
+template <bool MASKED> struct RangeMask {
+    MaskWords mask;
+    __device__ __forceinline__ explicit RangeMask(const uint32_t *mask_) : mask(mask_words(mask_)) {}
+    __device__ __forceinline__ bool skip(int64_t base) const { return uniform((int)mask[base >> 5]) == 0; }
+    __device__ __forceinline__ bool admits(int64_t row, bool in_slab) const { return in_slab && ((mask[row >> 5] >> (row & 31)) & 1u); }
+};
+template <> struct RangeMask<false> {
+    __device__ __forceinline__ explicit RangeMask(const uint32_t *) {}
+    __device__ __forceinline__ bool skip(int64_t) const { return false; }
+    __device__ __forceinline__ bool admits(int64_t, bool in_slab) const { return in_slab; }
+};
+template <int NCH, int METRIC, int PASS, bool MASKED = false> struct RangeHits : RangeMask<MASKED> {
     static constexpr int T = scan_tile(NCH);
     const RangeScanArgs &a;
     uint32_t klo, khi;
@@ -71,7 +92,7 @@ template <int NCH, int METRIC, int PASS> struct RangeHits {
     int cnt[T], lim[T];
     uint64_t *dst[T];
 
-    __device__ __forceinline__ explicit RangeHits(const RangeScanArgs &a_) : a(a_) {}
+    __device__ __forceinline__ explicit RangeHits(const RangeScanArgs &a_, const uint32_t *mask_ = nullptr) : RangeMask<MASKED>(mask_), a(a_) {}
     __device__ __forceinline__ void begin(int64_t q0_, int tq_, int64_t slab_) {
         q0 = q0_; tq = tq_; slab = slab_;
         lane = threadIdx.x & 63;
@@ -89,8 +110,6 @@ template <int NCH, int METRIC, int PASS> struct RangeHits {
             }
         }
     }
-    __device__ __forceinline__ bool skip(int64_t) const { return false; }
-    __device__ __forceinline__ bool admits(int64_t, bool in_slab) const { return in_slab; }
     __device__ __forceinline__ void take(int t, uint32_t key, int64_t row, bool ok) {
         // a query past the tile's end has no hits; the rows of a batch lie in lane order: r ascending = id ascending
         const bool hit = (lane & 15) == 0 && ok && t < tq && key >= klo && key <= khi;
@@ -120,12 +139,20 @@ hnsw_range_scan_kernel(const IndexView iv, const RangeScanArgs a) {
     scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
 
+// ... restricted to the rows `mask` allows (a kernel argument: scalar loads, wave-uniform tests)
+template <int NCH, int METRIC, int PASS>
+__global__ void __launch_bounds__(64 * SCAN_WAVES, scan_min_waves(NCH))
+hnsw_range_scan_masked_kernel(const IndexView iv, const RangeScanArgs a, const uint32_t *mask) {
+    RangeHits<NCH, METRIC, PASS, true> sel(a, mask);
+    scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
+}
+
 struct RangeCountArgs {
     const uint64_t *offs;      // [m * n_slabs + 1]
     int64_t m;
     int32_t n_slabs;
     const int32_t *map;        // [m] row i belongs to query map[i]; null: to query i
-    uint32_t n;                // the rows scanned
+    uint32_t n;                // the rows scanned (under a mask: the allowed ones)
     int32_t fresh;             // 1: the query took no walk: out_nd starts from 0 and out_nh is 0
     int64_t *cnt, *xcnt;       // [nq] by query, [m] by row
     uint32_t *out_nd, *out_nh, *out_stage;
@@ -171,7 +198,16 @@ struct RangeSelectArgs {
     int64_t *cnt;              // [nq] a served query's segment length
     int32_t *src;              // [nq] ... and its row of this stage's W
     LadderOut out;             // (its evaluations: the re-rank's included)
+    const uint32_t *mask;      // null, or the allow-mask (ceil(n / 32) words): the segment is the allowed members of the prefix
+    int64_t n;
+    int32_t *pre;              // [nq] under a mask: the served query's prefix length
 };
+
+// is the id_base-based id one of the n nodes, and allowed
+__device__ __forceinline__ bool range_allows(MaskWords bits, int64_t n, int32_t id_base, int32_t id) {
+    const int64_t v = (int64_t)id - id_base;
+    return v >= 0 && v < n && ((bits[v >> 5] >> (v & 31)) & 1u);
+}
 
 __global__ void __launch_bounds__(64)
 range_select_kernel(const RangeSelectArgs a) {
@@ -179,16 +215,20 @@ range_select_kernel(const RangeSelectArgs a) {
     const int64_t i = blockIdx.x;
     if (i >= a.m) return;
     const int64_t q = a.map ? a.map[i] : i;
-    int in = 0;                // W is ascending: its members in range are a prefix
+    const MaskWords bits = mask_words(a.mask);
+    int in = 0, al = 0;        // W is ascending: its members in range are a prefix; al: the allowed ones among them
     for (int j0 = 0; j0 < a.e; j0 += 64) {
         const int j = j0 + lane;
-        in += popc(ballot(j < a.e && a.wids[i * a.e + j] >= a.id_base && a.wdist[i * a.e + j] <= a.radius));
+        const bool hit = j < a.e && a.wids[i * a.e + j] >= a.id_base && a.wdist[i * a.e + j] <= a.radius;
+        in += popc(ballot(hit));
+        if (a.mask) al += popc(ballot(hit && range_allows(bits, a.n, a.id_base, a.wids[i * a.e + j])));
     }
-    // saturated: |W| = e and its last member is in range, that is all e entries are
+    // saturated: |W| = e and its last member is in range, that is all e entries are -- whatever the mask says
     if (lane == 0) {
         if (in < a.e) {
-            a.cnt[q] = in;
+            a.cnt[q] = a.mask ? al : in;
             a.src[q] = (int32_t)i;
+            if (a.mask) a.pre[q] = in;
         }
         ladder_settle(a.out, i, q, in < a.e);
     }
@@ -205,6 +245,10 @@ struct RangeFillArgs {
     const int64_t *lims;       // [nq + 1]
     int32_t *ids;
     float *dist;
+    const uint32_t *mask;      // null, or the allow-mask: only the allowed members of the prefix [0, pre[q]) are copied
+    int64_t n;
+    int32_t id_base;
+    const int32_t *pre;        // [nq]
 };
 
 __global__ void __launch_bounds__(64)
@@ -214,6 +258,24 @@ range_fill_kernel(const RangeFillArgs a) {
     const uint32_t s = a.stage[q];
     if (s >= (uint32_t)a.n_stages) return;          // the exact stage writes its own
     const int64_t to = a.lims[q], c = a.lims[q + 1] - to, from = (int64_t)a.src[q] * a.e[s];
+    if (a.mask) {               // W's order kept: an entry's place is the number of allowed entries before it
+        const MaskWords bits = mask_words(a.mask);
+        const int lane = threadIdx.x, pre = a.pre[q];
+        int64_t at = 0;
+        for (int j0 = 0; j0 < pre && at < c; j0 += 64) {
+            const int j = j0 + lane;
+            const int32_t id = j < pre ? a.wids[s][from + j] : a.id_base - 1;
+            const bool ok = j < pre && range_allows(bits, a.n, a.id_base, id);
+            const uint64_t m = ballot(ok);
+            const int64_t pos = at + popc(m & ((1ull << lane) - 1ull));
+            if (ok && pos < c) {
+                a.ids[to + pos] = id;
+                a.dist[to + pos] = a.wdist[s][from + j];
+            }
+            at += popc(m);
+        }
+        return;
+    }
     for (int64_t j = threadIdx.x; j < c; j += 64) {
         a.ids[to + j] = a.wids[s][from + j];
         a.dist[to + j] = a.wdist[s][from + j];
@@ -253,13 +315,17 @@ struct ExactPlan : ScanCut {
     const float *Q = nullptr;
     int64_t m = 0, q_stride = 0;
     const int32_t *map = nullptr;
+    const uint32_t *mask = nullptr;    // the call's allow-mask (device words), null: every row
+    int64_t n_allowed = 0;             // ... and how many rows it allows: what the exact stage adds to out_ndist (no mask: n)
     // (a count and an offset per (query, slab) cell)
     void cut(const hnsw_index *idx) { static_cast<ScanCut &>(*this) = scan_cut(idx, m, 1, 16, m); }
 };
 
 int launch_range_scan(const hnsw_index *idx, const ExactPlan &x, int pass, int64_t nq, const hnsw_dev::RangeScanArgs &a, hipStream_t st) {
     with_metric(idx->info.metric, [&](auto METRIC) { with_nch(x.nch, [&](auto NCH) {
-        if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 0>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a);
+        if (x.mask && pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_masked_kernel<NCH, METRIC, 0>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a, x.mask);
+        else if (x.mask) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_masked_kernel<NCH, METRIC, 1>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a, x.mask);
+        else if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 0>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a);
         else hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 1>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a);
     }); });
     return launched("range scan kernel");
@@ -293,7 +359,7 @@ int exact_count(hnsw_index *idx, const ExactPlan &x, float radius, bool fresh, h
     for (int64_t i0 = 0; i0 < x.m; i0 += x.piece) {
         const int64_t mp = std::min(x.piece, x.m - i0);
         if ((rc = exact_count_piece(idx, x, radius, i0, mp, st))) return rc;
-        const hnsw_dev::RangeCountArgs ca{(const uint64_t *)rb.offs.p, mp, (int32_t)x.slabs, x.map ? x.map + i0 : nullptr, (uint32_t)idx->iv.n, fresh,
+        const hnsw_dev::RangeCountArgs ca{(const uint64_t *)rb.offs.p, mp, (int32_t)x.slabs, x.map ? x.map + i0 : nullptr, (uint32_t)x.n_allowed, fresh,
                                           x.map ? (int64_t *)rb.cnt.p : (int64_t *)rb.cnt.p + i0, (int64_t *)rb.xcnt.p + i0,
                                           x.map ? (uint32_t *)rb.nd.p : (uint32_t *)rb.nd.p + i0, x.map ? (uint32_t *)rb.nh.p : (uint32_t *)rb.nh.p + i0,
                                           x.map ? (uint32_t *)rb.stage.p : (uint32_t *)rb.stage.p + i0};
@@ -342,7 +408,7 @@ int exact_fill(hnsw_index *idx, const ExactPlan &x, float radius, hnsw_range_res
 
 // The ladder for the batch (Q, nq, q_stride) on st: cnt / src / stage / nd / nh of the served queries in the handle's scratch,
 // the saturated ones left in x (gathered); e_of: the row length of each stage walked.  d_stage: see knn_search.
-int range_ladder(hnsw_index *idx, const hnsw_range_params &p, const float *Q, int64_t nq, int64_t q_stride, float *d_stage, hipStream_t st,
+int range_ladder(hnsw_index *idx, const hnsw_filter *f, const hnsw_range_params &p, const float *Q, int64_t nq, int64_t q_stride, float *d_stage, hipStream_t st,
                  ExactPlan &x, std::vector<int32_t> &e_of) {
     RangeBufs &rb = idx->range_scratch;
     const bool rerank = walk_is_inexact(idx);
@@ -363,7 +429,8 @@ int range_ladder(hnsw_index *idx, const hnsw_range_params &p, const float *Q, in
             return rc;
         const hnsw_dev::RangeSelectArgs sa{(const int32_t *)Wi.p, (const float *)Wd.p, m, e, L.map, p.radius, idx->iv.id_base, (int64_t *)rb.cnt.p,
                                            (int32_t *)rb.src.p,
-                                           L.out(rerank ? (const uint32_t *)rb.rnd.p : L.wb.nd, (uint32_t *)rb.nd.p, (uint32_t *)rb.nh.p, (uint32_t *)rb.stage.p)};
+                                           L.out(rerank ? (const uint32_t *)rb.rnd.p : L.wb.nd, (uint32_t *)rb.nd.p, (uint32_t *)rb.nh.p, (uint32_t *)rb.stage.p),
+                                           f ? (const uint32_t *)f->bits.p : nullptr, idx->iv.n, (int32_t *)rb.pre.p};
         hipLaunchKernelGGL(hnsw_dev::range_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
         if ((rc = launched("range select kernel")) || (rc = L.count_short())) return rc;
         if (L.n_short == 0) return HNSW_OK;
@@ -373,8 +440,9 @@ int range_ladder(hnsw_index *idx, const hnsw_range_params &p, const float *Q, in
     return HNSW_OK;
 }
 
-// Both entry points: p null = the brute-force form (every query is the exact stage's).  *out is set on success only.
-int range_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_range_params *p, float radius, hnsw_range_result **out) {
+// All four entry points: p null = the brute-force form (every query is the exact stage's); f null = no mask (the unfiltered entry
+// points on a handle without marked nodes).  *out is set on success only.
+int range_call(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride, const hnsw_range_params *p, float radius, hnsw_range_result **out) {
     HIP_TRY(hipSetDevice(idx->device));
     std::unique_ptr<hnsw_range_result> r(new hnsw_range_result());
     r->device = idx->device;
@@ -386,8 +454,20 @@ int range_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stri
         *out = r.release();
         return HNSW_OK;
     }
+    if (f && f->n_allowed == 0) {       // no node allowed: no walk, every segment empty
+        if ((rc = r->nd.ensure((size_t)nq * 4)) || (rc = r->nh.ensure((size_t)nq * 4)) || (rc = r->stage.ensure((size_t)nq * 4)) ||
+            (rc = r->ids.ensure(4)) || (rc = r->dist.ensure(4)))
+            return rc;
+        HIP_TRY(hipMemset(r->lims.p, 0, (size_t)(nq + 1) * 8));
+        HIP_TRY(hipMemset(r->nd.p, 0, (size_t)nq * 4));
+        HIP_TRY(hipMemset(r->nh.p, 0, (size_t)nq * 4));
+        HIP_TRY(hipMemset(r->stage.p, 0xFF, (size_t)nq * 4));
+        HIP_TRY(hipDeviceSynchronize());
+        *out = r.release();
+        return HNSW_OK;
+    }
     RangeBufs &rb = idx->range_scratch;
-    if ((rc = rb.cnt.ensure((size_t)(nq + 1) * 8)) || (rc = rb.src.ensure((size_t)nq * 4)) || (rc = rb.stage.ensure((size_t)nq * 4)) ||
+    if ((rc = rb.cnt.ensure((size_t)(nq + 1) * 8)) || (rc = rb.src.ensure((size_t)nq * 4)) || (rc = rb.pre.ensure((size_t)nq * 4)) || (rc = rb.stage.ensure((size_t)nq * 4)) ||
         (rc = rb.nd.ensure((size_t)nq * 4)) || (rc = rb.nh.ensure((size_t)nq * 4)) || (rc = r->nd.ensure((size_t)nq * 4)) ||
         (rc = r->nh.ensure((size_t)nq * 4)) || (rc = r->stage.ensure((size_t)nq * 4)))
         return rc;
@@ -397,9 +477,11 @@ int range_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stri
     hipStream_t st = idx->hs[0];
     // from here on work is queued that reads the caller's queries: no return without a synchronisation
     ExactPlan x;
+    x.mask = f ? (const uint32_t *)f->bits.p : nullptr;
+    x.n_allowed = f ? f->n_allowed : idx->iv.n;
     std::vector<int32_t> e_of;
     if (p) {
-        rc = range_ladder(idx, *p, c.b.Q, nq, q_stride, q_in_place ? (float *)idx->scratch.q.p : nullptr, st, x, e_of);
+        rc = range_ladder(idx, f, *p, c.b.Q, nq, q_stride, q_in_place ? (float *)idx->scratch.q.p : nullptr, st, x, e_of);
     } else {
         x.Q = c.b.Q; x.m = nq; x.q_stride = q_stride; x.map = nullptr;
     }
@@ -426,6 +508,7 @@ int range_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stri
         }
         fa.nq = nq; fa.stage = (const uint32_t *)rb.stage.p; fa.src = (const int32_t *)rb.src.p; fa.lims = (const int64_t *)r->lims.p;
         fa.ids = (int32_t *)r->ids.p; fa.dist = (float *)r->dist.p;
+        fa.mask = x.mask; fa.n = idx->iv.n; fa.id_base = idx->iv.id_base; fa.pre = (const int32_t *)rb.pre.p;
         hipLaunchKernelGGL(hnsw_dev::range_fill_kernel, dim3((unsigned)nq), dim3(64), 0, st, fa);
         rc = launched("range fill kernel");
     }
@@ -455,8 +538,9 @@ int check_range(const hnsw_index *idx, int64_t nq, int64_t q_stride, const float
 
 extern "C" {
 
-int32_t hnsw_range_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_range_params *params,
-                                hnsw_range_result **out) {
+// the two ladder entry points: `filtered` = f is the caller's and is checked; else f is null and the handle's marks decide
+static int32_t range_search_entry(hnsw_index *idx, bool filtered, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                  const hnsw_range_params *params, hnsw_range_result **out) {
     if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
     *out = nullptr;
     if (!params) return fail(HNSW_ERR_BAD_ARG, "null params");
@@ -468,19 +552,41 @@ int32_t hnsw_range_search_batch(hnsw_index *idx, const float *queries, int64_t n
         return fail(HNSW_ERR_BAD_ARG, "the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no range meaning");
     if (params->semantics != HNSW_SEM_OHNSW && params->semantics != HNSW_SEM_FUNCTOR) return fail(HNSW_ERR_BAD_ARG, "bad semantics %d", params->semantics);
     if (idx->iv.entry_point < 0) return fail(HNSW_ERR_EMPTY_INDEX, "range search: empty hgraph");
-    const int rc = check_range(idx, nq, q_stride, queries, params->radius);
+    int rc = check_range(idx, nq, q_stride, queries, params->radius);
     if (rc) return rc;
-    return range_call(idx, queries, nq, q_stride, params, params->radius, out);
+    if (filtered && (rc = check_filter(idx, f))) return rc;
+    return range_call(idx, filtered ? f : live_filter(idx), queries, nq, q_stride, params, params->radius, out);
 }
 
-int32_t hnsw_range_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, float radius, hnsw_range_result **out) {
+static int32_t range_brute_entry(hnsw_index *idx, bool filtered, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                 float radius, hnsw_range_result **out) {
     if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
     *out = nullptr;
     if (std::isnan(radius)) return fail(HNSW_ERR_BAD_ARG, "the radius is NaN");
     if (!idx) return fail(HNSW_ERR_BAD_ARG, "null index");
-    const int rc = check_range(idx, nq, q_stride, queries, radius);
+    int rc = check_range(idx, nq, q_stride, queries, radius);
     if (rc) return rc;
-    return range_call(idx, queries, nq, q_stride, nullptr, radius, out);
+    if (filtered && (rc = check_filter(idx, f))) return rc;
+    return range_call(idx, filtered ? f : live_filter(idx), queries, nq, q_stride, nullptr, radius, out);
+}
+
+int32_t hnsw_range_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_range_params *params,
+                                hnsw_range_result **out) {
+    return range_search_entry(idx, false, nullptr, queries, nq, q_stride, params, out);
+}
+
+int32_t hnsw_range_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                         const hnsw_range_params *params, hnsw_range_result **out) {
+    return range_search_entry(idx, true, f, queries, nq, q_stride, params, out);
+}
+
+int32_t hnsw_range_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, float radius, hnsw_range_result **out) {
+    return range_brute_entry(idx, false, nullptr, queries, nq, q_stride, radius, out);
+}
+
+int32_t hnsw_range_brute_force_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                              float radius, hnsw_range_result **out) {
+    return range_brute_entry(idx, true, f, queries, nq, q_stride, radius, out);
 }
 
 int32_t hnsw_range_result_size(const hnsw_range_result *r, int64_t *nq, int64_t *total) {

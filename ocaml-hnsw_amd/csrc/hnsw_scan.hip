@@ -284,7 +284,10 @@ extern "C" {
 
 int32_t hnsw_brute_force_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride, int32_t k, int32_t fill,
                                       int32_t *d_ids, float *d_dist, void *stream) {
-    return scan_search(idx, {d_queries, nq, q_stride, d_ids, d_dist, nullptr, nullptr, nullptr, nullptr}, k, fill, (hipStream_t)stream);
+    // (while nodes are marked deleted: the k smallest LIVE nodes, the masked scan under the handle's live mask)
+    const hnsw_filter *const live = idx ? live_filter(idx) : nullptr;
+    return scan_search(idx, {d_queries, nq, q_stride, d_ids, d_dist, nullptr, nullptr, nullptr, nullptr}, k, fill, (hipStream_t)stream,
+                       live ? live->table() : nullptr);
 }
 
 int32_t hnsw_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int32_t k, int32_t fill,
@@ -294,7 +297,8 @@ int32_t hnsw_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq
     HIP_TRY(hipSetDevice(idx->device));
     HostCall c;
     if ((rc = c.begin(idx, queries, nq, q_stride, k, out_ids, out_dist, nullptr, nullptr, false))) return rc;
-    rc = scan_search(idx, c.b, k, fill, idx->hs[0]);
+    const hnsw_filter *const live = live_filter(idx);
+    rc = scan_search(idx, c.b, k, fill, idx->hs[0], live ? live->table() : nullptr);
     if (rc) { (void)hipStreamSynchronize(idx->hs[0]); return rc; }
     return c.finish(idx, "scan", idx->hs[0]);
 }

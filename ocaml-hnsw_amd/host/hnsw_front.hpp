@@ -6,7 +6,8 @@
 //   Hnsw::Filter, Hnsw::Ohnsw::knn_filtered                                                (hnsw_filter_*, hnsw_search_batch_filtered)
 //   Hnsw::Filter::by_label / bits, Hnsw::Ohnsw::knn_filtered_each                          (hnsw_filter_create_by_label, hnsw_filter_bits,
 //                                                                                           hnsw_search_batch_filtered_each)
-//   Hnsw::RangeResult, Hnsw::Ohnsw::range_search / brute_force_range                       (hnsw_range_*)
+//   Hnsw::RangeResult, Hnsw::Ohnsw::range_search / brute_force_range                       (hnsw_range_*; with a Filter: the _filtered forms)
+//   Hnsw::Ohnsw::mark_deleted / unmark_deleted / deleted_count / deleted_mask / compact    (hnsw_index_mark_deleted ... hnsw_index_compact)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
@@ -247,6 +248,30 @@ inline std::vector<int32_t> remove(Hgraph &g, const std::vector<int64_t> &ids) {
     return new_id;
 }
 
+// Soft deletion owned by the index (hnsw_index_mark_deleted): the stored nodes `ids` (id_base-based, distinct) stay in the graph but
+// no search returns them any more -- while any node is marked the knn, brute-force and range searches answer under the mask of the
+// live nodes.  unmark_deleted makes them live again; compact is remove() of the marked nodes (the new id of every old node).
+inline void mark_deleted(Hgraph &g, const std::vector<int64_t> &ids) { check(hnsw_index_mark_deleted(g.handle(), ids.data(), (int64_t)ids.size())); }
+inline void unmark_deleted(Hgraph &g, const std::vector<int64_t> &ids) { check(hnsw_index_unmark_deleted(g.handle(), ids.data(), (int64_t)ids.size())); }
+inline int64_t deleted_count(const Hgraph &g) { int64_t c = 0; check(hnsw_index_deleted_count(g.handle(), &c)); return c; }
+// one entry per node: node v + id_base is marked (hnsw_index_deleted_bits)
+inline std::vector<bool> deleted_mask(const Hgraph &g) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    std::vector<uint32_t> w((size_t)((inf.n + 31) / 32) + 1, 0u);
+    check(hnsw_index_deleted_bits(g.handle(), w.data()));
+    std::vector<bool> out((size_t)inf.n);
+    for (int64_t v = 0; v < inf.n; ++v) out[(size_t)v] = (w[(size_t)(v >> 5)] >> (v & 31)) & 1u;
+    return out;
+}
+inline std::vector<int32_t> compact(Hgraph &g) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    std::vector<int32_t> new_id((size_t)inf.n);
+    check(hnsw_index_compact(g.handle(), new_id.data()));
+    return new_id;
+}
+
 // Ohnsw.knn hgraph visited ~k target (lib/ohnsw.ml:859-875): the MinQueue popped ascending.
 inline std::vector<value_distance> knn(const Hgraph &g, int k, const float *target) {
     std::vector<int32_t> ids; std::vector<float> dist;
@@ -311,6 +336,20 @@ inline RangeResult range_search(const Hgraph &g, float radius, const Mat &batch,
 inline RangeResult brute_force_range(const Hgraph &g, float radius, const Mat &batch) {
     hnsw_range_result *r = nullptr;
     check(hnsw_range_brute_force_batch(g.handle(), batch.data, batch.dim2, batch.dim1, radius, &r));
+    return RangeResult(r);
+}
+
+// ... both under an allow-mask (hnsw_range_search_batch_filtered, hnsw_range_brute_force_batch_filtered): each segment is the
+// unfiltered one with the nodes the Filter does not allow left out; stage and hops are the unfiltered call's
+inline RangeResult range_search(const Hgraph &g, const Filter &f, float radius, const Mat &batch, int ef = 64, int sem = HNSW_SEM_OHNSW) {
+    hnsw_range_params p{radius, ef, sem};
+    hnsw_range_result *r = nullptr;
+    check(hnsw_range_search_batch_filtered(g.handle(), f.handle(), batch.data, batch.dim2, batch.dim1, &p, &r));
+    return RangeResult(r);
+}
+inline RangeResult brute_force_range(const Hgraph &g, const Filter &f, float radius, const Mat &batch) {
+    hnsw_range_result *r = nullptr;
+    check(hnsw_range_brute_force_batch_filtered(g.handle(), f.handle(), batch.data, batch.dim2, batch.dim1, radius, &r));
     return RangeResult(r);
 }
 

@@ -171,6 +171,13 @@ let hnsw_range_search_batch =
 let hnsw_range_brute_force_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_range_brute_force_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> float @-> ptr range_handle @-> returning int32_t)
+(* ... under an allow-mask: each segment is the unfiltered one with the nodes the filter does not allow left out *)
+let hnsw_range_search_batch_filtered =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_range_search_batch_filtered"
+    (index @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr range_params @-> ptr range_handle @-> returning int32_t)
+let hnsw_range_brute_force_batch_filtered =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_range_brute_force_batch_filtered"
+    (index @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> float @-> ptr range_handle @-> returning int32_t)
 let hnsw_range_result_size =
   foreign ~from:lib "hnsw_range_result_size" (range_handle @-> ptr int64_t @-> ptr int64_t @-> returning int32_t)
 let hnsw_range_result_fetch =
@@ -206,6 +213,15 @@ let hnsw_index_insert =
 let hnsw_index_remove =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_remove"
     (index @-> ptr int64_t @-> int64_t @-> ptr int32_t @-> returning int32_t)
+(* soft deletion owned by the index (see the C header): mark, search around, compact *)
+let hnsw_index_mark_deleted =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_mark_deleted" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
+let hnsw_index_unmark_deleted =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_unmark_deleted" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
+let hnsw_index_deleted_count = foreign ~from:lib "hnsw_index_deleted_count" (index @-> ptr int64_t @-> returning int32_t)
+let hnsw_index_deleted_bits = foreign ~from:lib "hnsw_index_deleted_bits" (index @-> ptr uint32_t @-> returning int32_t)
+let hnsw_index_compact =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_compact" (index @-> ptr int32_t @-> returning int32_t)
 let hnsw_index_save = foreign ~from:lib ~release_runtime_lock:true "hnsw_index_save" (index @-> string @-> returning int32_t)
 let hnsw_index_load =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_load" (string @-> int32_t @-> ptr index @-> returning int32_t)
@@ -935,20 +951,35 @@ let fetch_range (r : range_handle) : (int * float) array array * int array =
            Array.init (b - a) (fun j -> (Int32.to_int (CArray.get ids (a + j)), CArray.get dist (a + j)))),
        Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s)))
 
-(* ~semantics: 0 Ohnsw's accept rule, 1 the functor's (2 is refused); ~ef: the ladder's first stage, 1..1024 *)
-let range_search ?(semantics = 0) (t : t) (batch : Lacaml.S.mat) ~radius ~ef : (int * float) array array * int array =
+(* ~semantics: 0 Ohnsw's accept rule, 1 the functor's (2 is refused); ~ef: the ladder's first stage, 1..1024; ?filter
+   (hnsw_range_search_batch_filtered): each segment is the unfiltered one with the nodes the filter does not allow left out, the
+   stages are the unfiltered call's *)
+let range_search ?(semantics = 0) ?(filter : filter option) (t : t) (batch : Lacaml.S.mat) ~radius ~ef
+    : (int * float) array array * int array =
   let nq = A2.dim2 batch in
   let p = make range_params in
   setf p r_radius radius; setf p r_ef (Int32.of_int ef); setf p r_semantics (Int32.of_int semantics);
   let out = allocate range_handle null in
-  check (hnsw_range_search_batch t.handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) (addr p) out);
+  (match filter with
+   | None ->
+     check (hnsw_range_search_batch t.handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) (addr p) out)
+   | Some f ->
+     check (hnsw_range_search_batch_filtered t.handle f.f_handle (bigarray_start array2 batch) (Int64.of_int nq)
+              (Int64.of_int t.dim) (addr p) out);
+     ignore (Sys.opaque_identity f));      (* (alive until the call has returned) *)
   fetch_range !@out
 
 (* the exact form: per query the in-range prefix of the full order over all stored vectors; needs no graph *)
-let brute_force_range (t : t) (batch : Lacaml.S.mat) ~radius : (int * float) array array =
+let brute_force_range ?(filter : filter option) (t : t) (batch : Lacaml.S.mat) ~radius : (int * float) array array =
   let nq = A2.dim2 batch in
   let out = allocate range_handle null in
-  check (hnsw_range_brute_force_batch t.handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) radius out);
+  (match filter with
+   | None ->
+     check (hnsw_range_brute_force_batch t.handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) radius out)
+   | Some f ->
+     check (hnsw_range_brute_force_batch_filtered t.handle f.f_handle (bigarray_start array2 batch) (Int64.of_int nq)
+              (Int64.of_int t.dim) radius out);
+     ignore (Sys.opaque_identity f));
   fst (fetch_range !@out)
 
 (* brute_force_knn_l2 (benchmark/dataset.ml:15-30) with its body on the device: the distance matrix it returns
@@ -1025,6 +1056,39 @@ let remove_batch t (ids : int array) : int array =
   let c_ids = CArray.make int64_t (max m 1) and c_new = CArray.make int32_t (max n_old 1) in
   Array.iteri (fun i v -> CArray.set c_ids i (Int64.of_int v)) ids;
   check (hnsw_index_remove t.handle (CArray.start c_ids) (Int64.of_int m) (CArray.start c_new));
+  Array.init n_old (fun v -> Int32.to_int (CArray.get c_new v))
+
+(* Soft deletion owned by the index (hnsw_index_mark_deleted ...): the stored nodes [ids] (id_base-based, distinct) stay in the
+   graph -- every walk still goes through them -- but no search returns them any more: while any node is marked the knn,
+   brute-force and range searches answer under the mask of the live nodes, and new filters are ANDed with it.  [unmark_deleted]
+   makes them live again; [compact] is [remove_batch] of the marked nodes (the new id of every old node, nothing marked after). *)
+let change_marks call t (ids : int array) =
+  let m = Array.length ids in
+  let c_ids = CArray.make int64_t (max m 1) in
+  Array.iteri (fun i v -> CArray.set c_ids i (Int64.of_int v)) ids;
+  check (call t.handle (CArray.start c_ids) (Int64.of_int m))
+let mark_deleted t (ids : int array) = change_marks hnsw_index_mark_deleted t ids
+let unmark_deleted t (ids : int array) = change_marks hnsw_index_unmark_deleted t ids
+let deleted_count t : int =
+  let c = allocate int64_t 0L in
+  check (hnsw_index_deleted_count t.handle c);
+  Int64.to_int !@c
+(* one bool per node: node v + id_base is marked *)
+let deleted_mask t : bool array =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let n = Int64.to_int (getf inf ii_n) in
+  let words = CArray.make uint32_t ~initial:Unsigned.UInt32.zero (max 1 ((n + 31) / 32)) in
+  check (hnsw_index_deleted_bits t.handle (CArray.start words));
+  Array.init n (fun v ->
+      Unsigned.UInt32.logand (Unsigned.UInt32.shift_right (CArray.get words (v lsr 5)) (v land 31)) Unsigned.UInt32.one
+      <> Unsigned.UInt32.zero)
+let compact t : int array =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let n_old = Int64.to_int (getf inf ii_n) in
+  let c_new = CArray.make int32_t (max n_old 1) in
+  check (hnsw_index_compact t.handle (CArray.start c_new));
   Array.init n_old (fun v -> Int32.to_int (CArray.get c_new v))
 
 (* flattened-index file (the reference has no persistence: lib/hnsw.ml:348, lib/ohnsw.ml:312 derive sexp with opaque values) *)
