@@ -22,6 +22,8 @@
  *                            one-process-per-GPU deployment: results are exchanged between devices first)
  *   hnsw_search_submit/_wait the same batch call in two halves (several batches in flight)
  *   hnsw_multi_*             the batch entry point over several GPUs from one host process (RCCL all-gather)
+ *   hnsw_sharded_*           (nothing in the reference) the ROWS partitioned over several GPUs, one graph per slice, every query
+ *                            on all slices, the answers merged on the device (hnsw_merge_lists): capacity where hnsw_multi is rate
  *   hnsw_distance_batch      Ohnsw.distance_l2 / EuclideanBa.distance (lib/ohnsw.ml:899,
  *                            lib/hnsw.ml:809-815) as timed by bench_dist/bench_dist.ml:22-33
  *   hnsw_index_layer_stats / hnsw_index_layer_isolated   Hgraph.Stats.compute (lib/hnsw.ml:353-375)
@@ -951,6 +953,81 @@ int32_t hnsw_index_layer_isolated(const hnsw_index *idx, int32_t layer, int64_t 
  * steady-state rate.  Option "half_rows" is not saved (the format is unchanged): a loaded index starts without half rows. */
 int32_t hnsw_index_save(const hnsw_index *idx, const char *path);
 int32_t hnsw_index_load(const char *path, int32_t device, hnsw_index **out);
+
+/* ---- sharded index: one data set PARTITIONED over several GPUs ------------------------------------------------------------------
+ * hnsw_multi replicates the index and splits the query batch: throughput, at G times the memory.  An hnsw_sharded splits the ROWS:
+ * each listed device holds a slice of the table with a graph of its own, every query visits all slices, and the per-slice answers
+ * are merged.  That is capacity: 100 M x 768 float32 vectors do not fit one device and do fit eight.
+ *
+ * THE PARTITION.  n_shards = G is in 1..64 (one lane of the merge kernel's wave per shard); outside that range every constructor
+ *   returns HNSW_ERR_BAD_ARG, and so does hnsw_sharded_build for n < n_shards.  A device may be listed more than once (the test
+ *   arrangement, and legitimate on one large GPU).  Shard g of G holds the rows [lo_g, lo_{g+1}), for hnsw_sharded_build with
+ *   lo_g = floor(n * g / G).  A local node v of shard g (0-based) has the GLOBAL id lo_g + v + id_base.  Global ids are int64: a
+ *   sharded table may hold more than 2^31 rows even though no single shard may.  hnsw_sharded_shard gives shard g's handle and
+ *   first_row = lo_g; hnsw_sharded_get_info gives n = lo_G, the shards' common d, metric and id_base, and the sum of their
+ *   device_bytes (each pointer may be NULL).
+ * hnsw_sharded_build.  Shard g is exactly hnsw_build(vectors + lo_g * row_stride, lo_{g+1} - lo_g, d, row_stride, params', devices[g])
+ *   where params' is *params with seed = params->seed + g: a shard's graph can be checked link for link against that public call.
+ *   The shards are built one after another, on the calling thread.  On any error every shard built so far is destroyed and *out is NULL.
+ * hnsw_sharded_create adopts G graphs built elsewhere (one OCaml build per slice): descs[g] describes shard g with LOCAL ids, as
+ *   hnsw_index_create takes it.  All shards must agree on d, metric and id_base (HNSW_ERR_BAD_ARG otherwise); lo_g is the running sum
+ *   of the shards' n, so here the shards need not be equal in size; hnsw_sharded_get_info and hnsw_sharded_shard report the real
+ *   bounds.
+ * SAVING AND LOADING.  hnsw_sharded_load runs hnsw_index_load(paths[g], devices[g]) per shard and applies the same agreement rules.
+ *   Saving needs no call of its own: hnsw_index_save on each borrowed shard handle writes the files hnsw_sharded_load reads.
+ * SHARD HANDLES.  A shard handle is an ordinary hnsw_index, borrowed (destroyed with the hnsw_sharded).  The read-only calls work on
+ *   it: searches, filters, range calls, stats, exports, hnsw_index_save.  It is marked as owned, as a replica of an hnsw_multi is:
+ *   hnsw_index_insert, hnsw_index_remove and hnsw_index_mark_deleted refuse it (HNSW_ERR_BAD_ARG) -- a shard that grows or shrinks
+ *   would move every later shard's first_row.  Sharded insert, remove, marks, filters and range calls are NOT BUILT.
+ * hnsw_sharded_set_option applies hnsw_index_set_option(name, value) to every shard, in order.  If shard j refuses, shards 0 .. j-1
+ *   are set back to the value they had before and shard j's error is returned.  (What "half_rows" / "sq8_rows" -1 freed is not made
+ *   again by that.)
+ *
+ * THE RESULT of hnsw_sharded_search_batch, in terms of public calls only.  Let R_g(q) be the row hnsw_search_batch returns for q on
+ *   shard g's handle with the same params -- the host form: exact, tie-overflow repair included, under half or sq8 rows with the
+ *   refine rules of that handle.  The real entries of the R_g (id >= id_base) get their global ids, and the answer is the first k of
+ *   their union under the total order (distance, global id), where the distance is the returned float32 value compared as IEEE <.
+ *   (No entry point returns -0 or, on data without NaN, a NaN for a real id.)  out_ids [nq][k] are int64; rows past the real entries
+ *   are filled per params->fill: id -1, and NaN (HNSW_FILL_OHNSW) or +inf (HNSW_FILL_BA).  out_ndist / out_nhops (optional, [nq]) are
+ *   the sums over the shards.  k > ef, ef > 1024, null pointers, strides and nq == 0 behave as in hnsw_search_batch.
+ *   HNSW_SEM_FUNCTOR_NEAREST_K is HNSW_ERR_BAD_ARG: "the k farthest of W" has no merged meaning.  A shard whose graph is empty is
+ *   HNSW_ERR_EMPTY_INDEX.  DETERMINISM: a query's row depends on its own vector and the params only.
+ * hnsw_sharded_brute_force_batch is the same merge over hnsw_brute_force_batch(shard g, k): the exact k nearest of ALL rows.  Each
+ *   pair's distance is computed by the same lanes in the same order wherever the row lives, so the returned distances are bit for bit
+ *   those of hnsw_brute_force_batch over one index holding all rows.  The ids are bit for bit the same too, with one
+ *   ROUNDING EXCEPTION: the unsharded scan orders by its pre-square-root key, two different keys can round to one float distance,
+ *   and among such entries the merge orders by id where the unsharded scan orders by key.  It cannot occur on data whose squared
+ *   sums are integers below 2^16.  k in 1..1024 (k < 1, unknown fill: HNSW_ERR_BAD_ARG; k > 1024: HNSW_ERR_UNSUPPORTED); k larger than a
+ *   shard fills inside that shard's list only.
+ * DATA MOVEMENT.  Every device searches the full batch on a stream of its own, concurrently; each shard's [nq][k] ids, distances and
+ *   counters go to devices[0] by peer copies ordered behind the shard's search; after one host round trip (a shard whose launch
+ *   flagged a tie overflow is repaired and sent again) the merge kernel runs on devices[0] and the merged rows are downloaded once.
+ *   One code path whether or not the devices are distinct.  Scratch belongs to the hnsw_sharded, is sized on demand and not counted
+ *   in device_bytes: ONE call in flight per handle.
+ *
+ * hnsw_merge_lists is the merge as an operator of its own (in the spirit of hnsw_rerank_batch; it needs no index): host arrays
+ *   ids and dist, each [n_lists][nq][k_in]; each list ascending under (distance, id) with its padding (id < id_base) at the end;
+ *   first_row [n_lists], non-decreasing.  out_ids [nq][k_out] (int64) = first_row[list] + id of the first k_out real entries of the
+ *   union under (distance, global id); out_dist their distances, the bits given.  Fewer real entries than k_out: the rest is filled
+ *   (id -1, NaN or +inf).  n_lists in 1..64, k_in in 1..1024, k_out in 1..1024; a value outside these ranges, an unknown fill or a
+ *   decreasing first_row is HNSW_ERR_BAD_ARG; nq == 0 is a no-op.  It runs on `device`.  Both sharded calls above go through its kernel. */
+typedef struct hnsw_sharded hnsw_sharded;
+int32_t hnsw_sharded_build(const float *vectors, int64_t n, int32_t d, int64_t row_stride, const hnsw_build_params *params,
+                           const int32_t *devices, int32_t n_shards, hnsw_sharded **out);
+int32_t hnsw_sharded_create(const hnsw_index_desc *const *descs, const int32_t *devices, int32_t n_shards, hnsw_sharded **out);
+int32_t hnsw_sharded_load(const char *const *paths, const int32_t *devices, int32_t n_shards, hnsw_sharded **out);
+int32_t hnsw_sharded_destroy(hnsw_sharded *s);   /* NULL is HNSW_OK */
+int32_t hnsw_sharded_num_shards(const hnsw_sharded *s, int32_t *n_shards);
+/* shard g (borrowed: destroyed with the hnsw_sharded) and the global row its local node 0 is; first_row may be NULL */
+int32_t hnsw_sharded_shard(hnsw_sharded *s, int32_t g, hnsw_index **out, int64_t *first_row);
+int32_t hnsw_sharded_get_info(const hnsw_sharded *s, int64_t *n, int32_t *d, int32_t *metric, int32_t *id_base, int64_t *device_bytes);
+int32_t hnsw_sharded_set_option(hnsw_sharded *s, const char *name, int64_t value);
+int32_t hnsw_sharded_search_batch(hnsw_sharded *s, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
+                                  int64_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops);
+int32_t hnsw_sharded_brute_force_batch(hnsw_sharded *s, const float *queries, int64_t nq, int64_t q_stride, int32_t k, int32_t fill,
+                                       int64_t *out_ids, float *out_dist);
+int32_t hnsw_merge_lists(int32_t device, const int32_t *ids, const float *dist, const int64_t *first_row, int32_t n_lists,
+                         int64_t nq, int32_t k_in, int32_t k_out, int32_t id_base, int32_t fill, int64_t *out_ids, float *out_dist);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,17 @@ _ABI = {
     "hnsw_multi_search_batch_device": [_vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "hnsw_multi_copy_result": [_vp, _i32, _vp, _vp],
     "hnsw_multi_debug_counters": [_vp, _vp],
+    "hnsw_sharded_build": [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp],
+    "hnsw_sharded_create": [_vp, _vp, _i32, _vp],
+    "hnsw_sharded_load": [_vp, _vp, _i32, _vp],
+    "hnsw_sharded_destroy": [_vp],
+    "hnsw_sharded_num_shards": [_vp, _vp],
+    "hnsw_sharded_shard": [_vp, _i32, _vp, _vp],
+    "hnsw_sharded_get_info": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_sharded_set_option": [_vp, _str, _i64],
+    "hnsw_sharded_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_sharded_brute_force_batch": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp],
+    "hnsw_merge_lists": [_i32, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
     "hnsw_host_register": [_vp, _i64],
     "hnsw_host_unregister": [_vp],
     "hnsw_host_alloc": [_vp, _i64],
@@ -527,7 +538,8 @@ class Hgraph:
 
     def release(self):
         if self._index is not None:
-            load().hnsw_index_destroy(self._index)
+            if self.__dict__.get("_owner") is None:      # (a shard borrowed from a ShardedHgraph is destroyed with it)
+                load().hnsw_index_destroy(self._index)
             self._index = None
 
     def __del__(self):
@@ -1171,6 +1183,149 @@ class MultiHgraph:
     def release(self):
         if self._h is not None:
             load().hnsw_multi_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def merge_lists(ids, dist, first_row, k_out, id_base=0, fill=FILL_OHNSW, device=0):
+    """hnsw_merge_lists: the merge of per-shard result lists as an operator of its own (no index needed).  ids int32 and dist float32
+    [n_lists][nq][k_in]: each list ascending under (distance, id) with its padding (id < id_base) at the end; first_row [n_lists],
+    non-decreasing.  -> (ids int64 [nq][k_out], distances float32 [nq][k_out]): the first k_out real entries of the union under
+    (distance, first_row[list] + id), the rest filled (id -1; NaN, FILL_BA: +inf)."""
+    I = _np.ascontiguousarray(ids, _np.int32)
+    D = _np.ascontiguousarray(dist, _np.float32)
+    F = _np.ascontiguousarray(first_row, _np.int64).reshape(-1)
+    if I.ndim != 3 or D.shape != I.shape or F.shape != (I.shape[0],):
+        raise InvalidArgument("ids and dist must be [n_lists][nq][k_in], first_row [n_lists]")
+    n_lists, nq, k_in = I.shape
+    out_ids = _np.empty((nq, max(int(k_out), 0)), _np.int64)
+    out_dist = _np.empty((nq, max(int(k_out), 0)), _np.float32)
+    _check(load().hnsw_merge_lists(int(device), _ptr(I), _ptr(D), _ptr(F), n_lists, nq, k_in, int(k_out), int(id_base), int(fill),
+                                   _ptr(out_ids), _ptr(out_dist)))
+    return out_ids, out_dist
+
+
+class ShardedHgraph:
+    """One data set PARTITIONED over several GPUs (hnsw_sharded): shard g holds the rows [first_row(g), first_row(g + 1)) with a graph
+    of its own on devices[g], every query visits all shards, and the per-shard answers are merged on devices[0] under (distance,
+    global id).  Global ids are int64: first_row(g) + local node + id_base.  A device may be listed several times.  Capacity, where
+    MultiHgraph (the index replicated, the batch split) is rate."""
+
+    def __init__(self, handle, devices):
+        self._h, self.devices = handle, [int(x) for x in devices]
+        self.n, self.d, self.metric, self.id_base, _ = self.info()
+
+    @staticmethod
+    def _devices(devices):
+        dev = _np.ascontiguousarray(devices, _np.int32).reshape(-1)
+        return dev, (_ptr(dev) if len(dev) else None)
+
+    @classmethod
+    def build(cls, batch, num_connections, num_nodes_search_construction, devices, seed=0, metric=METRIC_L2, id_base=0, max_batch=0,
+              batch_div=0, expected_ef=0, expected_sem=SEM_OHNSW):
+        """hnsw_sharded_build: shard g = Ohnsw.build_batch_bigarray of the rows [floor(n g / G), floor(n (g + 1) / G)) on devices[g]
+        with seed + g, built one after another"""
+        X, xs = _rows(batch)
+        if X.ndim != 2:
+            raise InvalidArgument("batch must be [n][d]")
+        p = _BuildParams(num_connections, num_nodes_search_construction, metric, id_base, seed, max_batch, batch_div, expected_ef, expected_sem)
+        dev, pdev = cls._devices(devices)
+        h = _C.c_void_p()
+        _check(load().hnsw_sharded_build(_ptr(X), X.shape[0], X.shape[1], max(xs, X.shape[1]), _C.byref(p), pdev, len(dev), _C.byref(h)))
+        return cls(h, dev)
+
+    @classmethod
+    def create(cls, hgraphs, devices):
+        """hnsw_sharded_create: adopt graphs built elsewhere, one Hgraph (host copy, LOCAL ids) per shard; the shards need not be
+        equal in size but must agree on d, metric and id_base"""
+        hgraphs = list(hgraphs)
+        keep = [hg._desc() for hg in hgraphs]
+        table = (_C.c_void_p * max(len(keep), 1))(*[_C.addressof(d) for d, _ in keep])
+        dev, pdev = cls._devices(devices)
+        if len(dev) != len(hgraphs):
+            raise InvalidArgument("one device per shard")
+        h = _C.c_void_p()
+        _check(load().hnsw_sharded_create(table, pdev, len(dev), _C.byref(h)))
+        return cls(h, dev)
+
+    @classmethod
+    def load(cls, paths, devices):
+        """hnsw_sharded_load: one index file per shard (what save() wrote)"""
+        paths = [str(p).encode() for p in paths]
+        table = (_C.c_char_p * max(len(paths), 1))(*paths)
+        dev, pdev = cls._devices(devices)
+        if len(dev) != len(paths):
+            raise InvalidArgument("one device per path")
+        h = _C.c_void_p()
+        _check(load().hnsw_sharded_load(table, pdev, len(dev), _C.byref(h)))
+        return cls(h, dev)
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise InvalidArgument("sharded index already released")
+        return self._h
+
+    def num_shards(self):
+        c = _C.c_int32(0)
+        _check(load().hnsw_sharded_num_shards(self.handle, _C.byref(c)))
+        return c.value
+
+    def shard(self, g):
+        """hnsw_sharded_shard -> (Hgraph, first_row): shard g's index, BORROWED (valid until this object's release(); its own
+        release() only forgets the handle), for the read-only calls: searches, filters, range calls, stats, export, save"""
+        h, lo = _C.c_void_p(), _C.c_int64(0)
+        _check(load().hnsw_sharded_shard(self.handle, int(g), _C.byref(h), _C.byref(lo)))
+        hg = Hgraph._from_handle(h, self.devices[int(g)])
+        hg._owner = self
+        return hg, lo.value
+
+    def save(self, paths):
+        """hnsw_index_save of every shard, in order, into `paths` (one per shard): the files load() reads"""
+        paths = list(paths)
+        if len(paths) != self.num_shards():
+            raise InvalidArgument("one path per shard")
+        for g, p in enumerate(paths):
+            self.shard(g)[0].save(p)
+
+    def info(self):
+        """hnsw_sharded_get_info -> (n, d, metric, id_base, device_bytes): the shards' rows and device bytes summed"""
+        n, b = _C.c_int64(0), _C.c_int64(0)
+        d, m, ib = _C.c_int32(0), _C.c_int32(0), _C.c_int32(0)
+        _check(load().hnsw_sharded_get_info(self.handle, _C.byref(n), _C.byref(d), _C.byref(m), _C.byref(ib), _C.byref(b)))
+        return n.value, d.value, m.value, ib.value, b.value
+
+    def set_option(self, name, value):
+        """hnsw_sharded_set_option: hnsw_index_set_option on every shard; a refusal leaves every shard as it was"""
+        _check(load().hnsw_sharded_set_option(self.handle, name.encode(), int(value)))
+
+    def knn_batch(self, batch, ef, k, fill=FILL_OHNSW, sem=SEM_OHNSW, counters=False):
+        """hnsw_sharded_search_batch -> (ids int64 [nq][k], distances [nq][k]), with counters (ids, distances, ndist, nhops -- sums
+        over the shards): the first k under (distance, global id) of the shards' own knn rows for (ef, k)"""
+        Q, qs, nq = _batch(self.d, batch)
+        ids, dist = _np.empty((nq, max(k, 0)), _np.int64), _np.empty((nq, max(k, 0)), _np.float32)
+        nd = _np.zeros(nq, _np.uint32) if counters else None
+        nh = _np.zeros(nq, _np.uint32) if counters else None
+        p = _SearchParams(ef, k, fill, sem)
+        _check(load().hnsw_sharded_search_batch(self.handle, _ptr(Q), nq, qs, _C.byref(p), _ptr(ids), _ptr(dist), _ptr(nd), _ptr(nh)))
+        return (ids, dist, nd, nh) if counters else (ids, dist)
+
+    def brute_force_knn(self, k, batch, fill=FILL_OHNSW):
+        """hnsw_sharded_brute_force_batch -> (ids int64 [nq][k], distances [nq][k]): the exact k nearest of all rows, the
+        distance bits of Ohnsw.brute_force_knn over one index holding them all"""
+        Q, qs, nq = _batch(self.d, batch)
+        ids, dist = _np.empty((nq, max(int(k), 0)), _np.int64), _np.empty((nq, max(int(k), 0)), _np.float32)
+        _check(load().hnsw_sharded_brute_force_batch(self.handle, _ptr(Q), nq, qs, int(k), fill, _ptr(ids), _ptr(dist)))
+        return ids, dist
+
+    def release(self):
+        if self._h is not None:
+            load().hnsw_sharded_destroy(self._h)
             self._h = None
 
     def __del__(self):

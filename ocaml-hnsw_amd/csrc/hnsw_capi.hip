@@ -1101,6 +1101,24 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }
 
+} // extern "C"
+
+// The value hnsw_index_set_option would have to be given to put option `name` back where it is now (not a public call:
+// hnsw_sharded_set_option undoes a half-applied option with it).  What -1 freed stays freed: "half_rows" / "sq8_rows" read 0 then.
+int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *value) {
+    if (!idx || !name || !value) return fail(HNSW_ERR_BAD_ARG, "null argument");
+    const struct { const char *name; int64_t value; } now[] = {
+        {"vt_bits", idx->vt_bits_override}, {"lds_pad", idx->lds_pad}, {"byte_rows", idx->byte_rows_off ? 0 : 1},
+        {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
+        {"sq8_rows", idx->sq8_on ? 1 : 0}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
+        {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
+        {"order_queries", idx->order_mode}, {"scan_slabs", idx->scan_slabs}};
+    for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }
+    return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
+}
+
+extern "C" {
+
 int32_t hnsw_search_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
                                  const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
                                  uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, void *stream) {

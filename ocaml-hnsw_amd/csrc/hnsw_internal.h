@@ -378,7 +378,7 @@ struct hnsw_index {
     hnsw_host::LadderBufs ladder_scratch;
     hnsw_host::FilterBufs filter_scratch;
     hnsw_host::RangeBufs range_scratch;
-    bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica): not grown or shrunk on its own (hnsw_index_insert, hnsw_index_remove)
+    bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica) or an hnsw_sharded (hnsw_sharded_shard): not grown or shrunk on its own (hnsw_index_insert, hnsw_index_remove)
     // the graph epoch: every successful hnsw_index_insert and hnsw_index_remove moves it on (adopt_graph).  A filter records the
     // epoch it was made in: n alone would let a mask through after "remove 5, insert 5"
     uint64_t epoch = 0;
@@ -529,6 +529,9 @@ int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_strid
 // padding of the caller's layout; their rows of b.ids / b.dist are left unwritten.
 int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *const *masks = nullptr,
                 const int32_t *tile_filter = nullptr, const int32_t *row_query = nullptr);
+// hnsw_scan.hip: what the exact scans check of a call, as check_batch does for the knn searches (k in 1..1024, the fill, nq, then -- unless
+// nq is 0 -- the buffers and q_stride)
+int check_scan(const ::hnsw_index *idx, int64_t nq, int64_t q_stride, int32_t k, int32_t fill, bool buffers);
 // hnsw_scan.hip: how an exact scan of m queries of this index is cut (scan_plan: k for the slab rule, bytes per (query, slab)
 // cell, the first piece's cap), the kernels' NCH and tile, and the grid of a launch of nq <= piece queries
 struct ScanCut : ScanPlan {
@@ -596,6 +599,8 @@ private:
     int cur = 0;                         // which list buffer `map` is
     std::vector<int32_t> shorts;
 };
+// hnsw_capi.hip: the value that puts option `name` of hnsw_index_set_option back where it is now (HNSW_ERR_BAD_ARG: no such option)
+int get_option(const ::hnsw_index *idx, const char *name, int64_t *value);
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
 hipError_t knn_download(const KnnBatch &b, int k, int32_t *ids, float *dist, uint32_t *nd, uint32_t *nh, hipStream_t st);
 // hnsw_capi.hip: the handle's stream (hs[0]) and flag word of the host-buffer calls, made on first use

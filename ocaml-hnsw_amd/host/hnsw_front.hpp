@@ -12,7 +12,8 @@
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
 //   Hnsw::MultiHgraph (one process, several GPUs)                                SURVEY 8e
-//   Hnsw::Stats::compute (Hgraph.Stats)                                          lib/hnsw.ml:353-375
+//   Hnsw::Sharded, Hnsw::merge_lists (the rows partitioned over several GPUs)    (hnsw_sharded_*, hnsw_merge_lists)
+//   Hnsw::Stats::compute (Hgraph.Stats)                                         lib/hnsw.ml:353-375
 //   Hnsw::HostMat (a page-locked Lacaml-shaped matrix the device accesses directly: hnsw_host_alloc)
 //
 // Same names, argument meaning and error behaviour: OCaml Invalid_argument -> std::invalid_argument
@@ -480,5 +481,82 @@ private:
     hnsw_multi *m_ = nullptr;
     int d_ = 0;
 };
+
+// One data set PARTITIONED over several GPUs (hnsw_sharded_*): shard g holds the rows [first_row(g), first_row(g + 1)) with a graph
+// of its own on devices[g]; every query visits all shards and the per-shard answers are merged on devices[0] under (distance,
+// global id).  Global ids are int64: first_row(g) + local node + id_base.
+class Sharded {
+public:
+    struct Info { int64_t n; int32_t d, metric, id_base; int64_t device_bytes; };
+    // hnsw_sharded_build: shard g = hnsw_build of the rows [floor(n g / G), floor(n (g + 1) / G)) with seed + g
+    static Sharded build(const Mat &batch, const hnsw_build_params &params, const std::vector<int32_t> &devices) {
+        Sharded s;
+        check(hnsw_sharded_build(batch.data, batch.dim2, batch.dim1, batch.dim1, &params, devices.data(), (int32_t)devices.size(), &s.s_));
+        return s;
+    }
+    // hnsw_sharded_create: one flattened graph with LOCAL ids per shard
+    static Sharded create(const std::vector<const hnsw_index_desc *> &descs, const std::vector<int32_t> &devices) {
+        if (descs.size() != devices.size()) throw std::invalid_argument("one device per shard");
+        Sharded s;
+        check(hnsw_sharded_create(descs.data(), devices.data(), (int32_t)devices.size(), &s.s_));
+        return s;
+    }
+    // hnsw_sharded_load: one index file per shard (hnsw_index_save of every shard(g) writes them)
+    static Sharded load(const std::vector<std::string> &paths, const std::vector<int32_t> &devices) {
+        if (paths.size() != devices.size()) throw std::invalid_argument("one device per path");
+        std::vector<const char *> p;
+        for (const std::string &x : paths) p.push_back(x.c_str());
+        Sharded s;
+        check(hnsw_sharded_load(p.data(), devices.data(), (int32_t)devices.size(), &s.s_));
+        return s;
+    }
+    Sharded(const Sharded &) = delete;
+    Sharded &operator=(const Sharded &) = delete;
+    Sharded(Sharded &&o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+    ~Sharded() { if (s_) hnsw_sharded_destroy(s_); }
+    hnsw_sharded *handle() const { return s_; }
+    int num_shards() const { int32_t c = 0; check(hnsw_sharded_num_shards(s_, &c)); return c; }
+    // shard g's handle (borrowed: read-only calls only) and the global row of its local node 0
+    std::pair<hnsw_index *, int64_t> shard(int g) const {
+        hnsw_index *h = nullptr; int64_t lo = 0;
+        check(hnsw_sharded_shard(s_, g, &h, &lo));
+        return {h, lo};
+    }
+    Info info() const {
+        Info i{};
+        check(hnsw_sharded_get_info(s_, &i.n, &i.d, &i.metric, &i.id_base, &i.device_bytes));
+        return i;
+    }
+    void set_option(const char *name, int64_t value) { check(hnsw_sharded_set_option(s_, name, value)); }
+    // hnsw_sharded_search_batch: ids (int64, global) and distances [nq][k]
+    std::pair<std::vector<int64_t>, std::vector<float>> knn_batch(const Mat &batch, int ef, int k, int fill = HNSW_FILL_OHNSW,
+                                                                  int sem = HNSW_SEM_OHNSW) const {
+        std::vector<int64_t> ids((size_t)batch.dim2 * k, -1); std::vector<float> dist((size_t)batch.dim2 * k, 0.f);
+        hnsw_search_params p{ef, k, fill, sem};
+        check(hnsw_sharded_search_batch(s_, batch.data, batch.dim2, batch.dim1, &p, ids.data(), dist.data(), nullptr, nullptr));
+        return {std::move(ids), std::move(dist)};
+    }
+    // hnsw_sharded_brute_force_batch: the exact k nearest of all rows
+    std::pair<std::vector<int64_t>, std::vector<float>> brute_force_knn(int k, const Mat &batch, int fill = HNSW_FILL_OHNSW) const {
+        std::vector<int64_t> ids((size_t)batch.dim2 * k, -1); std::vector<float> dist((size_t)batch.dim2 * k, 0.f);
+        check(hnsw_sharded_brute_force_batch(s_, batch.data, batch.dim2, batch.dim1, k, fill, ids.data(), dist.data()));
+        return {std::move(ids), std::move(dist)};
+    }
+private:
+    Sharded() = default;
+    hnsw_sharded *s_ = nullptr;
+};
+
+// hnsw_merge_lists: n_lists result lists per query (ids / dist [n_lists][nq][k_in], each ascending under (distance, id), padding
+// below id_base at the end) merged under (distance, first_row[list] + id) into ids (int64) and distances [nq][k_out]
+inline std::pair<std::vector<int64_t>, std::vector<float>> merge_lists(const std::vector<int32_t> &ids, const std::vector<float> &dist,
+                                                                       const std::vector<int64_t> &first_row, int64_t nq, int k_in, int k_out,
+                                                                       int id_base = 0, int fill = HNSW_FILL_OHNSW, int device = 0) {
+    if (ids.size() != first_row.size() * (size_t)nq * (size_t)k_in || dist.size() != ids.size()) throw std::invalid_argument("merge_lists: ids and dist must be [n_lists][nq][k_in]");
+    std::vector<int64_t> out((size_t)nq * k_out, -1); std::vector<float> od((size_t)nq * k_out, 0.f);
+    check(hnsw_merge_lists(device, ids.data(), dist.data(), first_row.data(), (int32_t)first_row.size(), nq, k_in, k_out, id_base, fill,
+                           out.data(), od.data()));
+    return {std::move(out), std::move(od)};
+}
 
 } // namespace Hnsw

@@ -1190,3 +1190,109 @@ let export (t : t) : flat =
                  (bigarray_start array1 deg) (bigarray_start array2 nbr));
       (nodes, deg, nbr)) in
   { deg0; nbr0; upper; max_layer; width0; width_upper; entry_point = Int64.to_int (getf inf ii_entry_point) }
+
+(* ---- sharded index (hnsw_sharded_*, see the C header): the ROWS partitioned over several GPUs, one graph per slice, every query
+   on all slices, the per-slice answers merged on the first device under (distance, global id).  Global ids are 64-bit on the C
+   side; an OCaml int holds them. *)
+type sharded_handle = unit ptr
+let sharded_handle : sharded_handle typ = ptr void
+let hnsw_sharded_build =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_build"
+    (ptr float @-> int64_t @-> int32_t @-> int64_t @-> ptr build_params @-> ptr int32_t @-> int32_t @-> ptr sharded_handle
+     @-> returning int32_t)
+let hnsw_sharded_create =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_create"
+    (ptr (ptr index_desc) @-> ptr int32_t @-> int32_t @-> ptr sharded_handle @-> returning int32_t)
+let hnsw_sharded_load =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_load"
+    (ptr string @-> ptr int32_t @-> int32_t @-> ptr sharded_handle @-> returning int32_t)
+let hnsw_sharded_destroy = foreign ~from:lib "hnsw_sharded_destroy" (sharded_handle @-> returning int32_t)
+let hnsw_sharded_num_shards = foreign ~from:lib "hnsw_sharded_num_shards" (sharded_handle @-> ptr int32_t @-> returning int32_t)
+let hnsw_sharded_shard =
+  foreign ~from:lib "hnsw_sharded_shard" (sharded_handle @-> int32_t @-> ptr index @-> ptr int64_t @-> returning int32_t)
+let hnsw_sharded_get_info =
+  foreign ~from:lib "hnsw_sharded_get_info"
+    (sharded_handle @-> ptr int64_t @-> ptr int32_t @-> ptr int32_t @-> ptr int32_t @-> ptr int64_t @-> returning int32_t)
+let hnsw_sharded_set_option =
+  foreign ~from:lib "hnsw_sharded_set_option" (sharded_handle @-> string @-> int64_t @-> returning int32_t)
+let hnsw_sharded_search_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_search_batch"
+    (sharded_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> ptr int64_t @-> ptr float
+     @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+let hnsw_sharded_brute_force_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_brute_force_batch"
+    (sharded_handle @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> ptr int64_t @-> ptr float @-> returning int32_t)
+let hnsw_merge_lists =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_merge_lists"
+    (int32_t @-> ptr int32_t @-> ptr float @-> ptr int64_t @-> int32_t @-> int64_t @-> int32_t @-> int32_t @-> int32_t @-> int32_t
+     @-> ptr int64_t @-> ptr float @-> returning int32_t)
+
+type sharded = { s_handle : sharded_handle; s_dim : int; s_base : int }
+
+(* hnsw_sharded_build: shard g = [build] of the columns [floor(n g / G), floor(n (g + 1) / G)) of [vectors] on devices.(g) with
+   seed + g; a device may be listed more than once *)
+let sharded_build ~(devices : int array) ?(metric = 0) ?(seed = 0) ?(max_batch = 0) ?(batch_div = 0) ?(expected_ef = 0)
+    ?(expected_semantics = 0) ~id_base ~num_connections ~num_nodes_search_construction (vectors : Lacaml.S.mat) : sharded =
+  let dim = A2.dim1 vectors and n = A2.dim2 vectors in
+  let b = make build_params in
+  setf b b_num_connections (Int32.of_int num_connections); setf b b_efc (Int32.of_int num_nodes_search_construction);
+  setf b b_metric (Int32.of_int metric); setf b b_id_base (Int32.of_int id_base);
+  setf b b_seed (Unsigned.UInt64.of_int seed); setf b b_max_batch (Int32.of_int max_batch);
+  setf b b_batch_div (Int32.of_int batch_div);
+  setf b b_expected_ef (Int32.of_int expected_ef); setf b b_expected_semantics (Int32.of_int expected_semantics);
+  let dev = CArray.of_list int32_t (List.map Int32.of_int (Array.to_list devices)) in
+  let out = allocate sharded_handle null in
+  check (hnsw_sharded_build (bigarray_start array2 vectors) (Int64.of_int n) (Int32.of_int dim) (Int64.of_int dim) (addr b)
+           (CArray.start dev) (Int32.of_int (Array.length devices)) out);
+  let s = { s_handle = !@out; s_dim = dim; s_base = id_base } in
+  Gc.finalise (fun s -> ignore (hnsw_sharded_destroy s.s_handle)) s;
+  s
+
+(* hnsw_sharded_set_option: the option on every shard; a refusal leaves every shard as it was *)
+let sharded_set_option (s : sharded) name (value : int) = check (hnsw_sharded_set_option s.s_handle name (Int64.of_int value))
+
+let sharded_rows nq k ids dist =
+  (Array.init nq (fun q -> Array.init k (fun j -> Int64.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))))
+
+(* hnsw_sharded_search_batch: for each query (a column of [batch]) the first k under (distance, global id) of the shards' own knn
+   rows for (ef, k).  -> (global ids, distances), both [nq][k]; past the real entries: id -1, distance nan. *)
+let sharded_knn_batch (s : sharded) (batch : Lacaml.S.mat) ~ef ~k : int array array * float array array =
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int64_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let p = make search_params in
+  setf p p_ef (Int32.of_int ef); setf p p_k (Int32.of_int k); setf p p_fill 0l; setf p p_semantics 0l;
+  check (hnsw_sharded_search_batch s.s_handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int s.s_dim) (addr p)
+           (CArray.start ids) (CArray.start dist) (from_voidp uint32_t null) (from_voidp uint32_t null));
+  sharded_rows nq k ids dist
+
+(* hnsw_sharded_brute_force_batch: the exact k nearest of ALL rows, the distance bits of [brute_force_knn] over one index of them *)
+let sharded_brute_force (s : sharded) (batch : Lacaml.S.mat) ~k : int array array * float array array =
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int64_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  check (hnsw_sharded_brute_force_batch s.s_handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int s.s_dim)
+           (Int32.of_int k) 0l (CArray.start ids) (CArray.start dist));
+  sharded_rows nq k ids dist
+
+(* hnsw_merge_lists: lists.(g).(q) = list g's (id, distance) pairs for query q, ascending under (distance, id), at most k_in of
+   them; first_row.(g) = the global row of list g's local node 0 (non-decreasing).  -> the first k_out of the union under
+   (distance, first_row.(g) + id) as (global ids, distances), both [nq][k_out]; past the real entries: id -1, distance nan. *)
+let merge_lists ?(device = 0) ?(id_base = 0) ~(first_row : int array) ~k_in ~k_out (lists : (int * float) array array array)
+  : int array array * float array array =
+  let n_lists = Array.length lists in
+  if n_lists <> Array.length first_row then invalid_arg "merge_lists: one first_row per list";
+  let nq = if n_lists = 0 then 0 else Array.length lists.(0) in
+  let ids = CArray.make int32_t ~initial:(Int32.of_int (id_base - 1)) (max 1 (n_lists * nq * k_in)) in
+  let dist = CArray.make float ~initial:0.0 (max 1 (n_lists * nq * k_in)) in
+  Array.iteri (fun g per_query ->
+      if Array.length per_query <> nq then invalid_arg "merge_lists: every list answers the same queries";
+      Array.iteri (fun q row ->
+          if Array.length row > k_in then invalid_arg "merge_lists: a row longer than k_in";
+          Array.iteri (fun j (v, d) ->
+              CArray.set ids ((g * nq + q) * k_in + j) (Int32.of_int v); CArray.set dist ((g * nq + q) * k_in + j) d) row) per_query) lists;
+  let first = CArray.of_list int64_t (List.map Int64.of_int (Array.to_list first_row)) in
+  let out_ids = CArray.make int64_t (max 1 (nq * k_out)) and out_dist = CArray.make float (max 1 (nq * k_out)) in
+  check (hnsw_merge_lists (Int32.of_int device) (CArray.start ids) (CArray.start dist) (CArray.start first) (Int32.of_int n_lists)
+           (Int64.of_int nq) (Int32.of_int k_in) (Int32.of_int k_out) (Int32.of_int id_base) 0l (CArray.start out_ids)
+           (CArray.start out_dist));
+  sharded_rows nq k_out out_ids out_dist
