@@ -23,7 +23,8 @@
  *   hnsw_search_submit/_wait the same batch call in two halves (several batches in flight)
  *   hnsw_multi_*             the batch entry point over several GPUs from one host process (RCCL all-gather)
  *   hnsw_sharded_*           (nothing in the reference) the ROWS partitioned over several GPUs, one graph per slice, every query
- *                            on all slices, the answers merged on the device (hnsw_merge_lists): capacity where hnsw_multi is rate
+ *                            on all slices, the answers merged on the device (hnsw_merge_lists): capacity where hnsw_multi is rate;
+ *                            also under a filter over the global rows and as range search (hnsw_merge_segments)
  *   hnsw_distance_batch      Ohnsw.distance_l2 / EuclideanBa.distance (lib/ohnsw.ml:899,
  *                            lib/hnsw.ml:809-815) as timed by bench_dist/bench_dist.ml:22-33
  *   hnsw_index_layer_stats / hnsw_index_layer_isolated   Hgraph.Stats.compute (lib/hnsw.ml:353-375)
@@ -978,7 +979,7 @@ int32_t hnsw_index_load(const char *path, int32_t device, hnsw_index **out);
  * SHARD HANDLES.  A shard handle is an ordinary hnsw_index, borrowed (destroyed with the hnsw_sharded).  The read-only calls work on
  *   it: searches, filters, range calls, stats, exports, hnsw_index_save.  It is marked as owned, as a replica of an hnsw_multi is:
  *   hnsw_index_insert, hnsw_index_remove and hnsw_index_mark_deleted refuse it (HNSW_ERR_BAD_ARG) -- a shard that grows or shrinks
- *   would move every later shard's first_row.  Sharded insert, remove, marks, filters and range calls are NOT BUILT.
+ *   would move every later shard's first_row.  Sharded insert, remove and marks are NOT BUILT; filters and range calls: see below.
  * hnsw_sharded_set_option applies hnsw_index_set_option(name, value) to every shard, in order.  If shard j refuses, shards 0 .. j-1
  *   are set back to the value they had before and shard j's error is returned.  (What "half_rows" / "sq8_rows" -1 freed is not made
  *   again by that.)
@@ -1028,6 +1029,85 @@ int32_t hnsw_sharded_brute_force_batch(hnsw_sharded *s, const float *queries, in
                                        int64_t *out_ids, float *out_dist);
 int32_t hnsw_merge_lists(int32_t device, const int32_t *ids, const float *dist, const int64_t *first_row, int32_t n_lists,
                          int64_t nq, int32_t k_in, int32_t k_out, int32_t id_base, int32_t fill, int64_t *out_ids, float *out_dist);
+
+/* ---- sharded index: a filter over the global rows, filtered search, range search ---------------------------------------------------
+ * The query calls a single index has under an allow-mask or a radius, for an hnsw_sharded.  Every definition is in terms of the
+ * public single-index calls on the borrowed shard handles.  Still NOT BUILT for a sharded index: insert, remove and marks (they
+ * change the partition), and -- NOT part of this section -- filters from labels (hnsw_filter_create_by_label) and one filter per
+ * query (hnsw_search_batch_filtered_each); those two work on a shard handle, one shard at a time.
+ *
+ * hnsw_sharded_filter_create.  bits is laid out as for hnsw_filter_create, over GLOBAL rows: bit v & 31 of word v >> 5 allows global
+ *   row v (0-based, whatever id_base is); n_bits must be the sharded index's n = lo_G (else HNSW_ERR_BAD_ARG).  Shard g's part is
+ *   hnsw_filter_create(shard g, B_g, n_g), where B_g is the bits [lo_g, lo_{g+1}) moved down so that global row lo_g is bit 0 (sliced
+ *   on the host, n / 8 bytes, once; the tail of B_g's last word is clear).  The object owns G ordinary filters;
+ *   hnsw_sharded_filter_part lends part g (for hnsw_filter_bits / hnsw_filter_count; destroyed with the sharded filter);
+ *   hnsw_sharded_filter_count is the sum of the parts' counts.  All or nothing: on any error *out is NULL and nothing stays
+ *   allocated.  Shard handles cannot grow, shrink or be marked, so a sharded filter never goes stale; destroy it before its
+ *   hnsw_sharded.  The calls below refuse a filter made for another hnsw_sharded (HNSW_ERR_BAD_ARG).
+ *
+ * hnsw_sharded_search_batch_filtered.  Let R_g(q) be the row hnsw_search_batch_filtered(shard g, f's part g, ... the same params ...)
+ *   returns for q.  The answer is the first k real entries of the union of the R_g under (distance, global id), then the fill:
+ *   exactly what hnsw_sharded_search_batch says about the unfiltered rows.  out_ndist / out_nhops (optional) are the sums over the
+ *   shards; out_stage[q] (optional) is the maximum over the shards as unsigned 32-bit numbers, so it is 0xFFFFFFFF as soon as one
+ *   shard answered q from its exact stage.  A shard whose part allows fewer than k nodes, or none, behaves as the single-index
+ *   definition says (exact stage, the fill inside its list); the merge then fills only what all shards together could not supply.
+ *   Errors (the outputs stay untouched): those of hnsw_sharded_search_batch; a null or foreign filter is HNSW_ERR_BAD_ARG;
+ *   HNSW_SEM_FUNCTOR_NEAREST_K is HNSW_ERR_BAD_ARG; an empty shard graph is HNSW_ERR_EMPTY_INDEX.
+ *
+ * hnsw_sharded_range_search_batch / hnsw_sharded_range_brute_force_batch.  Let S_g(q) be the segment q gets on shard g from
+ *   hnsw_range_search_batch (f NULL) or hnsw_range_search_batch_filtered with f's part g; for the exact form from
+ *   hnsw_range_brute_force_batch or hnsw_range_brute_force_batch_filtered.  Query q's merged segment is the union of the S_g(q) with
+ *   global ids (first_row[g] + id: int64), ascending under (distance, global id), the distance being the returned float compared
+ *   as IEEE <.  (A single-index segment is ordered by the scan's pre-rounding key: where two keys round to one float distance, two
+ *   entries of ONE shard can stand with the higher id first.  The merged segment is in (distance, global id) order there too: the
+ *   merge puts such entries right, so even with one shard it can differ from the shard's own segment in the order of such pairs.)
+ *   lims[q] = the sum over g of lims_g[q] (each shard's lims is a prefix sum, so the sum is one).  Counters: ndist and
+ *   nhops are summed, stage is the unsigned maximum over the shards.  For the exact form the in-range test is on distance bits that do
+ *   not depend on where a row lives: the merged SET is exactly that of hnsw_range_brute_force_batch over one index holding all
+ *   rows, and the order too, with the ROUNDING EXCEPTION of hnsw_sharded_brute_force_batch.  Errors: as the single-index calls (a
+ *   NaN radius, ef, semantics; HNSW_ERR_EMPTY_INDEX for the graph form only; nq == 0 gives a valid empty result), reported for the
+ *   lowest-numbered failing shard; a foreign filter is HNSW_ERR_BAD_ARG; a merged total above 2^31 - 1 is HNSW_ERR_UNSUPPORTED,
+ *   found from the shards' totals before the merged buffers are allocated.  An error leaves *out NULL and the shard results
+ *   destroyed.  An hnsw_sharded_range_result owns its buffers on devices[0] and holds no reference to the hnsw_sharded: it
+ *   outlives it; any number may be alive; _size, _fetch (every pointer optional), _device and _destroy (NULL is HNSW_OK) are those
+ *   of hnsw_range_result with int64 ids.
+ *
+ * DATA MOVEMENT.  The single-index filtered and range calls are host-driven ladders, complete on return, so they are not queued on
+ *   G streams: the G shard calls run on one host thread per shard (each sets its shard's device; at most 16 at a time; all joined
+ *   before anything else happens; the error message of the lowest-numbered failing shard is carried to the caller's thread).
+ *   Filtered k-NN: the shards' rows and counters are staged into the [G][nq][k] and [G][nq] tables on devices[0], then the merge
+ *   kernel of hnsw_merge_lists, then one download.  Range: every shard result stays on its device; its lims, ids, distances and
+ *   counters go to devices[0] by peer copies, one concatenated table per kind; then the segment merge and the counter reduce; the
+ *   shard results are destroyed before return.  ONE call in flight per hnsw_sharded, as for the calls above.
+ *
+ * hnsw_merge_segments is the segment merge as an operator of its own (it needs no index): host arrays lims[g] ([nq + 1], starting
+ *   at 0, non-decreasing), ids[g] and dist[g] ([lims[g][nq]]) for n_lists in 1..64 lists; each segment ascending under (distance,
+ *   id) with no padding entries (id_base is accepted for symmetry with hnsw_merge_lists and has no effect); first_row [n_lists],
+ *   non-decreasing.  The result is the merge defined above; the same global id in two lists: the lower list comes first; its
+ *   counters read as 0.  n_lists outside 1..64, a decreasing first_row, a lims that does not start at 0 or decreases, a null
+ *   array: HNSW_ERR_BAD_ARG, found on the host before a device is touched; more than 2^31 - 1 entries: HNSW_ERR_UNSUPPORTED.  That the
+ *   segments are sorted is not checked: entries of equal distance may stand in any id order (they are put right), distances out of
+ *   order give some permutation of each query's entries.  It runs on `device`. */
+typedef struct hnsw_sharded_filter hnsw_sharded_filter;
+typedef struct hnsw_sharded_range_result hnsw_sharded_range_result;   /* owns its buffers on devices[0]; int64 global ids */
+int32_t hnsw_sharded_filter_create(hnsw_sharded *s, const uint32_t *bits, int64_t n_bits, hnsw_sharded_filter **out);
+int32_t hnsw_sharded_filter_destroy(hnsw_sharded_filter *f);          /* NULL is HNSW_OK */
+int32_t hnsw_sharded_filter_count(const hnsw_sharded_filter *f, int64_t *n_allowed);
+int32_t hnsw_sharded_filter_part(const hnsw_sharded_filter *f, int32_t g, const hnsw_filter **out);   /* borrowed */
+int32_t hnsw_sharded_search_batch_filtered(hnsw_sharded *s, const hnsw_sharded_filter *f, const float *queries, int64_t nq,
+                                           int64_t q_stride, const hnsw_search_params *params, int64_t *out_ids, float *out_dist,
+                                           uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage);
+int32_t hnsw_sharded_range_search_batch(hnsw_sharded *s, const hnsw_sharded_filter *f /* may be NULL */, const float *queries,
+                                        int64_t nq, int64_t q_stride, const hnsw_range_params *params, hnsw_sharded_range_result **out);
+int32_t hnsw_sharded_range_brute_force_batch(hnsw_sharded *s, const hnsw_sharded_filter *f /* may be NULL */, const float *queries,
+                                             int64_t nq, int64_t q_stride, float radius, hnsw_sharded_range_result **out);
+int32_t hnsw_sharded_range_result_size(const hnsw_sharded_range_result *r, int64_t *nq, int64_t *total);
+int32_t hnsw_sharded_range_result_fetch(hnsw_sharded_range_result *r, int64_t *lims, int64_t *ids, float *dist, uint32_t *out_ndist,
+                                        uint32_t *out_nhops, uint32_t *out_stage);
+int32_t hnsw_sharded_range_result_device(hnsw_sharded_range_result *r, const int64_t **d_lims, const int64_t **d_ids, const float **d_dist);
+int32_t hnsw_sharded_range_result_destroy(hnsw_sharded_range_result *r);
+int32_t hnsw_merge_segments(int32_t device, int32_t n_lists, int64_t nq, const int64_t *const *lims, const int32_t *const *ids,
+                            const float *const *dist, const int64_t *first_row, int32_t id_base, hnsw_sharded_range_result **out);
 
 #ifdef __cplusplus
 }

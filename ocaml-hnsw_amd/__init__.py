@@ -114,6 +114,18 @@ _ABI = {
     "hnsw_sharded_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "hnsw_sharded_brute_force_batch": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp],
     "hnsw_merge_lists": [_i32, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
+    "hnsw_sharded_filter_create": [_vp, _vp, _i64, _vp],
+    "hnsw_sharded_filter_destroy": [_vp],
+    "hnsw_sharded_filter_count": [_vp, _vp],
+    "hnsw_sharded_filter_part": [_vp, _i32, _vp],
+    "hnsw_sharded_search_batch_filtered": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_sharded_range_search_batch": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "hnsw_sharded_range_brute_force_batch": [_vp, _vp, _vp, _i64, _i64, _f32, _vp],
+    "hnsw_sharded_range_result_size": [_vp, _vp, _vp],
+    "hnsw_sharded_range_result_fetch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_sharded_range_result_device": [_vp, _vp, _vp, _vp],
+    "hnsw_sharded_range_result_destroy": [_vp],
+    "hnsw_merge_segments": [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp],
     "hnsw_host_register": [_vp, _i64],
     "hnsw_host_unregister": [_vp],
     "hnsw_host_alloc": [_vp, _i64],
@@ -1210,6 +1222,130 @@ def merge_lists(ids, dist, first_row, k_out, id_base=0, fill=FILL_OHNSW, device=
     return out_ids, out_dist
 
 
+class ShardedRangeResult:
+    """What a sharded range call and merge_segments return (hnsw_sharded_range_result): as RangeResult, with int64 global ids, on
+    the first device of the sharded index; it outlives that index."""
+
+    def __init__(self, handle):
+        self._r = handle
+
+    @property
+    def handle(self):
+        if self._r is None:
+            raise InvalidArgument("range result already released")
+        return self._r
+
+    def size(self):
+        """hnsw_sharded_range_result_size -> (nq, total)"""
+        nq, total = _C.c_int64(0), _C.c_int64(0)
+        _check(load().hnsw_sharded_range_result_size(self.handle, _C.byref(nq), _C.byref(total)))
+        return nq.value, total.value
+
+    def fetch(self, counters=False):
+        """hnsw_sharded_range_result_fetch -> (lims int64 [nq + 1], ids int64 [total], distances float32 [total]), with counters
+        also (ndist, nhops, stage), uint32 [nq] each"""
+        nq, total = self.size()
+        lims, ids, dist = _np.zeros(nq + 1, _np.int64), _np.empty(total, _np.int64), _np.empty(total, _np.float32)
+        cnt = [_np.zeros(nq, _np.uint32) for _ in range(3)] if counters else [None] * 3
+        _check(load().hnsw_sharded_range_result_fetch(self.handle, _ptr(lims), _ptr(ids), _ptr(dist), _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2])))
+        return (lims, ids, dist) + tuple(cnt) if counters else (lims, ids, dist)
+
+    def device_pointers(self):
+        """hnsw_sharded_range_result_device -> the device addresses (lims, ids, distances) as integers, valid until release"""
+        p = [_C.c_void_p() for _ in range(3)]
+        _check(load().hnsw_sharded_range_result_device(self.handle, _C.byref(p[0]), _C.byref(p[1]), _C.byref(p[2])))
+        return tuple(x.value or 0 for x in p)
+
+    def release(self):
+        if self._r is not None:
+            load().hnsw_sharded_range_result_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def _take(self, counters, keep):
+        """the result itself (keep), or everything fetched and the device copy released"""
+        if keep:
+            return self
+        try:
+            return self.fetch(counters)
+        finally:
+            self.release()
+
+
+def merge_segments(lims, ids, dist, first_row, id_base=0, device=0, keep=False):
+    """hnsw_merge_segments: the merge of per-list range results as an operator of its own (no index needed).  lims[g] int64
+    [nq + 1] (from 0, non-decreasing), ids[g] int32 and dist[g] float32 [lims[g][nq]]: each segment ascending under (distance, id);
+    first_row [n_lists], non-decreasing.  -> (lims, ids int64, distances): per query the union of its segments under (distance,
+    first_row[list] + id), the same global id in two lists: the lower list first; keep: the ShardedRangeResult."""
+    L = [_np.ascontiguousarray(x, _np.int64).reshape(-1) for x in lims]
+    I = [_np.ascontiguousarray(x, _np.int32).reshape(-1) for x in ids]
+    D = [_np.ascontiguousarray(x, _np.float32).reshape(-1) for x in dist]
+    F = _np.ascontiguousarray(first_row, _np.int64).reshape(-1)
+    n = len(L)
+    if len(I) != n or len(D) != n or len(F) != n or any(len(x) != len(L[0]) or len(x) < 1 for x in L):
+        raise InvalidArgument("lims, ids, dist and first_row must list the same lists; every lims has nq + 1 entries")
+    if any(len(I[g]) != len(D[g]) or (len(I[g]) != L[g][-1]) for g in range(n)):
+        raise InvalidArgument("ids[g] and dist[g] must have lims[g][nq] entries")
+
+    def table(arrays):
+        return (_C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrays])
+
+    r = _C.c_void_p()
+    _check(load().hnsw_merge_segments(int(device), n, (len(L[0]) - 1) if n else 0, table(L), table(I), table(D), _ptr(F) if n else None,
+                                      int(id_base), _C.byref(r)))
+    return ShardedRangeResult(r)._take(False, keep)
+
+
+class ShardedFilter:
+    """An allow-mask over the GLOBAL rows of one ShardedHgraph (hnsw_sharded_filter): one ordinary filter per shard, each on its
+    shard's device; see ShardedHgraph.filter.  Release it before its index."""
+
+    def __init__(self, sharded, allow):
+        self._f = None
+        bits = pack_allow(allow, sharded.n, sharded.id_base)
+        f = _C.c_void_p()
+        _check(load().hnsw_sharded_filter_create(sharded.handle, _ptr(bits) if len(bits) else None, sharded.n, _C.byref(f)))
+        self._f, self._s, self.n = f, sharded, sharded.n
+
+    @property
+    def handle(self):
+        if self._f is None:
+            raise InvalidArgument("filter already released")
+        return self._f
+
+    def count(self):
+        """hnsw_sharded_filter_count: the allowed rows, summed over the shards"""
+        c = _C.c_int64(0)
+        _check(load().hnsw_sharded_filter_count(self.handle, _C.byref(c)))
+        return c.value
+
+    def part_bits(self, g):
+        """shard g's part as its device holds it (hnsw_sharded_filter_part, hnsw_filter_bits): uint32 [ceil(n_g / 32)], bit v = the
+        shard's local node v"""
+        p = _C.c_void_p()
+        _check(load().hnsw_sharded_filter_part(self.handle, int(g), _C.byref(p)))
+        n_g = self._s.shard(g)[0].info().n
+        out = _np.zeros((n_g + 31) // 32, _np.uint32)
+        _check(load().hnsw_filter_bits(p, _ptr(out) if len(out) else _C.byref(_C.c_uint32())))
+        return out
+
+    def release(self):
+        if self._f is not None:
+            load().hnsw_sharded_filter_destroy(self._f)
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 class ShardedHgraph:
     """One data set PARTITIONED over several GPUs (hnsw_sharded): shard g holds the rows [first_row(g), first_row(g + 1)) with a graph
     of its own on devices[g], every query visits all shards, and the per-shard answers are merged on devices[0] under (distance,
@@ -1322,6 +1458,58 @@ class ShardedHgraph:
         ids, dist = _np.empty((nq, max(int(k), 0)), _np.int64), _np.empty((nq, max(int(k), 0)), _np.float32)
         _check(load().hnsw_sharded_brute_force_batch(self.handle, _ptr(Q), nq, qs, int(k), fill, _ptr(ids), _ptr(dist)))
         return ids, dist
+
+    def filter(self, allow):
+        """hnsw_sharded_filter_create: allow = a boolean array over the n GLOBAL rows, or an array of global ids (id_base-based)
+        -> ShardedFilter, cut into one filter per shard"""
+        return ShardedFilter(self, allow)
+
+    def _filter(self, flt):
+        """(a ShardedFilter, whether it was made for this call) from a ShardedFilter or what filter() takes"""
+        return (flt, False) if isinstance(flt, ShardedFilter) else (ShardedFilter(self, flt), True)
+
+    def knn_batch_filtered(self, batch, ef, k, filter, fill=FILL_OHNSW, sem=SEM_OHNSW, counters=False):
+        """hnsw_sharded_search_batch_filtered -> (ids int64 [nq][k], distances [nq][k]), with counters (ids, distances, ndist, nhops
+        -- sums over the shards --, stage -- the unsigned maximum over the shards): the first k under (distance, global id) of the
+        shards' own filtered rows"""
+        f, own = self._filter(filter)
+        try:
+            Q, qs, nq = _batch(self.d, batch)
+            ids, dist = _np.empty((nq, max(k, 0)), _np.int64), _np.empty((nq, max(k, 0)), _np.float32)
+            cnt = [_np.zeros(nq, _np.uint32) for _ in range(3)] if counters else [None] * 3
+            p = _SearchParams(ef, k, fill, sem)
+            _check(load().hnsw_sharded_search_batch_filtered(self.handle, f.handle, _ptr(Q), nq, qs, _C.byref(p), _ptr(ids), _ptr(dist),
+                                                             _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2])))
+        finally:
+            if own:
+                f.release()
+        return (ids, dist) + tuple(cnt) if counters else (ids, dist)
+
+    def _range(self, batch, radius, ef, sem, filter, counters, keep):
+        Q, qs, nq = _batch(self.d, batch)
+        f, own = (None, False) if filter is None else self._filter(filter)
+        r = _C.c_void_p()
+        try:
+            fh = None if f is None else f.handle
+            if ef is None:
+                _check(load().hnsw_sharded_range_brute_force_batch(self.handle, fh, _ptr(Q), nq, qs, float(radius), _C.byref(r)))
+            else:
+                p = _RangeParams(float(radius), int(ef), sem)
+                _check(load().hnsw_sharded_range_search_batch(self.handle, fh, _ptr(Q), nq, qs, _C.byref(p), _C.byref(r)))
+        finally:
+            if own:
+                f.release()
+        return ShardedRangeResult(r)._take(counters, keep)
+
+    def range_search(self, batch, radius, ef=64, sem=SEM_OHNSW, filter=None, counters=False, keep=False):
+        """hnsw_sharded_range_search_batch -> (lims int64 [nq + 1], ids int64, distances), with counters also (ndist, nhops, stage):
+        per query the union of the shards' own range_search segments under (distance, global id); filter: a ShardedFilter or what
+        filter() takes; keep: the ShardedRangeResult instead"""
+        return self._range(batch, radius, ef, sem, filter, counters, keep)
+
+    def brute_force_range(self, batch, radius, filter=None, counters=False, keep=False):
+        """hnsw_sharded_range_brute_force_batch: the exact form -- the set Ohnsw.brute_force_range gives over one index of all rows"""
+        return self._range(batch, radius, None, SEM_OHNSW, filter, counters, keep)
 
     def release(self):
         if self._h is not None:

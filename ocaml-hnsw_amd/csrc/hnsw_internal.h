@@ -309,6 +309,14 @@ struct hnsw_filter {
     const uint32_t *const *table() const { return (const uint32_t *const *)((const char *)bits.p + table_offset(n)); }
 };
 
+// what a range call returns: lims, ids, distances and the per-query counters on the device of the index they came from
+// (hnsw_range.hip; the sharded range calls read the counters where they lie: hnsw_sharded.hip)
+struct hnsw_range_result {
+    int device = -1;
+    int64_t nq = 0, total = 0;
+    hnsw_host::DevBuf lims, ids, dist, nd, nh, stage;
+};
+
 struct hnsw_index {
     int device = -1;
     hnsw_dev::IndexView iv{};

@@ -287,13 +287,6 @@ range_fill_kernel(const RangeFillArgs a) {
 using hnsw_dev::IndexView;
 using namespace hnsw_host;
 
-// what a range call returns: lims, ids, distances and the per-query counters on the device of the index they came from
-struct hnsw_range_result {
-    int device = -1;
-    int64_t nq = 0, total = 0;
-    DevBuf lims, ids, dist, nd, nh, stage;
-};
-
 namespace {
 
 // out[0 .. count) = the exclusive sum of in[0 .. count) on st (count >= 1), through the handle's temporary storage

@@ -4,7 +4,14 @@
 // scales capacity.  The structure of a call is search_and_gather's: per-device streams, one flag word per device, a single host
 // round trip, knn_repair for a flagged shard -- with peer copies to devices[0] and the merge kernel where hnsw_multi has its
 // exchange.  No RCCL: the copies are 8 bytes * nq * k per shard.
+// The calls that are host-driven ladders on a single index -- filtered k-NN, range search -- run the public single-index call per
+// shard on a host thread of its own (on_shards) and merge what comes back: rows by the same merge kernel, range segments by the
+// rank merge (hnsw_merge_segments_kernel).  A sharded filter is the global mask cut into one ordinary filter per shard.
 #include "hnsw_internal.h"
+
+#include <atomic>
+#include <system_error>
+#include <thread>
 
 using namespace hnsw_host;
 
@@ -17,11 +24,12 @@ struct MergeArgs {
     const int32_t *ids;                  // [n_lists][nq][k_in], id_base-based ids local to the list
     const float *dist;                   // [n_lists][nq][k_in]
     const uint32_t *nd, *nh;             // [n_lists][nq] counters to sum per query, or null
+    const uint32_t *stg;                 // [n_lists][nq] a counter to reduce with max (unsigned) per query, or null
     int64_t nq;
     int32_t n_lists, k_in, k_out, id_base, fill;
     int64_t *out_ids;                    // [nq][k_out]: first_row[list] + id
     float *out_dist;                     // [nq][k_out]
-    uint32_t *out_nd, *out_nh;           // [nq], written when nd / nh are given
+    uint32_t *out_nd, *out_nh, *out_stg; // [nq], written when nd / nh / stg are given
     int64_t first_row[MERGE_LISTS];
 };
 
@@ -101,6 +109,147 @@ hnsw_merge_lists_kernel(const MergeArgs a) {
         const uint32_t s = wave_sum_u32(mine ? a.nh[(int64_t)lane * a.nq + q] : 0u);
         if (lane == 0) a.out_nh[q] = s;
     }
+    if (a.stg) {                                                                 // (the maximum: the minimum of the complements)
+        const uint32_t s = ~wave_min_u32(mine ? ~a.stg[(int64_t)lane * a.nq + q] : 0xFFFFFFFFu);
+        if (lane == 0) a.out_stg[q] = s;
+    }
+}
+
+// ---- the merge of variable-length sorted segments (the sharded range calls, hnsw_merge_segments) -----------------------------------
+// n_lists range results over the same nq queries: list g's segment for query q is the entries [lims_g[q], lims_g[q + 1]) of its ids
+// and distances, ascending by distance, no padding.  The lists' arrays lie one behind the other in one table per kind.
+//
+// Entries of EQUAL distance are expected in ascending id order, and almost always are.  Not always: a single-index range segment is
+// ordered by the scan's pre-rounding key, two different keys can round to one float distance (the header's ROUNDING EXCEPTION), and
+// then two entries of one distance stand in key order, the higher id first.  The merged order is (distance, global id) on the
+// returned floats, so such a pair is put right here: a pre-pass flags every (list, query) whose segment holds such a descent, and
+// only for a flagged segment the merge counts inside the run of equal distances entry by entry instead of by binary search.
+constexpr int SEG_BLOCK = 256;
+
+struct SegArgs {
+    const int64_t *lims;                 // [n_lists][nq + 1]: each list's own prefix sums
+    const int32_t *ids;                  // list g's ids from entry base[g] on, id_base-based and local to the list
+    const float *dist;                   // ... and its distances
+    int64_t nq;
+    int32_t n_lists;
+    uint8_t *flags;                      // [n_lists][nq], zeroed: 1 = the segment has equal distances with descending ids
+    int64_t *out_ids;                    // [sum of the lists' totals]: first_row[list] + id
+    float *out_dist;
+    int64_t base[MERGE_LISTS], first_row[MERGE_LISTS];
+};
+
+// the query of entry e of a list with the prefix sums lg (lg[nq] > e): lg[q] <= e < lg[q + 1]
+__device__ __forceinline__ int64_t segment_of(const int64_t *lg, int64_t nq, int64_t e) {
+    int64_t lo = 0, hi = nq;
+    while (hi - lo > 1) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (lg[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// The pre-pass, one thread per entry (grid as the merge's): an entry whose successor has the same distance and a lower id flags its
+// (list, query), if the successor belongs to the same query.  Plain stores of one value; the search for the query only at a descent.
+__global__ void __launch_bounds__(SEG_BLOCK)
+hnsw_merge_segments_flag_kernel(const SegArgs a) {
+    const int g = (int)blockIdx.y;
+    const int64_t *const lg = a.lims + (int64_t)g * (a.nq + 1);
+    const int64_t e = (int64_t)blockIdx.x * SEG_BLOCK + threadIdx.x;
+    if (e + 1 >= lg[a.nq]) return;
+    const int64_t at = a.base[g] + e;
+    if (merge_key(a.dist[at]) != merge_key(a.dist[at + 1]) || a.ids[at] <= a.ids[at + 1]) return;
+    const int64_t q = segment_of(lg, a.nq, e);
+    if (e + 1 < lg[q + 1]) a.flags[(int64_t)g * a.nq + q] = 1;
+}
+
+// A rank merge, one thread per input entry (grid y = the list, grid x over that list's entries: consecutive lanes load consecutive
+// ids and distances).  The thread finds its query q by a binary search of its flat index in its list's lims, loads its entry ONCE,
+// and its place in q's merged segment is
+//     sum over h of lims_h[q]  +  its index in its own segment  +  for every other list h the number of entries of S_h(q) before it,
+// where "before" is < under (merge_key(distance), global id as 64 bits) for h > g and <= for h < g: equal global ids in two lists
+// keep the lower list first, and the places of all entries of q are a permutation of q's merged segment.  Each count is one binary
+// search in S_h(q) (the distance is probed; the id only where the distances are equal).  A flagged S_h(q) -- the own segment
+// included -- is counted in two parts instead: the entries of a smaller distance (a binary search on the distance alone, which is
+// ascending whatever the ids do), then the run of this distance entry by entry, under (global id, list, index).  No atomics, no
+// loop as long as a segment (a run of one distance in a flagged segment is the longest), nothing that depends on the launch
+// geometry; empty segments and lists cost two loads of lims.  A place is < lims_out[q + 1] whatever the entries hold (each count is
+// at most |S_h(q)|): distances out of order give a wrong order, never a store out of bounds.
+__global__ void __launch_bounds__(SEG_BLOCK)
+hnsw_merge_segments_kernel(const SegArgs a) {
+    const int g = (int)blockIdx.y;
+    const int64_t stride = a.nq + 1;
+    const int64_t *const lg = a.lims + (int64_t)g * stride;
+    const int64_t e = (int64_t)blockIdx.x * SEG_BLOCK + threadIdx.x;
+    if (e >= lg[a.nq]) return;
+    const int64_t q = segment_of(lg, a.nq, e);
+    const float d = a.dist[a.base[g] + e];
+    const int64_t gid = a.first_row[g] + a.ids[a.base[g] + e];
+    const uint32_t key = merge_key(d);
+    int64_t pos = 0;
+    for (int h = 0; h < a.n_lists; ++h) {
+        const int64_t *const lh = a.lims + (int64_t)h * stride;
+        const int64_t b = lh[q], t = lh[q + 1];
+        pos += b;
+        if (b == t) continue;
+        const bool flagged = a.flags[(int64_t)h * a.nq + q] != 0;
+        if (h == g && !flagged) { pos += e - b; continue; }
+        const float *const dh = a.dist + a.base[h];
+        const int32_t *const ih = a.ids + a.base[h];
+        const int64_t first = a.first_row[h];
+        int64_t x = b, y = t;                                    // the entries of [b, x) are before this one, those of [y, t) are not
+        if (!flagged) {
+            while (x < y) {
+                const int64_t mid = x + ((y - x) >> 1);
+                const uint32_t km = merge_key(dh[mid]);
+                bool before = km < key;
+                if (km == key) {
+                    const int64_t gm = first + ih[mid];
+                    before = gm < gid || (gm == gid && h < g);
+                }
+                if (before) x = mid + 1; else y = mid;
+            }
+            pos += x - b;
+            continue;
+        }
+        while (x < y) {                                          // x: the first entry whose distance is not smaller
+            const int64_t mid = x + ((y - x) >> 1);
+            if (merge_key(dh[mid]) < key) x = mid + 1; else y = mid;
+        }
+        pos += x - b;
+        for (int64_t j = x; j < t && merge_key(dh[j]) == key; ++j) {
+            const int64_t gm = first + ih[j];
+            pos += (gm < gid || (gm == gid && (h < g || (h == g && j < e)))) ? 1 : 0;
+        }
+    }
+    a.out_ids[pos] = gid;
+    a.out_dist[pos] = d;
+}
+
+struct SegSumArgs {
+    const int64_t *lims;                 // [n_lists][nq + 1]
+    const uint32_t *nd, *nh, *stg;       // [n_lists][nq] the lists' counters, or null (all three): the merged counters read as 0
+    int64_t nq;
+    int32_t n_lists;
+    int64_t *out_lims;                   // [nq + 1]: the sum of the lists' lims, itself a prefix sum
+    uint32_t *out_nd, *out_nh, *out_stg; // [nq]: sum, sum, unsigned maximum
+};
+
+__global__ void __launch_bounds__(SEG_BLOCK)
+hnsw_merge_segments_sum_kernel(const SegSumArgs a) {
+    const int64_t q = (int64_t)blockIdx.x * SEG_BLOCK + threadIdx.x;
+    if (q > a.nq) return;
+    int64_t l = 0;
+    uint32_t nd = 0, nh = 0, stg = 0;
+    for (int g = 0; g < a.n_lists; ++g) {
+        l += a.lims[(int64_t)g * (a.nq + 1) + q];
+        if (a.nd && q < a.nq) {
+            nd += a.nd[(int64_t)g * a.nq + q];
+            nh += a.nh[(int64_t)g * a.nq + q];
+            stg = max(stg, a.stg[(int64_t)g * a.nq + q]);
+        }
+    }
+    a.out_lims[q] = l;
+    if (q < a.nq) { a.out_nd[q] = nd; a.out_nh[q] = nh; a.out_stg[q] = stg; }
 }
 
 } // namespace hnsw_dev
@@ -115,6 +264,23 @@ struct hnsw_sharded {
     Pinned<uint32_t> hFlags;             // [G] the launches' "any query flagged" words on the host
     // on devices[0]: every shard's results and counters ([G][nq][k], [G][nq]) and the merged rows.  One call in flight per handle.
     DevBuf gIds, gDist, gNd, gNh, mIds, mDist, mNd, mNh;
+    // ... the filtered search's stages ([G][nq] and merged), the range calls' concatenated lims ([G][nq + 1])
+    DevBuf gSt, mSt, gLims, gFlags;      // (gFlags: the segment merge's pre-pass, [G][nq] bytes)
+};
+
+// a mask over the global rows of one hnsw_sharded, cut into one ordinary filter per shard (which it owns)
+struct hnsw_sharded_filter {
+    const hnsw_sharded *owner = nullptr;
+    std::vector<hnsw_filter *> parts;    // [G]
+    ~hnsw_sharded_filter() { for (hnsw_filter *f : parts) (void)hnsw_filter_destroy(f); }
+};
+
+// what a sharded range call and hnsw_merge_segments return: as hnsw_range_result, with int64 global ids, on one device; it keeps no
+// reference to the handle it came from
+struct hnsw_sharded_range_result {
+    int device = -1;
+    int64_t nq = 0, total = 0;
+    DevBuf lims, ids, dist, nd, nh, stage;
 };
 
 namespace {
@@ -169,6 +335,44 @@ int copy_shard(hnsw_sharded *s, int g, int64_t nq, int k, bool with_counters) {
     return HNSW_OK;
 }
 
+// the tables of one k-NN call on devices[0] (the current device): every shard's rows and counters, the merged rows and counters
+int ensure_merge_tables(hnsw_sharded *s, int64_t nq, int k) {
+    const size_t G = s->shards.size(), rows = (size_t)nq * k;
+    int rc;
+    if ((rc = s->gIds.ensure(G * rows * 4)) || (rc = s->gDist.ensure(G * rows * 4)) || (rc = s->gNd.ensure(G * nq * 4)) ||
+        (rc = s->gNh.ensure(G * nq * 4)) || (rc = s->gSt.ensure(G * nq * 4)) || (rc = s->mIds.ensure(rows * 8)) || (rc = s->mDist.ensure(rows * 4)) ||
+        (rc = s->mNd.ensure((size_t)nq * 4)) || (rc = s->mNh.ensure((size_t)nq * 4)) || (rc = s->mSt.ensure((size_t)nq * 4)))
+        return rc;
+    return HNSW_OK;
+}
+
+// The end of every sharded k-NN call: the shards' rows lie in the tables on devices[0] (or are queued there on streams[0]); the
+// merge kernel, ONE download into the caller's arrays, the wait.  with_stage: the third counter table, reduced with max.
+int merge_and_download(hnsw_sharded *s, int64_t nq, int k, int32_t fill, bool with_counters, bool with_stage, int64_t *out_ids, float *out_dist,
+                       uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_st) {
+    const int G = (int)s->shards.size();
+    const size_t rows = (size_t)nq * k;
+    HIP_TRY(hipSetDevice(s->devices[0]));
+    hipStream_t st = s->streams[0];
+    MergeArgs a{(const int32_t *)s->gIds.p, (const float *)s->gDist.p, with_counters ? (const uint32_t *)s->gNd.p : nullptr,
+                with_counters ? (const uint32_t *)s->gNh.p : nullptr, with_stage ? (const uint32_t *)s->gSt.p : nullptr, nq, G, k, k,
+                s->shards[0]->iv.id_base, fill, (int64_t *)s->mIds.p, (float *)s->mDist.p, (uint32_t *)s->mNd.p, (uint32_t *)s->mNh.p,
+                (uint32_t *)s->mSt.p, {}};
+    for (int g = 0; g < G; ++g) a.first_row[g] = s->lo[(size_t)g];
+    const int rc = launch_merge(a, st);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(out_ids, s->mIds.p, rows * 8, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(out_dist, s->mDist.p, rows * 4, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess && with_counters && out_nd) e = hipMemcpyAsync(out_nd, s->mNd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess && with_counters && out_nh) e = hipMemcpyAsync(out_nh, s->mNh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess && with_stage && out_st) e = hipMemcpyAsync(out_st, s->mSt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (rc) return rc;
+    if (e != hipSuccess) return hip_fail(e, "result download");
+    if (es != hipSuccess) return hip_fail(es, "sharded search");
+    return HNSW_OK;
+}
+
 // Every shard answers the whole batch on its own device and stream (`search`: what is queued on shard g's stream behind the
 // upload), the answers go to devices[0] behind an event, after the one host round trip `repair` re-does a flagged shard, then the
 // merge and the download.  Both sharded entry points.
@@ -177,7 +381,7 @@ int search_and_merge(hnsw_sharded *s, const float *queries, int64_t nq, int64_t 
                      int64_t *out_ids, float *out_dist, uint32_t *out_nd, uint32_t *out_nh, Search &&search, Repair &&repair) {
     const int G = (int)s->shards.size();
     const int d = s->shards[0]->iv.d;
-    const size_t qbytes = query_bytes(nq, q_stride, d), rows = (size_t)nq * k;
+    const size_t qbytes = query_bytes(nq, q_stride, d);
     int rc;
     // ---- every allocation first: nothing below returns with work queued that it does not wait for ----
     if ((rc = ensure_streams(s))) return rc;
@@ -186,10 +390,7 @@ int search_and_merge(hnsw_sharded *s, const float *queries, int64_t nq, int64_t 
         if ((rc = s->buf[(size_t)g].ensure(nq, qbytes, k))) return rc;
     }
     HIP_TRY(hipSetDevice(s->devices[0]));
-    if ((rc = s->gIds.ensure((size_t)G * rows * 4)) || (rc = s->gDist.ensure((size_t)G * rows * 4)) || (rc = s->gNd.ensure((size_t)G * nq * 4)) ||
-        (rc = s->gNh.ensure((size_t)G * nq * 4)) || (rc = s->mIds.ensure(rows * 8)) || (rc = s->mDist.ensure(rows * 4)) ||
-        (rc = s->mNd.ensure((size_t)nq * 4)) || (rc = s->mNh.ensure((size_t)nq * 4)))
-        return rc;
+    if ((rc = ensure_merge_tables(s, nq, k))) return rc;
     auto queued = [&]() -> int {
         for (int g = 0; g < G; ++g) {
             const BatchBufs &b = s->buf[(size_t)g];
@@ -226,23 +427,7 @@ int search_and_merge(hnsw_sharded *s, const float *queries, int64_t nq, int64_t 
         HIP_TRY(hipSetDevice(s->devices[0]));
         if ((rc = copy_shard(s, g, nq, k, with_counters))) { (void)sync_all(s); return rc; }
     }
-    HIP_TRY(hipSetDevice(s->devices[0]));
-    hipStream_t st = s->streams[0];
-    MergeArgs a{(const int32_t *)s->gIds.p, (const float *)s->gDist.p, with_counters ? (const uint32_t *)s->gNd.p : nullptr,
-                with_counters ? (const uint32_t *)s->gNh.p : nullptr, nq, G, k, k, s->shards[0]->iv.id_base, fill,
-                (int64_t *)s->mIds.p, (float *)s->mDist.p, (uint32_t *)s->mNd.p, (uint32_t *)s->mNh.p, {}};
-    for (int g = 0; g < G; ++g) a.first_row[g] = s->lo[(size_t)g];
-    rc = launch_merge(a, st);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(out_ids, s->mIds.p, rows * 8, hipMemcpyDeviceToHost, st);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(out_dist, s->mDist.p, rows * 4, hipMemcpyDeviceToHost, st);
-    if (!rc && e == hipSuccess && with_counters && out_nd) e = hipMemcpyAsync(out_nd, s->mNd.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-    if (!rc && e == hipSuccess && with_counters && out_nh) e = hipMemcpyAsync(out_nh, s->mNh.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (rc) return rc;
-    if (e != hipSuccess) return hip_fail(e, "result download");
-    if (es != hipSuccess) return hip_fail(es, "sharded search");
-    return HNSW_OK;
+    return merge_and_download(s, nq, k, fill, with_counters, false, out_ids, out_dist, out_nd, out_nh, nullptr);
 }
 
 int check_shard_count(int32_t n_shards) {
@@ -274,6 +459,150 @@ template <class Make> int make_shards(const int32_t *devices, int32_t n_shards, 
         if (rc) { (void)hnsw_sharded_destroy(s); return rc; }   // (the message of the failing call stays)
     }
     *out = s;
+    return HNSW_OK;
+}
+
+// ---- the calls that are host-driven ladders on a single index: filtered k-NN and the range calls ----------------------------------
+constexpr int SHARD_THREADS = 16;        // host threads that drive shard calls at a time
+
+// call(g) for every shard, each on a host thread whose current device is the shard's: at most SHARD_THREADS threads, which take the
+// shards in order off one counter; all are joined before this returns.  The single-index calls they make are complete on return
+// and touch only their own handle (its scratch, its stream; the library's one process-wide table, the registered host ranges, is
+// behind a mutex).  The error message is thread-local: a failing shard's is taken on its thread, and the lowest-numbered failing
+// shard's code and message become this thread's.  One shard, or no thread to be had: on the calling thread, in order.
+template <class Call> int on_shards(hnsw_sharded *s, Call &&call) {
+    const int G = (int)s->shards.size();
+    std::vector<int> rc((size_t)G, HNSW_OK);
+    std::vector<std::string> msg((size_t)G);
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int g; (g = next.fetch_add(1)) < G;) {
+            const hipError_t e = hipSetDevice(s->devices[(size_t)g]);
+            rc[(size_t)g] = e == hipSuccess ? call(g) : hip_fail(e, "hipSetDevice");
+            if (rc[(size_t)g]) msg[(size_t)g] = hnsw_last_error();
+        }
+    };
+    std::vector<std::thread> threads;
+    if (G > 1) {
+        try {
+            for (int t = 0; t < std::min(G, SHARD_THREADS); ++t) threads.emplace_back(work);
+        } catch (const std::system_error &) {}       // (the threads that did start take every shard)
+    }
+    if (threads.empty()) work();
+    for (std::thread &t : threads) t.join();
+    for (int g = 0; g < G; ++g)
+        if (rc[(size_t)g]) return fail(rc[(size_t)g], "%s", msg[(size_t)g].c_str());
+    return HNSW_OK;
+}
+
+int check_sharded_filter(const hnsw_sharded *s, const hnsw_sharded_filter *f) {
+    if (!f) return fail(HNSW_ERR_BAD_ARG, "null sharded filter");
+    if (f->owner != s || f->parts.size() != s->shards.size()) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another hnsw_sharded");
+    return HNSW_OK;
+}
+
+struct RangeResultDeleter { void operator()(hnsw_range_result *r) const { (void)hnsw_range_result_destroy(r); } };
+using RangeResultPtr = std::unique_ptr<hnsw_range_result, RangeResultDeleter>;
+
+// The merge of n_lists range results that lie on `device` (current) as SegArgs describes them -- a.lims, a.ids, a.dist, a.base,
+// a.first_row, a.nq, a.n_lists set; totals[g] = list g's entries -- queued on st and waited for: r's buffers are allocated here, once
+// the summed total is known to fit.  nd / nh / stg: the lists' counters ([n_lists][nq], device), or all null.  flags: scratch for the
+// pre-pass ([n_lists][nq] bytes).
+int merge_segments_on_device(int device, hipStream_t st, hnsw_dev::SegArgs a, const std::vector<int64_t> &totals, const uint32_t *nd,
+                             const uint32_t *nh, const uint32_t *stg, DevBuf &flags, hnsw_sharded_range_result *r) {
+    int64_t total = 0, longest = 0;
+    for (int64_t t : totals) { total += t; longest = std::max(longest, t); }
+    if (total > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "%lld merged results: more than 2^31 - 1 in one call", (long long)total);
+    r->device = device;
+    r->nq = a.nq;
+    r->total = total;
+    const size_t cnt = (size_t)std::max<int64_t>(a.nq, 1) * 4;
+    int rc;
+    if ((rc = r->lims.ensure((size_t)(a.nq + 1) * 8)) || (rc = r->ids.ensure((size_t)std::max<int64_t>(total, 1) * 8)) ||
+        (rc = r->dist.ensure((size_t)std::max<int64_t>(total, 1) * 4)) || (rc = r->nd.ensure(cnt)) || (rc = r->nh.ensure(cnt)) || (rc = r->stage.ensure(cnt)))
+        return rc;
+    const hnsw_dev::SegSumArgs sa{a.lims, nd, nh, stg, a.nq, a.n_lists, (int64_t *)r->lims.p, (uint32_t *)r->nd.p, (uint32_t *)r->nh.p, (uint32_t *)r->stage.p};
+    hipLaunchKernelGGL(hnsw_dev::hnsw_merge_segments_sum_kernel, dim3((unsigned)((a.nq + 1 + hnsw_dev::SEG_BLOCK - 1) / hnsw_dev::SEG_BLOCK)),
+                       dim3(hnsw_dev::SEG_BLOCK), 0, st, sa);
+    rc = launched("segment sum kernel");
+    if (!rc && longest > 0) {
+        const size_t fbytes = (size_t)a.n_lists * (size_t)a.nq;
+        if ((rc = flags.ensure(fbytes))) { (void)hipStreamSynchronize(st); return rc; }
+        a.flags = (uint8_t *)flags.p;
+        a.out_ids = (int64_t *)r->ids.p;
+        a.out_dist = (float *)r->dist.p;
+        const dim3 grid((unsigned)((longest + hnsw_dev::SEG_BLOCK - 1) / hnsw_dev::SEG_BLOCK), (unsigned)a.n_lists);
+        if (hipMemsetAsync(flags.p, 0, fbytes, st) != hipSuccess) rc = fail(HNSW_ERR_HIP, "memset failed");
+        if (!rc) {
+            hipLaunchKernelGGL(hnsw_dev::hnsw_merge_segments_flag_kernel, grid, dim3(hnsw_dev::SEG_BLOCK), 0, st, a);
+            rc = launched("segment flag kernel");
+        }
+        if (!rc) {
+            hipLaunchKernelGGL(hnsw_dev::hnsw_merge_segments_kernel, grid, dim3(hnsw_dev::SEG_BLOCK), 0, st, a);
+            rc = launched("segment merge kernel");
+        }
+    }
+    const int rs = synced(st, "segment merge");
+    return rc ? rc : rs;
+}
+
+// Both sharded range calls once s, f and out are checked: `call` makes shard g's single-index call (complete on return, its result on
+// the shard's device); the results go to devices[0] by peer copies on streams[0], one table per kind, and are merged there.
+template <class Call> int sharded_range(hnsw_sharded *s, int64_t nq, hnsw_sharded_range_result **out, Call &&call) {
+    const int G = (int)s->shards.size();
+    std::vector<RangeResultPtr> part((size_t)G);
+    int rc = on_shards(s, [&](int g) {
+        hnsw_range_result *r = nullptr;
+        const int c = call(g, &r);
+        part[(size_t)g].reset(r);
+        return c;
+    });
+    if (rc) return rc;                   // (the shard results are destroyed with `part`)
+    hnsw_dev::SegArgs a{};
+    a.nq = nq;
+    a.n_lists = G;
+    std::vector<int64_t> totals((size_t)G);
+    int64_t sum = 0;
+    for (int g = 0; g < G; ++g) {
+        a.base[g] = sum;
+        a.first_row[g] = s->lo[(size_t)g];
+        sum += totals[(size_t)g] = part[(size_t)g]->total;
+    }
+    if (sum > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "%lld merged results: more than 2^31 - 1 in one call", (long long)sum);
+    if ((rc = ensure_streams(s))) return rc;
+    const int d0 = s->devices[0];
+    HIP_TRY(hipSetDevice(d0));
+    hipStream_t st = s->streams[0];
+    const size_t lbytes = (size_t)(nq + 1) * 8, cbytes = (size_t)nq * 4;
+    if ((rc = s->gLims.ensure((size_t)G * lbytes)) || (rc = s->gIds.ensure((size_t)std::max<int64_t>(sum, 1) * 4)) ||
+        (rc = s->gDist.ensure((size_t)std::max<int64_t>(sum, 1) * 4)) || (rc = s->gNd.ensure(std::max<size_t>((size_t)G * cbytes, 4))) ||
+        (rc = s->gNh.ensure(std::max<size_t>((size_t)G * cbytes, 4))) || (rc = s->gSt.ensure(std::max<size_t>((size_t)G * cbytes, 4))))
+        return rc;
+    auto copies = [&]() -> int {
+        for (int g = 0; g < G; ++g) {
+            const hnsw_range_result &p = *part[(size_t)g];
+            const size_t ebytes = (size_t)p.total * 4;
+            HIP_TRY(hipMemcpyPeerAsync((char *)s->gLims.p + (size_t)g * lbytes, d0, p.lims.p, p.device, lbytes, st));
+            if (ebytes) {
+                HIP_TRY(hipMemcpyPeerAsync((int32_t *)s->gIds.p + a.base[g], d0, p.ids.p, p.device, ebytes, st));
+                HIP_TRY(hipMemcpyPeerAsync((float *)s->gDist.p + a.base[g], d0, p.dist.p, p.device, ebytes, st));
+            }
+            if (cbytes) {
+                HIP_TRY(hipMemcpyPeerAsync((char *)s->gNd.p + (size_t)g * cbytes, d0, p.nd.p, p.device, cbytes, st));
+                HIP_TRY(hipMemcpyPeerAsync((char *)s->gNh.p + (size_t)g * cbytes, d0, p.nh.p, p.device, cbytes, st));
+                HIP_TRY(hipMemcpyPeerAsync((char *)s->gSt.p + (size_t)g * cbytes, d0, p.stage.p, p.device, cbytes, st));
+            }
+        }
+        return HNSW_OK;
+    };
+    if ((rc = copies())) { (void)hipStreamSynchronize(st); return rc; }     // (nothing stays queued that reads a shard result)
+    a.lims = (const int64_t *)s->gLims.p;
+    a.ids = (const int32_t *)s->gIds.p;
+    a.dist = (const float *)s->gDist.p;
+    std::unique_ptr<hnsw_sharded_range_result> r(new hnsw_sharded_range_result());
+    rc = merge_segments_on_device(d0, st, a, totals, nq ? (const uint32_t *)s->gNd.p : nullptr, (const uint32_t *)s->gNh.p, (const uint32_t *)s->gSt.p, s->gFlags, r.get());
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    *out = r.release();
     return HNSW_OK;
 }
 
@@ -418,12 +747,214 @@ int32_t hnsw_merge_lists(int32_t device, const int32_t *ids, const float *dist, 
     if ((rc = dIds.ensure(in)) || (rc = dDist.ensure(in)) || (rc = oIds.ensure(rows * 8)) || (rc = oDist.ensure(rows * 4))) return rc;
     HIP_TRY(hipMemcpy(dIds.p, ids, in, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dDist.p, dist, in, hipMemcpyHostToDevice));
-    MergeArgs a{(const int32_t *)dIds.p, (const float *)dDist.p, nullptr, nullptr, nq, n_lists, k_in, k_out, id_base, fill,
-                (int64_t *)oIds.p, (float *)oDist.p, nullptr, nullptr, {}};
+    MergeArgs a{(const int32_t *)dIds.p, (const float *)dDist.p, nullptr, nullptr, nullptr, nq, n_lists, k_in, k_out, id_base, fill,
+                (int64_t *)oIds.p, (float *)oDist.p, nullptr, nullptr, nullptr, {}};
     for (int g = 0; g < n_lists; ++g) a.first_row[g] = first_row[g];
     if ((rc = launch_merge(a, nullptr))) return rc;
     HIP_TRY(hipMemcpy(out_ids, oIds.p, rows * 8, hipMemcpyDeviceToHost));       // (the null stream: behind the kernel)
     HIP_TRY(hipMemcpy(out_dist, oDist.p, rows * 4, hipMemcpyDeviceToHost));
+    return HNSW_OK;
+}
+
+// ---- sharded filter, filtered k-NN, range search ------------------------------------------------------------------------------------
+
+int32_t hnsw_sharded_filter_create(hnsw_sharded *s, const uint32_t *bits, int64_t n_bits, hnsw_sharded_filter **out) {
+    if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
+    *out = nullptr;
+    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    if (n_bits != s->lo.back())
+        return fail(HNSW_ERR_BAD_ARG, "the filter has %lld bits, the sharded index %lld rows", (long long)n_bits, (long long)s->lo.back());
+    if (n_bits > 0 && !bits) return fail(HNSW_ERR_BAD_ARG, "null bits");
+    std::unique_ptr<hnsw_sharded_filter> f(new hnsw_sharded_filter());      // (owns the parts made so far: any return frees them)
+    f->owner = s;
+    const int64_t src_words = (n_bits + 31) / 32;
+    std::vector<uint32_t> part;
+    for (size_t g = 0; g < s->shards.size(); ++g) {
+        // shard g's bits [lo_g, lo_{g+1}) moved down to bit 0: a funnel shift over two source words, the tail of the last word clear
+        const int64_t lo = s->lo[g], n = s->lo[g + 1] - lo, words = (n + 31) / 32, w0 = lo >> 5;
+        const int sh = (int)(lo & 31);
+        part.assign((size_t)std::max<int64_t>(words, 1), 0u);
+        for (int64_t w = 0; w < words; ++w) {
+            const uint64_t a = bits[w0 + w], b = w0 + w + 1 < src_words ? bits[w0 + w + 1] : 0u;
+            part[(size_t)w] = (uint32_t)((a | (b << 32)) >> sh);
+        }
+        if (n & 31) part[(size_t)words - 1] &= (1u << (n & 31)) - 1u;
+        hnsw_filter *pf = nullptr;
+        const int rc = hnsw_filter_create(s->shards[g], part.data(), n, &pf);
+        if (rc) return rc;
+        f->parts.push_back(pf);
+    }
+    *out = f.release();
+    return HNSW_OK;
+}
+
+int32_t hnsw_sharded_filter_destroy(hnsw_sharded_filter *f) {
+    delete f;
+    return HNSW_OK;
+}
+
+int32_t hnsw_sharded_filter_count(const hnsw_sharded_filter *f, int64_t *n_allowed) {
+    if (!f || !n_allowed) return fail(HNSW_ERR_BAD_ARG, "null sharded filter or null n_allowed");
+    int64_t c = 0;
+    for (const hnsw_filter *p : f->parts) c += p->n_allowed;
+    *n_allowed = c;
+    return HNSW_OK;
+}
+
+int32_t hnsw_sharded_filter_part(const hnsw_sharded_filter *f, int32_t g, const hnsw_filter **out) {
+    if (!f || !out) return fail(HNSW_ERR_BAD_ARG, "null sharded filter or null out");
+    if (g < 0 || g >= (int32_t)f->parts.size()) return fail(HNSW_ERR_BAD_ARG, "shard %d out of range", g);
+    *out = f->parts[(size_t)g];
+    return HNSW_OK;
+}
+
+int32_t hnsw_sharded_search_batch_filtered(hnsw_sharded *s, const hnsw_sharded_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                           const hnsw_search_params *params, int64_t *out_ids, float *out_dist, uint32_t *out_ndist,
+                                           uint32_t *out_nhops, uint32_t *out_stage) {
+    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    int rc = check_batch(s->shards[0], params, nq, q_stride, queries && out_ids && out_dist);
+    if (rc) return rc;
+    if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
+        return fail(HNSW_ERR_BAD_ARG, "HNSW_SEM_FUNCTOR_NEAREST_K: the k farthest of W have no merged meaning over shards");
+    for (size_t g = 1; g < s->shards.size(); ++g) if ((rc = check_params(s->shards[g], params))) return rc;   // (an empty shard)
+    if ((rc = check_sharded_filter(s, f))) return rc;
+    if (nq == 0) return HNSW_OK;
+    // The single-index call is a host-driven ladder that answers into host arrays: every shard's rows and counters pass through
+    // these, then go to the tables on devices[0] in one copy per table
+    const size_t G = s->shards.size(), k = (size_t)params->k, rows = (size_t)nq * k;
+    std::vector<int32_t> ids(G * rows);
+    std::vector<float> dist(G * rows);
+    std::vector<uint32_t> cnt(3 * G * (size_t)nq);
+    uint32_t *const nd = cnt.data(), *const nh = nd + G * (size_t)nq, *const stg = nh + G * (size_t)nq;
+    rc = on_shards(s, [&](int g) {
+        const size_t z = (size_t)g;
+        return (int)hnsw_search_batch_filtered(s->shards[z], f->parts[z], queries, nq, q_stride, params, ids.data() + z * rows, dist.data() + z * rows,
+                                               nd + z * (size_t)nq, nh + z * (size_t)nq, stg + z * (size_t)nq);
+    });
+    if (rc || (rc = ensure_streams(s))) return rc;
+    HIP_TRY(hipSetDevice(s->devices[0]));
+    if ((rc = ensure_merge_tables(s, nq, (int)k))) return rc;
+    hipStream_t st = s->streams[0];
+    hipError_t e = hipMemcpyAsync(s->gIds.p, ids.data(), G * rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->gDist.p, dist.data(), G * rows * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->gNd.p, nd, G * (size_t)nq * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->gNh.p, nh, G * (size_t)nq * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->gSt.p, stg, G * (size_t)nq * 4, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "shard rows upload"); }
+    return merge_and_download(s, nq, (int)k, params->fill, true, true, out_ids, out_dist, out_ndist, out_nhops, out_stage);
+}
+
+int32_t hnsw_sharded_range_search_batch(hnsw_sharded *s, const hnsw_sharded_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                        const hnsw_range_params *params, hnsw_sharded_range_result **out) {
+    if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
+    *out = nullptr;
+    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    int rc;
+    if (f && (rc = check_sharded_filter(s, f))) return rc;
+    return sharded_range(s, nq, out, [&](int g, hnsw_range_result **r) {
+        hnsw_index *idx = s->shards[(size_t)g];
+        return (int)(f ? hnsw_range_search_batch_filtered(idx, f->parts[(size_t)g], queries, nq, q_stride, params, r)
+                       : hnsw_range_search_batch(idx, queries, nq, q_stride, params, r));
+    });
+}
+
+int32_t hnsw_sharded_range_brute_force_batch(hnsw_sharded *s, const hnsw_sharded_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                             float radius, hnsw_sharded_range_result **out) {
+    if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
+    *out = nullptr;
+    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    int rc;
+    if (f && (rc = check_sharded_filter(s, f))) return rc;
+    return sharded_range(s, nq, out, [&](int g, hnsw_range_result **r) {
+        hnsw_index *idx = s->shards[(size_t)g];
+        return (int)(f ? hnsw_range_brute_force_batch_filtered(idx, f->parts[(size_t)g], queries, nq, q_stride, radius, r)
+                       : hnsw_range_brute_force_batch(idx, queries, nq, q_stride, radius, r));
+    });
+}
+
+int32_t hnsw_sharded_range_result_size(const hnsw_sharded_range_result *r, int64_t *nq, int64_t *total) {
+    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+    if (nq) *nq = r->nq;
+    if (total) *total = r->total;
+    return HNSW_OK;
+}
+
+int32_t hnsw_sharded_range_result_fetch(hnsw_sharded_range_result *r, int64_t *lims, int64_t *ids, float *dist, uint32_t *out_ndist,
+                                        uint32_t *out_nhops, uint32_t *out_stage) {
+    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+    if (!lims && !ids && !dist && !out_ndist && !out_nhops && !out_stage) return HNSW_OK;
+    HIP_TRY(hipSetDevice(r->device));
+    if (lims) HIP_TRY(hipMemcpy(lims, r->lims.p, (size_t)(r->nq + 1) * 8, hipMemcpyDeviceToHost));
+    if (ids && r->total > 0) HIP_TRY(hipMemcpy(ids, r->ids.p, (size_t)r->total * 8, hipMemcpyDeviceToHost));
+    if (dist && r->total > 0) HIP_TRY(hipMemcpy(dist, r->dist.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
+    if (r->nq > 0) {
+        if (out_ndist) HIP_TRY(hipMemcpy(out_ndist, r->nd.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+        if (out_nhops) HIP_TRY(hipMemcpy(out_nhops, r->nh.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+        if (out_stage) HIP_TRY(hipMemcpy(out_stage, r->stage.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+    }
+    return HNSW_OK;
+}
+
+int32_t hnsw_sharded_range_result_device(hnsw_sharded_range_result *r, const int64_t **d_lims, const int64_t **d_ids, const float **d_dist) {
+    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+    if (d_lims) *d_lims = (const int64_t *)r->lims.p;
+    if (d_ids) *d_ids = (const int64_t *)r->ids.p;
+    if (d_dist) *d_dist = (const float *)r->dist.p;
+    return HNSW_OK;
+}
+
+int32_t hnsw_sharded_range_result_destroy(hnsw_sharded_range_result *r) {
+    delete r;
+    return HNSW_OK;
+}
+
+int32_t hnsw_merge_segments(int32_t device, int32_t n_lists, int64_t nq, const int64_t *const *lims, const int32_t *const *ids,
+                            const float *const *dist, const int64_t *first_row, int32_t id_base, hnsw_sharded_range_result **out) {
+    (void)id_base;                       // (segments carry no padding: nothing to tell from a real id)
+    if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
+    *out = nullptr;
+    if (n_lists < 1 || n_lists > MERGE_LISTS) return fail(HNSW_ERR_BAD_ARG, "n_lists=%d must be in 1..64", n_lists);
+    if (nq < 0 || nq > 0x7FFFFFFFLL) return fail(HNSW_ERR_BAD_ARG, "nq=%lld out of range", (long long)nq);
+    if (!lims || !first_row) return fail(HNSW_ERR_BAD_ARG, "null buffer");
+    hnsw_dev::SegArgs a{};
+    a.nq = nq;
+    a.n_lists = n_lists;
+    std::vector<int64_t> totals((size_t)n_lists);
+    int64_t sum = 0;
+    for (int g = 0; g < n_lists; ++g) {
+        if (g > 0 && first_row[g] < first_row[g - 1]) return fail(HNSW_ERR_BAD_ARG, "first_row must be non-decreasing (list %d)", g);
+        if (!lims[g]) return fail(HNSW_ERR_BAD_ARG, "lims[%d] is null", g);
+        if (lims[g][0] != 0) return fail(HNSW_ERR_BAD_ARG, "lims[%d] must start at 0", g);
+        for (int64_t q = 0; q < nq; ++q)
+            if (lims[g][q + 1] < lims[g][q]) return fail(HNSW_ERR_BAD_ARG, "lims[%d] must be non-decreasing (query %lld)", g, (long long)q);
+        const int64_t t = lims[g][nq];
+        if (t > 0 && (!ids || !dist || !ids[g] || !dist[g])) return fail(HNSW_ERR_BAD_ARG, "list %d has entries and no ids or distances", g);
+        if (t > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "list %d has %lld entries: more than 2^31 - 1", g, (long long)t);
+        a.base[g] = sum;
+        a.first_row[g] = first_row[g];
+        sum += totals[(size_t)g] = t;
+    }
+    if (sum > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "%lld merged results: more than 2^31 - 1 in one call", (long long)sum);
+    HIP_TRY(hipSetDevice(device));
+    const size_t lbytes = (size_t)(nq + 1) * 8;
+    DevBuf dLims, dIds, dDist;
+    int rc;
+    if ((rc = dLims.ensure((size_t)n_lists * lbytes)) || (rc = dIds.ensure((size_t)std::max<int64_t>(sum, 1) * 4)) ||
+        (rc = dDist.ensure((size_t)std::max<int64_t>(sum, 1) * 4)))
+        return rc;
+    for (int g = 0; g < n_lists; ++g) {
+        HIP_TRY(hipMemcpy((char *)dLims.p + (size_t)g * lbytes, lims[g], lbytes, hipMemcpyHostToDevice));
+        if (totals[(size_t)g] == 0) continue;
+        HIP_TRY(hipMemcpy((int32_t *)dIds.p + a.base[g], ids[g], (size_t)totals[(size_t)g] * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((float *)dDist.p + a.base[g], dist[g], (size_t)totals[(size_t)g] * 4, hipMemcpyHostToDevice));
+    }
+    a.lims = (const int64_t *)dLims.p;
+    a.ids = (const int32_t *)dIds.p;
+    a.dist = (const float *)dDist.p;
+    std::unique_ptr<hnsw_sharded_range_result> r(new hnsw_sharded_range_result());
+    DevBuf flags;
+    if ((rc = merge_segments_on_device(device, nullptr, a, totals, nullptr, nullptr, nullptr, flags, r.get()))) return rc;   // (the null stream: behind the copies)
+    *out = r.release();
     return HNSW_OK;
 }
 

@@ -13,7 +13,10 @@
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
 //   Hnsw::MultiHgraph (one process, several GPUs)                                SURVEY 8e
 //   Hnsw::Sharded, Hnsw::merge_lists (the rows partitioned over several GPUs)    (hnsw_sharded_*, hnsw_merge_lists)
-//   Hnsw::Stats::compute (Hgraph.Stats)                                         lib/hnsw.ml:353-375
+//   Hnsw::ShardedFilter, Hnsw::ShardedRangeResult, Hnsw::Sharded::knn_filtered / range_search / brute_force_range,
+//   Hnsw::merge_segments                                                         (hnsw_sharded_filter_*, hnsw_sharded_search_batch_filtered,
+//                                                                                 hnsw_sharded_range_*, hnsw_merge_segments)
+//   Hnsw::Stats::compute (Hgraph.Stats)                                        lib/hnsw.ml:353-375
 //   Hnsw::HostMat (a page-locked Lacaml-shaped matrix the device accesses directly: hnsw_host_alloc)
 //
 // Same names, argument meaning and error behaviour: OCaml Invalid_argument -> std::invalid_argument
@@ -482,6 +485,55 @@ private:
     int d_ = 0;
 };
 
+class Sharded;
+
+// An allow-mask over the GLOBAL rows of one Sharded (hnsw_sharded_filter_create): allow[v] = global row v may be returned.  One
+// ordinary filter per shard, cut on the host; never stale (shards cannot change).  Destroy it before its Sharded.
+class ShardedFilter {
+public:
+    ShardedFilter(const Sharded &s, const std::vector<bool> &allow);
+    ShardedFilter(const ShardedFilter &) = delete;
+    ShardedFilter &operator=(const ShardedFilter &) = delete;
+    ShardedFilter(ShardedFilter &&o) noexcept : f_(o.f_) { o.f_ = nullptr; }
+    ~ShardedFilter() { if (f_) hnsw_sharded_filter_destroy(f_); }
+    const hnsw_sharded_filter *handle() const { return f_; }
+    int64_t count() const { int64_t c = 0; check(hnsw_sharded_filter_count(f_, &c)); return c; }   // the allowed rows of all shards
+    // shard g's part (borrowed): an ordinary filter of that shard's handle
+    const hnsw_filter *part(int g) const { const hnsw_filter *p = nullptr; check(hnsw_sharded_filter_part(f_, g, &p)); return p; }
+private:
+    hnsw_sharded_filter *f_ = nullptr;
+};
+
+// What a sharded range call and merge_segments return (hnsw_sharded_range_result): as RangeResult with int64 global ids, on the
+// first device of its Sharded, which it outlives.
+class ShardedRangeResult {
+public:
+    static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
+    struct Host { std::vector<int64_t> lims, ids; std::vector<float> dist; std::vector<uint32_t> ndist, nhops, stage; };
+    explicit ShardedRangeResult(hnsw_sharded_range_result *r) : r_(r) {}
+    ShardedRangeResult(const ShardedRangeResult &) = delete;
+    ShardedRangeResult &operator=(const ShardedRangeResult &) = delete;
+    ShardedRangeResult(ShardedRangeResult &&o) noexcept : r_(o.r_) { o.r_ = nullptr; }
+    ~ShardedRangeResult() { if (r_) hnsw_sharded_range_result_destroy(r_); }
+    hnsw_sharded_range_result *handle() const { return r_; }
+    int64_t nq() const { int64_t a = 0, b = 0; check(hnsw_sharded_range_result_size(r_, &a, &b)); return a; }
+    int64_t total() const { int64_t a = 0, b = 0; check(hnsw_sharded_range_result_size(r_, &a, &b)); return b; }
+    // everything on the host (hnsw_sharded_range_result_fetch)
+    Host fetch() const {
+        const size_t n = (size_t)nq(), t = (size_t)total();
+        Host h{std::vector<int64_t>(n + 1, 0), std::vector<int64_t>(t), std::vector<float>(t), std::vector<uint32_t>(n), std::vector<uint32_t>(n),
+               std::vector<uint32_t>(n)};
+        check(hnsw_sharded_range_result_fetch(r_, h.lims.data(), h.ids.data(), h.dist.data(), h.ndist.data(), h.nhops.data(), h.stage.data()));
+        return h;
+    }
+    // borrowed device pointers, valid while this object lives (hnsw_sharded_range_result_device)
+    void device(const int64_t **d_lims, const int64_t **d_ids, const float **d_dist) const {
+        check(hnsw_sharded_range_result_device(r_, d_lims, d_ids, d_dist));
+    }
+private:
+    hnsw_sharded_range_result *r_ = nullptr;
+};
+
 // One data set PARTITIONED over several GPUs (hnsw_sharded_*): shard g holds the rows [first_row(g), first_row(g + 1)) with a graph
 // of its own on devices[g]; every query visits all shards and the per-shard answers are merged on devices[0] under (distance,
 // global id).  Global ids are int64: first_row(g) + local node + id_base.
@@ -542,10 +594,62 @@ public:
         check(hnsw_sharded_brute_force_batch(s_, batch.data, batch.dim2, batch.dim1, k, fill, ids.data(), dist.data()));
         return {std::move(ids), std::move(dist)};
     }
+    // hnsw_sharded_search_batch_filtered: the first k under (distance, global id) of the shards' own filtered rows; stage[q] = the
+    // maximum over the shards (exact_stage as soon as one shard answered q from its exact scan)
+    struct Filtered {
+        static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
+        std::vector<int64_t> ids; std::vector<float> dist; std::vector<uint32_t> stage;
+    };
+    Filtered knn_filtered(const ShardedFilter &f, const Mat &batch, int ef, int k, int fill = HNSW_FILL_OHNSW, int sem = HNSW_SEM_OHNSW) const {
+        const size_t nq = (size_t)batch.dim2, kk = (size_t)(k > 0 ? k : 0);
+        Filtered out{std::vector<int64_t>(nq * kk, -1), std::vector<float>(nq * kk, 0.f), std::vector<uint32_t>(nq, 0u)};
+        hnsw_search_params p{ef, k, fill, sem};
+        check(hnsw_sharded_search_batch_filtered(s_, f.handle(), batch.data, batch.dim2, batch.dim1, &p, out.ids.data(), out.dist.data(), nullptr,
+                                                 nullptr, out.stage.data()));
+        return out;
+    }
+    // hnsw_sharded_range_search_batch / hnsw_sharded_range_brute_force_batch: per query the union of the shards' own segments under
+    // (distance, global id); f (optional): under the shards' parts of a ShardedFilter
+    ShardedRangeResult range_search(float radius, const Mat &batch, int ef = 64, int sem = HNSW_SEM_OHNSW, const ShardedFilter *f = nullptr) const {
+        hnsw_range_params p{radius, ef, sem};
+        hnsw_sharded_range_result *r = nullptr;
+        check(hnsw_sharded_range_search_batch(s_, f ? f->handle() : nullptr, batch.data, batch.dim2, batch.dim1, &p, &r));
+        return ShardedRangeResult(r);
+    }
+    ShardedRangeResult brute_force_range(float radius, const Mat &batch, const ShardedFilter *f = nullptr) const {
+        hnsw_sharded_range_result *r = nullptr;
+        check(hnsw_sharded_range_brute_force_batch(s_, f ? f->handle() : nullptr, batch.data, batch.dim2, batch.dim1, radius, &r));
+        return ShardedRangeResult(r);
+    }
 private:
     Sharded() = default;
     hnsw_sharded *s_ = nullptr;
 };
+
+inline ShardedFilter::ShardedFilter(const Sharded &s, const std::vector<bool> &allow) {
+    std::vector<uint32_t> bits((allow.size() + 31) / 32 + 1, 0u);
+    for (size_t v = 0; v < allow.size(); ++v) if (allow[v]) bits[v >> 5] |= 1u << (v & 31);
+    check(hnsw_sharded_filter_create(s.handle(), bits.data(), (int64_t)allow.size(), &f_));
+}
+
+// hnsw_merge_segments: n_lists range results over the same queries (lims[g]: nq + 1 entries from 0; ids[g] / dist[g]: lims[g][nq]
+// entries, each segment ascending under (distance, id)) merged per query under (distance, first_row[list] + id); the same global id
+// in two lists: the lower list first
+inline ShardedRangeResult merge_segments(const std::vector<std::vector<int64_t>> &lims, const std::vector<std::vector<int32_t>> &ids,
+                                         const std::vector<std::vector<float>> &dist, const std::vector<int64_t> &first_row, int id_base = 0,
+                                         int device = 0) {
+    const size_t n = lims.size();
+    if (ids.size() != n || dist.size() != n || first_row.size() != n) throw std::invalid_argument("merge_segments: one lims, ids, dist and first_row per list");
+    std::vector<const int64_t *> pl; std::vector<const int32_t *> pi; std::vector<const float *> pd;
+    for (size_t g = 0; g < n; ++g) {
+        if (lims[g].empty() || lims[g].size() != lims[0].size() || ids[g].size() != (size_t)lims[g].back() || dist[g].size() != ids[g].size())
+            throw std::invalid_argument("merge_segments: lims[g] has nq + 1 entries, ids[g] and dist[g] lims[g][nq]");
+        pl.push_back(lims[g].data()); pi.push_back(ids[g].data()); pd.push_back(dist[g].data());
+    }
+    hnsw_sharded_range_result *r = nullptr;
+    check(hnsw_merge_segments(device, (int32_t)n, n ? (int64_t)lims[0].size() - 1 : 0, pl.data(), pi.data(), pd.data(), first_row.data(), id_base, &r));
+    return ShardedRangeResult(r);
+}
 
 // hnsw_merge_lists: n_lists result lists per query (ids / dist [n_lists][nq][k_in], each ascending under (distance, id), padding
 // below id_base at the end) merged under (distance, first_row[list] + id) into ids (int64) and distances [nq][k_out]

@@ -1296,3 +1296,158 @@ let merge_lists ?(device = 0) ?(id_base = 0) ~(first_row : int array) ~k_in ~k_o
            (Int64.of_int nq) (Int32.of_int k_in) (Int32.of_int k_out) (Int32.of_int id_base) 0l (CArray.start out_ids)
            (CArray.start out_dist));
   sharded_rows nq k_out out_ids out_dist
+
+(* ---- sharded index: a filter over the global rows, filtered search, range search (see the C header).  Not bound for a sharded
+   index, because the library does not build them: filters from labels and one filter per query. *)
+type sharded_filter_handle = unit ptr
+let sharded_filter_handle : sharded_filter_handle typ = ptr void
+type sharded_range_handle = unit ptr
+let sharded_range_handle : sharded_range_handle typ = ptr void
+let hnsw_sharded_filter_create =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_filter_create"
+    (sharded_handle @-> ptr uint32_t @-> int64_t @-> ptr sharded_filter_handle @-> returning int32_t)
+let hnsw_sharded_filter_destroy = foreign ~from:lib "hnsw_sharded_filter_destroy" (sharded_filter_handle @-> returning int32_t)
+let hnsw_sharded_filter_count =
+  foreign ~from:lib "hnsw_sharded_filter_count" (sharded_filter_handle @-> ptr int64_t @-> returning int32_t)
+let hnsw_sharded_filter_part =
+  foreign ~from:lib "hnsw_sharded_filter_part" (sharded_filter_handle @-> int32_t @-> ptr filter_handle @-> returning int32_t)
+let hnsw_sharded_search_batch_filtered =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_search_batch_filtered"
+    (sharded_handle @-> sharded_filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> ptr int64_t
+     @-> ptr float @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+let hnsw_sharded_range_search_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_range_search_batch"
+    (sharded_handle @-> sharded_filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr range_params
+     @-> ptr sharded_range_handle @-> returning int32_t)
+let hnsw_sharded_range_brute_force_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_range_brute_force_batch"
+    (sharded_handle @-> sharded_filter_handle @-> ptr float @-> int64_t @-> int64_t @-> float @-> ptr sharded_range_handle
+     @-> returning int32_t)
+let hnsw_sharded_range_result_size =
+  foreign ~from:lib "hnsw_sharded_range_result_size" (sharded_range_handle @-> ptr int64_t @-> ptr int64_t @-> returning int32_t)
+let hnsw_sharded_range_result_fetch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_sharded_range_result_fetch"
+    (sharded_range_handle @-> ptr int64_t @-> ptr int64_t @-> ptr float @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t
+     @-> returning int32_t)
+let hnsw_sharded_range_result_device =
+  foreign ~from:lib "hnsw_sharded_range_result_device"
+    (sharded_range_handle @-> ptr (ptr int64_t) @-> ptr (ptr int64_t) @-> ptr (ptr float) @-> returning int32_t)
+let hnsw_sharded_range_result_destroy =
+  foreign ~from:lib "hnsw_sharded_range_result_destroy" (sharded_range_handle @-> returning int32_t)
+let hnsw_merge_segments =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_merge_segments"
+    (int32_t @-> int32_t @-> int64_t @-> ptr (ptr int64_t) @-> ptr (ptr int32_t) @-> ptr (ptr float) @-> ptr int64_t @-> int32_t
+     @-> ptr sharded_range_handle @-> returning int32_t)
+
+(* A mask over the GLOBAL rows of a sharded index (hnsw_sharded_filter_create): allow.(v) = global row v may be returned; one entry
+   per row of the whole table.  The library cuts it into one filter per shard.  The filter keeps its index alive. *)
+type sharded_filter = { sf_handle : sharded_filter_handle; sf_index : sharded }
+
+let sharded_filter_create (s : sharded) (allow : bool array) : sharded_filter =
+  let n = Array.length allow in
+  let words = (n + 31) / 32 in
+  let bits = CArray.make uint32_t ~initial:Unsigned.UInt32.zero (max 1 words) in
+  Array.iteri (fun v a ->
+      if a then CArray.set bits (v lsr 5) (Unsigned.UInt32.logor (CArray.get bits (v lsr 5)) (Unsigned.UInt32.shift_left Unsigned.UInt32.one (v land 31))))
+    allow;
+  let out = allocate sharded_filter_handle null in
+  check (hnsw_sharded_filter_create s.s_handle (CArray.start bits) (Int64.of_int n) out);
+  let f = { sf_handle = !@out; sf_index = s } in
+  Gc.finalise (fun f -> ignore (hnsw_sharded_filter_destroy f.sf_handle)) f;
+  f
+
+(* the allowed rows, summed over the shards *)
+let sharded_filter_count (f : sharded_filter) : int =
+  let c = allocate int64_t 0L in
+  check (hnsw_sharded_filter_count f.sf_handle c);
+  Int64.to_int !@c
+
+let stage_of s = let s = Unsigned.UInt32.to_int s in if s = 0xFFFFFFFF then -1 else s
+
+(* hnsw_sharded_search_batch_filtered: the first k under (distance, global id) of the shards' own [knn_batch_filtered] rows.
+   -> (global ids, distances, stages); stages.(q) = the maximum over the shards, -1 as soon as one shard took its exact scan. *)
+let sharded_knn_batch_filtered ?(semantics = 0) ?(fill = 0) (f : sharded_filter) (batch : Lacaml.S.mat) ~ef ~k :
+  int array array * float array array * int array =
+  let s = f.sf_index in
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int64_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let stage = CArray.make uint32_t (max 1 nq) in
+  let p = make search_params in
+  setf p p_ef (Int32.of_int ef); setf p p_k (Int32.of_int k); setf p p_fill (Int32.of_int fill);
+  setf p p_semantics (Int32.of_int semantics);
+  check (hnsw_sharded_search_batch_filtered s.s_handle f.sf_handle (bigarray_start array2 batch) (Int64.of_int nq)
+           (Int64.of_int s.s_dim) (addr p) (CArray.start ids) (CArray.start dist) (from_voidp uint32_t null)
+           (from_voidp uint32_t null) (CArray.start stage));
+  let rows, dists = sharded_rows nq k ids dist in
+  (rows, dists, Array.init nq (fun q -> stage_of (CArray.get stage q)))
+
+(* a sharded range result fetched whole and freed: per query its (global id, distance) pairs, ascending under (distance, global
+   id), and its stage (the maximum over the shards, -1 = an exact scan) *)
+let fetch_sharded_range (r : sharded_range_handle) : (int * float) array array * int array =
+  Fun.protect ~finally:(fun () -> ignore (hnsw_sharded_range_result_destroy r)) (fun () ->
+      let nq = allocate int64_t 0L and total = allocate int64_t 0L in
+      check (hnsw_sharded_range_result_size r nq total);
+      let nq = Int64.to_int !@nq and total = Int64.to_int !@total in
+      let lims = CArray.make int64_t (nq + 1) in
+      let ids = CArray.make int64_t (max 1 total) and dist = CArray.make float (max 1 total) in
+      let stage = CArray.make uint32_t (max 1 nq) in
+      check (hnsw_sharded_range_result_fetch r (CArray.start lims) (CArray.start ids) (CArray.start dist) (from_voidp uint32_t null)
+               (from_voidp uint32_t null) (CArray.start stage));
+      (Array.init nq (fun q ->
+           let a = Int64.to_int (CArray.get lims q) and b = Int64.to_int (CArray.get lims (q + 1)) in
+           Array.init (b - a) (fun j -> (Int64.to_int (CArray.get ids (a + j)), CArray.get dist (a + j)))),
+       Array.init nq (fun q -> stage_of (CArray.get stage q))))
+
+let sharded_filter_arg = function None -> null | Some (f : sharded_filter) -> f.sf_handle
+
+(* hnsw_sharded_range_search_batch: per query the union of the shards' own [range_search] segments; ?filter: under the shards'
+   parts of a sharded filter *)
+let sharded_range_search ?(semantics = 0) ?(filter : sharded_filter option) (s : sharded) (batch : Lacaml.S.mat) ~radius ~ef
+  : (int * float) array array * int array =
+  let nq = A2.dim2 batch in
+  let p = make range_params in
+  setf p r_radius radius; setf p r_ef (Int32.of_int ef); setf p r_semantics (Int32.of_int semantics);
+  let out = allocate sharded_range_handle null in
+  check (hnsw_sharded_range_search_batch s.s_handle (sharded_filter_arg filter) (bigarray_start array2 batch) (Int64.of_int nq)
+           (Int64.of_int s.s_dim) (addr p) out);
+  ignore (Sys.opaque_identity filter);      (* (alive until the call has returned) *)
+  fetch_sharded_range !@out
+
+(* hnsw_sharded_range_brute_force_batch: the exact form, the set [brute_force_range] gives over one index of all rows *)
+let sharded_brute_force_range ?(filter : sharded_filter option) (s : sharded) (batch : Lacaml.S.mat) ~radius
+  : (int * float) array array * int array =
+  let nq = A2.dim2 batch in
+  let out = allocate sharded_range_handle null in
+  check (hnsw_sharded_range_brute_force_batch s.s_handle (sharded_filter_arg filter) (bigarray_start array2 batch) (Int64.of_int nq)
+           (Int64.of_int s.s_dim) radius out);
+  ignore (Sys.opaque_identity filter);
+  fetch_sharded_range !@out
+
+(* hnsw_merge_segments: lists.(g).(q) = list g's whole segment for query q as (id, distance) pairs, ascending under (distance,
+   id); first_row.(g) = the global row of list g's local node 0 (non-decreasing).  -> per query the union of its segments under
+   (distance, first_row.(g) + id); the same global id in two lists: the lower list first. *)
+let merge_segments ?(device = 0) ?(id_base = 0) ~(first_row : int array) (lists : (int * float) array array array)
+  : (int * float) array array =
+  let n_lists = Array.length lists in
+  if n_lists <> Array.length first_row then invalid_arg "merge_segments: one first_row per list";
+  let nq = if n_lists = 0 then 0 else Array.length lists.(0) in
+  let per_list = Array.map (fun per_query ->
+      if Array.length per_query <> nq then invalid_arg "merge_segments: every list answers the same queries";
+      let total = Array.fold_left (fun a row -> a + Array.length row) 0 per_query in
+      let lims = CArray.make int64_t ~initial:0L (nq + 1) in
+      let ids = CArray.make int32_t (max 1 total) and dist = CArray.make float (max 1 total) in
+      let at = ref 0 in
+      Array.iteri (fun q row ->
+          Array.iter (fun (v, d) -> CArray.set ids !at (Int32.of_int v); CArray.set dist !at d; incr at) row;
+          CArray.set lims (q + 1) (Int64.of_int !at)) per_query;
+      (lims, ids, dist)) lists in
+  let pl = CArray.make (ptr int64_t) (max 1 n_lists) and pi = CArray.make (ptr int32_t) (max 1 n_lists)
+  and pd = CArray.make (ptr float) (max 1 n_lists) in
+  Array.iteri (fun g (l, i, d) -> CArray.set pl g (CArray.start l); CArray.set pi g (CArray.start i); CArray.set pd g (CArray.start d))
+    per_list;
+  let first = CArray.of_list int64_t (List.map Int64.of_int (Array.to_list first_row)) in
+  let out = allocate sharded_range_handle null in
+  check (hnsw_merge_segments (Int32.of_int device) (Int32.of_int n_lists) (Int64.of_int nq) (CArray.start pl) (CArray.start pi)
+           (CArray.start pd) (CArray.start first) (Int32.of_int id_base) out);
+  ignore (Sys.opaque_identity per_list);    (* (alive until the call has returned) *)
+  fst (fetch_sharded_range !@out)
