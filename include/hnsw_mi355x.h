@@ -308,6 +308,21 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   hnsw_index_sq8_params / hnsw_index_sq8_codes give lo, s and the codes.  A scale per dimension would need a
  *                   weighted distance in a kernel family of its own: not built.  Rate and recall: not measured yet
  *                   (tools/sq8_rate.py prints the table for profiles/sq8_rows.txt).
+ *   "filter_collect" 0 = off (default: every result, counter and code path is exactly as without the option); 1 = the filtered
+ *                   searches answer from EVERY node the layer-0 walk evaluates, not from the final W only: a walk at ef 128
+ *                   evaluates about 950 to 2400 nodes and keeps 128, and each evaluated node has an exact distance.  The
+ *                   definition is the paragraph WITH OPTION filter_collect of the filtered search below.  Any other value is
+ *                   HNSW_ERR_BAD_ARG.  It changes answers only for queries the ladder would otherwise walk again (and, at stage 0,
+ *                   a tie at the k-th place): there it trades recall for not re-walking, which is why it is opt-in.
+ *                   k <= 128 only: for k > 128 the option has no effect and the ladder over W answers.
+ *                   EXCLUSIONS: exact-row formats only (float32, byte and split rows).  HNSW_ERR_BAD_ARG, the index unchanged,
+ *                   when it is set to 1 while option "half_rows" or "sq8_rows" is on, and when "half_rows" or "sq8_rows" is
+ *                   set to 1 while it is 1.  Not saved: a loaded index starts with it off.  hnsw_index_insert and
+ *                   hnsw_index_remove keep the setting.  Range search is not affected.  RATE AND RECALL (one MI355X, 1 M x 128 byte
+ *                   rows, ef 128, k 10, 10 k queries; tools/filter_rate.py --collect, profiles/filter_collect.txt), on against off:
+ *                   selectivity 0.01: 8.2 ms per batch against 45.9, recall@10 0.787 against 0.998; 0.1: 8.2 against 8.9, recall
+ *                   0.920 against 0.935; 1 and 0.5: 2-8 % slower with the same rows (the collect kernel runs the C++ hop loop);
+ *                   0.001: 5 % slower (the exact scan answers either way); a marked index: 2-8 % slower, the same rows.
  * and one that gives the half-row searches float32 answers again (off by default):
  *   "refine"        0 = off (default: behaviour is exactly as without the option); R in 1..1024 = a candidate count; -1 = all
  *                   of W; anything else is HNSW_ERR_BAD_ARG.  While the knn searches read the half rows, a search of (ef, k)
@@ -520,6 +535,25 @@ int32_t hnsw_rerank_batch_device(hnsw_index *idx, const float *d_queries, int64_
  *      hnsw_host_register are read and written in place, others are copied, as by the other host forms; complete on return.
  *   6. DETERMINISM.  A query's answer depends on its own vector, the mask and (ef, k, semantics) only: not on the batch it is in,
  *      and not on which stage other queries reached.
+ * WITH OPTION filter_collect (hnsw_index_set_option(idx, "filter_collect", 1); k <= 128, float32 / byte / split rows).  For the walk
+ * of (ef = e, the caller's semantics) for query q let X_e(q) be the nodes the layer-0 loop expands, and
+ *      E_e(q) = {the layer-0 entry node} united with adj0(c) for every c in X_e(q):
+ * THE EVALUATED SET, every node whose distance the layer-0 search evaluates.  It is a set: it does not depend on what the visited
+ * cache forgets, nor on option "visited_blocks".  Upper-layer evaluations are not collected.  R_e(q) is the first min(k, .) allowed
+ * members of E_e(q) under the order of hnsw_brute_force_batch: the ordered distance key (pre-square-root for L2), then the node
+ * id; distances are the bits of hnsw_distance_batch.  The ladder is unchanged (e_0 = ef, e_{j+1} = min(1024, 2 * e_j), the short
+ * queries compacted and walked as one batch per stage); only THE STAGE TEST changes: a query is served at the first stage where
+ * |R_e(q)| >= k, and its answer is R_e(q).  A query still short at 1024 goes to the unchanged exact stage, and a query whose filter
+ * allows fewer than k nodes takes no walk and goes there at once.  out_stage, out_nhops and out_ndist mean what they mean above
+ * (the sum over the walks taken, plus n_allowed for the exact stage); nothing is re-ranked; the walk itself is the unchanged walk:
+ * for a query served at stage j its hop count at that stage is hnsw_search_batch's for (e_j, e_j).  CONSEQUENCES: a query that
+ * point 1 serves at stage 0 gets the same row with the option, because every evaluated node outside the final W is at least as
+ * far as max(W) -- except where such a node is tied with max(W) at the k-th place, where (key, id) decides --; point 6
+ * (DETERMINISM) holds unchanged.  SCOPE: hnsw_search_batch_filtered and hnsw_search_batch_filtered_each; the plain calls that run
+ * under marks (hnsw_search_batch and hnsw_knn while n_deleted > 0 remain bit for bit the filtered call under LIVE, now with the
+ * same option); through hnsw_sharded_set_option the sharded filtered call, whose definition in terms of the shard handles' own
+ * rows is unchanged.  Range search is not affected.  For k > 128 the option has no effect (R lives in two key registers) and
+ * points 1 - 6 answer.  Exact-row formats only and not saved with the index: see the option list of hnsw_index_set_option.
  * Scratch (a stage's W, the short list, the gathered queries) belongs to the handle, is sized on demand and not counted in
  * device_bytes: ONE filtered call in flight per handle, and no range call beside it (the short list and the gathered queries are
  * shared between the filtered and the range calls).  There is no device-pointer form: the ladder needs the number of short

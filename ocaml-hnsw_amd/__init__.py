@@ -455,7 +455,9 @@ class Hgraph:
         return inf
 
     def set_option(self, name, value):
-        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "refine", ...)"""
+        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "refine", ...).
+        "filter_collect" 1 makes the filtered searches (knn_batch_filtered, knn_batch_filtered_each, the plain searches under
+        marks) answer from every node the layer-0 walk evaluates, not from the final W only (k <= 128, exact rows; default 0)"""
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
 
     def row_bytes(self):

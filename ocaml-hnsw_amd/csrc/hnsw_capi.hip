@@ -187,6 +187,15 @@ typedef int (*search_occupancy_fn)(int, int, size_t, int);
 const struct { int metric, semf, rows; search_launch_fn launch; search_occupancy_fn occupancy; } k_variants[] = {HNSW_SEARCH_VARIANTS(HNSW_V_ENTRY)};
 #undef HNSW_V_DECLARE
 #undef HNSW_V_ENTRY
+// ... and the collect kernel's (option "filter_collect") in hnsw_collect_variants.hip, by the same triples
+#define HNSW_C_DECLARE(m, s, f) \
+    hipError_t collect_launch_##m##_##s##_##f(int nch, int nslot, const IndexView &iv, const SearchArgs &a, const hnsw_dev::CollectArgs &c, hipStream_t st);
+#define HNSW_C_ENTRY(m, s, f) {m, s, f, collect_launch_##m##_##s##_##f},
+HNSW_COLLECT_VARIANTS(HNSW_C_DECLARE)
+typedef hipError_t (*collect_launch_fn)(int, int, const IndexView &, const SearchArgs &, const hnsw_dev::CollectArgs &, hipStream_t);
+const struct { int metric, semf, rows; collect_launch_fn launch; } k_collect_variants[] = {HNSW_COLLECT_VARIANTS(HNSW_C_ENTRY)};
+#undef HNSW_C_DECLARE
+#undef HNSW_C_ENTRY
 
 // the knn kernel's row format: 2 = byte rows (hnsw_rows8.hip) and the sq8 codes (hnsw_rows_sq8.hip: the same kernels), 3 = split
 // fp32 rows (hnsw_rows_split.hip), 4 = half rows (hnsw_rows16.hip), else plain fp32 rows, 1 = every chunk of the lane grid inside
@@ -207,6 +216,7 @@ struct KnnShape {
     int ef, semf, nch, nslot, slot_class;
     search_launch_fn launch;
     search_occupancy_fn occupancy;
+    collect_launch_fn collect;           // the collect kernel of the same shape; null: the row format has none (half, sq8)
     // waves of the kernel (blk: of its bitmap-block twin) one CU holds when each asks for `lds` bytes, 0 = unknown
     int waves_per_cu(size_t lds, bool blk = false) const { return occupancy(nch, nslot, lds, blk); }
     hnsw_index::ShapeChoice &choice(hnsw_index *idx) const { return idx->shape[slot_class][semf]; }
@@ -218,6 +228,8 @@ KnnShape knn_shape(const hnsw_index *idx, int ef, int semantics) {
     const int metric = idx->info.metric == HNSW_METRIC_L2 ? 0 : 1, rows = variant_full(idx);
     for (const auto &v : k_variants)
         if (v.metric == metric && v.semf == sh.semf && v.rows == rows) { sh.launch = v.launch; sh.occupancy = v.occupancy; }
+    for (const auto &v : k_collect_variants)
+        if (v.metric == metric && v.semf == sh.semf && v.rows == rows) sh.collect = v.launch;
     return sh;
 }
 
@@ -255,8 +267,11 @@ int knn_vt_bits(hnsw_index *idx, const KnnShape &sh) {
     return grown = b;
 }
 
-int launch_search_args(hnsw_index *idx, const KnnShape &sh, const SearchArgs &a, hipStream_t st) {
-    hipError_t e = sh.launch(sh.nch, sh.nslot, idx->iv, a, st);
+// collect: the collect kernel of the shape instead (a shape without one is an error, never the plain kernel)
+int launch_search_args(hnsw_index *idx, const KnnShape &sh, const SearchArgs &a, hipStream_t st, const hnsw_dev::CollectArgs *collect = nullptr) {
+    if (collect && (!sh.collect || a.k > 128))
+        return fail(HNSW_ERR_UNSUPPORTED, "no collect kernel for row format %d, k=%d", idx->info.row_format, a.k);
+    hipError_t e = collect ? sh.collect(sh.nch, sh.nslot, idx->iv, a, *collect, st) : sh.launch(sh.nch, sh.nslot, idx->iv, a, st);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "search kernel launch failed: %s", hipGetErrorString(e));
     return HNSW_OK;
 }
@@ -521,18 +536,19 @@ int check_batch(const hnsw_index *idx, const hnsw_search_params *p, int64_t nq, 
 // launch's and nothing of an ordered one: the pre-pass's entries and key, the LDS padding and the priorities describe the order
 // of all nq queries in the first launch, not of this list.
 int launch_rerun(hnsw_index *idx, const hnsw_search_params &p, const KnnBatch &b, const int32_t *qmap, int64_t c, uint32_t *slab,
-                 int32_t cap, hipStream_t st) {
+                 int32_t cap, hipStream_t st, const hnsw_dev::CollectArgs *collect = nullptr) {
     const KnnShape sh = knn_shape(idx, p.ef, p.semantics);
     SearchArgs a = knn_args(p, b, knn_vt_bits(idx, sh), knn_blk_bits(idx, sh));
     a.nq = c; a.qmap = qmap; a.q_limit = b.nq; a.ovf_g = slab; a.ovf_gcap = cap;
     a.any_flag = nullptr;                   // (the host has read the word already; a re-run query cannot overflow)
-    return launch_search_args(idx, sh, a, st);
+    return launch_search_args(idx, sh, a, st, collect);
 }
 
 int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const KnnBatch &caller_b, hipStream_t st, float *d_stage,
-               RefineBufs *walk, bool raw_walk) {
+               RefineBufs *walk, bool raw_walk, const hnsw_dev::CollectArgs *collect) {
     int rc = check_batch(idx, caller_params, caller_b.nq, caller_b.q_stride, caller_b.Q && caller_b.ids && caller_b.dist);
     if (rc || caller_b.nq == 0) return rc;
+    if (collect && !raw_walk) return fail(HNSW_ERR_BAD_ARG, "a collect walk is a raw walk");
     HIP_TRY(hipSetDevice(idx->device));
     // refine active: everything below is today's search with k := c into the walk's scratch; the re-rank at the end answers the caller
     const int refine_c = raw_walk ? 0 : refine_count(idx, caller_params);
@@ -578,7 +594,7 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
         launch_priorities(idx, sh, b.nq, a);
     }
     if (ev) HIP_TRY(hipEventRecord(ev[1], st));
-    rc = launch_search_args(idx, sh, a, st);
+    rc = launch_search_args(idx, sh, a, st, collect);
     if (!rc && idx->fb_queries > 0 && b.st && !b.any_flag) {
         // opt-in exact mode of the device-pointer entry point (option "device_fallback_slab_bytes"): the queries the launch
         // flagged are listed on the device and searched again with the slab, on the caller's stream, no host round trip.
@@ -591,7 +607,7 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
         read.Q = a.Q;                       // the queries as the search read them (the staged copy when there is one)
         // (at most min(cap, nq) queries can be listed: no more blocks than that; the blocks past the count leave at once)
         rc = launch_rerun(idx, *params, read, (const int32_t *)idx->dFbMap.p, std::min<int64_t>(cap, b.nq), (uint32_t *)idx->dFbSlab.p,
-                          (int32_t)std::min<int64_t>(idx->iv.n, 0x7FFFFFFF), st);
+                          (int32_t)std::min<int64_t>(idx->iv.n, 0x7FFFFFFF), st, collect);
     }
     if (!rc && refine_c > 0) {              // (behind the device fallback; reads the queries as the search read them, sq8: the caller's)
         KnnBatch to = caller_b;
@@ -607,7 +623,8 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
     return rc;
 }
 
-int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk, bool raw_walk) {
+int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk, bool raw_walk,
+               const hnsw_dev::CollectArgs *collect) {
     const int refine_c = raw_walk ? 0 : refine_count(idx, p);
     hnsw_search_params wp = *p;
     KnnBatch wb = b;
@@ -623,7 +640,7 @@ int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, 
         if (rc) return rc;
     }
     const int rc = rerun_overflowed(idx, b.nq, b.st, [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
-        return launch_rerun(idx, wp, wb, qmap, c, slab, cap, st);
+        return launch_rerun(idx, wp, wb, qmap, c, slab, cap, st, collect);
     });
     if (rc || refine_c == 0) return rc;
     // every query again (the same answer for those not repaired), and complete on return as the re-run is: callers go on to
@@ -1030,6 +1047,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
                 return fail(HNSW_ERR_BAD_ARG, "half_rows: the index searches its byte rows, which are exact and half the size of half rows "
                                               "(set byte_rows 0 first)");
             if (idx->sq8_on) return fail(HNSW_ERR_BAD_ARG, "half_rows: option sq8_rows is on (set sq8_rows 0 first)");
+            if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "half_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
             if (!idx->tables.Xh.p) {
                 const int rc = make_half_rows(idx);     // (a refusal -- NaN, fp16 overflow -- leaves the index as it was)
                 if (rc) return rc;
@@ -1052,6 +1070,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
             if (idx->info.row_format == HNSW_ROWS_BYTES)
                 return fail(HNSW_ERR_BAD_ARG, "sq8_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)");
             if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option half_rows is on (set half_rows 0 first)");
+            if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
             if (!idx->tables.Xq.p) {
                 const int rc = make_sq8_rows(idx);      // (a refusal -- NaN, infinity, range overflow -- leaves the index as it was)
                 if (rc) return rc;
@@ -1072,6 +1091,14 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     if (!strcmp(name, "refine")) {        // 0: off; 1..1024: re-rank max(k, value) members of W over the float32 rows; -1: all ef (half and sq8 rows only)
         if (value < -1 || value > 1024) return fail(HNSW_ERR_BAD_ARG, "refine=%lld: 0 (off), 1..1024 candidates or -1 (all of W)", (long long)value);
         idx->refine = (int)value;
+        return HNSW_OK;
+    }
+    if (!strcmp(name, "filter_collect")) {   // 1: the filtered searches answer from every node the walk evaluates (k <= 128, exact rows); 0: from the final W
+        if (value != 0 && value != 1) return fail(HNSW_ERR_BAD_ARG, "filter_collect=%lld: 0 (off) or 1", (long long)value);
+        if (value == 1 && (idx->half_rows_on || idx->sq8_on))     // (on, even while byte rows stand in front of them: "byte_rows" 0 would bring them back)
+            return fail(HNSW_ERR_BAD_ARG, "filter_collect: option %s is on, and a walk over those rows has no exact distances (set it 0 first)",
+                        idx->sq8_on ? "sq8_rows" : "half_rows");
+        idx->filter_collect = value == 1;
         return HNSW_OK;
     }
     if (!strcmp(name, "time_kernels")) { idx->time_kernels = value != 0; return HNSW_OK; }
@@ -1112,7 +1139,7 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
         {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
         {"sq8_rows", idx->sq8_on ? 1 : 0}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
-        {"order_queries", idx->order_mode}, {"scan_slabs", idx->scan_slabs}};
+        {"order_queries", idx->order_mode}, {"scan_slabs", idx->scan_slabs}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }

@@ -425,7 +425,9 @@ __device__ __forceinline__ void tie_mark_expanded(const OvfStore &ov, int pos, i
 // (Measured alternative, same results: deciding "my key is above K" per lane and selecting
 // mine / left neighbour / K without any scalar rank -- fewer scalar hand-offs but more vector
 // instructions; 4 % slower on an idle chip, 3 % on the 10 k batch.)
-template <int NSLOT, int SEM = 0>
+// TIES false: the list is a plain sorted set (the collect kernel's R): what falls off is gone, the tie list is not touched, and
+// (kd, kid) only has to be below the list's last KEY (an equal distance with a smaller id is fine).
+template <int NSLOT, int SEM = 0, bool TIES = true>
 __device__ __forceinline__ void wlist_insert(WList<NSLOT> &w, uint32_t kd, uint32_t kid, int lane,
                                              const OvfStore &ov, uint32_t &status) {
     const uint32_t klo = (kid + 1u) << 1;
@@ -481,7 +483,9 @@ __device__ __forceinline__ void wlist_insert(WList<NSLOT> &w, uint32_t kd, uint3
         }
     }
     w.wmax = rdlane(w.hi[NSLOT - 1], 63);
-    if (ev_hi != w.wmax) {
+    if constexpr (!TIES) {
+        (void)ev_lo;
+    } else if (ev_hi != w.wmax) {
         w.ovf_cnt = 0;                            // max(W).d dropped: every listed entry is dead
     } else if (ev_hi == DUMMY_HI) {               // W still holds dummies: nothing real fell off
     } else if (SEM != 0) {                        // evicted while tied with the new max(W): stays in C, and visited
@@ -1070,15 +1074,87 @@ __device__ __forceinline__ void accept_candidates(WList<NSLOT> &w, const WaveCtx
     }
 }
 
-// The rounds of one hop from candidate `base0` of the hop's list on.
-template <int NCH, int RB, int NSLOT, int METRIC, int SEM, int ROWS>
+// ---- option "filter_collect": the k nearest ALLOWED nodes among ALL the layer-0 search evaluates ----------------------------
+// The walk throws away all it evaluates but the ef members of W; every one of those nodes has an exact distance.  The collect
+// kernel carries a second list R beside W: the k smallest (key, id) among the allowed nodes of the evaluated set (the layer-0
+// entry node and every candidate of every round), a plain sorted SET in two key registers (k <= 128).  R never feeds back into
+// the walk.  A node the visited cache forgot is evaluated and offered again: wlist_insert ignores a node that is present, and one
+// that is absent was beaten by k others for good (R's last key never grows).
+
+// A mask's words as a kernel reads them once it has taken the mask's address out of a table of masks: a pointer loaded from memory
+// is a generic one to the compiler (flat loads, no scalar loads); every mask lies in device memory, and saying so keeps the loads
+// what they were when the mask was a kernel argument.
+using MaskWords = const __attribute__((address_space(1))) uint32_t *;
+__device__ __forceinline__ MaskWords mask_words(const uint32_t *p) { return (MaskWords)p; }
+
+// what the collect kernel takes beside SearchArgs: row q of the launch's batch (after SearchArgs::qmap) belongs to the caller's
+// query map[q] (null: q), which is answered under masks[which[that query]] (which null: masks[0])
+struct CollectArgs {
+    const uint32_t *const *masks;
+    const int32_t *which;
+    const int32_t *map;
+};
+struct Collect {
+    WList<2> r;
+    MaskWords bits;
+};
+// (kd, kid) -- wave-uniform -- joins R if it is below R's last key under (key, id)
+__device__ __forceinline__ void collect_offer(Collect &col, const WaveCtx &cx, uint32_t kd, uint32_t kid) {
+    const uint32_t klo = (kid + 1u) << 1;
+    if (kd < col.r.wmax || (kd == col.r.wmax && klo < rdlane(col.r.lo[1], 63))) {
+        uint32_t unused = 0;
+        wlist_insert<2, 0, false>(col.r, kd, kid, cx.lane, cx.ovf, unused);
+    }
+}
+// the place within its round (0 = the round's first candidate) of the candidate whose key hop_round leaves in this lane -- lane
+// 16 r + b holds candidate NB r + b; the integer path of the byte rows spreads a group's NB candidates over its 16 lanes --, for a
+// round that eval_round answered with `consumed`.  Lanes that hold no candidate get some number.
+template <int NCH, int ROWS>
+__device__ __forceinline__ int round_place(const WaveCtx &cx, int consumed) {
+    const int nb = consumed >> 2;
+    if constexpr (ROWS == 2 && NCH <= 4) {
+        if (cx.qint) return nb * cx.r + (cx.l16 >> (nb == 1 ? 4 : nb == 2 ? 3 : nb <= 4 ? 2 : 1));
+    }
+    return nb * cx.r + cx.l16;
+}
+// the mask word of the candidate lane j of a round starting at `base` answers for (candidate base + j; lanes past the hop's list
+// read the last candidate's): requested before the round's rows, so that it shares their flight
+__device__ __forceinline__ uint32_t collect_mask_word(const Collect &col, const WaveCtx &cx, int base, int cnt, uint32_t &id) {
+    const int ci = base + cx.lane < cnt ? base + cx.lane : cnt - 1;
+    id = (uint32_t)cx.cand_id[ci];
+    return col.bits[id >> 5];
+}
+// a round's candidates (ckey / cid as eval_round left them) offered to R: the allowed ones not beyond R's last key, in ascending lane order
+template <int NCH, int ROWS>
+__device__ __forceinline__ void collect_round(Collect &col, const WaveCtx &cx, uint32_t mword, uint32_t mid, int base, int cnt,
+                                              int consumed, uint32_t ckey, uint32_t cid) {
+    const uint64_t allow = ballot(base + cx.lane < cnt && ((mword >> (mid & 31u)) & 1u));   // bit j: the round's j-th candidate is allowed
+    const int place = round_place<NCH, ROWS>(cx, consumed) & 63;
+    uint64_t pass = ballot(ckey <= col.r.wmax && ((allow >> place) & 1ull));                 // (KEY_INF, a lane without a candidate, is above every wmax)
+    while (pass) {
+        const int i = __builtin_ctzll(pass);
+        pass &= pass - 1;
+        collect_offer(col, cx, rdlane(ckey, i), rdlane(cid, i));
+    }
+}
+
+// The rounds of one hop from candidate `base0` of the hop's list on.  COLLECT: every round's candidates are also offered to col->r.
+template <int NCH, int RB, int NSLOT, int METRIC, int SEM, int ROWS, bool COLLECT = false>
 __device__ __forceinline__ void hop_eval(const IndexView &iv, const float4 (&qv)[NCH], WList<NSLOT> &w,
                                          const WaveCtx &cx, int cnt, uint32_t &status, PhaseClock &pc,
-                                         const char *tail_row = nullptr, int base0 = 0) {
+                                         const char *tail_row = nullptr, int base0 = 0, Collect *col = nullptr) {
     const int lane = cx.lane;
     for (int base = base0; base < cnt;) {
         uint32_t ckey, cid;
-        base += eval_round<NCH, RB, METRIC, ROWS>(iv, qv, cx, base, cnt, ckey, cid, tail_row);
+        if constexpr (COLLECT) {
+            uint32_t mid;
+            const uint32_t mword = collect_mask_word(*col, cx, base, cnt, mid);
+            const int consumed = eval_round<NCH, RB, METRIC, ROWS>(iv, qv, cx, base, cnt, ckey, cid, tail_row);
+            collect_round<NCH, ROWS>(*col, cx, mword, mid, base, cnt, consumed, ckey, cid);
+            base += consumed;
+        } else {
+            base += eval_round<NCH, RB, METRIC, ROWS>(iv, qv, cx, base, cnt, ckey, cid, tail_row);
+        }
         uint64_t pass = ballot(SEM ? ckey <= w.wmax : ckey < w.wmax);
 #ifdef HNSW_PHASE_TIMING
         asm volatile("" :: "s"(pass));
@@ -1134,10 +1210,12 @@ namespace hnsw_dev {
 // the layer operators; the knn kernel is instantiated per case so that neither pays for the other's registers).
 // BLK 1 (the knn kernel's layer-0 search only): Visited is the bitmap-block cache over the neighbours' locality codes
 // (visited_blocks_mem_add) instead of the tag cache.
-template <int NCH, int RB, int NSLOT, int METRIC, int SEM = 0, int ROWS = -1, int BLK = 0>
+// COLLECT (the collect kernel's layer-0 search only): every candidate evaluated is also offered to col->r.  The hand-scheduled
+// loops never expose a round's keys: they are compiled out and the C++ loop below runs.
+template <int NCH, int RB, int NSLOT, int METRIC, int SEM = 0, int ROWS = -1, int BLK = 0, bool COLLECT = false>
 __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (&qv)[NCH], int layer,
                                              WList<NSLOT> &w, int ef, const WaveCtx &cx,
-                                             uint32_t &n_dist, uint32_t &n_hops, uint32_t &status) {
+                                             uint32_t &n_dist, uint32_t &n_hops, uint32_t &status, Collect *col = nullptr) {
     const int lane = cx.lane;
     const bool full_rows = ROWS < 0 ? iv.nchunks == 16 * NCH : ROWS == 1;
 #ifndef HNSW_PHASE_TIMING
@@ -1148,7 +1226,7 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
     // s_mov_b64 exec, -1: they are entered with all 64 lanes on -- the kernel runs one full wave per query and reaches this
     // point through wave-uniform branches only.  A query whose tie list went to the global slab keeps the C++ loop.)
     constexpr int SEMK = SEM != 0 ? 1 : 0;
-    constexpr bool ASM_ANY = HopLoop<NCH, NSLOT, METRIC, ROWS, SEMK, BLK>::available;
+    constexpr bool ASM_ANY = !COLLECT && HopLoop<NCH, NSLOT, METRIC, ROWS, SEMK, BLK>::available;
     bool asm_ok = false;
     if constexpr (ASM_ANY) {
         asm_ok = layer == 0 && cx.ovf.g == nullptr && ((uint64_t)iv.n + 1) * (uint64_t)iv.S0 < (1ull << 30) &&
@@ -1287,12 +1365,12 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
             n_dist += cnt;
             HNSW_PHASE(pc, 1);                                           // prefetch issue + compaction through LDS
             if (ROWS == 3)      // layer 0 only (the knn kernel): the tails of c's neighbours lie beside its adjacency row
-                hop_eval<NCH, RB, NSLOT, METRIC, SEM, 3>(iv, qv, w, cx, cnt, status, pc,
-                                                         reinterpret_cast<const char *>(iv.tail0) + (uint64_t)(uint32_t)c * (uint32_t)(iv.S0 * 16 * iv.tail_chunks));
-            else if (ROWS == 2) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 2>(iv, qv, w, cx, cnt, status, pc);                                  // :573-577
-            else if (ROWS == 4) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 4>(iv, qv, w, cx, cnt, status, pc);
-            else if (ROWS == 1 || (ROWS < 0 && full_rows)) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 1>(iv, qv, w, cx, cnt, status, pc);
-            else hop_eval<NCH, RB, NSLOT, METRIC, SEM, 0>(iv, qv, w, cx, cnt, status, pc);
+                hop_eval<NCH, RB, NSLOT, METRIC, SEM, 3, COLLECT>(iv, qv, w, cx, cnt, status, pc,
+                                                         reinterpret_cast<const char *>(iv.tail0) + (uint64_t)(uint32_t)c * (uint32_t)(iv.S0 * 16 * iv.tail_chunks), 0, col);
+            else if (ROWS == 2) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 2, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);                                  // :573-577
+            else if (ROWS == 4) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 4, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
+            else if (ROWS == 1 || (ROWS < 0 && full_rows)) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 1, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
+            else hop_eval<NCH, RB, NSLOT, METRIC, SEM, 0, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
         }
 #ifdef HNSW_PHASE_TIMING
         if (!wlist_full(w)) HNSW_PHASE(pc, 4); else                        // insertions while W still holds dummies
@@ -1466,6 +1544,81 @@ hnsw_search_kernel(const IndexView iv, const SearchArgs a) {
         // need PCIe atomics)
         if ((status & 1u) && a.any_flag) *reinterpret_cast<volatile uint32_t *>(a.any_flag) = 1u;
 #endif
+    }
+}
+
+// ---- the search kernel of option "filter_collect" ---------------------------------------------------------------------------
+// The walk of hnsw_search_kernel -- same prologue, same W, same counters and status word -- whose answer is not W[0..k) but R: the
+// first k allowed nodes, under (key, id), of the layer-0 entry node and everything the layer-0 search evaluates (see Collect).
+// Always the C++ hop loop and the tag-cache Visited (the evaluated set does not depend on what Visited forgets).  a.k <= 128.
+template <int NCH, int RB, int NSLOT, int METRIC, int SEMF, int ROWS>
+__global__ void __launch_bounds__(64)
+hnsw_search_collect_kernel(const IndexView iv, const SearchArgs a, const CollectArgs c) {
+    extern __shared__ uint32_t lds[];
+    const int lane = threadIdx.x;
+    if ((int64_t)blockIdx.x >= a.nq) return;
+    const int64_t q = a.qmap ? a.qmap[blockIdx.x] : (int64_t)blockIdx.x;
+    if (a.q_limit && (q < 0 || q >= a.q_limit)) return;     // never follow a bad map entry into memory
+    WaveCtx cx = make_ctx(lds, a.vt_bits, lane);
+    if (a.ovf_g) { cx.ovf.g = a.ovf_g + (int64_t)blockIdx.x * a.ovf_gcap; cx.ovf.gcap = a.ovf_gcap; }
+    if constexpr (NSLOT >= 3 || (NSLOT == 2 && ROWS != 2)) visited_three_ways(cx, iv.n);
+    if ((int)blockIdx.x < a.prio_head || (int)blockIdx.x >= a.prio_tail) __builtin_amdgcn_s_setprio(3);
+
+    float4 qv[NCH];
+    load_query<NCH>(qv, a.Q + q * a.q_stride, iv.d, cx.l16);
+    if (ROWS == 2) query_bytes<NCH>(cx, qv, iv.d);
+    visited_clear(cx);
+    Collect col;
+    {
+        const int64_t cq = c.map ? c.map[q] : q;
+        col.bits = mask_words(c.masks[c.which ? c.which[cq] : 0]);
+    }
+    wlist_init(col.r, a.k, lane);
+
+    uint32_t n_dist = 0, n_hops = 0, status = 0;
+    constexpr int DROWS = ROWS == 3 ? 0 : ROWS;
+
+    int cur;
+    uint32_t cur_key;
+    if (a.pre_entry) {
+        cur = a.pre_entry[q]; cur_key = a.pre_key[q]; n_dist = a.pre_nd[q];
+        if (a.pre_layer > 1) greedy_descend<NCH, RB, METRIC, DROWS>(iv, qv, a.pre_layer - 1, 1, cur, cur_key, cx, n_dist);
+    } else {
+        cur = iv.entry_point;
+        if (lane == 0) cx.cand_id[0] = cur;
+        __syncthreads();
+        { uint32_t ck, ci; hop_round<NCH, 1, METRIC, DROWS>(iv, qv, cx, 0, 1, ck, ci); cur_key = rdlane(ck, 0); }
+        n_dist += 1;
+        greedy_descend<NCH, RB, METRIC, DROWS>(iv, qv, iv.max_layer, 1, cur, cur_key, cx, n_dist);
+    }
+
+    WList<NSLOT> w;
+    wlist_init(w, a.ef, lane);
+    wlist_insert<NSLOT, SEMF>(w, cur_key, (uint32_t)cur, lane, cx.ovf, status);
+    if ((col.bits[(uint32_t)cur >> 5] >> ((uint32_t)cur & 31u)) & 1u) collect_offer(col, cx, cur_key, (uint32_t)cur);   // the layer-0 entry node
+    { uint32_t hw; (void)visited_mem(cx, (uint32_t)cur, hw); visited_add_masked(cx, (uint32_t)cur, hw, lane == 0); }
+    __syncthreads();
+    search_layer<NCH, RB, NSLOT, METRIC, SEMF, ROWS, 0, true>(iv, qv, 0, w, a.ef, cx, n_dist, n_hops, status, &col);
+
+    // results: R[0..k) ascending; what R lacks is filled
+    const int rbase = 2 * 64 - a.k;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int idx = s * 64 + lane - rbase;
+        if (idx >= 0 && idx < a.k) {
+            int32_t oid = -1;
+            float od = a.fill == 0 ? __uint_as_float(0x7FC00000u) : __uint_as_float(0x7F800000u);
+            const uint32_t hi = col.r.hi[s];
+            if (hi < DUMMY_HI) { oid = (int32_t)key_id(col.r.lo[s]) + iv.id_base; od = key_to_dist<METRIC>(hi); }
+            a.out_ids[q * a.k + idx] = oid;
+            a.out_dist[q * a.k + idx] = od;
+        }
+    }
+    if (lane == 0) {
+        if (a.out_ndist) a.out_ndist[q] = n_dist;
+        if (a.out_nhops) a.out_nhops[q] = n_hops;
+        if (a.out_status) a.out_status[q] = status;
+        if ((status & 1u) && a.any_flag) *reinterpret_cast<volatile uint32_t *>(a.any_flag) = 1u;
     }
 }
 

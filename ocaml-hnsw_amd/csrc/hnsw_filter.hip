@@ -8,6 +8,9 @@
 //            two filters (hnsw_filter_plan.h).
 // The ladder itself (Ladder: the walk of a stage, the short list, the gathered batch) is here too; the range search
 // (hnsw_range.hip) runs the same one with its own select rule.
+// Option "filter_collect" (k <= 128, exact rows) changes the stage test only: a stage's walk is the collect kernel's
+// (hnsw_search_collect_kernel), whose [m][k] rows hold R -- the first k allowed nodes of everything the walk evaluated -- and the
+// select kernel, run with e := k, serves the queries whose R is full.
 //
 // Kernels.
 //   filter_popcount_kernel  the uploaded mask: clears the bits past n in its last word and counts the rest; with a second operand
@@ -190,13 +193,16 @@ int Ladder::walk(int32_t *wids, float *wdist, int32_t fill) {
     if ((rc = lb.wnd.ensure((size_t)m * 4)) || (rc = lb.wnh.ensure((size_t)m * 4)) || (rc = lb.wst.ensure((size_t)m * 4)) ||
         (rc = lb.list[0].ensure((size_t)nq * 4)) || (rc = lb.list[1].ensure((size_t)nq * 4)) || (rc = lb.count.ensure(16)))
         return rc;
-    const hnsw_search_params wp{e, e, fill, semantics};
+    // (option "filter_collect": the same walk of ef = e; its rows are R's collect_k entries, not W's e)
+    const hnsw_search_params wp{e, collect_k ? collect_k : e, fill, semantics};
+    const hnsw_dev::CollectArgs ca{collect_masks, collect_which, map};
+    const hnsw_dev::CollectArgs *const collect = collect_k ? &ca : nullptr;
     wb = KnnBatch{Qj, m, qs, wids, wdist, (uint32_t *)lb.wnd.p, (uint32_t *)lb.wnh.p, (uint32_t *)lb.wst.p, idx->hFlagDev};
     *(volatile uint32_t *)idx->hFlag = 0;
     // (d_stage: only the caller's own matrix can lie in host memory, never a gathered batch)
-    if ((rc = knn_search(idx, &wp, wb, st, map ? nullptr : d_stage, nullptr, true))) return rc;
+    if ((rc = knn_search(idx, &wp, wb, st, map ? nullptr : d_stage, nullptr, true, collect))) return rc;
     if ((rc = synced(st, what))) return rc;
-    if ((*(volatile uint32_t *)idx->hFlag & 1u) && (rc = knn_repair(idx, &wp, wb, st, nullptr, true))) return rc;
+    if ((*(volatile uint32_t *)idx->hFlag & 1u) && (rc = knn_repair(idx, &wp, wb, st, nullptr, true, collect))) return rc;
     HIP_TRY(hipMemsetAsync(lb.count.p, 0, 4, st));
     return HNSW_OK;
 }
@@ -365,6 +371,10 @@ int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_para
         return rc;
     uint32_t *const d_stage_out = (uint32_t *)fb.stage.p;
     Ladder L(idx, b.Q, b.nq, b.q_stride, p.ef, p.semantics, d_stage, st, "filtered search");
+    // option "filter_collect" (k <= 128, exact rows): a stage's walk hands back R -- the first k allowed nodes of all it evaluated --
+    // in [m][k] rows, and the select kernel below, run with e := k, counts R's real entries: its stage test is |R| >= k
+    const bool collect = idx->filter_collect && k <= 128 && !rerank;
+    if (collect) { L.collect_k = k; L.collect_masks = fs.d_masks; L.collect_which = fs.d_which; }
     // who walks: the queries whose filter allows k nodes.  Everybody (the common case, and either all or none of a single-filter
     // call): stage 0 is the caller's batch in place; some: stage 0 starts from their list, the others wait for the exact stage
     std::vector<int32_t> walkers, fresh;
@@ -374,7 +384,7 @@ int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_para
     bool short_at_end = false;
     for (bool more = walked; more;) {
         const int64_t m = L.m;
-        const int e = L.e;
+        const int e = collect ? k : L.e;      // entries per row of the stage's walk
         if ((rc = fb.wids.ensure((size_t)m * e * 4)) || (rc = fb.wdist.ensure((size_t)m * e * 4)) || (rc = fb.cnt.ensure((size_t)m * 4)) ||
             (rerank && (rc = fb.cand.ensure((size_t)m * e * 4))))
             return rc;

@@ -67,6 +67,13 @@ template <class F> auto with_metric(int metric, F &&f) { return metric == HNSW_M
     X(0, 1, 0) X(0, 1, 1) X(0, 1, 2) X(0, 1, 3) X(0, 1, 4) \
     X(1, 0, 0) X(1, 0, 1) X(1, 0, 2) X(1, 0, 3) X(1, 0, 4) \
     X(1, 1, 0) X(1, 1, 1) X(1, 1, 2) X(1, 1, 3) X(1, 1, 4)
+// The collect kernel's variant objects (option "filter_collect"; hnsw_collect_variants.hip compiled once per line), same triples:
+// the row formats whose walk distances are exact over X (0 .. 3).  build.py's COLLECT_VARIANTS is the same list.
+#define HNSW_COLLECT_VARIANTS(X) \
+    X(0, 0, 0) X(0, 0, 1) X(0, 0, 2) X(0, 0, 3) \
+    X(0, 1, 0) X(0, 1, 1) X(0, 1, 2) X(0, 1, 3) \
+    X(1, 0, 0) X(1, 0, 1) X(1, 0, 2) X(1, 0, 3) \
+    X(1, 1, 0) X(1, 1, 1) X(1, 1, 2) X(1, 1, 3)
 
 int fail(int code, const char *fmt, ...);
 // the code and message of a failed HIP call
@@ -381,6 +388,9 @@ struct hnsw_index {
     // sq8_lo / sq8_scale describe tables.Xq whenever it exists.  hnsw_index_insert quantises the whole grown table again while it is on.
     bool sq8_on = false;
     float sq8_lo = 0.0f, sq8_scale = 1.0f;
+    // option "filter_collect": the filtered searches answer from every node the walk evaluates, not from the final W only
+    // (hnsw_search_collect_kernel; k <= 128, exact-row formats: it excludes half_rows and sq8_rows).  Not saved.
+    bool filter_collect = false;
     // the stages of hnsw_search_batch_filtered and of the range calls (ladder_scratch: of both), the range calls' exact scan: ONE
     // such call in flight per handle
     hnsw_host::LadderBufs ladder_scratch;
@@ -400,11 +410,7 @@ struct hnsw_index {
 
 namespace hnsw_dev {
 
-// A mask's words as a kernel reads them once it has taken the mask's address out of a table of masks: a pointer loaded from memory
-// is a generic one to the compiler (flat loads, no scalar loads); every mask lies in device memory, and saying so keeps the loads
-// what they were when the mask was a kernel argument.
-using MaskWords = const __attribute__((address_space(1))) uint32_t *;
-__device__ __forceinline__ MaskWords mask_words(const uint32_t *p) { return (MaskWords)p; }
+// (MaskWords / mask_words, a mask's words as a kernel reads them: hnsw_device.hip.h, beside the collect kernel's use of them)
 
 // The end of a ladder stage's select kernel (filter_select_kernel, range_select_kernel), one lane per walked query: row i of the
 // stage's batch belongs to query q.  Its walk's counters go to the query's; served, it gets the stage's number, else a place in
@@ -520,12 +526,14 @@ int check_batch(const ::hnsw_index *idx, const hnsw_search_params *p, int64_t nq
 // code space (walk->qt), the re-rank the caller's.
 // raw_walk: no re-rank whatever the options say -- b receives the walk's own W[0..k) and counters (sq8 rows: the queries still go
 // through walk->qt); what hnsw_search_batch_filtered masks and re-ranks itself (hnsw_filter.hip).
+// collect (with raw_walk only; exact-row formats, p->k <= 128): the launch is the collect kernel's -- b receives R, the first p->k
+// allowed nodes of all the walk of p->ef evaluates (option "filter_collect"), under the masks collect names.
 int knn_search(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, float *d_stage = nullptr,
-               RefineBufs *walk = nullptr, bool raw_walk = false);
+               RefineBufs *walk = nullptr, bool raw_walk = false, const hnsw_dev::CollectArgs *collect = nullptr);
 // hnsw_capi.hip: the exactness fallback of the host-buffer entry points (see rerun_overflowed) for a batch knn_search ran:
 // rewrites the rows of the queries it flagged in b.st (refine active: their rows of `walk`, then the batch is re-ranked again)
 int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, hipStream_t st, RefineBufs *walk = nullptr,
-               bool raw_walk = false);
+               bool raw_walk = false, const hnsw_dev::CollectArgs *collect = nullptr);
 // hnsw_rerank.hip: the re-rank kernel on `st` for device-resident arguments (hnsw_rerank_batch_device, unchecked); nd_out
 // (optional): nd_out[q] = (nd_in ? nd_in[q] : 0) + the number of candidates evaluated
 int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, const int32_t *cand, int32_t cand_stride, int32_t k,
@@ -585,6 +593,11 @@ struct Ladder {
     int e, stage = 0;
     KnnBatch wb{};                       // the stage's walk: W where the caller wants it, counters and status in the ladder's scratch
     uint32_t n_short = 0;
+    // option "filter_collect" (set by the filtered search before the first walk): collect_k > 0: a stage's walk is the collect
+    // kernel's, which writes [m][collect_k] rows -- R under masks[which[query]] -- instead of W's [m][e]
+    int collect_k = 0;
+    const uint32_t *const *collect_masks = nullptr;
+    const int32_t *collect_which = nullptr;
     Ladder(::hnsw_index *idx_, const float *Q_, int64_t nq_, int64_t q_stride_, int ef, int32_t semantics_, float *d_stage_, hipStream_t st_,
            const char *what_)
         : idx(idx_), Q(Q_), nq(nq_), q_stride(q_stride_), semantics(semantics_), d_stage(d_stage_), st(st_), what(what_), Qj(Q_), m(nq_),

@@ -361,6 +361,9 @@ inline RangeResult brute_force_range(const Hgraph &g, const Filter &f, float rad
 // allowed nodes, a query still short gets the exact scan over the allowed nodes; distances are over the float32 vectors whatever
 // rows the index searches.  ids / distances [nq][k] (-1 / NaN where fewer than k nodes are allowed); stage[q] = how often W
 // doubled for query q, exact_stage = the exact scan.
+// After hnsw_index_set_option(h, "filter_collect", 1) (off by default; k <= 128, float32 / byte / split rows) the answer comes from every
+// node the layer-0 walk evaluates, not from the final W only: a query is served at the first stage whose walk evaluated k allowed
+// nodes (the C header: WITH OPTION filter_collect).
 struct Filtered {
     static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
     std::vector<int32_t> ids; std::vector<float> dist; std::vector<uint32_t> stage;

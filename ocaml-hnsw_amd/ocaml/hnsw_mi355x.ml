@@ -867,7 +867,10 @@ let filter_count (f : filter) : int =
    1024 until it holds k allowed nodes; a query still short is answered by the exact scan over the allowed nodes.  Distances are
    over the float32 vectors whatever rows the index searches.  -> (ids, distances, stages), ids and distances [nq][k] (id -1,
    distance nan -- ~fill:1: infinity -- where fewer than k nodes are allowed), stages.(q) = how often W doubled, -1 = exact scan.
-   ~semantics: 0 Ohnsw's accept rule, 1 the functor's (2 is refused). *)
+   ~semantics: 0 Ohnsw's accept rule, 1 the functor's (2 is refused).
+   After `hnsw_index_set_option idx "filter_collect" 1L` (off by default; k <= 128, float32 / byte / split rows) the answer comes from
+   every node the layer-0 walk evaluates, not from the final W only: a query is served at the first stage whose walk evaluated k
+   allowed nodes (the C header: WITH OPTION filter_collect). *)
 let knn_batch_filtered ?(semantics = 0) ?(fill = 0) (f : filter) (batch : Lacaml.S.mat) ~ef ~k :
   int array array * float array array * int array =
   let t = f.f_index in

@@ -13,7 +13,13 @@ all queries against the loop of single-filter calls over each tenant's queries (
 alternating in one run, medians of --steps repetitions (20 at least) after a warm round of both, and the stage histogram.  The rows
 of the two are compared once (they are the same bits).  --loop-only times the loop alone, with per-tenant masks built on the host:
 what a build without the per-query call offers.
-Usage: python tools/filter_rate.py [--n 1000000] [--nq 10000] [--steps 5] [--tenants 1,10,100,1000] [--out profiles/filtered_search.txt]"""
+
+--collect: option "filter_collect" (the answer from every node the walk evaluates, not from the final W only) against the ladder
+over W, on one handle in one run: per selectivity ms per batch, the share of queries per stage and recall@10 against the exact
+scan under the mask (brute_force_knn over the allowed vectors), with the option off and on; then the plain hnsw_search_batch of a
+MARKED index (0.1 % and 10 % of the nodes marked deleted: what tools/soft_delete_rate.py times) both ways.  The table printed
+here is what profiles/filter_collect.txt holds.
+Usage: python tools/filter_rate.py [--n 1000000] [--nq 10000] [--steps 5] [--tenants 1,10,100,1000] [--collect] [--out profiles/filtered_search.txt]"""
 import argparse
 import os
 import sys
@@ -92,6 +98,53 @@ def tenants(hg, Q, n, ef, k, counts, steps, loop_only, say):
             f.release()
 
 
+def recall_at_k(ids, X, mask, Q, k):
+    """the share of the exact masked k nearest (a flat index of X[mask]: the same order, ids mapped back) found in ids"""
+    allowed = np.flatnonzero(mask)
+    sub = H.Hgraph.flat(X[mask])
+    truth = allowed[H.Ohnsw.brute_force_knn(sub, k, Q)[0]]
+    sub.release()
+    return float(np.mean([len(set(x) & set(y)) for x, y in zip(ids, truth)])) / k
+
+
+def collect(hg, X, Q, ef, k, steps, nr, say):
+    n, nq = len(X), len(Q)
+    say('option "filter_collect" off / on, the same handle, the two timed one after the other per line; recall@%d of the first %d queries '
+        "against the exact scan under the mask" % (k, nr))
+
+    def both(call, mask, what):
+        for v in (0, 1):
+            hg.set_option("filter_collect", v)
+            ms = median_ms(lambda: call(False), steps)
+            ids, _, _, _, stage = call(True)
+            say("%s, filter_collect %d: %9.3f ms per batch, %7.3f M q/s; %s; recall@%d %.4f"
+                % (what, v, ms, nq / ms / 1e3, stage_shares(stage, nq), k, recall_at_k(ids[:nr], X, mask, Q[:nr], k)))
+        hg.set_option("filter_collect", 0)
+
+    for sel in (1.0, 0.5, 0.1, 0.01, 0.001):
+        mask = np.ones(n, bool) if sel >= 1.0 else np.random.default_rng(int(sel * 1e6)).random(n) < sel
+        flt = hg.filter(mask)
+        both(lambda counters: H.Ohnsw.knn_batch_filtered(hg, k, Q, flt, ef=ef, counters=counters), mask,
+             "selectivity %-5g (%7d allowed)" % (sel, flt.count()))
+        flt.release()
+    # the plain call of a marked index (it answers under the live mask): the stages come from the filtered call under that mask,
+    # which the plain call is bit for bit
+    order = np.random.default_rng(11).permutation(n)
+    marked = 0
+    for share in (0.001, 0.1):
+        m = int(round(share * n))
+        hg.mark_deleted(order[marked:m])
+        marked = m
+        live = ~hg.deleted_mask()
+
+        def call(counters):
+            if not counters:
+                return H.Ohnsw.knn_batch_bigarray(hg, k, Q, ef=ef)
+            return H.Ohnsw.knn_batch_filtered(hg, k, Q, live, ef=ef, counters=True)
+        both(call, live, "marked %-5g %% (%7d nodes), hnsw_search_batch" % (100 * share, m))
+    hg.unmark_deleted(order[:marked])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -100,6 +153,7 @@ def main():
     ap.add_argument("--recall-queries", type=int, default=1000)
     ap.add_argument("--tenants", default=None, help="comma-separated tenant counts: time the mixed batch instead of the selectivity table")
     ap.add_argument("--loop-only", action="store_true", help="with --tenants: the loop of single-filter calls alone")
+    ap.add_argument("--collect", action="store_true", help='option "filter_collect" off and on: rate, stages and recall per selectivity, and the marked index')
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if H.device_count() < 1:
@@ -126,7 +180,9 @@ def main():
         say("mixed batch of %d queries, uniform random labels over the nodes, a uniform random tenant per query; medians of %d alternating repetitions"
             % (a.nq, max(a.steps, 20)))
         tenants(hg, Q, a.n, ef, k, [int(x) for x in a.tenants.split(",")], a.steps, a.loop_only, say)
-    for sel in (() if a.tenants else (1.0, 0.5, 0.1, 0.01, 0.001)):
+    if a.collect:
+        collect(hg, X, Q, ef, k, a.steps, nr, say)
+    for sel in (() if a.tenants or a.collect else (1.0, 0.5, 0.1, 0.01, 0.001)):
         mask = np.ones(a.n, bool) if sel >= 1.0 else np.random.default_rng(int(sel * 1e6)).random(a.n) < sel
         flt = hg.filter(mask)
         ms = median_ms(lambda: H.Ohnsw.knn_batch_filtered(hg, k, Q, flt, ef=ef), a.steps)
