@@ -629,8 +629,34 @@ def pack_allow(allow, n, id_base=0):
     return _np.packbits(padded, bitorder="little").view("<u4").astype(_np.uint32) if words else _np.zeros(0, _np.uint32)
 
 
-class Filter:
+class _Owner:
+    """What every class that owns one library handle shares: the handle is kept in the attribute _slot names (None once released),
+    _destroy names the call that gives it back, _gone is what `handle` says afterwards."""
+    _slot = _destroy = _gone = None
+
+    @property
+    def handle(self):
+        h = getattr(self, self._slot, None)
+        if h is None:
+            raise InvalidArgument(self._gone)
+        return h
+
+    def release(self):
+        h = getattr(self, self._slot, None)
+        if h is not None:
+            getattr(load(), self._destroy)(h)
+            setattr(self, self._slot, None)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class Filter(_Owner):
     """An allow-mask over the nodes of one index, resident on its device (hnsw_filter_create); see Hgraph.filter."""
+    _slot, _destroy, _gone = "_f", "hnsw_filter_destroy", "filter already released"
 
     def __init__(self, hgraph, allow):
         self._f = None
@@ -647,12 +673,6 @@ class Filter:
         self._f, self._hg, self.n = f, hgraph, n
         return self
 
-    @property
-    def handle(self):
-        if self._f is None:
-            raise InvalidArgument("filter already released")
-        return self._f
-
     def count(self):
         """hnsw_filter_count: the number of allowed nodes"""
         c = _C.c_int64(0)
@@ -664,17 +684,6 @@ class Filter:
         out = _np.zeros((self.n + 31) // 32, _np.uint32)
         _check(load().hnsw_filter_bits(self.handle, _ptr(out) if len(out) else _C.byref(_C.c_uint32())))
         return out
-
-    def release(self):
-        if self._f is not None:
-            load().hnsw_filter_destroy(self._f)
-            self._f = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
 
 def _search_filtered(hgraph, flt, batch, ef, k, fill, counters=False, sem=0, out=None):
@@ -721,51 +730,48 @@ def _search_filtered_each(hgraph, filters, which, batch, ef, k, fill, counters=F
     return (ids, dist, nd, nh, stage) if counters else (ids, dist)
 
 
-class RangeResult:
+class RangeResult(_Owner):
     """What a range call returns, resident on the index's device (hnsw_range_result): lims [nq + 1], ids and distances [total];
     query q's segment is [lims[q], lims[q + 1]).  For callers who keep the result on the device (device_pointers) or fetch parts
     of it; Ohnsw.range_search and its kin fetch everything and release it."""
+    _prefix, _id = "hnsw_range_result_", _np.int32             # the ABI functions' common prefix; what an id is
+    _slot, _destroy, _gone = "_r", _prefix + "destroy", "range result already released"
 
     def __init__(self, handle):
         self._r = handle
 
-    @property
-    def handle(self):
-        if self._r is None:
-            raise InvalidArgument("range result already released")
-        return self._r
+    def _call(self, name, *args):
+        _check(getattr(load(), self._prefix + name)(self.handle, *args))
 
     def size(self):
         """hnsw_range_result_size -> (nq, total)"""
         nq, total = _C.c_int64(0), _C.c_int64(0)
-        _check(load().hnsw_range_result_size(self.handle, _C.byref(nq), _C.byref(total)))
+        self._call("size", _C.byref(nq), _C.byref(total))
         return nq.value, total.value
 
     def fetch(self, counters=False):
-        """hnsw_range_result_fetch -> (lims int64 [nq + 1], ids int32 [total], distances float32 [total]), with counters also
-        (ndist, nhops, stage), uint32 [nq] each"""
+        """hnsw_range_result_fetch -> (lims int64 [nq + 1], ids [total] (int32; ShardedRangeResult: int64), distances float32
+        [total]), with counters also (ndist, nhops, stage), uint32 [nq] each"""
         nq, total = self.size()
-        lims, ids, dist = _np.zeros(nq + 1, _np.int64), _np.empty(total, _np.int32), _np.empty(total, _np.float32)
+        lims, ids, dist = _np.zeros(nq + 1, _np.int64), _np.empty(total, self._id), _np.empty(total, _np.float32)
         cnt = [_np.zeros(nq, _np.uint32) for _ in range(3)] if counters else [None] * 3
-        _check(load().hnsw_range_result_fetch(self.handle, _ptr(lims), _ptr(ids), _ptr(dist), _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2])))
+        self._call("fetch", _ptr(lims), _ptr(ids), _ptr(dist), _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2]))
         return (lims, ids, dist) + tuple(cnt) if counters else (lims, ids, dist)
 
     def device_pointers(self):
         """hnsw_range_result_device -> the device addresses (lims, ids, distances) as integers, valid until release"""
         p = [_C.c_void_p() for _ in range(3)]
-        _check(load().hnsw_range_result_device(self.handle, _C.byref(p[0]), _C.byref(p[1]), _C.byref(p[2])))
+        self._call("device", _C.byref(p[0]), _C.byref(p[1]), _C.byref(p[2]))
         return tuple(x.value or 0 for x in p)
 
-    def release(self):
-        if self._r is not None:
-            load().hnsw_range_result_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
+    def _take(self, counters, keep):
+        """the result itself (keep), or everything fetched and the device copy released"""
+        if keep:
+            return self
         try:
+            return self.fetch(counters)
+        finally:
             self.release()
-        except Exception:
-            pass
 
 
 def _range_search(hgraph, batch, radius, ef, sem=0, counters=False, keep=False, filter=None):
@@ -789,13 +795,7 @@ def _range_search(hgraph, batch, radius, ef, sem=0, counters=False, keep=False, 
     finally:
         if own is not None:
             own.release()
-    res = RangeResult(r)
-    if keep:
-        return res
-    try:
-        return res.fetch(counters)
-    finally:
-        res.release()
+    return RangeResult(r)._take(counters, keep)
 
 
 def _search(hgraph, batch, ef, k, fill, counters=False, sem=0, out=None):
@@ -1125,10 +1125,11 @@ class Ba:
         return Ohnsw.search_one(hgraph, layer, start, targets, with_distance=True)
 
 
-class MultiHgraph:
+class MultiHgraph(_Owner):
     """One host process, several GPUs: the flattened graph replicated on every listed
     device; knn_batch_bigarray / knn_batch split the batch into contiguous shards, one device each,
     and return the same arrays as the single-device calls."""
+    _slot, _destroy, _gone = "_h", "hnsw_multi_destroy", "multi index already released"
 
     def __init__(self, hgraph, devices):
         self.hgraph = hgraph
@@ -1194,16 +1195,6 @@ class MultiHgraph:
         """Hnsw.Ba.knn_batch over all replicas (lib/hnsw.ml:769-777)."""
         return self._search(batch, num_neighbours_search, num_neighbours, FILL_BA, SEM_FUNCTOR)[1]
 
-    def release(self):
-        if self._h is not None:
-            load().hnsw_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
 
 def merge_lists(ids, dist, first_row, k_out, id_base=0, fill=FILL_OHNSW, device=0):
@@ -1224,59 +1215,11 @@ def merge_lists(ids, dist, first_row, k_out, id_base=0, fill=FILL_OHNSW, device=
     return out_ids, out_dist
 
 
-class ShardedRangeResult:
+class ShardedRangeResult(RangeResult):
     """What a sharded range call and merge_segments return (hnsw_sharded_range_result): as RangeResult, with int64 global ids, on
     the first device of the sharded index; it outlives that index."""
-
-    def __init__(self, handle):
-        self._r = handle
-
-    @property
-    def handle(self):
-        if self._r is None:
-            raise InvalidArgument("range result already released")
-        return self._r
-
-    def size(self):
-        """hnsw_sharded_range_result_size -> (nq, total)"""
-        nq, total = _C.c_int64(0), _C.c_int64(0)
-        _check(load().hnsw_sharded_range_result_size(self.handle, _C.byref(nq), _C.byref(total)))
-        return nq.value, total.value
-
-    def fetch(self, counters=False):
-        """hnsw_sharded_range_result_fetch -> (lims int64 [nq + 1], ids int64 [total], distances float32 [total]), with counters
-        also (ndist, nhops, stage), uint32 [nq] each"""
-        nq, total = self.size()
-        lims, ids, dist = _np.zeros(nq + 1, _np.int64), _np.empty(total, _np.int64), _np.empty(total, _np.float32)
-        cnt = [_np.zeros(nq, _np.uint32) for _ in range(3)] if counters else [None] * 3
-        _check(load().hnsw_sharded_range_result_fetch(self.handle, _ptr(lims), _ptr(ids), _ptr(dist), _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2])))
-        return (lims, ids, dist) + tuple(cnt) if counters else (lims, ids, dist)
-
-    def device_pointers(self):
-        """hnsw_sharded_range_result_device -> the device addresses (lims, ids, distances) as integers, valid until release"""
-        p = [_C.c_void_p() for _ in range(3)]
-        _check(load().hnsw_sharded_range_result_device(self.handle, _C.byref(p[0]), _C.byref(p[1]), _C.byref(p[2])))
-        return tuple(x.value or 0 for x in p)
-
-    def release(self):
-        if self._r is not None:
-            load().hnsw_sharded_range_result_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def _take(self, counters, keep):
-        """the result itself (keep), or everything fetched and the device copy released"""
-        if keep:
-            return self
-        try:
-            return self.fetch(counters)
-        finally:
-            self.release()
+    _prefix, _id = "hnsw_sharded_range_result_", _np.int64
+    _destroy = _prefix + "destroy"
 
 
 def merge_segments(lims, ids, dist, first_row, id_base=0, device=0, keep=False):
@@ -1303,9 +1246,10 @@ def merge_segments(lims, ids, dist, first_row, id_base=0, device=0, keep=False):
     return ShardedRangeResult(r)._take(False, keep)
 
 
-class ShardedFilter:
+class ShardedFilter(_Owner):
     """An allow-mask over the GLOBAL rows of one ShardedHgraph (hnsw_sharded_filter): one ordinary filter per shard, each on its
     shard's device; see ShardedHgraph.filter.  Release it before its index."""
+    _slot, _destroy, _gone = "_f", "hnsw_sharded_filter_destroy", "filter already released"
 
     def __init__(self, sharded, allow):
         self._f = None
@@ -1313,12 +1257,6 @@ class ShardedFilter:
         f = _C.c_void_p()
         _check(load().hnsw_sharded_filter_create(sharded.handle, _ptr(bits) if len(bits) else None, sharded.n, _C.byref(f)))
         self._f, self._s, self.n = f, sharded, sharded.n
-
-    @property
-    def handle(self):
-        if self._f is None:
-            raise InvalidArgument("filter already released")
-        return self._f
 
     def count(self):
         """hnsw_sharded_filter_count: the allowed rows, summed over the shards"""
@@ -1336,23 +1274,14 @@ class ShardedFilter:
         _check(load().hnsw_filter_bits(p, _ptr(out) if len(out) else _C.byref(_C.c_uint32())))
         return out
 
-    def release(self):
-        if self._f is not None:
-            load().hnsw_sharded_filter_destroy(self._f)
-            self._f = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
 
-class ShardedHgraph:
+class ShardedHgraph(_Owner):
     """One data set PARTITIONED over several GPUs (hnsw_sharded): shard g holds the rows [first_row(g), first_row(g + 1)) with a graph
     of its own on devices[g], every query visits all shards, and the per-shard answers are merged on devices[0] under (distance,
     global id).  Global ids are int64: first_row(g) + local node + id_base.  A device may be listed several times.  Capacity, where
     MultiHgraph (the index replicated, the batch split) is rate."""
+    _slot, _destroy, _gone = "_h", "hnsw_sharded_destroy", "sharded index already released"
 
     def __init__(self, handle, devices):
         self._h, self.devices = handle, [int(x) for x in devices]
@@ -1402,12 +1331,6 @@ class ShardedHgraph:
         h = _C.c_void_p()
         _check(load().hnsw_sharded_load(table, pdev, len(dev), _C.byref(h)))
         return cls(h, dev)
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise InvalidArgument("sharded index already released")
-        return self._h
 
     def num_shards(self):
         c = _C.c_int32(0)
@@ -1513,13 +1436,3 @@ class ShardedHgraph:
         """hnsw_sharded_range_brute_force_batch: the exact form -- the set Ohnsw.brute_force_range gives over one index of all rows"""
         return self._range(batch, radius, None, SEM_OHNSW, filter, counters, keep)
 
-    def release(self):
-        if self._h is not None:
-            load().hnsw_sharded_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass

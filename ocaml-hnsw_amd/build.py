@@ -17,7 +17,7 @@ VARIANTS = [(m, s, f) for m in (0, 1) for s in (0, 1) for f in (0, 1, 2, 3, 4)] 
 # the collect kernel's variants (option "filter_collect"): the same triples over the exact-row formats, see hnsw_collect_variants.hip
 COLLECT_SOURCE = "hnsw_collect_variants.hip"
 COLLECT_VARIANTS = [(m, s, f) for m in (0, 1) for s in (0, 1) for f in (0, 1, 2, 3)]
-DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
+DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
         os.path.join(ROOT, "include", "hnsw_mi355x.h")]
 
 

@@ -6,6 +6,7 @@
 #include "hnsw_filter_plan.h"
 #include "hnsw_remove_plan.h"
 #include "hnsw_mark_plan.h"
+#include "hnsw_shard_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -17,6 +18,8 @@
 #include <string>
 #include <type_traits>
 #include <vector>
+
+struct hnsw_index;
 
 namespace hnsw_host {
 
@@ -162,6 +165,42 @@ template <class T> struct Pinned : Owned<T *, hipHostFree> {
     hipError_t alloc(size_t bytes, unsigned flags) { this->reset(); return hipHostMalloc((void **)&this->h, bytes, flags); }
 };
 
+// What a range call returns, on one device: lims [nq + 1], ids and distances [total], the per-query counters [nq].  Id: int32 ids
+// local to one index (hnsw_range_result), int64 global ids (hnsw_sharded_range_result); those two derive from it and stay distinct
+// ABI types, whose _size / _fetch / _device functions are the three below (r null: HNSW_ERR_BAD_ARG).
+template <class Id> struct RangeRecord {
+    int device = -1;
+    int64_t nq = 0, total = 0;
+    DevBuf lims, ids, dist, nd, nh, stage;
+    static int size(const RangeRecord *r, int64_t *nq, int64_t *total) {
+        if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+        if (nq) *nq = r->nq;
+        if (total) *total = r->total;
+        return HNSW_OK;
+    }
+    static int fetch(const RangeRecord *r, int64_t *lims, Id *ids, float *dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage) {
+        if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+        if (!lims && !ids && !dist && !out_ndist && !out_nhops && !out_stage) return HNSW_OK;
+        HIP_TRY(hipSetDevice(r->device));
+        if (lims) HIP_TRY(hipMemcpy(lims, r->lims.p, (size_t)(r->nq + 1) * 8, hipMemcpyDeviceToHost));
+        if (ids && r->total > 0) HIP_TRY(hipMemcpy(ids, r->ids.p, (size_t)r->total * sizeof(Id), hipMemcpyDeviceToHost));
+        if (dist && r->total > 0) HIP_TRY(hipMemcpy(dist, r->dist.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
+        if (r->nq > 0) {
+            if (out_ndist) HIP_TRY(hipMemcpy(out_ndist, r->nd.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+            if (out_nhops) HIP_TRY(hipMemcpy(out_nhops, r->nh.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+            if (out_stage) HIP_TRY(hipMemcpy(out_stage, r->stage.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
+        }
+        return HNSW_OK;
+    }
+    static int device_pointers(const RangeRecord *r, const int64_t **d_lims, const Id **d_ids, const float **d_dist) {
+        if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
+        if (d_lims) *d_lims = (const int64_t *)r->lims.p;
+        if (d_ids) *d_ids = (const Id *)r->ids.p;
+        if (d_dist) *d_dist = (const float *)r->dist.p;
+        return HNSW_OK;
+    }
+};
+
 // Every device table an index holds: the vectors and the graph, and the copies derived from them -- byte rows (X8, hnsw_rows8.hip),
 // half rows (Xh, hnsw_rows16.hip), sq8 rows (Xq, hnsw_rows_sq8.hip), split rows (Xm / tail0, hnsw_rows_split.hip), locality codes
 // (lcode / lcode0, hnsw_locality.hip); a derived table that does not exist has p == nullptr.  bind_view points the handle's IndexView at them.
@@ -207,6 +246,70 @@ struct BatchBufs {
         return HNSW_OK;
     }
     void release() { for (DevBuf *b : {&q, &ids, &dist, &nd, &nh, &st, &flag, &scan}) b->release(); }
+};
+
+// an owned index handle: one under construction (destroyed unless released to the caller), or a member of a device group
+struct IndexDeleter { void operator()(::hnsw_index *idx) const { (void)hnsw_index_destroy(idx); } };
+using IndexPtr = std::unique_ptr<::hnsw_index, IndexDeleter>;
+
+// The per-device half of a multi-device handle (hnsw_multi: replicas, hnsw_sharded: shards): member g is an index on devices[g]
+// (a device may be listed several times) with a stream, an event "member g's work is enqueued up to here", the buffers of one
+// batch and a pinned host word for its launch's "any query flagged" word.  Streams, events, buffers and words are made by the
+// first call that needs them (ensure_streams).  One call in flight per group.
+struct DeviceGroup {
+    std::vector<IndexPtr> members;
+    std::vector<int> devices;
+    std::vector<Stream> streams;         // [G], each made on its device
+    std::vector<Event> done;             // [G]
+    std::vector<BatchBufs> buf;          // [G], each on its device
+    Pinned<uint32_t> hFlags;             // [G]
+    ~DeviceGroup() { release(); }
+    size_t size() const { return members.size(); }
+    ::hnsw_index *operator[](size_t g) const { return members[g].get(); }
+    // idx, on `device`, becomes the next member: the group owns it from here on, and it is never grown, shrunk or marked on its own
+    // (hnsw_index::multi_replica)
+    int adopt(::hnsw_index *idx, int device);
+    // all or nothing: a failure leaves the group as it was, so the next call tries again
+    int ensure_streams() {
+        const size_t G = members.size();
+        if (streams.size() == G) return HNSW_OK;
+        std::vector<Stream> s(G);
+        std::vector<Event> e(G);
+        Pinned<uint32_t> flags;
+        if (!hFlags) HIP_TRY(flags.alloc(G * sizeof(uint32_t), hipHostMallocPortable));
+        for (size_t g = 0; g < G; ++g) {
+            HIP_TRY(hipSetDevice(devices[g]));
+            HIP_TRY(hipStreamCreateWithFlags(&s[g].h, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&e[g].h, hipEventDisableTiming));
+        }
+        streams = std::move(s); done = std::move(e);
+        buf.resize(G);
+        if (flags) hFlags = std::move(flags);
+        return HNSW_OK;
+    }
+    // waits for EVERY stream, whatever the others answer ("nothing stays queued"), and reports the first failure
+    int sync_all() {
+        int rc = HNSW_OK;
+        for (size_t g = 0; g < streams.size(); ++g) {
+            hipError_t e = hipSetDevice(devices[g]);
+            if (e == hipSuccess) e = hipStreamSynchronize(streams[g]);
+            if (e != hipSuccess && !rc) rc = hip_fail(e, "hipStreamSynchronize");
+        }
+        return rc;
+    }
+    // per device, with that device current: the buffers, the stream, the event; then the members.  Harmless twice.
+    void release() {
+        for (size_t g = 0; g < devices.size(); ++g) {
+            (void)hipSetDevice(devices[g]);
+            if (g < buf.size()) buf[g].release();
+            if (g < streams.size()) streams[g].reset();
+            if (g < done.size()) done[g].reset();
+        }
+        buf.clear(); streams.clear(); done.clear();
+        hFlags.reset();
+        for (IndexPtr &m : members) m.reset();
+        members.clear(); devices.clear();
+    }
 };
 
 // the walk's side of a refined search (option "refine"): the first c members of W per query -- ids and distances [nq][c] -- and the
@@ -292,7 +395,6 @@ int upload_rows(const float *vectors, int64_t n, int d, int64_t row_stride, floa
 
 } // namespace hnsw_host
 
-struct hnsw_index;
 // one submitted batch (hnsw_search_submit / hnsw_search_wait): its own device buffers and stream
 struct hnsw_request {
     hnsw_index *idx = nullptr;
@@ -318,11 +420,9 @@ struct hnsw_filter {
 
 // what a range call returns: lims, ids, distances and the per-query counters on the device of the index they came from
 // (hnsw_range.hip; the sharded range calls read the counters where they lie: hnsw_sharded.hip)
-struct hnsw_range_result {
-    int device = -1;
-    int64_t nq = 0, total = 0;
-    hnsw_host::DevBuf lims, ids, dist, nd, nh, stage;
-};
+struct hnsw_range_result : hnsw_host::RangeRecord<int32_t> {};
+// ... and a sharded range call and hnsw_merge_segments: int64 global ids, on one device; it keeps no reference to the handle it came from
+struct hnsw_sharded_range_result : hnsw_host::RangeRecord<int64_t> {};
 
 struct hnsw_index {
     int device = -1;
@@ -435,9 +535,12 @@ __device__ __forceinline__ void ladder_settle(const LadderOut &o, int64_t i, int
 
 namespace hnsw_host {
 
-// a handle under construction: destroyed unless released to the caller
-struct IndexDeleter { void operator()(::hnsw_index *idx) const { (void)hnsw_index_destroy(idx); } };
-using IndexPtr = std::unique_ptr<::hnsw_index, IndexDeleter>;
+inline int DeviceGroup::adopt(::hnsw_index *idx, int device) {
+    idx->multi_replica = true;
+    members.emplace_back(idx);
+    devices.push_back(device);
+    return HNSW_OK;
+}
 
 // hnsw_capi.hip: IndexView's table pointers from idx->tables (X8 / Xm left out while option byte_rows / split_rows is 0; Xh in
 // the view while option half_rows is 1 and no byte rows are: it takes the place of Xm; Xq in the byte rows' place while option

@@ -53,25 +53,18 @@ int load_rccl(RcclApi &api) {
     return HNSW_OK;
 }
 
-// shard g of G over nq queries: [g*nq/G, (g+1)*nq/G) -- the same bounds as sharding.shard_bounds
-inline int64_t shard_lo(int64_t nq, int g, int G) { return (int64_t)((__int128)nq * g / G); }
-
 } // namespace
 
 struct hnsw_multi {
-    std::vector<hnsw_index *> replicas;
-    std::vector<int> devices;
+    // the replicas, one per listed device.  buf[g]: its query shard (shard g of G over nq queries: shard_lo), the FULL [nq][k]
+    // result, per-shard counters, the launch's "any query flagged" word (see hnsw_search_batch); done[g]: what the same-device
+    // copy arrangement waits for
+    DeviceGroup grp;
     bool distinct = true;                 // every device listed once: the RCCL path; otherwise (several replicas on
                                           // one device: tests) the gather is device-to-device copies
     RcclApi rccl;
     std::vector<ncclComm_t> comms;        // [G], created at the first device-resident search
-    std::vector<Stream> streams;          // [G]
-    std::vector<Event> done;              // [G] "this device's search is enqueued up to here" (the same-device copy arrangement)
-    // per device: its query shard; the FULL [nq][k] result; per-shard counters; the launch's "any query flagged" word (see
-    // hnsw_search_batch)
-    std::vector<BatchBufs> buf;
     int64_t last_nq = 0; int last_k = 0;
-    Pinned<uint32_t> hFlags;              // [G] pinned host words the flags are copied into
     // what the exchanges of this handle were made of (hnsw_multi_debug_counters): calls issued, summed over the devices
     int64_t n_allgather = 0, n_broadcast = 0, n_peer_copies = 0, n_repaired_shards = 0;
 };
@@ -84,36 +77,18 @@ namespace {
         if (r__ != ncclSuccess) return fail(HNSW_ERR_HIP, "%s failed: %s", #expr, (m)->rccl.GetErrorString(r__)); \
     } while (0)
 
-int ensure_streams(hnsw_multi *m) {
-    const size_t G = m->replicas.size();
-    if (m->streams.size() == G) return HNSW_OK;
-    m->streams.resize(G);
-    m->buf.resize(G);
-    if (!m->hFlags) HIP_TRY(m->hFlags.alloc(G * sizeof(uint32_t), hipHostMallocPortable));
-    for (size_t g = 0; g < G; ++g) {
-        HIP_TRY(hipSetDevice(m->devices[g]));
-        HIP_TRY(hipStreamCreateWithFlags(&m->streams[g].h, hipStreamNonBlocking));
-        Event e;
-        HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
-        m->done.push_back(std::move(e));
-    }
-    return HNSW_OK;
-}
-
 int ensure_comms(hnsw_multi *m) {
     if (!m->distinct || !m->comms.empty()) return HNSW_OK;
     int rc = load_rccl(m->rccl);
     if (rc) return rc;
-    m->comms.assign(m->replicas.size(), nullptr);
-    ncclResult_t r = m->rccl.CommInitAll(m->comms.data(), (int)m->devices.size(), m->devices.data());
+    m->comms.assign(m->grp.size(), nullptr);
+    ncclResult_t r = m->rccl.CommInitAll(m->comms.data(), (int)m->grp.devices.size(), m->grp.devices.data());
     if (r != ncclSuccess) {
         m->comms.clear();
-        return fail(HNSW_ERR_HIP, "ncclCommInitAll over %d devices failed: %s", (int)m->devices.size(), m->rccl.GetErrorString(r));
+        return fail(HNSW_ERR_HIP, "ncclCommInitAll over %d devices failed: %s", (int)m->grp.devices.size(), m->rccl.GetErrorString(r));
     }
     return HNSW_OK;
 }
-
-int sync_all(hnsw_multi *m);
 
 // An exchange that was only PARTLY enqueued (one device's collective refused inside the group) must not be left standing:
 // the devices whose collectives were accepted would wait on their streams for a peer that never joins -- harmless at
@@ -123,7 +98,7 @@ int sync_all(hnsw_multi *m);
 void abort_comms(hnsw_multi *m) {
     for (size_t g = 0; g < m->comms.size(); ++g) {
         if (!m->comms[g]) continue;
-        (void)hipSetDevice(m->devices[g]);
+        (void)hipSetDevice(m->grp.devices[g]);
         (void)m->rccl.CommAbort(m->comms[g]);
     }
     m->comms.clear();
@@ -132,34 +107,34 @@ void abort_comms(hnsw_multi *m) {
 // Sharded search + gather: on return every device's dIds / dDist hold the full [nq][k] result.
 int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
                       uint32_t *out_ndist, uint32_t *out_nhops) {
-    const int G = (int)m->replicas.size();
+    const int G = (int)m->grp.size();
     const int k = params->k;
     int rc;
-    if ((rc = ensure_streams(m)) || (rc = ensure_comms(m))) return rc;
-    const int d = m->replicas[0]->iv.d;
+    if ((rc = m->grp.ensure_streams()) || (rc = ensure_comms(m))) return rc;
+    const int d = m->grp[0]->iv.d;
     const size_t full = (size_t)nq * k;
     // ---- per device: upload the shard, search it (results straight into the shard's slice of the full table).  Nothing
     //      below waits on the host until every device has its search AND the exchange enqueued: whether a shard needs
     //      the exactness fallback comes back as one word per device, read after the exchange ----
     for (int g = 0; g < G; ++g) {
         const int64_t lo = shard_lo(nq, g, G), hi = shard_lo(nq, g + 1, G);
-        hnsw_index *idx = m->replicas[(size_t)g];
-        BatchBufs &b = m->buf[(size_t)g];
-        HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
+        hnsw_index *idx = m->grp[(size_t)g];
+        BatchBufs &b = m->grp.buf[(size_t)g];
+        HIP_TRY(hipSetDevice(m->grp.devices[(size_t)g]));
         if ((rc = b.ids.ensure(std::max<size_t>(full, 1) * 4)) || (rc = b.dist.ensure(std::max<size_t>(full, 1) * 4)) || (rc = b.flag.ensure(16)))
             return rc;
-        m->hFlags[g] = 0;
+        m->grp.hFlags[g] = 0;
         if (hi <= lo) continue;
         const int64_t ns = hi - lo;
         const size_t qbytes = query_bytes(ns, q_stride, d);
         if ((rc = b.q.ensure(qbytes)) || (rc = b.nd.ensure((size_t)ns * 4)) || (rc = b.nh.ensure((size_t)ns * 4)) || (rc = b.st.ensure((size_t)ns * 4)))
             return rc;
-        hipStream_t st = m->streams[(size_t)g];
+        hipStream_t st = m->grp.streams[(size_t)g];
         const KnnBatch shard = b.batch(ns, q_stride, k, lo);
         HIP_TRY(hipMemsetAsync(shard.any_flag, 0, 4, st));
         HIP_TRY(hipMemcpyAsync(b.q.p, queries + lo * q_stride, qbytes, hipMemcpyHostToDevice, st));
         if ((rc = knn_search(idx, params, shard, st))) return rc;
-        HIP_TRY(hipMemcpyAsync(&m->hFlags[g], shard.any_flag, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&m->grp.hFlags[g], shard.any_flag, 4, hipMemcpyDeviceToHost, st));
     }
     // ---- the exchange: every device receives every shard (shards [r_lo, r_hi) only: the whole table, or, after the
     //      fallback, the repaired shards again) ----
@@ -172,23 +147,23 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
             // (tests) HNSW_MULTI_FAIL_ENQUEUE=g: device g's enqueue is answered as refused, after the devices before it were accepted
             const int fail_at = env_int("HNSW_MULTI_FAIL_ENQUEUE", -1);
             for (int g = 0; g < G && !err; ++g) {
-                if (hipSetDevice(m->devices[(size_t)g]) != hipSuccess) { err = fail(HNSW_ERR_HIP, "hipSetDevice failed"); break; }
+                if (hipSetDevice(m->grp.devices[(size_t)g]) != hipSuccess) { err = fail(HNSW_ERR_HIP, "hipSetDevice failed"); break; }
                 if (g == fail_at) { err = fail(HNSW_ERR_HIP, "RCCL exchange failed: enqueue on device %d refused (HNSW_MULTI_FAIL_ENQUEUE)", g); break; }
-                int32_t *ids = (int32_t *)m->buf[(size_t)g].ids.p;
-                float *dd = (float *)m->buf[(size_t)g].dist.p;
+                int32_t *ids = (int32_t *)m->grp.buf[(size_t)g].ids.p;
+                float *dd = (float *)m->grp.buf[(size_t)g].dist.p;
                 ncclResult_t r1 = ncclSuccess;
                 if (equal) {       // in place: the send buffer is this rank's slice of the receive buffer
                     const size_t cnt = (size_t)(nq / G) * k;
-                    r1 = m->rccl.AllGather(ids + (size_t)g * cnt, ids, cnt, ncclInt32, m->comms[(size_t)g], m->streams[(size_t)g]);
-                    if (r1 == ncclSuccess) r1 = m->rccl.AllGather(dd + (size_t)g * cnt, dd, cnt, ncclFloat32, m->comms[(size_t)g], m->streams[(size_t)g]);
+                    r1 = m->rccl.AllGather(ids + (size_t)g * cnt, ids, cnt, ncclInt32, m->comms[(size_t)g], m->grp.streams[(size_t)g]);
+                    if (r1 == ncclSuccess) r1 = m->rccl.AllGather(dd + (size_t)g * cnt, dd, cnt, ncclFloat32, m->comms[(size_t)g], m->grp.streams[(size_t)g]);
                     if (r1 == ncclSuccess) m->n_allgather += 2;
                 } else {           // unequal shards: one in-place broadcast per shard (all-gather-v)
                     for (int r = 0; r < G && r1 == ncclSuccess; ++r) {
                         if (only_shard >= 0 && r != only_shard) continue;
                         const int64_t lo = shard_lo(nq, r, G), hi = shard_lo(nq, r + 1, G);
                         if (hi <= lo) continue;
-                        r1 = m->rccl.Broadcast(ids + lo * k, ids + lo * k, (size_t)(hi - lo) * k, ncclInt32, r, m->comms[(size_t)g], m->streams[(size_t)g]);
-                        if (r1 == ncclSuccess) r1 = m->rccl.Broadcast(dd + lo * k, dd + lo * k, (size_t)(hi - lo) * k, ncclFloat32, r, m->comms[(size_t)g], m->streams[(size_t)g]);
+                        r1 = m->rccl.Broadcast(ids + lo * k, ids + lo * k, (size_t)(hi - lo) * k, ncclInt32, r, m->comms[(size_t)g], m->grp.streams[(size_t)g]);
+                        if (r1 == ncclSuccess) r1 = m->rccl.Broadcast(dd + lo * k, dd + lo * k, (size_t)(hi - lo) * k, ncclFloat32, r, m->comms[(size_t)g], m->grp.streams[(size_t)g]);
                         if (r1 == ncclSuccess) m->n_broadcast += 2;
                     }
                 }
@@ -207,20 +182,20 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
             // several replicas on one device (a test arrangement): RCCL refuses duplicate devices, and the
             // "exchange" between buffers of the same device is a device-to-device copy
             for (int g = 0; g < G; ++g) {
-                HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
+                HIP_TRY(hipSetDevice(m->grp.devices[(size_t)g]));
                 for (int r = 0; r < G; ++r) {
                     if (r == g || (only_shard >= 0 && r != only_shard)) continue;
                     const int64_t lo = shard_lo(nq, r, G), hi = shard_lo(nq, r + 1, G);
                     if (hi <= lo) continue;
                     // the copy runs on the RECEIVER's stream: it must not start before the sender's search is done
                     if (only_shard < 0) {
-                        hipEvent_t ev = m->done[(size_t)r];
-                        HIP_TRY(hipStreamWaitEvent(m->streams[(size_t)g], ev, 0));
+                        hipEvent_t ev = m->grp.done[(size_t)r];
+                        HIP_TRY(hipStreamWaitEvent(m->grp.streams[(size_t)g], ev, 0));
                     }
-                    HIP_TRY(hipMemcpyPeerAsync((int32_t *)m->buf[(size_t)g].ids.p + lo * k, m->devices[(size_t)g], (int32_t *)m->buf[(size_t)r].ids.p + lo * k,
-                                               m->devices[(size_t)r], (size_t)(hi - lo) * k * 4, m->streams[(size_t)g]));
-                    HIP_TRY(hipMemcpyPeerAsync((float *)m->buf[(size_t)g].dist.p + lo * k, m->devices[(size_t)g], (float *)m->buf[(size_t)r].dist.p + lo * k,
-                                               m->devices[(size_t)r], (size_t)(hi - lo) * k * 4, m->streams[(size_t)g]));
+                    HIP_TRY(hipMemcpyPeerAsync((int32_t *)m->grp.buf[(size_t)g].ids.p + lo * k, m->grp.devices[(size_t)g], (int32_t *)m->grp.buf[(size_t)r].ids.p + lo * k,
+                                               m->grp.devices[(size_t)r], (size_t)(hi - lo) * k * 4, m->grp.streams[(size_t)g]));
+                    HIP_TRY(hipMemcpyPeerAsync((float *)m->grp.buf[(size_t)g].dist.p + lo * k, m->grp.devices[(size_t)g], (float *)m->grp.buf[(size_t)r].dist.p + lo * k,
+                                               m->grp.devices[(size_t)r], (size_t)(hi - lo) * k * 4, m->grp.streams[(size_t)g]));
                     m->n_peer_copies += 2;
                 }
             }
@@ -229,47 +204,39 @@ int search_and_gather(hnsw_multi *m, const float *queries, int64_t nq, int64_t q
     };
     if (!m->distinct) {   // the copy arrangement orders receiver streams behind sender streams with one event per device
         for (int g = 0; g < G; ++g) {
-            HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
-            HIP_TRY(hipEventRecord(m->done[(size_t)g], m->streams[(size_t)g]));
+            HIP_TRY(hipSetDevice(m->grp.devices[(size_t)g]));
+            HIP_TRY(hipEventRecord(m->grp.done[(size_t)g], m->grp.streams[(size_t)g]));
         }
     }
     if ((rc = exchange(-1))) return rc;
     // ---- now the one host round trip: wait, read the flag words; a flagged shard (rare) is searched again with the
     //      global slab and its slice of the table is sent round once more ----
-    if ((rc = sync_all(m))) return rc;
+    if ((rc = m->grp.sync_all())) return rc;
     for (int g = 0; g < G; ++g) {
         const int64_t lo = shard_lo(nq, g, G), hi = shard_lo(nq, g + 1, G);
         if (hi <= lo) continue;
-        const KnnBatch shard = m->buf[(size_t)g].batch(hi - lo, q_stride, k, lo);
-        HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
-        if (m->hFlags[g] & 1u) {
-            if ((rc = knn_repair(m->replicas[(size_t)g], params, shard, nullptr))) return rc;
+        const KnnBatch shard = m->grp.buf[(size_t)g].batch(hi - lo, q_stride, k, lo);
+        HIP_TRY(hipSetDevice(m->grp.devices[(size_t)g]));
+        if (m->grp.hFlags[g] & 1u) {
+            if ((rc = knn_repair(m->grp[(size_t)g], params, shard, nullptr))) return rc;
             m->n_repaired_shards++;
             if ((rc = exchange(g))) return rc;
         }
         HIP_TRY(knn_download(shard, k, nullptr, nullptr, out_ndist ? out_ndist + lo : nullptr, out_nhops ? out_nhops + lo : nullptr,
-                             m->streams[(size_t)g]));
+                             m->grp.streams[(size_t)g]));
     }
     m->last_nq = nq; m->last_k = k;
-    return HNSW_OK;
-}
-
-int sync_all(hnsw_multi *m) {
-    for (size_t g = 0; g < m->replicas.size(); ++g) {
-        HIP_TRY(hipSetDevice(m->devices[g]));
-        HIP_TRY(hipStreamSynchronize(m->streams[g]));
-    }
     return HNSW_OK;
 }
 
 // the checks of both entry points, in this order: the handle, the params pointer, the batch (nq >= 1, the buffers, q_stride),
 // the params' values (before any allocation sized by them; same text as the single-device call)
 int check_multi(const hnsw_multi *m, const hnsw_search_params *p, int64_t nq, int64_t q_stride, bool buffers) {
-    if (!m || m->replicas.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_multi");
+    if (!m || m->grp.members.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_multi");
     if (!p) return fail(HNSW_ERR_BAD_ARG, "null params");
     if (nq < 1 || !buffers) return fail(HNSW_ERR_BAD_ARG, "bad buffers (nq=%lld)", (long long)nq);
-    if (q_stride < m->replicas[0]->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
-    return check_params(m->replicas[0], p);
+    if (q_stride < m->grp[0]->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
+    return check_params(m->grp[0], p);
 }
 
 } // namespace
@@ -285,9 +252,7 @@ int32_t hnsw_multi_create(const hnsw_index_desc *desc, const int32_t *devices, i
         hnsw_index *idx = nullptr;
         const int rc = hnsw_index_create(desc, devices[g], &idx);
         if (rc) { hnsw_multi_destroy(m); return rc; }   // the message of the failing create stays
-        idx->multi_replica = true;       // grown only together with the other replicas (hnsw_index_insert refuses it)
-        m->replicas.push_back(idx);
-        m->devices.push_back(devices[g]);
+        (void)m->grp.adopt(idx, devices[g]);     // grown only together with the other replicas (hnsw_index_insert refuses it)
         for (int h = 0; h < g; ++h) if (devices[h] == devices[g]) m->distinct = false;
     }
     *out = m;
@@ -296,32 +261,23 @@ int32_t hnsw_multi_create(const hnsw_index_desc *desc, const int32_t *devices, i
 
 int32_t hnsw_multi_destroy(hnsw_multi *m) {
     if (!m) return HNSW_OK;
-    for (size_t g = 0; g < m->streams.size(); ++g) {
-        (void)hipSetDevice(m->devices[g]);
-        if (m->streams[g]) { (void)hipStreamSynchronize(m->streams[g]); }
-    }
+    (void)m->grp.sync_all();
     for (ncclComm_t c : m->comms) if (c) (void)m->rccl.CommDestroy(c);
-    for (size_t g = 0; g < m->streams.size(); ++g) {
-        (void)hipSetDevice(m->devices[g]);
-        m->buf[g].release();
-        m->streams[g].reset();
-        if (g < m->done.size()) m->done[g].reset();
-    }
-    for (hnsw_index *idx : m->replicas) (void)hnsw_index_destroy(idx);
+    m->grp.release();
     delete m;
     return HNSW_OK;
 }
 
 int32_t hnsw_multi_num_replicas(const hnsw_multi *m, int32_t *n_devices) {
     if (!m || !n_devices) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    *n_devices = (int32_t)m->replicas.size();
+    *n_devices = (int32_t)m->grp.size();
     return HNSW_OK;
 }
 
 int32_t hnsw_multi_replica(hnsw_multi *m, int32_t g, hnsw_index **out) {
     if (!m || !out) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    if (g < 0 || g >= (int32_t)m->replicas.size()) return fail(HNSW_ERR_BAD_ARG, "replica %d out of range", g);
-    *out = m->replicas[(size_t)g];
+    if (g < 0 || g >= (int32_t)m->grp.size()) return fail(HNSW_ERR_BAD_ARG, "replica %d out of range", g);
+    *out = m->grp[(size_t)g];
     return HNSW_OK;
 }
 
@@ -329,11 +285,11 @@ int32_t hnsw_multi_search_batch_device(hnsw_multi *m, const float *queries, int6
                                        const hnsw_search_params *params, int32_t **d_ids, float **d_dist) {
     int rc = check_multi(m, params, nq, q_stride, queries != nullptr);
     if (rc) return rc;
-    if ((rc = search_and_gather(m, queries, nq, q_stride, params, nullptr, nullptr))) { (void)sync_all(m); return rc; }
-    if ((rc = sync_all(m))) return rc;
-    for (size_t g = 0; g < m->replicas.size(); ++g) {
-        if (d_ids) d_ids[g] = (int32_t *)m->buf[g].ids.p;
-        if (d_dist) d_dist[g] = (float *)m->buf[g].dist.p;
+    if ((rc = search_and_gather(m, queries, nq, q_stride, params, nullptr, nullptr))) { (void)m->grp.sync_all(); return rc; }
+    if ((rc = m->grp.sync_all())) return rc;
+    for (size_t g = 0; g < m->grp.size(); ++g) {
+        if (d_ids) d_ids[g] = (int32_t *)m->grp.buf[g].ids.p;
+        if (d_dist) d_dist[g] = (float *)m->grp.buf[g].dist.p;
     }
     return HNSW_OK;
 }
@@ -346,12 +302,12 @@ int32_t hnsw_multi_debug_counters(const hnsw_multi *m, int64_t *out4) {
 
 int32_t hnsw_multi_copy_result(hnsw_multi *m, int32_t g, int32_t *out_ids, float *out_dist) {
     if (!m || !out_ids || !out_dist) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    if (g < 0 || g >= (int32_t)m->replicas.size()) return fail(HNSW_ERR_BAD_ARG, "replica %d out of range", g);
-    if (m->last_nq < 1 || m->streams.empty()) return fail(HNSW_ERR_BAD_ARG, "no device-resident result yet");
-    HIP_TRY(hipSetDevice(m->devices[(size_t)g]));
+    if (g < 0 || g >= (int32_t)m->grp.size()) return fail(HNSW_ERR_BAD_ARG, "replica %d out of range", g);
+    if (m->last_nq < 1 || m->grp.streams.empty()) return fail(HNSW_ERR_BAD_ARG, "no device-resident result yet");
+    HIP_TRY(hipSetDevice(m->grp.devices[(size_t)g]));
     const size_t bytes = (size_t)m->last_nq * m->last_k * 4;
-    HIP_TRY(hipMemcpy(out_ids, m->buf[(size_t)g].ids.p, bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_dist, m->buf[(size_t)g].dist.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_ids, m->grp.buf[(size_t)g].ids.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_dist, m->grp.buf[(size_t)g].dist.p, bytes, hipMemcpyDeviceToHost));
     return HNSW_OK;
 }
 
@@ -359,15 +315,15 @@ int32_t hnsw_multi_search_batch(hnsw_multi *m, const float *queries, int64_t nq,
                                 const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
                                 uint32_t *out_ndist, uint32_t *out_nhops) {
     // one replica, or nothing to search: the single-device call (once the handle, the params pointer and nq >= 0 are checked)
-    if (m && !m->replicas.empty() && params && nq >= 0 && (m->replicas.size() == 1 || nq == 0))
-        return hnsw_search_batch(m->replicas[0], queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops);
+    if (m && !m->grp.members.empty() && params && nq >= 0 && (m->grp.size() == 1 || nq == 0))
+        return hnsw_search_batch(m->grp[0], queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops);
     int rc = check_multi(m, params, nq, q_stride, queries && out_ids && out_dist);
     if (rc) return rc;
-    if ((rc = search_and_gather(m, queries, nq, q_stride, params, out_ndist, out_nhops))) { (void)sync_all(m); return rc; }
+    if ((rc = search_and_gather(m, queries, nq, q_stride, params, out_ndist, out_nhops))) { (void)m->grp.sync_all(); return rc; }
     // the host gets the table from ONE device (it is complete everywhere after the exchange)
-    HIP_TRY(hipSetDevice(m->devices[0]));
-    HIP_TRY(knn_download(m->buf[0].batch(nq, q_stride, params->k), params->k, out_ids, out_dist, nullptr, nullptr, m->streams[0]));
-    return sync_all(m);
+    HIP_TRY(hipSetDevice(m->grp.devices[0]));
+    HIP_TRY(knn_download(m->grp.buf[0].batch(nq, q_stride, params->k), params->k, out_ids, out_dist, nullptr, nullptr, m->grp.streams[0]));
+    return m->grp.sync_all();
 }
 
 } // extern "C"

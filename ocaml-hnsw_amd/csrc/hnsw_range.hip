@@ -582,41 +582,15 @@ int32_t hnsw_range_brute_force_batch_filtered(hnsw_index *idx, const hnsw_filter
     return range_brute_entry(idx, true, f, queries, nq, q_stride, radius, out);
 }
 
-int32_t hnsw_range_result_size(const hnsw_range_result *r, int64_t *nq, int64_t *total) {
-    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
-    if (nq) *nq = r->nq;
-    if (total) *total = r->total;
-    return HNSW_OK;
-}
-
+// the result's functions (the bodies: RangeRecord, hnsw_internal.h)
+int32_t hnsw_range_result_size(const hnsw_range_result *r, int64_t *nq, int64_t *total) { return RangeRecord<int32_t>::size(r, nq, total); }
 int32_t hnsw_range_result_fetch(hnsw_range_result *r, int64_t *lims, int32_t *ids, float *dist, uint32_t *out_ndist, uint32_t *out_nhops,
                                 uint32_t *out_stage) {
-    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
-    if (!lims && !ids && !dist && !out_ndist && !out_nhops && !out_stage) return HNSW_OK;
-    HIP_TRY(hipSetDevice(r->device));
-    if (lims) HIP_TRY(hipMemcpy(lims, r->lims.p, (size_t)(r->nq + 1) * 8, hipMemcpyDeviceToHost));
-    if (ids && r->total > 0) HIP_TRY(hipMemcpy(ids, r->ids.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
-    if (dist && r->total > 0) HIP_TRY(hipMemcpy(dist, r->dist.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
-    if (r->nq > 0) {
-        if (out_ndist) HIP_TRY(hipMemcpy(out_ndist, r->nd.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
-        if (out_nhops) HIP_TRY(hipMemcpy(out_nhops, r->nh.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
-        if (out_stage) HIP_TRY(hipMemcpy(out_stage, r->stage.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
-    }
-    return HNSW_OK;
+    return RangeRecord<int32_t>::fetch(r, lims, ids, dist, out_ndist, out_nhops, out_stage);
 }
-
 int32_t hnsw_range_result_device(hnsw_range_result *r, const int64_t **d_lims, const int32_t **d_ids, const float **d_dist) {
-    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
-    if (d_lims) *d_lims = (const int64_t *)r->lims.p;
-    if (d_ids) *d_ids = (const int32_t *)r->ids.p;
-    if (d_dist) *d_dist = (const float *)r->dist.p;
-    return HNSW_OK;
+    return RangeRecord<int32_t>::device_pointers(r, d_lims, d_ids, d_dist);
 }
-
-int32_t hnsw_range_result_destroy(hnsw_range_result *r) {
-    if (!r) return HNSW_OK;
-    delete r;
-    return HNSW_OK;
-}
+int32_t hnsw_range_result_destroy(hnsw_range_result *r) { delete r; return HNSW_OK; }
 
 } // extern "C"

@@ -255,13 +255,9 @@ hnsw_merge_segments_sum_kernel(const SegSumArgs a) {
 } // namespace hnsw_dev
 
 struct hnsw_sharded {
-    std::vector<hnsw_index *> shards;
-    std::vector<int> devices;
+    // the shards.  buf[g]: the whole batch, its [nq][k] results, counters and flag word; done[g]: what the copies to devices[0] wait for
+    DeviceGroup grp;
     std::vector<int64_t> lo;             // [G + 1]: shard g holds the rows [lo[g], lo[g + 1])
-    std::vector<Stream> streams;         // [G], made by the first search
-    std::vector<Event> done;             // [G] "shard g's search is enqueued up to here": what the copies to devices[0] wait for
-    std::vector<BatchBufs> buf;          // [G] on its device: the whole batch, its [nq][k] results, counters and flag word
-    Pinned<uint32_t> hFlags;             // [G] the launches' "any query flagged" words on the host
     // on devices[0]: every shard's results and counters ([G][nq][k], [G][nq]) and the merged rows.  One call in flight per handle.
     DevBuf gIds, gDist, gNd, gNh, mIds, mDist, mNd, mNh;
     // ... the filtered search's stages ([G][nq] and merged), the range calls' concatenated lims ([G][nq + 1])
@@ -275,56 +271,22 @@ struct hnsw_sharded_filter {
     ~hnsw_sharded_filter() { for (hnsw_filter *f : parts) (void)hnsw_filter_destroy(f); }
 };
 
-// what a sharded range call and hnsw_merge_segments return: as hnsw_range_result, with int64 global ids, on one device; it keeps no
-// reference to the handle it came from
-struct hnsw_sharded_range_result {
-    int device = -1;
-    int64_t nq = 0, total = 0;
-    DevBuf lims, ids, dist, nd, nh, stage;
-};
-
 namespace {
 
 using hnsw_dev::MergeArgs;
 using hnsw_dev::MERGE_LISTS;
+static_assert(MERGE_LISTS == SEG_LISTS, "a SegPlan holds as many lists as SegArgs");
 
 int launch_merge(const MergeArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(hnsw_dev::hnsw_merge_lists_kernel, dim3((unsigned)a.nq), dim3(MERGE_LISTS), 0, st, a);
     return launched("merge kernel");
 }
 
-int ensure_streams(hnsw_sharded *s) {
-    const size_t G = s->shards.size();
-    if (s->streams.size() == G) return HNSW_OK;
-    s->streams.clear(); s->done.clear();
-    s->buf.resize(G);
-    if (!s->hFlags) HIP_TRY(s->hFlags.alloc(G * sizeof(uint32_t), hipHostMallocPortable));
-    std::vector<Stream> streams(G);
-    std::vector<Event> done(G);
-    for (size_t g = 0; g < G; ++g) {
-        HIP_TRY(hipSetDevice(s->devices[g]));
-        HIP_TRY(hipStreamCreateWithFlags(&streams[g].h, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&done[g].h, hipEventDisableTiming));
-    }
-    s->streams = std::move(streams); s->done = std::move(done);
-    return HNSW_OK;
-}
-
-int sync_all(hnsw_sharded *s) {
-    int rc = HNSW_OK;
-    for (size_t g = 0; g < s->streams.size(); ++g) {
-        hipError_t e = hipSetDevice(s->devices[g]);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->streams[g]);
-        if (e != hipSuccess && !rc) rc = hip_fail(e, "hipStreamSynchronize");
-    }
-    return rc;
-}
-
 // shard g's [nq][k] results (and its counters, with_counters) into its slice of the tables on devices[0], on devices[0]'s stream
 int copy_shard(hnsw_sharded *s, int g, int64_t nq, int k, bool with_counters) {
-    const int d0 = s->devices[0], dg = s->devices[(size_t)g];
-    const BatchBufs &b = s->buf[(size_t)g];
-    hipStream_t st = s->streams[0];
+    const int d0 = s->grp.devices[0], dg = s->grp.devices[(size_t)g];
+    const BatchBufs &b = s->grp.buf[(size_t)g];
+    hipStream_t st = s->grp.streams[0];
     const size_t rows = (size_t)nq * k, rbytes = rows * 4, cbytes = (size_t)nq * 4;
     HIP_TRY(hipMemcpyPeerAsync((int32_t *)s->gIds.p + (size_t)g * rows, d0, b.ids.p, dg, rbytes, st));
     HIP_TRY(hipMemcpyPeerAsync((float *)s->gDist.p + (size_t)g * rows, d0, b.dist.p, dg, rbytes, st));
@@ -337,7 +299,7 @@ int copy_shard(hnsw_sharded *s, int g, int64_t nq, int k, bool with_counters) {
 
 // the tables of one k-NN call on devices[0] (the current device): every shard's rows and counters, the merged rows and counters
 int ensure_merge_tables(hnsw_sharded *s, int64_t nq, int k) {
-    const size_t G = s->shards.size(), rows = (size_t)nq * k;
+    const size_t G = s->grp.size(), rows = (size_t)nq * k;
     int rc;
     if ((rc = s->gIds.ensure(G * rows * 4)) || (rc = s->gDist.ensure(G * rows * 4)) || (rc = s->gNd.ensure(G * nq * 4)) ||
         (rc = s->gNh.ensure(G * nq * 4)) || (rc = s->gSt.ensure(G * nq * 4)) || (rc = s->mIds.ensure(rows * 8)) || (rc = s->mDist.ensure(rows * 4)) ||
@@ -346,17 +308,27 @@ int ensure_merge_tables(hnsw_sharded *s, int64_t nq, int k) {
     return HNSW_OK;
 }
 
+// ... of one range call: every shard's lims and counters ([G][nq + 1], [G][nq]) and the `entries` ids and distances of all shards
+int ensure_range_tables(hnsw_sharded *s, int64_t nq, int64_t entries) {
+    const size_t G = s->grp.size(), ebytes = (size_t)std::max<int64_t>(entries, 1) * 4, cbytes = std::max<size_t>(G * (size_t)nq * 4, 4);
+    int rc;
+    if ((rc = s->gLims.ensure(G * (size_t)(nq + 1) * 8)) || (rc = s->gIds.ensure(ebytes)) || (rc = s->gDist.ensure(ebytes)) ||
+        (rc = s->gNd.ensure(cbytes)) || (rc = s->gNh.ensure(cbytes)) || (rc = s->gSt.ensure(cbytes)))
+        return rc;
+    return HNSW_OK;
+}
+
 // The end of every sharded k-NN call: the shards' rows lie in the tables on devices[0] (or are queued there on streams[0]); the
 // merge kernel, ONE download into the caller's arrays, the wait.  with_stage: the third counter table, reduced with max.
 int merge_and_download(hnsw_sharded *s, int64_t nq, int k, int32_t fill, bool with_counters, bool with_stage, int64_t *out_ids, float *out_dist,
                        uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_st) {
-    const int G = (int)s->shards.size();
+    const int G = (int)s->grp.size();
     const size_t rows = (size_t)nq * k;
-    HIP_TRY(hipSetDevice(s->devices[0]));
-    hipStream_t st = s->streams[0];
+    HIP_TRY(hipSetDevice(s->grp.devices[0]));
+    hipStream_t st = s->grp.streams[0];
     MergeArgs a{(const int32_t *)s->gIds.p, (const float *)s->gDist.p, with_counters ? (const uint32_t *)s->gNd.p : nullptr,
                 with_counters ? (const uint32_t *)s->gNh.p : nullptr, with_stage ? (const uint32_t *)s->gSt.p : nullptr, nq, G, k, k,
-                s->shards[0]->iv.id_base, fill, (int64_t *)s->mIds.p, (float *)s->mDist.p, (uint32_t *)s->mNd.p, (uint32_t *)s->mNh.p,
+                s->grp[0]->iv.id_base, fill, (int64_t *)s->mIds.p, (float *)s->mDist.p, (uint32_t *)s->mNd.p, (uint32_t *)s->mNh.p,
                 (uint32_t *)s->mSt.p, {}};
     for (int g = 0; g < G; ++g) a.first_row[g] = s->lo[(size_t)g];
     const int rc = launch_merge(a, st);
@@ -379,53 +351,53 @@ int merge_and_download(hnsw_sharded *s, int64_t nq, int k, int32_t fill, bool wi
 template <class Search, class Repair>
 int search_and_merge(hnsw_sharded *s, const float *queries, int64_t nq, int64_t q_stride, int k, int32_t fill, bool with_counters,
                      int64_t *out_ids, float *out_dist, uint32_t *out_nd, uint32_t *out_nh, Search &&search, Repair &&repair) {
-    const int G = (int)s->shards.size();
-    const int d = s->shards[0]->iv.d;
+    const int G = (int)s->grp.size();
+    const int d = s->grp[0]->iv.d;
     const size_t qbytes = query_bytes(nq, q_stride, d);
     int rc;
     // ---- every allocation first: nothing below returns with work queued that it does not wait for ----
-    if ((rc = ensure_streams(s))) return rc;
+    if ((rc = s->grp.ensure_streams())) return rc;
     for (int g = 0; g < G; ++g) {
-        HIP_TRY(hipSetDevice(s->devices[(size_t)g]));
-        if ((rc = s->buf[(size_t)g].ensure(nq, qbytes, k))) return rc;
+        HIP_TRY(hipSetDevice(s->grp.devices[(size_t)g]));
+        if ((rc = s->grp.buf[(size_t)g].ensure(nq, qbytes, k))) return rc;
     }
-    HIP_TRY(hipSetDevice(s->devices[0]));
+    HIP_TRY(hipSetDevice(s->grp.devices[0]));
     if ((rc = ensure_merge_tables(s, nq, k))) return rc;
     auto queued = [&]() -> int {
         for (int g = 0; g < G; ++g) {
-            const BatchBufs &b = s->buf[(size_t)g];
-            hipStream_t st = s->streams[(size_t)g];
-            HIP_TRY(hipSetDevice(s->devices[(size_t)g]));
-            s->hFlags[g] = 0;
+            const BatchBufs &b = s->grp.buf[(size_t)g];
+            hipStream_t st = s->grp.streams[(size_t)g];
+            HIP_TRY(hipSetDevice(s->grp.devices[(size_t)g]));
+            s->grp.hFlags[g] = 0;
             const KnnBatch batch = b.batch(nq, q_stride, k);
             HIP_TRY(hipMemsetAsync(batch.any_flag, 0, 4, st));
             HIP_TRY(hipMemcpyAsync(b.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
-            int r = search(s->shards[(size_t)g], batch, st);
+            int r = search(s->grp[(size_t)g], batch, st);
             if (r) return r;
-            HIP_TRY(hipMemcpyAsync(&s->hFlags[g], batch.any_flag, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipEventRecord(s->done[(size_t)g], st));
+            HIP_TRY(hipMemcpyAsync(&s->grp.hFlags[g], batch.any_flag, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(s->grp.done[(size_t)g], st));
         }
         // the copies run on devices[0]'s stream, each behind its shard's search
-        HIP_TRY(hipSetDevice(s->devices[0]));
+        HIP_TRY(hipSetDevice(s->grp.devices[0]));
         for (int g = 0; g < G; ++g) {
-            hipEvent_t ev = s->done[(size_t)g];
-            HIP_TRY(hipStreamWaitEvent(s->streams[0], ev, 0));
+            hipEvent_t ev = s->grp.done[(size_t)g];
+            HIP_TRY(hipStreamWaitEvent(s->grp.streams[0], ev, 0));
             int r = copy_shard(s, g, nq, k, with_counters);
             if (r) return r;
         }
         return HNSW_OK;
     };
     rc = queued();
-    const int rs = sync_all(s);             // the one host round trip (also after a failure: nothing stays queued)
+    const int rs = s->grp.sync_all();             // the one host round trip (also after a failure: nothing stays queued)
     if (rc || (rc = rs)) return rc;
     for (int g = 0; g < G; ++g) {
-        if (!(s->hFlags[g] & 1u)) continue;
+        if (!(s->grp.hFlags[g] & 1u)) continue;
         // (rare) the shard's launch flagged a tie overflow: its flagged queries are searched again, complete on return, and the
         // shard's rows are sent once more
-        HIP_TRY(hipSetDevice(s->devices[(size_t)g]));
-        if ((rc = repair(s->shards[(size_t)g], s->buf[(size_t)g].batch(nq, q_stride, k)))) return rc;
-        HIP_TRY(hipSetDevice(s->devices[0]));
-        if ((rc = copy_shard(s, g, nq, k, with_counters))) { (void)sync_all(s); return rc; }
+        HIP_TRY(hipSetDevice(s->grp.devices[(size_t)g]));
+        if ((rc = repair(s->grp[(size_t)g], s->grp.buf[(size_t)g].batch(nq, q_stride, k)))) return rc;
+        HIP_TRY(hipSetDevice(s->grp.devices[0]));
+        if ((rc = copy_shard(s, g, nq, k, with_counters))) { (void)s->grp.sync_all(); return rc; }
     }
     return merge_and_download(s, nq, k, fill, with_counters, false, out_ids, out_dist, out_nd, out_nh, nullptr);
 }
@@ -437,14 +409,12 @@ int check_shard_count(int32_t n_shards) {
 
 // idx becomes the next shard of s (which owns it from here on): every shard agrees with the first on d, metric and id_base
 int adopt_shard(hnsw_sharded *s, hnsw_index *idx, int device) {
-    idx->multi_replica = true;           // never grown, shrunk or marked on its own: every later shard's first_row would move
-    s->shards.push_back(idx);
-    s->devices.push_back(device);
+    (void)s->grp.adopt(idx, device);     // never grown, shrunk or marked on its own: every later shard's first_row would move
     s->lo.push_back(s->lo.back() + idx->iv.n);
-    const hnsw_index *first = s->shards[0];
+    const hnsw_index *first = s->grp[0];
     if (idx->iv.d != first->iv.d || idx->info.metric != first->info.metric || idx->iv.id_base != first->iv.id_base)
         return fail(HNSW_ERR_BAD_ARG, "shard %d (d=%d metric=%d id_base=%d) does not agree with shard 0 (d=%d metric=%d id_base=%d)",
-                    (int)s->shards.size() - 1, idx->iv.d, idx->info.metric, idx->iv.id_base, first->iv.d, first->info.metric, first->iv.id_base);
+                    (int)s->grp.size() - 1, idx->iv.d, idx->info.metric, idx->iv.id_base, first->iv.d, first->info.metric, first->iv.id_base);
     return HNSW_OK;
 }
 
@@ -471,13 +441,13 @@ constexpr int SHARD_THREADS = 16;        // host threads that drive shard calls 
 // behind a mutex).  The error message is thread-local: a failing shard's is taken on its thread, and the lowest-numbered failing
 // shard's code and message become this thread's.  One shard, or no thread to be had: on the calling thread, in order.
 template <class Call> int on_shards(hnsw_sharded *s, Call &&call) {
-    const int G = (int)s->shards.size();
+    const int G = (int)s->grp.size();
     std::vector<int> rc((size_t)G, HNSW_OK);
     std::vector<std::string> msg((size_t)G);
     std::atomic<int> next{0};
     auto work = [&]() {
         for (int g; (g = next.fetch_add(1)) < G;) {
-            const hipError_t e = hipSetDevice(s->devices[(size_t)g]);
+            const hipError_t e = hipSetDevice(s->grp.devices[(size_t)g]);
             rc[(size_t)g] = e == hipSuccess ? call(g) : hip_fail(e, "hipSetDevice");
             if (rc[(size_t)g]) msg[(size_t)g] = hnsw_last_error();
         }
@@ -495,24 +465,47 @@ template <class Call> int on_shards(hnsw_sharded *s, Call &&call) {
     return HNSW_OK;
 }
 
+// what both k-NN entry points check first, in this order: the handle, the batch against shard 0 (check_batch), the semantics, the
+// params against every later shard (an empty shard refuses what shard 0 let through)
+int check_sharded_knn(const hnsw_sharded *s, const hnsw_search_params *params, int64_t nq, int64_t q_stride, bool buffers) {
+    if (!s || s->grp.members.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    int rc = check_batch(s->grp[0], params, nq, q_stride, buffers);
+    if (rc) return rc;
+    if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
+        return fail(HNSW_ERR_BAD_ARG, "HNSW_SEM_FUNCTOR_NEAREST_K: the k farthest of W have no merged meaning over shards");
+    for (size_t g = 1; g < s->grp.size(); ++g) if ((rc = check_params(s->grp[g], params))) return rc;
+    return HNSW_OK;
+}
+
 int check_sharded_filter(const hnsw_sharded *s, const hnsw_sharded_filter *f) {
     if (!f) return fail(HNSW_ERR_BAD_ARG, "null sharded filter");
-    if (f->owner != s || f->parts.size() != s->shards.size()) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another hnsw_sharded");
+    if (f->owner != s || f->parts.size() != s->grp.size()) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another hnsw_sharded");
     return HNSW_OK;
 }
 
 struct RangeResultDeleter { void operator()(hnsw_range_result *r) const { (void)hnsw_range_result_destroy(r); } };
 using RangeResultPtr = std::unique_ptr<hnsw_range_result, RangeResultDeleter>;
 
-// The merge of n_lists range results that lie on `device` (current) as SegArgs describes them -- a.lims, a.ids, a.dist, a.base,
-// a.first_row, a.nq, a.n_lists set; totals[g] = list g's entries -- queued on st and waited for: r's buffers are allocated here, once
-// the summed total is known to fit.  nd / nh / stg: the lists' counters ([n_lists][nq], device), or all null.  flags: scratch for the
-// pre-pass ([n_lists][nq] bytes).
-int merge_segments_on_device(int device, hipStream_t st, hnsw_dev::SegArgs a, const std::vector<int64_t> &totals, const uint32_t *nd,
-                             const uint32_t *nh, const uint32_t *stg, DevBuf &flags, hnsw_sharded_range_result *r) {
-    int64_t total = 0, longest = 0;
-    for (int64_t t : totals) { total += t; longest = std::max(longest, t); }
-    if (total > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "%lld merged results: more than 2^31 - 1 in one call", (long long)total);
+// the two refusals of a SegPlan, in the words of the callers
+int seg_list_too_long(int g, int64_t entries) {
+    return fail(HNSW_ERR_UNSUPPORTED, "list %d has %lld entries: more than 2^31 - 1", g, (long long)entries);
+}
+int seg_sum_too_long(const SegPlan &p) {
+    return fail(HNSW_ERR_UNSUPPORTED, "%lld merged results: more than 2^31 - 1 in one call", (long long)p.sum);
+}
+
+// The merge of p's lists (closed: the sum fits) over nq queries, which lie on `device` (current) in one table per kind -- lims
+// [n_lists][nq + 1], list g's ids and distances from entry p.base[g] on -- queued on st and waited for: r's buffers are allocated
+// here.  nd / nh / stg: the lists' counters ([n_lists][nq], device), or all null.  flags: scratch for the pre-pass ([n_lists][nq] bytes).
+int merge_segments_on_device(int device, hipStream_t st, const SegPlan &p, int64_t nq, const int64_t *lims, const int32_t *ids, const float *dist,
+                             const uint32_t *nd, const uint32_t *nh, const uint32_t *stg, DevBuf &flags, hnsw_sharded_range_result *r) {
+    hnsw_dev::SegArgs a{};
+    a.lims = lims; a.ids = ids; a.dist = dist;
+    a.nq = nq;
+    a.n_lists = p.n_lists;
+    std::copy(p.base, p.base + p.n_lists, a.base);
+    std::copy(p.first_row, p.first_row + p.n_lists, a.first_row);
+    const int64_t total = p.sum, longest = p.longest;
     r->device = device;
     r->nq = a.nq;
     r->total = total;
@@ -549,7 +542,7 @@ int merge_segments_on_device(int device, hipStream_t st, hnsw_dev::SegArgs a, co
 // Both sharded range calls once s, f and out are checked: `call` makes shard g's single-index call (complete on return, its result on
 // the shard's device); the results go to devices[0] by peer copies on streams[0], one table per kind, and are merged there.
 template <class Call> int sharded_range(hnsw_sharded *s, int64_t nq, hnsw_sharded_range_result **out, Call &&call) {
-    const int G = (int)s->shards.size();
+    const int G = (int)s->grp.size();
     std::vector<RangeResultPtr> part((size_t)G);
     int rc = on_shards(s, [&](int g) {
         hnsw_range_result *r = nullptr;
@@ -558,34 +551,24 @@ template <class Call> int sharded_range(hnsw_sharded *s, int64_t nq, hnsw_sharde
         return c;
     });
     if (rc) return rc;                   // (the shard results are destroyed with `part`)
-    hnsw_dev::SegArgs a{};
-    a.nq = nq;
-    a.n_lists = G;
-    std::vector<int64_t> totals((size_t)G);
-    int64_t sum = 0;
-    for (int g = 0; g < G; ++g) {
-        a.base[g] = sum;
-        a.first_row[g] = s->lo[(size_t)g];
-        sum += totals[(size_t)g] = part[(size_t)g]->total;
-    }
-    if (sum > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "%lld merged results: more than 2^31 - 1 in one call", (long long)sum);
-    if ((rc = ensure_streams(s))) return rc;
-    const int d0 = s->devices[0];
+    SegPlan plan;
+    for (int g = 0; g < G; ++g)          // (a single-index result never has more than 2^31 - 1 entries)
+        if (plan.add(part[(size_t)g]->total, s->lo[(size_t)g])) return seg_list_too_long(g, part[(size_t)g]->total);
+    if (plan.close()) return seg_sum_too_long(plan);
+    if ((rc = s->grp.ensure_streams())) return rc;
+    const int d0 = s->grp.devices[0];
     HIP_TRY(hipSetDevice(d0));
-    hipStream_t st = s->streams[0];
+    hipStream_t st = s->grp.streams[0];
     const size_t lbytes = (size_t)(nq + 1) * 8, cbytes = (size_t)nq * 4;
-    if ((rc = s->gLims.ensure((size_t)G * lbytes)) || (rc = s->gIds.ensure((size_t)std::max<int64_t>(sum, 1) * 4)) ||
-        (rc = s->gDist.ensure((size_t)std::max<int64_t>(sum, 1) * 4)) || (rc = s->gNd.ensure(std::max<size_t>((size_t)G * cbytes, 4))) ||
-        (rc = s->gNh.ensure(std::max<size_t>((size_t)G * cbytes, 4))) || (rc = s->gSt.ensure(std::max<size_t>((size_t)G * cbytes, 4))))
-        return rc;
+    if ((rc = ensure_range_tables(s, nq, plan.sum))) return rc;
     auto copies = [&]() -> int {
         for (int g = 0; g < G; ++g) {
             const hnsw_range_result &p = *part[(size_t)g];
             const size_t ebytes = (size_t)p.total * 4;
             HIP_TRY(hipMemcpyPeerAsync((char *)s->gLims.p + (size_t)g * lbytes, d0, p.lims.p, p.device, lbytes, st));
             if (ebytes) {
-                HIP_TRY(hipMemcpyPeerAsync((int32_t *)s->gIds.p + a.base[g], d0, p.ids.p, p.device, ebytes, st));
-                HIP_TRY(hipMemcpyPeerAsync((float *)s->gDist.p + a.base[g], d0, p.dist.p, p.device, ebytes, st));
+                HIP_TRY(hipMemcpyPeerAsync((int32_t *)s->gIds.p + plan.base[g], d0, p.ids.p, p.device, ebytes, st));
+                HIP_TRY(hipMemcpyPeerAsync((float *)s->gDist.p + plan.base[g], d0, p.dist.p, p.device, ebytes, st));
             }
             if (cbytes) {
                 HIP_TRY(hipMemcpyPeerAsync((char *)s->gNd.p + (size_t)g * cbytes, d0, p.nd.p, p.device, cbytes, st));
@@ -596,11 +579,9 @@ template <class Call> int sharded_range(hnsw_sharded *s, int64_t nq, hnsw_sharde
         return HNSW_OK;
     };
     if ((rc = copies())) { (void)hipStreamSynchronize(st); return rc; }     // (nothing stays queued that reads a shard result)
-    a.lims = (const int64_t *)s->gLims.p;
-    a.ids = (const int32_t *)s->gIds.p;
-    a.dist = (const float *)s->gDist.p;
     std::unique_ptr<hnsw_sharded_range_result> r(new hnsw_sharded_range_result());
-    rc = merge_segments_on_device(d0, st, a, totals, nq ? (const uint32_t *)s->gNd.p : nullptr, (const uint32_t *)s->gNh.p, (const uint32_t *)s->gSt.p, s->gFlags, r.get());
+    rc = merge_segments_on_device(d0, st, plan, nq, (const int64_t *)s->gLims.p, (const int32_t *)s->gIds.p, (const float *)s->gDist.p,
+                                  nq ? (const uint32_t *)s->gNd.p : nullptr, (const uint32_t *)s->gNh.p, (const uint32_t *)s->gSt.p, s->gFlags, r.get());
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     *out = r.release();
     return HNSW_OK;
@@ -617,7 +598,7 @@ int32_t hnsw_sharded_build(const float *vectors, int64_t n, int32_t d, int64_t r
     int rc = check_shard_count(n_shards);
     if (rc) return rc;
     if (n < n_shards) return fail(HNSW_ERR_BAD_ARG, "n=%lld < n_shards=%d: a shard would be empty", (long long)n, n_shards);
-    auto lo = [&](int g) { return (int64_t)((__int128)n * g / n_shards); };      // sharding.shard_bounds
+    auto lo = [&](int g) { return shard_lo(n, g, n_shards); };
     return make_shards(devices, n_shards, out, [&](int g, hnsw_index **idx) {
         hnsw_build_params p = *params;
         p.seed = params->seed + (uint64_t)g;
@@ -645,28 +626,22 @@ int32_t hnsw_sharded_load(const char *const *paths, const int32_t *devices, int3
 
 int32_t hnsw_sharded_destroy(hnsw_sharded *s) {
     if (!s) return HNSW_OK;
-    (void)sync_all(s);
-    for (size_t g = 0; g < s->buf.size(); ++g) {
-        (void)hipSetDevice(s->devices[g]);
-        s->buf[g].release();
-        if (g < s->streams.size()) s->streams[g].reset();
-        if (g < s->done.size()) s->done[g].reset();
-    }
-    for (hnsw_index *idx : s->shards) (void)hnsw_index_destroy(idx);
+    (void)s->grp.sync_all();
+    s->grp.release();
     delete s;
     return HNSW_OK;
 }
 
 int32_t hnsw_sharded_num_shards(const hnsw_sharded *s, int32_t *n_shards) {
     if (!s || !n_shards) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    *n_shards = (int32_t)s->shards.size();
+    *n_shards = (int32_t)s->grp.size();
     return HNSW_OK;
 }
 
 int32_t hnsw_sharded_shard(hnsw_sharded *s, int32_t g, hnsw_index **out, int64_t *first_row) {
     if (!s || !out) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    if (g < 0 || g >= (int32_t)s->shards.size()) return fail(HNSW_ERR_BAD_ARG, "shard %d out of range", g);
-    *out = s->shards[(size_t)g];
+    if (g < 0 || g >= (int32_t)s->grp.size()) return fail(HNSW_ERR_BAD_ARG, "shard %d out of range", g);
+    *out = s->grp[(size_t)g];
     if (first_row) *first_row = s->lo[(size_t)g];
     return HNSW_OK;
 }
@@ -674,29 +649,29 @@ int32_t hnsw_sharded_shard(hnsw_sharded *s, int32_t g, hnsw_index **out, int64_t
 int32_t hnsw_sharded_get_info(const hnsw_sharded *s, int64_t *n, int32_t *d, int32_t *metric, int32_t *id_base, int64_t *device_bytes) {
     if (!s) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
     int64_t bytes = 0;
-    for (const hnsw_index *idx : s->shards) {
+    for (const IndexPtr &idx : s->grp.members) {
         hnsw_index_info info;
-        const int rc = hnsw_index_get_info(idx, &info);
+        const int rc = hnsw_index_get_info(idx.get(), &info);
         if (rc) return rc;
         bytes += info.device_bytes;
     }
     if (n) *n = s->lo.back();
-    if (d) *d = s->shards[0]->iv.d;
-    if (metric) *metric = s->shards[0]->info.metric;
-    if (id_base) *id_base = s->shards[0]->iv.id_base;
+    if (d) *d = s->grp[0]->iv.d;
+    if (metric) *metric = s->grp[0]->info.metric;
+    if (id_base) *id_base = s->grp[0]->iv.id_base;
     if (device_bytes) *device_bytes = bytes;
     return HNSW_OK;
 }
 
 int32_t hnsw_sharded_set_option(hnsw_sharded *s, const char *name, int64_t value) {
     if (!s || !name) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    std::vector<int64_t> before(s->shards.size(), 0);
-    for (size_t g = 0; g < s->shards.size(); ++g) {
-        int rc = get_option(s->shards[g], name, &before[g]);
-        if (!rc) rc = hnsw_index_set_option(s->shards[g], name, value);
+    std::vector<int64_t> before(s->grp.size(), 0);
+    for (size_t g = 0; g < s->grp.size(); ++g) {
+        int rc = get_option(s->grp[g], name, &before[g]);
+        if (!rc) rc = hnsw_index_set_option(s->grp[g], name, value);
         if (rc) {
             const std::string msg = hnsw_last_error();          // shard g's refusal is what the caller reads
-            for (size_t h = 0; h < g; ++h) (void)hnsw_index_set_option(s->shards[h], name, before[h]);
+            for (size_t h = 0; h < g; ++h) (void)hnsw_index_set_option(s->grp[h], name, before[h]);
             return fail(rc, "%s", msg.c_str());
         }
     }
@@ -705,13 +680,8 @@ int32_t hnsw_sharded_set_option(hnsw_sharded *s, const char *name, int64_t value
 
 int32_t hnsw_sharded_search_batch(hnsw_sharded *s, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
                                   int64_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops) {
-    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
-    int rc = check_batch(s->shards[0], params, nq, q_stride, queries && out_ids && out_dist);
-    if (rc) return rc;
-    if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
-        return fail(HNSW_ERR_BAD_ARG, "HNSW_SEM_FUNCTOR_NEAREST_K: the k farthest of W have no merged meaning over shards");
-    for (size_t g = 1; g < s->shards.size(); ++g) if ((rc = check_params(s->shards[g], params))) return rc;   // (an empty shard)
-    if (nq == 0) return HNSW_OK;
+    const int rc = check_sharded_knn(s, params, nq, q_stride, queries && out_ids && out_dist);
+    if (rc || nq == 0) return rc;
     return search_and_merge(
         s, queries, nq, q_stride, params->k, params->fill, true, out_ids, out_dist, out_ndist, out_nhops,
         [&](hnsw_index *idx, const KnnBatch &b, hipStream_t st) { return knn_search(idx, params, b, st); },
@@ -720,8 +690,8 @@ int32_t hnsw_sharded_search_batch(hnsw_sharded *s, const float *queries, int64_t
 
 int32_t hnsw_sharded_brute_force_batch(hnsw_sharded *s, const float *queries, int64_t nq, int64_t q_stride, int32_t k, int32_t fill,
                                        int64_t *out_ids, float *out_dist) {
-    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
-    const int rc = check_scan(s->shards[0], nq, q_stride, k, fill, queries && out_ids && out_dist);
+    if (!s || s->grp.members.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    const int rc = check_scan(s->grp[0], nq, q_stride, k, fill, queries && out_ids && out_dist);
     if (rc || nq == 0) return rc;
     return search_and_merge(
         s, queries, nq, q_stride, k, fill, false, out_ids, out_dist, nullptr, nullptr,
@@ -761,26 +731,19 @@ int32_t hnsw_merge_lists(int32_t device, const int32_t *ids, const float *dist, 
 int32_t hnsw_sharded_filter_create(hnsw_sharded *s, const uint32_t *bits, int64_t n_bits, hnsw_sharded_filter **out) {
     if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    if (!s || s->grp.members.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
     if (n_bits != s->lo.back())
         return fail(HNSW_ERR_BAD_ARG, "the filter has %lld bits, the sharded index %lld rows", (long long)n_bits, (long long)s->lo.back());
     if (n_bits > 0 && !bits) return fail(HNSW_ERR_BAD_ARG, "null bits");
     std::unique_ptr<hnsw_sharded_filter> f(new hnsw_sharded_filter());      // (owns the parts made so far: any return frees them)
     f->owner = s;
-    const int64_t src_words = (n_bits + 31) / 32;
     std::vector<uint32_t> part;
-    for (size_t g = 0; g < s->shards.size(); ++g) {
-        // shard g's bits [lo_g, lo_{g+1}) moved down to bit 0: a funnel shift over two source words, the tail of the last word clear
-        const int64_t lo = s->lo[g], n = s->lo[g + 1] - lo, words = (n + 31) / 32, w0 = lo >> 5;
-        const int sh = (int)(lo & 31);
-        part.assign((size_t)std::max<int64_t>(words, 1), 0u);
-        for (int64_t w = 0; w < words; ++w) {
-            const uint64_t a = bits[w0 + w], b = w0 + w + 1 < src_words ? bits[w0 + w + 1] : 0u;
-            part[(size_t)w] = (uint32_t)((a | (b << 32)) >> sh);
-        }
-        if (n & 31) part[(size_t)words - 1] &= (1u << (n & 31)) - 1u;
+    for (size_t g = 0; g < s->grp.size(); ++g) {
+        const int64_t lo = s->lo[g], n = s->lo[g + 1] - lo;      // shard g's bits [lo_g, lo_{g+1}) moved down to bit 0
+        part.resize((size_t)std::max<int64_t>((n + 31) / 32, 1));
+        cut_mask(bits, n_bits, lo, n, part.data());
         hnsw_filter *pf = nullptr;
-        const int rc = hnsw_filter_create(s->shards[g], part.data(), n, &pf);
+        const int rc = hnsw_filter_create(s->grp[g], part.data(), n, &pf);
         if (rc) return rc;
         f->parts.push_back(pf);
     }
@@ -811,30 +774,25 @@ int32_t hnsw_sharded_filter_part(const hnsw_sharded_filter *f, int32_t g, const 
 int32_t hnsw_sharded_search_batch_filtered(hnsw_sharded *s, const hnsw_sharded_filter *f, const float *queries, int64_t nq, int64_t q_stride,
                                            const hnsw_search_params *params, int64_t *out_ids, float *out_dist, uint32_t *out_ndist,
                                            uint32_t *out_nhops, uint32_t *out_stage) {
-    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
-    int rc = check_batch(s->shards[0], params, nq, q_stride, queries && out_ids && out_dist);
-    if (rc) return rc;
-    if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
-        return fail(HNSW_ERR_BAD_ARG, "HNSW_SEM_FUNCTOR_NEAREST_K: the k farthest of W have no merged meaning over shards");
-    for (size_t g = 1; g < s->shards.size(); ++g) if ((rc = check_params(s->shards[g], params))) return rc;   // (an empty shard)
-    if ((rc = check_sharded_filter(s, f))) return rc;
+    int rc = check_sharded_knn(s, params, nq, q_stride, queries && out_ids && out_dist);
+    if (rc || (rc = check_sharded_filter(s, f))) return rc;
     if (nq == 0) return HNSW_OK;
     // The single-index call is a host-driven ladder that answers into host arrays: every shard's rows and counters pass through
     // these, then go to the tables on devices[0] in one copy per table
-    const size_t G = s->shards.size(), k = (size_t)params->k, rows = (size_t)nq * k;
+    const size_t G = s->grp.size(), k = (size_t)params->k, rows = (size_t)nq * k;
     std::vector<int32_t> ids(G * rows);
     std::vector<float> dist(G * rows);
     std::vector<uint32_t> cnt(3 * G * (size_t)nq);
     uint32_t *const nd = cnt.data(), *const nh = nd + G * (size_t)nq, *const stg = nh + G * (size_t)nq;
     rc = on_shards(s, [&](int g) {
         const size_t z = (size_t)g;
-        return (int)hnsw_search_batch_filtered(s->shards[z], f->parts[z], queries, nq, q_stride, params, ids.data() + z * rows, dist.data() + z * rows,
+        return (int)hnsw_search_batch_filtered(s->grp[z], f->parts[z], queries, nq, q_stride, params, ids.data() + z * rows, dist.data() + z * rows,
                                                nd + z * (size_t)nq, nh + z * (size_t)nq, stg + z * (size_t)nq);
     });
-    if (rc || (rc = ensure_streams(s))) return rc;
-    HIP_TRY(hipSetDevice(s->devices[0]));
+    if (rc || (rc = s->grp.ensure_streams())) return rc;
+    HIP_TRY(hipSetDevice(s->grp.devices[0]));
     if ((rc = ensure_merge_tables(s, nq, (int)k))) return rc;
-    hipStream_t st = s->streams[0];
+    hipStream_t st = s->grp.streams[0];
     hipError_t e = hipMemcpyAsync(s->gIds.p, ids.data(), G * rows * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(s->gDist.p, dist.data(), G * rows * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(s->gNd.p, nd, G * (size_t)nq * 4, hipMemcpyHostToDevice, st);
@@ -848,11 +806,11 @@ int32_t hnsw_sharded_range_search_batch(hnsw_sharded *s, const hnsw_sharded_filt
                                         const hnsw_range_params *params, hnsw_sharded_range_result **out) {
     if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    if (!s || s->grp.members.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
     int rc;
     if (f && (rc = check_sharded_filter(s, f))) return rc;
     return sharded_range(s, nq, out, [&](int g, hnsw_range_result **r) {
-        hnsw_index *idx = s->shards[(size_t)g];
+        hnsw_index *idx = s->grp[(size_t)g];
         return (int)(f ? hnsw_range_search_batch_filtered(idx, f->parts[(size_t)g], queries, nq, q_stride, params, r)
                        : hnsw_range_search_batch(idx, queries, nq, q_stride, params, r));
     });
@@ -862,51 +820,26 @@ int32_t hnsw_sharded_range_brute_force_batch(hnsw_sharded *s, const hnsw_sharded
                                              float radius, hnsw_sharded_range_result **out) {
     if (!out) return fail(HNSW_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    if (!s || s->shards.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
+    if (!s || s->grp.members.empty()) return fail(HNSW_ERR_BAD_ARG, "null hnsw_sharded");
     int rc;
     if (f && (rc = check_sharded_filter(s, f))) return rc;
     return sharded_range(s, nq, out, [&](int g, hnsw_range_result **r) {
-        hnsw_index *idx = s->shards[(size_t)g];
+        hnsw_index *idx = s->grp[(size_t)g];
         return (int)(f ? hnsw_range_brute_force_batch_filtered(idx, f->parts[(size_t)g], queries, nq, q_stride, radius, r)
                        : hnsw_range_brute_force_batch(idx, queries, nq, q_stride, radius, r));
     });
 }
 
-int32_t hnsw_sharded_range_result_size(const hnsw_sharded_range_result *r, int64_t *nq, int64_t *total) {
-    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
-    if (nq) *nq = r->nq;
-    if (total) *total = r->total;
-    return HNSW_OK;
-}
-
+// the result's functions (the bodies: RangeRecord, hnsw_internal.h)
+int32_t hnsw_sharded_range_result_size(const hnsw_sharded_range_result *r, int64_t *nq, int64_t *total) { return RangeRecord<int64_t>::size(r, nq, total); }
 int32_t hnsw_sharded_range_result_fetch(hnsw_sharded_range_result *r, int64_t *lims, int64_t *ids, float *dist, uint32_t *out_ndist,
                                         uint32_t *out_nhops, uint32_t *out_stage) {
-    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
-    if (!lims && !ids && !dist && !out_ndist && !out_nhops && !out_stage) return HNSW_OK;
-    HIP_TRY(hipSetDevice(r->device));
-    if (lims) HIP_TRY(hipMemcpy(lims, r->lims.p, (size_t)(r->nq + 1) * 8, hipMemcpyDeviceToHost));
-    if (ids && r->total > 0) HIP_TRY(hipMemcpy(ids, r->ids.p, (size_t)r->total * 8, hipMemcpyDeviceToHost));
-    if (dist && r->total > 0) HIP_TRY(hipMemcpy(dist, r->dist.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
-    if (r->nq > 0) {
-        if (out_ndist) HIP_TRY(hipMemcpy(out_ndist, r->nd.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
-        if (out_nhops) HIP_TRY(hipMemcpy(out_nhops, r->nh.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
-        if (out_stage) HIP_TRY(hipMemcpy(out_stage, r->stage.p, (size_t)r->nq * 4, hipMemcpyDeviceToHost));
-    }
-    return HNSW_OK;
+    return RangeRecord<int64_t>::fetch(r, lims, ids, dist, out_ndist, out_nhops, out_stage);
 }
-
 int32_t hnsw_sharded_range_result_device(hnsw_sharded_range_result *r, const int64_t **d_lims, const int64_t **d_ids, const float **d_dist) {
-    if (!r) return fail(HNSW_ERR_BAD_ARG, "null result");
-    if (d_lims) *d_lims = (const int64_t *)r->lims.p;
-    if (d_ids) *d_ids = (const int64_t *)r->ids.p;
-    if (d_dist) *d_dist = (const float *)r->dist.p;
-    return HNSW_OK;
+    return RangeRecord<int64_t>::device_pointers(r, d_lims, d_ids, d_dist);
 }
-
-int32_t hnsw_sharded_range_result_destroy(hnsw_sharded_range_result *r) {
-    delete r;
-    return HNSW_OK;
-}
+int32_t hnsw_sharded_range_result_destroy(hnsw_sharded_range_result *r) { delete r; return HNSW_OK; }
 
 int32_t hnsw_merge_segments(int32_t device, int32_t n_lists, int64_t nq, const int64_t *const *lims, const int32_t *const *ids,
                             const float *const *dist, const int64_t *first_row, int32_t id_base, hnsw_sharded_range_result **out) {
@@ -916,44 +849,37 @@ int32_t hnsw_merge_segments(int32_t device, int32_t n_lists, int64_t nq, const i
     if (n_lists < 1 || n_lists > MERGE_LISTS) return fail(HNSW_ERR_BAD_ARG, "n_lists=%d must be in 1..64", n_lists);
     if (nq < 0 || nq > 0x7FFFFFFFLL) return fail(HNSW_ERR_BAD_ARG, "nq=%lld out of range", (long long)nq);
     if (!lims || !first_row) return fail(HNSW_ERR_BAD_ARG, "null buffer");
-    hnsw_dev::SegArgs a{};
-    a.nq = nq;
-    a.n_lists = n_lists;
-    std::vector<int64_t> totals((size_t)n_lists);
-    int64_t sum = 0;
+    SegPlan plan;
     for (int g = 0; g < n_lists; ++g) {
         if (g > 0 && first_row[g] < first_row[g - 1]) return fail(HNSW_ERR_BAD_ARG, "first_row must be non-decreasing (list %d)", g);
         if (!lims[g]) return fail(HNSW_ERR_BAD_ARG, "lims[%d] is null", g);
-        if (lims[g][0] != 0) return fail(HNSW_ERR_BAD_ARG, "lims[%d] must start at 0", g);
-        for (int64_t q = 0; q < nq; ++q)
-            if (lims[g][q + 1] < lims[g][q]) return fail(HNSW_ERR_BAD_ARG, "lims[%d] must be non-decreasing (query %lld)", g, (long long)q);
+        int64_t q = 0;
+        switch (check_lims(lims[g], nq, &q)) {
+        case LIMS_START: return fail(HNSW_ERR_BAD_ARG, "lims[%d] must start at 0", g);
+        case LIMS_DECREASE: return fail(HNSW_ERR_BAD_ARG, "lims[%d] must be non-decreasing (query %lld)", g, (long long)q);
+        case LIMS_OK: break;
+        }
         const int64_t t = lims[g][nq];
         if (t > 0 && (!ids || !dist || !ids[g] || !dist[g])) return fail(HNSW_ERR_BAD_ARG, "list %d has entries and no ids or distances", g);
-        if (t > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "list %d has %lld entries: more than 2^31 - 1", g, (long long)t);
-        a.base[g] = sum;
-        a.first_row[g] = first_row[g];
-        sum += totals[(size_t)g] = t;
+        if (plan.add(t, first_row[g])) return seg_list_too_long(g, t);
     }
-    if (sum > 0x7FFFFFFFLL) return fail(HNSW_ERR_UNSUPPORTED, "%lld merged results: more than 2^31 - 1 in one call", (long long)sum);
+    if (plan.close()) return seg_sum_too_long(plan);
     HIP_TRY(hipSetDevice(device));
-    const size_t lbytes = (size_t)(nq + 1) * 8;
+    const size_t lbytes = (size_t)(nq + 1) * 8, ebytes = (size_t)std::max<int64_t>(plan.sum, 1) * 4;
     DevBuf dLims, dIds, dDist;
     int rc;
-    if ((rc = dLims.ensure((size_t)n_lists * lbytes)) || (rc = dIds.ensure((size_t)std::max<int64_t>(sum, 1) * 4)) ||
-        (rc = dDist.ensure((size_t)std::max<int64_t>(sum, 1) * 4)))
-        return rc;
+    if ((rc = dLims.ensure((size_t)n_lists * lbytes)) || (rc = dIds.ensure(ebytes)) || (rc = dDist.ensure(ebytes))) return rc;
     for (int g = 0; g < n_lists; ++g) {
         HIP_TRY(hipMemcpy((char *)dLims.p + (size_t)g * lbytes, lims[g], lbytes, hipMemcpyHostToDevice));
-        if (totals[(size_t)g] == 0) continue;
-        HIP_TRY(hipMemcpy((int32_t *)dIds.p + a.base[g], ids[g], (size_t)totals[(size_t)g] * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy((float *)dDist.p + a.base[g], dist[g], (size_t)totals[(size_t)g] * 4, hipMemcpyHostToDevice));
+        if (plan.total[g] == 0) continue;
+        HIP_TRY(hipMemcpy((int32_t *)dIds.p + plan.base[g], ids[g], (size_t)plan.total[g] * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((float *)dDist.p + plan.base[g], dist[g], (size_t)plan.total[g] * 4, hipMemcpyHostToDevice));
     }
-    a.lims = (const int64_t *)dLims.p;
-    a.ids = (const int32_t *)dIds.p;
-    a.dist = (const float *)dDist.p;
     std::unique_ptr<hnsw_sharded_range_result> r(new hnsw_sharded_range_result());
     DevBuf flags;
-    if ((rc = merge_segments_on_device(device, nullptr, a, totals, nullptr, nullptr, nullptr, flags, r.get()))) return rc;   // (the null stream: behind the copies)
+    if ((rc = merge_segments_on_device(device, nullptr, plan, nq, (const int64_t *)dLims.p, (const int32_t *)dIds.p, (const float *)dDist.p, nullptr, nullptr,
+                                       nullptr, flags, r.get())))       // (the null stream: behind the copies)
+        return rc;
     *out = r.release();
     return HNSW_OK;
 }

@@ -125,33 +125,41 @@ private:
     int64_t n_ = 0;
 };
 
-// What a range call returns (hnsw_range_result), resident on the device of its index: lims [nq + 1], ids and distances [total];
-// query q's segment is [lims[q], lims[q + 1]), ascending under (distance, id).  Owns its device buffers; any number may be alive.
-class RangeResult {
+// What a range call returns, resident on one device: lims [nq + 1], ids and distances [total]; query q's segment is [lims[q],
+// lims[q + 1]), ascending under (distance, id).  Owns its device buffers; any number may be alive.  Id and R: the id type and the
+// ABI's result type, whose four functions follow.
+template <class Id, class R, int32_t (*Size)(const R *, int64_t *, int64_t *),
+          int32_t (*Fetch)(R *, int64_t *, Id *, float *, uint32_t *, uint32_t *, uint32_t *),
+          int32_t (*Device)(R *, const int64_t **, const Id **, const float **), int32_t (*Destroy)(R *)>
+class RangeResultOf {
 public:
     static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
-    struct Host { std::vector<int64_t> lims; std::vector<int32_t> ids; std::vector<float> dist; std::vector<uint32_t> ndist, nhops, stage; };
-    explicit RangeResult(hnsw_range_result *r) : r_(r) {}
-    RangeResult(const RangeResult &) = delete;
-    RangeResult &operator=(const RangeResult &) = delete;
-    RangeResult(RangeResult &&o) noexcept : r_(o.r_) { o.r_ = nullptr; }
-    ~RangeResult() { if (r_) hnsw_range_result_destroy(r_); }
-    hnsw_range_result *handle() const { return r_; }
-    int64_t nq() const { int64_t a = 0, b = 0; check(hnsw_range_result_size(r_, &a, &b)); return a; }
-    int64_t total() const { int64_t a = 0, b = 0; check(hnsw_range_result_size(r_, &a, &b)); return b; }
-    // everything on the host (hnsw_range_result_fetch)
+    struct Host { std::vector<int64_t> lims; std::vector<Id> ids; std::vector<float> dist; std::vector<uint32_t> ndist, nhops, stage; };
+    explicit RangeResultOf(R *r) : r_(r) {}
+    RangeResultOf(const RangeResultOf &) = delete;
+    RangeResultOf &operator=(const RangeResultOf &) = delete;
+    RangeResultOf(RangeResultOf &&o) noexcept : r_(o.r_) { o.r_ = nullptr; }
+    ~RangeResultOf() { if (r_) Destroy(r_); }
+    R *handle() const { return r_; }
+    int64_t nq() const { int64_t a = 0, b = 0; check(Size(r_, &a, &b)); return a; }
+    int64_t total() const { int64_t a = 0, b = 0; check(Size(r_, &a, &b)); return b; }
+    // everything on the host (the _fetch function)
     Host fetch() const {
         const size_t n = (size_t)nq(), t = (size_t)total();
-        Host h{std::vector<int64_t>(n + 1, 0), std::vector<int32_t>(t), std::vector<float>(t), std::vector<uint32_t>(n), std::vector<uint32_t>(n),
+        Host h{std::vector<int64_t>(n + 1, 0), std::vector<Id>(t), std::vector<float>(t), std::vector<uint32_t>(n), std::vector<uint32_t>(n),
                std::vector<uint32_t>(n)};
-        check(hnsw_range_result_fetch(r_, h.lims.data(), h.ids.data(), h.dist.data(), h.ndist.data(), h.nhops.data(), h.stage.data()));
+        check(Fetch(r_, h.lims.data(), h.ids.data(), h.dist.data(), h.ndist.data(), h.nhops.data(), h.stage.data()));
         return h;
     }
-    // borrowed device pointers, valid while this object lives (hnsw_range_result_device)
-    void device(const int64_t **d_lims, const int32_t **d_ids, const float **d_dist) const { check(hnsw_range_result_device(r_, d_lims, d_ids, d_dist)); }
+    // borrowed device pointers, valid while this object lives (the _device function)
+    void device(const int64_t **d_lims, const Id **d_ids, const float **d_dist) const { check(Device(r_, d_lims, d_ids, d_dist)); }
 private:
-    hnsw_range_result *r_ = nullptr;
+    R *r_ = nullptr;
 };
+// ... of one index (hnsw_range_result): int32 ids, on the index's device
+using RangeResultBase = RangeResultOf<int32_t, hnsw_range_result, hnsw_range_result_size, hnsw_range_result_fetch, hnsw_range_result_device,
+                                      hnsw_range_result_destroy>;
+class RangeResult : public RangeResultBase { using RangeResultBase::RangeResultBase; };
 
 // The sq8 copy of an index (hnsw_index_set_option(h, "sq8_rows", 1)): x ~ lo + scale * code; codes: [n][d] bytes.  Throws
 // std::invalid_argument when the index has no such copy.
@@ -509,33 +517,9 @@ private:
 
 // What a sharded range call and merge_segments return (hnsw_sharded_range_result): as RangeResult with int64 global ids, on the
 // first device of its Sharded, which it outlives.
-class ShardedRangeResult {
-public:
-    static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
-    struct Host { std::vector<int64_t> lims, ids; std::vector<float> dist; std::vector<uint32_t> ndist, nhops, stage; };
-    explicit ShardedRangeResult(hnsw_sharded_range_result *r) : r_(r) {}
-    ShardedRangeResult(const ShardedRangeResult &) = delete;
-    ShardedRangeResult &operator=(const ShardedRangeResult &) = delete;
-    ShardedRangeResult(ShardedRangeResult &&o) noexcept : r_(o.r_) { o.r_ = nullptr; }
-    ~ShardedRangeResult() { if (r_) hnsw_sharded_range_result_destroy(r_); }
-    hnsw_sharded_range_result *handle() const { return r_; }
-    int64_t nq() const { int64_t a = 0, b = 0; check(hnsw_sharded_range_result_size(r_, &a, &b)); return a; }
-    int64_t total() const { int64_t a = 0, b = 0; check(hnsw_sharded_range_result_size(r_, &a, &b)); return b; }
-    // everything on the host (hnsw_sharded_range_result_fetch)
-    Host fetch() const {
-        const size_t n = (size_t)nq(), t = (size_t)total();
-        Host h{std::vector<int64_t>(n + 1, 0), std::vector<int64_t>(t), std::vector<float>(t), std::vector<uint32_t>(n), std::vector<uint32_t>(n),
-               std::vector<uint32_t>(n)};
-        check(hnsw_sharded_range_result_fetch(r_, h.lims.data(), h.ids.data(), h.dist.data(), h.ndist.data(), h.nhops.data(), h.stage.data()));
-        return h;
-    }
-    // borrowed device pointers, valid while this object lives (hnsw_sharded_range_result_device)
-    void device(const int64_t **d_lims, const int64_t **d_ids, const float **d_dist) const {
-        check(hnsw_sharded_range_result_device(r_, d_lims, d_ids, d_dist));
-    }
-private:
-    hnsw_sharded_range_result *r_ = nullptr;
-};
+using ShardedRangeResultBase = RangeResultOf<int64_t, hnsw_sharded_range_result, hnsw_sharded_range_result_size, hnsw_sharded_range_result_fetch,
+                                             hnsw_sharded_range_result_device, hnsw_sharded_range_result_destroy>;
+class ShardedRangeResult : public ShardedRangeResultBase { using ShardedRangeResultBase::ShardedRangeResultBase; };
 
 // One data set PARTITIONED over several GPUs (hnsw_sharded_*): shard g holds the rows [first_row(g), first_row(g + 1)) with a graph
 // of its own on devices[g]; every query visits all shards and the per-shard answers are merged on devices[0] under (distance,

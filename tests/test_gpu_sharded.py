@@ -378,3 +378,41 @@ def test_cpp_front_end_sharded(H):
     assert os.path.exists(exe), "run __graft_entry__.build() first"
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "sharded front-end ok" in out.stdout, out.stdout + out.stderr
+
+
+# ---- 9. the device group's lifetime ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("released_first", ["sharded", "multi"])
+def test_two_device_groups_side_by_side_and_released_in_either_order(H, released_first):
+    """A sharded and a replicated handle on one device (three shards, two replicas: each a device group with streams, events and
+    buffers of its own), called alternately: every round gives round one's bits -- the multi rows hnsw_search_batch's on the
+    unsharded graph (7 queries over 2 replicas: the unequal-shard copies), the sharded rows the merge of the shards' own rows --
+    and after either handle is released, once or twice, the other still does."""
+    rng = np.random.default_rng(23)
+    X = rng.random((300, 8), dtype=np.float32)
+    Q = rng.random((7, 8), dtype=np.float32)
+    ef, k = 16, 5
+    hg = H.Ohnsw.build_batch_bigarray(X, M, EFC, seed=SEED).export()
+    s = H.ShardedHgraph.build(X, M, EFC, [0, 0, 0], seed=SEED)
+    m = H.MultiHgraph(hg, [0, 0])
+    try:
+        ids, dist, first_row, _, _ = _shard_rows(H, s, Q, ef, k, H.FILL_OHNSW, H.SEM_OHNSW)
+        want = {"sharded": np_merge(ids, dist, first_row, k, s.id_base, H.FILL_OHNSW), "multi": H._search(hg, Q, ef, k, H.FILL_OHNSW)}
+        call = {"sharded": lambda: s.knn_batch(Q, ef, k), "multi": lambda: m.knn_batch_bigarray(k, Q, ef=ef)}
+        handle = {"sharded": s, "multi": m}
+        round_one = {}
+        for r in range(3):
+            for name in ("sharded", "multi"):
+                got = call[name]()
+                _same(got, want[name], "%s round %d" % (name, r))
+                _same(got, round_one.setdefault(name, got), "%s round %d against round one" % (name, r))
+        survivor = "multi" if released_first == "sharded" else "sharded"
+        for _ in range(2):                                      # (the second release finds nothing to do)
+            handle[released_first].release()
+            _same(call[survivor](), round_one[survivor], "%s after the other's release" % survivor)
+        for _ in range(2):
+            handle[survivor].release()
+    finally:
+        s.release()
+        m.release()
+        hg.release()

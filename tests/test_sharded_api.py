@@ -127,3 +127,16 @@ def test_merge_lists_checks_its_ranges_on_the_host(H):
     assert call(first_row=down) == H.ERR_BAD_ARG                # first_row must be non-decreasing
     assert call(nq=0) == H.OK                                   # a no-op: no device is touched
     assert call(nq=0, i=None) == H.OK
+
+
+def test_shard_plan_against_a_naive_restatement(tmp_path):
+    """shard_lo, cut_mask, SegPlan and check_lims (hnsw_shard_plan.h: the partition bound, the cut of a global mask into per-shard
+    masks, the segment merge's bases and its two refusals, the lims validation): tests/cpp/test_shard_plan.cpp, a host program,
+    under AddressSanitizer and UndefinedBehaviorSanitizer"""
+    import subprocess
+    exe = str(tmp_path / "test_shard_plan")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "cpp", "test_shard_plan.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    done = re.search(r"shard plan ok: (\d+) cases, 0 differ", out.stdout)
+    assert out.returncode == 0 and done and int(done.group(1)) > 0, out.stdout + out.stderr
