@@ -204,8 +204,18 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   walk first (a descent pre-pass + a sort decide the order; per-query results are
  *                   unchanged, the long walks start first and the launch's drain phase gets shorter):
  *                   -1 = automatic (default), 0 = never, 1 = always;
+ *   "head_queries"  hnsw_search_batch on a page-locked query matrix, where the batch would be ordered and is a plain
+ *                   knn walk (no "refine", no "sq8_rows"): the first H rows of the batch are searched unordered by a
+ *                   launch of their own on a second stream, whose waves fetch their queries over the link themselves,
+ *                   while the pre-pass of the other rows waits for the link; the two parts join at the end of the
+ *                   call.  -1 = automatic (default: batches of at least 1.2 times the queries the device holds at once
+ *                   give 0.3 to 0.5 of their rows to the head), 0 = never, > 0 = H (at most nq - 1).  Ignored by every
+ *                   other call;
  *   "time_kernels"  1 = bracket the launches of every hnsw_search_batch_device call with HIP events
- *                   on the caller's stream (read back with hnsw_index_kernel_times);
+ *                   on the caller's stream (read back with hnsw_index_kernel_times).  A hnsw_search_batch call that
+ *                   splits off a head ("head_queries") times its other rows: the pre-pass and the search figure
+ *                   are theirs, the head's launch runs beside both on its own stream -- bytes of ALL nq queries
+ *                   over that search figure read high by about nq / (nq - H);
  *   "lds_pad"       LDS bytes a search workgroup asks for beyond its own (how many queries a CU holds
  *                   at once in a batch larger than the device holds): -1 = automatic (default);
  *   "scan_slabs"    into how many row slabs hnsw_brute_force_batch cuts the table (1..1024; 0 = automatic, the default);

@@ -695,6 +695,17 @@ int HostInput::upload(hipStream_t st) const {
 //    out.  What is left of the call is one launch and one synchronisation.
 //  * STAGED: the rest goes through the handle's scratch by hipMemcpyAsync.  (Chunks on two streams to overlap copies and search
 //    measured 1.08 against 1.06 ms in round 1.)
+// The knn call (hnsw_search_batch) on queries IN PLACE, where the batch would be ordered, runs in TWO parts (option "head_queries",
+// head_rows): the step is roughly "arrival of the last query over the link + the longest walk", and during the pre-pass --
+// descent waves waiting for their queries: 0.1 ms of a 10 k batch -- the chip is almost empty.  So rows [0, H) are the HEAD: one
+// plain, unordered launch on hs[1] with nothing in front of it, each wave fetching its own query, descending and walking while the
+// link is the bottleneck; rows [H, nq) go through the ordered sequence on hs[0] as a batch of their own (qmap, q_limit, LDS
+// padding and priorities are those of nq - H queries; the staged copy is their part of scratch.q).  The ordered launch then shares
+// the chip with H fewer walks and has fewer late starters or none.  The parts meet at the END only: the host synchronises hs[1]
+// before finish queues its download on hs[0] and synchronises that, so a staged counter array is copied behind both parts; both
+// launches store into the one hFlag word and knn_repair runs on the whole batch behind the synchronisation.  No cross-stream
+// edge anywhere in the call (profiles/r06_split_ab.txt paid for those).  An error in either part drains both streams before the
+// call returns.  Measured: profiles/head_split_ab.txt.
 // Every allocation is made before the first asynchronous copy is queued (a further input, as hnsw_rerank_batch's candidates, is
 // resolved before begin and uploaded after it); once one is queued no return without a synchronisation: it reads or writes the
 // caller's arrays.
@@ -1124,6 +1135,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         return HNSW_OK;
     }
     if (!strcmp(name, "order_queries")) { idx->order_mode = value < 0 ? -1 : (value ? 1 : 0); return HNSW_OK; }
+    if (!strcmp(name, "head_queries")) { idx->head_queries = std::max<int64_t>(-1, std::min<int64_t>(value, 0x7FFFFFFF)); return HNSW_OK; }
     if (!strcmp(name, "scan_slabs")) { idx->scan_slabs = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1024)); return HNSW_OK; }
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }
@@ -1139,7 +1151,7 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
         {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
         {"sq8_rows", idx->sq8_on ? 1 : 0}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
-        {"order_queries", idx->order_mode}, {"scan_slabs", idx->scan_slabs}, {"filter_collect", idx->filter_collect ? 1 : 0}};
+        {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }
@@ -1173,6 +1185,27 @@ int32_t hnsw_index_kernel_times(hnsw_index *idx, double *search_ms, double *prep
     return HNSW_OK;
 }
 
+// Option "head_queries": how many rows [0, H) of a host call's batch are searched as its HEAD (hnsw_search_batch), 0 = none.
+// Only where the call reads its query matrix in place, would order the whole batch, and is a plain knn walk (no re-rank: refine,
+// sq8 rows).  -1: H_AUTO below.
+int64_t head_rows(hnsw_index *idx, const hnsw_search_params *p, int64_t nq) {
+    if (idx->head_queries == 0 || nq < 2 || refine_count(idx, p) > 0 || idx->info.row_format == HNSW_ROWS_SQ8) return 0;
+    const Residency res = resident_queries(idx, knn_shape(idx, p->ef, p->semantics));
+    const int mode = idx->order_mode;
+    if (mode == 0 || (mode != 1 && 2 * nq <= res.queries)) return 0;          // the batch would not be ordered
+    if (idx->head_queries > 0) return std::min<int64_t>(idx->head_queries, nq - 1);
+    if (res.per_cu <= 0) return 0;
+    // H_AUTO (profiles/head_split_ab.txt, byte rows at ef 128, R = 8192): a batch the chip holds at once loses 4-6 % to a head
+    // of any size -- its walks take slots and memory requests from the descent waves and there are no late starters to save --;
+    // with nq - R late starters the split wins, 3 % at nq = 1.2 R and 8-10 % from 1.5 R on.  So: only when the late starters are a
+    // fifth of R or more; then the head that leaves the ordered part a whole number of passes of R, if that head is 0.3 to 0.5
+    // of the batch (more loses again: the descent starves), else 0.3 of the batch.
+    const int64_t R = res.queries;
+    if (5 * (nq - R) < R) return 0;
+    const int64_t passes = (7 * nq / 10) / R, h = nq - passes * R;
+    return passes >= 1 && 2 * h <= nq ? h : 3 * nq / 10;
+}
+
 int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
                           const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
                           uint32_t *out_ndist, uint32_t *out_nhops) {
@@ -1192,7 +1225,30 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
     hipStream_t st = idx->hs[0];
     c.b.any_flag = idx->hFlagDev;
     *(volatile uint32_t *)idx->hFlag = 0;
-    rc = knn_search(idx, params, c.b, st, q_in_place ? (float *)idx->scratch.q.p : nullptr);
+    // The head of the batch (head_rows; the comment above HostCall::begin): a plain launch on hs[1] in which every wave reads its
+    // own query over the link, descends and walks -- nothing in front of it, so its walks run while the main part's pre-pass waits
+    // for the link -- and the ordered sequence on hs[0] for the rows behind it; the two meet at the end only.
+    const int64_t H = q_in_place ? head_rows(idx, params, nq) : 0;
+    if (H > 0) {
+        if (!idx->hs[1]) HIP_TRY(hipStreamCreateWithFlags(&idx->hs[1].h, hipStreamNonBlocking));
+        KnnBatch head = c.b, rest = c.b;
+        head.nq = H;
+        rest.nq = nq - H; rest.Q += H * q_stride; rest.ids += H * params->k; rest.dist += H * params->k;
+        rest.nd += H; rest.nh += H; rest.st += H;
+        const KnnShape sh = knn_shape(idx, params->ef, params->semantics);
+        rc = launch_search_args(idx, sh, knn_args(*params, head, knn_vt_bits(idx, sh), knn_blk_bits(idx, sh)), idx->hs[1]);
+        if (!rc) {
+            const int mode = idx->order_mode;
+            idx->order_mode = 1;            // (the whole batch would be ordered: so is the part)
+            rc = knn_search(idx, params, rest, st, (float *)idx->scratch.q.p + H * q_stride);
+            idx->order_mode = mode;
+        }
+        // the join, from the host (cheaper than an event hs[0] waits for: profiles/head_split_ab.txt): the head, which began
+        // 0.1 ms before the ordered launch, has ended long before it; finish's download is queued behind this
+        const hipError_t eh = hipStreamSynchronize(idx->hs[1]);
+        if (!rc && eh != hipSuccess) rc = fail(HNSW_ERR_HIP, "search failed: %s", hipGetErrorString(eh));
+    } else
+        rc = knn_search(idx, params, c.b, st, q_in_place ? (float *)idx->scratch.q.p : nullptr);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     if ((rc = c.finish(idx, "search", st))) return rc;
     if (*(volatile uint32_t *)idx->hFlag & 1u) {      // (the flag: written by the kernel, pinned host memory)

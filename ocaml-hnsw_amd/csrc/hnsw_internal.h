@@ -468,6 +468,9 @@ struct hnsw_index {
     struct OrderScratch { hipStream_t st; hnsw_host::Table block; };
     std::vector<OrderScratch> order_scratch;
     int order_mode = -1;                 // option "order_queries": -1 automatic (batches larger than half of what the chip holds: resident_queries), 0 never, 1 always
+    // option "head_queries": rows [0, H) of a host call's batch searched unordered on hs[1] while the rest's pre-pass runs
+    // (head_rows, hnsw_capi.hip): -1 automatic, 0 never, > 0 that many (at most nq - 1)
+    int64_t head_queries = -1;
     int vt_bits_override = 0;
     int lds_pad = -1;                    // option "lds_pad": extra LDS bytes per search wave (-1 = balanced_lds_pad's choice)
     int scan_slabs = 0;                  // option "scan_slabs": row slabs of the exact scans (0 = scan_slab_rows' choice)
