@@ -102,8 +102,57 @@ enum {
 };
 
 enum { HNSW_METRIC_L2 = 0,  /* sqrt(sum (a_i-b_i)^2)                                     */
-       HNSW_METRIC_IP = 1 };/* 1 - <a,b>  (new: the reference has Euclidean only,
+       HNSW_METRIC_IP = 1,  /* 1 - <a,b>  (new: the reference has Euclidean only,
                                benchmark/dataset.ml:6-13; extension point = DISTANCE sig) */
+       HNSW_METRIC_COSINE = 2 };/* 1 - <a,b> / (|a| |b|): the index normalises what it is handed (below) */
+
+/* ---- cosine distance as a metric the index owns ---------------------------------------------------------------------------------
+ * THE NORMALISER N.  N(x) is a float32 row that is a function of the row's d values only -- not of its row number, stride,
+ * alignment, batch size or of where the matrix lies (device memory, a page-locked host matrix read in place):
+ *   s = <x,x> summed in float32 on the distance kernels' own lane grid: with NCH = the smallest of 1, 2, 4, 8, 16 that is
+ *       >= ceil(ceil(d / 4) / 16), lane l (0..15) starts from 0 and adds, for i = 0 .. NCH - 1 in this order, the four values of
+ *       chunk c = 16 i + l (dimensions 4c .. 4c + 3, in this order; dimensions >= d count as 0), each as one fused multiply-add
+ *       acc = fma(v, v, acc); the 16 partial sums p are then added as p[j] += p[j + 8 mod 16]; p[j] += p[j + 4 mod 16];
+ *       p[j] += p[j + 2 mod 16]; p[j] += p[j + 1 mod 16] (the order of every distance of this library);
+ *   norm = sqrt(s), correctly rounded;  N(x)_i = x_i / norm, one correctly rounded division each.
+ *   A row whose sum of squares is 0 becomes all zeros, its norm reads 0, and its cosine distance to everything is 1.
+ *   A row whose sum of squares is NaN or infinite becomes all NaN (its norm reads as s).
+ * hnsw_normalise_batch is N as an operator of its own (it needs no index): host arrays in ([n][in_stride], in_stride >= d) and out
+ *   ([n][out_stride], out_stride >= d; only the d values of a row are written), out_norms [n] or NULL.  out may be in with the
+ *   same stride (in == out with different strides: HNSW_ERR_BAD_ARG); otherwise the two arrays must not overlap.  n == 0 is
+ *   HNSW_OK; d in 1..1024, d > 1024: HNSW_ERR_UNSUPPORTED; a null in / out, n < 0, d < 1 or a stride < d: HNSW_ERR_BAD_ARG.
+ *
+ * THE TWIN CONTRACT.  A COSINE index over X answers every call on queries Q with exactly the bits (ids, distances, counters,
+ * stages, graph links) of an IP index over N(X) called with N(Q).  What follows from it:
+ *   * the index stores N(X) as its float32 rows; the rows as handed over are not kept on the device.  hnsw_index_get_rows returns
+ *     what a handle holds;
+ *   * hnsw_index_create, hnsw_build and hnsw_index_insert normalise the data they are handed and refuse the whole call, all or
+ *     nothing, with HNSW_ERR_BAD_ARG when a data row's sum of squares is not finite (the message names the first such row);
+ *     zero rows are accepted.  hnsw_index_insert takes params->metric = HNSW_METRIC_COSINE, as the index's;
+ *   * every call that takes queries or targets (the knn searches in all their forms, hnsw_distance_batch, the exact scans,
+ *     hnsw_rerank_batch, the filtered and the range calls, the layer operators, hnsw_select_neighbours_batch, the sharded calls)
+ *     normalises them exactly once, on the device, on the call's stream, into scratch of the handle: the caller's matrix is
+ *     not written.  A host call reads a page-locked matrix in place for that and then runs on the device-resident copy: it takes
+ *     no head split (option "head_queries" has no effect).  The device forms keep one scratch matrix of the batch's size per
+ *     caller stream they have been called on, for the life of the handle (as the ordering pre-pass keeps its block): a caller
+ *     that makes a stream per request grows the handle with every new stream -- reuse a few streams.  A batch larger than any
+ *     before on its stream allocates (hipMalloc) inside the call, so a COSINE device form cannot be recorded by a stream capture
+ *     unless a call of that size on that stream came before it;
+ *   * hnsw_index_save writes the stored rows with metric 2 (the file format stays 2); on hnsw_index_load the rows are not
+ *     normalised again: N(N(x)) is not N(x) bit for bit;
+ *   * hnsw_index_info.metric and hnsw_sharded_get_info report 2; the shards of an hnsw_sharded agree on it as on any metric;
+ *   * options "split_rows", "half_rows", "sq8_rows", "refine", "visited_blocks", "filter_collect" behave as for the IP twin
+ *     (byte rows only where N(X) happens to be byte-valued, as for the twin);
+ *   * NOT BUILT: hnsw_multi.  hnsw_multi_create refuses a COSINE desc with HNSW_ERR_UNSUPPORTED, "cosine: not built for hnsw_multi".
+ *
+ * hnsw_index_get_rows: the stored float32 rows of the m nodes ids[0..m) (id_base-based; ids NULL: all n rows in order, m must be n)
+ *   into the host array out ([m][out_stride], out_stride >= d; d values per row written).  For every metric and row format (the
+ *   float32 table is always there); for COSINE it is N(X).  An id out of range, m < 0, a null out (m > 0) or out_stride < d:
+ *   HNSW_ERR_BAD_ARG and nothing is written.  m == 0 is HNSW_OK. */
+int32_t hnsw_normalise_batch(int32_t device, const float *in, int64_t n, int32_t d, int64_t in_stride, float *out, int64_t out_stride,
+                             float *out_norms /* may be NULL */);
+int32_t hnsw_index_get_rows(const hnsw_index *idx, const int64_t *ids /* NULL: all n rows in order, m must be n */, int64_t m,
+                            float *out, int64_t out_stride);
 
 enum { HNSW_FILL_OHNSW = 0, /* missing results: id -1, distance NaN  (lib/ohnsw.ml:880-881) */
        HNSW_FILL_BA = 1 };  /* missing results: id -1, distance +inf (lib/hnsw.ml:771)      */

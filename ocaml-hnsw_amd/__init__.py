@@ -24,6 +24,9 @@ LIB_PATH = _os.environ.get("HNSW_LIB_PATH") or _os.path.join(_PKG_DIR, "libhnsw_
 OK, ERR_BAD_ARG, ERR_EMPTY_INDEX, ERR_DEGREE_OVERFLOW = 0, -1, -2, -3
 ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED = -4, -5, -6, -7
 METRIC_L2, METRIC_IP = 0, 1
+# 1 - <a,b> / (|a| |b|): the index stores N(X) and normalises every query batch itself (the twin contract of the C header); a
+# Hgraph's host copy `vectors` stays the caller's matrix
+METRIC_COSINE = 2
 FILL_OHNSW, FILL_BA = 0, 1
 SEM_OHNSW, SEM_FUNCTOR, SEM_FUNCTOR_NEAREST_K = 0, 1, 2
 # IndexInfo.row_format: what the knn searches read (HNSW_ROWS_*); ROWS_HALF only after set_option("half_rows", 1), ROWS_SQ8 only
@@ -42,6 +45,8 @@ _ABI = {
     "hnsw_index_create": [_vp, _i32, _vp],
     "hnsw_index_destroy": [_vp],
     "hnsw_index_get_info": [_vp, _vp],
+    "hnsw_normalise_batch": [_i32, _vp, _i64, _i32, _i64, _vp, _i64, _vp],
+    "hnsw_index_get_rows": [_vp, _vp, _i64, _vp, _i64],
     "hnsw_index_set_option": [_vp, _str, _i64],
     "hnsw_index_row_bytes": [_vp, _vp],
     "hnsw_index_sq8_params": [_vp, _vp, _vp],
@@ -241,6 +246,20 @@ def _batch(hgraph_d, batch, min_rows=0):
     return Q, max(qs, hgraph_d), Q.shape[0]
 
 
+def normalise(X, device=0, norms=False):
+    """hnsw_normalise_batch: N(X), the rows a METRIC_COSINE index stores for X and searches for a query batch X, as a fresh
+    [n][d] float32 matrix (norms=True: and the norms [n]).  A zero row stays zero (norm 0); a row whose sum of squares is not
+    finite becomes NaN.  What a caller uses to pre-normalise data for other tools, or to build the IP twin of a COSINE index."""
+    A, stride = _rows(X)
+    if A.ndim != 2:
+        raise InvalidArgument("X must be [n][d]")
+    n, d = A.shape
+    out = _np.empty((n, d), _np.float32)
+    nrm = _np.empty(n, _np.float32) if norms else None
+    _check(load().hnsw_normalise_batch(device, _ptr(A), n, d, max(stride, d), _ptr(out), d, _ptr(nrm)))
+    return (out, nrm) if norms else out
+
+
 def _out_pair(nq, k, out):
     """The result matrices (ids, dist) of nq queries: fresh ones, or out = the caller's pair (e.g. pinned matrices it reuses
     batch after batch), which the library fills as nq * k contiguous words each."""
@@ -351,6 +370,19 @@ class Hgraph:
             _check(L.hnsw_index_export_upper(self.handle, l, _ptr(nodes), _ptr(deg), _ptr(nbr)))
             self.upper.append((nodes, deg, nbr))
         return self
+
+    def rows(self, ids=None):
+        """hnsw_index_get_rows: the float32 rows the device index holds for the nodes `ids` (id_base-based; None: all n, in order)
+        as a fresh [m][d] matrix -- for METRIC_COSINE N(X), not the caller's matrix that `vectors` keeps"""
+        if ids is None:
+            m, p = self.info().n, None
+        else:
+            ids = _np.ascontiguousarray(ids, dtype=_np.int64).reshape(-1)
+            m, p = ids.size, _ptr(ids)
+        out = _np.empty((m, self.d), _np.float32)
+        if m:
+            _check(load().hnsw_index_get_rows(self.handle, p, m, _ptr(out), self.d))
+        return out
 
     def locality_codes(self):
         """hnsw_index_locality_codes: the permutation of 0 .. n-1 that keys the visited set's bitmap blocks (introspection)."""
@@ -1002,9 +1034,10 @@ class Ohnsw:
 
     @staticmethod
     def insert_batch(hgraph, batch, num_connections, num_nodes_search_construction, seed=0, max_batch=0, batch_div=0,
-                     expected_ef=0, expected_sem=SEM_OHNSW):
+                     expected_ef=0, expected_sem=SEM_OHNSW, metric=None):
         """Ohnsw.insert (lib/ohnsw.ml:766-837) for every row of `batch`, in order, on the device (hnsw_index_insert): the
-        index grows in place.  -> the new ids (np.int64, n_old + id_base onwards).  Levels are the draws hnsw_build with
+        index grows in place (metric: None = the index's own; another one is refused; a METRIC_COSINE index normalises the new
+        rows itself).  -> the new ids (np.int64, n_old + id_base onwards).  Levels are the draws hnsw_build with
         the same seed gives those positions.  Afterwards the Hgraph follows the device index: n, widths, max_layer and
         entry_point are refreshed, the host vectors (if any) grow by the batch, and deg0 / nbr0 / upper are None until
         export()."""
@@ -1013,7 +1046,7 @@ class Ohnsw:
             raise InvalidArgument("batch must be [m][d] with the index's d = %d" % hgraph.d)
         m = X.shape[0]
         n_old = hgraph.n
-        p = _BuildParams(num_connections, num_nodes_search_construction, hgraph.metric, hgraph.id_base, seed, max_batch,
+        p = _BuildParams(num_connections, num_nodes_search_construction, hgraph.metric if metric is None else int(metric), hgraph.id_base, seed, max_batch,
                          batch_div, expected_ef, expected_sem)
         _check(load().hnsw_index_insert(hgraph.handle, _ptr(X), m, max(xs, hgraph.d), _C.byref(p)))
         if m == 0:

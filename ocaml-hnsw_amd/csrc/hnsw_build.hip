@@ -211,7 +211,7 @@ static int32_t run_batches(BuildView &bv, const uint8_t *lvl, int64_t pos0, int6
 
 // the builder's parameter checks, shared by hnsw_build and hnsw_index_insert
 static int32_t check_build_params(const hnsw_build_params *p) {
-    if (p->metric != HNSW_METRIC_L2 && p->metric != HNSW_METRIC_IP) return fail(HNSW_ERR_BAD_ARG, "bad metric");
+    if (p->metric != HNSW_METRIC_L2 && p->metric != HNSW_METRIC_IP && p->metric != HNSW_METRIC_COSINE) return fail(HNSW_ERR_BAD_ARG, "bad metric");
     const int M = p->num_connections, efc = p->num_nodes_search_construction;
     if (M < 2 || 2 * M > 64) return fail(HNSW_ERR_UNSUPPORTED, "num_connections=%d must be in 2..32", M);
     if (efc < 1 || efc > 512) return fail(HNSW_ERR_UNSUPPORTED, "num_nodes_search_construction=%d must be in 1..512", efc);
@@ -256,6 +256,8 @@ static int32_t build_attempt(const float *vectors, int64_t n, int32_t d, int64_t
 
     if ((rc = alloc_graph_tables(idx->tables, n, stride, S0, SU, rowsU)) ||
         (rc = upload_rows(vectors, n, d, row_stride, (float *)idx->tables.X.p)) || (rc = upload_upper_layout(idx->tables, 0, ref))) return rc;
+    // COSINE: the graph is built over N(X), which is what the table holds from here on
+    if (p->metric == HNSW_METRIC_COSINE && (rc = cosine_store_rows((float *)idx->tables.X.p, n, d, "nothing built"))) return rc;
     iv.stride = stride; iv.n = n; iv.d = d; iv.nchunks = nchunks; iv.S0 = S0; iv.SU = SU; iv.rowsU = rowsU;
     iv.max_layer = 0; iv.entry_point = 0; iv.id_base = p->id_base;
     bind_view(idx.get());
@@ -415,6 +417,8 @@ static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64
         HIP_TRY(hipMemcpy(t.ref.p, ot.ref.p, (size_t)n_old * sizeof(int2), hipMemcpyDeviceToDevice));
     }
     if ((rc = upload_rows(vectors, m, ov.d, row_stride, (float *)t.X.p + n_old * stride))) return rc;
+    // COSINE: the new rows only -- the old ones are N(X) already (row numbers in the message: of the m new vectors)
+    if (idx->info.metric == HNSW_METRIC_COSINE && (rc = cosine_store_rows((float *)t.X.p + n_old * stride, m, ov.d, "nothing inserted"))) return rc;
     HIP_TRY(widen_rows(ot.nbr0.p, n_old, S0o, t.nbr0.p, S0));
     HIP_TRY(widen_rows(ot.nbrU.p, rowsU_old, SUo, t.nbrU.p, SU));
     if ((rc = upload_upper_layout(t, n_old, ref))) return rc;
@@ -539,6 +543,8 @@ int32_t hnsw_select_neighbours_batch(hnsw_index *idx, const float *targets, int6
     }
     if (hipMemcpy(dT.p, targets, tbytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dC.p, c0.data(), c0.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(dN.p, cand_cnt, (size_t)nb * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(HNSW_ERR_HIP, "upload failed");
+    // (COSINE: the uploaded copy becomes N(targets) in place)
+    if (is_cosine(idx) && (rc = cosine_normalise((const float *)dT.p, nb, idx->iv.d, t_stride, (float *)dT.p, t_stride, nullptr, nullptr, nullptr))) return rc;
     SelectOpArgs sa{};
     sa.targets = (const float *)dT.p; sa.t_stride = t_stride; sa.cand = (const int32_t *)dC.p; sa.cand_cnt = (const int32_t *)dN.p;
     sa.cand_stride = cand_stride; sa.nb = (int32_t)nb; sa.R = num_neighbours; sa.keep_all_if_few = keep_all_if_few;
@@ -806,7 +812,7 @@ int32_t hnsw_index_load(const char *path, int32_t device, hnsw_index **out) {
     d.vectors = X.data(); d.n = n; d.d = h.d; d.row_stride = h.d; d.metric = h.metric; d.id_base = h.id_base;
     d.max_degree0 = h.max_degree0; d.max_degree = h.max_degree; d.max_layer = h.max_layer; d.entry_point = h.entry_point;
     d.deg0 = deg0.data(); d.nbr0 = nbr0.data(); d.upper = layers.data();
-    const int rc = hnsw_index_create(&d, device, out);   // re-validates every id and degree
+    const int rc = create_index(&d, device, /*stored_rows=*/true, out);   // re-validates every id and degree; COSINE rows stay as saved
     if (rc) return rc;
     hnsw_index *idx = *out;
     if (!codes.empty()) (void)adopt_locality_codes(idx, codes.data());

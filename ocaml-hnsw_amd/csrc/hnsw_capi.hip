@@ -746,7 +746,14 @@ int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q
     ids = zi && !small ? nullptr : out_ids; dist = zi && !small ? nullptr : out_dist;
     nd = znd && !small ? nullptr : out_nd; nh = znh && !small ? nullptr : out_nh;
     if (q_in_place) *q_in_place = !q.from;
-    return q.upload(idx->hs[0]);
+    if ((rc = q.upload(idx->hs[0])) || !is_cosine(idx)) return rc;
+    // COSINE: the kernels read N(Q) in the handle's scratch, normalised on hs[0] from wherever the queries are (a page-locked
+    // matrix in place, the block, the staged copy): from here on the call is the device-resident one -- no zero-copy reads by the
+    // search, no head split (a failure here waits for the upload: it reads the caller's matrix)
+    int64_t qs = q_stride;
+    if ((rc = cosine_queries(idx, b.Q, nq, q_stride, idx->hs[0], &b.Q, &qs))) (void)hipStreamSynchronize(idx->hs[0]);
+    if (q_in_place) *q_in_place = false;
+    return rc;
 }
 
 int HostCall::finish(hnsw_index *idx, const char *what, hipStream_t st) {
@@ -884,13 +891,17 @@ int32_t hnsw_device_count(int32_t *count) {
     return HNSW_OK;
 }
 
-int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index **out) {
+int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index **out) { return create_index(d, device, false, out); }
+
+} // extern "C"
+
+int hnsw_host::create_index(const hnsw_index_desc *d, int32_t device, bool stored_rows, hnsw_index **out) {
     if (!d || !out) return fail(HNSW_ERR_BAD_ARG, "null argument");
     *out = nullptr;
     if (d->n < 0 || d->n > 0x7FFFFFF0LL) return fail(HNSW_ERR_BAD_ARG, "n=%lld out of range", (long long)d->n);
     if (d->d < 1) return fail(HNSW_ERR_BAD_ARG, "d=%d", d->d);
     if (d->row_stride < d->d) return fail(HNSW_ERR_BAD_ARG, "row_stride < d");
-    if (d->metric != HNSW_METRIC_L2 && d->metric != HNSW_METRIC_IP) return fail(HNSW_ERR_BAD_ARG, "bad metric %d", d->metric);
+    if (d->metric != HNSW_METRIC_L2 && d->metric != HNSW_METRIC_IP && d->metric != HNSW_METRIC_COSINE) return fail(HNSW_ERR_BAD_ARG, "bad metric %d", d->metric);
     if (d->max_degree0 < 1 || d->max_degree0 > 64) return fail(HNSW_ERR_UNSUPPORTED, "max_degree0=%d must be in 1..64", d->max_degree0);
     if (d->max_layer < 0 || d->max_layer > 255) return fail(HNSW_ERR_BAD_ARG, "max_layer=%d", d->max_layer);
     if (d->max_layer > 0 && (d->max_degree < 1 || d->max_degree > 64)) return fail(HNSW_ERR_UNSUPPORTED, "max_degree=%d must be in 1..64", d->max_degree);
@@ -961,6 +972,8 @@ int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index *
     const int64_t stride = padded_stride(d->d);
     int rc = alloc_graph_tables(t, n, stride, S0, SU, rowsU);
     if (!rc) rc = upload_rows(d->vectors, n, d->d, d->row_stride, (float *)t.X.p);
+    // COSINE: the table holds N(X) (rows a handle stored already are N(X): hnsw_index_load)
+    if (!rc && d->metric == HNSW_METRIC_COSINE && !stored_rows) rc = cosine_store_rows((float *)t.X.p, n, d->d, "no index made");
     if (!rc && hipMemcpy(t.nbr0.p, nbr0.data(), nbr0.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNSW_ERR_OOM, "graph upload failed");
     if (!rc && hipMemcpy(t.nbrU.p, nbrU.data(), nbrU.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNSW_ERR_OOM, "graph upload failed");
     if (!rc) rc = upload_upper_layout(t, 0, ref);
@@ -972,6 +985,8 @@ int32_t hnsw_index_create(const hnsw_index_desc *d, int32_t device, hnsw_index *
     inf.d = d->d; inf.metric = d->metric; inf.id_base = base; inf.max_degree = d->max_degree; inf.device = device;
     return finish_index(std::move(idx), d->expected_ef, d->expected_semantics, out);
 }
+
+extern "C" {
 
 int32_t hnsw_index_destroy(hnsw_index *idx) {
     if (!idx) return HNSW_OK;
@@ -1162,6 +1177,12 @@ int32_t hnsw_search_batch_device(hnsw_index *idx, const float *d_queries, int64_
                                  const hnsw_search_params *params, int32_t *d_ids, float *d_dist,
                                  uint32_t *d_ndist, uint32_t *d_nhops, uint32_t *d_status, void *stream) {
     if (idx && idx->n_deleted > 0) return marked_unsupported(idx, "hnsw_search_batch_device");
+    if (idx && is_cosine(idx)) {            // N(Q) on the caller's stream first; everything behind reads the handle's scratch
+        int rc = check_batch(idx, params, nq, q_stride, d_queries && d_ids && d_dist);
+        if (rc || nq == 0) return rc;
+        HIP_TRY(hipSetDevice(idx->device));
+        if ((rc = cosine_queries(idx, d_queries, nq, q_stride, (hipStream_t)stream, &d_queries, &q_stride))) return rc;
+    }
     return knn_search(idx, params, {d_queries, nq, q_stride, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr}, (hipStream_t)stream);
 }
 
@@ -1274,8 +1295,12 @@ int32_t hnsw_search_batch_h2d(hnsw_index *idx, const float *queries, int64_t nq,
     HostInput q;
     if ((rc = q.resolve(queries, qbytes, idx->scratch.q)) || (rc = q.upload(st))) return rc;
     // registered matrix: read by the device directly, the pre-pass (when there is one) leaves the device copy in sQ
-    rc = knn_search(idx, params, {(const float *)q.dev, nq, q_stride, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr},
-                    st, q.from ? nullptr : (float *)idx->scratch.q.p);
+    const float *dq = (const float *)q.dev;
+    const bool cosine = is_cosine(idx);     // N(Q) from the matrix where it lies into the handle's scratch: the search reads that
+    if (cosine) rc = cosine_queries(idx, dq, nq, q_stride, st, &dq, &q_stride);
+    if (!rc)
+        rc = knn_search(idx, params, {dq, nq, q_stride, d_ids, d_dist, d_ndist, d_nhops, d_status, nullptr},
+                        st, q.from || cosine ? nullptr : (float *)idx->scratch.q.p);
     // the call returns while the device still reads the caller's matrix (in place, or as the source of the DMA above): the
     // range remembers it, so that hnsw_host_unregister / hnsw_host_free wait instead of pulling the pages from under a kernel
     range_reader_enqueued(queries, qbytes, st);
@@ -1307,6 +1332,9 @@ int32_t hnsw_search_submit(hnsw_index *idx, const float *queries, int64_t nq, in
         return give_back(fail(HNSW_ERR_HIP, "query upload failed"));
     range_reader_enqueued(queries, qbytes, st);    // page-locked source: the DMA above outlives this call (see hnsw_host_unregister)
     if (hipMemsetAsync(b.any_flag, 0, 4, st) != hipSuccess) return give_back(fail(HNSW_ERR_HIP, "hipMemsetAsync failed"));
+    // COSINE: the request's own copy becomes N(Q) in place, so that hnsw_search_wait's repair reads what the search read
+    if (is_cosine(idx) && (rc = cosine_normalise(b.Q, nq, idx->iv.d, q_stride, (float *)r->buf.q.p, q_stride, nullptr, nullptr, st)))
+        return give_back(rc);
     if ((rc = knn_search(idx, params, b, st, nullptr, &r->refine))) return give_back(rc);
     // the results follow the search on the request's stream: hnsw_search_wait only has to wait for them
     idx->live_requests++;
@@ -1453,6 +1481,9 @@ int32_t hnsw_distance_batch_device(hnsw_index *idx, const float *d_queries, int6
     if (nq < 0 || m < 0 || !d_queries || !d_ids || !d_out) return fail(HNSW_ERR_BAD_ARG, "bad buffers");
     if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
     HIP_TRY(hipSetDevice(idx->device));
+    // (COSINE: N(Q) first, here for the host form too, which uploads its matrix and calls this one)
+    const int rc = cosine_queries(idx, d_queries, nq, q_stride, (hipStream_t)stream, &d_queries, &q_stride);
+    if (rc) return rc;
     const hipError_t e = launch_distance(idx, d_queries, q_stride, nq, d_ids, m, d_out, (hipStream_t)stream);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "distance kernel launch failed: %s", hipGetErrorString(e));
     return HNSW_OK;

@@ -60,7 +60,7 @@ template <int NCH, class F> auto with_nslot_knn(int nslot, F &&f) {
     if constexpr (has_odd_nslot(NCH)) return with_nslot<1, 2, 3, 4, 6, 8, 16>(nslot, f);
     else return with_nslot<1, 2, 4, 8, 16>(nslot, f);
 }
-// f(Int<0>) for HNSW_METRIC_L2, f(Int<1>) for the inner product
+// f(Int<0>) for HNSW_METRIC_L2, f(Int<1>) for the inner product -- and for HNSW_METRIC_COSINE, the inner product over unit rows
 template <class F> auto with_metric(int metric, F &&f) { return metric == HNSW_METRIC_L2 ? f(Int<0>{}) : f(Int<1>{}); }
 
 // The knn kernel's variant objects (hnsw_search_variants.hip compiled once per line): X(metric, accept rule, row format -- see
@@ -467,6 +467,10 @@ struct hnsw_index {
     // stream is ordered, so the block is free again when the next call on that stream needs it)
     struct OrderScratch { hipStream_t st; hnsw_host::Table block; };
     std::vector<OrderScratch> order_scratch;
+    // HNSW_METRIC_COSINE: N(Q) of the batch a call was handed, one matrix per caller stream (cosine_queries, hnsw_cosine.hip); kept
+    // between calls as order_scratch is.  Not an index table: not counted in device_bytes.
+    struct CosineScratch { hipStream_t st; hnsw_host::DevBuf q; };
+    std::vector<CosineScratch> cosine_scratch;
     int order_mode = -1;                 // option "order_queries": -1 automatic (batches larger than half of what the chip holds: resident_queries), 0 never, 1 always
     // option "head_queries": rows [0, H) of a host call's batch searched unordered on hs[1] while the rest's pre-pass runs
     // (head_rows, hnsw_capi.hip): -1 automatic, 0 never, > 0 that many (at most nq - 1)
@@ -554,6 +558,27 @@ void bind_view(::hnsw_index *idx);
 // hnsw_capi.hip: the end of hnsw_index_create and hnsw_build, once the graph tables are complete: the view bound, the row copies
 // made, the first search's one-time costs paid.  *out = idx on success.
 int finish_index(IndexPtr idx, int32_t expected_ef, int32_t expected_semantics, ::hnsw_index **out);
+
+// hnsw_capi.hip: hnsw_index_create; stored_rows: desc->vectors are rows a handle held (hnsw_index_load): a COSINE index takes them
+// as they are -- N is not idempotent bit for bit
+int create_index(const hnsw_index_desc *desc, int32_t device, bool stored_rows, ::hnsw_index **out);
+
+// ---- HNSW_METRIC_COSINE (hnsw_cosine.hip): an IP index over N(X) whose entry points hand N(Q) on --------------------------------
+// The normalise kernel on `st`: out row i = N(in row i) (include/hnsw_mi355x.h), d values per row; pad_rows: index rows, zero from d
+// to the row's end (out_stride = padded_stride(d)).  `in` may be a registered host matrix seen from the device; in == out (same
+// stride) is allowed.  norms (optional, [n]); bad_flag (optional, one word the caller set to 0xFFFFFFFF): the least row whose sum of
+// squares is NaN or infinite.
+int cosine_normalise(const float *in, int64_t n, int d, int64_t in_stride, float *out, int64_t out_stride, float *norms, uint32_t *bad_flag,
+                     hipStream_t st, bool pad_rows = false);
+// ... in place over the m freshly uploaded rows `rows` of an index's float32 table (rows of padded_stride(d) floats), waited for:
+// HNSW_ERR_BAD_ARG ("...: <what>") naming the first row i of the m whose sum of squares is not finite
+int cosine_store_rows(float *rows, int64_t m, int d, const char *what);
+// Where a call reads its queries: the caller's device matrix for L2 and IP (nothing queued); for COSINE the handle's scratch matrix
+// of stream `st`, filled with N(Q) by the kernel queued there (same stride).  Called ONCE per public call, at the entry point,
+// before the first internal consumer: knn_search, scan_search, Ladder, launch_rerank, the range scans, knn_repair and the sq8 query
+// transform all receive an already-normalised device matrix.
+int cosine_queries(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, hipStream_t st, const float **out_Q, int64_t *out_stride);
+inline bool is_cosine(const ::hnsw_index *idx) { return idx->info.metric == HNSW_METRIC_COSINE; }
 
 // hnsw_build.hip: HNSW_ERR_BAD_ARG ("...: <verb>") for a graph whose upper rows list a node that is not on that layer, or whose
 // entry point is not on the top layer: what hnsw_index_insert and hnsw_index_remove ask before they follow the rows (n > 0)

@@ -217,6 +217,9 @@ int32_t hnsw_search_layer_batch(hnsw_index *idx, int32_t layer, const float *tar
         return rc;
     HIP_TRY(hipMemcpy(idx->scratch.q.p, targets, qbytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dStart.p, st.data(), st.size() * 4, hipMemcpyHostToDevice));
+    // (COSINE: the uploaded copy becomes N(targets) in place)
+    if (is_cosine(idx) && (rc = cosine_normalise((const float *)idx->scratch.q.p, nq, idx->iv.d, t_stride, (float *)idx->scratch.q.p, t_stride, nullptr, nullptr, nullptr)))
+        return rc;
 
     LayerSearchArgs a{};
     a.Q = (const float *)idx->scratch.q.p; a.q_stride = t_stride; a.nq = nq;
@@ -260,6 +263,9 @@ int32_t hnsw_search_one_batch(hnsw_index *idx, int32_t layer, const float *targe
         return rc;
     HIP_TRY(hipMemcpy(idx->scratch.q.p, targets, qbytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(idx->scratch.nd.p, st.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
+    // (COSINE: the uploaded copy becomes N(targets) in place)
+    if (is_cosine(idx) && (rc = cosine_normalise((const float *)idx->scratch.q.p, nq, idx->iv.d, t_stride, (float *)idx->scratch.q.p, t_stride, nullptr, nullptr, nullptr)))
+        return rc;
     const hipError_t e = launch_search_one(idx, (const float *)idx->scratch.q.p, t_stride, nq, layer, (const int32_t *)idx->scratch.nd.p, (int32_t *)idx->scratch.ids.p,
                                            (float *)idx->scratch.dist.p);
     if (e != hipSuccess) return fail(HNSW_ERR_HIP, "search_one kernel launch failed: %s", hipGetErrorString(e));

@@ -247,6 +247,8 @@ int32_t hnsw_multi_create(const hnsw_index_desc *desc, const int32_t *devices, i
     if (!desc || !devices || !out) return fail(HNSW_ERR_BAD_ARG, "null argument");
     *out = nullptr;
     if (n_devices < 1 || n_devices > 64) return fail(HNSW_ERR_BAD_ARG, "n_devices=%d must be in 1..64", n_devices);
+    // (the replicas' exchange uploads and searches the caller's queries as they are: no normaliser stands in front of it)
+    if (desc->metric == HNSW_METRIC_COSINE) return fail(HNSW_ERR_UNSUPPORTED, "cosine: not built for hnsw_multi");
     hnsw_multi *m = new hnsw_multi();
     for (int g = 0; g < n_devices; ++g) {
         hnsw_index *idx = nullptr;

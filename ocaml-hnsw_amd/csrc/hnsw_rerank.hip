@@ -140,6 +140,7 @@ int32_t hnsw_rerank_batch_device(hnsw_index *idx, const float *d_queries, int64_
     int rc = check_rerank(idx, nq, q_stride, cand_stride, k, fill, d_queries && d_cand && d_ids && d_dist);
     if (rc || nq == 0) return rc;
     HIP_TRY(hipSetDevice(idx->device));
+    if ((rc = cosine_queries(idx, d_queries, nq, q_stride, (hipStream_t)stream, &d_queries, &q_stride))) return rc;     // (COSINE: N(Q) first)
     return launch_rerank(idx, d_queries, nq, q_stride, d_cand, cand_stride, k, fill, d_ids, d_dist, nullptr, nullptr, (hipStream_t)stream);
 }
 

@@ -286,6 +286,12 @@ int32_t hnsw_brute_force_batch_device(hnsw_index *idx, const float *d_queries, i
                                       int32_t *d_ids, float *d_dist, void *stream) {
     // (while nodes are marked deleted: the k smallest LIVE nodes, the masked scan under the handle's live mask)
     const hnsw_filter *const live = idx ? live_filter(idx) : nullptr;
+    if (idx && is_cosine(idx)) {            // N(Q) on the caller's stream first
+        int rc = check_scan(idx, nq, q_stride, k, fill, d_queries && d_ids && d_dist);
+        if (rc || nq == 0) return rc;
+        HIP_TRY(hipSetDevice(idx->device));
+        if ((rc = cosine_queries(idx, d_queries, nq, q_stride, (hipStream_t)stream, &d_queries, &q_stride))) return rc;
+    }
     return scan_search(idx, {d_queries, nq, q_stride, d_ids, d_dist, nullptr, nullptr, nullptr, nullptr}, k, fill, (hipStream_t)stream,
                        live ? live->table() : nullptr);
 }

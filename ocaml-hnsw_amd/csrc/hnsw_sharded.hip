@@ -372,7 +372,9 @@ int search_and_merge(hnsw_sharded *s, const float *queries, int64_t nq, int64_t 
             const KnnBatch batch = b.batch(nq, q_stride, k);
             HIP_TRY(hipMemsetAsync(batch.any_flag, 0, 4, st));
             HIP_TRY(hipMemcpyAsync(b.q.p, queries, qbytes, hipMemcpyHostToDevice, st));
-            int r = search(s->grp[(size_t)g], batch, st);
+            // COSINE: the device's uploaded copy becomes N(Q) in place, once, for the search and for a repair after it
+            int r = is_cosine(s->grp[(size_t)g]) ? cosine_normalise(batch.Q, nq, d, q_stride, (float *)b.q.p, q_stride, nullptr, nullptr, st) : HNSW_OK;
+            if (!r) r = search(s->grp[(size_t)g], batch, st);
             if (r) return r;
             HIP_TRY(hipMemcpyAsync(&s->grp.hFlags[g], batch.any_flag, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipEventRecord(s->grp.done[(size_t)g], st));

@@ -112,6 +112,22 @@ class Dataset:
         return cls(train, test, d)
 
 
+def metric_of(distance):
+    """The index metric for an ann-benchmarks `distance` attribute (Dataset.distance): "euclidean" -> METRIC_L2, "angular" or
+    "cosine" -> METRIC_COSINE (the index normalises data and queries itself); anything else: InvalidArgument."""
+    try:
+        from . import METRIC_L2, METRIC_COSINE, InvalidArgument
+    except ImportError:       # imported as a plain module (tools/)
+        from ocaml_hnsw_amd import METRIC_L2, METRIC_COSINE, InvalidArgument
+    if isinstance(distance, bytes):
+        distance = distance.decode()
+    if distance == "euclidean":
+        return METRIC_L2
+    if distance in ("angular", "cosine"):
+        return METRIC_COSINE
+    raise InvalidArgument("distance %r: no index metric (euclidean, angular, cosine)" % (distance,))
+
+
 def brute_force_knn_l2(train, test, k, block=256, device=None):
     """benchmark/dataset.ml:15-30: for each test vector the k smallest L2 distances, ascending.
 

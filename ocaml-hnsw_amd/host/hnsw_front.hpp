@@ -173,6 +173,17 @@ inline Sq8 sq8(const Hgraph &g) {
     return out;
 }
 
+// N(X) (hnsw_normalise_batch): every vector of `batch` scaled to unit length by the normaliser the header defines -- the rows a
+// HNSW_METRIC_COSINE index stores for X and searches for a query batch X -- as [n][dim] floats; norms (optional): the n norms.  A
+// zero vector stays zero, a vector whose sum of squares is not finite becomes NaN.  The metric itself is accepted wherever one is:
+// hnsw_index_desc.metric (Hgraph::create), Ohnsw::build_batch_bigarray, hnsw_build_params.metric (Sharded::build).
+inline std::vector<float> normalise(const Mat &batch, int device = 0, std::vector<float> *norms = nullptr) {
+    std::vector<float> out((size_t)batch.dim2 * (size_t)batch.dim1);
+    if (norms) norms->assign((size_t)batch.dim2, 0.f);
+    check(hnsw_normalise_batch(device, batch.data, batch.dim2, batch.dim1, batch.dim1, out.data(), batch.dim1, norms ? norms->data() : nullptr));
+    return out;
+}
+
 // A Lacaml-shaped float32 matrix (dim x n) in page-locked memory the library allocates (hnsw_host_alloc): knn_batch*
 // reads such a query matrix straight from the device, without an upload step.
 class HostMat {
@@ -247,6 +258,22 @@ inline int64_t insert(Hgraph &g, const Mat &batch, int num_connections, int num_
     hnsw_build_params p{num_connections, num_nodes_search_construction, inf.metric, inf.id_base, seed, max_batch, 0, expected_ef, HNSW_SEM_OHNSW};
     check(hnsw_index_insert(g.handle(), batch.data, batch.dim2, batch.dim1, &p));
     return inf.n + inf.id_base;
+}
+
+// The float32 rows g holds for the nodes `ids` (id_base-based; hnsw_index_get_rows) as [ids.size()][dim] floats, or -- no ids --
+// all n rows in order.  For a HNSW_METRIC_COSINE index these are N(X), not the vectors it was handed.
+inline std::vector<float> rows(const Hgraph &g, const std::vector<int64_t> &ids) {
+    std::vector<float> out(ids.size() * (size_t)g.dim());
+    if (ids.empty()) return out;
+    check(hnsw_index_get_rows(g.handle(), ids.data(), (int64_t)ids.size(), out.data(), g.dim()));
+    return out;
+}
+inline std::vector<float> rows(const Hgraph &g) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    std::vector<float> out((size_t)inf.n * (size_t)inf.d);
+    check(hnsw_index_get_rows(g.handle(), nullptr, inf.n, out.data(), inf.d));
+    return out;
 }
 
 // Hard deletion on the device (hnsw_index_remove): the stored nodes `ids` (id_base-based, distinct) leave g, the others keep

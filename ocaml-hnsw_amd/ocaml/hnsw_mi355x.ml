@@ -87,6 +87,14 @@ let hnsw_index_sq8_params =
   foreign ~from:lib "hnsw_index_sq8_params" (index @-> ptr float @-> ptr float @-> returning int32_t)
 let hnsw_index_sq8_codes =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_sq8_codes" (index @-> ptr void @-> returning int32_t)
+(* cosine distance (metric_cosine below; the twin contract of the C header): the normaliser N as an operator of its own, and the
+   float32 rows an index holds -- for a cosine index N(X), not the vectors it was handed *)
+let hnsw_normalise_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_normalise_batch"
+    (int32_t @-> ptr float @-> int64_t @-> int32_t @-> int64_t @-> ptr float @-> int64_t @-> ptr float @-> returning int32_t)
+let hnsw_index_get_rows =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_get_rows"
+    (index @-> ptr int64_t @-> int64_t @-> ptr float @-> int64_t @-> returning int32_t)
 let hnsw_index_kernel_times =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_kernel_times"
     (index @-> ptr double @-> ptr double @-> ptr int32_t @-> returning int32_t)
@@ -1142,6 +1150,30 @@ let sq8_codes (t : t) : (int, Bigarray.int8_unsigned_elt, Bigarray.c_layout) Big
   check (hnsw_index_get_info t.handle (addr inf));
   let out = Bigarray.Array2.create Bigarray.int8_unsigned Bigarray.c_layout (max 1 (Int64.to_int (getf inf ii_n))) t.dim in
   check (hnsw_index_sq8_codes t.handle (to_voidp (bigarray_start array2 out)));
+  out
+
+(* ?metric of [create], [build], [of_ohnsw], [of_ba] and [sharded_build]: HNSW_METRIC_L2, _IP, _COSINE.  A cosine index stores
+   N(X) and normalises every query batch itself: callers hand it unnormalised vectors everywhere. *)
+let metric_l2 = 0
+let metric_ip = 1
+let metric_cosine = 2
+
+(* N(X) (hnsw_normalise_batch): the columns of [x] scaled to unit length by the normaliser the C header defines, as a fresh
+   matrix, and their norms; a zero column stays zero, one whose sum of squares is not finite becomes nan *)
+let normalise ?(device = 0) (x : Lacaml.S.mat) : Lacaml.S.mat * Lacaml.S.vec =
+  let dim = A2.dim1 x and n = A2.dim2 x in
+  let out = Lacaml.S.Mat.create dim n and norms = Lacaml.S.Vec.create (max 1 n) in
+  check (hnsw_normalise_batch (Int32.of_int device) (bigarray_start array2 x) (Int64.of_int n) (Int32.of_int dim) (Int64.of_int dim)
+           (bigarray_start array2 out) (Int64.of_int dim) (bigarray_start array1 norms));
+  (out, norms)
+
+(* the float32 vectors the index holds (hnsw_index_get_rows), one column per node in id order: for [metric_cosine] N(X) *)
+let rows (t : t) : Lacaml.S.mat =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let n = Int64.to_int (getf inf ii_n) in
+  let out = Lacaml.S.Mat.create t.dim (max 1 n) in
+  check (hnsw_index_get_rows t.handle (from_voidp int64_t null) (Int64.of_int n) (bigarray_start array2 out) (Int64.of_int t.dim));
   out
 
 (* everything the first search with this ef (and accept rule) would do once -- the visited-structure decision, the kernel's
