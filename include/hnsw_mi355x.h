@@ -223,8 +223,10 @@ enum { HNSW_ROWS_F32 = 0,   /* the float32 rows as handed over                  
                                neighbour in the layer-0 adjacency (option "split_rows")                      */
        HNSW_ROWS_HALF = 4,  /* the values rounded to fp16 (option "half_rows"): NOT the search over the float32
                                vectors but the exact search over X rounded to fp16                          */
-       HNSW_ROWS_SQ8 = 5 }; /* 8-bit codes under one affine map (option "sq8_rows"): the walk is the exact search
+       HNSW_ROWS_SQ8 = 5,   /* 8-bit codes under one affine map (option "sq8_rows"): the walk is the exact search
                                over the codes, the answer its candidates re-ranked over the float32 vectors  */
+       HNSW_ROWS_SQ8_DIM = 6 }; /* 8-bit codes under one affine map PER DIMENSION (option "sq8_dim_rows"): the walk is
+                               the exact search over Z = codes * s, the answer re-ranked over the float32 vectors */
 
 typedef struct hnsw_index_info {
     int64_t n;
@@ -234,7 +236,7 @@ typedef struct hnsw_index_info {
     int64_t row_stride_bytes;  /* padded vector row on the device                             */
     int32_t device;
     int32_t row_format;        /* HNSW_ROWS_*: what the knn searches read right now (options "byte_rows", "split_rows",
-                                  "half_rows", "sq8_rows") */
+                                  "half_rows", "sq8_rows", "sq8_dim_rows") */
 } hnsw_index_info;
 
 int32_t hnsw_abi_version(void);
@@ -364,9 +366,53 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   SCRATCH: q' ([nq][d padded to 16] floats) lives beside the refine scratch -- owned by the handle, by the
  *                   request for submit / wait, sized on demand, not counted in device_bytes --: the same ONE
  *                   hnsw_search_batch_device / hnsw_search_batch_h2d call in flight per handle as with refine active.
- *                   hnsw_index_sq8_params / hnsw_index_sq8_codes give lo, s and the codes.  A scale per dimension would need a
- *                   weighted distance in a kernel family of its own: not built.  Rate and recall: not measured yet
- *                   (tools/sq8_rate.py prints the table for profiles/sq8_rows.txt).
+ *                   hnsw_index_sq8_params / hnsw_index_sq8_codes give lo, s and the codes.  A scale per dimension is option
+ *                   "sq8_dim_rows" below (a weighted L2 walk in a kernel family of its own).  HNSW_ERR_BAD_ARG while that
+ *                   option is on.  Rate and recall: not measured yet (tools/sq8_rate.py prints the table for profiles/sq8_rows.txt).
+ *   "sq8_dim_rows"  as "sq8_rows", with one affine map PER DIMENSION: where the columns of X do not share a range (a few outliers in
+ *                   one column are enough) one map for the whole table spends its 256 codes on the widest column and is blind in
+ *                   the others.  1 = make the copy if it is missing and search it, 0 = read the previous rows again (the copy is
+ *                   kept), -1 = ... and FREE the copy (after a device synchronisation); any other value is HNSW_ERR_BAD_ARG.
+ *                   QUANTISER (float32, round to nearest even, no contraction: numpy reproduces the bits): for each dimension i,
+ *                   lo_i = min, hi_i = max over the n stored values of column i (a bound of -0 counts as +0);
+ *                   s_i = (hi_i - lo_i) / 255, s_i = 1 when hi_i == lo_i; code = min(255, max(0, rint((x - lo_i) / s_i))), ties to
+ *                   even.  Rows lie in the byte kernels' lane grid: 64 * NCH bytes per row, zero padded.  A NaN or infinity in X,
+ *                   a column whose hi - lo overflows, or one so narrow that (hi - lo) / 255 rounds to 0, is HNSW_ERR_UNSUPPORTED
+ *                   (the message names the first such column) and leaves the index unchanged.
+ *                   WALK, with x^_i = lo_i + s_i * code_i.  Inner product (and HNSW_METRIC_COSINE through its inner-product twin):
+ *                   <x^, q> = sum(lo_i q_i) + <code, s o q>, the first term constant per query, so the walk is the UNCHANGED
+ *                   byte-row search over the codes C with q'_i = fl(s_i * q_i): bit for bit the inner-product search over
+ *                   C.astype(float32) with q'.  L2: |x^ - q|^2 = sum((s_i code_i - (q_i - lo_i))^2) is a weighted distance: a row
+ *                   format of the knn kernel of its own (the loads of the byte rows; per dimension z = fl((float)code * s_i),
+ *                   dx = fl(z - q''_i), acc = fma(dx, dx, acc) with q''_i = fl(q_i - lo_i), 0 beyond d; lanes, chunk order and
+ *                   16-lane tree of every distance of the library; the C++ hop loop: no hand-scheduled loop).  TWIN: ids, walk
+ *                   distances, hops and W of this walk are bit for bit those of a float32-row L2 index with the same graph over
+ *                   Z = C.astype(float32) * s (numpy float32), searched with Q'' = Q - lo.  q' and q'' are NOT checked for
+ *                   overflow, as with "sq8_rows".
+ *                   Everything after the walk is "sq8_rows" unchanged: c = min(ef, max(k, R)) members of W (R = option "refine")
+ *                   re-ranked over the FLOAT32 rows, unconditionally; the first k under (distance, node id) come back with the
+ *                   bits of hnsw_distance_batch; out_nhops is the walk's count, out_ndist the walk's count plus c;
+ *                   HNSW_SEM_FUNCTOR_NEAREST_K is HNSW_ERR_BAD_ARG; the same scratch and the same ONE call in flight per handle;
+ *                   every knn form, the filtered and range ladders (all of W re-ranked), marked indexes, multi replicas
+ *                   (hnsw_multi_replica) and sharded indexes (hnsw_sharded_set_option: one set of maps per shard).  The builder,
+ *                   hnsw_index_insert's searches, the layer operators, hnsw_distance_batch, the exact scans and hnsw_rerank_batch
+ *                   keep reading the float32 rows.  Option "visited_blocks" treats these rows as it treats sq8 rows.
+ *                   EXCLUSIONS: HNSW_ERR_BAD_ARG, the index unchanged, when it is set to 1 while byte rows are in use
+ *                   ("byte_rows" 0 first) or while option half_rows, sq8_rows or filter_collect is on, and when one of those
+ *                   three is set to 1 while this option is on; the split rows step aside.
+ *                   hnsw_index_info.row_format reports HNSW_ROWS_SQ8_DIM, hnsw_index_row_bytes gives d, and the copy's
+ *                   n * 64 * NCH bytes plus its two per-dimension tables (lo and s in the lane grid: 2 * 4 * 64 * NCH bytes) count
+ *                   in device_bytes.  Not saved: a loaded index starts without it.  hnsw_index_insert and hnsw_index_remove
+ *                   quantise the WHOLE remaining table again; a new vector that is not finite refuses the whole insert and leaves
+ *                   the index, the copy and its parameters as before.  hnsw_index_sq8_dim_params / hnsw_index_sq8_dim_codes
+ *                   give lo[d], s[d] and the codes.  Not built: hand-scheduled loops for this format, a saved copy.
+ *                   RATE AND RECALL (one MI355X, 1 M x 128, L2, ef 128, k 10, 10 k queries; tools/sq8_dim_rate.py,
+ *                   profiles/sq8_dim_rows.txt): the walk costs 1.01 to 1.03 times the launches of the "sq8_rows" walk on the same
+ *                   handle (the same bytes gathered; one more multiply per dimension, the C++ hop loop).  SIFT-like data: 16.6 M
+ *                   queries/s device-resident against 16.8 over sq8 rows and 13.4 over float32 rows, recall@10 0.989 for both kinds
+ *                   of codes at refine 0 and 1.000 at refine 64.  Standard normal data with 8 rows multiplied by 400 in dimension
+ *                   0: recall@10 0.285 against 0.093 over sq8 rows (0.167 at refine 64) and 0.293 over the float32 rows, at 2.3
+ *                   times the float32 rows' rate.
  *   "filter_collect" 0 = off (default: every result, counter and code path is exactly as without the option); 1 = the filtered
  *                   searches answer from EVERY node the layer-0 walk evaluates, not from the final W only: a walk at ef 128
  *                   evaluates about 950 to 2400 nodes and keeps 128, and each evaluated node has an exact distance.  The
@@ -376,7 +422,7 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   k <= 128 only: for k > 128 the option has no effect and the ladder over W answers.
  *                   EXCLUSIONS: exact-row formats only (float32, byte and split rows).  HNSW_ERR_BAD_ARG, the index unchanged,
  *                   when it is set to 1 while option "half_rows" or "sq8_rows" is on, and when "half_rows" or "sq8_rows" is
- *                   set to 1 while it is 1.  Not saved: a loaded index starts with it off.  hnsw_index_insert and
+ *                   set to 1 while it is 1 (option "sq8_dim_rows": likewise, both ways).  Not saved: a loaded index starts with it off.  hnsw_index_insert and
  *                   hnsw_index_remove keep the setting.  Range search is not affected.  RATE AND RECALL (one MI355X, 1 M x 128 byte
  *                   rows, ef 128, k 10, 10 k queries; tools/filter_rate.py --collect, profiles/filter_collect.txt), on against off:
  *                   selectivity 0.01: 8.2 ms per batch against 45.9, recall@10 0.787 against 0.998; 0.1: 8.2 against 8.9, recall
@@ -402,7 +448,7 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   demand and not counted in device_bytes: with refine active ONE hnsw_search_batch_device /
  *                   hnsw_search_batch_h2d call in flight per handle (calls on one stream are ordered and therefore fine).
  *                   While the searches read any other rows (bytes, split, float32) the option is accepted and does nothing
- *                   -- except over sq8 rows (option "sq8_rows"), whose searches are always re-ranked and take c from it --:
+ *                   -- except over sq8 rows (options "sq8_rows", "sq8_dim_rows"), whose searches are always re-ranked and take c from it --:
  *                   those distances are exact over X already, results and out_ndist are bit-identical to refine 0; set
  *                   before "half_rows" it takes effect when half rows are turned on.  HNSW_SEM_FUNCTOR_NEAREST_K with refine
  *                   active is HNSW_ERR_BAD_ARG ("the k farthest of W" has no refined meaning).  hnsw_index_insert keeps the
@@ -410,12 +456,17 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   roughly 950 to 2400 half-row evaluations (the benchmark's float shapes); the rate has not been measured
  *                   yet (tools/refine_rate.py prints the table that belongs beside profiles/half_rows.txt). */
 int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value);
-/* Bytes of one vector as the knn searches read it: d for byte and sq8 rows, 2 * d for half rows, 4 * d for float32 rows. */
+/* Bytes of one vector as the knn searches read it: d for byte and sq8 rows (either kind), 2 * d for half rows, 4 * d for float32 rows. */
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes);
 /* The sq8 copy (option "sq8_rows"), for callers who want X^ = lo + scale * codes: its two parameters, and its codes as
  * [n][d] bytes (the rows' padding is not exported).  HNSW_ERR_BAD_ARG when no copy exists (never made, or freed by -1). */
 int32_t hnsw_index_sq8_params(const hnsw_index *idx, float *lo, float *scale);
 int32_t hnsw_index_sq8_codes(const hnsw_index *idx, uint8_t *out);
+/* The per-dimension sq8 copy (option "sq8_dim_rows"), x^_i = lo[i] + scale[i] * code: its parameters (lo and scale: [d] floats
+ * each), and its codes as [n][d] bytes (the rows' padding is not exported).  HNSW_ERR_BAD_ARG for a null argument and when no copy
+ * exists (never made, or freed by -1). */
+int32_t hnsw_index_sq8_dim_params(const hnsw_index *idx, float *lo, float *scale);
+int32_t hnsw_index_sq8_dim_codes(const hnsw_index *idx, uint8_t *out);
 /* Mean durations (ms) over the device-entry calls recorded since the last call of this function
  * (option "time_kernels"): the search kernel itself, and the ordering pre-pass (descent kernel +
  * sort; 0 when the batch was searched in the given order).  Waits for the recorded calls. */

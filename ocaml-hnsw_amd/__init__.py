@@ -30,8 +30,9 @@ METRIC_COSINE = 2
 FILL_OHNSW, FILL_BA = 0, 1
 SEM_OHNSW, SEM_FUNCTOR, SEM_FUNCTOR_NEAREST_K = 0, 1, 2
 # IndexInfo.row_format: what the knn searches read (HNSW_ROWS_*); ROWS_HALF only after set_option("half_rows", 1), ROWS_SQ8 only
-# after set_option("sq8_rows", 1)
+# after set_option("sq8_rows", 1), ROWS_SQ8_DIM only after set_option("sq8_dim_rows", 1)
 ROWS_F32, ROWS_BYTES, ROWS_SPLIT, ROWS_HALF, ROWS_SQ8 = 0, 2, 3, 4, 5
+ROWS_SQ8_DIM = 6
 
 ABI_VERSION = 3          # HNSW_ABI_VERSION of include/hnsw_mi355x.h this mirror was written against
 
@@ -51,6 +52,8 @@ _ABI = {
     "hnsw_index_row_bytes": [_vp, _vp],
     "hnsw_index_sq8_params": [_vp, _vp, _vp],
     "hnsw_index_sq8_codes": [_vp, _vp],
+    "hnsw_index_sq8_dim_params": [_vp, _vp, _vp],
+    "hnsw_index_sq8_dim_codes": [_vp, _vp],
     "hnsw_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_device": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_h2d": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -487,13 +490,13 @@ class Hgraph:
         return inf
 
     def set_option(self, name, value):
-        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "refine", ...).
+        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "sq8_dim_rows", "refine", ...).
         "filter_collect" 1 makes the filtered searches (knn_batch_filtered, knn_batch_filtered_each, the plain searches under
         marks) answer from every node the layer-0 walk evaluates, not from the final W only (k <= 128, exact rows; default 0)"""
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
 
     def row_bytes(self):
-        """Bytes of one vector as the knn searches read it (d: byte and sq8 rows, 2 d: half rows, 4 d: float32 rows)."""
+        """Bytes of one vector as the knn searches read it (d: byte and sq8 rows of either kind, 2 d: half rows, 4 d: float32 rows)."""
         v = _C.c_int64(0)
         _check(load().hnsw_index_row_bytes(self.handle, _C.byref(v)))
         return v.value
@@ -508,6 +511,19 @@ class Hgraph:
         """hnsw_index_sq8_codes -> the codes of the sq8 copy, uint8 [n][d] (the rows' padding is not exported)"""
         out = _np.empty((self.info().n, self.d), _np.uint8)
         _check(load().hnsw_index_sq8_codes(self.handle, _ptr(out)))
+        return out
+
+    def sq8_dim_params(self):
+        """hnsw_index_sq8_dim_params -> (lo, scale), two float32 arrays of length d, of the per-dimension sq8 copy
+        (set_option("sq8_dim_rows", 1)): x[i] ~ lo[i] + scale[i] * code[i]"""
+        lo, s = _np.empty(self.d, _np.float32), _np.empty(self.d, _np.float32)
+        _check(load().hnsw_index_sq8_dim_params(self.handle, _ptr(lo), _ptr(s)))
+        return lo, s
+
+    def sq8_dim_codes(self):
+        """hnsw_index_sq8_dim_codes -> the codes of the per-dimension sq8 copy, uint8 [n][d] (the rows' padding is not exported)"""
+        out = _np.empty((self.info().n, self.d), _np.uint8)
+        _check(load().hnsw_index_sq8_dim_codes(self.handle, _ptr(out)))
         return out
 
     def filter(self, allow):

@@ -333,13 +333,14 @@ int check_upper_rows(const hnsw_index *idx, const char *verb) {
 // rows (per-slot tails follow the changed adjacency) unless option split_rows -1 freed them for good, the half rows while
 // option half_rows is 1 (new vectors that do not fit fp16 refuse the whole insert; at 0 the copy is not carried over), the
 // sq8 rows while option sq8_rows is 1 (the WHOLE table is quantised again: new vectors may widen the range; a range that
-// overflows refuses the whole insert), the locality codes (carry_codes: carried over as extend_locality_codes does; else dropped
+// overflows refuses the whole insert), the per-dimension sq8 rows while option sq8_dim_rows is 1 (likewise), the locality codes (carry_codes: carried over as extend_locality_codes does; else dropped
 // and built on demand).  Then the tables are swapped in and the graph epoch moves on.  On any error idx is as it was.
 int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics, const int32_t *new_id) {
     int32_t rc = make_byte_rows(nx.get());
     if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx.get());
     if (!rc && idx->half_rows_on && nx->iv.n > 0) rc = make_half_rows(nx.get());
     if (!rc && idx->sq8_on && nx->iv.n > 0) rc = make_sq8_rows(nx.get());
+    if (!rc && idx->sq8d_on && nx->iv.n > 0) rc = make_sq8_dim_rows(nx.get());
     if (!rc && carry_codes) rc = extend_locality_codes(idx, nx.get());
     // soft deletion: the marks move with their nodes; the new live mask is complete before anything is swapped
     std::unique_ptr<hnsw_filter> live;
@@ -360,6 +361,7 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
     idx->iv = nx->iv;
     idx->info = nx->info;
     idx->sq8_lo = nx->sq8_lo; idx->sq8_scale = nx->sq8_scale;   // (of the swapped-in codes, if any)
+    idx->sq8d_lo = std::move(nx->sq8d_lo); idx->sq8d_scale = std::move(nx->sq8d_scale);
     bind_view(idx);                                        // the options keep their effect
     idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
     nx.reset();
@@ -477,11 +479,11 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
                     (long long)idx->dFbSlab.bytes, (long long)(n * 4));
     // option sq8_rows is on: the codes are made again over the grown table, which needs every value finite -- asked before the
     // graph is grown, not after
-    if (idx->sq8_on)
+    if (codes_on(idx))
         for (int64_t i = 0; i < m; ++i)
             for (int32_t j = 0; j < idx->iv.d; ++j)
                 if (!std::isfinite(vectors[i * row_stride + j]))
-                    return fail(HNSW_ERR_UNSUPPORTED, "sq8 rows: value %d of new vector %lld is NaN or infinite: nothing inserted", j, (long long)i);
+                    return fail(HNSW_ERR_UNSUPPORTED, "%s: value %d of new vector %lld is NaN or infinite: nothing inserted", codes_option(idx), j, (long long)i);
     HIP_TRY(hipSetDevice(idx->device));
     if (n_old > 0) { const int32_t rcu = check_upper_rows(idx, "not grown"); if (rcu) return rcu; }
 

@@ -199,10 +199,12 @@ const struct { int metric, semf, rows; collect_launch_fn launch; } k_collect_var
 
 // the knn kernel's row format: 2 = byte rows (hnsw_rows8.hip) and the sq8 codes (hnsw_rows_sq8.hip: the same kernels), 3 = split
 // fp32 rows (hnsw_rows_split.hip), 4 = half rows (hnsw_rows16.hip), else plain fp32 rows, 1 = every chunk of the lane grid inside
-// the row.  (From the record bind_view keeps: byte, sq8 and half rows share IndexView's pointer.)
+// the row.  (From the record bind_view keeps: byte, sq8 and half rows share IndexView's pointer.)  5 = the per-dimension sq8 codes
+// under L2 (hnsw_rows_sq8_dim.hip: a weighted distance; under the inner product they are byte rows to the kernel, 2).
 inline int variant_full(const hnsw_index *idx) {
     switch (idx->info.row_format) {
     case HNSW_ROWS_BYTES: case HNSW_ROWS_SQ8: return 2;
+    case HNSW_ROWS_SQ8_DIM: return idx->info.metric == HNSW_METRIC_L2 ? 5 : 2;
     case HNSW_ROWS_SPLIT: return 3;
     case HNSW_ROWS_HALF: return 4;
     default: return idx->iv.nchunks == 16 * pick_nch(idx->iv.nchunks) ? 1 : 0;
@@ -230,6 +232,10 @@ KnnShape knn_shape(const hnsw_index *idx, int ef, int semantics) {
         if (v.metric == metric && v.semf == sh.semf && v.rows == rows) { sh.launch = v.launch; sh.occupancy = v.occupancy; }
     for (const auto &v : k_collect_variants)
         if (v.metric == metric && v.semf == sh.semf && v.rows == rows) sh.collect = v.launch;
+    if (rows == 5) {                     // hnsw_sq8_dim_walk.hip: one object per accept rule, L2 only
+        sh.launch = sh.semf ? search_launch_sq8_dim_1 : search_launch_sq8_dim_0;
+        sh.occupancy = sh.semf ? search_occupancy_sq8_dim_1 : search_occupancy_sq8_dim_0;
+    }
     return sh;
 }
 
@@ -330,8 +336,9 @@ int blk_capacity_bits(hnsw_index *idx, const KnnShape &sh) {
     return bits;
 }
 
-// do the knn searches run the byte-row kernels (over the byte rows, or over the sq8 codes)?
-inline bool walks_bytes(const hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_BYTES || idx->info.row_format == HNSW_ROWS_SQ8; }
+// do the knn searches gather byte rows (the byte rows, or codes -- the per-dimension codes' L2 kernel loads what the byte-row
+// kernels load, and is treated as they are)?
+inline bool walks_bytes(const hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_BYTES || walks_codes(idx); }
 
 // does option "visited_blocks" at -1 consider this shape at all?
 bool blk_auto_eligible(const hnsw_index *idx, int nslot) {
@@ -369,8 +376,8 @@ int knn_blk_bits(hnsw_index *idx, const KnnShape &sh) {
     // (sq8 rows: the probes are midpoints of float32 vectors and the walk reads code space -- moved there in place.  Not reached
     // today: blk_auto_eligible leaves the byte-row kernels, sq8's among them, out of the measurement, and "visited_blocks" 1
     // returns above.  Kept so that measuring them one day does not search float32 probes in code space.)
-    if (ok && idx->info.row_format == HNSW_ROWS_SQ8)
-        ok = sq8_transform_queries(idx, (const float *)probes.p, nq, idx->iv.stride, (float *)probes.p, nullptr, nullptr) == HNSW_OK;
+    if (ok && walks_codes(idx))
+        ok = codes_transform_queries(idx, (const float *)probes.p, nq, idx->iv.stride, (float *)probes.p, nullptr, nullptr) == HNSW_OK;
     hnsw_search_params p{};
     p.ef = ef; p.k = 1; p.fill = HNSW_FILL_OHNSW; p.semantics = semf;
     const KnnBatch b{(const float *)probes.p, nq, idx->iv.stride, (int32_t *)out.p, (float *)out.p + nq, (uint32_t *)out.p + 2 * nq,
@@ -471,18 +478,19 @@ void launch_priorities(hnsw_index *idx, const KnnShape &sh, int64_t nq, SearchAr
 // those of code space, which mean nothing to a caller: such a search is ALWAYS re-ranked, refine 0 takes the k first of W.
 int refine_count(const hnsw_index *idx, const hnsw_search_params *p) {
     const int format = idx->info.row_format;
-    if (format != HNSW_ROWS_SQ8 && (idx->refine == 0 || format != HNSW_ROWS_HALF)) return 0;
+    if (!walks_codes(idx) && (idx->refine == 0 || format != HNSW_ROWS_HALF)) return 0;
     return idx->refine < 0 ? p->ef : std::min(p->ef, std::max(p->k, idx->refine));
 }
-// The queries a walk over sq8 rows reads: b's moved to code space in walk.qt (made here when `transform`: Q' = (Q - lo) / scale for
-// L2, Q for the inner product; stage: see sq8_transform_queries), at the padded stride.  Every launch that walks the codes -- the
+// The queries a walk over codes reads: b's moved to the codes' space in walk.qt (made here when `transform` -- sq8 rows: Q' =
+// (Q - lo) / scale for L2, Q for the inner product; per-dimension sq8 rows: Q - lo for L2, s o Q for the inner product; stage: see
+// sq8_transform_queries), at the padded stride.  Every launch that walks the codes -- the
 // ordering pre-pass, the search, the device fallback, knn_repair's re-run -- goes through here; the re-rank keeps the caller's.
 int sq8_walk_queries(hnsw_index *idx, RefineBufs &walk, KnnBatch *wb, bool transform, float *stage, hipStream_t st) {
     const int64_t stride = padded_stride(idx->iv.d);
     if (transform) {
         int rc;
         if ((rc = walk.qt.ensure((size_t)wb->nq * stride * sizeof(float))) ||
-            (rc = sq8_transform_queries(idx, wb->Q, wb->nq, wb->q_stride, (float *)walk.qt.p, stage, st))) return rc;
+            (rc = codes_transform_queries(idx, wb->Q, wb->nq, wb->q_stride, (float *)walk.qt.p, stage, st))) return rc;
     }
     wb->Q = (const float *)walk.qt.p; wb->q_stride = stride;
     return HNSW_OK;
@@ -514,7 +522,7 @@ int check_params(const hnsw_index *idx, const hnsw_search_params *p) {
         return fail(HNSW_ERR_BAD_ARG, "bad semantics %d", p->semantics);
     if (p->semantics == HNSW_SEM_FUNCTOR_NEAREST_K && refine_count(idx, p) > 0)
         return fail(HNSW_ERR_BAD_ARG, "option %s is active: the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no refined meaning",
-                    idx->info.row_format == HNSW_ROWS_SQ8 ? "sq8_rows" : "refine");
+                    walks_codes(idx) ? codes_option(idx) : "refine");
     if (idx->iv.entry_point < 0) return fail(HNSW_ERR_EMPTY_INDEX, "knn: empty hgraph");
     return HNSW_OK;
 }
@@ -573,7 +581,7 @@ int knn_search(hnsw_index *idx, const hnsw_search_params *caller_params, const K
         ev = &idx->tev[idx->tev_used];      // claimed (tev_used advanced) only once all three are recorded
         HIP_TRY(hipEventRecord(ev[0], st));
     }
-    const bool sq8 = idx->info.row_format == HNSW_ROWS_SQ8;      // (then refine_c > 0, unless raw_walk)
+    const bool sq8 = walks_codes(idx);                            // (then refine_c > 0, unless raw_walk)
     const float *rerank_Q = nullptr;                              // sq8: the caller's queries, which the re-rank reads
     if (sq8) {                                                    // (behind ev[0]: timed with the pre-pass, or with the search when there is none)
         if ((rc = sq8_walk_queries(idx, walk ? *walk : idx->refine_scratch, &b, true, d_stage, st))) return rc;
@@ -628,7 +636,7 @@ int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, 
     const int refine_c = raw_walk ? 0 : refine_count(idx, p);
     hnsw_search_params wp = *p;
     KnnBatch wb = b;
-    if (refine_c > 0 || idx->info.row_format == HNSW_ROWS_SQ8) {
+    if (refine_c > 0 || walks_codes(idx)) {
         // the walk's results are where knn_search left them (raw_walk: in b itself): its flagged rows are rewritten there
         int rc = HNSW_OK;
         if (refine_c > 0) {
@@ -636,7 +644,7 @@ int knn_repair(hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b, 
             rc = refine_walk(b, refine_c, walk ? *walk : idx->refine_scratch, &wb);
         }
         // (sq8 rows: the re-run walks the codes with the queries knn_search moved to code space)
-        if (!rc && idx->info.row_format == HNSW_ROWS_SQ8) rc = sq8_walk_queries(idx, walk ? *walk : idx->refine_scratch, &wb, false, nullptr, st);
+        if (!rc && walks_codes(idx)) rc = sq8_walk_queries(idx, walk ? *walk : idx->refine_scratch, &wb, false, nullptr, st);
         if (rc) return rc;
     }
     const int rc = rerun_overflowed(idx, b.nq, b.st, [&](const int32_t *qmap, int64_t c, uint32_t *slab, int32_t cap) {
@@ -811,20 +819,23 @@ void bind_view(hnsw_index *idx) {
     // the knn searches read, in this order of precedence: byte rows (exact, the smallest), sq8 rows (option sq8_rows 1: in the
     // byte rows' place, for the same kernels) or half rows (option half_rows 1; the two options exclude each other), split rows, the
     // plain float32 rows
-    const bool bytes = !idx->byte_rows_off && t.X8.p, sq8 = !bytes && idx->sq8_on && t.Xq.p, half = !bytes && !sq8 && idx->half_rows_on && t.Xh.p;
+    // (the per-dimension codes, option sq8_dim_rows 1, likewise; the three options exclude each other)
+    const bool bytes = !idx->byte_rows_off && t.X8.p, sq8 = !bytes && idx->sq8_on && t.Xq.p, sq8d = !bytes && !sq8 && idx->sq8d_on && t.Xqd.p,
+               half = !bytes && !sq8 && !sq8d && idx->half_rows_on && t.Xh.p;
     iv.X = (const float *)t.X.p;
-    iv.X8 = bytes ? (const uint8_t *)t.X8.p : sq8 ? (const uint8_t *)t.Xq.p : nullptr;
+    iv.X8 = bytes ? (const uint8_t *)t.X8.p : sq8 ? (const uint8_t *)t.Xq.p : sq8d ? (const uint8_t *)t.Xqd.p : nullptr;
     if (half) iv.Xh = (const uint2 *)t.Xh.p;
     iv.stride8 = (half ? 128 : 64) * pick_nch(iv.nchunks);
-    iv.Xm = idx->split_rows_off || half || sq8 ? nullptr : (const float *)t.Xm.p;
+    iv.Xm = idx->split_rows_off || half || sq8 || sq8d ? nullptr : (const float *)t.Xm.p;
     iv.tail0 = (const float *)t.tail0.p;
+    if (sq8d) iv.sq8s = (const float *)t.qd_s.p;              // (in tail0's place: no split rows are read while the codes are)
     iv.nbr0 = (const int32_t *)t.nbr0.p; iv.nbrU = (const int32_t *)t.nbrU.p;
     iv.upper_off = (const int32_t *)t.off.p; iv.upper_lvl = (const uint8_t *)t.lvl.p; iv.upper_ref = (const int2 *)t.ref.p;
     iv.lcode = (const int32_t *)t.lcode.p; iv.lcode0 = (const int32_t *)t.lcode0.p;
     hnsw_index_info &inf = idx->info;
     inf.n = iv.n; inf.max_degree0 = iv.S0; inf.max_layer = iv.max_layer; inf.entry_point = (int64_t)iv.entry_point + iv.id_base;
     inf.row_stride_bytes = iv.stride * 4;
-    inf.row_format = bytes ? HNSW_ROWS_BYTES : sq8 ? HNSW_ROWS_SQ8 : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
+    inf.row_format = bytes ? HNSW_ROWS_BYTES : sq8 ? HNSW_ROWS_SQ8 : sq8d ? HNSW_ROWS_SQ8_DIM : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
 }
 
 int finish_index(IndexPtr owned, int32_t expected_ef, int32_t expected_semantics, hnsw_index **out) {
@@ -1039,7 +1050,7 @@ int32_t hnsw_index_prepare(hnsw_index *idx, const hnsw_search_params *params) {
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes) {
     if (!idx || !row_bytes) return fail(HNSW_ERR_BAD_ARG, "null argument");
     const int f = idx->info.row_format;
-    *row_bytes = (int64_t)idx->iv.d * (f == HNSW_ROWS_BYTES || f == HNSW_ROWS_SQ8 ? 1 : f == HNSW_ROWS_HALF ? 2 : 4);
+    *row_bytes = (int64_t)idx->iv.d * (f == HNSW_ROWS_BYTES || walks_codes(idx) ? 1 : f == HNSW_ROWS_HALF ? 2 : 4);
     return HNSW_OK;
 }
 
@@ -1072,7 +1083,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
             if (idx->info.row_format == HNSW_ROWS_BYTES)
                 return fail(HNSW_ERR_BAD_ARG, "half_rows: the index searches its byte rows, which are exact and half the size of half rows "
                                               "(set byte_rows 0 first)");
-            if (idx->sq8_on) return fail(HNSW_ERR_BAD_ARG, "half_rows: option sq8_rows is on (set sq8_rows 0 first)");
+            if (codes_on(idx)) return fail(HNSW_ERR_BAD_ARG, "half_rows: option %s is on (set it 0 first)", codes_option(idx));
             if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "half_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
             if (!idx->tables.Xh.p) {
                 const int rc = make_half_rows(idx);     // (a refusal -- NaN, fp16 overflow -- leaves the index as it was)
@@ -1096,6 +1107,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
             if (idx->info.row_format == HNSW_ROWS_BYTES)
                 return fail(HNSW_ERR_BAD_ARG, "sq8_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)");
             if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option half_rows is on (set half_rows 0 first)");
+            if (idx->sq8d_on) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option sq8_dim_rows is on (set sq8_dim_rows 0 first)");
             if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
             if (!idx->tables.Xq.p) {
                 const int rc = make_sq8_rows(idx);      // (a refusal -- NaN, infinity, range overflow -- leaves the index as it was)
@@ -1114,6 +1126,32 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         idx->forget_shapes();
         return HNSW_OK;
     }
+    if (!strcmp(name, "sq8_dim_rows")) {  // as "sq8_rows", the codes under one affine map per dimension (hnsw_rows_sq8_dim.hip)
+        if (value < -1 || value > 1) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows=%lld: 1 (on), 0 (off) or -1 (off, the copy freed)", (long long)value);
+        if (value > 0) {
+            if (idx->info.row_format == HNSW_ROWS_BYTES)
+                return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)");
+            if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option half_rows is on (set half_rows 0 first)");
+            if (idx->sq8_on) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option sq8_rows is on (set sq8_rows 0 first)");
+            if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
+            if (!idx->tables.Xqd.p) {
+                const int rc = make_sq8_dim_rows(idx);  // (a refusal -- NaN, infinity, a column's range -- leaves the index as it was)
+                if (rc) return rc;
+            }
+            idx->sq8d_on = true;
+        } else {
+            if (value < 0 && idx->tables.Xqd.p) {
+                HIP_TRY(hipSetDevice(idx->device));
+                HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy
+                idx->tables.Xqd.release(); idx->tables.qd_lo.release(); idx->tables.qd_s.release();
+                idx->sq8d_lo.clear(); idx->sq8d_scale.clear();
+            }
+            idx->sq8d_on = false;
+        }
+        bind_view(idx);
+        idx->forget_shapes();
+        return HNSW_OK;
+    }
     if (!strcmp(name, "refine")) {        // 0: off; 1..1024: re-rank max(k, value) members of W over the float32 rows; -1: all ef (half and sq8 rows only)
         if (value < -1 || value > 1024) return fail(HNSW_ERR_BAD_ARG, "refine=%lld: 0 (off), 1..1024 candidates or -1 (all of W)", (long long)value);
         idx->refine = (int)value;
@@ -1121,9 +1159,9 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     }
     if (!strcmp(name, "filter_collect")) {   // 1: the filtered searches answer from every node the walk evaluates (k <= 128, exact rows); 0: from the final W
         if (value != 0 && value != 1) return fail(HNSW_ERR_BAD_ARG, "filter_collect=%lld: 0 (off) or 1", (long long)value);
-        if (value == 1 && (idx->half_rows_on || idx->sq8_on))     // (on, even while byte rows stand in front of them: "byte_rows" 0 would bring them back)
+        if (value == 1 && (idx->half_rows_on || codes_on(idx)))   // (on, even while byte rows stand in front of them: "byte_rows" 0 would bring them back)
             return fail(HNSW_ERR_BAD_ARG, "filter_collect: option %s is on, and a walk over those rows has no exact distances (set it 0 first)",
-                        idx->sq8_on ? "sq8_rows" : "half_rows");
+                        codes_on(idx) ? codes_option(idx) : "half_rows");
         idx->filter_collect = value == 1;
         return HNSW_OK;
     }
@@ -1164,7 +1202,7 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
     const struct { const char *name; int64_t value; } now[] = {
         {"vt_bits", idx->vt_bits_override}, {"lds_pad", idx->lds_pad}, {"byte_rows", idx->byte_rows_off ? 0 : 1},
         {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
-        {"sq8_rows", idx->sq8_on ? 1 : 0}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
+        {"sq8_rows", idx->sq8_on ? 1 : 0}, {"sq8_dim_rows", idx->sq8d_on ? 1 : 0}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
         {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }
@@ -1210,7 +1248,7 @@ int32_t hnsw_index_kernel_times(hnsw_index *idx, double *search_ms, double *prep
 // Only where the call reads its query matrix in place, would order the whole batch, and is a plain knn walk (no re-rank: refine,
 // sq8 rows).  -1: H_AUTO below.
 int64_t head_rows(hnsw_index *idx, const hnsw_search_params *p, int64_t nq) {
-    if (idx->head_queries == 0 || nq < 2 || refine_count(idx, p) > 0 || idx->info.row_format == HNSW_ROWS_SQ8) return 0;
+    if (idx->head_queries == 0 || nq < 2 || refine_count(idx, p) > 0 || walks_codes(idx)) return 0;
     const Residency res = resident_queries(idx, knn_shape(idx, p->ef, p->semantics));
     const int mode = idx->order_mode;
     if (mode == 0 || (mode != 1 && 2 * nq <= res.queries)) return 0;          // the batch would not be ordered

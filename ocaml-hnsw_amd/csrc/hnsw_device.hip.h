@@ -59,7 +59,9 @@ struct IndexView {
     // neighbour in layer 0's adjacency: tail0[c][j] = the tail of node nbr0[c][j], so the tails of a hop's candidates
     // share the S0 * 16 * tail_chunks contiguous bytes of the expanded node.  nullptr = not available / switched off
     const float *Xm;
-    const float *tail0;      // [n][S0][4 * tail_chunks]
+    // (sq8s: while the searches walk the per-dimension codes -- ROWS 5, hnsw_rows_sq8_dim.hip: X8 holds the codes, Xm is null -- the
+    // codes' scales in the lane grid, [64 * NCH] floats, 0 beyond d.  One member for both, as X8 / Xh: the view's layout stays.)
+    union { const float *tail0; const float *sq8s; };      // tail0: [n][S0][4 * tail_chunks]
     int32_t stride_m;        // bytes per main row = 16 * main_chunks
     int32_t main_chunks;     // multiple of 8
     int32_t tail_chunks;     // 1 or 2; main_chunks + tail_chunks == nchunks
@@ -118,6 +120,14 @@ template <int METRIC> __device__ __forceinline__ float key_to_dist(uint32_t key)
 // ---- half rows (ROWS 4): the low / high fp16 of a dword as float -- exact (v_cvt_f32_f16; the high half by SDWA) ------------
 __device__ __forceinline__ float half_lo(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(u & 0xFFFFu)); }
 __device__ __forceinline__ float half_hi(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(u >> 16)); }
+
+// ---- per-dimension codes (ROWS 5): fl(fl(c * s) - q), the product and the difference TWO rounded operations (numpy: c * s - q on
+// float32 arrays).  hipcc contracts a * b - c into one fma by default, __fmul_rn / __fsub_rn included: the pragma forbids it here.
+__device__ __forceinline__ float scaled_diff(float c, float s, float q) {
+#pragma clang fp contract(off)
+    const float z = c * s;
+    return z - q;
+}
 
 // ---- DPP helpers ---------------------------------------------------------------------------
 template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
@@ -555,6 +565,8 @@ struct WaveCtx {
     bool qint;
     uint32_t qb[4];      // this lane's chunks of the query as packed bytes
     int32_t q2;          // sum of the squares of the whole query
+    // per-dimension codes only (ROWS 5, load_scales): the scales of this lane's chunks, sv[i] = s of dims 4 (16 i + l16) .. + 3
+    float4 sv[16];
 };
 // 4 KiB of tags at vt_bits = 11 plus 1 KiB: 28 waves per CU fit the 160 KiB LDS
 __host__ __device__ inline size_t wave_lds_words(int vt_bits) { return (((size_t)1 << vt_bits) >> 1) + 192 + OVF_CAP; }
@@ -713,13 +725,18 @@ __device__ __forceinline__ int adj_entry(const IndexView &iv, int layer, int c, 
 // 4 = half rows (IndexView::Xh, hnsw_rows16.hip): one uint2 per chunk -- a group's step is one whole 128-byte line --,
 // each half converted to float exactly, then the arithmetic of the fp32 row: the result is that of the fp32 row of
 // X rounded to fp16 bit for bit.  (The zero padding of a half row meets the zero padding of the query: it adds +0.)
+// 5 = per-dimension codes (IndexView::X8 and sq8s, hnsw_rows_sq8_dim.hip; L2 only): the loads of ROWS = 2; each byte c of dimension
+// i becomes z = fl((float)c * s_i) with the lane's scale registers (cx.sv) -- a rounded product of its own, never contracted into
+// the subtraction behind it -- then the arithmetic of the fp32 row: the result is that of the fp32 row of Z = C * s bit for bit.
+// (Beyond d code, scale and query are 0: exact zeros.)
 template <int NCH, int NB, int METRIC, int ROWS>
 __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv)[NCH], const WaveCtx &cx,
                                           int base, int cnt, uint32_t &out_key, uint32_t &out_id,
                                           const char *tail_row = nullptr) {
-    constexpr bool FULL = ROWS == 1 || ROWS == 2 || ROWS == 4;
+    static_assert(ROWS != 5 || METRIC == 0, "the per-dimension codes have an L2 walk only: the inner product walks them as byte rows");
+    constexpr bool FULL = ROWS == 1 || ROWS == 2 || ROWS == 4 || ROWS == 5;
     const int r = cx.r, l16 = cx.l16;
-    const uint32_t stride_b = (ROWS == 2 || ROWS == 4) ? (uint32_t)iv.stride8 : (uint32_t)iv.stride * 4u;
+    const uint32_t stride_b = (ROWS == 2 || ROWS == 4 || ROWS == 5) ? (uint32_t)iv.stride8 : (uint32_t)iv.stride * 4u;
     const int mine = base + NB * r;
     uint32_t id[NB];
 #pragma unroll
@@ -727,8 +744,9 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
         const int ci = (mine + b < cnt) ? mine + b : base + b;   // base + b < cnt: a round of NB batches has > 4*(NB-1) candidates
         id[b] = (uint32_t)cx.cand_id[ci];
     }
-    float4 v[ROWS == 2 || ROWS == 4 ? 1 : NB][ROWS == 2 || ROWS == 4 ? 1 : NCH];
-    uint32_t v8[ROWS == 2 ? NB : 1][ROWS == 2 ? NCH : 1];
+    constexpr bool CODES = ROWS == 2 || ROWS == 5;      // one dword per chunk
+    float4 v[CODES || ROWS == 4 ? 1 : NB][CODES || ROWS == 4 ? 1 : NCH];
+    uint32_t v8[CODES ? NB : 1][CODES ? NCH : 1];
     uint2 vh[ROWS == 4 ? NB : 1][ROWS == 4 ? NCH : 1];
     if constexpr (ROWS == 4) {
         const char *xlane = reinterpret_cast<const char *>(iv.Xh) + 8 * l16;
@@ -738,7 +756,7 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
 #pragma unroll
             for (int i = 0; i < NCH; ++i) vh[b][i] = row[i * 16];
         }
-    } else if constexpr (ROWS == 2) {
+    } else if constexpr (CODES) {
         const char *xlane = reinterpret_cast<const char *>(iv.X8) + 4 * l16;
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
@@ -843,11 +861,19 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
                 z = make_float4((float)(u & 0xFFu), (float)((u >> 8) & 0xFFu), (float)((u >> 16) & 0xFFu), (float)(u >> 24));
             } else if constexpr (ROWS == 4) {
                 z = make_float4(half_lo(vh[b][i].x), half_hi(vh[b][i].x), half_lo(vh[b][i].y), half_hi(vh[b][i].y));
+            } else if constexpr (ROWS == 5) {
+                const uint32_t u = v8[b][i];
+                z = make_float4((float)(u & 0xFFu), (float)((u >> 8) & 0xFFu), (float)((u >> 16) & 0xFFu), (float)(u >> 24));   // (scaled below)
             } else {
                 z = v[b][i];
             }
             float t = acc;
-            if (METRIC == 0) {
+            if (METRIC == 0 && ROWS == 5) {
+                float dx = scaled_diff(z.x, cx.sv[i].x, qv[i].x); t = __builtin_fmaf(dx, dx, t);
+                float dy = scaled_diff(z.y, cx.sv[i].y, qv[i].y); t = __builtin_fmaf(dy, dy, t);
+                float dz = scaled_diff(z.z, cx.sv[i].z, qv[i].z); t = __builtin_fmaf(dz, dz, t);
+                float dw = scaled_diff(z.w, cx.sv[i].w, qv[i].w); t = __builtin_fmaf(dw, dw, t);
+            } else if (METRIC == 0) {
                 float dx = z.x - qv[i].x; t = __builtin_fmaf(dx, dx, t);
                 float dy = z.y - qv[i].y; t = __builtin_fmaf(dy, dy, t);
                 float dz = z.z - qv[i].z; t = __builtin_fmaf(dz, dz, t);
@@ -925,6 +951,7 @@ __device__ __forceinline__ void greedy_descend(const IndexView &iv, const float4
                 uint32_t ckey, cid;
                 if (ROWS == 2) base += eval_round<NCH, RB, METRIC, 2>(iv, qv, cx, base, cnt, ckey, cid);
                 else if (ROWS == 4) base += eval_round<NCH, RB, METRIC, 4>(iv, qv, cx, base, cnt, ckey, cid);   // (half rows: every layer, as the oracle's space over Xh)
+                else if constexpr (ROWS == 5) base += eval_round<NCH, RB, METRIC, 5>(iv, qv, cx, base, cnt, ckey, cid);   // (per-dimension codes: every layer, as the space over Z)
                 else if (ROWS == 1 || (ROWS < 0 && full_rows)) base += eval_round<NCH, RB, METRIC, 1>(iv, qv, cx, base, cnt, ckey, cid);
                 else base += eval_round<NCH, RB, METRIC, 0>(iv, qv, cx, base, cnt, ckey, cid);
                 const uint32_t mk = wave_min_u32(ckey);
@@ -1369,6 +1396,7 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
                                                          reinterpret_cast<const char *>(iv.tail0) + (uint64_t)(uint32_t)c * (uint32_t)(iv.S0 * 16 * iv.tail_chunks), 0, col);
             else if (ROWS == 2) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 2, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);                                  // :573-577
             else if (ROWS == 4) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 4, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
+            else if constexpr (ROWS == 5) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 5, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else if (ROWS == 1 || (ROWS < 0 && full_rows)) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 1, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else hop_eval<NCH, RB, NSLOT, METRIC, SEM, 0, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
         }
@@ -1434,6 +1462,14 @@ __device__ __forceinline__ void query_bytes(WaveCtx &cx, const float4 (&qv)[NCH]
         cx.q2 = reduce16_i32((int32_t)sq);
     }
 }
+// per-dimension codes (ROWS 5): the lane's scales, one float4 per chunk, from the table in the lane grid ([64 * NCH] floats, 16-byte
+// aligned: one 16-byte load per chunk, once per query wave); they stay in registers beside qv
+template <int NCH>
+__device__ __forceinline__ void load_scales(WaveCtx &cx, const float *table) {
+    const float4 *t = reinterpret_cast<const float4 *>(table);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) cx.sv[i] = t[i * 16 + cx.l16];
+}
 // a database row as the query (rows are zero padded to the stride)
 template <int NCH>
 __device__ __forceinline__ void load_row(float4 (&qv)[NCH], const IndexView &iv, int node, int l16) {
@@ -1455,7 +1491,7 @@ __device__ __forceinline__ void load_row(float4 (&qv)[NCH], const IndexView &iv,
 constexpr int search_min_waves(int NCH, int NSLOT, int METRIC, int ROWS) {
     return (NCH <= 2 && NSLOT <= 2 && METRIC == 0 && ROWS == 1) ? 7 : (NCH == 2 && NSLOT <= 4 && METRIC == 0 && ROWS == 2) ? 8 : 1;
 }
-// SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3 | 4, see hop_round
+// SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3 | 4 | 5, see hop_round
 // BLK: 1 = Visited as bitmap blocks (a.blk_bits slots, iv.lcode / lcode0 present), see search_layer
 template <int NCH, int RB, int NSLOT, int METRIC, int SEMF, int ROWS, int BLK = 0>
 __global__ void __launch_bounds__(64, search_min_waves(NCH, NSLOT, METRIC, ROWS))
@@ -1483,6 +1519,7 @@ hnsw_search_kernel(const IndexView iv, const SearchArgs a) {
     float4 qv[NCH];
     load_query<NCH>(qv, a.Q + q * a.q_stride, iv.d, cx.l16);
     if (ROWS == 2) query_bytes<NCH>(cx, qv, iv.d);
+    if constexpr (ROWS == 5) load_scales<NCH>(cx, iv.sq8s);
     visited_clear(cx);
 
     uint32_t n_dist = 0, n_hops = 0, status = 0;
@@ -1643,13 +1680,14 @@ hnsw_descent_kernel(const IndexView iv, const float *Q, int64_t q_stride, int64_
     load_query<NCH>(qv, Q + q * q_stride, iv.d, cx.l16);
     if (stage && cx.r == 0) store_query<NCH>(qv, stage + q * q_stride, iv.d, cx.l16);   // Q may be host memory: keep a device copy
     if (ROWS == 2) query_bytes<NCH>(cx, qv, iv.d);
+    if constexpr (ROWS == 5) load_scales<NCH>(cx, iv.sq8s);
     int cur = iv.entry_point;
     if (lane == 0) cx.cand_id[0] = cur;
     __syncthreads();
     uint32_t cur_key;
-    if (ROWS == 2 || ROWS == 4) {     // (the compact rows: their own evaluation, as in the search kernel)
+    if constexpr (ROWS == 2 || ROWS == 4 || ROWS == 5) {     // (the compact rows: their own evaluation, as in the search kernel)
         uint32_t ck, ci;
-        hop_round<NCH, 1, METRIC, ROWS == 2 || ROWS == 4 ? ROWS : 1>(iv, qv, cx, 0, 1, ck, ci);
+        hop_round<NCH, 1, METRIC, ROWS>(iv, qv, cx, 0, 1, ck, ci);
         cur_key = rdlane(ck, 0);
     } else {
         eval_candidates<NCH, RB, METRIC>(iv, qv, cx.cand_id, cx.cand_key, cx.trash, 1, cx.r, cx.l16);

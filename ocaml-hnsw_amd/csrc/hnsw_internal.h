@@ -39,6 +39,11 @@ constexpr int rows_in_flight(int nch, bool compact = false) {
 // registers (pick_nslot_knn)
 constexpr bool has_odd_nslot(int nch) { return nch == 2 || nch == 4; }
 
+// ... and for the per-dimension codes' L2 walk (ROWS 5, hnsw_rows_sq8_dim.hip): a row in flight is a byte row's registers, but the
+// lane also holds NCH float4 of scales beside the query.  The byte rows' counts: with them no instance uses scratch memory
+// (DESIGN.md has the register table); NCH 16 holds one batch (its widest instance stands at 256 VGPRs).
+constexpr int rows_in_flight_sq8_dim(int nch) { return nch == 1 ? 8 : nch == 2 ? RB_NCH2 : nch == 4 ? 4 : nch == 8 ? 2 : 1; }
+
 template <int V> using Int = std::integral_constant<int, V>;
 // f(Int<NCH>) for the NCH that pick_nch returned
 template <class F> auto with_nch(int nch, F &&f) {
@@ -202,12 +207,14 @@ template <class Id> struct RangeRecord {
 };
 
 // Every device table an index holds: the vectors and the graph, and the copies derived from them -- byte rows (X8, hnsw_rows8.hip),
-// half rows (Xh, hnsw_rows16.hip), sq8 rows (Xq, hnsw_rows_sq8.hip), split rows (Xm / tail0, hnsw_rows_split.hip), locality codes
+// half rows (Xh, hnsw_rows16.hip), sq8 rows (Xq, hnsw_rows_sq8.hip), per-dimension sq8 rows (Xqd with their tables qd_lo / qd_s,
+// hnsw_rows_sq8_dim.hip), split rows (Xm / tail0, hnsw_rows_split.hip), locality codes
 // (lcode / lcode0, hnsw_locality.hip); a derived table that does not exist has p == nullptr.  bind_view points the handle's IndexView at them.
 struct IndexTables {
-    Table X, X8, Xh, Xq, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
+    Table X, X8, Xh, Xq, Xqd, qd_lo, qd_s, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
     template <class Self, class F> static void each(Self &t, F f) {
-        static constexpr Table IndexTables::*all[] = {&IndexTables::X, &IndexTables::X8, &IndexTables::Xh, &IndexTables::Xq, &IndexTables::Xm,
+        static constexpr Table IndexTables::*all[] = {&IndexTables::X, &IndexTables::X8, &IndexTables::Xh, &IndexTables::Xq, &IndexTables::Xqd,
+                                                      &IndexTables::qd_lo, &IndexTables::qd_s, &IndexTables::Xm,
                                                       &IndexTables::tail0, &IndexTables::lcode, &IndexTables::lcode0, &IndexTables::nbr0, &IndexTables::nbrU,
                                                       &IndexTables::off, &IndexTables::lvl, &IndexTables::ref};
         for (Table IndexTables::*m : all) f(t.*m);
@@ -495,6 +502,11 @@ struct hnsw_index {
     // sq8_lo / sq8_scale describe tables.Xq whenever it exists.  hnsw_index_insert quantises the whole grown table again while it is on.
     bool sq8_on = false;
     float sq8_lo = 0.0f, sq8_scale = 1.0f;
+    // option "sq8_dim_rows": the knn searches walk tables.Xqd, the 8-bit codes of x_i ~ lo_i + s_i * code under one affine map per
+    // dimension (1), or it is off (0, -1).  sq8d_lo / sq8d_scale ([d] each; on the device tables.qd_lo / qd_s in the lane grid)
+    // describe tables.Xqd whenever it exists.  hnsw_index_insert and hnsw_index_remove quantise the whole table again while it is on.
+    bool sq8d_on = false;
+    std::vector<float> sq8d_lo, sq8d_scale;
     // option "filter_collect": the filtered searches answer from every node the walk evaluates, not from the final W only
     // (hnsw_search_collect_kernel; k <= 128, exact-row formats: it excludes half_rows and sq8_rows).  Not saved.
     bool filter_collect = false;
@@ -551,7 +563,8 @@ inline int DeviceGroup::adopt(::hnsw_index *idx, int device) {
 
 // hnsw_capi.hip: IndexView's table pointers from idx->tables (X8 / Xm left out while option byte_rows / split_rows is 0; Xh in
 // the view while option half_rows is 1 and no byte rows are: it takes the place of Xm; Xq in the byte rows' place while option
-// sq8_rows is 1 and no byte rows are: Xm steps aside too), and the hnsw_index_info fields that
+// sq8_rows is 1 and no byte rows are: Xm steps aside too; Xqd there, and qd_s in tail0's place, while option sq8_dim_rows is 1
+// and no byte rows are), and the hnsw_index_info fields that
 // restate the view (n, max_degree0, max_layer, entry_point, row_stride_bytes, row_format).  Called by every change of the tables
 // or of those options.
 void bind_view(::hnsw_index *idx);
@@ -602,6 +615,21 @@ int make_sq8_rows(::hnsw_index *idx);
 // inner product, zero beyond d.  Q may be a registered host matrix seen from the device; stage (optional, [nq][q_stride] device
 // floats) then receives the queries as they were read.  Q == Qt (same stride) is allowed.
 int sq8_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st);
+// hnsw_rows_sq8_dim.hip: the 8-bit codes of tables.X under one affine map per dimension (tables.Xqd / qd_lo / qd_s, sq8d_lo,
+// sq8d_scale), all or nothing: HNSW_ERR_UNSUPPORTED, naming the first such column, when a value is NaN or infinite, a column's
+// max - min overflows or its step rounds to 0; HNSW_ERR_OOM when there is no room.  Leaves the view to the caller (bind_view).
+int make_sq8_dim_rows(::hnsw_index *idx);
+// ... and nq queries as the walk over those codes reads them, on `st`: Qt ([nq][padded_stride(d)] floats) = Q - lo for L2, s * Q
+// for the inner product, zero beyond d.  Q, stage and Q == Qt: as sq8_transform_queries.
+int sq8_dim_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st);
+// ... the transform of whichever codes the index walks (walks_codes)
+inline int codes_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st);
+// hnsw_sq8_dim_walk.hip, one object per accept rule (0 Ohnsw, 1 functor): the knn kernel's ROWS = 5 instances, the L2 walk over
+// those codes -- what a variant object of hnsw_search_variants.hip exports, for the one metric the format has a kernel for
+hipError_t search_launch_sq8_dim_0(int nch, int nslot, const hnsw_dev::IndexView &iv, const hnsw_dev::SearchArgs &a, hipStream_t st);
+hipError_t search_launch_sq8_dim_1(int nch, int nslot, const hnsw_dev::IndexView &iv, const hnsw_dev::SearchArgs &a, hipStream_t st);
+int search_occupancy_sq8_dim_0(int nch, int nslot, size_t lds, int blk);
+int search_occupancy_sq8_dim_1(int nch, int nslot, size_t lds, int blk);
 // hnsw_rows_split.hip: if a row ends 1..32 bytes past a 128-byte line (and there are no byte rows), build the split copy
 // (tables.Xm / tail0, iv.stride_m / main_chunks / tail_chunks); call after make_byte_rows, graph in place
 int make_split_rows(::hnsw_index *idx);
@@ -686,10 +714,22 @@ struct ScanCut : ScanPlan {
     dim3 grid(int64_t nq) const;
 };
 ScanCut scan_cut(const ::hnsw_index *idx, int64_t m, int k, int64_t cell_bytes, int64_t cap);
-// the walk's distances are not exact over X (half, sq8 rows): what is kept of W is re-ranked over the float32 rows
-inline bool walk_is_inexact(const ::hnsw_index *idx) {
-    return idx->info.row_format == HNSW_ROWS_HALF || idx->info.row_format == HNSW_ROWS_SQ8;
+// the walk reads codes (sq8 rows, per-dimension sq8 rows): its queries are moved to the codes' space first, its distances mean
+// nothing to a caller, and it always ends in the re-rank over the float32 rows
+inline bool walks_codes(const ::hnsw_index *idx) {
+    return idx->info.row_format == HNSW_ROWS_SQ8 || idx->info.row_format == HNSW_ROWS_SQ8_DIM;
 }
+// ... and is either option on (even while byte rows stand in front of the codes)?  Its name, for messages
+inline bool codes_on(const ::hnsw_index *idx) { return idx->sq8_on || idx->sq8d_on; }
+inline const char *codes_option(const ::hnsw_index *idx) {
+    return idx->sq8d_on || idx->info.row_format == HNSW_ROWS_SQ8_DIM ? "sq8_dim_rows" : "sq8_rows";
+}
+inline int codes_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st) {
+    return idx->info.row_format == HNSW_ROWS_SQ8_DIM ? sq8_dim_transform_queries(idx, Q, nq, q_stride, Qt, stage, st)
+                                                     : sq8_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
+}
+// the walk's distances are not exact over X (half rows, codes): what is kept of W is re-ranked over the float32 rows
+inline bool walk_is_inexact(const ::hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_HALF || walks_codes(idx); }
 // the filter the unfiltered searches answer under: the live nodes while some are marked deleted, else none
 inline const ::hnsw_filter *live_filter(const ::hnsw_index *idx) { return idx->n_deleted > 0 ? idx->live.get() : nullptr; }
 // hnsw_filter.hip: what every filtered entry point checks of one filter of the call (null, foreign, outgrown, stale: HNSW_ERR_BAD_ARG)

@@ -95,8 +95,17 @@ hipError_t launch_descent(const hnsw_index *idx, int row_format, const float *Q,
                                idx->iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage);
         }); });
     };
+    if (row_format == HNSW_ROWS_SQ8_DIM && idx->info.metric == HNSW_METRIC_L2) {
+        // the per-dimension codes under L2: the kernel's ROWS 5, the rows in flight of the knn kernel of that format (under the
+        // inner product they are byte rows: below)
+        with_nch(pick_nch(idx->iv.nchunks), [&](auto NCH) {
+            hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<NCH, rows_in_flight_sq8_dim(NCH), 0, 5>), dim3((unsigned)nq), dim3(64), lds, st,
+                               idx->iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, stage);
+        });
+        return hipGetLastError();
+    }
     switch (row_format) {
-    case HNSW_ROWS_BYTES: case HNSW_ROWS_SQ8: rows(Int<2>{}); break;       // (sq8: the codes in the byte rows' place, the queries in code space)
+    case HNSW_ROWS_BYTES: case HNSW_ROWS_SQ8: case HNSW_ROWS_SQ8_DIM: rows(Int<2>{}); break;   // (sq8: the codes in the byte rows' place, the queries in code space)
     case HNSW_ROWS_HALF: rows(Int<4>{}); break;
     default: rows(Int<-1>{}); break;
     }

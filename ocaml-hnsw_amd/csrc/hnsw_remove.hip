@@ -155,7 +155,7 @@ extern "C" int32_t hnsw_index_remove(hnsw_index *idx, const int64_t *ids, int64_
         (void)hipGetLastError();
         return rc;
     }
-    // byte rows (they may appear now), split, half and sq8 rows follow as after an insert; the locality codes are dropped and
+    // byte rows (they may appear now), split, half and sq8 rows (either kind) follow as after an insert; the locality codes are dropped and
     // built again on demand
     if ((rc = adopt_graph(idx, nx, /*carry_codes=*/false, 0, 0, plan.new_id.data()))) return rc;
     if (out_new_id) for (int64_t v = 0; v < n_old; ++v) out_new_id[v] = plan.new_id[(size_t)v] + base;      // removed: id_base - 1

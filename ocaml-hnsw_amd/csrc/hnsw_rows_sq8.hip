@@ -11,7 +11,8 @@
 // code space, never reach the caller: an sq8 search always ends in the exact re-rank over the float32 rows (hnsw_rerank.hip,
 // refine_count in hnsw_capi.hip).  The copy is made on request only (option "sq8_rows").  The float32 rows stay: the builder,
 // the layer operators, hnsw_distance_batch, the exact scan and hnsw_index_insert's searches use them.
-// (A scale per dimension would quantise finer, but its distance is a weighted one: a kernel family of its own.  Not here.)
+// (A scale per dimension quantises finer, but its L2 distance is a weighted one: a kernel family of its own, option "sq8_dim_rows",
+// hnsw_rows_sq8_dim.hip.)
 #include "hnsw_internal.h"
 
 using namespace hnsw_host;

@@ -48,9 +48,11 @@ inline void check(int rc) {
 
 // hnsw_index_info.row_format: what the knn searches read (HNSW_ROWS_*); HALF only after hnsw_index_set_option(h, "half_rows", 1),
 // which makes them search the vectors rounded to fp16; SQ8 only after hnsw_index_set_option(h, "sq8_rows", 1), which makes them
-// walk 8-bit codes of the vectors and re-rank over the float32 rows
+// walk 8-bit codes of the vectors and re-rank over the float32 rows; SQ8_DIM only after hnsw_index_set_option(h, "sq8_dim_rows", 1):
+// the same with one affine map per dimension
 namespace Rows {
 constexpr int F32 = HNSW_ROWS_F32, BYTES = HNSW_ROWS_BYTES, SPLIT = HNSW_ROWS_SPLIT, HALF = HNSW_ROWS_HALF, SQ8 = HNSW_ROWS_SQ8;
+constexpr int SQ8_DIM = HNSW_ROWS_SQ8_DIM;
 }
 
 // Flattened Ohnsw.Hgraph.t / Hnsw.Ba.Hgraph.t resident on the device.
@@ -170,6 +172,18 @@ inline Sq8 sq8(const Hgraph &g) {
     Sq8 out{0.0f, 1.0f, std::vector<uint8_t>((size_t)inf.n * (size_t)inf.d)};
     check(hnsw_index_sq8_params(g.handle(), &out.lo, &out.scale));
     check(hnsw_index_sq8_codes(g.handle(), out.codes.data()));
+    return out;
+}
+
+// The per-dimension sq8 copy of an index (hnsw_index_set_option(h, "sq8_dim_rows", 1)): x[i] ~ lo[i] + scale[i] * code[i]; lo, scale:
+// [d]; codes: [n][d] bytes.  Throws std::invalid_argument when the index has no such copy.
+struct Sq8Dim { std::vector<float> lo, scale; std::vector<uint8_t> codes; };
+inline Sq8Dim sq8_dim(const Hgraph &g) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    Sq8Dim out{std::vector<float>((size_t)inf.d), std::vector<float>((size_t)inf.d), std::vector<uint8_t>((size_t)inf.n * (size_t)inf.d)};
+    check(hnsw_index_sq8_dim_params(g.handle(), out.lo.data(), out.scale.data()));
+    check(hnsw_index_sq8_dim_codes(g.handle(), out.codes.data()));
     return out;
 }
 

@@ -87,6 +87,12 @@ let hnsw_index_sq8_params =
   foreign ~from:lib "hnsw_index_sq8_params" (index @-> ptr float @-> ptr float @-> returning int32_t)
 let hnsw_index_sq8_codes =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_sq8_codes" (index @-> ptr void @-> returning int32_t)
+(* the per-dimension sq8 copy (`hnsw_index_set_option idx "sq8_dim_rows" 1L`: one affine map per dimension, a weighted L2 walk, see
+   the C header): its parameters lo and scale, [d] floats each (x_i ~ lo_i + scale_i * code_i), and its codes, [n][d] bytes *)
+let hnsw_index_sq8_dim_params =
+  foreign ~from:lib "hnsw_index_sq8_dim_params" (index @-> ptr float @-> ptr float @-> returning int32_t)
+let hnsw_index_sq8_dim_codes =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_sq8_dim_codes" (index @-> ptr void @-> returning int32_t)
 (* cosine distance (metric_cosine below; the twin contract of the C header): the normaliser N as an operator of its own, and the
    float32 rows an index holds -- for a cosine index N(X), not the vectors it was handed *)
 let hnsw_normalise_batch =
@@ -279,12 +285,14 @@ let ii_device = field index_info "device" int32_t
 let ii_row_format = field index_info "row_format" int32_t
 (* its values, HNSW_ROWS_*: float32 rows, byte rows, split rows, half rows (only after `hnsw_index_set_option idx
    "half_rows" 1L`: the search over the vectors rounded to fp16), sq8 rows (only after `hnsw_index_set_option idx "sq8_rows" 1L`:
-   the walk over 8-bit codes, re-ranked over the float32 rows) *)
+   the walk over 8-bit codes, re-ranked over the float32 rows), per-dimension sq8 rows (only after `hnsw_index_set_option idx
+   "sq8_dim_rows" 1L`: the same with one affine map per dimension) *)
 let rows_f32 = 0l
 let rows_bytes = 2l
 let rows_split = 3l
 let rows_half = 4l
 let rows_sq8 = 5l
+let rows_sq8_dim = 6l
 let () = seal index_info
 let hnsw_index_get_info = foreign ~from:lib "hnsw_index_get_info" (index @-> ptr index_info @-> returning int32_t)
 (* the flattened graph of a device index (built there by hnsw_build, or loaded from a file) back to the host *)
@@ -1150,6 +1158,19 @@ let sq8_codes (t : t) : (int, Bigarray.int8_unsigned_elt, Bigarray.c_layout) Big
   check (hnsw_index_get_info t.handle (addr inf));
   let out = Bigarray.Array2.create Bigarray.int8_unsigned Bigarray.c_layout (max 1 (Int64.to_int (getf inf ii_n))) t.dim in
   check (hnsw_index_sq8_codes t.handle (to_voidp (bigarray_start array2 out)));
+  out
+
+(* the per-dimension sq8 copy of the index (option "sq8_dim_rows"): (lo, scale), d values each, and the codes, one row of d bytes
+   per node; Invalid_argument when the index has no such copy *)
+let sq8_dim_params (t : t) : float array * float array =
+  let lo = CArray.make float t.dim and scale = CArray.make float t.dim in
+  check (hnsw_index_sq8_dim_params t.handle (CArray.start lo) (CArray.start scale));
+  (Array.of_list (CArray.to_list lo), Array.of_list (CArray.to_list scale))
+let sq8_dim_codes (t : t) : (int, Bigarray.int8_unsigned_elt, Bigarray.c_layout) Bigarray.Array2.t =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let out = Bigarray.Array2.create Bigarray.int8_unsigned Bigarray.c_layout (max 1 (Int64.to_int (getf inf ii_n))) t.dim in
+  check (hnsw_index_sq8_dim_codes t.handle (to_voidp (bigarray_start array2 out)));
   out
 
 (* ?metric of [create], [build], [of_ohnsw], [of_ba] and [sharded_build]: HNSW_METRIC_L2, _IP, _COSINE.  A cosine index stores
