@@ -1253,6 +1253,74 @@ int32_t hnsw_sharded_range_result_destroy(hnsw_sharded_range_result *r);
 int32_t hnsw_merge_segments(int32_t device, int32_t n_lists, int64_t nq, const int64_t *const *lims, const int32_t *const *ids,
                             const float *const *dist, const int64_t *first_row, int32_t id_base, hnsw_sharded_range_result **out);
 
+/* ---- grouped search: the k nearest GROUPS, one node per label ("group by", "collapse": chunked documents, tenants, products) ----
+ * THE LABELS.  hnsw_labels_create uploads one label per node (labels: a host array of n values, not retained).  n must be the
+ * index's current n, n_labels >= 1, each label in -1 .. n_labels - 1, where -1 means the node is in no group; any other value is
+ * HNSW_ERR_BAD_ARG, found on the host before anything is allocated, and *out is NULL.  A node marked deleted
+ * (hnsw_index_mark_deleted) gets -1 in the device copy; hnsw_labels_get copies the n labels as the device holds them back to the
+ * host.  The object belongs to the handle and its graph epoch: after hnsw_index_insert, hnsw_index_remove,
+ * hnsw_index_mark_deleted or hnsw_index_unmark_deleted it is stale and every call that takes it answers HNSW_ERR_BAD_ARG, as for a
+ * filter.  hnsw_labels_info reports n_labels, n_labelled (the nodes with a label >= 0) and n_groups (the labels at least one node
+ * carries), both counted on the device at creation; each pointer may be NULL.  Cost: 4 * n bytes on the device, NOT counted in
+ * hnsw_index_info.device_bytes.  Not saved with the index.  Any number of label objects per index; hnsw_labels_destroy(NULL) is HNSW_OK.
+ *
+ * THE RESULT of hnsw_search_batch_grouped, in terms of public calls only.  A node is ELIGIBLE when its label is >= 0 and, with a
+ * filter (f may be NULL), it is allowed.  For an ordered list S of node ids let G(S) be the subsequence that keeps the first
+ * eligible member of each label.  W_e(q) is as the filtered section defines it: the ids hnsw_search_batch returns for (ef = e,
+ * k = e) with the caller's semantics, the host form.
+ *   1. LADDER.  e_0 = ef, e_{j+1} = min(1024, 2 * e_j).  A query is served at the first stage j with |G(W_{e_j}(q))| >= k; its
+ *      answer is the first k members of G(W_{e_j}(q)).  Only the queries still short are searched again at the next stage, as one
+ *      compacted batch.  The walk itself is never filtered or grouped: it is the walk every other entry point runs.
+ *   2. EXACT STAGE.  A query still short at e = 1024, and EVERY query, with no walk made, when n_groups < k or f->n_allowed < k,
+ *      gets what hnsw_brute_force_batch_grouped returns: for each label the eligible node smallest under the scan's order -- the
+ *      ordered pre-square-root key, then the node id, over the float32 rows -- and of those the k smallest, ascending.  With fewer
+ *      than k groups the first entries are real and the rest filled per params->fill: id -1, label -1, distance NaN
+ *      (HNSW_FILL_OHNSW) or +inf (HNSW_FILL_BA).
+ *   3. DISTANCES ARE ALWAYS OVER THE FLOAT32 ROWS: the bits of hnsw_distance_batch for the returned ids.
+ *        - byte, split and float32 rows: the walk's distances are those bits already.
+ *        - HNSW_ROWS_HALF, HNSW_ROWS_SQ8 and HNSW_ROWS_SQ8_DIM: ALL eligible members of W_e(q) are first re-ranked over the float32
+ *          rows by hnsw_rerank_batch's kernel (the ineligible members as padding, k := e), at every stage the query walks, and G is
+ *          taken over that re-ranked list.  The stage test is unchanged: it does not depend on the order.
+ *   4. OUTPUTS.  out_ids [nq][k] (id_base-based), out_dist [nq][k], ascending, out_labels [nq][k].  out_stage (optional, [nq]): j
+ *      for a query served at ladder stage j, 0xFFFFFFFF for the exact stage.  out_nhops (optional): the sum of the hops of the walks
+ *      taken (0 without a walk).  out_ndist (optional): the walks' evaluations, plus the members re-ranked (half / sq8 rows: the
+ *      eligible members of W at each stage walked), plus n_labelled for the exact stage -- with a filter that last term is
+ *      f->n_allowed.
+ *   5. ERRORS are those of hnsw_search_batch_filtered.  k > ef: HNSW_ERR_BAD_ARG; ef > 1024: HNSW_ERR_UNSUPPORTED;
+ *      HNSW_SEM_FUNCTOR_NEAREST_K: HNSW_ERR_BAD_ARG; an empty index: HNSW_ERR_EMPTY_INDEX; null, foreign or stale labels, a
+ *      foreign or stale filter: HNSW_ERR_BAD_ARG; null pointers, q_stride and nq as hnsw_search_batch; nq == 0 is a no-op.  An error
+ *      leaves the outputs untouched.  Matrices of hnsw_host_alloc / hnsw_host_register are read and written in place, others are
+ *      copied; complete on return.
+ *   6. DETERMINISM.  A row depends on the query's own vector, the labels, the mask and (ef, k, semantics) only: not on the batch
+ *      it is in, and not on which stage other queries reached.
+ * ONE filtered, range or grouped call in flight per handle: they share the ladder's and the filtered search's scratch.  There is
+ * no device-pointer form.
+ *
+ * hnsw_brute_force_batch_grouped is the exact form: the rows point 2 describes, for every query.  k in 1..1024: k < 1 or a bad
+ * fill is HNSW_ERR_BAD_ARG, k > 1024 HNSW_ERR_UNSUPPORTED.  It needs no graph, always scans the float32 rows, and its result does
+ * not depend on option "scan_slabs" or on the batch.  Scratch: one 64-bit cell per (query, label), 8 * n_labels bytes per query of
+ * a piece of the batch (pieces of at most 256 MiB, never below one tile of the scan); it belongs to the handle and is not counted
+ * in device_bytes; if it cannot be allocated the call answers HNSW_ERR_OOM with the outputs untouched.
+ *
+ * NOT BUILT: more than one member per group (group_size > 1); one label object per query; hnsw_sharded_* grouped forms (a borrowed
+ * shard or replica handle is served like any handle); option "filter_collect" for this call (the option is ignored here).
+ * Rates (tools/group_rate.py, profiles/grouped.txt; one run), MI355X, 1 M x 128 byte rows, ef 128, k 10, 10 k queries: all-distinct
+ * labels 1.81 ms per batch, random groups of 10 nodes 1.79 ms, against 0.86 ms for hnsw_search_batch and 6.3 - 6.6 ms for
+ * hnsw_search_batch_filtered under an all-ones mask on the same handle; 256 far-apart clusters as labels: 336 ms, every query ends
+ * in the exact stage; the exact stage alone: 0.028 / 0.042 / 0.068 ms per query for 10^3 / 10^5 / 10^6 labels (64 queries). */
+typedef struct hnsw_labels hnsw_labels;
+int32_t hnsw_labels_create(hnsw_index *idx, const int32_t *labels, int64_t n, int32_t n_labels, hnsw_labels **out);
+int32_t hnsw_labels_destroy(hnsw_labels *l);                       /* NULL is HNSW_OK */
+int32_t hnsw_labels_info(const hnsw_labels *l, int32_t *n_labels, int64_t *n_labelled, int64_t *n_groups);  /* each may be NULL */
+int32_t hnsw_labels_get(const hnsw_labels *l, int32_t *out);       /* the n labels as the device holds them */
+int32_t hnsw_search_batch_grouped(hnsw_index *idx, const hnsw_labels *labels, const hnsw_filter *f /* may be NULL */,
+                                  const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
+                                  int32_t *out_ids, float *out_dist, int32_t *out_labels,
+                                  uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage);
+int32_t hnsw_brute_force_batch_grouped(hnsw_index *idx, const hnsw_labels *labels, const hnsw_filter *f /* may be NULL */,
+                                       const float *queries, int64_t nq, int64_t q_stride, int32_t k, int32_t fill,
+                                       int32_t *out_ids, float *out_dist, int32_t *out_labels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,12 @@ _ABI = {
     "hnsw_host_unregister": [_vp],
     "hnsw_host_alloc": [_vp, _i64],
     "hnsw_host_free": [_vp],
+    "hnsw_labels_create": [_vp, _vp, _i64, _i32, _vp],
+    "hnsw_labels_destroy": [_vp],
+    "hnsw_labels_info": [_vp, _vp, _vp, _vp],
+    "hnsw_labels_get": [_vp, _vp],
+    "hnsw_search_batch_grouped": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_brute_force_batch_grouped": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -550,6 +556,12 @@ class Hgraph:
         _check(load().hnsw_filter_create_by_label(self.handle, _ptr(lab) if lab.size else None, lab.size, n_labels, out))
         return [Filter._adopt(self, _C.c_void_p(out[l]), lab.size) for l in range(n_labels)]
 
+    def labels(self, labels, n_labels=None):
+        """hnsw_labels_create -> Labels: one label per node (0-based position in `labels`; -1: the node is in no group), uploaded once:
+        the groups of Ohnsw.knn_batch_grouped.  n_labels defaults to max label + 1.  Valid until the index changes (insert_batch,
+        remove_batch, mark_deleted, unmark_deleted)."""
+        return Labels(self, labels, n_labels)
+
     def mark_deleted(self, ids):
         """hnsw_index_mark_deleted: soft deletion.  The stored nodes `ids` (id_base-based, distinct) stay in the graph -- every walk
         still goes through them -- but no search returns them any more: while any node is marked, the knn, brute-force and range
@@ -732,6 +744,66 @@ class Filter(_Owner):
         out = _np.zeros((self.n + 31) // 32, _np.uint32)
         _check(load().hnsw_filter_bits(self.handle, _ptr(out) if len(out) else _C.byref(_C.c_uint32())))
         return out
+
+
+class Labels(_Owner):
+    """One label per node of one index, resident on its device (hnsw_labels_create); see Hgraph.labels."""
+    _slot, _destroy, _gone = "_l", "hnsw_labels_destroy", "labels already released"
+
+    def __init__(self, hgraph, labels, n_labels=None):
+        self._l = None
+        lab = _np.asarray(labels)
+        if lab.dtype.kind not in "iu" or lab.ndim != 1:
+            raise InvalidArgument("labels must be a vector of integers, one per node")
+        if lab.size and (lab.min() < -(2 ** 31) or lab.max() >= 2 ** 31):
+            raise InvalidArgument("labels must fit 32 bits")
+        lab = _np.ascontiguousarray(lab, _np.int32)
+        if n_labels is None:
+            n_labels = max(int(lab.max()) + 1, 1) if lab.size else 1
+        if n_labels < 1:
+            raise InvalidArgument("n_labels must be >= 1")
+        h = _C.c_void_p()
+        _check(load().hnsw_labels_create(hgraph.handle, _ptr(lab) if lab.size else None, lab.size, int(n_labels), _C.byref(h)))
+        self._l, self._hg, self.n = h, hgraph, lab.size
+
+    def info(self):
+        """hnsw_labels_info -> (n_labels, n_labelled, n_groups): nodes with a label >= 0, labels at least one node carries"""
+        a, b, c = _C.c_int32(0), _C.c_int64(0), _C.c_int64(0)
+        _check(load().hnsw_labels_info(self.handle, _C.byref(a), _C.byref(b), _C.byref(c)))
+        return a.value, b.value, c.value
+
+    def get(self):
+        """hnsw_labels_get: the n labels as the device holds them (-1 where the node was marked deleted at creation)"""
+        out = _np.zeros(self.n, _np.int32)
+        _check(load().hnsw_labels_get(self.handle, _ptr(out) if self.n else _C.byref(_C.c_int32())))
+        return out
+
+
+def _grouped_args(hgraph, labels, flt):
+    if not isinstance(labels, Labels):
+        raise InvalidArgument("labels must be a Labels object (Hgraph.labels)")
+    own = None if flt is None or isinstance(flt, Filter) else Filter(hgraph, flt)
+    return own, (None if flt is None else (own or flt).handle)
+
+
+def _search_grouped(hgraph, labels, batch, ef, k, fill, counters=False, sem=0, flt=None):
+    """hnsw_search_batch_grouped; labels: a Labels; flt: None, a Filter, or what Hgraph.filter takes
+    -> (ids, dist, labels), with counters (ids, dist, labels, ndist, nhops, stage)."""
+    own, fh = _grouped_args(hgraph, labels, flt)
+    try:
+        Q, qs, nq = _batch(hgraph.d, batch)
+        ids, dist = _out_pair(nq, k, None)
+        lab = _np.empty((nq, max(k, 0)), _np.int32)
+        nd = _np.zeros(nq, _np.uint32) if counters else None
+        nh = _np.zeros(nq, _np.uint32) if counters else None
+        stage = _np.zeros(nq, _np.uint32) if counters else None
+        p = _SearchParams(ef, k, fill, sem)
+        _check(load().hnsw_search_batch_grouped(hgraph.handle, labels.handle, fh, _ptr(Q), nq, qs, _C.byref(p), _ptr(ids), _ptr(dist), _ptr(lab),
+                                                _ptr(nd), _ptr(nh), _ptr(stage)))
+    finally:
+        if own is not None:
+            own.release()
+    return (ids, dist, lab, nd, nh, stage) if counters else (ids, dist, lab)
 
 
 def _search_filtered(hgraph, flt, batch, ef, k, fill, counters=False, sem=0, out=None):
@@ -981,6 +1053,32 @@ class Ohnsw:
         return ids, dist
 
     @staticmethod
+    def knn_batch_grouped(hgraph, k, batch, labels, ef=None, filter=None, counters=False):
+        """The k nearest GROUPS, one node per label (hnsw_search_batch_grouped) -> (ids, distances, labels), with counters (ids,
+        distances, labels, ndist, nhops, stage).  labels: a Labels (Hgraph.labels).  W grows ef, 2 ef, ... 1024 until it holds nodes
+        of k distinct labels (stage = how often it doubled), each label represented by its first member of W; a query still short
+        gets the exact grouped scan (stage = STAGE_EXACT).  filter (a Filter, or what Hgraph.filter takes): only allowed nodes
+        count.  Distances are over the float32 vectors whatever rows the index searches; id -1 / label -1 / NaN where there are
+        fewer than k groups."""
+        return _search_grouped(hgraph, labels, batch, k if ef is None else ef, k, FILL_OHNSW, counters, flt=filter)
+
+    @staticmethod
+    def brute_force_grouped(hgraph, k, batch, labels, filter=None, fill=FILL_OHNSW):
+        """The exact grouped search (hnsw_brute_force_batch_grouped) -> (ids, distances, labels): per label its nearest node under
+        (distance, id) over all n float32 vectors, of those the k nearest, ascending.  Needs no graph."""
+        own, fh = _grouped_args(hgraph, labels, filter)
+        try:
+            Q, qs, nq = _batch(hgraph.d, batch)
+            ids, dist = _out_pair(nq, int(k), None)
+            lab = _np.empty((nq, max(int(k), 0)), _np.int32)
+            _check(load().hnsw_brute_force_batch_grouped(hgraph.handle, labels.handle, fh, _ptr(Q), nq, qs, int(k), fill, _ptr(ids), _ptr(dist),
+                                                         _ptr(lab)))
+        finally:
+            if own is not None:
+                own.release()
+        return ids, dist, lab
+
+    @staticmethod
     def rerank(hgraph, k, batch, cand, fill=FILL_OHNSW, out=None):
         """hnsw_rerank_batch -> (ids, distances): for each query the k nearest of ITS candidates cand[q] (int32 [nq][cand_stride],
         entries below id_base are padding) over the float32 vectors, under (distance, id), ascending; ids [nq][k] (-1 past the
@@ -1154,6 +1252,12 @@ class Ba:
     def knn_batch_filtered_each(hgraph, batch, num_neighbours_search, num_neighbours, filters, which, counters=False):
         """knn_batch_filtered with one filter per query (see Ohnsw.knn_batch_filtered_each; the functor accept rule, +inf fill)."""
         return _search_filtered_each(hgraph, filters, which, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR)
+
+    @staticmethod
+    def knn_batch_grouped(hgraph, batch, num_neighbours_search, num_neighbours, labels, filter=None, counters=False):
+        """knn_batch over groups (see Ohnsw.knn_batch_grouped; the functor accept rule, 1-based ids in a 1-based index, +inf / -1
+        where there are fewer than k groups) -> (ids, distances, labels), with counters (..., ndist, nhops, stage)."""
+        return _search_grouped(hgraph, labels, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR, flt=filter)
 
     @staticmethod
     def range_search(hgraph, batch, num_neighbours_search, radius, counters=False, filter=None):

@@ -7,6 +7,7 @@
 #include "hnsw_remove_plan.h"
 #include "hnsw_mark_plan.h"
 #include "hnsw_shard_plan.h"
+#include "hnsw_group_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -349,6 +350,12 @@ struct FilterBufs {
     // (filter_plan): row -> query, tile -> filter, and per row the evaluations to add and whether the query took no walk
     DevBuf masks, which, rows;
 };
+// ... of the grouped calls (hnsw_group.hip), beside the ladder's and the filtered search's buffers, which they use too
+struct GroupBufs {
+    DevBuf best;                         // the exact stage: best[piece][n_labels] words (key << 32 | row), all ones = no node yet
+    DevBuf lab, rlab;                    // out_labels [nq][k]; the labels column of a compact [m][k] result
+    DevBuf part_words, part_lab;         // ... of a row of many cells: the k smallest words of each of its stripes and their labels
+};
 // ... of the range calls.  What a caller keeps (lims, ids, distances, counters) belongs to the hnsw_range_result instead.
 constexpr int RANGE_STAGES = 11;         // the longest ladder: ef = 1, 2, 4, ... 1024
 struct RangeBufs {
@@ -423,6 +430,17 @@ struct hnsw_filter {
     hnsw_host::DevBuf bits;
     static size_t table_offset(int64_t n) { return ((size_t)std::max<int64_t>((n + 31) / 32, 1) * 4 + 7) / 8 * 8; }
     const uint32_t *const *table() const { return (const uint32_t *const *)((const char *)bits.p + table_offset(n)); }
+};
+
+// one label per node of one index (hnsw_labels_create): the groups of hnsw_search_batch_grouped.  Bound to the handle, its n and
+// its graph epoch as a filter is.
+struct hnsw_labels {
+    const hnsw_index *idx = nullptr;
+    int64_t n = 0;
+    uint64_t epoch = 0;
+    int32_t n_labels = 0;
+    int64_t n_labelled = 0, n_groups = 0;    // nodes with a label >= 0; labels a node carries (labels_prepare_kernel)
+    hnsw_host::DevBuf lab;                   // [n] int32, -1 where the node has no label or was marked deleted at creation
 };
 
 // what a range call returns: lims, ids, distances and the per-query counters on the device of the index they came from
@@ -515,6 +533,7 @@ struct hnsw_index {
     hnsw_host::LadderBufs ladder_scratch;
     hnsw_host::FilterBufs filter_scratch;
     hnsw_host::RangeBufs range_scratch;
+    hnsw_host::GroupBufs group_scratch;  // the grouped calls: they share ladder_scratch and filter_scratch with the filtered call
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica) or an hnsw_sharded (hnsw_sharded_shard): not grown or shrunk on its own (hnsw_index_insert, hnsw_index_remove)
     // the graph epoch: every successful hnsw_index_insert and hnsw_index_remove moves it on (adopt_graph).  A filter records the
     // epoch it was made in: n alone would let a mask through after "remove 5, insert 5"

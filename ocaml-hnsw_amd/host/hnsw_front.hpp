@@ -6,6 +6,8 @@
 //   Hnsw::Filter, Hnsw::Ohnsw::knn_filtered                                                (hnsw_filter_*, hnsw_search_batch_filtered)
 //   Hnsw::Filter::by_label / bits, Hnsw::Ohnsw::knn_filtered_each                          (hnsw_filter_create_by_label, hnsw_filter_bits,
 //                                                                                           hnsw_search_batch_filtered_each)
+//   Hnsw::Labels, Hnsw::Ohnsw::knn_grouped / brute_force_grouped                           (hnsw_labels_*, hnsw_search_batch_grouped,
+//                                                                                           hnsw_brute_force_batch_grouped)
 //   Hnsw::RangeResult, Hnsw::Ohnsw::range_search / brute_force_range                       (hnsw_range_*; with a Filter: the _filtered forms)
 //   Hnsw::Ohnsw::mark_deleted / unmark_deleted / deleted_count / deleted_mask / compact    (hnsw_index_mark_deleted ... hnsw_index_compact)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
@@ -124,6 +126,34 @@ public:
 private:
     Filter(hnsw_filter *f, int64_t n) : f_(f), n_(n) {}
     hnsw_filter *f_ = nullptr;
+    int64_t n_ = 0;
+};
+
+// One label per node of one index, resident on its device (hnsw_labels_create): the groups of Ohnsw::knn_grouped.  labels[v] in
+// -1 .. n_labels - 1, -1: node v is in no group.  One entry per node; refused once the index has changed (Ohnsw::insert,
+// Ohnsw::remove, mark_deleted, unmark_deleted).  Destroy it before its index.
+class Labels {
+public:
+    Labels(const Hgraph &g, const std::vector<int32_t> &labels, int n_labels) : n_((int64_t)labels.size()) {
+        check(hnsw_labels_create(g.handle(), labels.data(), n_, n_labels, &l_));
+    }
+    Labels(const Labels &) = delete;
+    Labels &operator=(const Labels &) = delete;
+    Labels(Labels &&o) noexcept : l_(o.l_), n_(o.n_) { o.l_ = nullptr; }
+    ~Labels() { if (l_) hnsw_labels_destroy(l_); }
+    const hnsw_labels *handle() const { return l_; }
+    struct Info { int32_t n_labels; int64_t n_labelled, n_groups; };
+    // n_labelled: the nodes with a label >= 0; n_groups: the labels at least one node carries
+    Info info() const { Info i{}; check(hnsw_labels_info(l_, &i.n_labels, &i.n_labelled, &i.n_groups)); return i; }
+    // the labels as the device holds them (hnsw_labels_get): -1 where the node was marked deleted at creation
+    std::vector<int32_t> get() const {
+        std::vector<int32_t> out((size_t)n_ + 1, 0);
+        check(hnsw_labels_get(l_, out.data()));
+        out.pop_back();
+        return out;
+    }
+private:
+    hnsw_labels *l_ = nullptr;
     int64_t n_ = 0;
 };
 
@@ -441,6 +471,35 @@ inline Filtered knn_filtered_each(const Hgraph &g, const std::vector<Filter> &fi
     hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
     check(hnsw_search_batch_filtered_each(g.handle(), table.data(), (int32_t)table.size(), which.data(), batch.data, batch.dim2, batch.dim1, &p,
                                           out.ids.data(), out.dist.data(), nullptr, nullptr, out.stage.data()));
+    return out;
+}
+
+// The k nearest GROUPS, one node per label (hnsw_search_batch_grouped): W grows ef, 2 ef, ... 1024 until it holds nodes of k distinct
+// labels, each label represented by its first eligible member of W; a query still short gets the exact grouped scan.  f (optional):
+// only the nodes it allows count.  ids / distances / labels [nq][k] (-1 / NaN / -1 where there are fewer than k groups); stage as
+// knn_filtered's.
+struct Grouped {
+    static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
+    std::vector<int32_t> ids; std::vector<float> dist; std::vector<int32_t> labels; std::vector<uint32_t> stage;
+};
+inline Grouped knn_grouped(const Hgraph &g, const Labels &l, int k, const Mat &batch, int ef = 0, const Filter *f = nullptr,
+                           int sem = HNSW_SEM_OHNSW, int fill = HNSW_FILL_OHNSW) {
+    const size_t nq = (size_t)batch.dim2, cells = nq * (size_t)(k > 0 ? k : 0);
+    Grouped out{std::vector<int32_t>(cells, -1), std::vector<float>(cells, 0.f), std::vector<int32_t>(cells, -1), std::vector<uint32_t>(nq, 0u)};
+    hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
+    check(hnsw_search_batch_grouped(g.handle(), l.handle(), f ? f->handle() : nullptr, batch.data, batch.dim2, batch.dim1, &p, out.ids.data(),
+                                    out.dist.data(), out.labels.data(), nullptr, nullptr, out.stage.data()));
+    return out;
+}
+// ... its exact form (hnsw_brute_force_batch_grouped): per label its nearest node under (distance, id) over all stored vectors, of
+// those the k nearest, ascending.  Needs no graph; every stage reads exact_stage.
+inline Grouped brute_force_grouped(const Hgraph &g, const Labels &l, int k, const Mat &batch, const Filter *f = nullptr,
+                                   int fill = HNSW_FILL_OHNSW) {
+    const size_t nq = (size_t)batch.dim2, cells = nq * (size_t)(k > 0 ? k : 0);
+    Grouped out{std::vector<int32_t>(cells, -1), std::vector<float>(cells, 0.f), std::vector<int32_t>(cells, -1),
+                std::vector<uint32_t>(nq, Grouped::exact_stage)};
+    check(hnsw_brute_force_batch_grouped(g.handle(), l.handle(), f ? f->handle() : nullptr, batch.data, batch.dim2, batch.dim1, k, fill,
+                                         out.ids.data(), out.dist.data(), out.labels.data()));
     return out;
 }
 

@@ -185,6 +185,24 @@ let hnsw_range_search_batch =
 let hnsw_range_brute_force_batch =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_range_brute_force_batch"
     (index @-> ptr float @-> int64_t @-> int64_t @-> float @-> ptr range_handle @-> returning int32_t)
+(* grouped search (see the C header): one label per node, uploaded once, and the k nearest groups, one node per label *)
+type labels_handle = unit ptr
+let labels_handle : labels_handle typ = ptr void
+let hnsw_labels_create =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_labels_create"
+    (index @-> ptr int32_t @-> int64_t @-> int32_t @-> ptr labels_handle @-> returning int32_t)
+let hnsw_labels_destroy = foreign ~from:lib "hnsw_labels_destroy" (labels_handle @-> returning int32_t)
+let hnsw_labels_info =
+  foreign ~from:lib "hnsw_labels_info" (labels_handle @-> ptr int32_t @-> ptr int64_t @-> ptr int64_t @-> returning int32_t)
+let hnsw_labels_get = foreign ~from:lib "hnsw_labels_get" (labels_handle @-> ptr int32_t @-> returning int32_t)
+let hnsw_search_batch_grouped =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_grouped"
+    (index @-> labels_handle @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> ptr int32_t
+     @-> ptr float @-> ptr int32_t @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+let hnsw_brute_force_batch_grouped =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_brute_force_batch_grouped"
+    (index @-> labels_handle @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> ptr int32_t
+     @-> ptr float @-> ptr int32_t @-> returning int32_t)
 (* ... under an allow-mask: each segment is the unfiltered one with the nodes the filter does not allow left out *)
 let hnsw_range_search_batch_filtered =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_range_search_batch_filtered"
@@ -902,6 +920,72 @@ let knn_batch_filtered ?(semantics = 0) ?(fill = 0) (f : filter) (batch : Lacaml
   (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
    Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
    Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))
+
+(* Grouped search (hnsw_labels_create / hnsw_search_batch_grouped): the k nearest GROUPS, one node per label.
+   [labels_create t labels ~n_labels]: labels.(v) in -1 .. n_labels - 1 is node v's group, -1 = none; one entry per node of the
+   index.  Uploaded once and reused; refused once the index has changed ([insert], [remove], marks).  Keeps its index alive. *)
+type labels = { l_handle : labels_handle; l_index : t; l_n : int }
+
+let labels_create (t : t) (labels : int array) ~n_labels : labels =
+  let n = Array.length labels in
+  let lab = CArray.make int32_t (max 1 n) in
+  Array.iteri (fun v l -> CArray.set lab v (Int32.of_int l)) labels;
+  let out = allocate labels_handle null in
+  check (hnsw_labels_create t.handle (CArray.start lab) (Int64.of_int n) (Int32.of_int n_labels) out);
+  let l = { l_handle = !@out; l_index = t; l_n = n } in
+  Gc.finalise (fun l -> ignore (hnsw_labels_destroy l.l_handle)) l;
+  l
+
+(* (n_labels, n_labelled, n_groups): the nodes with a label >= 0, the labels at least one node carries *)
+let labels_info (l : labels) : int * int * int =
+  let a = allocate int32_t 0l and b = allocate int64_t 0L and c = allocate int64_t 0L in
+  check (hnsw_labels_info l.l_handle a b c);
+  (Int32.to_int !@a, Int64.to_int !@b, Int64.to_int !@c)
+
+(* the labels as the device holds them: -1 where the node was marked deleted at creation *)
+let labels_get (l : labels) : int array =
+  let out = CArray.make int32_t (max 1 l.l_n) in
+  check (hnsw_labels_get l.l_handle (CArray.start out));
+  Array.init l.l_n (fun v -> Int32.to_int (CArray.get out v))
+
+let grouped_rows nq k ids dist lab =
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
+   Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get lab (q * k + j)))))
+
+(* [knn_batch_grouped l batch ~ef ~k]: for each query (a column of [batch]) the k nearest distinct labels, each represented by its
+   nearest node.  W grows ef, 2 ef, ... 1024 until it holds nodes of k labels; a query still short is answered by the exact
+   grouped scan.  ?filter: only allowed nodes count.  -> (ids, distances, labels, stages), [nq][k] each (id -1, label -1,
+   distance nan -- ~fill:1: infinity -- where there are fewer than k groups), stages.(q) = how often W doubled, -1 = exact. *)
+let knn_batch_grouped ?(semantics = 0) ?(fill = 0) ?filter (l : labels) (batch : Lacaml.S.mat) ~ef ~k :
+  int array array * float array array * int array array * int array =
+  let t = l.l_index in
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let lab = CArray.make int32_t (max 1 (nq * k)) in
+  let stage = CArray.make uint32_t (max 1 nq) in
+  let p = make search_params in
+  setf p p_ef (Int32.of_int ef); setf p p_k (Int32.of_int k); setf p p_fill (Int32.of_int fill);
+  setf p p_semantics (Int32.of_int semantics);
+  let fh = match filter with Some (f : filter) -> f.f_handle | None -> null in
+  check (hnsw_search_batch_grouped t.handle l.l_handle fh (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim)
+           (addr p) (CArray.start ids) (CArray.start dist) (CArray.start lab) (from_voidp uint32_t null) (from_voidp uint32_t null)
+           (CArray.start stage));
+  let i, d, g = grouped_rows nq k ids dist lab in
+  (i, d, g, Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))
+
+(* [brute_force_grouped l batch ~k] (hnsw_brute_force_batch_grouped): the exact form -- per label its nearest node under (distance,
+   id) over all stored vectors, of those the k nearest.  Needs no graph. *)
+let brute_force_grouped ?(fill = 0) ?filter (l : labels) (batch : Lacaml.S.mat) ~k :
+  int array array * float array array * int array array =
+  let t = l.l_index in
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let lab = CArray.make int32_t (max 1 (nq * k)) in
+  let fh = match filter with Some (f : filter) -> f.f_handle | None -> null in
+  check (hnsw_brute_force_batch_grouped t.handle l.l_handle fh (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim)
+           (Int32.of_int k) (Int32.of_int fill) (CArray.start ids) (CArray.start dist) (CArray.start lab));
+  grouped_rows nq k ids dist lab
 
 (* [filters_by_label t labels ~n_labels] (hnsw_filter_create_by_label): n_labels filters from one label per node of the index;
    filter l allows node v iff labels.(v) = l, a label of -1 puts the node in no filter.  The labels are uploaded once and one
