@@ -225,8 +225,10 @@ enum { HNSW_ROWS_F32 = 0,   /* the float32 rows as handed over                  
                                vectors but the exact search over X rounded to fp16                          */
        HNSW_ROWS_SQ8 = 5,   /* 8-bit codes under one affine map (option "sq8_rows"): the walk is the exact search
                                over the codes, the answer its candidates re-ranked over the float32 vectors  */
-       HNSW_ROWS_SQ8_DIM = 6 }; /* 8-bit codes under one affine map PER DIMENSION (option "sq8_dim_rows"): the walk is
+       HNSW_ROWS_SQ8_DIM = 6, /* 8-bit codes under one affine map PER DIMENSION (option "sq8_dim_rows"): the walk is
                                the exact search over Z = codes * s, the answer re-ranked over the float32 vectors */
+       HNSW_ROWS_BITS = 7 }; /* one bit per dimension (option "bit_rows"): the walk runs under Hamming distance over the
+                               bits x_i > t_i, the answer is its candidates re-ranked over the float32 vectors */
 
 typedef struct hnsw_index_info {
     int64_t n;
@@ -454,9 +456,63 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   active is HNSW_ERR_BAD_ARG ("the k farthest of W" has no refined meaning).  hnsw_index_insert keeps the
  *                   setting; it is not saved (neither is "half_rows").  COST: c float32 rows per query on top of the walk's
  *                   roughly 950 to 2400 half-row evaluations (the benchmark's float shapes); the rate has not been measured
- *                   yet (tools/refine_rate.py prints the table that belongs beside profiles/half_rows.txt). */
+ *                   yet (tools/refine_rate.py prints the table that belongs beside profiles/half_rows.txt).
+ * and one more row format that CHANGES results, for wide rows (off by default):
+ *   "bit_rows"      binary quantisation: the knn searches walk ONE BIT per dimension under Hamming distance and answer from the
+ *                   float32 rows.  A 1024-dimensional row is one 128-byte line (float32: 32 lines, sq8: 8), a 512-dimensional one
+ *                   half a line.  0 = off (default; the copy is FREED, after a device synchronisation, and the previous rows are
+ *                   read again); 1 = on, the thresholds t at the column means; 2 = on, the thresholds at zero (sign bits: the
+ *                   usual choice for cosine / inner-product embeddings); any other value is HNSW_ERR_BAD_ARG.  Setting 1 or 2
+ *                   makes the copy (again, when the mode changes).
+ *                   THRESHOLDS t[d].  Mode 2: t_i = +0.  Mode 1: t_i = the float32 rounding of the mean of column i of the rows
+ *                   the handle holds (hnsw_index_get_rows; for a HNSW_METRIC_COSINE index these are N(X)), the mean accumulated in
+ *                   float64 by a two-stage reduction whose grid is fixed by (n, d) alone: the same table gives the same bits on
+ *                   every call.  The sums and the finite check come from one pass over the rows; a NaN or infinity, under either
+ *                   mode, is HNSW_ERR_UNSUPPORTED (the message names the first such column) and leaves the index unchanged.
+ *                   CODES.  Bit i of a row is x_i > t_i: equality gives 0, and -0 counts as +0.  Bits are packed little-endian into
+ *                   uint32 words: dimension i is bit i % 32 of word i / 32.  With NW = ceil(d / 512) (1 or 2) a stored row is
+ *                   16 * NW words (64 * NW bytes), zero beyond d; lane l16 of a 16-lane group reads word 16 * j + l16 in step j, so
+ *                   for d > 512 a group's step pair is one whole 128-byte line.
+ *                   QUERIES get the same rule against the same t, on the device, once per call (for a HNSW_METRIC_COSINE index
+ *                   after the index's own normalisation); a page-locked host matrix is read in place, each value once.
+ *                   WALK.  H = sum over the words of popcount(row_word ^ query_word), an integer; the walk's key is that of the
+ *                   squared L2 distance 4 * H -- (float)(4 * H) -- on every layer, WHATEVER the index's metric: Hamming order is the
+ *                   order of L2, of -IP and of cosine between +-1 vectors.  TWIN: ids, members of W, hops and evaluations of this
+ *                   walk are bit for bit those of a float32-row L2 index with the same graph over S = where(X > t, 1, -1)
+ *                   (float32), searched with where(Q > t, 1, -1): every term of that float sum is 0 or 4 and every partial sum an
+ *                   integer <= 4096, so the float32 arithmetic never rounds and the order of summation does not show.
+ *                   Everything after the walk is "sq8_rows" unchanged: c = min(ef, max(k, R)) members of W (R = option "refine")
+ *                   re-ranked over the FLOAT32 rows under the index's real metric, unconditionally; the first k under (distance,
+ *                   node id) come back with the bits of hnsw_distance_batch; out_nhops is the walk's count, out_ndist the walk's
+ *                   count plus c; HNSW_SEM_FUNCTOR_NEAREST_K is HNSW_ERR_BAD_ARG; the same scratch and the same ONE call in flight
+ *                   per handle; every knn form, the filtered, range and grouped ladders (all of W re-ranked), marked indexes,
+ *                   multi replicas (hnsw_multi_replica) and sharded indexes (hnsw_sharded_set_option: thresholds per shard).  With
+ *                   R = 0 ONLY THE FIRST k BY HAMMING DISTANCE are re-scored -- one bit per dimension orders neighbours coarsely --:
+ *                   "refine" -1 (all ef) is the setting this format is meant for; the default of "refine" is not changed.
+ *                   The builder, hnsw_index_insert's searches, the layer operators, hnsw_distance_batch, the exact scans and
+ *                   hnsw_rerank_batch keep reading the float32 rows.  Option "visited_blocks" treats these rows as sq8 rows.
+ *                   EXCLUSIONS: HNSW_ERR_BAD_ARG, the index unchanged, when it is set to 1 or 2 while byte rows are in use
+ *                   ("byte_rows" 0 first) or while option half_rows, sq8_rows, sq8_dim_rows or filter_collect is on, and when one
+ *                   of those four is set to 1 while this option is on; the split rows step aside.
+ *                   hnsw_index_info.row_format reports HNSW_ROWS_BITS, hnsw_index_row_bytes gives (d + 7) / 8, and the copy's
+ *                   n * 64 * NW bytes plus its threshold table (4 * 512 * NW bytes) count in device_bytes; at 0 device_bytes is
+ *                   what it was.  Not saved: a loaded index starts without the copy.  hnsw_index_insert and hnsw_index_remove
+ *                   quantise the WHOLE remaining table again (mode 1: the means move); a new vector that is not finite refuses the
+ *                   whole insert.  hnsw_index_bit_params / hnsw_index_bit_codes give t and the codes.
+ *                   Not built: hand-scheduled hop loops for this format, an asymmetric distance (float query against bits), more
+ *                   than one bit per dimension, a saved copy, "filter_collect" with bit rows, a changed default for "refine".
+ *                   RATE AND RECALL (one MI355X; 200 000 clustered unit vectors, inner product, M 16, k 10, 10 k queries; medians of
+ *                   15 device-resident calls, the formats alternated on one handle; tools/bit_rows_rate.py, profiles/bit_rows.txt).
+ *                   d = 1024, ef 128: the walk's launches take 1.31 ms per batch over the bits against 2.18 ms over the
+ *                   "sq8_dim_rows" codes and 6.82 ms over the float32 rows -- and find little: recall@10 0.18 at refine 0, 0.72 at
+ *                   refine -1 (1.95 ms), where the sq8_dim codes reach 0.998 at refine 40 in 2.36 ms.  The bits need a wide W:
+ *                   refine -1 gives 0.89 at ef 256 (3.43 ms) and 0.986 at ef 512 (7.67 ms; float32 rows: 1.000 in 11.5 ms, sq8_dim
+ *                   1.000 in 6.74 ms).  d = 512: the walk over the bits (1.28 to 1.35 ms at ef 128) is no faster than the one over
+ *                   the sq8_dim codes (1.23 ms): both are bound by a hop's latency, not by bytes.  On this data the sq8_dim codes
+ *                   are the better trade at every setting measured; the two threshold modes do not differ. */
 int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value);
-/* Bytes of one vector as the knn searches read it: d for byte and sq8 rows (either kind), 2 * d for half rows, 4 * d for float32 rows. */
+/* Bytes of one vector as the knn searches read it: d for byte and sq8 rows (either kind), 2 * d for half rows, 4 * d for float32 rows,
+ * (d + 7) / 8 for bit rows. */
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes);
 /* The sq8 copy (option "sq8_rows"), for callers who want X^ = lo + scale * codes: its two parameters, and its codes as
  * [n][d] bytes (the rows' padding is not exported).  HNSW_ERR_BAD_ARG when no copy exists (never made, or freed by -1). */
@@ -467,6 +523,11 @@ int32_t hnsw_index_sq8_codes(const hnsw_index *idx, uint8_t *out);
  * exists (never made, or freed by -1). */
 int32_t hnsw_index_sq8_dim_params(const hnsw_index *idx, float *lo, float *scale);
 int32_t hnsw_index_sq8_dim_codes(const hnsw_index *idx, uint8_t *out);
+/* The 1-bit copy (option "bit_rows"): its thresholds t ([d] floats; mode 2: all +0), and its codes as [n][ceil(d / 32)] uint32
+ * words, dimension i in bit i % 32 of word i / 32 (the rows' padding words are not exported).  HNSW_ERR_BAD_ARG for a null argument
+ * and while the option is off. */
+int32_t hnsw_index_bit_params(const hnsw_index *idx, float *t /* [d] */);
+int32_t hnsw_index_bit_codes(const hnsw_index *idx, uint32_t *out /* [n][ceil(d/32)], padding words not exported */);
 /* Mean durations (ms) over the device-entry calls recorded since the last call of this function
  * (option "time_kernels"): the search kernel itself, and the ordering pre-pass (descent kernel +
  * sort; 0 when the batch was searched in the given order).  Waits for the recorded calls. */

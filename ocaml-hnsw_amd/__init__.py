@@ -33,6 +33,7 @@ SEM_OHNSW, SEM_FUNCTOR, SEM_FUNCTOR_NEAREST_K = 0, 1, 2
 # after set_option("sq8_rows", 1), ROWS_SQ8_DIM only after set_option("sq8_dim_rows", 1)
 ROWS_F32, ROWS_BYTES, ROWS_SPLIT, ROWS_HALF, ROWS_SQ8 = 0, 2, 3, 4, 5
 ROWS_SQ8_DIM = 6
+ROWS_BITS = 7            # only after set_option("bit_rows", 1 or 2)
 
 ABI_VERSION = 3          # HNSW_ABI_VERSION of include/hnsw_mi355x.h this mirror was written against
 
@@ -54,6 +55,8 @@ _ABI = {
     "hnsw_index_sq8_codes": [_vp, _vp],
     "hnsw_index_sq8_dim_params": [_vp, _vp, _vp],
     "hnsw_index_sq8_dim_codes": [_vp, _vp],
+    "hnsw_index_bit_params": [_vp, _vp],
+    "hnsw_index_bit_codes": [_vp, _vp],
     "hnsw_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_device": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_h2d": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -496,7 +499,7 @@ class Hgraph:
         return inf
 
     def set_option(self, name, value):
-        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "sq8_dim_rows", "refine", ...).
+        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "sq8_dim_rows", "bit_rows", "refine", ...).
         "filter_collect" 1 makes the filtered searches (knn_batch_filtered, knn_batch_filtered_each, the plain searches under
         marks) answer from every node the layer-0 walk evaluates, not from the final W only (k <= 128, exact rows; default 0)"""
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
@@ -530,6 +533,20 @@ class Hgraph:
         """hnsw_index_sq8_dim_codes -> the codes of the per-dimension sq8 copy, uint8 [n][d] (the rows' padding is not exported)"""
         out = _np.empty((self.info().n, self.d), _np.uint8)
         _check(load().hnsw_index_sq8_dim_codes(self.handle, _ptr(out)))
+        return out
+
+    def bit_params(self):
+        """hnsw_index_bit_params -> t, float32 [d]: the thresholds of the 1-bit copy (set_option("bit_rows", 1): the column means,
+        2: zeros); bit i of a row is x[i] > t[i]"""
+        t = _np.empty(self.d, _np.float32)
+        _check(load().hnsw_index_bit_params(self.handle, _ptr(t)))
+        return t
+
+    def bit_codes(self):
+        """hnsw_index_bit_codes -> the codes of the 1-bit copy, uint32 [n][ceil(d / 32)]: dimension i is bit i % 32 of word i // 32
+        (numpy.packbits(X > t, axis=1, bitorder="little") viewed as uint32; the rows' padding words are not exported)"""
+        out = _np.empty((self.info().n, (self.d + 31) // 32), _np.uint32)
+        _check(load().hnsw_index_bit_codes(self.handle, _ptr(out)))
         return out
 
     def filter(self, allow):

@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libhnsw_mi355x.so")
 SOURCES = ["hnsw_capi.hip", "hnsw_build.hip", "hnsw_layer_ops.hip", "hnsw_multi.hip", "hnsw_order.hip", "hnsw_rows8.hip",
-           "hnsw_rows_split.hip", "hnsw_rows16.hip", "hnsw_rows_sq8.hip", "hnsw_rows_sq8_dim.hip", "hnsw_locality.hip", "hnsw_scan.hip", "hnsw_rerank.hip", "hnsw_filter.hip",
+           "hnsw_rows_split.hip", "hnsw_rows16.hip", "hnsw_rows_sq8.hip", "hnsw_rows_sq8_dim.hip", "hnsw_rows_bits.hip", "hnsw_locality.hip", "hnsw_scan.hip", "hnsw_rerank.hip", "hnsw_filter.hip",
            "hnsw_range.hip", "hnsw_remove.hip", "hnsw_soft_delete.hip", "hnsw_sharded.hip", "hnsw_cosine.hip", "hnsw_group.hip"]
 # the knn kernel's variants: one object per (metric, accept rule, row shape), see hnsw_search_variants.hip
 VARIANT_SOURCE = "hnsw_search_variants.hip"
@@ -20,7 +20,10 @@ COLLECT_VARIANTS = [(m, s, f) for m in (0, 1) for s in (0, 1) for f in (0, 1, 2,
 # the L2 walk over the per-dimension sq8 codes (option "sq8_dim_rows"): one object per accept rule, see hnsw_sq8_dim_walk.hip
 SQ8_DIM_WALK_SOURCE = "hnsw_sq8_dim_walk.hip"
 SQ8_DIM_WALKS = [0, 1]
-DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, SQ8_DIM_WALK_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_group_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
+# the Hamming walk over the 1-bit codes (option "bit_rows"): one object per accept rule, see hnsw_bits_walk.hip
+BITS_WALK_SOURCE = "hnsw_bits_walk.hip"
+BITS_WALKS = [0, 1]
+DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, SQ8_DIM_WALK_SOURCE, BITS_WALK_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_group_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
         os.path.join(ROOT, "include", "hnsw_mi355x.h")]
 
 
@@ -65,6 +68,7 @@ def build(force=False, verbose=False, resource_log=None):
     units += [("hnsw_collect_variants_%d_%d_%d" % v, COLLECT_SOURCE,
                ["-DHNSW_V_METRIC=%d" % v[0], "-DHNSW_V_SEMF=%d" % v[1], "-DHNSW_V_FULL=%d" % v[2]]) for v in COLLECT_VARIANTS]
     units += [("hnsw_sq8_dim_walk_%d" % s_, SQ8_DIM_WALK_SOURCE, ["-DHNSW_V_SEMF=%d" % s_]) for s_ in SQ8_DIM_WALKS]
+    units += [("hnsw_bits_walk_%d" % s_, BITS_WALK_SOURCE, ["-DHNSW_V_SEMF=%d" % s_]) for s_ in BITS_WALKS]
     # the CPUs this process may use (a shared host's os.cpu_count() can be many times that), at most 16 compilers
     usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)
     jobs = max(1, int(os.environ.get("HNSW_BUILD_JOBS") or os.environ.get("MAX_JOBS") or min(16, usable)))

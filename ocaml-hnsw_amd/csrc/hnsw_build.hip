@@ -341,6 +341,7 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
     if (!rc && idx->half_rows_on && nx->iv.n > 0) rc = make_half_rows(nx.get());
     if (!rc && idx->sq8_on && nx->iv.n > 0) rc = make_sq8_rows(nx.get());
     if (!rc && idx->sq8d_on && nx->iv.n > 0) rc = make_sq8_dim_rows(nx.get());
+    if (!rc && idx->bit_mode && nx->iv.n > 0) rc = make_bit_rows(nx.get(), idx->bit_mode);   // (option bit_rows: likewise; mode 1's means move)
     if (!rc && carry_codes) rc = extend_locality_codes(idx, nx.get());
     // soft deletion: the marks move with their nodes; the new live mask is complete before anything is swapped
     std::unique_ptr<hnsw_filter> live;
@@ -362,6 +363,7 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
     idx->info = nx->info;
     idx->sq8_lo = nx->sq8_lo; idx->sq8_scale = nx->sq8_scale;   // (of the swapped-in codes, if any)
     idx->sq8d_lo = std::move(nx->sq8d_lo); idx->sq8d_scale = std::move(nx->sq8d_scale);
+    idx->bit_t = std::move(nx->bit_t);
     bind_view(idx);                                        // the options keep their effect
     idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
     nx.reset();

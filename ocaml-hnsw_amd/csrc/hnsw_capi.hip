@@ -200,11 +200,13 @@ const struct { int metric, semf, rows; collect_launch_fn launch; } k_collect_var
 // the knn kernel's row format: 2 = byte rows (hnsw_rows8.hip) and the sq8 codes (hnsw_rows_sq8.hip: the same kernels), 3 = split
 // fp32 rows (hnsw_rows_split.hip), 4 = half rows (hnsw_rows16.hip), else plain fp32 rows, 1 = every chunk of the lane grid inside
 // the row.  (From the record bind_view keeps: byte, sq8 and half rows share IndexView's pointer.)  5 = the per-dimension sq8 codes
-// under L2 (hnsw_rows_sq8_dim.hip: a weighted distance; under the inner product they are byte rows to the kernel, 2).
+// under L2 (hnsw_rows_sq8_dim.hip: a weighted distance; under the inner product they are byte rows to the kernel, 2).  6 = the
+// 1-bit codes (hnsw_rows_bits.hip), under every metric.
 inline int variant_full(const hnsw_index *idx) {
     switch (idx->info.row_format) {
     case HNSW_ROWS_BYTES: case HNSW_ROWS_SQ8: return 2;
     case HNSW_ROWS_SQ8_DIM: return idx->info.metric == HNSW_METRIC_L2 ? 5 : 2;
+    case HNSW_ROWS_BITS: return 6;
     case HNSW_ROWS_SPLIT: return 3;
     case HNSW_ROWS_HALF: return 4;
     default: return idx->iv.nchunks == 16 * pick_nch(idx->iv.nchunks) ? 1 : 0;
@@ -226,8 +228,10 @@ struct KnnShape {
 KnnShape knn_shape(const hnsw_index *idx, int ef, int semantics) {
     KnnShape sh{};
     sh.ef = ef; sh.semf = semantics ? 1 : 0;
-    sh.nch = pick_nch(idx->iv.nchunks); sh.nslot = pick_nslot_knn(ef, sh.nch); sh.slot_class = slot_class(sh.nslot);
     const int metric = idx->info.metric == HNSW_METRIC_L2 ? 0 : 1, rows = variant_full(idx);
+    // (bit rows: the kernel's NCH is NW, the 16-word steps of a row, not the float32 row's chunks per lane)
+    sh.nch = rows == 6 ? bit_words(idx->iv.d) : pick_nch(idx->iv.nchunks);
+    sh.nslot = pick_nslot_knn(ef, sh.nch); sh.slot_class = slot_class(sh.nslot);
     for (const auto &v : k_variants)
         if (v.metric == metric && v.semf == sh.semf && v.rows == rows) { sh.launch = v.launch; sh.occupancy = v.occupancy; }
     for (const auto &v : k_collect_variants)
@@ -235,6 +239,10 @@ KnnShape knn_shape(const hnsw_index *idx, int ef, int semantics) {
     if (rows == 5) {                     // hnsw_sq8_dim_walk.hip: one object per accept rule, L2 only
         sh.launch = sh.semf ? search_launch_sq8_dim_1 : search_launch_sq8_dim_0;
         sh.occupancy = sh.semf ? search_occupancy_sq8_dim_1 : search_occupancy_sq8_dim_0;
+    }
+    if (rows == 6) {                     // hnsw_bits_walk.hip: one object per accept rule, the one Hamming walk under every metric
+        sh.launch = sh.semf ? search_launch_bits_1 : search_launch_bits_0;
+        sh.occupancy = sh.semf ? search_occupancy_bits_1 : search_occupancy_bits_0;
     }
     return sh;
 }
@@ -337,7 +345,8 @@ int blk_capacity_bits(hnsw_index *idx, const KnnShape &sh) {
 }
 
 // do the knn searches gather byte rows (the byte rows, or codes -- the per-dimension codes' L2 kernel loads what the byte-row
-// kernels load, and is treated as they are)?
+// kernels load, and is treated as they are; the bit rows are smaller still and bound by a hop's latency all the more)?  Not "one
+// byte per dimension": hnsw_index_row_bytes asks the format.
 inline bool walks_bytes(const hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_BYTES || walks_codes(idx); }
 
 // does option "visited_blocks" at -1 consider this shape at all?
@@ -819,14 +828,15 @@ void bind_view(hnsw_index *idx) {
     // the knn searches read, in this order of precedence: byte rows (exact, the smallest), sq8 rows (option sq8_rows 1: in the
     // byte rows' place, for the same kernels) or half rows (option half_rows 1; the two options exclude each other), split rows, the
     // plain float32 rows
-    // (the per-dimension codes, option sq8_dim_rows 1, likewise; the three options exclude each other)
+    // (the per-dimension codes, option sq8_dim_rows 1, and the 1-bit codes, option bit_rows 1 / 2, likewise; the four options
+    // exclude each other)
     const bool bytes = !idx->byte_rows_off && t.X8.p, sq8 = !bytes && idx->sq8_on && t.Xq.p, sq8d = !bytes && !sq8 && idx->sq8d_on && t.Xqd.p,
-               half = !bytes && !sq8 && !sq8d && idx->half_rows_on && t.Xh.p;
+               bits = !bytes && !sq8 && !sq8d && idx->bit_mode != 0 && t.Xb.p, half = !bytes && !sq8 && !sq8d && !bits && idx->half_rows_on && t.Xh.p;
     iv.X = (const float *)t.X.p;
-    iv.X8 = bytes ? (const uint8_t *)t.X8.p : sq8 ? (const uint8_t *)t.Xq.p : sq8d ? (const uint8_t *)t.Xqd.p : nullptr;
+    iv.X8 = bytes ? (const uint8_t *)t.X8.p : sq8 ? (const uint8_t *)t.Xq.p : sq8d ? (const uint8_t *)t.Xqd.p : bits ? (const uint8_t *)t.Xb.p : nullptr;
     if (half) iv.Xh = (const uint2 *)t.Xh.p;
-    iv.stride8 = (half ? 128 : 64) * pick_nch(iv.nchunks);
-    iv.Xm = idx->split_rows_off || half || sq8 || sq8d ? nullptr : (const float *)t.Xm.p;
+    iv.stride8 = bits ? 64 * bit_words(iv.d) : (half ? 128 : 64) * pick_nch(iv.nchunks);
+    iv.Xm = idx->split_rows_off || half || sq8 || sq8d || bits ? nullptr : (const float *)t.Xm.p;
     iv.tail0 = (const float *)t.tail0.p;
     if (sq8d) iv.sq8s = (const float *)t.qd_s.p;              // (in tail0's place: no split rows are read while the codes are)
     iv.nbr0 = (const int32_t *)t.nbr0.p; iv.nbrU = (const int32_t *)t.nbrU.p;
@@ -835,7 +845,7 @@ void bind_view(hnsw_index *idx) {
     hnsw_index_info &inf = idx->info;
     inf.n = iv.n; inf.max_degree0 = iv.S0; inf.max_layer = iv.max_layer; inf.entry_point = (int64_t)iv.entry_point + iv.id_base;
     inf.row_stride_bytes = iv.stride * 4;
-    inf.row_format = bytes ? HNSW_ROWS_BYTES : sq8 ? HNSW_ROWS_SQ8 : sq8d ? HNSW_ROWS_SQ8_DIM : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
+    inf.row_format = bytes ? HNSW_ROWS_BYTES : sq8 ? HNSW_ROWS_SQ8 : sq8d ? HNSW_ROWS_SQ8_DIM : bits ? HNSW_ROWS_BITS : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
 }
 
 int finish_index(IndexPtr owned, int32_t expected_ef, int32_t expected_semantics, hnsw_index **out) {
@@ -1050,6 +1060,7 @@ int32_t hnsw_index_prepare(hnsw_index *idx, const hnsw_search_params *params) {
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes) {
     if (!idx || !row_bytes) return fail(HNSW_ERR_BAD_ARG, "null argument");
     const int f = idx->info.row_format;
+    if (f == HNSW_ROWS_BITS) { *row_bytes = ((int64_t)idx->iv.d + 7) / 8; return HNSW_OK; }   // (codes, but not a byte per dimension)
     *row_bytes = (int64_t)idx->iv.d * (f == HNSW_ROWS_BYTES || walks_codes(idx) ? 1 : f == HNSW_ROWS_HALF ? 2 : 4);
     return HNSW_OK;
 }
@@ -1108,6 +1119,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
                 return fail(HNSW_ERR_BAD_ARG, "sq8_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)");
             if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option half_rows is on (set half_rows 0 first)");
             if (idx->sq8d_on) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option sq8_dim_rows is on (set sq8_dim_rows 0 first)");
+            if (idx->bit_mode) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option bit_rows is on (set bit_rows 0 first)");
             if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
             if (!idx->tables.Xq.p) {
                 const int rc = make_sq8_rows(idx);      // (a refusal -- NaN, infinity, range overflow -- leaves the index as it was)
@@ -1133,6 +1145,7 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
                 return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)");
             if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option half_rows is on (set half_rows 0 first)");
             if (idx->sq8_on) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option sq8_rows is on (set sq8_rows 0 first)");
+            if (idx->bit_mode) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option bit_rows is on (set bit_rows 0 first)");
             if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
             if (!idx->tables.Xqd.p) {
                 const int rc = make_sq8_dim_rows(idx);  // (a refusal -- NaN, infinity, a column's range -- leaves the index as it was)
@@ -1147,6 +1160,35 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
                 idx->sq8d_lo.clear(); idx->sq8d_scale.clear();
             }
             idx->sq8d_on = false;
+        }
+        bind_view(idx);
+        idx->forget_shapes();
+        return HNSW_OK;
+    }
+    if (!strcmp(name, "bit_rows")) {      // 1-bit codes walked under Hamming distance (hnsw_rows_bits.hip): 1 = thresholds at the column means, 2 = at zero
+        if (value < 0 || value > 2) return fail(HNSW_ERR_BAD_ARG, "bit_rows=%lld: 0 (off), 1 (thresholds at the column means) or 2 (at zero)", (long long)value);
+        if (value > 0) {
+            if (idx->info.row_format == HNSW_ROWS_BYTES)
+                return fail(HNSW_ERR_BAD_ARG, "bit_rows: the index searches its byte rows, which are exact (set byte_rows 0 first)");
+            if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "bit_rows: option half_rows is on (set half_rows 0 first)");
+            if (idx->sq8_on) return fail(HNSW_ERR_BAD_ARG, "bit_rows: option sq8_rows is on (set sq8_rows 0 first)");
+            if (idx->sq8d_on) return fail(HNSW_ERR_BAD_ARG, "bit_rows: option sq8_dim_rows is on (set sq8_dim_rows 0 first)");
+            if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "bit_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
+            if (!idx->tables.Xb.p || idx->bit_mode != (int)value) {
+                HIP_TRY(hipSetDevice(idx->device));
+                HIP_TRY(hipDeviceSynchronize());         // launches that still read a copy of the other mode
+                const int rc = make_bit_rows(idx, (int)value);   // (a refusal -- NaN, infinity -- leaves the index as it was)
+                if (rc) return rc;
+            }
+            idx->bit_mode = (int)value;
+        } else {
+            if (idx->tables.Xb.p) {
+                HIP_TRY(hipSetDevice(idx->device));
+                HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy
+                idx->tables.Xb.release(); idx->tables.bit_t.release();
+                idx->bit_t.clear();
+            }
+            idx->bit_mode = 0;
         }
         bind_view(idx);
         idx->forget_shapes();
@@ -1202,7 +1244,7 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
     const struct { const char *name; int64_t value; } now[] = {
         {"vt_bits", idx->vt_bits_override}, {"lds_pad", idx->lds_pad}, {"byte_rows", idx->byte_rows_off ? 0 : 1},
         {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
-        {"sq8_rows", idx->sq8_on ? 1 : 0}, {"sq8_dim_rows", idx->sq8d_on ? 1 : 0}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
+        {"sq8_rows", idx->sq8_on ? 1 : 0}, {"sq8_dim_rows", idx->sq8d_on ? 1 : 0}, {"bit_rows", idx->bit_mode}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
         {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }

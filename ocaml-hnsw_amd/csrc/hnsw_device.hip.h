@@ -50,6 +50,8 @@ struct IndexView {
     //   X8 (ROWS 2): a lossless copy for data whose every value is an integer in 0..255 (SIFT descriptors): rows of 64*NCH
     //       bytes, zero padded; chunk c of a row (dims 4c..4c+3) is one dword
     //   Xh (ROWS 4, option "half_rows"): the values rounded to fp16: rows of 128*NCH bytes, zero padded; chunk c is 8 bytes
+    //   X8 again (ROWS 6, option "bit_rows", hnsw_rows_bits.hip): one bit per dimension, rows of 16*NW dwords (NW = the kernel's
+    //       NCH for this format, 1 or 2), zero padded; dimension i is bit i % 32 of dword i / 32
     // (one member for both, so that the view's layout -- every kernel's arguments -- is what it was before half rows existed)
     union { const uint8_t *X8; const uint2 *Xh; };
     int32_t stride8;         // bytes per row of that copy
@@ -563,7 +565,7 @@ struct WaveCtx {
     OvfStore ovf;        // lds: [OVF_CAP]
     // byte rows only (query_bytes): the query itself is byte-valued and short enough for exact integer arithmetic
     bool qint;
-    uint32_t qb[4];      // this lane's chunks of the query as packed bytes
+    uint32_t qb[4];      // this lane's chunks of the query as packed bytes (bit rows, ROWS 6, load_query_bits: its NW words of query bits)
     int32_t q2;          // sum of the squares of the whole query
     // per-dimension codes only (ROWS 5, load_scales): the scales of this lane's chunks, sv[i] = s of dims 4 (16 i + l16) .. + 3
     float4 sv[16];
@@ -729,14 +731,20 @@ __device__ __forceinline__ int adj_entry(const IndexView &iv, int layer, int c, 
 // i becomes z = fl((float)c * s_i) with the lane's scale registers (cx.sv) -- a rounded product of its own, never contracted into
 // the subtraction behind it -- then the arithmetic of the fp32 row: the result is that of the fp32 row of Z = C * s bit for bit.
 // (Beyond d code, scale and query are 0: exact zeros.)
+// 6 = bit rows (IndexView::X8, hnsw_rows_bits.hip; NCH is NW, the 16-word steps of a row): one dword per lane and step, xor with
+// the lane's query word (cx.qb, in registers for the whole walk) and popcount-accumulate; the NB integer counts go through
+// transpose_reduce16_i32 and the keys land in the lanes the integer path of the byte rows leaves them in.  The key is that of the
+// squared L2 distance 4 H between the +-1 vectors the bits stand for (METRIC 0 whatever the index's metric): every term of that
+// float sum is 0 or 4, so the integer is the float32 row's result bit for bit.  qv is not read.
 template <int NCH, int NB, int METRIC, int ROWS>
 __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv)[NCH], const WaveCtx &cx,
                                           int base, int cnt, uint32_t &out_key, uint32_t &out_id,
                                           const char *tail_row = nullptr) {
     static_assert(ROWS != 5 || METRIC == 0, "the per-dimension codes have an L2 walk only: the inner product walks them as byte rows");
-    constexpr bool FULL = ROWS == 1 || ROWS == 2 || ROWS == 4 || ROWS == 5;
+    static_assert(ROWS != 6 || (METRIC == 0 && NCH <= 2), "bit rows: the key is that of L2 over +-1 vectors, a row is one or two 16-word steps");
+    constexpr bool FULL = ROWS == 1 || ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6;
     const int r = cx.r, l16 = cx.l16;
-    const uint32_t stride_b = (ROWS == 2 || ROWS == 4 || ROWS == 5) ? (uint32_t)iv.stride8 : (uint32_t)iv.stride * 4u;
+    const uint32_t stride_b = (ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6) ? (uint32_t)iv.stride8 : (uint32_t)iv.stride * 4u;
     const int mine = base + NB * r;
     uint32_t id[NB];
 #pragma unroll
@@ -744,7 +752,7 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
         const int ci = (mine + b < cnt) ? mine + b : base + b;   // base + b < cnt: a round of NB batches has > 4*(NB-1) candidates
         id[b] = (uint32_t)cx.cand_id[ci];
     }
-    constexpr bool CODES = ROWS == 2 || ROWS == 5;      // one dword per chunk
+    constexpr bool CODES = ROWS == 2 || ROWS == 5 || ROWS == 6;      // one dword per chunk (ROWS 6: per 16-word step)
     float4 v[CODES || ROWS == 4 ? 1 : NB][CODES || ROWS == 4 ? 1 : NCH];
     uint32_t v8[CODES ? NB : 1][CODES ? NCH : 1];
     uint2 vh[ROWS == 4 ? NB : 1][ROWS == 4 ? NCH : 1];
@@ -850,6 +858,29 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
             return;
         }
     }
+    if constexpr (ROWS == 6) {
+        constexpr int NBP = NB <= 1 ? 1 : NB <= 2 ? 2 : NB <= 4 ? 4 : 8;   // batches padded to a power of two
+        int32_t t[NBP];
+#pragma unroll
+        for (int b = 0; b < NBP; ++b) {
+            int32_t h = 0;
+            if (b < NB) {
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) h += __builtin_popcount(v8[b][i] ^ cx.qb[i]);
+            }
+            t[b] = h;
+        }
+        const int32_t hsum = transpose_reduce16_i32<NBP>(t, l16);        // (as the integer path above: lane (b << SH) of the group ends with batch b's sum)
+        constexpr int SH = NBP == 1 ? 4 : NBP == 2 ? 3 : NBP == 4 ? 2 : 1;
+        const int b = l16 >> SH;
+        uint32_t myid = id[0];
+#pragma unroll
+        for (int j = 1; j < NB; ++j) myid = (b == j) ? id[j] : myid;
+        const bool rep = (l16 & ((1 << SH) - 1)) == 0 && b < NB && mine + b < cnt;
+        out_key = rep ? dist_to_key<0>((float)(4 * hsum)) : KEY_INF;
+        out_id = myid;
+        return;
+    }
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         float acc = 0.0f;
@@ -952,6 +983,7 @@ __device__ __forceinline__ void greedy_descend(const IndexView &iv, const float4
                 if (ROWS == 2) base += eval_round<NCH, RB, METRIC, 2>(iv, qv, cx, base, cnt, ckey, cid);
                 else if (ROWS == 4) base += eval_round<NCH, RB, METRIC, 4>(iv, qv, cx, base, cnt, ckey, cid);   // (half rows: every layer, as the oracle's space over Xh)
                 else if constexpr (ROWS == 5) base += eval_round<NCH, RB, METRIC, 5>(iv, qv, cx, base, cnt, ckey, cid);   // (per-dimension codes: every layer, as the space over Z)
+                else if constexpr (ROWS == 6) base += eval_round<NCH, RB, METRIC, 6>(iv, qv, cx, base, cnt, ckey, cid);   // (bit rows: every layer, as the space over the +-1 vectors)
                 else if (ROWS == 1 || (ROWS < 0 && full_rows)) base += eval_round<NCH, RB, METRIC, 1>(iv, qv, cx, base, cnt, ckey, cid);
                 else base += eval_round<NCH, RB, METRIC, 0>(iv, qv, cx, base, cnt, ckey, cid);
                 const uint32_t mk = wave_min_u32(ckey);
@@ -1397,6 +1429,7 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
             else if (ROWS == 2) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 2, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);                                  // :573-577
             else if (ROWS == 4) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 4, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else if constexpr (ROWS == 5) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 5, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
+            else if constexpr (ROWS == 6) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 6, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else if (ROWS == 1 || (ROWS < 0 && full_rows)) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 1, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else hop_eval<NCH, RB, NSLOT, METRIC, SEM, 0, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
         }
@@ -1470,6 +1503,15 @@ __device__ __forceinline__ void load_scales(WaveCtx &cx, const float *table) {
 #pragma unroll
     for (int i = 0; i < NCH; ++i) cx.sv[i] = t[i * 16 + cx.l16];
 }
+// bit rows (ROWS 6): the lane's NW words of the query's bits, from the first 16 * NW words of the query's row as
+// bits_transform_queries left it; they stay in registers (cx.qb) for the whole walk, and qv is zero: nothing reads it
+template <int NCH>
+__device__ __forceinline__ void load_query_bits(float4 (&qv)[NCH], WaveCtx &cx, const float *qp) {
+    static_assert(NCH <= 2, "a bit row is one or two 16-word steps");
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(qp);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) { cx.qb[i] = w[i * 16 + cx.l16]; qv[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
+}
 // a database row as the query (rows are zero padded to the stride)
 template <int NCH>
 __device__ __forceinline__ void load_row(float4 (&qv)[NCH], const IndexView &iv, int node, int l16) {
@@ -1491,7 +1533,7 @@ __device__ __forceinline__ void load_row(float4 (&qv)[NCH], const IndexView &iv,
 constexpr int search_min_waves(int NCH, int NSLOT, int METRIC, int ROWS) {
     return (NCH <= 2 && NSLOT <= 2 && METRIC == 0 && ROWS == 1) ? 7 : (NCH == 2 && NSLOT <= 4 && METRIC == 0 && ROWS == 2) ? 8 : 1;
 }
-// SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3 | 4 | 5, see hop_round
+// SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3 | 4 | 5 | 6, see hop_round
 // BLK: 1 = Visited as bitmap blocks (a.blk_bits slots, iv.lcode / lcode0 present), see search_layer
 template <int NCH, int RB, int NSLOT, int METRIC, int SEMF, int ROWS, int BLK = 0>
 __global__ void __launch_bounds__(64, search_min_waves(NCH, NSLOT, METRIC, ROWS))
@@ -1517,7 +1559,8 @@ hnsw_search_kernel(const IndexView iv, const SearchArgs a) {
 #endif
 
     float4 qv[NCH];
-    load_query<NCH>(qv, a.Q + q * a.q_stride, iv.d, cx.l16);
+    if constexpr (ROWS == 6) load_query_bits<NCH>(qv, cx, a.Q + q * a.q_stride);
+    else load_query<NCH>(qv, a.Q + q * a.q_stride, iv.d, cx.l16);
     if (ROWS == 2) query_bytes<NCH>(cx, qv, iv.d);
     if constexpr (ROWS == 5) load_scales<NCH>(cx, iv.sq8s);
     visited_clear(cx);
@@ -1677,15 +1720,19 @@ hnsw_descent_kernel(const IndexView iv, const float *Q, int64_t q_stride, int64_
     if (q >= nq) return;
     WaveCtx cx = make_ctx(lds, 4, lane);
     float4 qv[NCH];
-    load_query<NCH>(qv, Q + q * q_stride, iv.d, cx.l16);
-    if (stage && cx.r == 0) store_query<NCH>(qv, stage + q * q_stride, iv.d, cx.l16);   // Q may be host memory: keep a device copy
+    if constexpr (ROWS == 6) {               // (bit rows: Q is the device-resident matrix of query bits, never the caller's: no stage)
+        load_query_bits<NCH>(qv, cx, Q + q * q_stride);
+    } else {
+        load_query<NCH>(qv, Q + q * q_stride, iv.d, cx.l16);
+        if (stage && cx.r == 0) store_query<NCH>(qv, stage + q * q_stride, iv.d, cx.l16);   // Q may be host memory: keep a device copy
+    }
     if (ROWS == 2) query_bytes<NCH>(cx, qv, iv.d);
     if constexpr (ROWS == 5) load_scales<NCH>(cx, iv.sq8s);
     int cur = iv.entry_point;
     if (lane == 0) cx.cand_id[0] = cur;
     __syncthreads();
     uint32_t cur_key;
-    if constexpr (ROWS == 2 || ROWS == 4 || ROWS == 5) {     // (the compact rows: their own evaluation, as in the search kernel)
+    if constexpr (ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6) {     // (the compact rows: their own evaluation, as in the search kernel)
         uint32_t ck, ci;
         hop_round<NCH, 1, METRIC, ROWS>(iv, qv, cx, 0, 1, ck, ci);
         cur_key = rdlane(ck, 0);

@@ -45,6 +45,12 @@ constexpr bool has_odd_nslot(int nch) { return nch == 2 || nch == 4; }
 // (DESIGN.md has the register table); NCH 16 holds one batch (its widest instance stands at 256 VGPRs).
 constexpr int rows_in_flight_sq8_dim(int nch) { return nch == 1 ? 8 : nch == 2 ? RB_NCH2 : nch == 4 ? 4 : nch == 8 ? 2 : 1; }
 
+// ... and for the walk over the 1-bit codes (ROWS 6, hnsw_rows_bits.hip): a row in flight is NW = 1 or 2 dwords per lane, so the
+// limit is ids in flight, not registers: 8 batches, the most eval_round issues, for both widths (DESIGN.md has the register table).
+constexpr int rows_in_flight_bits(int /*nw*/) { return 8; }
+// NW: 16-word steps of a bit row (d <= 512: 64 bytes a row, else 128) -- the knn kernel's NCH for that format
+inline int bit_words(int d) { return d > 512 ? 2 : 1; }
+
 template <int V> using Int = std::integral_constant<int, V>;
 // f(Int<NCH>) for the NCH that pick_nch returned
 template <class F> auto with_nch(int nch, F &&f) {
@@ -209,13 +215,13 @@ template <class Id> struct RangeRecord {
 
 // Every device table an index holds: the vectors and the graph, and the copies derived from them -- byte rows (X8, hnsw_rows8.hip),
 // half rows (Xh, hnsw_rows16.hip), sq8 rows (Xq, hnsw_rows_sq8.hip), per-dimension sq8 rows (Xqd with their tables qd_lo / qd_s,
-// hnsw_rows_sq8_dim.hip), split rows (Xm / tail0, hnsw_rows_split.hip), locality codes
+// hnsw_rows_sq8_dim.hip), bit rows (Xb with their thresholds bit_t, hnsw_rows_bits.hip), split rows (Xm / tail0, hnsw_rows_split.hip), locality codes
 // (lcode / lcode0, hnsw_locality.hip); a derived table that does not exist has p == nullptr.  bind_view points the handle's IndexView at them.
 struct IndexTables {
-    Table X, X8, Xh, Xq, Xqd, qd_lo, qd_s, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
+    Table X, X8, Xh, Xq, Xqd, qd_lo, qd_s, Xb, bit_t, Xm, tail0, lcode, lcode0, nbr0, nbrU, off, lvl, ref;
     template <class Self, class F> static void each(Self &t, F f) {
         static constexpr Table IndexTables::*all[] = {&IndexTables::X, &IndexTables::X8, &IndexTables::Xh, &IndexTables::Xq, &IndexTables::Xqd,
-                                                      &IndexTables::qd_lo, &IndexTables::qd_s, &IndexTables::Xm,
+                                                      &IndexTables::qd_lo, &IndexTables::qd_s, &IndexTables::Xb, &IndexTables::bit_t, &IndexTables::Xm,
                                                       &IndexTables::tail0, &IndexTables::lcode, &IndexTables::lcode0, &IndexTables::nbr0, &IndexTables::nbrU,
                                                       &IndexTables::off, &IndexTables::lvl, &IndexTables::ref};
         for (Table IndexTables::*m : all) f(t.*m);
@@ -525,6 +531,11 @@ struct hnsw_index {
     // describe tables.Xqd whenever it exists.  hnsw_index_insert and hnsw_index_remove quantise the whole table again while it is on.
     bool sq8d_on = false;
     std::vector<float> sq8d_lo, sq8d_scale;
+    // option "bit_rows": the knn searches walk tables.Xb, one bit per dimension (x_i > t_i) under Hamming distance; 1: t = the column
+    // means, 2: t = 0; 0: off, and the copy is freed.  bit_t ([d]; on the device tables.bit_t, [512 * NW] floats) describes tables.Xb
+    // whenever it exists.  hnsw_index_insert and hnsw_index_remove quantise the whole table again while it is on.
+    int bit_mode = 0;
+    std::vector<float> bit_t;
     // option "filter_collect": the filtered searches answer from every node the walk evaluates, not from the final W only
     // (hnsw_search_collect_kernel; k <= 128, exact-row formats: it excludes half_rows and sq8_rows).  Not saved.
     bool filter_collect = false;
@@ -583,7 +594,7 @@ inline int DeviceGroup::adopt(::hnsw_index *idx, int device) {
 // hnsw_capi.hip: IndexView's table pointers from idx->tables (X8 / Xm left out while option byte_rows / split_rows is 0; Xh in
 // the view while option half_rows is 1 and no byte rows are: it takes the place of Xm; Xq in the byte rows' place while option
 // sq8_rows is 1 and no byte rows are: Xm steps aside too; Xqd there, and qd_s in tail0's place, while option sq8_dim_rows is 1
-// and no byte rows are), and the hnsw_index_info fields that
+// and no byte rows are; Xb there while option bit_rows is on and no byte rows are), and the hnsw_index_info fields that
 // restate the view (n, max_degree0, max_layer, entry_point, row_stride_bytes, row_format).  Called by every change of the tables
 // or of those options.
 void bind_view(::hnsw_index *idx);
@@ -649,6 +660,19 @@ hipError_t search_launch_sq8_dim_0(int nch, int nslot, const hnsw_dev::IndexView
 hipError_t search_launch_sq8_dim_1(int nch, int nslot, const hnsw_dev::IndexView &iv, const hnsw_dev::SearchArgs &a, hipStream_t st);
 int search_occupancy_sq8_dim_0(int nch, int nslot, size_t lds, int blk);
 int search_occupancy_sq8_dim_1(int nch, int nslot, size_t lds, int blk);
+// hnsw_rows_bits.hip: the 1-bit codes of tables.X (tables.Xb / bit_t, idx->bit_t) under thresholds of `mode` (1: the column means,
+// 2: zero), all or nothing: HNSW_ERR_UNSUPPORTED, naming the first such column, when a value is NaN or infinite (mode 1);
+// HNSW_ERR_OOM when there is no room.  Leaves the option's value and the view to the caller (bind_view).
+int make_bit_rows(::hnsw_index *idx, int mode);
+// ... and nq queries as the walk over those codes reads them, on `st`: the first 16 * NW words of every Qt row ([nq][padded_stride(d)]
+// floats) are the query's bits q_i > t_i, zero beyond d.  Q and stage: as sq8_transform_queries; Q == Qt is NOT allowed.
+int bits_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st);
+// hnsw_bits_walk.hip, one object per accept rule (0 Ohnsw, 1 functor): the knn kernel's ROWS = 6 instances, the Hamming walk over
+// those codes under every metric; nch here is NW
+hipError_t search_launch_bits_0(int nch, int nslot, const hnsw_dev::IndexView &iv, const hnsw_dev::SearchArgs &a, hipStream_t st);
+hipError_t search_launch_bits_1(int nch, int nslot, const hnsw_dev::IndexView &iv, const hnsw_dev::SearchArgs &a, hipStream_t st);
+int search_occupancy_bits_0(int nch, int nslot, size_t lds, int blk);
+int search_occupancy_bits_1(int nch, int nslot, size_t lds, int blk);
 // hnsw_rows_split.hip: if a row ends 1..32 bytes past a 128-byte line (and there are no byte rows), build the split copy
 // (tables.Xm / tail0, iv.stride_m / main_chunks / tail_chunks); call after make_byte_rows, graph in place
 int make_split_rows(::hnsw_index *idx);
@@ -733,17 +757,19 @@ struct ScanCut : ScanPlan {
     dim3 grid(int64_t nq) const;
 };
 ScanCut scan_cut(const ::hnsw_index *idx, int64_t m, int k, int64_t cell_bytes, int64_t cap);
-// the walk reads codes (sq8 rows, per-dimension sq8 rows): its queries are moved to the codes' space first, its distances mean
+// the walk reads codes (sq8 rows, per-dimension sq8 rows, bit rows): its queries are moved to the codes' space first, its distances mean
 // nothing to a caller, and it always ends in the re-rank over the float32 rows
 inline bool walks_codes(const ::hnsw_index *idx) {
-    return idx->info.row_format == HNSW_ROWS_SQ8 || idx->info.row_format == HNSW_ROWS_SQ8_DIM;
+    return idx->info.row_format == HNSW_ROWS_SQ8 || idx->info.row_format == HNSW_ROWS_SQ8_DIM || idx->info.row_format == HNSW_ROWS_BITS;
 }
 // ... and is either option on (even while byte rows stand in front of the codes)?  Its name, for messages
-inline bool codes_on(const ::hnsw_index *idx) { return idx->sq8_on || idx->sq8d_on; }
+inline bool codes_on(const ::hnsw_index *idx) { return idx->sq8_on || idx->sq8d_on || idx->bit_mode != 0; }
 inline const char *codes_option(const ::hnsw_index *idx) {
+    if (idx->bit_mode != 0 || idx->info.row_format == HNSW_ROWS_BITS) return "bit_rows";
     return idx->sq8d_on || idx->info.row_format == HNSW_ROWS_SQ8_DIM ? "sq8_dim_rows" : "sq8_rows";
 }
 inline int codes_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st) {
+    if (idx->info.row_format == HNSW_ROWS_BITS) return bits_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
     return idx->info.row_format == HNSW_ROWS_SQ8_DIM ? sq8_dim_transform_queries(idx, Q, nq, q_stride, Qt, stage, st)
                                                      : sq8_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
 }

@@ -104,6 +104,15 @@ hipError_t launch_descent(const hnsw_index *idx, int row_format, const float *Q,
         });
         return hipGetLastError();
     }
+    if (row_format == HNSW_ROWS_BITS) {
+        // the 1-bit codes: the kernel's ROWS 6 under every metric (its key is L2's over the +-1 vectors), NCH = the row's 16-word steps
+        auto launch = [&](auto NW) {
+            hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<NW, rows_in_flight_bits(NW), 0, 6>), dim3((unsigned)nq), dim3(64), lds, st,
+                               idx->iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, (float *)nullptr);
+        };
+        if (bit_words(idx->iv.d) == 2) launch(Int<2>{}); else launch(Int<1>{});
+        return hipGetLastError();
+    }
     switch (row_format) {
     case HNSW_ROWS_BYTES: case HNSW_ROWS_SQ8: case HNSW_ROWS_SQ8_DIM: rows(Int<2>{}); break;   // (sq8: the codes in the byte rows' place, the queries in code space)
     case HNSW_ROWS_HALF: rows(Int<4>{}); break;

@@ -51,10 +51,12 @@ inline void check(int rc) {
 // hnsw_index_info.row_format: what the knn searches read (HNSW_ROWS_*); HALF only after hnsw_index_set_option(h, "half_rows", 1),
 // which makes them search the vectors rounded to fp16; SQ8 only after hnsw_index_set_option(h, "sq8_rows", 1), which makes them
 // walk 8-bit codes of the vectors and re-rank over the float32 rows; SQ8_DIM only after hnsw_index_set_option(h, "sq8_dim_rows", 1):
-// the same with one affine map per dimension
+// the same with one affine map per dimension; BITS only after hnsw_index_set_option(h, "bit_rows", 1 or 2): one bit per dimension,
+// walked under Hamming distance and re-ranked over the float32 rows
 namespace Rows {
 constexpr int F32 = HNSW_ROWS_F32, BYTES = HNSW_ROWS_BYTES, SPLIT = HNSW_ROWS_SPLIT, HALF = HNSW_ROWS_HALF, SQ8 = HNSW_ROWS_SQ8;
 constexpr int SQ8_DIM = HNSW_ROWS_SQ8_DIM;
+constexpr int BITS = HNSW_ROWS_BITS;
 }
 
 // Flattened Ohnsw.Hgraph.t / Hnsw.Ba.Hgraph.t resident on the device.
@@ -214,6 +216,20 @@ inline Sq8Dim sq8_dim(const Hgraph &g) {
     Sq8Dim out{std::vector<float>((size_t)inf.d), std::vector<float>((size_t)inf.d), std::vector<uint8_t>((size_t)inf.n * (size_t)inf.d)};
     check(hnsw_index_sq8_dim_params(g.handle(), out.lo.data(), out.scale.data()));
     check(hnsw_index_sq8_dim_codes(g.handle(), out.codes.data()));
+    return out;
+}
+
+// The 1-bit copy of an index (hnsw_index_set_option(h, "bit_rows", 1 or 2)): bit i of a row is x[i] > t[i]; t: [d]; codes:
+// [n][words] uint32 with words = ceil(d / 32), dimension i in bit i % 32 of word i / 32.  Throws std::invalid_argument while the
+// option is off.
+struct Bits { std::vector<float> t; std::vector<uint32_t> codes; size_t words; };
+inline Bits bits(const Hgraph &g) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    const size_t words = ((size_t)inf.d + 31) / 32;
+    Bits out{std::vector<float>((size_t)inf.d), std::vector<uint32_t>((size_t)inf.n * words), words};
+    check(hnsw_index_bit_params(g.handle(), out.t.data()));
+    check(hnsw_index_bit_codes(g.handle(), out.codes.data()));
     return out;
 }
 

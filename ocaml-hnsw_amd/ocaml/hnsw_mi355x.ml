@@ -93,6 +93,12 @@ let hnsw_index_sq8_dim_params =
   foreign ~from:lib "hnsw_index_sq8_dim_params" (index @-> ptr float @-> ptr float @-> returning int32_t)
 let hnsw_index_sq8_dim_codes =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_sq8_dim_codes" (index @-> ptr void @-> returning int32_t)
+(* the 1-bit copy (`hnsw_index_set_option idx "bit_rows" 1L` -- thresholds at the column means -- or `2L` -- at zero: a Hamming walk,
+   re-ranked over the float32 rows, see the C header): its thresholds, [d] floats, and its codes, [n][ceil(d/32)] uint32 words *)
+let hnsw_index_bit_params =
+  foreign ~from:lib "hnsw_index_bit_params" (index @-> ptr float @-> returning int32_t)
+let hnsw_index_bit_codes =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_bit_codes" (index @-> ptr void @-> returning int32_t)
 (* cosine distance (metric_cosine below; the twin contract of the C header): the normaliser N as an operator of its own, and the
    float32 rows an index holds -- for a cosine index N(X), not the vectors it was handed *)
 let hnsw_normalise_batch =
@@ -311,6 +317,8 @@ let rows_split = 3l
 let rows_half = 4l
 let rows_sq8 = 5l
 let rows_sq8_dim = 6l
+(* bit rows (only after `hnsw_index_set_option idx "bit_rows" 1L` or `2L`: one bit per dimension, walked under Hamming distance) *)
+let rows_bits = 7l
 let () = seal index_info
 let hnsw_index_get_info = foreign ~from:lib "hnsw_index_get_info" (index @-> ptr index_info @-> returning int32_t)
 (* the flattened graph of a device index (built there by hnsw_build, or loaded from a file) back to the host *)
@@ -1255,6 +1263,19 @@ let sq8_dim_codes (t : t) : (int, Bigarray.int8_unsigned_elt, Bigarray.c_layout)
   check (hnsw_index_get_info t.handle (addr inf));
   let out = Bigarray.Array2.create Bigarray.int8_unsigned Bigarray.c_layout (max 1 (Int64.to_int (getf inf ii_n))) t.dim in
   check (hnsw_index_sq8_dim_codes t.handle (to_voidp (bigarray_start array2 out)));
+  out
+
+(* the 1-bit copy of the index (option "bit_rows"): the d thresholds (bit i of a row is x_i > t_i), and the codes, one row of
+   ceil(d/32) words per node, dimension i in bit (i mod 32) of word (i / 32); Invalid_argument while the option is off *)
+let bit_params (t : t) : float array =
+  let thr = CArray.make float t.dim in
+  check (hnsw_index_bit_params t.handle (CArray.start thr));
+  Array.of_list (CArray.to_list thr)
+let bit_codes (t : t) : (int32, Bigarray.int32_elt, Bigarray.c_layout) Bigarray.Array2.t =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let out = Bigarray.Array2.create Bigarray.int32 Bigarray.c_layout (max 1 (Int64.to_int (getf inf ii_n))) ((t.dim + 31) / 32) in
+  check (hnsw_index_bit_codes t.handle (to_voidp (bigarray_start array2 out)));
   out
 
 (* ?metric of [create], [build], [of_ohnsw], [of_ba] and [sharded_build]: HNSW_METRIC_L2, _IP, _COSINE.  A cosine index stores
