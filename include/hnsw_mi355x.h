@@ -509,7 +509,48 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   refine -1 gives 0.89 at ef 256 (3.43 ms) and 0.986 at ef 512 (7.67 ms; float32 rows: 1.000 in 11.5 ms, sq8_dim
  *                   1.000 in 6.74 ms).  d = 512: the walk over the bits (1.28 to 1.35 ms at ef 128) is no faster than the one over
  *                   the sq8_dim codes (1.23 ms): both are bound by a hop's latency, not by bytes.  On this data the sq8_dim codes
- *                   are the better trade at every setting measured; the two threshold modes do not differ. */
+ *                   are the better trade at every setting measured; the two threshold modes do not differ.
+ *   "bit_query_bits" supersedes the "asymmetric distance" item of the Not built list above: 0 = off (default: every result, counter
+ *                   and code path of "bit_rows" is exactly as without the option); 4 = while the searches walk the bit rows, the QUERY
+ *                   keeps 4 bits per dimension; any other value is HNSW_ERR_BAD_ARG.  The rows are the same copy, the same bytes and
+ *                   the same device_bytes, and row_format stays HNSW_ROWS_BITS.  It may be set before or after "bit_rows" and takes
+ *                   effect while the bit rows are walked, as "refine" does for half rows; while other rows are walked it is accepted
+ *                   and does nothing.
+ *                   QUERY CODES, made on the device once per call, where the query's bits are made when the option is off (for a
+ *                   HNSW_METRIC_COSINE index after the index's own normalisation; a page-locked host matrix is read in place, each
+ *                   value once).  With the index's thresholds t (hnsw_index_bit_params): y_i = fl(q_i - t_i) in float32 for i < d;
+ *                   a = max |y_i|; r = fl(7.0f / a), an IEEE-rounded division, not a reciprocal estimate; v_i = (int)rint(fl(y_i *
+ *                   r)), ONE rounded product, round-half-even, in -7..7 by construction.  DEGENERATE QUERIES: if a = 0, or any y_i is
+ *                   NaN or infinite, or r is infinite (a subnormal a), every code of that query is 0; every node then ties and the
+ *                   walk orders by node id.  PLANES: a code is stored as the four bit planes of its two's-complement nibble, v = p0 +
+ *                   2 * p1 + 4 * p2 - 8 * p3; each plane is packed exactly as a row's bits are (dimension i in bit i % 32 of word
+ *                   i / 32, 16 * NW words a plane, zero beyond d), so a query row is 64 * NW words.  hnsw_index_bit_query_codes
+ *                   returns the v_i.
+ *                   WALK.  The loads are those of "bit_rows".  Per row word, c_p = popcount(row_word & plane_p word) and the term is
+ *                   c0 + 2 * c1 + 4 * c2 - 8 * c3; their sum over the row's words is A = the sum of v_i over the row's set bits, an
+ *                   integer.  With SV = the sum of all v_i (made once per walk), acc = 2 * A - SV is <v, s> for the +-1 vector s the
+ *                   row's bits stand for, and the key is the inner product's -- that of the distance 1 - (float)acc -- on every
+ *                   layer, WHATEVER the index's metric: for a fixed query, -<y, s> orders the rows as |y - c * s| does, so the
+ *                   argument of "bit_rows" carries over.  TWIN: ids, members of W, hops and evaluations of this walk are bit for bit
+ *                   those of a float32-row HNSW_METRIC_IP index with the same graph over S = where(X > t, 1, -1) (float32),
+ *                   searched with V (the codes as float32): every term of that float sum is an integer of magnitude <= 7 and every
+ *                   partial sum an integer of magnitude <= 7168, so the float32 arithmetic never rounds and the order of summation
+ *                   does not show.  Shapes, batches in flight, the visited set and everything after the walk (the re-rank over the
+ *                   float32 rows under the real metric, "refine", out_ndist = the walk's count plus c, ladders, marks, shards,
+ *                   hnsw_search_submit / _wait, HNSW_SEM_FUNCTOR_NEAREST_K refused) are those of "bit_rows".
+ *                   Not saved.  hnsw_index_insert and hnsw_index_remove keep it; hnsw_sharded_set_option forwards it; a replica of a
+ *                   multi index takes it through hnsw_multi_replica.
+ *                   RATE AND RECALL (one MI355X; the data, the method and the handle of the figures above; tools/bit_rows_rate.py --query-bits,
+ *                   profiles/bit_query_bits.txt; option on against off, same handle, same session, refine -1).  d = 1024: the search
+ *                   launches take 1.90 ms per 10 k batch against 1.95 ms at ef 128, 3.50 against 3.39 at ef 256, 7.62 against 7.69 at ef
+ *                   512 -- the 4-bit query costs nothing measurable -- and recall@10 goes from 0.72 to 0.88, from 0.89 to 0.97, from
+ *                   0.986 to 0.9986; d = 512: 1.50 against 1.68 ms, 2.68 against 2.62, 5.92 against 6.00, recall 0.72 to 0.89, 0.89 to
+ *                   0.97, 0.988 to 0.9992.  With refine 40: 0.42 to 0.62.  The query transform takes 19 to 39 us per 10 k queries
+ *                   (the 1-bit one: 15 to 28 us), the pre-pass 0.085 ms against 0.068.  The extra registers (5 to 7 VGPRs for d <=
+ *                   512, 12 above) cross an occupancy step for 16 of the 40 kernel instances; no rate above follows the steps.  It
+ *                   still does not beat the "sq8_dim_rows" codes at equal recall (0.998 at ef 128 with 40 re-ranked in 2.32 ms at d =
+ *                   1024, 1.32 ms at d = 512); only the cheapest points at d = 1024 (0.62 in 1.42 ms, 0.88 in 1.90 ms) lie below the
+ *                   fastest sq8_dim setting measured. */
 int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value);
 /* Bytes of one vector as the knn searches read it: d for byte and sq8 rows (either kind), 2 * d for half rows, 4 * d for float32 rows,
  * (d + 7) / 8 for bit rows. */
@@ -528,6 +569,10 @@ int32_t hnsw_index_sq8_dim_codes(const hnsw_index *idx, uint8_t *out);
  * and while the option is off. */
 int32_t hnsw_index_bit_params(const hnsw_index *idx, float *t /* [d] */);
 int32_t hnsw_index_bit_codes(const hnsw_index *idx, uint32_t *out /* [n][ceil(d/32)], padding words not exported */);
+/* The 4-bit query codes of option "bit_query_bits" (the rule stands there): the v_i in -7..7 the walk would use for these queries
+ * ([nq][q_stride] floats on the host; a HNSW_METRIC_COSINE index normalises them first), as [nq][d] int8.  It does not require
+ * "bit_query_bits" to be on.  HNSW_ERR_BAD_ARG for a null argument, nq < 0, q_stride < d, and while option "bit_rows" is off. */
+int32_t hnsw_index_bit_query_codes(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int8_t *out /* [nq][d] */);
 /* Mean durations (ms) over the device-entry calls recorded since the last call of this function
  * (option "time_kernels"): the search kernel itself, and the ordering pre-pass (descent kernel +
  * sort; 0 when the batch was searched in the given order).  Waits for the recorded calls. */

@@ -57,6 +57,7 @@ _ABI = {
     "hnsw_index_sq8_dim_codes": [_vp, _vp],
     "hnsw_index_bit_params": [_vp, _vp],
     "hnsw_index_bit_codes": [_vp, _vp],
+    "hnsw_index_bit_query_codes": [_vp, _vp, _i64, _i64, _vp],
     "hnsw_search_batch": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_device": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_h2d": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -499,7 +500,7 @@ class Hgraph:
         return inf
 
     def set_option(self, name, value):
-        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "sq8_dim_rows", "bit_rows", "refine", ...).
+        """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "sq8_dim_rows", "bit_rows", "bit_query_bits", "refine", ...).
         "filter_collect" 1 makes the filtered searches (knn_batch_filtered, knn_batch_filtered_each, the plain searches under
         marks) answer from every node the layer-0 walk evaluates, not from the final W only (k <= 128, exact rows; default 0)"""
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
@@ -547,6 +548,17 @@ class Hgraph:
         (numpy.packbits(X > t, axis=1, bitorder="little") viewed as uint32; the rows' padding words are not exported)"""
         out = _np.empty((self.info().n, (self.d + 31) // 32), _np.uint32)
         _check(load().hnsw_index_bit_codes(self.handle, _ptr(out)))
+        return out
+
+    def bit_query_codes(self, Q):
+        """hnsw_index_bit_query_codes -> int8 [nq][d]: the 4-bit codes in -7..7 that the walk over the bit rows uses for the queries Q
+        under set_option("bit_query_bits", 4) (the rule: the C header; a COSINE index normalises Q first).  Needs "bit_rows" on, not
+        "bit_query_bits"""
+        Q = _np.ascontiguousarray(_np.atleast_2d(_np.asarray(Q, _np.float32)))
+        if Q.shape[1] != self.d:
+            raise InvalidArgument("bit_query_codes: queries of %d dimensions, the index has %d" % (Q.shape[1], self.d))
+        out = _np.empty((Q.shape[0], self.d), _np.int8)
+        _check(load().hnsw_index_bit_query_codes(self.handle, _ptr(Q), Q.shape[0], Q.shape[1], _ptr(out)))
         return out
 
     def filter(self, allow):

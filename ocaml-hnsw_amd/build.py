@@ -23,7 +23,10 @@ SQ8_DIM_WALKS = [0, 1]
 # the Hamming walk over the 1-bit codes (option "bit_rows"): one object per accept rule, see hnsw_bits_walk.hip
 BITS_WALK_SOURCE = "hnsw_bits_walk.hip"
 BITS_WALKS = [0, 1]
-DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, SQ8_DIM_WALK_SOURCE, BITS_WALK_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_group_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
+# the same rows against a 4-bit query (option "bit_query_bits"): one object per accept rule, see hnsw_bits_asym_walk.hip
+BITS_ASYM_WALK_SOURCE = "hnsw_bits_asym_walk.hip"
+BITS_ASYM_WALKS = [0, 1]
+DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, SQ8_DIM_WALK_SOURCE, BITS_WALK_SOURCE, BITS_ASYM_WALK_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_group_plan.h", "hnsw_bits_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
         os.path.join(ROOT, "include", "hnsw_mi355x.h")]
 
 
@@ -69,6 +72,7 @@ def build(force=False, verbose=False, resource_log=None):
                ["-DHNSW_V_METRIC=%d" % v[0], "-DHNSW_V_SEMF=%d" % v[1], "-DHNSW_V_FULL=%d" % v[2]]) for v in COLLECT_VARIANTS]
     units += [("hnsw_sq8_dim_walk_%d" % s_, SQ8_DIM_WALK_SOURCE, ["-DHNSW_V_SEMF=%d" % s_]) for s_ in SQ8_DIM_WALKS]
     units += [("hnsw_bits_walk_%d" % s_, BITS_WALK_SOURCE, ["-DHNSW_V_SEMF=%d" % s_]) for s_ in BITS_WALKS]
+    units += [("hnsw_bits_asym_walk_%d" % s_, BITS_ASYM_WALK_SOURCE, ["-DHNSW_V_SEMF=%d" % s_]) for s_ in BITS_ASYM_WALKS]
     # the CPUs this process may use (a shared host's os.cpu_count() can be many times that), at most 16 compilers
     usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)
     jobs = max(1, int(os.environ.get("HNSW_BUILD_JOBS") or os.environ.get("MAX_JOBS") or min(16, usable)))

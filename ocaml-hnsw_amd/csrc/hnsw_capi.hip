@@ -243,6 +243,10 @@ KnnShape knn_shape(const hnsw_index *idx, int ef, int semantics) {
     if (rows == 6) {                     // hnsw_bits_walk.hip: one object per accept rule, the one Hamming walk under every metric
         sh.launch = sh.semf ? search_launch_bits_1 : search_launch_bits_0;
         sh.occupancy = sh.semf ? search_occupancy_bits_1 : search_occupancy_bits_0;
+        if (walks_bit_planes(idx)) {     // option bit_query_bits 4: hnsw_bits_asym_walk.hip, the kernel's ROWS 7 over the same rows and shapes
+            sh.launch = sh.semf ? search_launch_bits_asym_1 : search_launch_bits_asym_0;
+            sh.occupancy = sh.semf ? search_occupancy_bits_asym_1 : search_occupancy_bits_asym_0;
+        }
     }
     return sh;
 }
@@ -384,7 +388,8 @@ int knn_blk_bits(hnsw_index *idx, const KnnShape &sh) {
     bool ok = hipGetLastError() == hipSuccess;
     // (sq8 rows: the probes are midpoints of float32 vectors and the walk reads code space -- moved there in place.  Not reached
     // today: blk_auto_eligible leaves the byte-row kernels, sq8's among them, out of the measurement, and "visited_blocks" 1
-    // returns above.  Kept so that measuring them one day does not search float32 probes in code space.)
+    // returns above.  Kept so that measuring them one day does not search float32 probes in code space.  The bit rows refuse a
+    // transform in place -- their query rows have a stride of their own, walk_query_stride -- and so answer "tags" here.)
     if (ok && walks_codes(idx))
         ok = codes_transform_queries(idx, (const float *)probes.p, nq, idx->iv.stride, (float *)probes.p, nullptr, nullptr) == HNSW_OK;
     hnsw_search_params p{};
@@ -492,10 +497,11 @@ int refine_count(const hnsw_index *idx, const hnsw_search_params *p) {
 }
 // The queries a walk over codes reads: b's moved to the codes' space in walk.qt (made here when `transform` -- sq8 rows: Q' =
 // (Q - lo) / scale for L2, Q for the inner product; per-dimension sq8 rows: Q - lo for L2, s o Q for the inner product; stage: see
-// sq8_transform_queries), at the padded stride.  Every launch that walks the codes -- the
+// sq8_transform_queries; bit rows: the query's bits, or its four bit planes under option bit_query_bits), at the stride
+// walk_query_stride names -- the padded stride, or the plane rows' own.  Every launch that walks the codes -- the
 // ordering pre-pass, the search, the device fallback, knn_repair's re-run -- goes through here; the re-rank keeps the caller's.
 int sq8_walk_queries(hnsw_index *idx, RefineBufs &walk, KnnBatch *wb, bool transform, float *stage, hipStream_t st) {
-    const int64_t stride = padded_stride(idx->iv.d);
+    const int64_t stride = walk_query_stride(idx);
     if (transform) {
         int rc;
         if ((rc = walk.qt.ensure((size_t)wb->nq * stride * sizeof(float))) ||
@@ -1194,6 +1200,12 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         idx->forget_shapes();
         return HNSW_OK;
     }
+    if (!strcmp(name, "bit_query_bits")) {   // 4: the walk over the bit rows keeps the query at 4 bits a dimension (hnsw_bits_asym_walk.hip); 0: at one
+        if (value != 0 && value != 4) return fail(HNSW_ERR_BAD_ARG, "bit_query_bits=%lld: 0 (off) or 4", (long long)value);
+        idx->bit_query_bits = (int)value;   // (takes effect while the searches walk the bit rows, as refine does for half rows; not saved)
+        idx->forget_shapes();               // (another kernel of the same shape: its residency may differ)
+        return HNSW_OK;
+    }
     if (!strcmp(name, "refine")) {        // 0: off; 1..1024: re-rank max(k, value) members of W over the float32 rows; -1: all ef (half and sq8 rows only)
         if (value < -1 || value > 1024) return fail(HNSW_ERR_BAD_ARG, "refine=%lld: 0 (off), 1..1024 candidates or -1 (all of W)", (long long)value);
         idx->refine = (int)value;
@@ -1244,7 +1256,7 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
     const struct { const char *name; int64_t value; } now[] = {
         {"vt_bits", idx->vt_bits_override}, {"lds_pad", idx->lds_pad}, {"byte_rows", idx->byte_rows_off ? 0 : 1},
         {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
-        {"sq8_rows", idx->sq8_on ? 1 : 0}, {"sq8_dim_rows", idx->sq8d_on ? 1 : 0}, {"bit_rows", idx->bit_mode}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
+        {"sq8_rows", idx->sq8_on ? 1 : 0}, {"sq8_dim_rows", idx->sq8d_on ? 1 : 0}, {"bit_rows", idx->bit_mode}, {"bit_query_bits", idx->bit_query_bits}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
         {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }

@@ -566,7 +566,8 @@ struct WaveCtx {
     // byte rows only (query_bytes): the query itself is byte-valued and short enough for exact integer arithmetic
     bool qint;
     uint32_t qb[4];      // this lane's chunks of the query as packed bytes (bit rows, ROWS 6, load_query_bits: its NW words of query bits)
-    int32_t q2;          // sum of the squares of the whole query
+    int32_t q2;          // sum of the squares of the whole query (ROWS 7, load_query_planes: SV, the sum of the query's 4-bit codes)
+    uint32_t qp[8];      // ROWS 7 only (option "bit_query_bits"): this lane's words of the query's four bit planes, qp[4 i + p] = plane p of step i
     // per-dimension codes only (ROWS 5, load_scales): the scales of this lane's chunks, sv[i] = s of dims 4 (16 i + l16) .. + 3
     float4 sv[16];
 };
@@ -736,15 +737,22 @@ __device__ __forceinline__ int adj_entry(const IndexView &iv, int layer, int c, 
 // transpose_reduce16_i32 and the keys land in the lanes the integer path of the byte rows leaves them in.  The key is that of the
 // squared L2 distance 4 H between the +-1 vectors the bits stand for (METRIC 0 whatever the index's metric): every term of that
 // float sum is 0 or 4, so the integer is the float32 row's result bit for bit.  qv is not read.
+// 7 = bit rows against a 4-bit query (option "bit_query_bits", hnsw_bits_asym_walk.hip): the loads of ROWS 6; the query is four bit
+// planes of its two's-complement codes v = p0 + 2 p1 + 4 p2 - 8 p3 in -7..7 (cx.qp, in registers for the whole walk), a step's term
+// is c0 + 2 c1 + 4 c2 - 8 c3 with c_p = popcount(row word & plane p), the reduction is that of ROWS 6 and gives A = the sum of v_i
+// over the row's set bits.  acc = 2 A - SV (cx.q2 = SV, the sum of all v_i) is <v, s> for the +-1 vector s the bits stand for, and
+// the key is the inner product's (METRIC 1 whatever the index's metric): every term of that float sum is an integer of magnitude
+// <= 7 and every partial sum one of magnitude <= 7168, so the integer is the float32 row's result bit for bit.  qv is not read.
 template <int NCH, int NB, int METRIC, int ROWS>
 __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv)[NCH], const WaveCtx &cx,
                                           int base, int cnt, uint32_t &out_key, uint32_t &out_id,
                                           const char *tail_row = nullptr) {
     static_assert(ROWS != 5 || METRIC == 0, "the per-dimension codes have an L2 walk only: the inner product walks them as byte rows");
     static_assert(ROWS != 6 || (METRIC == 0 && NCH <= 2), "bit rows: the key is that of L2 over +-1 vectors, a row is one or two 16-word steps");
-    constexpr bool FULL = ROWS == 1 || ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6;
+    static_assert(ROWS != 7 || (METRIC == 1 && NCH <= 2), "bit rows, 4-bit query: the key is that of the inner product with +-1 vectors");
+    constexpr bool FULL = ROWS == 1 || ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6 || ROWS == 7;
     const int r = cx.r, l16 = cx.l16;
-    const uint32_t stride_b = (ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6) ? (uint32_t)iv.stride8 : (uint32_t)iv.stride * 4u;
+    const uint32_t stride_b = (ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6 || ROWS == 7) ? (uint32_t)iv.stride8 : (uint32_t)iv.stride * 4u;
     const int mine = base + NB * r;
     uint32_t id[NB];
 #pragma unroll
@@ -752,7 +760,7 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
         const int ci = (mine + b < cnt) ? mine + b : base + b;   // base + b < cnt: a round of NB batches has > 4*(NB-1) candidates
         id[b] = (uint32_t)cx.cand_id[ci];
     }
-    constexpr bool CODES = ROWS == 2 || ROWS == 5 || ROWS == 6;      // one dword per chunk (ROWS 6: per 16-word step)
+    constexpr bool CODES = ROWS == 2 || ROWS == 5 || ROWS == 6 || ROWS == 7;      // one dword per chunk (ROWS 6, 7: per 16-word step)
     float4 v[CODES || ROWS == 4 ? 1 : NB][CODES || ROWS == 4 ? 1 : NCH];
     uint32_t v8[CODES ? NB : 1][CODES ? NCH : 1];
     uint2 vh[ROWS == 4 ? NB : 1][ROWS == 4 ? NCH : 1];
@@ -881,6 +889,33 @@ __device__ __forceinline__ void hop_round(const IndexView &iv, const float4 (&qv
         out_id = myid;
         return;
     }
+    if constexpr (ROWS == 7) {
+        constexpr int NBP = NB <= 1 ? 1 : NB <= 2 ? 2 : NB <= 4 ? 4 : 8;   // batches padded to a power of two
+        int32_t t[NBP];
+#pragma unroll
+        for (int b = 0; b < NBP; ++b) {
+            int32_t h = 0;
+            if (b < NB) {
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) {
+                    const uint32_t wd = v8[b][i];
+                    h += __builtin_popcount(wd & cx.qp[4 * i + 0]) + 2 * __builtin_popcount(wd & cx.qp[4 * i + 1]) +
+                         4 * __builtin_popcount(wd & cx.qp[4 * i + 2]) - 8 * __builtin_popcount(wd & cx.qp[4 * i + 3]);
+                }
+            }
+            t[b] = h;
+        }
+        const int32_t asum = transpose_reduce16_i32<NBP>(t, l16);        // (as ROWS 6: lane (b << SH) of the group ends with batch b's A)
+        constexpr int SH = NBP == 1 ? 4 : NBP == 2 ? 3 : NBP == 4 ? 2 : 1;
+        const int b = l16 >> SH;
+        uint32_t myid = id[0];
+#pragma unroll
+        for (int j = 1; j < NB; ++j) myid = (b == j) ? id[j] : myid;
+        const bool rep = (l16 & ((1 << SH) - 1)) == 0 && b < NB && mine + b < cnt;
+        out_key = rep ? dist_to_key<1>((float)(2 * asum - cx.q2)) : KEY_INF;
+        out_id = myid;
+        return;
+    }
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         float acc = 0.0f;
@@ -984,6 +1019,7 @@ __device__ __forceinline__ void greedy_descend(const IndexView &iv, const float4
                 else if (ROWS == 4) base += eval_round<NCH, RB, METRIC, 4>(iv, qv, cx, base, cnt, ckey, cid);   // (half rows: every layer, as the oracle's space over Xh)
                 else if constexpr (ROWS == 5) base += eval_round<NCH, RB, METRIC, 5>(iv, qv, cx, base, cnt, ckey, cid);   // (per-dimension codes: every layer, as the space over Z)
                 else if constexpr (ROWS == 6) base += eval_round<NCH, RB, METRIC, 6>(iv, qv, cx, base, cnt, ckey, cid);   // (bit rows: every layer, as the space over the +-1 vectors)
+                else if constexpr (ROWS == 7) base += eval_round<NCH, RB, METRIC, 7>(iv, qv, cx, base, cnt, ckey, cid);   // (... against the 4-bit query: likewise)
                 else if (ROWS == 1 || (ROWS < 0 && full_rows)) base += eval_round<NCH, RB, METRIC, 1>(iv, qv, cx, base, cnt, ckey, cid);
                 else base += eval_round<NCH, RB, METRIC, 0>(iv, qv, cx, base, cnt, ckey, cid);
                 const uint32_t mk = wave_min_u32(ckey);
@@ -1430,6 +1466,7 @@ __device__ __forceinline__ void search_layer(const IndexView &iv, const float4 (
             else if (ROWS == 4) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 4, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else if constexpr (ROWS == 5) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 5, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else if constexpr (ROWS == 6) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 6, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
+            else if constexpr (ROWS == 7) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 7, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else if (ROWS == 1 || (ROWS < 0 && full_rows)) hop_eval<NCH, RB, NSLOT, METRIC, SEM, 1, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
             else hop_eval<NCH, RB, NSLOT, METRIC, SEM, 0, COLLECT>(iv, qv, w, cx, cnt, status, pc, nullptr, 0, col);
         }
@@ -1512,6 +1549,24 @@ __device__ __forceinline__ void load_query_bits(float4 (&qv)[NCH], WaveCtx &cx, 
 #pragma unroll
     for (int i = 0; i < NCH; ++i) { cx.qb[i] = w[i * 16 + cx.l16]; qv[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
 }
+// bit rows against a 4-bit query (ROWS 7): the lane's 4 * NW plane words from the 64 * NW words of the query's row as
+// bits_asym_transform_queries left it (plane p: words 16 NW p .. 16 NW (p + 1)); they stay in registers (cx.qp) for the whole walk.
+// SV, the sum of the query's codes, is made here once from the planes (every lane of the wave ends with it) and kept in cx.q2.
+template <int NCH>
+__device__ __forceinline__ void load_query_planes(float4 (&qv)[NCH], WaveCtx &cx, const float *qp) {
+    static_assert(NCH <= 2, "a bit row is one or two 16-word steps");
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(qp);
+    int32_t sv = 0;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) cx.qp[4 * i + p] = w[p * 16 * NCH + i * 16 + cx.l16];
+        sv += __builtin_popcount(cx.qp[4 * i + 0]) + 2 * __builtin_popcount(cx.qp[4 * i + 1]) + 4 * __builtin_popcount(cx.qp[4 * i + 2]) -
+              8 * __builtin_popcount(cx.qp[4 * i + 3]);
+        qv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    cx.q2 = reduce16_i32(sv);
+}
 // a database row as the query (rows are zero padded to the stride)
 template <int NCH>
 __device__ __forceinline__ void load_row(float4 (&qv)[NCH], const IndexView &iv, int node, int l16) {
@@ -1533,7 +1588,7 @@ __device__ __forceinline__ void load_row(float4 (&qv)[NCH], const IndexView &iv,
 constexpr int search_min_waves(int NCH, int NSLOT, int METRIC, int ROWS) {
     return (NCH <= 2 && NSLOT <= 2 && METRIC == 0 && ROWS == 1) ? 7 : (NCH == 2 && NSLOT <= 4 && METRIC == 0 && ROWS == 2) ? 8 : 1;
 }
-// SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3 | 4 | 5 | 6, see hop_round
+// SEMF: 0 = Ohnsw accept rule, 1 = the functor path's (a.sem 1 and 2); ROWS: 0 | 1 | 2 | 3 | 4 | 5 | 6 | 7, see hop_round
 // BLK: 1 = Visited as bitmap blocks (a.blk_bits slots, iv.lcode / lcode0 present), see search_layer
 template <int NCH, int RB, int NSLOT, int METRIC, int SEMF, int ROWS, int BLK = 0>
 __global__ void __launch_bounds__(64, search_min_waves(NCH, NSLOT, METRIC, ROWS))
@@ -1560,6 +1615,7 @@ hnsw_search_kernel(const IndexView iv, const SearchArgs a) {
 
     float4 qv[NCH];
     if constexpr (ROWS == 6) load_query_bits<NCH>(qv, cx, a.Q + q * a.q_stride);
+    else if constexpr (ROWS == 7) load_query_planes<NCH>(qv, cx, a.Q + q * a.q_stride);
     else load_query<NCH>(qv, a.Q + q * a.q_stride, iv.d, cx.l16);
     if (ROWS == 2) query_bytes<NCH>(cx, qv, iv.d);
     if constexpr (ROWS == 5) load_scales<NCH>(cx, iv.sq8s);
@@ -1722,6 +1778,8 @@ hnsw_descent_kernel(const IndexView iv, const float *Q, int64_t q_stride, int64_
     float4 qv[NCH];
     if constexpr (ROWS == 6) {               // (bit rows: Q is the device-resident matrix of query bits, never the caller's: no stage)
         load_query_bits<NCH>(qv, cx, Q + q * q_stride);
+    } else if constexpr (ROWS == 7) {        // (... or of the 4-bit query's planes)
+        load_query_planes<NCH>(qv, cx, Q + q * q_stride);
     } else {
         load_query<NCH>(qv, Q + q * q_stride, iv.d, cx.l16);
         if (stage && cx.r == 0) store_query<NCH>(qv, stage + q * q_stride, iv.d, cx.l16);   // Q may be host memory: keep a device copy
@@ -1732,7 +1790,7 @@ hnsw_descent_kernel(const IndexView iv, const float *Q, int64_t q_stride, int64_
     if (lane == 0) cx.cand_id[0] = cur;
     __syncthreads();
     uint32_t cur_key;
-    if constexpr (ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6) {     // (the compact rows: their own evaluation, as in the search kernel)
+    if constexpr (ROWS == 2 || ROWS == 4 || ROWS == 5 || ROWS == 6 || ROWS == 7) {     // (the compact rows: their own evaluation, as in the search kernel)
         uint32_t ck, ci;
         hop_round<NCH, 1, METRIC, ROWS>(iv, qv, cx, 0, 1, ck, ci);
         cur_key = rdlane(ck, 0);

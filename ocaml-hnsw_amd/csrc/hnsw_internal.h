@@ -8,6 +8,7 @@
 #include "hnsw_mark_plan.h"
 #include "hnsw_shard_plan.h"
 #include "hnsw_group_plan.h"
+#include "hnsw_bits_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -48,8 +49,7 @@ constexpr int rows_in_flight_sq8_dim(int nch) { return nch == 1 ? 8 : nch == 2 ?
 // ... and for the walk over the 1-bit codes (ROWS 6, hnsw_rows_bits.hip): a row in flight is NW = 1 or 2 dwords per lane, so the
 // limit is ids in flight, not registers: 8 batches, the most eval_round issues, for both widths (DESIGN.md has the register table).
 constexpr int rows_in_flight_bits(int /*nw*/) { return 8; }
-// NW: 16-word steps of a bit row (d <= 512: 64 bytes a row, else 128) -- the knn kernel's NCH for that format
-inline int bit_words(int d) { return d > 512 ? 2 : 1; }
+// (NW = bit_words(d), the 16-word steps of a bit row and the knn kernel's NCH for that format: hnsw_bits_plan.h)
 
 template <int V> using Int = std::integral_constant<int, V>;
 // f(Int<NCH>) for the NCH that pick_nch returned
@@ -328,8 +328,8 @@ struct DeviceGroup {
 
 // the walk's side of a refined search (option "refine"): the first c members of W per query -- ids and distances [nq][c] -- and the
 // walk's evaluation counts [nq], which the re-rank reads; ids also stages hnsw_rerank_batch's candidates.  Beside them qt: the
-// queries the walk reads while the index searches its sq8 rows (Q', [nq][padded_stride(d)] floats: sq8_transform_queries), sized by
-// knn_search.  Not index tables: not counted in device_bytes.
+// queries the walk reads while the index searches its sq8 rows (Q', [nq][padded_stride(d)] floats: sq8_transform_queries; the bit
+// rows against a 4-bit query: [nq][walk_query_stride] words of bit planes), sized by knn_search.  Not index tables: not counted in device_bytes.
 struct RefineBufs {
     DevBuf ids, dist, nd, qt;
     int ensure(int64_t nq, int c) {
@@ -399,7 +399,7 @@ inline int slot_class(int nslot) {
     switch (nslot) { case 1: return 0; case 2: return 1; case 3: return 2; case 4: return 3; case 6: return 4; case 8: return 5; default: return 6; }
 }
 constexpr int SLOT_CLASSES = 7;
-inline int64_t padded_stride(int d) { return ((int64_t)d + 15) / 16 * 16; } // floats: rows are multiples of 64 B
+// (padded_stride(d), the floats of a row -- rows are multiples of 64 B --: hnsw_bits_plan.h)
 
 // The graph tables of an index of n nodes: X (max(n, 1) rows of `stride` floats), nbr0 ([n][S0]) and nbrU ([max(rowsU, 1)][SU])
 // with every slot empty (-1), off / lvl / ref (max(n, 1) entries each, written by upload_upper_layout)
@@ -536,6 +536,11 @@ struct hnsw_index {
     // whenever it exists.  hnsw_index_insert and hnsw_index_remove quantise the whole table again while it is on.
     int bit_mode = 0;
     std::vector<float> bit_t;
+    // option "bit_query_bits": 4 = while the searches walk tables.Xb, the query keeps 4 bits a dimension (four bit planes of codes in
+    // -7..7, bits_asym_transform_queries) and the walk's key is the inner product's (the knn kernel's ROWS 7, hnsw_bits_asym_walk.hip);
+    // 0 = one bit, the Hamming walk.  The rows are the same copy either way.  Accepted, without effect, while other rows are walked.
+    // Not saved.
+    int bit_query_bits = 0;
     // option "filter_collect": the filtered searches answer from every node the walk evaluates, not from the final W only
     // (hnsw_search_collect_kernel; k <= 128, exact-row formats: it excludes half_rows and sq8_rows).  Not saved.
     bool filter_collect = false;
@@ -667,6 +672,18 @@ int make_bit_rows(::hnsw_index *idx, int mode);
 // ... and nq queries as the walk over those codes reads them, on `st`: the first 16 * NW words of every Qt row ([nq][padded_stride(d)]
 // floats) are the query's bits q_i > t_i, zero beyond d.  Q and stage: as sq8_transform_queries; Q == Qt is NOT allowed.
 int bits_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st);
+// ... and as the walk of option bit_query_bits 4 reads them: every Qt row is bit_plane_words(d) = 64 * NW words, the four bit planes
+// p0..p3 of the query's codes v = p0 + 2 p1 + 4 p2 - 8 p3 (include/hnsw_mi355x.h: the rule), each packed as a row's bits are.  One
+// wave per query.  Q and stage: as sq8_transform_queries; Q == Qt is NOT allowed.  codes (optional, [nq][d] int8, device): the v_i
+// themselves; Qt may then be null.
+int bits_asym_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, int8_t *codes,
+                                hipStream_t st);
+// hnsw_bits_asym_walk.hip, one object per accept rule: the knn kernel's ROWS = 7 instances, the walk over the same codes against
+// those planes under the inner product's key; nch here is NW
+hipError_t search_launch_bits_asym_0(int nch, int nslot, const hnsw_dev::IndexView &iv, const hnsw_dev::SearchArgs &a, hipStream_t st);
+hipError_t search_launch_bits_asym_1(int nch, int nslot, const hnsw_dev::IndexView &iv, const hnsw_dev::SearchArgs &a, hipStream_t st);
+int search_occupancy_bits_asym_0(int nch, int nslot, size_t lds, int blk);
+int search_occupancy_bits_asym_1(int nch, int nslot, size_t lds, int blk);
 // hnsw_bits_walk.hip, one object per accept rule (0 Ohnsw, 1 functor): the knn kernel's ROWS = 6 instances, the Hamming walk over
 // those codes under every metric; nch here is NW
 hipError_t search_launch_bits_0(int nch, int nslot, const hnsw_dev::IndexView &iv, const hnsw_dev::SearchArgs &a, hipStream_t st);
@@ -768,7 +785,13 @@ inline const char *codes_option(const ::hnsw_index *idx) {
     if (idx->bit_mode != 0 || idx->info.row_format == HNSW_ROWS_BITS) return "bit_rows";
     return idx->sq8d_on || idx->info.row_format == HNSW_ROWS_SQ8_DIM ? "sq8_dim_rows" : "sq8_rows";
 }
+// ... does it walk the bit rows against the 4-bit query's planes (option bit_query_bits 4; the kernel's ROWS 7)?
+inline bool walks_bit_planes(const ::hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_BITS && idx->bit_query_bits == 4; }
+// floats (words) per row of the matrix the walk over codes reads its queries from (RefineBufs::qt) -- what its allocation, the
+// transform and SearchArgs.q_stride share (walk_query_words, hnsw_bits_plan.h: the planes' rows have a stride of their own)
+inline int64_t walk_query_stride(const ::hnsw_index *idx) { return walk_query_words(idx->iv.d, walks_bit_planes(idx)); }
 inline int codes_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st) {
+    if (walks_bit_planes(idx)) return bits_asym_transform_queries(idx, Q, nq, q_stride, Qt, stage, nullptr, st);
     if (idx->info.row_format == HNSW_ROWS_BITS) return bits_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
     return idx->info.row_format == HNSW_ROWS_SQ8_DIM ? sq8_dim_transform_queries(idx, Q, nq, q_stride, Qt, stage, st)
                                                      : sq8_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);

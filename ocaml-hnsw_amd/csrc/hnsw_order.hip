@@ -110,7 +110,13 @@ hipError_t launch_descent(const hnsw_index *idx, int row_format, const float *Q,
             hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<NW, rows_in_flight_bits(NW), 0, 6>), dim3((unsigned)nq), dim3(64), lds, st,
                                idx->iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, (float *)nullptr);
         };
-        if (bit_words(idx->iv.d) == 2) launch(Int<2>{}); else launch(Int<1>{});
+        // ... or, against a 4-bit query (option bit_query_bits), ROWS 7: the inner product's key over the same rows
+        auto launch_asym = [&](auto NW) {
+            hipLaunchKernelGGL((hnsw_dev::hnsw_descent_kernel<NW, rows_in_flight_bits(NW), 1, 7>), dim3((unsigned)nq), dim3(64), lds, st,
+                               idx->iv, Q, qs, nq, to_layer, entry, key, nd, sortkey, index, (float *)nullptr);
+        };
+        if (walks_bit_planes(idx)) { if (bit_words(idx->iv.d) == 2) launch_asym(Int<2>{}); else launch_asym(Int<1>{}); }
+        else if (bit_words(idx->iv.d) == 2) launch(Int<2>{}); else launch(Int<1>{});
         return hipGetLastError();
     }
     switch (row_format) {

@@ -6,6 +6,9 @@
 // hnsw_bits_walk.hip).  The walk's distances never reach the caller: as over sq8 rows the search always ends in the exact re-rank
 // over the float32 rows under the index's real metric (refine_count in hnsw_capi.hip).  The copy is made on request only; the
 // float32 rows stay for everything that is not a knn walk.
+// Option "bit_query_bits" 4 walks the SAME rows against a query kept at 4 bits a dimension (bit_query_planes_kernel makes its codes and
+// bit planes here; the walk is the knn kernel's ROWS = 7, hnsw_bits_asym_walk.hip): an asymmetric distance, the inner product of the
+// query's codes with the +-1 vector a row's bits stand for.
 #include "hnsw_internal.h"
 
 using namespace hnsw_host;
@@ -98,6 +101,57 @@ bit_pack_kernel(const float *M, int64_t stride, int64_t rows, int32_t d, int32_t
     }
 }
 
+// Option "bit_query_bits" 4: one row of M as its 4-bit codes (include/hnsw_mi355x.h states the rule): one wave per row, lane l holds
+// y_i = fl(x_i - t_i) of the dimensions 64 u + l (d <= 1024: at most 16 registers); a = max |y_i| over the wave, r = fl(7 / a) -- a
+// correctly rounded division --, v_i = rint(fl(y_i * r)) half-to-even, in -7..7; every code is 0 when a = 0, a y_i is NaN or infinite,
+// or r is infinite.  out (optional, [rows][out_stride] dwords): the four bit planes of the two's-complement nibbles, plane p in words
+// 2 * units_per_row * p .. of the row, each packed as bit_pack_kernel packs bits (a ballot is two words; units_per_row = 8 * NW
+// covers a plane with its zero padding).  codes (optional, [rows][d] int8): the v_i themselves.  thr, stage: as bit_pack_kernel.
+__global__ void __launch_bounds__(256)
+bit_query_planes_kernel(const float *M, int64_t stride, int64_t rows, int32_t d, int32_t units_per_row, const float *thr, uint32_t *out,
+                        int64_t out_stride, float *stage, int8_t *codes) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= rows) return;                       // (wave-uniform)
+    float y[16];
+    float a = 0.0f;
+    bool bad = false;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        const int dim = 64 * u + lane;
+        y[u] = 0.0f;
+        if (u < units_per_row && dim < d) {
+            const float x = M[row * stride + dim];
+            if (stage) stage[row * stride + dim] = x;
+            y[u] = x - thr[dim];
+            const float m = fabsf(y[u]);
+            bad = bad || !(m < __builtin_inff());  // NaN or infinite
+            a = fmaxf(a, m);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o));
+    const float r = __fdiv_rn(7.0f, a);
+    const bool zero = __builtin_amdgcn_ballot_w64(bad) != 0 || !(a > 0.0f) || !(r < __builtin_inff());
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        if (u < units_per_row) {                   // (wave-uniform)
+            const int dim = 64 * u + lane;
+            const int v = zero ? 0 : (int)rintf(__fmul_rn(y[u], r));
+            if (codes && dim < d) codes[row * d + dim] = (int8_t)v;
+            if (out) {
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const uint64_t m = __builtin_amdgcn_ballot_w64(((v >> p) & 1) != 0);
+                    if (lane == 0)
+                        *reinterpret_cast<uint2 *>(out + row * out_stride + 2 * units_per_row * p + 2 * u) = make_uint2((uint32_t)m, (uint32_t)(m >> 32));
+                }
+            }
+        }
+    }
+}
+
 unsigned grid_for_waves(int64_t waves, int64_t cap) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, (waves + 3) / 4)); }
 
 } // namespace
@@ -170,9 +224,40 @@ int bits_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, 
     return HNSW_OK;
 }
 
+int bits_asym_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, int8_t *codes,
+                                hipStream_t st) {
+    if (Qt && (const void *)Q == (const void *)Qt) return fail(HNSW_ERR_UNSUPPORTED, "bit rows: the query planes cannot be made in place");
+    if (nq <= 0) return HNSW_OK;
+    const int32_t units = 8 * bit_words(idx->iv.d);               // (a Qt row is bit_plane_words(d) = 4 planes * 2 * units words)
+    hipLaunchKernelGGL(bit_query_planes_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, Q, q_stride, nq, idx->iv.d, units,
+                       (const float *)idx->tables.bit_t.p, (uint32_t *)Qt, bit_plane_words(idx->iv.d), stage, codes);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(HNSW_ERR_HIP, "bit-row query planes launch failed: %s", hipGetErrorString(e));
+    return HNSW_OK;
+}
+
 } // namespace hnsw_host
 
 extern "C" {
+
+int32_t hnsw_index_bit_query_codes(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int8_t *out) {
+    if (!idx || !queries || !out) return fail(HNSW_ERR_BAD_ARG, "null argument");
+    if (nq < 0 || nq > 0x7FFFFFFFLL) return fail(HNSW_ERR_BAD_ARG, "nq=%lld out of range", (long long)nq);
+    if (q_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "q_stride < d");
+    if (!idx->bit_mode || !idx->tables.Xb.p) return fail(HNSW_ERR_BAD_ARG, "the index has no bit rows (option bit_rows 1 or 2 makes them)");
+    if (nq == 0) return HNSW_OK;
+    HIP_TRY(hipSetDevice(idx->device));
+    const size_t d = (size_t)idx->iv.d;
+    DevBuf q, codes;
+    int rc;
+    if ((rc = q.ensure((size_t)nq * d * 4)) || (rc = codes.ensure((size_t)nq * d))) return rc;
+    HIP_TRY(hipMemcpy2D(q.p, d * 4, queries, (size_t)q_stride * 4, d * 4, (size_t)nq, hipMemcpyHostToDevice));
+    // (COSINE: the codes are those of N(Q), as the searches make them behind the index's own normalisation)
+    if (is_cosine(idx) && (rc = cosine_normalise((const float *)q.p, nq, idx->iv.d, (int64_t)d, (float *)q.p, (int64_t)d, nullptr, nullptr, nullptr))) return rc;
+    if ((rc = bits_asym_transform_queries(idx, (const float *)q.p, nq, (int64_t)d, nullptr, nullptr, (int8_t *)codes.p, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(out, codes.p, (size_t)nq * d, hipMemcpyDeviceToHost));
+    return HNSW_OK;
+}
 
 int32_t hnsw_index_bit_params(const hnsw_index *idx, float *t) {
     if (!idx || !t) return fail(HNSW_ERR_BAD_ARG, "null argument");

@@ -233,6 +233,18 @@ inline Bits bits(const Hgraph &g) {
     return out;
 }
 
+// The 4-bit query codes of option "bit_query_bits" (hnsw_index_set_option(h, "bit_query_bits", 4): the walk over the bit rows keeps
+// the query at 4 bits a dimension): for Q, [nq][d] floats, the [nq][d] codes in -7..7 the walk would use.  Throws
+// std::invalid_argument while option "bit_rows" is off.
+inline std::vector<int8_t> bit_query_codes(const Hgraph &g, const std::vector<float> &Q) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    const size_t d = (size_t)inf.d, nq = d ? Q.size() / d : 0;
+    std::vector<int8_t> out(nq * d);
+    check(hnsw_index_bit_query_codes(g.handle(), Q.data(), (int64_t)nq, (int64_t)d, out.data()));
+    return out;
+}
+
 // N(X) (hnsw_normalise_batch): every vector of `batch` scaled to unit length by the normaliser the header defines -- the rows a
 // HNSW_METRIC_COSINE index stores for X and searches for a query batch X -- as [n][dim] floats; norms (optional): the n norms.  A
 // zero vector stays zero, a vector whose sum of squares is not finite becomes NaN.  The metric itself is accepted wherever one is:

@@ -99,6 +99,11 @@ let hnsw_index_bit_params =
   foreign ~from:lib "hnsw_index_bit_params" (index @-> ptr float @-> returning int32_t)
 let hnsw_index_bit_codes =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_bit_codes" (index @-> ptr void @-> returning int32_t)
+(* the 4-bit query codes of option "bit_query_bits" (`hnsw_index_set_option idx "bit_query_bits" 4L`: the walk over the bit rows keeps
+   the query at 4 bits a dimension, see the C header): [nq][d] int8 in -7..7 for nq host queries *)
+let hnsw_index_bit_query_codes =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_bit_query_codes"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> ptr void @-> returning int32_t)
 (* cosine distance (metric_cosine below; the twin contract of the C header): the normaliser N as an operator of its own, and the
    float32 rows an index holds -- for a cosine index N(X), not the vectors it was handed *)
 let hnsw_normalise_batch =
@@ -1276,6 +1281,18 @@ let bit_codes (t : t) : (int32, Bigarray.int32_elt, Bigarray.c_layout) Bigarray.
   check (hnsw_index_get_info t.handle (addr inf));
   let out = Bigarray.Array2.create Bigarray.int32 Bigarray.c_layout (max 1 (Int64.to_int (getf inf ii_n))) ((t.dim + 31) / 32) in
   check (hnsw_index_bit_codes t.handle (to_voidp (bigarray_start array2 out)));
+  out
+
+(* the codes in -7..7 that the walk over the bit rows uses for [queries] (one query per row, t.dim columns) under option
+   "bit_query_bits" 4: one row of t.dim codes per query; Invalid_argument while option "bit_rows" is off *)
+let bit_query_codes (t : t) (queries : (float, Bigarray.float32_elt, Bigarray.c_layout) Bigarray.Array2.t)
+    : (int, Bigarray.int8_signed_elt, Bigarray.c_layout) Bigarray.Array2.t =
+  let nq = Bigarray.Array2.dim1 queries in
+  if Bigarray.Array2.dim2 queries <> t.dim then invalid_arg "Hnsw_mi355x.bit_query_codes: dimension mismatch";
+  let out = Bigarray.Array2.create Bigarray.int8_signed Bigarray.c_layout (max 1 nq) t.dim in
+  if nq > 0 then
+    check (hnsw_index_bit_query_codes t.handle (bigarray_start array2 queries) (Int64.of_int nq) (Int64.of_int t.dim)
+             (to_voidp (bigarray_start array2 out)));
   out
 
 (* ?metric of [create], [build], [of_ohnsw], [of_ba] and [sharded_build]: HNSW_METRIC_L2, _IP, _COSINE.  A cosine index stores

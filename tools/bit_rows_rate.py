@@ -12,7 +12,11 @@ are switched on that handle, at ef in {128, 256, 512} and R in {0, 4 k, -1}, k 1
 Method: every configuration is warmed by one untimed call; the configurations are visited in --rounds rounds, alternating the formats
 inside each round, --steps timed calls per visit; the figure is the median over all of a configuration's calls and the spread its
 min .. max.  One process, nothing else of ours on the device.  The table printed here is what profiles/bit_rows.txt holds.
-Usage: python tools/bit_rows_rate.py [--dims 1024,512] [--n 200000] [--rounds 3] [--steps 5]"""
+--query-bits: the leg of option "bit_query_bits" instead (profiles/bit_query_bits.txt): the formats are sq8_dim_rows, bit_rows 1 with
+the query at one bit (the Hamming walk) and bit_rows 1 with bit_query_bits 4 (the same rows against the 4-bit query), alternated
+on the one handle, at refine -1 and 40.  The pre-pass column holds the query transform as well (it is queued behind the first event),
+so its difference between the two bit formats bounds what the 4-bit transform and the descent against the planes cost.
+Usage: python tools/bit_rows_rate.py [--dims 1024,512] [--n 200000] [--rounds 3] [--steps 5] [--query-bits]"""
 import argparse
 import os
 import sys
@@ -26,12 +30,15 @@ import half_rows_rate as R  # noqa: E402
 
 H = R.H
 K = 10
-FORMATS = (("float32", None, 0), ("sq8_dim", "sq8_dim_rows", 1), ("bits/mean", "bit_rows", 1), ("bits/sign", "bit_rows", 2))
+FORMATS = (("float32", None, 0, 0), ("sq8_dim", "sq8_dim_rows", 1, 0), ("bits/mean", "bit_rows", 1, 0), ("bits/sign", "bit_rows", 2, 0))
+# (name, option, value, bit_query_bits) of the --query-bits leg
+QUERY_BITS_FORMATS = (("float32", None, 0, 0), ("sq8_dim", "sq8_dim_rows", 1, 0), ("bits/q1", "bit_rows", 1, 0), ("bits/q4", "bit_rows", 1, 4))
 
 
-def switch(hg, option, value):
+def switch(hg, option, value, query_bits=0):
     for other in ("sq8_dim_rows", "bit_rows"):
         hg.set_option(other, -1 if other == "sq8_dim_rows" else 0)
+    hg.set_option("bit_query_bits", query_bits)
     if option:
         hg.set_option(option, value)
 
@@ -60,7 +67,7 @@ def timed(hg, Qd, ef, ids_t, dist_t, steps):
     return calls, kern, pre
 
 
-def run(d, n, nq, rounds, steps):
+def run(d, n, nq, rounds, steps, query_bits=False):
     X, Q = R.clustered_unit(n, d, 1), R.clustered_unit(nq, d, 2)
     t0 = time.time()
     hg = H.Ohnsw.build_batch_bigarray(X, 16, 200, seed=1, metric=H.METRIC_IP)
@@ -70,13 +77,14 @@ def run(d, n, nq, rounds, steps):
     ids_t = torch.empty((nq, K), dtype=torch.int32, device=R.DEV)
     dist_t = torch.empty((nq, K), dtype=torch.float32, device=R.DEV)
     gt = H.Ohnsw.brute_force_knn(hg, K, Q[:1000])[0]
-    configs = [(f, ef, r) for ef in (128, 256, 512) for f in FORMATS for r in ((0,) if f[1] is None else (0, 4 * K, -1))]
+    formats, refines = (QUERY_BITS_FORMATS, (4 * K, -1)) if query_bits else (FORMATS, (0, 4 * K, -1))
+    configs = [(f, ef, r) for ef in (128, 256, 512) for f in formats for r in ((0,) if f[1] is None else refines)]
     acc = {c: ([], [], []) for c in configs}
     rec, row_bytes = {}, {}
     for rnd in range(rounds + 1):                    # round 0 warms every configuration and takes its recall: not timed
         for cfg in configs:
-            (name, option, value), ef, refine = cfg
-            switch(hg, option, value)
+            (name, option, value, qbits), ef, refine = cfg
+            switch(hg, option, value, qbits)
             hg.set_option("refine", refine)
             if rnd == 0:
                 ids = H.Ohnsw.knn_batch_bigarray(hg, K, Q[:1000], ef=ef)[0]
@@ -87,7 +95,7 @@ def run(d, n, nq, rounds, steps):
                 into.extend(got)
     base = {}
     for cfg in configs:
-        (name, option, value), ef, refine = cfg
+        (name, option, value, qbits), ef, refine = cfg
         calls, kern, pre = (np.array(a) for a in acc[cfg])
         if option is None:
             base[ef] = (np.median(calls), np.median(kern))
@@ -109,10 +117,11 @@ def main():
     ap.add_argument("--nq", type=int, default=10000)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--query-bits", action="store_true", help="the leg of option bit_query_bits: the bit rows against a 1-bit and a 4-bit query")
     a = ap.parse_args()
     H.load()
     for d in (int(x) for x in a.dims.split(",")):
-        run(d, a.n, a.nq, a.rounds, a.steps)
+        run(d, a.n, a.nq, a.rounds, a.steps, a.query_bits)
 
 
 if __name__ == "__main__":
