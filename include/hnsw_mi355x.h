@@ -1427,6 +1427,74 @@ int32_t hnsw_brute_force_batch_grouped(hnsw_index *idx, const hnsw_labels *label
                                        const float *queries, int64_t nq, int64_t q_stride, int32_t k, int32_t fill,
                                        int32_t *out_ids, float *out_dist, int32_t *out_labels);
 
+/* ---- keys: stable 64-bit names the index owns -- search, find and mutate by key ----
+ * hnsw_index_remove and hnsw_index_compact renumber every surviving node, so a row number is no name to keep.  An index may own one
+ * KEY per stored node: a caller-chosen int64_t, every value legal (INT64_MIN, -1, 0 and INT64_MAX included), pairwise distinct
+ * within the index.  The index keeps the keys on the device in row order (key_of, 8 n bytes) beside a lookup table of the n pairs
+ * (key, node) ordered by key as SIGNED 64-bit numbers (12 n bytes), rebuilt from key_of whenever that changes, and moves the keys
+ * with their nodes through insert, remove and compact.  Everything here is opt-in: a handle never given keys behaves bit for bit as
+ * before, and no other entry point changes its result on such a handle.  The tables belong to the handle as the live mask does:
+ * NOT counted in hnsw_index_info.device_bytes; hnsw_index_keys_info reports has_keys (0 / 1) and their bytes (each pointer may be
+ * NULL).  Every call below but set / clear / info / insert_keyed answers HNSW_ERR_BAD_ARG on a handle without keys.
+ *
+ * hnsw_index_set_keys(idx, keys, n): n must be the index's n; NULL keys with n > 0 are refused.  The keys must be pairwise distinct,
+ *   otherwise HNSW_ERR_BAD_ARG and the message names the smallest duplicated key (a min-reduction on the device, not the first to
+ *   arrive).  All or nothing: on any error, HNSW_ERR_OOM included, the handle keeps the keys it had, or none.  A second call
+ *   replaces all keys.  It does not move the graph epoch: filters and labels stay valid.  A replica of an hnsw_multi or a shard of
+ *   an hnsw_sharded is refused, as hnsw_index_insert refuses them.
+ * hnsw_index_clear_keys: afterwards the handle is one that never had keys.
+ * hnsw_index_keys_of(idx, ids, m, missing_key, out): out[i] = the key of node ids[i] (id_base-based); any id outside
+ *   [id_base, id_base + n) gives missing_key -- that includes the searches' fill id -1.  A node marked deleted still has its key:
+ *   the ids are explicit.  ids == NULL: all n rows in order, m must be n.  This is the operator that makes every other search form
+ *   usable with keys: range results, grouped rows, the per-query-filter call, the layer operators.  hnsw_index_keys_of_device is
+ *   the same over device arrays, queued on `stream` (d_ids and d_out must not be NULL when m > 0).
+ * hnsw_index_find_keys(idx, keys, m, out_ids): out_ids[i] = the id_base-based id of the node whose key is keys[i], or id_base - 1
+ *   if there is none (a binary search per key on the device).  Repeated keys in the call are fine; m == 0 is a no-op.
+ * hnsw_search_batch_keyed: with f NULL the rows are those of hnsw_search_batch (marks honoured as there), otherwise those of
+ *   hnsw_search_batch_filtered(f); both passed through hnsw_index_keys_of with missing_key: out_keys [nq][k].  Distances and
+ *   counters are bit-identical to those calls', errors are theirs.  out_stage is optional: as the filtered call writes it, and zero
+ *   for the plain path of an unmarked handle.  It costs one translate launch over the device-resident ids and the download of
+ *   8-byte instead of 4-byte rows, not a second pass over host memory.
+ * hnsw_index_insert_keyed(idx, vectors, m, row_stride, keys, params): hnsw_index_insert of the vectors -- the graph is link for
+ *   link what the plain call builds on a twin without keys -- with the m keys appended to key_of.  Refused before anything is
+ *   built, the index and its keys untouched: a key equal to a stored key, or two equal keys in the call (HNSW_ERR_BAD_ARG, the key
+ *   named); an index without keys that has n > 0 (hnsw_index_set_keys first).  An EMPTY index without keys starts its keys with this
+ *   call.  Plain hnsw_index_insert on a handle with keys is refused (HNSW_ERR_BAD_ARG, pointing at the keyed call): an index with
+ *   keys must never hold a node without one.
+ * hnsw_index_remove, hnsw_index_compact on a handle with keys: the keys move with their nodes under out_new_id's numbering
+ *   (new_key_of[new_id[v]] = key_of[v], on the device), inside the all-or-nothing swap.  Removing every node leaves an empty index
+ *   that still has keys (none).
+ * hnsw_index_remove_keys(idx, keys, m, out_new_id) is hnsw_index_remove(find(keys)); hnsw_index_mark_deleted_keys and
+ *   hnsw_index_unmark_deleted_keys are hnsw_index_mark_deleted(find(keys)) and hnsw_index_unmark_deleted(find(keys)).  An absent
+ *   key is HNSW_ERR_BAD_ARG with the key named (the first by position), and nothing is changed.  Duplicates: remove's and mark's rule.
+ * hnsw_filter_create_by_keys(idx, keys, m, out): an ordinary filter that allows exactly the named nodes, ANDed with the live mask
+ *   as hnsw_filter_create's is.  An absent key is refused, naming the first by position; a repeated key is fine; on error *out is NULL.
+ * hnsw_index_save stays accepted and the format does not change: keys are NOT saved.  hnsw_index_keys_of(NULL ids) before the
+ *   save and hnsw_index_set_keys on the loaded handle is the round trip.
+ *
+ * NOT BUILT: keys for hnsw_sharded and hnsw_multi; upsert (replace the vector under a key); saved keys; keyed forms of the range,
+ * grouped and per-query-filter calls -- compose those with hnsw_index_keys_of.
+ * Rates (tools/keys_rate.py, profiles/keys.txt; one run), MI355X, 1 M x 128 byte rows, ef 128, k 10, 10 k queries, the two calls
+ * alternating on one handle: hnsw_search_batch_keyed 0.894 ms per batch against 0.849 ms for hnsw_search_batch (+0.045 ms: the
+ * launch and 800 KB of keys downloaded where the plain call downloads 400 KB of ids); hnsw_index_set_keys of 1 M keys 1.75 ms;
+ * hnsw_index_find_keys 0.05 ms for 10 k keys and 0.99 ms for 1 M; hnsw_index_remove_keys of 1000 keys 53 ms against 75 ms for
+ * hnsw_index_remove of the same nodes on a twin (one run each). */
+int32_t hnsw_index_set_keys(hnsw_index *idx, const int64_t *keys, int64_t n);
+int32_t hnsw_index_clear_keys(hnsw_index *idx);
+int32_t hnsw_index_keys_info(const hnsw_index *idx, int32_t *has_keys, int64_t *bytes);
+int32_t hnsw_index_keys_of(const hnsw_index *idx, const int32_t *ids, int64_t m, int64_t missing_key, int64_t *out);
+int32_t hnsw_index_keys_of_device(hnsw_index *idx, const int32_t *d_ids, int64_t m, int64_t missing_key, int64_t *d_out, void *stream);
+int32_t hnsw_index_find_keys(const hnsw_index *idx, const int64_t *keys, int64_t m, int64_t *out_ids);
+int32_t hnsw_search_batch_keyed(hnsw_index *idx, const hnsw_filter *f /* may be NULL */, const float *queries, int64_t nq,
+                                int64_t q_stride, const hnsw_search_params *params, int64_t missing_key, int64_t *out_keys,
+                                float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage);
+int32_t hnsw_index_insert_keyed(hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const int64_t *keys,
+                                const hnsw_build_params *params);
+int32_t hnsw_index_remove_keys(hnsw_index *idx, const int64_t *keys, int64_t m, int32_t *out_new_id);
+int32_t hnsw_index_mark_deleted_keys(hnsw_index *idx, const int64_t *keys, int64_t m);
+int32_t hnsw_index_unmark_deleted_keys(hnsw_index *idx, const int64_t *keys, int64_t m);
+int32_t hnsw_filter_create_by_keys(hnsw_index *idx, const int64_t *keys, int64_t m, hnsw_filter **out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,18 @@ _ABI = {
     "hnsw_labels_get": [_vp, _vp],
     "hnsw_search_batch_grouped": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_brute_force_batch_grouped": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
+    "hnsw_index_set_keys": [_vp, _vp, _i64],
+    "hnsw_index_clear_keys": [_vp],
+    "hnsw_index_keys_info": [_vp, _vp, _vp],
+    "hnsw_index_keys_of": [_vp, _vp, _i64, _i64, _vp],
+    "hnsw_index_keys_of_device": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "hnsw_index_find_keys": [_vp, _vp, _i64, _vp],
+    "hnsw_search_batch_keyed": [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_index_insert_keyed": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "hnsw_index_remove_keys": [_vp, _vp, _i64, _vp],
+    "hnsw_index_mark_deleted_keys": [_vp, _vp, _i64],
+    "hnsw_index_unmark_deleted_keys": [_vp, _vp, _i64],
+    "hnsw_filter_create_by_keys": [_vp, _vp, _i64, _vp],
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -271,6 +283,19 @@ def normalise(X, device=0, norms=False):
     nrm = _np.empty(n, _np.float32) if norms else None
     _check(load().hnsw_normalise_batch(device, _ptr(A), n, d, max(stride, d), _ptr(out), d, _ptr(nrm)))
     return (out, nrm) if norms else out
+
+
+def _keys(keys):
+    """a vector of keys as the library reads it: contiguous int64 (every int64 value is a legal key)"""
+    a = _np.asarray(keys)
+    if a.size and a.dtype.kind not in "iu":
+        raise InvalidArgument("keys must be integers")
+    if a.dtype == _np.uint64 and a.size and int(a.max()) >= 2 ** 63:
+        raise InvalidArgument("keys must fit a signed 64-bit integer")
+    return _np.ascontiguousarray(a, dtype=_np.int64).reshape(-1)
+
+
+MISSING_KEY = -1         # the default `missing` of the keyed calls: what a row holds where the search wrote its fill id
 
 
 def _out_pair(nq, k, out):
@@ -632,6 +657,85 @@ class Hgraph:
             self._adopt(self.info())
         return new_id
 
+    def _shrunk(self, new_id):
+        """after a removal: the host vectors (if any) lose the removed rows, n and the widths follow the device index"""
+        X = self.vectors
+        if X is not None:
+            self.vectors = _np.ascontiguousarray(_np.asarray(X, dtype=_np.float32)[new_id >= self.id_base])
+            self.row_stride = self.d
+        self._adopt(self.info())
+
+    # ---- keys the index owns (hnsw_index_set_keys ...): stable int64 names that survive remove_batch and compact ----
+    def set_keys(self, keys):
+        """hnsw_index_set_keys: one caller-chosen int64 key per stored node, in row order, pairwise distinct (a duplicate is refused
+        naming the smallest duplicated key; the handle then keeps the keys it had).  The index keeps them on the device and moves
+        them with their nodes through insert_batch_keyed, remove_batch and compact.  Filters and labels stay valid."""
+        k = _keys(keys)
+        _check(load().hnsw_index_set_keys(self.handle, _ptr(k) if k.size else None, k.size))
+
+    def clear_keys(self):
+        """hnsw_index_clear_keys: afterwards the index is one that never had keys"""
+        _check(load().hnsw_index_clear_keys(self.handle))
+
+    def keys_info(self):
+        """hnsw_index_keys_info -> (has_keys, bytes on the device: not part of info().device_bytes)"""
+        has, b = _C.c_int32(0), _C.c_int64(0)
+        _check(load().hnsw_index_keys_info(self.handle, _C.byref(has), _C.byref(b)))
+        return bool(has.value), b.value
+
+    def keys(self, ids=None, missing=MISSING_KEY):
+        """hnsw_index_keys_of: the keys of the nodes `ids` (id_base-based, any shape; None: all n in row order) as int64 of that
+        shape; `missing` where an id names no node -- the searches' fill id -1 included.  What turns the ids of ANY search form
+        (range, grouped, per-query filters, layer operators) into keys."""
+        if ids is None:
+            n = self.info().n
+            out = _np.empty(n, _np.int64)
+            _check(load().hnsw_index_keys_of(self.handle, None, n, int(missing), _ptr(out) if n else None))
+            return out
+        a = _np.asarray(ids)
+        if a.size and (a.min() < -(2 ** 31) or a.max() >= 2 ** 31):
+            a = _np.where((a < -(2 ** 31)) | (a >= 2 ** 31), self.id_base - 1, a)        # (no node either way)
+        a = _np.ascontiguousarray(a, dtype=_np.int32)
+        out = _np.empty(a.shape, _np.int64)
+        if a.size:
+            _check(load().hnsw_index_keys_of(self.handle, _ptr(a), a.size, int(missing), _ptr(out)))
+        return out
+
+    def find_keys(self, keys):
+        """hnsw_index_find_keys -> int64 ids (id_base-based) of the nodes with these keys, id_base - 1 where no node has the key"""
+        k = _keys(keys)
+        out = _np.empty(k.size, _np.int64)
+        _check(load().hnsw_index_find_keys(self.handle, _ptr(k) if k.size else None, k.size, _ptr(out) if k.size else None))
+        return out
+
+    def remove_keys(self, keys):
+        """hnsw_index_remove_keys: Ohnsw.remove_batch of the nodes with these keys (an absent key is refused, nothing changed)
+        -> the new id of every old node, as remove_batch"""
+        k = _keys(keys)
+        new_id = _np.empty(self.n, _np.int32)
+        _check(load().hnsw_index_remove_keys(self.handle, _ptr(k) if k.size else None, k.size, _ptr(new_id)))
+        if k.size:
+            self._shrunk(new_id)
+        return new_id
+
+    def mark_deleted_keys(self, keys):
+        """hnsw_index_mark_deleted_keys: mark_deleted of the nodes with these keys (an absent key is refused, nothing changed)"""
+        k = _keys(keys)
+        _check(load().hnsw_index_mark_deleted_keys(self.handle, _ptr(k) if k.size else None, k.size))
+
+    def unmark_deleted_keys(self, keys):
+        """hnsw_index_unmark_deleted_keys: unmark_deleted of the nodes with these keys"""
+        k = _keys(keys)
+        _check(load().hnsw_index_unmark_deleted_keys(self.handle, _ptr(k) if k.size else None, k.size))
+
+    def filter_by_keys(self, keys):
+        """hnsw_filter_create_by_keys -> Filter: allows exactly the nodes with these keys (repeats are fine, an absent key is
+        refused), ANDed with the live mask as Hgraph.filter's is"""
+        k = _keys(keys)
+        f = _C.c_void_p()
+        _check(load().hnsw_filter_create_by_keys(self.handle, _ptr(k) if k.size else None, k.size, _C.byref(f)))
+        return Filter._adopt(self, f, self.info().n)
+
     def kernel_times(self):
         """(search kernel ms, ordering pre-pass ms, calls) averaged over the device-entry calls since the
         last call (needs set_option("time_kernels", 1)); waits for them."""
@@ -852,6 +956,26 @@ def _search_filtered(hgraph, flt, batch, ef, k, fill, counters=False, sem=0, out
         if own is not None:
             own.release()
     return (ids, dist, nd, nh, stage) if counters else (ids, dist)
+
+
+def _search_keyed(hgraph, batch, ef, k, fill, counters=False, sem=0, flt=None, missing=MISSING_KEY):
+    """hnsw_search_batch_keyed; flt: None, a Filter, or what Hgraph.filter takes
+    -> (keys, dist), with counters (keys, dist, ndist, nhops, stage)."""
+    own = None if flt is None or isinstance(flt, Filter) else Filter(hgraph, flt)
+    try:
+        Q, qs, nq = _batch(hgraph.d, batch)
+        keys = _np.empty((nq, max(k, 0)), _np.int64)
+        dist = _np.empty((nq, max(k, 0)), _np.float32)
+        nd = _np.zeros(nq, _np.uint32) if counters else None
+        nh = _np.zeros(nq, _np.uint32) if counters else None
+        stage = _np.zeros(nq, _np.uint32) if counters else None
+        p = _SearchParams(ef, k, fill, sem)
+        _check(load().hnsw_search_batch_keyed(hgraph.handle, None if flt is None else (own or flt).handle, _ptr(Q), nq, qs, _C.byref(p),
+                                              int(missing), _ptr(keys), _ptr(dist), _ptr(nd), _ptr(nh), _ptr(stage)))
+    finally:
+        if own is not None:
+            own.release()
+    return (keys, dist, nd, nh, stage) if counters else (keys, dist)
 
 
 def _search_filtered_each(hgraph, filters, which, batch, ef, k, fill, counters=False, sem=0, out=None):
@@ -1092,6 +1216,13 @@ class Ohnsw:
         return _search_grouped(hgraph, labels, batch, k if ef is None else ef, k, FILL_OHNSW, counters, flt=filter)
 
     @staticmethod
+    def knn_batch_keyed(hgraph, k, batch, ef=None, filter=None, counters=False, missing=MISSING_KEY):
+        """knn_batch_bigarray answered in the index's keys (hnsw_search_batch_keyed; Hgraph.set_keys) -> (keys, distances), with
+        counters (keys, distances, ndist, nhops, stage): keys [nq][k] int64, `missing` where fewer than k were found.  filter (a
+        Filter, or what Hgraph.filter takes): the rows of knn_batch_filtered instead.  Distances and counters are those calls'."""
+        return _search_keyed(hgraph, batch, k if ef is None else ef, k, FILL_OHNSW, counters, flt=filter, missing=missing)
+
+    @staticmethod
     def brute_force_grouped(hgraph, k, batch, labels, filter=None, fill=FILL_OHNSW):
         """The exact grouped search (hnsw_brute_force_batch_grouped) -> (ids, distances, labels): per label its nearest node under
         (distance, id) over all n float32 vectors, of those the k nearest, ascending.  Needs no graph."""
@@ -1199,6 +1330,29 @@ class Ohnsw:
         return _np.arange(n_old + hgraph.id_base, n_old + m + hgraph.id_base, dtype=_np.int64)
 
     @staticmethod
+    def insert_batch_keyed(hgraph, batch, keys, num_connections, num_nodes_search_construction, seed=0, max_batch=0, batch_div=0,
+                           expected_ef=0, expected_sem=SEM_OHNSW, metric=None):
+        """insert_batch into an index that owns keys (hnsw_index_insert_keyed): the same graph, with keys[i] the key of row i of
+        `batch`.  A key that is stored already, or twice in `keys`, refuses the call before anything is built; so does an index
+        that has nodes and no keys (Hgraph.set_keys first; an EMPTY one starts its keys here).  -> the new ids."""
+        X, xs = _rows(batch)
+        if X.ndim != 2 or (X.shape[0] and X.shape[1] != hgraph.d):
+            raise InvalidArgument("batch must be [m][d] with the index's d = %d" % hgraph.d)
+        kk = _keys(keys)
+        m = X.shape[0]
+        if kk.size != m:
+            raise InvalidArgument("%d keys for %d vectors" % (kk.size, m))
+        n_old = hgraph.n
+        p = _BuildParams(num_connections, num_nodes_search_construction, hgraph.metric if metric is None else int(metric), hgraph.id_base, seed, max_batch,
+                         batch_div, expected_ef, expected_sem)
+        _check(load().hnsw_index_insert_keyed(hgraph.handle, _ptr(X), m, max(xs, hgraph.d), _ptr(kk) if m else None, _C.byref(p)))
+        if m == 0:
+            return _np.arange(0, dtype=_np.int64)
+        hgraph._append_vectors(X)
+        hgraph._adopt(hgraph.info())
+        return _np.arange(n_old + hgraph.id_base, n_old + m + hgraph.id_base, dtype=_np.int64)
+
+    @staticmethod
     def remove_batch(hgraph, ids):
         """Hard deletion on the device (hnsw_index_remove): the stored nodes `ids` (id_base-based, distinct) leave the index, the
         others keep their order and are renumbered, and the graph is repaired by the three-pass rule the header defines.  -> the
@@ -1287,6 +1441,12 @@ class Ba:
         """knn_batch over groups (see Ohnsw.knn_batch_grouped; the functor accept rule, 1-based ids in a 1-based index, +inf / -1
         where there are fewer than k groups) -> (ids, distances, labels), with counters (..., ndist, nhops, stage)."""
         return _search_grouped(hgraph, labels, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR, flt=filter)
+
+    @staticmethod
+    def knn_batch_keyed(hgraph, batch, num_neighbours_search, num_neighbours, filter=None, counters=False, missing=MISSING_KEY):
+        """knn_batch answered in the index's keys (see Ohnsw.knn_batch_keyed; the functor accept rule, +inf / `missing` where fewer
+        than k were found) -> (keys, distances), with counters (..., ndist, nhops, stage)."""
+        return _search_keyed(hgraph, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR, flt=filter, missing=missing)
 
     @staticmethod
     def range_search(hgraph, batch, num_neighbours_search, radius, counters=False, filter=None):

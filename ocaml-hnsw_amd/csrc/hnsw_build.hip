@@ -335,7 +335,8 @@ int check_upper_rows(const hnsw_index *idx, const char *verb) {
 // sq8 rows while option sq8_rows is 1 (the WHOLE table is quantised again: new vectors may widen the range; a range that
 // overflows refuses the whole insert), the per-dimension sq8 rows while option sq8_dim_rows is 1 (likewise), the locality codes (carry_codes: carried over as extend_locality_codes does; else dropped
 // and built on demand).  Then the tables are swapped in and the graph epoch moves on.  On any error idx is as it was.
-int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics, const int32_t *new_id) {
+int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics, const int32_t *new_id,
+                const int64_t *append_keys) {
     int32_t rc = make_byte_rows(nx.get());
     if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx.get());
     if (!rc && idx->half_rows_on && nx->iv.n > 0) rc = make_half_rows(nx.get());
@@ -346,6 +347,9 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
     // soft deletion: the marks move with their nodes; the new live mask is complete before anything is swapped
     std::unique_ptr<hnsw_filter> live;
     if (!rc) rc = renumbered_live_filter(idx, new_id, nx->iv.n, live);
+    // keys: they move with their nodes too (on the device: keys_renumber_kernel), lookup table and all, before anything is swapped
+    std::unique_ptr<KeyTables> keys;
+    if (!rc) rc = renumbered_keys(idx, new_id, nx->iv.n, append_keys, keys);
     if (rc) {
         nx.reset();
         (void)hipGetLastError();                    // (a failed allocation must not surface in the next call on this handle)
@@ -371,6 +375,7 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
     idx->n_deleted = live ? n - live->n_allowed : 0;
     if (live) live->epoch = idx->epoch;
     idx->live = std::move(live);                           // (null when nothing is marked any more)
+    idx->keys = std::move(keys);                           // (null on a handle without keys)
     // the per-shape decisions that follow n or the row format
     idx->forget_shapes(/*keep_visited=*/carry_codes && rows_before == idx->info.row_format);
     if (idx->fb_queries > 0 && n > 0) idx->fb_queries = std::min<int64_t>((int64_t)idx->dFbSlab.bytes / (n * 4), 65536);
@@ -458,6 +463,14 @@ int32_t hnsw_build(const float *vectors, int64_t n, int32_t d, int64_t row_strid
 }
 
 int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p) {
+    if (idx && idx->keys)
+        return fail(HNSW_ERR_BAD_ARG, "the index has keys and must never hold a node without one: hnsw_index_insert_keyed (the keyed call) inserts into it");
+    return insert_vectors(idx, vectors, m, row_stride, p, nullptr);
+}
+
+} // extern "C"
+
+int hnsw_host::insert_vectors(hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p, const int64_t *keys) {
     if (!idx || !p) return fail(HNSW_ERR_BAD_ARG, "null argument");
     if (m < 0) return fail(HNSW_ERR_BAD_ARG, "m=%lld < 0", (long long)m);
     if (m == 0) return HNSW_OK;
@@ -502,8 +515,10 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
         (void)hipGetLastError();
         return rc;
     }
-    return adopt_graph(idx, nx, /*carry_codes=*/true, p->expected_ef, p->expected_semantics);
+    return adopt_graph(idx, nx, /*carry_codes=*/true, p->expected_ef, p->expected_semantics, nullptr, keys);
 }
+
+extern "C" {
 
 // ---- select_neighbours operator ----------------------------------------------------------------------
 int32_t hnsw_select_neighbours_batch(hnsw_index *idx, const float *targets, int64_t nb, int64_t t_stride,

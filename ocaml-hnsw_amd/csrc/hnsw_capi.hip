@@ -739,13 +739,14 @@ int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q
     const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d), rbytes = (size_t)nq * k_ * 4, cbytes = (size_t)nq * 4;
     int rc;
     HostInput q;
-    if ((rc = idx->scratch.ensure(nq, qbytes, k_)) || (rc = ensure_host_call_state(idx)) || (rc = q.resolve(queries, qbytes, idx->scratch.q)))
+    if ((rc = idx->scratch.ensure(nq, qbytes, k_)) || (rc = ensure_host_call_state(idx)) || (rc = q.resolve(queries, qbytes, idx->scratch.q)) ||
+        (ko && (rc = idx->key_scratch.ensure(rbytes * 2))))
         return rc;
     int32_t *zi = (int32_t *)registered_device_address(out_ids, rbytes);
     float *zd = (float *)registered_device_address(out_dist, rbytes);
     uint32_t *znd = (uint32_t *)registered_device_address(out_nd, cbytes), *znh = (uint32_t *)registered_device_address(out_nh, cbytes);
     if (!zi || !zd) zi = nullptr, zd = nullptr;
-    small = allow_small && q.from && !zi && !znd && !znh && qbytes <= SMALL_BLOCK && rbytes <= SMALL_BLOCK && cbytes <= SMALL_BLOCK;
+    small = allow_small && !ko && q.from && !zi && !znd && !znh && qbytes <= SMALL_BLOCK && rbytes <= SMALL_BLOCK && cbytes <= SMALL_BLOCK;
     if (small) {
         if (!idx->hSmall) {
             HIP_TRY(idx->hSmall.alloc(5 * SMALL_BLOCK, hipHostMallocMapped));
@@ -780,7 +781,14 @@ int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q
 }
 
 int HostCall::finish(hnsw_index *idx, const char *what, hipStream_t st) {
-    const hipError_t ed = small ? hipSuccess : knn_download(b, k, ids, dist, nd, nh, st), es = st ? hipStreamSynchronize(st) : hipDeviceSynchronize();
+    hipError_t ed = small ? hipSuccess : knn_download(b, k, ids, dist, nd, nh, st);
+    int rk = HNSW_OK;
+    if (ko && ed == hipSuccess) {           // the rows as keys: one launch over the ids where the search left them, then their download
+        rk = keys_translate(idx, b.ids, b.nq * k, ko->missing, (int64_t *)idx->key_scratch.p, st);
+        if (!rk) ed = hipMemcpyAsync(ko->keys, idx->key_scratch.p, (size_t)b.nq * k * 8, hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = st ? hipStreamSynchronize(st) : hipDeviceSynchronize();
+    if (rk) return rk;
     if (ed != hipSuccess) return hip_fail(ed, "result download");
     if (es != hipSuccess) return fail(HNSW_ERR_HIP, "%s failed: %s", what, hipGetErrorString(es));
     if (small) {
@@ -1322,17 +1330,26 @@ int64_t head_rows(hnsw_index *idx, const hnsw_search_params *p, int64_t nq) {
 int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
                           const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
                           uint32_t *out_ndist, uint32_t *out_nhops) {
-    int rc = check_batch(idx, params, nq, q_stride, queries && out_ids && out_dist);
+    return knn_host_call(idx, queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, nullptr, nullptr);
+}
+
+} // extern "C"
+
+int hnsw_host::knn_host_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
+                             int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko) {
+    int rc = check_batch(idx, params, nq, q_stride, queries && (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist);
     if (rc) return rc;
     // nodes are marked deleted: the filtered search under the handle's live mask, ladder, exact stage and all
     if (idx->n_deleted > 0)
-        return hnsw_search_batch_filtered(idx, idx->live.get(), queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, nullptr);
+        return filtered_host_call(idx, idx->live.get(), queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, out_stage, ko);
     if (nq == 0) return rc;
+    if (out_stage) memset(out_stage, 0, (size_t)nq * 4);
     HIP_TRY(hipSetDevice(idx->device));
     // Where the matrices live: HostCall::begin.  The search is ordered longest walk first when the batch is larger than the chip
     // holds; whether any query needs the exactness fallback comes back as one word (pinned host memory, the kernel stores it),
     // not as a scan of nq status words.
     HostCall c;
+    c.ko = ko;
     bool q_in_place = false;
     if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
     hipStream_t st = idx->hs[0];
@@ -1372,6 +1389,8 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
     }
     return HNSW_OK;
 }
+
+extern "C" {
 
 int32_t hnsw_search_batch_h2d(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride,
                               const hnsw_search_params *params, int32_t *d_ids, float *d_dist,

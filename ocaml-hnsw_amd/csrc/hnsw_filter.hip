@@ -424,8 +424,9 @@ int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_para
 // both search entry points once their arguments are checked (nq > 0).  fs.d_masks / fs.d_which are allocated; host_masks (the
 // per-query form): what they hold is still to be uploaded, from there and from fs.which, on the call's stream
 int filtered_call(hnsw_index *idx, const FilterSet &fs, const uint32_t *const *host_masks, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
-                  int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage) {
+                  int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko = nullptr) {
     HostCall c;
+    c.ko = ko;
     bool q_in_place = false;
     int rc;
     if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
@@ -532,7 +533,15 @@ int32_t hnsw_filter_count(const hnsw_filter *f, int64_t *n_allowed) {
 int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
                                    const hnsw_search_params *params, int32_t *out_ids, float *out_dist, uint32_t *out_ndist,
                                    uint32_t *out_nhops, uint32_t *out_stage) {
-    int rc = check_batch(idx, params, nq, q_stride, queries && out_ids && out_dist);
+    return filtered_host_call(idx, f, queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, out_stage, nullptr);
+}
+
+} // extern "C"
+
+int hnsw_host::filtered_host_call(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
+                                  const hnsw_search_params *params, int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops,
+                                  uint32_t *out_stage, const KeysOut *ko) {
+    int rc = check_batch(idx, params, nq, q_stride, queries && (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist);
     if (rc) return rc;
     if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
         return fail(HNSW_ERR_BAD_ARG, "the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no filtered meaning");
@@ -541,8 +550,10 @@ int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const 
     HIP_TRY(hipSetDevice(idx->device));
     // the table of one filter: the mask's own address, on the device since the filter was made
     return filtered_call(idx, FilterSet{&f, 1, nullptr, f->table(), nullptr}, nullptr, queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops,
-                         out_stage);
+                         out_stage, ko);
 }
+
+extern "C" {
 
 int32_t hnsw_search_batch_filtered_each(hnsw_index *idx, const hnsw_filter *const *filters, int32_t n_filters, const int32_t *query_filter,
                                         const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params, int32_t *out_ids,

@@ -9,6 +9,7 @@
 #include "hnsw_shard_plan.h"
 #include "hnsw_group_plan.h"
 #include "hnsw_bits_plan.h"
+#include "hnsw_keys_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -374,6 +375,20 @@ struct RangeBufs {
     DevBuf words[2], cub;                            // ... the hits as (key << 32 | row), unsorted and sorted; hipcub's temporary storage
 };
 
+// The keys an index owns (hnsw_keys.hip): key_of [n] int64 in row order, and the lookup table -- the n pairs (key, node) in
+// ascending SIGNED key order as two columns, sorted [n] int64 and node [n] int32 -- rebuilt from key_of whenever that changes.
+// Owned by the handle as the live mask is: not index tables, not counted in device_bytes (hnsw_index_keys_info reports bytes()).
+struct KeyTables {
+    Table key_of, sorted, node;
+    int64_t n = 0;
+    size_t bytes() const { return key_of.bytes + sorted.bytes + node.bytes; }
+};
+// where a keyed host call writes its rows: [nq][k] keys, missing where the search wrote its fill id
+struct KeysOut {
+    int64_t *keys;
+    int64_t missing;
+};
+
 inline int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
     return (s && *s) ? atoi(s) : dflt;
@@ -560,6 +575,10 @@ struct hnsw_index {
     // path.  Not an index table: not counted in device_bytes.
     std::unique_ptr<hnsw_filter> live;
     int64_t n_deleted = 0;
+    // Keys (hnsw_keys.hip): null on a handle never given keys, which every entry point then treats as before; else one key per
+    // node, n entries, moved with the nodes by adopt_graph.  key_scratch: the [nq][k] keys of a keyed host call before their download.
+    std::unique_ptr<hnsw_host::KeyTables> keys;
+    hnsw_host::DevBuf key_scratch;
 };
 
 namespace hnsw_dev {
@@ -634,8 +653,11 @@ int check_upper_rows(const ::hnsw_index *idx, const char *verb);
 // hnsw_build.hip: the end of hnsw_index_insert and hnsw_index_remove: nx's graph tables become idx's (see there)
 // new_id: how the nodes were renumbered (hnsw_index_remove: RemovePlan::new_id; null: ids kept, hnsw_index_insert) -- what the
 // marks of soft deletion follow
+// append_keys (hnsw_index_insert_keyed, [nx->iv.n - idx->iv.n]): the keys of the new nodes -- what the keys follow
 int adopt_graph(::hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expected_ef, int32_t expected_semantics,
-                const int32_t *new_id = nullptr);
+                const int32_t *new_id = nullptr, const int64_t *append_keys = nullptr);
+// hnsw_build.hip: hnsw_index_insert once the keyed question is settled: keys null on a handle without keys, else one per vector
+int insert_vectors(::hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p, const int64_t *keys);
 
 // hnsw_rows8.hip: if every value of tables.X is an integer in 0..255, build the byte copy (tables.X8, iv.stride8)
 int make_byte_rows(::hnsw_index *idx);
@@ -811,6 +833,12 @@ int count_filter(::hnsw_filter *f, const uint32_t *and_with);
 // new_id (host, [idx->iv.n], 0-based, -1 = removed; null: every node keeps its id and the nodes from idx->iv.n on are new and live).
 // out stays null when idx has no marked node.
 int renumbered_live_filter(const ::hnsw_index *idx, const int32_t *new_id, int64_t n_new, std::unique_ptr<::hnsw_filter> &out);
+// hnsw_keys.hip: the key tables an index of n_new nodes gets when nx replaces idx's graph (adopt_graph, before the swap), lookup
+// table included: new_id as above (keys_renumber_kernel; null: the old keys kept in place and append_keys, n_new - idx->iv.n of
+// them, behind).  out stays null when idx has no keys and none are appended.
+int renumbered_keys(const ::hnsw_index *idx, const int32_t *new_id, int64_t n_new, const int64_t *append_keys, std::unique_ptr<KeyTables> &out);
+// hnsw_keys.hip: keys_translate_kernel on st: d_out[i] = the key of node d_ids[i] - id_base, or missing where that is no node (m entries)
+int keys_translate(const ::hnsw_index *idx, const int32_t *d_ids, int64_t m, int64_t missing, int64_t *d_out, hipStream_t st);
 // hnsw_filter.hip: the escalation both the filtered and the range search run -- e = ef, 2 ef, ... 1024: the batch is walked with
 // (ef = k = e, raw_walk), the caller's select kernel serves what it can and appends the other queries to the short list
 // (ladder_settle) and only those, gathered into one compact batch, are walked again.  Everything is queued on st and waited for
@@ -859,6 +887,13 @@ private:
     int cur = 0;                         // which list buffer `map` is
     std::vector<int32_t> shorts;
 };
+// hnsw_capi.hip: hnsw_search_batch; ko (optional): the rows go to ko->keys as keys and out_ids may be null (hnsw_search_batch_keyed);
+// out_stage (optional): as the filtered call writes it while nodes are marked, zero otherwise
+int knn_host_call(::hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params, int32_t *out_ids,
+                  float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko);
+// hnsw_filter.hip: hnsw_search_batch_filtered; ko: likewise
+int filtered_host_call(::hnsw_index *idx, const ::hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
+                       int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko);
 // hnsw_capi.hip: the value that puts option `name` of hnsw_index_set_option back where it is now (HNSW_ERR_BAD_ARG: no such option)
 int get_option(const ::hnsw_index *idx, const char *name, int64_t *value);
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
@@ -884,6 +919,9 @@ struct HostCall {
     int32_t *ids = nullptr;
     float *dist = nullptr;
     uint32_t *nd = nullptr, *nh = nullptr;
+    // a keyed call (set before begin, out_ids then null): finish translates the device-resident ids into the handle's key_scratch
+    // and downloads that into ko->keys; such a call never takes the small block
+    const KeysOut *ko = nullptr;
     // *q_in_place: the device reads the queries from host memory (the knn call then hands knn_search scratch.q to stage them in)
     int begin(::hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int k, int32_t *out_ids, float *out_dist,
               uint32_t *out_nd, uint32_t *out_nh, bool allow_small, bool *q_in_place = nullptr);

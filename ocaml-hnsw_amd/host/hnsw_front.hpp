@@ -10,6 +10,8 @@
 //                                                                                           hnsw_brute_force_batch_grouped)
 //   Hnsw::RangeResult, Hnsw::Ohnsw::range_search / brute_force_range                       (hnsw_range_*; with a Filter: the _filtered forms)
 //   Hnsw::Ohnsw::mark_deleted / unmark_deleted / deleted_count / deleted_mask / compact    (hnsw_index_mark_deleted ... hnsw_index_compact)
+//   Hnsw::Ohnsw::set_keys / clear_keys / keys_info / keys_of / find_keys / knn_keyed / insert_keyed / remove_keys /
+//   mark_deleted_keys / unmark_deleted_keys, Hnsw::Filter::by_keys                         (hnsw_index_set_keys ... hnsw_filter_create_by_keys)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
@@ -117,6 +119,15 @@ public:
         out.reserve(raw.size());
         for (hnsw_filter *f : raw) out.push_back(Filter(f, (int64_t)labels.size()));
         return out;
+    }
+    // exactly the nodes with these keys of an index that owns keys (hnsw_filter_create_by_keys): repeats are fine, an absent key is
+    // refused; ANDed with the live mask as every filter is
+    static Filter by_keys(const Hgraph &g, const std::vector<int64_t> &keys) {
+        hnsw_index_info inf{};
+        check(hnsw_index_get_info(g.handle(), &inf));
+        hnsw_filter *f = nullptr;
+        check(hnsw_filter_create_by_keys(g.handle(), keys.data(), (int64_t)keys.size(), &f));
+        return Filter(f, inf.n);
     }
     // the mask as the device holds it (hnsw_filter_bits): ceil(n / 32) words, bit (v & 31) of word (v >> 5) = node v
     std::vector<uint32_t> bits() const {
@@ -529,6 +540,77 @@ inline Grouped brute_force_grouped(const Hgraph &g, const Labels &l, int k, cons
     check(hnsw_brute_force_batch_grouped(g.handle(), l.handle(), f ? f->handle() : nullptr, batch.data, batch.dim2, batch.dim1, k, fill,
                                          out.ids.data(), out.dist.data(), out.labels.data()));
     return out;
+}
+
+// ---- keys the index owns: one caller-chosen int64 per stored node, pairwise distinct, kept on the device in row order and moved with
+// the nodes through insert_keyed, remove and compact (hnsw_index_set_keys ...; the definitions: include/hnsw_mi355x.h) ----
+inline void set_keys(Hgraph &g, const std::vector<int64_t> &keys) { check(hnsw_index_set_keys(g.handle(), keys.data(), (int64_t)keys.size())); }
+inline void clear_keys(Hgraph &g) { check(hnsw_index_clear_keys(g.handle())); }
+// (has keys?, their bytes on the device: not part of hnsw_index_info.device_bytes)
+inline std::pair<bool, int64_t> keys_info(const Hgraph &g) {
+    int32_t has = 0; int64_t bytes = 0;
+    check(hnsw_index_keys_info(g.handle(), &has, &bytes));
+    return {has != 0, bytes};
+}
+// the keys of the nodes `ids` (id_base-based; `missing` where an id names no node, the searches' fill id -1 included) ...
+inline std::vector<int64_t> keys_of(const Hgraph &g, const std::vector<int32_t> &ids, int64_t missing = -1) {
+    std::vector<int64_t> out(ids.size());
+    if (!ids.empty()) check(hnsw_index_keys_of(g.handle(), ids.data(), (int64_t)ids.size(), missing, out.data()));
+    return out;
+}
+// ... and of all n nodes in row order
+inline std::vector<int64_t> keys_of(const Hgraph &g) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    std::vector<int64_t> out((size_t)inf.n + 1);
+    check(hnsw_index_keys_of(g.handle(), nullptr, inf.n, 0, out.data()));
+    out.pop_back();
+    return out;
+}
+// the id_base-based ids of the nodes with these keys, id_base - 1 where no node has the key
+inline std::vector<int64_t> find_keys(const Hgraph &g, const std::vector<int64_t> &keys) {
+    std::vector<int64_t> out(keys.size());
+    if (!keys.empty()) check(hnsw_index_find_keys(g.handle(), keys.data(), (int64_t)keys.size(), out.data()));
+    return out;
+}
+// knn_batch_bigarray answered in keys (hnsw_search_batch_keyed): keys / distances [nq][k], `missing` / NaN where fewer than k were
+// found; f (optional): the rows of knn_filtered under it.  stage as knn_filtered's, zero for the plain path.
+struct Keyed {
+    std::vector<int64_t> keys; std::vector<float> dist; std::vector<uint32_t> stage;
+};
+inline Keyed knn_keyed(const Hgraph &g, int k, const Mat &batch, int ef = 0, const Filter *f = nullptr, int64_t missing = -1,
+                       int sem = HNSW_SEM_OHNSW, int fill = HNSW_FILL_OHNSW) {
+    const size_t nq = (size_t)batch.dim2, cells = nq * (size_t)(k > 0 ? k : 0);
+    Keyed out{std::vector<int64_t>(cells, missing), std::vector<float>(cells, 0.f), std::vector<uint32_t>(nq, 0u)};
+    hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
+    check(hnsw_search_batch_keyed(g.handle(), f ? f->handle() : nullptr, batch.data, batch.dim2, batch.dim1, &p, missing, out.keys.data(),
+                                  out.dist.data(), nullptr, nullptr, out.stage.data()));
+    return out;
+}
+// insert() into an index that owns keys (hnsw_index_insert_keyed): keys[i] names vector i of `batch`; a stored or repeated key
+// refuses the call before anything is built.  An empty index without keys starts its keys here.  Returns the first new id.
+inline int64_t insert_keyed(Hgraph &g, const Mat &batch, const std::vector<int64_t> &keys, int num_connections, int num_nodes_search_construction,
+                            uint64_t seed = 0, int max_batch = 0, int expected_ef = 0) {
+    if ((int64_t)keys.size() != batch.dim2) throw std::invalid_argument("insert_keyed: one key per vector");
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    hnsw_build_params p{num_connections, num_nodes_search_construction, inf.metric, inf.id_base, seed, max_batch, 0, expected_ef, HNSW_SEM_OHNSW};
+    check(hnsw_index_insert_keyed(g.handle(), batch.data, batch.dim2, batch.dim1, keys.data(), &p));
+    return inf.n + inf.id_base;
+}
+// remove() / mark_deleted() / unmark_deleted() of the nodes with these keys: an absent key refuses the call, nothing changed
+inline std::vector<int32_t> remove_keys(Hgraph &g, const std::vector<int64_t> &keys) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    std::vector<int32_t> new_id((size_t)inf.n);
+    check(hnsw_index_remove_keys(g.handle(), keys.data(), (int64_t)keys.size(), new_id.data()));
+    return new_id;
+}
+inline void mark_deleted_keys(Hgraph &g, const std::vector<int64_t> &keys) { check(hnsw_index_mark_deleted_keys(g.handle(), keys.data(), (int64_t)keys.size())); }
+inline void unmark_deleted_keys(Hgraph &g, const std::vector<int64_t> &keys) { check(hnsw_index_unmark_deleted_keys(g.handle(), keys.data(), (int64_t)keys.size())); }
+// ... and for ids already on the device, queued on `stream` (hnsw_index_keys_of_device)
+inline void keys_of_device(Hgraph &g, const int32_t *d_ids, int64_t m, int64_t missing, int64_t *d_out, void *stream = nullptr) {
+    check(hnsw_index_keys_of_device(g.handle(), d_ids, m, missing, d_out, stream));
 }
 
 // The exact re-rank (hnsw_rerank_batch): for each query the k nearest of ITS candidates cand[q][0 .. cand_stride) (entries below

@@ -261,6 +261,37 @@ let hnsw_index_mark_deleted =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_mark_deleted" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
 let hnsw_index_unmark_deleted =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_unmark_deleted" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
+(* keys the index owns (see the C header): one caller-chosen int64 per stored node, moved with the nodes *)
+let hnsw_index_set_keys =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_set_keys" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
+let hnsw_index_clear_keys = foreign ~from:lib "hnsw_index_clear_keys" (index @-> returning int32_t)
+let hnsw_index_keys_info = foreign ~from:lib "hnsw_index_keys_info" (index @-> ptr int32_t @-> ptr int64_t @-> returning int32_t)
+let hnsw_index_keys_of =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_keys_of"
+    (index @-> ptr int32_t @-> int64_t @-> int64_t @-> ptr int64_t @-> returning int32_t)
+let hnsw_index_keys_of_device =
+  foreign ~from:lib "hnsw_index_keys_of_device"
+    (index @-> ptr int32_t @-> int64_t @-> int64_t @-> ptr int64_t @-> ptr void @-> returning int32_t)
+let hnsw_index_find_keys =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_find_keys"
+    (index @-> ptr int64_t @-> int64_t @-> ptr int64_t @-> returning int32_t)
+let hnsw_search_batch_keyed =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_keyed"
+    (index @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> int64_t @-> ptr int64_t
+     @-> ptr float @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+let hnsw_index_insert_keyed =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_insert_keyed"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int64_t @-> ptr build_params @-> returning int32_t)
+let hnsw_index_remove_keys =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_remove_keys"
+    (index @-> ptr int64_t @-> int64_t @-> ptr int32_t @-> returning int32_t)
+let hnsw_index_mark_deleted_keys =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_mark_deleted_keys" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
+let hnsw_index_unmark_deleted_keys =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_unmark_deleted_keys" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
+let hnsw_filter_create_by_keys =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_filter_create_by_keys"
+    (index @-> ptr int64_t @-> int64_t @-> ptr filter_handle @-> returning int32_t)
 let hnsw_index_deleted_count = foreign ~from:lib "hnsw_index_deleted_count" (index @-> ptr int64_t @-> returning int32_t)
 let hnsw_index_deleted_bits = foreign ~from:lib "hnsw_index_deleted_bits" (index @-> ptr uint32_t @-> returning int32_t)
 let hnsw_index_compact =
@@ -1206,6 +1237,98 @@ let compact t : int array =
   let c_new = CArray.make int32_t (max n_old 1) in
   check (hnsw_index_compact t.handle (CArray.start c_new));
   Array.init n_old (fun v -> Int32.to_int (CArray.get c_new v))
+
+(* Keys the index owns (hnsw_index_set_keys ...): one caller-chosen key per stored node -- an OCaml int, every value legal,
+   pairwise distinct -- kept on the device in row order and moved with the nodes through [insert_batch_keyed], [remove_batch] and
+   [compact]; row numbers change with every removal, keys do not.  [set_keys t keys]: one key per node (a duplicate is refused
+   naming the smallest duplicated key, the index keeps the keys it had).  [keys_of t ids]: the keys of nodes (id_base-based;
+   [missing] where an id names no node, the searches' fill id -1 included); [keys_all t]: all of them in row order.
+   [find_keys t keys]: the ids of the nodes with these keys, id_base - 1 where there is none. *)
+let c_keys (keys : int array) =
+  let c = CArray.make int64_t (max 1 (Array.length keys)) in
+  Array.iteri (fun i v -> CArray.set c i (Int64.of_int v)) keys;
+  c
+let set_keys t (keys : int array) = check (hnsw_index_set_keys t.handle (CArray.start (c_keys keys)) (Int64.of_int (Array.length keys)))
+let clear_keys t = check (hnsw_index_clear_keys t.handle)
+let keys_info t : bool * int =
+  let has = allocate int32_t 0l and bytes = allocate int64_t 0L in
+  check (hnsw_index_keys_info t.handle has bytes);
+  (!@has <> 0l, Int64.to_int !@bytes)
+let keys_of ?(missing = -1) t (ids : int array) : int array =
+  let m = Array.length ids in
+  let c_ids = CArray.make int32_t (max 1 m) and out = CArray.make int64_t (max 1 m) in
+  Array.iteri (fun i v -> CArray.set c_ids i (Int32.of_int v)) ids;
+  check (hnsw_index_keys_of t.handle (CArray.start c_ids) (Int64.of_int m) (Int64.of_int missing) (CArray.start out));
+  Array.init m (fun i -> Int64.to_int (CArray.get out i))
+let keys_all t : int array =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let n = Int64.to_int (getf inf ii_n) in
+  let out = CArray.make int64_t (max 1 n) in
+  check (hnsw_index_keys_of t.handle (from_voidp int32_t null) (Int64.of_int n) 0L (CArray.start out));
+  Array.init n (fun i -> Int64.to_int (CArray.get out i))
+let find_keys t (keys : int array) : int array =
+  let m = Array.length keys in
+  let out = CArray.make int64_t (max 1 m) in
+  check (hnsw_index_find_keys t.handle (CArray.start (c_keys keys)) (Int64.of_int m) (CArray.start out));
+  Array.init m (fun i -> Int64.to_int (CArray.get out i))
+
+(* [knn_batch_keyed t batch ~ef ~k]: [knn_batch] answered in keys (hnsw_search_batch_keyed) -> (keys, distances, stages), [nq][k]
+   ([missing] / nan where fewer than k were found).  ?filter: the rows of [knn_batch_filtered] under it; stages as there, 0 for the
+   plain path.  One translate launch over the ids on the device, no second pass on the host. *)
+let knn_batch_keyed ?(semantics = 0) ?(fill = 0) ?filter ?(missing = -1) (t : t) (batch : Lacaml.S.mat) ~ef ~k :
+  int array array * float array array * int array =
+  let nq = A2.dim2 batch in
+  let keys = CArray.make int64_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let stage = CArray.make uint32_t (max 1 nq) in
+  let p = make search_params in
+  setf p p_ef (Int32.of_int ef); setf p p_k (Int32.of_int k); setf p p_fill (Int32.of_int fill);
+  setf p p_semantics (Int32.of_int semantics);
+  let fh = match filter with Some (f : filter) -> f.f_handle | None -> null in
+  check (hnsw_search_batch_keyed t.handle fh (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) (addr p)
+           (Int64.of_int missing) (CArray.start keys) (CArray.start dist) (from_voidp uint32_t null) (from_voidp uint32_t null)
+           (CArray.start stage));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int64.to_int (CArray.get keys (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
+   Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))
+
+(* [insert_batch_keyed t batch keys]: [insert_batch] into an index that owns keys (hnsw_index_insert_keyed), keys.(i) naming
+   column i of [batch].  A stored or repeated key refuses the call before anything is built; an empty index without keys starts
+   its keys here.  Plain [insert_batch] is refused on an index with keys.  Returns the first new id. *)
+let insert_batch_keyed t (batch : Lacaml.S.mat) (keys : int array) ~num_connections ~num_nodes_search_construction ?(seed = 0)
+    ?(max_batch = 0) ?(batch_div = 0) ?(expected_ef = 0) ?(expected_semantics = 0) () : int =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  if A2.dim1 batch <> t.dim then invalid_arg "insert_batch_keyed: vectors of another dimension";
+  if Array.length keys <> A2.dim2 batch then invalid_arg "insert_batch_keyed: one key per vector";
+  let b = make build_params in
+  setf b b_num_connections (Int32.of_int num_connections); setf b b_efc (Int32.of_int num_nodes_search_construction);
+  setf b b_metric (getf inf ii_metric); setf b b_id_base (getf inf ii_id_base);
+  setf b b_seed (Unsigned.UInt64.of_int seed); setf b b_max_batch (Int32.of_int max_batch);
+  setf b b_batch_div (Int32.of_int batch_div);
+  setf b b_expected_ef (Int32.of_int expected_ef); setf b b_expected_semantics (Int32.of_int expected_semantics);
+  check (hnsw_index_insert_keyed t.handle (bigarray_start array2 batch) (Int64.of_int (A2.dim2 batch)) (Int64.of_int t.dim)
+           (CArray.start (c_keys keys)) (addr b));
+  Int64.to_int (getf inf ii_n) + Int32.to_int (getf inf ii_id_base)
+
+(* [remove_keys] / [mark_deleted_keys] / [unmark_deleted_keys]: [remove_batch] / [mark_deleted] / [unmark_deleted] of the nodes
+   with these keys; an absent key refuses the call and nothing is changed.  [filter_by_keys]: an ordinary [filter] that allows
+   exactly those nodes. *)
+let remove_keys t (keys : int array) : int array =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let n_old = Int64.to_int (getf inf ii_n) in
+  let c_new = CArray.make int32_t (max n_old 1) in
+  check (hnsw_index_remove_keys t.handle (CArray.start (c_keys keys)) (Int64.of_int (Array.length keys)) (CArray.start c_new));
+  Array.init n_old (fun v -> Int32.to_int (CArray.get c_new v))
+let mark_deleted_keys t (keys : int array) = change_marks hnsw_index_mark_deleted_keys t keys
+let unmark_deleted_keys t (keys : int array) = change_marks hnsw_index_unmark_deleted_keys t keys
+let filter_by_keys (t : t) (keys : int array) : filter =
+  let out = allocate filter_handle null in
+  check (hnsw_filter_create_by_keys t.handle (CArray.start (c_keys keys)) (Int64.of_int (Array.length keys)) out);
+  let f = { f_handle = !@out; f_index = t } in
+  Gc.finalise (fun f -> ignore (hnsw_filter_destroy f.f_handle)) f;
+  f
 
 (* flattened-index file (the reference has no persistence: lib/hnsw.ml:348, lib/ohnsw.ml:312 derive sexp with opaque values) *)
 let save (t : t) (path : string) = check (hnsw_index_save t.handle path)
