@@ -1495,6 +1495,72 @@ int32_t hnsw_index_mark_deleted_keys(hnsw_index *idx, const int64_t *keys, int64
 int32_t hnsw_index_unmark_deleted_keys(hnsw_index *idx, const int64_t *keys, int64_t m);
 int32_t hnsw_filter_create_by_keys(hnsw_index *idx, const int64_t *keys, int64_t m, hnsw_filter **out);
 
+/* ---- search by stored item: neighbours of nodes named by id or by key, the k-NN graph of the whole index ----
+ * "What is near THIS stored item": the queries of a call are rows the index already holds, so only their ids cross the link -- the
+ * rows are gathered on the device out of the float32 table, which is resident whatever row_format is.
+ *
+ * THE DEFINITION is one equivalence.  Let Q = hnsw_index_get_rows(ids): the stored float32 rows (for HNSW_METRIC_COSINE that is N(X)).
+ *   exclude_self = 0: the call answers bit for bit what hnsw_search_batch(idx, Q, params) answers on the same handle in the same
+ *     state: ids, distances and both counters.
+ *   exclude_self = 1: let P = {ef' = max(ef, k + 1), k' = k + 1, fill, semantics} and R = hnsw_search_batch(idx, Q, P).  For query q
+ *     let p be the smallest j in [0, k] with R.ids[q][j] == ids[q], or k if there is none.  The output row is R's row with
+ *     position p deleted: k entries.  If self is absent from the first k + 1, the row is the first k of them.  Trailing fill
+ *     entries stay fill: removal shifts them left unchanged.  The counters are R's.
+ * Everything the host call does is therefore inherited, not restated: the row formats (byte, split, half, sq8, sq8_dim, bits,
+ * bit_query_bits) with their query transforms and re-rank; option "refine"; COSINE's normalisation of the call's queries (so
+ * N(N(x)), as for any caller); the live mask of a marked handle with the filtered ladder and the exact stage -- a node marked
+ * deleted is a legal QUERY, its row is there, and it can never be in its own row --; the ordering pre-pass, the tie-overflow repair
+ * and option "visited_blocks".  A query's row depends on its own id only, not on the batch it is in.
+ *
+ * hnsw_index_get_rows_device(idx, d_ids, m, d_out, out_stride, stream): the bits of hnsw_index_get_rows over device arrays, queued on
+ *   `stream`: d_ids [m] int32, id_base-based; row j of d_out (out_stride floats apart, d written) is the row of node d_ids[j].  An id
+ *   outside the index gives a row of d zeros: the device cannot refuse.  m == 0 is a no-op; NULL arrays with m > 0, or
+ *   out_stride < d, are HNSW_ERR_BAD_ARG.  It uses no scratch of the handle.  With it and hnsw_search_batch_device a
+ *   device-resident caller composes its own search by id.
+ * hnsw_search_batch_by_id(idx, ids, nq, params, exclude_self, out_ids, out_dist, out_ndist, out_nhops): the definition above.  ids
+ *   [nq] are int32 and id_base-based, so the output of a search can be fed straight back; repeated ids are fine.  An id out of range
+ *   is HNSW_ERR_BAD_ARG naming the first by position, and nothing is written.  exclude_self other than 0 / 1 is HNSW_ERR_BAD_ARG;
+ *   exclude_self = 1 with HNSW_SEM_FUNCTOR_NEAREST_K is HNSW_ERR_BAD_ARG (the k farthest of a W one wider have no meaning);
+ *   k + 1 > 1024 is HNSW_ERR_UNSUPPORTED.  Every other check and error is hnsw_search_batch's, on P.  nq == 0 is a no-op.
+ *   out_ids / out_dist [nq][k]; matrices of hnsw_host_alloc / hnsw_host_register are written in place, others downloaded;
+ *   out_ndist / out_nhops are optional.  Complete on return.
+ * hnsw_search_batch_by_key(idx, keys, nq, params, exclude_self, missing_key, out_keys, ...): by_id(find_keys(keys)) with the rows
+ *   returned as keys (hnsw_index_keys_of's rule with missing_key, applied in the same pass that removes self).  An absent key is
+ *   HNSW_ERR_BAD_ARG naming the first by position, and nothing is written: hnsw_index_remove_keys' rule.  A handle without keys is
+ *   HNSW_ERR_BAD_ARG.  Distances and counters are bit for bit those of the by-id call.
+ * hnsw_brute_force_batch_by_id(idx, ids, nq, k, fill, exclude_self, out_ids, out_dist): the same two definitions over
+ *   hnsw_brute_force_batch: k + 1 <= 1024, marks honoured as there.  Under L2 it is the exact answer without self: the nodes ahead
+ *   of self under (distance, id) are its lower-numbered duplicates; if more than k of them exist, self is past position k and the
+ *   first k are right.
+ * hnsw_knn_graph(idx, params, exact, out_ids, out_dist): the k-NN graph of the whole index.  Row v of out_ids / out_dist ([n][k];
+ *   out_dist may be NULL) is the row of hnsw_search_batch_by_id for ids[v] = id_base + v with exclude_self = 1 -- with exact = 1
+ *   the row of hnsw_brute_force_batch_by_id instead --, bit for bit that one call.  It is computed inside the library in chunks of
+ *   option "graph_chunk_rows" nodes (hnsw_index_set_option; default 65536, values < 1 refused), so the handle's scratch stays a
+ *   chunk's whatever n is; the option changes no result.  n == 0 is HNSW_OK.
+ * A replica of an hnsw_multi (hnsw_multi_replica) is accepted read-only, as the scan accepts it.  After hnsw_index_insert,
+ * hnsw_index_remove or hnsw_index_compact the calls see the table as it then is.  One such call in flight per handle: they share
+ * the host calls' scratch.
+ *
+ * NOT BUILT: a device-pointer form of the search by id (compose hnsw_index_get_rows_device and hnsw_search_batch_device);
+ * hnsw_sharded_* forms; range search by id; starting the layer-0 walk at the node itself instead of descending (the knn kernels
+ * take a pre-computed entry already, but the ladder, the repair path and the re-rank would all have to carry it along: a follow-up
+ * with a definition of its own, through hnsw_search_layer_batch); overlap of one chunk's download with the next chunk's search in
+ * hnsw_knn_graph.
+ * Rates (tools/by_id_rate.py, profiles/by_id.txt; one run), MI355X, 1 M x 128 byte rows, ef 128, k 10, 10 k stored nodes as the
+ * queries, the calls alternating on one handle: hnsw_search_batch_by_id 0.778 ms per batch (exclude_self 1: 0.781) against 0.849 ms
+ * for hnsw_search_batch over the same rows from a page-locked matrix and 1.551 ms for hnsw_index_get_rows + hnsw_search_batch with
+ * k + 1 + the strip on the host; hnsw_knn_graph of all 1 M nodes 56.4 ms. */
+int32_t hnsw_index_get_rows_device(hnsw_index *idx, const int32_t *d_ids, int64_t m, float *d_out, int64_t out_stride, void *stream);
+int32_t hnsw_search_batch_by_id(hnsw_index *idx, const int32_t *ids, int64_t nq, const hnsw_search_params *params,
+                                int32_t exclude_self, int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops);
+int32_t hnsw_search_batch_by_key(hnsw_index *idx, const int64_t *keys, int64_t nq, const hnsw_search_params *params,
+                                 int32_t exclude_self, int64_t missing_key, int64_t *out_keys, float *out_dist,
+                                 uint32_t *out_ndist, uint32_t *out_nhops);
+int32_t hnsw_brute_force_batch_by_id(hnsw_index *idx, const int32_t *ids, int64_t nq, int32_t k, int32_t fill, int32_t exclude_self,
+                                     int32_t *out_ids, float *out_dist);
+int32_t hnsw_knn_graph(hnsw_index *idx, const hnsw_search_params *params, int32_t exact, int32_t *out_ids /* [n][k] */,
+                       float *out_dist /* [n][k] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,11 @@ _ABI = {
     "hnsw_index_mark_deleted_keys": [_vp, _vp, _i64],
     "hnsw_index_unmark_deleted_keys": [_vp, _vp, _i64],
     "hnsw_filter_create_by_keys": [_vp, _vp, _i64, _vp],
+    "hnsw_index_get_rows_device": [_vp, _vp, _i64, _vp, _i64, _vp],
+    "hnsw_search_batch_by_id": [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
+    "hnsw_search_batch_by_key": [_vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
+    "hnsw_brute_force_batch_by_id": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "hnsw_knn_graph": [_vp, _vp, _i32, _vp, _vp],
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -421,6 +426,17 @@ class Hgraph:
         if m:
             _check(load().hnsw_index_get_rows(self.handle, p, m, _ptr(out), self.d))
         return out
+
+    def knn_graph(self, k, ef=None, exact=False, sem=SEM_OHNSW, fill=FILL_OHNSW, distances=True):
+        """hnsw_knn_graph: the k-NN graph of the whole index -> (ids [n][k], distances [n][k]), distances=False: ids alone.  Row v is
+        the row of Ohnsw.knn_batch_by_id for node id_base + v without the node itself (exact=True: of Ohnsw.brute_force_by_id),
+        computed on the device in chunks of option "graph_chunk_rows" nodes; ef None: ef == k."""
+        n = self.info().n
+        ids = _np.empty((n, max(int(k), 0)), _np.int32)
+        dist = _np.empty((n, max(int(k), 0)), _np.float32) if distances else None
+        p = _SearchParams(int(k) if ef is None else int(ef), int(k), fill, sem)
+        _check(load().hnsw_knn_graph(self.handle, _C.byref(p), 1 if exact else 0, _ptr(ids), _ptr(dist)))
+        return (ids, dist) if distances else ids
 
     def locality_codes(self):
         """hnsw_index_locality_codes: the permutation of 0 .. n-1 that keys the visited set's bitmap blocks (introspection)."""
@@ -1071,6 +1087,42 @@ def _range_search(hgraph, batch, radius, ef, sem=0, counters=False, keep=False, 
     return RangeResult(r)._take(counters, keep)
 
 
+def _ids32(ids):
+    """the ids of a call by stored item as the library reads them: contiguous int32, id_base-based (a search's output fits as it is)"""
+    a = _np.asarray(ids)
+    if a.size and a.dtype.kind not in "iu":
+        raise InvalidArgument("ids must be integers")
+    if a.size and (int(a.max()) > 2 ** 31 - 1 or int(a.min()) < -2 ** 31):
+        raise InvalidArgument("ids must fit a signed 32-bit integer")
+    return _np.ascontiguousarray(a, dtype=_np.int32).reshape(-1)
+
+
+def _search_by_id(hgraph, ids, ef, k, fill, exclude_self=True, counters=False, sem=0, out=None):
+    """hnsw_search_batch_by_id: the stored rows `ids` as the queries -> (ids, dist), with counters (ids, dist, ndist, nhops)"""
+    q = _ids32(ids)
+    nq = q.size
+    oi, od = _out_pair(nq, k, out)
+    nd = _np.zeros(nq, _np.uint32) if counters else None
+    nh = _np.zeros(nq, _np.uint32) if counters else None
+    p = _SearchParams(ef, k, fill, sem)
+    _check(load().hnsw_search_batch_by_id(hgraph.handle, _ptr(q), nq, _C.byref(p), int(exclude_self), _ptr(oi), _ptr(od), _ptr(nd), _ptr(nh)))
+    return (oi, od, nd, nh) if counters else (oi, od)
+
+
+def _search_by_key(hgraph, keys, ef, k, fill, exclude_self=True, counters=False, sem=0, missing=MISSING_KEY):
+    """hnsw_search_batch_by_key: the stored rows under `keys` as the queries -> (keys, dist), with counters (keys, dist, ndist, nhops)"""
+    q = _keys(keys)
+    nq = q.size
+    ok = _np.empty((nq, max(k, 0)), _np.int64)
+    od = _np.empty((nq, max(k, 0)), _np.float32)
+    nd = _np.zeros(nq, _np.uint32) if counters else None
+    nh = _np.zeros(nq, _np.uint32) if counters else None
+    p = _SearchParams(ef, k, fill, sem)
+    _check(load().hnsw_search_batch_by_key(hgraph.handle, _ptr(q), nq, _C.byref(p), int(exclude_self), int(missing), _ptr(ok), _ptr(od),
+                                           _ptr(nd), _ptr(nh)))
+    return (ok, od, nd, nh) if counters else (ok, od)
+
+
 def _search(hgraph, batch, ef, k, fill, counters=False, sem=0, out=None):
     Q, qs, nq = _batch(hgraph.d, batch)
     ids, dist = _out_pair(nq, k, out)
@@ -1121,6 +1173,13 @@ def search_batch_device(hgraph, d_queries, nq, q_stride, ef, k, d_ids, d_dist, d
 def brute_force_device(hgraph, d_queries, nq, q_stride, k, d_ids, d_dist, fill=FILL_OHNSW, stream=0):
     """hnsw_brute_force_batch_device: the exact scan on device pointers (ints), asynchronous on HIP stream `stream`."""
     _check(load().hnsw_brute_force_batch_device(hgraph.handle, d_queries, nq, q_stride, k, fill, d_ids, d_dist, stream or None))
+
+
+def rows_device(hgraph, d_ids, m, d_out, out_stride, stream=0):
+    """hnsw_index_get_rows_device: the stored float32 rows of the nodes d_ids (device int32, id_base-based) into the device matrix
+    d_out, rows out_stride floats apart (pointers as ints), asynchronous on HIP stream `stream`; an id outside the index gives a
+    row of zeros.  With search_batch_device a device-resident caller composes its own search by id."""
+    _check(load().hnsw_index_get_rows_device(hgraph.handle, d_ids or None, m, d_out or None, out_stride, stream or None))
 
 
 def rerank_device(hgraph, d_queries, nq, q_stride, d_cand, cand_stride, k, d_ids, d_dist, fill=FILL_OHNSW, stream=0):
@@ -1221,6 +1280,30 @@ class Ohnsw:
         counters (keys, distances, ndist, nhops, stage): keys [nq][k] int64, `missing` where fewer than k were found.  filter (a
         Filter, or what Hgraph.filter takes): the rows of knn_batch_filtered instead.  Distances and counters are those calls'."""
         return _search_keyed(hgraph, batch, k if ef is None else ef, k, FILL_OHNSW, counters, flt=filter, missing=missing)
+
+    @staticmethod
+    def knn_batch_by_id(hgraph, k, ids, ef=None, exclude_self=True, counters=False, out=None):
+        """knn_batch_bigarray with the stored vectors of the nodes `ids` as the queries (hnsw_search_batch_by_id) -> (ids, distances),
+        with counters (ids, distances, ndist, nhops).  Only the ids cross the link: the rows are gathered on the device.
+        exclude_self=False: exactly knn_batch_bigarray(hgraph, k, hgraph.rows(ids), ef).  exclude_self=True ("more like this"): the
+        search runs k + 1 wide with ef' = max(ef, k + 1) and each row has the node's own id removed -- the first k entries if the
+        node is not among them.  ids: int32, id_base-based: a search's output can be fed straight back."""
+        return _search_by_id(hgraph, ids, k if ef is None else ef, k, FILL_OHNSW, exclude_self, counters, out=out)
+
+    @staticmethod
+    def knn_batch_by_key(hgraph, k, keys, ef=None, exclude_self=True, counters=False, missing=MISSING_KEY):
+        """knn_batch_by_id for the nodes stored under `keys`, answered in keys (hnsw_search_batch_by_key) -> (keys, distances), with
+        counters (keys, distances, ndist, nhops).  An absent key is refused.  Distances and counters are the by-id call's."""
+        return _search_by_key(hgraph, keys, k if ef is None else ef, k, FILL_OHNSW, exclude_self, counters, missing=missing)
+
+    @staticmethod
+    def brute_force_by_id(hgraph, k, ids, exclude_self=True, fill=FILL_OHNSW):
+        """brute_force_knn with the stored vectors of the nodes `ids` as the queries (hnsw_brute_force_batch_by_id) -> (ids,
+        distances); exclude_self as in knn_batch_by_id.  Needs no graph."""
+        q = _ids32(ids)
+        oi, od = _out_pair(q.size, int(k), None)
+        _check(load().hnsw_brute_force_batch_by_id(hgraph.handle, _ptr(q), q.size, int(k), fill, int(exclude_self), _ptr(oi), _ptr(od)))
+        return oi, od
 
     @staticmethod
     def brute_force_grouped(hgraph, k, batch, labels, filter=None, fill=FILL_OHNSW):
@@ -1447,6 +1530,18 @@ class Ba:
         """knn_batch answered in the index's keys (see Ohnsw.knn_batch_keyed; the functor accept rule, +inf / `missing` where fewer
         than k were found) -> (keys, distances), with counters (..., ndist, nhops, stage)."""
         return _search_keyed(hgraph, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR, flt=filter, missing=missing)
+
+    @staticmethod
+    def knn_batch_by_id(hgraph, ids, num_neighbours_search, num_neighbours, exclude_self=True, counters=False):
+        """knn_batch with the stored vectors of the nodes `ids` as the queries (see Ohnsw.knn_batch_by_id; the functor accept rule,
+        1-based ids in a 1-based index, +inf / -1 where fewer than k were found) -> (ids, distances), with counters (..., ndist, nhops)."""
+        return _search_by_id(hgraph, ids, num_neighbours_search, num_neighbours, FILL_BA, exclude_self, counters, sem=SEM_FUNCTOR)
+
+    @staticmethod
+    def knn_batch_by_key(hgraph, keys, num_neighbours_search, num_neighbours, exclude_self=True, counters=False, missing=MISSING_KEY):
+        """knn_batch_by_id for the nodes stored under `keys`, answered in keys (see Ohnsw.knn_batch_by_key; the functor accept rule)
+        -> (keys, distances), with counters (..., ndist, nhops)."""
+        return _search_by_key(hgraph, keys, num_neighbours_search, num_neighbours, FILL_BA, exclude_self, counters, sem=SEM_FUNCTOR, missing=missing)
 
     @staticmethod
     def range_search(hgraph, batch, num_neighbours_search, radius, counters=False, filter=None):

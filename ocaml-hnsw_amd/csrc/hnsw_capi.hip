@@ -701,8 +701,21 @@ int HostInput::resolve(const void *p, size_t n, DevBuf &stage) {
     dev = stage.p; from = p;
     return rc;
 }
+int HostInput::resolve_rows(hnsw_index *idx, const int32_t *ids, int64_t nq, DevBuf &stage) {
+    bytes = (size_t)nq * padded_stride(idx->iv.d) * sizeof(float); from = nullptr;
+    int rc;
+    if ((rc = stage.ensure(bytes)) || (rc = idx->by_id_scratch.self.ensure((size_t)nq * 4))) return rc;
+    dev = stage.p;
+    rows_of = idx; row_ids = ids; d_row_ids = (int32_t *)idx->by_id_scratch.self.p; n_rows = nq;
+    return HNSW_OK;
+}
 int HostInput::upload(hipStream_t st) const {
     if (from) HIP_TRY(hipMemcpyAsync(const_cast<void *>(dev), from, bytes, hipMemcpyHostToDevice, st));
+    if (rows_of) {      // the ids up, then whole padded rows of the float32 table: what a staged copy of the same vectors holds, zeros behind d
+        HIP_TRY(hipMemcpyAsync(d_row_ids, row_ids, (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
+        const int64_t stride = padded_stride(rows_of->iv.d);
+        return gather_rows(rows_of, d_row_ids, n_rows, (int32_t)stride, (float *)const_cast<void *>(dev), stride, st);
+    }
     return HNSW_OK;
 }
 
@@ -736,15 +749,31 @@ constexpr size_t SMALL_BLOCK = 32768;
 
 int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int k_, int32_t *out_ids, float *out_dist,
                     uint32_t *out_nd, uint32_t *out_nh, bool allow_small, bool *q_in_place) {
-    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d), rbytes = (size_t)nq * k_ * 4, cbytes = (size_t)nq * 4;
+    // (a drop-self call: the kernels' rows are k_ wide, the caller's one entry narrower)
+    const bool drop = rows && rows->drop_self;
+    const size_t qbytes = query_bytes(nq, q_stride, idx->iv.d), rbytes = (size_t)nq * (drop ? k_ - 1 : k_) * 4, cbytes = (size_t)nq * 4;
     int rc;
     HostInput q;
-    if ((rc = idx->scratch.ensure(nq, qbytes, k_)) || (rc = ensure_host_call_state(idx)) || (rc = q.resolve(queries, qbytes, idx->scratch.q)) ||
+    if ((rc = idx->scratch.ensure(nq, qbytes, k_)) || (rc = ensure_host_call_state(idx)) ||
+        (rc = rows ? q.resolve_rows(idx, rows->ids, nq, idx->scratch.q) : q.resolve(queries, qbytes, idx->scratch.q)) ||
         (ko && (rc = idx->key_scratch.ensure(rbytes * 2))))
         return rc;
     int32_t *zi = (int32_t *)registered_device_address(out_ids, rbytes);
     float *zd = (float *)registered_device_address(out_dist, rbytes);
     uint32_t *znd = (uint32_t *)registered_device_address(out_nd, cbytes), *znh = (uint32_t *)registered_device_address(out_nh, cbytes);
+    if (drop) {
+        // the epilogue's outputs: the caller's page-locked matrices in place (ids, or keys, and distances: both or neither), else
+        // the handle's scratch; the kernels themselves write the k_ wide rows of scratch.ids / scratch.dist
+        int64_t *zk = ko ? (int64_t *)registered_device_address(ko->keys, rbytes * 2) : nullptr;
+        const bool in_place = zd && (ko ? zk != nullptr : zi != nullptr);
+        ByIdBufs &bb = idx->by_id_scratch;
+        if (!in_place && ((rc = bb.dist.ensure(rbytes)) || (!ko && (rc = bb.ids.ensure(rbytes))))) return rc;
+        drop_dist = in_place ? zd : (float *)bb.dist.p;
+        drop_ids = ko ? nullptr : in_place ? zi : (int32_t *)bb.ids.p;
+        drop_keys = !ko ? nullptr : in_place ? zk : (int64_t *)idx->key_scratch.p;
+        if (in_place) out_ids = nullptr, out_dist = nullptr;      // (complete when the epilogue is: nothing to download)
+        zi = nullptr; zd = nullptr;
+    }
     if (!zi || !zd) zi = nullptr, zd = nullptr;
     small = allow_small && !ko && q.from && !zi && !znd && !znh && qbytes <= SMALL_BLOCK && rbytes <= SMALL_BLOCK && cbytes <= SMALL_BLOCK;
     if (small) {
@@ -769,7 +798,7 @@ int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q
     // ... and the caller's arrays that are not complete when the kernels are
     ids = zi && !small ? nullptr : out_ids; dist = zi && !small ? nullptr : out_dist;
     nd = znd && !small ? nullptr : out_nd; nh = znh && !small ? nullptr : out_nh;
-    if (q_in_place) *q_in_place = !q.from;
+    if (q_in_place) *q_in_place = !q.from && !rows;
     if ((rc = q.upload(idx->hs[0])) || !is_cosine(idx)) return rc;
     // COSINE: the kernels read N(Q) in the handle's scratch, normalised on hs[0] from wherever the queries are (a page-locked
     // matrix in place, the block, the staged copy): from here on the call is the device-resident one -- no zero-copy reads by the
@@ -781,9 +810,21 @@ int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q
 }
 
 int HostCall::finish(hnsw_index *idx, const char *what, hipStream_t st) {
-    hipError_t ed = small ? hipSuccess : knn_download(b, k, ids, dist, nd, nh, st);
+    const bool drop = rows && rows->drop_self;
+    // (a drop-self call downloads the counters here and its rows from where the epilogue below leaves them)
+    hipError_t ed = small ? hipSuccess : knn_download(b, k, drop ? nullptr : ids, drop ? nullptr : dist, nd, nh, st);
     int rk = HNSW_OK;
-    if (ko && ed == hipSuccess) {           // the rows as keys: one launch over the ids where the search left them, then their download
+    if (drop && ed == hipSuccess) {
+        // the k wide inner rows where the search left them -> the k - 1 wide rows without each query's own id, as ids or as keys in
+        // the same pass; then their download unless they were written in place (begin left ids / dist / ko's in_place accordingly)
+        const size_t rbytes = (size_t)b.nq * (k - 1) * 4;
+        rk = drop_self_rows(idx, b.ids, b.dist, (const int32_t *)idx->by_id_scratch.self.p, b.nq, k - 1, drop_ids, drop_keys, ko ? ko->missing : 0,
+                            drop_dist, st);
+        if (!rk && ids) ed = hipMemcpyAsync(ids, drop_ids, rbytes, hipMemcpyDeviceToHost, st);
+        if (!rk && dist && ed == hipSuccess) ed = hipMemcpyAsync(dist, drop_dist, rbytes, hipMemcpyDeviceToHost, st);
+        if (!rk && ko && drop_keys == (int64_t *)idx->key_scratch.p && ed == hipSuccess)
+            ed = hipMemcpyAsync(ko->keys, drop_keys, rbytes * 2, hipMemcpyDeviceToHost, st);
+    } else if (ko && ed == hipSuccess) {           // the rows as keys: one launch over the ids where the search left them, then their download
         rk = keys_translate(idx, b.ids, b.nq * k, ko->missing, (int64_t *)idx->key_scratch.p, st);
         if (!rk) ed = hipMemcpyAsync(ko->keys, idx->key_scratch.p, (size_t)b.nq * k * 8, hipMemcpyDeviceToHost, st);
     }
@@ -1252,6 +1293,11 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     if (!strcmp(name, "order_queries")) { idx->order_mode = value < 0 ? -1 : (value ? 1 : 0); return HNSW_OK; }
     if (!strcmp(name, "head_queries")) { idx->head_queries = std::max<int64_t>(-1, std::min<int64_t>(value, 0x7FFFFFFF)); return HNSW_OK; }
     if (!strcmp(name, "scan_slabs")) { idx->scan_slabs = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1024)); return HNSW_OK; }
+    if (!strcmp(name, "graph_chunk_rows")) {         // the nodes hnsw_knn_graph searches per inner call (hnsw_by_id.hip)
+        if (value < 1) return fail(HNSW_ERR_BAD_ARG, "graph_chunk_rows=%lld: a chunk holds at least one node", (long long)value);
+        idx->graph_chunk_rows = std::min<int64_t>(value, 0x7FFFFFFF);
+        return HNSW_OK;
+    }
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }
 
@@ -1266,7 +1312,7 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
         {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
         {"sq8_rows", idx->sq8_on ? 1 : 0}, {"sq8_dim_rows", idx->sq8d_on ? 1 : 0}, {"bit_rows", idx->bit_mode}, {"bit_query_bits", idx->bit_query_bits}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
-        {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"filter_collect", idx->filter_collect ? 1 : 0}};
+        {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"graph_chunk_rows", idx->graph_chunk_rows}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }
@@ -1336,12 +1382,13 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
 } // extern "C"
 
 int hnsw_host::knn_host_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
-                             int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko) {
-    int rc = check_batch(idx, params, nq, q_stride, queries && (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist);
+                             int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko,
+                             const RowsIn *rows) {
+    int rc = check_batch(idx, params, nq, q_stride, (rows ? rows->ids != nullptr : queries != nullptr) && (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist);
     if (rc) return rc;
     // nodes are marked deleted: the filtered search under the handle's live mask, ladder, exact stage and all
     if (idx->n_deleted > 0)
-        return filtered_host_call(idx, idx->live.get(), queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, out_stage, ko);
+        return filtered_host_call(idx, idx->live.get(), queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, out_stage, ko, rows);
     if (nq == 0) return rc;
     if (out_stage) memset(out_stage, 0, (size_t)nq * 4);
     HIP_TRY(hipSetDevice(idx->device));
@@ -1350,6 +1397,7 @@ int hnsw_host::knn_host_call(hnsw_index *idx, const float *queries, int64_t nq, 
     // not as a scan of nq status words.
     HostCall c;
     c.ko = ko;
+    c.rows = rows;
     bool q_in_place = false;
     if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
     hipStream_t st = idx->hs[0];

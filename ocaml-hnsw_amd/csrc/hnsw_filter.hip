@@ -424,9 +424,11 @@ int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_para
 // both search entry points once their arguments are checked (nq > 0).  fs.d_masks / fs.d_which are allocated; host_masks (the
 // per-query form): what they hold is still to be uploaded, from there and from fs.which, on the call's stream
 int filtered_call(hnsw_index *idx, const FilterSet &fs, const uint32_t *const *host_masks, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
-                  int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko = nullptr) {
+                  int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko = nullptr,
+                  const RowsIn *rows = nullptr) {
     HostCall c;
     c.ko = ko;
+    c.rows = rows;
     bool q_in_place = false;
     int rc;
     if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
@@ -540,8 +542,8 @@ int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const 
 
 int hnsw_host::filtered_host_call(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
                                   const hnsw_search_params *params, int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops,
-                                  uint32_t *out_stage, const KeysOut *ko) {
-    int rc = check_batch(idx, params, nq, q_stride, queries && (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist);
+                                  uint32_t *out_stage, const KeysOut *ko, const RowsIn *rows) {
+    int rc = check_batch(idx, params, nq, q_stride, (rows ? rows->ids != nullptr : queries != nullptr) && (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist);
     if (rc) return rc;
     if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
         return fail(HNSW_ERR_BAD_ARG, "the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no filtered meaning");
@@ -550,7 +552,7 @@ int hnsw_host::filtered_host_call(hnsw_index *idx, const hnsw_filter *f, const f
     HIP_TRY(hipSetDevice(idx->device));
     // the table of one filter: the mask's own address, on the device since the filter was made
     return filtered_call(idx, FilterSet{&f, 1, nullptr, f->table(), nullptr}, nullptr, queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops,
-                         out_stage, ko);
+                         out_stage, ko, rows);
 }
 
 extern "C" {

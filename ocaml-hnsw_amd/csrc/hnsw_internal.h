@@ -10,6 +10,7 @@
 #include "hnsw_group_plan.h"
 #include "hnsw_bits_plan.h"
 #include "hnsw_keys_plan.h"
+#include "hnsw_by_id_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -389,6 +390,19 @@ struct KeysOut {
     int64_t missing;
 };
 
+// A host call whose queries are ROWS OF THE INDEX (hnsw_by_id.hip): ids [nq], id_base-based and already validated by the entry
+// point.  drop_self: the call runs k + 1 wide (the k handed to HostCall::begin is that k + 1) into the handle's scratch and the
+// drop-self epilogue writes the caller's [nq][k] rows (the rule: hnsw_by_id_plan.h).
+struct RowsIn {
+    const int32_t *ids;
+    bool drop_self;
+};
+// ... its scratch: the queries' own ids on the device [nq], and the compacted [nq][k] ids and distances of a drop-self call before
+// their download (keys: the handle's key_scratch).  Not index tables: not counted in device_bytes.
+struct ByIdBufs {
+    DevBuf self, ids, dist;
+};
+
 inline int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
     return (s && *s) ? atoi(s) : dflt;
@@ -579,6 +593,10 @@ struct hnsw_index {
     // node, n entries, moved with the nodes by adopt_graph.  key_scratch: the [nq][k] keys of a keyed host call before their download.
     std::unique_ptr<hnsw_host::KeyTables> keys;
     hnsw_host::DevBuf key_scratch;
+    // Searches by stored item (hnsw_by_id.hip): scratch of the host calls whose queries are rows of the index, and option
+    // "graph_chunk_rows": the nodes hnsw_knn_graph searches per inner call (>= 1)
+    hnsw_host::ByIdBufs by_id_scratch;
+    int64_t graph_chunk_rows = hnsw_host::GRAPH_CHUNK_ROWS;
 };
 
 namespace hnsw_dev {
@@ -889,11 +907,14 @@ private:
 };
 // hnsw_capi.hip: hnsw_search_batch; ko (optional): the rows go to ko->keys as keys and out_ids may be null (hnsw_search_batch_keyed);
 // out_stage (optional): as the filtered call writes it while nodes are marked, zero otherwise
+// rows (optional; queries is then null and q_stride padded_stride(d)): the queries are rows of the index, gathered on the device
+// (RowsIn; hnsw_search_batch_by_id)
 int knn_host_call(::hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params, int32_t *out_ids,
-                  float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko);
+                  float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko, const RowsIn *rows = nullptr);
 // hnsw_filter.hip: hnsw_search_batch_filtered; ko: likewise
 int filtered_host_call(::hnsw_index *idx, const ::hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
-                       int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko);
+                       int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko,
+                       const RowsIn *rows = nullptr);
 // hnsw_capi.hip: the value that puts option `name` of hnsw_index_set_option back where it is now (HNSW_ERR_BAD_ARG: no such option)
 int get_option(const ::hnsw_index *idx, const char *name, int64_t *value);
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
@@ -903,12 +924,29 @@ int ensure_host_call_state(::hnsw_index *idx);
 
 // hnsw_capi.hip: where the device reads the host array [p, p + bytes): in place when it lies in a range of hnsw_host_alloc /
 // hnsw_host_register, else in `stage`, grown to hold it (resolve: allocates, queues nothing), after upload has queued the copy
+// ... or, a third source, ROWS OF THE INDEX: dev is `stage`, sized for nq rows of padded_stride(d) floats (resolve_rows: allocates,
+// queues nothing), which upload fills by the gather kernel behind the upload of the nq ids (hnsw_by_id.hip) -- no row crosses the link
 struct HostInput {
     const void *dev = nullptr, *from = nullptr;     // from: the host array while it still has to be copied to dev, else null
     size_t bytes = 0;
+    ::hnsw_index *rows_of = nullptr;                // rows of this index: their ids on the host, where those go on the device, how many
+    const int32_t *row_ids = nullptr;
+    int32_t *d_row_ids = nullptr;
+    int64_t n_rows = 0;
     int resolve(const void *p, size_t n, DevBuf &stage);
+    int resolve_rows(::hnsw_index *idx, const int32_t *ids, int64_t nq, DevBuf &stage);
     int upload(hipStream_t st) const;
 };
+// hnsw_by_id.hip: the gather kernel on `st`: row j of d_out (out_stride floats apart) = the first `width` floats of the float32 row
+// of node d_ids[j] - id_base (tables.X; width <= padded_stride(d)), zeros where that is no node
+int gather_rows(const ::hnsw_index *idx, const int32_t *d_ids, int64_t m, int32_t width, float *d_out, int64_t out_stride, hipStream_t st);
+// hnsw_by_id.hip: the drop-self epilogue on `st` over the inner rows d_ids / d_dist [nq][k + 1]: the [nq][k] rows with each query's
+// own id (d_self [nq]) removed into out_dist and out_ids -- or, out_keys not null, into out_keys as the index's keys
+// (hnsw_index_keys_of's rule with `missing`).  The outputs may be page-locked host matrices seen from the device.
+int drop_self_rows(const ::hnsw_index *idx, const int32_t *d_ids, const float *d_dist, const int32_t *d_self, int64_t nq, int32_t k,
+                   int32_t *out_ids, int64_t *out_keys, int64_t missing, float *out_dist, hipStream_t st);
+// hnsw_keys.hip: the 0-based nodes of m keys of a keyed handle (host arrays; -1: no node has the key)
+int keys_find_nodes(const ::hnsw_index *idx, const int64_t *keys, int64_t m, std::vector<int32_t> &nodes);
 // hnsw_capi.hip: the matrices of one synchronous host-buffer call on the handle's stream hs[0] (rules: beside HostCall::begin)
 struct HostCall {
     KnnBatch b{};                                   // what the kernels read and write
@@ -922,6 +960,15 @@ struct HostCall {
     // a keyed call (set before begin, out_ids then null): finish translates the device-resident ids into the handle's key_scratch
     // and downloads that into ko->keys; such a call never takes the small block
     const KeysOut *ko = nullptr;
+    // the queries are rows of the index (set before begin, `queries` then null and q_stride padded_stride(d)): begin gathers them
+    // into scratch.q and from there the call is the device-resident one, as a COSINE call is -- no head split, no zero-copy reads,
+    // no small block.  rows->drop_self: begin's k is the inner k + 1, the kernels write scratch, and finish runs the drop-self
+    // epilogue over it into drop_ids (or drop_keys) / drop_dist -- the caller's page-locked matrices in place, else the handle's
+    // by_id_scratch / key_scratch, downloaded from there
+    const RowsIn *rows = nullptr;
+    int32_t *drop_ids = nullptr;
+    int64_t *drop_keys = nullptr;
+    float *drop_dist = nullptr;
     // *q_in_place: the device reads the queries from host memory (the knn call then hands knn_search scratch.q to stage them in)
     int begin(::hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int k, int32_t *out_ids, float *out_dist,
               uint32_t *out_nd, uint32_t *out_nh, bool allow_small, bool *q_in_place = nullptr);

@@ -189,6 +189,8 @@ int renumbered_keys(const hnsw_index *idx, const int32_t *new_id, int64_t n_new,
     return HNSW_OK;
 }
 
+int keys_find_nodes(const hnsw_index *idx, const int64_t *keys, int64_t m, std::vector<int32_t> &nodes) { return find_nodes(idx, keys, m, nodes); }
+
 int keys_translate(const hnsw_index *idx, const int32_t *d_ids, int64_t m, int64_t missing, int64_t *d_out, hipStream_t st) {
     if (m <= 0) return HNSW_OK;
     const KeyTables &kt = *idx->keys;

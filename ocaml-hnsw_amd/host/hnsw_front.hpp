@@ -12,6 +12,9 @@
 //   Hnsw::Ohnsw::mark_deleted / unmark_deleted / deleted_count / deleted_mask / compact    (hnsw_index_mark_deleted ... hnsw_index_compact)
 //   Hnsw::Ohnsw::set_keys / clear_keys / keys_info / keys_of / find_keys / knn_keyed / insert_keyed / remove_keys /
 //   mark_deleted_keys / unmark_deleted_keys, Hnsw::Filter::by_keys                         (hnsw_index_set_keys ... hnsw_filter_create_by_keys)
+//   Hnsw::Ohnsw::knn_by_id / knn_by_key / brute_force_by_id / knn_graph / rows_device      (hnsw_search_batch_by_id, hnsw_search_batch_by_key,
+//                                                                                           hnsw_brute_force_batch_by_id, hnsw_knn_graph,
+//                                                                                           hnsw_index_get_rows_device)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
@@ -611,6 +614,55 @@ inline void unmark_deleted_keys(Hgraph &g, const std::vector<int64_t> &keys) { c
 // ... and for ids already on the device, queued on `stream` (hnsw_index_keys_of_device)
 inline void keys_of_device(Hgraph &g, const int32_t *d_ids, int64_t m, int64_t missing, int64_t *d_out, void *stream = nullptr) {
     check(hnsw_index_keys_of_device(g.handle(), d_ids, m, missing, d_out, stream));
+}
+
+// ---- search by stored item: the queries are rows the index holds, named by id or by key; only the ids cross the link (the
+// definition: include/hnsw_mi355x.h, the last section) ----
+// knn_batch_bigarray with the stored vectors of the nodes `ids` (int32, id_base-based: a search's output fits) as the queries
+// (hnsw_search_batch_by_id) -> (ids, distances) [ids.size()][k].  exclude_self: the search runs k + 1 wide with ef' = max(ef, k + 1)
+// and each row loses the node's own id (the first k entries if it is not among them); false: exactly the search over rows(ids).
+inline std::pair<std::vector<int32_t>, std::vector<float>> knn_by_id(const Hgraph &g, int k, const std::vector<int32_t> &ids, int ef = 0,
+                                                                      bool exclude_self = true, int sem = HNSW_SEM_OHNSW, int fill = HNSW_FILL_OHNSW) {
+    std::vector<int32_t> out(ids.size() * (size_t)(k > 0 ? k : 0), -1);
+    std::vector<float> dist(out.size(), 0.f);
+    hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
+    check(hnsw_search_batch_by_id(g.handle(), ids.data(), (int64_t)ids.size(), &p, exclude_self ? 1 : 0, out.data(), dist.data(), nullptr, nullptr));
+    return {std::move(out), std::move(dist)};
+}
+// ... for the nodes stored under `keys`, answered in keys (hnsw_search_batch_by_key); an absent key refuses the call
+inline std::pair<std::vector<int64_t>, std::vector<float>> knn_by_key(const Hgraph &g, int k, const std::vector<int64_t> &keys, int ef = 0,
+                                                                       bool exclude_self = true, int64_t missing = -1, int sem = HNSW_SEM_OHNSW,
+                                                                       int fill = HNSW_FILL_OHNSW) {
+    std::vector<int64_t> out(keys.size() * (size_t)(k > 0 ? k : 0), missing);
+    std::vector<float> dist(out.size(), 0.f);
+    hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
+    check(hnsw_search_batch_by_key(g.handle(), keys.data(), (int64_t)keys.size(), &p, exclude_self ? 1 : 0, missing, out.data(), dist.data(), nullptr, nullptr));
+    return {std::move(out), std::move(dist)};
+}
+// ... the exact form (hnsw_brute_force_batch_by_id): brute_force_knn over the stored vectors of the nodes `ids`
+inline std::pair<std::vector<int32_t>, std::vector<float>> brute_force_by_id(const Hgraph &g, int k, const std::vector<int32_t> &ids,
+                                                                              bool exclude_self = true, int fill = HNSW_FILL_OHNSW) {
+    std::vector<int32_t> out(ids.size() * (size_t)(k > 0 ? k : 0), -1);
+    std::vector<float> dist(out.size(), 0.f);
+    check(hnsw_brute_force_batch_by_id(g.handle(), ids.data(), (int64_t)ids.size(), k, fill, exclude_self ? 1 : 0, out.data(), dist.data()));
+    return {std::move(out), std::move(dist)};
+}
+// the k-NN graph of the whole index (hnsw_knn_graph): row v = the row of knn_by_id (exact: of brute_force_by_id) for node
+// id_base + v without the node itself -> (ids, distances) [n][k]
+inline std::pair<std::vector<int32_t>, std::vector<float>> knn_graph(const Hgraph &g, int k, int ef = 0, bool exact = false, int sem = HNSW_SEM_OHNSW,
+                                                                      int fill = HNSW_FILL_OHNSW) {
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    std::vector<int32_t> out((size_t)inf.n * (size_t)(k > 0 ? k : 0), -1);
+    std::vector<float> dist(out.size(), 0.f);
+    hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
+    check(hnsw_knn_graph(g.handle(), &p, exact ? 1 : 0, out.data(), dist.data()));
+    return {std::move(out), std::move(dist)};
+}
+// the stored float32 rows of the nodes d_ids (device int32, id_base-based) into the device matrix d_out, queued on `stream`
+// (hnsw_index_get_rows_device); an id outside the index gives a row of zeros
+inline void rows_device(Hgraph &g, const int32_t *d_ids, int64_t m, float *d_out, int64_t out_stride, void *stream = nullptr) {
+    check(hnsw_index_get_rows_device(g.handle(), d_ids, m, d_out, out_stride, stream));
 }
 
 // The exact re-rank (hnsw_rerank_batch): for each query the k nearest of ITS candidates cand[q][0 .. cand_stride) (entries below

@@ -292,6 +292,24 @@ let hnsw_index_unmark_deleted_keys =
 let hnsw_filter_create_by_keys =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_filter_create_by_keys"
     (index @-> ptr int64_t @-> int64_t @-> ptr filter_handle @-> returning int32_t)
+(* search by stored item (see the C header, the last section): the queries are rows the index holds; only their ids cross the link *)
+let hnsw_index_get_rows_device =
+  foreign ~from:lib "hnsw_index_get_rows_device"
+    (index @-> ptr int32_t @-> int64_t @-> ptr float @-> int64_t @-> ptr void @-> returning int32_t)
+let hnsw_search_batch_by_id =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_by_id"
+    (index @-> ptr int32_t @-> int64_t @-> ptr search_params @-> int32_t @-> ptr int32_t @-> ptr float @-> ptr uint32_t
+     @-> ptr uint32_t @-> returning int32_t)
+let hnsw_search_batch_by_key =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_by_key"
+    (index @-> ptr int64_t @-> int64_t @-> ptr search_params @-> int32_t @-> int64_t @-> ptr int64_t @-> ptr float
+     @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+let hnsw_brute_force_batch_by_id =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_brute_force_batch_by_id"
+    (index @-> ptr int32_t @-> int64_t @-> int32_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float @-> returning int32_t)
+let hnsw_knn_graph =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_knn_graph"
+    (index @-> ptr search_params @-> int32_t @-> ptr int32_t @-> ptr float @-> returning int32_t)
 let hnsw_index_deleted_count = foreign ~from:lib "hnsw_index_deleted_count" (index @-> ptr int64_t @-> returning int32_t)
 let hnsw_index_deleted_bits = foreign ~from:lib "hnsw_index_deleted_bits" (index @-> ptr uint32_t @-> returning int32_t)
 let hnsw_index_compact =
@@ -1291,6 +1309,57 @@ let knn_batch_keyed ?(semantics = 0) ?(fill = 0) ?filter ?(missing = -1) (t : t)
   (Array.init nq (fun q -> Array.init k (fun j -> Int64.to_int (CArray.get keys (q * k + j)))),
    Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
    Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))
+
+(* Search by stored item (hnsw_search_batch_by_id ...): the stored vectors of the nodes [ids] (id_base-based: a search's output can be
+   fed straight back) are the queries, gathered on the device -- only the ids cross the link.  [exclude_self] (the default): the
+   search runs k + 1 wide with ef' = max(ef, k + 1) and each row loses the node's own id, the first k entries if it is not among
+   them; [~exclude_self:false]: exactly [knn_batch] over the stored rows.  -> (ids, distances), [nq][k] (-1 / nan where fewer were
+   found).  [knn_batch_by_key]: the same for the nodes stored under [keys], answered in keys; an absent key refuses the call.
+   [brute_force_by_id]: the exact form.  [knn_graph t ~ef ~k]: the row of [knn_batch_by_id] (?exact: of [brute_force_by_id]) of
+   every node, computed on the device in chunks (option "graph_chunk_rows"). *)
+let by_id_params ~semantics ~fill ~ef ~k =
+  let p = make search_params in
+  setf p p_ef (Int32.of_int ef); setf p p_k (Int32.of_int k); setf p p_fill (Int32.of_int fill);
+  setf p p_semantics (Int32.of_int semantics);
+  p
+let c_ids32 (ids : int array) =
+  let c = CArray.make int32_t (max 1 (Array.length ids)) in
+  Array.iteri (fun i v -> CArray.set c i (Int32.of_int v)) ids;
+  c
+let knn_batch_by_id ?(semantics = 0) ?(fill = 0) ?(exclude_self = true) (t : t) (ids : int array) ~ef ~k :
+  int array array * float array array =
+  let nq = Array.length ids in
+  let out = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let p = by_id_params ~semantics ~fill ~ef ~k in
+  check (hnsw_search_batch_by_id t.handle (CArray.start (c_ids32 ids)) (Int64.of_int nq) (addr p) (if exclude_self then 1l else 0l)
+           (CArray.start out) (CArray.start dist) (from_voidp uint32_t null) (from_voidp uint32_t null));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get out (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))))
+let knn_batch_by_key ?(semantics = 0) ?(fill = 0) ?(exclude_self = true) ?(missing = -1) (t : t) (keys : int array) ~ef ~k :
+  int array array * float array array =
+  let nq = Array.length keys in
+  let out = CArray.make int64_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let p = by_id_params ~semantics ~fill ~ef ~k in
+  check (hnsw_search_batch_by_key t.handle (CArray.start (c_keys keys)) (Int64.of_int nq) (addr p) (if exclude_self then 1l else 0l)
+           (Int64.of_int missing) (CArray.start out) (CArray.start dist) (from_voidp uint32_t null) (from_voidp uint32_t null));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int64.to_int (CArray.get out (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))))
+let brute_force_by_id ?(fill = 0) ?(exclude_self = true) (t : t) (ids : int array) ~k : int array array * float array array =
+  let nq = Array.length ids in
+  let out = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  check (hnsw_brute_force_batch_by_id t.handle (CArray.start (c_ids32 ids)) (Int64.of_int nq) (Int32.of_int k) (Int32.of_int fill)
+           (if exclude_self then 1l else 0l) (CArray.start out) (CArray.start dist));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get out (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))))
+let knn_graph ?(semantics = 0) ?(fill = 0) ?(exact = false) (t : t) ~ef ~k : int array array * float array array =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  let n = Int64.to_int (getf inf ii_n) in
+  let out = CArray.make int32_t (max 1 (n * k)) and dist = CArray.make float (max 1 (n * k)) in
+  let p = by_id_params ~semantics ~fill ~ef ~k in
+  check (hnsw_knn_graph t.handle (addr p) (if exact then 1l else 0l) (CArray.start out) (CArray.start dist));
+  (Array.init n (fun v -> Array.init k (fun j -> Int32.to_int (CArray.get out (v * k + j)))),
+   Array.init n (fun v -> Array.init k (fun j -> CArray.get dist (v * k + j))))
 
 (* [insert_batch_keyed t batch keys]: [insert_batch] into an index that owns keys (hnsw_index_insert_keyed), keys.(i) naming
    column i of [batch].  A stored or repeated key refuses the call before anything is built; an empty index without keys starts
