@@ -1472,8 +1472,9 @@ int32_t hnsw_brute_force_batch_grouped(hnsw_index *idx, const hnsw_labels *label
  * hnsw_index_save stays accepted and the format does not change: keys are NOT saved.  hnsw_index_keys_of(NULL ids) before the
  *   save and hnsw_index_set_keys on the loaded handle is the round trip.
  *
- * NOT BUILT: keys for hnsw_sharded and hnsw_multi; upsert (replace the vector under a key); saved keys; keyed forms of the range,
- * grouped and per-query-filter calls -- compose those with hnsw_index_keys_of.
+ * NOT BUILT: keys for hnsw_sharded and hnsw_multi; saved keys; keyed forms of the range,
+ * grouped and per-query-filter calls -- compose those with hnsw_index_keys_of.  (upsert, replacing the vector under a key: built,
+ * see hnsw_index_upsert_keyed in the header's last section.)
  * Rates (tools/keys_rate.py, profiles/keys.txt; one run), MI355X, 1 M x 128 byte rows, ef 128, k 10, 10 k queries, the two calls
  * alternating on one handle: hnsw_search_batch_keyed 0.894 ms per batch against 0.849 ms for hnsw_search_batch (+0.045 ms: the
  * launch and 800 KB of keys downloaded where the plain call downloads 400 KB of ids); hnsw_index_set_keys of 1 M keys 1.75 ms;
@@ -1560,6 +1561,68 @@ int32_t hnsw_brute_force_batch_by_id(hnsw_index *idx, const int32_t *ids, int64_
                                      int32_t *out_ids, float *out_dist);
 int32_t hnsw_knn_graph(hnsw_index *idx, const hnsw_search_params *params, int32_t exact, int32_t *out_ids /* [n][k] */,
                        float *out_dist /* [n][k] or NULL */);
+
+/* ==== upsert: replace or add vectors in one all-or-nothing call ====
+ * "Store this vector under this key, whether the key is there or not."  The index could grow (hnsw_index_insert_keyed) and shrink
+ * (hnsw_index_remove_keys); changing the vector under a key took both, two table swaps, and was not atomic: a refused insert left
+ * the old vectors gone and the new ones absent.
+ *
+ * THE DEFINITION is ONE equivalence.  Let P be the call's keys that are stored.  hnsw_index_upsert_keyed(idx, X, keys, m, ...)
+ * leaves the handle exactly as this sequence leaves it:
+ *   1. hnsw_index_remove_keys(idx, P in the call's order);
+ *   2. hnsw_index_insert_keyed(idx, X, m, row_stride, keys, params).
+ * "Exactly": link for link on every layer, row for row, level for level, key for key, entry point and max_layer, every derived
+ * row copy with its parameters (hnsw_index_sq8_params, hnsw_index_sq8_dim_params, hnsw_index_bit_params), the marks, and every
+ * search result bit for bit.  The one difference is the purpose of the call: the graph epoch moves on once, not twice (filters and
+ * labels made before are refused afterwards), there is one table swap, one re-derivation of the row copies over the final table
+ * (the sq8 kinds quantise the whole table once), one warm-up.
+ * Everything else is inherited from the two calls, not restated: the m rows become the nodes n_old - |P| ... n_old - |P| + m - 1
+ * (plus id_base) in the call's row order, stored or not; their levels are the draws of those positions under params->seed; the
+ * repair rule of hnsw_index_remove; batching, the widening of rows narrower than 2M / M, COSINE's normalisation of the new rows,
+ * expected_ef and the prepared shapes of hnsw_index_insert.  A node marked deleted whose key is upserted comes back live (it was
+ * removed and inserted); the other marks move with their nodes.  The locality codes are dropped and built again on demand, as the
+ * removal leaves them for the insert that follows it; with no stored key in the call they are carried over, as hnsw_index_insert_keyed
+ * carries them.
+ * hnsw_index_update(idx, ids, X, m, ...) is the same definition over hnsw_index_remove(ids) and hnsw_index_insert(X), for handles
+ * without keys: the m stored nodes ids[i] (id_base-based) are replaced by the rows X[i].  A handle with keys is refused
+ * (HNSW_ERR_BAD_ARG, pointing at the keyed call), as hnsw_index_insert refuses it.
+ *
+ * Outputs (both optional, written only when the call succeeds): out_replaced[i] = 1 if keys[i] was stored, else 0; out_new_id
+ * [n_old] as hnsw_index_remove writes it: the id a kept node has afterwards, id_base - 1 for a replaced node.
+ * Special cases: m == 0 is a no-op that fills out_new_id with the identity (the epoch does not move).  With P empty the call IS
+ * hnsw_index_insert_keyed.  With every stored node in P it empties the index and then equals hnsw_build of X with the keys.
+ *
+ * Refused, all before anything is built, the handle untouched (HNSW_ERR_BAD_ARG unless named): two equal keys in the call, naming
+ * the smallest such key as hnsw_index_set_keys does; a handle that has nodes and no keys in the keyed call (an EMPTY index without
+ * keys is accepted and starts its keys here, as hnsw_index_insert_keyed accepts it); in hnsw_index_update an id out of range or
+ * repeated; and everything hnsw_index_remove and hnsw_index_insert refuse: submitted requests not waited for, a replica of an
+ * hnsw_multi, a shard of an hnsw_sharded, params->metric or params->id_base that differ from the index's, rows wider than 2M / M,
+ * a NaN or infinite new value while a code option (sq8_rows, sq8_dim_rows, bit_rows) is on (HNSW_ERR_UNSUPPORTED), a
+ * device_fallback_slab_bytes slab that holds no query of the final n.  The insert's checks are made against the index the
+ * removal WILL leave (its node count and top layer are plain arithmetic).
+ * All or nothing, which the two-call sequence is not: on any error at any stage -- HNSW_ERR_OOM, a value out of fp16 range under
+ * half_rows, a degree overflow that exhausts its retries included -- the index is exactly as before: same graph, same keys, same
+ * marks, same epoch, filters made before still accepted.
+ *
+ * Device memory: the call holds no more than either call alone, two copies of the index at its peak (the old tables and the new
+ * ones).  The removal half builds its repaired graph straight into tables sized for the final node count and upper-row count, and
+ * the insert half uploads the new rows behind the kept ones and grows the graph in place on those same tables.  A handle whose
+ * rows are narrower than 2M / M (a graph flattened from elsewhere) goes through hnsw_index_insert's widening copy: a third copy for
+ * the duration of the call.  A degree overflow of the builder runs the removal again (it is deterministic) before the batches get
+ * four times the removal buffer.
+ *
+ * NOT BUILT: upsert for hnsw_sharded and hnsw_multi; an in-place update that keeps the node's id (the definition renumbers, as the
+ * removal does); saved keys.
+ * Rates (tools/upsert_rate.py, profiles/upsert.txt; one run), MI355X, 1 M x 128 byte rows, M 16, efC 200, calls of 1000 keys, half
+ * stored and half new, against hnsw_index_remove_keys + hnsw_index_insert_keyed on a twin, the two taking turns: 131.1 ms per call
+ * against 135.9 ms for the pair (minima 128.7 / 133.1; with sq8_rows on 146.7 / 141.3): the ranges overlap, the call is not
+ * measurably faster -- the removal's repair is 126 ms of the pair, the whole insert call 10 ms.  Sampled peak of device memory above
+ * the index: 843 MB for both (the index: 798 MB). */
+int32_t hnsw_index_upsert_keyed(hnsw_index *idx, const float *vectors, const int64_t *keys, int64_t m, int64_t row_stride,
+                                const hnsw_build_params *params, uint8_t *out_replaced /* optional [m] */,
+                                int32_t *out_new_id /* optional [n_old] */);
+int32_t hnsw_index_update(hnsw_index *idx, const int64_t *ids, const float *vectors, int64_t m, int64_t row_stride,
+                          const hnsw_build_params *params, int32_t *out_new_id /* optional [n_old] */);
 
 #ifdef __cplusplus
 }

@@ -165,6 +165,8 @@ _ABI = {
     "hnsw_search_batch_by_key": [_vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
     "hnsw_brute_force_batch_by_id": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "hnsw_knn_graph": [_vp, _vp, _i32, _vp, _vp],
+    "hnsw_index_upsert_keyed": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "hnsw_index_update": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -733,6 +735,11 @@ class Hgraph:
         if k.size:
             self._shrunk(new_id)
         return new_id
+
+    def upsert(self, batch, keys, num_connections, num_nodes_search_construction, **build_args):
+        """Ohnsw.upsert_batch_keyed(self, ...): replace the vectors under the stored keys, add the others, in one all-or-nothing
+        call -> (replaced bool[m], new_id int32[n_old])"""
+        return Ohnsw.upsert_batch_keyed(self, batch, keys, num_connections, num_nodes_search_construction, **build_args)
 
     def mark_deleted_keys(self, keys):
         """hnsw_index_mark_deleted_keys: mark_deleted of the nodes with these keys (an absent key is refused, nothing changed)"""
@@ -1434,6 +1441,56 @@ class Ohnsw:
         hgraph._append_vectors(X)
         hgraph._adopt(hgraph.info())
         return _np.arange(n_old + hgraph.id_base, n_old + m + hgraph.id_base, dtype=_np.int64)
+
+    @staticmethod
+    def upsert_batch_keyed(hgraph, batch, keys, num_connections, num_nodes_search_construction, seed=0, max_batch=0, batch_div=0,
+                           expected_ef=0, expected_sem=SEM_OHNSW, metric=None):
+        """Replace or add vectors by key in one all-or-nothing call (hnsw_index_upsert_keyed): row i of `batch` becomes the vector
+        under keys[i], whether that key is stored or not.  The index afterwards is exactly what Hgraph.remove_keys(the stored ones
+        among keys) followed by insert_batch_keyed(batch, keys) leaves, with one table swap and one epoch step instead of two; on
+        any error it is exactly as before.  Two equal keys in the call are refused.  -> (replaced: bool [m], keys[i] was stored;
+        new_id: int32 [n_old] as remove_batch returns it, id_base - 1 for a replaced node).  The rows of the call are the nodes
+        n_old - replaced.sum() + i + id_base."""
+        X, xs = _rows(batch)
+        if X.ndim != 2 or (X.shape[0] and X.shape[1] != hgraph.d):
+            raise InvalidArgument("batch must be [m][d] with the index's d = %d" % hgraph.d)
+        kk = _keys(keys)
+        m = X.shape[0]
+        if kk.size != m:
+            raise InvalidArgument("%d keys for %d vectors" % (kk.size, m))
+        p = _BuildParams(num_connections, num_nodes_search_construction, hgraph.metric if metric is None else int(metric), hgraph.id_base, seed, max_batch,
+                         batch_div, expected_ef, expected_sem)
+        replaced = _np.zeros(m, _np.uint8)
+        new_id = _np.empty(hgraph.n, _np.int32)
+        _check(load().hnsw_index_upsert_keyed(hgraph.handle, _ptr(X) if m else None, _ptr(kk) if m else None, m, max(xs, hgraph.d), _C.byref(p),
+                                              _ptr(replaced) if m else None, _ptr(new_id) if new_id.size else None))
+        if m:
+            hgraph._shrunk(new_id)
+            hgraph._append_vectors(X)
+        return replaced.astype(bool), new_id
+
+    @staticmethod
+    def update_batch(hgraph, ids, batch, num_connections, num_nodes_search_construction, seed=0, max_batch=0, batch_div=0,
+                     expected_ef=0, expected_sem=SEM_OHNSW, metric=None):
+        """upsert_batch_keyed for an index without keys (hnsw_index_update): the stored nodes `ids` (id_base-based, distinct) are
+        replaced by the rows of `batch`: exactly remove_batch(ids) followed by insert_batch(batch), in one all-or-nothing call.
+        An index with keys is refused (upsert_batch_keyed updates it).  -> new_id as remove_batch returns it."""
+        X, xs = _rows(batch)
+        if X.ndim != 2 or (X.shape[0] and X.shape[1] != hgraph.d):
+            raise InvalidArgument("batch must be [m][d] with the index's d = %d" % hgraph.d)
+        ids = _np.ascontiguousarray(ids, dtype=_np.int64).reshape(-1)
+        m = X.shape[0]
+        if ids.size != m:
+            raise InvalidArgument("%d ids for %d vectors" % (ids.size, m))
+        p = _BuildParams(num_connections, num_nodes_search_construction, hgraph.metric if metric is None else int(metric), hgraph.id_base, seed, max_batch,
+                         batch_div, expected_ef, expected_sem)
+        new_id = _np.empty(hgraph.n, _np.int32)
+        _check(load().hnsw_index_update(hgraph.handle, _ptr(ids) if m else None, _ptr(X) if m else None, m, max(xs, hgraph.d), _C.byref(p),
+                                        _ptr(new_id) if new_id.size else None))
+        if m:
+            hgraph._shrunk(new_id)
+            hgraph._append_vectors(X)
+        return new_id
 
     @staticmethod
     def remove_batch(hgraph, ids):

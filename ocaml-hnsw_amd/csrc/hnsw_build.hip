@@ -389,11 +389,66 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
 
 } // namespace hnsw_host
 
-// One attempt of hnsw_index_insert: a new handle `out` with the graph of idx grown by the m vectors -- idx's tables copied
-// (rows widened to 2M / M) into tables sized for n_old + m nodes, then run_batches from position n_old.  idx is only read.
+// The levels and the upper-row layout of m nodes appended behind n_old nodes that hold rowsU_old upper rows: node n_old + j draws
+// position n_old + j's level.  Shared by hnsw_index_insert and the insert half of hnsw_index_upsert_keyed / hnsw_index_update.
+namespace {
+struct GrowPlan {
+    std::vector<uint8_t> lvl;          // [m]
+    std::vector<int2> ref;             // [m]: (first upper row or -1, level)
+    int64_t rowsU = 0;                 // upper rows afterwards
+    int lcap_new = 1;                  // 1 + the highest new level
+};
+GrowPlan grow_plan(const hnsw_build_params *p, int64_t n_old, int64_t m, int64_t rowsU_old) {
+    GrowPlan g;
+    const double level_mult = 1.0 / std::log((double)p->num_connections);
+    g.lvl.resize((size_t)m);
+    for (int64_t j = 0; j < m; ++j) g.lvl[(size_t)j] = node_level(p->seed, n_old + j, level_mult);
+    for (uint8_t l : g.lvl) g.lcap_new = std::max(g.lcap_new, (int)l + 1);
+    g.rowsU = upper_layout(g.lvl.data(), m, rowsU_old, g.ref);
+    return g;
+}
+} // namespace
+
+int64_t hnsw_host::grown_upper_rows(const hnsw_build_params *p, int64_t n_old, int64_t m, int64_t rowsU_old) {
+    return grow_plan(p, n_old, m, n_old > 0 ? rowsU_old : 0).rowsU;
+}
+
+// "Grow in place": nx holds a graph of n_old = nx->iv.n nodes (rows compacted or with holes, widths nx->iv.S0 / SU = 2M / M) in
+// tables that alloc_graph_tables sized for n_old + m nodes and grown_upper_rows upper rows, the rows behind the graph empty;
+// nx->info names its metric.  The m vectors are uploaded behind the stored ones (COSINE: normalised), their layout written, and
+// run_batches inserts them from position n_old on those same tables.  On an error nx is to be discarded, never patched.
+int hnsw_host::grow_graph_in_place(hnsw_index *nx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p,
+                                   int64_t rem_scale, bool *rem_overflow) {
+    *rem_overflow = false;
+    IndexTables &t = nx->tables;
+    IndexView &iv = nx->iv;
+    const int64_t n_old = iv.n, n = n_old + m, stride = iv.stride;
+    const int M = p->num_connections;
+    const GrowPlan g = grow_plan(p, n_old, m, n_old > 0 ? iv.rowsU : 0);
+    int cur_max = n_old > 0 ? iv.max_layer : 0, entry = n_old > 0 ? iv.entry_point : 0;
+    const int lcap = std::max(cur_max + 1, g.lcap_new);
+    int rc;
+    BuildView bv{};
+    if ((rc = upload_rows(vectors, m, iv.d, row_stride, (float *)t.X.p + n_old * stride))) return rc;
+    // COSINE: the new rows only -- the old ones are N(X) already (row numbers in the message: of the m new vectors)
+    if (nx->info.metric == HNSW_METRIC_COSINE && (rc = cosine_store_rows((float *)t.X.p + n_old * stride, m, iv.d, "nothing inserted"))) return rc;
+    if ((rc = upload_upper_layout(t, n_old, g.ref))) return rc;
+    iv.n = n; iv.S0 = 2 * M; iv.SU = M; iv.rowsU = g.rowsU; iv.max_layer = cur_max; iv.entry_point = entry;
+    bind_view(nx);                                                      // (the derived tables are the caller's)
+    bv.iv = iv; bv.nbr0_w = (int32_t *)t.nbr0.p; bv.nbrU_w = (int32_t *)t.nbrU.p;
+    if (n > 1 && (rc = run_batches(bv, g.lvl.data() + (n_old > 0 ? 0 : 1), std::max<int64_t>(n_old, 1), n, lcap, p, rem_scale,
+                                   rem_overflow, &cur_max, &entry))) return rc;
+    iv.max_layer = cur_max; iv.entry_point = entry;
+    nx->info.max_degree = M;
+    bind_view(nx);
+    return HNSW_OK;
+}
+
+// One attempt of hnsw_index_insert: a new handle `out` with the graph of idx grown by the m vectors.  "Make tables + copy old":
+// idx's tables copied (rows widened to 2M / M) into tables sized for n_old + m nodes; then grow_graph_in_place.  idx is only read.
 // The derived tables (byte / split rows, locality codes) are the caller's.
-static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p,
-                              int64_t rem_scale, bool *rem_overflow, IndexPtr &out) {
+int hnsw_host::insert_graph(const hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p,
+                            int64_t rem_scale, bool *rem_overflow, IndexPtr &out) {
     *rem_overflow = false;
     out.reset();
     const IndexView &ov = idx->iv;
@@ -401,14 +456,7 @@ static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64
     const int M = p->num_connections, S0 = 2 * M, SU = M;
     const int S0o = ov.S0, SUo = ov.SU;
     const int64_t stride = ov.stride, rowsU_old = n_old > 0 ? ov.rowsU : 0;
-    const double level_mult = 1.0 / std::log((double)M);
-    std::vector<uint8_t> lvl((size_t)m);
-    for (int64_t j = 0; j < m; ++j) lvl[(size_t)j] = node_level(p->seed, n_old + j, level_mult);
-    int cur_max = n_old > 0 ? ov.max_layer : 0, entry = n_old > 0 ? ov.entry_point : 0;
-    int lcap = cur_max + 1;
-    for (uint8_t l : lvl) lcap = std::max(lcap, (int)l + 1);
-    std::vector<int2> ref;
-    const int64_t rowsU = upper_layout(lvl.data(), m, rowsU_old, ref);
+    const int64_t rowsU = grown_upper_rows(p, n_old, m, rowsU_old);
     if (rowsU > 0x7FFFFFF0LL) return fail(HNSW_ERR_UNSUPPORTED, "too many upper rows");
 
     IndexPtr nx(new hnsw_index());
@@ -416,8 +464,6 @@ static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64
     int rc;
     const IndexTables &ot = idx->tables;
     IndexTables &t = nx->tables;
-    IndexView &iv = nx->iv;
-    BuildView bv{};
     if ((rc = alloc_graph_tables(t, n, stride, S0, SU, rowsU))) return rc;
     if (n_old > 0) {
         HIP_TRY(hipMemcpy(t.X.p, ot.X.p, (size_t)n_old * stride * 4, hipMemcpyDeviceToDevice));
@@ -425,22 +471,12 @@ static int32_t insert_attempt(const hnsw_index *idx, const float *vectors, int64
         HIP_TRY(hipMemcpy(t.lvl.p, ot.lvl.p, (size_t)n_old, hipMemcpyDeviceToDevice));
         HIP_TRY(hipMemcpy(t.ref.p, ot.ref.p, (size_t)n_old * sizeof(int2), hipMemcpyDeviceToDevice));
     }
-    if ((rc = upload_rows(vectors, m, ov.d, row_stride, (float *)t.X.p + n_old * stride))) return rc;
-    // COSINE: the new rows only -- the old ones are N(X) already (row numbers in the message: of the m new vectors)
-    if (idx->info.metric == HNSW_METRIC_COSINE && (rc = cosine_store_rows((float *)t.X.p + n_old * stride, m, ov.d, "nothing inserted"))) return rc;
     HIP_TRY(widen_rows(ot.nbr0.p, n_old, S0o, t.nbr0.p, S0));
     HIP_TRY(widen_rows(ot.nbrU.p, rowsU_old, SUo, t.nbrU.p, SU));
-    if ((rc = upload_upper_layout(t, n_old, ref))) return rc;
-    iv = ov;                                                            // d, stride, nchunks, id_base
-    iv.n = n; iv.S0 = S0; iv.SU = SU; iv.rowsU = rowsU; iv.max_layer = cur_max; iv.entry_point = entry;
-    bind_view(nx.get());                                                // (the derived tables are the caller's)
-    bv.iv = iv; bv.nbr0_w = (int32_t *)t.nbr0.p; bv.nbrU_w = (int32_t *)t.nbrU.p;
-    if (n > 1 && (rc = run_batches(bv, lvl.data() + (n_old > 0 ? 0 : 1), std::max<int64_t>(n_old, 1), n, lcap, p, rem_scale,
-                                   rem_overflow, &cur_max, &entry))) return rc;
-    iv.max_layer = cur_max; iv.entry_point = entry;
+    nx->iv = ov;                                                        // d, stride, nchunks, id_base; n_old, top and entry
+    nx->iv.S0 = S0; nx->iv.SU = SU; nx->iv.rowsU = rowsU_old;
     nx->info = idx->info;                                               // d, metric, id_base, device
-    nx->info.max_degree = SU;
-    bind_view(nx.get());
+    if ((rc = grow_graph_in_place(nx.get(), vectors, m, row_stride, p, rem_scale, rem_overflow))) return rc;
     out = std::move(nx);
     return HNSW_OK;
 }
@@ -470,11 +506,11 @@ int32_t hnsw_index_insert(hnsw_index *idx, const float *vectors, int64_t m, int6
 
 } // extern "C"
 
-int hnsw_host::insert_vectors(hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p, const int64_t *keys) {
-    if (!idx || !p) return fail(HNSW_ERR_BAD_ARG, "null argument");
-    if (m < 0) return fail(HNSW_ERR_BAD_ARG, "m=%lld < 0", (long long)m);
-    if (m == 0) return HNSW_OK;
-    const int64_t n_old = idx->iv.n, n = n_old + m;
+// What hnsw_index_insert refuses of its arguments before anything is built (m > 0): idx holds n_old nodes with top layer max_layer
+// when the m vectors arrive -- its own, or, for the insert half of an upsert, what the removal half will leave.
+int hnsw_host::check_insert(const hnsw_index *idx, int64_t n_old, int max_layer, const float *vectors, int64_t m, int64_t row_stride,
+                            const hnsw_build_params *p) {
+    const int64_t n = n_old + m;
     if (!vectors) return fail(HNSW_ERR_BAD_ARG, "null vectors");
     if (n > 0x7FFFFFF0LL) return fail(HNSW_ERR_BAD_ARG, "n=%lld out of range", (long long)n);
     if (row_stride < idx->iv.d) return fail(HNSW_ERR_BAD_ARG, "row_stride=%lld < d=%d", (long long)row_stride, idx->iv.d);
@@ -484,7 +520,7 @@ int hnsw_host::insert_vectors(hnsw_index *idx, const float *vectors, int64_t m, 
     const int M = p->num_connections;
     if (n_old > 0 && idx->iv.S0 > 2 * M)
         return fail(HNSW_ERR_BAD_ARG, "max_degree0=%d of the index is wider than 2 * num_connections=%d", idx->iv.S0, 2 * M);
-    if (n_old > 0 && idx->iv.max_layer > 0 && idx->iv.SU > M)
+    if (n_old > 0 && max_layer > 0 && idx->iv.SU > M)
         return fail(HNSW_ERR_BAD_ARG, "max_degree=%d of the index is wider than num_connections=%d", idx->iv.SU, M);
     if (n_old > 0 && idx->iv.entry_point < 0) return fail(HNSW_ERR_BAD_ARG, "the index has nodes but no entry point");
     if (idx->live_requests > 0) return fail(HNSW_ERR_BAD_ARG, "%d submitted requests not waited for (hnsw_search_wait first)", idx->live_requests);
@@ -499,6 +535,15 @@ int hnsw_host::insert_vectors(hnsw_index *idx, const float *vectors, int64_t m, 
             for (int32_t j = 0; j < idx->iv.d; ++j)
                 if (!std::isfinite(vectors[i * row_stride + j]))
                     return fail(HNSW_ERR_UNSUPPORTED, "%s: value %d of new vector %lld is NaN or infinite: nothing inserted", codes_option(idx), j, (long long)i);
+    return HNSW_OK;
+}
+
+int hnsw_host::insert_vectors(hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p, const int64_t *keys) {
+    if (!idx || !p) return fail(HNSW_ERR_BAD_ARG, "null argument");
+    if (m < 0) return fail(HNSW_ERR_BAD_ARG, "m=%lld < 0", (long long)m);
+    if (m == 0) return HNSW_OK;
+    const int64_t n_old = idx->iv.n;
+    { const int32_t rcc = check_insert(idx, n_old, idx->iv.max_layer, vectors, m, row_stride, p); if (rcc) return rcc; }
     HIP_TRY(hipSetDevice(idx->device));
     if (n_old > 0) { const int32_t rcu = check_upper_rows(idx, "not grown"); if (rcu) return rcu; }
 
@@ -507,7 +552,7 @@ int hnsw_host::insert_vectors(hnsw_index *idx, const float *vectors, int64_t m, 
     int32_t rc = HNSW_OK;
     for (int64_t scale = 1; scale <= 64; scale *= 4) {
         bool overflow = false;
-        rc = insert_attempt(idx, vectors, m, row_stride, p, scale, &overflow, nx);
+        rc = insert_graph(idx, vectors, m, row_stride, p, scale, &overflow, nx);
         if (!overflow) break;
     }
     if (rc) {

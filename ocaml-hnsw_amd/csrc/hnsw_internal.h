@@ -11,6 +11,7 @@
 #include "hnsw_bits_plan.h"
 #include "hnsw_keys_plan.h"
 #include "hnsw_by_id_plan.h"
+#include "hnsw_upsert_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -677,6 +678,26 @@ int adopt_graph(::hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expec
 // hnsw_build.hip: hnsw_index_insert once the keyed question is settled: keys null on a handle without keys, else one per vector
 int insert_vectors(::hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p, const int64_t *keys);
 
+// hnsw_build.hip: what hnsw_index_insert refuses of its arguments before anything is built, for an index that holds n_old nodes with
+// top layer max_layer when the m vectors arrive (see there)
+int check_insert(const ::hnsw_index *idx, int64_t n_old, int max_layer, const float *vectors, int64_t m, int64_t row_stride,
+                 const hnsw_build_params *p);
+// hnsw_build.hip: the two parts of one insert attempt.  insert_graph: tables for idx's nodes + m, idx's graph copied into them,
+// then grow_graph_in_place, which inserts m vectors behind the nx->iv.n nodes nx holds in tables already sized for them
+// (grown_upper_rows: the upper rows that takes).  The upsert runs the second part alone on the tables its removal half filled.
+int64_t grown_upper_rows(const hnsw_build_params *p, int64_t n_old, int64_t m, int64_t rowsU_old);
+int grow_graph_in_place(::hnsw_index *nx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p,
+                        int64_t rem_scale, bool *rem_overflow);
+int insert_graph(const ::hnsw_index *idx, const float *vectors, int64_t m, int64_t row_stride, const hnsw_build_params *p,
+                 int64_t rem_scale, bool *rem_overflow, IndexPtr &out);
+// hnsw_remove.hip: one removal attempt: out = a new handle with the repaired graph of idx's live nodes, in tables sized for
+// n_tables nodes and rowsU_tables upper rows (see there).  idx is only read.
+int remove_graph(const ::hnsw_index *idx, const RemovePlan &plan, int64_t n_tables, int64_t rowsU_tables, IndexPtr &out);
+// hnsw_upsert.hip: hnsw_index_upsert_keyed / hnsw_index_update once the call's rows are split (UpsertPlan, |P| > 0): the removal of
+// P and the insert of the m vectors in front of ONE adopt_graph.  keys: one per vector on a keyed handle, else null.
+int upsert_vectors(::hnsw_index *idx, const UpsertPlan &up, const float *vectors, int64_t m, int64_t row_stride,
+                   const hnsw_build_params *p, const int64_t *keys);
+
 // hnsw_rows8.hip: if every value of tables.X is an integer in 0..255, build the byte copy (tables.X8, iv.stride8)
 int make_byte_rows(::hnsw_index *idx);
 // hnsw_rows16.hip: the half copy of tables.X (tables.Xh): HNSW_ERR_UNSUPPORTED, nothing allocated, when a value is NaN or
@@ -853,7 +874,8 @@ int count_filter(::hnsw_filter *f, const uint32_t *and_with);
 int renumbered_live_filter(const ::hnsw_index *idx, const int32_t *new_id, int64_t n_new, std::unique_ptr<::hnsw_filter> &out);
 // hnsw_keys.hip: the key tables an index of n_new nodes gets when nx replaces idx's graph (adopt_graph, before the swap), lookup
 // table included: new_id as above (keys_renumber_kernel; null: the old keys kept in place and append_keys, n_new - idx->iv.n of
-// them, behind).  out stays null when idx has no keys and none are appended.
+// them, behind).  Both at once (the upsert): the survivors under new_id and append_keys, n_new - survivors of them, behind the
+// survivors, in the same launch; one sort for the lookup table.  out stays null when idx has no keys and none are appended.
 int renumbered_keys(const ::hnsw_index *idx, const int32_t *new_id, int64_t n_new, const int64_t *append_keys, std::unique_ptr<KeyTables> &out);
 // hnsw_keys.hip: keys_translate_kernel on st: d_out[i] = the key of node d_ids[i] - id_base, or missing where that is no node (m entries)
 int keys_translate(const ::hnsw_index *idx, const int32_t *d_ids, int64_t m, int64_t missing, int64_t *d_out, hipStream_t st);

@@ -15,7 +15,8 @@
 //   keys_translate_kernel   one lane per result entry: out[i] = 0 <= ids[i] - id_base < n ? key_of[ids[i] - id_base] : missing.
 //                           The tail of every keyed search: nq k ids read, as many 8-byte stores, the gather from key_of (8 n bytes,
 //                           L2-resident at 1 M nodes).
-//   keys_renumber_kernel    new_key_of[new_id[v]] = key_of[v] for every surviving v.
+//   keys_renumber_kernel    new_key_of[new_id[v]] = key_of[v] for every surviving v; the lanes past n_old write the keys an upsert
+//                           appends behind the survivors (new_key_of[kept + i] = append[i]): one launch for both.
 //   keys_allow_kernel       sets the mask bits of a list of nodes (hnsw_filter_create_by_keys), as mark_bits_kernel does.
 #include "hnsw_internal.h"
 
@@ -60,10 +61,16 @@ keys_translate_kernel(const int64_t *key_of, int64_t n, int32_t id_base, const i
 }
 
 __global__ void __launch_bounds__(256)
-keys_renumber_kernel(const int64_t *key_of, const int32_t *new_id, int64_t n_old, int64_t n_new, int64_t *out) {
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n_old; v += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t j = new_id[v];            // 0-based, -1 = removed; survivors map one to one onto [0, n_new)
-        if (j >= 0 && j < n_new) out[j] = key_of[v];
+keys_renumber_kernel(const int64_t *key_of, const int32_t *new_id, int64_t n_old, int64_t n_new, int64_t *out, const int64_t *append,
+                     int64_t kept, int64_t n_append) {
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n_old + n_append; v += (int64_t)gridDim.x * blockDim.x) {
+        if (v < n_old) {
+            const int64_t j = new_id[v];        // 0-based, -1 = removed; survivors map one to one onto [0, kept), kept <= n_new
+            if (j >= 0 && j < n_new) out[j] = key_of[v];
+        } else {
+            const int64_t j = kept + (v - n_old);       // the appended keys, behind the survivors (kept + n_append == n_new: the host)
+            if (j < n_new) out[j] = append[v - n_old];
+        }
     }
 }
 
@@ -171,14 +178,24 @@ int renumbered_keys(const hnsw_index *idx, const int32_t *new_id, int64_t n_new,
     if (e != hipSuccess) return hip_fail(e, "key table allocation");
     int rc;
     if (new_id) {
-        if (n_old > 0 && n_new > 0) {
-            DevBuf d_new;
-            if ((rc = d_new.ensure((size_t)n_old * 4))) return rc;
-            HIP_TRY(hipMemcpy(d_new.p, new_id, (size_t)n_old * 4, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(hnsw_dev::keys_renumber_kernel, dim3(blocks_for(n_old)), dim3(256), 0, nullptr, (const int64_t *)idx->keys->key_of.p,
-                               (const int32_t *)d_new.p, n_old, n_new, (int64_t *)kt->key_of.p);
+        // the survivors keep their keys under new_id; append_keys (the upsert: both at once) go behind them in the same launch
+        const int64_t n_have = kept;                    // nodes that have a key to carry: none on a handle without keys
+        int64_t survivors = 0;
+        for (int64_t v = 0; v < n_have; ++v) survivors += new_id[v] >= 0;
+        const int64_t n_append = append_keys ? n_new - survivors : 0;
+        if (survivors + n_append != n_new || n_append < 0)
+            return fail(HNSW_ERR_BAD_ARG, "a keyed index must never hold a node without a key (%lld nodes, %lld keys)", (long long)n_new,
+                        (long long)(survivors + std::max<int64_t>(n_append, 0)));
+        if (n_new > 0) {
+            DevBuf d_new, d_app;
+            if ((rc = d_new.ensure((size_t)std::max<int64_t>(n_have, 1) * 4)) || (rc = d_app.ensure((size_t)std::max<int64_t>(n_append, 1) * 8))) return rc;
+            if (n_have > 0) HIP_TRY(hipMemcpy(d_new.p, new_id, (size_t)n_have * 4, hipMemcpyHostToDevice));
+            if (n_append > 0) HIP_TRY(hipMemcpy(d_app.p, append_keys, (size_t)n_append * 8, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(hnsw_dev::keys_renumber_kernel, dim3(blocks_for(n_have + n_append)), dim3(256), 0, nullptr,
+                               n_have > 0 ? (const int64_t *)idx->keys->key_of.p : nullptr, (const int32_t *)d_new.p, n_have, n_new,
+                               (int64_t *)kt->key_of.p, (const int64_t *)d_app.p, survivors, n_append);
             if ((rc = launched("keys renumber kernel"))) return rc;
-            HIP_TRY(hipDeviceSynchronize());        // (d_new is freed on return)
+            HIP_TRY(hipDeviceSynchronize());        // (d_new and d_app are freed on return)
         }
     } else {
         if (kept > 0) HIP_TRY(hipMemcpy(kt->key_of.p, idx->keys->key_of.p, (size_t)kept * 8, hipMemcpyDeviceToDevice));

@@ -13,12 +13,13 @@ using hnsw_dev::RemoveLayer;
 using hnsw_dev::RemoveView;
 using hnsw_dev::REMOVE_ROW;
 
-namespace {
-
 // One attempt: `out` = a new handle with the repaired graph of idx's live nodes (plan: remove_plan of idx's levels).  idx is only
-// read.  The derived tables are the caller's (adopt_graph).
-int32_t remove_attempt(const hnsw_index *idx, const RemovePlan &plan, IndexPtr &out) {
+// read.  The derived tables are the caller's (adopt_graph).  n_tables / rowsU_tables: the nodes and upper rows the new tables are
+// sized for -- plan.n / plan.rowsU for hnsw_index_remove; more for the removal half of an upsert, whose insert half grows the graph
+// on these same tables (grow_graph_in_place: the rows behind the live part stay empty here).
+int hnsw_host::remove_graph(const hnsw_index *idx, const RemovePlan &plan, int64_t n_tables, int64_t rowsU_tables, IndexPtr &out) {
     out.reset();
+    if (n_tables < plan.n || rowsU_tables < plan.rowsU) return fail(HNSW_ERR_BAD_ARG, "remove: tables smaller than the live graph");
     const hnsw_dev::IndexView &ov = idx->iv;
     const int64_t n_old = ov.n, n = plan.n;
     const int S0 = ov.S0, SU = ov.SU;
@@ -27,7 +28,7 @@ int32_t remove_attempt(const hnsw_index *idx, const RemovePlan &plan, IndexPtr &
     nx->device = idx->device;
     IndexTables &t = nx->tables;
     int rc;
-    if ((rc = alloc_graph_tables(t, n, ov.stride, S0, SU, plan.rowsU))) return rc;
+    if ((rc = alloc_graph_tables(t, n_tables, ov.stride, S0, SU, rowsU_tables))) return rc;
     if (n > 0) {
         std::vector<int2> ref((size_t)n);
         for (int64_t j = 0; j < n; ++j) ref[(size_t)j] = make_int2(plan.upper_row[(size_t)j], (int)plan.level[(size_t)j]);
@@ -118,8 +119,6 @@ int32_t remove_attempt(const hnsw_index *idx, const RemovePlan &plan, IndexPtr &
     return HNSW_OK;
 }
 
-} // namespace
-
 extern "C" int32_t hnsw_index_remove(hnsw_index *idx, const int64_t *ids, int64_t m, int32_t *out_new_id) {
     if (!idx) return fail(HNSW_ERR_BAD_ARG, "null index");
     if (m < 0) return fail(HNSW_ERR_BAD_ARG, "m=%lld < 0", (long long)m);
@@ -149,7 +148,7 @@ extern "C" int32_t hnsw_index_remove(hnsw_index *idx, const int64_t *ids, int64_
 
     // the shrunk graph, in tables of its own: on any error idx is as it was
     IndexPtr nx;
-    int32_t rc = remove_attempt(idx, plan, nx);
+    int32_t rc = remove_graph(idx, plan, plan.n, plan.rowsU, nx);
     if (rc) {
         nx.reset();
         (void)hipGetLastError();

@@ -10,6 +10,7 @@
 //                                                                                           hnsw_brute_force_batch_grouped)
 //   Hnsw::RangeResult, Hnsw::Ohnsw::range_search / brute_force_range                       (hnsw_range_*; with a Filter: the _filtered forms)
 //   Hnsw::Ohnsw::mark_deleted / unmark_deleted / deleted_count / deleted_mask / compact    (hnsw_index_mark_deleted ... hnsw_index_compact)
+//   Hnsw::Ohnsw::upsert_keyed / update                            hnsw_index_upsert_keyed / hnsw_index_update (replace or add, all or nothing)
 //   Hnsw::Ohnsw::set_keys / clear_keys / keys_info / keys_of / find_keys / knn_keyed / insert_keyed / remove_keys /
 //   mark_deleted_keys / unmark_deleted_keys, Hnsw::Filter::by_keys                         (hnsw_index_set_keys ... hnsw_filter_create_by_keys)
 //   Hnsw::Ohnsw::knn_by_id / knn_by_key / brute_force_by_id / knn_graph / rows_device      (hnsw_search_batch_by_id, hnsw_search_batch_by_key,
@@ -611,6 +612,32 @@ inline std::vector<int32_t> remove_keys(Hgraph &g, const std::vector<int64_t> &k
 }
 inline void mark_deleted_keys(Hgraph &g, const std::vector<int64_t> &keys) { check(hnsw_index_mark_deleted_keys(g.handle(), keys.data(), (int64_t)keys.size())); }
 inline void unmark_deleted_keys(Hgraph &g, const std::vector<int64_t> &keys) { check(hnsw_index_unmark_deleted_keys(g.handle(), keys.data(), (int64_t)keys.size())); }
+// Replace or add vectors by key in one all-or-nothing call (hnsw_index_upsert_keyed): vector i of `batch` becomes the vector under
+// keys[i], stored or not.  g afterwards is exactly what remove_keys(the stored ones among keys) + insert_keyed(batch, keys) leaves,
+// with one table swap and one epoch step; on any error it is exactly as before.  Two equal keys in the call are refused.
+struct Upserted { std::vector<uint8_t> replaced; std::vector<int32_t> new_id; };   // [m]: keys[i] was stored; [n_old]: as remove() returns it
+inline Upserted upsert_keyed(Hgraph &g, const Mat &batch, const std::vector<int64_t> &keys, int num_connections, int num_nodes_search_construction,
+                             uint64_t seed = 0, int max_batch = 0, int expected_ef = 0) {
+    if ((int64_t)keys.size() != batch.dim2) throw std::invalid_argument("upsert_keyed: one key per vector");
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    hnsw_build_params p{num_connections, num_nodes_search_construction, inf.metric, inf.id_base, seed, max_batch, 0, expected_ef, HNSW_SEM_OHNSW};
+    Upserted out{std::vector<uint8_t>(keys.size(), 0), std::vector<int32_t>((size_t)inf.n)};
+    check(hnsw_index_upsert_keyed(g.handle(), batch.data, keys.data(), batch.dim2, batch.dim1, &p, out.replaced.data(), out.new_id.data()));
+    return out;
+}
+// ... and for an index without keys (hnsw_index_update): the stored nodes `ids` (id_base-based, distinct) are replaced by the vectors
+// of `batch`: exactly remove(ids) + insert(batch).  An index with keys is refused.  Returns new_id as remove() does.
+inline std::vector<int32_t> update(Hgraph &g, const std::vector<int64_t> &ids, const Mat &batch, int num_connections, int num_nodes_search_construction,
+                                   uint64_t seed = 0, int max_batch = 0, int expected_ef = 0) {
+    if ((int64_t)ids.size() != batch.dim2) throw std::invalid_argument("update: one id per vector");
+    hnsw_index_info inf{};
+    check(hnsw_index_get_info(g.handle(), &inf));
+    hnsw_build_params p{num_connections, num_nodes_search_construction, inf.metric, inf.id_base, seed, max_batch, 0, expected_ef, HNSW_SEM_OHNSW};
+    std::vector<int32_t> new_id((size_t)inf.n);
+    check(hnsw_index_update(g.handle(), ids.data(), batch.data, batch.dim2, batch.dim1, &p, new_id.data()));
+    return new_id;
+}
 // ... and for ids already on the device, queued on `stream` (hnsw_index_keys_of_device)
 inline void keys_of_device(Hgraph &g, const int32_t *d_ids, int64_t m, int64_t missing, int64_t *d_out, void *stream = nullptr) {
     check(hnsw_index_keys_of_device(g.handle(), d_ids, m, missing, d_out, stream));

@@ -285,6 +285,12 @@ let hnsw_index_insert_keyed =
 let hnsw_index_remove_keys =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_remove_keys"
     (index @-> ptr int64_t @-> int64_t @-> ptr int32_t @-> returning int32_t)
+let hnsw_index_upsert_keyed =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_upsert_keyed"
+    (index @-> ptr float @-> ptr int64_t @-> int64_t @-> int64_t @-> ptr build_params @-> ptr uint8_t @-> ptr int32_t @-> returning int32_t)
+let hnsw_index_update =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_index_update"
+    (index @-> ptr int64_t @-> ptr float @-> int64_t @-> int64_t @-> ptr build_params @-> ptr int32_t @-> returning int32_t)
 let hnsw_index_mark_deleted_keys =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_mark_deleted_keys" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
 let hnsw_index_unmark_deleted_keys =
@@ -1379,6 +1385,51 @@ let insert_batch_keyed t (batch : Lacaml.S.mat) (keys : int array) ~num_connecti
   check (hnsw_index_insert_keyed t.handle (bigarray_start array2 batch) (Int64.of_int (A2.dim2 batch)) (Int64.of_int t.dim)
            (CArray.start (c_keys keys)) (addr b));
   Int64.to_int (getf inf ii_n) + Int32.to_int (getf inf ii_id_base)
+
+(* [upsert_batch_keyed t batch keys]: replace or add vectors by key in one all-or-nothing call (hnsw_index_upsert_keyed): column i of
+   [batch] becomes the vector under keys.(i), stored or not.  The index afterwards is exactly what [remove_keys] of the stored ones
+   among [keys] followed by [insert_batch_keyed t batch keys] leaves, with one table swap and one epoch step; on any error it is
+   exactly as before.  Two equal keys in the call are refused.  Returns (replaced, new_id): replaced.(i) = keys.(i) was stored;
+   new_id as [remove_batch] returns it (id_base - 1 for a replaced node). *)
+let upsert_build_params inf ~num_connections ~num_nodes_search_construction ~seed ~max_batch ~batch_div ~expected_ef ~expected_semantics =
+  let b = make build_params in
+  setf b b_num_connections (Int32.of_int num_connections); setf b b_efc (Int32.of_int num_nodes_search_construction);
+  setf b b_metric (getf inf ii_metric); setf b b_id_base (getf inf ii_id_base);
+  setf b b_seed (Unsigned.UInt64.of_int seed); setf b b_max_batch (Int32.of_int max_batch);
+  setf b b_batch_div (Int32.of_int batch_div);
+  setf b b_expected_ef (Int32.of_int expected_ef); setf b b_expected_semantics (Int32.of_int expected_semantics);
+  b
+let upsert_batch_keyed t (batch : Lacaml.S.mat) (keys : int array) ~num_connections ~num_nodes_search_construction ?(seed = 0)
+    ?(max_batch = 0) ?(batch_div = 0) ?(expected_ef = 0) ?(expected_semantics = 0) () : bool array * int array =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  if A2.dim1 batch <> t.dim then invalid_arg "upsert_batch_keyed: vectors of another dimension";
+  let m = A2.dim2 batch in
+  if Array.length keys <> m then invalid_arg "upsert_batch_keyed: one key per vector";
+  let b = upsert_build_params inf ~num_connections ~num_nodes_search_construction ~seed ~max_batch ~batch_div ~expected_ef ~expected_semantics in
+  let n_old = Int64.to_int (getf inf ii_n) in
+  let c_rep = CArray.make uint8_t (max m 1) and c_new = CArray.make int32_t (max n_old 1) in
+  check (hnsw_index_upsert_keyed t.handle (bigarray_start array2 batch) (CArray.start (c_keys keys)) (Int64.of_int m) (Int64.of_int t.dim)
+           (addr b) (CArray.start c_rep) (CArray.start c_new));
+  (Array.init m (fun i -> Unsigned.UInt8.to_int (CArray.get c_rep i) <> 0), Array.init n_old (fun v -> Int32.to_int (CArray.get c_new v)))
+
+(* [update_batch t ids batch]: the same for an index without keys (hnsw_index_update): the stored nodes [ids] (id_base-based,
+   distinct) are replaced by the columns of [batch]: exactly [remove_batch t ids] followed by [insert_batch t batch].  An index with
+   keys is refused.  Returns new_id as [remove_batch] does. *)
+let update_batch t (ids : int array) (batch : Lacaml.S.mat) ~num_connections ~num_nodes_search_construction ?(seed = 0)
+    ?(max_batch = 0) ?(batch_div = 0) ?(expected_ef = 0) ?(expected_semantics = 0) () : int array =
+  let inf = make index_info in
+  check (hnsw_index_get_info t.handle (addr inf));
+  if A2.dim1 batch <> t.dim then invalid_arg "update_batch: vectors of another dimension";
+  let m = A2.dim2 batch in
+  if Array.length ids <> m then invalid_arg "update_batch: one id per vector";
+  let b = upsert_build_params inf ~num_connections ~num_nodes_search_construction ~seed ~max_batch ~batch_div ~expected_ef ~expected_semantics in
+  let n_old = Int64.to_int (getf inf ii_n) in
+  let c_ids = CArray.make int64_t (max m 1) and c_new = CArray.make int32_t (max n_old 1) in
+  Array.iteri (fun i v -> CArray.set c_ids i (Int64.of_int v)) ids;
+  check (hnsw_index_update t.handle (CArray.start c_ids) (bigarray_start array2 batch) (Int64.of_int m) (Int64.of_int t.dim) (addr b)
+           (CArray.start c_new));
+  Array.init n_old (fun v -> Int32.to_int (CArray.get c_new v))
 
 (* [remove_keys] / [mark_deleted_keys] / [unmark_deleted_keys]: [remove_batch] / [mark_deleted] / [unmark_deleted] of the nodes
    with these keys; an absent key refuses the call and nothing is changed.  [filter_by_keys]: an ordinary [filter] that allows
