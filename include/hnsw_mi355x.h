@@ -65,6 +65,7 @@
 #ifndef HNSW_MI355X_H
 #define HNSW_MI355X_H
 
+#include <math.h>   /* INFINITY: HNSW_CURSOR_START */
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -1623,6 +1624,64 @@ int32_t hnsw_index_upsert_keyed(hnsw_index *idx, const float *vectors, const int
                                 int32_t *out_new_id /* optional [n_old] */);
 int32_t hnsw_index_update(hnsw_index *idx, const int64_t *ids, const float *vectors, int64_t m, int64_t row_stride,
                           const hnsw_build_params *params, int32_t *out_new_id /* optional [n_old] */);
+
+/* #### paged k-NN search: the NEXT k after a (distance, id) cursor ####
+ * "Ten more, please."  hnsw_search_batch answers the k nearest with k <= ef <= 1024; past that it has no answer, and a caller who
+ * pages by asking for a larger k throws the head away each time.  These two calls take, per query, a CURSOR -- the (distance, id)
+ * of the last result the caller holds -- and return the k results that come after it.
+ *
+ * 0. ORDER.  D(q, v) is the float hnsw_distance_batch returns for the pair: over the float32 rows whatever row_format says, under
+ *    HNSW_METRIC_COSINE over N(X) with N(q).  ord(x) is the monotone map of a float's bits that puts -0 below +0 and a positive NaN
+ *    above +inf (the sign bit flipped, a negative value's other bits too).  The PAGED ORDER is (ord(D), node id).  It orders by what
+ *    the caller holds: hnsw_brute_force_batch orders by (key, id), and for L2 the key is the squared sum BEFORE the square root,
+ *    which maps two to three neighbouring sums onto one float -- a caller never sees keys, so a cursor cannot name one.  The paged
+ *    order is a coarsening of that order and differs from it only among nodes whose returned L2 distances are equal while their
+ *    squared sums are not; under inner product and cosine the two coincide.
+ *    Node v is AFTER cursor c iff ord(D) > ord(c.dist), or they are equal and v + id_base > c.id, the ids compared in 64 bits.  Any
+ *    c.id is legal: {r, INT32_MAX} means "strictly beyond distance r", {r, id_base - 1} "from distance r on"; HNSW_CURSOR_START is
+ *    before every node.  after == NULL: HNSW_CURSOR_START for every query.  A NaN c.dist is HNSW_ERR_BAD_ARG, found on the host
+ *    before any launch.
+ * 1. ELIGIBLE: a node that is after the query's cursor, is allowed by f when f is given, and is not marked deleted (the live mask
+ *    is ANDed as every filtered call does).
+ * 2. hnsw_brute_force_batch_after: row q is the first k eligible nodes under the paged order, the rest filled per `fill` (id -1;
+ *    NaN or +inf).  It needs no graph; n = 0 is HNSW_OK with filled rows; the k limits are those of hnsw_brute_force_batch.  The
+ *    result never depends on option scan_slabs or on the row format.
+ * 3. hnsw_search_batch_after: W_e(q) is as the range section defines it -- hnsw_search_batch at (ef = e, k = e), the host form;
+ *    under inexact rows (half rows, codes) all its members re-ranked with k := e.  A_e(q) is the eligible members of W_e(q).
+ *    LADDER: e_0 = ef, e_{j+1} = min(1024, 2 e_j); a query is served at the first stage with |A_e| >= k, and its row is the first k
+ *    of A_e UNDER THE PAGED ORDER (W ascends in (key, id), so D is non-decreasing along it: only runs of equal D have their ids put
+ *    in order).  Only the queries still short are walked again, as one compacted batch in ascending query order.  EXACT STAGE: a
+ *    query still short at e = 1024 -- and every query when fewer than k nodes are allowed at all -- gets the row of point 2; its
+ *    out_stage is 0xFFFFFFFF.  The walk is never modified.
+ * 4. out_next[q] (optional) is (distance, id) of the row's last real entry, the input cursor when the row has none.  A row with
+ *    fewer than k real entries always comes from the exact stage, so it means "exhausted".
+ * 5. CONSEQUENCES.  Pages fetched by feeding out_next back are pairwise disjoint and ascending across pages; those pages of the
+ *    brute-force form, concatenated, are the full paged order; with the start cursor a query served at stage 0 has the multiset of
+ *    hnsw_search_batch's row, and that row bit for bit where the row's distances are distinct (rows whose walk distances are exact
+ *    over the float32 rows: float32, byte and split rows; under half rows and codes the row is that of the re-ranked W_ef).
+ * 6. COUNTERS are those of hnsw_search_batch_filtered: the evaluations and hops of every stage walked (inexact rows: plus the
+ *    re-ranked members), the stage that served the query; the exact stage adds the number of allowed live nodes.  ERRORS are those
+ *    of hnsw_search_batch_filtered -- k > ef, ef > 1024, HNSW_SEM_FUNCTOR_NEAREST_K, an empty index for the graph form, a stale or
+ *    foreign filter, strides, null buffers; nq == 0 is a no-op -- and outputs are untouched on error.
+ * 7. DETERMINISM: a row depends on the query's vector, its cursor, the mask and (ef, k, semantics) only -- not on the batch.
+ * 8. Scratch is the handle's: one filtered, range or paged call in flight per handle.  The cursors are host arrays, 8 bytes per
+ *    query, uploaded with the call.
+ * 9. NOT BUILT: device-pointer forms; per-query filters; keyed output (hnsw_index_keys_of turns the ids into keys); the
+ *    hnsw_sharded and hnsw_multi forms; cursors that survive hnsw_index_remove, hnsw_index_compact or an upsert -- those calls
+ *    RENUMBER the nodes, and a cursor names a position by id.
+ * 10. COST, plainly: results past about rank 1024 - k are exact-scan results (a pass over the whole table per page), and the last,
+ *    short page walks the whole ladder first.  Rates: tools/after_rate.py, profiles/after.txt. */
+typedef struct hnsw_cursor { float dist; int32_t id; } hnsw_cursor;   /* id: id_base-based */
+#define HNSW_CURSOR_START { -INFINITY, INT32_MIN }                     /* an initialiser: before every node */
+
+int32_t hnsw_search_batch_after(hnsw_index *idx, const hnsw_filter *f /* may be NULL */,
+                                const hnsw_cursor *after /* [nq]; NULL: HNSW_CURSOR_START for every query */, const float *queries,
+                                int64_t nq, int64_t q_stride, const hnsw_search_params *params, int32_t *out_ids, float *out_dist,
+                                hnsw_cursor *out_next /* optional [nq] */, uint32_t *out_ndist, uint32_t *out_nhops,
+                                uint32_t *out_stage /* each optional */);
+int32_t hnsw_brute_force_batch_after(hnsw_index *idx, const hnsw_filter *f /* may be NULL */, const hnsw_cursor *after,
+                                     const float *queries, int64_t nq, int64_t q_stride, int32_t k, int32_t fill, int32_t *out_ids,
+                                     float *out_dist, hnsw_cursor *out_next /* optional [nq] */);
 
 #ifdef __cplusplus
 }

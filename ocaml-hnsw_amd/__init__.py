@@ -167,6 +167,8 @@ _ABI = {
     "hnsw_knn_graph": [_vp, _vp, _i32, _vp, _vp],
     "hnsw_index_upsert_keyed": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "hnsw_index_update": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "hnsw_search_batch_after": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_brute_force_batch_after": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -981,6 +983,49 @@ def _search_filtered(hgraph, flt, batch, ef, k, fill, counters=False, sem=0, out
     return (ids, dist, nd, nh, stage) if counters else (ids, dist)
 
 
+CURSOR_DTYPE = _np.dtype([("dist", "<f4"), ("id", "<i4")])     # hnsw_cursor: the (distance, id) a page ends at
+CURSOR_START = _np.array((-_np.inf, -2 ** 31), dtype=CURSOR_DTYPE)[()]   # HNSW_CURSOR_START: before every node
+
+
+def _cursors(after, nq):
+    """the cursors of a paged call as the library reads them: None (the start cursor for every query), one cursor for all, or [nq]"""
+    if after is None:
+        return None
+    a = _np.asarray(after, dtype=CURSOR_DTYPE)
+    if a.ndim == 0:
+        a = _np.full(nq, a, dtype=CURSOR_DTYPE)
+    if a.shape != (nq,):
+        raise InvalidArgument("after must be one cursor per query: [nq] of dtype CURSOR_DTYPE")
+    return _np.ascontiguousarray(a)
+
+
+def _search_after(hgraph, batch, after, ef, k, fill, counters=False, sem=0, flt=None):
+    """hnsw_search_batch_after (ef None: hnsw_brute_force_batch_after); flt: None, a Filter, or what Hgraph.filter takes
+    -> (ids, dist, next), with counters (ids, dist, next, ndist, nhops, stage)."""
+    own = None if flt is None or isinstance(flt, Filter) else Filter(hgraph, flt)
+    try:
+        f = None if flt is None else (own or flt).handle
+        Q, qs, nq = _batch(hgraph.d, batch)
+        cur = _cursors(after, nq)
+        ids, dist = _out_pair(nq, int(k), None)
+        nxt = _np.empty(nq, CURSOR_DTYPE)
+        if ef is None:
+            if counters:
+                raise InvalidArgument("the brute-force form has no counters")
+            _check(load().hnsw_brute_force_batch_after(hgraph.handle, f, _ptr(cur), _ptr(Q), nq, qs, int(k), fill, _ptr(ids), _ptr(dist), _ptr(nxt)))
+            return ids, dist, nxt
+        nd = _np.zeros(nq, _np.uint32) if counters else None
+        nh = _np.zeros(nq, _np.uint32) if counters else None
+        stage = _np.zeros(nq, _np.uint32) if counters else None
+        p = _SearchParams(ef, k, fill, sem)
+        _check(load().hnsw_search_batch_after(hgraph.handle, f, _ptr(cur), _ptr(Q), nq, qs, _C.byref(p), _ptr(ids), _ptr(dist), _ptr(nxt),
+                                              _ptr(nd), _ptr(nh), _ptr(stage)))
+    finally:
+        if own is not None:
+            own.release()
+    return (ids, dist, nxt, nd, nh, stage) if counters else (ids, dist, nxt)
+
+
 def _search_keyed(hgraph, batch, ef, k, fill, counters=False, sem=0, flt=None, missing=MISSING_KEY):
     """hnsw_search_batch_keyed; flt: None, a Filter, or what Hgraph.filter takes
     -> (keys, dist), with counters (keys, dist, ndist, nhops, stage)."""
@@ -1289,6 +1334,43 @@ class Ohnsw:
         return _search_keyed(hgraph, batch, k if ef is None else ef, k, FILL_OHNSW, counters, flt=filter, missing=missing)
 
     @staticmethod
+    def knn_batch_after(hgraph, k, batch, after=None, ef=None, filter=None, counters=False):
+        """The NEXT k: knn_batch_bigarray's results that come after a cursor (hnsw_search_batch_after) -> (ids, distances, next), with
+        counters (ids, distances, next, ndist, nhops, stage).  after: one (distance, id) per query (CURSOR_DTYPE; None: CURSOR_START,
+        the first page) -- feed `next` back for the page after.  The order is (distance, id) over the returned float distances.  W
+        grows ef, 2 ef, ... 1024 until it holds k nodes after the cursor; a query still short gets the exact paged scan (stage =
+        STAGE_EXACT), so a row with fewer than k real entries means "exhausted".  filter (a Filter, or what Hgraph.filter takes):
+        only allowed nodes count.  Cursors do not survive remove_batch, compact or an upsert: those renumber the nodes."""
+        return _search_after(hgraph, batch, after, k if ef is None else ef, k, FILL_OHNSW, counters, flt=filter)
+
+    @staticmethod
+    def brute_force_after(hgraph, k, batch, after=None, filter=None, fill=FILL_OHNSW):
+        """The exact form of knn_batch_after (hnsw_brute_force_batch_after) -> (ids, distances, next): per query the first k nodes
+        after its cursor under (distance, id) over all n vectors, allowed by `filter` if given.  Needs no graph; each page is one
+        pass over the table."""
+        return _search_after(hgraph, batch, after, None, k, fill, flt=filter)
+
+    @staticmethod
+    def knn_pages(hgraph, k, batch, ef=None, filter=None, exact=False):
+        """A generator over the pages of knn_batch_after (exact=True: of brute_force_after), from the start cursor on: yields (ids,
+        distances, next) and stops after the page on which every row is exhausted (has fewer than k real entries)."""
+        own = None if filter is None or isinstance(filter, Filter) else Filter(hgraph, filter)
+        try:
+            cur = None
+            while True:
+                if exact:
+                    page = Ohnsw.brute_force_after(hgraph, k, batch, cur, filter=own or filter)
+                else:
+                    page = Ohnsw.knn_batch_after(hgraph, k, batch, cur, ef=ef, filter=own or filter)
+                yield page
+                if ((page[0] >= hgraph.id_base).sum(axis=1) < k).all():
+                    return
+                cur = page[2]
+        finally:
+            if own is not None:
+                own.release()
+
+    @staticmethod
     def knn_batch_by_id(hgraph, k, ids, ef=None, exclude_self=True, counters=False, out=None):
         """knn_batch_bigarray with the stored vectors of the nodes `ids` as the queries (hnsw_search_batch_by_id) -> (ids, distances),
         with counters (ids, distances, ndist, nhops).  Only the ids cross the link: the rows are gathered on the device.
@@ -1587,6 +1669,12 @@ class Ba:
         """knn_batch answered in the index's keys (see Ohnsw.knn_batch_keyed; the functor accept rule, +inf / `missing` where fewer
         than k were found) -> (keys, distances), with counters (..., ndist, nhops, stage)."""
         return _search_keyed(hgraph, batch, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR, flt=filter, missing=missing)
+
+    @staticmethod
+    def knn_batch_after(hgraph, batch, num_neighbours_search, num_neighbours, after=None, filter=None, counters=False):
+        """knn_batch's results that come after a cursor (see Ohnsw.knn_batch_after; the functor accept rule, +inf where a row is
+        exhausted) -> (ids, distances, next)."""
+        return _search_after(hgraph, batch, after, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR, flt=filter)
 
     @staticmethod
     def knn_batch_by_id(hgraph, ids, num_neighbours_search, num_neighbours, exclude_self=True, counters=False):

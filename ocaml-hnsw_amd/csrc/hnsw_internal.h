@@ -365,6 +365,11 @@ struct GroupBufs {
     DevBuf lab, rlab;                    // out_labels [nq][k]; the labels column of a compact [m][k] result
     DevBuf part_words, part_lab;         // ... of a row of many cells: the k smallest words of each of its stripes and their labels
 };
+// ... of the paged calls (hnsw_after.hip), beside the ladder's and the filtered search's buffers, which they use too
+struct AfterBufs {
+    DevBuf lo;                           // the cursors as bounds in word space (uint64 [nq], by query)
+    DevBuf cand, cdist, rnd;             // half rows / codes: one stage's walk before its re-rank; its evaluations after it
+};
 // ... of the range calls.  What a caller keeps (lims, ids, distances, counters) belongs to the hnsw_range_result instead.
 constexpr int RANGE_STAGES = 11;         // the longest ladder: ef = 1, 2, 4, ... 1024
 struct RangeBufs {
@@ -580,6 +585,7 @@ struct hnsw_index {
     hnsw_host::FilterBufs filter_scratch;
     hnsw_host::RangeBufs range_scratch;
     hnsw_host::GroupBufs group_scratch;  // the grouped calls: they share ladder_scratch and filter_scratch with the filtered call
+    hnsw_host::AfterBufs after_scratch;  // the paged calls (hnsw_after.hip): likewise
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica) or an hnsw_sharded (hnsw_sharded_shard): not grown or shrunk on its own (hnsw_index_insert, hnsw_index_remove)
     // the graph epoch: every successful hnsw_index_insert and hnsw_index_remove moves it on (adopt_graph).  A filter records the
     // epoch it was made in: n alone would let a mask through after "remove 5, insert 5"

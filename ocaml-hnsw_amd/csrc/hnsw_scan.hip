@@ -22,57 +22,7 @@
 
 namespace hnsw_dev {
 
-constexpr int SCAN_BUF = 64;           // survivor words per query and wave (LDS)
-constexpr uint64_t SCAN_EMPTY = ~0ull; // no candidate: above every real word
-
-struct ScanArgs {
-    const float *Q;        // the queries of this launch
-    int64_t q_stride, nq;
-    int32_t k, n_slabs;
-    int64_t slab_rows;     // slab s = rows [s * slab_rows, min(n, (s + 1) * slab_rows))
-    uint64_t *lists;       // [nq][n_slabs][2][k]: the first half holds the result
-};
-
-// what one lane wrote to LDS or global memory, seen by the other lanes of its wave
-__device__ __forceinline__ void scan_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ uint64_t scan_uniform64(uint64_t v) {
-    return ((uint64_t)(uint32_t)uniform((int)(v >> 32)) << 32) | (uint32_t)uniform((int)(uint32_t)v);
-}
-// number of words below e in the ascending words p[0 .. n)
-__device__ __forceinline__ int scan_lower_bound(const uint64_t *p, int n, uint64_t e) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (p[mid] < e) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// Merges the cnt (<= 64, distinct) words of buf into the ascending list cur[0 .. k) (padded with SCAN_EMPTY); the k smallest of
-// the union go to oth[0 .. k), ascending and padded.  sorted: 64 words of LDS scratch.  The words are distinct (a node occurs
-// once), so a word's place in the union is its place in its own sequence plus the number of smaller words in the other one.
-__device__ __forceinline__ void scan_flush(const uint64_t *buf, uint64_t *sorted, int cnt, const uint64_t *cur, uint64_t *oth,
-                                           int k, int lane) {
-    scan_wave_sync();
-    const uint64_t e = lane < cnt ? buf[lane] : SCAN_EMPTY;
-    int rank = 0;
-    for (int j = 0; j < cnt; ++j) rank += buf[j] < e ? 1 : 0;
-    if (lane < cnt) sorted[rank] = e;
-    scan_wave_sync();
-    if (lane < cnt) {
-        const int pos = rank + scan_lower_bound(cur, k, e);
-        if (pos < k) oth[pos] = e;
-    }
-    for (int j = lane; j < k; j += 64) {
-        const uint64_t le = cur[j];
-        const int pos = j + scan_lower_bound(sorted, cnt, le);   // (padding: all cnt words are below it)
-        if (pos < k) oth[pos] = le;
-    }
-    scan_wave_sync();
-}
+// (SCAN_BUF, SCAN_EMPTY, ScanArgs, scan_flush and its helpers: hnsw_scan_device.hip.h -- the paged scan, hnsw_after.hip, keeps its lists the same way)
 
 // The top-k selection of one (tile, slab) wave (scan_slab's Select).  MASKED: `mask` holds one bit per row, bit row & 31 of word
 // row >> 5, ceil(n / 32) words; a row whose bit is clear contributes no candidate, and a 32-row word without a set bit is stepped

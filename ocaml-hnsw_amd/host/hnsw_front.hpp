@@ -16,6 +16,7 @@
 //   Hnsw::Ohnsw::knn_by_id / knn_by_key / brute_force_by_id / knn_graph / rows_device      (hnsw_search_batch_by_id, hnsw_search_batch_by_key,
 //                                                                                           hnsw_brute_force_batch_by_id, hnsw_knn_graph,
 //                                                                                           hnsw_index_get_rows_device)
+//   Hnsw::Cursor, Hnsw::Ohnsw::knn_after / brute_force_after                               (hnsw_search_batch_after, hnsw_brute_force_batch_after)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
@@ -294,6 +295,14 @@ private:
 
 // Hgraph.Stats (lib/hnsw.ml:353-375): per layer its size and the mima record {min; max; mean; isolated}; `isolated` is the
 // reference's list -- node ids, descending (consed during the ascending fold of min_max_connectivity).
+// a position in the paged order (hnsw_cursor): the (distance, id) of the last result a caller holds; start(): before every node
+struct Cursor : hnsw_cursor {
+    Cursor() : hnsw_cursor(HNSW_CURSOR_START) {}
+    Cursor(float dist_, int32_t id_) : hnsw_cursor{dist_, id_} {}
+    static Cursor start() { return Cursor(); }
+};
+static_assert(sizeof(Cursor) == sizeof(hnsw_cursor), "Hnsw::Cursor is laid out as hnsw_cursor");
+
 namespace Stats {
 struct mima { int min, max; double mean; std::vector<int64_t> isolated; };
 struct t { int64_t num_nodes; std::vector<int64_t> layer_sizes; std::vector<mima> layer_connectivity; };
@@ -690,6 +699,39 @@ inline std::pair<std::vector<int32_t>, std::vector<float>> knn_graph(const Hgrap
 // (hnsw_index_get_rows_device); an id outside the index gives a row of zeros
 inline void rows_device(Hgraph &g, const int32_t *d_ids, int64_t m, float *d_out, int64_t out_stride, void *stream = nullptr) {
     check(hnsw_index_get_rows_device(g.handle(), d_ids, m, d_out, out_stride, stream));
+}
+
+// ---- paged search: the NEXT k after a (distance, id) cursor (the definition: include/hnsw_mi355x.h, the last section) ----
+// knn_after (hnsw_search_batch_after): `after` holds one cursor per query (empty: Cursor::start() for all, the first page); the
+// order is (distance, id) over the returned float distances.  W grows ef, 2 ef, ... 1024 until it holds k nodes after the cursor
+// (stage[q] = how often it doubled); a query still short gets the exact paged scan (exact_stage).  next[q] is the cursor to hand
+// back for the page after; a row with fewer than k real entries means "exhausted".  f (optional): only allowed nodes count.
+// Cursors do not survive remove(), compact() or an upsert: those renumber the nodes.
+struct Paged {
+    static constexpr uint32_t exact_stage = 0xFFFFFFFFu;
+    std::vector<int32_t> ids; std::vector<float> dist; std::vector<Cursor> next; std::vector<uint32_t> stage;
+};
+inline Paged knn_after(const Hgraph &g, int k, const Mat &batch, const std::vector<Cursor> &after = {}, int ef = 0, const Filter *f = nullptr,
+                       int sem = HNSW_SEM_OHNSW, int fill = HNSW_FILL_OHNSW) {
+    const size_t nq = (size_t)batch.dim2;
+    if (!after.empty() && after.size() != nq) throw std::invalid_argument("knn_after: one cursor per query");
+    Paged out{std::vector<int32_t>(nq * (size_t)(k > 0 ? k : 0), -1), std::vector<float>(nq * (size_t)(k > 0 ? k : 0), 0.f),
+              std::vector<Cursor>(nq, Cursor::start()), std::vector<uint32_t>(nq, 0u)};
+    hnsw_search_params p{ef > 0 ? ef : k, k, fill, sem};
+    check(hnsw_search_batch_after(g.handle(), f ? f->handle() : nullptr, after.empty() ? nullptr : after.data(), batch.data, batch.dim2, batch.dim1,
+                                  &p, out.ids.data(), out.dist.data(), out.next.data(), nullptr, nullptr, out.stage.data()));
+    return out;
+}
+// ... the exact form (hnsw_brute_force_batch_after): the first k nodes after each cursor over all stored vectors; needs no graph
+inline Paged brute_force_after(const Hgraph &g, int k, const Mat &batch, const std::vector<Cursor> &after = {}, const Filter *f = nullptr,
+                               int fill = HNSW_FILL_OHNSW) {
+    const size_t nq = (size_t)batch.dim2;
+    if (!after.empty() && after.size() != nq) throw std::invalid_argument("brute_force_after: one cursor per query");
+    Paged out{std::vector<int32_t>(nq * (size_t)(k > 0 ? k : 0), -1), std::vector<float>(nq * (size_t)(k > 0 ? k : 0), 0.f),
+              std::vector<Cursor>(nq, Cursor::start()), std::vector<uint32_t>(nq, Paged::exact_stage)};
+    check(hnsw_brute_force_batch_after(g.handle(), f ? f->handle() : nullptr, after.empty() ? nullptr : after.data(), batch.data, batch.dim2,
+                                       batch.dim1, k, fill, out.ids.data(), out.dist.data(), out.next.data()));
+    return out;
 }
 
 // The exact re-rank (hnsw_rerank_batch): for each query the k nearest of ITS candidates cand[q][0 .. cand_stride) (entries below

@@ -316,6 +316,20 @@ let hnsw_brute_force_batch_by_id =
 let hnsw_knn_graph =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_knn_graph"
     (index @-> ptr search_params @-> int32_t @-> ptr int32_t @-> ptr float @-> returning int32_t)
+(* paged search (see the C header, the last section): the next k after a (distance, id) cursor *)
+type cursor
+let cursor : cursor structure typ = structure "hnsw_cursor"
+let cu_dist = field cursor "dist" float
+let cu_id = field cursor "id" int32_t
+let () = seal cursor
+let hnsw_search_batch_after =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_after"
+    (index @-> filter_handle @-> ptr cursor @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> ptr int32_t @-> ptr float
+     @-> ptr cursor @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+let hnsw_brute_force_batch_after =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_brute_force_batch_after"
+    (index @-> filter_handle @-> ptr cursor @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float
+     @-> ptr cursor @-> returning int32_t)
 let hnsw_index_deleted_count = foreign ~from:lib "hnsw_index_deleted_count" (index @-> ptr int64_t @-> returning int32_t)
 let hnsw_index_deleted_bits = foreign ~from:lib "hnsw_index_deleted_bits" (index @-> ptr uint32_t @-> returning int32_t)
 let hnsw_index_compact =
@@ -1366,6 +1380,53 @@ let knn_graph ?(semantics = 0) ?(fill = 0) ?(exact = false) (t : t) ~ef ~k : int
   check (hnsw_knn_graph t.handle (addr p) (if exact then 1l else 0l) (CArray.start out) (CArray.start dist));
   (Array.init n (fun v -> Array.init k (fun j -> Int32.to_int (CArray.get out (v * k + j)))),
    Array.init n (fun v -> Array.init k (fun j -> CArray.get dist (v * k + j))))
+
+(* Paged search (hnsw_search_batch_after, hnsw_brute_force_batch_after): the NEXT k after a cursor.  A cursor is the (distance, id)
+   of the last result the caller holds; [cursor_start] is before every node.  The order is (distance, id) over the returned float
+   distances.  [knn_batch_after t batch ~ef ~k]: ?after one cursor per query (default: the first page) -> (ids, distances, next,
+   stages): W grows ef, 2 ef, ... 1024 until it holds k nodes after the cursor (stages.(q) = how often it doubled), a query still
+   short gets the exact paged scan (-1); next.(q) is the cursor to hand back for the page after, and a row with fewer than k real
+   entries means "exhausted".  ?filter: only allowed nodes count.  [brute_force_after]: the exact form, one pass over the table per
+   page, no graph needed.  Cursors do not survive [remove], [compact] or an upsert: those renumber the nodes. *)
+let cursor_start : float * int = (neg_infinity, Int32.to_int Int32.min_int)
+let c_cursors (after : (float * int) array option) nq =
+  let c = CArray.make cursor (max 1 nq) in
+  (match after with
+   | Some a ->
+     if Array.length a <> nq then invalid_arg "after: one cursor per query";
+     Array.iteri (fun q (d, i) -> let e = CArray.get c q in setf e cu_dist d; setf e cu_id (Int32.of_int i); CArray.set c q e) a
+   | None ->
+     for q = 0 to nq - 1 do
+       let e = CArray.get c q in
+       setf e cu_dist (fst cursor_start); setf e cu_id Int32.min_int; CArray.set c q e
+     done);
+  c
+let cursors_out c nq = Array.init nq (fun q -> let e = CArray.get c q in (getf e cu_dist, Int32.to_int (getf e cu_id)))
+let knn_batch_after ?(semantics = 0) ?(fill = 0) ?filter ?after (t : t) (batch : Lacaml.S.mat) ~ef ~k :
+  int array array * float array array * (float * int) array * int array =
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let stage = CArray.make uint32_t (max 1 nq) and next = CArray.make cursor (max 1 nq) in
+  let p = by_id_params ~semantics ~fill ~ef ~k in
+  let fh = match filter with Some (f : filter) -> f.f_handle | None -> null in
+  check (hnsw_search_batch_after t.handle fh (CArray.start (c_cursors after nq)) (bigarray_start array2 batch) (Int64.of_int nq)
+           (Int64.of_int t.dim) (addr p) (CArray.start ids) (CArray.start dist) (CArray.start next) (from_voidp uint32_t null)
+           (from_voidp uint32_t null) (CArray.start stage));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
+   cursors_out next nq,
+   Array.init nq (fun q -> let s = Unsigned.UInt32.to_int (CArray.get stage q) in if s = 0xFFFFFFFF then -1 else s))
+let brute_force_after ?(fill = 0) ?filter ?after (t : t) (batch : Lacaml.S.mat) ~k :
+  int array array * float array array * (float * int) array =
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let next = CArray.make cursor (max 1 nq) in
+  let fh = match filter with Some (f : filter) -> f.f_handle | None -> null in
+  check (hnsw_brute_force_batch_after t.handle fh (CArray.start (c_cursors after nq)) (bigarray_start array2 batch) (Int64.of_int nq)
+           (Int64.of_int t.dim) (Int32.of_int k) (Int32.of_int fill) (CArray.start ids) (CArray.start dist) (CArray.start next));
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
+   cursors_out next nq)
 
 (* [insert_batch_keyed t batch keys]: [insert_batch] into an index that owns keys (hnsw_index_insert_keyed), keys.(i) naming
    column i of [batch].  A stored or repeated key refuses the call before anything is built; an empty index without keys starts
