@@ -2,8 +2,8 @@
 // hnsw_brute_force_batch_after).  The order is the one a caller can hold: (ord(returned float distance), node id) -- a coarsening
 // of the exact scan's (key, id), from which it differs only among nodes whose L2 distances are equal while their squared sums are
 // not (hnsw_after_plan.h: ord, the word of a pair, the cursor as a bound in word space).  The search composes pieces that exist
-// already -- the unchanged walk (knn_search with k := ef: W stays on the device), the ladder (Ladder, hnsw_filter.hip), the re-rank
-// kernel with k := e (hnsw_rerank.hip), the exact scan's body (hnsw_scan_device.hip.h) -- with one select rule and one selection policy:
+// already -- the ladder's loop and its W over the float32 rows (Ladder::run, Ladder::walk_exact, hnsw_filter.hip), the exact scan's body
+// (hnsw_scan_device.hip.h), the host frame (ladder_host_call) -- with one stage body, one select rule and one selection policy:
 //   ladder   e = ef, 2 ef, ... 1024: a query is served at the first e whose W holds k ELIGIBLE members (after its cursor, allowed,
 //            live); its row is the first k of them under the paged order.  Only the queries still short are walked again;
 //   exact    a query still short at e = 1024, every query when fewer than k nodes are allowed, and every query of the brute-force
@@ -23,8 +23,8 @@
 //   after_merge_kernel<METRIC>  hnsw_scan_merge_kernel over distance-words: one workgroup per query merges its slabs' lists and writes
 //                           ids (+ id_base), distances (ord's inverse) and the fill to the row of the query it belongs to, with the
 //                           exact stage's counters.
-// No LDS in the select kernel, vector stores only.  All scratch is the handle's (LadderBufs, FilterBufs, AfterBufs, scratch.scan): one
-// filtered, range or paged call in flight per handle.  out_next is plain arithmetic over the finished rows (next_cursor), on the host.
+// No LDS in the select kernel, vector stores only.  All scratch is the handle's (LadderBufs; FilterBufs' wids / wdist / stage;
+// AfterBufs; scratch.scan): one filtered, range, grouped or paged call in flight per handle.  out_next is plain arithmetic over the finished rows (next_cursor), on the host.
 #include "hnsw_internal.h"
 #include "hnsw_scan_device.hip.h"
 #include "hnsw_after_plan.h"
@@ -47,11 +47,10 @@ struct AfterScanArgs {
 // The paged top-k selection of one (tile, slab) wave (scan_slab's Select): ScanTopK over distance-words with a lower bound per
 // query of the tile.  thr[t]: the word of the k-th smallest admitted candidate so far (all ones until there are k); khi[t] (L2): the
 // largest KEY whose distance-word's upper half is not above thr[t]'s.
-template <int NCH, int METRIC, bool MASKED> struct ScanAfter {
+template <int NCH, int METRIC, bool MASKED> struct ScanAfter : ScanMask<MASKED> {
     static constexpr int T = scan_tile(NCH);
     static constexpr int LIMIT = SCAN_BUF - 4 * scan_rows(NCH);
     const AfterScanArgs &a;
-    MaskWords mask;
     uint64_t (*bufs)[SCAN_BUF], *sorted, *lists0;
     int64_t list_step;
     uint64_t thr[T], lo[T];
@@ -60,7 +59,7 @@ template <int NCH, int METRIC, bool MASKED> struct ScanAfter {
     uint32_t par;
     bool full;
 
-    __device__ __forceinline__ ScanAfter(const AfterScanArgs &a_, const uint32_t *mask_) : a(a_), mask(mask_words(mask_)) {}
+    __device__ __forceinline__ ScanAfter(const AfterScanArgs &a_, const uint32_t *mask_) : ScanMask<MASKED>(mask_), a(a_) {}
     __device__ __forceinline__ void begin(int64_t q0, int tq_, int64_t slab) {
         __shared__ uint64_t bufs_all[SCAN_WAVES][T][SCAN_BUF];
         __shared__ uint64_t sorted_all[SCAN_WAVES][SCAN_BUF];
@@ -86,10 +85,6 @@ template <int NCH, int METRIC, bool MASKED> struct ScanAfter {
             }
         }
         scan_wave_sync();
-    }
-    __device__ __forceinline__ bool skip(int64_t base) const { return MASKED && uniform((int)mask[base >> 5]) == 0; }
-    __device__ __forceinline__ bool admits(int64_t row, bool in_slab) const {
-        return in_slab && (!MASKED || ((mask[row >> 5] >> (row & 31)) & 1u));
     }
     __device__ __forceinline__ void take(int t, uint32_t key, int64_t row, bool ok) {
         const uint32_t bound = METRIC == 0 ? khi[METRIC == 0 ? t : 0] : (uint32_t)(thr[t] >> 32);
@@ -149,7 +144,7 @@ struct AfterMergeArgs {
     int64_t row0;
     int32_t *out_ids;          // [nq][k] by query
     float *out_dist;
-    // the exact stage's counters (out_nd null: none): out_nd += add (fresh: = add, out_nh = 0), out_stage = 0xFFFFFFFF
+    // the exact stage's counters (out_nd null: none): exact_settle
     uint32_t *out_nd, *out_nh, *out_stage;
     uint32_t add;
     int32_t fresh;
@@ -199,11 +194,7 @@ after_merge_kernel(const AfterMergeArgs a) {
         a.out_ids[q * k + j] = -1;
         a.out_dist[q * k + j] = a.fill == 0 ? __uint_as_float(0x7FC00000u) : __uint_as_float(0x7F800000u);
     }
-    if (threadIdx.x == 0 && a.out_nd) {
-        a.out_nd[q] = (a.fresh ? 0u : a.out_nd[q]) + a.add;
-        if (a.fresh) a.out_nh[q] = 0u;
-        a.out_stage[q] = 0xFFFFFFFFu;
-    }
+    if (threadIdx.x == 0 && a.out_nd) exact_settle(a.out_nd, a.out_nh, a.out_stage, q, a.add, a.fresh != 0);
 }
 
 struct AfterSelectArgs {
@@ -223,10 +214,8 @@ struct AfterSelectArgs {
 
 // is entry j of the row a node, allowed, and after the cursor
 __device__ __forceinline__ bool after_eligible(const AfterSelectArgs &a, MaskWords bits, uint64_t lo, const int32_t *wi, const float *wd, int j) {
-    const int64_t v = (int64_t)wi[j] - a.id_base;
-    if (v < 0 || v >= a.n) return false;
-    if (a.mask && !((bits[v >> 5] >> (v & 31)) & 1u)) return false;
-    return hnsw_after::word(wd[j], (uint32_t)v) > lo;
+    if (!is_node(a.n, a.id_base, wi[j]) || (a.mask && !node_allowed(bits, a.n, a.id_base, wi[j]))) return false;
+    return hnsw_after::word(wd[j], (uint32_t)((int64_t)wi[j] - a.id_base)) > lo;
 }
 
 __global__ void __launch_bounds__(64)
@@ -314,38 +303,27 @@ int after_scan(hnsw_index *idx, const float *Q, int64_t m, int64_t q_stride, con
 // fb.stage on return.  f: the mask the call answers under (the caller's filter, else the live mask, else none).
 int after_search(hnsw_index *idx, const hnsw_filter *f, const hnsw_search_params &p, const KnnBatch &b, float *d_stage, hipStream_t st) {
     FilterBufs &fb = idx->filter_scratch;
-    AfterBufs &ab = idx->after_scratch;
     const int k = p.k;
-    const bool rerank = walk_is_inexact(idx);
     const uint32_t *const mask = f ? (const uint32_t *)f->bits.p : nullptr;
     const int64_t n_allowed = f ? f->n_allowed : idx->iv.n;
     uint32_t *const d_stage_out = (uint32_t *)fb.stage.p;
     Ladder L(idx, b.Q, b.nq, b.q_stride, p.ef, p.semantics, d_stage, st, "paged search");
-    const bool walked = n_allowed >= k;     // (else no cursor leaves k eligible nodes: every query is the exact stage's, unwalked)
-    bool short_at_end = false;
+    LadderLeft left;
     int rc;
-    for (bool more = walked; more;) {
-        const int64_t m = L.m;
-        const int e = L.e;
-        if ((rc = fb.wids.ensure((size_t)m * e * 4)) || (rc = fb.wdist.ensure((size_t)m * e * 4)) ||
-            (rerank && ((rc = ab.cand.ensure((size_t)m * e * 4)) || (rc = ab.cdist.ensure((size_t)m * e * 4)) || (rc = ab.rnd.ensure((size_t)m * 4)))))
-            return rc;
+    // (fewer than k allowed nodes: no cursor leaves k eligible ones, every query is the exact stage's, unwalked)
+    rc = L.run(n_allowed >= k, [&](Ladder &, int64_t m, int e) -> int {
+        if ((rc = fb.wids.ensure((size_t)m * e * 4)) || (rc = fb.wdist.ensure((size_t)m * e * 4))) return rc;
         int32_t *const Wi = (int32_t *)fb.wids.p;
         float *const Wd = (float *)fb.wdist.p;
-        if ((rc = L.walk(rerank ? (int32_t *)ab.cand.p : Wi, rerank ? (float *)ab.cdist.p : Wd, HNSW_FILL_OHNSW))) return rc;
-        // half rows / codes: all members of W over the float32 rows, k := e
-        if (rerank && (rc = launch_rerank(idx, L.Qj, m, L.qs, L.wb.ids, e, e, HNSW_FILL_OHNSW, Wi, Wd, L.wb.nd, (uint32_t *)ab.rnd.p, st))) return rc;
-        const hnsw_dev::AfterSelectArgs sa{Wi, Wd, m, e, k, L.map, mask, idx->iv.n, idx->iv.id_base, (const uint64_t *)ab.lo.p, b.ids, b.dist,
-                                           L.out(rerank ? (const uint32_t *)ab.rnd.p : L.wb.nd, b.nd, b.nh, d_stage_out)};
+        if ((rc = L.walk_exact(Wi, Wd, HNSW_FILL_OHNSW))) return rc;
+        const hnsw_dev::AfterSelectArgs sa{Wi, Wd, m, e, k, L.map, mask, idx->iv.n, idx->iv.id_base, (const uint64_t *)idx->after_scratch.lo.p, b.ids, b.dist,
+                                           L.out(b.nd, b.nh, d_stage_out)};
         hipLaunchKernelGGL(hnsw_dev::after_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
-        if ((rc = launched("paged select kernel")) || (rc = L.count_short())) return rc;
-        if (L.n_short == 0) break;
-        if ((rc = L.advance(more))) return rc;
-        short_at_end = !more;
-    }
-    if (walked && !short_at_end) return HNSW_OK;
-    // the L.m queries of (L.Qj, L.map): the ladder's last batch, or the caller's own when nobody walked
-    return after_scan(idx, L.Qj, L.m, L.qs, L.map, k, p.fill, st, mask, b.ids, b.dist, b.nd, b.nh, d_stage_out, (uint32_t)n_allowed, !walked);
+        return launched("paged select kernel");
+    }, left);
+    if (rc || left == LadderLeft::none) return rc;
+    // the L.m queries of (L.Qj, L.map): the batch the ladder left
+    return after_scan(idx, L.Qj, L.m, L.qs, L.map, k, p.fill, st, mask, b.ids, b.dist, b.nd, b.nh, d_stage_out, (uint32_t)n_allowed, left == LadderLeft::fresh);
 }
 
 // what both entry points check of the cursors, on the host, before any launch
@@ -370,20 +348,15 @@ int after_call(hnsw_index *idx, const hnsw_filter *f, const hnsw_cursor *after, 
     }
     int rc;
     if ((rc = idx->after_scratch.lo.ensure((size_t)nq * 8)) || (rc = idx->filter_scratch.stage.ensure((size_t)nq * 4))) return rc;
-    HostCall c;
-    bool q_in_place = false;
-    if ((rc = c.begin(idx, queries, nq, q_stride, k, out_ids, out_dist, out_ndist, out_nhops, params != nullptr, &q_in_place))) return rc;
-    hipStream_t st = idx->hs[0];
-    // (from here on copies are queued that read the caller's arrays: no return without a synchronisation)
-    if (hipMemcpyAsync(idx->after_scratch.lo.p, lo.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(HNSW_ERR_HIP, "cursor upload failed");
-    if (!rc && params) rc = after_search(idx, f, *params, c.b, q_in_place ? (float *)idx->scratch.q.p : nullptr, st);
-    if (!rc && !params)
-        rc = after_scan(idx, c.b.Q, nq, q_stride, nullptr, k, fill, st, f ? (const uint32_t *)f->bits.p : nullptr, c.b.ids, c.b.dist, nullptr, nullptr,
-                        nullptr, 0u, true);
-    if (!rc && params && out_stage && hipMemcpyAsync(out_stage, idx->filter_scratch.stage.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(HNSW_ERR_HIP, "stage download failed");
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    if ((rc = c.finish(idx, params ? "paged search" : "paged scan", st))) return rc;
+    rc = ladder_host_call(idx, queries, nq, q_stride, k, out_ids, out_dist, out_ndist, out_nhops, params ? out_stage : nullptr, params != nullptr, nullptr,
+                          nullptr, nullptr, params ? "paged search" : "paged scan", [&](const KnnBatch &b, float *d_stage, hipStream_t st) -> int {
+        if (hipMemcpyAsync(idx->after_scratch.lo.p, lo.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+            return fail(HNSW_ERR_HIP, "cursor upload failed");
+        if (params) return after_search(idx, f, *params, b, d_stage, st);
+        return after_scan(idx, b.Q, nq, q_stride, nullptr, k, fill, st, f ? (const uint32_t *)f->bits.p : nullptr, b.ids, b.dist, nullptr, nullptr, nullptr, 0u,
+                          true);
+    });
+    if (rc) return rc;
     if (out_next)
         for (int64_t q = 0; q < nq; ++q) {
             const hnsw_cursor &in = after ? after[q] : start;

@@ -6,8 +6,9 @@
 //   exact    a query still short at e = 1024, and every query whose filter allows fewer than k nodes, gets the masked exact scan:
 //            one launch sequence for all filters, the queries ordered by (filter, query) and laid out so that no scan tile spans
 //            two filters (hnsw_filter_plan.h).
-// The ladder itself (Ladder: the walk of a stage, the short list, the gathered batch) is here too; the range search
-// (hnsw_range.hip) runs the same one with its own select rule.
+// The ladder itself (Ladder: the loop, the walk of a stage and its re-rank over the float32 rows, the short list, the gathered
+// batch) is here too, and so is the scatter kernel: the range, grouped and paged searches (hnsw_range.hip, hnsw_group.hip,
+// hnsw_after.hip) run the same loop, each with a stage body and a select rule of its own.
 // Option "filter_collect" (k <= 128, exact rows) changes the stage test only: a stage's walk is the collect kernel's
 // (hnsw_search_collect_kernel), whose [m][k] rows hold R -- the first k allowed nodes of everything the walk evaluated -- and the
 // select kernel, run with e := k, serves the queries whose R is full.
@@ -24,8 +25,10 @@
 //                           are appended to the short list (ladder_settle).
 //   ladder_gather_kernel    the short queries' vectors as one compact, zero-padded matrix: the next walk's / the exact stage's batch
 //                           (a padding row of the exact stage's layout: the zero vector).
-//   filter_scatter_kernel   rows of a compact result (re-rank, scan) to the rows of the queries they belong to; padding rows are dropped.
-// No LDS, vector stores only.  All scratch is the handle's (LadderBufs, FilterBufs): one filtered or range call in flight per handle.
+//   filter_scatter_kernel   rows of a compact result (re-rank, scan; the grouped exact stage's, with their labels column) to the rows
+//                           of the queries they belong to; padding rows are dropped.
+// No LDS, vector stores only.  All scratch is the handle's (LadderBufs, FilterBufs): one filtered, range, grouped or paged call in
+// flight per handle.
 #include "hnsw_internal.h"
 
 namespace hnsw_dev {
@@ -89,11 +92,6 @@ struct SelectArgs {
     LadderOut out;
 };
 
-__device__ __forceinline__ bool filter_allows(const SelectArgs &a, MaskWords bits, int32_t id) {
-    const int64_t v = (int64_t)id - a.id_base;
-    return v >= 0 && v < a.n && ((bits[v >> 5] >> (v & 31)) & 1u);
-}
-
 __global__ void __launch_bounds__(64)
 filter_select_kernel(const SelectArgs a) {
     const int lane = threadIdx.x;
@@ -105,20 +103,20 @@ filter_select_kernel(const SelectArgs a) {
     int cnt = 0;
     for (int j0 = 0; j0 < a.e; j0 += 64) {
         const int j = j0 + lane;
-        cnt += popc(ballot(j < a.e && filter_allows(a, bits, wi[j])));
+        cnt += popc(ballot(j < a.e && node_allowed(bits, a.n, a.id_base, wi[j])));
     }
     const bool served = cnt >= a.k;
     if (a.cand) {               // W with everything but a served query's allowed members as padding
         for (int j = lane; j < a.e; j += 64) {
             const int32_t id = wi[j];
-            a.cand[i * a.e + j] = served && filter_allows(a, bits, id) ? id : a.id_base - 1;
+            a.cand[i * a.e + j] = served && node_allowed(bits, a.n, a.id_base, id) ? id : a.id_base - 1;
         }
     } else if (served) {        // the first k allowed members, in W's order
         int at = 0;
         for (int j0 = 0; j0 < a.e && at < a.k; j0 += 64) {
             const int j = j0 + lane;
             const int32_t id = j < a.e ? wi[j] : a.id_base - 1;
-            const bool ok = j < a.e && filter_allows(a, bits, id);
+            const bool ok = j < a.e && node_allowed(bits, a.n, a.id_base, id);
             const uint64_t m = ballot(ok);
             const int pos = at + popc(m & ((1ull << lane) - 1ull));
             if (ok && pos < a.k) {
@@ -144,24 +142,6 @@ ladder_gather_kernel(const float *Q, int64_t q_stride, int32_t d, const int32_t 
     for (int64_t c = threadIdx.x; c < out_stride; c += 64) out[i * out_stride + c] = q >= 0 && c < d ? qp[c] : 0.f;
 }
 
-struct ScatterArgs {
-    const int32_t *rids;       // [m][k] compact results
-    const float *rdist;
-    int64_t m;
-    int32_t k;
-    const int32_t *map;        // [m] row i belongs to query map[i] (< 0: a padding row, dropped); null: to query i
-    const int32_t *cnt;        // null: every row; else only the rows with cnt[i] >= k (the served ones)
-    const uint32_t *add;       // null, or [m]: evaluations to add to out_nd
-    uint32_t add_const;        // ... plus this many
-    const int32_t *fresh_of;   // null, or [m]: `fresh` per row
-    int32_t fresh;             // 1: the query took no walk: out_nd starts from 0 and out_nh is 0
-    int32_t set_stage;         // 1: out_stage[q] = stage
-    uint32_t stage;
-    int32_t *out_ids;          // [nq][k]
-    float *out_dist;
-    uint32_t *out_nd, *out_nh, *out_stage;
-};
-
 __global__ void __launch_bounds__(64)
 filter_scatter_kernel(const ScatterArgs a) {
     const int64_t i = blockIdx.x;
@@ -171,12 +151,12 @@ filter_scatter_kernel(const ScatterArgs a) {
     for (int j = threadIdx.x; j < a.k; j += 64) {
         a.out_ids[q * a.k + j] = a.rids[i * a.k + j];
         a.out_dist[q * a.k + j] = a.rdist[i * a.k + j];
+        if (a.rlab) a.out_labels[q * a.k + j] = a.rlab[i * a.k + j];
     }
     if (threadIdx.x == 0) {
-        const bool fresh = a.fresh_of ? a.fresh_of[i] != 0 : a.fresh != 0;
-        a.out_nd[q] = (fresh ? 0u : a.out_nd[q]) + (a.add ? a.add[i] : 0u) + a.add_const;
-        if (fresh) a.out_nh[q] = 0u;
-        if (a.set_stage) a.out_stage[q] = a.stage;
+        const uint32_t add = (a.add ? a.add[i] : 0u) + a.add_const;
+        if (a.exact) exact_settle(a.out_nd, a.out_nh, a.out_stage, q, add, a.fresh_of ? a.fresh_of[i] != 0 : a.fresh != 0);
+        else a.out_nd[q] += add;
     }
 }
 
@@ -198,6 +178,8 @@ int Ladder::walk(int32_t *wids, float *wdist, int32_t fill) {
     const hnsw_dev::CollectArgs ca{collect_masks, collect_which, map};
     const hnsw_dev::CollectArgs *const collect = collect_k ? &ca : nullptr;
     wb = KnnBatch{Qj, m, qs, wids, wdist, (uint32_t *)lb.wnd.p, (uint32_t *)lb.wnh.p, (uint32_t *)lb.wst.p, idx->hFlagDev};
+    evals = wb.nd;
+    counted = false;
     *(volatile uint32_t *)idx->hFlag = 0;
     // (d_stage: only the caller's own matrix can lie in host memory, never a gathered batch)
     if ((rc = knn_search(idx, &wp, wb, st, map ? nullptr : d_stage, nullptr, true, collect))) return rc;
@@ -207,12 +189,30 @@ int Ladder::walk(int32_t *wids, float *wdist, int32_t fill) {
     return HNSW_OK;
 }
 
-hnsw_dev::LadderOut Ladder::out(const uint32_t *wnd, uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage) const {
+int Ladder::walk_raw(int32_t *Wi, float *Wd, int32_t fill) {
+    if (!walk_is_inexact(idx)) return walk(Wi, Wd, fill);
+    LadderBufs &lb = idx->ladder_scratch;
+    int rc;
+    if ((rc = lb.cand.ensure((size_t)m * e * 4)) || (rc = lb.cdist.ensure((size_t)m * e * 4)) || (rc = lb.rnd.ensure((size_t)m * 4))) return rc;
+    return walk((int32_t *)lb.cand.p, (float *)lb.cdist.p, fill);
+}
+
+int Ladder::rerank_all(int32_t *Wi, float *Wd, int32_t fill) {
+    if (!walk_is_inexact(idx)) return HNSW_OK;
+    uint32_t *const rnd = (uint32_t *)idx->ladder_scratch.rnd.p;
+    const int rc = launch_rerank(idx, Qj, m, qs, wb.ids, e, e, fill, Wi, Wd, wb.nd, rnd, st);
+    evals = rnd;
+    return rc;
+}
+
+hnsw_dev::LadderOut Ladder::out(uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage) const {
     const LadderBufs &lb = idx->ladder_scratch;
-    return {wnd, wb.nh, (uint32_t)stage, stage > 0, out_nd, out_nh, out_stage, (int32_t *)lb.list[cur ^ 1].p, (uint32_t *)lb.count.p};
+    return {evals, wb.nh, (uint32_t)stage, stage > 0, out_nd, out_nh, out_stage, (int32_t *)lb.list[cur ^ 1].p, (uint32_t *)lb.count.p};
 }
 
 int Ladder::count_short() {
+    if (counted) return HNSW_OK;
+    counted = true;
     HIP_TRY(hipMemcpyAsync(&n_short, idx->ladder_scratch.count.p, 4, hipMemcpyDeviceToHost, st));
     return synced(st, what);
 }
@@ -256,15 +256,9 @@ int Ladder::advance(bool &more) {
     return HNSW_OK;
 }
 
-// what every filtered entry point checks of one filter of the call
-int check_filter(const hnsw_index *idx, const hnsw_filter *f) {
-    if (!f) return fail(HNSW_ERR_BAD_ARG, "null filter");
-    if (f->idx != idx) return fail(HNSW_ERR_BAD_ARG, "the filter was made for another index");
-    if (f->n != idx->iv.n)
-        return fail(HNSW_ERR_BAD_ARG, "the filter was made for %lld nodes, the index has grown to %lld", (long long)f->n, (long long)idx->iv.n);
-    if (f->epoch != idx->epoch)
-        return fail(HNSW_ERR_BAD_ARG, "the filter was made before the index last changed (hnsw_index_insert / hnsw_index_remove / hnsw_index_mark_deleted): it is stale");
-    return HNSW_OK;
+int scatter_rows(const hnsw_dev::ScatterArgs &a, hipStream_t st, const char *what) {
+    hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)a.m), dim3(64), 0, st, a);
+    return launched(what);
 }
 
 // a filter of n nodes for idx (its epoch) with its mask allocated (not initialised) and the mask's own address behind it
@@ -354,10 +348,9 @@ int exact_stage_each(hnsw_index *idx, const FilterSet &fs, const hnsw_search_par
     if ((rc = scan_search(idx, {(const float *)lb.q.p, R, pad, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr, nullptr, nullptr, nullptr}, k, p.fill, st,
                           fs.d_masks, d_rows + 3 * R, d_rows)))
         return rc;
-    const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, R, k, d_rows, nullptr, (const uint32_t *)(d_rows + R), 0u,
-                                   d_rows + 2 * R, 0, 1, 0xFFFFFFFFu, b.ids, b.dist, b.nd, b.nh, d_stage_out};
-    hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)R), dim3(64), 0, st, sc);
-    return launched("filter scatter kernel");
+    return scatter_rows({(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, nullptr, R, k, d_rows, nullptr, (const uint32_t *)(d_rows + R), 0u, 1,
+                         d_rows + 2 * R, 0, b.ids, b.dist, nullptr, b.nd, b.nh, d_stage_out},
+                        st, "filter scatter kernel");
 }
 
 // The ladder and the exact stage for a batch HostCall::begin has placed (c.b): the results are in c.b's rows and fb.stage on return.
@@ -381,44 +374,39 @@ int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_para
     if (fs.which) for (int64_t q = 0; q < b.nq; ++q) (fs.of(q).n_allowed >= k ? walkers : fresh).push_back((int32_t)q);
     const bool walked = fs.which ? !walkers.empty() : fs.filters[0]->n_allowed >= k;
     if (walked && !fresh.empty() && (rc = L.start_from(walkers.data(), (int64_t)walkers.size()))) return rc;
-    bool short_at_end = false;
-    for (bool more = walked; more;) {
-        const int64_t m = L.m;
-        const int e = collect ? k : L.e;      // entries per row of the stage's walk
+    LadderLeft left;
+    rc = L.run(walked, [&](Ladder &, int64_t m, int e) -> int {
+        if (collect) e = k;                   // entries per row of the stage's walk
         if ((rc = fb.wids.ensure((size_t)m * e * 4)) || (rc = fb.wdist.ensure((size_t)m * e * 4)) || (rc = fb.cnt.ensure((size_t)m * 4)) ||
             (rerank && (rc = fb.cand.ensure((size_t)m * e * 4))))
             return rc;
         if ((rc = L.walk((int32_t *)fb.wids.p, (float *)fb.wdist.p, p.fill))) return rc;
         const hnsw_dev::SelectArgs sa{L.wb.ids, L.wb.dist, m, e, k, L.map, fs.d_masks, fs.d_which, idx->iv.n, idx->iv.id_base, b.ids, b.dist,
-                                      rerank ? (int32_t *)fb.cand.p : nullptr, (int32_t *)fb.cnt.p, L.out(L.wb.nd, b.nd, b.nh, d_stage_out)};
+                                      rerank ? (int32_t *)fb.cand.p : nullptr, (int32_t *)fb.cnt.p, L.out(b.nd, b.nh, d_stage_out)};
         hipLaunchKernelGGL(hnsw_dev::filter_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
         if ((rc = launched("filter select kernel")) || (rc = L.count_short())) return rc;
         if (rerank && (int64_t)L.n_short < m) {
             // the served queries' allowed members over the float32 rows, then their rows to where they belong
             if ((rc = launch_rerank(idx, L.Qj, m, L.qs, (const int32_t *)fb.cand.p, e, k, p.fill, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr,
-                                    (uint32_t *)fb.rnd.p, st)))
+                                    (uint32_t *)fb.rnd.p, st)) ||
+                (rc = scatter_rows({(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, nullptr, m, k, L.map, (const int32_t *)fb.cnt.p,
+                                    (const uint32_t *)fb.rnd.p, 0u, 0, nullptr, 0, b.ids, b.dist, nullptr, b.nd, b.nh, d_stage_out},
+                                   st, "filter scatter kernel")))
                 return rc;
-            const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, m, k, L.map, (const int32_t *)fb.cnt.p,
-                                           (const uint32_t *)fb.rnd.p, 0u, nullptr, 0, 0, 0u, b.ids, b.dist, b.nd, b.nh, d_stage_out};
-            hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)m), dim3(64), 0, st, sc);
             // (waited for here: a failure of theirs is this stage's, not the next walk's)
-            if ((rc = launched("filter scatter kernel")) || (rc = synced(st, "filtered search"))) return rc;
+            return synced(st, "filtered search");
         }
-        if (L.n_short == 0) break;
-        if ((rc = L.advance(more))) return rc;
-        short_at_end = !more;
-    }
-    if (walked && !short_at_end && fresh.empty()) return HNSW_OK;
-    if (fs.which) return exact_stage_each(idx, fs, p, b, short_at_end ? L.batch_queries() : std::vector<int32_t>(), fresh, d_stage_out, st);
+        return HNSW_OK;
+    }, left);
+    if (rc || (left == LadderLeft::none && fresh.empty())) return rc;
+    if (fs.which) return exact_stage_each(idx, fs, p, b, left == LadderLeft::walked ? L.batch_queries() : std::vector<int32_t>(), fresh, d_stage_out, st);
     // the exact stage under one filter: the k smallest allowed nodes under (distance, id) for the L.m queries of (L.Qj, L.map) -- the
-    // ladder's last batch, or the caller's own when nobody walked --, which need no other layout
-    const hnsw_filter *const f = fs.filters[0];
+    // batch the ladder left --, which need no other layout
     if ((rc = scan_search(idx, {L.Qj, L.m, L.qs, (int32_t *)fb.rids.p, (float *)fb.rdist.p, nullptr, nullptr, nullptr, nullptr}, k, p.fill, st, fs.d_masks)))
         return rc;
-    const hnsw_dev::ScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, L.m, k, L.map, nullptr, nullptr, (uint32_t)f->n_allowed,
-                                   nullptr, !walked, 1, 0xFFFFFFFFu, b.ids, b.dist, b.nd, b.nh, d_stage_out};
-    hipLaunchKernelGGL(hnsw_dev::filter_scatter_kernel, dim3((unsigned)L.m), dim3(64), 0, st, sc);
-    return launched("filter scatter kernel");
+    return scatter_rows({(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, nullptr, L.m, k, L.map, nullptr, nullptr, (uint32_t)fs.filters[0]->n_allowed, 1,
+                         nullptr, left == LadderLeft::fresh, b.ids, b.dist, nullptr, b.nd, b.nh, d_stage_out},
+                        st, "filter scatter kernel");
 }
 
 // both search entry points once their arguments are checked (nq > 0).  fs.d_masks / fs.d_which are allocated; host_masks (the
@@ -426,24 +414,15 @@ int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_para
 int filtered_call(hnsw_index *idx, const FilterSet &fs, const uint32_t *const *host_masks, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
                   int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko = nullptr,
                   const RowsIn *rows = nullptr) {
-    HostCall c;
-    c.ko = ko;
-    c.rows = rows;
-    bool q_in_place = false;
-    int rc;
-    if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
-    hipStream_t st = idx->hs[0];
-    // (from here on copies are queued that read the caller's arrays: no return without a synchronisation)
-    if (host_masks) {
-        hipError_t e = hipMemcpyAsync(const_cast<uint32_t **>(fs.d_masks), host_masks, (size_t)fs.n * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(const_cast<int32_t *>(fs.d_which), fs.which, (size_t)nq * 4, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) rc = hip_fail(e, "filter table upload");
-    }
-    if (!rc) rc = filtered_search(idx, fs, *params, c.b, q_in_place ? (float *)idx->scratch.q.p : nullptr, st);
-    if (!rc && out_stage && hipMemcpyAsync(out_stage, idx->filter_scratch.stage.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(HNSW_ERR_HIP, "stage download failed");
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    return c.finish(idx, "filtered search", st);
+    return ladder_host_call(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, out_stage, true, ko, rows, nullptr,
+                            "filtered search", [&](const KnnBatch &b, float *d_stage, hipStream_t st) -> int {
+        if (host_masks) {
+            hipError_t e = hipMemcpyAsync(const_cast<uint32_t **>(fs.d_masks), host_masks, (size_t)fs.n * 8, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(const_cast<int32_t *>(fs.d_which), fs.which, (size_t)nq * 4, hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) return hip_fail(e, "filter table upload");
+        }
+        return filtered_search(idx, fs, *params, b, d_stage, st);
+    });
 }
 
 } // namespace

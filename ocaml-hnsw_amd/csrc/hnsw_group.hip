@@ -1,17 +1,17 @@
 // hnsw_group.hip -- grouped k-NN search: one label per node (hnsw_labels_*), hnsw_search_batch_grouped -- the k nearest DISTINCT
-// labels, each represented by its nearest node -- and the exact form hnsw_brute_force_batch_grouped.  A third select rule of the
-// ladder that the filtered and the range search run (Ladder, hnsw_filter.hip) and a third selection policy of the one exact-scan
-// body (scan_slab, hnsw_scan_device.hip.h), as the header defines it:
+// labels, each represented by its nearest node -- and the exact form hnsw_brute_force_batch_grouped.  One stage body and select rule
+// for the ladder's loop (Ladder::run, hnsw_filter.hip) and one selection policy of the one exact-scan body (scan_slab,
+// hnsw_scan_device.hip.h), inside the shared host frame (ladder_host_call), as the header defines it:
 //   ladder   e = ef, 2 ef, ... 1024: a query is served at the first e whose W holds eligible nodes of k distinct labels (eligible:
 //            label >= 0 and, with a filter, allowed); its answer is the first eligible member of each of the first k labels, in
-//            W's order.  Half rows and codes: the eligible members of W are re-ranked over the float32 rows first (launch_rerank
-//            with k := e) and the select reads the re-ranked rows.
+//            W's order.  Half rows and codes: the eligible members of W are re-ranked over the float32 rows first (the two halves
+//            of Ladder::walk_exact, group_cand_kernel between them) and the select reads the re-ranked rows.
 //   exact    a query still short at e = 1024, and every query when there are fewer than k groups (or the filter allows fewer than
 //            k nodes): per label the smallest eligible node under (key, id), then the k smallest of those.
 //
 // Kernels.
 //   labels_prepare_kernel   the uploaded labels: -1 where the live mask has no bit; counts the labelled nodes and the labels in use.
-//   group_cand_kernel       W with the ineligible entries turned into padding: the re-rank's candidate matrix.
+//   group_cand_kernel       W with the ineligible entries turned into padding, in place: the re-rank's candidate matrix.
 //   group_select_kernel     one wave per walked query, 64 entries of W per pass: an entry is a representative iff it is eligible
 //                           and its label is neither among those accepted so far (kept in LDS, at most k) nor in an earlier lane
 //                           of the pass (the readlane / ballot loop of filter_label_kernel).  Stops at k.  A served query's ids,
@@ -22,8 +22,9 @@
 //                           the k-th smallest, the words up to it are ranked in LDS -- become ids, key_to_dist and labels, then
 //                           the fill; a row of more than 16 384 cells in stripes, one workgroup each, whose k words are picked
 //                           from by a second launch.
-//   group_scatter_kernel    rows of a compact result, with their labels column, to the rows of the queries they belong to.
-// Vector stores only.  Scratch is the handle's (LadderBufs, FilterBufs, GroupBufs): one filtered, range or grouped call in flight.
+// The exact stage's compact rows, with their labels column, go to their queries through the filtered search's scatter kernel (scatter_rows).
+// Vector stores only.  Scratch is the handle's (LadderBufs; FilterBufs' wids / wdist / rids / rdist / stage; GroupBufs): one filtered,
+// range, grouped or paged call in flight.
 #include "hnsw_internal.h"
 #include "hnsw_scan_device.hip.h"
 
@@ -64,12 +65,11 @@ struct GroupEligible {
 };
 // the label of an eligible entry, -1 for every other
 __device__ __forceinline__ int32_t group_label(const GroupEligible &g, int32_t id) {
-    const int64_t v = (int64_t)id - g.id_base;
-    if (v < 0 || v >= g.n) return -1;
-    if (g.mask && !((g.mask[v >> 5] >> (v & 31)) & 1u)) return -1;
-    return g.labels[v];
+    if (!is_node(g.n, g.id_base, id) || (g.mask && !node_allowed(mask_words(g.mask), g.n, g.id_base, id))) return -1;
+    return g.labels[(int64_t)id - g.id_base];
 }
 
+// (cand may be wids: an entry is read and written by the same lane)
 __global__ void __launch_bounds__(64)
 group_cand_kernel(const int32_t *wids, int64_t m, int32_t e, const GroupEligible g, int32_t *cand) {
     const int64_t i = blockIdx.x;
@@ -154,23 +154,21 @@ struct GroupScanArgs {
 // bit is set (MASKED) and its label is >= 0; its word (key << 32 | row) goes to the cell of (query, label) by atomicMin when a
 // plain load finds the cell above it.  Ascending words = the total order (distance, id), so the cell ends as the label's smallest
 // eligible node whatever the slabs' order.
-template <int NCH, bool MASKED> struct ScanGroupBest {
+template <int NCH, bool MASKED> struct ScanGroupBest : ScanMask<MASKED> {
     const GroupScanArgs &a;
-    MaskWords mask;
     unsigned long long *rows;  // the cells of the tile's first query
     int tq, lane;
     int32_t lab;               // the label of the row admits was last asked about
-    __device__ __forceinline__ ScanGroupBest(const GroupScanArgs &a_) : a(a_), mask(mask_words(a_.mask)) {}
+    __device__ __forceinline__ ScanGroupBest(const GroupScanArgs &a_) : ScanMask<MASKED>(a_.mask), a(a_) {}
     __device__ __forceinline__ void begin(int64_t q0, int tq_, int64_t) {
         lane = threadIdx.x & 63;
         tq = tq_;
         rows = a.best + q0 * a.n_labels;
         lab = -1;
     }
-    __device__ __forceinline__ bool skip(int64_t base) const { return MASKED && uniform((int)mask[base >> 5]) == 0; }
     __device__ __forceinline__ bool admits(int64_t row, bool in_slab) {
         // (the label of a row past the slab's end is never loaded: such a row may lie past the table's)
-        lab = in_slab && (!MASKED || ((mask[row >> 5] >> (row & 31)) & 1u)) ? a.labels[row] : -1;
+        lab = ScanMask<MASKED>::admits(row, in_slab) ? a.labels[row] : -1;
         return lab >= 0;
     }
     __device__ __forceinline__ void take(int t, uint32_t key, int64_t row, bool ok) {
@@ -271,39 +269,6 @@ group_pick_kernel(const unsigned long long *words, const int32_t *word_lab, int6
     }
 }
 
-struct GroupScatterArgs {
-    const int32_t *rids;       // [m][k] compact results
-    const float *rdist;
-    const int32_t *rlab;
-    int64_t m;
-    int32_t k;
-    const int32_t *map;        // [m] row i belongs to query map[i]; null: to query i
-    uint32_t add;              // evaluations to add to out_nd
-    int32_t fresh;             // 1: the query took no walk: out_nd starts from 0 and out_nh is 0
-    uint32_t stage;            // what out_stage becomes
-    int32_t *out_ids;          // [nq][k]
-    float *out_dist;
-    int32_t *out_labels;
-    uint32_t *out_nd, *out_nh, *out_stage;
-};
-
-__global__ void __launch_bounds__(64)
-group_scatter_kernel(const GroupScatterArgs a) {
-    const int64_t i = blockIdx.x;
-    if (i >= a.m) return;
-    const int64_t q = a.map ? a.map[i] : i;
-    for (int j = threadIdx.x; j < a.k; j += 64) {
-        a.out_ids[q * a.k + j] = a.rids[i * a.k + j];
-        a.out_dist[q * a.k + j] = a.rdist[i * a.k + j];
-        a.out_labels[q * a.k + j] = a.rlab[i * a.k + j];
-    }
-    if (threadIdx.x == 0) {
-        a.out_nd[q] = (a.fresh ? 0u : a.out_nd[q]) + a.add;
-        if (a.fresh) a.out_nh[q] = 0u;
-        a.out_stage[q] = a.stage;
-    }
-}
-
 } // namespace hnsw_dev
 
 using namespace hnsw_host;
@@ -311,17 +276,6 @@ using namespace hnsw_host;
 namespace {
 
 constexpr int64_t GROUP_STRIPE = 16384;     // cells of a best row one workgroup of the pick takes
-
-// what every call that takes a labels object checks of it: check_filter's rule
-int check_labels(const hnsw_index *idx, const hnsw_labels *l) {
-    if (!l) return fail(HNSW_ERR_BAD_ARG, "null labels");
-    if (l->idx != idx) return fail(HNSW_ERR_BAD_ARG, "the labels were made for another index");
-    if (l->n != idx->iv.n)
-        return fail(HNSW_ERR_BAD_ARG, "the labels were made for %lld nodes, the index has grown to %lld", (long long)l->n, (long long)idx->iv.n);
-    if (l->epoch != idx->epoch)
-        return fail(HNSW_ERR_BAD_ARG, "the labels were made before the index last changed (hnsw_index_insert / hnsw_index_remove / hnsw_index_mark_deleted): they are stale");
-    return HNSW_OK;
-}
 
 hnsw_dev::GroupEligible eligible_of(const hnsw_index *idx, const hnsw_labels *l, const hnsw_filter *f) {
     return {(const int32_t *)l->lab.p, f ? (const uint32_t *)f->bits.p : nullptr, idx->iv.n, idx->iv.id_base};
@@ -384,50 +338,35 @@ int grouped_search(hnsw_index *idx, const hnsw_labels *l, const hnsw_filter *f, 
     const int k = p.k;
     const bool rerank = walk_is_inexact(idx);
     int rc;
-    if ((rc = fb.stage.ensure((size_t)b.nq * 4)) || (rc = gb.lab.ensure((size_t)b.nq * k * 4)) || (rc = fb.rnd.ensure((size_t)b.nq * 4))) return rc;
+    if ((rc = fb.stage.ensure((size_t)b.nq * 4)) || (rc = gb.lab.ensure((size_t)b.nq * k * 4))) return rc;
     uint32_t *const d_stage_out = (uint32_t *)fb.stage.p;
     int32_t *const d_lab = (int32_t *)gb.lab.p;
     const hnsw_dev::GroupEligible ge = eligible_of(idx, l, f);
     Ladder L(idx, b.Q, b.nq, b.q_stride, p.ef, p.semantics, d_stage, st, "grouped search");
     // with fewer than k groups (or allowed nodes) no W can serve a query: nobody walks, everybody gets the exact stage
     const bool walked = l->n_groups >= k && (!f || f->n_allowed >= k);
-    bool short_at_end = false;
-    for (bool more = walked; more;) {
-        const int64_t m = L.m;
-        const int e = L.e;
-        if ((rc = fb.wids.ensure((size_t)m * e * 4)) || (rc = fb.wdist.ensure((size_t)m * e * 4)) ||
-            (rerank && ((rc = fb.cand.ensure((size_t)m * e * 4)) || (rc = fb.rids.ensure((size_t)m * e * 4)) || (rc = fb.rdist.ensure((size_t)m * e * 4)))))
-            return rc;
-        if ((rc = L.walk((int32_t *)fb.wids.p, (float *)fb.wdist.p, p.fill))) return rc;
-        const int32_t *wids = L.wb.ids;
-        const float *wdist = L.wb.dist;
-        const uint32_t *wnd = L.wb.nd;
+    LadderLeft left;
+    rc = L.run(walked, [&](Ladder &, int64_t m, int e) -> int {
+        if ((rc = fb.wids.ensure((size_t)m * e * 4)) || (rc = fb.wdist.ensure((size_t)m * e * 4))) return rc;
+        int32_t *const Wi = (int32_t *)fb.wids.p;
+        float *const Wd = (float *)fb.wdist.p;
+        if ((rc = L.walk_raw(Wi, Wd, p.fill))) return rc;
         if (rerank) {
-            // ALL eligible members of W over the float32 rows (the others as padding, k := e); the select reads the re-ranked rows
-            hipLaunchKernelGGL(hnsw_dev::group_cand_kernel, dim3((unsigned)m), dim3(64), 0, st, wids, m, e, ge, (int32_t *)fb.cand.p);
-            if ((rc = launched("group candidate kernel")) ||
-                (rc = launch_rerank(idx, L.Qj, m, L.qs, (const int32_t *)fb.cand.p, e, e, p.fill, (int32_t *)fb.rids.p, (float *)fb.rdist.p, L.wb.nd,
-                                    (uint32_t *)fb.rnd.p, st)))
-                return rc;
-            wids = (const int32_t *)fb.rids.p;
-            wdist = (const float *)fb.rdist.p;
-            wnd = (const uint32_t *)fb.rnd.p;
+            // only the ELIGIBLE members of W go over the float32 rows (the others as padding); the select reads the re-ranked rows
+            hipLaunchKernelGGL(hnsw_dev::group_cand_kernel, dim3((unsigned)m), dim3(64), 0, st, L.wb.ids, m, e, ge, L.wb.ids);
+            if ((rc = launched("group candidate kernel")) || (rc = L.rerank_all(Wi, Wd, p.fill))) return rc;
         }
-        const hnsw_dev::GroupSelectArgs sa{wids, wdist, m, e, k, L.map, ge, b.ids, b.dist, d_lab, L.out(wnd, b.nd, b.nh, d_stage_out)};
+        const hnsw_dev::GroupSelectArgs sa{Wi, Wd, m, e, k, L.map, ge, b.ids, b.dist, d_lab, L.out(b.nd, b.nh, d_stage_out)};
         hipLaunchKernelGGL(hnsw_dev::group_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
-        if ((rc = launched("group select kernel")) || (rc = L.count_short())) return rc;
-        if (L.n_short == 0) break;
-        if ((rc = L.advance(more))) return rc;
-        short_at_end = !more;
-    }
-    if (walked && !short_at_end) return HNSW_OK;
-    // the exact stage for the L.m queries of (L.Qj, L.map): the ladder's last batch, or the caller's own when nobody walked
+        return launched("group select kernel");
+    }, left);
+    if (rc || left == LadderLeft::none) return rc;
+    // the exact stage for the L.m queries of (L.Qj, L.map): the batch the ladder left
     if ((rc = fb.rids.ensure((size_t)L.m * k * 4)) || (rc = fb.rdist.ensure((size_t)L.m * k * 4)) || (rc = gb.rlab.ensure((size_t)L.m * k * 4))) return rc;
     if ((rc = group_exact(idx, l, f, L.Qj, L.m, L.qs, k, p.fill, (int32_t *)fb.rids.p, (float *)fb.rdist.p, (int32_t *)gb.rlab.p, st))) return rc;
-    const hnsw_dev::GroupScatterArgs sc{(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, (const int32_t *)gb.rlab.p, L.m, k, L.map,
-                                        (uint32_t)(f ? f->n_allowed : l->n_labelled), !walked, 0xFFFFFFFFu, b.ids, b.dist, d_lab, b.nd, b.nh, d_stage_out};
-    hipLaunchKernelGGL(hnsw_dev::group_scatter_kernel, dim3((unsigned)L.m), dim3(64), 0, st, sc);
-    return launched("group scatter kernel");
+    return scatter_rows({(const int32_t *)fb.rids.p, (const float *)fb.rdist.p, (const int32_t *)gb.rlab.p, L.m, k, L.map, nullptr, nullptr,
+                         (uint32_t)(f ? f->n_allowed : l->n_labelled), 1, nullptr, left == LadderLeft::fresh, b.ids, b.dist, d_lab, b.nd, b.nh, d_stage_out},
+                        st, "group scatter kernel");
 }
 
 } // namespace
@@ -504,18 +443,11 @@ int32_t hnsw_search_batch_grouped(hnsw_index *idx, const hnsw_labels *labels, co
     if ((rc = check_labels(idx, labels)) || (f && (rc = check_filter(idx, f)))) return rc;
     if (nq == 0) return HNSW_OK;
     HIP_TRY(hipSetDevice(idx->device));
-    HostCall c;
-    bool q_in_place = false;
-    if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
-    hipStream_t st = idx->hs[0];
-    // (from here on copies are queued that read the caller's arrays: no return without a synchronisation)
-    rc = grouped_search(idx, labels, f, *params, c.b, q_in_place ? (float *)idx->scratch.q.p : nullptr, st);
-    if (!rc && hipMemcpyAsync(out_labels, idx->group_scratch.lab.p, (size_t)nq * params->k * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(HNSW_ERR_HIP, "labels download failed");
-    if (!rc && out_stage && hipMemcpyAsync(out_stage, idx->filter_scratch.stage.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(HNSW_ERR_HIP, "stage download failed");
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    return c.finish(idx, "grouped search", st);
+    const HostColumn lab{out_labels, &idx->group_scratch.lab, (size_t)nq * params->k * 4, "labels"};
+    return ladder_host_call(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, out_stage, true, nullptr, nullptr, &lab,
+                            "grouped search", [&](const KnnBatch &b, float *d_stage, hipStream_t st) -> int {
+        return grouped_search(idx, labels, f, *params, b, d_stage, st);
+    });
 }
 
 int32_t hnsw_brute_force_batch_grouped(hnsw_index *idx, const hnsw_labels *labels, const hnsw_filter *f, const float *queries, int64_t nq,
@@ -525,16 +457,12 @@ int32_t hnsw_brute_force_batch_grouped(hnsw_index *idx, const hnsw_labels *label
     if ((rc = check_labels(idx, labels)) || (f && (rc = check_filter(idx, f)))) return rc;
     if (nq == 0) return HNSW_OK;
     HIP_TRY(hipSetDevice(idx->device));
-    HostCall c;
-    if ((rc = idx->group_scratch.lab.ensure((size_t)nq * k * 4)) ||
-        (rc = c.begin(idx, queries, nq, q_stride, k, out_ids, out_dist, nullptr, nullptr, false)))
-        return rc;
-    hipStream_t st = idx->hs[0];
-    rc = group_exact(idx, labels, f, c.b.Q, nq, c.b.q_stride, k, fill, c.b.ids, c.b.dist, (int32_t *)idx->group_scratch.lab.p, st);
-    if (!rc && hipMemcpyAsync(out_labels, idx->group_scratch.lab.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(HNSW_ERR_HIP, "labels download failed");
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    return c.finish(idx, "grouped scan", st);
+    if ((rc = idx->group_scratch.lab.ensure((size_t)nq * k * 4))) return rc;
+    const HostColumn lab{out_labels, &idx->group_scratch.lab, (size_t)nq * k * 4, "labels"};
+    return ladder_host_call(idx, queries, nq, q_stride, k, out_ids, out_dist, nullptr, nullptr, nullptr, false, nullptr, nullptr, &lab, "grouped scan",
+                            [&](const KnnBatch &b, float *, hipStream_t st) -> int {
+        return group_exact(idx, labels, f, b.Q, nq, b.q_stride, k, fill, b.ids, b.dist, (int32_t *)idx->group_scratch.lab.p, st);
+    });
 }
 
 } // extern "C"

@@ -342,39 +342,41 @@ struct RefineBufs {
     }
 };
 
-// Scratch of the ladder that the filtered and the range search share (Ladder, hnsw_filter.hip) and of what each does around it,
-// sized on demand by the call; not index tables: not counted in device_bytes.  One host thread uses a handle and both calls are
-// synchronous, so one LadderBufs serves both.
+// Scratch of the ladder that the filtered, range, grouped and paged searches all climb (Ladder, hnsw_filter.hip), sized on demand
+// by the call; not index tables: not counted in device_bytes.  One host thread uses a handle and every such call is synchronous,
+// so one LadderBufs serves them all.
 struct LadderBufs {
     DevBuf wnd, wnh, wst;                // one stage's walk: evaluations, hops, status of its m queries
     DevBuf list[2], count;               // the queries still unserved, written by one stage and read by the next; how many
     DevBuf q;                            // their vectors, gathered ([m][padded_stride(d)])
+    // half rows / codes (Ladder::walk_exact; range, grouped, paged): one stage's walk before its re-rank ([m][e] ids and
+    // distances); the re-rank's evaluation counts after it ([m])
+    DevBuf cand, cdist, rnd;
 };
+// ... of the filtered calls; the grouped and the paged calls use wids / wdist, rids / rdist and stage for the same purposes
 struct FilterBufs {
     DevBuf wids, wdist;                  // one stage's W ([m][e] ids and distances)
-    DevBuf cnt, cand;                    // per walked query its allowed members of W; half / sq8 rows: the masked W the re-rank reads
-    DevBuf rids, rdist, rnd;             // a compact [m][k] result (re-rank, exact scan) before its rows go to their queries
-    DevBuf stage;                        // out_stage [nq]
+    DevBuf cnt, cand;                    // filtered: per walked query its allowed members of W; half rows / codes: the masked W the re-rank reads
+    DevBuf rids, rdist, rnd;             // a compact [m][k] result (filtered: re-rank, exact scan; grouped: exact stage) before its rows go to their queries
+    DevBuf stage;                        // out_stage [nq]: filtered, grouped and paged (ladder_host_call downloads it)
     // hnsw_search_batch_filtered_each: the masks' device addresses [n_filters], query_filter [nq]; the exact stage's rows
     // (filter_plan): row -> query, tile -> filter, and per row the evaluations to add and whether the query took no walk
     DevBuf masks, which, rows;
 };
-// ... of the grouped calls (hnsw_group.hip), beside the ladder's and the filtered search's buffers, which they use too
+// ... of the grouped calls (hnsw_group.hip) alone
 struct GroupBufs {
     DevBuf best;                         // the exact stage: best[piece][n_labels] words (key << 32 | row), all ones = no node yet
     DevBuf lab, rlab;                    // out_labels [nq][k]; the labels column of a compact [m][k] result
     DevBuf part_words, part_lab;         // ... of a row of many cells: the k smallest words of each of its stripes and their labels
 };
-// ... of the paged calls (hnsw_after.hip), beside the ladder's and the filtered search's buffers, which they use too
+// ... of the paged calls (hnsw_after.hip) alone
 struct AfterBufs {
     DevBuf lo;                           // the cursors as bounds in word space (uint64 [nq], by query)
-    DevBuf cand, cdist, rnd;             // half rows / codes: one stage's walk before its re-rank; its evaluations after it
 };
-// ... of the range calls.  What a caller keeps (lims, ids, distances, counters) belongs to the hnsw_range_result instead.
+// ... of the range calls alone.  What a caller keeps (lims, ids, distances, counters) belongs to the hnsw_range_result instead.
 constexpr int RANGE_STAGES = 11;         // the longest ladder: ef = 1, 2, 4, ... 1024
 struct RangeBufs {
-    DevBuf wids[RANGE_STAGES], wdist[RANGE_STAGES];  // every stage's W ([m][e], half / sq8 rows: re-ranked), kept until the fill
-    DevBuf cand, cdist, rnd;                         // one stage's walk before its re-rank; its evaluations after it
+    DevBuf wids[RANGE_STAGES], wdist[RANGE_STAGES];  // every stage's W ([m][e], half rows / codes: re-ranked), kept until the fill
     DevBuf cnt, src, stage, nd, nh;                  // per query: segment length (int64 [nq + 1]), its row of its stage's W, counters
     DevBuf pre;                                      // ... under a mask: the length of the in-range prefix the segment was taken from
     DevBuf counts, offs;                             // the exact scan: hits per (query, slab) (uint64 [m][slabs] + 1) and their exclusive sum
@@ -579,13 +581,13 @@ struct hnsw_index {
     // option "filter_collect": the filtered searches answer from every node the walk evaluates, not from the final W only
     // (hnsw_search_collect_kernel; k <= 128, exact-row formats: it excludes half_rows and sq8_rows).  Not saved.
     bool filter_collect = false;
-    // the stages of hnsw_search_batch_filtered and of the range calls (ladder_scratch: of both), the range calls' exact scan: ONE
-    // such call in flight per handle
+    // the stages of the filtered, range, grouped and paged calls (ladder_scratch: of all four; who uses what of the others: beside
+    // the types), the range calls' exact scan: ONE such call in flight per handle
     hnsw_host::LadderBufs ladder_scratch;
     hnsw_host::FilterBufs filter_scratch;
     hnsw_host::RangeBufs range_scratch;
-    hnsw_host::GroupBufs group_scratch;  // the grouped calls: they share ladder_scratch and filter_scratch with the filtered call
-    hnsw_host::AfterBufs after_scratch;  // the paged calls (hnsw_after.hip): likewise
+    hnsw_host::GroupBufs group_scratch;
+    hnsw_host::AfterBufs after_scratch;
     bool multi_replica = false;          // owned by an hnsw_multi (hnsw_multi_replica) or an hnsw_sharded (hnsw_sharded_shard): not grown or shrunk on its own (hnsw_index_insert, hnsw_index_remove)
     // the graph epoch: every successful hnsw_index_insert and hnsw_index_remove moves it on (adopt_graph).  A filter records the
     // epoch it was made in: n alone would let a mask through after "remove 5, insert 5"
@@ -610,7 +612,27 @@ namespace hnsw_dev {
 
 // (MaskWords / mask_words, a mask's words as a kernel reads them: hnsw_device.hip.h, beside the collect kernel's use of them)
 
-// The end of a ladder stage's select kernel (filter_select_kernel, range_select_kernel), one lane per walked query: row i of the
+// is the id_base-based id one of the n nodes (a filled entry of W is not) ...
+__device__ __forceinline__ bool is_node(int64_t n, int32_t id_base, int32_t id) {
+    const int64_t v = (int64_t)id - id_base;
+    return v >= 0 && v < n;
+}
+// ... and allowed by the mask -- the test of the four select kernels; group_label and after_eligible, whose mask is optional, put
+// their own conditions on top
+__device__ __forceinline__ bool node_allowed(MaskWords bits, int64_t n, int32_t id_base, int32_t id) {
+    const int64_t v = (int64_t)id - id_base;
+    return is_node(n, id_base, id) && ((bits[v >> 5] >> (v & 31)) & 1u);
+}
+
+// The counters of a query the exact stage answers (the scatter kernel, after_merge_kernel, range_count_kernel): `add` evaluations
+// on top of its walks' -- fresh: it took no walk, they start from 0 and it made no hop -- and the exact stage's number
+__device__ __forceinline__ void exact_settle(uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage, int64_t q, uint32_t add, bool fresh) {
+    out_nd[q] = (fresh ? 0u : out_nd[q]) + add;
+    if (fresh) out_nh[q] = 0u;
+    out_stage[q] = 0xFFFFFFFFu;
+}
+
+// The end of a ladder stage's select kernel (filter_, range_, group_, after_select_kernel), one lane per walked query: row i of the
 // stage's batch belongs to query q.  Its walk's counters go to the query's; served, it gets the stage's number, else a place in
 // the short list through one atomic counter (the host sorts the list: the next stage's order, and with it nothing a caller can
 // see, depends on who came first).
@@ -628,6 +650,26 @@ __device__ __forceinline__ void ladder_settle(const LadderOut &o, int64_t i, int
     if (served) o.out_stage[q] = o.stage;
     else o.short_list[atomicAdd(o.short_count, 1u)] = (int32_t)q;     // (at most m entries: one per block)
 }
+
+// filter_scatter_kernel (hnsw_filter.hip; scatter_rows launches it): rows of a compact result to the rows of the queries they belong to
+struct ScatterArgs {
+    const int32_t *rids;       // [m][k] compact results
+    const float *rdist;
+    const int32_t *rlab;       // null, or their labels column (the grouped calls), which goes to out_labels
+    int64_t m;
+    int32_t k;
+    const int32_t *map;        // [m] row i belongs to query map[i] (< 0: a padding row, dropped); null: to query i
+    const int32_t *cnt;        // null: every row; else only the rows with cnt[i] >= k (the served ones)
+    const uint32_t *add;       // null, or [m]: evaluations to add to out_nd
+    uint32_t add_const;        // ... plus this many
+    int32_t exact;             // 1: the exact stage's rows, their counters by exact_settle; 0: a stage's re-ranked rows, out_nd += add
+    const int32_t *fresh_of;   // exact: null, or [m]: `fresh` per row
+    int32_t fresh;             // exact: 1: the query took no walk
+    int32_t *out_ids;          // [nq][k]
+    float *out_dist;
+    int32_t *out_labels;
+    uint32_t *out_nd, *out_nh, *out_stage;
+};
 
 } // namespace hnsw_dev
 
@@ -867,8 +909,21 @@ inline int codes_transform_queries(const ::hnsw_index *idx, const float *Q, int6
 inline bool walk_is_inexact(const ::hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_HALF || walks_codes(idx); }
 // the filter the unfiltered searches answer under: the live nodes while some are marked deleted, else none
 inline const ::hnsw_filter *live_filter(const ::hnsw_index *idx) { return idx->n_deleted > 0 ? idx->live.get() : nullptr; }
-// hnsw_filter.hip: what every filtered entry point checks of one filter of the call (null, foreign, outgrown, stale: HNSW_ERR_BAD_ARG)
-int check_filter(const ::hnsw_index *idx, const ::hnsw_filter *f);
+// What every entry point checks of an object bound to a handle, its n and its graph epoch -- a filter, a labels object -- (null,
+// foreign, outgrown, stale: HNSW_ERR_BAD_ARG); noun and plural: how the messages name it
+template <class Bound> int check_bound(const ::hnsw_index *idx, const Bound *h, const char *noun, bool plural) {
+    const char *const was = plural ? "were" : "was";
+    if (!h) return fail(HNSW_ERR_BAD_ARG, "null %s", noun);
+    if (h->idx != idx) return fail(HNSW_ERR_BAD_ARG, "the %s %s made for another index", noun, was);
+    if (h->n != idx->iv.n)
+        return fail(HNSW_ERR_BAD_ARG, "the %s %s made for %lld nodes, the index has grown to %lld", noun, was, (long long)h->n, (long long)idx->iv.n);
+    if (h->epoch != idx->epoch)
+        return fail(HNSW_ERR_BAD_ARG, "the %s %s made before the index last changed (hnsw_index_insert / hnsw_index_remove / hnsw_index_mark_deleted): %s stale",
+                    noun, was, plural ? "they are" : "it is");
+    return HNSW_OK;
+}
+inline int check_filter(const ::hnsw_index *idx, const ::hnsw_filter *f) { return check_bound(idx, f, "filter", false); }
+inline int check_labels(const ::hnsw_index *idx, const ::hnsw_labels *l) { return check_bound(idx, l, "labels", true); }
 // hnsw_filter.hip: a filter of idx's n nodes (and epoch) with its mask allocated (not initialised) and the mask's own address behind it
 int new_filter(const ::hnsw_index *idx, int64_t n, std::unique_ptr<::hnsw_filter> &f);
 // hnsw_filter.hip: f's n_allowed counted on the device (filter_popcount_kernel; the bits past n cleared); and_with (optional, device
@@ -885,11 +940,15 @@ int renumbered_live_filter(const ::hnsw_index *idx, const int32_t *new_id, int64
 int renumbered_keys(const ::hnsw_index *idx, const int32_t *new_id, int64_t n_new, const int64_t *append_keys, std::unique_ptr<KeyTables> &out);
 // hnsw_keys.hip: keys_translate_kernel on st: d_out[i] = the key of node d_ids[i] - id_base, or missing where that is no node (m entries)
 int keys_translate(const ::hnsw_index *idx, const int32_t *d_ids, int64_t m, int64_t missing, int64_t *d_out, hipStream_t st);
-// hnsw_filter.hip: the escalation both the filtered and the range search run -- e = ef, 2 ef, ... 1024: the batch is walked with
-// (ef = k = e, raw_walk), the caller's select kernel serves what it can and appends the other queries to the short list
-// (ladder_settle) and only those, gathered into one compact batch, are walked again.  Everything is queued on st and waited for
-// where the host needs a number (the tie-overflow word, the short count).  A failure returns with work queued: the entry points
-// synchronise st before they return it.
+// hnsw_filter.hip: the escalation the filtered, range, grouped and paged searches run -- e = ef, 2 ef, ... 1024: the batch is walked
+// with (ef = k = e, raw_walk), the caller's select kernel serves what it can and appends the other queries to the short list
+// (ladder_settle) and only those, gathered into one compact batch, are walked again.  run is the loop; a search is one stage body
+// handed to it and what it does with the batch run leaves.  Everything is queued on st and waited for where the host needs a
+// number (the tie-overflow word, the short count).  A failure returns with work queued: the entry points synchronise st before
+// they return it.
+// what run leaves for the exact stage: nothing (every query was served), or the batch (Qj, m, qs, map) -- `walked`: queries still
+// short at e = 1024, their counters hold their walks'; `fresh`: nobody walked, the batch is still the caller's (exact_settle's fresh)
+enum class LadderLeft { none, walked, fresh };
 struct Ladder {
     ::hnsw_index *idx;
     const float *Q;                      // the caller's batch (device address) ...
@@ -917,22 +976,49 @@ struct Ladder {
           qs(q_stride_), e(ef) {}
     // stage 0 for the `count` queries of `list` only (host, ascending): gathered, as a later stage's batch is
     int start_from(const int32_t *list, int64_t count);
+    // The loop.  walks false: nobody walks, the batch goes to the exact stage as it is.  Else, until nobody is short or e cannot
+    // grow: stage(*this, m, e) sizes the caller's buffers, walks and launches the caller's select kernel; the short queries are
+    // counted and, if any, become the next stage's batch.  left: what is left for the exact stage.
+    template <class Stage> int run(bool walks, Stage &&stage, LadderLeft &left) {
+        left = walks ? LadderLeft::none : LadderLeft::fresh;
+        for (bool more = walks; more;) {
+            int rc;
+            if ((rc = stage(*this, m, e)) || (rc = count_short())) return rc;
+            if (n_short == 0) break;
+            if ((rc = advance(more))) return rc;
+            if (!more) left = LadderLeft::walked;
+        }
+        return HNSW_OK;
+    }
     // W_e of the batch into wids / wdist ([m][e]): the host form's search of (ef = e, k = e), its tie-overflow repair included,
-    // without a re-rank; the short counter zeroed
+    // without a re-rank; the short counter zeroed; evals = the walk's evaluation counts
     int walk(int32_t *wids, float *wdist, int32_t fill);
-    // what the select kernel's ladder_settle takes: wnd = the evaluations to add (the walk's, or the re-rank's sum)
-    hnsw_dev::LadderOut out(const uint32_t *wnd, uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage) const;
-    // after the select kernel: n_short
+    // W_e of the batch OVER THE FLOAT32 ROWS into Wi / Wd ([m][e]): walk, and for half rows and codes -- whose walk lands in the
+    // ladder's own cand / cdist -- the re-rank of all its members (launch_rerank with k := e); evals = the evaluations of both.
+    // The two halves apart, for a caller that turns some of wb.ids into padding between them (the grouped search).
+    int walk_exact(int32_t *Wi, float *Wd, int32_t fill) {
+        const int rc = walk_raw(Wi, Wd, fill);
+        return rc ? rc : rerank_all(Wi, Wd, fill);
+    }
+    int walk_raw(int32_t *Wi, float *Wd, int32_t fill);
+    int rerank_all(int32_t *Wi, float *Wd, int32_t fill);
+    const uint32_t *evals = nullptr;     // [m] the stage's evaluations to add: what out() hands ladder_settle
+    // what the select kernel's ladder_settle takes
+    hnsw_dev::LadderOut out(uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage) const;
+    // after the select kernel: n_short, read once per walk (a stage body that needs the number may ask before run does)
     int count_short();
-    // the n_short > 0 short queries, ascending, become the batch; false: they were short at e = 1024, the ladder is over
-    int advance(bool &more);
-    // the queries of the batch advance made (host, ascending)
+    // the queries of the batch the last stage left (host, ascending)
     const std::vector<int32_t> &batch_queries() const { return shorts; }
 private:
+    // the n_short > 0 short queries, ascending, become the batch; false: they were short at e = 1024, the ladder is over
+    int advance(bool &more);
     int gather();                        // the m queries of `map` become the rows of the ladder's own matrix
     int cur = 0;                         // which list buffer `map` is
+    bool counted = false;                // n_short is this walk's
     std::vector<int32_t> shorts;
 };
+// hnsw_filter.hip: filter_scatter_kernel on st, one wave per row of a; what: the kernel's name in a launch failure's message
+int scatter_rows(const hnsw_dev::ScatterArgs &a, hipStream_t st, const char *what);
 // hnsw_capi.hip: hnsw_search_batch; ko (optional): the rows go to ko->keys as keys and out_ids may be null (hnsw_search_batch_keyed);
 // out_stage (optional): as the filtered call writes it while nodes are marked, zero otherwise
 // rows (optional; queries is then null and q_stride padded_stride(d)): the queries are rows of the index, gathered on the device
@@ -1004,6 +1090,36 @@ struct HostCall {
     // the block; a failed synchronisation reads "<what> failed: ..."
     int finish(::hnsw_index *idx, const char *what, hipStream_t st);
 };
+// a further [nq][..] column a ladder host call downloads from the handle's scratch (the grouped calls' labels)
+struct HostColumn {
+    void *host;
+    const DevBuf *dev;
+    size_t bytes;
+    const char *noun;                               // in "<noun> download failed"
+};
+// The frame of the filtered, grouped and paged host calls, graph and brute-force forms: HostCall::begin (ko / rows: see HostCall),
+// body(batch, d_stage, st) -- d_stage: see knn_search -- on the handle's stream, the downloads of `extra` (optional) and of
+// out_stage (optional; from filter_scratch.stage), then finish(what).  An error after begin waits for the stream before it returns.
+template <class Body>
+int ladder_host_call(::hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int k, int32_t *out_ids, float *out_dist,
+                     uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage, bool allow_small, const KeysOut *ko, const RowsIn *rows,
+                     const HostColumn *extra, const char *what, Body &&body) {
+    HostCall c;
+    c.ko = ko;
+    c.rows = rows;
+    bool q_in_place = false;
+    int rc;
+    if ((rc = c.begin(idx, queries, nq, q_stride, k, out_ids, out_dist, out_nd, out_nh, allow_small, &q_in_place))) return rc;
+    hipStream_t st = idx->hs[0];
+    // (from here on copies are queued that read the caller's arrays: no return without a synchronisation)
+    rc = body(c.b, q_in_place ? (float *)idx->scratch.q.p : nullptr, st);
+    if (!rc && extra && hipMemcpyAsync(extra->host, extra->dev->p, extra->bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = fail(HNSW_ERR_HIP, "%s download failed", extra->noun);
+    if (!rc && out_stage && hipMemcpyAsync(out_stage, idx->filter_scratch.stage.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = fail(HNSW_ERR_HIP, "stage download failed");
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    return c.finish(idx, what, st);
+}
 
 // log2 entries of the per-query LDS visited cache (never changes results)
 inline int search_vt_bits(const hnsw_index *idx, int ef) {

@@ -1,8 +1,8 @@
 // hnsw_range.hip -- range search: every stored vector within distance `radius` of a query (hnsw_range_search_batch,
 // hnsw_range_brute_force_batch, hnsw_range_result_*).  The result has no fixed k: per query a segment of (id, distance) pairs,
 // ascending under the exact scan's order, found through lims [nq + 1].  The search composes pieces that exist already -- the
-// unchanged walk (knn_search with k := ef: W stays on the device), the re-rank kernel (hnsw_rerank.hip) -- with a scan that selects
-// by a distance bound instead of by rank:
+// ladder's loop and its W over the float32 rows (Ladder::run, Ladder::walk_exact, hnsw_filter.hip) -- with a stage body that keeps
+// every stage's W, a select rule of its own and a scan that selects by a distance bound instead of by rank:
 //   ladder   e = ef, 2 ef, ... 1024: a query is served at the first e whose W is not saturated (the walk ran out of graph, or W's
 //            last member is out of range); its segment is W's in-range prefix.  Only the queries still saturated are walked again,
 //            gathered into one compact batch;
@@ -17,7 +17,7 @@
 //                           position among the slab's hits in id order (ballot, prefix count): the layout is deterministic.
 //   hnsw_range_scan_masked_kernel<NCH, METRIC, PASS>  the same two passes over the rows an allow-mask names (the filtered range
 //                           calls; the plain ones while nodes are marked deleted): RangeHits<.., MASKED = true>, whose skip / admits
-//                           are those of ScanTopK<NCH, true> -- a disallowed row is never counted, stored or sorted, and a mask
+//                           are ScanMask's, as every policy's -- a disallowed row is never counted, stored or sorted, and a mask
 //                           word without a set bit is stepped over unloaded.
 //   range_count_kernel      per exact-stage query the sum of its slabs' counts (from the exclusive sum), its counters and stage.
 //   range_unpack_kernel     the sorted words of an exact-stage query as ids (+ id_base) and key_to_dist.
@@ -25,13 +25,13 @@
 //                           Served: its count, stage and row.  Under a mask the stage test is the same one (the mask has no say in
 //                           "saturated"); a served query records the prefix length and the number of allowed members in it: the
 //                           second is its segment length.  Saturated: appended to the short list (ladder_settle); the ladder
-//                           (Ladder, hnsw_filter.hip) gathers them for the next walk.
+//                           gathers them for the next walk.
 //   range_fill_kernel       the served queries' prefixes from their stages' W to lims[q], once every size is known.  Under a mask:
 //                           the allowed members of the prefix, compacted by ballot and prefix count, 64 entries per pass, in W's order.
 // Between the scan's passes: an exclusive sum of the counts (hipcub::DeviceScan), the grand total read on the host, the result
 // allocated.  After the fill hipcub::DeviceSegmentedRadixSort orders each exact-stage segment by its 64-bit words: ascending words
 // = the total order (distance key, node id), no drops however many ties.  Vector stores only.  All scratch is the handle's
-// (LadderBufs, RangeBufs): one range or filtered call in flight per handle; lims, ids, distances and counters belong to the
+// (LadderBufs, RangeBufs): one filtered, range, grouped or paged call in flight per handle; lims, ids, distances and counters belong to the
 // hnsw_range_result.
 #include "hnsw_internal.h"
 #include "hnsw_scan_device.hip.h"
@@ -68,21 +68,8 @@ template <int METRIC> __device__ __forceinline__ void range_key_bounds(float rad
 }
 
 // The hits of one (tile, slab) wave (scan_slab's Select): counted (PASS 0), or written where PASS 0's counts say (PASS 1)
-// MASKED: as ScanTopK<NCH, true> -- one bit per row, bit row & 31 of word row >> 5, ceil(n / 32) words; a row whose bit is clear is
-// no hit, and a 32-row word without a set bit is stepped over without loading its rows.  (The mask is a base the unmasked form does
-// not have: its kernels are what they were before there was a mask.)
-template <bool MASKED> struct RangeMask {
-    MaskWords mask;
-    __device__ __forceinline__ explicit RangeMask(const uint32_t *mask_) : mask(mask_words(mask_)) {}
-    __device__ __forceinline__ bool skip(int64_t base) const { return uniform((int)mask[base >> 5]) == 0; }
-    __device__ __forceinline__ bool admits(int64_t row, bool in_slab) const { return in_slab && ((mask[row >> 5] >> (row & 31)) & 1u); }
-};
-template <> struct RangeMask<false> {
-    __device__ __forceinline__ explicit RangeMask(const uint32_t *) {}
-    __device__ __forceinline__ bool skip(int64_t) const { return false; }
-    __device__ __forceinline__ bool admits(int64_t, bool in_slab) const { return in_slab; }
-};
-template <int NCH, int METRIC, int PASS, bool MASKED = false> struct RangeHits : RangeMask<MASKED> {
+// MASKED: only the rows the mask allows (skip and admits: ScanMask).
+template <int NCH, int METRIC, int PASS, bool MASKED = false> struct RangeHits : ScanMask<MASKED> {
     static constexpr int T = scan_tile(NCH);
     const RangeScanArgs &a;
     uint32_t klo, khi;
@@ -92,7 +79,7 @@ template <int NCH, int METRIC, int PASS, bool MASKED = false> struct RangeHits :
     int cnt[T], lim[T];
     uint64_t *dst[T];
 
-    __device__ __forceinline__ explicit RangeHits(const RangeScanArgs &a_, const uint32_t *mask_ = nullptr) : RangeMask<MASKED>(mask_), a(a_) {}
+    __device__ __forceinline__ explicit RangeHits(const RangeScanArgs &a_, const uint32_t *mask_ = nullptr) : ScanMask<MASKED>(mask_), a(a_) {}
     __device__ __forceinline__ void begin(int64_t q0_, int tq_, int64_t slab_) {
         q0 = q0_; tq = tq_; slab = slab_;
         lane = threadIdx.x & 63;
@@ -166,9 +153,7 @@ range_count_kernel(const RangeCountArgs a) {
     const int64_t c = (int64_t)(a.offs[(i + 1) * a.n_slabs] - a.offs[i * a.n_slabs]);
     a.cnt[q] = c;
     a.xcnt[i] = c;
-    a.out_nd[q] = (a.fresh ? 0u : a.out_nd[q]) + a.n;
-    if (a.fresh) a.out_nh[q] = 0u;
-    a.out_stage[q] = 0xFFFFFFFFu;
+    exact_settle(a.out_nd, a.out_nh, a.out_stage, q, a.n, a.fresh != 0);
 }
 
 // one wave per exact-stage query: sorted words -> ids and distances at lims[q]
@@ -203,12 +188,6 @@ struct RangeSelectArgs {
     int32_t *pre;              // [nq] under a mask: the served query's prefix length
 };
 
-// is the id_base-based id one of the n nodes, and allowed
-__device__ __forceinline__ bool range_allows(MaskWords bits, int64_t n, int32_t id_base, int32_t id) {
-    const int64_t v = (int64_t)id - id_base;
-    return v >= 0 && v < n && ((bits[v >> 5] >> (v & 31)) & 1u);
-}
-
 __global__ void __launch_bounds__(64)
 range_select_kernel(const RangeSelectArgs a) {
     const int lane = threadIdx.x;
@@ -221,7 +200,7 @@ range_select_kernel(const RangeSelectArgs a) {
         const int j = j0 + lane;
         const bool hit = j < a.e && a.wids[i * a.e + j] >= a.id_base && a.wdist[i * a.e + j] <= a.radius;
         in += popc(ballot(hit));
-        if (a.mask) al += popc(ballot(hit && range_allows(bits, a.n, a.id_base, a.wids[i * a.e + j])));
+        if (a.mask) al += popc(ballot(hit && node_allowed(bits, a.n, a.id_base, a.wids[i * a.e + j])));
     }
     // saturated: |W| = e and its last member is in range, that is all e entries are -- whatever the mask says
     if (lane == 0) {
@@ -265,7 +244,7 @@ range_fill_kernel(const RangeFillArgs a) {
         for (int j0 = 0; j0 < pre && at < c; j0 += 64) {
             const int j = j0 + lane;
             const int32_t id = j < pre ? a.wids[s][from + j] : a.id_base - 1;
-            const bool ok = j < pre && range_allows(bits, a.n, a.id_base, id);
+            const bool ok = j < pre && node_allowed(bits, a.n, a.id_base, id);
             const uint64_t m = ballot(ok);
             const int64_t pos = at + popc(m & ((1ull << lane) - 1ull));
             if (ok && pos < c) {
@@ -404,31 +383,22 @@ int exact_fill(hnsw_index *idx, const ExactPlan &x, float radius, hnsw_range_res
 int range_ladder(hnsw_index *idx, const hnsw_filter *f, const hnsw_range_params &p, const float *Q, int64_t nq, int64_t q_stride, float *d_stage, hipStream_t st,
                  ExactPlan &x, std::vector<int32_t> &e_of) {
     RangeBufs &rb = idx->range_scratch;
-    const bool rerank = walk_is_inexact(idx);
-    int rc;
     Ladder L(idx, Q, nq, q_stride, p.ef, p.semantics, d_stage, st, "range search");
-    x.m = 0;
-    for (bool more = true; more;) {
-        const int64_t m = L.m;
-        const int e = L.e;
+    LadderLeft left;
+    int rc;
+    rc = L.run(true, [&](Ladder &, int64_t m, int e) -> int {
         DevBuf &Wi = rb.wids[L.stage], &Wd = rb.wdist[L.stage];
-        if ((rc = Wi.ensure((size_t)m * e * 4)) || (rc = Wd.ensure((size_t)m * e * 4)) ||
-            (rerank && ((rc = rb.cand.ensure((size_t)m * e * 4)) || (rc = rb.cdist.ensure((size_t)m * e * 4)) || (rc = rb.rnd.ensure((size_t)m * 4)))))
-            return rc;
+        if ((rc = Wi.ensure((size_t)m * e * 4)) || (rc = Wd.ensure((size_t)m * e * 4))) return rc;
         e_of.push_back(e);
-        if ((rc = L.walk((int32_t *)(rerank ? rb.cand.p : Wi.p), (float *)(rerank ? rb.cdist.p : Wd.p), HNSW_FILL_OHNSW))) return rc;
-        // half / sq8 rows: all members of W over the float32 rows, k := e
-        if (rerank && (rc = launch_rerank(idx, L.Qj, m, L.qs, L.wb.ids, e, e, HNSW_FILL_OHNSW, (int32_t *)Wi.p, (float *)Wd.p, L.wb.nd, (uint32_t *)rb.rnd.p, st)))
-            return rc;
+        if ((rc = L.walk_exact((int32_t *)Wi.p, (float *)Wd.p, HNSW_FILL_OHNSW))) return rc;
         const hnsw_dev::RangeSelectArgs sa{(const int32_t *)Wi.p, (const float *)Wd.p, m, e, L.map, p.radius, idx->iv.id_base, (int64_t *)rb.cnt.p,
-                                           (int32_t *)rb.src.p,
-                                           L.out(rerank ? (const uint32_t *)rb.rnd.p : L.wb.nd, (uint32_t *)rb.nd.p, (uint32_t *)rb.nh.p, (uint32_t *)rb.stage.p),
+                                           (int32_t *)rb.src.p, L.out((uint32_t *)rb.nd.p, (uint32_t *)rb.nh.p, (uint32_t *)rb.stage.p),
                                            f ? (const uint32_t *)f->bits.p : nullptr, idx->iv.n, (int32_t *)rb.pre.p};
         hipLaunchKernelGGL(hnsw_dev::range_select_kernel, dim3((unsigned)m), dim3(64), 0, st, sa);
-        if ((rc = launched("range select kernel")) || (rc = L.count_short())) return rc;
-        if (L.n_short == 0) return HNSW_OK;
-        if ((rc = L.advance(more))) return rc;
-    }
+        return launched("range select kernel");
+    }, left);
+    x.m = 0;
+    if (rc || left == LadderLeft::none) return rc;
     x.Q = L.Qj; x.m = L.m; x.q_stride = L.qs; x.map = L.map;
     return HNSW_OK;
 }

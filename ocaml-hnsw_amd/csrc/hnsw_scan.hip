@@ -24,14 +24,11 @@ namespace hnsw_dev {
 
 // (SCAN_BUF, SCAN_EMPTY, ScanArgs, scan_flush and its helpers: hnsw_scan_device.hip.h -- the paged scan, hnsw_after.hip, keeps its lists the same way)
 
-// The top-k selection of one (tile, slab) wave (scan_slab's Select).  MASKED: `mask` holds one bit per row, bit row & 31 of word
-// row >> 5, ceil(n / 32) words; a row whose bit is clear contributes no candidate, and a 32-row word without a set bit is stepped
-// over without loading its rows.
-template <int NCH, bool MASKED> struct ScanTopK {
+// The top-k selection of one (tile, slab) wave (scan_slab's Select).  MASKED: only the rows the mask allows (skip and admits: ScanMask).
+template <int NCH, bool MASKED> struct ScanTopK : ScanMask<MASKED> {
     static constexpr int T = scan_tile(NCH);
     static constexpr int LIMIT = SCAN_BUF - 4 * scan_rows(NCH);   // a buffer up to here takes the survivors of one more pass over the UB batches
     const ScanArgs &a;
-    MaskWords mask;
     // per query of the tile: its list's two halves, which half is current (bit t of par), the threshold word, the buffer's fill
     uint64_t (*bufs)[SCAN_BUF], *sorted, *lists0;
     int64_t list_step;
@@ -40,7 +37,7 @@ template <int NCH, bool MASKED> struct ScanTopK {
     uint32_t par;
     bool full;
 
-    __device__ __forceinline__ ScanTopK(const ScanArgs &a_, const uint32_t *mask_) : a(a_), mask(mask_words(mask_)) {}
+    __device__ __forceinline__ ScanTopK(const ScanArgs &a_, const uint32_t *mask_) : ScanMask<MASKED>(mask_), a(a_) {}
     __device__ __forceinline__ void begin(int64_t q0, int tq_, int64_t slab) {
         __shared__ uint64_t bufs_all[SCAN_WAVES][T][SCAN_BUF];
         __shared__ uint64_t sorted_all[SCAN_WAVES][SCAN_BUF];
@@ -60,10 +57,6 @@ template <int NCH, bool MASKED> struct ScanTopK {
             if (t < tq) for (int j = lane; j < a.k; j += 64) lists0[t * list_step + j] = SCAN_EMPTY;
         }
         scan_wave_sync();
-    }
-    __device__ __forceinline__ bool skip(int64_t base) const { return MASKED && uniform((int)mask[base >> 5]) == 0; }
-    __device__ __forceinline__ bool admits(int64_t row, bool in_slab) const {
-        return in_slab && (!MASKED || ((mask[row >> 5] >> (row & 31)) & 1u));
     }
     __device__ __forceinline__ void take(int t, uint32_t key, int64_t row, bool ok) {
         if (ballot(key <= (uint32_t)(thr[t] >> 32))) {           // rare: some row of the four may be among the k smallest

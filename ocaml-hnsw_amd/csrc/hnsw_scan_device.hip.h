@@ -1,5 +1,5 @@
-// hnsw_scan_device.hip.h -- the one body of the exact scans: the k-scan and its masked form (hnsw_scan.hip) and the range scan's
-// two passes (hnsw_range.hip).  scan_slab walks the rows of one (tile, slab) wave and hands the key of every (row, query) pair to
+// hnsw_scan_device.hip.h -- the one body of the exact scans: the k-scan and its masked form (hnsw_scan.hip), the range scan's
+// two passes (hnsw_range.hip), the grouped scan (hnsw_group.hip) and the paged scan (hnsw_after.hip).  scan_slab walks the rows of one (tile, slab) wave and hands the key of every (row, query) pair to
 // a selection policy; what is kept of them is the policy's business, the arithmetic is here once: the lane grid, the fmaf chain,
 // the reduce16 tree and dist_to_key of every other kernel, so the keys are the bits of hnsw_distance_batch.
 #pragma once
@@ -113,6 +113,22 @@ __device__ __forceinline__ void scan_slab(const IndexView &iv, const float *Q, i
     }
     sel.end();
 }
+
+// The mask members of every selection policy (ScanTopK, ScanAfter, ScanGroupBest, RangeHits), as a base.  MASKED: `mask` holds one
+// bit per row, bit row & 31 of word row >> 5, ceil(n / 32) words; a row whose bit is clear is no candidate, and a 32-row word
+// without a set bit is stepped over without loading its rows.  The unmasked form holds nothing: its kernels are what they would be
+// if there were no masks.
+template <bool MASKED> struct ScanMask {
+    MaskWords mask;
+    __device__ __forceinline__ explicit ScanMask(const uint32_t *mask_) : mask(mask_words(mask_)) {}
+    __device__ __forceinline__ bool skip(int64_t base) const { return uniform((int)mask[base >> 5]) == 0; }
+    __device__ __forceinline__ bool admits(int64_t row, bool in_slab) const { return in_slab && ((mask[row >> 5] >> (row & 31)) & 1u); }
+};
+template <> struct ScanMask<false> {
+    __device__ __forceinline__ explicit ScanMask(const uint32_t *) {}
+    __device__ __forceinline__ bool skip(int64_t) const { return false; }
+    __device__ __forceinline__ bool admits(int64_t, bool in_slab) const { return in_slab; }
+};
 
 // ---- what the scans that keep the k smallest words per (query, slab) share (ScanTopK, hnsw_scan.hip; ScanAfter, hnsw_after.hip) ----
 
