@@ -1683,6 +1683,67 @@ int32_t hnsw_brute_force_batch_after(hnsw_index *idx, const hnsw_filter *f /* ma
                                      const float *queries, int64_t nq, int64_t q_stride, int32_t k, int32_t fill, int32_t *out_ids,
                                      float *out_dist, hnsw_cursor *out_next /* optional [nq] */);
 
+/* ++++ diversified k-NN search: greedy maximal marginal relevance (MMR) over a pool of candidates ++++
+ * On real corpora the k nearest are near-duplicates of each other: chunks of one document, re-posts, product variants.  MMR takes
+ * a POOL of p > k candidates and picks k of them greedily, trading nearness to the query against nearness to what is already
+ * picked.  It needs no labels (hnsw_search_batch_grouped does), only the vectors, and those are resident: the pool's ids and rows
+ * never cross the link, only [nq][k] comes down.
+ *
+ * 0. THE OPERATOR: hnsw_diversify_batch (host arrays) and hnsw_diversify_batch_device (device pointers, asynchronous on `stream`).
+ *    ONE definition; the two searches of point 4 are compositions over it.
+ *    CANDIDATES are exactly hnsw_rerank_batch's: cand[q][0 .. cand_stride) id_base-based, entries < id_base are padding, the ids
+ *    of a row distinct, cand_stride in 1..1024.  In the host form an id >= id_base + n is HNSW_ERR_BAD_ARG, named, refused
+ *    before any launch; the device form skips it.  C is the real candidates of a row, c = |C|.
+ * 1. THE NUMBERS.  r(v), the RELEVANCE, is the float hnsw_distance_batch returns for (query q, node v): over the float32 rows
+ *    whatever row_format says.  rank(v) is v's position in the row hnsw_rerank_batch returns for the same candidates with
+ *    k = cand_stride -- the order (key, id) of hnsw_brute_force_batch; every tie below is broken by it, no new order is invented.
+ *    D(s, v), the PAIR DISTANCE, is the float hnsw_distance_batch returns with the stored float32 row of s as the query and v as
+ *    the id.  Under HNSW_METRIC_COSINE the twin contract holds as everywhere: the call answers with the bits of the inner-product
+ *    index over N(X) called with N(Q); the stored rows are not normalised again.
+ * 2. SELECTION.  mu = fl(1.0f - lambda), computed once in float32.  Pick 1 is the candidate of rank 0.  After the picks S, for every
+ *    v not yet picked m(v) = min over s in S of D(s, v) and
+ *        g(v) = fl( fl(lambda * r(v)) - fl(mu * m(v)) )
+ *    -- three separately rounded float32 operations, no fused multiply-add (numpy: lambda * r - mu * m on float32 arrays).  The next
+ *    pick is the v with the smallest g, compared as IEEE values (-0 equals +0); among equal g the smallest rank wins.  Repeat until
+ *    k are picked or C is exhausted.
+ * 3. OUTPUT, in SELECTION ORDER, which is not ascending by distance: out_ids[q][j] id_base-based, out_dist[q][j] = r, out_div[q][j]
+ *    (optional) = m at the moment of selection, +inf for pick 1.  Past min(k, c) ids and distances take hnsw_rerank_batch's fill
+ *    (id -1; NaN or +inf) and out_div the same float.
+ *    CONSEQUENCES: with lambda = 1 ids and distances are bit for bit hnsw_rerank_batch's; a query's row depends on its own
+ *    candidates only, not on the batch; NaN in data or query: no promise.
+ *    REFUSED (HNSW_ERR_BAD_ARG unless named; outputs untouched; nq == 0 is a no-op): a null handle or array (out_div may be null),
+ *    nq < 0, q_stride < d, cand_stride < 1 (> 1024: HNSW_ERR_UNSUPPORTED), k outside 1..cand_stride, an unknown fill, lambda NaN
+ *    or outside [0, 1].
+ * 4. THE SEARCHES.  hnsw_search_batch_diverse is, bit for bit, hnsw_search_batch with k := pool (hnsw_search_batch_filtered when a
+ *    filter is given) followed by hnsw_diversify_batch over its id rows with k = params->k, lambda, and params->fill: the inner
+ *    call's rows of -1 are the padding; out_nd, out_nh and out_status are the inner call's counters unchanged (out_status: what the
+ *    filtered call writes as out_stage; zero from the plain call); params->k <= pool <= params->ef, else HNSW_ERR_BAD_ARG (pool
+ *    > 1024: HNSW_ERR_UNSUPPORTED).  Everything the inner call does is inherited, not restated: row formats and option refine,
+ *    COSINE, marks (a marked index takes the filtered path, so no marked node is a candidate), the ordering pre-pass, the
+ *    tie-overflow repair, option filter_collect, every refusal.  The selection launch follows the search on the handle's stream and
+ *    reads the ids where the search left them.
+ *    hnsw_brute_force_batch_diverse is the same composition over hnsw_brute_force_batch with k <= pool <= 1024.  It takes no
+ *    filter: a filtered exact top-k under (key, id) does not exist as a call.
+ * 5. Scratch -- the pool's rows, the selection's rows before their download -- is the handle's, sized on demand, not counted in
+ *    device_bytes: one such call in flight per handle.
+ * 6. NOT BUILT: per-query filters; keyed output (hnsw_index_keys_of translates the ids); device-pointer forms of the two searches
+ *    (a device-resident caller composes hnsw_search_batch_device and hnsw_diversify_batch_device on one stream); the hnsw_sharded
+ *    and hnsw_multi forms; a per-query lambda.
+ * 7. COST, plainly: a selection evaluates c + (k - 1) * (at most c - 1) rows per query, each round re-reading the pool's rows:
+ *    at pool 128, k 10 the order of one walk at ef 128.  Rates: tools/diverse_rate.py, profiles/diverse.txt. */
+int32_t hnsw_diversify_batch(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const int32_t *cand,
+                             int32_t cand_stride, int32_t k, float lambda, int32_t fill, int32_t *out_ids, float *out_dist,
+                             float *out_div /* may be NULL */);
+int32_t hnsw_diversify_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride, const int32_t *d_cand,
+                                    int32_t cand_stride, int32_t k, float lambda, int32_t fill, int32_t *d_ids, float *d_dist,
+                                    float *d_div /* may be NULL */, void *stream);
+int32_t hnsw_search_batch_diverse(hnsw_index *idx, const hnsw_filter *filter /* may be NULL */, const float *queries, int64_t nq,
+                                  int64_t q_stride, const hnsw_search_params *params, int32_t pool, float lambda, int32_t *out_ids,
+                                  float *out_dist, float *out_div /* may be NULL */, uint32_t *out_nd, uint32_t *out_nh,
+                                  uint32_t *out_status /* each optional */);
+int32_t hnsw_brute_force_batch_diverse(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int32_t k, int32_t pool,
+                                       float lambda, int32_t fill, int32_t *out_ids, float *out_dist, float *out_div /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

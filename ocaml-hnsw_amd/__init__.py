@@ -169,6 +169,10 @@ _ABI = {
     "hnsw_index_update": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "hnsw_search_batch_after": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_brute_force_batch_after": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
+    "hnsw_diversify_batch": [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp],
+    "hnsw_diversify_batch_device": [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp],
+    "hnsw_search_batch_diverse": [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hnsw_brute_force_batch_diverse": [_vp, _vp, _i64, _i64, _i32, _i32, _f32, _i32, _vp, _vp, _vp],
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -1026,6 +1030,32 @@ def _search_after(hgraph, batch, after, ef, k, fill, counters=False, sem=0, flt=
     return (ids, dist, nxt, nd, nh, stage) if counters else (ids, dist, nxt)
 
 
+def _search_diverse(hgraph, batch, ef, k, pool, lam, fill, counters=False, sem=0, flt=None):
+    """hnsw_search_batch_diverse (ef None: hnsw_brute_force_batch_diverse); flt: None, a Filter, or what Hgraph.filter takes
+    -> (ids, dist, div), with counters (ids, dist, div, ndist, nhops, status)."""
+    own = None if flt is None or isinstance(flt, Filter) else Filter(hgraph, flt)
+    try:
+        Q, qs, nq = _batch(hgraph.d, batch)
+        ids, dist = _out_pair(nq, int(k), None)
+        div = _np.empty((nq, max(int(k), 0)), _np.float32)
+        if ef is None:
+            if counters or flt is not None:
+                raise InvalidArgument("the brute-force form has no counters and takes no filter")
+            _check(load().hnsw_brute_force_batch_diverse(hgraph.handle, _ptr(Q), nq, qs, int(k), int(pool), float(lam), fill, _ptr(ids), _ptr(dist),
+                                                         _ptr(div)))
+            return ids, dist, div
+        nd = _np.zeros(nq, _np.uint32) if counters else None
+        nh = _np.zeros(nq, _np.uint32) if counters else None
+        status = _np.zeros(nq, _np.uint32) if counters else None
+        p = _SearchParams(ef, k, fill, sem)
+        _check(load().hnsw_search_batch_diverse(hgraph.handle, None if flt is None else (own or flt).handle, _ptr(Q), nq, qs, _C.byref(p), int(pool),
+                                                float(lam), _ptr(ids), _ptr(dist), _ptr(div), _ptr(nd), _ptr(nh), _ptr(status)))
+    finally:
+        if own is not None:
+            own.release()
+    return (ids, dist, div, nd, nh, status) if counters else (ids, dist, div)
+
+
 def _search_keyed(hgraph, batch, ef, k, fill, counters=False, sem=0, flt=None, missing=MISSING_KEY):
     """hnsw_search_batch_keyed; flt: None, a Filter, or what Hgraph.filter takes
     -> (keys, dist), with counters (keys, dist, ndist, nhops, stage)."""
@@ -1241,6 +1271,13 @@ def rerank_device(hgraph, d_queries, nq, q_stride, d_cand, cand_stride, k, d_ids
                                            stream or None))
 
 
+def diversify_device(hgraph, d_queries, nq, q_stride, d_cand, cand_stride, k, lam, d_ids, d_dist, d_div=0, fill=FILL_OHNSW, stream=0):
+    """hnsw_diversify_batch_device: the greedy MMR selection among given candidates on device pointers (ints), asynchronous on HIP
+    stream `stream`; d_div optional."""
+    _check(load().hnsw_diversify_batch_device(hgraph.handle, d_queries, nq, q_stride, d_cand, cand_stride, k, float(lam), fill, d_ids, d_dist,
+                                              d_div or None, stream or None))
+
+
 def search_batch_h2d(hgraph, batch, ef, k, d_ids, d_dist, d_ndist=0, d_nhops=0, d_status=0, stream=0,
                      fill=FILL_OHNSW, sem=SEM_OHNSW):
     """hnsw_search_batch_h2d: queries from a HOST matrix (read by the device directly when it was registered with pin()),
@@ -1423,6 +1460,37 @@ class Ohnsw:
         ids, dist = _out_pair(nq, int(k), out)
         _check(load().hnsw_rerank_batch(hgraph.handle, _ptr(Q), nq, qs, _ptr(C), C.shape[1], int(k), fill, _ptr(ids), _ptr(dist)))
         return ids, dist
+
+    @staticmethod
+    def diversify(hgraph, k, batch, cand, lam=0.5, fill=FILL_OHNSW):
+        """hnsw_diversify_batch -> (ids, distances, div): greedy maximal marginal relevance among ITS candidates cand[q] (int32
+        [nq][cand_stride], entries below id_base are padding, as rerank's).  Pick 1 is the nearest candidate; every further pick
+        minimises lam * distance to the query - (1 - lam) * distance to the nearest node already picked, three float32 operations,
+        ties to the candidate rerank ranks first.  Rows are in SELECTION order: ids [nq][k] (-1 past the real candidates),
+        distances to the query (NaN there; FILL_BA: +inf) and div, the distance to the nearest earlier pick at the moment of
+        selection (+inf for pick 1).  lam = 1 is rerank.  Needs no graph; only [nq][k] comes back."""
+        Q, qs, nq = _batch(hgraph.d, batch)
+        C = _np.ascontiguousarray(cand, _np.int32)
+        if C.ndim != 2 or C.shape[0] != nq:
+            raise InvalidArgument("cand must be [nq][cand_stride]")
+        ids, dist = _out_pair(nq, int(k), None)
+        div = _np.empty((nq, max(int(k), 0)), _np.float32)
+        _check(load().hnsw_diversify_batch(hgraph.handle, _ptr(Q), nq, qs, _ptr(C), C.shape[1], int(k), float(lam), fill, _ptr(ids), _ptr(dist),
+                                           _ptr(div)))
+        return ids, dist, div
+
+    @staticmethod
+    def knn_batch_diverse(hgraph, k, batch, pool, lam=0.5, ef=None, filter=None, counters=False):
+        """k DIVERSE neighbours (hnsw_search_batch_diverse) -> (ids, distances, div), with counters (ids, distances, div, ndist, nhops,
+        status): knn_batch_bigarray at k := pool (knn_batch_filtered under `filter`: a Filter, or what Hgraph.filter takes), then
+        diversify over its rows -- the pool never leaves the device.  k <= pool <= ef (ef defaults to pool)."""
+        return _search_diverse(hgraph, batch, pool if ef is None else ef, k, pool, lam, FILL_OHNSW, counters, flt=filter)
+
+    @staticmethod
+    def brute_force_diverse(hgraph, k, batch, pool, lam=0.5, fill=FILL_OHNSW):
+        """The exact form of knn_batch_diverse (hnsw_brute_force_batch_diverse) -> (ids, distances, div): brute_force_knn at k := pool
+        (k <= pool <= 1024), then diversify over its rows.  Needs no graph."""
+        return _search_diverse(hgraph, batch, None, k, pool, lam, fill)
 
     @staticmethod
     def search_k(hgraph, layer, start_nodes, targets, k, ef=None, sem=SEM_OHNSW, counters=False):
@@ -1675,6 +1743,12 @@ class Ba:
         """knn_batch's results that come after a cursor (see Ohnsw.knn_batch_after; the functor accept rule, +inf where a row is
         exhausted) -> (ids, distances, next)."""
         return _search_after(hgraph, batch, after, num_neighbours_search, num_neighbours, FILL_BA, counters, sem=SEM_FUNCTOR, flt=filter)
+
+    @staticmethod
+    def knn_batch_diverse(hgraph, batch, num_neighbours_search, num_neighbours, pool, lam=0.5, filter=None, counters=False):
+        """knn_batch's results diversified (see Ohnsw.knn_batch_diverse; the functor accept rule, +inf where a row is short)
+        -> (ids, distances, div)"""
+        return _search_diverse(hgraph, batch, num_neighbours_search, num_neighbours, pool, lam, FILL_BA, counters, sem=SEM_FUNCTOR, flt=filter)
 
     @staticmethod
     def knn_batch_by_id(hgraph, ids, num_neighbours_search, num_neighbours, exclude_self=True, counters=False):

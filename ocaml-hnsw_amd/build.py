@@ -10,7 +10,7 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libhnsw_mi355x.so")
 SOURCES = ["hnsw_capi.hip", "hnsw_build.hip", "hnsw_layer_ops.hip", "hnsw_multi.hip", "hnsw_order.hip", "hnsw_rows8.hip",
            "hnsw_rows_split.hip", "hnsw_rows16.hip", "hnsw_rows_sq8.hip", "hnsw_rows_sq8_dim.hip", "hnsw_rows_bits.hip", "hnsw_locality.hip", "hnsw_scan.hip", "hnsw_rerank.hip", "hnsw_filter.hip",
-           "hnsw_range.hip", "hnsw_remove.hip", "hnsw_soft_delete.hip", "hnsw_sharded.hip", "hnsw_cosine.hip", "hnsw_group.hip", "hnsw_keys.hip", "hnsw_by_id.hip", "hnsw_upsert.hip", "hnsw_after.hip"]
+           "hnsw_range.hip", "hnsw_remove.hip", "hnsw_soft_delete.hip", "hnsw_sharded.hip", "hnsw_cosine.hip", "hnsw_group.hip", "hnsw_keys.hip", "hnsw_by_id.hip", "hnsw_upsert.hip", "hnsw_after.hip", "hnsw_diverse.hip"]
 # the knn kernel's variants: one object per (metric, accept rule, row shape), see hnsw_search_variants.hip
 VARIANT_SOURCE = "hnsw_search_variants.hip"
 VARIANTS = [(m, s, f) for m in (0, 1) for s in (0, 1) for f in (0, 1, 2, 3, 4)]   # f: rows ragged fp32 / full fp32 / bytes / split fp32 / half
@@ -26,7 +26,7 @@ BITS_WALKS = [0, 1]
 # the same rows against a 4-bit query (option "bit_query_bits"): one object per accept rule, see hnsw_bits_asym_walk.hip
 BITS_ASYM_WALK_SOURCE = "hnsw_bits_asym_walk.hip"
 BITS_ASYM_WALKS = [0, 1]
-DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, SQ8_DIM_WALK_SOURCE, BITS_WALK_SOURCE, BITS_ASYM_WALK_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_group_plan.h", "hnsw_bits_plan.h", "hnsw_keys_plan.h", "hnsw_by_id_plan.h", "hnsw_upsert_plan.h", "hnsw_after_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
+DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, SQ8_DIM_WALK_SOURCE, BITS_WALK_SOURCE, BITS_ASYM_WALK_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_group_plan.h", "hnsw_bits_plan.h", "hnsw_keys_plan.h", "hnsw_by_id_plan.h", "hnsw_upsert_plan.h", "hnsw_after_plan.h", "hnsw_diverse_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
         os.path.join(ROOT, "include", "hnsw_mi355x.h")]
 
 

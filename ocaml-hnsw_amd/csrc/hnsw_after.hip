@@ -349,7 +349,7 @@ int after_call(hnsw_index *idx, const hnsw_filter *f, const hnsw_cursor *after, 
     int rc;
     if ((rc = idx->after_scratch.lo.ensure((size_t)nq * 8)) || (rc = idx->filter_scratch.stage.ensure((size_t)nq * 4))) return rc;
     rc = ladder_host_call(idx, queries, nq, q_stride, k, out_ids, out_dist, out_ndist, out_nhops, params ? out_stage : nullptr, params != nullptr, nullptr,
-                          nullptr, nullptr, params ? "paged search" : "paged scan", [&](const KnnBatch &b, float *d_stage, hipStream_t st) -> int {
+                          nullptr, nullptr, nullptr, params ? "paged search" : "paged scan", [&](const KnnBatch &b, float *d_stage, hipStream_t st) -> int {
         if (hipMemcpyAsync(idx->after_scratch.lo.p, lo.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st) != hipSuccess)
             return fail(HNSW_ERR_HIP, "cursor upload failed");
         if (params) return after_search(idx, f, *params, b, d_stage, st);

@@ -758,6 +758,11 @@ int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q
         (rc = rows ? q.resolve_rows(idx, rows->ids, nq, idx->scratch.q) : q.resolve(queries, qbytes, idx->scratch.q)) ||
         (ko && (rc = idx->key_scratch.ensure(rbytes * 2))))
         return rc;
+    if (dv) {           // (the selection's rows, dv->k wide)
+        const size_t sbytes = (size_t)nq * dv->k * 4;
+        DiverseBufs &db = idx->diverse_scratch;
+        if ((rc = db.ids.ensure(sbytes)) || (rc = db.dist.ensure(sbytes)) || (dv->div && (rc = db.div.ensure(sbytes)))) return rc;
+    }
     int32_t *zi = (int32_t *)registered_device_address(out_ids, rbytes);
     float *zd = (float *)registered_device_address(out_dist, rbytes);
     uint32_t *znd = (uint32_t *)registered_device_address(out_nd, cbytes), *znh = (uint32_t *)registered_device_address(out_nh, cbytes);
@@ -775,7 +780,7 @@ int HostCall::begin(hnsw_index *idx, const float *queries, int64_t nq, int64_t q
         zi = nullptr; zd = nullptr;
     }
     if (!zi || !zd) zi = nullptr, zd = nullptr;
-    small = allow_small && !ko && q.from && !zi && !znd && !znh && qbytes <= SMALL_BLOCK && rbytes <= SMALL_BLOCK && cbytes <= SMALL_BLOCK;
+    small = allow_small && !ko && !dv && q.from && !zi && !znd && !znh && qbytes <= SMALL_BLOCK && rbytes <= SMALL_BLOCK && cbytes <= SMALL_BLOCK;
     if (small) {
         if (!idx->hSmall) {
             HIP_TRY(idx->hSmall.alloc(5 * SMALL_BLOCK, hipHostMallocMapped));
@@ -824,6 +829,14 @@ int HostCall::finish(hnsw_index *idx, const char *what, hipStream_t st) {
         if (!rk && dist && ed == hipSuccess) ed = hipMemcpyAsync(dist, drop_dist, rbytes, hipMemcpyDeviceToHost, st);
         if (!rk && ko && drop_keys == (int64_t *)idx->key_scratch.p && ed == hipSuccess)
             ed = hipMemcpyAsync(ko->keys, drop_keys, rbytes * 2, hipMemcpyDeviceToHost, st);
+    } else if (dv && ed == hipSuccess) {           // the selection over the rows where the inner call left them, then its rows' download
+        const DiverseBufs &db = idx->diverse_scratch;
+        const size_t sbytes = (size_t)b.nq * dv->k * 4;
+        rk = launch_diversify(idx, b.Q, b.nq, b.q_stride, b.ids, k, dv->k, dv->lambda, dv->fill, (int32_t *)db.ids.p, (float *)db.dist.p,
+                              dv->div ? (float *)db.div.p : nullptr, st);
+        if (!rk) ed = hipMemcpyAsync(dv->ids, db.ids.p, sbytes, hipMemcpyDeviceToHost, st);
+        if (!rk && ed == hipSuccess) ed = hipMemcpyAsync(dv->dist, db.dist.p, sbytes, hipMemcpyDeviceToHost, st);
+        if (!rk && dv->div && ed == hipSuccess) ed = hipMemcpyAsync(dv->div, db.div.p, sbytes, hipMemcpyDeviceToHost, st);
     } else if (ko && ed == hipSuccess) {           // the rows as keys: one launch over the ids where the search left them, then their download
         rk = keys_translate(idx, b.ids, b.nq * k, ko->missing, (int64_t *)idx->key_scratch.p, st);
         if (!rk) ed = hipMemcpyAsync(ko->keys, idx->key_scratch.p, (size_t)b.nq * k * 8, hipMemcpyDeviceToHost, st);
@@ -1383,12 +1396,13 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
 
 int hnsw_host::knn_host_call(hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
                              int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko,
-                             const RowsIn *rows) {
-    int rc = check_batch(idx, params, nq, q_stride, (rows ? rows->ids != nullptr : queries != nullptr) && (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist);
+                             const RowsIn *rows, const DiverseOut *dv) {
+    int rc = check_batch(idx, params, nq, q_stride, (rows ? rows->ids != nullptr : queries != nullptr) &&
+                                                        (dv ? dv->ids && dv->dist : (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist));
     if (rc) return rc;
     // nodes are marked deleted: the filtered search under the handle's live mask, ladder, exact stage and all
     if (idx->n_deleted > 0)
-        return filtered_host_call(idx, idx->live.get(), queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, out_stage, ko, rows);
+        return filtered_host_call(idx, idx->live.get(), queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops, out_stage, ko, rows, dv);
     if (nq == 0) return rc;
     if (out_stage) memset(out_stage, 0, (size_t)nq * 4);
     HIP_TRY(hipSetDevice(idx->device));
@@ -1398,6 +1412,7 @@ int hnsw_host::knn_host_call(hnsw_index *idx, const float *queries, int64_t nq, 
     HostCall c;
     c.ko = ko;
     c.rows = rows;
+    c.dv = dv;
     bool q_in_place = false;
     if ((rc = c.begin(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, true, &q_in_place))) return rc;
     hipStream_t st = idx->hs[0];

@@ -413,8 +413,8 @@ int filtered_search(hnsw_index *idx, const FilterSet &fs, const hnsw_search_para
 // per-query form): what they hold is still to be uploaded, from there and from fs.which, on the call's stream
 int filtered_call(hnsw_index *idx, const FilterSet &fs, const uint32_t *const *host_masks, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
                   int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko = nullptr,
-                  const RowsIn *rows = nullptr) {
-    return ladder_host_call(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, out_stage, true, ko, rows, nullptr,
+                  const RowsIn *rows = nullptr, const DiverseOut *dv = nullptr) {
+    return ladder_host_call(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, out_stage, true, ko, rows, dv, nullptr,
                             "filtered search", [&](const KnnBatch &b, float *d_stage, hipStream_t st) -> int {
         if (host_masks) {
             hipError_t e = hipMemcpyAsync(const_cast<uint32_t **>(fs.d_masks), host_masks, (size_t)fs.n * 8, hipMemcpyHostToDevice, st);
@@ -521,8 +521,9 @@ int32_t hnsw_search_batch_filtered(hnsw_index *idx, const hnsw_filter *f, const 
 
 int hnsw_host::filtered_host_call(hnsw_index *idx, const hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride,
                                   const hnsw_search_params *params, int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops,
-                                  uint32_t *out_stage, const KeysOut *ko, const RowsIn *rows) {
-    int rc = check_batch(idx, params, nq, q_stride, (rows ? rows->ids != nullptr : queries != nullptr) && (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist);
+                                  uint32_t *out_stage, const KeysOut *ko, const RowsIn *rows, const DiverseOut *dv) {
+    int rc = check_batch(idx, params, nq, q_stride, (rows ? rows->ids != nullptr : queries != nullptr) &&
+                                                        (dv ? dv->ids && dv->dist : (ko ? ko->keys != nullptr : out_ids != nullptr) && out_dist));
     if (rc) return rc;
     if (params->semantics == HNSW_SEM_FUNCTOR_NEAREST_K)
         return fail(HNSW_ERR_BAD_ARG, "the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no filtered meaning");
@@ -531,7 +532,7 @@ int hnsw_host::filtered_host_call(hnsw_index *idx, const hnsw_filter *f, const f
     HIP_TRY(hipSetDevice(idx->device));
     // the table of one filter: the mask's own address, on the device since the filter was made
     return filtered_call(idx, FilterSet{&f, 1, nullptr, f->table(), nullptr}, nullptr, queries, nq, q_stride, params, out_ids, out_dist, out_ndist, out_nhops,
-                         out_stage, ko, rows);
+                         out_stage, ko, rows, dv);
 }
 
 extern "C" {

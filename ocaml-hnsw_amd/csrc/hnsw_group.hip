@@ -444,7 +444,7 @@ int32_t hnsw_search_batch_grouped(hnsw_index *idx, const hnsw_labels *labels, co
     if (nq == 0) return HNSW_OK;
     HIP_TRY(hipSetDevice(idx->device));
     const HostColumn lab{out_labels, &idx->group_scratch.lab, (size_t)nq * params->k * 4, "labels"};
-    return ladder_host_call(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, out_stage, true, nullptr, nullptr, &lab,
+    return ladder_host_call(idx, queries, nq, q_stride, params->k, out_ids, out_dist, out_ndist, out_nhops, out_stage, true, nullptr, nullptr, nullptr, &lab,
                             "grouped search", [&](const KnnBatch &b, float *d_stage, hipStream_t st) -> int {
         return grouped_search(idx, labels, f, *params, b, d_stage, st);
     });
@@ -459,7 +459,7 @@ int32_t hnsw_brute_force_batch_grouped(hnsw_index *idx, const hnsw_labels *label
     HIP_TRY(hipSetDevice(idx->device));
     if ((rc = idx->group_scratch.lab.ensure((size_t)nq * k * 4))) return rc;
     const HostColumn lab{out_labels, &idx->group_scratch.lab, (size_t)nq * k * 4, "labels"};
-    return ladder_host_call(idx, queries, nq, q_stride, k, out_ids, out_dist, nullptr, nullptr, nullptr, false, nullptr, nullptr, &lab, "grouped scan",
+    return ladder_host_call(idx, queries, nq, q_stride, k, out_ids, out_dist, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, &lab, "grouped scan",
                             [&](const KnnBatch &b, float *, hipStream_t st) -> int {
         return group_exact(idx, labels, f, b.Q, nq, b.q_stride, k, fill, b.ids, b.dist, (int32_t *)idx->group_scratch.lab.p, st);
     });

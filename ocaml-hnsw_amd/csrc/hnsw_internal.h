@@ -410,6 +410,21 @@ struct RowsIn {
 struct ByIdBufs {
     DevBuf self, ids, dist;
 };
+// A host call that ends in the selection of hnsw_diverse.hip (hnsw_search_batch_diverse, hnsw_brute_force_batch_diverse): the inner
+// call runs as wide as the pool (the k handed to HostCall::begin) into the handle's scratch, never into the caller's arrays, and
+// HostCall::finish queues the selection kernel over those rows and downloads its [nq][k] rows into ids / dist / div (div optional)
+struct DiverseOut {
+    int32_t k;
+    float lambda;
+    int32_t fill;
+    int32_t *ids;
+    float *dist, *div;
+};
+// ... its scratch: the selection's [nq][k] rows before their download (div: also hnsw_diversify_batch's).  Not index tables: not
+// counted in device_bytes.
+struct DiverseBufs {
+    DevBuf ids, dist, div;
+};
 
 inline int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
@@ -605,6 +620,7 @@ struct hnsw_index {
     // Searches by stored item (hnsw_by_id.hip): scratch of the host calls whose queries are rows of the index, and option
     // "graph_chunk_rows": the nodes hnsw_knn_graph searches per inner call (>= 1)
     hnsw_host::ByIdBufs by_id_scratch;
+    hnsw_host::DiverseBufs diverse_scratch;                  // the diversified searches (hnsw_diverse.hip)
     int64_t graph_chunk_rows = hnsw_host::GRAPH_CHUNK_ROWS;
 };
 
@@ -866,6 +882,9 @@ int knn_repair(::hnsw_index *idx, const hnsw_search_params *p, const KnnBatch &b
 // (optional): nd_out[q] = (nd_in ? nd_in[q] : 0) + the number of candidates evaluated
 int launch_rerank(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, const int32_t *cand, int32_t cand_stride, int32_t k,
                   int32_t fill, int32_t *out_ids, float *out_dist, const uint32_t *nd_in, uint32_t *nd_out, hipStream_t st);
+// hnsw_diverse.hip: the selection kernel on `st` for device-resident arguments (hnsw_diversify_batch_device, unchecked; out_div optional)
+int launch_diversify(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, const int32_t *cand, int32_t cand_stride, int32_t k,
+                     float lambda, int32_t fill, int32_t *out_ids, float *out_dist, float *out_div, hipStream_t st);
 // hnsw_scan.hip: the exact scan of b's queries on `st` into b.ids / b.dist (hnsw_brute_force_batch_device, with its checks).  masks
 // (optional, a device table of masks of ceil(n / 32) device words each): only the rows whose bit is set are candidates, in the mask
 // of the query's tile -- masks[tile_filter[t]] for the t-th tile of scan_tile(NCH) queries (tile_filter: device, one entry per
@@ -1023,12 +1042,15 @@ int scatter_rows(const hnsw_dev::ScatterArgs &a, hipStream_t st, const char *wha
 // out_stage (optional): as the filtered call writes it while nodes are marked, zero otherwise
 // rows (optional; queries is then null and q_stride padded_stride(d)): the queries are rows of the index, gathered on the device
 // (RowsIn; hnsw_search_batch_by_id)
+// dv (optional; out_ids and out_dist are then null and params->k is the pool): the rows stay on the device and the selection's go to
+// dv's arrays (DiverseOut; hnsw_search_batch_diverse)
 int knn_host_call(::hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params, int32_t *out_ids,
-                  float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko, const RowsIn *rows = nullptr);
-// hnsw_filter.hip: hnsw_search_batch_filtered; ko: likewise
+                  float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko, const RowsIn *rows = nullptr,
+                  const DiverseOut *dv = nullptr);
+// hnsw_filter.hip: hnsw_search_batch_filtered; ko, dv: likewise
 int filtered_host_call(::hnsw_index *idx, const ::hnsw_filter *f, const float *queries, int64_t nq, int64_t q_stride, const hnsw_search_params *params,
                        int32_t *out_ids, float *out_dist, uint32_t *out_ndist, uint32_t *out_nhops, uint32_t *out_stage, const KeysOut *ko,
-                       const RowsIn *rows = nullptr);
+                       const RowsIn *rows = nullptr, const DiverseOut *dv = nullptr);
 // hnsw_capi.hip: the value that puts option `name` of hnsw_index_set_option back where it is now (HNSW_ERR_BAD_ARG: no such option)
 int get_option(const ::hnsw_index *idx, const char *name, int64_t *value);
 // hnsw_capi.hip: queues the copies of a batch's results into the host arrays that are not null
@@ -1080,6 +1102,9 @@ struct HostCall {
     // epilogue over it into drop_ids (or drop_keys) / drop_dist -- the caller's page-locked matrices in place, else the handle's
     // by_id_scratch / key_scratch, downloaded from there
     const RowsIn *rows = nullptr;
+    // a diverse call (set before begin, out_ids and out_dist then null, k the pool): finish runs the selection over the device-resident
+    // rows into the handle's diverse_scratch and downloads that into dv's arrays; such a call never takes the small block
+    const DiverseOut *dv = nullptr;
     int32_t *drop_ids = nullptr;
     int64_t *drop_keys = nullptr;
     float *drop_dist = nullptr;
@@ -1097,16 +1122,17 @@ struct HostColumn {
     size_t bytes;
     const char *noun;                               // in "<noun> download failed"
 };
-// The frame of the filtered, grouped and paged host calls, graph and brute-force forms: HostCall::begin (ko / rows: see HostCall),
+// The frame of the filtered, grouped and paged host calls, graph and brute-force forms: HostCall::begin (ko / rows / dv: see HostCall),
 // body(batch, d_stage, st) -- d_stage: see knn_search -- on the handle's stream, the downloads of `extra` (optional) and of
 // out_stage (optional; from filter_scratch.stage), then finish(what).  An error after begin waits for the stream before it returns.
 template <class Body>
 int ladder_host_call(::hnsw_index *idx, const float *queries, int64_t nq, int64_t q_stride, int k, int32_t *out_ids, float *out_dist,
                      uint32_t *out_nd, uint32_t *out_nh, uint32_t *out_stage, bool allow_small, const KeysOut *ko, const RowsIn *rows,
-                     const HostColumn *extra, const char *what, Body &&body) {
+                     const DiverseOut *dv, const HostColumn *extra, const char *what, Body &&body) {
     HostCall c;
     c.ko = ko;
     c.rows = rows;
+    c.dv = dv;
     bool q_in_place = false;
     int rc;
     if ((rc = c.begin(idx, queries, nq, q_stride, k, out_ids, out_dist, out_nd, out_nh, allow_small, &q_in_place))) return rc;

@@ -17,6 +17,8 @@
 //                                                                                           hnsw_brute_force_batch_by_id, hnsw_knn_graph,
 //                                                                                           hnsw_index_get_rows_device)
 //   Hnsw::Cursor, Hnsw::Ohnsw::knn_after / brute_force_after                               (hnsw_search_batch_after, hnsw_brute_force_batch_after)
+//   Hnsw::Ohnsw::diversify / knn_diverse / brute_force_diverse                             (hnsw_diversify_batch, hnsw_search_batch_diverse,
+//                                                                                           hnsw_brute_force_batch_diverse)
 //   Hnsw::Ohnsw::brute_force_knn                                                           benchmark/dataset.ml:15-30
 //   Hnsw::Ba::knn / knn_batch                                                    lib/hnsw.ml:763-777
 //   Hnsw::Ohnsw::search_k / search_one, Hnsw::Ba::search                         lib/ohnsw.ml:492-588, lib/hnsw_algo.ml:350-437
@@ -731,6 +733,42 @@ inline Paged brute_force_after(const Hgraph &g, int k, const Mat &batch, const s
               std::vector<Cursor>(nq, Cursor::start()), std::vector<uint32_t>(nq, Paged::exact_stage)};
     check(hnsw_brute_force_batch_after(g.handle(), f ? f->handle() : nullptr, after.empty() ? nullptr : after.data(), batch.data, batch.dim2,
                                        batch.dim1, k, fill, out.ids.data(), out.dist.data(), out.next.data()));
+    return out;
+}
+
+// ---- diversified search: greedy maximal marginal relevance over a pool (the definition: include/hnsw_mi355x.h, the last section) ----
+// Rows are in SELECTION order: ids (-1 past the real candidates), dist = the distance to the query, div = the distance to the nearest
+// earlier pick at the moment of selection (+inf for pick 1); status: the inner search's out_status (the graph form).
+struct Diverse {
+    std::vector<int32_t> ids; std::vector<float> dist, div; std::vector<uint32_t> status;
+};
+// diversify (hnsw_diversify_batch): k of ITS candidates cand[q][0 .. cand_stride) per query (entries below id_base are padding); pick 1
+// is the nearest, every further pick minimises lambda * distance - (1 - lambda) * distance to the nearest pick.  lambda = 1 is rerank.
+inline Diverse diversify(const Hgraph &g, int k, const Mat &batch, const int32_t *cand, int cand_stride, float lambda = 0.5f,
+                         int fill = HNSW_FILL_OHNSW) {
+    const size_t cells = (size_t)batch.dim2 * (size_t)(k > 0 ? k : 0);
+    Diverse out{std::vector<int32_t>(cells, -1), std::vector<float>(cells, 0.f), std::vector<float>(cells, 0.f), {}};
+    check(hnsw_diversify_batch(g.handle(), batch.data, batch.dim2, batch.dim1, cand, cand_stride, k, lambda, fill, out.ids.data(), out.dist.data(),
+                               out.div.data()));
+    return out;
+}
+// knn_diverse (hnsw_search_batch_diverse): the search at k := pool (under f: the filtered search), then diversify over its rows on the
+// device; k <= pool <= ef (ef 0: pool)
+inline Diverse knn_diverse(const Hgraph &g, int k, const Mat &batch, int pool, float lambda = 0.5f, int ef = 0, const Filter *f = nullptr,
+                           int sem = HNSW_SEM_OHNSW, int fill = HNSW_FILL_OHNSW) {
+    const size_t nq = (size_t)batch.dim2, cells = nq * (size_t)(k > 0 ? k : 0);
+    Diverse out{std::vector<int32_t>(cells, -1), std::vector<float>(cells, 0.f), std::vector<float>(cells, 0.f), std::vector<uint32_t>(nq, 0u)};
+    hnsw_search_params p{ef > 0 ? ef : pool, k, fill, sem};
+    check(hnsw_search_batch_diverse(g.handle(), f ? f->handle() : nullptr, batch.data, batch.dim2, batch.dim1, &p, pool, lambda, out.ids.data(),
+                                    out.dist.data(), out.div.data(), nullptr, nullptr, out.status.data()));
+    return out;
+}
+// ... the exact form (hnsw_brute_force_batch_diverse): the pool is the exact scan's first `pool` nodes; needs no graph
+inline Diverse brute_force_diverse(const Hgraph &g, int k, const Mat &batch, int pool, float lambda = 0.5f, int fill = HNSW_FILL_OHNSW) {
+    const size_t cells = (size_t)batch.dim2 * (size_t)(k > 0 ? k : 0);
+    Diverse out{std::vector<int32_t>(cells, -1), std::vector<float>(cells, 0.f), std::vector<float>(cells, 0.f), {}};
+    check(hnsw_brute_force_batch_diverse(g.handle(), batch.data, batch.dim2, batch.dim1, k, pool, lambda, fill, out.ids.data(), out.dist.data(),
+                                         out.div.data()));
     return out;
 }
 

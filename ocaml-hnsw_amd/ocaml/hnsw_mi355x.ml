@@ -330,6 +330,19 @@ let hnsw_brute_force_batch_after =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_brute_force_batch_after"
     (index @-> filter_handle @-> ptr cursor @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float
      @-> ptr cursor @-> returning int32_t)
+(* diversified search (see the C header, the last section): greedy maximal marginal relevance over a pool of candidates *)
+let hnsw_diversify_batch =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_diversify_batch"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> int32_t @-> int32_t @-> float @-> int32_t @-> ptr int32_t
+     @-> ptr float @-> ptr float @-> returning int32_t)
+let hnsw_search_batch_diverse =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_search_batch_diverse"
+    (index @-> filter_handle @-> ptr float @-> int64_t @-> int64_t @-> ptr search_params @-> int32_t @-> float @-> ptr int32_t
+     @-> ptr float @-> ptr float @-> ptr uint32_t @-> ptr uint32_t @-> ptr uint32_t @-> returning int32_t)
+let hnsw_brute_force_batch_diverse =
+  foreign ~from:lib ~release_runtime_lock:true "hnsw_brute_force_batch_diverse"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> int32_t @-> int32_t @-> float @-> int32_t @-> ptr int32_t @-> ptr float
+     @-> ptr float @-> returning int32_t)
 let hnsw_index_deleted_count = foreign ~from:lib "hnsw_index_deleted_count" (index @-> ptr int64_t @-> returning int32_t)
 let hnsw_index_deleted_bits = foreign ~from:lib "hnsw_index_deleted_bits" (index @-> ptr uint32_t @-> returning int32_t)
 let hnsw_index_compact =
@@ -425,6 +438,10 @@ let hnsw_rerank_batch_device =
   foreign ~from:lib "hnsw_rerank_batch_device"
     (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> int32_t @-> int32_t @-> int32_t @-> ptr int32_t @-> ptr float
      @-> ptr void @-> returning int32_t)
+let hnsw_diversify_batch_device =
+  foreign ~from:lib "hnsw_diversify_batch_device"
+    (index @-> ptr float @-> int64_t @-> int64_t @-> ptr int32_t @-> int32_t @-> int32_t @-> float @-> int32_t @-> ptr int32_t
+     @-> ptr float @-> ptr float @-> ptr void @-> returning int32_t)
 let hnsw_host_register = foreign ~from:lib "hnsw_host_register" (ptr void @-> int64_t @-> returning int32_t)
 let hnsw_host_unregister = foreign ~from:lib "hnsw_host_unregister" (ptr void @-> returning int32_t)
 let hnsw_host_alloc = foreign ~from:lib "hnsw_host_alloc" (ptr (ptr void) @-> int64_t @-> returning int32_t)
@@ -1427,6 +1444,51 @@ let brute_force_after ?(fill = 0) ?filter ?after (t : t) (batch : Lacaml.S.mat) 
   (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
    Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
    cursors_out next nq)
+
+(* Diversified search (hnsw_diversify_batch, hnsw_search_batch_diverse, hnsw_brute_force_batch_diverse): greedy maximal marginal
+   relevance.  [diversify t queries ~candidates ~k ~lambda]: k of ITS candidates per query ([rerank]'s lists); pick 1 is the nearest,
+   every further pick minimises lambda * distance - (1 - lambda) * distance to the nearest node already picked, ties to the
+   candidate [rerank] ranks first -> (ids, distances, diversities) in SELECTION order; past a query's candidates id -1, nan;
+   diversities.(q).(j) is the distance to the nearest earlier pick at the moment of selection (infinity for pick 1).  lambda = 1.
+   is [rerank].  [knn_batch_diverse t batch ~ef ~k ~pool ~lambda]: the search at k := pool (?filter: the filtered search), then
+   [diversify] over its rows without leaving the device; k <= pool <= ef.  [brute_force_diverse]: the same over the exact scan,
+   k <= pool <= 1024, no graph needed. *)
+let rows3 nq k ids dist div =
+  (Array.init nq (fun q -> Array.init k (fun j -> Int32.to_int (CArray.get ids (q * k + j)))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get dist (q * k + j))),
+   Array.init nq (fun q -> Array.init k (fun j -> CArray.get div (q * k + j))))
+let diversify ?(fill = 0) (t : t) (queries : Lacaml.S.mat) ~(candidates : int array array) ~k ~lambda :
+  int array array * float array array * float array array =
+  let nq = A2.dim2 queries in
+  if Array.length candidates <> nq then invalid_arg "diversify: one candidate list per query";
+  let stride = Array.fold_left (fun m row -> max m (Array.length row)) 1 candidates in
+  let cand = CArray.make int32_t ~initial:(Int32.of_int (t.k_base - 1)) (max 1 (nq * stride)) in
+  Array.iteri (fun q row -> Array.iteri (fun j v -> CArray.set cand (q * stride + j) (Int32.of_int v)) row) candidates;
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let div = CArray.make float (max 1 (nq * k)) in
+  check (hnsw_diversify_batch t.handle (bigarray_start array2 queries) (Int64.of_int nq) (Int64.of_int t.dim)
+           (CArray.start cand) (Int32.of_int stride) (Int32.of_int k) lambda (Int32.of_int fill) (CArray.start ids) (CArray.start dist)
+           (CArray.start div));
+  rows3 nq k ids dist div
+let knn_batch_diverse ?(semantics = 0) ?(fill = 0) ?filter (t : t) (batch : Lacaml.S.mat) ~ef ~k ~pool ~lambda :
+  int array array * float array array * float array array =
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let div = CArray.make float (max 1 (nq * k)) in
+  let p = by_id_params ~semantics ~fill ~ef ~k in
+  let fh = match filter with Some (f : filter) -> f.f_handle | None -> null in
+  check (hnsw_search_batch_diverse t.handle fh (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) (addr p)
+           (Int32.of_int pool) lambda (CArray.start ids) (CArray.start dist) (CArray.start div) (from_voidp uint32_t null)
+           (from_voidp uint32_t null) (from_voidp uint32_t null));
+  rows3 nq k ids dist div
+let brute_force_diverse ?(fill = 0) (t : t) (batch : Lacaml.S.mat) ~k ~pool ~lambda :
+  int array array * float array array * float array array =
+  let nq = A2.dim2 batch in
+  let ids = CArray.make int32_t (max 1 (nq * k)) and dist = CArray.make float (max 1 (nq * k)) in
+  let div = CArray.make float (max 1 (nq * k)) in
+  check (hnsw_brute_force_batch_diverse t.handle (bigarray_start array2 batch) (Int64.of_int nq) (Int64.of_int t.dim) (Int32.of_int k)
+           (Int32.of_int pool) lambda (Int32.of_int fill) (CArray.start ids) (CArray.start dist) (CArray.start div));
+  rows3 nq k ids dist div
 
 (* [insert_batch_keyed t batch keys]: [insert_batch] into an index that owns keys (hnsw_index_insert_keyed), keys.(i) naming
    column i of [batch].  A stored or repeated key refuses the call before anything is built; an empty index without keys starts
