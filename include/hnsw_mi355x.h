@@ -600,6 +600,10 @@ int32_t hnsw_search_batch(hnsw_index *idx, const float *queries, int64_t nq, int
  *                                           back.  Registering an array twice is not an error; an array of which only a
  *                                           part is registered already is refused (HNSW_ERR_BAD_ARG); an array somebody else
  *                                           has page-locked is accepted, left to its owner and never accessed in place.
+ *                                           Where the runtime cannot page-lock existing memory at all (hipHostRegister
+ *                                           refuses every array: some virtual machines), the call still succeeds and the
+ *                                           rules above hold, but the array stays pageable and is staged through copies:
+ *                                           there only hnsw_host_alloc gives memory that the device accesses in place.
  * Only ranges obtained through these four calls are accessed directly; any other pointer is staged through copies.
  * LIFETIME.  A range may be unregistered / freed at any time after the call that used it has RETURNED: hnsw_host_unregister and
  * hnsw_host_free wait for the asynchronous work that still reads it (hnsw_search_batch_h2d's kernels read a registered query

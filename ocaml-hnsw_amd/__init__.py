@@ -815,7 +815,8 @@ def host_empty(shape, dtype=_np.float32):
 def pin(array):
     """hnsw_host_register: page-lock a host array the caller keeps alive (its query or result matrix of a benchmark
     loop): the host-buffer entry points then access it directly from the device.  Undo with unpin() BEFORE the array is
-    freed (host_empty() gives memory the library owns instead)."""
+    freed (host_empty() gives memory the library owns instead).  Where the runtime cannot page-lock existing memory at all
+    (some virtual machines) the call succeeds all the same and the array is staged through copies: use host_empty() there."""
     a = _np.asarray(array)
     if not a.flags["C_CONTIGUOUS"]:
         raise InvalidArgument("pin: array must be C-contiguous")

@@ -7,6 +7,7 @@
 #include "hnsw_internal.h"
 
 #include <mutex>
+#include <sys/mman.h>
 
 using hnsw_dev::IndexView;
 using hnsw_dev::SearchArgs;
@@ -52,7 +53,8 @@ thread_local std::string g_last_error;
 // for those events before the pages are unpinned or freed: unregistering early is slow, never a GPU page fault (round 4's
 // second suite abort was exactly that: DESIGN.md section 7).
 struct InFlight { hipStream_t st; hipEvent_t ev; };
-enum { RANGE_ALLOCATED = 0, RANGE_REGISTERED = 1, RANGE_FOREIGN = 2 };   // hipHostMalloc / hipHostRegister by this library / pinned by somebody else
+// hipHostMalloc / hipHostRegister by this library / pinned by somebody else / left pageable: this machine's runtime registers nothing
+enum { RANGE_ALLOCATED = 0, RANGE_REGISTERED = 1, RANGE_FOREIGN = 2, RANGE_PAGEABLE = 3 };
 struct HostRange { const char *p; size_t bytes; char *dev; int kind; std::vector<InFlight> readers; };
 std::mutex g_ranges_mu;
 std::vector<HostRange> g_ranges;
@@ -108,6 +110,21 @@ bool retire_range(const void *p, int *kind) {
         (void)hipEventDestroy(f.ev);
     }
     return true;
+}
+
+// Whether hipHostRegister works on this machine at all, asked once with a fresh page that nobody else can have page-locked:
+// where even that is refused, a refusal says nothing about the caller's array.  (A page that cannot be had counts as "it does".)
+bool runtime_registers_host_memory() {
+    static const bool works = [] {
+        void *page = mmap(nullptr, 4096, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (page == MAP_FAILED) return true;
+        *(volatile char *)page = 0;
+        const bool ok = hipHostRegister(page, 4096, hipHostRegisterPortable) == hipSuccess;
+        if (!ok || hipHostUnregister(page) != hipSuccess) (void)hipGetLastError();
+        munmap(page, 4096);
+        return ok;
+    }();
+    return works;
 }
 
 int fail(int code, const char *fmt, ...) {
@@ -1573,6 +1590,13 @@ int32_t hnsw_host_register(void *p, int64_t bytes) {
             remember_range(p, (size_t)bytes, nullptr, RANGE_FOREIGN);
             return HNSW_OK;
         }
+        // A runtime that cannot page-lock existing memory at all (a virtual machine without that facility refuses a fresh page of
+        // this library's own in the same way): the range is kept on the list, so that registering twice, overlaps and
+        // hnsw_host_unregister behave as everywhere, but stays pageable and is staged through copies like any other pointer.
+        if (!runtime_registers_host_memory()) {
+            remember_range(p, (size_t)bytes, nullptr, RANGE_PAGEABLE);
+            return HNSW_OK;
+        }
         return fail(HNSW_ERR_HIP, "hipHostRegister(%lld bytes) failed: %s", (long long)bytes, hipGetErrorString(e));
     }
     // "success" is believed only if every page answers as page-locked host memory (at most 4096 probes: the step grows with
@@ -1602,7 +1626,7 @@ int32_t hnsw_host_unregister(void *p) {
     }
     if (!retire_range(p, &kind))       // (waits for the asynchronous calls that still read the range)
         return fail(HNSW_ERR_BAD_ARG, "hnsw_host_unregister: no range registered through hnsw_host_register starts at %p", p);
-    if (kind == RANGE_FOREIGN) return HNSW_OK;                 // not this library's registration to undo
+    if (kind == RANGE_FOREIGN || kind == RANGE_PAGEABLE) return HNSW_OK;   // not this library's registration to undo / none to undo
     hipError_t e = hipHostUnregister(p);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(HNSW_ERR_HIP, "hipHostUnregister failed: %s", hipGetErrorString(e)); }
     return HNSW_OK;
