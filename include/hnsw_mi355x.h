@@ -273,6 +273,18 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *   "lds_pad"       LDS bytes a search workgroup asks for beyond its own (how many queries a CU holds
  *                   at once in a batch larger than the device holds): -1 = automatic (default);
  *   "scan_slabs"    into how many row slabs hnsw_brute_force_batch cuts the table (1..1024; 0 = automatic, the default);
+ *   "scan_bytes"    0 (default) = the exact scans are exactly what they are without the option.  1 = where the index holds
+ *                   byte rows (see "byte_rows"; the copy is used whatever that option says), d <= 256 and the call names no
+ *                   per-query filters, hnsw_brute_force_batch / _device -- and every call that ends in them: by id,
+ *                   hnsw_knn_graph with exact, the diverse brute force, the exact stage of hnsw_search_batch_filtered, the
+ *                   scans under marks, the shards' scans -- compute the integer sums with 8-bit matrix instructions over the
+ *                   byte rows, a quarter of the bytes.  Same ids, same distance bits: every sum is an integer below 2^24,
+ *                   which the float arithmetic holds exactly.  A launch any of whose query values is not an integer in
+ *                   0..255 runs the float kernels instead; that is decided on the device, so the device-pointer form still
+ *                   never waits for the host.  hnsw_index_scan_path tells which ran.  Any other value is refused.  Not
+ *                   saved.  Not built: the range, grouped and paged scans, per-query filters
+ *                   (hnsw_search_batch_filtered_each), sq8 codes as scan rows, d > 256, a float matrix path.
+ *                   Measured: profiles/scan_bytes.txt;
  *   "byte_rows"     when every value of the vectors is an integer in 0..255 (SIFT descriptors stored as
  *                   float32) the index keeps a second, lossless copy of the rows as bytes and the knn
  *                   searches read that one: each byte is converted back to the float it came from and
@@ -693,6 +705,9 @@ int32_t hnsw_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq
                                int32_t k, int32_t fill, int32_t *out_ids, float *out_dist);
 int32_t hnsw_brute_force_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
                                       int32_t k, int32_t fill, int32_t *d_ids, float *d_dist, void *stream);
+/* What the handle's last exact-scan launch ran (option "scan_bytes"): *out = 0 none yet, 1 the float scan, 2 the matrix scan over
+ * the byte rows.  Where the queries decided it on the device, the call waits for the device and reads the word. */
+int32_t hnsw_index_scan_path(hnsw_index *idx, int32_t *out);
 
 /* Exact re-ranking of caller-given candidates (the refine step of option "refine" as an operator of its own): for query q the
  * candidates cand[q][0 .. cand_stride) (id_base-based) are evaluated against the FLOAT32 vectors -- whatever

@@ -173,6 +173,7 @@ _ABI = {
     "hnsw_diversify_batch_device": [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp],
     "hnsw_search_batch_diverse": [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
     "hnsw_brute_force_batch_diverse": [_vp, _vp, _i64, _i64, _i32, _i32, _f32, _i32, _vp, _vp, _vp],
+    "hnsw_index_scan_path": [_vp, _vp],
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -551,8 +552,17 @@ class Hgraph:
     def set_option(self, name, value):
         """hnsw_index_set_option: every option of the C header by its name ("byte_rows", "half_rows", "sq8_rows", "sq8_dim_rows", "bit_rows", "bit_query_bits", "refine", ...).
         "filter_collect" 1 makes the filtered searches (knn_batch_filtered, knn_batch_filtered_each, the plain searches under
-        marks) answer from every node the layer-0 walk evaluates, not from the final W only (k <= 128, exact rows; default 0)"""
+        marks) answer from every node the layer-0 walk evaluates, not from the final W only (k <= 128, exact rows; default 0).
+        "scan_bytes" 1 sends the exact scans of byte-valued data (byte rows, d <= 256) through the 8-bit matrix kernels: same ids,
+        same distance bits; scan_path() tells which kernel ran (default 0)"""
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
+
+    def scan_path(self):
+        """hnsw_index_scan_path: what the handle's last exact-scan launch ran: 0 none yet, 1 the float scan, 2 the matrix scan over
+        the byte rows (set_option("scan_bytes", 1), byte-valued data and queries, d <= 256)"""
+        v = _C.c_int32(0)
+        _check(load().hnsw_index_scan_path(self.handle, _C.byref(v)))
+        return v.value
 
     def row_bytes(self):
         """Bytes of one vector as the knn searches read it (d: byte and sq8 rows of either kind, 2 d: half rows, 4 d: float32 rows)."""

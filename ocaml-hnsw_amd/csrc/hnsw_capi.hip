@@ -1323,6 +1323,11 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     if (!strcmp(name, "order_queries")) { idx->order_mode = value < 0 ? -1 : (value ? 1 : 0); return HNSW_OK; }
     if (!strcmp(name, "head_queries")) { idx->head_queries = std::max<int64_t>(-1, std::min<int64_t>(value, 0x7FFFFFFF)); return HNSW_OK; }
     if (!strcmp(name, "scan_slabs")) { idx->scan_slabs = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1024)); return HNSW_OK; }
+    if (!strcmp(name, "scan_bytes")) {       // 1: the exact scans take the matrix kernels over the byte rows where they may (hnsw_scan_bytes.hip)
+        if (value != 0 && value != 1) return fail(HNSW_ERR_BAD_ARG, "scan_bytes=%lld: 0 (off) or 1", (long long)value);
+        idx->scan_bytes = (int)value;
+        return HNSW_OK;
+    }
     if (!strcmp(name, "graph_chunk_rows")) {         // the nodes hnsw_knn_graph searches per inner call (hnsw_by_id.hip)
         if (value < 1) return fail(HNSW_ERR_BAD_ARG, "graph_chunk_rows=%lld: a chunk holds at least one node", (long long)value);
         idx->graph_chunk_rows = std::min<int64_t>(value, 0x7FFFFFFF);
@@ -1342,7 +1347,7 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
         {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
         {"sq8_rows", idx->sq8_on ? 1 : 0}, {"sq8_dim_rows", idx->sq8d_on ? 1 : 0}, {"bit_rows", idx->bit_mode}, {"bit_query_bits", idx->bit_query_bits}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
-        {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"graph_chunk_rows", idx->graph_chunk_rows}, {"filter_collect", idx->filter_collect ? 1 : 0}};
+        {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"scan_bytes", idx->scan_bytes}, {"graph_chunk_rows", idx->graph_chunk_rows}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }

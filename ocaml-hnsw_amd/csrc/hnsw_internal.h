@@ -3,6 +3,7 @@
 #include "../../include/hnsw_mi355x.h"
 #include "hnsw_device.hip.h"
 #include "hnsw_scan_plan.h"
+#include "hnsw_scan_bytes_plan.h"
 #include "hnsw_filter_plan.h"
 #include "hnsw_remove_plan.h"
 #include "hnsw_mark_plan.h"
@@ -250,6 +251,8 @@ inline size_t query_bytes(int64_t nq, int64_t q_stride, int d) { return ((size_t
 // by that call
 struct BatchBufs {
     DevBuf q, ids, dist, nd, nh, st, flag, scan;
+    // option "scan_bytes" (hnsw_scan_bytes.hip): one piece's query codes and terms; the path word and the prepass's counters (16 bytes)
+    DevBuf scan_codes, scan_state;
     // these buffers as a batch of nq queries whose results go to rows row0.. of ids / dist (a multi shard's slice of the table)
     KnnBatch batch(int64_t nq, int64_t q_stride, int k, int64_t row0 = 0) const {
         return {(const float *)q.p, nq, q_stride, (int32_t *)ids.p + row0 * k, (float *)dist.p + row0 * k,
@@ -262,7 +265,7 @@ struct BatchBufs {
             return rc;
         return HNSW_OK;
     }
-    void release() { for (DevBuf *b : {&q, &ids, &dist, &nd, &nh, &st, &flag, &scan}) b->release(); }
+    void release() { for (DevBuf *b : {&q, &ids, &dist, &nd, &nh, &st, &flag, &scan, &scan_codes, &scan_state}) b->release(); }
 };
 
 // an owned index handle: one under construction (destroyed unless released to the caller), or a member of a device group
@@ -561,6 +564,10 @@ struct hnsw_index {
     int vt_bits_override = 0;
     int lds_pad = -1;                    // option "lds_pad": extra LDS bytes per search wave (-1 = balanced_lds_pad's choice)
     int scan_slabs = 0;                  // option "scan_slabs": row slabs of the exact scans (0 = scan_slab_rows' choice)
+    // option "scan_bytes": 1 = scan_search takes the matrix kernels over the byte rows where it may (scan_bytes_eligible); 0 (default):
+    // never.  scan_path_known: what the last scan_search launched when the host knows it (SCAN_PATH_NONE / _FLOAT); -1: the
+    // prepass decided on the device, hnsw_index_scan_path reads scratch.scan_state's first word
+    int scan_bytes = 0, scan_path_known = 0;
     std::vector<std::pair<int, int>> prepared;   // (ef, accept rule) of every hnsw_index_prepare: what hnsw_index_save writes down
     // what the options "byte_rows" / "split_rows" asked for (bind_view leaves an unused copy out of the view), so that
     // hnsw_index_insert, which makes the row copies again, keeps their effect: byte_rows 0, split_rows 0 (off), split_rows -1
@@ -892,6 +899,10 @@ int launch_diversify(::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_st
 // padding of the caller's layout; their rows of b.ids / b.dist are left unwritten.
 int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hipStream_t st, const uint32_t *const *masks = nullptr,
                 const int32_t *tile_filter = nullptr, const int32_t *row_query = nullptr);
+// hnsw_scan_bytes.hip: the prepass and the matrix scan of nq queries (one piece of scan_search, its cut and its lists) on `st`;
+// *path = the device word the float kernels behind them compare with SCAN_PATH_FLOAT.  masks: null, or the table whose first mask applies.
+int scan_bytes_launch(::hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
+                      uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path);
 // hnsw_scan.hip: what the exact scans check of a call, as check_batch does for the knn searches (k in 1..1024, the fill, nq, then -- unless
 // nq is 0 -- the buffers and q_stride)
 int check_scan(const ::hnsw_index *idx, int64_t nq, int64_t q_stride, int32_t k, int32_t fill, bool buffers);

@@ -557,6 +557,14 @@ inline Grouped brute_force_grouped(const Hgraph &g, const Labels &l, int k, cons
     return out;
 }
 
+// what the handle's last exact-scan launch ran (hnsw_index_scan_path): 0 none yet, 1 the float scan, 2 the matrix scan over the byte
+// rows (option "scan_bytes")
+inline int32_t scan_path(Hgraph &g) {
+    int32_t path = 0;
+    check(hnsw_index_scan_path(g.handle(), &path));
+    return path;
+}
+
 // ---- keys the index owns: one caller-chosen int64 per stored node, pairwise distinct, kept on the device in row order and moved with
 // the nodes through insert_keyed, remove and compact (hnsw_index_set_keys ...; the definitions: include/hnsw_mi355x.h) ----
 inline void set_keys(Hgraph &g, const std::vector<int64_t> &keys) { check(hnsw_index_set_keys(g.handle(), keys.data(), (int64_t)keys.size())); }

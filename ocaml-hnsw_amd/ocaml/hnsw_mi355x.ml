@@ -261,6 +261,8 @@ let hnsw_index_mark_deleted =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_mark_deleted" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
 let hnsw_index_unmark_deleted =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_unmark_deleted" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
+(* what the handle's last exact-scan launch ran (option "scan_bytes"): 0 none yet, 1 the float scan, 2 the matrix scan *)
+let hnsw_index_scan_path = foreign ~from:lib "hnsw_index_scan_path" (index @-> ptr int32_t @-> returning int32_t)
 (* keys the index owns (see the C header): one caller-chosen int64 per stored node, moved with the nodes *)
 let hnsw_index_set_keys =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_set_keys" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
@@ -1303,6 +1305,10 @@ let c_keys (keys : int array) =
   let c = CArray.make int64_t (max 1 (Array.length keys)) in
   Array.iteri (fun i v -> CArray.set c i (Int64.of_int v)) keys;
   c
+let scan_path t : int =
+  let path = allocate int32_t 0l in
+  check (hnsw_index_scan_path t.handle path);
+  Int32.to_int !@path
 let set_keys t (keys : int array) = check (hnsw_index_set_keys t.handle (CArray.start (c_keys keys)) (Int64.of_int (Array.length keys)))
 let clear_keys t = check (hnsw_index_clear_keys t.handle)
 let keys_info t : bool * int =
