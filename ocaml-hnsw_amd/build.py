@@ -26,7 +26,7 @@ BITS_WALKS = [0, 1]
 # the same rows against a 4-bit query (option "bit_query_bits"): one object per accept rule, see hnsw_bits_asym_walk.hip
 BITS_ASYM_WALK_SOURCE = "hnsw_bits_asym_walk.hip"
 BITS_ASYM_WALKS = [0, 1]
-DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, SQ8_DIM_WALK_SOURCE, BITS_WALK_SOURCE, BITS_ASYM_WALK_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_scan_bytes_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_group_plan.h", "hnsw_bits_plan.h", "hnsw_keys_plan.h", "hnsw_by_id_plan.h", "hnsw_upsert_plan.h", "hnsw_after_plan.h", "hnsw_diverse_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
+DEPS = SOURCES + [VARIANT_SOURCE, COLLECT_SOURCE, SQ8_DIM_WALK_SOURCE, BITS_WALK_SOURCE, BITS_ASYM_WALK_SOURCE, "hnsw_device.hip.h", "hnsw_hop_asm.hip.h", "hnsw_hop_loop.inc", "hnsw_hop_slots.inc", "hnsw_hop_instances.inc", "hnsw_scan_device.hip.h", "hnsw_scan_plan.h", "hnsw_scan_bytes_plan.h", "hnsw_filter_plan.h", "hnsw_remove_plan.h", "hnsw_mark_plan.h", "hnsw_shard_plan.h", "hnsw_group_plan.h", "hnsw_bits_plan.h", "hnsw_rows_plan.h", "hnsw_keys_plan.h", "hnsw_by_id_plan.h", "hnsw_upsert_plan.h", "hnsw_after_plan.h", "hnsw_diverse_plan.h", "hnsw_build_device.hip.h", "hnsw_remove_device.hip.h", "hnsw_internal.h",
         os.path.join(ROOT, "include", "hnsw_mi355x.h")]
 
 

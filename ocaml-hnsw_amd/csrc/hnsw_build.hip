@@ -339,10 +339,8 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
                 const int64_t *append_keys) {
     int32_t rc = make_byte_rows(nx.get());
     if (!rc && !idx->split_rows_freed) rc = make_split_rows(nx.get());
-    if (!rc && idx->half_rows_on && nx->iv.n > 0) rc = make_half_rows(nx.get());
-    if (!rc && idx->sq8_on && nx->iv.n > 0) rc = make_sq8_rows(nx.get());
-    if (!rc && idx->sq8d_on && nx->iv.n > 0) rc = make_sq8_dim_rows(nx.get());
-    if (!rc && idx->bit_mode && nx->iv.n > 0) rc = make_bit_rows(nx.get(), idx->bit_mode);   // (option bit_rows: likewise; mode 1's means move)
+    // (the lossy copy that is on, over the whole new table: the range of the codes, mode 1's means of the bit rows move with it)
+    if (!rc && idx->lossy_on != LOSSY_NONE && nx->iv.n > 0) rc = make_lossy_rows(nx.get(), idx->lossy_on, idx->bit_mode);
     if (!rc && carry_codes) rc = extend_locality_codes(idx, nx.get());
     // soft deletion: the marks move with their nodes; the new live mask is complete before anything is swapped
     std::unique_ptr<hnsw_filter> live;
@@ -365,9 +363,7 @@ int adopt_graph(hnsw_index *idx, IndexPtr &nx, bool carry_codes, int32_t expecte
     std::swap(idx->tables, nx->tables);                    // (nx takes the old tables with it)
     idx->iv = nx->iv;
     idx->info = nx->info;
-    idx->sq8_lo = nx->sq8_lo; idx->sq8_scale = nx->sq8_scale;   // (of the swapped-in codes, if any)
-    idx->sq8d_lo = std::move(nx->sq8d_lo); idx->sq8d_scale = std::move(nx->sq8d_scale);
-    idx->bit_t = std::move(nx->bit_t);
+    static_cast<LossyParams &>(*idx) = std::move(static_cast<LossyParams &>(*nx));   // (of the swapped-in codes, if any)
     bind_view(idx);                                        // the options keep their effect
     idx->lcode_state = nx->lcode_state;                    // 1: carried over; 0: built on demand (also where the old graph could not)
     nx.reset();
@@ -530,11 +526,11 @@ int hnsw_host::check_insert(const hnsw_index *idx, int64_t n_old, int max_layer,
                     (long long)idx->dFbSlab.bytes, (long long)(n * 4));
     // option sq8_rows is on: the codes are made again over the grown table, which needs every value finite -- asked before the
     // graph is grown, not after
-    if (codes_on(idx))
+    if (k_lossy_rows[idx->lossy_on].codes)
         for (int64_t i = 0; i < m; ++i)
             for (int32_t j = 0; j < idx->iv.d; ++j)
                 if (!std::isfinite(vectors[i * row_stride + j]))
-                    return fail(HNSW_ERR_UNSUPPORTED, "%s: value %d of new vector %lld is NaN or infinite: nothing inserted", codes_option(idx), j, (long long)i);
+                    return fail(HNSW_ERR_UNSUPPORTED, "%s: value %d of new vector %lld is NaN or infinite: nothing inserted", k_lossy_rows[idx->lossy_on].option, j, (long long)i);
     return HNSW_OK;
 }
 

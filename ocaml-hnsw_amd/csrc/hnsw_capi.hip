@@ -220,13 +220,12 @@ const struct { int metric, semf, rows; collect_launch_fn launch; } k_collect_var
 // under L2 (hnsw_rows_sq8_dim.hip: a weighted distance; under the inner product they are byte rows to the kernel, 2).  6 = the
 // 1-bit codes (hnsw_rows_bits.hip), under every metric.
 inline int variant_full(const hnsw_index *idx) {
+    const LossyRowsDesc &lossy = k_lossy_rows[lossy_rows_of_format(idx->info.row_format)];
     switch (idx->info.row_format) {
-    case HNSW_ROWS_BYTES: case HNSW_ROWS_SQ8: return 2;
-    case HNSW_ROWS_SQ8_DIM: return idx->info.metric == HNSW_METRIC_L2 ? 5 : 2;
-    case HNSW_ROWS_BITS: return 6;
+    case HNSW_ROWS_BYTES: return 2;
     case HNSW_ROWS_SPLIT: return 3;
-    case HNSW_ROWS_HALF: return 4;
-    default: return idx->iv.nchunks == 16 * pick_nch(idx->iv.nchunks) ? 1 : 0;
+    case HNSW_ROWS_F32: return idx->iv.nchunks == 16 * pick_nch(idx->iv.nchunks) ? 1 : 0;
+    default: return idx->info.metric == HNSW_METRIC_L2 ? lossy.knn_rows_l2 : lossy.knn_rows;      // (a lossy copy: its table entry)
     }
 }
 
@@ -554,7 +553,7 @@ int check_params(const hnsw_index *idx, const hnsw_search_params *p) {
         return fail(HNSW_ERR_BAD_ARG, "bad semantics %d", p->semantics);
     if (p->semantics == HNSW_SEM_FUNCTOR_NEAREST_K && refine_count(idx, p) > 0)
         return fail(HNSW_ERR_BAD_ARG, "option %s is active: the k farthest of W (HNSW_SEM_FUNCTOR_NEAREST_K) have no refined meaning",
-                    walks_codes(idx) ? codes_option(idx) : "refine");
+                    walks_codes(idx) ? k_lossy_rows[idx->lossy_on].option : "refine");
     if (idx->iv.entry_point < 0) return fail(HNSW_ERR_EMPTY_INDEX, "knn: empty hgraph");
     return HNSW_OK;
 }
@@ -915,22 +914,29 @@ void bind_view(hnsw_index *idx) {
     // plain float32 rows
     // (the per-dimension codes, option sq8_dim_rows 1, and the 1-bit codes, option bit_rows 1 / 2, likewise; the four options
     // exclude each other)
-    const bool bytes = !idx->byte_rows_off && t.X8.p, sq8 = !bytes && idx->sq8_on && t.Xq.p, sq8d = !bytes && !sq8 && idx->sq8d_on && t.Xqd.p,
-               bits = !bytes && !sq8 && !sq8d && idx->bit_mode != 0 && t.Xb.p, half = !bytes && !sq8 && !sq8d && !bits && idx->half_rows_on && t.Xh.p;
+    const LossyRows on = idx->lossy_on;
+    const int format = bound_rows(idx->byte_rows_off, t.X8.p, on, on != LOSSY_NONE && lossy_table(t, on).p, idx->split_rows_off, t.Xm.p);
+    const bool lossy = lossy_rows_of_format(format) != LOSSY_NONE;       // (then `on` is that copy)
     iv.X = (const float *)t.X.p;
-    iv.X8 = bytes ? (const uint8_t *)t.X8.p : sq8 ? (const uint8_t *)t.Xq.p : sq8d ? (const uint8_t *)t.Xqd.p : bits ? (const uint8_t *)t.Xb.p : nullptr;
-    if (half) iv.Xh = (const uint2 *)t.Xh.p;
-    iv.stride8 = bits ? 64 * bit_words(iv.d) : (half ? 128 : 64) * pick_nch(iv.nchunks);
-    iv.Xm = idx->split_rows_off || half || sq8 || sq8d || bits ? nullptr : (const float *)t.Xm.p;
+    // the byte rows, or codes in their place for the same kernels
+    iv.X8 = format == HNSW_ROWS_BYTES ? (const uint8_t *)t.X8.p : k_lossy_rows[on].codes && lossy ? (const uint8_t *)lossy_table(t, on).p : nullptr;
+    iv.stride8 = 64 * pick_nch(iv.nchunks);
+    // (IndexView keeps Xh in X8's word and sq8s in tail0's: X8 and tail0 are written first, their other names by the switch)
     iv.tail0 = (const float *)t.tail0.p;
-    if (sq8d) iv.sq8s = (const float *)t.qd_s.p;              // (in tail0's place: no split rows are read while the codes are)
+    switch (format) {
+    case HNSW_ROWS_SQ8_DIM: iv.sq8s = (const float *)t.qd_s.p; break;      // (in tail0's place: no split rows are read while the codes are)
+    case HNSW_ROWS_BITS: iv.stride8 = 64 * bit_words(iv.d); break;
+    case HNSW_ROWS_HALF: iv.Xh = (const uint2 *)t.Xh.p; iv.stride8 = 128 * pick_nch(iv.nchunks); break;
+    default: break;
+    }
+    iv.Xm = idx->split_rows_off || lossy ? nullptr : (const float *)t.Xm.p;   // (a lossy copy takes the split rows' place too)
     iv.nbr0 = (const int32_t *)t.nbr0.p; iv.nbrU = (const int32_t *)t.nbrU.p;
     iv.upper_off = (const int32_t *)t.off.p; iv.upper_lvl = (const uint8_t *)t.lvl.p; iv.upper_ref = (const int2 *)t.ref.p;
     iv.lcode = (const int32_t *)t.lcode.p; iv.lcode0 = (const int32_t *)t.lcode0.p;
     hnsw_index_info &inf = idx->info;
     inf.n = iv.n; inf.max_degree0 = iv.S0; inf.max_layer = iv.max_layer; inf.entry_point = (int64_t)iv.entry_point + iv.id_base;
     inf.row_stride_bytes = iv.stride * 4;
-    inf.row_format = bytes ? HNSW_ROWS_BYTES : sq8 ? HNSW_ROWS_SQ8 : sq8d ? HNSW_ROWS_SQ8_DIM : bits ? HNSW_ROWS_BITS : half ? HNSW_ROWS_HALF : iv.Xm ? HNSW_ROWS_SPLIT : HNSW_ROWS_F32;
+    inf.row_format = format;
 }
 
 int finish_index(IndexPtr owned, int32_t expected_ef, int32_t expected_semantics, hnsw_index **out) {
@@ -1092,6 +1098,30 @@ int hnsw_host::create_index(const hnsw_index_desc *d, int32_t device, bool store
     return finish_index(std::move(idx), d->expected_ef, d->expected_semantics, out);
 }
 
+// hnsw_index_set_option for the option of one lossy copy: what plan_rows_option (hnsw_rows_plan.h) decided, carried out
+static int set_lossy_rows_option(hnsw_index *idx, LossyRows kind, int64_t value) {
+    IndexTables &t = idx->tables;
+    const RowsOptionPlan plan = plan_rows_option(kind, value, idx->info.row_format, idx->lossy_on, lossy_table(t, kind).p, idx->bit_mode, idx->filter_collect);
+    if (plan.code) return fail(plan.code, "%s", plan.message);
+    if (plan.release || (plan.make && k_lossy_rows[kind].value_is_mode)) {
+        HIP_TRY(hipSetDevice(idx->device));
+        HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy (a made one: a copy of the other mode)
+    }
+    // (a refusal to make it -- NaN, infinity, fp16 overflow, a range -- leaves the index as it was)
+    if (const int rc = plan.make ? make_lossy_rows(idx, kind, (int)value) : HNSW_OK) return rc;
+    if (plan.release)
+        switch (kind) {
+        case LOSSY_HALF: t.Xh.release(); break;
+        case LOSSY_SQ8: t.Xq.release(); break;
+        case LOSSY_SQ8_DIM: t.Xqd.release(); t.qd_lo.release(); t.qd_s.release(); idx->sq8d_lo.clear(); idx->sq8d_scale.clear(); break;
+        default: t.Xb.release(); t.bit_t.release(); idx->bit_t.clear(); break;
+        }
+    idx->lossy_on = plan.on; idx->bit_mode = plan.bit_mode;
+    bind_view(idx);
+    idx->forget_shapes();
+    return HNSW_OK;
+}
+
 extern "C" {
 
 int32_t hnsw_index_destroy(hnsw_index *idx) {
@@ -1145,8 +1175,8 @@ int32_t hnsw_index_prepare(hnsw_index *idx, const hnsw_search_params *params) {
 int32_t hnsw_index_row_bytes(const hnsw_index *idx, int64_t *row_bytes) {
     if (!idx || !row_bytes) return fail(HNSW_ERR_BAD_ARG, "null argument");
     const int f = idx->info.row_format;
-    if (f == HNSW_ROWS_BITS) { *row_bytes = ((int64_t)idx->iv.d + 7) / 8; return HNSW_OK; }   // (codes, but not a byte per dimension)
-    *row_bytes = (int64_t)idx->iv.d * (f == HNSW_ROWS_BYTES || walks_codes(idx) ? 1 : f == HNSW_ROWS_HALF ? 2 : 4);
+    const int value_bits = f == HNSW_ROWS_BYTES ? 8 : k_lossy_rows[lossy_rows_of_format(f)].value_bits;     // (the bit rows: codes, but not a byte per dimension)
+    *row_bytes = ((int64_t)idx->iv.d * value_bits + 7) / 8;
     return HNSW_OK;
 }
 
@@ -1174,111 +1204,11 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         idx->forget_shapes();
         return HNSW_OK;
     }
-    if (!strcmp(name, "half_rows")) {     // 1: search the fp16 copy (made now if missing); 0: the fp32 / split rows again, the copy kept; -1: ... and freed
-        if (value > 0) {
-            if (idx->info.row_format == HNSW_ROWS_BYTES)
-                return fail(HNSW_ERR_BAD_ARG, "half_rows: the index searches its byte rows, which are exact and half the size of half rows "
-                                              "(set byte_rows 0 first)");
-            if (codes_on(idx)) return fail(HNSW_ERR_BAD_ARG, "half_rows: option %s is on (set it 0 first)", codes_option(idx));
-            if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "half_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
-            if (!idx->tables.Xh.p) {
-                const int rc = make_half_rows(idx);     // (a refusal -- NaN, fp16 overflow -- leaves the index as it was)
-                if (rc) return rc;
-            }
-            idx->half_rows_on = true;
-        } else {
-            if (value < 0 && idx->tables.Xh.p) {
-                HIP_TRY(hipSetDevice(idx->device));
-                HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy
-                idx->tables.Xh.release();
-            }
-            idx->half_rows_on = false;
-        }
-        bind_view(idx);
-        idx->forget_shapes();
-        return HNSW_OK;
-    }
-    if (!strcmp(name, "sq8_rows")) {      // 1: walk the 8-bit codes (made now if missing), re-rank over the fp32 rows; 0: the previous rows again, the codes kept; -1: ... and freed
-        if (value > 0) {
-            if (idx->info.row_format == HNSW_ROWS_BYTES)
-                return fail(HNSW_ERR_BAD_ARG, "sq8_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)");
-            if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option half_rows is on (set half_rows 0 first)");
-            if (idx->sq8d_on) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option sq8_dim_rows is on (set sq8_dim_rows 0 first)");
-            if (idx->bit_mode) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option bit_rows is on (set bit_rows 0 first)");
-            if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "sq8_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
-            if (!idx->tables.Xq.p) {
-                const int rc = make_sq8_rows(idx);      // (a refusal -- NaN, infinity, range overflow -- leaves the index as it was)
-                if (rc) return rc;
-            }
-            idx->sq8_on = true;
-        } else {
-            if (value < 0 && idx->tables.Xq.p) {
-                HIP_TRY(hipSetDevice(idx->device));
-                HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy
-                idx->tables.Xq.release();
-            }
-            idx->sq8_on = false;
-        }
-        bind_view(idx);
-        idx->forget_shapes();
-        return HNSW_OK;
-    }
-    if (!strcmp(name, "sq8_dim_rows")) {  // as "sq8_rows", the codes under one affine map per dimension (hnsw_rows_sq8_dim.hip)
-        if (value < -1 || value > 1) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows=%lld: 1 (on), 0 (off) or -1 (off, the copy freed)", (long long)value);
-        if (value > 0) {
-            if (idx->info.row_format == HNSW_ROWS_BYTES)
-                return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)");
-            if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option half_rows is on (set half_rows 0 first)");
-            if (idx->sq8_on) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option sq8_rows is on (set sq8_rows 0 first)");
-            if (idx->bit_mode) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option bit_rows is on (set bit_rows 0 first)");
-            if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "sq8_dim_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
-            if (!idx->tables.Xqd.p) {
-                const int rc = make_sq8_dim_rows(idx);  // (a refusal -- NaN, infinity, a column's range -- leaves the index as it was)
-                if (rc) return rc;
-            }
-            idx->sq8d_on = true;
-        } else {
-            if (value < 0 && idx->tables.Xqd.p) {
-                HIP_TRY(hipSetDevice(idx->device));
-                HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy
-                idx->tables.Xqd.release(); idx->tables.qd_lo.release(); idx->tables.qd_s.release();
-                idx->sq8d_lo.clear(); idx->sq8d_scale.clear();
-            }
-            idx->sq8d_on = false;
-        }
-        bind_view(idx);
-        idx->forget_shapes();
-        return HNSW_OK;
-    }
-    if (!strcmp(name, "bit_rows")) {      // 1-bit codes walked under Hamming distance (hnsw_rows_bits.hip): 1 = thresholds at the column means, 2 = at zero
-        if (value < 0 || value > 2) return fail(HNSW_ERR_BAD_ARG, "bit_rows=%lld: 0 (off), 1 (thresholds at the column means) or 2 (at zero)", (long long)value);
-        if (value > 0) {
-            if (idx->info.row_format == HNSW_ROWS_BYTES)
-                return fail(HNSW_ERR_BAD_ARG, "bit_rows: the index searches its byte rows, which are exact (set byte_rows 0 first)");
-            if (idx->half_rows_on) return fail(HNSW_ERR_BAD_ARG, "bit_rows: option half_rows is on (set half_rows 0 first)");
-            if (idx->sq8_on) return fail(HNSW_ERR_BAD_ARG, "bit_rows: option sq8_rows is on (set sq8_rows 0 first)");
-            if (idx->sq8d_on) return fail(HNSW_ERR_BAD_ARG, "bit_rows: option sq8_dim_rows is on (set sq8_dim_rows 0 first)");
-            if (idx->filter_collect) return fail(HNSW_ERR_BAD_ARG, "bit_rows: option filter_collect is on, which needs exact rows (set filter_collect 0 first)");
-            if (!idx->tables.Xb.p || idx->bit_mode != (int)value) {
-                HIP_TRY(hipSetDevice(idx->device));
-                HIP_TRY(hipDeviceSynchronize());         // launches that still read a copy of the other mode
-                const int rc = make_bit_rows(idx, (int)value);   // (a refusal -- NaN, infinity -- leaves the index as it was)
-                if (rc) return rc;
-            }
-            idx->bit_mode = (int)value;
-        } else {
-            if (idx->tables.Xb.p) {
-                HIP_TRY(hipSetDevice(idx->device));
-                HIP_TRY(hipDeviceSynchronize());         // launches that still read the copy
-                idx->tables.Xb.release(); idx->tables.bit_t.release();
-                idx->bit_t.clear();
-            }
-            idx->bit_mode = 0;
-        }
-        bind_view(idx);
-        idx->forget_shapes();
-        return HNSW_OK;
-    }
+    // the lossy copies, each by its option: half_rows (1: search the fp16 copy, made now if missing; 0: the fp32 / split rows again, the
+    // copy kept; -1: ... and freed), sq8_rows (likewise: walk the 8-bit codes, re-rank over the fp32 rows), sq8_dim_rows (the codes
+    // under one affine map per dimension, hnsw_rows_sq8_dim.hip), bit_rows (1-bit codes walked under Hamming distance,
+    // hnsw_rows_bits.hip: 1 = thresholds at the column means, 2 = at zero)
+    if (const LossyRows kind = lossy_rows_by_option(name); kind != LOSSY_NONE) return set_lossy_rows_option(idx, kind, value);
     if (!strcmp(name, "bit_query_bits")) {   // 4: the walk over the bit rows keeps the query at 4 bits a dimension (hnsw_bits_asym_walk.hip); 0: at one
         if (value != 0 && value != 4) return fail(HNSW_ERR_BAD_ARG, "bit_query_bits=%lld: 0 (off) or 4", (long long)value);
         idx->bit_query_bits = (int)value;   // (takes effect while the searches walk the bit rows, as refine does for half rows; not saved)
@@ -1292,9 +1222,8 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     }
     if (!strcmp(name, "filter_collect")) {   // 1: the filtered searches answer from every node the walk evaluates (k <= 128, exact rows); 0: from the final W
         if (value != 0 && value != 1) return fail(HNSW_ERR_BAD_ARG, "filter_collect=%lld: 0 (off) or 1", (long long)value);
-        if (value == 1 && (idx->half_rows_on || codes_on(idx)))   // (on, even while byte rows stand in front of them: "byte_rows" 0 would bring them back)
-            return fail(HNSW_ERR_BAD_ARG, "filter_collect: option %s is on, and a walk over those rows has no exact distances (set it 0 first)",
-                        codes_on(idx) ? codes_option(idx) : "half_rows");
+        if (value == 1 && idx->lossy_on != LOSSY_NONE)   // (on, even while byte rows stand in front of them: "byte_rows" 0 would bring them back)
+            return fail(HNSW_ERR_BAD_ARG, "filter_collect: option %s is on, and a walk over those rows has no exact distances (set it 0 first)", k_lossy_rows[idx->lossy_on].option);
         idx->filter_collect = value == 1;
         return HNSW_OK;
     }
@@ -1344,11 +1273,13 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
     if (!idx || !name || !value) return fail(HNSW_ERR_BAD_ARG, "null argument");
     const struct { const char *name; int64_t value; } now[] = {
         {"vt_bits", idx->vt_bits_override}, {"lds_pad", idx->lds_pad}, {"byte_rows", idx->byte_rows_off ? 0 : 1},
-        {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1}, {"half_rows", idx->half_rows_on ? 1 : 0},
-        {"sq8_rows", idx->sq8_on ? 1 : 0}, {"sq8_dim_rows", idx->sq8d_on ? 1 : 0}, {"bit_rows", idx->bit_mode}, {"bit_query_bits", idx->bit_query_bits}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
+        {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1},
+        {"bit_query_bits", idx->bit_query_bits}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
         {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"scan_bytes", idx->scan_bytes}, {"graph_chunk_rows", idx->graph_chunk_rows}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }
+    // (a lossy copy's option: 1 while it is on, the bit rows: their mode)
+    if (const LossyRows k = lossy_rows_by_option(name)) { *value = idx->lossy_on != k ? 0 : k_lossy_rows[k].value_is_mode ? idx->bit_mode : 1; return HNSW_OK; }
     return fail(HNSW_ERR_BAD_ARG, "unknown option %s", name);
 }
 

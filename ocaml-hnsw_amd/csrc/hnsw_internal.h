@@ -10,6 +10,7 @@
 #include "hnsw_shard_plan.h"
 #include "hnsw_group_plan.h"
 #include "hnsw_bits_plan.h"
+#include "hnsw_rows_plan.h"
 #include "hnsw_keys_plan.h"
 #include "hnsw_by_id_plan.h"
 #include "hnsw_upsert_plan.h"
@@ -232,6 +233,17 @@ struct IndexTables {
     }
     void release() { each(*this, [](Table &t) { t.release(); }); }
     size_t bytes() const { size_t s = 0; each(*this, [&](const Table &t) { s += t.bytes; }); return s; }
+};
+// What the handle keeps on the host of its lossy copies' maps -- everything hnsw_index_insert and hnsw_index_remove hand over, in one
+// move, from the handle they built the new copy in (adopt_graph)
+struct LossyParams {
+    // sq8_lo / sq8_scale describe tables.Xq, the 8-bit codes of x ~ sq8_lo + sq8_scale * code, whenever it exists
+    float sq8_lo = 0.0f, sq8_scale = 1.0f;
+    // sq8d_lo / sq8d_scale ([d] each; on the device tables.qd_lo / qd_s in the lane grid) describe tables.Xqd, the 8-bit codes of
+    // x_i ~ lo_i + s_i * code under one affine map per dimension, whenever it exists
+    std::vector<float> sq8d_lo, sq8d_scale;
+    // bit_t ([d]; on the device tables.bit_t, [512 * NW] floats) describes tables.Xb, one bit per dimension (x_i > t_i), whenever it exists
+    std::vector<float> bit_t;
 };
 
 // where one knn launch reads its queries and writes its results (device addresses; nd / nh / st / any_flag may be null)
@@ -510,7 +522,7 @@ struct hnsw_range_result : hnsw_host::RangeRecord<int32_t> {};
 // ... and a sharded range call and hnsw_merge_segments: int64 global ids, on one device; it keeps no reference to the handle it came from
 struct hnsw_sharded_range_result : hnsw_host::RangeRecord<int64_t> {};
 
-struct hnsw_index {
+struct hnsw_index : hnsw_host::LossyParams {
     int device = -1;
     hnsw_dev::IndexView iv{};
     hnsw_index_info info{};
@@ -573,28 +585,22 @@ struct hnsw_index {
     // hnsw_index_insert, which makes the row copies again, keeps their effect: byte_rows 0, split_rows 0 (off), split_rows -1
     // (off and freed for good)
     bool byte_rows_off = false, split_rows_off = false, split_rows_freed = false;
+    // Which lossy copy of the rows its option turned on (half rows, sq8 codes, per-dimension sq8 codes, 1-bit codes), even while
+    // byte rows stand in front of it: one value, so at most one is on.  hnsw_index_insert, hnsw_index_remove and the upsert make
+    // that copy again over the changed table.
+    hnsw_host::LossyRows lossy_on = hnsw_host::LOSSY_NONE;
     // option "half_rows": the knn searches read tables.Xh (1), or it is off (0, -1).  Not a default: half rows change results.
-    // hnsw_index_insert makes the copy again while it is on.
-    bool half_rows_on = false;
+    // option "sq8_rows": the knn searches walk tables.Xq (1), or it is off (0, -1).  The WHOLE table is quantised again when it grows.
+    // option "sq8_dim_rows": the knn searches walk tables.Xqd (1), or it is off (0, -1); made again likewise.
+    // option "bit_rows": the knn searches walk tables.Xb under Hamming distance; 1: t = the column means, 2: t = 0; 0: off, and the
+    // copy is freed.  bit_mode: that parameter, 1 or 2 while the option is on and 0 otherwise; whether it is on is lossy_on's to say.
+    // (The maps of the three kinds of codes: LossyParams.)
+    int bit_mode = 0;
     // option "refine": 0 off; 1..1024 / -1: while the knn searches read the half rows, the head of W (max(k, refine) members, -1: all
     // ef) is re-ranked over the float32 rows (refine_count, hnsw_rerank.hip).  refine_scratch: the walk's results of the calls that
     // bring no scratch of their own (every entry point but submit / wait).
     int refine = 0;
     hnsw_host::RefineBufs refine_scratch;
-    // option "sq8_rows": the knn searches walk tables.Xq, the 8-bit codes of x ~ sq8_lo + sq8_scale * code (1), or it is off (0, -1).
-    // sq8_lo / sq8_scale describe tables.Xq whenever it exists.  hnsw_index_insert quantises the whole grown table again while it is on.
-    bool sq8_on = false;
-    float sq8_lo = 0.0f, sq8_scale = 1.0f;
-    // option "sq8_dim_rows": the knn searches walk tables.Xqd, the 8-bit codes of x_i ~ lo_i + s_i * code under one affine map per
-    // dimension (1), or it is off (0, -1).  sq8d_lo / sq8d_scale ([d] each; on the device tables.qd_lo / qd_s in the lane grid)
-    // describe tables.Xqd whenever it exists.  hnsw_index_insert and hnsw_index_remove quantise the whole table again while it is on.
-    bool sq8d_on = false;
-    std::vector<float> sq8d_lo, sq8d_scale;
-    // option "bit_rows": the knn searches walk tables.Xb, one bit per dimension (x_i > t_i) under Hamming distance; 1: t = the column
-    // means, 2: t = 0; 0: off, and the copy is freed.  bit_t ([d]; on the device tables.bit_t, [512 * NW] floats) describes tables.Xb
-    // whenever it exists.  hnsw_index_insert and hnsw_index_remove quantise the whole table again while it is on.
-    int bit_mode = 0;
-    std::vector<float> bit_t;
     // option "bit_query_bits": 4 = while the searches walk tables.Xb, the query keeps 4 bits a dimension (four bit planes of codes in
     // -7..7, bits_asym_transform_queries) and the walk's key is the inner product's (the knn kernel's ROWS 7, hnsw_bits_asym_walk.hip);
     // 0 = one bit, the Hamming walk.  The rows are the same copy either way.  Accepted, without effect, while other rows are walked.
@@ -801,6 +807,24 @@ int search_occupancy_sq8_dim_1(int nch, int nslot, size_t lds, int blk);
 // 2: zero), all or nothing: HNSW_ERR_UNSUPPORTED, naming the first such column, when a value is NaN or infinite (mode 1);
 // HNSW_ERR_OOM when there is no room.  Leaves the option's value and the view to the caller (bind_view).
 int make_bit_rows(::hnsw_index *idx, int mode);
+// The four of them by their LossyRows value (hnsw_rows_plan.h): the table whose presence says that the copy exists, and the call
+// that makes it (bit_mode: the bit rows' mode)
+inline const Table &lossy_table(const IndexTables &t, LossyRows kind) {
+    switch (kind) {
+    case LOSSY_HALF: return t.Xh;
+    case LOSSY_SQ8: return t.Xq;
+    case LOSSY_SQ8_DIM: return t.Xqd;
+    default: return t.Xb;
+    }
+}
+inline int make_lossy_rows(::hnsw_index *idx, LossyRows kind, int bit_mode) {
+    switch (kind) {
+    case LOSSY_HALF: return make_half_rows(idx);
+    case LOSSY_SQ8: return make_sq8_rows(idx);
+    case LOSSY_SQ8_DIM: return make_sq8_dim_rows(idx);
+    default: return make_bit_rows(idx, bit_mode);
+    }
+}
 // ... and nq queries as the walk over those codes reads them, on `st`: the first 16 * NW words of every Qt row ([nq][padded_stride(d)]
 // floats) are the query's bits q_i > t_i, zero beyond d.  Q and stage: as sq8_transform_queries; Q == Qt is NOT allowed.
 int bits_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st);
@@ -915,28 +939,23 @@ struct ScanCut : ScanPlan {
 ScanCut scan_cut(const ::hnsw_index *idx, int64_t m, int k, int64_t cell_bytes, int64_t cap);
 // the walk reads codes (sq8 rows, per-dimension sq8 rows, bit rows): its queries are moved to the codes' space first, its distances mean
 // nothing to a caller, and it always ends in the re-rank over the float32 rows
-inline bool walks_codes(const ::hnsw_index *idx) {
-    return idx->info.row_format == HNSW_ROWS_SQ8 || idx->info.row_format == HNSW_ROWS_SQ8_DIM || idx->info.row_format == HNSW_ROWS_BITS;
-}
-// ... and is either option on (even while byte rows stand in front of the codes)?  Its name, for messages
-inline bool codes_on(const ::hnsw_index *idx) { return idx->sq8_on || idx->sq8d_on || idx->bit_mode != 0; }
-inline const char *codes_option(const ::hnsw_index *idx) {
-    if (idx->bit_mode != 0 || idx->info.row_format == HNSW_ROWS_BITS) return "bit_rows";
-    return idx->sq8d_on || idx->info.row_format == HNSW_ROWS_SQ8_DIM ? "sq8_dim_rows" : "sq8_rows";
-}
+inline bool walks_codes(const ::hnsw_index *idx) { return k_lossy_rows[lossy_rows_of_format(idx->info.row_format)].codes; }
 // ... does it walk the bit rows against the 4-bit query's planes (option bit_query_bits 4; the kernel's ROWS 7)?
 inline bool walks_bit_planes(const ::hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_BITS && idx->bit_query_bits == 4; }
 // floats (words) per row of the matrix the walk over codes reads its queries from (RefineBufs::qt) -- what its allocation, the
 // transform and SearchArgs.q_stride share (walk_query_words, hnsw_bits_plan.h: the planes' rows have a stride of their own)
 inline int64_t walk_query_stride(const ::hnsw_index *idx) { return walk_query_words(idx->iv.d, walks_bit_planes(idx)); }
 inline int codes_transform_queries(const ::hnsw_index *idx, const float *Q, int64_t nq, int64_t q_stride, float *Qt, float *stage, hipStream_t st) {
-    if (walks_bit_planes(idx)) return bits_asym_transform_queries(idx, Q, nq, q_stride, Qt, stage, nullptr, st);
-    if (idx->info.row_format == HNSW_ROWS_BITS) return bits_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
-    return idx->info.row_format == HNSW_ROWS_SQ8_DIM ? sq8_dim_transform_queries(idx, Q, nq, q_stride, Qt, stage, st)
-                                                     : sq8_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
+    switch (idx->info.row_format) {
+    case HNSW_ROWS_BITS:
+        return walks_bit_planes(idx) ? bits_asym_transform_queries(idx, Q, nq, q_stride, Qt, stage, nullptr, st)
+                                     : bits_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
+    case HNSW_ROWS_SQ8_DIM: return sq8_dim_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
+    default: return sq8_transform_queries(idx, Q, nq, q_stride, Qt, stage, st);
+    }
 }
 // the walk's distances are not exact over X (half rows, codes): what is kept of W is re-ranked over the float32 rows
-inline bool walk_is_inexact(const ::hnsw_index *idx) { return idx->info.row_format == HNSW_ROWS_HALF || walks_codes(idx); }
+inline bool walk_is_inexact(const ::hnsw_index *idx) { return lossy_rows_of_format(idx->info.row_format) != LOSSY_NONE; }
 // the filter the unfiltered searches answer under: the live nodes while some are marked deleted, else none
 inline const ::hnsw_filter *live_filter(const ::hnsw_index *idx) { return idx->n_deleted > 0 ? idx->live.get() : nullptr; }
 // What every entry point checks of an object bound to a handle, its n and its graph epoch -- a filter, a labels object -- (null,

@@ -360,3 +360,62 @@ def test_recall_close_to_float32_rows(H, d, metric):
     assert r32 > 0.8, r32
     assert r16 >= r32 - 0.005, (r16, r32)
     hg.release()
+
+
+# What hnsw_index_set_option answers when one lossy copy is asked for while another is on, (held, requested) -> hnsw_last_error(),
+# and when one is asked for while the byte rows are read: every pair, the whole message
+_OTHER_COPY_ON = {
+    ("sq8_rows", "half_rows"): "half_rows: option sq8_rows is on (set it 0 first)",
+    ("sq8_dim_rows", "half_rows"): "half_rows: option sq8_dim_rows is on (set it 0 first)",
+    ("bit_rows", "half_rows"): "half_rows: option bit_rows is on (set it 0 first)",
+    ("half_rows", "sq8_rows"): "sq8_rows: option half_rows is on (set half_rows 0 first)",
+    ("sq8_dim_rows", "sq8_rows"): "sq8_rows: option sq8_dim_rows is on (set sq8_dim_rows 0 first)",
+    ("bit_rows", "sq8_rows"): "sq8_rows: option bit_rows is on (set bit_rows 0 first)",
+    ("half_rows", "sq8_dim_rows"): "sq8_dim_rows: option half_rows is on (set half_rows 0 first)",
+    ("sq8_rows", "sq8_dim_rows"): "sq8_dim_rows: option sq8_rows is on (set sq8_rows 0 first)",
+    ("bit_rows", "sq8_dim_rows"): "sq8_dim_rows: option bit_rows is on (set bit_rows 0 first)",
+    ("half_rows", "bit_rows"): "bit_rows: option half_rows is on (set half_rows 0 first)",
+    ("sq8_rows", "bit_rows"): "bit_rows: option sq8_rows is on (set sq8_rows 0 first)",
+    ("sq8_dim_rows", "bit_rows"): "bit_rows: option sq8_dim_rows is on (set sq8_dim_rows 0 first)",
+}
+_BYTE_ROWS_READ = {
+    "half_rows": "half_rows: the index searches its byte rows, which are exact and half the size of half rows (set byte_rows 0 first)",
+    "sq8_rows": "sq8_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)",
+    "sq8_dim_rows": "sq8_dim_rows: the index searches its byte rows, which are exact and the same size (set byte_rows 0 first)",
+    "bit_rows": "bit_rows: the index searches its byte rows, which are exact (set byte_rows 0 first)",
+}
+
+
+def test_one_lossy_copy_at_a_time_every_pair_and_its_message(H):
+    L = H.load()
+    n, d = 300, 24
+    X, Q = _floats(n, d, 91), _floats(16, d, 92)
+    hg = H.Ohnsw.build_batch_bigarray(X, 8, 40, seed=3)
+    Xb = np.random.default_rng(93).integers(0, 256, size=(n, d)).astype(np.float32)
+    hb = H.Ohnsw.build_batch_bigarray(Xb, 8, 40, seed=3)
+
+    def state(h, queries):
+        ids, dist = H.Ohnsw.knn_batch_bigarray(h, 5, queries, ef=32)
+        return h.info().row_format, h.info().device_bytes, ids.tobytes(), dist.tobytes()
+
+    def refused(h, queries, option, message):
+        before = state(h, queries)
+        for value in ((1, 2) if option == "bit_rows" else (1,)):
+            assert L.hnsw_index_set_option(h.handle, option.encode(), value) == H.ERR_BAD_ARG, (option, value)
+            assert L.hnsw_last_error().decode() == message
+            assert state(h, queries) == before, (option, value)
+
+    plain = state(hg, Q)
+    assert plain[0] == ROWS_F32
+    assert len(_OTHER_COPY_ON) == 12
+    for (held, asked), message in _OTHER_COPY_ON.items():
+        hg.set_option(held, 1)
+        assert hg.info().row_format not in (ROWS_F32, ROWS_BYTES, ROWS_SPLIT) and hg.info().device_bytes > plain[1], held
+        refused(hg, Q, asked, message)
+        hg.set_option(held, 0 if held == "bit_rows" else -1)
+        assert state(hg, Q) == plain, held
+    assert hb.info().row_format == ROWS_BYTES
+    for asked, message in _BYTE_ROWS_READ.items():
+        refused(hb, Xb[:16], asked, message)
+    hg.release()
+    hb.release()

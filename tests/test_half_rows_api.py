@@ -57,3 +57,17 @@ def test_set_option_errors_map_to_the_ocaml_exceptions(H):
     # what the option reports for data that does not fit fp16 (HNSW_ERR_UNSUPPORTED) is a Failure carrying its code
     with pytest.raises(H.Failure, match=r"^\[-7\]"):
         H._check(H.ERR_UNSUPPORTED)
+
+
+def test_rows_plan_is_the_option_code_it_replaced(tmp_path):
+    """hnsw_rows_plan.h (the table of the lossy row copies, which rows the searches read, what their four options do) against a
+    restatement of the code it replaced -- bind_view's chain, the four branches of hnsw_index_set_option with their messages,
+    variant_full, hnsw_index_row_bytes -- over every state: tests/cpp/test_rows_plan.cpp, a host program, under AddressSanitizer and
+    UndefinedBehaviorSanitizer"""
+    import subprocess
+    exe = str(tmp_path / "test_rows_plan")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_rows_plan.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    done = re.search(r"rows plan ok: (\d+) cases, 0 differ", out.stdout)
+    assert out.returncode == 0 and done and int(done.group(1)) > 30000, out.stdout + out.stderr
