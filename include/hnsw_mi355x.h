@@ -283,8 +283,20 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   0..255 runs the float kernels instead; that is decided on the device, so the device-pointer form still
  *                   never waits for the host.  hnsw_index_scan_path tells which ran.  Any other value is refused.  Not
  *                   saved.  Not built: the range, grouped and paged scans, per-query filters
- *                   (hnsw_search_batch_filtered_each), sq8 codes as scan rows, d > 256, a float matrix path.
+ *                   (hnsw_search_batch_filtered_each), sq8 codes as scan rows, d > 256.
  *                   Measured: profiles/scan_bytes.txt;
+ *   "scan_matrix"   0 (default) = the exact scans are exactly what they are without the option.  1 = where d <= 512, the call
+ *                   names no per-query filters and "scan_bytes" does not take the handle (the byte path has precedence and
+ *                   its float fallback stays the float kernels), the same calls as for "scan_bytes" -- COSINE indices
+ *                   included: inner product over the normalised rows -- screen the float32 rows with fp32 matrix instructions
+ *                   (v_mfma_f32_32x32x2_f32, tiles of 32 queries).  The matrix unit makes no key: it yields a proven bound per
+ *                   (row, query) pair, a pair is dropped only when that bound puts its exact key above the query's k-th so
+ *                   far, and every other pair is evaluated by the float scan's own arithmetic.  Same ids, same distance bits,
+ *                   by construction; only the speed depends on the data (norms far above the distances let most pairs
+ *                   through).  A launch any of whose query values is not finite runs the float kernels instead, decided on
+ *                   the device.  hnsw_index_scan_path tells which ran (3).  Any other value is refused.  Not saved.  Not
+ *                   built: the range, grouped and paged scans, per-query filters, d > 512, half, sq8 or bit rows as scan
+ *                   operands, a bf16 or split-precision screen.  Measured: profiles/scan_matrix.txt;
  *   "byte_rows"     when every value of the vectors is an integer in 0..255 (SIFT descriptors stored as
  *                   float32) the index keeps a second, lossless copy of the rows as bytes and the knn
  *                   searches read that one: each byte is converted back to the float it came from and
@@ -705,8 +717,9 @@ int32_t hnsw_brute_force_batch(hnsw_index *idx, const float *queries, int64_t nq
                                int32_t k, int32_t fill, int32_t *out_ids, float *out_dist);
 int32_t hnsw_brute_force_batch_device(hnsw_index *idx, const float *d_queries, int64_t nq, int64_t q_stride,
                                       int32_t k, int32_t fill, int32_t *d_ids, float *d_dist, void *stream);
-/* What the handle's last exact-scan launch ran (option "scan_bytes"): *out = 0 none yet, 1 the float scan, 2 the matrix scan over
- * the byte rows.  Where the queries decided it on the device, the call waits for the device and reads the word. */
+/* What the handle's last exact-scan launch ran (options "scan_bytes", "scan_matrix"): *out = 0 none yet, 1 the float scan, 2 the
+ * matrix scan over the byte rows, 3 the float matrix scan.  Where the queries decided it on the device, the call waits for the
+ * device and reads the word. */
 int32_t hnsw_index_scan_path(hnsw_index *idx, int32_t *out);
 
 /* Exact re-ranking of caller-given candidates (the refine step of option "refine" as an operator of its own): for query q the

@@ -28,6 +28,7 @@ METRIC_L2, METRIC_IP = 0, 1
 # Hgraph's host copy `vectors` stays the caller's matrix
 METRIC_COSINE = 2
 FILL_OHNSW, FILL_BA = 0, 1
+SCAN_PATH_NONE, SCAN_PATH_FLOAT, SCAN_PATH_BYTES, SCAN_PATH_MATRIX = 0, 1, 2, 3     # Hgraph.scan_path()
 SEM_OHNSW, SEM_FUNCTOR, SEM_FUNCTOR_NEAREST_K = 0, 1, 2
 # IndexInfo.row_format: what the knn searches read (HNSW_ROWS_*); ROWS_HALF only after set_option("half_rows", 1), ROWS_SQ8 only
 # after set_option("sq8_rows", 1), ROWS_SQ8_DIM only after set_option("sq8_dim_rows", 1)
@@ -554,12 +555,15 @@ class Hgraph:
         "filter_collect" 1 makes the filtered searches (knn_batch_filtered, knn_batch_filtered_each, the plain searches under
         marks) answer from every node the layer-0 walk evaluates, not from the final W only (k <= 128, exact rows; default 0).
         "scan_bytes" 1 sends the exact scans of byte-valued data (byte rows, d <= 256) through the 8-bit matrix kernels: same ids,
-        same distance bits; scan_path() tells which kernel ran (default 0)"""
+        same distance bits; scan_path() tells which kernel ran (default 0).
+        "scan_matrix" 1 screens the exact scans of float rows (d <= 512) with fp32 matrix instructions and evaluates what the
+        screen cannot drop with the float scan's own arithmetic: same ids, same distance bits (default 0)"""
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
 
     def scan_path(self):
         """hnsw_index_scan_path: what the handle's last exact-scan launch ran: 0 none yet, 1 the float scan, 2 the matrix scan over
-        the byte rows (set_option("scan_bytes", 1), byte-valued data and queries, d <= 256)"""
+        the byte rows (set_option("scan_bytes", 1), byte-valued data and queries, d <= 256), 3 the float matrix scan
+        (SCAN_PATH_MATRIX: set_option("scan_matrix", 1), finite queries, d <= 512)"""
         v = _C.c_int32(0)
         _check(load().hnsw_index_scan_path(self.handle, _C.byref(v)))
         return v.value

@@ -1257,6 +1257,11 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
         idx->scan_bytes = (int)value;
         return HNSW_OK;
     }
+    if (!strcmp(name, "scan_matrix")) {      // 1: the exact scans screen float rows with the fp32 matrix kernels where they may (hnsw_scan_matrix.hip)
+        if (value != 0 && value != 1) return fail(HNSW_ERR_BAD_ARG, "scan_matrix=%lld: 0 (off) or 1", (long long)value);
+        idx->scan_matrix = (int)value;
+        return HNSW_OK;
+    }
     if (!strcmp(name, "graph_chunk_rows")) {         // the nodes hnsw_knn_graph searches per inner call (hnsw_by_id.hip)
         if (value < 1) return fail(HNSW_ERR_BAD_ARG, "graph_chunk_rows=%lld: a chunk holds at least one node", (long long)value);
         idx->graph_chunk_rows = std::min<int64_t>(value, 0x7FFFFFFF);
@@ -1276,7 +1281,7 @@ int hnsw_host::get_option(const hnsw_index *idx, const char *name, int64_t *valu
         {"split_rows", idx->split_rows_freed ? -1 : idx->split_rows_off ? 0 : 1},
         {"bit_query_bits", idx->bit_query_bits}, {"refine", idx->refine}, {"time_kernels", idx->time_kernels ? 1 : 0},
         {"visited_blocks", idx->blk_mode}, {"device_fallback_slab_bytes", (int64_t)idx->dFbSlab.bytes},
-        {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"scan_bytes", idx->scan_bytes}, {"graph_chunk_rows", idx->graph_chunk_rows}, {"filter_collect", idx->filter_collect ? 1 : 0}};
+        {"order_queries", idx->order_mode}, {"head_queries", idx->head_queries}, {"scan_slabs", idx->scan_slabs}, {"scan_bytes", idx->scan_bytes}, {"scan_matrix", idx->scan_matrix}, {"graph_chunk_rows", idx->graph_chunk_rows}, {"filter_collect", idx->filter_collect ? 1 : 0}};
     for (const auto &o : now) if (!strcmp(name, o.name)) { *value = o.value; return HNSW_OK; }
     // (a lossy copy's option: 1 while it is on, the bit rows: their mode)
     if (const LossyRows k = lossy_rows_by_option(name)) { *value = idx->lossy_on != k ? 0 : k_lossy_rows[k].value_is_mode ? idx->bit_mode : 1; return HNSW_OK; }

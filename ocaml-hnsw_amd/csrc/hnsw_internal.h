@@ -4,6 +4,7 @@
 #include "hnsw_device.hip.h"
 #include "hnsw_scan_plan.h"
 #include "hnsw_scan_bytes_plan.h"
+#include "hnsw_scan_matrix_plan.h"
 #include "hnsw_filter_plan.h"
 #include "hnsw_remove_plan.h"
 #include "hnsw_mark_plan.h"
@@ -580,6 +581,9 @@ struct hnsw_index : hnsw_host::LossyParams {
     // never.  scan_path_known: what the last scan_search launched when the host knows it (SCAN_PATH_NONE / _FLOAT); -1: the
     // prepass decided on the device, hnsw_index_scan_path reads scratch.scan_state's first word
     int scan_bytes = 0, scan_path_known = 0;
+    // option "scan_matrix": 1 = scan_search screens float rows with the fp32 matrix kernels where it may (scan_matrix_eligible;
+    // hnsw_scan_matrix.hip); 0 (default): never.  Not saved.
+    int scan_matrix = 0;
     std::vector<std::pair<int, int>> prepared;   // (ef, accept rule) of every hnsw_index_prepare: what hnsw_index_save writes down
     // what the options "byte_rows" / "split_rows" asked for (bind_view leaves an unused copy out of the view), so that
     // hnsw_index_insert, which makes the row copies again, keeps their effect: byte_rows 0, split_rows 0 (off), split_rows -1
@@ -927,6 +931,12 @@ int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, h
 // *path = the device word the float kernels behind them compare with SCAN_PATH_FLOAT.  masks: null, or the table whose first mask applies.
 int scan_bytes_launch(::hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
                       uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path);
+// hnsw_scan_matrix.hip: the same for the float matrix scan over the float32 rows (option "scan_matrix"); the path word says SCAN_PATH_MATRIX
+// where it ran.  Its query terms share scratch.scan_codes with the byte scan's codes: a handle takes one of the two paths.
+int scan_matrix_launch(::hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
+                       uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path);
+// hnsw_scan_bytes.hip: the handle's path word and the prepasses' two counters (scratch.scan_state), zeroed once on `st`
+int ensure_scan_state(::hnsw_index *idx, hipStream_t st);
 // hnsw_scan.hip: what the exact scans check of a call, as check_batch does for the knn searches (k in 1..1024, the fill, nq, then -- unless
 // nq is 0 -- the buffers and q_stride)
 int check_scan(const ::hnsw_index *idx, int64_t nq, int64_t q_stride, int32_t k, int32_t fill, bool buffers);

@@ -98,7 +98,7 @@ template <int NCH, bool MASKED> struct ScanTopK : ScanMask<MASKED> {
 template <int NCH, int METRIC>
 __global__ void __launch_bounds__(64 * SCAN_WAVES, scan_min_waves(NCH))
 hnsw_scan_kernel(const IndexView iv, const ScanArgs a, const uint32_t *path, uint32_t expect) {
-    if (path && *path != expect) return;            // (the byte scan of hnsw_scan_bytes.hip filled the lists; null: no such question)
+    if (path && *path != expect) return;            // (a matrix scan -- hnsw_scan_bytes.hip, hnsw_scan_matrix.hip -- filled the lists; null: no such question)
     ScanTopK<NCH, false> sel(a, nullptr);
     scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
@@ -203,7 +203,10 @@ int scan_search(hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hip
     // option "scan_bytes": byte rows and d <= 256 send every piece through the byte scan's prepass and kernels first; the float
     // kernels behind them run only when the prepass found a query value that is no byte (the path word; no host round trip)
     const bool bytes = scan_bytes_eligible(idx->scan_bytes, idx->tables.X8.p != nullptr, iv.d, tile_filter != nullptr) && c.slabs > 0;
-    if (c.slabs > 0) idx->scan_path_known = bytes ? -1 : SCAN_PATH_FLOAT;      // (an empty table: no scan kernel is launched)
+    // option "scan_matrix": float rows of d <= 512 go through the matrix scan's prepass and kernels the same way (a handle the byte
+    // scan may serve keeps the byte scan); the float kernels behind them run only when a query value is not finite
+    const bool matrix = scan_matrix_eligible(idx->scan_matrix, bytes, iv.d, tile_filter != nullptr) && c.slabs > 0;
+    if (c.slabs > 0) idx->scan_path_known = bytes || matrix ? -1 : SCAN_PATH_FLOAT;      // (an empty table: no scan kernel is launched)
     for (int64_t q0 = 0; q0 < b.nq; q0 += c.piece) {
         const int64_t nq = std::min(c.piece, b.nq - q0);
         // a piece's first query is its first tile's first: scan_plan cuts pieces of a multiple of T queries (or makes one piece), so
@@ -212,6 +215,7 @@ int scan_search(hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, hip
         ScanArgs a{b.Q + q0 * b.q_stride, b.q_stride, nq, k, (int32_t)c.slabs, c.slab_rows, (uint64_t *)idx->scratch.scan.p};
         const uint32_t *path = nullptr;
         if (bytes && (rc = scan_bytes_launch(idx, a.Q, a.q_stride, nq, k, c.nch, c.slabs, c.slab_rows, a.lists, masks, st, &path))) return rc;
+        if (matrix && (rc = scan_matrix_launch(idx, a.Q, a.q_stride, nq, k, c.nch, c.slabs, c.slab_rows, a.lists, masks, st, &path))) return rc;
         if (c.slabs > 0) {
             with_metric(idx->info.metric, [&](auto METRIC) { with_nch(c.nch, [&](auto NCH) {
                 if (masks) hipLaunchKernelGGL((hnsw_dev::hnsw_scan_masked_kernel<NCH, METRIC>), c.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, iv, a, masks, tile_filter, q0 / c.T,

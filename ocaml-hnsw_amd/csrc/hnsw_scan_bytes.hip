@@ -286,7 +286,7 @@ namespace hnsw_host {
 
 // the handle's path word and the prepass's two counters, zeroed once by a one-thread kernel on the stream of the first launch that
 // reads them (no blocking copy; a kernel, not a memset node, so the launch may also be recorded)
-static int ensure_scan_state(hnsw_index *idx, hipStream_t st) {
+int ensure_scan_state(hnsw_index *idx, hipStream_t st) {
     if (idx->scratch.scan_state.p) return HNSW_OK;
     int rc = idx->scratch.scan_state.ensure(16);
     if (rc) return rc;

@@ -16,6 +16,23 @@ __host__ __device__ constexpr int scan_rows(int nch) { return nch == 1 ? 4 : nch
 // allows them: profiles/scan_family_resources.txt)
 __host__ __device__ constexpr int scan_min_waves(int nch) { return nch == 1 || nch == 8 ? 4 : nch == 16 ? 2 : 3; }
 
+// One float4 chunk of the scans' distance arithmetic: the lane's fmaf chain over a row chunk z and a query chunk qi.  scan_slab and the
+// exact evaluation of the float matrix scan's survivors (hnsw_scan_matrix.hip) both go through it, so their keys are the same bits.
+template <int METRIC> __device__ __forceinline__ float scan_chain(float acc, const float4 z, const float4 qi) {
+    if (METRIC == 0) {
+        float dx = z.x - qi.x; acc = __builtin_fmaf(dx, dx, acc);
+        float dy = z.y - qi.y; acc = __builtin_fmaf(dy, dy, acc);
+        float dz = z.z - qi.z; acc = __builtin_fmaf(dz, dz, acc);
+        float dw = z.w - qi.w; acc = __builtin_fmaf(dw, dw, acc);
+    } else {
+        acc = __builtin_fmaf(z.x, qi.x, acc);
+        acc = __builtin_fmaf(z.y, qi.y, acc);
+        acc = __builtin_fmaf(z.z, qi.z, acc);
+        acc = __builtin_fmaf(z.w, qi.w, acc);
+    }
+    return acc;
+}
+
 // Grid: (query tiles) x (groups of SCAN_WAVES row slabs), one wave per (tile, slab); slab s = rows [s * slab_rows, min(n, (s + 1)
 // * slab_rows)).  A wave keeps the chunks of the T queries of its tile in registers (NCH <= 4) or shares them with the other
 // waves of its workgroup through LDS (NCH >= 8, as hnsw_distance_kernel does) and walks its rows in id order, 4 * UB rows in
@@ -94,17 +111,7 @@ __device__ __forceinline__ void scan_slab(const IndexView &iv, const float *Q, i
                 for (int i = 0; i < NCH; ++i) {
                     const float4 z = v[u][i];
                     const float4 qi = QLDS ? qs[(t * NCH + i) * 16 + l16] : qv[QLDS ? 0 : t][QLDS ? 0 : i];
-                    if (METRIC == 0) {
-                        float dx = z.x - qi.x; acc = __builtin_fmaf(dx, dx, acc);
-                        float dy = z.y - qi.y; acc = __builtin_fmaf(dy, dy, acc);
-                        float dz = z.z - qi.z; acc = __builtin_fmaf(dz, dz, acc);
-                        float dw = z.w - qi.w; acc = __builtin_fmaf(dw, dw, acc);
-                    } else {
-                        acc = __builtin_fmaf(z.x, qi.x, acc);
-                        acc = __builtin_fmaf(z.y, qi.y, acc);
-                        acc = __builtin_fmaf(z.z, qi.z, acc);
-                        acc = __builtin_fmaf(z.w, qi.w, acc);
-                    }
+                    acc = scan_chain<METRIC>(acc, z, qi);
                 }
                 sel.take(t, dist_to_key<METRIC>(reduce16(acc)), row, ok);
             }

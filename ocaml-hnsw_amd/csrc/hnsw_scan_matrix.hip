@@ -1,0 +1,354 @@
+// hnsw_scan_matrix.hip -- the exact k-nearest scan of float rows through fp32 matrix instructions (option "scan_matrix").
+//
+// The float scan's key comes from a fixed fmaf chain per 16-lane group and the reduce16 tree (hnsw_scan_device.hip.h); no matrix
+// instruction sums in that order.  So the matrix unit never makes a key here.  It SCREENS: per (row, query) pair it yields a proven
+// bound (hnsw_scan_matrix_plan.h) and a pair is dropped only when that bound shows its exact key above the
+// query's current k-th word.  Every pair that is not dropped is evaluated by the scan's own chain (scan_chain, reduce16,
+// dist_to_key) and enters the lists with that key: the lists, scan_flush and hnsw_scan_merge_kernel are the float scan's, and so
+// are the ids and the distance bits.  Only the speed depends on the bound being tight.
+//
+// Two kernels in front of the unchanged float kernels and hnsw_scan_merge_kernel.
+//   hnsw_scan_matrix_queries_kernel<METRIC>: one wave per query.  Writes the query's term of the screen (its squared norm folded
+//     with the margin) and -- the last wave to finish -- the handle's path word: 3 when every value of the launch's queries is
+//     finite, else 1 (the float kernels, launched behind with the same lists, return unless it is 1).
+//   hnsw_scan_matrix_kernel<NCH, METRIC, MASKED>: grid (tiles of 32 queries) x (groups of slabs), one wave per (tile, slab),
+//     scan_matrix_waves(NCH) waves per workgroup.  Rows are taken as 64 * NCH floats wide (NCH = pick_nch, at most 8: d <= 512).
+//     B operand: the tile's 32 queries in LDS as float32, zero beyond d and beyond the tile's last query, loaded once by the
+//       workgroup and shared by its waves; the row pitch is padded by 4 floats so that the lanes of one ds_read_b128 pass spread
+//       over the banks.
+//     A operand: a block of 32 rows (aligned to 32, so that it is one mask word) straight from global memory, float4 per lane:
+//       lane (j = l % 32, h = l / 32) holds floats [8 s + 4 h, + 4) of row base + j at step s and reads the same floats of query
+//       j from the tile; component c of the pair feeds one v_mfma_f32_32x32x2_f32 (k = 8 s + c and 8 s + 4 + c: which k a
+//       register stands for does not matter, both operands use one map and the sum is over all k).  One load, four instructions.
+//     Pipeline: a stage is a block's piece of scan_matrix_piece(NCH) floats per row (32 or 64 VGPRs); the next stage's loads --
+//       the block's next piece or the next block's first -- are in flight while this one is multiplied.  16 accumulators.
+//     Row norms: fma over the lane's floats of the operand registers and one cross-half exchange; they reach the accumulator
+//       layout (lane l: query l % 32, rows 8 a + 4 (l / 32) + b of the block) through 128 bytes of LDS.  No table of norms exists:
+//       insert, remove, upsert and compact have nothing to maintain.
+//     Common path: one multiply-add (L2) or subtract (IP) and one compare per accumulator against the lane's bound.  A masked or
+//       out-of-slab row's term is +inf: above every bound.
+//     Survivors go, as bare row numbers, into the query's 64-word LDS buffer.  A buffer that may not take another block (and, at
+//       the slab's end, every buffer) gets its exact keys: one 16-lane group per pair, eight pairs a round, the row read again
+//       (from L2) and the query's chunks from the tile.  A word not below the query's k-th word is discarded, the others are
+//       packed in place and merged into the query's list by scan_flush, and the bound is refreshed.  (The k-th word changes only
+//       at a merge, so an earlier key would drop nothing more.)
+#include "hnsw_internal.h"
+#include "hnsw_scan_device.hip.h"
+
+namespace hnsw_dev {
+
+using namespace hnsw_host;      // the plan header's constants and the rule
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+struct ScanMatrixArgs {
+    const float *X;        // [n][stride] zero-padded rows
+    int64_t stride, n;
+    int32_t d, nchunks;
+    const float *Q;        // the queries of this launch
+    int64_t q_stride, nq;
+    const float *qterm;    // [nq] as the prepass wrote them
+    int32_t k, n_slabs;
+    int64_t slab_rows;
+    uint64_t *lists;
+    const uint32_t *path;  // the handle's path word
+    float eps;             // scan_matrix_eps(d)
+};
+
+// state: the byte prepass's three words (hnsw_scan_bytes.hip): [0] the path word, [1] "a value was not finite" of the launch in
+// flight, [2] its finished waves.  One exact scan is in flight per handle.
+template <int METRIC>
+__global__ void __launch_bounds__(256)
+hnsw_scan_matrix_queries_kernel(const float *Q, int64_t q_stride, int64_t nq, int32_t d, float eps, float *qterm, uint32_t *state) {
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    bool ok = true;
+    if (q < nq) {
+        float s = 0.f;
+        for (int e = lane; e < d; e += 64) {
+            const float v = Q[q * q_stride + e];
+            ok = ok && __builtin_fabsf(v) <= FLT_MAX;
+            s = __builtin_fmaf(v, v, s);
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+        if (lane == 0) qterm[q] = scan_matrix_query_term(METRIC, s, eps);
+    }
+    const bool bad = ballot(!ok) != 0ull;
+    if (lane == 0) {
+        if (bad) atomicOr(&state[1], 1u);
+        __threadfence();
+        if (atomicAdd(&state[2], 1u) == gridDim.x * 4u - 1u) {      // the launch's last wave
+            __threadfence();
+            const uint32_t any_bad = atomicExch(&state[1], 0u);
+            atomicExch(&state[2], 0u);
+            state[0] = any_bad ? (uint32_t)SCAN_PATH_FLOAT : (uint32_t)SCAN_PATH_MATRIX;
+        }
+    }
+}
+
+// the bound a lane compares its accumulators' screen values against: from the query's k-th word so far and the query's term
+template <int METRIC> __device__ __forceinline__ float scan_matrix_lane_bound(uint64_t thr, float qterm) {
+    if (thr == SCAN_EMPTY) return __builtin_inff();         // fewer than k words so far: every row survives
+    const uint32_t key = (uint32_t)(thr >> 32);
+    return scan_matrix_bound(METRIC, METRIC == 0 ? __uint_as_float(key) : key_to_dist<1>(key), qterm);
+}
+
+// LDS words one lane wrote, read by the other lanes of its wave: a wave's LDS operations complete in issue order, so the compiler
+// alone must be held (scan_wave_sync would also wait for the row loads in flight)
+__device__ __forceinline__ void scan_matrix_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The exact key of (row, the query whose chunks lie at qrow in the tile), by one 16-lane group: scan_slab's arithmetic -- lane l16 on
+// the chunks l16, l16 + 16, ..., zero beyond the row's end, the fmaf chain, the tree.
+template <int NCH, int METRIC>
+__device__ __forceinline__ uint32_t scan_matrix_exact_key(const float *rp, int nchunks, const float *qrow, int l16) {
+    float4 z[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = i * 16 + l16;
+        z[i] = *reinterpret_cast<const float4 *>(rp + 4 * (c < nchunks ? c : 0));
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = i * 16 + l16;
+        if (c >= nchunks) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        acc = scan_chain<METRIC>(acc, z[i], *reinterpret_cast<const float4 *>(qrow + 4 * c));
+    }
+    return dist_to_key<METRIC>(reduce16(acc));
+}
+
+template <int NCH, int METRIC, bool MASKED>
+__global__ void __launch_bounds__(64 * scan_matrix_waves(NCH))
+hnsw_scan_matrix_kernel(const ScanMatrixArgs a, const uint32_t *const *masks) {
+    constexpr int T = SCAN_MATRIX_TILE, W = scan_matrix_waves(NCH);
+    constexpr int KW = scan_matrix_width(NCH), PITCH = scan_matrix_pitch(NCH);
+    constexpr int PF = scan_matrix_piece(NCH), SP = PF / 8;     // floats of a row per stage; steps (float4 per lane) per stage
+    constexpr int LIMIT = SCAN_BUF - 32;                        // a buffer up to here takes the survivors of one more block
+    static_assert(NCH == 1 || NCH == 2 || NCH == 4 || NCH == 8, "rows of 64 to 512 floats");
+    static_assert(SCAN_BUF == 64 && SCAN_MATRIX_WAVE_BYTES == T * SCAN_BUF * 8 + SCAN_BUF * 8 + T * 4 + 32 * 4, "the plan header's LDS");
+    __shared__ __attribute__((aligned(16))) float tile[T * PITCH];
+    __shared__ uint64_t bufs_all[W][T][SCAN_BUF];
+    __shared__ uint64_t sorted_all[W][SCAN_BUF];
+    __shared__ int cnt_all[W][T];
+    __shared__ __attribute__((aligned(16))) float rterm_all[W][32];
+    if (*a.path != (uint32_t)SCAN_PATH_MATRIX) return;          // (the whole workgroup: before the barrier)
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;     // the lane's query column (and row of the A operand); which half of a step's k range
+    const int64_t q0 = (int64_t)blockIdx.x * T;
+    const int tq = (int)(a.nq - q0 < T ? a.nq - q0 : T);
+    // the tile, once per workgroup: zero beyond d and beyond the tile's last query
+    for (int c = threadIdx.x; c < T * (KW / 4); c += 64 * W) {
+        const int t = c / (KW / 4), e0 = 4 * (c % (KW / 4));
+        const float *qp = a.Q + (q0 + (t < tq ? t : 0)) * a.q_stride;
+        float4 v;
+        v.x = (t < tq && e0 + 0 < a.d) ? qp[e0 + 0] : 0.f; v.y = (t < tq && e0 + 1 < a.d) ? qp[e0 + 1] : 0.f;
+        v.z = (t < tq && e0 + 2 < a.d) ? qp[e0 + 2] : 0.f; v.w = (t < tq && e0 + 3 < a.d) ? qp[e0 + 3] : 0.f;
+        *reinterpret_cast<float4 *>(tile + t * PITCH + e0) = v;
+    }
+    __syncthreads();
+    const int64_t slab = (int64_t)blockIdx.y * W + uniform(wave);
+    if (slab >= a.n_slabs) return;              // (after the only workgroup barrier)
+    const int64_t r0 = slab * a.slab_rows, r1 = r0 + a.slab_rows < a.n ? r0 + a.slab_rows : a.n;
+    const MaskWords mask = mask_words(MASKED ? masks[0] : nullptr);
+    uint64_t (*const bufs)[SCAN_BUF] = bufs_all[wave];
+    uint64_t *const sorted = sorted_all[wave];
+    int *const cnt = cnt_all[wave];
+    float *const rterm = rterm_all[wave];
+    const int nchunks = a.nchunks;
+    const int np = (4 * nchunks + PF - 1) / PF;                 // stages per block: the pieces that hold a real dimension
+
+    const float cq = j < tq ? a.qterm[q0 + j] : 0.f;
+    uint64_t *const lists0 = a.lists + ((q0 * a.n_slabs + slab) * 2) * (int64_t)a.k;
+    const int64_t list_step = (int64_t)a.n_slabs * 2 * a.k;
+    for (int t = 0; t < tq; ++t) for (int i = lane; i < a.k; i += 64) lists0[t * list_step + i] = SCAN_EMPTY;
+    if (lane < T) cnt[lane] = 0;
+    scan_wave_sync();
+    uint64_t thr = j < tq ? SCAN_EMPTY : 0ull;                  // the query's k-th word so far (no word is below 0)
+    float bound = j < tq ? __builtin_inff() : -__builtin_inff();
+    uint32_t par = 0;                                           // bit t: query t's current list is the second half
+
+    // merges query t's buffer of c words into its list
+    auto flush = [&](int t, int c) {
+        if (c == 0) { if (lane == 0) cnt[t] = 0; return; }
+        uint64_t *const A = lists0 + t * list_step;
+        const bool p = (par >> t) & 1u;
+        scan_flush(bufs[t], sorted, c, A + (p ? a.k : 0), A + (p ? 0 : a.k), a.k, lane);
+        par ^= 1u << t;
+        if (lane == 0) cnt[t] = 0;
+    };
+    // the rows of the 32-row block at `base` that may be candidates: in the slab, and allowed (wave-uniform)
+    auto candidates = [&](int64_t base) -> uint32_t {
+        const int lo = r0 > base ? (int)(r0 - base) : 0;
+        const int64_t left = r1 - base;
+        uint32_t w = (left >= 32 ? ~0u : ((1u << (int)left) - 1u)) & (~0u << lo);
+        if constexpr (MASKED) w &= (uint32_t)uniform((int)mask[base >> 5]);
+        return w;
+    };
+    // piece p of row base + j, the lane's float4 per step; the row clamped into the slab (a clamped row is no candidate) and a chunk
+    // past the row's end clamped to its first (zeroed before use)
+    auto load = [&](float4 (&x)[SP], int64_t base, int p) {
+        int64_t row = base + j;
+        row = row < r0 ? r0 : row;
+        row = row < r1 ? row : r1 - 1;
+        const float *rp = a.X + (uint64_t)row * (uint64_t)a.stride;
+#pragma unroll
+        for (int s = 0; s < SP; ++s) {
+            const int c = 2 * (SP * p + s) + h;
+            x[s] = *reinterpret_cast<const float4 *>(rp + 4 * (c < nchunks ? c : 0));
+        }
+    };
+
+    // The c bare row numbers of query t's buffer get their exact keys, eight pairs a round (one 16-lane group per pair, two pairs per
+    // group so that two rows' loads are in flight); a word not below the query's k-th word is discarded, the others are packed in
+    // place, never ahead of what the round read.  Returns how many words are left.  (Deferred to the buffer's merge: the k-th word
+    // changes only there, so nothing is gained by knowing a key sooner.)
+    auto evaluate = [&](int t, int c) -> int {
+        const uint64_t thr_t = ((uint64_t)rdlane((uint32_t)(thr >> 32), t) << 32) | rdlane((uint32_t)thr, t);
+        const float *const qrow = tile + t * PITCH;
+        int w = 0;
+        for (int i = 0; i < c; i += 8) {
+            uint32_t row[2], key[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) { const int at = i + 4 * u + (lane >> 4); row[u] = (uint32_t)bufs[t][at < c ? at : 0]; }
+            scan_matrix_lds_sync();
+#pragma unroll
+            for (int u = 0; u < 2; ++u) key[u] = scan_matrix_exact_key<NCH, METRIC>(a.X + (uint64_t)row[u] * (uint64_t)a.stride, nchunks, qrow, lane & 15);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const uint64_t e = ((uint64_t)key[u] << 32) | row[u];
+                const bool in = (lane & 15) == 0 && i + 4 * u + (lane >> 4) < c && e < thr_t;
+                const uint64_t m = ballot(in);
+                if (in) bufs[t][w + popc(m & ((1ull << lane) - 1ull))] = e;
+                w += popc(m);
+            }
+        }
+        return w;
+    };
+
+    int64_t base = r0 & ~31ll;
+    uint32_t vw = 0;
+    while (base < r1 && (vw = candidates(base)) == 0u) base += 32;
+    float4 an[SP];
+    if (base < r1) load(an, base, 0);
+    while (base < r1) {
+        const int64_t cur = base;
+        const uint32_t cw = vw;
+        v16f acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float nx = 0.f;
+        for (int p = 0; p < np; ++p) {
+            float4 ax[SP];
+#pragma unroll
+            for (int s = 0; s < SP; ++s) ax[s] = an[s];
+            if (p + 1 < np) load(an, cur, p + 1);
+            else {
+                base += 32;
+                while (base < r1 && (vw = candidates(base)) == 0u) base += 32;
+                if (base < r1) load(an, base, 0);
+            }
+            if (p == np - 1) {                  // only the last piece reaches past the row's end
+#pragma unroll
+                for (int s = 0; s < SP; ++s) if (2 * (SP * p + s) + h >= nchunks) ax[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            const float *bp = tile + j * PITCH + PF * p + 4 * h;
+#pragma unroll
+            for (int s = 0; s < SP; ++s) {
+                const float4 b = *reinterpret_cast<const float4 *>(bp + 8 * s);
+                nx = __builtin_fmaf(ax[s].x, ax[s].x, nx); nx = __builtin_fmaf(ax[s].y, ax[s].y, nx);
+                nx = __builtin_fmaf(ax[s].z, ax[s].z, nx); nx = __builtin_fmaf(ax[s].w, ax[s].w, nx);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].x, b.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].y, b.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].z, b.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].w, b.w, acc, 0, 0, 0);
+            }
+        }
+
+        nx += __int_as_float(__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __float_as_int(nx)));   // the other half of the row
+        float rt = scan_matrix_row_term(METRIC, nx, a.eps);
+        if (!((cw >> j) & 1u)) rt = __builtin_inff();           // no candidate: above every bound
+        if (h == 0) rterm[j] = rt;
+        scan_matrix_lds_sync();
+
+        // accumulator v of the lane: row 8 (v / 4) + 4 h + v % 4 of the block, query j
+        float tv[16];
+        bool any = false;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 rr = *reinterpret_cast<const float4 *>(rterm + 8 * g + 4 * h);
+            tv[4 * g + 0] = scan_matrix_value(METRIC, rr.x, acc[4 * g + 0]);
+            tv[4 * g + 1] = scan_matrix_value(METRIC, rr.y, acc[4 * g + 1]);
+            tv[4 * g + 2] = scan_matrix_value(METRIC, rr.z, acc[4 * g + 2]);
+            tv[4 * g + 3] = scan_matrix_value(METRIC, rr.w, acc[4 * g + 3]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) any = any || scan_matrix_survives(tv[4 * g + c], bound);
+        }
+        if (ballot(any)) {                      // rare once the lists are full
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int ri = 8 * (v >> 2) + 4 * h + (v & 3);
+                if (scan_matrix_survives(tv[v], bound) && ((cw >> ri) & 1u) && j < tq) bufs[j][atomicAdd(&cnt[j], 1)] = (uint32_t)(cur + ri);
+            }
+            scan_wave_sync();
+            const int c = cnt[j];               // (at most LIMIT + 32 = SCAN_BUF: a row of the block survives once per query)
+            uint32_t need = (uint32_t)ballot(h == 0 && c > LIMIT);
+            if (need) {
+                while (need) {
+                    const int t = __builtin_ctz(need);
+                    need &= need - 1u;
+                    flush(t, evaluate(t, __builtin_amdgcn_readlane(c, t)));
+                }
+                scan_wave_sync();
+                if (j < tq) {
+                    thr = (lists0 + j * list_step + (((par >> j) & 1u) ? a.k : 0))[a.k - 1];
+                    bound = scan_matrix_lane_bound<METRIC>(thr, cq);
+                }
+            }
+        }
+    }
+    // what is left in the buffers; the result belongs in the first half
+    scan_wave_sync();
+    for (int t = 0; t < tq; ++t) {
+        const int c = uniform(cnt[t]);
+        if (c > 0) flush(t, evaluate(t, c));
+        uint64_t *const A = lists0 + t * list_step;
+        if ((par >> t) & 1u) for (int i = lane; i < a.k; i += 64) A[i] = A[a.k + i];
+    }
+}
+
+} // namespace hnsw_dev
+
+namespace hnsw_host {
+
+int scan_matrix_launch(hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
+                       uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path) {
+    int rc = ensure_scan_state(idx, st);
+    if (rc) return rc;
+    const hnsw_dev::IndexView &iv = idx->iv;
+    if (nch != scan_matrix_nch(iv.d)) return fail(HNSW_ERR_HIP, "matrix scan: %d chunks per lane for d=%d", nch, iv.d);
+    if ((rc = idx->scratch.scan_codes.ensure((size_t)scan_matrix_scratch(nq)))) return rc;
+    float *const qterm = (float *)idx->scratch.scan_codes.p;
+    uint32_t *const state = (uint32_t *)idx->scratch.scan_state.p;
+    const float eps = scan_matrix_eps(iv.d);
+    with_metric(idx->info.metric, [&](auto METRIC) {
+        hipLaunchKernelGGL(hnsw_dev::hnsw_scan_matrix_queries_kernel<METRIC>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, Q, q_stride, nq, iv.d,
+                           eps, qterm, state);
+    });
+    if ((rc = launched("matrix scan query prepass"))) return rc;
+    const hnsw_dev::ScanMatrixArgs a{iv.X, iv.stride, iv.n, iv.d, iv.nchunks, Q, q_stride, nq, qterm, k, (int32_t)slabs, slab_rows, lists, state, eps};
+    const dim3 grid((unsigned)scan_matrix_tiles(nq), (unsigned)scan_matrix_slab_groups(slabs, nch));
+    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {
+        if constexpr (NCH <= 8) {
+            if (masks) hipLaunchKernelGGL((hnsw_dev::hnsw_scan_matrix_kernel<NCH, METRIC, true>), grid, dim3(64 * scan_matrix_waves(NCH)), 0, st, a, masks);
+            else hipLaunchKernelGGL((hnsw_dev::hnsw_scan_matrix_kernel<NCH, METRIC, false>), grid, dim3(64 * scan_matrix_waves(NCH)), 0, st, a, masks);
+        }
+    }); });
+    if ((rc = launched("matrix scan kernel"))) return rc;
+    *path = state;
+    return HNSW_OK;
+}
+
+} // namespace hnsw_host
