@@ -294,9 +294,13 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   far, and every other pair is evaluated by the float scan's own arithmetic.  Same ids, same distance bits,
  *                   by construction; only the speed depends on the data (norms far above the distances let most pairs
  *                   through).  A launch any of whose query values is not finite runs the float kernels instead, decided on
- *                   the device.  hnsw_index_scan_path tells which ran (3).  Any other value is refused.  Not saved.  Not
- *                   built: the range, grouped and paged scans, per-query filters, d > 512, half, sq8 or bit rows as scan
- *                   operands, a bf16 or split-precision screen.  Measured: profiles/scan_matrix.txt;
+ *                   the device.  hnsw_index_scan_path tells which ran (3).  The exact range scans (both passes, plain and
+ *                   masked: hnsw_range_brute_force_batch, the exact stage of hnsw_range_search_batch, their filtered forms,
+ *                   under marks, the shards') are screened the same way against the radius's largest key, which is fixed from
+ *                   the first row on: same lims, ids and distance bits; a handle "scan_bytes" takes keeps the float range
+ *                   kernels.  Any other value is refused.  Not saved.  Not built: the grouped and paged scans, per-query
+ *                   filters, d > 512, half, sq8 or bit rows as scan operands, a bf16 or split-precision screen.  Measured:
+ *                   profiles/scan_matrix.txt, profiles/range_matrix.txt;
  *   "byte_rows"     when every value of the vectors is an integer in 0..255 (SIFT descriptors stored as
  *                   float32) the index keeps a second, lossless copy of the rows as bytes and the knn
  *                   searches read that one: each byte is converted back to the float it came from and
@@ -719,7 +723,8 @@ int32_t hnsw_brute_force_batch_device(hnsw_index *idx, const float *d_queries, i
                                       int32_t k, int32_t fill, int32_t *d_ids, float *d_dist, void *stream);
 /* What the handle's last exact-scan launch ran (options "scan_bytes", "scan_matrix"): *out = 0 none yet, 1 the float scan, 2 the
  * matrix scan over the byte rows, 3 the float matrix scan.  Where the queries decided it on the device, the call waits for the
- * device and reads the word. */
+ * device and reads the word.  The exact range scans (hnsw_range_brute_force_batch, the exact stage of hnsw_range_search_batch, their
+ * filtered forms) report here as well: 3 under "scan_matrix", else 1 -- the range scan has no byte form. */
 int32_t hnsw_index_scan_path(hnsw_index *idx, int32_t *out);
 
 /* Exact re-ranking of caller-given candidates (the refine step of option "refine" as an operator of its own): for query q the

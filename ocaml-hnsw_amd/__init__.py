@@ -563,7 +563,9 @@ class Hgraph:
     def scan_path(self):
         """hnsw_index_scan_path: what the handle's last exact-scan launch ran: 0 none yet, 1 the float scan, 2 the matrix scan over
         the byte rows (set_option("scan_bytes", 1), byte-valued data and queries, d <= 256), 3 the float matrix scan
-        (SCAN_PATH_MATRIX: set_option("scan_matrix", 1), finite queries, d <= 512)"""
+        (SCAN_PATH_MATRIX: set_option("scan_matrix", 1), finite queries, d <= 512).  The exact range scans report here too
+        (brute_force_range, the exact stage of range_search, their filtered forms): 3 under "scan_matrix", else 1 -- the range scan
+        has no byte form"""
         v = _C.c_int32(0)
         _check(load().hnsw_index_scan_path(self.handle, _C.byref(v)))
         return v.value

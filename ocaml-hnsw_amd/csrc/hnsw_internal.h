@@ -643,6 +643,8 @@ struct hnsw_index : hnsw_host::LossyParams {
 
 namespace hnsw_dev {
 
+struct RangeScanArgs;       // one launch of the exact range scan (hnsw_scan_device.hip.h)
+
 // (MaskWords / mask_words, a mask's words as a kernel reads them: hnsw_device.hip.h, beside the collect kernel's use of them)
 
 // is the id_base-based id one of the n nodes (a filled entry of W is not) ...
@@ -935,6 +937,13 @@ int scan_bytes_launch(::hnsw_index *idx, const float *Q, int64_t q_stride, int64
 // where it ran.  Its query terms share scratch.scan_codes with the byte scan's codes: a handle takes one of the two paths.
 int scan_matrix_launch(::hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
                        uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path);
+// ... its prepass alone: the queries' terms of the screen (*qterm, nq floats in scratch.scan_codes) and the path word (*path)
+int scan_matrix_prepass(::hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int nch, hipStream_t st, const float **qterm,
+                        const uint32_t **path);
+// hnsw_range_matrix.hip: one pass (0 counts, 1 writes the words) of the exact range scan of a's queries through the matrix screen;
+// pass 0 runs the prepass first, pass 1 reads what the pass 0 before it left.  mask: null, or the allow-mask.  *path as above.
+int range_matrix_launch(::hnsw_index *idx, int pass, int nch, const hnsw_dev::RangeScanArgs &a, const uint32_t *mask, hipStream_t st,
+                        const uint32_t **path);
 // hnsw_scan_bytes.hip: the handle's path word and the prepasses' two counters (scratch.scan_state), zeroed once on `st`
 int ensure_scan_state(::hnsw_index *idx, hipStream_t st);
 // hnsw_scan.hip: what the exact scans check of a call, as check_batch does for the knn searches (k in 1..1024, the fill, nq, then -- unless

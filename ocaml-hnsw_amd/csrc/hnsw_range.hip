@@ -19,6 +19,9 @@
 //                           calls; the plain ones while nodes are marked deleted): RangeHits<.., MASKED = true>, whose skip / admits
 //                           are ScanMask's, as every policy's -- a disallowed row is never counted, stored or sorted, and a mask
 //                           word without a set bit is stepped over unloaded.
+//   hnsw_range_scan_matrix_kernel (hnsw_range_matrix.hip; option "scan_matrix")  the same two passes, plain and masked, screened by
+//                           fp32 matrix instructions: launched in front of the kernels above into the same cells; those then
+//                           return at once unless the path word says a query value was not finite (path / expect, as the k-scan's).
 //   range_count_kernel      per exact-stage query the sum of its slabs' counts (from the exclusive sum), its counters and stage.
 //   range_unpack_kernel     the sorted words of an exact-stage query as ids (+ id_base) and key_to_dist.
 //   range_select_kernel     one wave per walked query: |W| and the length of W's in-range prefix, 64 entries per pass (ballot).
@@ -40,32 +43,8 @@
 
 namespace hnsw_dev {
 
-struct RangeScanArgs {
-    const float *Q;            // the queries of this launch
-    int64_t q_stride, nq;
-    int32_t n_slabs;
-    int64_t slab_rows;         // slab s = rows [s * slab_rows, min(n, (s + 1) * slab_rows))
-    float radius;
-    uint64_t *counts;          // PASS 0: [nq][n_slabs] hits
-    const uint64_t *offs;      // PASS 1: [nq * n_slabs + 1] the exclusive sum of counts
-    const int64_t *xoff;       // PASS 1: [nq] where query i's words start ...
-    uint64_t *words;           // ... in here
-};
-
-// The keys [lo, hi] whose distance is <= radius (hi < lo: none).  key_to_dist is monotone over the keys of real distances -- [0,
-// +inf] for L2, [-inf, +inf] for the inner product; the keys outside are NaNs, never in range -- so the hits are an interval, found
-// with the comparison the definition names: 32 steps of uniform work per wave instead of a square root per evaluation.
-template <int METRIC> __device__ __forceinline__ void range_key_bounds(float radius, uint32_t &lo, uint32_t &hi) {
-    const uint32_t first = METRIC == 0 ? 0u : 0x007FFFFFu, last = METRIC == 0 ? 0x7F800000u : 0xFF800000u;
-    lo = first;
-    if (!(key_to_dist<METRIC>(first) <= radius)) { lo = 1u; hi = 0u; return; }
-    uint32_t a = first, b = last;              // a is in range; the answer lies in [a, b]
-    while (a < b) {
-        const uint32_t mid = a + ((b - a) >> 1) + 1u;
-        if (key_to_dist<METRIC>(mid) <= radius) a = mid; else b = mid - 1u;
-    }
-    hi = a;
-}
+// (RangeScanArgs and range_key_bounds -- the keys [lo, hi] whose distance is <= radius: hnsw_scan_device.hip.h, shared with the
+// matrix-screened form of the scan, hnsw_range_matrix.hip)
 
 // The hits of one (tile, slab) wave (scan_slab's Select): counted (PASS 0), or written where PASS 0's counts say (PASS 1)
 // MASKED: only the rows the mask allows (skip and admits: ScanMask).
@@ -121,7 +100,8 @@ template <int NCH, int METRIC, int PASS, bool MASKED = false> struct RangeHits :
 
 template <int NCH, int METRIC, int PASS>
 __global__ void __launch_bounds__(64 * SCAN_WAVES, scan_min_waves(NCH))
-hnsw_range_scan_kernel(const IndexView iv, const RangeScanArgs a) {
+hnsw_range_scan_kernel(const IndexView iv, const RangeScanArgs a, const uint32_t *path, uint32_t expect) {
+    if (path && *path != expect) return;            // (the matrix-screened scan, hnsw_range_matrix.hip, served the launch; null: no such question)
     RangeHits<NCH, METRIC, PASS> sel(a);
     scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
@@ -129,7 +109,8 @@ hnsw_range_scan_kernel(const IndexView iv, const RangeScanArgs a) {
 // ... restricted to the rows `mask` allows (a kernel argument: scalar loads, wave-uniform tests)
 template <int NCH, int METRIC, int PASS>
 __global__ void __launch_bounds__(64 * SCAN_WAVES, scan_min_waves(NCH))
-hnsw_range_scan_masked_kernel(const IndexView iv, const RangeScanArgs a, const uint32_t *mask) {
+hnsw_range_scan_masked_kernel(const IndexView iv, const RangeScanArgs a, const uint32_t *mask, const uint32_t *path, uint32_t expect) {
+    if (path && *path != expect) return;
     RangeHits<NCH, METRIC, PASS, true> sel(a, mask);
     scan_slab<NCH, METRIC>(iv, a.Q, a.q_stride, a.nq, a.n_slabs, a.slab_rows, sel);
 }
@@ -289,16 +270,30 @@ struct ExactPlan : ScanCut {
     const int32_t *map = nullptr;
     const uint32_t *mask = nullptr;    // the call's allow-mask (device words), null: every row
     int64_t n_allowed = 0;             // ... and how many rows it allows: what the exact stage adds to out_ndist (no mask: n)
+    // option "scan_matrix": the scan's passes go through the matrix screen first (hnsw_range_matrix.hip), under scan_search's rule: a
+    // handle the byte scan would take keeps the float kernels (the range scan has no byte form)
+    bool matrix = false;
     // (a count and an offset per (query, slab) cell)
-    void cut(const hnsw_index *idx) { static_cast<ScanCut &>(*this) = scan_cut(idx, m, 1, 16, m); }
+    void cut(hnsw_index *idx) {
+        static_cast<ScanCut &>(*this) = scan_cut(idx, m, 1, 16, m);
+        const bool bytes = scan_bytes_eligible(idx->scan_bytes, idx->tables.X8.p != nullptr, idx->iv.d, false);
+        matrix = scan_matrix_eligible(idx->scan_matrix, bytes, idx->iv.d, false) && slabs > 0;
+        if (slabs > 0) idx->scan_path_known = matrix ? -1 : SCAN_PATH_FLOAT;       // (an empty table: no scan kernel is launched)
+    }
 };
 
-int launch_range_scan(const hnsw_index *idx, const ExactPlan &x, int pass, int64_t nq, const hnsw_dev::RangeScanArgs &a, hipStream_t st) {
+// one pass over nq queries: the matrix kernels where the plan says so, then the float kernels -- which, behind the matrix kernels,
+// run only when the prepass found a query value that is not finite (the path word; no host round trip)
+int launch_range_scan(hnsw_index *idx, const ExactPlan &x, int pass, int64_t nq, const hnsw_dev::RangeScanArgs &a, hipStream_t st) {
+    const uint32_t *path = nullptr;
+    int rc;
+    if (x.matrix && (rc = range_matrix_launch(idx, pass, x.nch, a, x.mask, st, &path))) return rc;
+    const uint32_t expect = (uint32_t)SCAN_PATH_FLOAT;
     with_metric(idx->info.metric, [&](auto METRIC) { with_nch(x.nch, [&](auto NCH) {
-        if (x.mask && pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_masked_kernel<NCH, METRIC, 0>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a, x.mask);
-        else if (x.mask) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_masked_kernel<NCH, METRIC, 1>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a, x.mask);
-        else if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 0>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a);
-        else hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 1>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a);
+        if (x.mask && pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_masked_kernel<NCH, METRIC, 0>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a, x.mask, path, expect);
+        else if (x.mask) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_masked_kernel<NCH, METRIC, 1>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a, x.mask, path, expect);
+        else if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 0>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a, path, expect);
+        else hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_kernel<NCH, METRIC, 1>), x.grid(nq), dim3(64 * hnsw_dev::SCAN_WAVES), 0, st, idx->iv, a, path, expect);
     }); });
     return launched("range scan kernel");
 }

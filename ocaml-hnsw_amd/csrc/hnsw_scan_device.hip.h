@@ -137,6 +137,35 @@ template <> struct ScanMask<false> {
     __device__ __forceinline__ bool admits(int64_t, bool in_slab) const { return in_slab; }
 };
 
+// ---- what the kernels of the exact range scan share (RangeHits, hnsw_range.hip; its matrix-screened form, hnsw_range_matrix.hip) ----
+
+struct RangeScanArgs {
+    const float *Q;            // the queries of this launch
+    int64_t q_stride, nq;
+    int32_t n_slabs;
+    int64_t slab_rows;         // slab s = rows [s * slab_rows, min(n, (s + 1) * slab_rows))
+    float radius;
+    uint64_t *counts;          // PASS 0: [nq][n_slabs] hits
+    const uint64_t *offs;      // PASS 1: [nq * n_slabs + 1] the exclusive sum of counts
+    const int64_t *xoff;       // PASS 1: [nq] where query i's words start ...
+    uint64_t *words;           // ... in here
+};
+
+// The keys [lo, hi] whose distance is <= radius (hi < lo: none).  key_to_dist is monotone over the keys of real distances -- [0,
+// +inf] for L2, [-inf, +inf] for the inner product; the keys outside are NaNs, never in range -- so the hits are an interval, found
+// with the comparison the definition names: 32 steps of uniform work per wave instead of a square root per evaluation.
+template <int METRIC> __device__ __forceinline__ void range_key_bounds(float radius, uint32_t &lo, uint32_t &hi) {
+    const uint32_t first = METRIC == 0 ? 0u : 0x007FFFFFu, last = METRIC == 0 ? 0x7F800000u : 0xFF800000u;
+    lo = first;
+    if (!(key_to_dist<METRIC>(first) <= radius)) { lo = 1u; hi = 0u; return; }
+    uint32_t a = first, b = last;              // a is in range; the answer lies in [a, b]
+    while (a < b) {
+        const uint32_t mid = a + ((b - a) >> 1) + 1u;
+        if (key_to_dist<METRIC>(mid) <= radius) a = mid; else b = mid - 1u;
+    }
+    hi = a;
+}
+
 // ---- what the scans that keep the k smallest words per (query, slab) share (ScanTopK, hnsw_scan.hip; ScanAfter, hnsw_after.hip) ----
 
 constexpr int SCAN_BUF = 64;           // survivor words per query and wave (LDS)

@@ -10,7 +10,8 @@
 // Two kernels in front of the unchanged float kernels and hnsw_scan_merge_kernel.
 //   hnsw_scan_matrix_queries_kernel<METRIC>: one wave per query.  Writes the query's term of the screen (its squared norm folded
 //     with the margin) and -- the last wave to finish -- the handle's path word: 3 when every value of the launch's queries is
-//     finite, else 1 (the float kernels, launched behind with the same lists, return unless it is 1).
+//     finite, else 1 (the float kernels, launched behind with the same lists, return unless it is 1).  The range scan's matrix
+//     kernel (hnsw_range_matrix.hip) takes its query terms and its path word from the same prepass (scan_matrix_prepass).
 //   hnsw_scan_matrix_kernel<NCH, METRIC, MASKED>: grid (tiles of 32 queries) x (groups of slabs), one wave per (tile, slab),
 //     scan_matrix_waves(NCH) waves per workgroup.  Rows are taken as 64 * NCH floats wide (NCH = pick_nch, at most 8: d <= 512).
 //     B operand: the tile's 32 queries in LDS as float32, zero beyond d and beyond the tile's last query, loaded once by the
@@ -33,13 +34,13 @@
 //       packed in place and merged into the query's list by scan_flush, and the bound is refreshed.  (The k-th word changes only
 //       at a merge, so an earlier key would drop nothing more.)
 #include "hnsw_internal.h"
-#include "hnsw_scan_device.hip.h"
+#include "hnsw_scan_matrix_device.hip.h"
 
 namespace hnsw_dev {
 
 using namespace hnsw_host;      // the plan header's constants and the rule
 
-typedef float v16f __attribute__((ext_vector_type(16)));
+// (v16f, scan_matrix_lds_sync, scan_matrix_exact_key: hnsw_scan_matrix_device.hip.h -- the range scan's matrix kernel shares them)
 
 struct ScanMatrixArgs {
     const float *X;        // [n][stride] zero-padded rows
@@ -92,33 +93,6 @@ template <int METRIC> __device__ __forceinline__ float scan_matrix_lane_bound(ui
     if (thr == SCAN_EMPTY) return __builtin_inff();         // fewer than k words so far: every row survives
     const uint32_t key = (uint32_t)(thr >> 32);
     return scan_matrix_bound(METRIC, METRIC == 0 ? __uint_as_float(key) : key_to_dist<1>(key), qterm);
-}
-
-// LDS words one lane wrote, read by the other lanes of its wave: a wave's LDS operations complete in issue order, so the compiler
-// alone must be held (scan_wave_sync would also wait for the row loads in flight)
-__device__ __forceinline__ void scan_matrix_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// The exact key of (row, the query whose chunks lie at qrow in the tile), by one 16-lane group: scan_slab's arithmetic -- lane l16 on
-// the chunks l16, l16 + 16, ..., zero beyond the row's end, the fmaf chain, the tree.
-template <int NCH, int METRIC>
-__device__ __forceinline__ uint32_t scan_matrix_exact_key(const float *rp, int nchunks, const float *qrow, int l16) {
-    float4 z[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int c = i * 16 + l16;
-        z[i] = *reinterpret_cast<const float4 *>(rp + 4 * (c < nchunks ? c : 0));
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int c = i * 16 + l16;
-        if (c >= nchunks) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        acc = scan_chain<METRIC>(acc, z[i], *reinterpret_cast<const float4 *>(qrow + 4 * c));
-    }
-    return dist_to_key<METRIC>(reduce16(acc));
 }
 
 template <int NCH, int METRIC, bool MASKED>
@@ -323,8 +297,8 @@ hnsw_scan_matrix_kernel(const ScanMatrixArgs a, const uint32_t *const *masks) {
 
 namespace hnsw_host {
 
-int scan_matrix_launch(hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
-                       uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path) {
+int scan_matrix_prepass(hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int nch, hipStream_t st, const float **qterm_out,
+                        const uint32_t **path) {
     int rc = ensure_scan_state(idx, st);
     if (rc) return rc;
     const hnsw_dev::IndexView &iv = idx->iv;
@@ -332,12 +306,24 @@ int scan_matrix_launch(hnsw_index *idx, const float *Q, int64_t q_stride, int64_
     if ((rc = idx->scratch.scan_codes.ensure((size_t)scan_matrix_scratch(nq)))) return rc;
     float *const qterm = (float *)idx->scratch.scan_codes.p;
     uint32_t *const state = (uint32_t *)idx->scratch.scan_state.p;
-    const float eps = scan_matrix_eps(iv.d);
     with_metric(idx->info.metric, [&](auto METRIC) {
         hipLaunchKernelGGL(hnsw_dev::hnsw_scan_matrix_queries_kernel<METRIC>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, Q, q_stride, nq, iv.d,
-                           eps, qterm, state);
+                           scan_matrix_eps(iv.d), qterm, state);
     });
     if ((rc = launched("matrix scan query prepass"))) return rc;
+    *qterm_out = qterm;
+    *path = state;
+    return HNSW_OK;
+}
+
+int scan_matrix_launch(hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
+                       uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path) {
+    const float *qterm = nullptr;
+    const uint32_t *state = nullptr;
+    int rc = scan_matrix_prepass(idx, Q, q_stride, nq, nch, st, &qterm, &state);
+    if (rc) return rc;
+    const hnsw_dev::IndexView &iv = idx->iv;
+    const float eps = scan_matrix_eps(iv.d);
     const hnsw_dev::ScanMatrixArgs a{iv.X, iv.stride, iv.n, iv.d, iv.nchunks, Q, q_stride, nq, qterm, k, (int32_t)slabs, slab_rows, lists, state, eps};
     const dim3 grid((unsigned)scan_matrix_tiles(nq), (unsigned)scan_matrix_slab_groups(slabs, nch));
     with_metric(idx->info.metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {

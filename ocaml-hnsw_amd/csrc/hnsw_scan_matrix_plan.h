@@ -1,7 +1,8 @@
 // hnsw_scan_matrix_plan.h -- the host arithmetic of the exact scan of float rows through fp32 matrix instructions
 // (hnsw_scan_matrix.hip; option "scan_matrix"): when scan_search may take it, its LDS layout, waves, scratch and grid, and the
-// screening rule with its margins.  Plain arithmetic on plain numbers, so that a host program can check it
-// (tests/cpp/test_scan_matrix_plan.cpp); the rule's functions are the ones the kernel calls.
+// screening rule with its margins; at the end what the range scan's form of it adds (hnsw_range_matrix.hip).  Plain arithmetic on
+// plain numbers, so that a host program can check it (tests/cpp/test_scan_matrix_plan.cpp, tests/cpp/test_range_matrix_plan.cpp);
+// the rule's functions are the ones the kernels call.
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -70,5 +71,24 @@ HNSW_SCAN_MATRIX_FN float scan_matrix_bound(int metric, float thr, float query_t
     return __builtin_fmaf(__builtin_fabsf(t) + 1.0f, 0x1p-20f, t) + query_term;
 }
 HNSW_SCAN_MATRIX_FN bool scan_matrix_survives(float value, float bound) { return !(value > bound); }
+
+// ---- the range scan through the same screen (hnsw_range_matrix.hip) -------------------------------------------------------------
+// The tile, the operands and the pipeline are the k-scan's; what a wave keeps beside them is smaller: survivors are bare 32-bit row
+// numbers (no word is built before the exact evaluation, no list is merged, so no `sorted` scratch either).
+constexpr int RANGE_MATRIX_BUF = 64;        // survivor rows per query and wave: one more block's 32 fit up to 32
+// LDS per wave: 32 buffers of 64 row numbers (8 KB), 32 counters, 32 row terms
+constexpr int RANGE_MATRIX_WAVE_BYTES = SCAN_MATRIX_TILE * RANGE_MATRIX_BUF * 4 + SCAN_MATRIX_TILE * 4 + 32 * 4;
+// waves per workgroup, one slab each: the pipeline's stage decides, not the LDS -- a stage of 64 floats per row leaves room for two
+// waves per SIMD, one of 128 takes a SIMD's whole register file (scan_matrix_piece)
+constexpr int range_matrix_waves(int nch) { return scan_matrix_piece(nch) == 64 ? 8 : 4; }
+constexpr int range_matrix_lds_bytes(int nch) { return scan_matrix_tile_bytes(nch) + range_matrix_waves(nch) * RANGE_MATRIX_WAVE_BYTES; }
+inline int64_t range_matrix_slab_groups(int64_t slabs, int nch) { return (slabs + range_matrix_waves(nch) - 1) / range_matrix_waves(nch); }
+// The float the key `khi` -- the largest key in range (range_key_bounds) -- was made from: the squared-distance sum (L2) or the
+// distance 1 - sum (IP), what scan_matrix_bound takes for its threshold.  The bound is then fixed for the whole slab, and a pair is
+// dropped only when its exact key is proven above khi; the interval's lower end only excludes NaN keys, at the exact evaluation.
+HNSW_SCAN_MATRIX_FN float range_matrix_threshold(int metric, uint32_t khi) {
+    const uint32_t bits = metric == 0 ? khi : (khi & 0x80000000u) ? (khi & 0x7FFFFFFFu) : ~khi;       // (IP: key_to_dist)
+    return __builtin_bit_cast(float, bits);
+}
 
 } // namespace hnsw_host

@@ -8,8 +8,16 @@ matrices, host clock, median of --steps calls after a warm call).  Two parts, ru
   --part search  hnsw_range_search_batch (M 16, efC 200, ef 128) at radii where most queries are served at stage 0, beside
                  hnsw_search_batch of (ef, ef) on the same batch, with the share of queries per stage and the range recall against
                  hnsw_range_brute_force_batch: hits found / hits true, summed over the queries.
-Informational: nothing gates on it.  The table printed here is what profiles/range_search.txt holds.
-Usage: python tools/range_rate.py --part scan|search [--n 1000000] [--nq 10000] [--steps 5] [--out FILE (appended to)]"""
+  --part matrix  hnsw_range_brute_force_batch with option "scan_matrix" off and on, alternating within one handle, --steps (7)
+                 timings per leg after two warm rounds, reported as ranges: 1 M x 128 Gaussian float rows, L2, at the radius of the
+                 median 10th-neighbour distance (1 000 and 10 000 queries), at a wide radius with about 1 % of the table per query,
+                 and on the rows and queries + 100 (norms far above the distances).  The call takes host queries: they are
+                 page-locked and read in place, the result stays on the device (keep), the host clock spans the call, which ends in
+                 a synchronisation.  Every on/off pair is compared: lims, ids and distance bits must be equal.  --kernels: a few
+                 calls per option at 1 000 queries and nothing else, to be run under a kernel trace, in a run of its own.
+                 The table of profiles/range_matrix.txt.
+Informational: nothing gates on it.  The table printed by the first two parts is what profiles/range_search.txt holds.
+Usage: python tools/range_rate.py --part scan|search|matrix [--n 1000000] [--nq 10000] [--steps 5] [--kernels] [--out FILE (appended to)]"""
 import argparse
 import os
 import sys
@@ -49,12 +57,52 @@ def radius_for(X, Q, hits, sample=32):
     return float(np.median(out))
 
 
+def matrix_part(a, say):
+    """option "scan_matrix" off / on over the exact range scan (see the module's docstring)"""
+    d, steps = 128, max(5, a.steps)
+    say('hnsw_range_brute_force_batch, option "scan_matrix" off / on, one handle, alternating: n %d, d %d, L2, %d timings per leg' % (a.n, d, steps))
+    for leg, shift in (("gauss", 0.0),) if a.kernels else (("gauss", 0.0), ("shifted", 100.0)):
+        rng = np.random.default_rng(11)
+        X = rng.standard_normal((a.n, d), dtype=np.float32) + np.float32(shift)
+        Qall = rng.standard_normal((a.nq, d), dtype=np.float32) + np.float32(shift)
+        hg = H.Hgraph.flat(X)
+        cases = [(10, min(1000, a.nq))]
+        if not a.kernels and leg == "gauss":
+            cases += [(10, a.nq), (max(10, a.n // 100), min(1000, a.nq))]
+        for hits, nq in cases:
+            radius = radius_for(X, Qall, hits)
+            Q = H.host_empty((nq, d))          # page-locked: read in place
+            Q[:] = Qall[:nq]
+            t, got = {0: [], 1: []}, {}
+            for r in range((2 if a.kernels else steps) + 2):        # (two warm rounds)
+                for v in (0, 1):
+                    hg.set_option("scan_matrix", v)
+                    t0 = time.perf_counter()
+                    res = H.Ohnsw.brute_force_range(hg, radius, Q, keep=True)
+                    dt = (time.perf_counter() - t0) * 1e3
+                    assert hg.scan_path() == (H.SCAN_PATH_MATRIX if v else H.SCAN_PATH_FLOAT)
+                    if r >= 2:
+                        t[v].append(dt)
+                    if r == 0:
+                        got[v] = res.fetch()
+                    res.release()
+            for x, y in zip(got[0], got[1]):
+                assert np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x, y.view(np.uint32) if y.dtype == np.float32 else y)
+            disjoint = max(t[1]) < min(t[0]) or max(t[0]) < min(t[1])
+            say("%-7s nq %5d radius %8.3f (mean %9.1f hits per query, %9d in all): off %8.3f .. %8.3f ms, on %8.3f .. %8.3f ms; ranges %s; "
+                "off/on of the medians %.2f; on: %.3f ms per 1 000 queries"
+                % (leg, nq, radius, float(np.diff(got[1][0]).mean()), int(got[1][0][-1]), min(t[0]), max(t[0]), min(t[1]), max(t[1]),
+                   "disjoint" if disjoint else "overlap", np.median(t[0]) / np.median(t[1]), np.median(t[1]) * 1000.0 / nq))
+        hg.release()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("scan", "search"), required=True)
+    ap.add_argument("--part", choices=("scan", "search", "matrix"), required=True)
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--nq", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if H.device_count() < 1:
@@ -64,6 +112,13 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
+
+    if a.part == "matrix":
+        matrix_part(a, say)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
 
     d, M, efc, ef = 128, 16, 200, 128
     rng = np.random.default_rng(7)
