@@ -281,10 +281,15 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   byte rows, a quarter of the bytes.  Same ids, same distance bits: every sum is an integer below 2^24,
  *                   which the float arithmetic holds exactly.  A launch any of whose query values is not an integer in
  *                   0..255 runs the float kernels instead; that is decided on the device, so the device-pointer form still
- *                   never waits for the host.  hnsw_index_scan_path tells which ran.  Any other value is refused.  Not
- *                   saved.  Not built: the range, grouped and paged scans, per-query filters
- *                   (hnsw_search_batch_filtered_each), sq8 codes as scan rows, d > 256.
- *                   Measured: profiles/scan_bytes.txt;
+ *                   never waits for the host.  hnsw_index_scan_path tells which ran.  2 = everything 1 is, and under the
+ *                   same conditions the exact range scans (both passes, plain and masked: hnsw_range_brute_force_batch, the
+ *                   exact stage of hnsw_range_search_batch, their filtered forms, under marks, the shards') take 8-bit matrix
+ *                   kernels of their own over the byte rows: the matrix unit makes the key itself, and a pair is a hit when
+ *                   its integer is at most the largest integer whose key the radius admits.  Same lims, ids and distance
+ *                   bits; the fallback is the float range kernels, decided on the device the same way (with 1 the range scans
+ *                   stay the float kernels).  Any other value is refused.  Not saved.  Not built: the grouped and paged
+ *                   scans, per-query filters (hnsw_search_batch_filtered_each), sq8 codes as scan rows, d > 256.
+ *                   Measured: profiles/scan_bytes.txt, profiles/range_bytes.txt;
  *   "scan_matrix"   0 (default) = the exact scans are exactly what they are without the option.  1 = where d <= 512, the call
  *                   names no per-query filters and "scan_bytes" does not take the handle (the byte path has precedence and
  *                   its float fallback stays the float kernels), the same calls as for "scan_bytes" -- COSINE indices
@@ -297,8 +302,8 @@ int32_t hnsw_index_get_info(const hnsw_index *idx, hnsw_index_info *info);
  *                   the device.  hnsw_index_scan_path tells which ran (3).  The exact range scans (both passes, plain and
  *                   masked: hnsw_range_brute_force_batch, the exact stage of hnsw_range_search_batch, their filtered forms,
  *                   under marks, the shards') are screened the same way against the radius's largest key, which is fixed from
- *                   the first row on: same lims, ids and distance bits; a handle "scan_bytes" takes keeps the float range
- *                   kernels.  Any other value is refused.  Not saved.  Not built: the grouped and paged scans, per-query
+ *                   the first row on: same lims, ids and distance bits; a handle "scan_bytes" takes is not screened (its
+ *                   range scans are the float kernels under 1, the byte kernels under 2).  Any other value is refused.  Not saved.  Not built: the grouped and paged scans, per-query
  *                   filters, d > 512, half, sq8 or bit rows as scan operands, a bf16 or split-precision screen.  Measured:
  *                   profiles/scan_matrix.txt, profiles/range_matrix.txt;
  *   "byte_rows"     when every value of the vectors is an integer in 0..255 (SIFT descriptors stored as
@@ -724,7 +729,7 @@ int32_t hnsw_brute_force_batch_device(hnsw_index *idx, const float *d_queries, i
 /* What the handle's last exact-scan launch ran (options "scan_bytes", "scan_matrix"): *out = 0 none yet, 1 the float scan, 2 the
  * matrix scan over the byte rows, 3 the float matrix scan.  Where the queries decided it on the device, the call waits for the
  * device and reads the word.  The exact range scans (hnsw_range_brute_force_batch, the exact stage of hnsw_range_search_batch, their
- * filtered forms) report here as well: 3 under "scan_matrix", else 1 -- the range scan has no byte form. */
+ * filtered forms) report here as well: 2 under "scan_bytes" 2, 3 under "scan_matrix", else 1. */
 int32_t hnsw_index_scan_path(hnsw_index *idx, int32_t *out);
 
 /* Exact re-ranking of caller-given candidates (the refine step of option "refine" as an operator of its own): for query q the

@@ -555,7 +555,8 @@ class Hgraph:
         "filter_collect" 1 makes the filtered searches (knn_batch_filtered, knn_batch_filtered_each, the plain searches under
         marks) answer from every node the layer-0 walk evaluates, not from the final W only (k <= 128, exact rows; default 0).
         "scan_bytes" 1 sends the exact scans of byte-valued data (byte rows, d <= 256) through the 8-bit matrix kernels: same ids,
-        same distance bits; scan_path() tells which kernel ran (default 0).
+        same distance bits; scan_path() tells which kernel ran (default 0).  2 is 1 and the exact range scans (brute_force_range,
+        the exact stage of range_search, their filtered forms) through 8-bit matrix kernels of their own: same lims, ids, bits.
         "scan_matrix" 1 screens the exact scans of float rows (d <= 512) with fp32 matrix instructions and evaluates what the
         screen cannot drop with the float scan's own arithmetic: same ids, same distance bits (default 0)"""
         _check(load().hnsw_index_set_option(self.handle, name.encode(), int(value)))
@@ -564,8 +565,8 @@ class Hgraph:
         """hnsw_index_scan_path: what the handle's last exact-scan launch ran: 0 none yet, 1 the float scan, 2 the matrix scan over
         the byte rows (set_option("scan_bytes", 1), byte-valued data and queries, d <= 256), 3 the float matrix scan
         (SCAN_PATH_MATRIX: set_option("scan_matrix", 1), finite queries, d <= 512).  The exact range scans report here too
-        (brute_force_range, the exact stage of range_search, their filtered forms): 3 under "scan_matrix", else 1 -- the range scan
-        has no byte form"""
+        (brute_force_range, the exact stage of range_search, their filtered forms): 2 under set_option("scan_bytes", 2), 3 under
+        "scan_matrix", else 1"""
         v = _C.c_int32(0)
         _check(load().hnsw_index_scan_path(self.handle, _C.byref(v)))
         return v.value

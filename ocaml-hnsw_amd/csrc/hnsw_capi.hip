@@ -1252,8 +1252,8 @@ int32_t hnsw_index_set_option(hnsw_index *idx, const char *name, int64_t value) 
     if (!strcmp(name, "order_queries")) { idx->order_mode = value < 0 ? -1 : (value ? 1 : 0); return HNSW_OK; }
     if (!strcmp(name, "head_queries")) { idx->head_queries = std::max<int64_t>(-1, std::min<int64_t>(value, 0x7FFFFFFF)); return HNSW_OK; }
     if (!strcmp(name, "scan_slabs")) { idx->scan_slabs = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1024)); return HNSW_OK; }
-    if (!strcmp(name, "scan_bytes")) {       // 1: the exact scans take the matrix kernels over the byte rows where they may (hnsw_scan_bytes.hip)
-        if (value != 0 && value != 1) return fail(HNSW_ERR_BAD_ARG, "scan_bytes=%lld: 0 (off) or 1", (long long)value);
+    if (!strcmp(name, "scan_bytes")) {       // 1: the exact k-scans take the matrix kernels over the byte rows where they may (hnsw_scan_bytes.hip); 2: the range scans too (hnsw_range_bytes.hip)
+        if (value < 0 || value > 2) return fail(HNSW_ERR_BAD_ARG, "scan_bytes=%lld: 0 (off), 1 (the k-scans) or 2 (the k-scans and the range scans)", (long long)value);
         idx->scan_bytes = (int)value;
         return HNSW_OK;
     }

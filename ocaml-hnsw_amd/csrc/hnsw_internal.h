@@ -577,8 +577,8 @@ struct hnsw_index : hnsw_host::LossyParams {
     int vt_bits_override = 0;
     int lds_pad = -1;                    // option "lds_pad": extra LDS bytes per search wave (-1 = balanced_lds_pad's choice)
     int scan_slabs = 0;                  // option "scan_slabs": row slabs of the exact scans (0 = scan_slab_rows' choice)
-    // option "scan_bytes": 1 = scan_search takes the matrix kernels over the byte rows where it may (scan_bytes_eligible); 0 (default):
-    // never.  scan_path_known: what the last scan_search launched when the host knows it (SCAN_PATH_NONE / _FLOAT); -1: the
+    // option "scan_bytes": 1 = scan_search takes the matrix kernels over the byte rows where it may (scan_bytes_eligible); 2 = so do
+    // the exact range scans (range_bytes_eligible; hnsw_range_bytes.hip); 0 (default): never.  scan_path_known: what the last scan_search launched when the host knows it (SCAN_PATH_NONE / _FLOAT); -1: the
     // prepass decided on the device, hnsw_index_scan_path reads scratch.scan_state's first word
     int scan_bytes = 0, scan_path_known = 0;
     // option "scan_matrix": 1 = scan_search screens float rows with the fp32 matrix kernels where it may (scan_matrix_eligible;
@@ -933,6 +933,13 @@ int scan_search(::hnsw_index *idx, const KnnBatch &b, int32_t k, int32_t fill, h
 // *path = the device word the float kernels behind them compare with SCAN_PATH_FLOAT.  masks: null, or the table whose first mask applies.
 int scan_bytes_launch(::hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
                       uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path);
+// ... its prepass alone: the queries' codes and integer terms (in scratch.scan_codes, laid out by scan_bytes_scratch(nq, d)) and the path word
+int scan_bytes_prepass(::hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, hipStream_t st, const uint8_t **codes, const int32_t **terms,
+                       const uint32_t **path);
+// hnsw_range_bytes.hip: one pass (0 counts, 1 writes the words) of the exact range scan of a's queries over the byte rows (option
+// "scan_bytes" 2); pass 0 runs the prepass first, pass 1 reads what the pass 0 before it left.  mask: null, or the allow-mask.
+int range_bytes_launch(::hnsw_index *idx, int pass, int nch, const hnsw_dev::RangeScanArgs &a, const uint32_t *mask, hipStream_t st,
+                       const uint32_t **path);
 // hnsw_scan_matrix.hip: the same for the float matrix scan over the float32 rows (option "scan_matrix"); the path word says SCAN_PATH_MATRIX
 // where it ran.  Its query terms share scratch.scan_codes with the byte scan's codes: a handle takes one of the two paths.
 int scan_matrix_launch(::hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,

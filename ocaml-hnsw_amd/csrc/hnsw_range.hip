@@ -22,6 +22,9 @@
 //   hnsw_range_scan_matrix_kernel (hnsw_range_matrix.hip; option "scan_matrix")  the same two passes, plain and masked, screened by
 //                           fp32 matrix instructions: launched in front of the kernels above into the same cells; those then
 //                           return at once unless the path word says a query value was not finite (path / expect, as the k-scan's).
+//   hnsw_range_scan_bytes_kernel (hnsw_range_bytes.hip; option "scan_bytes" 2)  the same two passes, plain and masked, over the byte
+//                           rows through 8-bit matrix instructions, which make the key itself; launched in front of the float
+//                           kernels the same way, which then run only when a query value is no byte.
 //   range_count_kernel      per exact-stage query the sum of its slabs' counts (from the exclusive sum), its counters and stage.
 //   range_unpack_kernel     the sorted words of an exact-stage query as ids (+ id_base) and key_to_dist.
 //   range_select_kernel     one wave per walked query: |W| and the length of W's in-range prefix, 64 entries per pass (ballot).
@@ -270,23 +273,26 @@ struct ExactPlan : ScanCut {
     const int32_t *map = nullptr;
     const uint32_t *mask = nullptr;    // the call's allow-mask (device words), null: every row
     int64_t n_allowed = 0;             // ... and how many rows it allows: what the exact stage adds to out_ndist (no mask: n)
-    // option "scan_matrix": the scan's passes go through the matrix screen first (hnsw_range_matrix.hip), under scan_search's rule: a
-    // handle the byte scan would take keeps the float kernels (the range scan has no byte form)
-    bool matrix = false;
+    // option "scan_bytes" 2: the scan's passes go through the byte kernels first (hnsw_range_bytes.hip).  Option "scan_matrix": through
+    // the matrix screen (hnsw_range_matrix.hip), under scan_search's rule: a handle the byte k-scan takes (value 1 or 2) keeps the float
+    // kernels as its fallback, never the screen
+    bool bytes = false, matrix = false;
     // (a count and an offset per (query, slab) cell)
     void cut(hnsw_index *idx) {
         static_cast<ScanCut &>(*this) = scan_cut(idx, m, 1, 16, m);
-        const bool bytes = scan_bytes_eligible(idx->scan_bytes, idx->tables.X8.p != nullptr, idx->iv.d, false);
-        matrix = scan_matrix_eligible(idx->scan_matrix, bytes, idx->iv.d, false) && slabs > 0;
-        if (slabs > 0) idx->scan_path_known = matrix ? -1 : SCAN_PATH_FLOAT;       // (an empty table: no scan kernel is launched)
+        const bool has_rows = idx->tables.X8.p != nullptr;
+        bytes = range_bytes_eligible(idx->scan_bytes, has_rows, idx->iv.d, false) && slabs > 0;
+        matrix = scan_matrix_eligible(idx->scan_matrix, scan_bytes_eligible(idx->scan_bytes, has_rows, idx->iv.d, false), idx->iv.d, false) && slabs > 0;
+        if (slabs > 0) idx->scan_path_known = bytes || matrix ? -1 : SCAN_PATH_FLOAT;      // (an empty table: no scan kernel is launched)
     }
 };
 
-// one pass over nq queries: the matrix kernels where the plan says so, then the float kernels -- which, behind the matrix kernels,
-// run only when the prepass found a query value that is not finite (the path word; no host round trip)
+// one pass over nq queries: the byte or the matrix kernels where the plan says so, then the float kernels -- which, behind those,
+// run only when the prepass found a query value that is no byte, or not finite (the path word; no host round trip)
 int launch_range_scan(hnsw_index *idx, const ExactPlan &x, int pass, int64_t nq, const hnsw_dev::RangeScanArgs &a, hipStream_t st) {
     const uint32_t *path = nullptr;
     int rc;
+    if (x.bytes && (rc = range_bytes_launch(idx, pass, x.nch, a, x.mask, st, &path))) return rc;
     if (x.matrix && (rc = range_matrix_launch(idx, pass, x.nch, a, x.mask, st, &path))) return rc;
     const uint32_t expect = (uint32_t)SCAN_PATH_FLOAT;
     with_metric(idx->info.metric, [&](auto METRIC) { with_nch(x.nch, [&](auto NCH) {

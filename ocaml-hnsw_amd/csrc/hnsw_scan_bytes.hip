@@ -7,7 +7,8 @@
 // Two kernels in front of the unchanged hnsw_scan_merge_kernel.
 //   hnsw_scan_bytes_queries_kernel<METRIC>: one wave per query.  Writes the query's codes q' = q - 128 as int8 in the byte-row
 //     layout (64 * NCH bytes, ZERO beyond d), its integer term (below), and -- the last wave to finish -- the handle's path word:
-//     2 when every value of the launch's queries is an integer in 0..255 (-0.0 counts as 0), else 1.
+//     2 when every value of the launch's queries is an integer in 0..255 (-0.0 counts as 0), else 1.  The range scan's byte kernels
+//     (hnsw_range_bytes.hip; option value 2) take their codes, terms and path word from the same prepass (scan_bytes_prepass).
 //   hnsw_scan_bytes_kernel<NCH, METRIC, MASKED>: the grid of the float scan with tiles of 32 queries: one wave per (tile, slab),
 //     SCAN_BYTES_WAVES waves per workgroup.  Returns at once unless the path word is 2 (the float kernels, launched behind it
 //     with the same lists, return unless it is 1).
@@ -295,8 +296,9 @@ int ensure_scan_state(hnsw_index *idx, hipStream_t st) {
     return HNSW_OK;
 }
 
-int scan_bytes_launch(hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
-                      uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path) {
+// the prepass of nq queries: their codes and terms into scratch.scan_codes, the path word (the k-scan's pieces; the range scan's PASS 0)
+int scan_bytes_prepass(hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, hipStream_t st, const uint8_t **codes_out, const int32_t **terms_out,
+                       const uint32_t **path) {
     int rc = ensure_scan_state(idx, st);
     if (rc) return rc;
     const int d = idx->iv.d;
@@ -310,6 +312,17 @@ int scan_bytes_launch(hnsw_index *idx, const float *Q, int64_t q_stride, int64_t
                            scan_bytes_row_bytes(d), codes, terms, state);
     });
     if ((rc = launched("scan query prepass"))) return rc;
+    *codes_out = codes; *terms_out = terms; *path = state;
+    return HNSW_OK;
+}
+
+int scan_bytes_launch(hnsw_index *idx, const float *Q, int64_t q_stride, int64_t nq, int32_t k, int nch, int64_t slabs, int64_t slab_rows,
+                      uint64_t *lists, const uint32_t *const *masks, hipStream_t st, const uint32_t **path) {
+    const uint8_t *codes = nullptr;
+    const int32_t *terms = nullptr;
+    const uint32_t *state = nullptr;
+    int rc = scan_bytes_prepass(idx, Q, q_stride, nq, st, &codes, &terms, &state);
+    if (rc) return rc;
     const hnsw_dev::ScanBytesArgs a{(const uint8_t *)idx->tables.X8.p, idx->iv.n, codes, terms, nq, k, (int32_t)slabs, slab_rows, lists, state};
     const dim3 grid((unsigned)scan_bytes_tiles(nq), (unsigned)scan_bytes_slab_groups(slabs));
     with_metric(idx->info.metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {

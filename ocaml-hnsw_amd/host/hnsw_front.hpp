@@ -558,7 +558,7 @@ inline Grouped brute_force_grouped(const Hgraph &g, const Labels &l, int k, cons
 }
 
 // what the handle's last exact-scan launch ran (hnsw_index_scan_path): 0 none yet, 1 the float scan, 2 the matrix scan over the byte
-// rows (option "scan_bytes"), 3 the float matrix scan (option "scan_matrix")
+// rows (option "scan_bytes": 1 the k-scans, 2 the range scans too), 3 the float matrix scan (option "scan_matrix")
 constexpr int32_t SCAN_PATH_MATRIX = 3;
 inline int32_t scan_path(Hgraph &g) {
     int32_t path = 0;

@@ -262,7 +262,7 @@ let hnsw_index_mark_deleted =
 let hnsw_index_unmark_deleted =
   foreign ~from:lib ~release_runtime_lock:true "hnsw_index_unmark_deleted" (index @-> ptr int64_t @-> int64_t @-> returning int32_t)
 (* what the handle's last exact-scan launch ran (options "scan_bytes", "scan_matrix"): 0 none yet, 1 the float scan, 2 the matrix scan
-   over the byte rows, 3 the float matrix scan *)
+   over the byte rows ("scan_bytes" 1: the k-scans, 2: the range scans too), 3 the float matrix scan *)
 let scan_path_matrix = 3
 let hnsw_index_scan_path = foreign ~from:lib "hnsw_index_scan_path" (index @-> ptr int32_t @-> returning int32_t)
 (* keys the index owns (see the C header): one caller-chosen int64 per stored node, moved with the nodes *)

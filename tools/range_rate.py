@@ -16,8 +16,12 @@ matrices, host clock, median of --steps calls after a warm call).  Two parts, ru
                  a synchronisation.  Every on/off pair is compared: lims, ids and distance bits must be equal.  --kernels: a few
                  calls per option at 1 000 queries and nothing else, to be run under a kernel trace, in a run of its own.
                  The table of profiles/range_matrix.txt.
+  --part bytes   the same measurement for option "scan_bytes" 0 against 2 (the range scan's 8-bit matrix kernels): 1 M x 128
+                 byte-valued rows of the C2 shape, L2 and IP, 1 000 and 10 000 queries at the radius of the median 10th-neighbour
+                 distance and 1 000 queries at a wide radius (the median distance of the n / 100-th neighbour); hits per query and
+                 their share of the table are printed.  --kernels: as above (L2 only).  The table of profiles/range_bytes.txt.
 Informational: nothing gates on it.  The table printed by the first two parts is what profiles/range_search.txt holds.
-Usage: python tools/range_rate.py --part scan|search|matrix [--n 1000000] [--nq 10000] [--steps 5] [--kernels] [--out FILE (appended to)]"""
+Usage: python tools/range_rate.py --part scan|search|matrix|bytes [--n 1000000] [--nq 10000] [--steps 5] [--kernels] [--out FILE (appended to)]"""
 import argparse
 import os
 import sys
@@ -96,9 +100,53 @@ def matrix_part(a, say):
         hg.release()
 
 
+def bytes_part(a, say):
+    """option "scan_bytes" 0 / 2 over the exact range scan (see the module's docstring)"""
+    d, steps = 128, max(5, a.steps)
+    say('hnsw_range_brute_force_batch, option "scan_bytes" 0 / 2, one handle, alternating: n %d, d %d, byte-valued rows, %d timings per leg' % (a.n, d, steps))
+    rng = np.random.default_rng(7)          # (the C2 shape of the other parts: clustered SIFT-like integers in 0..218)
+    centres = rng.integers(20, 200, size=(256, d))
+    X = np.clip(np.rint(centres[rng.integers(0, 256, a.n)] + rng.normal(0, 25, size=(a.n, d))), 0, 218).astype(np.float32)
+    Qall = np.clip(np.rint(centres[rng.integers(0, 256, a.nq)] + rng.normal(0, 25, size=(a.nq, d))), 0, 218).astype(np.float32)
+    for metric, name in ((H.METRIC_L2, "L2"),) if a.kernels else ((H.METRIC_L2, "L2"), (H.METRIC_IP, "IP")):
+        hg = H.Hgraph.flat(X, metric=metric)
+        cases = [(10, min(1000, a.nq))]
+        if not a.kernels:
+            cases += [(10, a.nq), (max(10, a.n // 100), min(1000, a.nq))]
+        for hits, nq in cases:
+            if metric == H.METRIC_L2:
+                radius = radius_for(X, Qall, hits)
+            else:       # the distance is 1 - product: the median over a few queries of their hits-th smallest
+                radius = float(np.median([np.partition(1.0 - (X @ q).astype(np.float64), hits - 1)[hits - 1] for q in Qall[:32]]))
+            Q = H.host_empty((nq, d))          # page-locked: read in place
+            Q[:] = Qall[:nq]
+            t, got = {0: [], 2: []}, {}
+            for r in range((2 if a.kernels else steps) + 2):        # (two warm rounds)
+                for v in (0, 2):
+                    hg.set_option("scan_bytes", v)
+                    t0 = time.perf_counter()
+                    res = H.Ohnsw.brute_force_range(hg, radius, Q, keep=True)
+                    dt = (time.perf_counter() - t0) * 1e3
+                    assert hg.scan_path() == (2 if v else 1)
+                    if r >= 2:
+                        t[v].append(dt)
+                    if r == 0:
+                        got[v] = res.fetch()
+                    res.release()
+            for x, y in zip(got[0], got[2]):
+                assert np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x, y.view(np.uint32) if y.dtype == np.float32 else y)
+            mean = float(np.diff(got[2][0]).mean())
+            disjoint = max(t[2]) < min(t[0]) or max(t[0]) < min(t[2])
+            say("%s nq %5d radius %14.3f (mean %9.1f hits per query = %.4f %% of the table, %9d in all): off %8.3f .. %8.3f ms, on %8.3f .. %8.3f ms; "
+                "ranges %s; off/on of the medians %.2f; on: %.3f ms per 1 000 queries"
+                % (name, nq, radius, mean, 100.0 * mean / a.n, int(got[2][0][-1]), min(t[0]), max(t[0]), min(t[2]), max(t[2]),
+                   "disjoint" if disjoint else "overlap", np.median(t[0]) / np.median(t[2]), np.median(t[2]) * 1000.0 / nq))
+        hg.release()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("scan", "search", "matrix"), required=True)
+    ap.add_argument("--part", choices=("scan", "search", "matrix", "bytes"), required=True)
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--nq", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=5)
@@ -113,8 +161,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    if a.part == "matrix":
-        matrix_part(a, say)
+    if a.part in ("matrix", "bytes"):
+        (matrix_part if a.part == "matrix" else bytes_part)(a, say)
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
