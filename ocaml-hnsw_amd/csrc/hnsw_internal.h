@@ -80,6 +80,11 @@ template <int NCH, class F> auto with_nslot_knn(int nslot, F &&f) {
 }
 // f(Int<0>) for HNSW_METRIC_L2, f(Int<1>) for the inner product -- and for HNSW_METRIC_COSINE, the inner product over unit rows
 template <class F> auto with_metric(int metric, F &&f) { return metric == HNSW_METRIC_L2 ? f(Int<0>{}) : f(Int<1>{}); }
+// f(Int<PASS>, MASKED) for a matrix-unit range scan's pass (0 counts, 1 writes) and whether it has a mask (std::true_type / false_type)
+template <class F> auto with_range_pass(int pass, bool masked, F &&f) {
+    if (masked) return pass == 0 ? f(Int<0>{}, std::true_type{}) : f(Int<1>{}, std::true_type{});
+    return pass == 0 ? f(Int<0>{}, std::false_type{}) : f(Int<1>{}, std::false_type{});
+}
 
 // The knn kernel's variant objects (hnsw_search_variants.hip compiled once per line): X(metric, accept rule, row format -- see
 // variant_full).  build.py's VARIANTS is the same list (tests/test_abi_load.py compares them).

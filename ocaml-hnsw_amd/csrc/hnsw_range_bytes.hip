@@ -10,8 +10,9 @@
 //   hnsw_range_scan_bytes_kernel<NCH, METRIC, PASS, MASKED>: grid (tiles of 32 queries) x (groups of RANGE_BYTES_WAVES slabs), one
 //     wave per (tile, slab); the slabs are the float range scan's (ExactPlan), so a cell is a cell.  Returns at once unless the path
 //     word is 2 (the float range kernels, launched behind it into the same cells, return unless it is 1).
-//     Operands, pipeline, row terms: the byte k-scan's (hnsw_scan_bytes.hip has the lane maps and the algebra), restated here and not
-//       shared, so that hnsw_scan_bytes_kernel compiles exactly as it did -- 32-row blocks aligned to a mask word straight from
+//     Operands, pipeline, row terms: the byte k-scan's (hnsw_scan_bytes.hip has the lane maps and the algebra), restated here:
+//       through one shared walk the k-scan's NCH 2 instances ran 2 to 4 % slower (profiles/scan_walk_refactor.txt) -- 32-row blocks
+//       aligned to a mask word straight from
 //       tables.X8, lane l on 16 contiguous bytes of row l % 32 per step, x xor 0x80 as the A operand; the tile's codes in 8 NCH
 //       registers as B for the whole slab; v_mfma_i32_32x32x32_i8; the next candidate block's loads in flight during the multiply;
 //       row terms from the raw registers by v_dot4_u32_u8, one ds_bpermute across the halves, 128 bytes of LDS into the accumulator
@@ -47,13 +48,6 @@ struct RangeBytesArgs {
     const uint32_t *path;  // the handle's path word
     RangeScanArgs r;       // the pass's queries, cut, radius and cells: what the float range kernels get
 };
-
-// LDS words one lane wrote, read by the other lanes of its wave: a wave's LDS operations complete in issue order, so the compiler
-// alone must be held
-__device__ __forceinline__ void range_bytes_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 template <int NCH, int METRIC, int PASS, bool MASKED>
 __global__ void __launch_bounds__(64 * RANGE_BYTES_WAVES)
@@ -150,9 +144,9 @@ hnsw_range_scan_bytes_kernel(const RangeBytesArgs a, const uint32_t *mask_) {
 
         int rt = METRIC == 0 ? (int)s2 - 256 * (int)s1 : -128 * (int)s1;
         rt += __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, rt);      // the other half of the row
-        if (!((cw >> j) & 1u)) rt = RANGE_BYTES_NO_ROW;                 // no candidate: above every bound
+        if (!((cw >> j) & 1u)) rt = SCAN_BYTES_NO_ROW;                  // no candidate: above every bound
         if (h == 0) rterm[j] = rt;
-        range_bytes_lds_sync();
+        scan_lds_sync();
 
         v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -210,14 +204,9 @@ int range_bytes_launch(hnsw_index *idx, int pass, int nch, const hnsw_dev::Range
         return fail(HNSW_ERR_HIP, "byte range scan: pass %d without its prepass (d=%d)", pass, d);
     const hnsw_dev::RangeBytesArgs a{(const uint8_t *)idx->tables.X8.p, idx->iv.n, codes, terms, state, r};
     const dim3 grid((unsigned)scan_bytes_tiles(r.nq), (unsigned)range_bytes_slab_groups(r.n_slabs)), block(64 * RANGE_BYTES_WAVES);
-    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {
-        if constexpr (NCH <= 4) {
-            if (mask && pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_bytes_kernel<NCH, METRIC, 0, true>), grid, block, 0, st, a, mask);
-            else if (mask) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_bytes_kernel<NCH, METRIC, 1, true>), grid, block, 0, st, a, mask);
-            else if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_bytes_kernel<NCH, METRIC, 0, false>), grid, block, 0, st, a, mask);
-            else hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_bytes_kernel<NCH, METRIC, 1, false>), grid, block, 0, st, a, mask);
-        }
-    }); });
+    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) { with_range_pass(pass, mask != nullptr, [&](auto PASS, auto MASKED) {
+        if constexpr (NCH <= 4) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_bytes_kernel<NCH, METRIC, PASS, MASKED>), grid, block, 0, st, a, mask);
+    }); }); });
     if ((rc = launched("byte range scan kernel"))) return rc;
     *path = state;
     return HNSW_OK;

@@ -13,12 +13,10 @@
 //
 //   hnsw_range_scan_matrix_kernel<NCH, METRIC, PASS, MASKED>: grid (tiles of 32 queries) x (groups of slabs), one wave per (tile,
 //     slab), range_matrix_waves(NCH) waves per workgroup; the slabs are the float range scan's (ExactPlan), so a cell is a cell.
-//     Tile, A operand, pipeline, row norms: hnsw_scan_matrix_kernel's (its header comment has the lane maps) -- the tile in LDS as
-//       float32 with pitch 64 NCH + 4, zero beyond d and the tile's end; 32-row blocks aligned to a mask word straight from global
-//       memory, one float4 load feeding four v_mfma_f32_32x32x2_f32; the next piece's loads in flight during the multiply; norms
-//       from the operand registers and one ds_bpermute, through 128 bytes of LDS to the accumulator layout; +inf for a masked or
-//       out-of-slab row; a mask word without a set bit stepped over unloaded.  The loop is restated here and not shared: the
-//       k-scan's instances sit one register from the end of the file at NCH 4 / 8 and are left exactly as they compile today.
+//     Tile, A operand, pipeline, row norms, screen: the k-scan's, scan_matrix_load_tile and scan_matrix_walk
+//       (hnsw_scan_matrix_device.hip.h has the lane maps) -- the tile in LDS as float32 with pitch 64 NCH + 4; 32-row blocks aligned
+//       to a mask word straight from global memory; +inf for a masked or out-of-slab row; a mask word without a set bit stepped over
+//       unloaded.
 //     Survivors: bare 32-bit row numbers in the query's buffer of 64 (8 KB per wave).  A buffer that may not take another block's
 //       32 (and, at the slab's end, every buffer) is evaluated: one 16-lane group per pair, eight pairs a round.
 //     Hits: lane t carries query t's hit count for the cell (every update is wave-uniform: a ballot's population count).  PASS 0
@@ -49,14 +47,11 @@ template <int NCH, int METRIC, int PASS, bool MASKED>
 __global__ void __launch_bounds__(64 * range_matrix_waves(NCH))
 hnsw_range_scan_matrix_kernel(const RangeMatrixArgs a, const uint32_t *mask_) {
     constexpr int T = SCAN_MATRIX_TILE, W = range_matrix_waves(NCH), BUF = RANGE_MATRIX_BUF;
-    constexpr int KW = scan_matrix_width(NCH), PITCH = scan_matrix_pitch(NCH);
-    constexpr int PF = scan_matrix_piece(NCH), SP = PF / 8;     // floats of a row per stage; steps (float4 per lane) per stage
-    constexpr int LIMIT = BUF - 32;                             // a buffer up to here takes the survivors of one more block
-    static_assert(NCH == 1 || NCH == 2 || NCH == 4 || NCH == 8, "rows of 64 to 512 floats");
+    constexpr int PITCH = scan_matrix_pitch(NCH);
     static_assert(T == 32 && RANGE_MATRIX_WAVE_BYTES == T * BUF * 4 + T * 4 + 32 * 4, "the plan header's LDS per wave");
     static_assert(range_matrix_lds_bytes(NCH) == T * PITCH * 4 + W * RANGE_MATRIX_WAVE_BYTES && range_matrix_lds_bytes(NCH) <= SCAN_MATRIX_LDS_MAX,
                   "the plan header's LDS budget");
-    static_assert(W == (PF == 64 ? 8 : 4), "two waves per SIMD only with the short stage");
+    static_assert(W == (scan_matrix_piece(NCH) == 64 ? 8 : 4), "two waves per SIMD only with the short stage");
     __shared__ __attribute__((aligned(16))) float tile[T * PITCH];
     __shared__ uint32_t bufs_all[W][T][BUF];
     __shared__ int cnt_all[W][T];
@@ -64,18 +59,10 @@ hnsw_range_scan_matrix_kernel(const RangeMatrixArgs a, const uint32_t *mask_) {
     if (*a.path != (uint32_t)SCAN_PATH_MATRIX) return;          // (the whole workgroup: before the barrier)
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 31, h = lane >> 5;     // the lane's query column (and row of the A operand); which half of a step's k range
+    const int j = lane & 31;                    // the lane's query column
     const int64_t q0 = (int64_t)blockIdx.x * T;
     const int tq = (int)(a.r.nq - q0 < T ? a.r.nq - q0 : T);
-    // the tile, once per workgroup: zero beyond d and beyond the tile's last query
-    for (int c = threadIdx.x; c < T * (KW / 4); c += 64 * W) {
-        const int t = c / (KW / 4), e0 = 4 * (c % (KW / 4));
-        const float *qp = a.r.Q + (q0 + (t < tq ? t : 0)) * a.r.q_stride;
-        float4 v;
-        v.x = (t < tq && e0 + 0 < a.d) ? qp[e0 + 0] : 0.f; v.y = (t < tq && e0 + 1 < a.d) ? qp[e0 + 1] : 0.f;
-        v.z = (t < tq && e0 + 2 < a.d) ? qp[e0 + 2] : 0.f; v.w = (t < tq && e0 + 3 < a.d) ? qp[e0 + 3] : 0.f;
-        *reinterpret_cast<float4 *>(tile + t * PITCH + e0) = v;
-    }
+    scan_matrix_load_tile<NCH, W>(tile, a.r.Q, a.r.q_stride, q0, tq, a.d);
     __syncthreads();
     const int64_t slab = (int64_t)blockIdx.y * W + uniform(wave);
     if (slab >= a.r.n_slabs) return;            // (after the only workgroup barrier)
@@ -85,7 +72,6 @@ hnsw_range_scan_matrix_kernel(const RangeMatrixArgs a, const uint32_t *mask_) {
     int *const cnt = cnt_all[wave];
     float *const rterm = rterm_all[wave];
     const int nchunks = a.nchunks;
-    const int np = (4 * nchunks + PF - 1) / PF;                 // stages per block: the pieces that hold a real dimension
 
     // the key interval of the radius, once per wave; the lane's bound from its upper end, fixed for the whole slab
     uint32_t klo, khi;
@@ -108,27 +94,6 @@ hnsw_range_scan_matrix_kernel(const RangeMatrixArgs a, const uint32_t *mask_) {
     if (lane < T) cnt[lane] = 0;
     scan_wave_sync();
 
-    // the rows of the 32-row block at `base` that may be candidates: in the slab, and allowed (wave-uniform)
-    auto candidates = [&](int64_t base) -> uint32_t {
-        const int lo = r0 > base ? (int)(r0 - base) : 0;
-        const int64_t left = r1 - base;
-        uint32_t w = (left >= 32 ? ~0u : ((1u << (int)left) - 1u)) & (~0u << lo);
-        if constexpr (MASKED) w &= (uint32_t)uniform((int)mask[base >> 5]);
-        return w;
-    };
-    // piece p of row base + j, the lane's float4 per step; the row clamped into the slab (a clamped row is no candidate) and a chunk
-    // past the row's end clamped to its first (zeroed before use)
-    auto load = [&](float4 (&x)[SP], int64_t base, int p) {
-        int64_t row = base + j;
-        row = row < r0 ? r0 : row;
-        row = row < r1 ? row : r1 - 1;
-        const float *rp = a.X + (uint64_t)row * (uint64_t)a.stride;
-#pragma unroll
-        for (int s = 0; s < SP; ++s) {
-            const int c = 2 * (SP * p + s) + h;
-            x[s] = *reinterpret_cast<const float4 *>(rp + 4 * (c < nchunks ? c : 0));
-        }
-    };
     // The c (>= 1) row numbers of query t's buffer get their exact keys, eight pairs a round (one 16-lane group per pair, two pairs
     // per group so that two rows' loads are in flight); a key inside the interval is a hit: counted, and in PASS 1 written.
     auto evaluate = [&](int t, int c) {
@@ -140,7 +105,7 @@ hnsw_range_scan_matrix_kernel(const RangeMatrixArgs a, const uint32_t *mask_) {
             uint32_t row[2], key[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) { const int at = i + 4 * u + (lane >> 4); row[u] = bufs[t][at < c ? at : 0]; }
-            scan_matrix_lds_sync();
+            scan_lds_sync();
 #pragma unroll
             for (int u = 0; u < 2; ++u) key[u] = scan_matrix_exact_key<NCH, METRIC>(a.X + (uint64_t)row[u] * (uint64_t)a.stride, nchunks, qrow, lane & 15);
 #pragma unroll
@@ -158,81 +123,8 @@ hnsw_range_scan_matrix_kernel(const RangeMatrixArgs a, const uint32_t *mask_) {
         if (lane == 0) cnt[t] = 0;
     };
 
-    int64_t base = r0 & ~31ll;
-    uint32_t vw = 0;
-    while (base < r1 && (vw = candidates(base)) == 0u) base += 32;
-    float4 an[SP];
-    if (base < r1) load(an, base, 0);
-    while (base < r1) {
-        const int64_t cur = base;
-        const uint32_t cw = vw;
-        v16f acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float nx = 0.f;
-        for (int p = 0; p < np; ++p) {
-            float4 ax[SP];
-#pragma unroll
-            for (int s = 0; s < SP; ++s) ax[s] = an[s];
-            if (p + 1 < np) load(an, cur, p + 1);
-            else {
-                base += 32;
-                while (base < r1 && (vw = candidates(base)) == 0u) base += 32;
-                if (base < r1) load(an, base, 0);
-            }
-            if (p == np - 1) {                  // only the last piece reaches past the row's end
-#pragma unroll
-                for (int s = 0; s < SP; ++s) if (2 * (SP * p + s) + h >= nchunks) ax[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            const float *bp = tile + j * PITCH + PF * p + 4 * h;
-#pragma unroll
-            for (int s = 0; s < SP; ++s) {
-                const float4 b = *reinterpret_cast<const float4 *>(bp + 8 * s);
-                nx = __builtin_fmaf(ax[s].x, ax[s].x, nx); nx = __builtin_fmaf(ax[s].y, ax[s].y, nx);
-                nx = __builtin_fmaf(ax[s].z, ax[s].z, nx); nx = __builtin_fmaf(ax[s].w, ax[s].w, nx);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].x, b.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].y, b.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].z, b.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].w, b.w, acc, 0, 0, 0);
-            }
-        }
-
-        nx += __int_as_float(__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __float_as_int(nx)));   // the other half of the row
-        float rt = scan_matrix_row_term(METRIC, nx, a.eps);
-        if (!((cw >> j) & 1u)) rt = __builtin_inff();           // no candidate: above every bound
-        if (h == 0) rterm[j] = rt;
-        scan_matrix_lds_sync();
-
-        // accumulator v of the lane: row 8 (v / 4) + 4 h + v % 4 of the block, query j
-        float tv[16];
-        bool any = false;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 rr = *reinterpret_cast<const float4 *>(rterm + 8 * g + 4 * h);
-            tv[4 * g + 0] = scan_matrix_value(METRIC, rr.x, acc[4 * g + 0]);
-            tv[4 * g + 1] = scan_matrix_value(METRIC, rr.y, acc[4 * g + 1]);
-            tv[4 * g + 2] = scan_matrix_value(METRIC, rr.z, acc[4 * g + 2]);
-            tv[4 * g + 3] = scan_matrix_value(METRIC, rr.w, acc[4 * g + 3]);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) any = any || scan_matrix_survives(tv[4 * g + c], bound);
-        }
-        if (ballot(any)) {                      // rare on a selective radius
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int ri = 8 * (v >> 2) + 4 * h + (v & 3);
-                if (scan_matrix_survives(tv[v], bound) && ((cw >> ri) & 1u) && j < tq) bufs[j][atomicAdd(&cnt[j], 1)] = (uint32_t)(cur + ri);
-            }
-            scan_wave_sync();
-            const int c = cnt[j];               // (at most LIMIT + 32 = BUF: a row of the block survives once per query)
-            uint32_t need = (uint32_t)ballot(h == 0 && c > LIMIT);
-            if (need) {
-                while (need) {
-                    const int t = __builtin_ctz(need);
-                    need &= need - 1u;
-                    evaluate(t, __builtin_amdgcn_readlane(c, t));
-                }
-                scan_wave_sync();
-            }
-        }
-    }
+    // a full buffer is evaluated; the bound never moves
+    scan_matrix_walk<NCH, METRIC, MASKED>(a.X, a.stride, nchunks, a.eps, r0, r1, mask, tile, rterm, bufs, cnt, tq, bound, evaluate, [] {});
     // what is left in the buffers, then the cell's count
     scan_wave_sync();
     for (int t = 0; t < tq; ++t) {
@@ -256,15 +148,10 @@ int range_matrix_launch(hnsw_index *idx, int pass, int nch, const hnsw_dev::Rang
     if (!qterm || !state || nch != scan_matrix_nch(iv.d)) return fail(HNSW_ERR_HIP, "matrix range scan: pass %d without its prepass (d=%d)", pass, iv.d);
     const hnsw_dev::RangeMatrixArgs a{iv.X, iv.stride, iv.n, iv.d, iv.nchunks, qterm, state, scan_matrix_eps(iv.d), r};
     const dim3 grid((unsigned)scan_matrix_tiles(r.nq), (unsigned)range_matrix_slab_groups(r.n_slabs, nch));
-    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) {
-        if constexpr (NCH <= 8) {
-            const dim3 block(64 * range_matrix_waves(NCH));
-            if (mask && pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_matrix_kernel<NCH, METRIC, 0, true>), grid, block, 0, st, a, mask);
-            else if (mask) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_matrix_kernel<NCH, METRIC, 1, true>), grid, block, 0, st, a, mask);
-            else if (pass == 0) hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_matrix_kernel<NCH, METRIC, 0, false>), grid, block, 0, st, a, mask);
-            else hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_matrix_kernel<NCH, METRIC, 1, false>), grid, block, 0, st, a, mask);
-        }
-    }); });
+    with_metric(idx->info.metric, [&](auto METRIC) { with_nch(nch, [&](auto NCH) { with_range_pass(pass, mask != nullptr, [&](auto PASS, auto MASKED) {
+        if constexpr (NCH <= 8)
+            hipLaunchKernelGGL((hnsw_dev::hnsw_range_scan_matrix_kernel<NCH, METRIC, PASS, MASKED>), grid, dim3(64 * range_matrix_waves(NCH)), 0, st, a, mask);
+    }); }); });
     if ((rc = launched("matrix range scan kernel"))) return rc;
     *path = state;
     return HNSW_OK;

@@ -85,16 +85,7 @@ hnsw_scan_bytes_queries_kernel(const float *Q, int64_t q_stride, int64_t nq, int
         if (lane == 0) terms[q] = METRIC == 0 ? s2 - 256 * s1 : -128 * s1;
     }
     const bool bad = ballot(!ok) != 0ull;
-    if (lane == 0) {
-        if (bad) atomicOr(&state[1], 1u);
-        __threadfence();
-        if (atomicAdd(&state[2], 1u) == gridDim.x * 4u - 1u) {      // the launch's last wave
-            __threadfence();
-            const uint32_t any_bad = atomicExch(&state[1], 0u);
-            atomicExch(&state[2], 0u);
-            state[0] = any_bad ? (uint32_t)hnsw_host::SCAN_PATH_FLOAT : (uint32_t)hnsw_host::SCAN_PATH_BYTES;
-        }
-    }
+    if (lane == 0) scan_prepass_publish(state, bad, (uint32_t)hnsw_host::SCAN_PATH_BYTES);
 }
 
 // the bound a lane compares its accumulators' rank values (less the query's term cq) against: the rank value of the query's k-th word
@@ -104,13 +95,6 @@ template <int METRIC> __device__ __forceinline__ int scan_bytes_bound(uint64_t t
     // (exact both ways: the keys of the list were made from integers below 2^24)
     const int m = METRIC == 0 ? (int)__uint_as_float(key) : -(int)(1.0f - key_to_dist<1>(key));
     return m - cq;
-}
-
-// LDS words one lane wrote, read by the other lanes of its wave: a wave's LDS operations complete in issue order, so the compiler
-// alone must be held (scan_wave_sync would also wait for the row loads in flight)
-__device__ __forceinline__ void scan_bytes_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
 }
 
 template <int NCH, int METRIC, bool MASKED>
@@ -210,9 +194,9 @@ __device__ __forceinline__ void scan_bytes_slab(const ScanBytesArgs &a, const ui
 
         int rt = METRIC == 0 ? (int)s2 - 256 * (int)s1 : -128 * (int)s1;
         rt += __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, rt);      // the other half of the row
-        if (!((cw >> j) & 1u)) rt = 0x3FFFFFFF;                         // no candidate: above every bound a full list sets
+        if (!((cw >> j) & 1u)) rt = hnsw_host::SCAN_BYTES_NO_ROW;       // no candidate: above every bound a full list sets
         if (h == 0) rterm[j] = rt;
-        scan_bytes_lds_sync();
+        scan_lds_sync();
 
         v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll

@@ -75,7 +75,10 @@ HNSW_SCAN_BYTES_FN bool range_bytes_bound(int metric, uint32_t klo, uint32_t khi
 }
 // A lane compares v = (row term) - (1 or 2) acc against (bound - query term).  Real row and query terms lie within +-2^25 and
 // |acc| <= 2^22, so |v| < 2^27 and |bound - query term| < 2^26: the row term of a row that is no candidate puts v above every lane
-// bound, the lane bound of a query without hits lies below every v, and no subtraction overflows.
-constexpr int32_t RANGE_BYTES_NO_ROW = 0x3FFFFFFF, RANGE_BYTES_NO_HIT = -0x40000000;
+// bound, the lane bound of a query without hits lies below every v, and no subtraction overflows.  The k-scan makes the same values
+// and its row sentinel is the same: above every bound that a full list sets (a list still short of k words takes every candidate row
+// and tests the candidate word itself).
+constexpr int32_t SCAN_BYTES_NO_ROW = 0x3FFFFFFF, RANGE_BYTES_NO_HIT = -0x40000000;
+constexpr int32_t RANGE_BYTES_NO_ROW = SCAN_BYTES_NO_ROW;      // (the name the range scan's host test knows)
 
 } // namespace hnsw_host

@@ -4,6 +4,7 @@
 // the reduce16 tree and dist_to_key of every other kernel, so the keys are the bits of hnsw_distance_batch.
 #pragma once
 #include "hnsw_device.hip.h"
+#include "hnsw_scan_bytes_plan.h"      // (the path words)
 
 namespace hnsw_dev {
 
@@ -183,6 +184,26 @@ struct ScanArgs {
 __device__ __forceinline__ void scan_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
+}
+// LDS words one lane wrote, read by the other lanes of its wave: a wave's LDS operations complete in issue order, so the compiler
+// alone must be held (scan_wave_sync would also wait for the row loads in flight)
+__device__ __forceinline__ void scan_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+// The tail of a query prepass (hnsw_scan_bytes.hip, hnsw_scan_matrix.hip: four waves per workgroup), by lane 0 of every wave.
+// state: [0] the handle's path word, [1] "a query of the launch in flight cannot take the matrix path", [2] its finished waves.  The
+// launch's last wave publishes the path word -- `fine` when no wave saw such a query, else the float kernels' -- and leaves [1] and
+// [2] at 0.
+__device__ __forceinline__ void scan_prepass_publish(uint32_t *state, bool bad, uint32_t fine) {
+    if (bad) atomicOr(&state[1], 1u);
+    __threadfence();
+    if (atomicAdd(&state[2], 1u) == gridDim.x * 4u - 1u) {      // the launch's last wave
+        __threadfence();
+        const uint32_t any_bad = atomicExch(&state[1], 0u);
+        atomicExch(&state[2], 0u);
+        state[0] = any_bad ? (uint32_t)hnsw_host::SCAN_PATH_FLOAT : fine;
+    }
 }
 __device__ __forceinline__ uint64_t scan_uniform64(uint64_t v) {
     return ((uint64_t)(uint32_t)uniform((int)(v >> 32)) << 32) | (uint32_t)uniform((int)(uint32_t)v);

@@ -14,20 +14,9 @@
 //     kernel (hnsw_range_matrix.hip) takes its query terms and its path word from the same prepass (scan_matrix_prepass).
 //   hnsw_scan_matrix_kernel<NCH, METRIC, MASKED>: grid (tiles of 32 queries) x (groups of slabs), one wave per (tile, slab),
 //     scan_matrix_waves(NCH) waves per workgroup.  Rows are taken as 64 * NCH floats wide (NCH = pick_nch, at most 8: d <= 512).
-//     B operand: the tile's 32 queries in LDS as float32, zero beyond d and beyond the tile's last query, loaded once by the
-//       workgroup and shared by its waves; the row pitch is padded by 4 floats so that the lanes of one ds_read_b128 pass spread
-//       over the banks.
-//     A operand: a block of 32 rows (aligned to 32, so that it is one mask word) straight from global memory, float4 per lane:
-//       lane (j = l % 32, h = l / 32) holds floats [8 s + 4 h, + 4) of row base + j at step s and reads the same floats of query
-//       j from the tile; component c of the pair feeds one v_mfma_f32_32x32x2_f32 (k = 8 s + c and 8 s + 4 + c: which k a
-//       register stands for does not matter, both operands use one map and the sum is over all k).  One load, four instructions.
-//     Pipeline: a stage is a block's piece of scan_matrix_piece(NCH) floats per row (32 or 64 VGPRs); the next stage's loads --
-//       the block's next piece or the next block's first -- are in flight while this one is multiplied.  16 accumulators.
-//     Row norms: fma over the lane's floats of the operand registers and one cross-half exchange; they reach the accumulator
-//       layout (lane l: query l % 32, rows 8 a + 4 (l / 32) + b of the block) through 128 bytes of LDS.  No table of norms exists:
-//       insert, remove, upsert and compact have nothing to maintain.
-//     Common path: one multiply-add (L2) or subtract (IP) and one compare per accumulator against the lane's bound.  A masked or
-//       out-of-slab row's term is +inf: above every bound.
+//     Tile, operands, pipeline, row norms, screen: scan_matrix_load_tile and scan_matrix_walk (hnsw_scan_matrix_device.hip.h has
+//       the lane maps), which the range scan's matrix kernel walks too: the tile's 32 queries in LDS, 32-row blocks straight from
+//       global memory, one multiply-add (L2) or subtract (IP) and one compare per accumulator against the lane's bound.
 //     Survivors go, as bare row numbers, into the query's 64-word LDS buffer.  A buffer that may not take another block (and, at
 //       the slab's end, every buffer) gets its exact keys: one 16-lane group per pair, eight pairs a round, the row read again
 //       (from L2) and the query's chunks from the tile.  A word not below the query's k-th word is discarded, the others are
@@ -39,8 +28,6 @@
 namespace hnsw_dev {
 
 using namespace hnsw_host;      // the plan header's constants and the rule
-
-// (v16f, scan_matrix_lds_sync, scan_matrix_exact_key: hnsw_scan_matrix_device.hip.h -- the range scan's matrix kernel shares them)
 
 struct ScanMatrixArgs {
     const float *X;        // [n][stride] zero-padded rows
@@ -76,16 +63,7 @@ hnsw_scan_matrix_queries_kernel(const float *Q, int64_t q_stride, int64_t nq, in
         if (lane == 0) qterm[q] = scan_matrix_query_term(METRIC, s, eps);
     }
     const bool bad = ballot(!ok) != 0ull;
-    if (lane == 0) {
-        if (bad) atomicOr(&state[1], 1u);
-        __threadfence();
-        if (atomicAdd(&state[2], 1u) == gridDim.x * 4u - 1u) {      // the launch's last wave
-            __threadfence();
-            const uint32_t any_bad = atomicExch(&state[1], 0u);
-            atomicExch(&state[2], 0u);
-            state[0] = any_bad ? (uint32_t)SCAN_PATH_FLOAT : (uint32_t)SCAN_PATH_MATRIX;
-        }
-    }
+    if (lane == 0) scan_prepass_publish(state, bad, (uint32_t)SCAN_PATH_MATRIX);
 }
 
 // the bound a lane compares its accumulators' screen values against: from the query's k-th word so far and the query's term
@@ -99,10 +77,7 @@ template <int NCH, int METRIC, bool MASKED>
 __global__ void __launch_bounds__(64 * scan_matrix_waves(NCH))
 hnsw_scan_matrix_kernel(const ScanMatrixArgs a, const uint32_t *const *masks) {
     constexpr int T = SCAN_MATRIX_TILE, W = scan_matrix_waves(NCH);
-    constexpr int KW = scan_matrix_width(NCH), PITCH = scan_matrix_pitch(NCH);
-    constexpr int PF = scan_matrix_piece(NCH), SP = PF / 8;     // floats of a row per stage; steps (float4 per lane) per stage
-    constexpr int LIMIT = SCAN_BUF - 32;                        // a buffer up to here takes the survivors of one more block
-    static_assert(NCH == 1 || NCH == 2 || NCH == 4 || NCH == 8, "rows of 64 to 512 floats");
+    constexpr int PITCH = scan_matrix_pitch(NCH);
     static_assert(SCAN_BUF == 64 && SCAN_MATRIX_WAVE_BYTES == T * SCAN_BUF * 8 + SCAN_BUF * 8 + T * 4 + 32 * 4, "the plan header's LDS");
     __shared__ __attribute__((aligned(16))) float tile[T * PITCH];
     __shared__ uint64_t bufs_all[W][T][SCAN_BUF];
@@ -112,18 +87,10 @@ hnsw_scan_matrix_kernel(const ScanMatrixArgs a, const uint32_t *const *masks) {
     if (*a.path != (uint32_t)SCAN_PATH_MATRIX) return;          // (the whole workgroup: before the barrier)
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 31, h = lane >> 5;     // the lane's query column (and row of the A operand); which half of a step's k range
+    const int j = lane & 31;                    // the lane's query column
     const int64_t q0 = (int64_t)blockIdx.x * T;
     const int tq = (int)(a.nq - q0 < T ? a.nq - q0 : T);
-    // the tile, once per workgroup: zero beyond d and beyond the tile's last query
-    for (int c = threadIdx.x; c < T * (KW / 4); c += 64 * W) {
-        const int t = c / (KW / 4), e0 = 4 * (c % (KW / 4));
-        const float *qp = a.Q + (q0 + (t < tq ? t : 0)) * a.q_stride;
-        float4 v;
-        v.x = (t < tq && e0 + 0 < a.d) ? qp[e0 + 0] : 0.f; v.y = (t < tq && e0 + 1 < a.d) ? qp[e0 + 1] : 0.f;
-        v.z = (t < tq && e0 + 2 < a.d) ? qp[e0 + 2] : 0.f; v.w = (t < tq && e0 + 3 < a.d) ? qp[e0 + 3] : 0.f;
-        *reinterpret_cast<float4 *>(tile + t * PITCH + e0) = v;
-    }
+    scan_matrix_load_tile<NCH, W>(tile, a.Q, a.q_stride, q0, tq, a.d);
     __syncthreads();
     const int64_t slab = (int64_t)blockIdx.y * W + uniform(wave);
     if (slab >= a.n_slabs) return;              // (after the only workgroup barrier)
@@ -134,7 +101,6 @@ hnsw_scan_matrix_kernel(const ScanMatrixArgs a, const uint32_t *const *masks) {
     int *const cnt = cnt_all[wave];
     float *const rterm = rterm_all[wave];
     const int nchunks = a.nchunks;
-    const int np = (4 * nchunks + PF - 1) / PF;                 // stages per block: the pieces that hold a real dimension
 
     const float cq = j < tq ? a.qterm[q0 + j] : 0.f;
     uint64_t *const lists0 = a.lists + ((q0 * a.n_slabs + slab) * 2) * (int64_t)a.k;
@@ -155,28 +121,6 @@ hnsw_scan_matrix_kernel(const ScanMatrixArgs a, const uint32_t *const *masks) {
         par ^= 1u << t;
         if (lane == 0) cnt[t] = 0;
     };
-    // the rows of the 32-row block at `base` that may be candidates: in the slab, and allowed (wave-uniform)
-    auto candidates = [&](int64_t base) -> uint32_t {
-        const int lo = r0 > base ? (int)(r0 - base) : 0;
-        const int64_t left = r1 - base;
-        uint32_t w = (left >= 32 ? ~0u : ((1u << (int)left) - 1u)) & (~0u << lo);
-        if constexpr (MASKED) w &= (uint32_t)uniform((int)mask[base >> 5]);
-        return w;
-    };
-    // piece p of row base + j, the lane's float4 per step; the row clamped into the slab (a clamped row is no candidate) and a chunk
-    // past the row's end clamped to its first (zeroed before use)
-    auto load = [&](float4 (&x)[SP], int64_t base, int p) {
-        int64_t row = base + j;
-        row = row < r0 ? r0 : row;
-        row = row < r1 ? row : r1 - 1;
-        const float *rp = a.X + (uint64_t)row * (uint64_t)a.stride;
-#pragma unroll
-        for (int s = 0; s < SP; ++s) {
-            const int c = 2 * (SP * p + s) + h;
-            x[s] = *reinterpret_cast<const float4 *>(rp + 4 * (c < nchunks ? c : 0));
-        }
-    };
-
     // The c bare row numbers of query t's buffer get their exact keys, eight pairs a round (one 16-lane group per pair, two pairs per
     // group so that two rows' loads are in flight); a word not below the query's k-th word is discarded, the others are packed in
     // place, never ahead of what the round read.  Returns how many words are left.  (Deferred to the buffer's merge: the k-th word
@@ -189,7 +133,7 @@ hnsw_scan_matrix_kernel(const ScanMatrixArgs a, const uint32_t *const *masks) {
             uint32_t row[2], key[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) { const int at = i + 4 * u + (lane >> 4); row[u] = (uint32_t)bufs[t][at < c ? at : 0]; }
-            scan_matrix_lds_sync();
+            scan_lds_sync();
 #pragma unroll
             for (int u = 0; u < 2; ++u) key[u] = scan_matrix_exact_key<NCH, METRIC>(a.X + (uint64_t)row[u] * (uint64_t)a.stride, nchunks, qrow, lane & 15);
 #pragma unroll
@@ -204,85 +148,15 @@ hnsw_scan_matrix_kernel(const ScanMatrixArgs a, const uint32_t *const *masks) {
         return w;
     };
 
-    int64_t base = r0 & ~31ll;
-    uint32_t vw = 0;
-    while (base < r1 && (vw = candidates(base)) == 0u) base += 32;
-    float4 an[SP];
-    if (base < r1) load(an, base, 0);
-    while (base < r1) {
-        const int64_t cur = base;
-        const uint32_t cw = vw;
-        v16f acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float nx = 0.f;
-        for (int p = 0; p < np; ++p) {
-            float4 ax[SP];
-#pragma unroll
-            for (int s = 0; s < SP; ++s) ax[s] = an[s];
-            if (p + 1 < np) load(an, cur, p + 1);
-            else {
-                base += 32;
-                while (base < r1 && (vw = candidates(base)) == 0u) base += 32;
-                if (base < r1) load(an, base, 0);
+    // a full buffer is evaluated and merged; after a block's merges the lanes refresh their bounds
+    scan_matrix_walk<NCH, METRIC, MASKED>(a.X, a.stride, nchunks, a.eps, r0, r1, mask, tile, rterm, bufs, cnt, tq, bound,
+        [&](int t, int c) { flush(t, evaluate(t, c)); },
+        [&] {
+            if (j < tq) {
+                thr = (lists0 + j * list_step + (((par >> j) & 1u) ? a.k : 0))[a.k - 1];
+                bound = scan_matrix_lane_bound<METRIC>(thr, cq);
             }
-            if (p == np - 1) {                  // only the last piece reaches past the row's end
-#pragma unroll
-                for (int s = 0; s < SP; ++s) if (2 * (SP * p + s) + h >= nchunks) ax[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            const float *bp = tile + j * PITCH + PF * p + 4 * h;
-#pragma unroll
-            for (int s = 0; s < SP; ++s) {
-                const float4 b = *reinterpret_cast<const float4 *>(bp + 8 * s);
-                nx = __builtin_fmaf(ax[s].x, ax[s].x, nx); nx = __builtin_fmaf(ax[s].y, ax[s].y, nx);
-                nx = __builtin_fmaf(ax[s].z, ax[s].z, nx); nx = __builtin_fmaf(ax[s].w, ax[s].w, nx);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].x, b.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].y, b.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].z, b.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax[s].w, b.w, acc, 0, 0, 0);
-            }
-        }
-
-        nx += __int_as_float(__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __float_as_int(nx)));   // the other half of the row
-        float rt = scan_matrix_row_term(METRIC, nx, a.eps);
-        if (!((cw >> j) & 1u)) rt = __builtin_inff();           // no candidate: above every bound
-        if (h == 0) rterm[j] = rt;
-        scan_matrix_lds_sync();
-
-        // accumulator v of the lane: row 8 (v / 4) + 4 h + v % 4 of the block, query j
-        float tv[16];
-        bool any = false;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 rr = *reinterpret_cast<const float4 *>(rterm + 8 * g + 4 * h);
-            tv[4 * g + 0] = scan_matrix_value(METRIC, rr.x, acc[4 * g + 0]);
-            tv[4 * g + 1] = scan_matrix_value(METRIC, rr.y, acc[4 * g + 1]);
-            tv[4 * g + 2] = scan_matrix_value(METRIC, rr.z, acc[4 * g + 2]);
-            tv[4 * g + 3] = scan_matrix_value(METRIC, rr.w, acc[4 * g + 3]);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) any = any || scan_matrix_survives(tv[4 * g + c], bound);
-        }
-        if (ballot(any)) {                      // rare once the lists are full
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int ri = 8 * (v >> 2) + 4 * h + (v & 3);
-                if (scan_matrix_survives(tv[v], bound) && ((cw >> ri) & 1u) && j < tq) bufs[j][atomicAdd(&cnt[j], 1)] = (uint32_t)(cur + ri);
-            }
-            scan_wave_sync();
-            const int c = cnt[j];               // (at most LIMIT + 32 = SCAN_BUF: a row of the block survives once per query)
-            uint32_t need = (uint32_t)ballot(h == 0 && c > LIMIT);
-            if (need) {
-                while (need) {
-                    const int t = __builtin_ctz(need);
-                    need &= need - 1u;
-                    flush(t, evaluate(t, __builtin_amdgcn_readlane(c, t)));
-                }
-                scan_wave_sync();
-                if (j < tq) {
-                    thr = (lists0 + j * list_step + (((par >> j) & 1u) ? a.k : 0))[a.k - 1];
-                    bound = scan_matrix_lane_bound<METRIC>(thr, cq);
-                }
-            }
-        }
-    }
+        });
     // what is left in the buffers; the result belongs in the first half
     scan_wave_sync();
     for (int t = 0; t < tq; ++t) {

@@ -68,10 +68,14 @@ def test_byte_range_scan_returns_the_float_range_scans_bits(H, d, metric, slabs)
     hg.release()
 
 
-@pytest.mark.parametrize("metric", [0, 1])
-def test_masked_byte_range_scan(H, metric):
+@pytest.mark.parametrize("metric, slabs", [pytest.param(0, None, id="0"), pytest.param(1, None, id="1"),    # the plan's own slabs
+                                           # three slabs: the edges at rows 173 and 346 fall inside mask words 5 and 10
+                                           pytest.param(0, 3, id="0-slabs3"), pytest.param(1, 3, id="1-slabs3")])
+def test_masked_byte_range_scan(H, metric, slabs):
     X, Q = _case(100, seed=1)[:2]
     hg = H.Hgraph.flat(X, metric=metric)
+    if slabs:
+        hg.set_option("scan_slabs", slabs)
     mask = np.isin(np.arange(N), ALLOWED)
     for how in ("filter", "marks"):                         # the call's allow-mask, then the same rows through the handle's live mask
         if how == "marks":

@@ -82,10 +82,14 @@ def test_matrix_range_scan_returns_the_float_range_scans_bits(H, d, metric, kind
     hg.release()
 
 
-@pytest.mark.parametrize("metric", [0, 1])
-def test_masked_matrix_range_scan(H, metric):
+@pytest.mark.parametrize("metric, slabs", [pytest.param(0, None, id="0"), pytest.param(1, None, id="1"),    # the plan's own slabs
+                                           # three slabs: the edges at rows 173 and 346 fall inside mask words 5 and 10
+                                           pytest.param(0, 3, id="0-slabs3"), pytest.param(1, 3, id="1-slabs3")])
+def test_masked_matrix_range_scan(H, metric, slabs):
     X, Q = _data("gauss", 100, seed=1)
     hg = H.Hgraph.flat(X, metric=metric)
+    if slabs:
+        hg.set_option("scan_slabs", slabs)
     mask = np.isin(np.arange(N), ALLOWED)
     lims, ids, _, _ = _on_off(H, hg, (MATRIX, FLOAT), "masked", lambda: H.Ohnsw.brute_force_range(hg, 1e30, Q, filter=mask))
     assert all(sorted(ids[lims[q]:lims[q + 1]]) == ALLOWED for q in range(NQ))
